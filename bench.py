@@ -38,10 +38,16 @@ max / sum reductions of the result (plus, with --bcast-weights, one RCCL broadca
 per GPU, RCCL process group; --single-process keeps everything in one process (one host thread and one context per GPU,
 no process group) for boxes where spawning is not possible.
 
+A plain run does only what the headline needs: set-up, --warmup steps, the untimed ramp, the --steps timed steps, the
+result line (and, with --dump-outputs DIR, what the last timed step computed as DIR/<name>.npy).  --full adds every other
+leg -- the serialised kernel table and the in-region brackets, the latency distribution, config #4's second timed region,
+the self-check against the CPU oracle and the CPU baselines -- each still switchable off by its own --no-* / --latency-steps.
+
 One JSON line on rank 0:
-  * `value` = whole-job frames/s with inputs resident in HBM;
+  * `value` = whole-job frames/s with inputs resident in HBM; `ms_per_step` = milliseconds of one timed step;
   * `roofline` = the WHOLE STEP against its binding bound (fp32 MFMA for encode+decode: 5.43 MFLOP of fp32 MFMA work
     per stream-frame = 34.5 ns at 157.3 TFLOP/s, vs 13.4 ns of HBM time for the bytes the kernels move);
+  with --full also:
   * `kernels` = per-kernel durations measured live with HIP events on the library's own streams in a SERIALISED pass
     (lyra_hip_set_serial: the library streams strictly in call order, so no cross-stream contention), each with
     its own binding bound computed from the bytes it actually moves (lyra_amd/csrc/state_layout.h);
@@ -149,7 +155,7 @@ def parse(argv=None):
                     help="external sample rate: both resamplers around the codec when it is not 16000")
     ap.add_argument("--per-call", action="store_true",
                     help="drive the individual `_dev` entry points from Python instead of lyra_hip_run_steps_dev")
-    ap.add_argument("--latency-steps", type=int, default=200, help="isolated steps for the latency distribution (0: skip)")
+    ap.add_argument("--latency-steps", type=int, default=200, help="isolated steps for the latency distribution (0: skip; --full only)")
     ap.add_argument("--ramp-steps", type=int, default=64,
                     help="extra UNTIMED steps enqueued right before the timed region so that it starts on a chip at its "
                          "loaded clocks: after >= 20 ms of idling a 20-step region runs 14 %% slower "
@@ -165,12 +171,12 @@ def parse(argv=None):
                     help="skip the self-check: after all timing, the packets and the PCM of the run's LAST TWO steps are "
                          "compared, for the first --verify-streams streams of every rank, with the CPU oracle replaying "
                          "every step the context has executed since its reset (state is carried, so the end state "
-                         "vouches for the whole run).  Outside every timed region.")
+                         "vouches for the whole run).  Outside every timed region; --full only.")
     ap.add_argument("--verify-streams", type=int, default=32)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baselines (--full only)")
     ap.add_argument("--no-cpu-confine", action="store_true",
                     help="at --gpus N > 1 do not confine each rank to its share of the CPU quota (confine_rank_to_cpu_share)")
-    ap.add_argument("--no-kernel-table", action="store_true")
+    ap.add_argument("--no-kernel-table", action="store_true", help="skip the serialised kernel table (--full only)")
     ap.add_argument("--per-call-split", action="store_true",
                     help="with --per-call at an external rate: every codec call on its own (resample, encode, decode, estimator, "
                          "resample) instead of lyra_hip_encode_ext_dev / lyra_hip_decode_ext_dev, one call per side and hop")
@@ -187,7 +193,18 @@ def parse(argv=None):
     ap.add_argument("--stub-context", action="store_true",
                     help="CPU-only test hook: run main() itself -- process group (gloo), sharding, weight broadcast, "
                          "barriers, reductions, result line -- with a stand-in for the GPU shard that only counts its calls")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beyond the headline: serialised kernel table, latency steps, config #4's second timed "
+                         "region, the self-check against the CPU oracle, the CPU baselines (off: none of them run, whatever "
+                         "--no-kernel-table / --latency-steps / --no-verify / --no-cpu-baseline say)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (the arrays the caller of the "
+                         "timed path receives: packets, PCM, ...) as DIR/<name>.npy in float32 (float64 where that would round), at most 64 MB in all (a fixed "
+                         "sample of the streams beyond that); with --gpus N > 1 every rank writes rank<r>_<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def resolve_workload(args, world):
@@ -624,6 +641,25 @@ class Shard:
         self.ctx.synchronize()
         self.torch.cuda.synchronize(self.dev)
 
+    def outputs(self, kind, step):
+        """What absolute step `step` (of kind `kind`) handed its caller, copied to the host: the packet / PCM buffer set
+        of that step (the two-buffer rule: set step & 1) and the per-hop outputs of the legs that are on."""
+        self.sync()
+        s = step & 1
+        out = {}
+        if kind == "encdec":
+            out["packets"] = self.packets[s]
+            if self.packet_bytes is not None:
+                out["packet_bytes"] = self.packet_bytes[s]
+        out["pcm_out"] = self.pcm_out[s]
+        if self.ext_out is not None:
+            out["pcm_out_ext"] = self.ext_out[s]
+        if self.is_noise is not None:
+            out["is_noise"] = self.is_noise
+        if self.mel is not None:
+            out["logmel"] = self.mel
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
     def kernel_table(self, kind, first, nsteps):
         """Serialised pass: every kernel bracketed by HIP events, the library streams strictly in call order."""
         ctx = self.ctx
@@ -684,6 +720,13 @@ class StubShard:
     def sync(self):
         self.calls["sync"] += 1
 
+    def outputs(self, kind, step):
+        """Per stream: its id, the step it reports and how many steps of each kind the stub has counted so far."""
+        B = self.wl["B"]
+        ids = np.arange(self.first_id, self.first_id + B, dtype=np.int64)
+        counts = np.array([self.calls["encdec"], self.calls["generate"], self.calls["decode"]], np.int64)
+        return {"stream_ids": ids, "step": np.full(B, step, np.int64), "calls": np.tile(counts, (B, 1))}
+
     def kernel_table(self, kind, first, nsteps):
         self.steps(kind, first, nsteps + 2)
         return None
@@ -722,15 +765,49 @@ def latency_stats(samples):
             "p99": round(pick(0.99), 1), "max": round(float(a[-1]), 1), "stddev": round(float(a.std()), 1)}
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def _as_float(a):
+    """float32 where it holds every value exactly (bytes, int16 PCM, flags, integers below 2^24, float32), else float64."""
+    a = np.asarray(a)
+    if a.dtype == np.float32 or (a.dtype.kind in "iub" and (a.dtype.itemsize <= 2 or np.abs(a).max(initial=0) < 2 ** 24)):
+        return a.astype(np.float32)
+    return a.astype(np.float64)
+
+
+def write_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, prefix=""):
+    """--dump-outputs: every array (streams on axis 0) as out_dir/<prefix><name>.npy in float32 / float64 (_as_float).
+    Over `budget` bytes in all, the same fixed, seeded sample of streams is kept from every array, in stream order, and
+    its row indices are written as <prefix>sampled_streams.npy.  -> {file name: shape}."""
+    conv = {k: _as_float(v) for k, v in arrays.items()}
+    n = min(a.shape[0] for a in conv.values())
+    total = sum(a.nbytes for a in conv.values())
+    if total > budget:
+        per_row = total / n
+        keep = max(1, int((budget - 4096 * (len(conv) + 1) - 8 * n) // per_row))   # npy headers, the row indices
+        rows = np.sort(np.random.Generator(np.random.PCG64(SEED)).choice(n, size=min(keep, n), replace=False))
+        conv = {k: a[rows] for k, a in conv.items()}
+        conv["sampled_streams"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for k, a in conv.items():
+        name = prefix + k + ".npy"
+        np.save(os.path.join(out_dir, name), np.ascontiguousarray(a))
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def run_shard(sh, args, wl, barrier):
-    """Warm-up, serialised kernel table, timed region(s), latency leg of one shard -> dict of raw results."""
-    K, W = args.steps, args.warmup
+    """Warm-up and timed region of one shard (plus, with --dump-outputs, what its last step computed); under --full also the
+    serialised kernel table, the latency leg, config #4's second region and the self-check -> dict of raw results."""
+    K, W, full = args.steps, args.warmup, args.full
     kind = "encdec" if wl["mode"] == "encdec" else "generate"
     sh.steps(kind, 0, W)
     sh.sync()
     table = None
     cursor = W
-    if not args.no_kernel_table:
+    if full and not args.no_kernel_table:
         table = sh.kernel_table(kind, cursor, 8)
         cursor += 10
         sh.steps(kind, cursor, 2)   # back to the overlapped regime before timing
@@ -747,10 +824,12 @@ def run_shard(sh, args, wl, barrier):
     res = {"seconds": secs, "table": table, "dom": dom, "dom_prof": prof.get(dom) if dom else None,
            "doms": [(k, prof.get(k)) for k in doms],
            "enqueue_seconds": getattr(sh, "enqueue_seconds", None)}
-    if args.latency_steps > 0:
+    if args.dump_outputs:   # before anything else overwrites the buffers of the last timed step
+        res["outputs"] = sh.outputs(kind, cursor - 1)
+    if full and args.latency_steps > 0:
         res["latency"] = sh.latency(kind, cursor, args.latency_steps)
         cursor += args.latency_steps
-    if wl["mode"] == "decode":
+    if full and wl["mode"] == "decode":
         sh.steps("decode", cursor, 3)
         sh.sync()
         cursor += 3
@@ -765,7 +844,7 @@ def run_shard(sh, args, wl, barrier):
         secs2, _ = sh.timed("decode", cursor, K, barrier)
         res["secondary_seconds"] = secs2
         res["secondary_table"] = table2
-    if not args.no_verify:
+    if full and not args.no_verify:
         try:
             res["verify"] = sh.verify(args.verify_streams)
         except Exception as e:   # a broken checker must not take the measurement down; it must not pass silently either
@@ -838,7 +917,7 @@ def result_line(args, wl, world, secs, frames, res, launcher):
     if res.get("verify") is not None:
         out["verified"] = res["verify"].get("verified")
         out["verify"] = res["verify"]
-    if mode == "decode":
+    if mode == "decode" and res.get("secondary_seconds") is not None:
         s2 = res["secondary_seconds"]
         v2 = frames / s2
         out["secondary"] = {"what": "lyra_hip_decode_dev: packets -> PCM (RVQ decode fused into decoder stage 0)",
@@ -930,8 +1009,11 @@ def main_single_process(args, ngpu):
         t.join()
     secs = max(r["seconds"] for r in results)
     res = dict(results[0])
-    if wl["mode"] == "decode":
+    if wl["mode"] == "decode" and args.full:
         res["secondary_seconds"] = max(r["secondary_seconds"] for r in results)
+    if args.dump_outputs:
+        for r in range(ngpu):
+            write_outputs(args.dump_outputs, results[r]["outputs"], DUMP_BUDGET_BYTES // ngpu, f"rank{r}_" if ngpu > 1 else "")
     out = result_line(args, wl, ngpu, secs, wl["B"] * ngpu * args.steps, res, "one process, one host thread per GPU")
     print(json.dumps(out))
 
@@ -1007,8 +1089,10 @@ def main(argv=None):
             dist.barrier()
 
     res = run_shard(sh, args, wl, barrier)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, res["outputs"], DUMP_BUDGET_BYTES // world, f"rank{rank}_" if world > 1 else "")
     secs, frames = reduce_job(res["seconds"], wl["B"] * args.steps, world, dev)
-    if wl["mode"] == "decode":
+    if wl["mode"] == "decode" and args.full:
         res["secondary_seconds"], _ = reduce_job(res["secondary_seconds"], 0, world, dev)
     per_rank = gather_ranks(rank_summary(res, args, wl), world)
     out = None
@@ -1043,7 +1127,7 @@ def main(argv=None):
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if not args.no_cpu_baseline and not stub:   # rank 0's host cores, at any world size
+        if args.full and not args.no_cpu_baseline and not stub:   # rank 0's host cores, at any world size
             if confined:   # back to the CPUs a one-rank run has
                 try:
                     os.sched_setaffinity(0, confined[0])

@@ -8,6 +8,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+REF_MODEL_COEFFS = os.path.join(ROOT, "oracle", "_ref", "model_coeffs")
 
 
 def pytest_configure(config):
@@ -17,6 +18,21 @@ def pytest_configure(config):
 @pytest.fixture(scope="session")
 def golden_dir():
     return GOLDEN
+
+
+@pytest.fixture(scope="session")
+def ref_model_coeffs():
+    """The reference's model directory (three .tflite + lyra_config.binarypb) as build() staged it (oracle/Makefile)."""
+    if not os.path.isfile(os.path.join(REF_MODEL_COEFFS, "lyragan.tflite")):
+        pytest.skip("oracle/_ref/model_coeffs not staged: build() stages it only where the reference tree is readable")
+    return REF_MODEL_COEFFS
+
+
+@pytest.fixture(scope="session")
+def speech_sample1():
+    """sample1_16kHz of the reference's testdata as int16 PCM (tests/golden/sample_wavs.npz)."""
+    import numpy as np
+    return np.load(os.path.join(GOLDEN, "sample_wavs.npz"))["sample1_16kHz"]
 
 
 @pytest.fixture(scope="session")

@@ -167,10 +167,10 @@ def test_bench_main_two_ranks_with_stub_context_gloo():
 def test_bench_default_invocation_spawns_one_rank_per_gpu():
     """`python bench.py --gpus 2` exactly as a driver without a launcher types it: bench.py re-executes itself under
     torch.distributed.run, so the job is two processes with a process group (gloo here, RCCL on the GPU box), not two
-    threads of one process.  Stub shard; the latency leg and the kernel-table pass run too."""
+    threads of one process.  Stub shard; the latency leg and the kernel-table pass run too (--full)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--stub-context", "--gpus", "2", "--steps", "5", "--warmup", "2",
-           "--no-cpu-baseline", "--latency-steps", "10"]
+           "--full", "--no-cpu-baseline", "--latency-steps", "10"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -193,7 +193,7 @@ def test_bench_eight_ranks_config5_and_default_respawn():
     world size (skipped here only because the stub has no oracle workload to time: --no-cpu-baseline)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--stub-context", "--gpus", "8", "--config", "5", "--steps", "4",
-           "--warmup", "1", "--no-cpu-baseline", "--latency-steps", "0", "--no-kernel-table", "--ramp-steps", "0"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--latency-steps", "0", "--no-kernel-table", "--ramp-steps", "0"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -224,6 +224,58 @@ def test_bench_force_dist_one_rank_gloo():
     assert r["n_gpus"] == 1 and r["ranks"] == 1 and "forced at one rank" in r["process_group"]
     assert abs(r["value"] - 4096 * 5 / (5 * 1e-4)) < 1.0
     assert r["stub"]["weights_bytes"] == os.path.getsize(os.path.join(ROOT, "lyra_amd", "assets", "lyra_v1.lyrapack"))
+
+
+def test_bench_plain_run_is_lean_and_full_run_has_every_leg(tmp_path):
+    """A plain run: warm-up, the untimed ramp, the timed steps, the result line -- no kernel table, latency leg,
+    self-check or CPU baseline; --full brings them all back.  --dump-outputs writes what the last timed step computed."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--stub-context", "--steps", "5", "--warmup", "2"]
+    out = subprocess.run(base + ["--dump-outputs", str(tmp_path / "plain")], capture_output=True, text=True, env=env, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in r, k
+    assert r["steps"] == 5 and abs(r["ms_per_step"] - 0.1) < 1e-9
+    assert r["stub"]["calls"]["encdec"] == 2 + 64 + 5                  # warm-up + untimed ramp + timed, nothing else
+    for k in ("kernels", "step_latency_us", "verified", "verify", "cpu_baseline", "cpu_baseline_xnnpack"):
+        assert k not in r, k
+    d = tmp_path / "plain"
+    assert sorted(os.listdir(d)) == ["calls.npy", "step.npy", "stream_ids.npy"]
+    ids, step, calls = (np.load(d / f) for f in ("stream_ids.npy", "step.npy", "calls.npy"))
+    assert ids.dtype == step.dtype == calls.dtype == np.float32
+    assert np.array_equal(ids, np.arange(4096)) and np.all(step == 2 + 64 + 5 - 1)
+    assert np.all(calls == [2 + 64 + 5, 0, 0])                        # taken right after the timed region
+    out = subprocess.run(base + ["--full", "--no-cpu-baseline", "--latency-steps", "10", "--dump-outputs", str(tmp_path / "full")],
+                         capture_output=True, text=True, env=env, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert r["stub"]["calls"]["encdec"] == 2 + 10 + 2 + 64 + 5 + 10 and r["verified"] is True and r["step_latency_us"]["n"] == 10
+    assert np.all(np.load(tmp_path / "full" / "calls.npy") == [2 + 10 + 2 + 64 + 5, 0, 0])
+
+
+def test_bench_dump_outputs_stays_within_its_budget(tmp_path):
+    """Over the budget every array keeps the same fixed, seeded sample of streams (rows), written in stream order; the
+    same call twice writes the same files."""
+    sys.path.insert(0, ROOT)
+    import bench
+    B = 1000
+    arrays = {"pcm_out": (np.arange(B * 320) % 30000 - 15000).astype(np.int16).reshape(B, 320), "packets": np.full((B, 23), 255, np.uint8),
+              "big": np.full(B, 1 << 30, np.int64)}
+    small = bench.write_outputs(str(tmp_path / "a"), arrays, budget=B * 400 * 4)
+    assert small == {"pcm_out.npy": [B, 320], "packets.npy": [B, 23], "big.npy": [B]}
+    assert np.load(tmp_path / "a" / "big.npy").dtype == np.float64 and np.load(tmp_path / "a" / "pcm_out.npy").dtype == np.float32
+    budget = 200 * 1024
+    for sub in ("b", "c"):
+        shapes = bench.write_outputs(str(tmp_path / sub), arrays, budget=budget)
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in shapes)
+    assert total <= budget and 0 < shapes["pcm_out.npy"][0] < B
+    rows = np.load(tmp_path / "b" / "sampled_streams.npy")
+    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0)
+    pcm = np.load(tmp_path / "b" / "pcm_out.npy")
+    assert np.array_equal(pcm, arrays["pcm_out"][rows.astype(int)].astype(np.float32))
+    for f in shapes:
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f)), f
 
 
 def test_bench_roofline_bookkeeping():
@@ -292,27 +344,22 @@ def test_call_combiner_under_thread_sanitizer(tmp_path):
         assert r.returncode == 0, (r.returncode, r.stderr[-500:])
 
 
-REF_MODEL_DIR = "/root/reference/lyra/model_coeffs"
-
-
 def _pack_tool():
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "lyra_amd", "csrc"), "../pack_tool"], stdout=subprocess.DEVNULL)
     return os.path.join(ROOT, "lyra_amd", "pack_tool")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODEL_DIR), reason="reference model directory not present on this box")
-def test_cxx_tflite_reader_reproduces_the_shipped_container(tmp_path):
+def test_cxx_tflite_reader_reproduces_the_shipped_container(tmp_path, ref_model_coeffs):
     """lyra_hip_create() accepts the reference's model directory as is (three .tflite + lyra_config.binarypb,
     lyra_components.cc:42-55): its C++ flatbuffer reader (csrc/tflite_pack.cc) must yield, byte for byte, the
     container the repository ships (written by tools/pack_weights.py from the same directory)."""
     out = tmp_path / "cxx.lyrapack"
-    subprocess.check_call([_pack_tool(), REF_MODEL_DIR, str(out)], stdout=subprocess.DEVNULL)
+    subprocess.check_call([_pack_tool(), ref_model_coeffs, str(out)], stdout=subprocess.DEVNULL)
     shipped = open(os.path.join(ROOT, "lyra_amd", "assets", "lyra_v1.lyrapack"), "rb").read()
     assert open(out, "rb").read() == shipped
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODEL_DIR), reason="reference model directory not present on this box")
-def test_cxx_tflite_reader_rejects_bad_model_dirs(tmp_path):
+def test_cxx_tflite_reader_rejects_bad_model_dirs(tmp_path, ref_model_coeffs):
     import shutil
     tool = _pack_tool()
     names = ["soundstream_encoder.tflite", "quantizer.tflite", "lyragan.tflite", "lyra_config.binarypb"]
@@ -321,7 +368,7 @@ def test_cxx_tflite_reader_rejects_bad_model_dirs(tmp_path):
         d = tmp_path / name
         d.mkdir()
         for n in names:
-            shutil.copy(os.path.join(REF_MODEL_DIR, n), d / n)
+            shutil.copy(os.path.join(ref_model_coeffs, n), d / n)
         return d
 
     def run(d):

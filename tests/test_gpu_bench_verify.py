@@ -1,4 +1,4 @@
-"""bench.py checks the run it times: the exact call pattern of the driver's invocation (`--steps 20 --warmup 5`: warm-up,
+"""bench.py checks the run it times: the exact call pattern of the driver's invocation with --full (`--steps 20 --warmup 5`: warm-up,
 serialised kernel table, 64 ramp steps, the timed lyra_hip_run_steps_dev region, latency steps, one context, input ring
 cycled) is replayed by the CPU oracle and the GPU's final packets / PCM must be bit-equal -- for every BASELINE config the
 bench offers (lyra_benchmark_lib.cc:121-160 is the loop being replaced).  A negative control shows the check has teeth."""
@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 def _run(argv):
     import bench
-    args = bench.parse(argv + ["--no-cpu-baseline", "--verify-streams", "64"])
+    args = bench.parse(argv + ["--full", "--no-cpu-baseline", "--verify-streams", "64"])
     wl = bench.resolve_workload(args, 1)
     sh = bench.Shard(0, 0, wl, args)
     res = bench.run_shard(sh, args, wl, lambda: None)
@@ -45,6 +45,26 @@ def test_bench_verify_has_teeth():
     sh.ctx.close()
 
 
+def test_bench_plain_run_dumps_the_verified_last_step(tmp_path):
+    """A plain run (no --full): warm-up, ramp, timed steps and nothing after them, so the outputs --dump-outputs takes are
+    the last timed step's -- and those are the oracle's (the self-check, called by hand here, replays every step)."""
+    import bench
+    args = bench.parse(["--config", "2", "--steps", "6", "--warmup", "2", "--ramp-steps", "4", "--dump-outputs", str(tmp_path)])
+    wl = bench.resolve_workload(args, 1)
+    sh = bench.Shard(0, 0, wl, args)
+    res = bench.run_shard(sh, args, wl, lambda: None)
+    assert "verify" not in res and res["table"] is None and "latency" not in res
+    assert [n for _, _, n in sh.history] == [2, 4, 6]
+    assert sh.verify(64)["verified"] is True
+    last = (2 + 4 + 6 - 1) & 1
+    bench.write_outputs(str(tmp_path), res["outputs"])
+    assert sorted(os.listdir(tmp_path)) == ["packets.npy", "pcm_out.npy"]
+    pk, pcm = np.load(tmp_path / "packets.npy"), np.load(tmp_path / "pcm_out.npy")
+    assert pk.dtype == pcm.dtype == np.float32 and pk.shape == (1024, 8) and pcm.shape == (1024, 320)
+    assert np.array_equal(pk, sh.packets[last].cpu().numpy()) and np.array_equal(pcm, sh.pcm_out[last].cpu().numpy())
+    sh.ctx.close()
+
+
 def test_bench_rccl_path_with_one_rank():
     """The N > 1 code path of bench.py has only ever met gloo on CPU (no multi-GPU box was available to this build):
     `--force-dist` brings the RCCL process group up with ONE rank, so init_process_group("nccl"), the weight broadcast,
@@ -55,7 +75,7 @@ def test_bench_rccl_path_with_one_rank():
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29531", os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--bcast-weights",
-           "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--latency-steps", "0", "--verify-streams", "16"]
+           "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--latency-steps", "0", "--verify-streams", "16"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -76,7 +96,7 @@ def test_bench_two_ranks_sharing_the_one_gpu():
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29532", os.path.join(root, "bench.py"), "--gpus", "2", "--oversubscribe-device", "0", "--bcast-weights",
-           "--config", "2", "--steps", "12", "--warmup", "3", "--no-cpu-baseline", "--latency-steps", "0", "--verify-streams", "16"]
+           "--config", "2", "--steps", "12", "--warmup", "3", "--full", "--no-cpu-baseline", "--latency-steps", "0", "--verify-streams", "16"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -6,17 +6,13 @@ integers (no numpy int64 vector code shared with the interpreter).
 
 It validates the interpreter's convolution arithmetic layer by layer on real speech with live state; it does NOT turn the
 parity claim into "pinned to TFLite" -- no TFLite binary exists offline (README "Parity").
-Needs the reference's flatbuffers: skipped on the GPU box.
+Needs the reference's flatbuffers (oracle/_ref/model_coeffs, staged by build()): skipped where they are not staged.
 """
 import math
 import os
-import wave
 
 import numpy as np
 import pytest
-
-REF = "/root/reference/lyra"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF + "/model_coeffs"), reason="reference flatbuffers not present")
 
 
 def _qm(m):
@@ -106,22 +102,20 @@ def _check_graph(path, sig_input, frames, mode):
     return n_checked
 
 
-def _speech(n):
-    w = wave.open(REF + "/testdata/sample1_16kHz.wav")
-    pcm = np.frombuffer(w.readframes(w.getnframes()), np.int16)
+def _speech(pcm, n):
     return pcm[20 * 320:(20 + n) * 320].reshape(n, 320)   # skip the leading near-silence
 
 
 @pytest.mark.parametrize("mode", ["exact", "gemmlowp_double"])
-def test_encoder_convs_vs_torch(mode):
-    frames = [(h.astype(np.float32) / np.float32(32768.0)).reshape(1, 320) for h in _speech(3)]
-    n = _check_graph(REF + "/model_coeffs/soundstream_encoder.tflite", "input_audio", frames, mode)
+def test_encoder_convs_vs_torch(mode, ref_model_coeffs, speech_sample1):
+    frames = [(h.astype(np.float32) / np.float32(32768.0)).reshape(1, 320) for h in _speech(speech_sample1, 3)]
+    n = _check_graph(os.path.join(ref_model_coeffs, "soundstream_encoder.tflite"), "input_audio", frames, mode)
     assert n == {"CONV_2D": 23 * 3, "DEPTHWISE_CONV_2D": 9 * 3, "TRANSPOSE_CONV": 0}   # SURVEY.md section 2 op histogram
 
 
 @pytest.mark.parametrize("mode", ["exact", "gemmlowp_double"])
-def test_decoder_convs_vs_torch(mode, golden_dir):
+def test_decoder_convs_vs_torch(mode, golden_dir, ref_model_coeffs):
     g = np.load(os.path.join(golden_dir, "speech_sample1.npz"))
     frames = [f.reshape(1, 1, 64) for f in g["lossy_exact"][20:23]]
-    n = _check_graph(REF + "/model_coeffs/lyragan.tflite", "input_audio", frames, mode)
+    n = _check_graph(os.path.join(ref_model_coeffs, "lyragan.tflite"), "input_audio", frames, mode)
     assert n == {"CONV_2D": 19 * 3, "DEPTHWISE_CONV_2D": 9 * 3, "TRANSPOSE_CONV": 8 * 3}

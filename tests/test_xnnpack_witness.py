@@ -17,7 +17,7 @@ settles (profiles/history/r04_xnnpack_witness.txt has the table):
     chain, taps ascending -- now the canonical fp32 order;
   * the last layer (one output channel) is routed to a different x86 kernel (4x2c4 SSE: four lane sums, unfused), which no
     ARM build shares: the canonical order stays the fused chain there, and the difference is bounded below.
-Needs the reference flatbuffers and torch: this container only (skipped on the GPU box).
+Needs the reference flatbuffers (oracle/_ref/model_coeffs, staged by build()) and torch; skipped where either is missing.
 """
 import os
 
@@ -26,8 +26,8 @@ import pytest
 
 from oracle import xnn_witness
 
-pytestmark = pytest.mark.skipif(not (os.path.isdir("/root/reference/lyra/model_coeffs") and xnn_witness.available()),
-                                reason="needs /root/reference and oracle/_xnn/libxnn_witness.so")
+pytestmark = pytest.mark.skipif(not xnn_witness.available(), reason="needs oracle/_xnn/libxnn_witness.so")
+GRAPHS = {"ENC": "soundstream_encoder.tflite", "DEC": "lyragan.tflite"}
 
 
 def _cmp():
@@ -35,21 +35,26 @@ def _cmp():
     return xnn_compare
 
 
-def test_every_arithmetic_op_of_the_encoder_equals_real_xnnpack():
+def _speech_frames(pcm, n, start=20):
+    """xnn_compare.speech_frames over the stored copy of sample1_16kHz."""
+    return [(h.astype(np.float32) / np.float32(32768.0)).reshape(1, 320) for h in pcm[start * 320:(start + n) * 320].reshape(n, 320)]
+
+
+def test_every_arithmetic_op_of_the_encoder_equals_real_xnnpack(ref_model_coeffs, speech_sample1):
     xc = _cmp()
-    res = xc.per_op_on_traced(xc.ENC, "input_audio", xc.speech_frames(4))
+    res = xc.per_op_on_traced(os.path.join(ref_model_coeffs, GRAPHS["ENC"]), "input_audio", _speech_frames(speech_sample1, 4))
     assert sum(1 for k in res if k[2] == "q") == 34 and sum(1 for k in res if k[2] == "f") == 45   # every arithmetic op visited
     for k, r in sorted(res.items()):
         assert r["refused"] == 0, ("XNNPACK refused to create the operator", k)
         assert r["differ"] == 0, (k, r)
 
 
-def test_every_arithmetic_op_of_the_decoder_equals_real_xnnpack(golden_dir):
+def test_every_arithmetic_op_of_the_decoder_equals_real_xnnpack(golden_dir, ref_model_coeffs):
     xc = _cmp()
     g = np.load(os.path.join(golden_dir, "speech_sample1.npz"))
     key = "lossy_xnnpack" if "lossy_xnnpack" in g.files else "lossy_exact"
     frames = [f.reshape(1, 1, 64) for f in g[key][20:24]]
-    res = xc.per_op_on_traced(xc.DEC, "input_audio", frames)
+    res = xc.per_op_on_traced(os.path.join(ref_model_coeffs, GRAPHS["DEC"]), "input_audio", frames)
     assert sum(1 for k in res if k[2] == "q") == 42 and sum(1 for k in res if k[2] == "f") == 52
     n_last = 0
     for k, r in sorted(res.items()):
@@ -63,9 +68,9 @@ def test_every_arithmetic_op_of_the_decoder_equals_real_xnnpack(golden_dir):
 
 
 @pytest.mark.parametrize("which", ["ENC", "DEC"])
-def test_int8_elementwise_ops_exhaustively(which):
+def test_int8_elementwise_ops_exhaustively(which, ref_model_coeffs):
     xc = _cmp()
-    rows = xc.elementwise_exhaustive(getattr(xc, which))
+    rows = xc.elementwise_exhaustive(os.path.join(ref_model_coeffs, GRAPHS[which]))
     names = [r["name"] for r in rows]
     assert names.count("LEAKY_RELU") == (7 if which == "ENC" else 6) and names.count("ADD") == 2
     for r in rows:
@@ -78,9 +83,9 @@ def test_int8_elementwise_ops_exhaustively(which):
 
 
 @pytest.mark.parametrize("which", ["ENC", "DEC"])
-def test_int8_convolutions_requantise_in_fp32(which):
+def test_int8_convolutions_requantise_in_fp32(which, ref_model_coeffs):
     xc = _cmp()
-    rows = xc.conv_requant_random(getattr(xc, which), rows_per_layer=6000)
+    rows = xc.conv_requant_random(os.path.join(ref_model_coeffs, GRAPHS[which]), rows_per_layer=6000)
     assert len(rows) == (9 if which == "ENC" else 15)
     for r in rows:
         assert r["vs_model"] == 0, r
@@ -91,9 +96,9 @@ def test_int8_convolutions_requantise_in_fp32(which):
 
 
 @pytest.mark.parametrize("which", ["ENC", "DEC"])
-def test_fp32_layers_are_bias_first_fused_chains(which):
+def test_fp32_layers_are_bias_first_fused_chains(which, ref_model_coeffs):
     xc = _cmp()
-    rows = xc.fp32_layers_random(getattr(xc, which))
+    rows = xc.fp32_layers_random(os.path.join(ref_model_coeffs, GRAPHS[which]))
     assert len(rows) == (23 if which == "ENC" else 21)
     for r in rows:
         if r["last"]:

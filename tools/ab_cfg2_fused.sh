@@ -1,5 +1,5 @@
 P=$PWD/lyra_amd/variants/parked.so
-run() { python bench.py --config 2 --no-cpu-baseline --latency-steps 0 --steps 2000 2>/dev/null | python -c "
+run() { python bench.py --config 2 --full --no-cpu-baseline --latency-steps 0 --steps 2000 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', r['value'], r['ms_per_step'], r.get('verified'))"; }
 for i in 1 2; do

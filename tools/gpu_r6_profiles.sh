@@ -4,8 +4,8 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -4
 TAG=r06 bash tools/gpu_profile_round.sh 2>&1 | tail -40
 O=gpurun_out/r06
-timeout 300 python bench.py --full-decoder --dtx --rate 48000 --no-cpu-baseline > $O/r06_bench_full_dtx_48k.json 2>> $O/bench.err
-timeout 300 python bench.py --requant builtin_mixed --no-cpu-baseline > $O/r06_bench_builtin_mixed.json 2>> $O/bench.err
+timeout 300 python bench.py --full --full-decoder --dtx --rate 48000 --no-cpu-baseline > $O/r06_bench_full_dtx_48k.json 2>> $O/bench.err
+timeout 300 python bench.py --full --requant builtin_mixed --no-cpu-baseline > $O/r06_bench_builtin_mixed.json 2>> $O/bench.err
 for a in "16000 0" "48000 10"; do set -- $a; timeout 300 lyra_amd/batch_bench lyra_amd/assets 4096 $1 9200 $2 200; done > $O/r06_batch_bench.jsonl 2>> $O/bench.err
 timeout 300 lyra_amd/plugin_demo --bench lyra_amd/assets 2000 120 > $O/r06_plugin_boundary_bench.txt 2>&1
 for f in $O/r06_bench_*.json; do python - "$f" <<'PY'
