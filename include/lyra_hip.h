@@ -251,7 +251,8 @@ int lyra_hip_encode_dtx(lyra_hip_ctx* ctx, const int32_t* stream_ids, int B, con
                         uint8_t* packets, int32_t* packet_bytes);
 
 /* LyraDecoder::SetEncodedPacket + DecodeSamples(320) steady state, no loss/PLC
- * (lyra/lyra_decoder.cc:172-226,284-326): unpack -> DecodeToLossyFeatures -> generative model. */
+ * (lyra/lyra_decoder.cc:172-226,284-326): unpack -> DecodeToLossyFeatures -> generative model.
+ * (Lost packets / DTX's empty packets on the device path: lyra_hip_decode_lossy_dev below.) */
 int lyra_hip_decode(lyra_hip_ctx* ctx, const int32_t* stream_ids, int B, const uint8_t* packets, int num_bits,
                     int16_t* pcm);
 
@@ -306,6 +307,11 @@ int lyra_hip_decode_ext_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_ids, int 
                                            lyra_hip_generate_dev on those features (lyra_gan_model path) */
 #define LYRA_HIP_STEP_DTX 4u            /* encode with enable_dtx: lyra_hip_encode_dtx_dev (lyra_encoder.cc:131-141) */
 #define LYRA_HIP_STEP_DECODER_NOISE 8u  /* NoiseEstimator::ReceiveSamples on every decoded hop (lyra_decoder.cc:304-311) */
+#define LYRA_HIP_STEP_PACKET_LOSS 16u   /* the decode leg is lyra_hip_decode_lossy_dev: row b of step `step` is received when
+                                           d_received_ring[step % n_received_ring][b] != 0 (NULL: always) and, with
+                                           ENCODE | DTX, the encoder's d_packet_bytes[set][b] != 0; the decoder-side
+                                           estimator always runs, d_is_noise is optional.  Needs DECODE, no d_features.
+                                           The three fields after d_ext_out are read only with this flag. */
 typedef struct lyra_hip_steps {
   const int32_t* d_stream_ids;   /* [B] */
   int B;
@@ -327,8 +333,43 @@ typedef struct lyra_hip_steps {
   int external_rate;             /* 0 / 16000: none; 8000 / 32000 / 48000: the encoder's and the decoder's resampler
                                     (lyra_encoder.cc:119-122, lyra_decoder.cc:107-113) around the codec */
   int16_t* d_ext_out[2];         /* [B][320 * external_rate / 16000] each: decoder output at the external rate */
+  /* LYRA_HIP_STEP_PACKET_LOSS only (appended: callers built against the struct without them keep working) */
+  const uint8_t* d_received_ring;  /* [n_received_ring][B] 0 / 1, or NULL = all received */
+  int n_received_ring;
+  int32_t* d_is_comfort_noise;     /* [B] or NULL: is_comfort_noise() after the step's hop */
 } lyra_hip_steps;
 int lyra_hip_run_steps_dev(lyra_hip_ctx* ctx, const lyra_hip_steps* steps);
+
+/* ---- Packet loss on the device path: hop-synchronous receivers ---------------------------------------------------------
+ * LyraDecoder::SetEncodedPacket (if a packet arrived) + DecodeSamples(one hop) for B streams (lyra_decoder.cc:172-373), the
+ * case of decoder_main_lib.cc:95-135 and of a media server: on every 20 ms tick each stream receives one packet or none and
+ * then decodes exactly one hop.  The reference's packet-loss concealment (ZeroFeatureEstimator features), the cosine
+ * cross-fade to comfort noise after 80 ms of consecutive losses, the fade back when packets return and the decoder-side
+ * NoiseEstimator fed with received hops only all run on the device; the per-stream state is three small integers kept in
+ * the stream's comfort-noise slot (all zero after lyra_hip_create / lyra_hip_reset_streams = the reference's initial state).
+ *   d_packet_bytes[b] == 0: no packet this hop (lost, or DTX's empty packet) -> concealment / comfort noise; otherwise it
+ *   must equal the packet size of num_bits and row b of d_packets [B][num_bits / 8 rounded up] is read.  A value that is
+ *   neither is treated as "no packet" and counted in a device error word (lyra_hip_decode_lossy_errors); it never faults.
+ *   d_pcm16 [B][320]: the hop at 16 kHz; d_pcm_ext [B][sample_rate_hz / 50] (may be NULL at 16000): the same through the
+ *   decoder's resampler; d_is_noise [B] (may be NULL): the decoder-side estimator's is_noise() after the tick (unchanged on
+ *   ticks without a packet); d_is_comfort_noise [B] (may be NULL): LyraDecoder::is_comfort_noise() after the tick.
+ * ONE decode-side call for rule (2) of "Streams".  Like lyra_hip_decode_ext_dev, its outputs -- d_pcm16 included, the mix
+ * writes it -- complete on the NOISE stream (lyra_hip_stream_noise / lyra_hip_stream_wait / lyra_hip_synchronize).
+ * Every stream of one call must be in the hop-synchronous regime: arbitrary DecodeSamples(n) requests are
+ * BatchLyraDecoder's (lyra_amd/host/lyra_batch_codec.cc).  Combinations:
+ *   - LYRA_HIP_SUBBATCHES > 1: supported; the call is not split (it stands for every chunk, as small calls do);
+ *   - lyra_hip_set_serial: supported; the call then also ends with its noise-stream half before the next encode-side call;
+ *   - lyra_hip_decode_dev / lyra_hip_decode_ext_dev on the same stream: allowed -- they advance the generative model as a
+ *     received hop would but neither read nor change the loss state or the comfort-noise generator; that is NOT what the
+ *     reference computes for such a mix, so a stream should use one form between resets;
+ *   - lyra_hip_comfort_noise[_dev] and the decoder twin use the same comfort-noise state: do not mix them with this call
+ *     on one stream between resets. */
+int lyra_hip_decode_lossy_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_ids, int B, const uint8_t* d_packets,
+                              const int32_t* d_packet_bytes, int num_bits, int sample_rate_hz, int16_t* d_pcm16,
+                              int16_t* d_pcm_ext, int32_t* d_is_noise, int32_t* d_is_comfort_noise);
+/* Number of d_packet_bytes values since context creation (or the last clear) that were neither 0 nor the packet size;
+ * synchronises.  clear != 0 resets the count.  Negative: error. */
+long lyra_hip_decode_lossy_errors(lyra_hip_ctx* ctx, int clear);
 
 /* ---- Decoder twin: the device half of a batched LyraDecoder (lyra_amd/host/lyra_batch_codec.cc) ------------------------
  * LyraDecoder::DecodeSamplesInternal (lyra_decoder.cc:228-315) keeps per stream the conditioned hop of the generative

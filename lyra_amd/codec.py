@@ -60,10 +60,13 @@ class StepsDesc(C.Structure):
                 ("first_step", C.c_long), ("n_steps", C.c_int), ("ring", C.c_int), ("d_pcm_ring", C.c_void_p),
                 ("d_packets", C.c_void_p * 2), ("d_packet_bytes", C.c_void_p * 2), ("d_pcm_out", C.c_void_p * 2),
                 ("d_features", C.c_void_p), ("n_features", C.c_int), ("d_packet_ring", C.c_void_p), ("n_packet_ring", C.c_int), ("d_is_noise", C.c_void_p), ("external_rate", C.c_int),
-                ("d_ext_out", C.c_void_p * 2)]
+                ("d_ext_out", C.c_void_p * 2),
+                # read by the library only with STEP_PACKET_LOSS
+                ("d_received_ring", C.c_void_p), ("n_received_ring", C.c_int), ("d_is_comfort_noise", C.c_void_p)]
 
 
 STEP_ENCODE, STEP_DECODE, STEP_DTX, STEP_DECODER_NOISE = 1, 2, 4, 8
+STEP_PACKET_LOSS = 16
 
 
 _libs = {}
@@ -122,6 +125,10 @@ def _load(path=None):
     if hasattr(L, "lyra_hip_encode_ext_dev"):   # (one hop at an external rate, one call per side: round 6)
         L.lyra_hip_encode_ext_dev.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp]
         L.lyra_hip_decode_ext_dev.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp]
+    if hasattr(L, "lyra_hip_decode_lossy_dev"):
+        L.lyra_hip_decode_lossy_dev.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp]
+        L.lyra_hip_decode_lossy_errors.argtypes = [vp, ci]
+        L.lyra_hip_decode_lossy_errors.restype = C.c_long
     L.lyra_hip_set_cng_seed.argtypes = [vp, C.c_uint64]
     L.lyra_hip_set_encoder_sample_rate.argtypes = [vp, C.c_int]
     L.lyra_hip_stream.restype = vp
@@ -509,6 +516,29 @@ class LyraHip:
                        self._dev_ptr(d_pcm_ext, "int16", (B, n_ext), "external-rate pcm") if d_pcm_ext is not None else None,
                        self._dev_ptr(d_is_noise, "int32", (B,), "is_noise") if d_is_noise is not None else None)
 
+    def decode_lossy_dev(self, d_ids, d_packets, d_packet_bytes, num_bits, sample_rate_hz, d_pcm16, d_pcm_ext=None,
+                         d_is_noise=None, d_is_comfort_noise=None):
+        """LyraDecoder::SetEncodedPacket (if received) + DecodeSamples(one hop) for a hop-synchronous receiver
+        (lyra_hip_decode_lossy_dev): d_packet_bytes int32 [B], 0 = no packet this hop (concealment / comfort noise), else
+        the packet size; d_pcm16 [B][320], d_pcm_ext [B][rate / 50] (rate != 16000), d_is_noise / d_is_comfort_noise int32
+        [B] optional.  The outputs complete on the noise stream."""
+        B = d_packets.shape[0]
+        n_ext = HOP * sample_rate_hz // 16000
+        self._dev_call(self.L.lyra_hip_decode_lossy_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
+                       self._dev_ptr(d_packets, "uint8", (B, packet_size(num_bits)), "packets"),
+                       self._dev_ptr(d_packet_bytes, "int32", (B,), "packet bytes"), num_bits, sample_rate_hz,
+                       self._dev_ptr(d_pcm16, "int16", (B, HOP), "pcm"),
+                       self._dev_ptr(d_pcm_ext, "int16", (B, n_ext), "external-rate pcm") if d_pcm_ext is not None else None,
+                       self._dev_ptr(d_is_noise, "int32", (B,), "is_noise") if d_is_noise is not None else None,
+                       self._dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise")
+                       if d_is_comfort_noise is not None else None)
+
+    def decode_lossy_errors(self, clear=False):
+        """packet_bytes values seen by decode_lossy_dev / run_steps that were neither 0 nor the packet size (synchronises)."""
+        n = self.L.lyra_hip_decode_lossy_errors(self.h, 1 if clear else 0)
+        self._chk(n if n < 0 else 0)
+        return n
+
     def noise_receive_dev(self, d_ids, d_pcm, d_is_noise, side="decoder"):
         """NoiseEstimator::ReceiveSamples on device buffers: pcm int16 [B][320] -> is_noise int32 [B]."""
         B = d_pcm.shape[0]
@@ -531,18 +561,26 @@ class LyraHip:
 
     def run_steps_dev(self, d_ids, num_bits, n_steps, first_step=0, d_pcm_ring=None, d_packets=None, d_pcm_out=None,
                       d_features=None, d_packet_bytes=None, d_is_noise=None, external_rate=16000, d_ext_out=None,
-                      encode=True, decode=True, dtx=False, decoder_noise=False, d_packet_ring=None):
+                      encode=True, decode=True, dtx=False, decoder_noise=False, d_packet_ring=None,
+                      d_received_ring=None, d_is_comfort_noise=None, packet_loss=False):
         """lyra_hip_run_steps_dev: n_steps hops of every stream from ONE C call.  d_pcm_ring int16
         [ring][B][320 * external_rate / 16000]; d_packets / d_pcm_out / d_packet_bytes / d_ext_out: pairs of tensors
-        (step i uses element (first_step + i) & 1)."""
+        (step i uses element (first_step + i) & 1).  packet_loss: the decode leg is decode_lossy_dev; d_received_ring
+        uint8 [n][B] (None = all received; step i reads row (first_step + i) % n), with dtx DTX's empty packets are not
+        received either."""
         B = d_ids.shape[0]
         n_ext = HOP * external_rate // 16000
         S = StepsDesc()
         S.d_stream_ids = self._dev_ptr(d_ids, "int32", (B,), "stream ids")
         S.B, S.num_bits, S.first_step, S.n_steps = B, num_bits, first_step, n_steps
         S.flags = (STEP_ENCODE if encode else 0) | (STEP_DECODE if decode else 0) | (STEP_DTX if dtx else 0) | \
-            (STEP_DECODER_NOISE if decoder_noise else 0)
+            (STEP_DECODER_NOISE if decoder_noise else 0) | (STEP_PACKET_LOSS if packet_loss else 0)
         S.external_rate = external_rate
+        if d_received_ring is not None:
+            S.n_received_ring = d_received_ring.shape[0]
+            S.d_received_ring = self._dev_ptr(d_received_ring, "uint8", (S.n_received_ring, B), "received ring")
+        if d_is_comfort_noise is not None:
+            S.d_is_comfort_noise = self._dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise")
         if d_pcm_ring is not None:
             S.ring = d_pcm_ring.shape[0]
             S.d_pcm_ring = self._dev_ptr(d_pcm_ring, "int16", (S.ring, B, n_ext), "pcm ring")

@@ -116,6 +116,17 @@ struct lyra_hip_ctx {
   float* d_twin_fade = nullptr;    // [TWIN_FADE_N] cross-fade weights
   int32_t* d_twin_iota = nullptr;  // [max_streams] 0, 1, 2, ...
   uint8_t* h_twin_args = nullptr;  // pinned
+  // lyra_hip_decode_lossy_dev (lossy_api.inc): the tick's scratch.  What the noise-stream leg of call i reads is rewritten
+  // by call i + 2's decode-stream half (ordered after it by dec_side_begin), not by call i + 1's: [2] by call parity.
+  int lossy_cap = 0;
+  int32_t* d_lossy_ids[2] = {};      // [3][lossy_cap]: generative model / comfort noise / noise estimator id lists (-1: skip)
+  int32_t* d_lossy_info[2] = {};     // [lossy_cap] lossy_info() per row
+  int16_t* d_lossy_gan[2] = {};      // [lossy_cap][320] generative hop
+  int16_t* d_lossy_cng = nullptr;    // [lossy_cap][320] comfort-noise hop (noise stream only)
+  float* d_lossy_feat = nullptr;     // [lossy_cap][64] lossy features (decode stream only)
+  float* d_lossy_fade = nullptr;     // [TWIN_FADE_N] cross-fade weights
+  unsigned* d_lossy_err = nullptr;   // packet_bytes values that were neither 0 nor the packet size
+  long n_lossy_calls = 0;
   // Small host-buffer calls (the per-object plugin contract: B = 1 per blocking call) skip the copy engine: the kernels read
   // their input from and write their output to this pinned, device-mapped arena directly -- three copy packets and their
   // stream bubbles fewer per call (lyra_amd/plugin_demo --bench).  ZC_MAX streams per call; LYRA_HIP_NO_ZEROCOPY=1 turns it off.
@@ -181,6 +192,7 @@ int sync_all(lyra_hip_ctx* c) {
 }
 
 void twin_free(lyra_hip_ctx* c);
+void lossy_free(lyra_hip_ctx* c);
 void pipe_free(lyra_hip_ctx* c);
 void free_scratch(lyra_hip_ctx* c) {
   void* ps[] = {c->d_ids, c->d_ids_dec, c->d_pcm_in, c->d_e0, c->d_e1, c->d_feat, c->d_feat2, c->d_codes, c->d_idx, c->d_pkt,
@@ -696,6 +708,10 @@ int launch_noise(lyra_hip_ctx* c, int side, hipStream_t st_, const int32_t* d_id
   return 0;
 }
 
+int lossy_tick_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_packets, const int32_t* d_pkt_bytes,
+                      const uint8_t* d_rx, int num_bits, int ext, int16_t* d_pcm16, int16_t* d_pcm_ext, int32_t* d_is_noise,
+                      int32_t* d_is_cn);   // lossy_api.inc
+
 template <class K>
 hipError_t set_lds(K kernel, size_t bytes) {
   return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -920,6 +936,7 @@ void lyra_hip_destroy(lyra_hip_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)sync_all(c);
   twin_free(c);
+  lossy_free(c);
   pipe_free(c);
   if (c->h_zc) (void)hipHostFree(c->h_zc);
   c->h_zc = nullptr;
@@ -1753,7 +1770,12 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
   if (dec && (!S->d_pcm_out[0] || !S->d_pcm_out[1])) return fail(c, LYRA_HIP_EINVAL, "run_steps: two PCM output buffers needed");
   if ((F & LYRA_HIP_STEP_DTX) && (!S->d_packet_bytes[0] || !S->d_packet_bytes[1]))
     return fail(c, LYRA_HIP_EINVAL, "run_steps: DTX needs two packet_bytes buffers");
-  if ((F & LYRA_HIP_STEP_DECODER_NOISE) && (!dec || !S->d_is_noise))
+  // PACKET_LOSS: the fields appended to lyra_hip_steps are read only under this flag (older callers' structs end before them)
+  const bool loss = F & LYRA_HIP_STEP_PACKET_LOSS;
+  if (loss && (!dec || feats)) return fail(c, LYRA_HIP_EINVAL, "run_steps: PACKET_LOSS needs DECODE of packets (no d_features)");
+  if (loss && S->d_received_ring && S->n_received_ring <= 0)
+    return fail(c, LYRA_HIP_EINVAL, "run_steps: PACKET_LOSS with d_received_ring needs n_received_ring >= 1");
+  if ((F & LYRA_HIP_STEP_DECODER_NOISE) && (!dec || (!S->d_is_noise && !loss)))
     return fail(c, LYRA_HIP_EINVAL, "run_steps: DECODER_NOISE needs DECODE and d_is_noise");
   const int ext = S->external_rate ? S->external_rate : 16000;
   const bool rs = ext != 16000;
@@ -1779,7 +1801,8 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
   static const bool out_on_chain_split = getenv("LYRA_HIP_RS_OUT_ON_CHAIN_SPLIT") != nullptr;
   const bool rs_out_off_chain = rs && !c->serial && (c->nsub == 1 || !out_on_chain_split);
   struct LocalScope { lyra_hip_ctx* c; ~LocalScope() { c->chunk_local = false; c->ids_stable = false; } } local_scope{c};
-  c->chunk_local = c->nsub > 1 && !c->serial && enc && dec && !feats && !rs && !(F & (LYRA_HIP_STEP_DTX | LYRA_HIP_STEP_DECODER_NOISE)) &&
+  c->chunk_local = c->nsub > 1 && !c->serial && enc && dec && !feats && !rs && !loss &&
+                   !(F & (LYRA_HIP_STEP_DTX | LYRA_HIP_STEP_DECODER_NOISE)) &&
                    !getenv("LYRA_HIP_NO_CHUNK_LOCAL");
   for (int i = 0; i < S->n_steps; ++i) {
     const long step = S->first_step + i;
@@ -1820,7 +1843,16 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
         rc = lyra_hip_encode_dev(c, S->d_stream_ids, S->B, in, S->num_bits, S->d_packets[set]);
       if (rc) return rc;
     }
-    if (dec) {
+    if (dec && loss) {   // lyra_hip_decode_lossy_dev (lossy_api.inc): concealment / comfort noise on the device
+      const uint8_t* pk = S->d_packets[set];
+      if (!enc && S->d_packet_ring && S->n_packet_ring > 0)
+        pk = S->d_packet_ring + (size_t)(step % S->n_packet_ring) * B * (size_t)((S->num_bits + 7) / 8);
+      const uint8_t* rx = S->d_received_ring ? S->d_received_ring + (size_t)(step % S->n_received_ring) * B : nullptr;
+      const int32_t* pb = (enc && (F & LYRA_HIP_STEP_DTX)) ? S->d_packet_bytes[set] : nullptr;
+      if ((rc = lossy_tick_launch(c, S->d_stream_ids, S->B, pk, pb, rx, S->num_bits, ext, S->d_pcm_out[set],
+                                  rs ? S->d_ext_out[set] : nullptr, S->d_is_noise, S->d_is_comfort_noise)))
+        return rc;
+    } else if (dec) {
       if (feats) rc = lyra_hip_generate_dev(c, S->d_stream_ids, S->B, S->d_features + (size_t)(step % (S->n_features > 0 ? S->n_features : 1)) * B * 64, S->d_pcm_out[set]);
       else {
         const uint8_t* pk = S->d_packets[set];
@@ -1924,3 +1956,4 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
 
 #include "pipe_api.inc"
 #include "twin_api.inc"
+#include "lossy_api.inc"

@@ -126,6 +126,10 @@ struct NoiseP { int hops_per_update; float max_smoothing, bound_decay; };
 __global__ void logmel_kernel(const MelP* P, const int16_t* pcm, const int32_t* ids, int B, uint8_t* state, int stride,
                               int prev_off, float* mel, int noise_tail, NoiseP NP, int32_t* is_noise_out,
                               int32_t* masked_ids);
+// the same with rows of id -1 skipped entirely (the estimator of lyra_hip_decode_lossy_dev sees received hops only)
+__global__ void logmel_masked_kernel(const MelP* P, const int16_t* pcm, const int32_t* ids, int B, uint8_t* state, int stride,
+                                     int prev_off, float* mel, int noise_tail, NoiseP NP, int32_t* is_noise_out,
+                                     int32_t* masked_ids);
 __global__ void noise_update_kernel(NoiseP P, const int32_t* ids, int B, uint8_t* state, const float* mel,
                                     int32_t* is_noise_out, int32_t* masked_ids);
 // Resampler (lyra/resampler.cc): out/in = up/down, coef[phase][tap] oldest tap first (oracle lo_resampler_design)
@@ -147,6 +151,15 @@ __global__ void twin_assemble_kernel(const TwinSlice* slices, int B, const int16
 __global__ void cng_kernel(const MelP* P, unsigned long long seed, const int32_t* ids, int B, uint8_t* state,
                            const uint8_t* noise_state, const float* features, int16_t* pcm);
 __global__ void noise_read_kernel(const int32_t* ids, int B, const uint8_t* state, int field_off, float* out);
+// ---- hop-synchronous packet loss (lossy_kernels.hip, lossy_plan.h; lyra_hip_decode_lossy_dev) -------------------------
+// plan: the per-tick transition of every row; rx_ring_row / pkt_bytes may be null (all received / all packets whole)
+__global__ void lossy_plan_kernel(const int32_t* ids, int B, const int32_t* pkt_bytes, int nbytes, const uint8_t* rx_ring_row,
+                                  uint8_t* cng_state, int32_t* gen_ids, int32_t* cng_ids, int32_t* est_ids, int32_t* info,
+                                  float* feats, unsigned* err);
+// the tick's output hop per row (generative / comfort noise / cross-fade) + is_noise of unreceived rows + is_comfort_noise
+__global__ void lossy_mix_kernel(const int32_t* ids, int B, const int32_t* info, const int16_t* gan, const int16_t* cng,
+                                 const float* fade_w, int16_t* out, const uint8_t* noise_state, int32_t* is_noise,
+                                 int32_t* is_cn);
 size_t logmel_lds_bytes();
 size_t cng_lds_bytes();
 struct ResetP { int8_t e_r2_1, e_r2_2, e_d2, e_bott, d_r0_0, d_r0_1, d_r0_2; };

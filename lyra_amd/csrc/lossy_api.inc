@@ -1,0 +1,138 @@
+// lossy_api.inc -- part of api.hip: lyra_hip_decode_lossy_dev, LyraDecoder::SetEncodedPacket (when a packet arrived) +
+// DecodeSamples(one hop) for hop-synchronous receivers, with the reference's packet-loss concealment, comfort noise and
+// cross-fades (lyra_decoder.cc:172-373) run on the device.  The per-stream control state (concealment / fade progress,
+// fade direction) is one word in the stream's comfort-noise slot (lossy_plan.h).  One tick is
+//   decode stream: rvq_decode of the packet rows -> lossy_plan_kernel (transition, id lists, zero features of the rows
+//                  that conceal) -> the decoder chain on the generative list (TileCtx: id -1 writes no state, no output);
+//   noise stream:  cng_kernel on the comfort-noise list (reads the estimate BEFORE this tick's update) -> lossy_mix_kernel
+//                  -> the decoder-side NoiseEstimator on the received rows' generative hop -> the output resampler,
+// the noise-stream half being ONE noise call as in noise_and_resample_deferred (lyra_hip_run_steps_dev's decoder legs).
+
+namespace {
+
+void lossy_free(lyra_hip_ctx* c) {
+  void* ps[] = {c->d_lossy_ids[0], c->d_lossy_ids[1], c->d_lossy_info[0], c->d_lossy_info[1], c->d_lossy_gan[0],
+                c->d_lossy_gan[1], c->d_lossy_cng, c->d_lossy_feat, c->d_lossy_fade, c->d_lossy_err};
+  for (void* p : ps)
+    if (p) (void)hipFree(p);
+  for (int i = 0; i < 2; ++i) { c->d_lossy_ids[i] = nullptr; c->d_lossy_info[i] = nullptr; c->d_lossy_gan[i] = nullptr; }
+  c->d_lossy_cng = nullptr; c->d_lossy_feat = nullptr; c->d_lossy_fade = nullptr; c->d_lossy_err = nullptr;
+  c->lossy_cap = 0;
+}
+
+int lossy_ensure(lyra_hip_ctx* c, int B) {
+  if (!c->d_lossy_fade) {
+    const std::vector<float> w = fade_weights();
+    HIPCHK(c, dalloc(&c->d_lossy_fade, w.size()));
+    HIPCHK(c, dalloc(&c->d_lossy_err, 1));
+    HIPCHK(c, hipMemcpy(c->d_lossy_fade, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(c->d_lossy_err, 0, 4));
+  }
+  if (B <= c->lossy_cap) return 0;
+  int rc = sync_all(c);   // (the buffers of the calls in flight)
+  if (rc) return rc;
+  void* keep[] = {c->d_lossy_fade, c->d_lossy_err};
+  c->d_lossy_fade = nullptr; c->d_lossy_err = nullptr;
+  lossy_free(c);
+  c->d_lossy_fade = (float*)keep[0]; c->d_lossy_err = (unsigned*)keep[1];
+  const size_t n = (size_t)B;
+  for (int i = 0; i < 2; ++i) {
+    HIPCHK(c, dalloc(&c->d_lossy_ids[i], 3 * n));
+    HIPCHK(c, dalloc(&c->d_lossy_info[i], n));
+    HIPCHK(c, dalloc(&c->d_lossy_gan[i], n * 320));
+  }
+  HIPCHK(c, dalloc(&c->d_lossy_cng, n * 320));
+  HIPCHK(c, dalloc(&c->d_lossy_feat, n * 64));
+  c->lossy_cap = B;
+  return 0;
+}
+
+// One tick of B streams.  d_pkt_bytes / d_rx may be null (every packet whole / every row received).
+int lossy_tick_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_packets, const int32_t* d_pkt_bytes,
+                      const uint8_t* d_rx, int num_bits, int ext, int16_t* d_pcm16, int16_t* d_pcm_ext, int32_t* d_is_noise,
+                      int32_t* d_is_cn) {
+  DEVSCOPE(c);
+  int rc = ensure_scratch(c, B);
+  if (rc) return rc;
+  if ((rc = lossy_ensure(c, B))) return rc;
+  const int set = (int)(c->n_lossy_calls & 1);
+  const size_t cap = (size_t)c->lossy_cap;
+  int32_t* gen_ids = c->d_lossy_ids[set];
+  int32_t* cng_ids = gen_ids + cap;
+  int32_t* est_ids = gen_ids + 2 * cap;
+  int32_t* info = c->d_lossy_info[set];
+  int16_t* gan = c->d_lossy_gan[set];
+  // ---- decode stream: one unsplit decode-side call (on split contexts it stands for every chunk, dec_side_done) ----
+  if ((rc = dec_side_begin(c, 0, 1))) return rc;
+  if ((rc = launch_rvq_decode(c, 0, B, nullptr, d_packets, num_bits / 4, c->d_lossy_feat))) return rc;
+  hipLaunchKernelGGL(lossy_plan_kernel, dim3(cdiv(B, 256)), dim3(256), 0, c->sd[0], d_ids, B, d_pkt_bytes, (num_bits + 7) / 8,
+                     d_rx, c->sm.base[st::R_CNG], gen_ids, cng_ids, est_ids, info, c->d_lossy_feat, c->d_lossy_err);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = launch_generate(c, 0, 0, gen_ids, B, c->d_lossy_feat, gan))) return rc;
+  if ((rc = dec_side_done(c, 0, 1))) return rc;
+  c->n_dec_calls++;
+  // ---- noise stream: comfort noise, mix, estimator, resampler as ONE noise call --------------------------------------
+  if ((rc = noise_dev_begin(c))) return rc;
+  { ProfScope ps(c, K_CNG, c->sn);
+    hipLaunchKernelGGL(cng_kernel, dim3(B), dim3(256), cng_lds_bytes(), c->sn, c->model.d_mel, c->cng_seed, cng_ids, B,
+                       c->sm.base[st::R_CNG], (const uint8_t*)c->sm.base[st::R_NOISE_D], (const float*)nullptr, c->d_lossy_cng); }
+  hipLaunchKernelGGL(lossy_mix_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sn, d_ids, B, (const int32_t*)info,
+                     (const int16_t*)gan, (const int16_t*)c->d_lossy_cng, (const float*)c->d_lossy_fade, d_pcm16,
+                     (const uint8_t*)c->sm.base[st::R_NOISE_D], d_is_noise, d_is_cn);
+  HIPCHK(c, hipGetLastError());
+  { ProfScope ps(c, K_NOISE, c->sn);   // launch_noise on the received rows only (lyra_decoder.cc:304-311)
+    hipLaunchKernelGGL(logmel_masked_kernel, dim3(cdiv(B, 2)), dim3(256), logmel_lds_bytes(), c->sn, c->model.d_mel_rate[1],
+                       (const int16_t*)gan, (const int32_t*)est_ids, B, c->sm.base[st::R_NOISE_D], (int)st::NOISE_BYTES,
+                       (int)st::N_PREV, (float*)nullptr, 1, noise_params(16000), d_is_noise, (int32_t*)nullptr); }
+  HIPCHK(c, hipGetLastError());
+  if (ext != 16000) {
+    if ((rc = launch_resample(c, 1, d_ids, B, d_pcm16, 320, 16000, ext, d_pcm_ext, nullptr, 0, 0, c->sn))) return rc;
+    c->rs_sn_pending = true;
+  }
+  if ((rc = noise_dev_done(c))) return rc;
+  c->n_lossy_calls++;
+  if (c->serial) {   // strict call order: the decode-side call ends with its noise-stream half
+    HIPCHK(c, hipStreamWaitEvent(c->sd[0], c->ev_noise[(c->n_noise_calls - 1) & 1], 0));
+    const int slot = (int)((c->n_dec_calls - 1) & 1);
+    for (int j = 0; j < c->nsub; ++j) HIPCHK(c, hipEventRecord(c->ev_dec[slot][j], c->sd[0]));
+    if (c->nsub == 1) c->noise_done_dec = c->n_noise_calls;
+  }
+  return 0;
+}
+
+int check_rate(lyra_hip_ctx* c, int rate) {
+  if (rate != 8000 && rate != 16000 && rate != 32000 && rate != 48000)
+    return fail(c, LYRA_HIP_EINVAL, "sample rate %d Hz is not supported by the codec (lyra_config.h:57)", rate);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lyra_hip_decode_lossy_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_packets,
+                              const int32_t* d_packet_bytes, int num_bits, int sample_rate_hz, int16_t* d_pcm16,
+                              int16_t* d_pcm_ext, int32_t* d_is_noise, int32_t* d_is_comfort_noise) {
+  int rc = check_batch(c, B);
+  if (rc) return rc;
+  if ((rc = check_bits(c, num_bits))) return rc;
+  if ((rc = check_rate(c, sample_rate_hz))) return rc;
+  if (!d_ids || !d_packets || !d_packet_bytes || !d_pcm16 || (sample_rate_hz != 16000 && !d_pcm_ext))
+    return fail(c, LYRA_HIP_EINVAL, "decode_lossy: null pointer");
+  return lossy_tick_launch(c, d_ids, B, d_packets, d_packet_bytes, nullptr, num_bits, sample_rate_hz, d_pcm16, d_pcm_ext,
+                           d_is_noise, d_is_comfort_noise);
+}
+
+long lyra_hip_decode_lossy_errors(lyra_hip_ctx* c, int clear) {
+  if (!c) return LYRA_HIP_EINVAL;
+  if (!c->d_lossy_err) return 0;
+  DEVSCOPE(c);
+  int rc = sync_all(c);
+  if (rc) return rc;
+  unsigned n = 0;
+  HIPCHK(c, hipMemcpy(&n, c->d_lossy_err, 4, hipMemcpyDeviceToHost));
+  if (clear) HIPCHK(c, hipMemset(c->d_lossy_err, 0, 4));
+  return (long)n;
+}
+
+}  // extern "C"

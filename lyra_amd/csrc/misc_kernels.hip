@@ -477,13 +477,15 @@ __device__ __forceinline__ int digit_reverse4_1024(int n) {   // reverse the fiv
 // noise_tail != 0: `state` is a NoiseEstimator region and the kernel goes on with NoiseEstimator::ReceiveSamples' second
 // half (noise_update_wave; wavefront f handles frame f) on the mel vector while it is still in LDS -- one launch and no
 // trip of the 160 bins through HBM (`mel` may then be null).
-__global__ __launch_bounds__(256) void logmel_kernel(const MelP* __restrict__ Pp, const int16_t* __restrict__ pcm,
-                                                      const int32_t* __restrict__ ids, int B,
-                                                      uint8_t* __restrict__ state, int stride, int prev_off,
-                                                      float* __restrict__ mel, int noise_tail, NoiseP NP,
-                                                      int32_t* __restrict__ is_noise_out,
-                                                      int32_t* __restrict__ masked_ids) {
-  LYRA_STRESS(7);
+// kMasked (logmel_masked_kernel): an id of -1 masks its row -- no history, no estimator, no output is touched (the decoder-
+// side estimator of lyra_hip_decode_lossy_dev runs only on the received rows of a tick).
+template <bool kMasked>
+__device__ __forceinline__ void logmel_body(const MelP* __restrict__ Pp, const int16_t* __restrict__ pcm,
+                                            const int32_t* __restrict__ ids, int B,
+                                            uint8_t* __restrict__ state, int stride, int prev_off,
+                                            float* __restrict__ mel, int noise_tail, NoiseP NP,
+                                            int32_t* __restrict__ is_noise_out,
+                                            int32_t* __restrict__ masked_ids) {
   typedef double f64x2 __attribute__((ext_vector_type(2)));
   const MelP& P = *Pp;
   extern __shared__ __attribute__((aligned(16))) double dsm[];
@@ -495,8 +497,16 @@ __global__ __launch_bounds__(256) void logmel_kernel(const MelP* __restrict__ Pp
   float* tail_sh = reinterpret_cast<float*>(dsm + 1540 + 160);
   float* tail_avg = reinterpret_cast<float*>(dsm + 1540 + 160 + 320);
   const int tid = threadIdx.x;
-  const int b0 = blockIdx.x * 2, b1 = b0 + 1;
-  const bool two = b1 < B;
+  int b0_ = blockIdx.x * 2;
+  bool two_ = b0_ + 1 < B;
+  if constexpr (kMasked) {   // a masked first row hands its place to the second one (out_index follows b0)
+    const bool ok0 = ids[b0_] >= 0, ok1 = two_ && ids[b0_ + 1] >= 0;
+    if (!ok0 && !ok1) return;   // (workgroup-uniform, before any barrier)
+    if (!ok0) b0_ += 1;
+    two_ = ok0 && ok1;
+  }
+  const int b0 = b0_, b1 = b0 + 1;
+  const bool two = two_;
   if constexpr ((LYRA_MEL_ABL & 16) != 0) return;
   LYRA_TSTAMP(110);
   int16_t* prev0 = reinterpret_cast<int16_t*>(state + (size_t)ids[b0] * stride + prev_off);
@@ -632,6 +642,25 @@ __global__ __launch_bounds__(256) void logmel_kernel(const MelP* __restrict__ Pp
                          is_noise_out, masked_ids);
   }
   LYRA_TSTAMP(119);
+}
+
+__global__ __launch_bounds__(256) void logmel_kernel(const MelP* __restrict__ Pp, const int16_t* __restrict__ pcm,
+                                                      const int32_t* __restrict__ ids, int B,
+                                                      uint8_t* __restrict__ state, int stride, int prev_off,
+                                                      float* __restrict__ mel, int noise_tail, NoiseP NP,
+                                                      int32_t* __restrict__ is_noise_out,
+                                                      int32_t* __restrict__ masked_ids) {
+  LYRA_STRESS(7);
+  logmel_body<false>(Pp, pcm, ids, B, state, stride, prev_off, mel, noise_tail, NP, is_noise_out, masked_ids);
+}
+__global__ __launch_bounds__(256) void logmel_masked_kernel(const MelP* __restrict__ Pp, const int16_t* __restrict__ pcm,
+                                                             const int32_t* __restrict__ ids, int B,
+                                                             uint8_t* __restrict__ state, int stride, int prev_off,
+                                                             float* __restrict__ mel, int noise_tail, NoiseP NP,
+                                                             int32_t* __restrict__ is_noise_out,
+                                                             int32_t* __restrict__ masked_ids) {
+  LYRA_STRESS(7);
+  logmel_body<true>(Pp, pcm, ids, B, state, stride, prev_off, mel, noise_tail, NP, is_noise_out, masked_ids);
 }
 
 // =============================================================================================
@@ -958,6 +987,7 @@ __global__ __launch_bounds__(256) void cng_kernel(const MelP* __restrict__ Pp, u
   double* mel = dsm + 2048;   // [160], then unused
   const int tid = threadIdx.x, b = blockIdx.x;
   const int id = ids[b];
+  if (id < 0) return;   // masked row (lyra_hip_decode_lossy_dev: no comfort noise this tick): no output, no hop advance
   uint8_t* slot = state + (size_t)id * st::CNG_BYTES;
   const unsigned long long hop = *reinterpret_cast<const unsigned long long*>(slot + st::C_HOP);
   double* ola = reinterpret_cast<double*>(slot + st::C_OLA);

@@ -100,6 +100,7 @@ constexpr int RS_BYTES = align256(RS_HIST + (RS_TAPS - 1) * 4);
 
 // ---- R_CNG: ComfortNoiseGenerator (lyra/comfort_noise_generator.h): overlap-add tail of the inverse STFT --------------
 constexpr int C_HOP = 0;                           // uint64: hops generated (random-phase counter)
+// bytes 8..11: the packet-loss control word of lyra_hip_decode_lossy_dev (lossy_plan.h LOSSY_CTL; 0 = initial state)
 constexpr int C_OLA = 64;                          // f64[1024] overlap-add accumulator, [0, 320) = next hop
 constexpr int CNG_BYTES = align256(C_OLA + 1024 * 8);
 

@@ -24,6 +24,19 @@ void twin_free(lyra_hip_ctx* c) {
   c->twin_out_n = 0;
 }
 
+// MaybeOverlapAndInsert's cross-fade weight for fade_progress TWIN_FADE_LO + i (also lyra_hip_decode_lossy_dev's mix)
+std::vector<float> fade_weights() {
+  std::vector<float> w((size_t)TWIN_FADE_N);
+  const int kFadeDurationSamples = 640;   // GetFadeDurationSamples (lyra_decoder.cc:53-62)
+  for (int i = 0; i < TWIN_FADE_N; ++i) {
+    const int fade_progress = TWIN_FADE_LO + i;
+    // the expression of MaybeOverlapAndInsert (lyra_decoder.cc:364-365), evaluated as C++ evaluates it there
+    const float overlap_weight = (1.f + std::cos(fade_progress * M_PI / kFadeDurationSamples)) / 2.f;
+    w[(size_t)i] = overlap_weight;
+  }
+  return w;
+}
+
 int twin_ensure(lyra_hip_ctx* c) {
   if (c->d_twin_gan) return 0;
   const size_t n = (size_t)c->max_streams;
@@ -37,14 +50,7 @@ int twin_ensure(lyra_hip_ctx* c) {
   HIPCHK(c, hipHostMalloc((void**)&c->h_twin_args, c->twin_args_cap, hipHostMallocDefault));
   std::vector<int32_t> iota(n);
   for (size_t i = 0; i < n; ++i) iota[i] = (int32_t)i;
-  std::vector<float> w((size_t)TWIN_FADE_N);
-  const int kFadeDurationSamples = 640;   // GetFadeDurationSamples (lyra_decoder.cc:53-62)
-  for (int i = 0; i < TWIN_FADE_N; ++i) {
-    const int fade_progress = TWIN_FADE_LO + i;
-    // the expression of MaybeOverlapAndInsert (lyra_decoder.cc:364-365), evaluated as C++ evaluates it there
-    const float overlap_weight = (1.f + std::cos(fade_progress * M_PI / kFadeDurationSamples)) / 2.f;
-    w[(size_t)i] = overlap_weight;
-  }
+  const std::vector<float> w = fade_weights();
   HIPCHK(c, hipMemcpy(c->d_twin_iota, iota.data(), n * 4, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->d_twin_fade, w.data(), w.size() * 4, hipMemcpyHostToDevice));
   return 0;
