@@ -16,6 +16,12 @@ FADE = 640          # GetFadeDurationSamples (lyra_decoder.cc:53-62)
 TO_CNG, FROM_CNG = 1, -1
 
 
+def fade_weight(fade_progress):
+    """MaybeOverlapAndInsert's overlap weight (lyra_decoder.cc:364-365), (1.f + std::cos(double)) / 2.f: the sum and
+    the division are double (the float literals are promoted), and the float variable takes the result, rounded once."""
+    return np.float32((1.0 + math.cos(fade_progress * math.pi / FADE)) / 2.0)
+
+
 class OracleKit:
     """The components the two classes below are assembled from: the oracle's (default), or stand-ins with the same
     interface (tests/host_stub/fake_kit.py, for the CPU test of the C++ twins' host logic)."""
@@ -109,6 +115,12 @@ class RefLyraDecoder:
         self.leftover = np.zeros(0, np.int16)
         self.concealment, self.fade, self.fade_dir = 0, 0, FROM_CNG
         self.noise_buf = np.zeros(0, np.int16)
+        # what the last DecodeSamples call did (for tests that classify the samples they compare): the internal 16 kHz
+        # samples it produced, and per pass of the loop (gen_n, cng_n, fade, fade_dir) -- the samples of the generative
+        # model and of the comfort-noise generator, and the fade progress / direction a cross-fade starts from
+        self.last_internal = np.zeros(0, np.int16)
+        self.last_segments = []
+        self.is_noise = True            # the decoder-side estimator's is_noise(): true until it has received a hop
 
     def SetEncodedPacket(self, packet):
         packet = np.asarray(packet, np.uint8)
@@ -155,6 +167,7 @@ class RefLyraDecoder:
 
     def _internal(self, total):
         result = []
+        self.last_segments = []
         done = 0
         while done < total:
             n = self._n_to_generate(total, done)
@@ -185,16 +198,18 @@ class RefLyraDecoder:
                 fade = self.fade
                 mixed = np.empty(n, np.int16)
                 for i in range(n):
-                    w = np.float32((np.float32(1.0) + math.cos(fade * math.pi / FADE)) / np.float32(2.0))
+                    w = fade_weight(fade)
                     v = np.float32(np.float32(audio[i]) * w) + np.float32(np.float32(noise[i]) * np.float32(np.float32(1.0) - w))
                     mixed[i] = np.int16(np.trunc(np.float32(v)))
                     fade += self.fade_dir
                 result.append(mixed)
+            self.last_segments.append((gen_n, cng_n, self.fade, self.fade_dir))
             self.fade = next_fade
             if received:
                 self.noise_buf = np.concatenate([self.noise_buf, audio])
                 if self.noise_buf.size == HOP:
-                    self.noise.ReceiveSamples(self.noise_buf)
+                    self.is_noise = bool(self.noise.ReceiveSamples(self.noise_buf)[0])
                     self.noise_buf = np.zeros(0, np.int16)
             done += n
-        return np.concatenate(result) if result else np.zeros(0, np.int16)
+        self.last_internal = np.concatenate(result) if result else np.zeros(0, np.int16)
+        return self.last_internal

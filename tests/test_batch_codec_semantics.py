@@ -2,8 +2,9 @@
 lyra/lyra_encoder.cc:113-156, lyra/lyra_decoder.cc:172-373): resampling, DTX, packet queueing, DecodeSamples(n) that
 straddles hops, packet-loss concealment, comfort noise, cross-fades.  The C++ twins run on the GPU through the C ABI
 (lyra_amd/decoder_demo); the expectation is oracle/lyra_codec_model.py, the per-stream restatement of the reference's
-classes over the CPU oracle.  Packets bit-exact; PCM bit-exact wherever only the generative model speaks, within 2 LSB
-where comfort noise is mixed in (device fp64 sin/cos/exp vs host libm, see test_resampler_cng.py)."""
+classes over the CPU oracle.  Packets bit-exact; PCM bit-exact wherever only the generative model speaks, within 1 LSB
+where comfort noise is mixed in (device fp64 sin/cos/exp vs host libm, see test_resampler_cng.py), within 2 LSB at the
+other rates where such a sample lies in the output resampler's window (test_gpu_lossy_decode.py: Tally, CnReach)."""
 import os
 import subprocess
 
@@ -64,6 +65,7 @@ def _run_session(tmp_path, oracle, rate, bitrate, dtx, pcm, script, demo=None, p
                                               (16000, 9200, True), (32000, 6000, True)])
 def test_batch_codec_session_vs_reference_model(tmp_path, golden_dir, oracle_default, rate, bitrate, dtx):
     from oracle import lyra_codec_model as M
+    from test_gpu_lossy_decode import CnReach, Tally
     from oracle import lyra_oracle
     bits = {3200: 64, 6000: 120, 9200: 184}[bitrate]
     speech = np.load(os.path.join(golden_dir, "sample_wavs.npz"))["sample1_16kHz"]
@@ -89,9 +91,9 @@ def test_batch_codec_session_vs_reference_model(tmp_path, golden_dir, oracle_def
 
     encs = [M.RefLyraEncoder(oracle_default, rate, bits, dtx) for _ in range(n)]
     decs = [M.RefLyraDecoder(oracle_default, rate, cng_seed=0x4C797261 ^ s) for s in range(n)]
+    reach = [CnReach(rate) for _ in range(n)]
+    tally = Tally(cn_lsb=1 if rate == 16000 else 2)
     pos = 0
-    n_exact = n_total = 0
-    worst = 0
     saw_cng = False
     for t, (mask, sizes) in enumerate(script):
         for s in range(n):
@@ -106,13 +108,11 @@ def test_batch_codec_session_vs_reference_model(tmp_path, golden_dir, oracle_def
             pos += n * k
             for s in range(n):
                 want = decs[s].DecodeSamples(k)
-                d = np.abs(got[s].astype(int) - want.astype(int))
-                worst = max(worst, int(d.max()))
-                n_exact += int((d == 0).sum()); n_total += k
+                tally.check(got[s], want, reach[s](decs[s], k), f"tick {t}, stream {s}, DecodeSamples({k})")
                 saw_cng = saw_cng or decs[s].is_comfort_noise()
     assert pos == out.size
-    assert worst <= 2, worst
-    assert n_exact / n_total > 0.97
+    tally.report(f"BatchLyraDecoder session {rate} Hz")
+    assert tally.exact_fraction() > 0.97
     assert saw_cng                      # the 9-packet burst takes stream 0 all the way into comfort noise
     if dtx:
         assert (lengths == 0).sum() > 5   # the silent stretch is sent as empty packets

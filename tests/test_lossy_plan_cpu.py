@@ -87,3 +87,43 @@ def test_lossy_transition_matches_reference_model(tmp_path, rate):
             seen_back += int(prev_cn and not cn)
             prev_cn = bool(cn)
     assert seen_cn > 0 and seen_back > 0       # the scripts reach pure comfort noise and come back from it
+
+
+_WEIGHTS = r'''
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+// the cross-fade weight as a float variable initialised from the C++ expression, for fade progress -640 .. 1280
+int main() {
+  for (int f = -640; f <= 1280; ++f) {
+    const float w = (1.f + std::cos(f * M_PI / 640)) / 2.f;
+    uint32_t u;
+    std::memcpy(&u, &w, 4);
+    std::printf("%u\n", u);
+  }
+  return 0;
+}
+'''
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
+def test_fade_weight_is_the_cpp_expression(tmp_path):
+    """oracle/lyra_codec_model.fade_weight (the model's cross-fade) against the overlap weight of MaybeOverlapAndInsert
+    (lyra_decoder.cc:364-365) as a C++ compiler evaluates it -- in double, rounded to float once -- bit for bit over every
+    fade progress the decoder can reach and beyond.  The float32 evaluation NumPy 2 gives np.float32(1) + math.cos(..)
+    is off by one ulp in about a third of them; the check must see that."""
+    from oracle import lyra_codec_model as M
+    import math
+    src, exe = tmp_path / "w.cc", tmp_path / "w"
+    src.write_text(_WEIGHTS)
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", str(src), "-o", str(exe)], timeout=120)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr
+    want = np.array(r.stdout.split(), np.uint32).view(np.float32)
+    f = np.arange(-640, 1281)
+    assert want.size == f.size
+    got = np.array([M.fade_weight(int(x)) for x in f], np.float32)
+    assert got.view(np.uint32).tolist() == want.view(np.uint32).tolist()
+    single = np.array([np.float32((np.float32(1.0) + math.cos(x * math.pi / 640)) / np.float32(2.0)) for x in f], np.float32)
+    assert (single.view(np.uint32) != want.view(np.uint32)).sum() > 100      # the test tells the two apart
