@@ -133,7 +133,7 @@ typedef struct lyra_hip_ctx lyra_hip_ctx;
  * layer shapes the kernels are specialised to): a truncated or foreign file
  * gives LYRA_HIP_EMODEL.
  * Developer switches read from the environment here (results are bit-identical
- * either way; each exists for an A/B recorded in DESIGN.md):
+ * either way):
  *   LYRA_HIP_SUBBATCHES=<n>  split every `_dev` call into n sub-batches on stream
  *                            sets of their own (pays when only one side is driven:
  *                            decode-only at B = 8192 +6 % with n = 2; default 1).
@@ -145,23 +145,13 @@ typedef struct lyra_hip_ctx lyra_hip_ctx;
  *                            stages 1 + 2 as one launch, bit 3: decoder stages 0 + 1 (all slower at
  *                            B = 4096; default 0);
  *   LYRA_HIP_RVQ_WIDE=1      the 104 KB / 244-VGPR quantizer kernel;
- *   LYRA_HIP_FLAT_PRIO=1     all library streams at the same priority;
- *   LYRA_HIP_EVENT_FENCE=1   internal events with system-scope fences;
- *   LYRA_HIP_NO_CODE_WARM=1  skip the stage kernels' instruction pre-fetch;
  *   LYRA_HIP_CU_MASKS=e,d,q,n  CU-mask patterns (32-bit hex, repeated over the chip) of the encode / decode / quantizer /
  *                            noise streams; 0 = no mask (default: 00ff00ff,ff00ff00,00ff00ff,ff00ff00 when
  *                            max_streams <= 1024, none above);
  *   LYRA_HIP_PRIO=e,d,q      stream priorities of the encode / decode / quantizer streams (0 lowest .. 2 highest;
  *                            default 0,0,2: the two chains equal, the small quantizer first; 0,2,0 = rounds 2-3:
  *                            decoder chain first -- better for blocking decode calls beside an encoder, bimodal for the `_dev` pipeline);
- *   LYRA_HIP_TILE_DIV_<K>=k  launch stage kernel K (ENC_S0 .. DEC_S2) as k slices of its tiles,
- *   LYRA_HIP_LDS_PAD_<K>=b   give its workgroups b extra bytes of LDS (occupancy experiments; K also logmel_noise, resample);
- *   read by lyra_hip_run_steps_dev (profiles/r06_modes_timelines.txt):
- *   LYRA_HIP_RS_LEAD=1       the input resampler one hop ahead of the extractor instead of two;
- *   LYRA_HIP_RS_OUT_ON_CHAIN_SPLIT=1  on contexts that split batches: the output resampler on the decode streams (old form);
- *   LYRA_HIP_SPLIT_SN_CALLS=1  a hop's decoder-side NoiseEstimator and output resampler as two noise-stream calls
- *                            instead of one (the form before round 6's last session: the quantizer of hop i then
- *                            waits for the estimator of hop i - 1). */
+ *   LYRA_HIP_TILE_DIV_<K>=k  launch stage kernel K (ENC_S0 .. DEC_S2) as k slices of its tiles. */
 /* max_streams: 1 .. 289,262 per context (per-stream state is addressed with 32-bit byte offsets; 83 KB of state per stream,
  * so that is 24 GB of the 288 -- more streams: more contexts). */
 int lyra_hip_create(const char* model_dir, int device, int max_streams, int requant_mode, lyra_hip_ctx** out);

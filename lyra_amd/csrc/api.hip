@@ -72,8 +72,9 @@ struct lyra_hip_ctx {
   int32_t* d_ids = nullptr;      // encode-side staging of host ids
   int32_t* d_ids_dec = nullptr;  // decode-side staging of host ids
   int16_t* d_pcm_in = nullptr;
-  static constexpr int RS_RING = 3;
-  int16_t* d_rs16[RS_RING] = {};  // run_steps: the input resampler's 16 kHz hops, by step mod 3 (resample_in_ahead: two hops ahead)
+  static constexpr int RS_LEAD = 2;               // run_steps: the input resampler runs this many hops ahead (resample_in_ahead) ...
+  static constexpr int RS_RING = RS_LEAD + 1;     // ... into a ring of the hops in flight
+  int16_t* d_rs16[RS_RING] = {};  // run_steps: the input resampler's 16 kHz hops, by step mod RS_RING
   hipEvent_t ev_rs_in[RS_RING] = {};   // ... and the end of the launch that filled each
   hipEvent_t ev_ahead_order = nullptr, ev_ahead_last = nullptr;
   // sub-batches (nsub > 1) only: a call that is split differently from the previous call of its side joins that call's
@@ -129,7 +130,7 @@ struct lyra_hip_ctx {
   long n_lossy_calls = 0;
   // Small host-buffer calls (the per-object plugin contract: B = 1 per blocking call) skip the copy engine: the kernels read
   // their input from and write their output to this pinned, device-mapped arena directly -- three copy packets and their
-  // stream bubbles fewer per call (lyra_amd/plugin_demo --bench).  ZC_MAX streams per call; LYRA_HIP_NO_ZEROCOPY=1 turns it off.
+  // stream bubbles fewer per call (lyra_amd/plugin_demo --bench).  ZC_MAX streams per call.
   static constexpr int ZC_MAX = 16;
   static constexpr size_t ZC_IDS = 0, ZC_IN = 256, ZC_OUT = 256 + ZC_MAX * 640, ZC_BYTES = 256 + 2 * ZC_MAX * 640;
   uint8_t* h_zc = nullptr;
@@ -137,7 +138,6 @@ struct lyra_hip_ctx {
   uint8_t* d_twin_args = nullptr;
   size_t twin_args_cap = 0, twin_args_used = 0;
   void* pipe = nullptr;            // PipeState (pipe_api.inc): the two-deep pipelined host-buffer calls, created on first use
-  size_t lds_pad[6] = {};          // experiment hook, see lds_pad()
   int tile_div[6] = {1, 1, 1, 1, 1, 1};   // tiles per workgroup of each stage kernel (LYRA_TILE_LOOP), see tile_div()
   bool chunk_local = false;                       // see wait_encode_side
   bool ids_stable = false;                        // inside lyra_hip_run_steps_dev, after its first step: see enc_cross_begin
@@ -287,15 +287,6 @@ hipError_t make_stream_kind(lyra_hip_ctx* c, hipStream_t* s, int kind, int prior
   return hipStreamCreateWithPriority(s, hipStreamNonBlocking, priority);
 }
 
-// EXPERIMENT hook (occupancy): LYRA_HIP_LDS_PAD_<kernel>=bytes asks for that much extra dynamic LDS per workgroup of a
-// stage kernel, i.e. fewer of its workgroups per CU and more room for the kernel running beside it.
-inline size_t lds_pad(const char* kernel) {
-  char name[64];
-  snprintf(name, sizeof name, "LYRA_HIP_LDS_PAD_%s", kernel);
-  const char* v = getenv(name);
-  return v ? (size_t)atol(v) : 0;
-}
-
 // LYRA_HIP_TILE_DIV_<kernel>=k launches a stage kernel as k back-to-back slices of 1/k of its tiles each (tile0 = first
 // tile of the slice): at any time the kernel holds at most 1/k of the CUs' LDS and wave slots, the rest stays free for
 // the other chain's kernel.
@@ -314,10 +305,8 @@ const CodeSize kCodeSizes[] = {
     {"", 0, 0}};
 // What a kernel is told to warm: from the 128-byte line of its s_getpc to the end of the function.  The offset of that
 // instruction is read back from the kernel object at build time (code_sizes.sh), so the range ends inside the function
-// wherever the compiler scheduled the s_getpc; disabled with LYRA_HIP_NO_CODE_WARM=1
+// wherever the compiler scheduled the s_getpc
 int code_warm_bytes(const char* kernel) {
-  static const bool off = getenv("LYRA_HIP_NO_CODE_WARM") != nullptr;
-  if (off) return 0;
   for (const CodeSize& c : kCodeSizes)
     if (strcmp(c.name, kernel) == 0) return c.bytes > 2048 && c.bytes > c.getpc ? c.bytes - c.getpc : 0;
   return 0;
@@ -414,9 +403,6 @@ int encq_begin(lyra_hip_ctx* c, int k, int nk_now = 1) {
 struct EventList { hipEvent_t e[lyra_hip_ctx::KMAX]; int n = 0; };
 EventList encq_buffer_free(lyra_hip_ctx* c, int k, int nk_now) {
   EventList l;
-#ifdef LYRA_ABL_NO_FEAT_WAIT   // TIMING-ONLY ablation (a race): the extractor's last stage does not wait -- what a deeper feature ring
-  return l;                    // with one wait per several steps could return at most (profiles/r06_ab_t1_featwait.txt)
-#endif
   if (c->n_encq_calls < 2) return l;
   const int p = (int)(c->n_encq_calls & 1), nk_then = c->encq_nk[p];
   if (nk_then == nk_now) { l.e[l.n++] = c->ev_encs[p][k]; return l; }
@@ -563,7 +549,7 @@ int launch_extract(lyra_hip_ctx* c, int k, int lo, const int32_t* d_ids, int B, 
 #endif
   { ProfScope ps(c, K_ENC_S0, st_);
     for (int nt = cdiv(B, enc_s0_streams_per_wg()), g = cdiv(nt, c->tile_div[0]), t0 = 0; t0 < nt; t0 += g)
-      hipLaunchKernelGGL(enc_s0_kernel, dim3(std::min(g, nt - t0)), dim3(enc_s0_threads()), enc_s0_lds_bytes() + c->lds_pad[0], st_,
+      hipLaunchKernelGGL(enc_s0_kernel, dim3(std::min(g, nt - t0)), dim3(enc_s0_threads()), enc_s0_lds_bytes(), st_,
                          M.d_enc0, d_pcm, d_ids, B, c->sm.base[st::R_E0], e0, c->cw[K_ENC_S0], t0); }
 #ifdef LYRA_PARKED
   if ((c->fused & 4) && c->mode == 2) {   // stages 1 + 2 in one launch
@@ -578,13 +564,13 @@ int launch_extract(lyra_hip_ctx* c, int k, int lo, const int32_t* d_ids, int B, 
 #endif
   { ProfScope ps(c, K_ENC_S1, st_);
     for (int nt = cdiv(B, enc_s1_streams_per_wg()), g = cdiv(nt, c->tile_div[1]), t0 = 0; t0 < nt; t0 += g)
-      hipLaunchKernelGGL(enc_s1_kernel, dim3(std::min(g, nt - t0)), dim3(enc_s1_threads()), enc_s1_lds_bytes() + c->lds_pad[1], st_,
+      hipLaunchKernelGGL(enc_s1_kernel, dim3(std::min(g, nt - t0)), dim3(enc_s1_threads()), enc_s1_lds_bytes(), st_,
                          M.d_enc1, e0, d_ids, B, c->sm.base[st::R_E1], e1, c->cw[K_ENC_S1], t0); }
   for (int i = 0; i < before_s2.n; ++i) HIPCHK(c, hipStreamWaitEvent(st_, before_s2.e[i], 0));
   { ProfScope ps(c, K_ENC_S2, st_);
     for (int nt = cdiv(B, enc_s2_streams_per_wg()), g = cdiv(nt, c->tile_div[2]), t0 = 0; t0 < nt; t0 += g)
       hipLaunchKernelGGL(c->mode == 2 ? enc_s2_xn_kernel : c->mode == 3 ? enc_s2_bm_kernel : c->mode ? enc_s2_dr_kernel : enc_s2_kernel, dim3(std::min(g, nt - t0)), dim3(512),
-                         enc_s2_lds_bytes() + c->lds_pad[2], st_, M.d_enc2, e1, d_ids, B, c->sm.base[st::R_E2], d_feat, codes,
+                         enc_s2_lds_bytes(), st_, M.d_enc2, e1, d_ids, B, c->sm.base[st::R_E2], d_feat, codes,
                          c->cw[K_ENC_S2], t0); }
   HIPCHK(c, hipGetLastError());
   c->last_B_enc = B;
@@ -641,7 +627,7 @@ int launch_generate(lyra_hip_ctx* c, int k, int lo, const int32_t* d_ids, int B,
       hipLaunchKernelGGL(dec_s01_xn_kernel, dim3(cdiv(B, 8)), dim3(512), dec_s01_lds_bytes(), st_, M.d_dec0, M.d_dec1, d_feat, d_ids, B,
                          c->sm.base[st::R_D0], c->sm.base[st::R_D1], d0, d1, d_pkt, num_stages, M.cb, c->cw[K_DEC_S0]); }
     { ProfScope ps(c, K_DEC_S2, st_);
-      hipLaunchKernelGGL(dec_s2_kernel, dim3(cdiv(B, dec_s2_streams_per_wg())), dim3(dec_s2_threads()), dec_s2_lds_bytes() + c->lds_pad[5], st_,
+      hipLaunchKernelGGL(dec_s2_kernel, dim3(cdiv(B, dec_s2_streams_per_wg())), dim3(dec_s2_threads()), dec_s2_lds_bytes(), st_,
                          M.d_dec2, d1, d_ids, B, c->sm.base[st::R_D2], d_pcm, c->cw[K_DEC_S2], 0); }
     HIPCHK(c, hipGetLastError());
     c->last_B_dec = B;
@@ -651,16 +637,16 @@ int launch_generate(lyra_hip_ctx* c, int k, int lo, const int32_t* d_ids, int B,
   { ProfScope ps(c, K_DEC_S0, st_);
     for (int nt = cdiv(B, dec_s0_streams_per_wg()), g = cdiv(nt, c->tile_div[3]), t0 = 0; t0 < nt; t0 += g)
       hipLaunchKernelGGL(c->mode == 2 ? dec_s0_xn_kernel : c->mode == 3 ? dec_s0_bm_kernel : c->mode ? dec_s0_dr_kernel : dec_s0_kernel, dim3(std::min(g, nt - t0)), dim3(512),
-                         dec_s0_lds_bytes() + c->lds_pad[3], st_,
+                         dec_s0_lds_bytes(), st_,
                          M.d_dec0, d_feat, d_ids, B, c->sm.base[st::R_D0], d0, d_pkt, num_stages, M.cb,
                          c->cw[K_DEC_S0], t0); }
   { ProfScope ps(c, K_DEC_S1, st_);
     for (int nt = cdiv(B, dec_s1_streams_per_wg()), g = cdiv(nt, c->tile_div[4]), t0 = 0; t0 < nt; t0 += g)
-      hipLaunchKernelGGL(dec_s1_kernel, dim3(std::min(g, nt - t0)), dim3(dec_s1_threads()), dec_s1_lds_bytes() + c->lds_pad[4], st_,
+      hipLaunchKernelGGL(dec_s1_kernel, dim3(std::min(g, nt - t0)), dim3(dec_s1_threads()), dec_s1_lds_bytes(), st_,
                          M.d_dec1, d0, d_ids, B, c->sm.base[st::R_D1], d1, c->cw[K_DEC_S1], t0); }
   { ProfScope ps(c, K_DEC_S2, st_);
     for (int nt = cdiv(B, dec_s2_streams_per_wg()), g = cdiv(nt, c->tile_div[5]), t0 = 0; t0 < nt; t0 += g)
-      hipLaunchKernelGGL(dec_s2_kernel, dim3(std::min(g, nt - t0)), dim3(dec_s2_threads()), dec_s2_lds_bytes() + c->lds_pad[5], st_,
+      hipLaunchKernelGGL(dec_s2_kernel, dim3(std::min(g, nt - t0)), dim3(dec_s2_threads()), dec_s2_lds_bytes(), st_,
                          M.d_dec2, d1, d_ids, B, c->sm.base[st::R_D2], d_pcm, c->cw[K_DEC_S2], t0); }
   HIPCHK(c, hipGetLastError());
   c->last_B_dec = B;
@@ -700,8 +686,7 @@ int launch_noise(lyra_hip_ctx* c, int side, hipStream_t st_, const int32_t* d_id
   const int rate = side == 0 ? c->enc_noise_rate : 16000;
   const MelP* melp = c->model.d_mel_rate[rate == 8000 ? 0 : rate == 32000 ? 2 : rate == 48000 ? 3 : 1];
   { ProfScope ps(c, K_NOISE, st_);
-    static const size_t pad = lds_pad("logmel_noise");   // experiment hook (fewer estimator workgroups per CU)
-    hipLaunchKernelGGL(logmel_kernel, dim3(cdiv(B, 2)), dim3(256), logmel_lds_bytes() + pad, st_, melp, d_pcm, d_ids,
+    hipLaunchKernelGGL(logmel_kernel, dim3(cdiv(B, 2)), dim3(256), logmel_lds_bytes(), st_, melp, d_pcm, d_ids,
                        B, region, (int)st::NOISE_BYTES, (int)st::N_PREV, (float*)nullptr, 1,
                        noise_params(rate), d_is_noise, d_masked_ids); }
   HIPCHK(c, hipGetLastError());
@@ -817,13 +802,13 @@ static int create_impl(const char* model_dir, const void* image, size_t image_by
   // frames/s instead of 7.2 M (LYRA_HIP_PRIO=0,2,0 restores the old schedule for such a service).
   int prio_lo = 0, prio_hi = 0;
   if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess) prio_lo = prio_hi = 0;
-  int prio[3] = {prio_lo, prio_lo, getenv("LYRA_HIP_FLAT_PRIO") ? prio_lo : prio_hi};
-  if (const char* p = getenv("LYRA_HIP_PRIO")) {   // experiment hook: "e,d,q" each 0 = lowest .. 2 = highest
+  int prio[3] = {prio_lo, prio_lo, prio_hi};
+  if (const char* p = getenv("LYRA_HIP_PRIO")) {   // "e,d,q" each 0 = lowest .. 2 = highest
     int v[3] = {0, 0, 2};
     sscanf(p, "%d,%d,%d", &v[0], &v[1], &v[2]);
     for (int i = 0; i < 3; ++i) prio[i] = v[i] >= 2 ? prio_hi : (v[i] == 1 ? (prio_lo + prio_hi) / 2 : prio_lo);
   }
-  const unsigned evflags = hipEventDisableTiming | (getenv("LYRA_HIP_EVENT_FENCE") ? 0u : (unsigned)hipEventDisableSystemFence);
+  const unsigned evflags = hipEventDisableTiming | hipEventDisableSystemFence;
   // CU partitioning (placement_probe.hip (a probe of an earlier round, removed since: git history), profiles/history/r04_placement_probe.txt): two concurrent dispatches of <= 256
   // workgroups are placed independently of each other -- of 2 x 128 workgroups 68 CUs get two and 68 none -- and a stage
   // kernel lasts as long as its slowest tile.  Streams created with complementary CU masks keep the chains apart.
@@ -883,11 +868,10 @@ static int create_impl(const char* model_dir, const void* image, size_t image_by
   }
   {
     const char* names[6] = {"ENC_S0", "ENC_S1", "ENC_S2", "DEC_S0", "DEC_S1", "DEC_S2"};
-    for (int i = 0; i < 6; ++i) c->lds_pad[i] = lds_pad(names[i]);
     for (int i = 0; i < 6; ++i) c->tile_div[i] = tile_div(names[i]);
   }
-  if (set_lds(enc_s0_kernel, enc_s0_lds_bytes() + c->lds_pad[0]) != hipSuccess || set_lds(enc_s1_kernel, enc_s1_lds_bytes() + c->lds_pad[1]) != hipSuccess ||
-      set_lds(enc_s2_kernel, enc_s2_lds_bytes() + c->lds_pad[2]) != hipSuccess ||
+  if (set_lds(enc_s0_kernel, enc_s0_lds_bytes()) != hipSuccess || set_lds(enc_s1_kernel, enc_s1_lds_bytes()) != hipSuccess ||
+      set_lds(enc_s2_kernel, enc_s2_lds_bytes()) != hipSuccess ||
 #ifdef LYRA_PARKED
       set_lds(enc_side_kernel, enc_side_lds_bytes()) != hipSuccess ||
       set_lds(enc_side_dr_kernel, enc_side_lds_bytes()) != hipSuccess || set_lds(dec_side_kernel, dec_side_lds_bytes()) != hipSuccess ||
@@ -895,11 +879,11 @@ static int create_impl(const char* model_dir, const void* image, size_t image_by
       set_lds(enc_side_xn_kernel, enc_side_lds_bytes()) != hipSuccess || set_lds(dec_side_xn_kernel, dec_side_lds_bytes()) != hipSuccess ||
       set_lds(enc_s12_xn_kernel, enc_s12_lds_bytes()) != hipSuccess || set_lds(dec_s01_xn_kernel, dec_s01_lds_bytes()) != hipSuccess ||
 #endif
-      set_lds(dec_s0_kernel, dec_s0_lds_bytes() + c->lds_pad[3]) != hipSuccess ||
+      set_lds(dec_s0_kernel, dec_s0_lds_bytes()) != hipSuccess ||
       set_lds(enc_s2_dr_kernel, enc_s2_lds_bytes()) != hipSuccess || set_lds(dec_s0_dr_kernel, dec_s0_lds_bytes()) != hipSuccess ||
       set_lds(enc_s2_bm_kernel, enc_s2_lds_bytes()) != hipSuccess || set_lds(dec_s0_bm_kernel, dec_s0_lds_bytes()) != hipSuccess ||
-      set_lds(enc_s2_xn_kernel, enc_s2_lds_bytes() + c->lds_pad[2]) != hipSuccess || set_lds(dec_s0_xn_kernel, dec_s0_lds_bytes() + c->lds_pad[3]) != hipSuccess ||
-      set_lds(dec_s1_kernel, dec_s1_lds_bytes() + c->lds_pad[4]) != hipSuccess || set_lds(dec_s2_kernel, dec_s2_lds_bytes() + c->lds_pad[5]) != hipSuccess ||
+      set_lds(enc_s2_xn_kernel, enc_s2_lds_bytes()) != hipSuccess || set_lds(dec_s0_xn_kernel, dec_s0_lds_bytes()) != hipSuccess ||
+      set_lds(dec_s1_kernel, dec_s1_lds_bytes()) != hipSuccess || set_lds(dec_s2_kernel, dec_s2_lds_bytes()) != hipSuccess ||
       set_lds(logmel_kernel, logmel_lds_bytes()) != hipSuccess || set_lds(cng_kernel, cng_lds_bytes()) != hipSuccess)
     return bail(LYRA_HIP_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
   for (int i = 0; i < K_COUNT; ++i) c->cw[i] = code_warm_bytes(kKernelNames[i]);
@@ -919,8 +903,7 @@ static int create_impl(const char* model_dir, const void* image, size_t image_by
   if (getenv("LYRA_HIP_FUSED") && atoi(getenv("LYRA_HIP_FUSED")))
     return bail(LYRA_HIP_EINVAL, "LYRA_HIP_FUSED: the one-launch-per-side kernels are not in this build (make EXTRA=-DLYRA_PARKED)");
 #endif
-  if (!(getenv("LYRA_HIP_NO_ZEROCOPY") && atoi(getenv("LYRA_HIP_NO_ZEROCOPY"))) &&
-      hipHostMalloc((void**)&c->h_zc, lyra_hip_ctx::ZC_BYTES, hipHostMallocDefault) != hipSuccess)
+  if (hipHostMalloc((void**)&c->h_zc, lyra_hip_ctx::ZC_BYTES, hipHostMallocDefault) != hipSuccess)
     c->h_zc = nullptr;   // optional: the copy-engine path remains
   for (int k = 0; k < c->nsub; ++k)
     if (enc_side_done(c, k) != 0) return bail(LYRA_HIP_EHIP, "hipEventRecord failed");
@@ -1234,8 +1217,7 @@ static int launch_resample(lyra_hip_ctx* c, int side, const int32_t* d_ids, int 
     c->rs_sn_pending = false;
   }
   { ProfScope ps(c, K_RESAMPLE, st_);
-    static const size_t pad = lds_pad("resample");   // experiment hook
-    hipLaunchKernelGGL(resample_kernel, dim3(cdiv(B, resample_streams_per_wg())), dim3(256), resample_lds_bytes(n_in) + pad, st_, P, d_ids, B,
+    hipLaunchKernelGGL(resample_kernel, dim3(cdiv(B, resample_streams_per_wg())), dim3(256), resample_lds_bytes(n_in), st_, P, d_ids, B,
                        c->sm.base[side == 0 ? st::R_RS_E : st::R_RS_D], d_in, n_in, in_stride > 0 ? in_stride : n_in, d_out,
                        n_out, out_stride > 0 ? out_stride : n_out); }
   HIPCHK(c, hipGetLastError());
@@ -1313,7 +1295,7 @@ static int noise_and_resample_deferred(lyra_hip_ctx* c, const int32_t* d_ids, in
 // of step i-1, which rvq_encode(i-1) -- earlier on the same stream -- has waited for.  TWO hops ahead since round 6: at an
 // external rate the decoder chain is the slower one, the quantizer runs late (it waits for the noise stream's work of two
 // hops ago) and a hop resampled only ONE step ahead, queued behind it, arrived after the extractor wanted it -- a ~90 us
-// stall every second hop (profiles/r06_modes_timelines.txt; LYRA_HIP_RS_LEAD=1 is the old form).  (The DTX NoiseEstimator
+// stall every second hop (profiles/r06_modes_timelines.txt).  (The DTX NoiseEstimator
 // was tried on this stream too: no gain -- +31 us per step in front of the extractor or ahead -- and not kept.)
 static int resample_in_ahead(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int16_t* d_in, int n_in, int in_rate, long step) {
   const int p = (int)(step % lyra_hip_ctx::RS_RING);
@@ -1797,13 +1779,11 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
   // The decoder-side legs leave the chain on split contexts too (round 6): the noise stream joins every chunk's decode
   // (noise_dev_begin) and dec_side_begin orders every chunk behind the noise stream's older work -- decode-only at 8192 streams
   // in two sub-batches, 48 kHz: 26.1 -> 27.1 M frames/s (profiles/r06_cfg4_legs.txt).  The INPUT resampler stays on the chain
-  // there: ahead on sq[0] it would only be ordered behind chunk 0's extractor.  LYRA_HIP_RS_OUT_ON_CHAIN_SPLIT=1: the old form.
-  static const bool out_on_chain_split = getenv("LYRA_HIP_RS_OUT_ON_CHAIN_SPLIT") != nullptr;
-  const bool rs_out_off_chain = rs && !c->serial && (c->nsub == 1 || !out_on_chain_split);
+  // there: ahead on sq[0] it would only be ordered behind chunk 0's extractor.
+  const bool rs_out_off_chain = rs && !c->serial;
   struct LocalScope { lyra_hip_ctx* c; ~LocalScope() { c->chunk_local = false; c->ids_stable = false; } } local_scope{c};
   c->chunk_local = c->nsub > 1 && !c->serial && enc && dec && !feats && !rs && !loss &&
-                   !(F & (LYRA_HIP_STEP_DTX | LYRA_HIP_STEP_DECODER_NOISE)) &&
-                   !getenv("LYRA_HIP_NO_CHUNK_LOCAL");
+                   !(F & (LYRA_HIP_STEP_DTX | LYRA_HIP_STEP_DECODER_NOISE));
   for (int i = 0; i < S->n_steps; ++i) {
     const long step = S->first_step + i;
     const int set = (int)(step & 1);
@@ -1822,7 +1802,6 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
         }
       } else if (rs) {         // ... two steps ahead, on the quantizer stream (resample_in_ahead)
         DEVSCOPE(c);
-        static const int lead = getenv("LYRA_HIP_RS_LEAD") ? std::max(1, std::min(2, atoi(getenv("LYRA_HIP_RS_LEAD")))) : 2;   // experiment hook
         auto ahead = [&](int j) {   // the hop of step first_step + j, if this call has one
           if (j >= S->n_steps) return 0;
           const int16_t* src = S->d_pcm_ring + (size_t)((S->first_step + j) % S->ring) * B * (size_t)n_ext;
@@ -1830,9 +1809,9 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
         };
         if (i == 0) {
           if ((rc = ahead_begin(c))) return rc;
-          for (int j = 0; j < lead; ++j) if ((rc = ahead(j))) return rc;
+          for (int j = 0; j < lyra_hip_ctx::RS_LEAD; ++j) if ((rc = ahead(j))) return rc;
         }
-        if ((rc = ahead(i + lead))) return rc;
+        if ((rc = ahead(i + lyra_hip_ctx::RS_LEAD))) return rc;
         const int slot = (int)(step % lyra_hip_ctx::RS_RING);
         for (int k = 0; k < c->nsub; ++k) HIPCHK(c, hipStreamWaitEvent(c->se[k], c->ev_rs_in[slot], 0));
         in = c->d_rs16[slot];
@@ -1861,8 +1840,7 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
         rc = lyra_hip_decode_dev(c, S->d_stream_ids, S->B, pk, S->num_bits, S->d_pcm_out[set]);
       }
       if (rc) return rc;
-      static const bool split_sn = getenv("LYRA_HIP_SPLIT_SN_CALLS") != nullptr;   // experiment hook: the form before round 6
-      if ((F & LYRA_HIP_STEP_DECODER_NOISE) && rs_out_off_chain && !split_sn) {   // both legs: one noise-stream call
+      if ((F & LYRA_HIP_STEP_DECODER_NOISE) && rs_out_off_chain) {   // both legs: one noise-stream call
         if ((rc = noise_and_resample_deferred(c, S->d_stream_ids, S->B, S->d_pcm_out[set], S->d_is_noise, ext, S->d_ext_out[set]))) return rc;
       } else {
         if (F & LYRA_HIP_STEP_DECODER_NOISE)   // lyra_decoder.cc:304-311: every decoded hop of a received packet

@@ -69,12 +69,9 @@ __device__ __forceinline__ void dec_s0_body(const DecS0P* __restrict__ Pp, const
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m = lane & 15, q = lane >> 4;
   const int b0 = tile * SD0;
-  wg_schedule_hint();
   LYRA_TSTAMP(80);
   LYRA_WSTAMP(120);
-#if !defined(LYRA_WGTRACE_D1) && !defined(LYRA_WGTRACE_D2)
   LYRA_WG_BEGIN();
-#endif
   if (tid < SD0) {
     int id = ids[min(b0 + tid, B - 1)];
     sids[tid] = id;
@@ -140,12 +137,7 @@ __device__ __forceinline__ void dec_s0_body(const DecS0P* __restrict__ Pp, const
           *reinterpret_cast<const f32x4*>(&FB[(2 * 16 + s) * FS + p4 * 4]);
   }
   LYRA_TSTAMP(81);
-#ifdef LYRA_T1_ABL   // TIMING-ONLY ablation (results are wrong): odd tiles skip the GEMM phases of the T = 1 layers -- what a
-  const bool t1_skip = (tile & 1) != 0;   // 16-stream tile (twice the streams per 16-row MFMA tile) could return at most
-#else
-  constexpr bool t1_skip = false;
-#endif
-  if (!t1_skip) {  // conv k3 g4: per group [16 rows] x K=48 x N=128; LeakyReLU; QUANTIZE -> H8
+  {  // conv k3 g4: per group [16 rows] x K=48 x N=128; LeakyReLU; QUANTIZE -> H8
     f32x4 acc[1][4];
     const int g = wave >> 1;
     auto aoff = [&](int i, int c) { return (c * 16 + m) * FS + g * 16 + q * 4; };
@@ -161,7 +153,7 @@ __device__ __forceinline__ void dec_s0_body(const DecS0P* __restrict__ Pp, const
   }
   __syncthreads();
   LYRA_TSTAMP(82);
-  if (!t1_skip) {  // 4 grouped int8 transposed convs k4/s2 (one input row -> 4 output rows), carried tail of 2 rows
+  {  // 4 grouped int8 transposed convs k4/s2 (one input row -> 4 output rows), carried tail of 2 rows
     i32x4 acc[1][8];
     const int g = wave >> 1;
     const TconvQ U = P.up0[g];
@@ -343,9 +335,7 @@ __device__ __forceinline__ void dec_s0_body(const DecS0P* __restrict__ Pp, const
   }
   LYRA_TSTAMP(88);
   LYRA_WSTAMP(121);
-#if !defined(LYRA_WGTRACE_D1) && !defined(LYRA_WGTRACE_D2)
   LYRA_WG_END();
-#endif
   if (tid < SD0 && cx.valid(tid)) {   // this region's ring phase
     int ph = sphase[tid] + 1;
     *cx.at<int>(cx.soff(tid) + (uint32_t)(st::PHASE)) = ph >= st::PHASE_MOD ? 0 : ph;
@@ -362,10 +352,7 @@ __device__ __forceinline__ void dec_s0_body(const DecS0P* __restrict__ Pp, const
 namespace {
 constexpr int SD1 = 8;
 constexpr int CS1 = 136;
-#ifndef LYRA_S1_THREADS
-#define LYRA_S1_THREADS 512   // 8 waves per tile: 4 waves per SIMD with two tiles per CU (256 = the 4-wave layout)
-#endif
-constexpr int NTD1 = LYRA_S1_THREADS;
+constexpr int NTD1 = S1_THREADS;
 }  // namespace
 
 // tconv k10/s5, polyphase: output block b (5 rows x 64 ch = N 320) = bias, then x[b] . W[taps 0..4], then
@@ -460,13 +447,9 @@ __device__ __forceinline__ void dec_s1_body(const DecS1P& P, const float* __rest
   float* SB = PB + 4 * SD1 * CS1;       // [5][S][72]: tail of the previous frame's transposed conv
   int* sids = reinterpret_cast<int*>(SB + 5 * SD1 * 72);
   int* sphase = sids + SD1;
-  wg_schedule_hint();
   const int tid = threadIdx.x, wave = tid >> 6;
   const int b0 = tile * SD1;
   LYRA_TSTAMP(50);
-#ifdef LYRA_WGTRACE_D1   // per-workgroup trace of THIS kernel instead of dec_s0 (wg_trace_full.py (a probe of an earlier round, removed since: git history))
-  LYRA_WG_BEGIN();
-#endif
   // the stage input does not depend on the stream ids: requested with them, ahead of the barrier (see enc_s1_body)
   int my_id = 0;
   if (tid < SD1) my_id = ids[min(b0 + tid, B - 1)];
@@ -522,10 +505,6 @@ __device__ __forceinline__ void dec_s1_body(const DecS1P& P, const float* __rest
   if (NTD1 == 256) dec_s1_tconv<5>(XB, SB, P, cx, b0, out1, wave * 5, HB);
   else if (wave < 4) dec_s1_tconv<3>(XB, SB, P, cx, b0, out1, wave * 3, HB);
   else dec_s1_tconv<2>(XB, SB, P, cx, b0, out1, 12 + (wave - 4) * 2, HB);
-#ifdef LYRA_WGTRACE_D1
-  __syncthreads();
-  LYRA_WG_END();
-#endif
   if (tid < SD1 && cx.valid(tid)) {   // this region's ring phase
     int ph = sphase[tid] + 1;
     *cx.at<int>(cx.soff(tid) + (uint32_t)(st::PHASE)) = ph >= st::PHASE_MOD ? 0 : ph;
@@ -553,33 +532,20 @@ __device__ __forceinline__ void dec_s2_body(const DecS2P& P, const float* __rest
   int* sids = reinterpret_cast<int*>(SB + SD2 * 48);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m = lane & 15, q = lane >> 4;
-  wg_schedule_hint();
   const int b0 = tile * SD2;
   LYRA_TSTAMP(60);
-#ifdef LYRA_WGTRACE_D2
-  LYRA_WG_BEGIN();
-#endif
   int my_id = 0;
   if (tid < SD2) my_id = ids[min(b0 + tid, B - 1)];
   const int wn = wave & 3, wm = wave >> 2;
-  const int pcol = at16(wn * 16 + (lane & 15));
+  [[maybe_unused]] const int ncol = wn * 16 + (lane & 15);   // unused: see resblocks64r
   // the stage input does not depend on the stream ids: requested with them, ahead of the barrier (see enc_s1_body)
-  constexpr bool SW = LYRA_SWAP64 != 0;   // operand-swapped GEMMs: a lane holds 4 consecutive channels of ONE row (lyra_dev.h)
-  f32x4 xr[5][1];  // residual stream in registers (MFMA C layout; transposed with SW: see resblocks64r)
+  // the GEMMs run operand-swapped (lyra_dev.h SWAP): a lane holds 4 consecutive channels of ONE row
+  f32x4 xr[5][1];  // residual stream in registers (MFMA C layout, transposed: see resblocks64r)
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
-    if constexpr (SW) {
-      const int R = (wm * 5 + i) * 16 + m, t = R / SD2, s = R & (SD2 - 1);
-      const int sb = min(s, B - 1 - b0);
-      xr[i][0] = *goff<const f32x4>(in1 + (size_t)b0 * 1280, (uint32_t)(((sb * 20 + t) * 64 + wn * 16 + q * 4) * 4));
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        int R = (wm * 5 + i) * 16 + q * 4 + e, t = R / SD2, s = R & (SD2 - 1);
-        int sb = min(s, B - 1 - b0);
-        xr[i][0][e] = *goff<const float>(in1 + (size_t)b0 * 1280, (uint32_t)(((sb * 20 + t) * 64 + pcol) * 4));
-      }
-    }
+    const int R = (wm * 5 + i) * 16 + m, t = R / SD2, s = R & (SD2 - 1);
+    const int sb = min(s, B - 1 - b0);
+    xr[i][0] = *goff<const f32x4>(in1 + (size_t)b0 * 1280, (uint32_t)(((sb * 20 + t) * 64 + wn * 16 + q * 4) * 4));
   }
   if (tid < SD2) sids[tid] = my_id;
   const auto warm = l2_warm<NTD2, 1>(P.warm);
@@ -602,12 +568,7 @@ __device__ __forceinline__ void dec_s2_body(const DecS2P& P, const float* __rest
   for (int i = 0; i < 5; ++i)
 {
     const f32x4 a4 = lrelu4(xr[i][0]);
-    if constexpr (SW) {
-      *reinterpret_cast<f32x4*>(&XB[(3 * SD2 + (wm * 5 + i) * 16 + m) * CS0 + wn * 16 + q * 4]) = a4;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) XB[(3 * SD2 + (wm * 5 + i) * 16 + q * 4 + e) * CS0 + pcol] = a4[e];
-    }
+    *reinterpret_cast<f32x4*>(&XB[(3 * SD2 + (wm * 5 + i) * 16 + m) * CS0 + wn * 16 + q * 4]) = a4;
   }
   __syncthreads();
   // tconv k64/s16, polyphase: blocks b = 0..22 (+1 of padding), rows (b, s); K = 4 x 64 (newest input first: chunk
@@ -621,67 +582,40 @@ __device__ __forceinline__ void dec_s2_body(const DecS2P& P, const float* __rest
     };
     const float bias = as_global(P.up.b)[0];
     const f32x4 bias4[1] = {(f32x4){bias, bias, bias, bias}};
-    gemm_f32_init<2, 1, 16, 16, gemm_pf<2, 1>(), SW>(XB, aoff, P.up.w, bias4, acc);   // (one output channel: the splat is every phase's bias)
-    const int j = lane & 15;
-    if constexpr (SW) {
-      // row (b, s) = this lane's C column; its four values are phases 4q .. 4q + 3 = four CONSECUTIVE output samples
+    gemm_f32_init<2, 1, 16, 16, gemm_pf<2, 1>(), true>(XB, aoff, P.up.w, bias4, acc);   // (one output channel: the splat is every phase's bias)
+    // row (b, s) = this lane's C column; its four values are phases 4q .. 4q + 3 = four CONSECUTIVE output samples
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int R = (2 * wave + i) * 16 + m, b = R / SD2, s = R & (SD2 - 1);
-        if (b > 22) continue;
-        const int tau0 = 16 * b + 4 * q;
-        f32x4 y = acc[i][0];
-        f32x4 old = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (tau0 < 48) old = *reinterpret_cast<const f32x4*>(&SB[s * 48 + tau0]);
+    for (int i = 0; i < 2; ++i) {
+      const int R = (2 * wave + i) * 16 + m, b = R / SD2, s = R & (SD2 - 1);
+      if (b > 22) continue;
+      const int tau0 = 16 * b + 4 * q;
+      f32x4 y = acc[i][0];
+      f32x4 old = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (tau0 < 48) old = *reinterpret_cast<const f32x4*>(&SB[s * 48 + tau0]);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = y[e] + old[e];   // (+ 0.f beyond the old tail, as the graph's ADD does)
-        if (!cx.valid(s)) continue;
-        if (tau0 < 320) {
-          // UnitToInt16Scalar (dsp_utils.h:54-88): scale, clip, C truncation
-          int v[4];
+      for (int e = 0; e < 4; ++e) y[e] = y[e] + old[e];   // (+ 0.f beyond the old tail, as the graph's ADD does)
+      if (!cx.valid(s)) continue;
+      if (tau0 < 320) {
+        // UnitToInt16Scalar (dsp_utils.h:54-88): scale, clip, C truncation
+        int v[4];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            float f = y[e] * 32768.f;
-            f = f < -32768.f ? -32768.f : f;
-            f = f > 32767.f ? 32767.f : f;
-            v[e] = (int)(int16_t)f;
-          }
-          typedef int i32x2 __attribute__((ext_vector_type(2)));
-          const i32x2 pk = (i32x2){(v[0] & 0xffff) | (v[1] << 16), (v[2] & 0xffff) | (v[3] << 16)};
-          *goff<i32x2>(pcm + (size_t)b0 * 320, (uint32_t)((s * 320 + tau0) * 2)) = pk;
-        } else {
-          f32x4 t;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) t[e] = y[e] - P.up_sub;
-          *cx.at<f32x4>(cx.soff(s) + (uint32_t)(st::D_UP3 + (tau0 - 320) * 4)) = t;
+        for (int e = 0; e < 4; ++e) {
+          float f = y[e] * 32768.f;
+          f = f < -32768.f ? -32768.f : f;
+          f = f > 32767.f ? 32767.f : f;
+          v[e] = (int)(int16_t)f;
         }
-      }
-    } else
+        typedef int i32x2 __attribute__((ext_vector_type(2)));
+        const i32x2 pk = (i32x2){(v[0] & 0xffff) | (v[1] << 16), (v[2] & 0xffff) | (v[3] << 16)};
+        *goff<i32x2>(pcm + (size_t)b0 * 320, (uint32_t)((s * 320 + tau0) * 2)) = pk;
+      } else {
+        f32x4 t;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int R = (2 * wave + i) * 16 + q * 4 + e, b = R / SD2, s = R & (SD2 - 1);
-        if (b > 22) continue;
-        const int tau = 16 * b + j;
-        float y = acc[i][0][e];
-        y = y + (tau < 48 ? SB[s * 48 + tau] : 0.f);
-        if (!cx.valid(s)) continue;
-        if (tau < 320) {
-          // UnitToInt16Scalar (dsp_utils.h:54-88): scale, clip, C truncation
-          float v = y * 32768.f;
-          v = v < -32768.f ? -32768.f : v;
-          v = v > 32767.f ? 32767.f : v;
-          *goff<int16_t>(pcm + (size_t)b0 * 320, (uint32_t)((s * 320 + tau) * 2)) = (int16_t)v;
-        } else {
-          *cx.at<float>(cx.soff(s) + (uint32_t)(st::D_UP3 + (tau - 320) * 4)) = y - P.up_sub;
-        }
+        for (int e = 0; e < 4; ++e) t[e] = y[e] - P.up_sub;
+        *cx.at<f32x4>(cx.soff(s) + (uint32_t)(st::D_UP3 + (tau0 - 320) * 4)) = t;
       }
+    }
   }
-#ifdef LYRA_WGTRACE_D2
-  __syncthreads();
-  LYRA_WG_END();
-#endif
   l2_warm_sink(warm, state, B);
   l2_warm_sink(warm_code, state, B);
 }

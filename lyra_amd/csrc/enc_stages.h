@@ -22,10 +22,7 @@ constexpr int CS0 = 72;    // LDS row stride (64 + 8) floats
 constexpr int PBS = 376;   // PCM staging row stride (368 + 8) floats
 constexpr int S1 = 8;
 constexpr int CS1 = 136;   // 128 + 8
-#ifndef LYRA_S1_THREADS
-#define LYRA_S1_THREADS 512   // 8 waves per tile: 4 waves per SIMD with two tiles per CU (256 = the 4-wave layout)
-#endif
-constexpr int NT1 = LYRA_S1_THREADS;
+constexpr int NT1 = S1_THREADS;
 constexpr int NW1 = NT1 / 64;
 }  // namespace
 
@@ -51,7 +48,6 @@ __device__ __forceinline__ void enc_s0_body(const EncS0P& P, const int16_t* __re
   LYRA_WG_BEGIN();
   LYRA_TSTAMP(0);
   LYRA_WSTAMP(100);
-  wg_schedule_hint();
   if (tid < S0) sids[tid] = ids[min(b0 + tid, B - 1)];
   const auto warm = l2_warm<NT0, 1>(P.warm);
   const auto warm_code = code_warm<NT0>(code_bytes);
@@ -101,9 +97,7 @@ __device__ __forceinline__ void enc_s0_body(const EncS0P& P, const int16_t* __re
   LYRA_TSTAMP(1);
 
   const int wn = wave & 3, wm = wave >> 2;  // GEMM wave grid for N = 64: N tile x M group of 5 tiles
-  const int ncol = wn * 16 + (lane & 15);   // logical output channel of this lane's C column
-  const int pcol = at16(ncol);
-  constexpr bool SW = LYRA_SWAP64 != 0;     // operand-swapped GEMMs: a lane holds 4 consecutive channels of ONE row (lyra_dev.h)
+  // the GEMMs run operand-swapped (lyra_dev.h SWAP): a lane holds 4 consecutive channels of ONE row
 
   // ---- B. first conv k64/s16: [20*S rows] x K=64 x N=64 ---------------------------------------
   f32x4 xr[5][1];  // the residual stream X, resident in registers (MFMA C layout) through the three blocks
@@ -112,7 +106,7 @@ __device__ __forceinline__ void enc_s0_body(const EncS0P& P, const int16_t* __re
       int R = (wm * 5 + i) * 16 + m;
       return (R & (S0 - 1)) * PBS + (R / S0 + c) * 16 + q * 4;
     };
-    gemm_f32_bias<5, 1, 4, 4, gemm_pf<5, 1>(), SW>(PB, aoff, P.first.w + wn * 4 * 64, P.first.b, wn * 16, xr);
+    gemm_f32_bias<5, 1, 4, 4, gemm_pf<5, 1>(), true>(PB, aoff, P.first.w + wn * 4 * 64, P.first.b, wn * 16, xr);
   }
   __syncthreads();  // PCM staging area is free again
 #pragma unroll
@@ -133,12 +127,7 @@ __device__ __forceinline__ void enc_s0_body(const EncS0P& P, const int16_t* __re
   for (int i = 0; i < 5; ++i)
 {
     const f32x4 a4 = lrelu4(xr[i][0]);
-    if constexpr (SW) {
-      *reinterpret_cast<f32x4*>(&XB[(5 * S0 + (wm * 5 + i) * 16 + m) * CS0 + wn * 16 + q * 4]) = a4;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) XB[(5 * S0 + (wm * 5 + i) * 16 + q * 4 + e) * CS0 + pcol] = a4[e];
-    }
+    *reinterpret_cast<f32x4*>(&XB[(5 * S0 + (wm * 5 + i) * 16 + m) * CS0 + wn * 16 + q * 4]) = a4;
   }
   __syncthreads();
   for (int idx = tid; idx < 5 * S0 * 16; idx += NT0) {
@@ -158,28 +147,16 @@ __device__ __forceinline__ void enc_s0_body(const EncS0P& P, const int16_t* __re
       int R = i * 16 + m;
       return ((5 * (R / S0) + tap) * S0 + (R & (S0 - 1))) * CS0 + c16 * 16 + q * 4;
     };
-    gemm_f32_bias<MTW, NTW, 40, 40, gemm_pf<MTW, NTW>(), SW>(XB, aoff, P.down.w + (wave * NTW) * 40 * 64, P.down.b,
-                                                             wave * NTW * 16, acc);
+    gemm_f32_bias<MTW, NTW, 40, 40, gemm_pf<MTW, NTW>(), true>(XB, aoff, P.down.w + (wave * NTW) * 40 * 64, P.down.b,
+                                                               wave * NTW * 16, acc);
     LYRA_TSTAMP(5);
 #pragma unroll
-    for (int j = 0; j < NTW; ++j) {
-      if constexpr (SW) {   // row (tau, s) = this lane's C column, 4 consecutive physical channels: one 16-byte store
+    for (int j = 0; j < NTW; ++j) {   // row (tau, s) = this lane's C column, 4 consecutive physical channels: one 16-byte store
 #pragma unroll
-        for (int i = 0; i < MTW; ++i) {
-          const int R = i * 16 + m, tau = R / S0, s = R & (S0 - 1);
-          if (valid(s))
-            *goff<f32x4>(out0 + (size_t)b0 * 512, (uint32_t)(((s * 4 + tau) * 128 + (wave * NTW + j) * 16 + q * 4) * 4)) = acc[i][j];
-        }
-      } else {
-        int n = (wave * NTW + j) * 16 + (lane & 15);
-        int pc = at16(n);
-#pragma unroll
-        for (int i = 0; i < MTW; ++i)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            int R = i * 16 + q * 4 + e, tau = R / S0, s = R & (S0 - 1);
-            if (valid(s)) *goff<float>(out0 + (size_t)b0 * 512, (uint32_t)(((s * 4 + tau) * 128 + pc) * 4)) = acc[i][j][e];
-          }
+      for (int i = 0; i < MTW; ++i) {
+        const int R = i * 16 + m, tau = R / S0, s = R & (S0 - 1);
+        if (valid(s))
+          *goff<f32x4>(out0 + (size_t)b0 * 512, (uint32_t)(((s * 4 + tau) * 128 + (wave * NTW + j) * 16 + q * 4) * 4)) = acc[i][j];
       }
     }
   }
@@ -205,7 +182,6 @@ __device__ __forceinline__ void enc_s1_body(const EncS1P& P, const float* __rest
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m = lane & 15, q = lane >> 4;
   const int b0 = tile * S1;
-  wg_schedule_hint();
   LYRA_TSTAMP(70);
   LYRA_WSTAMP(102);
   // The stage input does not depend on the stream ids (only on the tile): requested in the same round trip as the ids, in
@@ -274,28 +250,17 @@ __device__ __forceinline__ void enc_s1_body(const EncS1P& P, const float* __rest
       int R = i * 16 + m;
       return ((2 * (R / S1) + tap) * S1 + (R & (S1 - 1))) * CS1 + g * 64 + c16 * 16 + q * 4;
     };
-    constexpr bool SW = LYRA_SWAP128 != 0;   // operand-swapped (lyra_dev.h): one 16-byte store per C tile
-    gemm_f32_bias<MTW, NTW, 16, 16, gemm_pf<MTW, NTW>(), SW>(XB, aoff, P.down.w + nt0 * 16 * 64, P.down.b, nt0 * 16, acc);
+    gemm_f32_bias<MTW, NTW, 16, 16, gemm_pf<MTW, NTW>()>(XB, aoff, P.down.w + nt0 * 16 * 64, P.down.b, nt0 * 16, acc);
 #pragma unroll
     for (int j = 0; j < NTW; ++j) {
-      if constexpr (SW) {
+      const int pc = at16((nt0 + j) * 16 + (lane & 15));
 #pragma unroll
-        for (int i = 0; i < MTW; ++i) {
-          const int R = i * 16 + m, tau = R / S1, s = R & (S1 - 1);
-          if (valid(s))
-            *goff<f32x4>(out1 + (size_t)b0 * 512, (uint32_t)(((s * 2 + tau) * 256 + (nt0 + j) * 16 + q * 4) * 4)) = acc[i][j];
+      for (int i = 0; i < MTW; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          int R = i * 16 + q * 4 + e, tau = R / S1, s = R & (S1 - 1);
+          if (valid(s)) *goff<float>(out1 + (size_t)b0 * 512, (uint32_t)(((s * 2 + tau) * 256 + pc) * 4)) = acc[i][j][e];
         }
-      } else {
-        int n = (nt0 + j) * 16 + (lane & 15);
-        int pc = at16(n);
-#pragma unroll
-        for (int i = 0; i < MTW; ++i)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            int R = i * 16 + q * 4 + e, tau = R / S1, s = R & (S1 - 1);
-            if (valid(s)) *goff<float>(out1 + (size_t)b0 * 512, (uint32_t)(((s * 2 + tau) * 256 + pc) * 4)) = acc[i][j][e];
-          }
-      }
     }
   }
   LYRA_TSTAMP(73);

@@ -5,6 +5,13 @@
 
 namespace lyra {
 
+// ---- launch shapes and occupancy targets of the stage kernels ----------------------------------
+constexpr int I8_WAVES = 4;       // waves per SIMD the int8 stage kernels are compiled for (5 -> at most 96 VGPRs)
+constexpr int C64_WAVES = 4;      // waves per SIMD the 64-channel stage kernels are compiled for (3 -> up to 168 VGPRs, no spills)
+constexpr int S0_STREAMS = 4;     // streams per workgroup of the 64-channel stages (4 with 256 threads, 8 with 512)
+constexpr int S1_THREADS = 512;   // threads per tile of the 128-channel stages: 8 waves, 4 per SIMD with two tiles per CU
+                                  // (256 = the 4-wave layout)
+
 // ---- encoder ---------------------------------------------------------------------------------
 struct EncS0P { ConvF first; DwF dw[3]; ConvF pw[3]; ConvF cv[3]; ConvF down; WarmRange warm; };
 struct EncS1P { DwF dw[3]; ConvF pw[3]; ConvF cv[3]; ConvF down; WarmRange warm; };

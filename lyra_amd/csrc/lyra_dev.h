@@ -20,13 +20,8 @@
 #include <stdint.h>
 
 // LYRA_SYNC_KEEP(): the barrier behind which the stream ids / ring phases sit (addresses depend on it).
-// -DLYRA_NO_BARRIER is a TIMING-ONLY ablation (results are garbage): every OTHER workgroup barrier becomes a wave barrier --
-// how much of a stage kernel is waiting for its slowest wave?
 #define LYRA_SYNC_KEEP() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_s_barrier(); \
                               __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); } while (0)
-#ifdef LYRA_NO_BARRIER
-#define __syncthreads() __builtin_amdgcn_wave_barrier()
-#endif
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -83,12 +78,10 @@ __device__ __forceinline__ float lrelu(float x) {
 }
 // Four at once: the two multiplies as v_pk_mul_f32 (two fp32 products per issue slot -- the same IEEE products), the
 // maxima stay scalar (there is no packed fp32 max): 6 instead of 8 vector instructions per four elements.  Round 6,
-// alternating on one box (profiles/r06_ab_pk_lrelu.txt): driver form 14.05 -> 14.09 M, sustained 14.45 -> 14.47 M frames/s
-// (-DLYRA_SCALAR_LRELU builds the old form).
+// alternating on one box (profiles/r06_ab_pk_lrelu.txt): driver form 14.05 -> 14.09 M, sustained 14.45 -> 14.47 M frames/s.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x4 lrelu4(f32x4 v) {
   f32x4 r;
-#ifndef LYRA_SCALAR_LRELU
   const f32x2 al = (f32x2){LYRA_LRELU_ALPHA, LYRA_LRELU_ALPHA};
   f32x2 lo = (f32x2){v[0], v[1]}, hi = (f32x2){v[2], v[3]}, alo, ahi;
   // The products are COMPILER-VISIBLE vector multiplies (selected as v_pk_mul_f32): v is usually a fresh MFMA result, and
@@ -101,9 +94,6 @@ __device__ __forceinline__ f32x4 lrelu4(f32x4 v) {
   asm("v_max_f32 %0, %1, %2" : "=v"(r[1]) : "v"(v[1]), "v"(alo[1]));
   asm("v_max_f32 %0, %1, %2" : "=v"(r[2]) : "v"(v[2]), "v"(ahi[0]));
   asm("v_max_f32 %0, %1, %2" : "=v"(r[3]) : "v"(v[3]), "v"(ahi[1]));
-#else
-  r[0] = lrelu(v[0]); r[1] = lrelu(v[1]); r[2] = lrelu(v[2]); r[3] = lrelu(v[3]);
-#endif
   return r;
 }
 __device__ __forceinline__ f32x4 fma4(f32x4 a, f32x4 b, f32x4 c) {
@@ -276,51 +266,11 @@ __device__ __forceinline__ const T LYRA_GLOBAL* wave_uniform(const T* p) {
   return (const T LYRA_GLOBAL*)(((uint64_t)hi << 32) | lo);
 }
 
-// Experiments on how co-resident workgroups share a SIMD (build flags, see DESIGN.md "what was tried"):
-//   LYRA_PRIO_MFMA   raise the wave's priority around every MFMA cluster (guide T5)
-//   LYRA_PRIO_SLOT   static priority = the wave's slot on its SIMD (0..3): co-resident tiles pipeline instead of
-//                    marching in lock-step
-//   LYRA_STAGGER=N   tiles in wave slot k start k * N * 64 cycles late
-#ifdef LYRA_PRIO_MFMA
-#define LYRA_MFMA_BEGIN() __builtin_amdgcn_s_setprio(2)
-#define LYRA_MFMA_END() __builtin_amdgcn_s_setprio(0)
-#else
-#define LYRA_MFMA_BEGIN() do { } while (0)
-#define LYRA_MFMA_END() do { } while (0)
-#endif
-__device__ __forceinline__ void wg_schedule_hint() {
-#if defined(LYRA_PRIO_SLOT) || defined(LYRA_STAGGER) || defined(LYRA_STAGGER2)
-  const unsigned slot = __builtin_amdgcn_s_getreg(63492) & 15u;   // HW_ID.wave_id: the wave's slot on its SIMD
-#endif
-#ifdef LYRA_PRIO_SLOT
-  switch (slot & 3u) {
-    case 0: __builtin_amdgcn_s_setprio(3); break;
-    case 1: __builtin_amdgcn_s_setprio(2); break;
-    case 2: __builtin_amdgcn_s_setprio(1); break;
-    default: __builtin_amdgcn_s_setprio(0); break;
-  }
-#endif
-#ifdef LYRA_STAGGER
-  for (unsigned i = 0; i < (slot & 3u) * LYRA_STAGGER; ++i) __builtin_amdgcn_s_sleep(64);
-#endif
-#ifdef LYRA_STAGGER2   // half of a CU's co-resident tiles (wave slots 2, 3 of each SIMD) start LYRA_STAGGER2 * 64 cycles late
-  if (slot & 2u) __builtin_amdgcn_s_sleep(LYRA_STAGGER2);
-#endif
-}
-
 // Software-pipelined: the B fragments (L2, ~500+ cycles) and A fragments (LDS) of chunk c+PF are requested
 // before the MFMAs of chunk c issue; the K loop is fully unrolled so the PF+1 register stages are static and
 // the compiler emits counted s_waitcnt (the prefetches stay in flight across the MFMA block).
 //   KS   = K-chunk stride between a tile's fragments in memory (> KC when only part of the packed K range is run)
 //   ZERO = start the chains from 0; otherwise acc carries values in (a chain continued from an earlier GEMM)
-// LYRA_WEIGHT_ALIAS (timing experiment only, results are wrong): every K chunk of a tile re-reads the tile's first
-// weight fragment -- the GEMM's L2 -> CU weight traffic collapses to one 1 KB fragment per wave and N tile while the
-// instruction stream stays the same.  What that buys is what weight bandwidth costs.
-#ifdef LYRA_WEIGHT_ALIAS
-#define LYRA_WCHUNK(c) 0
-#else
-#define LYRA_WCHUNK(c) (c)
-#endif
 // INIT: 0 = the chains start from 0, 1 = acc carries values in (a chain continued from an earlier GEMM), 2 = the chains
 // start from init[j] (the bias splat of N tile j): the first MFMA of every chain takes it as its C operand directly,
 // so no accumulator is written (or even allocated) before the first products arrive.
@@ -339,16 +289,10 @@ struct WPre { f32x4 b[PF][NTW]; f32x4 init[NTW]; };
 // shared an LDS bank at a row stride of 72 floats), the stage input of dec_s2 one dwordx4 load instead of four dword
 // loads.  Each output element is still bias, then fma over ascending k: the products commute, the chain does not change.
 // The bias comes as the lane's four channels (AT16-ordered array, one 16-byte load).
-#ifndef LYRA_SWAP64
-#define LYRA_SWAP64 1
-#endif
 // Measured, alternating on one box (profiles/r06_ab_swap64.txt, r06_ab_swap128.txt): the 64-channel stages swapped
 // 14.08 -> 14.13 M frames/s in the driver form and 14.43 -> 14.51 M sustained (static vector instructions of enc_s0 735 ->
 // 636, LDS instructions 180 -> 159); the 128-channel stages swapped as well LOSE 0.3 % again (their X update becomes a
-// 16-byte read-modify-write per C tile, and dec_s1 is at the register cap): -DLYRA_SWAP128=1 builds that, the default is off.
-#ifndef LYRA_SWAP128   // ... and the residual blocks + strided conv of the 128-channel stages
-#define LYRA_SWAP128 0
-#endif
+// 16-byte read-modify-write per C tile, and dec_s1 is at the register cap), so only the 64-channel stages run swapped.
 // this lane's four bias values of the N tile whose first channel is n0 (bias array in AT16 order)
 __device__ __forceinline__ f32x4 bias_quad(const float* bias, int n0) {
   return *reinterpret_cast<const f32x4 LYRA_GLOBAL*>(as_global(bias) + n0 + (((threadIdx.x & 63) >> 4) << 2));
@@ -362,7 +306,7 @@ __device__ __forceinline__ WPre<NTW, PF> gemm_f32_wprefetch(const f32x4* bfrag_g
 #pragma unroll
   for (int p = 0; p < PF; ++p)
 #pragma unroll
-    for (int j = 0; j < NTW; ++j) pre.b[p][j] = bbase[(j * KS + LYRA_WCHUNK(p < KC ? p : 0)) * 64 + lane];
+    for (int j = 0; j < NTW; ++j) pre.b[p][j] = bbase[(j * KS + (p < KC ? p : 0)) * 64 + lane];
   if constexpr (SWAP) {
 #pragma unroll
     for (int j = 0; j < NTW; ++j) pre.init[j] = bias_quad(bias, n0 + j * 16);
@@ -393,7 +337,7 @@ __device__ __forceinline__ void gemm_f32_core(const float* lds, AOff a_off, cons
   for (int p = 0; p < PF; ++p)
     if (p < KC) {
 #pragma unroll
-      for (int j = 0; j < NTW; ++j) bq[p][j] = pre_b ? pre_b[p][j] : bbase[(j * KS + LYRA_WCHUNK(p)) * 64 + lane];
+      for (int j = 0; j < NTW; ++j) bq[p][j] = pre_b ? pre_b[p][j] : bbase[(j * KS + p) * 64 + lane];
 #pragma unroll
       for (int i = 0; i < MTW; ++i) aq[p][i] = *reinterpret_cast<const f32x4*>(lds + a_off(i, p));
     }
@@ -402,15 +346,11 @@ __device__ __forceinline__ void gemm_f32_core(const float* lds, AOff a_off, cons
     if (c + PF < KC) {
       const int sl = (c + PF) % (PF + 1);
 #pragma unroll
-      for (int j = 0; j < NTW; ++j) bq[sl][j] = bbase[(j * KS + LYRA_WCHUNK(c + PF)) * 64 + lane];
+      for (int j = 0; j < NTW; ++j) bq[sl][j] = bbase[(j * KS + (c + PF)) * 64 + lane];
 #pragma unroll
       for (int i = 0; i < MTW; ++i) aq[sl][i] = *reinterpret_cast<const f32x4*>(lds + a_off(i, c + PF));
     }
-#ifdef LYRA_GEMM_SCHED_BARRIER   // experiment: keep the prefetch loads above this chunk's MFMAs (the scheduler sinks them otherwise)
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     const int cur = c % (PF + 1);
-    LYRA_MFMA_BEGIN();
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
@@ -422,7 +362,6 @@ __device__ __forceinline__ void gemm_f32_core(const float* lds, AOff a_off, cons
           acc[i][j] = SWAP ? __builtin_amdgcn_mfma_f32_16x16x4f32(bq[cur][j][kk], aq[cur][i][kk], cin, 0, 0, 0)
                            : __builtin_amdgcn_mfma_f32_16x16x4f32(aq[cur][i][kk], bq[cur][j][kk], cin, 0, 0, 0);
         }
-    LYRA_MFMA_END();
   }
 }
 

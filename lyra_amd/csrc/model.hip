@@ -428,8 +428,7 @@ bool build_model(const Pack& pk, int requant_mode, Model* M, std::string* err) {
   // pass over [warm.base, warm.base + warm.bytes) (l2_warm in lyra_dev.h).
   // ---- encoder (op numbering: tools/pack_weights.py) ----------------------------------
   size_t mark = B.mark();
-  constexpr bool SW64 = LYRA_SWAP64 != 0;   // the 64-channel stages' GEMMs run operand-swapped (lyra_dev.h)
-  constexpr bool SW128 = LYRA_SWAP128 != 0; // ... and the residual blocks / strided conv of the 128-channel stages
+  constexpr bool SW64 = true;   // the 64-channel stages' GEMMs run operand-swapped (lyra_dev.h), the 128-channel stages' do not
   B.conv_f("enc", 0, &M->enc0.first, 64, 64, 1, SW64);
   for (int r = 0; r < 3; ++r) {
     B.dw_f("enc", r, &M->enc0.dw[r], 64);
@@ -442,10 +441,10 @@ bool build_model(const Pack& pk, int requant_mode, Model* M, std::string* err) {
   mark = B.mark();
   for (int r = 0; r < 3; ++r) {
     B.dw_f("enc", 3 + r, &M->enc1.dw[r], 128);
-    B.conv_f("enc", 8 + 2 * r, &M->enc1.pw[r], 128, 1, 128, SW128);
-    B.conv_f("enc", 9 + 2 * r, &M->enc1.cv[r], 128, 1, 64, SW128);
+    B.conv_f("enc", 8 + 2 * r, &M->enc1.pw[r], 128, 1, 128);
+    B.conv_f("enc", 9 + 2 * r, &M->enc1.cv[r], 128, 1, 64);
   }
-  B.conv_f("enc", 14, &M->enc1.down, 256, 4, 64, SW128);
+  B.conv_f("enc", 14, &M->enc1.down, 256, 4, 64);
   const size_t p_enc1 = B.arena.reserve(sizeof(EncS1P));
   B.range(&M->enc1.warm, mark);
   mark = B.mark();
@@ -499,8 +498,8 @@ bool build_model(const Pack& pk, int requant_mode, Model* M, std::string* err) {
   mark = B.mark();
   for (int r = 0; r < 3; ++r) {
     B.dw_f("dec", 3 + r, &M->dec1.dw[r], 128);
-    B.conv_f("dec", 7 + 2 * r, &M->dec1.pw[r], 128, 1, 128, SW128);
-    B.conv_f("dec", 8 + 2 * r, &M->dec1.cv[r], 128, 1, 64, SW128);
+    B.conv_f("dec", 7 + 2 * r, &M->dec1.pw[r], 128, 1, 128);
+    B.conv_f("dec", 8 + 2 * r, &M->dec1.cv[r], 128, 1, 64);
   }
   B.tconv_f("dec", 6, &M->dec1.up, 64, 10, 128, 5);
   {

@@ -18,23 +18,12 @@ struct TileCtx {
   int stride;          // bytes per stream in this region
   // A stream id of -1 masks a slot (DTX: the hop is noise, the encoder must not run for that stream,
   // lyra_encoder.cc:131-141): it reads stream 0's state like a tail slot reads the last stream's, and writes nothing.
-#ifdef LYRA_STATE_ALIAS   // timing experiment only (results are wrong): every stream uses one of 64 state slots -- the
-                          // per-stream state never leaves L2, so what the HBM state traffic costs shows as the difference
-  __device__ __forceinline__ uint8_t* sbase(int s) const { return state + (size_t)(max(sids[s], 0) & 63) * stride; }
-#else
   __device__ __forceinline__ uint8_t* sbase(int s) const { return state + (size_t)max(sids[s], 0) * stride; }
-#endif
   __device__ __forceinline__ bool valid(int s) const { return s < nvalid && sids[s] >= 0; }
   // The same address as sbase(s) + byte_off, formed as UNIFORM base + 32-bit per-lane offset (a region is at most
   // max_streams x 15 KB < 4 GB): the access takes the scalar-base form `global_load v, v_off, s[base:base+1]` and the
   // per-lane address arithmetic is 32-bit (one v_add_u32 where the 64-bit form needs v_lshl_add_u64 / add + addc pairs).
-  __device__ __forceinline__ uint32_t soff(int s) const {
-#ifdef LYRA_STATE_ALIAS
-    return (uint32_t)(max(sids[s], 0) & 63) * (uint32_t)stride;
-#else
-    return (uint32_t)max(sids[s], 0) * (uint32_t)stride;
-#endif
-  }
+  __device__ __forceinline__ uint32_t soff(int s) const { return (uint32_t)max(sids[s], 0) * (uint32_t)stride; }
   template <class T>
   __device__ __forceinline__ T LYRA_GLOBAL* at(uint32_t byte_off) const {
     return (T LYRA_GLOBAL*)((uint8_t LYRA_GLOBAL*)state + byte_off);
@@ -68,13 +57,12 @@ __device__ __forceinline__ void state_touch_sink(uint32_t tok, uint8_t* state, i
 // takes < 30 KB and four workgroups fit on a CU -- the whole B = 4096 batch is resident in one wave of workgroups.
 // The depthwise conv runs on (row, channel quad) items with 16-byte LDS / history accesses; the residual add is a
 // register add.
-// LYRA_SWAP64 (round 6): the GEMMs run operand-swapped (lyra_dev.h gemm_f32_core SWAP) -- xr[i][0][e] =
+// Since round 6 the GEMMs run operand-swapped (lyra_dev.h gemm_f32_core SWAP) -- xr[i][0][e] =
 // X[row (wm*5+i)*16 + (lane&15)][physical channel wn*16 + 4q + e], and every epilogue is one 16-byte LDS store per C tile.
 template <int S, int NT>
 __device__ __forceinline__ void resblocks64r(f32x4 (&xr)[5][1], float* A, const TileCtx& cx, const DwF* dws,
                                              const ConvF* pws, const ConvF* cvs, int off0, int off1, int off2) {
   constexpr int CS = 72;
-  constexpr bool SW = LYRA_SWAP64 != 0;
   static_assert(20 * S / 16 == 5 * (NT / 256), "5 M tiles per wave");
 #pragma unroll 1
   for (int r = 0; r < 3; ++r) {
@@ -85,8 +73,9 @@ __device__ __forceinline__ void resblocks64r(f32x4 (&xr)[5][1], float* A, const 
     const int lane = tid & 63, wave = tid >> 6;
     const int m = lane & 15, q = lane >> 4;
     const int wn = wave & 3, wm = wave >> 2;
-    const int ncol = wn * 16 + (lane & 15);
-    const int pcol = at16(ncol);
+    // Unused, but without it the compiler schedules this loop differently (same results, other machine code than the
+    // build every measurement in profiles/ was taken with).
+    [[maybe_unused]] const int ncol = wn * 16 + (lane & 15);
     const int d = r == 0 ? 1 : (r == 1 ? 3 : 9);
     const int R2 = 2 * d;
     const int off = r == 0 ? off0 : (r == 1 ? off1 : off2);
@@ -120,12 +109,7 @@ __device__ __forceinline__ void resblocks64r(f32x4 (&xr)[5][1], float* A, const 
     for (int i = 0; i < 5; ++i)
 {
       const f32x4 a4 = lrelu4(xr[i][0]);
-      if constexpr (SW) {
-        *reinterpret_cast<f32x4*>(&A[((wm * 5 + i) * 16 + m) * CS + wn * 16 + q * 4]) = a4;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) A[((wm * 5 + i) * 16 + q * 4 + e) * CS + pcol] = a4[e];
-      }
+      *reinterpret_cast<f32x4*>(&A[((wm * 5 + i) * 16 + m) * CS + wn * 16 + q * 4]) = a4;
     }
     __syncthreads();
     LYRA_TSTAMP(10 + r * 8 + 1);
@@ -173,30 +157,25 @@ __device__ __forceinline__ void resblocks64r(f32x4 (&xr)[5][1], float* A, const 
     WPre<1, 1> cv_pre;
     {  // 4. pointwise 64 -> 64, LeakyReLU -> A
       f32x4 acc[5][1];
-      gemm_f32_bias<5, 1, 4, 4, gemm_pf<5, 1>(), SW>(A, aoff, pws[r].w + wn * 4 * 64, pws[r].b, wn * 16, acc);
+      gemm_f32_bias<5, 1, 4, 4, gemm_pf<5, 1>(), true>(A, aoff, pws[r].w + wn * 4 * 64, pws[r].b, wn * 16, acc);
       LYRA_TSTAMP(10 + r * 8 + 5);
       // the 1x1 conv's bias + first weight chunk, requested ahead of the barrier in front of it (see resblocks128; round 5:
       // +1.0 % on the whole step, +2.1 % at 1,024 streams).  The pointwise GEMM's own request stays behind its barrier: held
       // across the depthwise phase it costs spills at the 128-VGPR cap.
-      cv_pre = gemm_f32_wprefetch<1, 4, 4, 1, SW>(cvs[r].w + wn * 4 * 64, cvs[r].b, wn * 16);
+      cv_pre = gemm_f32_wprefetch<1, 4, 4, 1, true>(cvs[r].w + wn * 4 * 64, cvs[r].b, wn * 16);
       __syncthreads();
 #pragma unroll
       for (int i = 0; i < 5; ++i)
 {
         const f32x4 a4 = lrelu4(acc[i][0]);
-        if constexpr (SW) {
-          *reinterpret_cast<f32x4*>(&A[((wm * 5 + i) * 16 + m) * CS + wn * 16 + q * 4]) = a4;
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) A[((wm * 5 + i) * 16 + q * 4 + e) * CS + pcol] = a4[e];
-        }
+        *reinterpret_cast<f32x4*>(&A[((wm * 5 + i) * 16 + m) * CS + wn * 16 + q * 4]) = a4;
       }
       __syncthreads();
       LYRA_TSTAMP(10 + r * 8 + 6);
     }
     {  // 5. 1x1 conv 64 -> 64 + residual (registers)
       f32x4 acc[5][1];
-      gemm_f32_pre<5, 1, 4, 4, gemm_pf<5, 1>(), SW>(A, aoff, cvs[r].w + wn * 4 * 64, cv_pre, acc);
+      gemm_f32_pre<5, 1, 4, 4, gemm_pf<5, 1>(), true>(A, aoff, cvs[r].w + wn * 4 * 64, cv_pre, acc);
 #pragma unroll
       for (int i = 0; i < 5; ++i)
 #pragma unroll
@@ -250,11 +229,7 @@ __device__ __forceinline__ void resblocks128(float* X, float* D, float* P, const
                                              Hist128<1024 / NT> H) {
   static_assert(S == 8 && (NT == 256 || NT == 512), "thread <-> (stream, channel quad, row half) mapping");
   constexpr int CS = 136, NTW = 8 / (NT / 64), MT = 2, RPT = 1024 / NT;
-  constexpr bool SW = LYRA_SWAP128 != 0;   // operand-swapped GEMMs (lyra_dev.h): 16-byte epilogue accesses
-#ifndef LYRA_PF128_EXTRA
-#define LYRA_PF128_EXTRA 0   // experiment: weight / operand prefetch distance of the 128-channel blocks' GEMMs, in K chunks beyond the default
-#endif
-  constexpr int PF = gemm_pf<MT, NTW>() + LYRA_PF128_EXTRA;
+  constexpr int PF = gemm_pf<MT, NTW>();   // (the GEMMs are not operand-swapped here: lyra_dev.h SWAP)
 #pragma unroll 1
   for (int r = 0; r < 3; ++r) {
     int tid = threadIdx.x;
@@ -305,15 +280,15 @@ __device__ __forceinline__ void resblocks128(float* X, float* D, float* P, const
     // The first weight chunks + bias of each GEMM are requested ahead of the barrier / elementwise phase in front of it
     // (gemm_f32_wprefetch): the L2 round trip no longer stands between the barrier and the first MFMA.  Round 5: +1.2 % on
     // the whole step at 4,096 streams (enc_s1 -1.1 us, dec_s1 -2.2 us); the same in the 64-channel blocks costs spills.
-    const auto pw_pre = gemm_f32_wprefetch<NTW, 8, 8, PF, SW>(pws[r].w + (wave * NTW) * 8 * 64, pws[r].b, wave * NTW * 16);
+    const auto pw_pre = gemm_f32_wprefetch<NTW, 8, 8, PF>(pws[r].w + (wave * NTW) * 8 * 64, pws[r].b, wave * NTW * 16);
     WPre<NTW, PF> cv_pre;
     __syncthreads();
     LYRA_TSTAMP(40 + r * 8 + 2);
     {  // pointwise 128 -> 128, LeakyReLU
       f32x4 acc[MT][NTW];
       auto aoff = [&](int i, int c) { return (i * 16 + m) * CS + c * 16 + q * 4; };
-      gemm_f32_pre<MT, NTW, 8, 8, PF, SW>(D, aoff, pws[r].w + (wave * NTW) * 8 * 64, pw_pre, acc);
-      cv_pre = gemm_f32_wprefetch<NTW, 4, 4, PF, SW>(cvs[r].w + (wave * NTW) * 4 * 64, cvs[r].b, wave * NTW * 16);
+      gemm_f32_pre<MT, NTW, 8, 8, PF>(D, aoff, pws[r].w + (wave * NTW) * 8 * 64, pw_pre, acc);
+      cv_pre = gemm_f32_wprefetch<NTW, 4, 4, PF>(cvs[r].w + (wave * NTW) * 4 * 64, cvs[r].b, wave * NTW * 16);
       LYRA_TSTAMP(40 + r * 8 + 3);
       // The next block's history rows.  vmcnt retires in order, so these loads would stall the first weight
       // fetch of a GEMM issued right after them; here they have the two barriers and the LDS-only P write
@@ -324,15 +299,10 @@ __device__ __forceinline__ void resblocks128(float* X, float* D, float* P, const
         const int ncol = (wave * NTW + j) * 16 + (lane & 15);
         const int pcol = at16(ncol);
 #pragma unroll
-        for (int i = 0; i < MT; ++i)
-{
+        for (int i = 0; i < MT; ++i) {
           const f32x4 a4 = lrelu4(acc[i][j]);
-          if constexpr (SW) {
-            *reinterpret_cast<f32x4*>(&P[(i * 16 + m) * CS + (wave * NTW + j) * 16 + q * 4]) = a4;
-          } else {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) P[(i * 16 + q * 4 + e) * CS + pcol] = a4[e];
-          }
+          for (int e = 0; e < 4; ++e) P[(i * 16 + q * 4 + e) * CS + pcol] = a4[e];
         }
       }
       __syncthreads();
@@ -342,29 +312,19 @@ __device__ __forceinline__ void resblocks128(float* X, float* D, float* P, const
       f32x4 acc[MT][NTW];
       const int g = (wave * NTW) >> 2;
       auto aoff = [&](int i, int c) { return (i * 16 + m) * CS + g * 64 + c * 16 + q * 4; };
-      gemm_f32_pre<MT, NTW, 4, 4, PF, SW>(P, aoff, cvs[r].w + (wave * NTW) * 4 * 64, cv_pre, acc);
+      gemm_f32_pre<MT, NTW, 4, 4, PF>(P, aoff, cvs[r].w + (wave * NTW) * 4 * 64, cv_pre, acc);
       LYRA_TSTAMP(40 + r * 8 + 5);
 #pragma unroll
       for (int j = 0; j < NTW; ++j) {
         const int ncol = (wave * NTW + j) * 16 + (lane & 15);
         const int pcol = at16(ncol);
 #pragma unroll
-        for (int i = 0; i < MT; ++i) {
-          if constexpr (SW) {
-            f32x4* x = reinterpret_cast<f32x4*>(&X[(i * 16 + m) * CS + (wave * NTW + j) * 16 + q * 4]);
-            const f32x4 old = *x;
-            f32x4 sum;
+        for (int i = 0; i < MT; ++i)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) sum[e] = acc[i][j][e] + old[e];
-            *x = sum;
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              float* x = &X[(i * 16 + q * 4 + e) * CS + pcol];
-              *x = acc[i][j][e] + *x;
-            }
+          for (int e = 0; e < 4; ++e) {
+            float* x = &X[(i * 16 + q * 4 + e) * CS + pcol];
+            *x = acc[i][j][e] + *x;
           }
-        }
       }
     }
     __syncthreads();
