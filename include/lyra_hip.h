@@ -302,6 +302,14 @@ int lyra_hip_decode_ext_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_ids, int 
                                            ENCODE | DTX, the encoder's d_packet_bytes[set][b] != 0; the decoder-side
                                            estimator always runs, d_is_noise is optional.  Needs DECODE, no d_features.
                                            The three fields after d_ext_out are read only with this flag. */
+#define LYRA_HIP_STEP_MIXED_BITRATE 32u /* per-stream bitrates: num_bits must be 0; step `step` takes the bit counts of row
+                                           step % n_bits_ring of d_bits_ring.  The encode leg is lyra_hip_encode_mixed_dev
+                                           (d_packet_bytes[2] required, DTX or not; packet rows LYRA_HIP_MAX_PACKET_BYTES
+                                           apart).  DECODE needs PACKET_LOSS; its leg is lyra_hip_decode_lossy_mixed_dev on
+                                           the encoder's d_packet_bytes[set] (with ENCODE) or, decode-only, on the sizes
+                                           (bits + 7) / 8 of the same bits-ring row (d_packet_ring rows 23 bytes apart),
+                                           combined with d_received_ring.  The two fields after d_is_comfort_noise are read
+                                           only with this flag. */
 typedef struct lyra_hip_steps {
   const int32_t* d_stream_ids;   /* [B] */
   int B;
@@ -327,6 +335,9 @@ typedef struct lyra_hip_steps {
   const uint8_t* d_received_ring;  /* [n_received_ring][B] 0 / 1, or NULL = all received */
   int n_received_ring;
   int32_t* d_is_comfort_noise;     /* [B] or NULL: is_comfort_noise() after the step's hop */
+  /* LYRA_HIP_STEP_MIXED_BITRATE only (appended) */
+  const int32_t* d_bits_ring;      /* [n_bits_ring][B] bit counts per step and stream: the caller's bitrate schedule */
+  int n_bits_ring;
 } lyra_hip_steps;
 int lyra_hip_run_steps_dev(lyra_hip_ctx* ctx, const lyra_hip_steps* steps);
 
@@ -360,6 +371,34 @@ int lyra_hip_decode_lossy_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_ids, in
 /* Number of d_packet_bytes values since context creation (or the last clear) that were neither 0 nor the packet size;
  * synchronises.  clear != 0 resets the count.  Negative: error. */
 long lyra_hip_decode_lossy_errors(lyra_hip_ctx* ctx, int clear);
+
+/* ---- Per-stream bitrates on the device path ------------------------------------------------------------------------------
+ * Every LyraEncoder has a bitrate of its own that set_bitrate changes between hops (lyra_encoder.cc:158-166), and
+ * LyraDecoder::SetEncodedPacket takes each packet's bitrate from its size (lyra_decoder.cc:172-179, lyra_config.h:99-106).
+ * These two calls serve a batch whose streams run at different bitrates, changing on any hop, with ONE call per side.
+ * Packet rows are LYRA_HIP_MAX_PACKET_BYTES apart in both directions; bytes past packet_bytes[b] in a row are never written
+ * by the encoder and never read by the decoder.  Neither side keeps state that depends on the bitrate.
+ *   encode_mixed: the per-row form of lyra_hip_encode_ext_dev (same resampler, DTX and rate rules; one encode-side call,
+ *     packets written on the quantizer stream).  d_num_bits [B]: a multiple of 4 in 4..184 per row; row b's packet is what
+ *     lyra_hip_encode_ext_dev makes for that stream at that bit count, byte for byte, packet_bytes[b] = num_bits[b] / 8
+ *     rounded up (the last byte of an odd stage count carries a zero low nibble); a DTX noise hop gives 0.  An invalid
+ *     d_num_bits[b] gives packet_bytes[b] = 0, leaves the row unwritten and is counted in a device error word
+ *     (lyra_hip_encode_mixed_errors); the stream's encoder state advances as for a valid row.  d_packet_bytes is required.
+ *   decode_lossy_mixed: lyra_hip_decode_lossy_dev with the packet size chosen per row as SetEncodedPacket does:
+ *     d_packet_bytes[b] == 0: no packet; 8 / 15 / 23: received at 64 / 120 / 184 bits; any other value: no packet, counted
+ *     in lyra_hip_decode_lossy_errors.  Everything else -- state, outputs, streams, combinations -- is lyra_hip_decode_lossy_dev's.
+ * Both accept LYRA_HIP_SUBBATCHES > 1 (they are not split) and lyra_hip_set_serial.  In lyra_hip_run_steps_dev:
+ * LYRA_HIP_STEP_MIXED_BITRATE. */
+#define LYRA_HIP_MAX_PACKET_BYTES 23   /* packet row stride of the mixed calls: the 184-bit packet */
+int lyra_hip_encode_mixed_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_ids, int B, const int16_t* d_pcm_ext,
+                              int sample_rate_hz, const int32_t* d_num_bits, int dtx,
+                              uint8_t* d_packets /* [B][23] */, int32_t* d_packet_bytes /* [B], required */);
+/* Number of invalid d_num_bits values since context creation (or the last clear); synchronises.  Negative: error. */
+long lyra_hip_encode_mixed_errors(lyra_hip_ctx* ctx, int clear);
+int lyra_hip_decode_lossy_mixed_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_ids, int B,
+                                    const uint8_t* d_packets /* [B][23] */, const int32_t* d_packet_bytes,
+                                    int sample_rate_hz, int16_t* d_pcm16, int16_t* d_pcm_ext,
+                                    int32_t* d_is_noise, int32_t* d_is_comfort_noise);
 
 /* ---- Decoder twin: the device half of a batched LyraDecoder (lyra_amd/host/lyra_batch_codec.cc) ------------------------
  * LyraDecoder::DecodeSamplesInternal (lyra_decoder.cc:228-315) keeps per stream the conditioned hop of the generative
@@ -471,7 +510,9 @@ int lyra_hip_profile_timeline(lyra_hip_ctx* ctx, int cap, int* kernel_ids, float
 
 /* Test hook: copies stage-boundary activations of the LAST extract/generate call (device scratch) to host.
  * which: 0 enc stage0 out [B][4][128], 1 enc stage1 out [B][2][256], 2 enc int8 codes [B][64] (as f32),
- *        3 dec head out [B][4][128], 4 dec stage1 out [B][20][64].  Channel order is the library's
+ *        3 dec head out [B][4][128], 4 dec stage1 out [B][20][64],
+ *        5 the quantizer's exact-chain counters since creation (2 floats; lyra_hip_encode_mixed_dev adds the stages
+ *        a 16-frame tile runs past a shorter frame's own count).  Channel order is the library's
  *        internal one; returns the number of floats written or a negative error. */
 long lyra_hip_debug_read(lyra_hip_ctx* ctx, int which, float* host_out, long capacity);
 

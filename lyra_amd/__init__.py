@@ -6,5 +6,5 @@ This package is only the Python mirror of the reference's plugin surface over th
 creating a codec context without the built library or without a gfx950 device raises.
 """
 from .codec import (HOP, NUM_FEATURES, LyraHip, LyraHipError, ResidualVectorQuantizer, SoundStreamEncoder,  # noqa: F401
-                    LyraGanModel, LogMelSpectrogramExtractor, bitrate_to_num_bits, packet_size, build_library,
-                    library_path, default_model_dir)
+                    LyraGanModel, LogMelSpectrogramExtractor, bitrate_to_num_bits, packet_size, MAX_PACKET_BYTES,
+                    build_library, library_path, default_model_dir)

@@ -33,6 +33,9 @@ def packet_size(num_bits):
     return (num_bits + 7) // 8  # lyra_config.h: 8 / 15 / 23 bytes
 
 
+MAX_PACKET_BYTES = 23  # LYRA_HIP_MAX_PACKET_BYTES: packet row stride of the mixed-bitrate calls
+
+
 def library_path():
     # LYRA_HIP_LIB: developer override used to A/B kernel variants on the GPU box
     return os.environ.get("LYRA_HIP_LIB") or os.path.join(HERE, "liblyra_hip.so")
@@ -62,11 +65,14 @@ class StepsDesc(C.Structure):
                 ("d_features", C.c_void_p), ("n_features", C.c_int), ("d_packet_ring", C.c_void_p), ("n_packet_ring", C.c_int), ("d_is_noise", C.c_void_p), ("external_rate", C.c_int),
                 ("d_ext_out", C.c_void_p * 2),
                 # read by the library only with STEP_PACKET_LOSS
-                ("d_received_ring", C.c_void_p), ("n_received_ring", C.c_int), ("d_is_comfort_noise", C.c_void_p)]
+                ("d_received_ring", C.c_void_p), ("n_received_ring", C.c_int), ("d_is_comfort_noise", C.c_void_p),
+                # read by the library only with STEP_MIXED_BITRATE
+                ("d_bits_ring", C.c_void_p), ("n_bits_ring", C.c_int)]
 
 
 STEP_ENCODE, STEP_DECODE, STEP_DTX, STEP_DECODER_NOISE = 1, 2, 4, 8
 STEP_PACKET_LOSS = 16
+STEP_MIXED_BITRATE = 32
 
 
 _libs = {}
@@ -129,6 +135,11 @@ def _load(path=None):
         L.lyra_hip_decode_lossy_dev.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp]
         L.lyra_hip_decode_lossy_errors.argtypes = [vp, ci]
         L.lyra_hip_decode_lossy_errors.restype = C.c_long
+    if hasattr(L, "lyra_hip_encode_mixed_dev"):
+        L.lyra_hip_encode_mixed_dev.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, vp]
+        L.lyra_hip_encode_mixed_errors.argtypes = [vp, ci]
+        L.lyra_hip_encode_mixed_errors.restype = C.c_long
+        L.lyra_hip_decode_lossy_mixed_dev.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp, vp, vp]
     L.lyra_hip_set_cng_seed.argtypes = [vp, C.c_uint64]
     L.lyra_hip_set_encoder_sample_rate.argtypes = [vp, C.c_int]
     L.lyra_hip_stream.restype = vp
@@ -539,6 +550,40 @@ class LyraHip:
         self._chk(n if n < 0 else 0)
         return n
 
+    def encode_mixed_dev(self, d_ids, d_pcm_ext, sample_rate_hz, d_num_bits, d_packets, d_packet_bytes, dtx=False):
+        """encode_ext_dev with a bit count per stream (lyra_hip_encode_mixed_dev): d_num_bits int32 [B] (multiples of 4 in
+        4..184), d_packets uint8 [B][MAX_PACKET_BYTES] (row b gets packet_bytes[b] bytes, the rest is left alone),
+        d_packet_bytes int32 [B] (0: DTX noise hop or invalid bit count, see encode_mixed_errors)."""
+        B = d_pcm_ext.shape[0]
+        n_ext = HOP * sample_rate_hz // 16000
+        self._dev_call(self.L.lyra_hip_encode_mixed_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
+                       self._dev_ptr(d_pcm_ext, "int16", (B, n_ext), "pcm"), sample_rate_hz,
+                       self._dev_ptr(d_num_bits, "int32", (B,), "num_bits"), 1 if dtx else 0,
+                       self._dev_ptr(d_packets, "uint8", (B, MAX_PACKET_BYTES), "packets"),
+                       self._dev_ptr(d_packet_bytes, "int32", (B,), "packet bytes"))
+
+    def encode_mixed_errors(self, clear=False):
+        """Invalid bit counts seen by encode_mixed_dev / run_steps with a bits ring (synchronises)."""
+        n = self.L.lyra_hip_encode_mixed_errors(self.h, 1 if clear else 0)
+        self._chk(n if n < 0 else 0)
+        return n
+
+    def decode_lossy_mixed_dev(self, d_ids, d_packets, d_packet_bytes, sample_rate_hz, d_pcm16, d_pcm_ext=None,
+                               d_is_noise=None, d_is_comfort_noise=None):
+        """decode_lossy_dev with the packet size per row (lyra_hip_decode_lossy_mixed_dev): d_packets uint8
+        [B][MAX_PACKET_BYTES], d_packet_bytes int32 [B]: 0 = no packet, 8 / 15 / 23 = received at 64 / 120 / 184 bits,
+        anything else = no packet, counted in decode_lossy_errors."""
+        B = d_packets.shape[0]
+        n_ext = HOP * sample_rate_hz // 16000
+        self._dev_call(self.L.lyra_hip_decode_lossy_mixed_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
+                       self._dev_ptr(d_packets, "uint8", (B, MAX_PACKET_BYTES), "packets"),
+                       self._dev_ptr(d_packet_bytes, "int32", (B,), "packet bytes"), sample_rate_hz,
+                       self._dev_ptr(d_pcm16, "int16", (B, HOP), "pcm"),
+                       self._dev_ptr(d_pcm_ext, "int16", (B, n_ext), "external-rate pcm") if d_pcm_ext is not None else None,
+                       self._dev_ptr(d_is_noise, "int32", (B,), "is_noise") if d_is_noise is not None else None,
+                       self._dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise")
+                       if d_is_comfort_noise is not None else None)
+
     def noise_receive_dev(self, d_ids, d_pcm, d_is_noise, side="decoder"):
         """NoiseEstimator::ReceiveSamples on device buffers: pcm int16 [B][320] -> is_noise int32 [B]."""
         B = d_pcm.shape[0]
@@ -562,19 +607,25 @@ class LyraHip:
     def run_steps_dev(self, d_ids, num_bits, n_steps, first_step=0, d_pcm_ring=None, d_packets=None, d_pcm_out=None,
                       d_features=None, d_packet_bytes=None, d_is_noise=None, external_rate=16000, d_ext_out=None,
                       encode=True, decode=True, dtx=False, decoder_noise=False, d_packet_ring=None,
-                      d_received_ring=None, d_is_comfort_noise=None, packet_loss=False):
+                      d_received_ring=None, d_is_comfort_noise=None, packet_loss=False, d_bits_ring=None):
         """lyra_hip_run_steps_dev: n_steps hops of every stream from ONE C call.  d_pcm_ring int16
         [ring][B][320 * external_rate / 16000]; d_packets / d_pcm_out / d_packet_bytes / d_ext_out: pairs of tensors
         (step i uses element (first_step + i) & 1).  packet_loss: the decode leg is decode_lossy_dev; d_received_ring
         uint8 [n][B] (None = all received; step i reads row (first_step + i) % n), with dtx DTX's empty packets are not
-        received either."""
+        received either.  d_bits_ring int32 [n][B] sets STEP_MIXED_BITRATE: step i encodes (and, decode-only, decodes) at
+        the bit counts of row (first_step + i) % n, num_bits must be 0, packet rows are MAX_PACKET_BYTES long."""
         B = d_ids.shape[0]
+        nbytes = MAX_PACKET_BYTES if d_bits_ring is not None else packet_size(num_bits)
         n_ext = HOP * external_rate // 16000
         S = StepsDesc()
         S.d_stream_ids = self._dev_ptr(d_ids, "int32", (B,), "stream ids")
         S.B, S.num_bits, S.first_step, S.n_steps = B, num_bits, first_step, n_steps
         S.flags = (STEP_ENCODE if encode else 0) | (STEP_DECODE if decode else 0) | (STEP_DTX if dtx else 0) | \
-            (STEP_DECODER_NOISE if decoder_noise else 0) | (STEP_PACKET_LOSS if packet_loss else 0)
+            (STEP_DECODER_NOISE if decoder_noise else 0) | (STEP_PACKET_LOSS if packet_loss else 0) | \
+            (STEP_MIXED_BITRATE if d_bits_ring is not None else 0)
+        if d_bits_ring is not None:
+            S.n_bits_ring = d_bits_ring.shape[0]
+            S.d_bits_ring = self._dev_ptr(d_bits_ring, "int32", (S.n_bits_ring, B), "bits ring")
         S.external_rate = external_rate
         if d_received_ring is not None:
             S.n_received_ring = d_received_ring.shape[0]
@@ -586,7 +637,7 @@ class LyraHip:
             S.d_pcm_ring = self._dev_ptr(d_pcm_ring, "int16", (S.ring, B, n_ext), "pcm ring")
         for i in range(2):
             if d_packets is not None:
-                S.d_packets[i] = self._dev_ptr(d_packets[i], "uint8", (B, packet_size(num_bits)), "packets")
+                S.d_packets[i] = self._dev_ptr(d_packets[i], "uint8", (B, nbytes), "packets")
             if d_pcm_out is not None:
                 S.d_pcm_out[i] = self._dev_ptr(d_pcm_out[i], "int16", (B, HOP), "pcm out")
             if d_packet_bytes is not None:
@@ -599,7 +650,7 @@ class LyraHip:
                                          else (B, NUM_FEATURES), "features")
         if d_packet_ring is not None:  # decode-only: received packets [n][B][bytes], step i decodes frame (first_step + i) % n
             S.n_packet_ring = d_packet_ring.shape[0]
-            S.d_packet_ring = self._dev_ptr(d_packet_ring, "uint8", (S.n_packet_ring, B, packet_size(num_bits)), "packet ring")
+            S.d_packet_ring = self._dev_ptr(d_packet_ring, "uint8", (S.n_packet_ring, B, nbytes), "packet ring")
         if d_is_noise is not None:
             S.d_is_noise = self._dev_ptr(d_is_noise, "int32", (B,), "is_noise")
         self._dev_call(self.L.lyra_hip_run_steps_dev, C.byref(S))

@@ -128,6 +128,7 @@ struct lyra_hip_ctx {
   float* d_lossy_fade = nullptr;     // [TWIN_FADE_N] cross-fade weights
   unsigned* d_lossy_err = nullptr;   // packet_bytes values that were neither 0 nor the packet size
   long n_lossy_calls = 0;
+  unsigned* d_mixed_err = nullptr;   // lyra_hip_encode_mixed_dev (mixed_api.inc): bit counts outside the quantizer's domain
   // Small host-buffer calls (the per-object plugin contract: B = 1 per blocking call) skip the copy engine: the kernels read
   // their input from and write their output to this pinned, device-mapped arena directly -- three copy packets and their
   // stream bubbles fewer per call (lyra_amd/plugin_demo --bench).  ZC_MAX streams per call.
@@ -142,6 +143,8 @@ struct lyra_hip_ctx {
   bool chunk_local = false;                       // see wait_encode_side
   bool ids_stable = false;                        // inside lyra_hip_run_steps_dev, after its first step: see enc_cross_begin
   unsigned* d_rvq_stats = nullptr;                // rvq_encode_kernel: [0] frame-stages on the exact chain, [1] wavefront-stages (debug_read 5)
+                                                  // (rvq_encode_mixed_kernel: a tile runs to its largest stage count, and
+                                                  // the stages past a shorter frame's own count are counted too)
   uint32_t cu_pat[4] = {0, 0, 0, 0};              // CU mask pattern of the e / d / q / n streams (0: none), see make_stream_kind
   int enc_noise_rate = 16000;                     // what the DTX encoder's NoiseEstimator::Create is given (lyra_hip_set_encoder_sample_rate)
   int last_B_enc = 0, last_B_dec = 0;
@@ -693,9 +696,14 @@ int launch_noise(lyra_hip_ctx* c, int side, hipStream_t st_, const int32_t* d_id
   return 0;
 }
 
+// what d_pkt_bytes of a lossy tick holds: packet sizes of one bit count (rows num_bits / 8 rounded up apart), packet sizes
+// of any bit count or the bit counts themselves (rows LYRA_HIP_MAX_PACKET_BYTES apart: mixed_api.inc)
+enum { LOSSY_UNIFORM, LOSSY_MIXED_BYTES, LOSSY_MIXED_BITS };
 int lossy_tick_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_packets, const int32_t* d_pkt_bytes,
                       const uint8_t* d_rx, int num_bits, int ext, int16_t* d_pcm16, int16_t* d_pcm_ext, int32_t* d_is_noise,
-                      int32_t* d_is_cn);   // lossy_api.inc
+                      int32_t* d_is_cn, int mixed = LOSSY_UNIFORM);   // lossy_api.inc
+int encode_mixed16(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int16_t* d_pcm, const int32_t* d_bits, bool dtx,
+                   uint8_t* d_packets, int32_t* d_packet_bytes);   // mixed_api.inc
 
 template <class K>
 hipError_t set_lds(K kernel, size_t bytes) {
@@ -948,6 +956,7 @@ void lyra_hip_destroy(lyra_hip_ctx* c) {
   if (c->sn) (void)hipStreamDestroy(c->sn);
   if (c->d_state) (void)hipFree(c->d_state);
   if (c->d_rvq_stats) (void)hipFree(c->d_rvq_stats);
+  if (c->d_mixed_err) (void)hipFree(c->d_mixed_err);
   free_model(&c->model);
   delete c;
 }
@@ -1682,6 +1691,25 @@ int lyra_hip_decode(lyra_hip_ctx* c, const int32_t* ids, int B, const uint8_t* p
 // through run_steps; profiles/r06_per_call.txt).  Here the encoder's resampler runs in front of the extractor on the
 // extractor's own stream (its output never leaves the library: no cross-side edge), and the decoder's estimator and
 // resampler are one noise-stream call behind the decoder's last stage, as inside lyra_hip_run_steps_dev.
+// The encoder's resampler of encode_ext / encode_mixed (ext != 16000): *in = the 16 kHz hop for the extractor.
+static int encode_ext_resample(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int16_t* d_pcm_ext, int ext,
+                               const int16_t** in) {
+  DEVSCOPE(c);
+  int rc = ensure_scratch(c, B);
+  if (rc) return rc;
+  // same resampler slots as lyra_hip_resample_dev(ENCODER) and run_steps' ahead launches: behind those; the 16 kHz hop
+  // goes to a library buffer that only this stream's extractor reads (the previous hop's read precedes in stream order)
+  if ((rc = wait_ahead(c))) return rc;
+  if ((rc = encq_begin(c, 0, 1))) return rc;   // (split contexts: after every chunk of the encode-side call before; serial mode: in call order)
+  if ((rc = launch_resample(c, 0, d_ids, B, d_pcm_ext, 320 * (ext / 1000) / 16, ext, 16000, c->d_rs16[0], nullptr))) return rc;
+  if (c->nsub > 1) {   // the chunks of a split encode run on se[1..]: they read what se[0] has just written
+    HIPCHK(c, hipEventRecord(c->ev_ahead_order, c->se[0]));
+    for (int k = 1; k < c->nsub; ++k) HIPCHK(c, hipStreamWaitEvent(c->se[k], c->ev_ahead_order, 0));
+  }
+  *in = c->d_rs16[0];
+  return 0;
+}
+
 int lyra_hip_encode_ext_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int16_t* d_pcm_ext, int sample_rate_hz,
                             int num_bits, int dtx, uint8_t* d_packets, int32_t* d_packet_bytes) {
   int rc = check_batch(c, B);
@@ -1695,20 +1723,7 @@ int lyra_hip_encode_ext_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, const 
     return fail(c, LYRA_HIP_EINVAL, "encode_ext: DTX at %d Hz but the encoder-side noise estimator is set up for %d Hz "
                 "(call lyra_hip_set_encoder_sample_rate(%d) first)", ext, c->enc_noise_rate, ext);
   const int16_t* in = d_pcm_ext;
-  if (ext != 16000) {
-    DEVSCOPE(c);
-    if ((rc = ensure_scratch(c, B))) return rc;
-    // same resampler slots as lyra_hip_resample_dev(ENCODER) and run_steps' ahead launches: behind those; the 16 kHz hop
-    // goes to a library buffer that only this stream's extractor reads (the previous hop's read precedes in stream order)
-    if ((rc = wait_ahead(c))) return rc;
-    if ((rc = encq_begin(c, 0, 1))) return rc;   // (split contexts: after every chunk of the encode-side call before; serial mode: in call order)
-    if ((rc = launch_resample(c, 0, d_ids, B, d_pcm_ext, 320 * (ext / 1000) / 16, ext, 16000, c->d_rs16[0], nullptr))) return rc;
-    if (c->nsub > 1) {   // the chunks of a split encode run on se[1..]: they read what se[0] has just written
-      HIPCHK(c, hipEventRecord(c->ev_ahead_order, c->se[0]));
-      for (int k = 1; k < c->nsub; ++k) HIPCHK(c, hipStreamWaitEvent(c->se[k], c->ev_ahead_order, 0));
-    }
-    in = c->d_rs16[0];
-  }
+  if (ext != 16000 && (rc = encode_ext_resample(c, d_ids, B, d_pcm_ext, ext, &in))) return rc;
   return dtx ? lyra_hip_encode_dtx_dev(c, d_ids, B, in, num_bits, d_packets, d_packet_bytes)
              : lyra_hip_encode_dev(c, d_ids, B, in, num_bits, d_packets);
 }
@@ -1744,7 +1759,17 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
   const unsigned F = S->flags;
   const bool enc = F & LYRA_HIP_STEP_ENCODE, dec = F & LYRA_HIP_STEP_DECODE, feats = S->d_features != nullptr;
   if (!enc && !dec) return fail(c, LYRA_HIP_EINVAL, "run_steps: neither ENCODE nor DECODE requested");
-  if ((enc || (dec && !feats)) && (rc = check_bits(c, S->num_bits))) return rc;
+  // MIXED_BITRATE: the fields appended after d_is_comfort_noise are read only under this flag
+  const bool mixed = F & LYRA_HIP_STEP_MIXED_BITRATE;
+  if (mixed) {
+    if (S->num_bits != 0) return fail(c, LYRA_HIP_EINVAL, "run_steps: MIXED_BITRATE takes the bits from d_bits_ring (num_bits must be 0)");
+    if (!S->d_bits_ring || S->n_bits_ring <= 0) return fail(c, LYRA_HIP_EINVAL, "run_steps: MIXED_BITRATE needs d_bits_ring / n_bits_ring >= 1");
+    if (dec && !(F & LYRA_HIP_STEP_PACKET_LOSS)) return fail(c, LYRA_HIP_EINVAL, "run_steps: MIXED_BITRATE with DECODE needs PACKET_LOSS");
+    if (enc && (!S->d_packet_bytes[0] || !S->d_packet_bytes[1]))
+      return fail(c, LYRA_HIP_EINVAL, "run_steps: MIXED_BITRATE with ENCODE needs two packet_bytes buffers");
+  } else if ((enc || (dec && !feats)) && (rc = check_bits(c, S->num_bits))) {
+    return rc;
+  }
   if (!S->d_stream_ids || S->n_steps < 0 || S->first_step < 0) return fail(c, LYRA_HIP_EINVAL, "run_steps: bad argument");
   if (enc && (!S->d_pcm_ring || S->ring <= 0)) return fail(c, LYRA_HIP_EINVAL, "run_steps: ENCODE needs d_pcm_ring / ring");
   if ((enc || (dec && !feats && !S->d_packet_ring)) && (!S->d_packets[0] || !S->d_packets[1]))
@@ -1788,6 +1813,7 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
     const long step = S->first_step + i;
     const int set = (int)(step & 1);
     c->ids_stable = i > 0;   // one id list for every step of this call
+    const int32_t* bits = mixed ? S->d_bits_ring + (size_t)(step % S->n_bits_ring) * B : nullptr;
     if (enc) {
       const int16_t* in = S->d_pcm_ring + (size_t)(step % S->ring) * B * (size_t)n_ext;
       if (rs && !rs_off_chain) {   // lyra_encoder.cc:119-122: external rate -> 16 kHz, the encoder's own resampler
@@ -1816,13 +1842,25 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
         for (int k = 0; k < c->nsub; ++k) HIPCHK(c, hipStreamWaitEvent(c->se[k], c->ev_rs_in[slot], 0));
         in = c->d_rs16[slot];
       }
-      if (F & LYRA_HIP_STEP_DTX)
+      if (mixed)
+        rc = encode_mixed16(c, S->d_stream_ids, S->B, in, bits, F & LYRA_HIP_STEP_DTX, S->d_packets[set], S->d_packet_bytes[set]);
+      else if (F & LYRA_HIP_STEP_DTX)
         rc = lyra_hip_encode_dtx_dev(c, S->d_stream_ids, S->B, in, S->num_bits, S->d_packets[set], S->d_packet_bytes[set]);
       else
         rc = lyra_hip_encode_dev(c, S->d_stream_ids, S->B, in, S->num_bits, S->d_packets[set]);
       if (rc) return rc;
     }
-    if (dec && loss) {   // lyra_hip_decode_lossy_dev (lossy_api.inc): concealment / comfort noise on the device
+    if (dec && loss && mixed) {   // lyra_hip_decode_lossy_mixed_dev (mixed_api.inc)
+      const uint8_t* pk = S->d_packets[set];
+      if (!enc && S->d_packet_ring && S->n_packet_ring > 0)
+        pk = S->d_packet_ring + (size_t)(step % S->n_packet_ring) * B * (size_t)LYRA_HIP_MAX_PACKET_BYTES;
+      const uint8_t* rx = S->d_received_ring ? S->d_received_ring + (size_t)(step % S->n_received_ring) * B : nullptr;
+      // with ENCODE the encoder's sizes; decode-only the sizes of the step's bit counts, (bits + 7) / 8
+      if ((rc = lossy_tick_launch(c, S->d_stream_ids, S->B, pk, enc ? S->d_packet_bytes[set] : bits, rx, 0, ext,
+                                  S->d_pcm_out[set], rs ? S->d_ext_out[set] : nullptr, S->d_is_noise, S->d_is_comfort_noise,
+                                  enc ? LOSSY_MIXED_BYTES : LOSSY_MIXED_BITS)))
+        return rc;
+    } else if (dec && loss) {   // lyra_hip_decode_lossy_dev (lossy_api.inc): concealment / comfort noise on the device
       const uint8_t* pk = S->d_packets[set];
       if (!enc && S->d_packet_ring && S->n_packet_ring > 0)
         pk = S->d_packet_ring + (size_t)(step % S->n_packet_ring) * B * (size_t)((S->num_bits + 7) / 8);
@@ -1913,6 +1951,7 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
     case 3: src = c->d_d0; n = (long)c->last_B_dec * 4 * 128; break;
     case 4: src = c->d_d1; n = (long)c->last_B_dec * 20 * 64; break;
     case 5: {   // the quantizer's screen: frame-stages / wavefront-stages that took the exact chain since creation
+                // (lyra_hip_encode_mixed_dev: including the stages a tile runs past a shorter frame's own count)
       if (capacity < 2) return fail(c, LYRA_HIP_EINVAL, "debug buffer needs 2 floats");
       int rc5 = sync_all(c);
       if (rc5) return rc5;
@@ -1935,3 +1974,4 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
 #include "pipe_api.inc"
 #include "twin_api.inc"
 #include "lossy_api.inc"
+#include "mixed_api.inc"

@@ -123,6 +123,15 @@ __global__ void rvq_encode_wide_kernel(const float* cb, const float* feats, int 
                                   uint8_t* packets, const int32_t* mask_ids, int32_t* packet_bytes);
 __global__ void rvq_decode_kernel(const float* cb, const int32_t* indices, const uint8_t* packets, int num_stages,
                                   int B, float* feats);
+// mixed bitrates (lyra_hip_encode_mixed_dev / lyra_hip_decode_lossy_mixed_dev): packet rows MAX_PACKET_BYTES apart (lossy_plan.h).
+// encode: frame i at bits[i] / 4 stages; an invalid bits[i] (not a multiple of 4 in 4..184) -> packet_bytes[i] = 0, row
+// unwritten, counted in *err.  The tile runs to its largest stage count: stats counts those extra stages too.
+__global__ void rvq_encode_mixed_kernel(const float* cb, const float* cbn, const float* feats, int B, const int32_t* bits,
+                                        uint8_t* packets, const int32_t* mask_ids, int32_t* packet_bytes, unsigned* stats,
+                                        unsigned* err);
+// decode: row i at the stage count of its size pkt_bytes[i] (8 / 15 / 23 -> 16 / 30 / 46, else 0)
+__global__ void rvq_decode_mixed_kernel(const float* cb, const uint8_t* packets, const int32_t* pkt_bytes, int bytes_from_bits,
+                                        int B, float* feats);
 struct MelP { const double* hann; const double* tw_re; const double* tw_im; const int* band; const double* w;
               const double* wsum;   // [160] total forward weight of every mel band (comfort-noise inverse mel)
               const double* tw4_re; const double* tw4_im;   // [768] W_1024^j, radix-4 log-mel FFT
@@ -163,6 +172,10 @@ __global__ void noise_read_kernel(const int32_t* ids, int B, const uint8_t* stat
 __global__ void lossy_plan_kernel(const int32_t* ids, int B, const int32_t* pkt_bytes, int nbytes, const uint8_t* rx_ring_row,
                                   uint8_t* cng_state, int32_t* gen_ids, int32_t* cng_ids, int32_t* est_ids, int32_t* info,
                                   float* feats, unsigned* err);
+// the same with the received rule of mixed bitrates (lossy_plan.h mixed_received)
+__global__ void lossy_plan_mixed_kernel(const int32_t* ids, int B, const int32_t* pkt_bytes, int bytes_from_bits,
+                                        const uint8_t* rx_ring_row, uint8_t* cng_state, int32_t* gen_ids, int32_t* cng_ids,
+                                        int32_t* est_ids, int32_t* info, float* feats, unsigned* err);
 // the tick's output hop per row (generative / comfort noise / cross-fade) + is_noise of unreceived rows + is_comfort_noise
 __global__ void lossy_mix_kernel(const int32_t* ids, int B, const int32_t* info, const int16_t* gan, const int16_t* cng,
                                  const float* fade_w, int16_t* out, const uint8_t* noise_state, int32_t* is_noise,

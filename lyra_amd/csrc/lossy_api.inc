@@ -50,7 +50,7 @@ int lossy_ensure(lyra_hip_ctx* c, int B) {
 // One tick of B streams.  d_pkt_bytes / d_rx may be null (every packet whole / every row received).
 int lossy_tick_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_packets, const int32_t* d_pkt_bytes,
                       const uint8_t* d_rx, int num_bits, int ext, int16_t* d_pcm16, int16_t* d_pcm_ext, int32_t* d_is_noise,
-                      int32_t* d_is_cn) {
+                      int32_t* d_is_cn, int mixed) {
   DEVSCOPE(c);
   int rc = ensure_scratch(c, B);
   if (rc) return rc;
@@ -64,9 +64,19 @@ int lossy_tick_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_
   int16_t* gan = c->d_lossy_gan[set];
   // ---- decode stream: one unsplit decode-side call (on split contexts it stands for every chunk, dec_side_done) ----
   if ((rc = dec_side_begin(c, 0, 1))) return rc;
-  if ((rc = launch_rvq_decode(c, 0, B, nullptr, d_packets, num_bits / 4, c->d_lossy_feat))) return rc;
-  hipLaunchKernelGGL(lossy_plan_kernel, dim3(cdiv(B, 256)), dim3(256), 0, c->sd[0], d_ids, B, d_pkt_bytes, (num_bits + 7) / 8,
-                     d_rx, c->sm.base[st::R_CNG], gen_ids, cng_ids, est_ids, info, c->d_lossy_feat, c->d_lossy_err);
+  if (mixed == LOSSY_UNIFORM) {
+    if ((rc = launch_rvq_decode(c, 0, B, nullptr, d_packets, num_bits / 4, c->d_lossy_feat))) return rc;
+    hipLaunchKernelGGL(lossy_plan_kernel, dim3(cdiv(B, 256)), dim3(256), 0, c->sd[0], d_ids, B, d_pkt_bytes, (num_bits + 7) / 8,
+                       d_rx, c->sm.base[st::R_CNG], gen_ids, cng_ids, est_ids, info, c->d_lossy_feat, c->d_lossy_err);
+  } else {   // rows LYRA_HIP_MAX_PACKET_BYTES apart, each at the stage count of its size (mixed_api.inc)
+    const int from_bits = mixed == LOSSY_MIXED_BITS ? 1 : 0;
+    { ProfScope ps(c, K_RVQ_DEC, c->sd[0]);
+      hipLaunchKernelGGL(rvq_decode_mixed_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sd[0], c->model.cb, d_packets, d_pkt_bytes,
+                         from_bits, B, c->d_lossy_feat); }
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(lossy_plan_mixed_kernel, dim3(cdiv(B, 256)), dim3(256), 0, c->sd[0], d_ids, B, d_pkt_bytes, from_bits,
+                       d_rx, c->sm.base[st::R_CNG], gen_ids, cng_ids, est_ids, info, c->d_lossy_feat, c->d_lossy_err);
+  }
   HIPCHK(c, hipGetLastError());
   if ((rc = launch_generate(c, 0, 0, gen_ids, B, c->d_lossy_feat, gan))) return rc;
   if ((rc = dec_side_done(c, 0, 1))) return rc;

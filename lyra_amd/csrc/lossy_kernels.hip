@@ -10,7 +10,8 @@ namespace lyra {
 // One thread per row: read the stream's control word, apply the tick, write it back, and hand out the tick's id lists
 // (-1 = the row skips that leg) and mix info.  Then the rows that conceal get ZeroFeatureEstimator::Estimate's features
 // (64 x 0.0f, zero_feature_estimator.h) in place of the RVQ decode of whatever their packet row holds.
-// A packet_bytes value other than 0 and nbytes is "not received" and counted in *err.
+// A packet_bytes value other than 0 and nbytes is "not received" and counted in *err.  MIXED: received iff packet_bytes
+// is a size of the codec (mixed_received), counted iff neither that nor 0; bytes_from_bits as in rvq_decode_mixed_kernel.
 __global__ __launch_bounds__(256) void lossy_plan_kernel(const int32_t* __restrict__ ids, int B,
                                                           const int32_t* __restrict__ pkt_bytes, int nbytes,
                                                           const uint8_t* __restrict__ rx_ring_row,
@@ -18,32 +19,22 @@ __global__ __launch_bounds__(256) void lossy_plan_kernel(const int32_t* __restri
                                                           int32_t* __restrict__ cng_ids, int32_t* __restrict__ est_ids,
                                                           int32_t* __restrict__ info, float* __restrict__ feats,
                                                           unsigned* __restrict__ err) {
-  __shared__ int rx[256];
-  const int tid = threadIdx.x, b0 = blockIdx.x * 256, b = b0 + tid;
-  if (b < B) {
-    const int id = ids[b];
-    bool r = true;
-    if (pkt_bytes) {
-      const int pb = pkt_bytes[b];
-      r = pb == nbytes;
-      if (pb != 0 && pb != nbytes) atomicAdd(err, 1u);
-    }
-    if (rx_ring_row) r = r && rx_ring_row[b] != 0;
-    uint32_t* ctl = reinterpret_cast<uint32_t*>(cng_state + (size_t)id * st::CNG_BYTES + LOSSY_CTL);
-    const LossyTick t = lossy_tick(*ctl, r);
-    *ctl = t.ctl;
-    gen_ids[b] = t.run_gen ? id : -1;
-    cng_ids[b] = t.run_cng ? id : -1;
-    est_ids[b] = t.feed_est ? id : -1;
-    info[b] = lossy_info(t);
-    rx[tid] = r ? 1 : 0;
-  } else {
-    rx[tid] = 1;
-  }
-  __syncthreads();
-  const int rows = min(256, B - b0);
-  for (int i = tid; i < rows * 64; i += 256)
-    if (!rx[i >> 6]) feats[(size_t)b0 * 64 + i] = 0.f;
+  constexpr bool MIXED = false;
+  constexpr int bytes_from_bits = 0;
+#include "lossy_plan_tile.inc"
+}
+
+// lyra_hip_decode_lossy_mixed_dev: pkt_bytes is required (sizes, or with bytes_from_bits the schedule's bit counts)
+__global__ __launch_bounds__(256) void lossy_plan_mixed_kernel(const int32_t* __restrict__ ids, int B,
+                                                                const int32_t* __restrict__ pkt_bytes, int bytes_from_bits,
+                                                                const uint8_t* __restrict__ rx_ring_row,
+                                                                uint8_t* __restrict__ cng_state, int32_t* __restrict__ gen_ids,
+                                                                int32_t* __restrict__ cng_ids, int32_t* __restrict__ est_ids,
+                                                                int32_t* __restrict__ info, float* __restrict__ feats,
+                                                                unsigned* __restrict__ err) {
+  constexpr bool MIXED = true;
+  constexpr int nbytes = 0;
+#include "lossy_plan_tile.inc"
 }
 
 // One wavefront per row, lane l writes samples l + 64 j.  The arithmetic of twin_assemble_kernel (MaybeOverlapAndInsert,

@@ -68,4 +68,12 @@ LYRA_LOSSY_HD inline int32_t lossy_info(const LossyTick& t) {
          (t.comfort_noise ? LOSSY_CN : 0) | (t.mix_dir > 0 ? LOSSY_TO_CNG : 0) | ((t.mix_fade / 320) << 8);
 }
 
+// ---- mixed bitrates (lyra_hip_decode_lossy_mixed_dev, LYRA_HIP_STEP_MIXED_BITRATE) --------------------------------------
+// Packet rows are MAX_PACKET_BYTES apart; a row is received iff its size is one of the codec's (PacketSizeToNumQuantizedBits,
+// lyra_config.h:99-106); 0 is "no packet", any other size is counted as an error and treated as no packet.
+constexpr int MAX_PACKET_BYTES = 23;    // LYRA_HIP_MAX_PACKET_BYTES
+LYRA_LOSSY_HD inline bool mixed_received(int pb) { return pb == 8 || pb == 15 || pb == MAX_PACKET_BYTES; }
+// v is a size, or with from_bits (run_steps, decode-only) a bit count of the schedule: size (bits + 7) / 8, negative -> -1
+LYRA_LOSSY_HD inline int mixed_bytes(int v, int from_bits) { return !from_bits ? v : v < 0 ? -1 : (int)(((unsigned)v + 7u) >> 3); }
+
 }  // namespace lyra
