@@ -356,8 +356,9 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* ctx, const lyra_hip_steps* steps);
  *   ticks without a packet); d_is_comfort_noise [B] (may be NULL): LyraDecoder::is_comfort_noise() after the tick.
  * ONE decode-side call for rule (2) of "Streams".  Like lyra_hip_decode_ext_dev, its outputs -- d_pcm16 included, the mix
  * writes it -- complete on the NOISE stream (lyra_hip_stream_noise / lyra_hip_stream_wait / lyra_hip_synchronize).
- * Every stream of one call must be in the hop-synchronous regime: arbitrary DecodeSamples(n) requests are
- * BatchLyraDecoder's (lyra_amd/host/lyra_batch_codec.cc).  Combinations:
+ * Every stream of one call must be in the hop-synchronous regime: requests of up to one hop of any size are
+ * lyra_hip_decode_samples_dev's (below), arbitrary DecodeSamples(n) requests BatchLyraDecoder's
+ * (lyra_amd/host/lyra_batch_codec.cc).  Combinations:
  *   - LYRA_HIP_SUBBATCHES > 1: supported; the call is not split (it stands for every chunk, as small calls do);
  *   - lyra_hip_set_serial: supported; the call then also ends with its noise-stream half before the next encode-side call;
  *   - lyra_hip_decode_dev / lyra_hip_decode_ext_dev on the same stream: allowed -- they advance the generative model as a
@@ -399,6 +400,54 @@ int lyra_hip_decode_lossy_mixed_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_i
                                     const uint8_t* d_packets /* [B][23] */, const int32_t* d_packet_bytes,
                                     int sample_rate_hz, int16_t* d_pcm16, int16_t* d_pcm_ext,
                                     int32_t* d_is_noise, int32_t* d_is_comfort_noise);
+
+/* ---- Packet loss on the device path: any request size up to one hop -----------------------------------------------------
+ * LyraDecoder::SetEncodedPacket (for the rows that got a packet) + DecodeSamples(num_samples) for B streams
+ * (lyra_decoder.cc:172-373) when the receiver's request is NOT tied to the 20 ms hop: a WebRTC-style audio device that pulls
+ * 10 ms while packets arrive every 20 ms, a jitter buffer that hands packets over early or late.  The reference's whole loop
+ * -- GetNumSamplesToGenerate, concealment, the cross-fades to and from comfort noise, the generative model's feature FIFO,
+ * the decoder-side NoiseEstimator fed with whole received hops -- runs on the device without any host decision or
+ * synchronisation.  Per stream: seven integers in the comfort-noise slot (all zero after lyra_hip_create /
+ * lyra_hip_reset_streams = the reference's initial state), plus the hop in progress of the generative model and of the
+ * comfort-noise generator and the waiting feature vectors in arrays by stream id that the first call allocates.
+ *   Packets: the row conventions of lyra_hip_decode_lossy_mixed_dev -- rows LYRA_HIP_MAX_PACKET_BYTES apart,
+ *   d_packet_bytes[b] == 0: no packet in this call; 8 / 15 / 23: a packet at 64 / 120 / 184 bits; anything else: no packet,
+ *   counted in lyra_hip_decode_samples_errors.  At most one packet per stream and call; a caller with two packets for a
+ *   stream makes two calls, the second may have num_samples == 0 (SetEncodedPacket alone; d_pcm_ext may then be NULL).
+ *   Request size: the same for every row of a call, free to change from call to call; 0 <= num_samples <=
+ *   sample_rate_hz / 50 and num_samples * 16000 divisible by sample_rate_hz (any n at 8 and 16 kHz, even n at 32 kHz,
+ *   multiples of 3 at 48 kHz; 10 ms qualifies at every rate), else LYRA_HIP_EINVAL and nothing is enqueued.  Under that rule
+ *   BufferedResampler's leftover (buffered_resampler.cc:92-147) stays empty for ever.  Other sizes, and requests above one
+ *   hop, are BatchLyraDecoder's (lyra_amd/host/lyra_batch_codec.cc).
+ *   The feature FIFO holds LYRA_HIP_DECODE_SAMPLES_FIFO waiting vectors per stream (the reference's is unbounded): a packet
+ *   that finds it full is NOT delivered -- the stream goes on as if the packet had never come -- and is counted in
+ *   lyra_hip_decode_samples_errors.  A receiver that pulls audio at the rate packets arrive never holds more than 2.
+ *   d_pcm_ext [B][num_samples] at sample_rate_hz (at 16000 the internal samples themselves); d_is_noise [B] (may be NULL):
+ *   the decoder-side estimator's is_noise() after the call; d_is_comfort_noise [B] (may be NULL): is_comfort_noise().
+ * ONE decode-side call for rule (2) of "Streams"; its outputs complete on the NOISE stream, as lyra_hip_decode_lossy_dev's
+ * do.  LYRA_HIP_SUBBATCHES > 1 (the call is not split) and lyra_hip_set_serial are supported the same way.  For
+ * num_samples = one hop the result is lyra_hip_decode_lossy_mixed_dev's bit for bit.  The state shares the comfort-noise
+ * slot with lyra_hip_decode_lossy*_dev, the decoder twin and lyra_hip_comfort_noise[_dev] but is NOT theirs: do not mix
+ * this call with any of them on one stream between resets.  lyra_hip_decode_dev / lyra_hip_decode_ext_dev on the same stream
+ * advance the generative model without the loss state, as described for lyra_hip_decode_lossy_dev. */
+#define LYRA_HIP_DECODE_SAMPLES_FIFO 4
+int lyra_hip_decode_samples_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_ids, int B,
+                                const uint8_t* d_packets /* [B][23] */, const int32_t* d_packet_bytes /* [B] */,
+                                int num_samples, int sample_rate_hz, int16_t* d_pcm_ext /* [B][num_samples] */,
+                                int32_t* d_is_noise, int32_t* d_is_comfort_noise);
+/* Invalid d_packet_bytes values plus packets that found the FIFO full since context creation (or the last clear);
+ * synchronises.  clear != 0 resets the count.  Negative: error. */
+long lyra_hip_decode_samples_errors(lyra_hip_ctx* ctx, int clear);
+/* lyra_hip_decode_samples_dev with HOST buffers in two halves, up to two requests in flight (the form of
+ * lyra_hip_decode_begin / _end; what DeviceLyraDecoder, lyra_amd/host/lyra_device_decoder.h, is built on).  begin() copies
+ * ids [B], packets [B][23] and packet_bytes [B] into pinned staging at call time (the caller's arrays may be reused at once),
+ * uploads them and enqueues the call; it does not synchronise.  end() delivers the OLDEST begun request's
+ * [B][num_samples] samples into pcm (may be NULL for a request of 0 samples) and waits for that request only: the download
+ * runs under the kernels of the request begun after it.  Errors of begin(): those of lyra_hip_decode_samples_dev, and
+ * LYRA_HIP_EINVAL when two requests are already in flight. */
+int lyra_hip_decode_samples_begin(lyra_hip_ctx* ctx, const int32_t* stream_ids, int B, const uint8_t* packets /* [B][23] */,
+                                  const int32_t* packet_bytes /* [B] */, int num_samples, int sample_rate_hz);
+int lyra_hip_decode_samples_end(lyra_hip_ctx* ctx, int16_t* pcm /* [B][num_samples] */);
 
 /* ---- Decoder twin: the device half of a batched LyraDecoder (lyra_amd/host/lyra_batch_codec.cc) ------------------------
  * LyraDecoder::DecodeSamplesInternal (lyra_decoder.cc:228-315) keeps per stream the conditioned hop of the generative

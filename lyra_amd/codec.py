@@ -140,6 +140,10 @@ def _load(path=None):
         L.lyra_hip_encode_mixed_errors.argtypes = [vp, ci]
         L.lyra_hip_encode_mixed_errors.restype = C.c_long
         L.lyra_hip_decode_lossy_mixed_dev.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp, vp, vp]
+    if hasattr(L, "lyra_hip_decode_samples_dev"):
+        L.lyra_hip_decode_samples_dev.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp]
+        L.lyra_hip_decode_samples_errors.argtypes = [vp, ci]
+        L.lyra_hip_decode_samples_errors.restype = C.c_long
     L.lyra_hip_set_cng_seed.argtypes = [vp, C.c_uint64]
     L.lyra_hip_set_encoder_sample_rate.argtypes = [vp, C.c_int]
     L.lyra_hip_stream.restype = vp
@@ -583,6 +587,30 @@ class LyraHip:
                        self._dev_ptr(d_is_noise, "int32", (B,), "is_noise") if d_is_noise is not None else None,
                        self._dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise")
                        if d_is_comfort_noise is not None else None)
+
+    def decode_samples_dev(self, d_ids, d_packets, d_packet_bytes, num_samples, sample_rate_hz, d_pcm_ext=None,
+                           d_is_noise=None, d_is_comfort_noise=None):
+        """LyraDecoder::SetEncodedPacket (rows with a packet) + DecodeSamples(num_samples) for request sizes that are not
+        tied to the hop (lyra_hip_decode_samples_dev): d_packets uint8 [B][MAX_PACKET_BYTES], d_packet_bytes int32 [B] (0 = no
+        packet, 8 / 15 / 23 = a packet, anything else counted in decode_samples_errors); 0 <= num_samples <= rate / 50 with
+        num_samples * 16000 divisible by the rate; d_pcm_ext int16 [B][num_samples] (may be None when num_samples == 0);
+        d_is_noise / d_is_comfort_noise int32 [B] optional.  The outputs complete on the noise stream."""
+        if not hasattr(self.L, "lyra_hip_decode_samples_dev"):
+            raise RuntimeError("this build of liblyra_hip.so has no lyra_hip_decode_samples_dev")
+        B = d_packets.shape[0]
+        self._dev_call(self.L.lyra_hip_decode_samples_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
+                       self._dev_ptr(d_packets, "uint8", (B, MAX_PACKET_BYTES), "packets"),
+                       self._dev_ptr(d_packet_bytes, "int32", (B,), "packet bytes"), num_samples, sample_rate_hz,
+                       self._dev_ptr(d_pcm_ext, "int16", (B, num_samples), "pcm") if d_pcm_ext is not None else None,
+                       self._dev_ptr(d_is_noise, "int32", (B,), "is_noise") if d_is_noise is not None else None,
+                       self._dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise")
+                       if d_is_comfort_noise is not None else None)
+
+    def decode_samples_errors(self, clear=False):
+        """Invalid packet sizes plus packets that found the feature FIFO full, seen by decode_samples_dev (synchronises)."""
+        n = self.L.lyra_hip_decode_samples_errors(self.h, 1 if clear else 0)
+        self._chk(n if n < 0 else 0)
+        return n
 
     def noise_receive_dev(self, d_ids, d_pcm, d_is_noise, side="decoder"):
         """NoiseEstimator::ReceiveSamples on device buffers: pcm int16 [B][320] -> is_noise int32 [B]."""

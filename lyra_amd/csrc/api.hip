@@ -128,6 +128,23 @@ struct lyra_hip_ctx {
   float* d_lossy_fade = nullptr;     // [TWIN_FADE_N] cross-fade weights
   unsigned* d_lossy_err = nullptr;   // packet_bytes values that were neither 0 nor the packet size
   long n_lossy_calls = 0;
+  // lyra_hip_decode_samples_dev (decode_samples_api.inc).  By stream id, each read and written in order on ONE
+  // stream: the feature ring by the plan kernel (decode stream), the held hops by the slice kernel (noise stream).
+  float* d_ds_ring = nullptr;        // [max_streams][DS_FIFO_DEPTH][64] feature vectors waiting for their hop
+  int16_t* d_ds_gan = nullptr;       // [max_streams][320] generative hop in progress
+  int16_t* d_ds_cng = nullptr;       // [max_streams][320] comfort-noise hop in progress
+  int ds_cap = 0;                    // per call, [2] by call parity as the lossy call's:
+  int32_t* d_ds_ids[2] = {};         // [4][ds_cap]: generative model / comfort noise pass 1 / pass 2 / estimator id lists
+  int32_t* d_ds_info[2] = {};        // [ds_cap][4] ds_info() per row
+  int16_t* d_ds_gan_new[2] = {};     // [ds_cap][320] the generative hops started in the call
+  int16_t* d_ds_cng_new = nullptr;   // [ds_cap][320] the comfort-noise hops started in the call (noise stream only)
+  int16_t* d_ds_est = nullptr;       // [ds_cap][320] completed received hops (noise stream only)
+  int16_t* d_ds_pcm16 = nullptr;     // [ds_cap][320] internal-rate output in front of the resampler (noise stream only)
+  float* d_ds_feat = nullptr;        // [ds_cap][64] features of the rows' packets / of the hops that start (decode stream only)
+  float* d_ds_fade = nullptr;        // [TWIN_FADE_N] cross-fade weights
+  unsigned* d_ds_err = nullptr;      // invalid packet sizes + packets that found the ring full
+  long n_ds_calls = 0;
+  void* ds_host = nullptr;           // DsHost: the two requests in flight of lyra_hip_decode_samples_begin / _end
   unsigned* d_mixed_err = nullptr;   // lyra_hip_encode_mixed_dev (mixed_api.inc): bit counts outside the quantizer's domain
   // Small host-buffer calls (the per-object plugin contract: B = 1 per blocking call) skip the copy engine: the kernels read
   // their input from and write their output to this pinned, device-mapped arena directly -- three copy packets and their
@@ -196,6 +213,7 @@ int sync_all(lyra_hip_ctx* c) {
 
 void twin_free(lyra_hip_ctx* c);
 void lossy_free(lyra_hip_ctx* c);
+void ds_free(lyra_hip_ctx* c);
 void pipe_free(lyra_hip_ctx* c);
 void free_scratch(lyra_hip_ctx* c) {
   void* ps[] = {c->d_ids, c->d_ids_dec, c->d_pcm_in, c->d_e0, c->d_e1, c->d_feat, c->d_feat2, c->d_codes, c->d_idx, c->d_pkt,
@@ -928,6 +946,7 @@ void lyra_hip_destroy(lyra_hip_ctx* c) {
   (void)sync_all(c);
   twin_free(c);
   lossy_free(c);
+  ds_free(c);
   pipe_free(c);
   if (c->h_zc) (void)hipHostFree(c->h_zc);
   c->h_zc = nullptr;
@@ -1975,3 +1994,4 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
 #include "twin_api.inc"
 #include "lossy_api.inc"
 #include "mixed_api.inc"
+#include "decode_samples_api.inc"

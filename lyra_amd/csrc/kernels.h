@@ -180,6 +180,18 @@ __global__ void lossy_plan_mixed_kernel(const int32_t* ids, int B, const int32_t
 __global__ void lossy_mix_kernel(const int32_t* ids, int B, const int32_t* info, const int16_t* gan, const int16_t* cng,
                                  const float* fade_w, int16_t* out, const uint8_t* noise_state, int32_t* is_noise,
                                  int32_t* is_cn);
+// ---- any request size up to one hop (decode_samples_kernels.hip, decode_samples_plan.h; lyra_hip_decode_samples_dev) ------
+// plan: transition, id lists (-1: the row skips the leg), info [B][4], feature ring push / pop, features of starting hops
+__global__ void ds_plan_kernel(const int32_t* ids, int B, const int32_t* pkt_bytes, int n_internal, uint8_t* cng_state,
+                               int32_t* gen_ids, int32_t* cng1_ids, int32_t* cng2_ids, int32_t* est_ids, int32_t* info,
+                               float* feats, float* ring, unsigned* err);
+// the whole received hop of the rows whose hop completes -> est_in [B][320]
+__global__ void ds_est_gather_kernel(const int32_t* ids, int B, const int32_t* info, const int16_t* gan_new,
+                                     const int16_t* gan_held, int16_t* est_in);
+// the row's passes (slices, cross-fade) -> out [B][out_stride]; new hops -> held hops; is_noise of rows without update; is_cn
+__global__ void ds_slice_kernel(const int32_t* ids, int B, const int32_t* info, const int16_t* gan_new, const int16_t* cng_new,
+                                int16_t* gan_held, int16_t* cng_held, const float* fade_w, int16_t* out, int out_stride,
+                                const uint8_t* noise_state, int32_t* is_noise, int32_t* is_cn);
 size_t logmel_lds_bytes();
 size_t cng_lds_bytes();
 struct ResetP { int8_t e_r2_1, e_r2_2, e_d2, e_bott, d_r0_0, d_r0_1, d_r0_2; };

@@ -1,0 +1,186 @@
+// device_decoder_demo.cc -- decoder_demo's scripted session (same arguments, same script format, same three output files)
+// with DeviceLyraDecoder (lyra_device_decoder.h) in BatchLyraDecoder's place:
+//   device_decoder_demo <model_dir> <script.txt> <pcm_in.s16> <sample_rate> <bitrate> <dtx 0|1> <num_streams>
+//                       <packets_out.bin> <lengths_out.i32> <pcm_out.s16>
+// LYRA_DEMO_PIPELINED=1: DecodeSamplesAsync(request k + 1) is issued before WaitDecoded(k).  A request the decoder refuses
+// (outside its size rule) ends the program with exit code 6, as a failed DecodeSamples ends decoder_demo.
+//
+//   device_decoder_demo --bench <model_dir> <sample_rate> <num_streams> <hops> <loss_percent> <reps>
+// times one session -- 10 ms requests, a packet every second request, two-state (Gilbert) loss with mean burst 2, host
+// buffers -- through BatchLyraDecoder and through DeviceLyraDecoder, blocking and pipelined, the four forms alternated
+// `reps` times after one untimed pass of each; one JSON line with the median and the min..max of decoded hops per second.
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iterator>
+#include <random>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "lyra_batch_codec.h"
+#include "lyra_device_decoder.h"
+
+using namespace chromemedia::codec;
+
+namespace {
+
+// packets [hops][n][ps], received [hops][n]; every hop: the received packets, then two requests of 10 ms
+template <class Dec>
+bool Session(Dec* dec, int n, int ps, int n10, int hops, const std::vector<uint8_t>& packets, const std::vector<uint8_t>& received,
+             bool pipelined, std::vector<int16_t>* out) {
+  std::vector<int32_t> ids;
+  std::vector<uint8_t> delivered;
+  int waiting = 0;
+  absl::Span<int16_t> span(out->data(), out->size());
+  for (int t = 0; t < hops; ++t) {
+    ids.clear();
+    delivered.clear();
+    for (int s = 0; s < n; ++s)
+      if (received[(size_t)t * n + s]) {
+        ids.push_back(s);
+        const uint8_t* p = packets.data() + ((size_t)t * n + s) * ps;
+        delivered.insert(delivered.end(), p, p + ps);
+      }
+    if (!ids.empty() && !dec->SetEncodedPackets(absl::MakeConstSpan(ids), absl::MakeConstSpan(delivered))) return false;
+    for (int k = 0; k < 2; ++k) {
+      if (!pipelined) {
+        if (!dec->DecodeSamples(n10, span)) return false;
+        continue;
+      }
+      if (waiting == 2) { if (!dec->WaitDecoded(span)) return false; --waiting; }
+      if (!dec->DecodeSamplesAsync(n10)) return false;
+      ++waiting;
+    }
+  }
+  for (; waiting > 0; --waiting)
+    if (!dec->WaitDecoded(span)) return false;
+  return true;
+}
+
+int Bench(int argc, char** argv) {
+  if (argc != 8) { std::fprintf(stderr, "usage: see device_decoder_demo.cc\n"); return 2; }
+  const std::string model_dir = argv[2];
+  const int rate = std::atoi(argv[3]), n = std::atoi(argv[4]), hops = std::atoi(argv[5]), reps = std::atoi(argv[7]);
+  const double loss = std::atof(argv[6]) / 100.0;
+  const int hop = rate / 50, ps = 15;
+  std::mt19937 rng(5);
+  std::vector<uint8_t> packets((size_t)hops * n * ps), received((size_t)hops * n, 1);
+  {   // packets of a real encoder over a tone + noise; the decoder's work does not depend on what they say
+    auto enc = BatchLyraEncoder::Create(rate, 1, 6000, false, model_dir, n);
+    if (!enc) return 1;
+    std::vector<int16_t> pcm((size_t)n * hop);
+    for (int t = 0; t < hops; ++t) {
+      for (auto& v : pcm) v = (int16_t)((int)(rng() % 4001) - 2000);
+      auto p = enc->Encode(absl::MakeConstSpan(pcm));
+      if (!p || (int)p->size() != n * ps) return 4;
+      std::memcpy(packets.data() + (size_t)t * n * ps, p->data(), p->size());
+    }
+  }
+  if (loss > 0) {
+    std::uniform_real_distribution<double> u(0, 1);
+    const double p_lost = loss / (2.0 * (1.0 - loss)), p_back = 0.5;
+    for (int s = 0; s < n; ++s) {
+      bool rx = true;
+      for (int t = 0; t < hops; ++t) {
+        received[(size_t)t * n + s] = rx;
+        rx = rx ? u(rng) >= p_lost : u(rng) < p_back;
+      }
+    }
+  }
+  auto batch = BatchLyraDecoder::Create(rate, 1, model_dir, n);
+  auto device = DeviceLyraDecoder::Create(rate, 1, model_dir, n);
+  if (!batch || !device) return 1;
+  std::vector<int16_t> out((size_t)n * (hop / 2));
+  const char* names[4] = {"batch_blocking", "batch_pipelined", "device_blocking", "device_pipelined"};
+  std::vector<double> fps[4];
+  for (int rep = 0; rep <= reps; ++rep)   // pass 0 warms every form up and is not counted
+    for (int f = 0; f < 4; ++f) {
+      const auto t0 = std::chrono::steady_clock::now();
+      const bool ok = f < 2 ? Session(batch.get(), n, ps, hop / 2, hops, packets, received, f == 1, &out)
+                            : Session(device.get(), n, ps, hop / 2, hops, packets, received, f == 3, &out);
+      const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      if (!ok) return 6;
+      if (rep) fps[f].push_back((double)n * hops / dt);
+    }
+  std::printf("{\"bench\": \"decode_samples_host\", \"streams\": %d, \"rate\": %d, \"loss\": %.2f, \"hops\": %d, \"reps\": %d", n, rate,
+              loss, hops, reps);
+  for (int f = 0; f < 4; ++f) {
+    std::sort(fps[f].begin(), fps[f].end());
+    std::printf(", \"%s\": {\"frames_per_s_median\": %.0f, \"min\": %.0f, \"max\": %.0f}", names[f], fps[f][fps[f].size() / 2],
+                fps[f].front(), fps[f].back());
+  }
+  std::printf("}\n");
+  return 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc > 1 && std::strcmp(argv[1], "--bench") == 0) return Bench(argc, argv);
+  if (argc != 11) { std::fprintf(stderr, "usage: see device_decoder_demo.cc\n"); return 2; }
+  const std::string model_dir = argv[1];
+  const int rate = std::atoi(argv[4]), bitrate = std::atoi(argv[5]), dtx = std::atoi(argv[6]), n = std::atoi(argv[7]);
+  std::ifstream script(argv[2]);
+  std::ifstream in(argv[3], std::ios::binary);
+  std::vector<char> raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+  std::vector<int16_t> pcm(raw.size() / 2);
+  std::memcpy(pcm.data(), raw.data(), pcm.size() * 2);
+  auto enc = BatchLyraEncoder::Create(rate, 1, bitrate, dtx != 0, model_dir, n);
+  auto dec = DeviceLyraDecoder::Create(rate, 1, model_dir, n);
+  if (!enc || !dec) { std::fprintf(stderr, "creation failed\n"); return 1; }
+  std::ofstream pk_out(argv[8], std::ios::binary), len_out(argv[9], std::ios::binary), pcm_out(argv[10], std::ios::binary);
+  const char* e = std::getenv("LYRA_DEMO_PIPELINED");
+  const bool pipelined = e && std::atoi(e) != 0;
+  const size_t frame = static_cast<size_t>(n) * (rate / 50);
+  std::vector<int> waiting;   // sizes of the requests begun and not yet delivered (at most two)
+  auto deliver_oldest = [&]() {
+    std::vector<int16_t> out(static_cast<size_t>(n) * waiting.front());
+    if (!dec->WaitDecoded(absl::Span<int16_t>(out.data(), out.size()))) return false;
+    pcm_out.write(reinterpret_cast<const char*>(out.data()), out.size() * 2);
+    waiting.erase(waiting.begin());
+    return true;
+  };
+  std::string line;
+  size_t off = 0;
+  while (std::getline(script, line)) {
+    if (line.empty()) continue;
+    std::istringstream ls(line);
+    std::string mask;
+    ls >> mask;
+    if (static_cast<int>(mask.size()) != n || off + frame > pcm.size()) return 3;
+    auto packets = enc->Encode(absl::MakeConstSpan(pcm.data() + off, frame));
+    off += frame;
+    if (!packets) return 4;
+    pk_out.write(reinterpret_cast<const char*>(packets->data()), packets->size());
+    len_out.write(reinterpret_cast<const char*>(enc->packet_lengths().data()), n * 4);
+    std::vector<int32_t> ids;
+    std::vector<uint8_t> delivered;
+    const int ps = enc->packet_size();
+    for (int s = 0; s < n; ++s)
+      if (mask[s] == '1' && enc->packet_lengths()[s] > 0) {
+        ids.push_back(s);
+        delivered.insert(delivered.end(), packets->begin() + s * ps, packets->begin() + (s + 1) * ps);
+      }
+    if (!ids.empty() && !dec->SetEncodedPackets(absl::MakeConstSpan(ids), absl::MakeConstSpan(delivered))) return 5;
+    int k;
+    while (ls >> k) {
+      if (pipelined) {
+        if (waiting.size() == 2 && !deliver_oldest()) return 6;
+        if (!dec->DecodeSamplesAsync(k)) return 6;
+        waiting.push_back(k);
+        if (dec->requests_in_flight() != static_cast<int>(waiting.size())) return 7;
+      } else {
+        auto out = dec->DecodeSamples(k);
+        if (!out || out->size() != static_cast<size_t>(n) * k) return 6;
+        pcm_out.write(reinterpret_cast<const char*>(out->data()), out->size() * 2);
+      }
+    }
+  }
+  while (!waiting.empty())
+    if (!deliver_oldest()) return 6;
+  return 0;
+}
