@@ -310,6 +310,16 @@ int lyra_hip_decode_ext_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_ids, int 
                                            (bits + 7) / 8 of the same bits-ring row (d_packet_ring rows 23 bytes apart),
                                            combined with d_received_ring.  The two fields after d_is_comfort_noise are read
                                            only with this flag. */
+#define LYRA_HIP_STEP_MIXED_RATE 64u    /* per-stream sample rates: d_rates [B] holds each stream's rate (constant over the steps
+                                           of a call), external_rate must be 0; d_pcm_ring is [ring][B][LYRA_HIP_MAX_EXT_HOP],
+                                           d_ext_out[2] are [B][LYRA_HIP_MAX_EXT_HOP].  The encode leg is
+                                           lyra_hip_encode_rates_dev (d_packet_bytes[2] required, packet rows
+                                           LYRA_HIP_MAX_PACKET_BYTES apart), the decode leg lyra_hip_decode_lossy_rates_dev
+                                           (DECODE needs PACKET_LOSS).  With MIXED_BITRATE the bits of d_bits_ring, without it
+                                           num_bits in every row.  The caller then passes the `steps` member of a
+                                           lyra_hip_steps_rates (below): d_rates is read only with this flag.  NEVER set
+                                           this flag on a plain lyra_hip_steps: the library would read the 8 bytes behind
+                                           the struct as d_rates. */
 typedef struct lyra_hip_steps {
   const int32_t* d_stream_ids;   /* [B] */
   int B;
@@ -339,6 +349,13 @@ typedef struct lyra_hip_steps {
   const int32_t* d_bits_ring;      /* [n_bits_ring][B] bit counts per step and stream: the caller's bitrate schedule */
   int n_bits_ring;
 } lyra_hip_steps;
+/* LYRA_HIP_STEP_MIXED_RATE: lyra_hip_steps with one field behind it.  lyra_hip_steps itself keeps its size and its last
+ * field (callers and bindings built against it are untouched); in memory d_rates lies exactly where a field appended to
+ * lyra_hip_steps would lie.  Call lyra_hip_run_steps_dev(ctx, &r.steps). */
+typedef struct lyra_hip_steps_rates {
+  lyra_hip_steps steps;
+  const int32_t* d_rates;          /* [B] 8000 / 16000 / 32000 / 48000 per stream */
+} lyra_hip_steps_rates;
 int lyra_hip_run_steps_dev(lyra_hip_ctx* ctx, const lyra_hip_steps* steps);
 
 /* ---- Packet loss on the device path: hop-synchronous receivers ---------------------------------------------------------
@@ -400,6 +417,45 @@ int lyra_hip_decode_lossy_mixed_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_i
                                     const uint8_t* d_packets /* [B][23] */, const int32_t* d_packet_bytes,
                                     int sample_rate_hz, int16_t* d_pcm16, int16_t* d_pcm_ext,
                                     int32_t* d_is_noise, int32_t* d_is_comfort_noise);
+
+/* ---- Per-stream sample rates on the device path -----------------------------------------------------------------------
+ * The sample rate is a property of each codec object (LyraEncoder::Create / LyraDecoder::Create: 8 / 16 / 32 / 48 kHz), so a
+ * server has streams of all four rates in one tick.  These two calls serve such a batch with ONE call per side.
+ * External-rate audio rows are LYRA_HIP_MAX_EXT_HOP samples apart in both directions; row b holds d_sample_rates[b] / 50
+ * samples, the rest of the row is never read by the encoder and never written by the decoder.  Packet rows follow the
+ * per-stream-bitrate conventions above.
+ *   Row b of either call is, bit for bit, what the uniform call gives for that stream at that rate --
+ *   lyra_hip_encode_mixed_dev(sample_rate_hz = rate[b]) after lyra_hip_set_encoder_sample_rate(rate[b]), and
+ *   lyra_hip_decode_lossy_mixed_dev(sample_rate_hz = rate[b]) -- outputs and per-stream state alike: a stream may move
+ *   between the per-row call and the uniform call at its rate from hop to hop without a reset.
+ *   The per-row calls do NOT read lyra_hip_set_encoder_sample_rate's setting: with dtx != 0 each row's NoiseEstimator runs
+ *   with the constants and the mel filterbank of its own rate (lyra_encoder.cc:82-85).
+ *   Rows at 16000 have no resampler, as in the reference (lyra_encoder.cc:59, buffered_resampler.cc:123-126): the stream's
+ *   resampler slot is neither read nor written; on the decode side the d_pcm_ext row receives the 320 samples of d_pcm16.
+ *   A d_sample_rates[b] that is none of the four rates never faults and is counted in a device error word
+ *   (lyra_hip_rates_errors).  Encoder: packet_bytes[b] = 0, the packet row is unwritten and NO state of that stream
+ *   advances (resampler, estimator, extractor): the row is treated as absent from the hop.  Decoder: the tick runs as at
+ *   16 kHz (d_pcm16, loss state, estimator as usual), the d_pcm_ext row is unwritten.
+ *   A stream's rate belongs to the stream between resets.  Calling a stream with another rate without
+ *   lyra_hip_reset_streams in between is a caller error with unspecified audio for that stream; it does not fault and does
+ *   not disturb other rows.
+ * Streams and ordering as the calls they generalise: one encode-side / one decode-side call for rule (2); packets complete
+ * on the quantizer stream, decoder outputs on the noise stream; LYRA_HIP_SUBBATCHES > 1 accepted (not split);
+ * lyra_hip_set_serial supported.  Null pointers (every argument but d_is_noise / d_is_comfort_noise is required) or B out of
+ * range: LYRA_HIP_EINVAL, nothing enqueued.  In lyra_hip_run_steps_dev: LYRA_HIP_STEP_MIXED_RATE. */
+#define LYRA_HIP_MAX_EXT_HOP 960   /* row stride, in samples, of external-rate audio in the calls below: the 48 kHz hop */
+int lyra_hip_encode_rates_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_ids, int B,
+                              const int16_t* d_pcm_ext /* [B][960] */, const int32_t* d_sample_rates /* [B] */,
+                              const int32_t* d_num_bits /* [B], as lyra_hip_encode_mixed_dev */, int dtx,
+                              uint8_t* d_packets /* [B][23] */, int32_t* d_packet_bytes /* [B], required */);
+int lyra_hip_decode_lossy_rates_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_ids, int B,
+                                    const uint8_t* d_packets /* [B][23] */, const int32_t* d_packet_bytes /* [B] */,
+                                    const int32_t* d_sample_rates /* [B] */, int16_t* d_pcm16 /* [B][320] */,
+                                    int16_t* d_pcm_ext /* [B][960], required */, int32_t* d_is_noise,
+                                    int32_t* d_is_comfort_noise);
+/* Number of invalid d_sample_rates values seen by either call since context creation (or the last clear); synchronises.
+ * Negative: error. */
+long lyra_hip_rates_errors(lyra_hip_ctx* ctx, int clear);
 
 /* ---- Packet loss on the device path: any request size up to one hop -----------------------------------------------------
  * LyraDecoder::SetEncodedPacket (for the rows that got a packet) + DecodeSamples(num_samples) for B streams

@@ -7,4 +7,5 @@ creating a codec context without the built library or without a gfx950 device ra
 """
 from .codec import (HOP, NUM_FEATURES, LyraHip, LyraHipError, ResidualVectorQuantizer, SoundStreamEncoder,  # noqa: F401
                     LyraGanModel, LogMelSpectrogramExtractor, bitrate_to_num_bits, packet_size, MAX_PACKET_BYTES,
+                    MAX_EXT_HOP, STEP_MIXED_RATE,
                     build_library, library_path, default_model_dir)

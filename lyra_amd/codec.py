@@ -34,6 +34,7 @@ def packet_size(num_bits):
 
 
 MAX_PACKET_BYTES = 23  # LYRA_HIP_MAX_PACKET_BYTES: packet row stride of the mixed-bitrate calls
+MAX_EXT_HOP = 960      # LYRA_HIP_MAX_EXT_HOP: row stride (samples) of external-rate audio in the per-stream-rate calls
 
 
 def library_path():
@@ -70,9 +71,15 @@ class StepsDesc(C.Structure):
                 ("d_bits_ring", C.c_void_p), ("n_bits_ring", C.c_int)]
 
 
+class StepsDescRates(C.Structure):
+    """lyra_hip_steps_rates: lyra_hip_steps with d_rates behind it, read by the library only with STEP_MIXED_RATE."""
+    _fields_ = [("steps", StepsDesc), ("d_rates", C.c_void_p)]
+
+
 STEP_ENCODE, STEP_DECODE, STEP_DTX, STEP_DECODER_NOISE = 1, 2, 4, 8
 STEP_PACKET_LOSS = 16
 STEP_MIXED_BITRATE = 32
+STEP_MIXED_RATE = 64
 
 
 _libs = {}
@@ -140,6 +147,11 @@ def _load(path=None):
         L.lyra_hip_encode_mixed_errors.argtypes = [vp, ci]
         L.lyra_hip_encode_mixed_errors.restype = C.c_long
         L.lyra_hip_decode_lossy_mixed_dev.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp, vp, vp]
+    if hasattr(L, "lyra_hip_encode_rates_dev"):
+        L.lyra_hip_encode_rates_dev.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, vp]
+        L.lyra_hip_decode_lossy_rates_dev.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
+        L.lyra_hip_rates_errors.argtypes = [vp, ci]
+        L.lyra_hip_rates_errors.restype = C.c_long
     if hasattr(L, "lyra_hip_decode_samples_dev"):
         L.lyra_hip_decode_samples_dev.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp]
         L.lyra_hip_decode_samples_errors.argtypes = [vp, ci]
@@ -588,6 +600,42 @@ class LyraHip:
                        self._dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise")
                        if d_is_comfort_noise is not None else None)
 
+    def encode_rates_dev(self, d_ids, d_pcm_ext, d_sample_rates, d_num_bits, d_packets, d_packet_bytes, dtx=False):
+        """encode_mixed_dev with a sample rate per stream (lyra_hip_encode_rates_dev): d_pcm_ext int16 [B][MAX_EXT_HOP], row
+        b holds d_sample_rates[b] / 50 samples; d_sample_rates int32 [B] (8000 / 16000 / 32000 / 48000; anything else:
+        packet_bytes 0, no state advances, counted in rates_errors); the rest as encode_mixed_dev.  Does not read
+        set_encoder_sample_rate's setting."""
+        B = d_pcm_ext.shape[0]
+        self._dev_call(self.L.lyra_hip_encode_rates_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
+                       self._dev_ptr(d_pcm_ext, "int16", (B, MAX_EXT_HOP), "pcm"),
+                       self._dev_ptr(d_sample_rates, "int32", (B,), "sample rates"),
+                       self._dev_ptr(d_num_bits, "int32", (B,), "num_bits"), 1 if dtx else 0,
+                       self._dev_ptr(d_packets, "uint8", (B, MAX_PACKET_BYTES), "packets"),
+                       self._dev_ptr(d_packet_bytes, "int32", (B,), "packet bytes"))
+
+    def decode_lossy_rates_dev(self, d_ids, d_packets, d_packet_bytes, d_sample_rates, d_pcm16, d_pcm_ext,
+                               d_is_noise=None, d_is_comfort_noise=None):
+        """decode_lossy_mixed_dev with a sample rate per stream (lyra_hip_decode_lossy_rates_dev): d_pcm_ext int16
+        [B][MAX_EXT_HOP], row b receives d_sample_rates[b] / 50 samples (320 copies of d_pcm16 at 16000; nothing, counted
+        in rates_errors, at a value that is no codec rate)."""
+        B = d_packets.shape[0]
+        self._dev_call(self.L.lyra_hip_decode_lossy_rates_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
+                       self._dev_ptr(d_packets, "uint8", (B, MAX_PACKET_BYTES), "packets"),
+                       self._dev_ptr(d_packet_bytes, "int32", (B,), "packet bytes"),
+                       self._dev_ptr(d_sample_rates, "int32", (B,), "sample rates"),
+                       self._dev_ptr(d_pcm16, "int16", (B, HOP), "pcm"),
+                       self._dev_ptr(d_pcm_ext, "int16", (B, MAX_EXT_HOP), "external-rate pcm"),
+                       self._dev_ptr(d_is_noise, "int32", (B,), "is_noise") if d_is_noise is not None else None,
+                       self._dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise")
+                       if d_is_comfort_noise is not None else None)
+
+    def rates_errors(self, clear=False):
+        """Sample rates seen by encode_rates_dev / decode_lossy_rates_dev / run_steps with d_rates that are no codec rate
+        (synchronises)."""
+        n = self.L.lyra_hip_rates_errors(self.h, 1 if clear else 0)
+        self._chk(n if n < 0 else 0)
+        return n
+
     def decode_samples_dev(self, d_ids, d_packets, d_packet_bytes, num_samples, sample_rate_hz, d_pcm_ext=None,
                            d_is_noise=None, d_is_comfort_noise=None):
         """LyraDecoder::SetEncodedPacket (rows with a packet) + DecodeSamples(num_samples) for request sizes that are not
@@ -635,22 +683,33 @@ class LyraHip:
     def run_steps_dev(self, d_ids, num_bits, n_steps, first_step=0, d_pcm_ring=None, d_packets=None, d_pcm_out=None,
                       d_features=None, d_packet_bytes=None, d_is_noise=None, external_rate=16000, d_ext_out=None,
                       encode=True, decode=True, dtx=False, decoder_noise=False, d_packet_ring=None,
-                      d_received_ring=None, d_is_comfort_noise=None, packet_loss=False, d_bits_ring=None):
+                      d_received_ring=None, d_is_comfort_noise=None, packet_loss=False, d_bits_ring=None,
+                      d_rates=None):
         """lyra_hip_run_steps_dev: n_steps hops of every stream from ONE C call.  d_pcm_ring int16
         [ring][B][320 * external_rate / 16000]; d_packets / d_pcm_out / d_packet_bytes / d_ext_out: pairs of tensors
         (step i uses element (first_step + i) & 1).  packet_loss: the decode leg is decode_lossy_dev; d_received_ring
         uint8 [n][B] (None = all received; step i reads row (first_step + i) % n), with dtx DTX's empty packets are not
         received either.  d_bits_ring int32 [n][B] sets STEP_MIXED_BITRATE: step i encodes (and, decode-only, decodes) at
-        the bit counts of row (first_step + i) % n, num_bits must be 0, packet rows are MAX_PACKET_BYTES long."""
+        the bit counts of row (first_step + i) % n, num_bits must be 0, packet rows are MAX_PACKET_BYTES long.
+        d_rates int32 [B] sets STEP_MIXED_RATE (the call then passes a lyra_hip_steps_rates): each stream at its own sample rate (encode_rates_dev /
+        decode_lossy_rates_dev); external_rate must be left alone, d_pcm_ring is [ring][B][MAX_EXT_HOP], d_ext_out are
+        [B][MAX_EXT_HOP], packet rows are MAX_PACKET_BYTES long."""
         B = d_ids.shape[0]
-        nbytes = MAX_PACKET_BYTES if d_bits_ring is not None else packet_size(num_bits)
+        nbytes = MAX_PACKET_BYTES if (d_bits_ring is not None or d_rates is not None) else packet_size(num_bits)
         n_ext = HOP * external_rate // 16000
-        S = StepsDesc()
+        if d_rates is not None:
+            if external_rate not in (0, 16000):   # (16000: this wrapper's "none", as without d_rates)
+                raise ValueError("run_steps_dev: d_rates and external_rate=%d exclude each other" % external_rate)
+            n_ext, external_rate = MAX_EXT_HOP, 0
+        R = StepsDescRates()
+        S = R.steps
         S.d_stream_ids = self._dev_ptr(d_ids, "int32", (B,), "stream ids")
         S.B, S.num_bits, S.first_step, S.n_steps = B, num_bits, first_step, n_steps
         S.flags = (STEP_ENCODE if encode else 0) | (STEP_DECODE if decode else 0) | (STEP_DTX if dtx else 0) | \
             (STEP_DECODER_NOISE if decoder_noise else 0) | (STEP_PACKET_LOSS if packet_loss else 0) | \
-            (STEP_MIXED_BITRATE if d_bits_ring is not None else 0)
+            (STEP_MIXED_BITRATE if d_bits_ring is not None else 0) | (STEP_MIXED_RATE if d_rates is not None else 0)
+        if d_rates is not None:
+            R.d_rates = self._dev_ptr(d_rates, "int32", (B,), "sample rates")
         if d_bits_ring is not None:
             S.n_bits_ring = d_bits_ring.shape[0]
             S.d_bits_ring = self._dev_ptr(d_bits_ring, "int32", (S.n_bits_ring, B), "bits ring")
@@ -681,7 +740,7 @@ class LyraHip:
             S.d_packet_ring = self._dev_ptr(d_packet_ring, "uint8", (S.n_packet_ring, B, nbytes), "packet ring")
         if d_is_noise is not None:
             S.d_is_noise = self._dev_ptr(d_is_noise, "int32", (B,), "is_noise")
-        self._dev_call(self.L.lyra_hip_run_steps_dev, C.byref(S))
+        self._dev_call(self.L.lyra_hip_run_steps_dev, C.byref(R.steps))
 
     def decode_dev(self, d_ids, d_packets, num_bits, d_pcm):
         B = d_pcm.shape[0]

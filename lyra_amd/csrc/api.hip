@@ -145,6 +145,15 @@ struct lyra_hip_ctx {
   unsigned* d_ds_err = nullptr;      // invalid packet sizes + packets that found the ring full
   long n_ds_calls = 0;
   void* ds_host = nullptr;           // DsHost: the two requests in flight of lyra_hip_decode_samples_begin / _end
+  // per-stream sample rates (rates_api.inc)
+  ResampleP* d_rs_tab = nullptr;     // [2][3] polyphase designs: [rate -> 16 kHz | 16 kHz -> rate][8000, 32000, 48000]
+  NoiseP* d_noise_tab = nullptr;     // [4] noise_params of 8 / 16 / 32 / 48 kHz
+  unsigned* d_rates_err = nullptr;   // d_sample_rates values that are no codec rate
+  int32_t* d_rate_ids[RS_RING] = {}; // [cap] the rows' ids, -1 where the rate is invalid (beside d_rs16: run_steps' ahead launches)
+  int32_t* d_rate_ids_call[2] = {};  // the same for the launches in front of the extractor, by encode-call parity: the
+                                     // quantizer of call t reads it under call t + 1's resampler (as d_live_ids / d_live_ids2)
+  int32_t* d_rates_bits = nullptr;   // [max_streams] run_steps MIXED_RATE without MIXED_BITRATE: num_bits in every row
+  int rates_bits_val = -1;           // (what d_rates_bits holds; -1: nothing yet)
   unsigned* d_mixed_err = nullptr;   // lyra_hip_encode_mixed_dev (mixed_api.inc): bit counts outside the quantizer's domain
   // Small host-buffer calls (the per-object plugin contract: B = 1 per blocking call) skip the copy engine: the kernels read
   // their input from and write their output to this pinned, device-mapped arena directly -- three copy packets and their
@@ -215,6 +224,7 @@ void twin_free(lyra_hip_ctx* c);
 void lossy_free(lyra_hip_ctx* c);
 void ds_free(lyra_hip_ctx* c);
 void pipe_free(lyra_hip_ctx* c);
+void rates_free(lyra_hip_ctx* c);
 void free_scratch(lyra_hip_ctx* c) {
   void* ps[] = {c->d_ids, c->d_ids_dec, c->d_pcm_in, c->d_e0, c->d_e1, c->d_feat, c->d_feat2, c->d_codes, c->d_idx, c->d_pkt,
                 c->d_lossy, c->d_d0, c->d_d1, c->d_pcm_out, c->d_mel, c->d_mel_enc, c->d_flag_enc, c->d_flag_dec,
@@ -227,6 +237,8 @@ void free_scratch(lyra_hip_ctx* c) {
   c->d_flag_enc = nullptr; c->d_flag_dec = nullptr; c->d_live_ids = nullptr; c->d_live_ids2 = nullptr; c->d_pkt_bytes = nullptr;
   c->d_rs_in = nullptr; c->d_rs_out = nullptr;
   for (auto& p : c->d_rs16) { if (p) (void)hipFree(p); p = nullptr; }
+  for (auto& p : c->d_rate_ids) { if (p) (void)hipFree(p); p = nullptr; }
+  for (auto& p : c->d_rate_ids_call) { if (p) (void)hipFree(p); p = nullptr; }
   c->cap = 0;
 }
 
@@ -260,6 +272,8 @@ int ensure_scratch(lyra_hip_ctx* c, int B) {
   HIPCHK(c, dalloc(&c->d_rs_in, n * 960));
   HIPCHK(c, dalloc(&c->d_rs_out, n * 960));
   for (auto& p : c->d_rs16) HIPCHK(c, dalloc(&p, n * 320));
+  for (auto& p : c->d_rate_ids) HIPCHK(c, dalloc(&p, n));
+  for (auto& p : c->d_rate_ids_call) HIPCHK(c, dalloc(&p, n));
   c->cap = B;
   return 0;
 }
@@ -719,9 +733,19 @@ int launch_noise(lyra_hip_ctx* c, int side, hipStream_t st_, const int32_t* d_id
 enum { LOSSY_UNIFORM, LOSSY_MIXED_BYTES, LOSSY_MIXED_BITS };
 int lossy_tick_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_packets, const int32_t* d_pkt_bytes,
                       const uint8_t* d_rx, int num_bits, int ext, int16_t* d_pcm16, int16_t* d_pcm_ext, int32_t* d_is_noise,
-                      int32_t* d_is_cn, int mixed = LOSSY_UNIFORM);   // lossy_api.inc
+                      int32_t* d_is_cn, int mixed = LOSSY_UNIFORM, const int32_t* d_rates = nullptr);   // lossy_api.inc
 int encode_mixed16(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int16_t* d_pcm, const int32_t* d_bits, bool dtx,
-                   uint8_t* d_packets, int32_t* d_packet_bytes);   // mixed_api.inc
+                   uint8_t* d_packets, int32_t* d_packet_bytes, const int32_t* d_rates = nullptr);   // mixed_api.inc
+// per-stream sample rates (rates_api.inc)
+int rates_ensure(lyra_hip_ctx* c);
+int launch_noise_rates(lyra_hip_ctx* c, hipStream_t st_, const int32_t* d_ids, const int32_t* d_rates, int B,
+                       const int16_t* d_pcm, int32_t* d_is_noise, int32_t* d_masked_ids);
+int launch_resample_rates(lyra_hip_ctx* c, int dir, const int32_t* d_ids, const int32_t* d_rates, int B, const int16_t* d_in,
+                          int in_stride, int16_t* d_out, int out_stride, int32_t* d_ids_out, hipStream_t st_);
+int encode_rates_resample(lyra_hip_ctx* c, const int32_t* d_ids, const int32_t* d_rates, int B, const int16_t* d_pcm_ext,
+                          const int16_t** in, const int32_t** ids);
+int resample_rates_in_ahead(lyra_hip_ctx* c, const int32_t* d_ids, const int32_t* d_rates, int B, const int16_t* d_in, long step);
+int rates_uniform_bits(lyra_hip_ctx* c, int num_bits, const int32_t** bits);
 
 template <class K>
 hipError_t set_lds(K kernel, size_t bytes) {
@@ -976,6 +1000,7 @@ void lyra_hip_destroy(lyra_hip_ctx* c) {
   if (c->d_state) (void)hipFree(c->d_state);
   if (c->d_rvq_stats) (void)hipFree(c->d_rvq_stats);
   if (c->d_mixed_err) (void)hipFree(c->d_mixed_err);
+  rates_free(c);
   free_model(&c->model);
   delete c;
 }
@@ -1780,6 +1805,19 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
   if (!enc && !dec) return fail(c, LYRA_HIP_EINVAL, "run_steps: neither ENCODE nor DECODE requested");
   // MIXED_BITRATE: the fields appended after d_is_comfort_noise are read only under this flag
   const bool mixed = F & LYRA_HIP_STEP_MIXED_BITRATE;
+  // MIXED_RATE: the field appended after n_bits_ring is read only under this flag
+  const bool mrate = F & LYRA_HIP_STEP_MIXED_RATE;
+  static_assert(offsetof(lyra_hip_steps_rates, steps) == 0, "lyra_hip_steps_rates starts with lyra_hip_steps");
+  const int32_t* d_rates = mrate ? reinterpret_cast<const lyra_hip_steps_rates*>(S)->d_rates : nullptr;
+  if (mrate) {
+    if (!d_rates) return fail(c, LYRA_HIP_EINVAL, "run_steps: MIXED_RATE needs d_rates");
+    if (S->external_rate != 0) return fail(c, LYRA_HIP_EINVAL, "run_steps: MIXED_RATE takes the rates from d_rates (external_rate must be 0)");
+    if (S->d_features) return fail(c, LYRA_HIP_EINVAL, "run_steps: MIXED_RATE decodes packets (no d_features)");
+    if (dec && !(F & LYRA_HIP_STEP_PACKET_LOSS)) return fail(c, LYRA_HIP_EINVAL, "run_steps: MIXED_RATE with DECODE needs PACKET_LOSS");
+    if (enc && (!S->d_packet_bytes[0] || !S->d_packet_bytes[1]))
+      return fail(c, LYRA_HIP_EINVAL, "run_steps: MIXED_RATE with ENCODE needs two packet_bytes buffers");
+    if (dec && (!S->d_ext_out[0] || !S->d_ext_out[1])) return fail(c, LYRA_HIP_EINVAL, "run_steps: two external-rate output buffers needed");
+  }
   if (mixed) {
     if (S->num_bits != 0) return fail(c, LYRA_HIP_EINVAL, "run_steps: MIXED_BITRATE takes the bits from d_bits_ring (num_bits must be 0)");
     if (!S->d_bits_ring || S->n_bits_ring <= 0) return fail(c, LYRA_HIP_EINVAL, "run_steps: MIXED_BITRATE needs d_bits_ring / n_bits_ring >= 1");
@@ -1807,16 +1845,23 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
   const bool rs = ext != 16000;
   // A DTX LyraEncoder created at `ext` hands that rate to its NoiseEstimator (lyra_encoder.cc:82-85): a step that claims to
   // run what LyraEncoder::Encode runs must not combine an external rate with another estimator
-  if ((F & LYRA_HIP_STEP_DTX) && enc && c->enc_noise_rate != ext)
+  if ((F & LYRA_HIP_STEP_DTX) && enc && !mrate && c->enc_noise_rate != ext)   // (MIXED_RATE: each row's own estimator)
     return fail(c, LYRA_HIP_EINVAL, "run_steps: DTX at external_rate %d but the encoder-side noise estimator is set up for %d Hz "
                 "(call lyra_hip_set_encoder_sample_rate(%d) first)", ext, c->enc_noise_rate, ext);
-  const int n_ext = 320 * (ext / 1000) / 16;   // samples per 20 ms hop at the external rate
+  const int n_ext = mrate ? LYRA_HIP_MAX_EXT_HOP : 320 * (ext / 1000) / 16;   // samples per 20 ms hop at the external rate
   if (rs) {
     if (ext != 8000 && ext != 32000 && ext != 48000) return fail(c, LYRA_HIP_EINVAL, "run_steps: external_rate %d", ext);
     if (dec && (!S->d_ext_out[0] || !S->d_ext_out[1])) return fail(c, LYRA_HIP_EINVAL, "run_steps: two external-rate output buffers needed");
     if ((rc = ensure_scratch(c, S->B))) return rc;
   }
   const size_t B = (size_t)S->B;
+  const int32_t* uniform_bits = nullptr;
+  if (mrate) {
+    { DEVSCOPE(c); if ((rc = rates_ensure(c))) return rc; }
+    if ((rc = ensure_scratch(c, S->B))) return rc;
+    if (!mixed && (rc = rates_uniform_bits(c, S->num_bits, &uniform_bits))) return rc;
+  }
+  const bool mrate_ahead = mrate && !c->serial && c->nsub == 1;   // (as rs_off_chain)
   // the resamplers leave the codec's chains (resample_in_ahead / resample_deferred) in the default, unsplit configuration;
   // with sub-batches or strict call order they stay where the individual calls put them
   const bool rs_off_chain = rs && !c->serial && c->nsub == 1;
@@ -1832,10 +1877,13 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
     const long step = S->first_step + i;
     const int set = (int)(step & 1);
     c->ids_stable = i > 0;   // one id list for every step of this call
-    const int32_t* bits = mixed ? S->d_bits_ring + (size_t)(step % S->n_bits_ring) * B : nullptr;
+    const int32_t* bits = mixed ? S->d_bits_ring + (size_t)(step % S->n_bits_ring) * B : uniform_bits;
     if (enc) {
       const int16_t* in = S->d_pcm_ring + (size_t)(step % S->ring) * B * (size_t)n_ext;
-      if (rs && !rs_off_chain) {   // lyra_encoder.cc:119-122: external rate -> 16 kHz, the encoder's own resampler
+      const int32_t* enc_ids = S->d_stream_ids;
+      if (mrate && !mrate_ahead) {   // the per-row input resampler in front of the extractor, as lyra_hip_encode_rates_dev
+        if ((rc = encode_rates_resample(c, S->d_stream_ids, d_rates, S->B, in, &in, &enc_ids))) return rc;
+      } else if (rs && !rs_off_chain) {   // lyra_encoder.cc:119-122: external rate -> 16 kHz, the encoder's own resampler
         if ((rc = lyra_hip_resample_dev(c, LYRA_HIP_SIDE_ENCODER, S->d_stream_ids, S->B, in, n_ext, ext, 16000, c->d_pcm_in))) return rc;
         in = c->d_pcm_in;
         {   // the chunks of a split encode run on se[1..]: they read what se[0] has just written
@@ -1845,12 +1893,13 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
             for (int k = 1; k < c->nsub; ++k) HIPCHK(c, hipStreamWaitEvent(c->se[k], c->ev_ahead_order, 0));
           }
         }
-      } else if (rs) {         // ... two steps ahead, on the quantizer stream (resample_in_ahead)
+      } else if (rs || mrate) {   // ... two steps ahead, on the quantizer stream (resample_in_ahead / resample_rates_in_ahead)
         DEVSCOPE(c);
         auto ahead = [&](int j) {   // the hop of step first_step + j, if this call has one
           if (j >= S->n_steps) return 0;
           const int16_t* src = S->d_pcm_ring + (size_t)((S->first_step + j) % S->ring) * B * (size_t)n_ext;
-          return resample_in_ahead(c, S->d_stream_ids, S->B, src, n_ext, ext, S->first_step + j);
+          return mrate ? resample_rates_in_ahead(c, S->d_stream_ids, d_rates, S->B, src, S->first_step + j)
+                       : resample_in_ahead(c, S->d_stream_ids, S->B, src, n_ext, ext, S->first_step + j);
         };
         if (i == 0) {
           if ((rc = ahead_begin(c))) return rc;
@@ -1860,24 +1909,27 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
         const int slot = (int)(step % lyra_hip_ctx::RS_RING);
         for (int k = 0; k < c->nsub; ++k) HIPCHK(c, hipStreamWaitEvent(c->se[k], c->ev_rs_in[slot], 0));
         in = c->d_rs16[slot];
+        if (mrate) enc_ids = c->d_rate_ids[slot];
       }
-      if (mixed)
-        rc = encode_mixed16(c, S->d_stream_ids, S->B, in, bits, F & LYRA_HIP_STEP_DTX, S->d_packets[set], S->d_packet_bytes[set]);
+      if (mixed || mrate)
+        rc = encode_mixed16(c, enc_ids, S->B, in, bits, F & LYRA_HIP_STEP_DTX, S->d_packets[set], S->d_packet_bytes[set],
+                            d_rates);
       else if (F & LYRA_HIP_STEP_DTX)
         rc = lyra_hip_encode_dtx_dev(c, S->d_stream_ids, S->B, in, S->num_bits, S->d_packets[set], S->d_packet_bytes[set]);
       else
         rc = lyra_hip_encode_dev(c, S->d_stream_ids, S->B, in, S->num_bits, S->d_packets[set]);
       if (rc) return rc;
     }
-    if (dec && loss && mixed) {   // lyra_hip_decode_lossy_mixed_dev (mixed_api.inc)
+    if (dec && loss && (mixed || mrate)) {   // lyra_hip_decode_lossy_mixed_dev (mixed_api.inc) / _rates_dev (rates_api.inc)
       const uint8_t* pk = S->d_packets[set];
       if (!enc && S->d_packet_ring && S->n_packet_ring > 0)
         pk = S->d_packet_ring + (size_t)(step % S->n_packet_ring) * B * (size_t)LYRA_HIP_MAX_PACKET_BYTES;
       const uint8_t* rx = S->d_received_ring ? S->d_received_ring + (size_t)(step % S->n_received_ring) * B : nullptr;
       // with ENCODE the encoder's sizes; decode-only the sizes of the step's bit counts, (bits + 7) / 8
       if ((rc = lossy_tick_launch(c, S->d_stream_ids, S->B, pk, enc ? S->d_packet_bytes[set] : bits, rx, 0, ext,
-                                  S->d_pcm_out[set], rs ? S->d_ext_out[set] : nullptr, S->d_is_noise, S->d_is_comfort_noise,
-                                  enc ? LOSSY_MIXED_BYTES : LOSSY_MIXED_BITS)))
+                                  S->d_pcm_out[set], (rs || mrate) ? S->d_ext_out[set] : nullptr, S->d_is_noise,
+                                  S->d_is_comfort_noise, enc ? LOSSY_MIXED_BYTES : LOSSY_MIXED_BITS,
+                                  d_rates)))
         return rc;
     } else if (dec && loss) {   // lyra_hip_decode_lossy_dev (lossy_api.inc): concealment / comfort noise on the device
       const uint8_t* pk = S->d_packets[set];
@@ -1994,4 +2046,5 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
 #include "twin_api.inc"
 #include "lossy_api.inc"
 #include "mixed_api.inc"
+#include "rates_api.inc"
 #include "decode_samples_api.inc"

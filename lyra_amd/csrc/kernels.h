@@ -146,6 +146,12 @@ __global__ void logmel_kernel(const MelP* P, const int16_t* pcm, const int32_t* 
 __global__ void logmel_masked_kernel(const MelP* P, const int16_t* pcm, const int32_t* ids, int B, uint8_t* state, int stride,
                                      int prev_off, float* mel, int noise_tail, NoiseP NP, int32_t* is_noise_out,
                                      int32_t* masked_ids);
+// per-stream sample rates (lyra_hip_encode_rates_dev): P4 = the four rates' MelP (8 / 16 / 32 / 48 kHz), np_tab the four NoiseP,
+// rates[i] the rate of row i; rows of id -1 are skipped and named -1 in masked_ids
+__global__ void logmel_rates_kernel(const MelP* P4, const int16_t* pcm, const int32_t* ids, const int32_t* rates, int B,
+                                    uint8_t* state, int stride, int prev_off, const NoiseP* np_tab, int32_t* is_noise_out,
+                                    int32_t* masked_ids);
+size_t logmel_rates_lds_bytes();
 __global__ void noise_update_kernel(NoiseP P, const int32_t* ids, int B, uint8_t* state, const float* mel,
                                     int32_t* is_noise_out, int32_t* masked_ids);
 // Resampler (lyra/resampler.cc): out/in = up/down, coef[phase][tap] oldest tap first (oracle lo_resampler_design)
@@ -155,6 +161,13 @@ size_t resample_lds_bytes(int n_in);
 // in_stride / out_stride: samples between consecutive streams' rows (>= n_in / n_out: a chunk of longer rows)
 __global__ void resample_kernel(ResampleP P, const int32_t* ids, int B, uint8_t* state, const int16_t* in, int n_in,
                                 int in_stride, int16_t* out, int n_out, int out_stride);
+// per-stream sample rates: tab [2][3] = [dir][8000, 32000, 48000]; dir 0: rates[b] -> 16 kHz, 1: 16 kHz -> rates[b]; a row at
+// 16000 is copied (320 samples), any other non-codec rate writes nothing and is counted in *err; ids_out (optional):
+// ids[b], or -1 for such a row
+__global__ void resample_rates_kernel(const ResampleP* tab, int dir, const int32_t* rates, const int32_t* ids, int B,
+                                      uint8_t* state, const int16_t* in, int in_stride, int16_t* out, int out_stride,
+                                      int32_t* ids_out, unsigned* err);
+size_t resample_rates_lds_bytes();
 // ---- device half of BatchLyraDecoder (host/lyra_batch_codec.cc): hop buffers stay on the device, the host keeps ints --
 // One slice of LyraDecoder::DecodeSamplesInternal's loop for one stream (lyra_decoder.cc:228-315): which samples of the
 // conditioned generative-model hop and of the comfort-noise hop go where, and how they are cross-faded

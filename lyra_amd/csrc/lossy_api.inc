@@ -50,7 +50,7 @@ int lossy_ensure(lyra_hip_ctx* c, int B) {
 // One tick of B streams.  d_pkt_bytes / d_rx may be null (every packet whole / every row received).
 int lossy_tick_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_packets, const int32_t* d_pkt_bytes,
                       const uint8_t* d_rx, int num_bits, int ext, int16_t* d_pcm16, int16_t* d_pcm_ext, int32_t* d_is_noise,
-                      int32_t* d_is_cn, int mixed) {
+                      int32_t* d_is_cn, int mixed, const int32_t* d_rates) {
   DEVSCOPE(c);
   int rc = ensure_scratch(c, B);
   if (rc) return rc;
@@ -95,7 +95,11 @@ int lossy_tick_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_
                        (const int16_t*)gan, (const int32_t*)est_ids, B, c->sm.base[st::R_NOISE_D], (int)st::NOISE_BYTES,
                        (int)st::N_PREV, (float*)nullptr, 1, noise_params(16000), d_is_noise, (int32_t*)nullptr); }
   HIPCHK(c, hipGetLastError());
-  if (ext != 16000) {
+  if (d_rates) {   // per-stream rates (rates_api.inc): d_pcm_ext rows LYRA_HIP_MAX_EXT_HOP apart
+    if ((rc = launch_resample_rates(c, 1, d_ids, d_rates, B, d_pcm16, 320, d_pcm_ext, LYRA_HIP_MAX_EXT_HOP, nullptr, c->sn)))
+      return rc;
+    c->rs_sn_pending = true;
+  } else if (ext != 16000) {
     if ((rc = launch_resample(c, 1, d_ids, B, d_pcm16, 320, 16000, ext, d_pcm_ext, nullptr, 0, 0, c->sn))) return rc;
     c->rs_sn_pending = true;
   }

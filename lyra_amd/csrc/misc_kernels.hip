@@ -350,15 +350,23 @@ __device__ __forceinline__ int digit_reverse4_1024(int n) {   // reverse the fiv
 // trip of the 160 bins through HBM (`mel` may then be null).
 // kMasked (logmel_masked_kernel): an id of -1 masks its row -- no history, no estimator, no output is touched (the decoder-
 // side estimator of lyra_hip_decode_lossy_dev runs only on the received rows of a tick).
-template <bool kMasked>
+// kRates (logmel_rates_kernel): `Pp` is the array of the four rates' MelP (model.h d_mel_rate), `rates` holds one rate per
+// row and `np_tab` the four NoiseP; the two streams of a workgroup may differ in rate, so the mel weights (a second table
+// in LDS behind the FFT buffer), the band edges and the estimator's constants are selected per stream.
+__device__ __forceinline__ int mel_rate_index(int rate) { return rate == 8000 ? 0 : rate == 32000 ? 2 : rate == 48000 ? 3 : 1; }
+size_t logmel_rates_lds_bytes() { return (size_t)(1024 * 2 + 514) * 8; }
+
+template <bool kMasked, bool kRates = false>
 __device__ __forceinline__ void logmel_body(const MelP* __restrict__ Pp, const int16_t* __restrict__ pcm,
                                             const int32_t* __restrict__ ids, int B,
                                             uint8_t* __restrict__ state, int stride, int prev_off,
                                             float* __restrict__ mel, int noise_tail, NoiseP NP,
                                             int32_t* __restrict__ is_noise_out,
-                                            int32_t* __restrict__ masked_ids) {
+                                            int32_t* __restrict__ masked_ids,
+                                            const int32_t* __restrict__ rates = nullptr,
+                                            const NoiseP* __restrict__ np_tab = nullptr) {
   typedef double f64x2 __attribute__((ext_vector_type(2)));
-  const MelP& P = *Pp;
+  const MelP& P = Pp[kRates ? 1 : 0];   // (window and twiddles are the same tables at every rate)
   extern __shared__ __attribute__((aligned(16))) double dsm[];
   f64x2* z = reinterpret_cast<f64x2*>(dsm);   // Z[1024], (re, im) = (frame A, frame B) interleaved; later (|X_A[k]|, |X_B[k]|)
   // LDS reuse once the two spectra are separated (z[k], k > 512, is then dead): the mel weights of bins 0..512, the hop's
@@ -371,6 +379,9 @@ __device__ __forceinline__ void logmel_body(const MelP* __restrict__ Pp, const i
   int b0_ = blockIdx.x * 2;
   bool two_ = b0_ + 1 < B;
   if constexpr (kMasked) {   // a masked first row hands its place to the second one (out_index follows b0)
+    if constexpr (kRates) {   // the list the extractor and the quantizer run on names masked rows too
+      if (masked_ids && tid < 2 && b0_ + tid < B && ids[b0_ + tid] < 0) masked_ids[b0_ + tid] = -1;
+    }
     const bool ok0 = ids[b0_] >= 0, ok1 = two_ && ids[b0_ + 1] >= 0;
     if (!ok0 && !ok1) return;   // (workgroup-uniform, before any barrier)
     if (!ok0) b0_ += 1;
@@ -378,6 +389,10 @@ __device__ __forceinline__ void logmel_body(const MelP* __restrict__ Pp, const i
   }
   const int b0 = b0_, b1 = b0 + 1;
   const bool two = two_;
+  int ri0 = 1, ri1 = 1;
+  if constexpr (kRates) { ri0 = mel_rate_index(rates[b0]); ri1 = mel_rate_index(rates[two ? b1 : b0]); }
+  const MelP& PA = Pp[kRates ? ri0 : 0];   // frame 0's / frame 1's filterbank
+  const MelP& PB = Pp[kRates ? ri1 : 0];
   LYRA_TSTAMP(110);
   int16_t* prev0 = reinterpret_cast<int16_t*>(state + (size_t)ids[b0] * stride + prev_off);
   int16_t* prev1 = reinterpret_cast<int16_t*>(state + (size_t)ids[two ? b1 : b0] * stride + prev_off);
@@ -402,12 +417,17 @@ __device__ __forceinline__ void logmel_body(const MelP* __restrict__ Pp, const i
     w1r = P.tw4_re[t1]; w1i = P.tw4_im[t1]; w2r = P.tw4_re[2 * t1]; w2i = P.tw4_im[2 * t1];
     w3r = P.tw4_re[3 * t1]; w3i = P.tw4_im[3 * t1];
   }
-  const double wsel0 = P.w[tid], wsel1 = P.w[tid + 256], wsel2 = tid == 0 ? P.w[512] : 0.0;
+  const double wsel0 = PA.w[tid], wsel1 = PA.w[tid + 256], wsel2 = tid == 0 ? PA.w[512] : 0.0;
+  double vsel0 = 0.0, vsel1 = 0.0, vsel2 = 0.0;
+  if constexpr (kRates) { vsel0 = PB.w[tid]; vsel1 = PB.w[tid + 256]; vsel2 = tid == 0 ? PB.w[512] : 0.0; }
   // band sums: 320 (frame, band) items on 256 threads -- thread t < 160 takes (frame 0, band t), thread t >= 160 takes
   // (frame 1, band t - 96) i.e. the 96 widest bands, and threads t < 64 then also take (frame 1, band t), the narrow ones:
   // the longest chain is ONE wide band (<= 18 bins)
   const int my_band = tid < 160 ? tid : tid - 96;
-  const int be0 = P.band[my_band], be1 = P.band[my_band + 1], be2 = P.band[my_band + 2];
+  const int* bandp = (kRates && tid >= 160) ? PB.band : PA.band;
+  const int be0 = bandp[my_band], be1 = bandp[my_band + 1], be2 = bandp[my_band + 2];
+  int ce0 = be0, ce1 = be1, ce2 = be2;   // edges of the second item (frame 1, band tid) of threads < 64
+  if constexpr (kRates) { if (tid < 64) { ce0 = PB.band[tid]; ce1 = PB.band[tid + 1]; ce2 = PB.band[tid + 2]; } }
   {
     const double ar = (double)a0 * h0, ai = two ? (double)a1 * h0 : 0.0;
     const double br = (double)b0s * h1, bi = two ? (double)b1s * h1 : 0.0;
@@ -472,6 +492,12 @@ __device__ __forceinline__ void logmel_body(const MelP* __restrict__ Pp, const i
   wl[tid] = wsel0;
   wl[tid + 256] = wsel1;
   if (tid == 0) wl[512] = wsel2;
+  double* wl1 = kRates ? dsm + 2048 : wl;   // frame 1's weights
+  if constexpr (kRates) {
+    wl1[tid] = vsel0;
+    wl1[tid + 256] = vsel1;
+    if (tid == 0) wl1[512] = vsel2;
+  }
   __syncthreads();
   LYRA_TSTAMP(114);
   // the noise tail's view of the stream's slot is requested here, one batch, and arrives under the band sums
@@ -481,14 +507,17 @@ __device__ __forceinline__ void logmel_body(const MelP* __restrict__ Pp, const i
   if (noise_tail) npre = noise_prefetch(tail_id, state, tw < 2);
   // bins whose lower band is b-1 contribute (v - v*w) to band b, bins whose lower band is b contribute v*w; ascending
   // bin order (== the reference's scatter loop order per band); the next bin's operands are read one trip ahead
+  // (what band_item sums over is rebound per item under kRates: each frame has its own edges and weights)
+  int e0 = be0, e1 = be1, e2 = be2;
+  const double* wt = (kRates && tid >= 160) ? wl1 : wl;
   auto band_item = [&](int f, int band) {
     const double* mag = dsm + f;          // |X_f[i]| = mag[2 * i]
     double acc = 0.0;
-    double v = mag[2 * be0], wv = wl[be0];
-    for (int i = be0; i < be2; ++i) {
-      const double vn = mag[2 * i + 2], wn = wl[i + 1];
+    double v = mag[2 * e0], wv = wt[e0];
+    for (int i = e0; i < e2; ++i) {
+      const double vn = mag[2 * i + 2], wn = wt[i + 1];
       const double w = v * wv;
-      acc += i < be1 ? v - w : w;
+      acc += i < e1 ? v - w : w;
       v = vn; wv = wn;
     }
     float x = (float)acc;
@@ -500,6 +529,7 @@ __device__ __forceinline__ void logmel_body(const MelP* __restrict__ Pp, const i
   };
   if (tid < 160) band_item(0, tid);
   else if (two) band_item(1, tid - 96);
+  if constexpr (kRates) { e0 = ce0; e1 = ce1; e2 = ce2; wt = wl1; }
   if (tid < 64 && two) band_item(1, tid);
   LYRA_TSTAMP(115);
   if (noise_tail) {   // (uniform)
@@ -507,6 +537,7 @@ __device__ __forceinline__ void logmel_body(const MelP* __restrict__ Pp, const i
     LYRA_TSTAMP2(120);
     const int w = tw;
     const bool on = w == 0 || (w == 1 && two);
+    if constexpr (kRates) NP = np_tab[(w & 1) ? ri1 : ri0];   // (wave-uniform)
     noise_update_wave<2>(NP, w, on, tail_id, b0 + (w & 1), state, mel_lds + (w & 1) * 160, npre, tail_sh, tail_avg,
                          is_noise_out, masked_ids);
   }
@@ -530,6 +561,19 @@ __global__ __launch_bounds__(256) void logmel_masked_kernel(const MelP* __restri
                                                              int32_t* __restrict__ masked_ids) {
   LYRA_STRESS(7);
   logmel_body<true>(Pp, pcm, ids, B, state, stride, prev_off, mel, noise_tail, NP, is_noise_out, masked_ids);
+}
+// Per-stream sample rates (lyra_hip_encode_rates_dev): the DTX encoder's NoiseEstimator with each row's own filterbank
+// and constants; rows of id -1 (invalid rate) are skipped as in logmel_masked_kernel and named -1 in masked_ids.
+__global__ __launch_bounds__(256) void logmel_rates_kernel(const MelP* __restrict__ P4, const int16_t* __restrict__ pcm,
+                                                            const int32_t* __restrict__ ids,
+                                                            const int32_t* __restrict__ rates, int B,
+                                                            uint8_t* __restrict__ state, int stride, int prev_off,
+                                                            const NoiseP* __restrict__ np_tab,
+                                                            int32_t* __restrict__ is_noise_out,
+                                                            int32_t* __restrict__ masked_ids) {
+  LYRA_STRESS(7);
+  logmel_body<true, true>(P4, pcm, ids, B, state, stride, prev_off, nullptr, 1, NoiseP{}, is_noise_out, masked_ids, rates,
+                          np_tab);
 }
 
 // =============================================================================================
@@ -729,15 +773,7 @@ __global__ __launch_bounds__(256) void resample_kernel(ResampleP P, const int32_
   const int16_t* src = in + (size_t)bb * in_stride;
   // the new samples do not wait for the stream id; 16-byte items when the rows allow it
   const bool vec = ((in_stride | n_in) & 7) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
-  if (vec) {
-    for (int c = lane; c * 8 < n_in; c += 64) {
-      const i32x4 raw = *reinterpret_cast<const i32x4*>(src + c * 8);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) rsb[H + c * 8 + e] = (float)(int16_t)((raw[e >> 1] >> ((e & 1) * 16)) & 0xffff);
-    }
-  } else {
-    for (int i = lane; i < n_in; i += 64) rsb[H + i] = (float)src[i];
-  }
+#include "resample_load.inc"
   uint8_t* slot = state + (size_t)ids[bb] * st::RS_BYTES;
   float* hist = reinterpret_cast<float*>(slot + st::RS_HIST);
   const int in_pos = *reinterpret_cast<const int*>(slot + st::RS_IN_POS);
@@ -745,40 +781,61 @@ __global__ __launch_bounds__(256) void resample_kernel(ResampleP P, const int32_
   __syncthreads();
   if (!on) return;
   int16_t* dst = out + (size_t)b * out_stride;
-  auto clip = [](float acc) { return (int16_t)(acc < -32768.f ? -32768.f : (acc > 32767.f ? 32767.f : acc)); };   // ClipToInt16 (dsp_utils.h:56-72)
-  if (P.down == 1) {
-    // interpolation: output k * up + ph is phase ph of the window at input k -- a lane takes input positions
-    // k = lane, lane + 64, ...: one window of 35 samples in registers feeds all `up` phases, coefficients are scalars
-    for (int k = lane; k < n_in; k += 64) {
-      float win[st::RS_TAPS];
-#pragma unroll
-      for (int j = 0; j < st::RS_TAPS; ++j) win[j] = rsb[k + j];
-#pragma unroll
-      for (int ph = 0; ph < 3; ++ph) {
-        if (ph < P.up) {
-          float acc = 0.f;
-#pragma unroll
-          for (int j = 0; j < st::RS_TAPS; ++j) acc = acc + P.coef[ph][j] * win[j];
-          dst[k * P.up + ph] = clip(acc);
-        }
-      }
+#include "resample_fir.inc"
+}
+
+// Per-stream sample rates (lyra_hip_encode_rates_dev / lyra_hip_decode_lossy_rates_dev): row b is resampled between
+// rates[b] and 16 kHz with the design of its own rate.  tab = [2][3] designs, [dir][8000, 32000, 48000]; dir 0: rates[b]
+// -> 16 kHz (rows hold rates[b] / 50 samples in, 320 out), dir 1: 16 kHz -> rates[b].  One wavefront per stream as above,
+// so the design index is wave-uniform (readfirstlane) and the coefficients stay scalar operands; the LDS row is sized for
+// 48 kHz.  A row at 16000 is copied through and its slot not touched; any other value that is not a codec rate writes
+// nothing, is counted in *err and named -1 in ids_out (optional: ids[b] for every other row).  No workgroup barrier: a
+// wavefront only reads the LDS row it wrote.
+size_t resample_rates_lds_bytes() { return (size_t)4 * ((st::RS_TAPS - 1 + 960 + 3) & ~3) * 4; }
+
+__global__ __launch_bounds__(256) void resample_rates_kernel(const ResampleP* __restrict__ tab, int dir,
+                                                              const int32_t* __restrict__ rates,
+                                                              const int32_t* __restrict__ ids, int B,
+                                                              uint8_t* __restrict__ state, const int16_t* __restrict__ in,
+                                                              int in_stride, int16_t* __restrict__ out, int out_stride,
+                                                              int32_t* __restrict__ ids_out, unsigned* __restrict__ err) {
+  LYRA_STRESS(8);
+  extern __shared__ __attribute__((aligned(16))) float rsb_all[];   // [4][RS_TAPS - 1 + 960, padded to 4]
+  constexpr int H = st::RS_TAPS - 1;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const int b = blockIdx.x * 4 + w;
+  if (b >= B) return;
+  const int rate = __builtin_amdgcn_readfirstlane(rates[b]);
+  const int di = rate == 8000 ? 0 : rate == 32000 ? 1 : rate == 48000 ? 2 : -1;
+  const int id = ids[b];
+  const int16_t* src = in + (size_t)b * in_stride;
+  int16_t* dst = out + (size_t)b * out_stride;
+  if (di < 0) {   // (wave-uniform)
+    if (rate == 16000) {
+      for (int i = lane; i < 320; i += 64) dst[i] = src[i];
+    } else if (lane == 0) {
+      atomicAdd(err, 1u);
     }
-  } else {
-    // decimation: the first input index (0-based in this call) that yields an output follows from the carried phase
-    const int first = (P.down - in_pos % P.down) % P.down;
-    for (int o = lane; o < n_out; o += 64) {
-      const int k = first + o * P.down;
-      float acc = 0.f;
-#pragma unroll
-      for (int j = 0; j < st::RS_TAPS; ++j) acc = acc + P.coef[0][j] * rsb[k + j];
-      dst[o] = clip(acc);
-    }
+    if (ids_out && lane == 0) ids_out[b] = rate == 16000 ? id : -1;
+    return;
   }
-  // (same wavefront wrote and read this row: no barrier needed before the history leaves it)
-  if (lane < H) hist[lane] = rsb[n_in + lane];
-  // only the decimation phase is ever used: kept modulo 6 = lcm of the possible `down` factors (1, 2, 3), so the
-  // counter never wraps out of phase however long the stream runs (the oracle keeps an unbounded counter)
-  if (lane == 0) *reinterpret_cast<int*>(slot + st::RS_IN_POS) = (in_pos + n_in) % 6;
+  if (ids_out && lane == 0) ids_out[b] = id;
+  const ResampleP& P = tab[dir * 3 + di];
+  const int n_ext = rate / 50;
+  const int n_in = dir == 0 ? n_ext : 320, n_out = dir == 0 ? 320 : n_ext;
+  float* rsb = rsb_all + w * ((H + 960 + 3) & ~3);
+  const bool vec = (in_stride & 7) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;   // (every n_in is a multiple of 8)
+#include "resample_load.inc"
+  uint8_t* slot = state + (size_t)id * st::RS_BYTES;
+  float* hist = reinterpret_cast<float*>(slot + st::RS_HIST);
+  const int in_pos = *reinterpret_cast<const int*>(slot + st::RS_IN_POS);
+  if (lane < H) rsb[lane] = hist[lane];
+  // the FIR reads what other lanes of this wavefront have just written to its LDS row: no workgroup barrier is possible
+  // behind the early returns above and none is needed, but the order is pinned rather than assumed
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#include "resample_fir.inc"
 }
 
 // =============================================================================================

@@ -13,9 +13,10 @@ static_assert(lyra::MAX_PACKET_BYTES == LYRA_HIP_MAX_PACKET_BYTES, "packet row s
 namespace {
 
 // One unsplit encode-side call at 16 kHz: [noise estimator ->] extractor on se[0], quantizer on sq[0] (the structure of
-// lyra_hip_encode_dev with one chunk, and of lyra_hip_encode_dtx_dev).
+// lyra_hip_encode_dev with one chunk, and of lyra_hip_encode_dtx_dev).  d_rates (rates_api.inc): the estimator runs with each
+// row's own rate, and d_ids may hold -1 for rows that are absent from this hop (no state advances, packet_bytes 0).
 int encode_mixed16(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int16_t* d_pcm, const int32_t* d_bits, bool dtx,
-                   uint8_t* d_packets, int32_t* d_packet_bytes) {
+                   uint8_t* d_packets, int32_t* d_packet_bytes, const int32_t* d_rates) {
   DEVSCOPE(c);
   int rc = ensure_scratch(c, B);
   if (rc) return rc;
@@ -30,7 +31,8 @@ int encode_mixed16(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int16_t* 
     live = (c->n_encq_calls & 1) ? c->d_live_ids2 : c->d_live_ids;
     const EventList busy = encq_buffer_free(c, 0, 1);
     for (int i = 0; i < busy.n; ++i) HIPCHK(c, hipStreamWaitEvent(c->se[0], busy.e[i], 0));
-    rc = launch_noise(c, 0, c->se[0], d_ids, B, d_pcm, c->d_flag_enc, live);
+    rc = d_rates ? launch_noise_rates(c, c->se[0], d_ids, d_rates, B, d_pcm, c->d_flag_enc, live)
+                 : launch_noise(c, 0, c->se[0], d_ids, B, d_pcm, c->d_flag_enc, live);
     if (!rc) rc = launch_extract(c, 0, 0, live, B, d_pcm, feat);
   } else {
     rc = launch_extract(c, 0, 0, d_ids, B, d_pcm, feat, encq_buffer_free(c, 0, 1));
@@ -39,7 +41,7 @@ int encode_mixed16(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int16_t* 
   if (!rc) {
     { ProfScope ps(c, K_RVQ_ENC, c->sq[0]);
       hipLaunchKernelGGL(rvq_encode_mixed_kernel, dim3(cdiv(B, 16)), dim3(64), 0, c->sq[0], c->model.cb, c->model.cbn, feat, B,
-                         d_bits, d_packets, (const int32_t*)live, d_packet_bytes, c->d_rvq_stats, c->d_mixed_err); }
+                         d_bits, d_packets, (const int32_t*)(live ? live : d_rates ? d_ids : nullptr), d_packet_bytes, c->d_rvq_stats, c->d_mixed_err); }
     HIPCHK(c, hipGetLastError());
     rc = encq_done(c, 0);
   }

@@ -1,0 +1,37 @@
+// resample_fir.inc -- the polyphase FIR of one stream's pass and the write-back of its slot, textually shared by
+// resample_kernel and resample_rates_kernel (misc_kernels.hip).  Expects in scope: P (ResampleP), rsb (the wavefront's LDS
+// row [H history | n_in new samples]), n_in, n_out, in_pos, dst, hist, slot, lane, H.
+  auto clip = [](float acc) { return (int16_t)(acc < -32768.f ? -32768.f : (acc > 32767.f ? 32767.f : acc)); };   // ClipToInt16 (dsp_utils.h:56-72)
+  if (P.down == 1) {
+    // interpolation: output k * up + ph is phase ph of the window at input k -- a lane takes input positions
+    // k = lane, lane + 64, ...: one window of 35 samples in registers feeds all `up` phases, coefficients are scalars
+    for (int k = lane; k < n_in; k += 64) {
+      float win[st::RS_TAPS];
+#pragma unroll
+      for (int j = 0; j < st::RS_TAPS; ++j) win[j] = rsb[k + j];
+#pragma unroll
+      for (int ph = 0; ph < 3; ++ph) {
+        if (ph < P.up) {
+          float acc = 0.f;
+#pragma unroll
+          for (int j = 0; j < st::RS_TAPS; ++j) acc = acc + P.coef[ph][j] * win[j];
+          dst[k * P.up + ph] = clip(acc);
+        }
+      }
+    }
+  } else {
+    // decimation: the first input index (0-based in this call) that yields an output follows from the carried phase
+    const int first = (P.down - in_pos % P.down) % P.down;
+    for (int o = lane; o < n_out; o += 64) {
+      const int k = first + o * P.down;
+      float acc = 0.f;
+#pragma unroll
+      for (int j = 0; j < st::RS_TAPS; ++j) acc = acc + P.coef[0][j] * rsb[k + j];
+      dst[o] = clip(acc);
+    }
+  }
+  // (same wavefront wrote and read this row: no barrier needed before the history leaves it)
+  if (lane < H) hist[lane] = rsb[n_in + lane];
+  // only the decimation phase is ever used: kept modulo 6 = lcm of the possible `down` factors (1, 2, 3), so the
+  // counter never wraps out of phase however long the stream runs (the oracle keeps an unbounded counter)
+  if (lane == 0) *reinterpret_cast<int*>(slot + st::RS_IN_POS) = (in_pos + n_in) % 6;
