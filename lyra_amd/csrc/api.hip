@@ -114,7 +114,7 @@ struct lyra_hip_ctx {
   int16_t* d_twin_ext = nullptr;   // [max_streams][twin_ext_n] ... resampled
   size_t twin_out_cap = 0, twin_ext_cap = 0;   // samples allocated
   int twin_out_n = 0;              // row length of the request in flight (0: none)
-  float* d_twin_fade = nullptr;    // [TWIN_FADE_N] cross-fade weights
+  float* d_fade = nullptr;         // [TWIN_FADE_N] cross-fade weights (fade_ensure): the twin's, the lossy tick's and decode_samples' mix
   int32_t* d_twin_iota = nullptr;  // [max_streams] 0, 1, 2, ...
   uint8_t* h_twin_args = nullptr;  // pinned
   // lyra_hip_decode_lossy_dev (lossy_api.inc): the tick's scratch.  What the noise-stream leg of call i reads is rewritten
@@ -125,7 +125,6 @@ struct lyra_hip_ctx {
   int16_t* d_lossy_gan[2] = {};      // [lossy_cap][320] generative hop
   int16_t* d_lossy_cng = nullptr;    // [lossy_cap][320] comfort-noise hop (noise stream only)
   float* d_lossy_feat = nullptr;     // [lossy_cap][64] lossy features (decode stream only)
-  float* d_lossy_fade = nullptr;     // [TWIN_FADE_N] cross-fade weights
   unsigned* d_lossy_err = nullptr;   // packet_bytes values that were neither 0 nor the packet size
   long n_lossy_calls = 0;
   // lyra_hip_decode_samples_dev (decode_samples_api.inc).  By stream id, each read and written in order on ONE
@@ -141,7 +140,6 @@ struct lyra_hip_ctx {
   int16_t* d_ds_est = nullptr;       // [ds_cap][320] completed received hops (noise stream only)
   int16_t* d_ds_pcm16 = nullptr;     // [ds_cap][320] internal-rate output in front of the resampler (noise stream only)
   float* d_ds_feat = nullptr;        // [ds_cap][64] features of the rows' packets / of the hops that start (decode stream only)
-  float* d_ds_fade = nullptr;        // [TWIN_FADE_N] cross-fade weights
   unsigned* d_ds_err = nullptr;      // invalid packet sizes + packets that found the ring full
   long n_ds_calls = 0;
   void* ds_host = nullptr;           // DsHost: the two requests in flight of lyra_hip_decode_samples_begin / _end
@@ -225,20 +223,42 @@ void lossy_free(lyra_hip_ctx* c);
 void ds_free(lyra_hip_ctx* c);
 void pipe_free(lyra_hip_ctx* c);
 void rates_free(lyra_hip_ctx* c);
+// One owner per device buffer.  Buffers that are sized by one count (the frames of a call, the streams of the context) are
+// listed ONCE, as {slot, bytes per row, name}; free_bufs and alloc_bufs walk that list.  dfree is for the buffers with a size
+// of their own.  (A slot is the T* member seen as a void*, the hipMalloc((void**)&p) idiom of dalloc: it assumes that all
+// object pointers share one representation and that the compiler does not tell pointer types apart for aliasing.)
+struct Buf { void** slot; size_t row_bytes; const char* name; };
+using Bufs = std::vector<Buf>;
+template <class T>
+Buf buf_of(T*& p, size_t per_row, const char* name) { return {(void**)&p, per_row * sizeof(T), name}; }
+#define BUF(p, per_row) buf_of(p, per_row, #p)
+template <class... T>
+void dfree(T*&... p) { ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...); }
+void free_bufs(const Bufs& bs) {
+  for (const Buf& b : bs) dfree(*b.slot);
+}
+int alloc_bufs(lyra_hip_ctx* c, const Bufs& bs, size_t rows) {   // what is missing: after a failed allocation the next call allocates the rest
+  for (const Buf& b : bs) {
+    if (*b.slot) continue;
+    const hipError_t e = hipMalloc(b.slot, rows * b.row_bytes);
+    if (e != hipSuccess) return fail(c, LYRA_HIP_EHIP, "dalloc(&%s, %zu bytes): %s", b.name, rows * b.row_bytes, hipGetErrorString(e));
+  }
+  return 0;
+}
+
+Bufs scratch_bufs(lyra_hip_ctx* c) {   // per frame of `cap`
+  Bufs bs = {BUF(c->d_ids, 1), BUF(c->d_ids_dec, 1), BUF(c->d_pcm_in, 320), BUF(c->d_e0, 4 * 128), BUF(c->d_e1, 2 * 256),
+             BUF(c->d_feat, 64), BUF(c->d_feat2, 64), BUF(c->d_codes, 64), BUF(c->d_idx, 46), BUF(c->d_pkt, 23),
+             BUF(c->d_lossy, 64), BUF(c->d_d0, 4 * 128), BUF(c->d_d1, 20 * 64), BUF(c->d_pcm_out, 320), BUF(c->d_mel, 160),
+             BUF(c->d_mel_enc, 160), BUF(c->d_flag_enc, 1), BUF(c->d_flag_dec, 1), BUF(c->d_live_ids, 1),
+             BUF(c->d_live_ids2, 1), BUF(c->d_pkt_bytes, 1), BUF(c->d_rs_in, 960), BUF(c->d_rs_out, 960)};
+  for (auto& p : c->d_rs16) bs.push_back(buf_of(p, 320, "c->d_rs16[]"));
+  for (auto& p : c->d_rate_ids) bs.push_back(buf_of(p, 1, "c->d_rate_ids[]"));
+  for (auto& p : c->d_rate_ids_call) bs.push_back(buf_of(p, 1, "c->d_rate_ids_call[]"));
+  return bs;
+}
 void free_scratch(lyra_hip_ctx* c) {
-  void* ps[] = {c->d_ids, c->d_ids_dec, c->d_pcm_in, c->d_e0, c->d_e1, c->d_feat, c->d_feat2, c->d_codes, c->d_idx, c->d_pkt,
-                c->d_lossy, c->d_d0, c->d_d1, c->d_pcm_out, c->d_mel, c->d_mel_enc, c->d_flag_enc, c->d_flag_dec,
-                c->d_live_ids, c->d_live_ids2, c->d_pkt_bytes, c->d_rs_in, c->d_rs_out};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  c->d_ids = nullptr; c->d_ids_dec = nullptr; c->d_pcm_in = nullptr; c->d_e0 = nullptr; c->d_e1 = nullptr;
-  c->d_feat = nullptr; c->d_feat2 = nullptr; c->d_codes = nullptr; c->d_idx = nullptr; c->d_pkt = nullptr; c->d_lossy = nullptr;
-  c->d_d0 = nullptr; c->d_d1 = nullptr; c->d_pcm_out = nullptr; c->d_mel = nullptr; c->d_mel_enc = nullptr;
-  c->d_flag_enc = nullptr; c->d_flag_dec = nullptr; c->d_live_ids = nullptr; c->d_live_ids2 = nullptr; c->d_pkt_bytes = nullptr;
-  c->d_rs_in = nullptr; c->d_rs_out = nullptr;
-  for (auto& p : c->d_rs16) { if (p) (void)hipFree(p); p = nullptr; }
-  for (auto& p : c->d_rate_ids) { if (p) (void)hipFree(p); p = nullptr; }
-  for (auto& p : c->d_rate_ids_call) { if (p) (void)hipFree(p); p = nullptr; }
+  free_bufs(scratch_bufs(c));
   c->cap = 0;
 }
 
@@ -247,33 +267,7 @@ int ensure_scratch(lyra_hip_ctx* c, int B) {
   int rc = sync_all(c);
   if (rc) return rc;
   free_scratch(c);
-  size_t n = (size_t)B;
-  HIPCHK(c, dalloc(&c->d_ids, n));
-  HIPCHK(c, dalloc(&c->d_ids_dec, n));
-  HIPCHK(c, dalloc(&c->d_pcm_in, n * 320));
-  HIPCHK(c, dalloc(&c->d_e0, n * 4 * 128));
-  HIPCHK(c, dalloc(&c->d_e1, n * 2 * 256));
-  HIPCHK(c, dalloc(&c->d_feat, n * 64));
-  HIPCHK(c, dalloc(&c->d_feat2, n * 64));
-  HIPCHK(c, dalloc(&c->d_codes, n * 64));
-  HIPCHK(c, dalloc(&c->d_idx, n * 46));
-  HIPCHK(c, dalloc(&c->d_pkt, n * 23));
-  HIPCHK(c, dalloc(&c->d_lossy, n * 64));
-  HIPCHK(c, dalloc(&c->d_d0, n * 4 * 128));
-  HIPCHK(c, dalloc(&c->d_d1, n * 20 * 64));
-  HIPCHK(c, dalloc(&c->d_pcm_out, n * 320));
-  HIPCHK(c, dalloc(&c->d_mel, n * 160));
-  HIPCHK(c, dalloc(&c->d_mel_enc, n * 160));
-  HIPCHK(c, dalloc(&c->d_flag_enc, n));
-  HIPCHK(c, dalloc(&c->d_flag_dec, n));
-  HIPCHK(c, dalloc(&c->d_live_ids, n));
-  HIPCHK(c, dalloc(&c->d_live_ids2, n));
-  HIPCHK(c, dalloc(&c->d_pkt_bytes, n));
-  HIPCHK(c, dalloc(&c->d_rs_in, n * 960));
-  HIPCHK(c, dalloc(&c->d_rs_out, n * 960));
-  for (auto& p : c->d_rs16) HIPCHK(c, dalloc(&p, n * 320));
-  for (auto& p : c->d_rate_ids) HIPCHK(c, dalloc(&p, n));
-  for (auto& p : c->d_rate_ids_call) HIPCHK(c, dalloc(&p, n));
+  if ((rc = alloc_bufs(c, scratch_bufs(c), (size_t)B))) return rc;
   c->cap = B;
   return 0;
 }
@@ -290,6 +284,12 @@ int check_bits(lyra_hip_ctx* c, int num_bits) {
     return fail(c, LYRA_HIP_EINVAL, "The number of bits cannot exceed maximum (%d).", 4 * LYRA_HIP_MAX_STAGES);
   if (num_bits <= 0 || num_bits % 4 != 0)
     return fail(c, LYRA_HIP_EINVAL, "The number of bits (%d) has to be divisible by the number of bits per quantizer (4).", num_bits);
+  return 0;
+}
+
+int check_rate(lyra_hip_ctx* c, int rate) {
+  if (rate != 8000 && rate != 16000 && rate != 32000 && rate != 48000)
+    return fail(c, LYRA_HIP_EINVAL, "sample rate %d Hz is not supported by the codec (lyra_config.h:57)", rate);
   return 0;
 }
 
@@ -551,6 +551,45 @@ struct DeviceScope {
   DeviceScope devscope_((c)->device); \
   if (!devscope_.ok) return fail(c, LYRA_HIP_EHIP, "hipSetDevice(%d) failed", (c)->device)
 
+// lyra_hip_*_errors: one of the device error counters since context creation (or the last clear); synchronises
+long read_error_counter(lyra_hip_ctx* c, unsigned* lyra_hip_ctx::*counter, int clear) {
+  if (!c) return LYRA_HIP_EINVAL;
+  unsigned* d_err = c->*counter;
+  if (!d_err) return 0;
+  DEVSCOPE(c);
+  int rc = sync_all(c);
+  if (rc) return rc;
+  unsigned n = 0;
+  HIPCHK(c, hipMemcpy(&n, d_err, 4, hipMemcpyDeviceToHost));
+  if (clear) HIPCHK(c, hipMemset(d_err, 0, 4));
+  return (long)n;
+}
+
+// How a blocking host-buffer call moves its arguments.  A small call (lyra_hip_ctx::zc) skips the copy engine: memcpy into and
+// out of the pinned, device-mapped arena, which the kernels read and write directly; any other goes through the staging
+// buffers with hipMemcpyAsync on the call's stream.  at() picks the device-side pointer of an argument accordingly.
+struct HostIO {
+  lyra_hip_ctx* c; hipStream_t st; bool zc;
+  void* out_host = nullptr; const void* out_dev = nullptr; size_t out_bytes = 0;
+  template <class T>
+  T* at(size_t zc_offset, T* staging) const { return zc ? (T*)(c->h_zc + zc_offset) : staging; }
+  int in(void* dev, const void* host, size_t bytes) {
+    if (zc) std::memcpy(dev, host, bytes);
+    else HIPCHK(c, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, st));
+    return 0;
+  }
+  int out(void* host, const void* dev, size_t bytes) {   // behind the kernels: the copy engine's download is enqueued here
+    out_host = host; out_dev = dev; out_bytes = bytes;
+    if (!zc) HIPCHK(c, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+    return 0;
+  }
+  int finish() {   // ... the arena is read once the stream has drained
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (zc) std::memcpy(out_host, out_dev, out_bytes);
+    return 0;
+  }
+};
+
 // chunk k of a batch of B frames: [lo, lo + n), multiples of 16 streams so tiles stay whole
 void chunk_of(const lyra_hip_ctx* c, int B, int k, int* lo, int* n) {
   int per = (B / c->nsub + 15) / 16 * 16;
@@ -561,6 +600,32 @@ void chunk_of(const lyra_hip_ctx* c, int B, int k, int* lo, int* n) {
   *n = b - a;
 }
 int chunks_for(const lyra_hip_ctx* c, int B) { return (c->nsub > 1 && B >= 64 * c->nsub) ? c->nsub : 1; }
+
+// The chunk loop of a `_dev` call of one kind: CALL_ENC (enc_side_begin / _done), CALL_DEC (dec_side_begin / _done) or
+// CALL_ENCQ (encq_begin / encq_done; the body hands over to the quantizer itself).  body(k, lo, n, nk) enqueues chunk k,
+// frames [lo, lo + n); split = false: one chunk that stands for every chunk.  The call's bookkeeping follows its last chunk,
+// whether or not a chunk failed.
+enum CallKind { CALL_ENC, CALL_DEC, CALL_ENCQ };
+template <class Body>
+int run_chunks(lyra_hip_ctx* c, CallKind kind, int B, bool split, Body body) {
+  const int nk = split ? chunks_for(c, B) : 1;
+  int rc = 0;
+  for (int k = 0; k < nk && !rc; ++k) {
+    int lo = 0, n = B;
+    if (nk > 1) chunk_of(c, B, k, &lo, &n);
+    if (n <= 0) continue;
+    rc = kind == CALL_ENC ? enc_side_begin(c, k, nk) : kind == CALL_DEC ? dec_side_begin(c, k, nk) : encq_begin(c, k, nk);
+    if (!rc) rc = body(k, lo, n, nk);
+    if (!rc) rc = kind == CALL_ENC ? enc_side_done(c, k, nk) : kind == CALL_DEC ? dec_side_done(c, k, nk) : encq_done(c, k);
+  }
+  if (kind == CALL_ENCQ) {
+    c->encq_nk[c->n_encq_calls & 1] = nk;
+    c->n_encq_calls++;
+  }
+  if (kind == CALL_DEC) c->n_dec_calls++;
+  else c->enc_last_nk = nk;
+  return rc;
+}
 
 // before_s2: an event the LAST stage (the only one that writes d_feat) has to wait for -- the earlier stages run ahead.
 int launch_extract(lyra_hip_ctx* c, int k, int lo, const int32_t* d_ids, int B, const int16_t* d_pcm, float* d_feat,
@@ -734,8 +799,6 @@ enum { LOSSY_UNIFORM, LOSSY_MIXED_BYTES, LOSSY_MIXED_BITS };
 int lossy_tick_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_packets, const int32_t* d_pkt_bytes,
                       const uint8_t* d_rx, int num_bits, int ext, int16_t* d_pcm16, int16_t* d_pcm_ext, int32_t* d_is_noise,
                       int32_t* d_is_cn, int mixed = LOSSY_UNIFORM, const int32_t* d_rates = nullptr);   // lossy_api.inc
-int encode_mixed16(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int16_t* d_pcm, const int32_t* d_bits, bool dtx,
-                   uint8_t* d_packets, int32_t* d_packet_bytes, const int32_t* d_rates = nullptr);   // mixed_api.inc
 // per-stream sample rates (rates_api.inc)
 int rates_ensure(lyra_hip_ctx* c);
 int launch_noise_rates(lyra_hip_ctx* c, hipStream_t st_, const int32_t* d_ids, const int32_t* d_rates, int B,
@@ -746,6 +809,51 @@ int encode_rates_resample(lyra_hip_ctx* c, const int32_t* d_ids, const int32_t* 
                           const int16_t** in, const int32_t** ids);
 int resample_rates_in_ahead(lyra_hip_ctx* c, const int32_t* d_ids, const int32_t* d_rates, int B, const int16_t* d_in, long step);
 int rates_uniform_bits(lyra_hip_ctx* c, int num_bits, const int32_t** bits);
+
+// One unsplit `_dev` encode call at 16 kHz: [noise estimator ->] extractor on se[0], quantizer on sq[0].  What varies:
+//   dtx     lyra_encoder.cc:131-141: the noise estimator sees every hop; only non-noise hops reach the feature extractor;
+//   d_bits  null: every frame at num_bits (rvq_encode_kernel, packet rows num_bits / 8 rounded up apart); else each frame at
+//           d_bits[b] (mixed_api.inc: rvq_encode_mixed_kernel, packet rows LYRA_HIP_MAX_PACKET_BYTES apart);
+//   d_rates (rates_api.inc, with d_bits): the estimator runs with each row's own rate, and d_ids may hold -1 for rows that
+//           are absent from this hop (no state advances, packet_bytes 0).
+int encode16(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int16_t* d_pcm, bool dtx, int num_bits, const int32_t* d_bits,
+             const int32_t* d_rates, uint8_t* d_packets, int32_t* d_packet_bytes) {
+  DEVSCOPE(c);
+  int rc = ensure_scratch(c, B);
+  if (rc) return rc;
+  if (d_bits && !c->d_mixed_err) {
+    HIPCHK(c, dalloc(&c->d_mixed_err, 1));
+    HIPCHK(c, hipMemset(c->d_mixed_err, 0, 4));
+  }
+  return run_chunks(c, CALL_ENCQ, B, false, [&](int, int, int, int) {
+    float* feat = encq_features(c);
+    int32_t* live = nullptr;
+    int rc;
+    if (dtx) {
+      // (d_live_ids / d_flag_enc are rewritten by the next call's noise kernel on se[0]: it must not overtake this call's
+      // quantizer, which reads d_live_ids on sd[0] -- the next call's encq_begin waits for the call before the previous
+      // one only, so the mask travels with the features: one buffer per parity)
+      live = (c->n_encq_calls & 1) ? c->d_live_ids2 : c->d_live_ids;
+      // `live` travels with the features: both were last read by the quantizer(s) of the call before the previous one
+      const EventList busy = encq_buffer_free(c, 0, 1);
+      for (int i = 0; i < busy.n; ++i) HIPCHK(c, hipStreamWaitEvent(c->se[0], busy.e[i], 0));
+      rc = d_rates ? launch_noise_rates(c, c->se[0], d_ids, d_rates, B, d_pcm, c->d_flag_enc, live)
+                   : launch_noise(c, 0, c->se[0], d_ids, B, d_pcm, c->d_flag_enc, live);
+      if (!rc) rc = launch_extract(c, 0, 0, live, B, d_pcm, feat);
+    } else {
+      rc = launch_extract(c, 0, 0, d_ids, B, d_pcm, feat, encq_buffer_free(c, 0, 1));
+    }
+    if (!rc) rc = encq_handoff(c, 0);
+    if (rc) return rc;
+    const int32_t* mask = live ? live : d_rates ? d_ids : nullptr;
+    if (!d_bits) return launch_rvq_encode(c, 0, B, feat, num_bits / 4, nullptr, d_packets, mask, d_packet_bytes, true);
+    { ProfScope ps(c, K_RVQ_ENC, c->sq[0]);
+      hipLaunchKernelGGL(rvq_encode_mixed_kernel, dim3(cdiv(B, 16)), dim3(64), 0, c->sq[0], c->model.cb, c->model.cbn, feat, B,
+                         d_bits, d_packets, mask, d_packet_bytes, c->d_rvq_stats, c->d_mixed_err); }
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  });
+}
 
 template <class K>
 hipError_t set_lds(K kernel, size_t bytes) {
@@ -997,9 +1105,7 @@ void lyra_hip_destroy(lyra_hip_ctx* c) {
     if (e) (void)hipEventDestroy(e);
   if (c->ev_ahead_last) (void)hipEventDestroy(c->ev_ahead_last);
   if (c->sn) (void)hipStreamDestroy(c->sn);
-  if (c->d_state) (void)hipFree(c->d_state);
-  if (c->d_rvq_stats) (void)hipFree(c->d_rvq_stats);
-  if (c->d_mixed_err) (void)hipFree(c->d_mixed_err);
+  dfree(c->d_state, c->d_rvq_stats, c->d_mixed_err, c->d_fade);
   rates_free(c);
   free_model(&c->model);
   delete c;
@@ -1050,17 +1156,9 @@ int lyra_hip_extract_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int
   if (!d_ids || !d_pcm || !d_feat) return fail(c, LYRA_HIP_EINVAL, "null pointer");
   DEVSCOPE(c);
   if ((rc = ensure_scratch(c, B))) return rc;
-  const int nk = chunks_for(c, B);
-  for (int k = 0; k < nk && !rc; ++k) {
-    int lo = 0, n = B;
-    if (nk > 1) chunk_of(c, B, k, &lo, &n);
-    if (n <= 0) continue;
-    if ((rc = enc_side_begin(c, k, nk))) break;
-    rc = launch_extract(c, k, lo, d_ids + lo, n, d_pcm + (size_t)lo * 320, d_feat + (size_t)lo * 64);
-    if (!rc) rc = enc_side_done(c, k, nk);
-  }
-  c->enc_last_nk = nk;
-  return rc;
+  return run_chunks(c, CALL_ENC, B, true, [&](int k, int lo, int n, int) {
+    return launch_extract(c, k, lo, d_ids + lo, n, d_pcm + (size_t)lo * 320, d_feat + (size_t)lo * 64);
+  });
 }
 
 int lyra_hip_rvq_encode_dev(lyra_hip_ctx* c, int B, const float* d_feat, int num_bits, int32_t* d_idx) {
@@ -1093,17 +1191,9 @@ int lyra_hip_generate_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, const fl
   if (!d_ids || !d_pcm || !d_feat) return fail(c, LYRA_HIP_EINVAL, "null pointer");
   DEVSCOPE(c);
   if ((rc = ensure_scratch(c, B))) return rc;
-  const int nk = chunks_for(c, B);
-  for (int k = 0; k < nk && !rc; ++k) {
-    int lo = 0, n = B;
-    if (nk > 1) chunk_of(c, B, k, &lo, &n);
-    if (n <= 0) continue;
-    if ((rc = dec_side_begin(c, k, nk))) break;
-    rc = launch_generate(c, k, lo, d_ids + lo, n, d_feat + (size_t)lo * 64, d_pcm + (size_t)lo * 320);
-    if (!rc) rc = dec_side_done(c, k, nk);
-  }
-  c->n_dec_calls++;
-  return rc;
+  return run_chunks(c, CALL_DEC, B, true, [&](int k, int lo, int n, int) {
+    return launch_generate(c, k, lo, d_ids + lo, n, d_feat + (size_t)lo * 64, d_pcm + (size_t)lo * 320);
+  });
 }
 
 int lyra_hip_logmel_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int16_t* d_pcm, float* d_mel) {
@@ -1124,26 +1214,18 @@ int lyra_hip_encode_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int1
   if (rc) return rc;
   if ((rc = check_bits(c, num_bits))) return rc;
   if (!d_ids || !d_pcm || !d_packets) return fail(c, LYRA_HIP_EINVAL, "null pointer");
+  if (chunks_for(c, B) == 1) return encode16(c, d_ids, B, d_pcm, false, num_bits, nullptr, nullptr, d_packets, nullptr);
   DEVSCOPE(c);
   if ((rc = ensure_scratch(c, B))) return rc;
   const int nbytes = (num_bits + 7) / 8;
-  const int nk = chunks_for(c, B);
-  for (int k = 0; k < nk && !rc; ++k) {
-    int lo = 0, n = B;
-    if (nk > 1) chunk_of(c, B, k, &lo, &n);
-    if (n <= 0) continue;
-    if ((rc = encq_begin(c, k, nk))) break;
+  return run_chunks(c, CALL_ENCQ, B, true, [&](int k, int lo, int n, int nk) {
     float* feat = encq_features(c) + (size_t)lo * 64;
-    rc = launch_extract(c, k, lo, d_ids + lo, n, d_pcm + (size_t)lo * 320, feat, encq_buffer_free(c, k, nk));
+    int rc = launch_extract(c, k, lo, d_ids + lo, n, d_pcm + (size_t)lo * 320, feat, encq_buffer_free(c, k, nk));
     if (!rc) rc = encq_handoff(c, k);
     if (!rc) rc = launch_rvq_encode(c, k, n, feat, num_bits / 4, nullptr, d_packets + (size_t)lo * nbytes, nullptr, nullptr,
                                     true);
-    if (!rc) rc = encq_done(c, k);
-  }
-  c->encq_nk[c->n_encq_calls & 1] = nk;
-  c->n_encq_calls++;
-  c->enc_last_nk = nk;
-  return rc;
+    return rc;
+  });
 }
 
 int lyra_hip_decode_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_packets, int num_bits,
@@ -1155,18 +1237,10 @@ int lyra_hip_decode_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint
   DEVSCOPE(c);
   if ((rc = ensure_scratch(c, B))) return rc;
   const int nbytes = (num_bits + 7) / 8;
-  const int nk = chunks_for(c, B);
-  for (int k = 0; k < nk && !rc; ++k) {
-    int lo = 0, n = B;
-    if (nk > 1) chunk_of(c, B, k, &lo, &n);
-    if (n <= 0) continue;
-    if ((rc = dec_side_begin(c, k, nk))) break;
-    rc = launch_generate(c, k, lo, d_ids + lo, n, nullptr, d_pcm + (size_t)lo * 320,
-                         d_packets + (size_t)lo * nbytes, num_bits / 4);
-    if (!rc) rc = dec_side_done(c, k, nk);
-  }
-  c->n_dec_calls++;
-  return rc;
+  return run_chunks(c, CALL_DEC, B, true, [&](int k, int lo, int n, int) {
+    return launch_generate(c, k, lo, d_ids + lo, n, nullptr, d_pcm + (size_t)lo * 320, d_packets + (size_t)lo * nbytes,
+                           num_bits / 4);
+  });
 }
 
 // host-pointer entry points: validate, bind the device, size the scratch, drain both streams
@@ -1230,6 +1304,14 @@ static int ahead_end(lyra_hip_ctx* c) {
   c->ahead_unseen = true;
   return 0;
 }
+// The chunks of a split encode run on se[1..]: they read what se[0] has just written (a resampled hop)
+static int se0_to_chunks(lyra_hip_ctx* c) {
+  if (c->nsub > 1) {
+    HIPCHK(c, hipEventRecord(c->ev_ahead_order, c->se[0]));
+    for (int k = 1; k < c->nsub; ++k) HIPCHK(c, hipStreamWaitEvent(c->se[k], c->ev_ahead_order, 0));
+  }
+  return 0;
+}
 static int wait_ahead(lyra_hip_ctx* c) {
 #ifdef LYRA_MUTATE_NO_AHEAD_WAIT   // mutation build: tests/test_gpu_round3.py must FAIL without these edges
   return 0;
@@ -1278,11 +1360,12 @@ static int launch_resample(lyra_hip_ctx* c, int side, const int32_t* d_ids, int 
   return 0;
 }
 
-static int launch_cng(lyra_hip_ctx* c, const int32_t* d_ids, int B, const float* d_features, int16_t* d_pcm) {
-  // reads the decoder-side noise estimate: after every decoder-side `_dev` noise call (they run on sn)
-  if (!d_features) { int rc = wait_noise_stream(c); if (rc) return rc; }
-  { ProfScope ps(c, K_CNG, c->sd[0]);
-    hipLaunchKernelGGL(cng_kernel, dim3(B), dim3(256), cng_lds_bytes(), c->sd[0], c->model.d_mel, c->cng_seed, d_ids, B,
+// st_: the decode stream (lyra_hip_comfort_noise*, the twin) or the noise stream (the lossy tick, decode_samples: id -1 = skip)
+static int launch_cng(lyra_hip_ctx* c, hipStream_t st_, const int32_t* d_ids, int B, const float* d_features, int16_t* d_pcm) {
+  // reads the decoder-side noise estimate: on the decode stream after every decoder-side `_dev` noise call (they run on sn)
+  if (!d_features && st_ != c->sn) { int rc = wait_noise_stream(c); if (rc) return rc; }
+  { ProfScope ps(c, K_CNG, st_);
+    hipLaunchKernelGGL(cng_kernel, dim3(B), dim3(256), cng_lds_bytes(), st_, c->model.d_mel, c->cng_seed, d_ids, B,
                        c->sm.base[st::R_CNG], (const uint8_t*)c->sm.base[st::R_NOISE_D], d_features, d_pcm); }
   HIPCHK(c, hipGetLastError());
   return 0;
@@ -1382,7 +1465,7 @@ int lyra_hip_comfort_noise_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, con
   if (!d_ids || !d_pcm) return fail(c, LYRA_HIP_EINVAL, "null pointer");
   DEVSCOPE(c);
   if ((rc = dec_side_begin(c, 0))) return rc;
-  rc = launch_cng(c, d_ids, B, d_features, d_pcm);
+  rc = launch_cng(c, c->sd[0], d_ids, B, d_features, d_pcm);
   if (!rc) rc = dec_side_done(c, 0, 1);
   c->n_dec_calls++;
   return rc;
@@ -1395,7 +1478,7 @@ int lyra_hip_comfort_noise(lyra_hip_ctx* c, const int32_t* ids, int B, const flo
   hipStream_t st_ = c->sd[0];
   HIPCHK(c, hipMemcpyAsync(c->d_ids_dec, ids, (size_t)B * 4, hipMemcpyHostToDevice, st_));
   if (features) HIPCHK(c, hipMemcpyAsync(c->d_mel, features, (size_t)B * 160 * 4, hipMemcpyHostToDevice, st_));
-  if ((rc = launch_cng(c, c->d_ids_dec, B, features ? c->d_mel : nullptr, c->d_pcm_out))) return rc;
+  if ((rc = launch_cng(c, st_, c->d_ids_dec, B, features ? c->d_mel : nullptr, c->d_pcm_out))) return rc;
   HIPCHK(c, hipMemcpyAsync(pcm, c->d_pcm_out, (size_t)B * 640, hipMemcpyDeviceToHost, st_));
   HIPCHK(c, hipStreamSynchronize(st_));
   return 0;
@@ -1403,8 +1486,8 @@ int lyra_hip_comfort_noise(lyra_hip_ctx* c, const int32_t* ids, int B, const flo
 
 int lyra_hip_set_encoder_sample_rate(lyra_hip_ctx* c, int sample_rate_hz) {
   if (!c) return LYRA_HIP_EINVAL;
-  if (sample_rate_hz != 8000 && sample_rate_hz != 16000 && sample_rate_hz != 32000 && sample_rate_hz != 48000)
-    return fail(c, LYRA_HIP_EINVAL, "sample rate %d Hz is not supported by the codec (lyra_config.h:57)", sample_rate_hz);
+  int rc = check_rate(c, sample_rate_hz);
+  if (rc) return rc;
   c->enc_noise_rate = sample_rate_hz;
   return 0;
 }
@@ -1441,28 +1524,7 @@ int lyra_hip_encode_dtx_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, const 
   if (rc) return rc;
   if ((rc = check_bits(c, num_bits))) return rc;
   if (!d_ids || !d_pcm || !d_packets || !d_packet_bytes) return fail(c, LYRA_HIP_EINVAL, "null pointer");
-  DEVSCOPE(c);
-  if ((rc = ensure_scratch(c, B))) return rc;
-  if ((rc = encq_begin(c, 0))) return rc;
-  // lyra_encoder.cc:131-141: the noise estimator sees every hop; only non-noise hops reach the feature extractor
-  // (d_live_ids / d_flag_enc are rewritten by the next call's noise kernel on se[0]: it must not overtake this call's
-  // quantizer, which reads d_live_ids on sd[0] -- the next call's encq_begin waits for the call before the previous
-  // one only, so the mask travels with the features: one buffer per parity)
-  float* feat = encq_features(c);
-  int32_t* live = (c->n_encq_calls & 1) ? c->d_live_ids2 : c->d_live_ids;
-  {   // `live` travels with the features: both were last read by the quantizer(s) of the call before the previous one
-    const EventList busy = encq_buffer_free(c, 0, 1);
-    for (int i = 0; i < busy.n; ++i) HIPCHK(c, hipStreamWaitEvent(c->se[0], busy.e[i], 0));
-  }
-  rc = launch_noise(c, 0, c->se[0], d_ids, B, d_pcm, c->d_flag_enc, live);
-  if (!rc) rc = launch_extract(c, 0, 0, live, B, d_pcm, feat);
-  if (!rc) rc = encq_handoff(c, 0);
-  if (!rc) rc = launch_rvq_encode(c, 0, B, feat, num_bits / 4, nullptr, d_packets, live, d_packet_bytes, true);
-  if (!rc) rc = encq_done(c, 0);
-  c->encq_nk[c->n_encq_calls & 1] = 1;
-  c->n_encq_calls++;
-  c->enc_last_nk = 1;
-  return rc;
+  return encode16(c, d_ids, B, d_pcm, true, num_bits, nullptr, nullptr, d_packets, d_packet_bytes);
 }
 int lyra_hip_noise_receive(lyra_hip_ctx* c, int side, const int32_t* ids, int B, const int16_t* pcm, int32_t* is_noise) {
   PROLOGUE(c, B);
@@ -1585,25 +1647,16 @@ int lyra_hip_extract(lyra_hip_ctx* c, const int32_t* ids, int B, const int16_t* 
   PROLOGUE(c, B);
   if (!pcm || !features) return fail(c, LYRA_HIP_EINVAL, "null pointer");
   if ((rc = check_ids_host(c, ids, B))) return rc;
-  if (c->zc(B)) {   // zero-copy: see lyra_hip_ctx::h_zc
-    int32_t* z_ids = (int32_t*)(c->h_zc + lyra_hip_ctx::ZC_IDS);
-    int16_t* z_in = (int16_t*)(c->h_zc + lyra_hip_ctx::ZC_IN);
-    float* z_out = (float*)(c->h_zc + lyra_hip_ctx::ZC_OUT);
-    std::memcpy(z_ids, ids, (size_t)B * 4);
-    std::memcpy(z_in, pcm, (size_t)B * 640);
-    if ((rc = launch_extract(c, 0, 0, z_ids, B, z_in, z_out))) return rc;
-    if ((rc = enc_side_done(c, 0))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->se[0]));
-    std::memcpy(features, z_out, (size_t)B * 256);
-    return 0;
-  }
-  HIPCHK(c, hipMemcpyAsync(c->d_ids, ids, (size_t)B * 4, hipMemcpyHostToDevice, c->se[0]));
-  HIPCHK(c, hipMemcpyAsync(c->d_pcm_in, pcm, (size_t)B * 640, hipMemcpyHostToDevice, c->se[0]));
-  if ((rc = launch_extract(c, 0, 0, c->d_ids, B, c->d_pcm_in, c->d_feat))) return rc;
-  HIPCHK(c, hipMemcpyAsync(features, c->d_feat, (size_t)B * 256, hipMemcpyDeviceToHost, c->se[0]));
+  HostIO io{c, c->se[0], c->zc(B)};   // zero-copy: see lyra_hip_ctx::h_zc
+  int32_t* x_ids = io.at(lyra_hip_ctx::ZC_IDS, c->d_ids);
+  int16_t* x_in = io.at(lyra_hip_ctx::ZC_IN, c->d_pcm_in);
+  float* x_out = io.at(lyra_hip_ctx::ZC_OUT, c->d_feat);
+  if ((rc = io.in(x_ids, ids, (size_t)B * 4))) return rc;
+  if ((rc = io.in(x_in, pcm, (size_t)B * 640))) return rc;
+  if ((rc = launch_extract(c, 0, 0, x_ids, B, x_in, x_out))) return rc;
+  if ((rc = io.out(features, x_out, (size_t)B * 256))) return rc;
   if ((rc = enc_side_done(c, 0))) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->se[0]));
-  return 0;
+  return io.finish();
 }
 
 int lyra_hip_rvq_encode(lyra_hip_ctx* c, int B, const float* features, int num_bits, int32_t* indices) {
@@ -1613,22 +1666,14 @@ int lyra_hip_rvq_encode(lyra_hip_ctx* c, int B, const float* features, int num_b
   if (B <= 0 || !features || !indices) return fail(c, LYRA_HIP_EINVAL, "bad batch or null pointer");
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = ensure_scratch(c, B))) return rc;
-  if (c->zc(B)) {
-    float* z_in = (float*)(c->h_zc + lyra_hip_ctx::ZC_IN);
-    int32_t* z_out = (int32_t*)(c->h_zc + lyra_hip_ctx::ZC_OUT);
-    std::memcpy(z_in, features, (size_t)B * 256);
-    if ((rc = launch_rvq_encode(c, 0, B, z_in, num_bits / 4, z_out, nullptr))) return rc;
-    if ((rc = enc_side_done(c, 0))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->se[0]));
-    std::memcpy(indices, z_out, (size_t)B * 46 * 4);
-    return 0;
-  }
-  HIPCHK(c, hipMemcpyAsync(c->d_feat, features, (size_t)B * 256, hipMemcpyHostToDevice, c->se[0]));
-  if ((rc = launch_rvq_encode(c, 0, B, c->d_feat, num_bits / 4, c->d_idx, nullptr))) return rc;
-  HIPCHK(c, hipMemcpyAsync(indices, c->d_idx, (size_t)B * 46 * 4, hipMemcpyDeviceToHost, c->se[0]));
+  HostIO io{c, c->se[0], c->zc(B)};
+  float* x_in = io.at(lyra_hip_ctx::ZC_IN, c->d_feat);
+  int32_t* x_out = io.at(lyra_hip_ctx::ZC_OUT, c->d_idx);
+  if ((rc = io.in(x_in, features, (size_t)B * 256))) return rc;
+  if ((rc = launch_rvq_encode(c, 0, B, x_in, num_bits / 4, x_out, nullptr))) return rc;
+  if ((rc = io.out(indices, x_out, (size_t)B * 46 * 4))) return rc;
   if ((rc = enc_side_done(c, 0))) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->se[0]));
-  return 0;
+  return io.finish();
 }
 
 int lyra_hip_rvq_decode(lyra_hip_ctx* c, int B, const int32_t* indices, float* features) {
@@ -1638,20 +1683,13 @@ int lyra_hip_rvq_decode(lyra_hip_ctx* c, int B, const int32_t* indices, float* f
   int rc;
   if ((rc = ensure_scratch(c, B))) return rc;
   if ((rc = dec_side_begin(c, 0))) return rc;
-  if (c->zc(B)) {
-    int32_t* z_in = (int32_t*)(c->h_zc + lyra_hip_ctx::ZC_IN);
-    float* z_out = (float*)(c->h_zc + lyra_hip_ctx::ZC_OUT);
-    std::memcpy(z_in, indices, (size_t)B * 46 * 4);
-    if ((rc = launch_rvq_decode(c, 0, B, z_in, nullptr, 46, z_out))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->sd[0]));
-    std::memcpy(features, z_out, (size_t)B * 256);
-    return 0;
-  }
-  HIPCHK(c, hipMemcpyAsync(c->d_idx, indices, (size_t)B * 46 * 4, hipMemcpyHostToDevice, c->sd[0]));
-  if ((rc = launch_rvq_decode(c, 0, B, c->d_idx, nullptr, 46, c->d_lossy))) return rc;
-  HIPCHK(c, hipMemcpyAsync(features, c->d_lossy, (size_t)B * 256, hipMemcpyDeviceToHost, c->sd[0]));
-  HIPCHK(c, hipStreamSynchronize(c->sd[0]));
-  return 0;
+  HostIO io{c, c->sd[0], c->zc(B)};
+  int32_t* x_in = io.at(lyra_hip_ctx::ZC_IN, c->d_idx);
+  float* x_out = io.at(lyra_hip_ctx::ZC_OUT, c->d_lossy);
+  if ((rc = io.in(x_in, indices, (size_t)B * 46 * 4))) return rc;
+  if ((rc = launch_rvq_decode(c, 0, B, x_in, nullptr, 46, x_out))) return rc;
+  if ((rc = io.out(features, x_out, (size_t)B * 256))) return rc;
+  return io.finish();
 }
 
 int lyra_hip_generate(lyra_hip_ctx* c, const int32_t* ids, int B, const float* features, int16_t* pcm) {
@@ -1659,23 +1697,15 @@ int lyra_hip_generate(lyra_hip_ctx* c, const int32_t* ids, int B, const float* f
   if (!pcm || !features) return fail(c, LYRA_HIP_EINVAL, "null pointer");
   if ((rc = check_ids_host(c, ids, B))) return rc;
   if ((rc = dec_side_begin(c, 0))) return rc;
-  if (c->zc(B)) {
-    int32_t* z_ids = (int32_t*)(c->h_zc + lyra_hip_ctx::ZC_IDS);
-    float* z_in = (float*)(c->h_zc + lyra_hip_ctx::ZC_IN);
-    int16_t* z_out = (int16_t*)(c->h_zc + lyra_hip_ctx::ZC_OUT);
-    std::memcpy(z_ids, ids, (size_t)B * 4);
-    std::memcpy(z_in, features, (size_t)B * 256);
-    if ((rc = launch_generate(c, 0, 0, z_ids, B, z_in, z_out))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->sd[0]));
-    std::memcpy(pcm, z_out, (size_t)B * 640);
-    return 0;
-  }
-  HIPCHK(c, hipMemcpyAsync(c->d_ids_dec, ids, (size_t)B * 4, hipMemcpyHostToDevice, c->sd[0]));
-  HIPCHK(c, hipMemcpyAsync(c->d_lossy, features, (size_t)B * 256, hipMemcpyHostToDevice, c->sd[0]));
-  if ((rc = launch_generate(c, 0, 0, c->d_ids_dec, B, c->d_lossy, c->d_pcm_out))) return rc;
-  HIPCHK(c, hipMemcpyAsync(pcm, c->d_pcm_out, (size_t)B * 640, hipMemcpyDeviceToHost, c->sd[0]));
-  HIPCHK(c, hipStreamSynchronize(c->sd[0]));
-  return 0;
+  HostIO io{c, c->sd[0], c->zc(B)};
+  int32_t* x_ids = io.at(lyra_hip_ctx::ZC_IDS, c->d_ids_dec);
+  float* x_in = io.at(lyra_hip_ctx::ZC_IN, c->d_lossy);
+  int16_t* x_out = io.at(lyra_hip_ctx::ZC_OUT, c->d_pcm_out);
+  if ((rc = io.in(x_ids, ids, (size_t)B * 4))) return rc;
+  if ((rc = io.in(x_in, features, (size_t)B * 256))) return rc;
+  if ((rc = launch_generate(c, 0, 0, x_ids, B, x_in, x_out))) return rc;
+  if ((rc = io.out(pcm, x_out, (size_t)B * 640))) return rc;
+  return io.finish();
 }
 
 int lyra_hip_logmel(lyra_hip_ctx* c, const int32_t* ids, int B, const int16_t* pcm, float* mel) {
@@ -1746,10 +1776,7 @@ static int encode_ext_resample(lyra_hip_ctx* c, const int32_t* d_ids, int B, con
   if ((rc = wait_ahead(c))) return rc;
   if ((rc = encq_begin(c, 0, 1))) return rc;   // (split contexts: after every chunk of the encode-side call before; serial mode: in call order)
   if ((rc = launch_resample(c, 0, d_ids, B, d_pcm_ext, 320 * (ext / 1000) / 16, ext, 16000, c->d_rs16[0], nullptr))) return rc;
-  if (c->nsub > 1) {   // the chunks of a split encode run on se[1..]: they read what se[0] has just written
-    HIPCHK(c, hipEventRecord(c->ev_ahead_order, c->se[0]));
-    for (int k = 1; k < c->nsub; ++k) HIPCHK(c, hipStreamWaitEvent(c->se[k], c->ev_ahead_order, 0));
-  }
+  if ((rc = se0_to_chunks(c))) return rc;
   *in = c->d_rs16[0];
   return 0;
 }
@@ -1761,8 +1788,7 @@ int lyra_hip_encode_ext_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, const 
   if ((rc = check_bits(c, num_bits))) return rc;
   if (!d_ids || !d_pcm_ext || !d_packets || (dtx && !d_packet_bytes)) return fail(c, LYRA_HIP_EINVAL, "null pointer");
   const int ext = sample_rate_hz;
-  if (ext != 8000 && ext != 16000 && ext != 32000 && ext != 48000)
-    return fail(c, LYRA_HIP_EINVAL, "sample rate %d Hz is not supported by the codec (lyra_config.h:57)", ext);
+  if ((rc = check_rate(c, ext))) return rc;
   if (dtx && c->enc_noise_rate != ext)   // as lyra_hip_run_steps_dev: the DTX estimator is created at the encoder's external rate
     return fail(c, LYRA_HIP_EINVAL, "encode_ext: DTX at %d Hz but the encoder-side noise estimator is set up for %d Hz "
                 "(call lyra_hip_set_encoder_sample_rate(%d) first)", ext, c->enc_noise_rate, ext);
@@ -1778,8 +1804,7 @@ int lyra_hip_decode_ext_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, const 
   int rc = check_batch(c, B);
   if (rc) return rc;
   const int ext = sample_rate_hz;
-  if (ext != 8000 && ext != 16000 && ext != 32000 && ext != 48000)
-    return fail(c, LYRA_HIP_EINVAL, "sample rate %d Hz is not supported by the codec (lyra_config.h:57)", ext);
+  if ((rc = check_rate(c, ext))) return rc;
   if (!d_pcm16 || (ext != 16000 && !d_pcm_ext) || (estimate_noise && !d_is_noise)) return fail(c, LYRA_HIP_EINVAL, "null pointer");
   if ((rc = lyra_hip_decode_dev(c, d_ids, B, d_packets, num_bits, d_pcm16))) return rc;
   const bool rs = ext != 16000;
@@ -1886,13 +1911,7 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
       } else if (rs && !rs_off_chain) {   // lyra_encoder.cc:119-122: external rate -> 16 kHz, the encoder's own resampler
         if ((rc = lyra_hip_resample_dev(c, LYRA_HIP_SIDE_ENCODER, S->d_stream_ids, S->B, in, n_ext, ext, 16000, c->d_pcm_in))) return rc;
         in = c->d_pcm_in;
-        {   // the chunks of a split encode run on se[1..]: they read what se[0] has just written
-          DEVSCOPE(c);
-          if (c->nsub > 1) {
-            HIPCHK(c, hipEventRecord(c->ev_ahead_order, c->se[0]));
-            for (int k = 1; k < c->nsub; ++k) HIPCHK(c, hipStreamWaitEvent(c->se[k], c->ev_ahead_order, 0));
-          }
-        }
+        { DEVSCOPE(c); if ((rc = se0_to_chunks(c))) return rc; }
       } else if (rs || mrate) {   // ... two steps ahead, on the quantizer stream (resample_in_ahead / resample_rates_in_ahead)
         DEVSCOPE(c);
         auto ahead = [&](int j) {   // the hop of step first_step + j, if this call has one
@@ -1912,19 +1931,20 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
         if (mrate) enc_ids = c->d_rate_ids[slot];
       }
       if (mixed || mrate)
-        rc = encode_mixed16(c, enc_ids, S->B, in, bits, F & LYRA_HIP_STEP_DTX, S->d_packets[set], S->d_packet_bytes[set],
-                            d_rates);
+        rc = encode16(c, enc_ids, S->B, in, F & LYRA_HIP_STEP_DTX, 0, bits, d_rates, S->d_packets[set], S->d_packet_bytes[set]);
       else if (F & LYRA_HIP_STEP_DTX)
         rc = lyra_hip_encode_dtx_dev(c, S->d_stream_ids, S->B, in, S->num_bits, S->d_packets[set], S->d_packet_bytes[set]);
       else
         rc = lyra_hip_encode_dev(c, S->d_stream_ids, S->B, in, S->num_bits, S->d_packets[set]);
       if (rc) return rc;
     }
+    // the packets this step decodes (what its encoder wrote, or a slot of the caller's ring of received packets) and its
+    // row of the "received" ring
+    const size_t pk_row = (mixed || mrate) ? (size_t)LYRA_HIP_MAX_PACKET_BYTES : (size_t)((S->num_bits + 7) / 8);
+    const uint8_t* pk = (!enc && S->d_packet_ring && S->n_packet_ring > 0)
+                            ? S->d_packet_ring + (size_t)(step % S->n_packet_ring) * B * pk_row : S->d_packets[set];
+    const uint8_t* rx = (loss && S->d_received_ring) ? S->d_received_ring + (size_t)(step % S->n_received_ring) * B : nullptr;
     if (dec && loss && (mixed || mrate)) {   // lyra_hip_decode_lossy_mixed_dev (mixed_api.inc) / _rates_dev (rates_api.inc)
-      const uint8_t* pk = S->d_packets[set];
-      if (!enc && S->d_packet_ring && S->n_packet_ring > 0)
-        pk = S->d_packet_ring + (size_t)(step % S->n_packet_ring) * B * (size_t)LYRA_HIP_MAX_PACKET_BYTES;
-      const uint8_t* rx = S->d_received_ring ? S->d_received_ring + (size_t)(step % S->n_received_ring) * B : nullptr;
       // with ENCODE the encoder's sizes; decode-only the sizes of the step's bit counts, (bits + 7) / 8
       if ((rc = lossy_tick_launch(c, S->d_stream_ids, S->B, pk, enc ? S->d_packet_bytes[set] : bits, rx, 0, ext,
                                   S->d_pcm_out[set], (rs || mrate) ? S->d_ext_out[set] : nullptr, S->d_is_noise,
@@ -1932,22 +1952,13 @@ int lyra_hip_run_steps_dev(lyra_hip_ctx* c, const lyra_hip_steps* S) {
                                   d_rates)))
         return rc;
     } else if (dec && loss) {   // lyra_hip_decode_lossy_dev (lossy_api.inc): concealment / comfort noise on the device
-      const uint8_t* pk = S->d_packets[set];
-      if (!enc && S->d_packet_ring && S->n_packet_ring > 0)
-        pk = S->d_packet_ring + (size_t)(step % S->n_packet_ring) * B * (size_t)((S->num_bits + 7) / 8);
-      const uint8_t* rx = S->d_received_ring ? S->d_received_ring + (size_t)(step % S->n_received_ring) * B : nullptr;
       const int32_t* pb = (enc && (F & LYRA_HIP_STEP_DTX)) ? S->d_packet_bytes[set] : nullptr;
       if ((rc = lossy_tick_launch(c, S->d_stream_ids, S->B, pk, pb, rx, S->num_bits, ext, S->d_pcm_out[set],
                                   rs ? S->d_ext_out[set] : nullptr, S->d_is_noise, S->d_is_comfort_noise)))
         return rc;
     } else if (dec) {
       if (feats) rc = lyra_hip_generate_dev(c, S->d_stream_ids, S->B, S->d_features + (size_t)(step % (S->n_features > 0 ? S->n_features : 1)) * B * 64, S->d_pcm_out[set]);
-      else {
-        const uint8_t* pk = S->d_packets[set];
-        if (!enc && S->d_packet_ring && S->n_packet_ring > 0)
-          pk = S->d_packet_ring + (size_t)(step % S->n_packet_ring) * B * (size_t)((S->num_bits + 7) / 8);
-        rc = lyra_hip_decode_dev(c, S->d_stream_ids, S->B, pk, S->num_bits, S->d_pcm_out[set]);
-      }
+      else rc = lyra_hip_decode_dev(c, S->d_stream_ids, S->B, pk, S->num_bits, S->d_pcm_out[set]);
       if (rc) return rc;
       if ((F & LYRA_HIP_STEP_DECODER_NOISE) && rs_out_off_chain) {   // both legs: one noise-stream call
         if ((rc = noise_and_resample_deferred(c, S->d_stream_ids, S->B, S->d_pcm_out[set], S->d_is_noise, ext, S->d_ext_out[set]))) return rc;

@@ -19,13 +19,16 @@ static_assert(lyra::DS_FIFO_DEPTH == LYRA_HIP_DECODE_SAMPLES_FIFO, "documented d
 
 namespace {
 
+Bufs ds_stream_bufs(lyra_hip_ctx* c) {   // per stream of the context
+  return {BUF(c->d_ds_ring, DS_FIFO_DEPTH * 64), BUF(c->d_ds_gan, 320), BUF(c->d_ds_cng, 320)};
+}
+Bufs ds_call_bufs(lyra_hip_ctx* c) {   // per frame of `ds_cap`
+  return {BUF(c->d_ds_ids[0], 4), BUF(c->d_ds_info[0], 4), BUF(c->d_ds_gan_new[0], 320), BUF(c->d_ds_ids[1], 4),
+          BUF(c->d_ds_info[1], 4), BUF(c->d_ds_gan_new[1], 320), BUF(c->d_ds_cng_new, 320), BUF(c->d_ds_est, 320),
+          BUF(c->d_ds_pcm16, 320), BUF(c->d_ds_feat, 64)};
+}
 void ds_free_call_buffers(lyra_hip_ctx* c) {
-  void* ps[] = {c->d_ds_ids[0], c->d_ds_ids[1], c->d_ds_info[0], c->d_ds_info[1], c->d_ds_gan_new[0], c->d_ds_gan_new[1],
-                c->d_ds_cng_new, c->d_ds_est, c->d_ds_pcm16, c->d_ds_feat};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  for (int i = 0; i < 2; ++i) { c->d_ds_ids[i] = nullptr; c->d_ds_info[i] = nullptr; c->d_ds_gan_new[i] = nullptr; }
-  c->d_ds_cng_new = nullptr; c->d_ds_est = nullptr; c->d_ds_pcm16 = nullptr; c->d_ds_feat = nullptr;
+  free_bufs(ds_call_bufs(c));
   c->ds_cap = 0;
 }
 
@@ -52,29 +55,16 @@ void ds_free(lyra_hip_ctx* c) {
     c->ds_host = nullptr;
   }
   ds_free_call_buffers(c);
-  void* ps[] = {c->d_ds_ring, c->d_ds_gan, c->d_ds_cng, c->d_ds_fade, c->d_ds_err};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  c->d_ds_ring = nullptr; c->d_ds_gan = nullptr; c->d_ds_cng = nullptr; c->d_ds_fade = nullptr; c->d_ds_err = nullptr;
+  free_bufs(ds_stream_bufs(c));
+  dfree(c->d_ds_err);
 }
 
 int ds_ensure(lyra_hip_ctx* c, int B) {
   // by stream id; contents only matter while a stream's counters say so: no reset needed.  Each pointer is tested on its
-  // own, so a call after a failed allocation allocates only what is still missing.
-  const size_t ns = (size_t)c->max_streams;
-  if (!c->d_ds_ring) HIPCHK(c, dalloc(&c->d_ds_ring, ns * DS_FIFO_DEPTH * 64));
-  if (!c->d_ds_gan) HIPCHK(c, dalloc(&c->d_ds_gan, ns * 320));
-  if (!c->d_ds_cng) HIPCHK(c, dalloc(&c->d_ds_cng, ns * 320));
-  if (!c->d_ds_fade) {
-    const std::vector<float> w = fade_weights();
-    float* p = nullptr;
-    HIPCHK(c, dalloc(&p, w.size()));
-    if (hipMemcpy(p, w.data(), w.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(p);
-      return fail(c, LYRA_HIP_EHIP, "decode_samples: upload of the fade weights failed");
-    }
-    c->d_ds_fade = p;
-  }
+  // own (alloc_bufs), so a call after a failed allocation allocates only what is still missing.
+  int rc = alloc_bufs(c, ds_stream_bufs(c), (size_t)c->max_streams);
+  if (!rc) rc = fade_ensure(c);
+  if (rc) return rc;
   if (!c->d_ds_err) {
     unsigned* p = nullptr;
     HIPCHK(c, dalloc(&p, 1));
@@ -85,19 +75,9 @@ int ds_ensure(lyra_hip_ctx* c, int B) {
     c->d_ds_err = p;
   }
   if (B <= c->ds_cap) return 0;
-  int rc = sync_all(c);   // (the buffers of the calls in flight)
-  if (rc) return rc;
+  if ((rc = sync_all(c))) return rc;   // (the buffers of the calls in flight)
   ds_free_call_buffers(c);
-  const size_t n = (size_t)B;
-  for (int i = 0; i < 2; ++i) {
-    HIPCHK(c, dalloc(&c->d_ds_ids[i], 4 * n));
-    HIPCHK(c, dalloc(&c->d_ds_info[i], 4 * n));
-    HIPCHK(c, dalloc(&c->d_ds_gan_new[i], n * 320));
-  }
-  HIPCHK(c, dalloc(&c->d_ds_cng_new, n * 320));
-  HIPCHK(c, dalloc(&c->d_ds_est, n * 320));
-  HIPCHK(c, dalloc(&c->d_ds_pcm16, n * 320));
-  HIPCHK(c, dalloc(&c->d_ds_feat, n * 64));
+  if ((rc = alloc_bufs(c, ds_call_bufs(c), (size_t)B))) return rc;
   c->ds_cap = B;
   return 0;
 }
@@ -131,29 +111,18 @@ int ds_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_pac
   c->n_dec_calls++;
   // ---- noise stream: comfort noise, estimator, comfort noise, slices, resampler as ONE noise call ---------------------
   if ((rc = noise_dev_begin(c))) return rc;
-  const auto cng = [&](const int32_t* ids_) {
-    ProfScope ps(c, K_CNG, c->sn);
-    hipLaunchKernelGGL(cng_kernel, dim3(B), dim3(256), cng_lds_bytes(), c->sn, c->model.d_mel, c->cng_seed, ids_, B,
-                       c->sm.base[st::R_CNG], (const uint8_t*)c->sm.base[st::R_NOISE_D], (const float*)nullptr, c->d_ds_cng_new);
-  };
   if (n_int > 0) {
-    cng(cng1_ids);
-    HIPCHK(c, hipGetLastError());
+    if ((rc = launch_cng(c, c->sn, cng1_ids, B, nullptr, c->d_ds_cng_new))) return rc;
     hipLaunchKernelGGL(ds_est_gather_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sn, d_ids, B, (const int32_t*)info,
                        (const int16_t*)gan_new, (const int16_t*)c->d_ds_gan, c->d_ds_est);
     HIPCHK(c, hipGetLastError());
-    { ProfScope ps(c, K_NOISE, c->sn);   // launch_noise on the rows whose received hop completes (lyra_decoder.cc:304-311)
-      hipLaunchKernelGGL(logmel_masked_kernel, dim3(cdiv(B, 2)), dim3(256), logmel_lds_bytes(), c->sn, c->model.d_mel_rate[1],
-                         (const int16_t*)c->d_ds_est, (const int32_t*)est_ids, B, c->sm.base[st::R_NOISE_D], (int)st::NOISE_BYTES,
-                         (int)st::N_PREV, (float*)nullptr, 1, noise_params(16000), d_is_noise, (int32_t*)nullptr); }
-    HIPCHK(c, hipGetLastError());
-    cng(cng2_ids);
-    HIPCHK(c, hipGetLastError());
+    if ((rc = launch_noise_masked(c, est_ids, B, c->d_ds_est, d_is_noise))) return rc;   // the rows whose received hop completes
+    if ((rc = launch_cng(c, c->sn, cng2_ids, B, nullptr, c->d_ds_cng_new))) return rc;
   }
   int16_t* out16 = ext == 16000 ? d_pcm_ext : c->d_ds_pcm16;
   hipLaunchKernelGGL(ds_slice_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sn, d_ids, B, (const int32_t*)info,
                      (const int16_t*)gan_new, (const int16_t*)c->d_ds_cng_new, c->d_ds_gan, c->d_ds_cng,
-                     (const float*)c->d_ds_fade, out16, ext == 16000 ? n_ext : 320, (const uint8_t*)c->sm.base[st::R_NOISE_D],
+                     (const float*)c->d_fade, out16, ext == 16000 ? n_ext : 320, (const uint8_t*)c->sm.base[st::R_NOISE_D],
                      d_is_noise, d_is_cn);
   HIPCHK(c, hipGetLastError());
   if (ext != 16000 && n_int > 0) {
@@ -162,13 +131,7 @@ int ds_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_pac
   }
   if ((rc = noise_dev_done(c))) return rc;
   c->n_ds_calls++;
-  if (c->serial) {   // strict call order: the decode-side call ends with its noise-stream half
-    HIPCHK(c, hipStreamWaitEvent(c->sd[0], c->ev_noise[(c->n_noise_calls - 1) & 1], 0));
-    const int slot = (int)((c->n_dec_calls - 1) & 1);
-    for (int j = 0; j < c->nsub; ++j) HIPCHK(c, hipEventRecord(c->ev_dec[slot][j], c->sd[0]));
-    if (c->nsub == 1) c->noise_done_dec = c->n_noise_calls;
-  }
-  return 0;
+  return serial_noise_half_done(c);
 }
 
 }  // namespace
@@ -192,15 +155,7 @@ int lyra_hip_decode_samples_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, co
 }
 
 long lyra_hip_decode_samples_errors(lyra_hip_ctx* c, int clear) {
-  if (!c) return LYRA_HIP_EINVAL;
-  if (!c->d_ds_err) return 0;
-  DEVSCOPE(c);
-  int rc = sync_all(c);
-  if (rc) return rc;
-  unsigned n = 0;
-  HIPCHK(c, hipMemcpy(&n, c->d_ds_err, 4, hipMemcpyDeviceToHost));
-  if (clear) HIPCHK(c, hipMemset(c->d_ds_err, 0, 4));
-  return (long)n;
+  return read_error_counter(c, &lyra_hip_ctx::d_ds_err, clear);
 }
 
 // The same with HOST buffers, in two halves (the form of lyra_hip_decode_begin / _end): begin() copies ids, sizes and packets

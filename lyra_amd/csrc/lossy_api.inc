@@ -10,40 +10,53 @@
 
 namespace {
 
-void lossy_free(lyra_hip_ctx* c) {
-  void* ps[] = {c->d_lossy_ids[0], c->d_lossy_ids[1], c->d_lossy_info[0], c->d_lossy_info[1], c->d_lossy_gan[0],
-                c->d_lossy_gan[1], c->d_lossy_cng, c->d_lossy_feat, c->d_lossy_fade, c->d_lossy_err};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  for (int i = 0; i < 2; ++i) { c->d_lossy_ids[i] = nullptr; c->d_lossy_info[i] = nullptr; c->d_lossy_gan[i] = nullptr; }
-  c->d_lossy_cng = nullptr; c->d_lossy_feat = nullptr; c->d_lossy_fade = nullptr; c->d_lossy_err = nullptr;
+Bufs lossy_call_bufs(lyra_hip_ctx* c) {   // per frame of `lossy_cap`
+  return {BUF(c->d_lossy_ids[0], 3),  BUF(c->d_lossy_info[0], 1), BUF(c->d_lossy_gan[0], 320), BUF(c->d_lossy_ids[1], 3),
+          BUF(c->d_lossy_info[1], 1), BUF(c->d_lossy_gan[1], 320), BUF(c->d_lossy_cng, 320),   BUF(c->d_lossy_feat, 64)};
+}
+void lossy_free_call_bufs(lyra_hip_ctx* c) {
+  free_bufs(lossy_call_bufs(c));
   c->lossy_cap = 0;
+}
+void lossy_free(lyra_hip_ctx* c) {
+  lossy_free_call_bufs(c);
+  dfree(c->d_lossy_err);
 }
 
 int lossy_ensure(lyra_hip_ctx* c, int B) {
-  if (!c->d_lossy_fade) {
-    const std::vector<float> w = fade_weights();
-    HIPCHK(c, dalloc(&c->d_lossy_fade, w.size()));
+  int rc = fade_ensure(c);
+  if (rc) return rc;
+  if (!c->d_lossy_err) {
     HIPCHK(c, dalloc(&c->d_lossy_err, 1));
-    HIPCHK(c, hipMemcpy(c->d_lossy_fade, w.data(), w.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemset(c->d_lossy_err, 0, 4));
   }
   if (B <= c->lossy_cap) return 0;
-  int rc = sync_all(c);   // (the buffers of the calls in flight)
-  if (rc) return rc;
-  void* keep[] = {c->d_lossy_fade, c->d_lossy_err};
-  c->d_lossy_fade = nullptr; c->d_lossy_err = nullptr;
-  lossy_free(c);
-  c->d_lossy_fade = (float*)keep[0]; c->d_lossy_err = (unsigned*)keep[1];
-  const size_t n = (size_t)B;
-  for (int i = 0; i < 2; ++i) {
-    HIPCHK(c, dalloc(&c->d_lossy_ids[i], 3 * n));
-    HIPCHK(c, dalloc(&c->d_lossy_info[i], n));
-    HIPCHK(c, dalloc(&c->d_lossy_gan[i], n * 320));
-  }
-  HIPCHK(c, dalloc(&c->d_lossy_cng, n * 320));
-  HIPCHK(c, dalloc(&c->d_lossy_feat, n * 64));
+  if ((rc = sync_all(c))) return rc;   // (the buffers of the calls in flight)
+  lossy_free_call_bufs(c);
+  if ((rc = alloc_bufs(c, lossy_call_bufs(c), (size_t)B))) return rc;
   c->lossy_cap = B;
+  return 0;
+}
+
+// launch_noise (decoder side) on the noise stream for the rows of an id list (-1: skip): the estimator sees received hops only
+// (lyra_decoder.cc:304-311)
+int launch_noise_masked(lyra_hip_ctx* c, const int32_t* d_est_ids, int B, const int16_t* d_pcm, int32_t* d_is_noise) {
+  { ProfScope ps(c, K_NOISE, c->sn);
+    hipLaunchKernelGGL(logmel_masked_kernel, dim3(cdiv(B, 2)), dim3(256), logmel_lds_bytes(), c->sn, c->model.d_mel_rate[1],
+                       d_pcm, d_est_ids, B, c->sm.base[st::R_NOISE_D], (int)st::NOISE_BYTES, (int)st::N_PREV, (float*)nullptr, 1,
+                       noise_params(16000), d_is_noise, (int32_t*)nullptr); }
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+// The end of a decode-side call whose second half runs on the noise stream (the lossy tick, decode_samples), after that
+// half's noise_dev_done.  Strict call order (lyra_hip_set_serial): the decode-side call ends with its noise-stream half.
+int serial_noise_half_done(lyra_hip_ctx* c) {
+  if (!c->serial) return 0;
+  HIPCHK(c, hipStreamWaitEvent(c->sd[0], c->ev_noise[(c->n_noise_calls - 1) & 1], 0));
+  const int slot = (int)((c->n_dec_calls - 1) & 1);
+  for (int j = 0; j < c->nsub; ++j) HIPCHK(c, hipEventRecord(c->ev_dec[slot][j], c->sd[0]));
+  if (c->nsub == 1) c->noise_done_dec = c->n_noise_calls;
   return 0;
 }
 
@@ -83,18 +96,12 @@ int lossy_tick_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_
   c->n_dec_calls++;
   // ---- noise stream: comfort noise, mix, estimator, resampler as ONE noise call --------------------------------------
   if ((rc = noise_dev_begin(c))) return rc;
-  { ProfScope ps(c, K_CNG, c->sn);
-    hipLaunchKernelGGL(cng_kernel, dim3(B), dim3(256), cng_lds_bytes(), c->sn, c->model.d_mel, c->cng_seed, cng_ids, B,
-                       c->sm.base[st::R_CNG], (const uint8_t*)c->sm.base[st::R_NOISE_D], (const float*)nullptr, c->d_lossy_cng); }
+  if ((rc = launch_cng(c, c->sn, cng_ids, B, nullptr, c->d_lossy_cng))) return rc;
   hipLaunchKernelGGL(lossy_mix_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sn, d_ids, B, (const int32_t*)info,
-                     (const int16_t*)gan, (const int16_t*)c->d_lossy_cng, (const float*)c->d_lossy_fade, d_pcm16,
+                     (const int16_t*)gan, (const int16_t*)c->d_lossy_cng, (const float*)c->d_fade, d_pcm16,
                      (const uint8_t*)c->sm.base[st::R_NOISE_D], d_is_noise, d_is_cn);
   HIPCHK(c, hipGetLastError());
-  { ProfScope ps(c, K_NOISE, c->sn);   // launch_noise on the received rows only (lyra_decoder.cc:304-311)
-    hipLaunchKernelGGL(logmel_masked_kernel, dim3(cdiv(B, 2)), dim3(256), logmel_lds_bytes(), c->sn, c->model.d_mel_rate[1],
-                       (const int16_t*)gan, (const int32_t*)est_ids, B, c->sm.base[st::R_NOISE_D], (int)st::NOISE_BYTES,
-                       (int)st::N_PREV, (float*)nullptr, 1, noise_params(16000), d_is_noise, (int32_t*)nullptr); }
-  HIPCHK(c, hipGetLastError());
+  if ((rc = launch_noise_masked(c, est_ids, B, gan, d_is_noise))) return rc;
   if (d_rates) {   // per-stream rates (rates_api.inc): d_pcm_ext rows LYRA_HIP_MAX_EXT_HOP apart
     if ((rc = launch_resample_rates(c, 1, d_ids, d_rates, B, d_pcm16, 320, d_pcm_ext, LYRA_HIP_MAX_EXT_HOP, nullptr, c->sn)))
       return rc;
@@ -105,19 +112,7 @@ int lossy_tick_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_
   }
   if ((rc = noise_dev_done(c))) return rc;
   c->n_lossy_calls++;
-  if (c->serial) {   // strict call order: the decode-side call ends with its noise-stream half
-    HIPCHK(c, hipStreamWaitEvent(c->sd[0], c->ev_noise[(c->n_noise_calls - 1) & 1], 0));
-    const int slot = (int)((c->n_dec_calls - 1) & 1);
-    for (int j = 0; j < c->nsub; ++j) HIPCHK(c, hipEventRecord(c->ev_dec[slot][j], c->sd[0]));
-    if (c->nsub == 1) c->noise_done_dec = c->n_noise_calls;
-  }
-  return 0;
-}
-
-int check_rate(lyra_hip_ctx* c, int rate) {
-  if (rate != 8000 && rate != 16000 && rate != 32000 && rate != 48000)
-    return fail(c, LYRA_HIP_EINVAL, "sample rate %d Hz is not supported by the codec (lyra_config.h:57)", rate);
-  return 0;
+  return serial_noise_half_done(c);
 }
 
 }  // namespace
@@ -138,15 +133,7 @@ int lyra_hip_decode_lossy_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, cons
 }
 
 long lyra_hip_decode_lossy_errors(lyra_hip_ctx* c, int clear) {
-  if (!c) return LYRA_HIP_EINVAL;
-  if (!c->d_lossy_err) return 0;
-  DEVSCOPE(c);
-  int rc = sync_all(c);
-  if (rc) return rc;
-  unsigned n = 0;
-  HIPCHK(c, hipMemcpy(&n, c->d_lossy_err, 4, hipMemcpyDeviceToHost));
-  if (clear) HIPCHK(c, hipMemset(c->d_lossy_err, 0, 4));
-  return (long)n;
+  return read_error_counter(c, &lyra_hip_ctx::d_lossy_err, clear);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // mixed_api.inc -- part of api.hip: per-stream bitrates on the device path, one call per side.
 //   lyra_hip_encode_mixed_dev: LyraEncoder::Encode (lyra_encoder.cc:113-156) with each stream's own bitrate (set_bitrate,
 //     :158-166): resampler, DTX decision, feature extractor as lyra_hip_encode_ext_dev, then rvq_encode_mixed_kernel -- every
-//     frame at bits[b] / 4 stages, packet rows LYRA_HIP_MAX_PACKET_BYTES apart.
+//     frame at bits[b] / 4 stages, packet rows LYRA_HIP_MAX_PACKET_BYTES apart (api.hip encode16 with d_bits).
 //   lyra_hip_decode_lossy_mixed_dev: lossy_tick_launch with the sizes of SetEncodedPacket's PacketSizeToNumQuantizedBits
 //     (lyra_decoder.cc:172-179, lyra_config.h:99-106) per row: rvq_decode_mixed_kernel + lossy_plan_mixed_kernel.
 // Neither splits on contexts with LYRA_HIP_SUBBATCHES > 1 (one call stands for every chunk, as lyra_hip_encode_dtx_dev and
@@ -9,49 +9,6 @@
 #include "lossy_plan.h"
 
 static_assert(lyra::MAX_PACKET_BYTES == LYRA_HIP_MAX_PACKET_BYTES, "packet row stride of the mixed kernels");
-
-namespace {
-
-// One unsplit encode-side call at 16 kHz: [noise estimator ->] extractor on se[0], quantizer on sq[0] (the structure of
-// lyra_hip_encode_dev with one chunk, and of lyra_hip_encode_dtx_dev).  d_rates (rates_api.inc): the estimator runs with each
-// row's own rate, and d_ids may hold -1 for rows that are absent from this hop (no state advances, packet_bytes 0).
-int encode_mixed16(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int16_t* d_pcm, const int32_t* d_bits, bool dtx,
-                   uint8_t* d_packets, int32_t* d_packet_bytes, const int32_t* d_rates) {
-  DEVSCOPE(c);
-  int rc = ensure_scratch(c, B);
-  if (rc) return rc;
-  if (!c->d_mixed_err) {
-    HIPCHK(c, dalloc(&c->d_mixed_err, 1));
-    HIPCHK(c, hipMemset(c->d_mixed_err, 0, 4));
-  }
-  if ((rc = encq_begin(c, 0))) return rc;
-  float* feat = encq_features(c);
-  int32_t* live = nullptr;
-  if (dtx) {   // as lyra_hip_encode_dtx_dev: the mask travels with the features, one buffer per parity
-    live = (c->n_encq_calls & 1) ? c->d_live_ids2 : c->d_live_ids;
-    const EventList busy = encq_buffer_free(c, 0, 1);
-    for (int i = 0; i < busy.n; ++i) HIPCHK(c, hipStreamWaitEvent(c->se[0], busy.e[i], 0));
-    rc = d_rates ? launch_noise_rates(c, c->se[0], d_ids, d_rates, B, d_pcm, c->d_flag_enc, live)
-                 : launch_noise(c, 0, c->se[0], d_ids, B, d_pcm, c->d_flag_enc, live);
-    if (!rc) rc = launch_extract(c, 0, 0, live, B, d_pcm, feat);
-  } else {
-    rc = launch_extract(c, 0, 0, d_ids, B, d_pcm, feat, encq_buffer_free(c, 0, 1));
-  }
-  if (!rc) rc = encq_handoff(c, 0);
-  if (!rc) {
-    { ProfScope ps(c, K_RVQ_ENC, c->sq[0]);
-      hipLaunchKernelGGL(rvq_encode_mixed_kernel, dim3(cdiv(B, 16)), dim3(64), 0, c->sq[0], c->model.cb, c->model.cbn, feat, B,
-                         d_bits, d_packets, (const int32_t*)(live ? live : d_rates ? d_ids : nullptr), d_packet_bytes, c->d_rvq_stats, c->d_mixed_err); }
-    HIPCHK(c, hipGetLastError());
-    rc = encq_done(c, 0);
-  }
-  c->encq_nk[c->n_encq_calls & 1] = 1;
-  c->n_encq_calls++;
-  c->enc_last_nk = 1;
-  return rc;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -68,19 +25,11 @@ int lyra_hip_encode_mixed_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, cons
                 "(call lyra_hip_set_encoder_sample_rate(%d) first)", ext, c->enc_noise_rate, ext);
   const int16_t* in = d_pcm_ext;
   if (ext != 16000 && (rc = encode_ext_resample(c, d_ids, B, d_pcm_ext, ext, &in))) return rc;
-  return encode_mixed16(c, d_ids, B, in, d_num_bits, dtx != 0, d_packets, d_packet_bytes);
+  return encode16(c, d_ids, B, in, dtx != 0, 0, d_num_bits, nullptr, d_packets, d_packet_bytes);
 }
 
 long lyra_hip_encode_mixed_errors(lyra_hip_ctx* c, int clear) {
-  if (!c) return LYRA_HIP_EINVAL;
-  if (!c->d_mixed_err) return 0;
-  DEVSCOPE(c);
-  int rc = sync_all(c);
-  if (rc) return rc;
-  unsigned n = 0;
-  HIPCHK(c, hipMemcpy(&n, c->d_mixed_err, 4, hipMemcpyDeviceToHost));
-  if (clear) HIPCHK(c, hipMemset(c->d_mixed_err, 0, 4));
-  return (long)n;
+  return read_error_counter(c, &lyra_hip_ctx::d_mixed_err, clear);
 }
 
 int lyra_hip_decode_lossy_mixed_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_packets,

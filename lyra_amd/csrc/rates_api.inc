@@ -1,7 +1,7 @@
 // rates_api.inc -- part of api.hip: per-stream sample rates on the device path, one call per side.
 //   lyra_hip_encode_rates_dev: LyraEncoder::Encode (lyra_encoder.cc:113-156) for a batch whose encoders were created at
 //     different rates (LyraEncoder::Create, lyra_encoder.cc:59: no resampler at 16 kHz): resample_rates_kernel (each row's own
-//     design -> the 16 kHz hop, and the id list with -1 where the rate is no codec rate), then encode_mixed16 on that list
+//     design -> the 16 kHz hop, and the id list with -1 where the rate is no codec rate), then encode16 on that list
 //     with logmel_rates_kernel as the DTX estimator (each row's own filterbank and constants, noise_estimator.cc:96-124).
 //   lyra_hip_decode_lossy_rates_dev: lossy_tick_launch with resample_rates_kernel (16 kHz -> each row's rate) as the last
 //     launch of the tick's noise-stream call; the decoder-side estimator is a 16 kHz one at every rate (lyra_decoder.cc:129).
@@ -10,10 +10,7 @@
 namespace {
 
 void rates_free(lyra_hip_ctx* c) {
-  void* ps[] = {c->d_rs_tab, c->d_noise_tab, c->d_rates_err, c->d_rates_bits};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  c->d_rs_tab = nullptr; c->d_noise_tab = nullptr; c->d_rates_err = nullptr; c->d_rates_bits = nullptr;
+  dfree(c->d_rs_tab, c->d_noise_tab, c->d_rates_err, c->d_rates_bits);
   c->rates_bits_val = -1;
 }
 
@@ -70,16 +67,13 @@ int encode_rates_resample(lyra_hip_ctx* c, const int32_t* d_ids, const int32_t* 
   if ((rc = encq_begin(c, 0, 1))) return rc;
   // The id list travels with the call's features and `live`: without DTX it is the quantizer's mask, read on sq[0] while the
   // next call's resampler already runs on se[0].  One list per call parity, rewritten only after the quantizer of the call
-  // before the previous one (encq_buffer_free), as encode_mixed16 does for `live`.
+  // before the previous one (encq_buffer_free), as encode16 does for `live`.
   int32_t* vids = c->d_rate_ids_call[c->n_encq_calls & 1];
   const EventList busy = encq_buffer_free(c, 0, 1);
   for (int i = 0; i < busy.n; ++i) HIPCHK(c, hipStreamWaitEvent(c->se[0], busy.e[i], 0));
   if ((rc = launch_resample_rates(c, 0, d_ids, d_rates, B, d_pcm_ext, LYRA_HIP_MAX_EXT_HOP, c->d_rs16[0], 320, vids, c->se[0])))
     return rc;
-  if (c->nsub > 1) {   // the chunks of a split encode run on se[1..]: they read what se[0] has just written
-    HIPCHK(c, hipEventRecord(c->ev_ahead_order, c->se[0]));
-    for (int k = 1; k < c->nsub; ++k) HIPCHK(c, hipStreamWaitEvent(c->se[k], c->ev_ahead_order, 0));
-  }
+  if ((rc = se0_to_chunks(c))) return rc;
   *in = c->d_rs16[0];
   *ids = vids;
   return 0;
@@ -124,7 +118,7 @@ int lyra_hip_encode_rates_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, cons
   const int16_t* in = nullptr;
   const int32_t* ids = nullptr;
   if ((rc = encode_rates_resample(c, d_ids, d_sample_rates, B, d_pcm_ext, &in, &ids))) return rc;
-  return encode_mixed16(c, ids, B, in, d_num_bits, dtx != 0, d_packets, d_packet_bytes, d_sample_rates);
+  return encode16(c, ids, B, in, dtx != 0, 0, d_num_bits, d_sample_rates, d_packets, d_packet_bytes);
 }
 
 int lyra_hip_decode_lossy_rates_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_packets,
@@ -140,15 +134,7 @@ int lyra_hip_decode_lossy_rates_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B
 }
 
 long lyra_hip_rates_errors(lyra_hip_ctx* c, int clear) {
-  if (!c) return LYRA_HIP_EINVAL;
-  if (!c->d_rates_err) return 0;
-  DEVSCOPE(c);
-  int rc = sync_all(c);
-  if (rc) return rc;
-  unsigned n = 0;
-  HIPCHK(c, hipMemcpy(&n, c->d_rates_err, 4, hipMemcpyDeviceToHost));
-  if (clear) HIPCHK(c, hipMemset(c->d_rates_err, 0, 4));
-  return (long)n;
+  return read_error_counter(c, &lyra_hip_ctx::d_rates_err, clear);
 }
 
 }  // extern "C"

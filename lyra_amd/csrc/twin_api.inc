@@ -13,13 +13,9 @@
 namespace {
 
 void twin_free(lyra_hip_ctx* c) {
-  void* ps[] = {c->d_twin_gan, c->d_twin_cng, c->d_twin_noise, c->d_twin_out, c->d_twin_ext, c->d_twin_fade, c->d_twin_iota,
-                c->d_twin_args};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
+  dfree(c->d_twin_gan, c->d_twin_cng, c->d_twin_noise, c->d_twin_out, c->d_twin_ext, c->d_twin_iota, c->d_twin_args);
   if (c->h_twin_args) (void)hipHostFree(c->h_twin_args);
-  c->d_twin_gan = c->d_twin_cng = c->d_twin_noise = c->d_twin_out = c->d_twin_ext = nullptr;
-  c->d_twin_fade = nullptr; c->d_twin_iota = nullptr; c->d_twin_args = nullptr; c->h_twin_args = nullptr;
+  c->h_twin_args = nullptr;
   c->twin_out_cap = c->twin_ext_cap = c->twin_args_cap = c->twin_args_used = 0;
   c->twin_out_n = 0;
 }
@@ -36,23 +32,37 @@ std::vector<float> fade_weights() {
   }
   return w;
 }
+// The table on the device: created at first use by whichever of its users (the twin's assemble, the lossy tick's mix,
+// decode_samples' slices) comes first, freed by lyra_hip_destroy
+int fade_ensure(lyra_hip_ctx* c) {
+  if (c->d_fade) return 0;
+  const std::vector<float> w = fade_weights();
+  float* p = nullptr;
+  HIPCHK(c, dalloc(&p, w.size()));
+  const hipError_t e = hipMemcpy(p, w.data(), w.size() * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(p);
+    return fail(c, LYRA_HIP_EHIP, "upload of the fade weights failed: %s", hipGetErrorString(e));
+  }
+  c->d_fade = p;
+  return 0;
+}
 
 int twin_ensure(lyra_hip_ctx* c) {
+  int rc = fade_ensure(c);
+  if (rc) return rc;
   if (c->d_twin_gan) return 0;
   const size_t n = (size_t)c->max_streams;
   HIPCHK(c, dalloc(&c->d_twin_gan, n * 320));
   HIPCHK(c, dalloc(&c->d_twin_cng, n * 320));
   HIPCHK(c, dalloc(&c->d_twin_noise, n * 320));
   HIPCHK(c, dalloc(&c->d_twin_iota, n));
-  HIPCHK(c, dalloc(&c->d_twin_fade, (size_t)TWIN_FADE_N));
   c->twin_args_cap = 2 * (n * 1024 + 65536);   // two halves: one per request in flight (lyra_hip_twin_fetch_begin)
   HIPCHK(c, dalloc(&c->d_twin_args, c->twin_args_cap));
   HIPCHK(c, hipHostMalloc((void**)&c->h_twin_args, c->twin_args_cap, hipHostMallocDefault));
   std::vector<int32_t> iota(n);
   for (size_t i = 0; i < n; ++i) iota[i] = (int32_t)i;
-  const std::vector<float> w = fade_weights();
   HIPCHK(c, hipMemcpy(c->d_twin_iota, iota.data(), n * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_twin_fade, w.data(), w.size() * 4, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -140,7 +150,7 @@ int lyra_hip_twin_comfort_noise(lyra_hip_ctx* c, const int32_t* ids, int B) {
   int rc = twin_begin(c, ids, B, &d_ids);
   if (rc) return rc;
   // AddFeatures(noise_estimator_->noise_estimate()) + RunConditioning (lyra_decoder.cc:328-340): the estimate is read in place
-  if ((rc = launch_cng(c, d_ids, B, nullptr, c->d_pcm_out))) return rc;
+  if ((rc = launch_cng(c, c->sd[0], d_ids, B, nullptr, c->d_pcm_out))) return rc;
   return twin_scatter(c, d_ids, B, c->d_twin_cng);
 }
 
@@ -178,7 +188,7 @@ int lyra_hip_twin_assemble(lyra_hip_ctx* c, const lyra_hip_twin_slice* slices, i
   TwinSlice* d_sl;
   if ((rc = twin_stage(c, slices, (size_t)B * sizeof(TwinSlice), (void**)&d_sl))) return rc;
   hipLaunchKernelGGL(twin_assemble_kernel, dim3(B), dim3(256), 0, c->sd[0], (const TwinSlice*)d_sl, B,
-                     (const int16_t*)c->d_twin_gan, (const int16_t*)c->d_twin_cng, (const float*)c->d_twin_fade,
+                     (const int16_t*)c->d_twin_gan, (const int16_t*)c->d_twin_cng, (const float*)c->d_fade,
                      c->d_twin_out, out_samples, c->d_twin_noise);
   HIPCHK(c, hipGetLastError());
   return 0;
