@@ -564,6 +564,50 @@ int lyra_hip_decode_end(lyra_hip_ctx* ctx, int16_t* pcm);
 int lyra_hip_twin_fetch_begin(lyra_hip_ctx* ctx, int num_streams, int num_internal_samples, int out_rate);
 int lyra_hip_twin_fetch_end(lyra_hip_ctx* ctx, int16_t* out);
 
+/* ---- Stream state as blobs: move live streams between ids, contexts, GPUs and processes ------------------------------------
+ * A stream's whole codec state -- its slots in the 12 state regions plus what lyra_hip_decode_samples_dev keeps by stream id
+ * (the waiting feature vectors and the two hops in progress) -- as ONE relocatable blob of lyra_hip_stream_blob_bytes()
+ * bytes (a multiple of 256; format, header and the validation list: lyra_amd/csrc/stream_blob.h).  Row b of `blobs` is the
+ * state of stream_ids[b]; rows are lyra_hip_stream_blob_bytes() apart.  A stream that is exported, imported elsewhere and
+ * continued there produces, from the same inputs, bit for bit what it would have produced had it stayed -- comfort noise
+ * included: the blob carries the stream's effective comfort-noise key (exporting context's seed ^ source id), and import
+ * stores what makes the target slot keep that key under the target's seed and id.  Blobs of equal stream state are
+ * byte-identical whichever context or id they came from; every freshly reset stream has the same blob.
+ * Conventions:
+ *   - CONTROL-PLANE calls with lyra_hip_reset_streams' ordering: the context is drained before and after, nothing is in
+ *     flight while state is read or replaced, all four synchronise.  LYRA_HIP_EINVAL while a pipelined host request
+ *     (lyra_hip_encode_begin, lyra_hip_decode_begin, lyra_hip_twin_fetch_begin, lyra_hip_decode_samples_begin without its
+ *     _end, or a twin request being assembled) is outstanding.  There is no asynchronous form.
+ *   - `_dev` forms: d_stream_ids and d_blobs are device pointers, d_blobs 16-byte aligned; a blob goes GPU to GPU without
+ *     touching the host (copy it between devices yourself).  A row of id -1 is skipped; so is an id outside the context
+ *     (counted by import; export leaves that blob row unwritten and counts nothing: clear d_blobs first if ids may be out
+ *     of range).  The `_dev` forms cannot look at the ids: a call must not name a stream twice -- two rows of an import
+ *     with the same target id race on its slots, as in every `_dev` call.  Host forms reject ids outside 0..max_streams-1 and duplicates, as every host form does.
+ *   - `sides` of import: LYRA_HIP_STATE_ENCODER writes the encoder's regions only (the three encoder stages, the DTX noise
+ *     estimator, the input resampler), LYRA_HIP_STATE_DECODER the decoder's (the three decoder stages, log-mel history,
+ *     decoder-side noise estimator, output resampler, comfort-noise generator with the loss state machines, and the
+ *     decode-samples arrays, which are allocated as the first lyra_hip_decode_samples_dev call would).  The other side of
+ *     the target stream is left as it is.  Export always writes both.
+ *   - A blob is untrusted.  Import checks the header against its own constants and every integer of the payload that a
+ *     kernel forms an address or a trip count from against its domain, BEFORE it writes.  The `_dev` form refuses row by
+ *     row on the device: a refused row leaves its target stream untouched, adds one to lyra_hip_import_errors, and the other
+ *     rows of the call are imported.  The host form validates every row on the host first and returns LYRA_HIP_EINVAL with
+ *     nothing enqueued and nothing changed if any row fails.
+ *   - Caller duties: a stream's sample rate travels with it (the rate belongs to the stream, see
+ *     lyra_hip_encode_rates_dev), as does the DTX encoder's lyra_hip_set_encoder_sample_rate.  Source and target context
+ *     must have the same requant mode; a blob from another mode, model version or state layout is refused, not converted.
+ *   - Not in a blob: the decoder twin's by-id hops (BatchLyraDecoder keeps its per-stream state on the host). */
+#define LYRA_HIP_STATE_ENCODER 1u
+#define LYRA_HIP_STATE_DECODER 2u
+size_t lyra_hip_stream_blob_bytes(void);
+int lyra_hip_export_streams_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_ids, int B, uint8_t* d_blobs);
+int lyra_hip_import_streams_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_ids, int B, const uint8_t* d_blobs, unsigned sides);
+int lyra_hip_export_streams(lyra_hip_ctx* ctx, const int32_t* stream_ids, int B, uint8_t* blobs);
+int lyra_hip_import_streams(lyra_hip_ctx* ctx, const int32_t* stream_ids, int B, const uint8_t* blobs, unsigned sides);
+/* Blob rows lyra_hip_import_streams_dev refused since context creation (or the last clear); synchronises.  clear != 0
+ * resets the count.  Negative: error. */
+long lyra_hip_import_errors(lyra_hip_ctx* ctx, int clear);
+
 /* The context's FOUR HIP streams (hipStream_t as void*), for event timing / ordering by the caller: encode side, decode
  * side, the quantizer stream of lyra_hip_encode_dev / lyra_hip_encode_dtx_dev, and the noise stream.
  *  - The packets of the two encode calls are written on the QUANTIZER stream: lyra_hip_stream() does not cover them (it

@@ -156,6 +156,14 @@ def _load(path=None):
         L.lyra_hip_decode_samples_dev.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp]
         L.lyra_hip_decode_samples_errors.argtypes = [vp, ci]
         L.lyra_hip_decode_samples_errors.restype = C.c_long
+    if hasattr(L, "lyra_hip_export_streams"):
+        L.lyra_hip_stream_blob_bytes.restype = C.c_size_t
+        L.lyra_hip_stream_blob_bytes.argtypes = []
+        for suf in ("", "_dev"):
+            getattr(L, f"lyra_hip_export_streams{suf}").argtypes = [vp, vp, ci, vp]
+            getattr(L, f"lyra_hip_import_streams{suf}").argtypes = [vp, vp, ci, vp, C.c_uint]
+        L.lyra_hip_import_errors.argtypes = [vp, ci]
+        L.lyra_hip_import_errors.restype = C.c_long
     L.lyra_hip_set_cng_seed.argtypes = [vp, C.c_uint64]
     L.lyra_hip_set_encoder_sample_rate.argtypes = [vp, C.c_int]
     L.lyra_hip_stream.restype = vp
@@ -181,6 +189,9 @@ def _load(path=None):
     L.lyra_hip_debug_read.argtypes = [vp, ci, vp, C.c_long]
     _libs[path] = L
     return L
+
+
+STATE_ENCODER, STATE_DECODER, STATE_BOTH = 1, 2, 3   # LYRA_HIP_STATE_*: the `sides` of import_streams
 
 
 def _np(a, dtype, shape):
@@ -657,6 +668,44 @@ class LyraHip:
     def decode_samples_errors(self, clear=False):
         """Invalid packet sizes plus packets that found the feature FIFO full, seen by decode_samples_dev (synchronises)."""
         n = self.L.lyra_hip_decode_samples_errors(self.h, 1 if clear else 0)
+        self._chk(n if n < 0 else 0)
+        return n
+
+    # -- stream state as blobs (lyra_hip_export_streams / lyra_hip_import_streams) -------------------------------------
+    def stream_blob_bytes(self):
+        """Bytes of one stream's state blob (a multiple of 256)."""
+        return self.L.lyra_hip_stream_blob_bytes()
+
+    def export_streams(self, stream_ids):
+        """The whole codec state of the listed streams -> uint8 [B][stream_blob_bytes()].  Drains the context."""
+        ids = _np(stream_ids, np.int32, (-1,))
+        out = np.empty((ids.size, self.stream_blob_bytes()), np.uint8)
+        self._chk(self.L.lyra_hip_export_streams(self.h, ids.ctypes.data, ids.size, out.ctypes.data))
+        return out
+
+    def import_streams(self, stream_ids, blobs, sides=STATE_BOTH):
+        """Replace the state of stream_ids[b] by blobs[b] (uint8 [B][stream_blob_bytes()]); sides: STATE_ENCODER,
+        STATE_DECODER or both.  Every blob is validated first: one bad blob and nothing changes (LyraHipError)."""
+        ids = _np(stream_ids, np.int32, (-1,))
+        blobs = _np(blobs, np.uint8, (ids.size, self.stream_blob_bytes()))
+        self._chk(self.L.lyra_hip_import_streams(self.h, ids.ctypes.data, ids.size, blobs.ctypes.data, sides))
+
+    def export_streams_dev(self, d_ids, d_blobs):
+        """export_streams on device buffers: d_ids int32 [B] (-1 skips the row), d_blobs uint8 [B][stream_blob_bytes()]."""
+        B = d_ids.shape[0]
+        self._dev_call(self.L.lyra_hip_export_streams_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
+                       self._dev_ptr(d_blobs, "uint8", (B, self.stream_blob_bytes()), "blobs"))
+
+    def import_streams_dev(self, d_ids, d_blobs, sides=STATE_BOTH):
+        """import_streams on device buffers.  A blob that fails validation is skipped on the device, its target stream
+        left untouched and counted in import_errors(); the other rows are imported."""
+        B = d_ids.shape[0]
+        self._dev_call(self.L.lyra_hip_import_streams_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
+                       self._dev_ptr(d_blobs, "uint8", (B, self.stream_blob_bytes()), "blobs"), sides)
+
+    def import_errors(self, clear=False):
+        """Blob rows import_streams_dev refused (synchronises)."""
+        n = self.L.lyra_hip_import_errors(self.h, 1 if clear else 0)
         self._chk(n if n < 0 else 0)
         return n
 

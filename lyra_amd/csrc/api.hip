@@ -143,6 +143,10 @@ struct lyra_hip_ctx {
   unsigned* d_ds_err = nullptr;      // invalid packet sizes + packets that found the ring full
   long n_ds_calls = 0;
   void* ds_host = nullptr;           // DsHost: the two requests in flight of lyra_hip_decode_samples_begin / _end
+  // lyra_hip_export_streams / lyra_hip_import_streams (stream_state_api.inc)
+  unsigned* d_import_err = nullptr;  // blob rows lyra_hip_import_streams_dev refused
+  uint8_t* d_blobs = nullptr;        // staging of the host forms, blob_cap rows
+  int blob_cap = 0;
   // per-stream sample rates (rates_api.inc)
   ResampleP* d_rs_tab = nullptr;     // [2][3] polyphase designs: [rate -> 16 kHz | 16 kHz -> rate][8000, 32000, 48000]
   NoiseP* d_noise_tab = nullptr;     // [4] noise_params of 8 / 16 / 32 / 48 kHz
@@ -223,6 +227,7 @@ void lossy_free(lyra_hip_ctx* c);
 void ds_free(lyra_hip_ctx* c);
 void pipe_free(lyra_hip_ctx* c);
 void rates_free(lyra_hip_ctx* c);
+void blob_free(lyra_hip_ctx* c);
 // One owner per device buffer.  Buffers that are sized by one count (the frames of a call, the streams of the context) are
 // listed ONCE, as {slot, bytes per row, name}; free_bufs and alloc_bufs walk that list.  dfree is for the buffers with a size
 // of their own.  (A slot is the T* member seen as a void*, the hipMalloc((void**)&p) idiom of dalloc: it assumes that all
@@ -1107,6 +1112,7 @@ void lyra_hip_destroy(lyra_hip_ctx* c) {
   if (c->sn) (void)hipStreamDestroy(c->sn);
   dfree(c->d_state, c->d_rvq_stats, c->d_mixed_err, c->d_fade);
   rates_free(c);
+  blob_free(c);
   free_model(&c->model);
   delete c;
 }
@@ -2059,3 +2065,4 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
 #include "mixed_api.inc"
 #include "rates_api.inc"
 #include "decode_samples_api.inc"
+#include "stream_state_api.inc"

@@ -59,10 +59,16 @@ void ds_free(lyra_hip_ctx* c) {
   dfree(c->d_ds_err);
 }
 
-int ds_ensure(lyra_hip_ctx* c, int B) {
+int ds_ensure_streams(lyra_hip_ctx* c) {   // (also what lyra_hip_import_streams needs before it writes a decoder side)
   // by stream id; contents only matter while a stream's counters say so: no reset needed.  Each pointer is tested on its
   // own (alloc_bufs), so a call after a failed allocation allocates only what is still missing.
-  int rc = alloc_bufs(c, ds_stream_bufs(c), (size_t)c->max_streams);
+  // One spare row behind the last stream's: an imported DsState whose fields are each in their domain but contradict each
+  // other can make ds_slice_kernel read up to a hop past a held hop (stream_blob.h).
+  return alloc_bufs(c, ds_stream_bufs(c), (size_t)c->max_streams + 1);
+}
+
+int ds_ensure(lyra_hip_ctx* c, int B) {
+  int rc = ds_ensure_streams(c);
   if (!rc) rc = fade_ensure(c);
   if (rc) return rc;
   if (!c->d_ds_err) {

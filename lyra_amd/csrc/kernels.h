@@ -211,5 +211,14 @@ struct ResetP { int8_t e_r2_1, e_r2_2, e_d2, e_bott, d_r0_0, d_r0_1, d_r0_2; };
 // region base pointers and per-stream slot sizes (state_layout.h), filled on the host, passed by value
 struct StateMap { uint8_t* base[st::R_COUNT]; int bytes[st::R_COUNT]; };
 __global__ void reset_kernel(const ResetP* P, const int32_t* ids, int n, int all, StateMap sm);
+// ---- stream state as blobs (stream_state_kernels.hip, stream_blob.h; lyra_hip_export_streams / lyra_hip_import_streams) ----
+// one workgroup per row of blobs [B][sb::BYTES]; ring / gan / cng: the by-id arrays of lyra_hip_decode_samples_dev (export:
+// null = never allocated, the section is zero); import judges a row (sb::validate) before it writes, *err counts the refused
+__global__ void state_export_kernel(const int32_t* ids, int B, int max_streams, StateMap sm, const float* ring,
+                                    const int16_t* gan, const int16_t* cng, unsigned mode, unsigned long long seed,
+                                    uint8_t* blobs);
+__global__ void state_import_kernel(const int32_t* ids, int B, int max_streams, StateMap sm, float* ring, int16_t* gan,
+                                    int16_t* cng, unsigned mode, unsigned long long seed, unsigned sides, const uint8_t* blobs,
+                                    unsigned* err);
 
 }  // namespace lyra

@@ -923,7 +923,8 @@ __global__ __launch_bounds__(256) void cng_kernel(const MelP* __restrict__ Pp, u
   __syncthreads();
   const double PI = 3.14159265358979323846;
   const double gain = __builtin_sqrt(1024.0 * 320.0 / (384.0 * 240.0));
-  const unsigned long long sd = seed ^ (unsigned long long)(unsigned)id;
+  // (the slot key is zero unless the stream was imported from another id or context: state_layout.h C_KEY)
+  const unsigned long long sd = seed ^ (unsigned long long)(unsigned)id ^ *reinterpret_cast<const unsigned long long*>(slot + st::C_KEY);
   for (int i = P.start + tid; i <= P.end; i += 256) {
     // band[v + 1] = first bin whose lower band is >= v: find this bin's lower band ch (-1 .. 159)
     int lo = 0, hi = 161;   // band index domain v + 1

@@ -101,6 +101,10 @@ constexpr int RS_BYTES = align256(RS_HIST + (RS_TAPS - 1) * 4);
 // ---- R_CNG: ComfortNoiseGenerator (lyra/comfort_noise_generator.h): overlap-add tail of the inverse STFT --------------
 constexpr int C_HOP = 0;                           // uint64: hops generated (random-phase counter)
 // bytes 8..11: the packet-loss control word of lyra_hip_decode_lossy_dev (lossy_plan.h LOSSY_CTL; 0 = initial state)
+// bytes 16..43: DsState of lyra_hip_decode_samples_dev (decode_samples_plan.h DS_STATE); 12..15 and 44..47, 56..63 unused
+constexpr int C_KEY = 48;                          // uint64 slot key: the stream's comfort-noise phases are keyed by
+                                                   // seed ^ id ^ this word; 0 except after lyra_hip_import_streams, which
+                                                   // makes a moved stream keep the key it had where it started (stream_blob.h)
 constexpr int C_OLA = 64;                          // f64[1024] overlap-add accumulator, [0, 320) = next hop
 constexpr int CNG_BYTES = align256(C_OLA + 1024 * 8);
 

@@ -71,6 +71,13 @@ class BatchLyraEncoder {
   int frame_rate() const { return kBatchFrameRate; }
   int num_streams() const { return num_streams_; }
   int packet_size() const { return BatchBitrateToPacketSize(bitrate_); }
+  // One stream's ENCODER state as a blob that ImportStream of any BatchLyraEncoder of the same sample rate accepts, under any
+  // stream index (include/lyra_hip.h "Stream state as blobs" behind a 16-byte class header: kind, sample_rate_hz).  The
+  // stream goes on there bit for bit.  Both refuse (nullopt / false + LOG(ERROR)) while hops are in flight; ImportStream
+  // refuses a blob of another class, another rate or one that fails validation, and then changes nothing.
+  // (defined in lyra_stream_state.cc)
+  std::optional<std::vector<uint8_t>> ExportStream(int stream);
+  bool ImportStream(int stream, absl::Span<const uint8_t> blob);
 
  private:
   BatchLyraEncoder(lyra_hip_ctx* ctx, int sample_rate_hz, int bitrate, bool enable_dtx, int num_streams);

@@ -44,6 +44,13 @@ class DeviceLyraDecoder {
   int frame_rate() const { return kBatchFrameRate; }
   bool is_comfort_noise(int stream) const;
   int num_streams() const { return num_streams_; }
+  // One stream's DECODER state -- networks, estimator, resampler, comfort noise, the loss state machine with its waiting
+  // packets and hops in progress -- as a blob for ImportStream of any DeviceLyraDecoder of the same sample rate, under any
+  // stream index (BatchLyraEncoder::ExportStream's format, kind "device decoder").  A packet staged for the stream is handed
+  // to the device first, so it is part of the blob.  ImportStream rebuilds the stream's host mirror from the blob and drops a
+  // packet staged for the target.  Both refuse while requests are in flight.  (defined in lyra_stream_state.cc)
+  std::optional<std::vector<uint8_t>> ExportStream(int stream);
+  bool ImportStream(int stream, absl::Span<const uint8_t> blob);
 
  private:
   DeviceLyraDecoder(lyra_hip_ctx* ctx, int sample_rate_hz, int num_streams);
