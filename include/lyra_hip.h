@@ -608,6 +608,59 @@ int lyra_hip_import_streams(lyra_hip_ctx* ctx, const int32_t* stream_ids, int B,
  * resets the count.  Negative: error. */
 long lyra_hip_import_errors(lyra_hip_ctx* ctx, int clear);
 
+/* ---- Time-parallel spans: one long recording through the batched kernels ------------------------------------------------------
+ * The whole encoder and decoder state is convolution history, so a stream that starts from the reset state
+ * lyra_hip_span_warmup_frames(side) hops early holds, after them, exactly the state of the stream that ran from the start
+ * (derivation from the graphs' kernel sizes, strides and dilations: DESIGN.md 4.5, lyra_amd/csrc/spans_plan.h).  These calls
+ * cut long spans into chunks, run chunk 0 on the span's own stream and the others on scratch streams ("lanes") behind a
+ * discarded warm-up, all chunks advancing together through the batched stage kernels, and hand the last chunk's state back:
+ * packets, PCM and the span stream's state afterwards are the sequential result BIT FOR BIT, at batch throughput, for
+ * (L + W) / L times the work with chunks of L hops.
+ *   A span is n_frames consecutive hops of stream stream_id that lie at frame first_frame of the two FRAME-MAJOR buffers
+ *   (PCM [frames][320] int16, 16-byte aligned; packets [frames][num_bits / 8 rounded up]); frames outside every span are
+ *   neither read nor written.  A span CONTINUES from its stream's live state (for a fresh stream it is the whole file) and
+ *   leaves the stream as the hop-by-hop calls would: lyra_hip_export_streams gives the same bytes, hop-by-hop calls may follow.
+ *   Only the encoder's (encode_spans) or the decoder's (decode_spans) three stage regions of the stream change.
+ *   Lanes are streams of the same context that the caller lends for the call; whatever they held is lost: their encoder-side
+ *   (encode_spans) or decoder-side (decode_spans) stage state is the reset state when the call's work is done.
+ *   n_lanes == 0, or spans too short to cut, run sequentially on the spans' own ids.
+ *   Span ids and lane ids must be valid, distinct and disjoint and the spans' frame ranges non-negative and disjoint, else
+ *   LYRA_HIP_EINVAL with nothing enqueued.  spans and lane_ids are HOST arrays in every form, copied at call time.
+ *   `_dev` forms enqueue and do not synchronise (a call that follows another span call of its side first waits until that
+ *   call's plan upload has run); each is ONE call of its side for rules (1) to (3) of "Streams" and runs on
+ *   lyra_hip_stream() / lyra_hip_stream_decode() -- the packets too, the quantizer stream is not used.  The host-buffer forms
+ *   stage frames 0 .. the last span's end, run, synchronise and write the spans' frames of the output.
+ * Out of scope: DTX, packet loss / comfort noise (the NoiseEstimator is a true recurrence, not history), sample rates other
+ * than 16 kHz, per-span bitrates.  LYRA_HIP_SUBBATCHES > 1 is accepted (the call is not split). */
+typedef struct lyra_hip_span { int32_t stream_id; int64_t first_frame; int64_t n_frames; } lyra_hip_span;
+/* warm-up hops of side LYRA_HIP_SIDE_ENCODER / LYRA_HIP_SIDE_DECODER (25 / 25); LYRA_HIP_EINVAL for any other side */
+int lyra_hip_span_warmup_frames(int side);
+int lyra_hip_encode_spans_dev(lyra_hip_ctx* ctx, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                              const int16_t* d_pcm /* [frames][320] */, int num_bits, uint8_t* d_packets /* [frames][bytes] */);
+int lyra_hip_decode_spans_dev(lyra_hip_ctx* ctx, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                              const uint8_t* d_packets /* [frames][bytes] */, int num_bits, int16_t* d_pcm /* [frames][320] */);
+int lyra_hip_encode_spans(lyra_hip_ctx* ctx, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                          const int16_t* pcm, int num_bits, uint8_t* packets);
+int lyra_hip_decode_spans(lyra_hip_ctx* ctx, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                          const uint8_t* packets, int num_bits, int16_t* pcm);
+/* The planner of the four calls, a pure function (no context, no device).  Chunk r is row r of the call's batch: it runs on
+ * stream_id for n_warmup + n_frames steps; step i reads buffer frame first_frame - n_warmup + i and from step n_warmup on
+ * writes its output there.  Chunk 0 of a span runs on the span's own stream with no warm-up; the others on lanes, behind
+ * n_warmup = lyra_hip_span_warmup_frames(side) hops of the span's own earlier frames.  Order: the spans' own chunks by falling
+ * step count, then the lane chunks by falling step count, so the lanes that run at step i are a prefix of the lane rows.
+ * phase_offset (lanes): frames of the span in front of the chunk's first replayed hop, mod 18 -- the lane's ring phases start
+ * at the span stream's plus this, so the state that the last chunk (last = 1) hands over has the sequential stream's.
+ * What it minimises: the number of steps (about the longest chunk + warm-up), see lyra_amd/csrc/spans_plan.h.
+ * Returns the number of chunks written (<= n_spans + n_lanes; spans of no frames have none), *n_steps = steps of the call;
+ * LYRA_HIP_EINVAL for ids outside 0..max_streams-1 or named twice, overlapping frame ranges, negative values, cap too small. */
+typedef struct lyra_hip_span_chunk {
+  int32_t stream_id, span;
+  int64_t first_frame;
+  int32_t n_frames, n_warmup, phase_offset, last;
+} lyra_hip_span_chunk;
+int lyra_hip_spans_plan(int side, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes, int max_streams,
+                        lyra_hip_span_chunk* chunks, int cap, int* n_steps);
+
 /* The context's FOUR HIP streams (hipStream_t as void*), for event timing / ordering by the caller: encode side, decode
  * side, the quantizer stream of lyra_hip_encode_dev / lyra_hip_encode_dtx_dev, and the noise stream.
  *  - The packets of the two encode calls are written on the QUANTIZER stream: lyra_hip_stream() does not cover them (it

@@ -85,6 +85,40 @@ STEP_MIXED_RATE = 64
 _libs = {}
 
 
+# lyra_hip_span / lyra_hip_span_chunk (include/lyra_hip.h) as numpy record types
+SPAN_DTYPE = np.dtype([("stream_id", "<i4"), ("first_frame", "<i8"), ("n_frames", "<i8")], align=True)
+SPAN_CHUNK_DTYPE = np.dtype([("stream_id", "<i4"), ("span", "<i4"), ("first_frame", "<i8"), ("n_frames", "<i4"),
+                             ("n_warmup", "<i4"), ("phase_offset", "<i4"), ("last", "<i4")], align=True)
+SIDES = {"encoder": 0, "decoder": 1}
+
+
+def _spans(spans):
+    """[(stream_id, first_frame, n_frames), ...] or a SPAN_DTYPE array -> contiguous SPAN_DTYPE array"""
+    if isinstance(spans, np.ndarray) and spans.dtype == SPAN_DTYPE:
+        return np.ascontiguousarray(spans)
+    return np.array([tuple(int(v) for v in s) for s in spans], SPAN_DTYPE).reshape(-1)
+
+
+def span_warmup_frames(side, lib=None):
+    """Hops a fresh stream replays before its state equals the sequential stream's (lyra_hip_span_warmup_frames)."""
+    return (lib or _load()).lyra_hip_span_warmup_frames(SIDES[side])
+
+
+def spans_plan(side, spans, lane_ids, max_streams, lib=None):
+    """The planner of encode_spans / decode_spans (lyra_hip_spans_plan; no GPU): (chunks as a SPAN_CHUNK_DTYPE array in
+    batch-row order, number of steps).  LyraHipError for what the calls refuse."""
+    L = lib or _load()
+    sp = _spans(spans)
+    lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
+    chunks = np.zeros(sp.size + lanes.size + 1, SPAN_CHUNK_DTYPE)
+    steps = C.c_int(0)
+    n = L.lyra_hip_spans_plan(SIDES[side], sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size, int(max_streams),
+                              chunks.ctypes.data, chunks.size, C.addressof(steps))
+    if n < 0:
+        raise LyraHipError("lyra_hip_spans_plan: invalid spans or lanes")
+    return chunks[:n], steps.value
+
+
 def _load(path=None):
     """The C-ABI library (default: library_path()); a second path loads a build variant beside it (lyra_amd/variants/)."""
     path = os.path.abspath(path or library_path())
@@ -164,6 +198,12 @@ def _load(path=None):
             getattr(L, f"lyra_hip_import_streams{suf}").argtypes = [vp, vp, ci, vp, C.c_uint]
         L.lyra_hip_import_errors.argtypes = [vp, ci]
         L.lyra_hip_import_errors.restype = C.c_long
+    if hasattr(L, "lyra_hip_encode_spans"):
+        L.lyra_hip_span_warmup_frames.argtypes = [ci]
+        L.lyra_hip_spans_plan.argtypes = [ci, vp, ci, vp, ci, ci, vp, ci, vp]
+        for suf in ("", "_dev"):
+            getattr(L, f"lyra_hip_encode_spans{suf}").argtypes = [vp, vp, ci, vp, ci, vp, ci, vp]
+            getattr(L, f"lyra_hip_decode_spans{suf}").argtypes = [vp, vp, ci, vp, ci, vp, ci, vp]
     L.lyra_hip_set_cng_seed.argtypes = [vp, C.c_uint64]
     L.lyra_hip_set_encoder_sample_rate.argtypes = [vp, C.c_int]
     L.lyra_hip_stream.restype = vp
@@ -708,6 +748,59 @@ class LyraHip:
         n = self.L.lyra_hip_import_errors(self.h, 1 if clear else 0)
         self._chk(n if n < 0 else 0)
         return n
+
+    # -- time-parallel spans (lyra_hip_encode_spans / lyra_hip_decode_spans) ----------------------------------------------
+    def encode_spans(self, spans, pcm, num_bits, lane_ids=()):
+        """Long spans of a few streams, time-parallel and bit for bit the hop-by-hop result.  spans: (stream_id,
+        first_frame, n_frames) triples into the frame-major pcm int16 [frames][320]; lane_ids: streams lent as scratch
+        (their encoder state is reset afterwards).  Returns packets uint8 [frames][bytes]; rows outside every span are 0."""
+        sp = _spans(spans)
+        lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
+        pcm = _np(pcm, np.int16, (-1, HOP))
+        out = np.zeros((pcm.shape[0], packet_size(num_bits)), np.uint8)
+        self._check_span_frames(sp, pcm.shape[0])
+        self._chk(self.L.lyra_hip_encode_spans(self.h, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
+                                               pcm.ctypes.data, num_bits, out.ctypes.data))
+        return out
+
+    def decode_spans(self, spans, packets, num_bits, lane_ids=()):
+        """The decoder twin of encode_spans: packets uint8 [frames][bytes] -> pcm int16 [frames][320] (rows outside every
+        span are 0); the lanes' decoder state is reset afterwards."""
+        sp = _spans(spans)
+        lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
+        packets = _np(packets, np.uint8, (-1, packet_size(num_bits)))
+        out = np.zeros((packets.shape[0], HOP), np.int16)
+        self._check_span_frames(sp, packets.shape[0])
+        self._chk(self.L.lyra_hip_decode_spans(self.h, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
+                                               packets.ctypes.data, num_bits, out.ctypes.data))
+        return out
+
+    @staticmethod
+    def _check_span_frames(sp, frames):
+        if sp.size and (np.any(sp["first_frame"] < 0) or np.any(sp["n_frames"] < 0) or
+                        int(np.max(sp["first_frame"] + sp["n_frames"])) > frames):
+            raise LyraHipError(f"spans: a span lies outside the {frames} frames of the buffer")
+
+    def encode_spans_dev(self, spans, d_pcm, num_bits, d_packets, lane_ids=()):
+        """encode_spans on device buffers (spans and lane_ids stay host lists): d_pcm int16 [frames][320], d_packets uint8
+        [frames][bytes].  Enqueues and does not synchronise."""
+        sp = _spans(spans)
+        lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
+        F = d_pcm.shape[0]
+        self._check_span_frames(sp, F)
+        self._dev_call(self.L.lyra_hip_encode_spans_dev, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
+                       self._dev_ptr(d_pcm, "int16", (F, HOP), "pcm"), num_bits,
+                       self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"))
+
+    def decode_spans_dev(self, spans, d_packets, num_bits, d_pcm, lane_ids=()):
+        """decode_spans on device buffers.  Enqueues and does not synchronise."""
+        sp = _spans(spans)
+        lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
+        F = d_pcm.shape[0]
+        self._check_span_frames(sp, F)
+        self._dev_call(self.L.lyra_hip_decode_spans_dev, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
+                       self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"), num_bits,
+                       self._dev_ptr(d_pcm, "int16", (F, HOP), "pcm"))
 
     def noise_receive_dev(self, d_ids, d_pcm, d_is_noise, side="decoder"):
         """NoiseEstimator::ReceiveSamples on device buffers: pcm int16 [B][320] -> is_noise int32 [B]."""

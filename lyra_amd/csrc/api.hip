@@ -12,6 +12,7 @@
 
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -167,6 +168,7 @@ struct lyra_hip_ctx {
   uint8_t* d_twin_args = nullptr;
   size_t twin_args_cap = 0, twin_args_used = 0;
   void* pipe = nullptr;            // PipeState (pipe_api.inc): the two-deep pipelined host-buffer calls, created on first use
+  void* span_calls = nullptr;      // SpanCalls (spans_api.inc): plan rows and scratch of the time-parallel span calls, created on first use
   int tile_div[6] = {1, 1, 1, 1, 1, 1};   // tiles per workgroup of each stage kernel (LYRA_TILE_LOOP), see tile_div()
   bool chunk_local = false;                       // see wait_encode_side
   bool ids_stable = false;                        // inside lyra_hip_run_steps_dev, after its first step: see enc_cross_begin
@@ -228,6 +230,7 @@ void ds_free(lyra_hip_ctx* c);
 void pipe_free(lyra_hip_ctx* c);
 void rates_free(lyra_hip_ctx* c);
 void blob_free(lyra_hip_ctx* c);
+void spans_free(lyra_hip_ctx* c);
 // One owner per device buffer.  Buffers that are sized by one count (the frames of a call, the streams of the context) are
 // listed ONCE, as {slot, bytes per row, name}; free_bufs and alloc_bufs walk that list.  dfree is for the buffers with a size
 // of their own.  (A slot is the T* member seen as a void*, the hipMalloc((void**)&p) idiom of dalloc: it assumes that all
@@ -1085,6 +1088,7 @@ void lyra_hip_destroy(lyra_hip_ctx* c) {
   lossy_free(c);
   ds_free(c);
   pipe_free(c);
+  spans_free(c);
   if (c->h_zc) (void)hipHostFree(c->h_zc);
   c->h_zc = nullptr;
   free_scratch(c);
@@ -2066,3 +2070,4 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
 #include "rates_api.inc"
 #include "decode_samples_api.inc"
 #include "stream_state_api.inc"
+#include "spans_api.inc"

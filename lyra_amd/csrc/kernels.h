@@ -208,6 +208,20 @@ __global__ void ds_slice_kernel(const int32_t* ids, int B, const int32_t* info, 
 size_t logmel_lds_bytes();
 size_t cng_lds_bytes();
 struct ResetP { int8_t e_r2_1, e_r2_2, e_d2, e_bott, d_r0_0, d_r0_1, d_r0_2; };
+// the byte that the 16 bytes at offset o of a slot of region r hold after a reset: zero, or the zero point of an int8 history
+__device__ __forceinline__ int reset_fill(const ResetP& P, int r, int o) {
+  if (r == st::R_E2) {
+    if (o >= st::E_R2_1 && o < st::E_R2_2) return P.e_r2_1;
+    if (o >= st::E_R2_2 && o < st::E_D2) return P.e_r2_2;
+    if (o >= st::E_D2 && o < st::E_BOTT) return P.e_d2;
+    if (o >= st::E_BOTT && o < st::E_BOTT + 2 * 512) return P.e_bott;
+  } else if (r == st::R_D0) {
+    if (o >= st::D_R0_0 && o < st::D_R0_1) return P.d_r0_0;
+    if (o >= st::D_R0_1 && o < st::D_R0_2) return P.d_r0_1;
+    if (o >= st::D_R0_2 && o < st::D_UP1) return P.d_r0_2;
+  }
+  return 0;
+}
 // region base pointers and per-stream slot sizes (state_layout.h), filled on the host, passed by value
 struct StateMap { uint8_t* base[st::R_COUNT]; int bytes[st::R_COUNT]; };
 __global__ void reset_kernel(const ResetP* P, const int32_t* ids, int n, int all, StateMap sm);
@@ -220,5 +234,20 @@ __global__ void state_export_kernel(const int32_t* ids, int B, int max_streams, 
 __global__ void state_import_kernel(const int32_t* ids, int B, int max_streams, StateMap sm, float* ring, int16_t* gan,
                                     int16_t* cng, unsigned mode, unsigned long long seed, unsigned sides, const uint8_t* blobs,
                                     unsigned* err);
+// ---- time-parallel spans (spans_kernels.hip, spans_plan.h; lyra_hip_encode_spans_dev / lyra_hip_decode_spans_dev) ----------
+// One row of a span call's batch: stream `id` runs n_steps steps; step i reads buffer frame frame0 + i and, from step n_warm
+// on, writes its output there.  Lanes (target >= 0) start from the reset state with target's ring phases + phase_add.
+struct SpanRow { int32_t id, n_steps, n_warm, target, phase_add, handover; long long frame0; };
+// step's rows between the frame-major buffer and the dense [B][row_bytes] rows of the stage kernels.  gather: frames -> dense,
+// and step_ids[r] = the row's id while it runs, else -1; scatter: dense -> frames for the rows past their warm-up.
+// unit16: rows are moved in 16-byte units (row_bytes a multiple of 16, both buffers 16-byte aligned), else byte by byte.
+__global__ void span_gather_kernel(const SpanRow* rows, int B, int step, const uint8_t* frames, int row_bytes, int unit16,
+                                   uint8_t* dense, int32_t* step_ids);
+__global__ void span_scatter_kernel(const SpanRow* rows, int B, int step, const uint8_t* dense, int row_bytes, int unit16,
+                                    uint8_t* frames);
+// regions r0 .. r0 + 2 (R_E0 or R_D0) of rows[b].id: the reset state; ring phase words: target's + phase_add (target >= 0)
+__global__ void span_lane_init_kernel(const ResetP* P, const SpanRow* rows, int n, int r0, StateMap sm);
+// rows with handover != 0: regions r0 .. r0 + 2 of the lane -> the same regions of target
+__global__ void span_handover_kernel(const SpanRow* rows, int n, int r0, StateMap sm);
 
 }  // namespace lyra

@@ -1002,17 +1002,7 @@ __global__ __launch_bounds__(256) void reset_kernel(const ResetP* __restrict__ P
     const int bytes = sm.bytes[r];   // (st::REGION_BYTES is a host-side table: no runtime indexing of it here)
     uint8_t* base = sm.base[r] + (size_t)id * bytes;
     for (int o = threadIdx.x * 16; o < bytes; o += 256 * 16) {
-      int v = 0;
-      if (r == st::R_E2) {
-        if (o >= st::E_R2_1 && o < st::E_R2_2) v = P.e_r2_1;
-        else if (o >= st::E_R2_2 && o < st::E_D2) v = P.e_r2_2;
-        else if (o >= st::E_D2 && o < st::E_BOTT) v = P.e_d2;
-        else if (o >= st::E_BOTT && o < st::E_BOTT + 2 * 512) v = P.e_bott;
-      } else if (r == st::R_D0) {
-        if (o >= st::D_R0_0 && o < st::D_R0_1) v = P.d_r0_0;
-        else if (o >= st::D_R0_1 && o < st::D_R0_2) v = P.d_r0_1;
-        else if (o >= st::D_R0_2 && o < st::D_UP1) v = P.d_r0_2;
-      }
+      const int v = reset_fill(P, r, o);
       const int w = (v & 255) * 0x01010101;
       i32x4 q = (i32x4){w, w, w, w};
       if ((r == st::R_NOISE_E || r == st::R_NOISE_D) && o == 0) q[st::N_IS_NOISE / 4] = 1;

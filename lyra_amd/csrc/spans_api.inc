@@ -1,0 +1,277 @@
+// spans_api.inc -- part of api.hip: lyra_hip_encode_spans[_dev] / lyra_hip_decode_spans[_dev], one long recording (or a few)
+// through the batched stage kernels time-parallel (spans_plan.h: the warm-up bound and the planner; spans_kernels.hip: the row
+// movement and the hand-over).  A call is ONE call of its side for the ordering rules of include/lyra_hip.h "Streams": the
+// whole of it runs on the side's first stream (se[0] with the quantizer behind the extractor, as the host form of
+// lyra_hip_encode runs it; sd[0]) between enc_side_begin / _done or dec_side_begin / _done, and works on scratch of its own --
+// the feature buffers of the `_dev` encode calls may still be read by a quantizer on sq[0].
+// Per call: the plan (host), one upload of the rows, lane preparation, T steps of {gather, stages, [quantizer, scatter]},
+// hand-over, lane reset.  Nothing is read back and no step waits for the host.
+#include "spans_plan.h"
+
+static_assert(sizeof(lyra_hip_span) == sizeof(sp::Span) && sizeof(lyra_hip_span_chunk) == sizeof(sp::Chunk) &&
+                  offsetof(lyra_hip_span_chunk, last) == offsetof(sp::Chunk, last) &&
+                  offsetof(lyra_hip_span, n_frames) == offsetof(sp::Span, n_frames),
+              "the ABI structs are the planner's");
+static_assert(LYRA_HIP_SIDE_ENCODER == sp::SIDE_ENC && LYRA_HIP_SIDE_DECODER == sp::SIDE_DEC, "side numbers");
+
+namespace {
+
+struct SpanSide {
+  SpanRow* h_rows = nullptr;        // pinned: the upload of the call in flight
+  SpanRow* d_rows = nullptr;        // [rows_cap]: the batch rows, then one row per lane for the final reset
+  int rows_cap = 0;
+  hipEvent_t ev_up = nullptr;       // end of that upload: h_rows may be rewritten
+  bool up_pending = false;
+  int cap = 0;                      // dense scratch, rows
+  uint8_t* d_in = nullptr;          // [cap][640]  gathered PCM (encode) / packets (decode, 23-byte rows at most)
+  uint8_t* d_out = nullptr;         // [cap][640]  packets (encode) / PCM (decode) in front of the scatter
+  float* d_feat = nullptr;          // [cap][64]   encode: features between extractor and quantizer
+  int32_t* d_step_ids = nullptr;    // [cap]       the step's id list (-1: the row has ended)
+};
+struct SpanCalls { SpanSide side[2]; };
+
+SpanCalls* span_calls_of(lyra_hip_ctx* c) { return static_cast<SpanCalls*>(c->span_calls); }
+
+void span_side_free(SpanSide& S) {
+  if (S.h_rows) (void)hipHostFree(S.h_rows);
+  S.h_rows = nullptr;
+  dfree(S.d_rows, S.d_in, S.d_out, S.d_feat, S.d_step_ids);
+  if (S.ev_up) (void)hipEventDestroy(S.ev_up);
+  S.ev_up = nullptr;
+  S.rows_cap = S.cap = 0;
+}
+
+void spans_free(lyra_hip_ctx* c) {
+  SpanCalls* P = span_calls_of(c);
+  if (!P) return;
+  for (SpanSide& S : P->side) span_side_free(S);
+  delete P;
+  c->span_calls = nullptr;
+}
+
+// buffers of one side for `rows` batch rows + `n_lanes` reset rows; growing drains the side's stream first
+int span_side_ensure(lyra_hip_ctx* c, SpanSide& S, hipStream_t st_, int rows, int n_lanes) {
+  if (!S.ev_up) HIPCHK(c, hipEventCreateWithFlags(&S.ev_up, hipEventDisableTiming));
+  if (S.up_pending) {   // the previous call's upload has to have left the pinned rows
+    HIPCHK(c, hipEventSynchronize(S.ev_up));
+    S.up_pending = false;
+  }
+  if (rows + n_lanes > S.rows_cap) {
+    HIPCHK(c, hipStreamSynchronize(st_));
+    if (S.h_rows) (void)hipHostFree(S.h_rows);
+    S.h_rows = nullptr;
+    dfree(S.d_rows);
+    S.rows_cap = 0;
+    HIPCHK(c, hipHostMalloc((void**)&S.h_rows, (size_t)(rows + n_lanes) * sizeof(SpanRow), hipHostMallocDefault));
+    HIPCHK(c, dalloc(&S.d_rows, (size_t)(rows + n_lanes)));
+    S.rows_cap = rows + n_lanes;
+  }
+  if (rows > S.cap) {
+    HIPCHK(c, hipStreamSynchronize(st_));
+    dfree(S.d_in, S.d_out, S.d_feat, S.d_step_ids);
+    S.cap = 0;
+    HIPCHK(c, dalloc(&S.d_in, (size_t)rows * 640));
+    HIPCHK(c, dalloc(&S.d_out, (size_t)rows * 640));
+    HIPCHK(c, dalloc(&S.d_feat, (size_t)rows * 64));
+    HIPCHK(c, dalloc(&S.d_step_ids, (size_t)rows));
+    S.cap = rows;
+  }
+  return 0;
+}
+
+struct SpanPlan {
+  std::vector<sp::Chunk> chunks;
+  int n_own = 0, n_steps = 0;
+  int64_t end_frame = 0;   // one past the last buffer frame any span names
+};
+
+int span_plan_checked(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                      SpanPlan* P, const char* what) {
+  if (n_spans <= 0 || !spans) return fail(c, LYRA_HIP_EINVAL, "%s: no spans", what);
+  const int n = sp::plan(side, reinterpret_cast<const sp::Span*>(spans), n_spans, lane_ids, n_lanes, c->max_streams, &P->chunks,
+                         &P->n_steps);
+  if (n < 0)
+    return fail(c, LYRA_HIP_EINVAL,
+                "%s: span and lane ids must be distinct streams of the context (0..%d), frame ranges non-negative and disjoint",
+                what, c->max_streams - 1);
+  for (const sp::Chunk& ch : P->chunks) P->n_own += ch.n_warmup == 0;
+  for (int s = 0; s < n_spans; ++s) P->end_frame = std::max<int64_t>(P->end_frame, spans[s].first_frame + spans[s].n_frames);
+  return 0;
+}
+
+void span_fill_rows(const SpanPlan& P, const lyra_hip_span* spans, const int32_t* lane_ids, int n_lanes, SpanRow* rows) {
+  int r = 0;
+  for (const sp::Chunk& ch : P.chunks) {
+    const bool lane = ch.n_warmup > 0;
+    rows[r++] = SpanRow{ch.stream_id, ch.n_warmup + ch.n_frames, ch.n_warmup, lane ? spans[ch.span].stream_id : -1,
+                        ch.phase_offset, ch.last, (long long)(ch.first_frame - ch.n_warmup)};
+  }
+  for (int l = 0; l < n_lanes; ++l) rows[r++] = SpanRow{lane_ids[l], 0, 0, -1, 0, 0, 0};
+}
+
+// rows of the batch that still run at step i: own rows and lane rows are each sorted by falling step count
+int span_batch_at(const SpanPlan& P, const SpanRow* rows, int step, int* own_running) {
+  const int n = (int)P.chunks.size();
+  int own = 0, lanes = 0;
+  while (own < P.n_own && rows[own].n_steps > step) ++own;
+  while (P.n_own + lanes < n && rows[P.n_own + lanes].n_steps > step) ++lanes;
+  *own_running = own;
+  return lanes ? P.n_own + lanes : own;
+}
+
+inline int span_grid(int B, int units) { return (int)(((long long)B * units + 255) / 256); }
+
+// The enqueue of one call.  enc: d_src PCM [frames][320], d_dst packets [frames][nbytes]; else the reverse.
+int spans_enqueue(lyra_hip_ctx* c, bool enc, const SpanPlan& P, const lyra_hip_span* spans, const int32_t* lane_ids,
+                  int n_lanes, const void* d_src, int num_bits, void* d_dst) {
+  if (!c->span_calls) c->span_calls = new SpanCalls();
+  SpanSide& S = span_calls_of(c)->side[enc ? 0 : 1];
+  hipStream_t st_ = enc ? c->se[0] : c->sd[0];
+  const int rows = (int)P.chunks.size(), nbytes = (num_bits + 7) / 8, r0 = enc ? st::R_E0 : st::R_D0;
+  int rc = span_side_ensure(c, S, st_, std::max(rows, 1), n_lanes);
+  if (rc) return rc;
+  if (rows && (rc = ensure_scratch(c, rows))) return rc;   // the stage kernels' own boundary buffers
+  span_fill_rows(P, spans, lane_ids, n_lanes, S.h_rows);
+  if ((rc = enc ? enc_side_begin(c, 0) : dec_side_begin(c, 0))) return rc;
+  if (rows + n_lanes) {
+    HIPCHK(c, hipMemcpyAsync(S.d_rows, S.h_rows, (size_t)(rows + n_lanes) * sizeof(SpanRow), hipMemcpyHostToDevice, st_));
+    HIPCHK(c, hipEventRecord(S.ev_up, st_));
+    S.up_pending = true;
+  }
+  const int n_lane_rows = rows - P.n_own;
+  if (n_lane_rows) {
+    hipLaunchKernelGGL(span_lane_init_kernel, dim3(n_lane_rows), dim3(256), 0, st_, c->model.d_reset, S.d_rows + P.n_own,
+                       n_lane_rows, r0, c->sm);
+    HIPCHK(c, hipGetLastError());
+  }
+  const int W = sp::warmup(enc ? sp::SIDE_ENC : sp::SIDE_DEC);
+  const int in_bytes = enc ? 640 : nbytes, out_bytes = enc ? nbytes : 640;
+  for (int i = 0; i < P.n_steps && !rc; ++i) {
+    int own = 0;
+    const int B = span_batch_at(P, S.h_rows, i, &own);
+    hipLaunchKernelGGL(span_gather_kernel, dim3(span_grid(B, enc ? 40 : in_bytes)), dim3(256), 0, st_, S.d_rows, B, i,
+                       (const uint8_t*)d_src, in_bytes, enc ? 1 : 0, S.d_in, S.d_step_ids);
+    HIPCHK(c, hipGetLastError());
+    if (enc) {
+      rc = launch_extract(c, 0, 0, S.d_step_ids, B, (const int16_t*)S.d_in, S.d_feat);
+      // warm-up steps of the lanes skip the quantizer: before step W only the spans' own rows produce
+      const int Bq = i < W ? own : B;
+      if (!rc && Bq) rc = launch_rvq_encode(c, 0, Bq, S.d_feat, num_bits / 4, nullptr, S.d_out, S.d_step_ids);
+      if (rc || !Bq) continue;
+      hipLaunchKernelGGL(span_scatter_kernel, dim3(span_grid(Bq, out_bytes)), dim3(256), 0, st_, S.d_rows, Bq, i, S.d_out,
+                         out_bytes, 0, (uint8_t*)d_dst);
+    } else {
+      if ((rc = launch_generate(c, 0, 0, S.d_step_ids, B, nullptr, (int16_t*)S.d_out, S.d_in, num_bits / 4))) continue;
+      const int Bs = i < W ? own : B;
+      if (!Bs) continue;
+      hipLaunchKernelGGL(span_scatter_kernel, dim3(span_grid(Bs, 40)), dim3(256), 0, st_, S.d_rows, Bs, i, S.d_out, out_bytes,
+                         1, (uint8_t*)d_dst);
+    }
+    HIPCHK(c, hipGetLastError());
+  }
+  if (!rc && n_lane_rows) {
+    hipLaunchKernelGGL(span_handover_kernel, dim3(n_lane_rows), dim3(256), 0, st_, S.d_rows + P.n_own, n_lane_rows, r0, c->sm);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (!rc && n_lanes) {   // every lane the caller lent, used or not, comes back reset
+    hipLaunchKernelGGL(span_lane_init_kernel, dim3(n_lanes), dim3(256), 0, st_, c->model.d_reset, S.d_rows + rows, n_lanes, r0,
+                       c->sm);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (enc) {
+    if (!rc) rc = enc_side_done(c, 0);
+  } else {
+    if (!rc) rc = dec_side_done(c, 0, 1);
+    c->n_dec_calls++;
+  }
+  return rc;
+}
+
+int spans_call_dev(lyra_hip_ctx* c, bool enc, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                   const void* d_src, int num_bits, void* d_dst, SpanPlan* P) {
+  const char* what = enc ? "encode_spans" : "decode_spans";
+  if (!c) return LYRA_HIP_EINVAL;
+  int rc = check_bits(c, num_bits);
+  if (rc) return rc;
+  if (n_lanes < 0 || (n_lanes && !lane_ids)) return fail(c, LYRA_HIP_EINVAL, "%s: bad lane list", what);
+  if ((rc = span_plan_checked(c, enc ? sp::SIDE_ENC : sp::SIDE_DEC, spans, n_spans, lane_ids, n_lanes, P, what))) return rc;
+  if (P->end_frame && (!d_src || !d_dst)) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
+  const void* pcm = enc ? d_src : d_dst;
+  if (reinterpret_cast<uintptr_t>(pcm) & 15) return fail(c, LYRA_HIP_EINVAL, "%s: the PCM buffer must be 16-byte aligned", what);
+  DEVSCOPE(c);
+  return spans_enqueue(c, enc, *P, spans, lane_ids, n_lanes, d_src, num_bits, d_dst);
+}
+
+// host-buffer form: frames 0 .. end_frame - 1 of both buffers are staged (copy, run, synchronise)
+int spans_call_host(lyra_hip_ctx* c, bool enc, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                    const void* src, int num_bits, void* dst) {
+  if (!c) return LYRA_HIP_EINVAL;
+  int rc = check_bits(c, num_bits);
+  if (rc) return rc;
+  int64_t end = 0;
+  for (int s = 0; spans && s < n_spans; ++s)
+    if (spans[s].first_frame >= 0 && spans[s].n_frames >= 0) end = std::max<int64_t>(end, spans[s].first_frame + spans[s].n_frames);
+  if (end && (!src || !dst)) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", enc ? "encode_spans" : "decode_spans");
+  DEVSCOPE(c);
+  const size_t nbytes = (size_t)(num_bits + 7) / 8, in_b = (size_t)end * (enc ? 640 : nbytes), out_b = (size_t)end * (enc ? nbytes : 640);
+  uint8_t *d_in = nullptr, *d_out = nullptr;
+  if (end) {
+    if (dalloc(&d_in, in_b) != hipSuccess || dalloc(&d_out, out_b) != hipSuccess) {
+      dfree(d_in, d_out);
+      return fail(c, LYRA_HIP_ENOMEM, "spans: staging %zu + %zu bytes failed", in_b, out_b);
+    }
+  }
+  hipStream_t st_ = enc ? c->se[0] : c->sd[0];
+  SpanPlan P;
+  rc = 0;
+  if (end && hipMemcpy(d_in, src, in_b, hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, LYRA_HIP_EHIP, "spans: upload failed");
+  if (!rc) rc = spans_call_dev(c, enc, spans, n_spans, lane_ids, n_lanes, d_in, num_bits, d_out, &P);
+  if (!rc && hipStreamSynchronize(st_) != hipSuccess) rc = fail(c, LYRA_HIP_EHIP, "spans: synchronise failed");
+  const size_t ob = enc ? nbytes : 640;   // only the spans' own frames of the caller's output are written
+  for (int s = 0; !rc && s < n_spans; ++s)
+    if (spans[s].n_frames && hipMemcpy((uint8_t*)dst + spans[s].first_frame * ob, d_out + spans[s].first_frame * ob,
+                                       spans[s].n_frames * ob, hipMemcpyDeviceToHost) != hipSuccess)
+      rc = fail(c, LYRA_HIP_EHIP, "spans: download failed");
+  if (rc) (void)hipStreamSynchronize(st_);
+  dfree(d_in, d_out);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lyra_hip_span_warmup_frames(int side) { return sp::warmup(side) < 0 ? LYRA_HIP_EINVAL : sp::warmup(side); }
+
+int lyra_hip_spans_plan(int side, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes, int max_streams,
+                        lyra_hip_span_chunk* chunks, int cap, int* n_steps) {
+  std::vector<sp::Chunk> out;
+  const int n = sp::plan(side, reinterpret_cast<const sp::Span*>(spans), n_spans, lane_ids, n_lanes, max_streams, &out, n_steps);
+  if (n < 0 || n > cap || (n && !chunks)) return LYRA_HIP_EINVAL;
+  if (n) std::memcpy(chunks, out.data(), (size_t)n * sizeof(sp::Chunk));
+  return n;
+}
+
+int lyra_hip_encode_spans_dev(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                              const int16_t* d_pcm, int num_bits, uint8_t* d_packets) {
+  SpanPlan P;
+  return spans_call_dev(c, true, spans, n_spans, lane_ids, n_lanes, d_pcm, num_bits, d_packets, &P);
+}
+
+int lyra_hip_decode_spans_dev(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                              const uint8_t* d_packets, int num_bits, int16_t* d_pcm) {
+  SpanPlan P;
+  return spans_call_dev(c, false, spans, n_spans, lane_ids, n_lanes, d_packets, num_bits, d_pcm, &P);
+}
+
+int lyra_hip_encode_spans(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                          const int16_t* pcm, int num_bits, uint8_t* packets) {
+  return spans_call_host(c, true, spans, n_spans, lane_ids, n_lanes, pcm, num_bits, packets);
+}
+
+int lyra_hip_decode_spans(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                          const uint8_t* packets, int num_bits, int16_t* pcm) {
+  return spans_call_host(c, false, spans, n_spans, lane_ids, n_lanes, packets, num_bits, pcm);
+}
+
+}  // extern "C"

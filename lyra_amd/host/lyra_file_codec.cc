@@ -11,6 +11,12 @@
 #include "glog/logging.h"
 #include "lyra_batch_codec.h"
 
+// The span calls are bound weakly: this file also links against builds of the C ABI that predate them (an older
+// liblyra_hip.so, the CPU stand-in of the host-logic tests), where the time-parallel functions report that and fail.
+#pragma weak lyra_hip_encode_spans
+#pragma weak lyra_hip_decode_spans
+#pragma weak lyra_hip_span_warmup_frames
+
 namespace chromemedia {
 namespace codec {
 namespace {
@@ -135,9 +141,42 @@ bool EncodeWavs(const std::vector<std::vector<int16_t>>& wav_data, int num_chann
   return true;
 }
 
+namespace {
+bool EncodeFilesImpl(const std::vector<ghc::filesystem::path>& wav_paths,
+                     const std::vector<ghc::filesystem::path>& output_paths, int bitrate, bool enable_preprocessing,
+                     bool enable_dtx, const ghc::filesystem::path& model_path, int num_lanes, int device);
+bool DecodeFilesImpl(const std::vector<ghc::filesystem::path>& encoded_paths,
+                     const std::vector<ghc::filesystem::path>& output_paths, int sample_rate_hz, int bitrate,
+                     const ghc::filesystem::path& model_path, int num_lanes, int device);
+}  // namespace
+
 bool EncodeFiles(const std::vector<ghc::filesystem::path>& wav_paths,
                  const std::vector<ghc::filesystem::path>& output_paths, int bitrate, bool enable_preprocessing,
                  bool enable_dtx, const ghc::filesystem::path& model_path, int device) {
+  return EncodeFilesImpl(wav_paths, output_paths, bitrate, enable_preprocessing, enable_dtx, model_path, -1, device);
+}
+bool EncodeFilesTimeParallel(const std::vector<ghc::filesystem::path>& wav_paths,
+                             const std::vector<ghc::filesystem::path>& output_paths, int bitrate, bool enable_preprocessing,
+                             bool enable_dtx, const ghc::filesystem::path& model_path, int num_lanes, int device) {
+  return EncodeFilesImpl(wav_paths, output_paths, bitrate, enable_preprocessing, enable_dtx, model_path, std::max(num_lanes, 0),
+                         device);
+}
+bool DecodeFiles(const std::vector<ghc::filesystem::path>& encoded_paths,
+                 const std::vector<ghc::filesystem::path>& output_paths, int sample_rate_hz, int bitrate,
+                 const ghc::filesystem::path& model_path, int device) {
+  return DecodeFilesImpl(encoded_paths, output_paths, sample_rate_hz, bitrate, model_path, -1, device);
+}
+bool DecodeFilesTimeParallel(const std::vector<ghc::filesystem::path>& encoded_paths,
+                             const std::vector<ghc::filesystem::path>& output_paths, int sample_rate_hz, int bitrate,
+                             const ghc::filesystem::path& model_path, int num_lanes, int device) {
+  return DecodeFilesImpl(encoded_paths, output_paths, sample_rate_hz, bitrate, model_path, std::max(num_lanes, 0), device);
+}
+
+namespace {
+// num_lanes < 0: hop by hop (EncodeWavs); else time-parallel with that many lanes
+bool EncodeFilesImpl(const std::vector<ghc::filesystem::path>& wav_paths,
+                     const std::vector<ghc::filesystem::path>& output_paths, int bitrate, bool enable_preprocessing,
+                     bool enable_dtx, const ghc::filesystem::path& model_path, int num_lanes, int device) {
   if (wav_paths.size() != output_paths.size()) { LOG(ERROR) << "One output path per input file is required."; return false; }
   std::vector<std::vector<int16_t>> wavs(wav_paths.size());
   int channels = 1, rate = kBatchInternalSampleRateHz;
@@ -148,7 +187,9 @@ bool EncodeFiles(const std::vector<ghc::filesystem::path>& wav_paths,
     if (ch != channels || sr != rate) { LOG(ERROR) << "All files of a batch must share channels / sample rate."; return false; }
   }
   std::vector<std::vector<uint8_t>> encoded;
-  if (!EncodeWavs(wavs, channels, rate, bitrate, enable_preprocessing, enable_dtx, model_path, &encoded, device)) {
+  if (!(num_lanes < 0 ? EncodeWavs(wavs, channels, rate, bitrate, enable_preprocessing, enable_dtx, model_path, &encoded, device)
+                      : EncodeWavsTimeParallel(wavs, channels, rate, bitrate, enable_preprocessing, enable_dtx, model_path,
+                                               &encoded, num_lanes, device))) {
     LOG(ERROR) << "Unable to encode features for the batch starting with " << (wav_paths.empty() ? "" : wav_paths[0].string());
     return false;
   }
@@ -159,6 +200,7 @@ bool EncodeFiles(const std::vector<ghc::filesystem::path>& wav_paths,
   }
   return true;
 }
+}  // namespace
 
 bool DecodeFeaturesBatch(const std::vector<std::vector<uint8_t>>& packet_streams, int packet_size,
                          const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
@@ -205,9 +247,103 @@ bool DecodeFeaturesBatch(const std::vector<std::vector<uint8_t>>& packet_streams
   return true;
 }
 
-bool DecodeFiles(const std::vector<ghc::filesystem::path>& encoded_paths,
-                 const std::vector<ghc::filesystem::path>& output_paths, int sample_rate_hz, int bitrate,
-                 const ghc::filesystem::path& model_path, int device) {
+namespace {
+
+// Frame-major concatenation of the streams' whole rows (row_size units each) + one span per stream; the lanes are the ids
+// behind the files'.  Lanes are capped so that a lane chunk is at least as long as its warm-up (work inflation <= 2).
+struct SpanJob {
+  std::vector<lyra_hip_span> spans;
+  std::vector<int32_t> lanes;
+  int64_t frames = 0;
+};
+template <class T>
+SpanJob MakeSpanJob(const std::vector<std::vector<T>>& streams, size_t row_size, int side, int num_lanes, std::vector<T>* rows) {
+  SpanJob job;
+  for (size_t i = 0; i < streams.size(); ++i) {
+    const int64_t n = (int64_t)(streams[i].size() / row_size);
+    job.spans.push_back({(int32_t)i, job.frames, n});
+    rows->insert(rows->end(), streams[i].begin(), streams[i].begin() + n * row_size);
+    job.frames += n;
+  }
+  const int64_t worth = job.frames / (2 * lyra_hip_span_warmup_frames(side));
+  const int n_lanes = (int)std::max<int64_t>(0, std::min<int64_t>(num_lanes, worth));
+  for (int l = 0; l < n_lanes; ++l) job.lanes.push_back((int32_t)streams.size() + l);
+  return job;
+}
+bool HaveSpanCalls() {
+  if (lyra_hip_encode_spans && lyra_hip_decode_spans && lyra_hip_span_warmup_frames) return true;
+  LOG(ERROR) << "This build of the lyra_hip library has no time-parallel span calls.";
+  return false;
+}
+
+}  // namespace
+
+bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, int num_channels, int sample_rate_hz,
+                            int bitrate, bool enable_preprocessing, bool enable_dtx,
+                            const ghc::filesystem::path& model_path, std::vector<std::vector<uint8_t>>* encoded_features,
+                            int num_lanes, int device) {
+  if (!CheckScope(num_channels, sample_rate_hz, enable_preprocessing, enable_dtx) || !HaveSpanCalls()) return false;
+  const int num_bits = BatchBitrateToNumQuantizedBits(bitrate);
+  if (num_bits < 0) { LOG(ERROR) << "Bitrate " << bitrate << " bps is not supported by codec."; return false; }
+  const int n = (int)wav_data.size();
+  encoded_features->assign(n, {});
+  if (n == 0) return true;
+  std::vector<int16_t> pcm;
+  const SpanJob job = MakeSpanJob(wav_data, kBatchHopSamples, LYRA_HIP_SIDE_ENCODER, num_lanes, &pcm);
+  Ctx ctx;
+  if (lyra_hip_create(model_path.string().c_str(), device, n + (int)job.lanes.size(), LYRA_HIP_REQUANT_DEFAULT, &ctx.c) != 0) {
+    LOG(ERROR) << "Could not create lyra encoder: " << lyra_hip_last_error(nullptr);
+    return false;
+  }
+  const size_t packet_size = (size_t)BatchBitrateToPacketSize(bitrate);
+  std::vector<uint8_t> packets((size_t)job.frames * packet_size);
+  if (lyra_hip_encode_spans(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), pcm.data(), num_bits,
+                            packets.data()) != 0) {
+    LOG(ERROR) << "Unable to encode features: " << lyra_hip_last_error(ctx.c);
+    return false;
+  }
+  for (int i = 0; i < n; ++i)
+    (*encoded_features)[i].assign(packets.begin() + job.spans[i].first_frame * packet_size,
+                                  packets.begin() + (job.spans[i].first_frame + job.spans[i].n_frames) * packet_size);
+  return true;
+}
+
+bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams, int packet_size,
+                                const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
+                                int num_lanes, int device) {
+  int num_bits = -1;
+  for (int br : {3200, 6000, 9200})
+    if (BatchBitrateToPacketSize(br) == packet_size) num_bits = BatchBitrateToNumQuantizedBits(br);
+  if (num_bits < 0) { LOG(ERROR) << "The packet size (" << packet_size << " bytes) is not supported."; return false; }
+  if (!HaveSpanCalls()) return false;
+  const int n = (int)packet_streams.size();
+  decoded_audio->assign(n, {});
+  if (n == 0) return true;
+  for (const auto& p : packet_streams)
+    if (p.size() % packet_size != 0) { LOG(ERROR) << "Encoded stream is not a whole number of packets."; return false; }
+  std::vector<uint8_t> packets;
+  const SpanJob job = MakeSpanJob(packet_streams, (size_t)packet_size, LYRA_HIP_SIDE_DECODER, num_lanes, &packets);
+  Ctx ctx;
+  if (lyra_hip_create(model_path.string().c_str(), device, n + (int)job.lanes.size(), LYRA_HIP_REQUANT_DEFAULT, &ctx.c) != 0) {
+    LOG(ERROR) << "Could not create lyra decoder: " << lyra_hip_last_error(nullptr);
+    return false;
+  }
+  std::vector<int16_t> pcm((size_t)job.frames * kBatchHopSamples);
+  if (lyra_hip_decode_spans(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), packets.data(), num_bits,
+                            pcm.data()) != 0) {
+    LOG(ERROR) << "Could not decode samples: " << lyra_hip_last_error(ctx.c);
+    return false;
+  }
+  for (int i = 0; i < n; ++i)
+    (*decoded_audio)[i].assign(pcm.begin() + job.spans[i].first_frame * kBatchHopSamples,
+                               pcm.begin() + (job.spans[i].first_frame + job.spans[i].n_frames) * kBatchHopSamples);
+  return true;
+}
+
+namespace {
+bool DecodeFilesImpl(const std::vector<ghc::filesystem::path>& encoded_paths,
+                     const std::vector<ghc::filesystem::path>& output_paths, int sample_rate_hz, int bitrate,
+                     const ghc::filesystem::path& model_path, int num_lanes, int device) {
   if (encoded_paths.size() != output_paths.size()) { LOG(ERROR) << "One output path per input file is required."; return false; }
   if (!CheckScope(1, sample_rate_hz, false, false)) return false;
   if (BatchBitrateToNumQuantizedBits(bitrate) < 0) { LOG(ERROR) << "Bitrate " << bitrate << " bps is not supported by codec."; return false; }
@@ -218,11 +354,15 @@ bool DecodeFiles(const std::vector<ghc::filesystem::path>& encoded_paths,
     streams[i].assign((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
   }
   std::vector<std::vector<int16_t>> audio;
-  if (!DecodeFeaturesBatch(streams, BatchBitrateToPacketSize(bitrate), model_path, &audio, device)) return false;
+  const int packet_size = BatchBitrateToPacketSize(bitrate);
+  if (!(num_lanes < 0 ? DecodeFeaturesBatch(streams, packet_size, model_path, &audio, device)
+                      : DecodeFeaturesTimeParallel(streams, packet_size, model_path, &audio, num_lanes, device)))
+    return false;
   for (size_t i = 0; i < output_paths.size(); ++i)
     if (!WriteWav16(output_paths[i], audio[i], 1, sample_rate_hz)) return false;
   return true;
 }
+}  // namespace
 
 }  // namespace codec
 }  // namespace chromemedia

@@ -2,7 +2,7 @@
 // library functions EncodeWav / EncodeFile (cli_example/encoder_main_lib.h:29-38, .cc:42-133) and DecodeFeatures /
 // DecodeFile (cli_example/decoder_main_lib.h:51-69).  File i is stream i of one GPU context; files of different
 // lengths simply leave the batch when they run out of full 20 ms hops (the C ABI takes any subset of stream ids
-// per call).  The `.lyra` format is the reference's: the packets of a stream concatenated, nothing else
+// per call).  The ...TimeParallel forms below give the same bytes for long files at batch throughput.  The `.lyra` format is the reference's: the packets of a stream concatenated, nothing else
 // (encoder_main_lib.cc:120-130; a trailing partial hop is dropped, :71-73).
 //
 // Same scope as lyra_batch_codec.h: 16 kHz mono 16-bit WAV only, no preprocessing / DTX / packet-loss simulation.
@@ -35,6 +35,28 @@ bool DecodeFeaturesBatch(const std::vector<std::vector<uint8_t>>& packet_streams
 bool DecodeFiles(const std::vector<ghc::filesystem::path>& encoded_paths,
                  const std::vector<ghc::filesystem::path>& output_paths, int sample_rate_hz, int bitrate,
                  const ghc::filesystem::path& model_path, int device = 0);
+
+// ---- Time-parallel forms: long recordings at batch throughput --------------------------------------------------------
+// The same results, byte for byte, as the four functions above, through lyra_hip_encode_spans / lyra_hip_decode_spans
+// (include/lyra_hip.h "Time-parallel spans"): every file is one span, cut into chunks that run side by side on up to
+// num_lanes scratch streams of the context, each behind a discarded warm-up.  The hop-by-hop functions above advance one hop
+// per blocking call -- one file, or the long tail of a batch of unequal files, is B = 1; these take a number of steps of about
+// total hops / lanes + warm-up.  Lanes are capped so that a chunk is at least as long as its warm-up.
+constexpr int kDefaultSpanLanes = 4096;
+bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, int num_channels, int sample_rate_hz,
+                            int bitrate, bool enable_preprocessing, bool enable_dtx,
+                            const ghc::filesystem::path& model_path, std::vector<std::vector<uint8_t>>* encoded_features,
+                            int num_lanes = kDefaultSpanLanes, int device = 0);
+bool EncodeFilesTimeParallel(const std::vector<ghc::filesystem::path>& wav_paths,
+                             const std::vector<ghc::filesystem::path>& output_paths, int bitrate, bool enable_preprocessing,
+                             bool enable_dtx, const ghc::filesystem::path& model_path, int num_lanes = kDefaultSpanLanes,
+                             int device = 0);
+bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams, int packet_size,
+                                const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
+                                int num_lanes = kDefaultSpanLanes, int device = 0);
+bool DecodeFilesTimeParallel(const std::vector<ghc::filesystem::path>& encoded_paths,
+                             const std::vector<ghc::filesystem::path>& output_paths, int sample_rate_hz, int bitrate,
+                             const ghc::filesystem::path& model_path, int num_lanes = kDefaultSpanLanes, int device = 0);
 
 // Minimal RIFF/WAVE PCM16 I/O (the reference uses audio_dsp's wav_util: Read16BitWavFileToVector /
 // Write16BitWavFileFromVector).  False on anything but uncompressed 16-bit PCM.

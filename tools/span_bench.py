@@ -1,0 +1,143 @@
+#!/usr/bin/env python3
+"""One long recording, encode then decode, time-parallel against hop by hop (BASELINE config #1: one file).
+
+   python tools/span_bench.py [--hops 180000] [--lanes 4096] [--bits 184] [--out profiles/span_transcode.jsonl]
+
+Two records, appended to --out:
+  span_transcode   lyra_hip_encode_spans_dev + lyra_hip_decode_spans_dev on device buffers, one stream of --hops hops with
+                   --lanes lanes: wall time per direction (after a warm call), useful frames/s (the recording's hops, warm-up
+                   hops not counted), the plan's step count and work inflation (L + W) / L, and `verified`: a prefix of
+                   packets and PCM compared with the hop-by-hop calls lyra_hip_encode / lyra_hip_decode on a twin context.
+  file_transcode   the same recording as a WAV file through lyra_amd/file_demo, hop by hop (EncodeFiles / DecodeFiles: one
+                   blocking call per hop, B = 1) and with --time-parallel, timed in this run as whole processes (context
+                   creation and file I/O included); `verified`: both runs wrote the same .lyra and the same decoded WAV.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+import wave
+
+import numpy as np
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, ROOT)
+
+
+def recording(hops):
+    """speech of the golden recordings, looped, with a slowly varying gain and a little noise so that no two hops are equal"""
+    w = np.load(os.path.join(ROOT, "tests", "golden", "sample_wavs.npz"))
+    src = np.concatenate([w["sample1_16kHz"], w["sample2_16kHz"]]).astype(np.float32)
+    n = hops * 320
+    rng = np.random.default_rng(7)
+    x = src[np.arange(n) % src.size] * (0.6 + 0.4 * np.sin(np.arange(n) * 1e-5)) + rng.integers(-60, 61, n)
+    return np.clip(x, -32768, 32767).astype(np.int16).reshape(hops, 320)
+
+
+def device_leg(args, pcm):
+    import torch
+    import lyra_amd
+    from lyra_amd import codec
+    dev = torch.device("cuda", 0)
+    hops = pcm.shape[0]
+    ctx = lyra_amd.LyraHip(device=0, max_streams=args.lanes + 1, requant="xnnpack")
+    lanes = np.arange(1, args.lanes + 1, dtype=np.int32)
+    spans = [(0, 0, hops)]
+    chunks, steps = codec.spans_plan("encoder", spans, lanes, args.lanes + 1)
+    W = codec.span_warmup_frames("encoder")
+    lane_chunks = chunks[chunks["n_warmup"] > 0]
+    L = int(lane_chunks["n_frames"].max()) if lane_chunks.size else hops
+    d_pcm = torch.from_numpy(pcm).to(dev)
+    d_pk = torch.zeros((hops, codec.packet_size(args.bits)), dtype=torch.uint8, device=dev)
+    d_out = torch.zeros((hops, 320), dtype=torch.int16, device=dev)
+    times = {"encode": [], "decode": []}
+    for rep in range(args.reps + 1):   # rep 0 warms (allocations, code)
+        ctx.reset()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ctx.encode_spans_dev(spans, d_pcm, args.bits, d_pk, lanes)
+        ctx.synchronize()
+        t1 = time.perf_counter()
+        ctx.decode_spans_dev(spans, d_pk, args.bits, d_out, lanes)
+        ctx.synchronize()
+        t2 = time.perf_counter()
+        if rep:
+            times["encode"].append(t1 - t0)
+            times["decode"].append(t2 - t1)
+    pk, out = d_pk.cpu().numpy(), d_out.cpu().numpy()
+    # verified: a prefix against the hop-by-hop calls on a twin context (it crosses the first chunk boundaries)
+    twin = lyra_amd.LyraHip(device=0, max_streams=1, requant="xnnpack")
+    n = min(hops, args.verify_hops)
+    ok = True
+    for h in range(n):
+        p = twin.encode(pcm[h:h + 1], args.bits, [0])
+        o = twin.decode(p, args.bits, [0])
+        ok = ok and np.array_equal(p[0], pk[h]) and np.array_equal(o[0], out[h])
+    enc, dec = float(np.median(times["encode"])), float(np.median(times["decode"]))
+    return dict(kind="span_transcode", hops=hops, lanes=int(args.lanes), bits=args.bits, chunks=int(len(chunks)), steps=int(steps),
+                warmup=W, chunk_hops=L, inflation=round((L + W) / L, 4) if lane_chunks.size else 1.0,
+                encode_s=round(enc, 5), decode_s=round(dec, 5), encode_frames_per_s=round(hops / enc),
+                decode_frames_per_s=round(hops / dec), reps=args.reps, verified=bool(ok), verified_hops=n)
+
+
+def file_leg(args, pcm):
+    import lyra_amd
+    demo = os.path.join(ROOT, "lyra_amd", "file_demo")
+    bitrate = {64: 3200, 120: 6000, 184: 9200}[args.bits]
+    hops = min(pcm.shape[0], args.file_hops) if args.file_hops else pcm.shape[0]
+    rec = dict(kind="file_transcode", hops=hops, bits=args.bits, lanes=int(args.lanes))
+    with tempfile.TemporaryDirectory() as tmp:
+        wav = os.path.join(tmp, "recording.wav")
+        with wave.open(wav, "wb") as w:
+            w.setnchannels(1); w.setsampwidth(2); w.setframerate(16000)
+            w.writeframes(pcm[:hops].tobytes())
+        outs = {}
+        for name, flag in (("time_parallel", ["--time-parallel=%d" % args.lanes]), ("hop_by_hop", [])):
+            out_dir = os.path.join(tmp, name)
+            os.mkdir(out_dir)
+            t0 = time.perf_counter()
+            r = subprocess.run([demo, *flag, lyra_amd.default_model_dir(), str(bitrate), out_dir, wav],
+                               capture_output=True, text=True, timeout=args.file_timeout)
+            rec[name + "_s"] = round(time.perf_counter() - t0, 3)
+            if r.returncode != 0:
+                rec[name + "_error"] = r.stderr[-300:]
+            outs[name] = out_dir
+            print(json.dumps({name + "_s": rec[name + "_s"]}), flush=True)
+        same = True
+        for f in ("recording.lyra", "recording_decoded.wav"):
+            a, b = (os.path.join(outs[k], f) for k in ("time_parallel", "hop_by_hop"))
+            same = same and os.path.isfile(a) and os.path.isfile(b) and open(a, "rb").read() == open(b, "rb").read()
+        rec["verified"] = bool(same)
+    if rec.get("time_parallel_s") and rec.get("hop_by_hop_s"):
+        rec["hop_by_hop_over_time_parallel"] = round(rec["hop_by_hop_s"] / rec["time_parallel_s"], 2)
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--hops", type=int, default=180000)
+    ap.add_argument("--lanes", type=int, default=4096)
+    ap.add_argument("--bits", type=int, default=184)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--verify-hops", type=int, default=400)
+    ap.add_argument("--file-hops", type=int, default=0, help="hops of the file leg (0: all)")
+    ap.add_argument("--file-timeout", type=int, default=900)
+    ap.add_argument("--skip-file-leg", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "span_transcode.jsonl"))
+    args = ap.parse_args()
+    pcm = recording(args.hops)
+    recs = [device_leg(args, pcm)]
+    print(json.dumps(recs[0]), flush=True)
+    if not args.skip_file_leg:
+        recs.append(file_leg(args, pcm))
+        print(json.dumps(recs[1]), flush=True)
+    with open(args.out, "a") as f:
+        for r in recs:
+            f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()
