@@ -630,8 +630,25 @@ long lyra_hip_import_errors(lyra_hip_ctx* ctx, int clear);
  *   call's plan upload has run); each is ONE call of its side for rules (1) to (3) of "Streams" and runs on
  *   lyra_hip_stream() / lyra_hip_stream_decode() -- the packets too, the quantizer stream is not used.  The host-buffer forms
  *   stage frames 0 .. the last span's end, run, synchronise and write the spans' frames of the output.
- * Out of scope: DTX, packet loss / comfort noise (the NoiseEstimator is a true recurrence, not history), sample rates other
- * than 16 kHz, per-span bitrates.  LYRA_HIP_SUBBATCHES > 1 is accepted (the call is not split). */
+ *   Sample rates: the `_ext` forms take the PCM at sample_rate_hz = 8000 / 16000 / 32000 / 48000, rows of sample_rate_hz / 50
+ *   samples (160 / 320 / 640 / 960: every row a multiple of 16 bytes), ONE rate per call.  The resampler's state is its last 34
+ *   input samples and a decimation phase -- history again, and so short that it needs no lanes: one launch resamples every
+ *   frame of every span, in front of the steps (encode) or behind them (decode); frame 0 of a span continues from the span
+ *   stream's resampler slot and leaves in it what the hop-by-hop calls would.  Packets, external-rate PCM and stream state
+ *   are BIT FOR BIT those of lyra_hip_resample[_dev](ENCODER) + lyra_hip_encode[_dev] per hop (lyra_hip_encode_ext_dev
+ *   without DTX) and of lyra_hip_decode[_dev] + lyra_hip_resample[_dev](DECODER) per hop, whether the span continues a live
+ *   stream or hop-by-hop calls follow it.  Besides the three stage regions only the resampler slot of the span streams' side
+ *   changes; the lanes' resampler slots are not touched.
+ *   d_pcm16 [frames][320] is the caller's 16 kHz workspace (16-byte aligned; the `_dev` forms allocate nothing, the host forms
+ *   keep it next to their staging buffers): after encode it holds the resampled audio of the spans' frames, after decode the
+ *   16 kHz output, as in lyra_hip_decode_ext_dev; other rows are not touched.  At 16000 the call is the plain span call on the
+ *   external-rate buffer, d_pcm16 may be NULL and no resampler slot is read or written.  Any other rate, a null or misaligned
+ *   buffer or anything the planner refuses: LYRA_HIP_EINVAL with nothing enqueued.
+ *   Each `_ext` call is ONE call of its side as above and the resampler pass runs on the side's own stream inside it:
+ *   UNLIKE lyra_hip_decode_ext_dev, whose external-rate output completes on the noise stream, everything a
+ *   lyra_hip_decode_spans_ext_dev call writes completes on lyra_hip_stream_decode().
+ * Out of scope: DTX, packet loss / comfort noise (the NoiseEstimator is a true recurrence, not history), per-span sample
+ * rates, per-span bitrates.  LYRA_HIP_SUBBATCHES > 1 is accepted (the call is not split). */
 typedef struct lyra_hip_span { int32_t stream_id; int64_t first_frame; int64_t n_frames; } lyra_hip_span;
 /* warm-up hops of side LYRA_HIP_SIDE_ENCODER / LYRA_HIP_SIDE_DECODER (25 / 25); LYRA_HIP_EINVAL for any other side */
 int lyra_hip_span_warmup_frames(int side);
@@ -643,6 +660,16 @@ int lyra_hip_encode_spans(lyra_hip_ctx* ctx, const lyra_hip_span* spans, int n_s
                           const int16_t* pcm, int num_bits, uint8_t* packets);
 int lyra_hip_decode_spans(lyra_hip_ctx* ctx, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                           const uint8_t* packets, int num_bits, int16_t* pcm);
+int lyra_hip_encode_spans_ext_dev(lyra_hip_ctx* ctx, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                                  const int16_t* d_pcm_ext /* [frames][rate / 50] */, int sample_rate_hz,
+                                  int16_t* d_pcm16 /* [frames][320] workspace */, int num_bits, uint8_t* d_packets);
+int lyra_hip_decode_spans_ext_dev(lyra_hip_ctx* ctx, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                                  const uint8_t* d_packets, int num_bits, int sample_rate_hz,
+                                  int16_t* d_pcm16 /* [frames][320] */, int16_t* d_pcm_ext /* [frames][rate / 50] */);
+int lyra_hip_encode_spans_ext(lyra_hip_ctx* ctx, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                              const int16_t* pcm_ext, int sample_rate_hz, int num_bits, uint8_t* packets);
+int lyra_hip_decode_spans_ext(lyra_hip_ctx* ctx, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                              const uint8_t* packets, int num_bits, int sample_rate_hz, int16_t* pcm_ext);
 /* The planner of the four calls, a pure function (no context, no device).  Chunk r is row r of the call's batch: it runs on
  * stream_id for n_warmup + n_frames steps; step i reads buffer frame first_frame - n_warmup + i and from step n_warmup on
  * writes its output there.  Chunk 0 of a span runs on the span's own stream with no warm-up; the others on lanes, behind

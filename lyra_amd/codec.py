@@ -204,6 +204,11 @@ def _load(path=None):
         for suf in ("", "_dev"):
             getattr(L, f"lyra_hip_encode_spans{suf}").argtypes = [vp, vp, ci, vp, ci, vp, ci, vp]
             getattr(L, f"lyra_hip_decode_spans{suf}").argtypes = [vp, vp, ci, vp, ci, vp, ci, vp]
+    if hasattr(L, "lyra_hip_encode_spans_ext"):
+        L.lyra_hip_encode_spans_ext.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, vp]
+        L.lyra_hip_decode_spans_ext.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, vp]
+        L.lyra_hip_encode_spans_ext_dev.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, ci, vp]
+        L.lyra_hip_decode_spans_ext_dev.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, vp, vp]
     L.lyra_hip_set_cng_seed.argtypes = [vp, C.c_uint64]
     L.lyra_hip_set_encoder_sample_rate.argtypes = [vp, C.c_int]
     L.lyra_hip_stream.restype = vp
@@ -750,30 +755,47 @@ class LyraHip:
         return n
 
     # -- time-parallel spans (lyra_hip_encode_spans / lyra_hip_decode_spans) ----------------------------------------------
-    def encode_spans(self, spans, pcm, num_bits, lane_ids=()):
+    def encode_spans(self, spans, pcm, num_bits, lane_ids=(), sample_rate_hz=16000):
         """Long spans of a few streams, time-parallel and bit for bit the hop-by-hop result.  spans: (stream_id,
         first_frame, n_frames) triples into the frame-major pcm int16 [frames][320]; lane_ids: streams lent as scratch
-        (their encoder state is reset afterwards).  Returns packets uint8 [frames][bytes]; rows outside every span are 0."""
+        (their encoder state is reset afterwards).  Returns packets uint8 [frames][bytes]; rows outside every span are 0.
+        sample_rate_hz other than 16000 (lyra_hip_encode_spans_ext): pcm is [frames][sample_rate_hz / 50] and the result that
+        of resample(side="encoder") + encode per hop."""
         sp = _spans(spans)
         lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
-        pcm = _np(pcm, np.int16, (-1, HOP))
+        pcm = _np(pcm, np.int16, (-1, self._span_hop(sample_rate_hz)))
         out = np.zeros((pcm.shape[0], packet_size(num_bits)), np.uint8)
         self._check_span_frames(sp, pcm.shape[0])
-        self._chk(self.L.lyra_hip_encode_spans(self.h, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
-                                               pcm.ctypes.data, num_bits, out.ctypes.data))
+        if sample_rate_hz == 16000:
+            self._chk(self.L.lyra_hip_encode_spans(self.h, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
+                                                   pcm.ctypes.data, num_bits, out.ctypes.data))
+        else:
+            self._chk(self.L.lyra_hip_encode_spans_ext(self.h, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
+                                                       pcm.ctypes.data, sample_rate_hz, num_bits, out.ctypes.data))
         return out
 
-    def decode_spans(self, spans, packets, num_bits, lane_ids=()):
+    def decode_spans(self, spans, packets, num_bits, lane_ids=(), sample_rate_hz=16000):
         """The decoder twin of encode_spans: packets uint8 [frames][bytes] -> pcm int16 [frames][320] (rows outside every
-        span are 0); the lanes' decoder state is reset afterwards."""
+        span are 0); the lanes' decoder state is reset afterwards.  sample_rate_hz other than 16000
+        (lyra_hip_decode_spans_ext): pcm int16 [frames][sample_rate_hz / 50], that of decode + resample(side="decoder")."""
         sp = _spans(spans)
         lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
         packets = _np(packets, np.uint8, (-1, packet_size(num_bits)))
-        out = np.zeros((packets.shape[0], HOP), np.int16)
+        out = np.zeros((packets.shape[0], self._span_hop(sample_rate_hz)), np.int16)
         self._check_span_frames(sp, packets.shape[0])
-        self._chk(self.L.lyra_hip_decode_spans(self.h, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
-                                               packets.ctypes.data, num_bits, out.ctypes.data))
+        if sample_rate_hz == 16000:
+            self._chk(self.L.lyra_hip_decode_spans(self.h, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
+                                                   packets.ctypes.data, num_bits, out.ctypes.data))
+        else:
+            self._chk(self.L.lyra_hip_decode_spans_ext(self.h, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
+                                                       packets.ctypes.data, num_bits, sample_rate_hz, out.ctypes.data))
         return out
+
+    @staticmethod
+    def _span_hop(sample_rate_hz):
+        if sample_rate_hz not in (8000, 16000, 32000, 48000):
+            raise LyraHipError(f"spans: sample rate {sample_rate_hz} Hz (8000 / 16000 / 32000 / 48000)")
+        return sample_rate_hz // 50
 
     @staticmethod
     def _check_span_frames(sp, frames):
@@ -781,26 +803,42 @@ class LyraHip:
                         int(np.max(sp["first_frame"] + sp["n_frames"])) > frames):
             raise LyraHipError(f"spans: a span lies outside the {frames} frames of the buffer")
 
-    def encode_spans_dev(self, spans, d_pcm, num_bits, d_packets, lane_ids=()):
+    def encode_spans_dev(self, spans, d_pcm, num_bits, d_packets, lane_ids=(), sample_rate_hz=16000, d_pcm16=None):
         """encode_spans on device buffers (spans and lane_ids stay host lists): d_pcm int16 [frames][320], d_packets uint8
-        [frames][bytes].  Enqueues and does not synchronise."""
+        [frames][bytes].  Enqueues and does not synchronise.  sample_rate_hz other than 16000
+        (lyra_hip_encode_spans_ext_dev): d_pcm is [frames][sample_rate_hz / 50] and d_pcm16 int16 [frames][320] the caller's
+        workspace, which holds the resampled audio of the spans' frames afterwards."""
         sp = _spans(spans)
         lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
         F = d_pcm.shape[0]
         self._check_span_frames(sp, F)
-        self._dev_call(self.L.lyra_hip_encode_spans_dev, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
-                       self._dev_ptr(d_pcm, "int16", (F, HOP), "pcm"), num_bits,
+        if sample_rate_hz == 16000 and d_pcm16 is None:
+            self._dev_call(self.L.lyra_hip_encode_spans_dev, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
+                           self._dev_ptr(d_pcm, "int16", (F, HOP), "pcm"), num_bits,
+                           self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"))
+            return
+        self._dev_call(self.L.lyra_hip_encode_spans_ext_dev, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
+                       self._dev_ptr(d_pcm, "int16", (F, sample_rate_hz // 50), "pcm"), sample_rate_hz,
+                       self._dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm") if d_pcm16 is not None else None, num_bits,
                        self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"))
 
-    def decode_spans_dev(self, spans, d_packets, num_bits, d_pcm, lane_ids=()):
-        """decode_spans on device buffers.  Enqueues and does not synchronise."""
+    def decode_spans_dev(self, spans, d_packets, num_bits, d_pcm, lane_ids=(), sample_rate_hz=16000, d_pcm16=None):
+        """decode_spans on device buffers.  Enqueues and does not synchronise.  sample_rate_hz other than 16000
+        (lyra_hip_decode_spans_ext_dev): d_pcm is [frames][sample_rate_hz / 50] and d_pcm16 int16 [frames][320] receives the
+        16 kHz output; all of it completes on the decode stream."""
         sp = _spans(spans)
         lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
         F = d_pcm.shape[0]
         self._check_span_frames(sp, F)
-        self._dev_call(self.L.lyra_hip_decode_spans_dev, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
-                       self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"), num_bits,
-                       self._dev_ptr(d_pcm, "int16", (F, HOP), "pcm"))
+        if sample_rate_hz == 16000 and d_pcm16 is None:
+            self._dev_call(self.L.lyra_hip_decode_spans_dev, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
+                           self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"), num_bits,
+                           self._dev_ptr(d_pcm, "int16", (F, HOP), "pcm"))
+            return
+        self._dev_call(self.L.lyra_hip_decode_spans_ext_dev, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
+                       self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"), num_bits, sample_rate_hz,
+                       self._dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm") if d_pcm16 is not None else None,
+                       self._dev_ptr(d_pcm, "int16", (F, sample_rate_hz // 50), "pcm"))
 
     def noise_receive_dev(self, d_ids, d_pcm, d_is_noise, side="decoder"):
         """NoiseEstimator::ReceiveSamples on device buffers: pcm int16 [B][320] -> is_noise int32 [B]."""

@@ -249,5 +249,15 @@ __global__ void span_scatter_kernel(const SpanRow* rows, int B, int step, const 
 __global__ void span_lane_init_kernel(const ResetP* P, const SpanRow* rows, int n, int r0, StateMap sm);
 // rows with handover != 0: regions r0 .. r0 + 2 of the lane -> the same regions of target
 __global__ void span_handover_kernel(const SpanRow* rows, int n, int r0, StateMap sm);
+// One span with frames of a call at 8 / 32 / 48 kHz: frames frame0 .. frame0 + n_frames - 1 of both PCM buffers belong to stream
+// `id`; wg0 = the span's first workgroup of span_resample_kernel (four frames each; rows in rising wg0).  Uploaded behind the
+// call's SpanRows, hence their size.
+struct SpanRsRow { long long frame0, n_frames; int32_t id, wg0, pad[2]; };
+static_assert(sizeof(SpanRsRow) == sizeof(SpanRow), "one upload holds both kinds of row");
+// in [frames][n_in] -> out [frames][n_out] for the frames of the rows' spans, with the design P (n_out = n_in * up / down);
+// state = the resampler region of the side (R_RS_E / R_RS_D): read and written by each span's frame 0 only (the phase word is
+// read by all).  grid = the workgroups of all rows, 256 threads, LDS resample_lds_bytes(n_in).
+__global__ void span_resample_kernel(ResampleP P, const SpanRsRow* rows, int n_rows, uint8_t* state, const int16_t* in, int n_in,
+                                     int16_t* out, int n_out);
 
 }  // namespace lyra

@@ -782,6 +782,7 @@ __global__ __launch_bounds__(256) void resample_kernel(ResampleP P, const int32_
   if (!on) return;
   int16_t* dst = out + (size_t)b * out_stride;
 #include "resample_fir.inc"
+#include "resample_slot.inc"
 }
 
 // Per-stream sample rates (lyra_hip_encode_rates_dev / lyra_hip_decode_lossy_rates_dev): row b is resampled between
@@ -836,6 +837,7 @@ __global__ __launch_bounds__(256) void resample_rates_kernel(const ResampleP* __
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #include "resample_fir.inc"
+#include "resample_slot.inc"
 }
 
 // =============================================================================================

@@ -1,6 +1,7 @@
-// resample_fir.inc -- the polyphase FIR of one stream's pass and the write-back of its slot, textually shared by
-// resample_kernel and resample_rates_kernel (misc_kernels.hip).  Expects in scope: P (ResampleP), rsb (the wavefront's LDS
-// row [H history | n_in new samples]), n_in, n_out, in_pos, dst, hist, slot, lane, H.
+// resample_fir.inc -- the polyphase FIR of one wavefront's pass, textually shared by resample_kernel, resample_rates_kernel
+// (misc_kernels.hip: one stream's call) and span_resample_kernel (spans_kernels.hip: one frame of a span).  The stream-per-
+// wavefront kernels follow it with resample_slot.inc, the write-back of the slot.  Expects in scope: P (ResampleP), rsb (the
+// wavefront's LDS row [H history | n_in new samples]), n_in, n_out, in_pos, dst, lane.
   auto clip = [](float acc) { return (int16_t)(acc < -32768.f ? -32768.f : (acc > 32767.f ? 32767.f : acc)); };   // ClipToInt16 (dsp_utils.h:56-72)
   if (P.down == 1) {
     // interpolation: output k * up + ph is phase ph of the window at input k -- a lane takes input positions
@@ -30,8 +31,3 @@
       dst[o] = clip(acc);
     }
   }
-  // (same wavefront wrote and read this row: no barrier needed before the history leaves it)
-  if (lane < H) hist[lane] = rsb[n_in + lane];
-  // only the decimation phase is ever used: kept modulo 6 = lcm of the possible `down` factors (1, 2, 3), so the
-  // counter never wraps out of phase however long the stream runs (the oracle keeps an unbounded counter)
-  if (lane == 0) *reinterpret_cast<int*>(slot + st::RS_IN_POS) = (in_pos + n_in) % 6;

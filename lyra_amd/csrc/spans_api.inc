@@ -1,11 +1,15 @@
-// spans_api.inc -- part of api.hip: lyra_hip_encode_spans[_dev] / lyra_hip_decode_spans[_dev], one long recording (or a few)
-// through the batched stage kernels time-parallel (spans_plan.h: the warm-up bound and the planner; spans_kernels.hip: the row
+// spans_api.inc -- part of api.hip: lyra_hip_encode_spans[_ext][_dev] / lyra_hip_decode_spans[_ext][_dev], one long recording (or a
+// few) through the batched stage kernels time-parallel (spans_plan.h: the warm-up bound and the planner; spans_kernels.hip: the row
 // movement and the hand-over).  A call is ONE call of its side for the ordering rules of include/lyra_hip.h "Streams": the
 // whole of it runs on the side's first stream (se[0] with the quantizer behind the extractor, as the host form of
 // lyra_hip_encode runs it; sd[0]) between enc_side_begin / _done or dec_side_begin / _done, and works on scratch of its own --
 // the feature buffers of the `_dev` encode calls may still be read by a quantizer on sq[0].
 // Per call: the plan (host), one upload of the rows, lane preparation, T steps of {gather, stages, [quantizer, scatter]},
 // hand-over, lane reset.  Nothing is read back and no step waits for the host.
+// The `_ext` calls at 8 / 32 / 48 kHz add ONE launch of span_resample_kernel on the same stream inside the same bracket: over all
+// frames of the spans in front of the steps (encode: external rate -> the caller's [frames][320] workspace, which the steps
+// then read) or behind them (decode: the steps write the workspace).  The resampler needs no lanes: its state is the 34 input
+// samples in front of a frame, and those are in the buffer.
 #include "spans_plan.h"
 
 static_assert(sizeof(lyra_hip_span) == sizeof(sp::Span) && sizeof(lyra_hip_span_chunk) == sizeof(sp::Chunk) &&
@@ -18,7 +22,8 @@ namespace {
 
 struct SpanSide {
   SpanRow* h_rows = nullptr;        // pinned: the upload of the call in flight
-  SpanRow* d_rows = nullptr;        // [rows_cap]: the batch rows, then one row per lane for the final reset
+  SpanRow* d_rows = nullptr;        // [rows_cap]: the batch rows, then one row per lane for the final reset, then (`_ext`
+                                    // calls) one SpanRsRow per span with frames
   int rows_cap = 0;
   hipEvent_t ev_up = nullptr;       // end of that upload: h_rows may be rewritten
   bool up_pending = false;
@@ -49,7 +54,7 @@ void spans_free(lyra_hip_ctx* c) {
   c->span_calls = nullptr;
 }
 
-// buffers of one side for `rows` batch rows + `n_lanes` reset rows; growing drains the side's stream first
+// buffers of one side for `rows` batch rows + `n_lanes` reset and resampler rows; growing drains the side's stream first
 int span_side_ensure(lyra_hip_ctx* c, SpanSide& S, hipStream_t st_, int rows, int n_lanes) {
   if (!S.ev_up) HIPCHK(c, hipEventCreateWithFlags(&S.ev_up, hipEventDisableTiming));
   if (S.up_pending) {   // the previous call's upload has to have left the pinned rows
@@ -121,22 +126,81 @@ int span_batch_at(const SpanPlan& P, const SpanRow* rows, int step, int* own_run
 
 inline int span_grid(int B, int units) { return (int)(((long long)B * units + 255) / 256); }
 
-// The enqueue of one call.  enc: d_src PCM [frames][320], d_dst packets [frames][nbytes]; else the reverse.
-int spans_enqueue(lyra_hip_ctx* c, bool enc, const SpanPlan& P, const lyra_hip_span* spans, const int32_t* lane_ids,
-                  int n_lanes, const void* d_src, int num_bits, void* d_dst) {
+// The external-rate side of an `_ext` call: rate 16000 = none, the call is the plain one.
+struct SpanExt {
+  int rate = 16000;
+  int16_t* d_pcm16 = nullptr;   // [frames][320], the caller's: resampled input (encode) / the steps' output (decode)
+  int n_ext() const { return rate / 50; }
+  bool on() const { return rate != 16000; }
+};
+
+// rows of span_resample_kernel: the spans with frames, four frames per workgroup.  Returns the workgroups, -1: too many.
+long long span_rs_rows(const lyra_hip_span* spans, int n_spans, SpanRsRow* rows, int* n_rows) {
+  long long wg = 0;
+  int n = 0;
+  for (int s = 0; s < n_spans; ++s) {
+    if (!spans[s].n_frames) continue;
+    if (rows) rows[n] = SpanRsRow{spans[s].first_frame, spans[s].n_frames, spans[s].stream_id, (int32_t)wg, {0, 0}};
+    ++n;
+    wg += (spans[s].n_frames + 3) / 4;
+    if (wg > INT32_MAX) return -1;
+  }
+  *n_rows = n;
+  return wg;
+}
+
+// one launch over every frame of every span: in [frames][n_in] -> out [frames][n_in * to / from] on st_ (slots: see
+// launch_resample -- behind run_steps' launches ahead on the quantizer stream / on the noise stream)
+int launch_span_resample(lyra_hip_ctx* c, bool enc, hipStream_t st_, const SpanRsRow* d_rows, int n_rows, long long wgs, int from,
+                         int to, const int16_t* d_in, int16_t* d_out) {
+  ResampleP P;
+  if (!resample_design(from, to, &P)) return fail(c, LYRA_HIP_EINVAL, "spans: unsupported resampling %d -> %d Hz", from, to);
+  int rc = 0;
+  if (enc) {
+    if ((rc = wait_ahead(c))) return rc;
+  } else if (c->rs_sn_pending) {
+    if ((rc = wait_noise_stream(c))) return rc;
+    c->rs_sn_pending = false;
+  }
+  const int n_in = from / 50, n_out = to / 50;
+  hipLaunchKernelGGL(span_resample_kernel, dim3((unsigned)wgs), dim3(256), resample_lds_bytes(n_in), st_, P, d_rows, n_rows,
+                     c->sm.base[enc ? st::R_RS_E : st::R_RS_D], d_in, n_in, d_out, n_out);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+// The enqueue of one call.  enc: d_src PCM [frames][320], d_dst packets [frames][nbytes]; else the reverse.  X.on(): the PCM
+// of d_src / d_dst is [frames][X.n_ext()] and the steps work on X.d_pcm16.
+int spans_enqueue(lyra_hip_ctx* c, bool enc, const SpanPlan& P, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids,
+                  int n_lanes, const void* d_src, int num_bits, void* d_dst, const SpanExt& X) {
   if (!c->span_calls) c->span_calls = new SpanCalls();
   SpanSide& S = span_calls_of(c)->side[enc ? 0 : 1];
   hipStream_t st_ = enc ? c->se[0] : c->sd[0];
   const int rows = (int)P.chunks.size(), nbytes = (num_bits + 7) / 8, r0 = enc ? st::R_E0 : st::R_D0;
-  int rc = span_side_ensure(c, S, st_, std::max(rows, 1), n_lanes);
+  int n_rs = 0;
+  const long long rs_wgs = X.on() ? span_rs_rows(spans, n_spans, nullptr, &n_rs) : 0;
+  if (rs_wgs < 0) return fail(c, LYRA_HIP_EINVAL, "spans: too many frames for one resampler pass");
+  int rc = span_side_ensure(c, S, st_, std::max(rows, 1), n_lanes + n_rs);
   if (rc) return rc;
   if (rows && (rc = ensure_scratch(c, rows))) return rc;   // the stage kernels' own boundary buffers
   span_fill_rows(P, spans, lane_ids, n_lanes, S.h_rows);
+  const int rs0 = rows + n_lanes;   // the resampler's rows lie behind the lanes' reset rows
+  if (n_rs) span_rs_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(S.h_rows + rs0), &n_rs);
   if ((rc = enc ? enc_side_begin(c, 0) : dec_side_begin(c, 0))) return rc;
-  if (rows + n_lanes) {
-    HIPCHK(c, hipMemcpyAsync(S.d_rows, S.h_rows, (size_t)(rows + n_lanes) * sizeof(SpanRow), hipMemcpyHostToDevice, st_));
+  if (rs0 + n_rs) {
+    HIPCHK(c, hipMemcpyAsync(S.d_rows, S.h_rows, (size_t)(rs0 + n_rs) * sizeof(SpanRow), hipMemcpyHostToDevice, st_));
     HIPCHK(c, hipEventRecord(S.ev_up, st_));
     S.up_pending = true;
+  }
+  const SpanRsRow* d_rs_rows = reinterpret_cast<const SpanRsRow*>(S.d_rows + rs0);
+  void* d_ext_out = nullptr;
+  if (X.on() && enc) {   // the steps read the 16 kHz workspace ...
+    if (n_rs && (rc = launch_span_resample(c, true, st_, d_rs_rows, n_rs, rs_wgs, X.rate, 16000, (const int16_t*)d_src, X.d_pcm16)))
+      return rc;
+    d_src = X.d_pcm16;
+  } else if (X.on()) {   // ... or write it
+    d_ext_out = d_dst;
+    d_dst = X.d_pcm16;
   }
   const int n_lane_rows = rows - P.n_own;
   if (n_lane_rows) {
@@ -178,6 +242,8 @@ int spans_enqueue(lyra_hip_ctx* c, bool enc, const SpanPlan& P, const lyra_hip_s
                        c->sm);
     HIPCHK(c, hipGetLastError());
   }
+  if (!rc && d_ext_out && n_rs)
+    rc = launch_span_resample(c, false, st_, d_rs_rows, n_rs, rs_wgs, 16000, X.rate, X.d_pcm16, (int16_t*)d_ext_out);
   if (enc) {
     if (!rc) rc = enc_side_done(c, 0);
   } else {
@@ -187,37 +253,49 @@ int spans_enqueue(lyra_hip_ctx* c, bool enc, const SpanPlan& P, const lyra_hip_s
   return rc;
 }
 
+bool span_rate_ok(int rate) { return rate == 8000 || rate == 16000 || rate == 32000 || rate == 48000; }
+
 int spans_call_dev(lyra_hip_ctx* c, bool enc, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
-                   const void* d_src, int num_bits, void* d_dst, SpanPlan* P) {
+                   const void* d_src, int num_bits, void* d_dst, SpanPlan* P, const SpanExt& X = SpanExt()) {
   const char* what = enc ? "encode_spans" : "decode_spans";
   if (!c) return LYRA_HIP_EINVAL;
   int rc = check_bits(c, num_bits);
   if (rc) return rc;
+  if (!span_rate_ok(X.rate)) return fail(c, LYRA_HIP_EINVAL, "%s: sample rate %d Hz (8000 / 16000 / 32000 / 48000)", what, X.rate);
   if (n_lanes < 0 || (n_lanes && !lane_ids)) return fail(c, LYRA_HIP_EINVAL, "%s: bad lane list", what);
   if ((rc = span_plan_checked(c, enc ? sp::SIDE_ENC : sp::SIDE_DEC, spans, n_spans, lane_ids, n_lanes, P, what))) return rc;
   if (P->end_frame && (!d_src || !d_dst)) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
   const void* pcm = enc ? d_src : d_dst;
   if (reinterpret_cast<uintptr_t>(pcm) & 15) return fail(c, LYRA_HIP_EINVAL, "%s: the PCM buffer must be 16-byte aligned", what);
+  if (X.on() && ((P->end_frame && !X.d_pcm16) || (reinterpret_cast<uintptr_t>(X.d_pcm16) & 15)))
+    return fail(c, LYRA_HIP_EINVAL, "%s: at %d Hz the 16 kHz buffer must be given, 16-byte aligned", what, X.rate);
   DEVSCOPE(c);
-  return spans_enqueue(c, enc, *P, spans, lane_ids, n_lanes, d_src, num_bits, d_dst);
+  return spans_enqueue(c, enc, *P, spans, n_spans, lane_ids, n_lanes, d_src, num_bits, d_dst, X);
 }
 
-// host-buffer form: frames 0 .. end_frame - 1 of both buffers are staged (copy, run, synchronise)
+// host-buffer form: frames 0 .. end_frame - 1 of both buffers are staged (copy, run, synchronise); PCM rows of rate / 50 samples,
+// and at a rate other than 16000 the 16 kHz workspace lives next to the staging buffers
 int spans_call_host(lyra_hip_ctx* c, bool enc, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
-                    const void* src, int num_bits, void* dst) {
+                    const void* src, int num_bits, void* dst, int rate = 16000) {
   if (!c) return LYRA_HIP_EINVAL;
   int rc = check_bits(c, num_bits);
   if (rc) return rc;
+  if (!span_rate_ok(rate))
+    return fail(c, LYRA_HIP_EINVAL, "%s: sample rate %d Hz (8000 / 16000 / 32000 / 48000)", enc ? "encode_spans" : "decode_spans", rate);
   int64_t end = 0;
   for (int s = 0; spans && s < n_spans; ++s)
     if (spans[s].first_frame >= 0 && spans[s].n_frames >= 0) end = std::max<int64_t>(end, spans[s].first_frame + spans[s].n_frames);
   if (end && (!src || !dst)) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", enc ? "encode_spans" : "decode_spans");
   DEVSCOPE(c);
-  const size_t nbytes = (size_t)(num_bits + 7) / 8, in_b = (size_t)end * (enc ? 640 : nbytes), out_b = (size_t)end * (enc ? nbytes : 640);
+  const size_t nbytes = (size_t)(num_bits + 7) / 8, pcm_b = (size_t)rate / 50 * 2;
+  const size_t in_b = (size_t)end * (enc ? pcm_b : nbytes), out_b = (size_t)end * (enc ? nbytes : pcm_b);
   uint8_t *d_in = nullptr, *d_out = nullptr;
+  SpanExt X;
+  X.rate = rate;
   if (end) {
-    if (dalloc(&d_in, in_b) != hipSuccess || dalloc(&d_out, out_b) != hipSuccess) {
-      dfree(d_in, d_out);
+    if (dalloc(&d_in, in_b) != hipSuccess || dalloc(&d_out, out_b) != hipSuccess ||
+        (X.on() && dalloc(&X.d_pcm16, (size_t)end * 320) != hipSuccess)) {
+      dfree(d_in, d_out, X.d_pcm16);
       return fail(c, LYRA_HIP_ENOMEM, "spans: staging %zu + %zu bytes failed", in_b, out_b);
     }
   }
@@ -225,15 +303,15 @@ int spans_call_host(lyra_hip_ctx* c, bool enc, const lyra_hip_span* spans, int n
   SpanPlan P;
   rc = 0;
   if (end && hipMemcpy(d_in, src, in_b, hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, LYRA_HIP_EHIP, "spans: upload failed");
-  if (!rc) rc = spans_call_dev(c, enc, spans, n_spans, lane_ids, n_lanes, d_in, num_bits, d_out, &P);
+  if (!rc) rc = spans_call_dev(c, enc, spans, n_spans, lane_ids, n_lanes, d_in, num_bits, d_out, &P, X);
   if (!rc && hipStreamSynchronize(st_) != hipSuccess) rc = fail(c, LYRA_HIP_EHIP, "spans: synchronise failed");
-  const size_t ob = enc ? nbytes : 640;   // only the spans' own frames of the caller's output are written
+  const size_t ob = enc ? nbytes : pcm_b;   // only the spans' own frames of the caller's output are written
   for (int s = 0; !rc && s < n_spans; ++s)
     if (spans[s].n_frames && hipMemcpy((uint8_t*)dst + spans[s].first_frame * ob, d_out + spans[s].first_frame * ob,
                                        spans[s].n_frames * ob, hipMemcpyDeviceToHost) != hipSuccess)
       rc = fail(c, LYRA_HIP_EHIP, "spans: download failed");
   if (rc) (void)hipStreamSynchronize(st_);
-  dfree(d_in, d_out);
+  dfree(d_in, d_out, X.d_pcm16);
   return rc;
 }
 
@@ -272,6 +350,36 @@ int lyra_hip_encode_spans(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spa
 int lyra_hip_decode_spans(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                           const uint8_t* packets, int num_bits, int16_t* pcm) {
   return spans_call_host(c, false, spans, n_spans, lane_ids, n_lanes, packets, num_bits, pcm);
+}
+
+int lyra_hip_encode_spans_ext_dev(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                                  const int16_t* d_pcm_ext, int sample_rate_hz, int16_t* d_pcm16, int num_bits,
+                                  uint8_t* d_packets) {
+  SpanPlan P;
+  SpanExt X;
+  X.rate = sample_rate_hz;
+  X.d_pcm16 = d_pcm16;
+  return spans_call_dev(c, true, spans, n_spans, lane_ids, n_lanes, d_pcm_ext, num_bits, d_packets, &P, X);
+}
+
+int lyra_hip_decode_spans_ext_dev(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                                  const uint8_t* d_packets, int num_bits, int sample_rate_hz, int16_t* d_pcm16,
+                                  int16_t* d_pcm_ext) {
+  SpanPlan P;
+  SpanExt X;
+  X.rate = sample_rate_hz;
+  X.d_pcm16 = d_pcm16;
+  return spans_call_dev(c, false, spans, n_spans, lane_ids, n_lanes, d_packets, num_bits, d_pcm_ext, &P, X);
+}
+
+int lyra_hip_encode_spans_ext(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                              const int16_t* pcm_ext, int sample_rate_hz, int num_bits, uint8_t* packets) {
+  return spans_call_host(c, true, spans, n_spans, lane_ids, n_lanes, pcm_ext, num_bits, packets, sample_rate_hz);
+}
+
+int lyra_hip_decode_spans_ext(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                              const uint8_t* packets, int num_bits, int sample_rate_hz, int16_t* pcm_ext) {
+  return spans_call_host(c, false, spans, n_spans, lane_ids, n_lanes, packets, num_bits, pcm_ext, sample_rate_hz);
 }
 
 }  // extern "C"

@@ -12,10 +12,13 @@
 #include "lyra_batch_codec.h"
 
 // The span calls are bound weakly: this file also links against builds of the C ABI that predate them (an older
-// liblyra_hip.so, the CPU stand-in of the host-logic tests), where the time-parallel functions report that and fail.
+// liblyra_hip.so, the CPU stand-in of the host-logic tests), where the time-parallel functions report that and fail --
+// the `_ext` pair on its own, so that a library with the plain span calls alone still serves 16 kHz.
 #pragma weak lyra_hip_encode_spans
 #pragma weak lyra_hip_decode_spans
 #pragma weak lyra_hip_span_warmup_frames
+#pragma weak lyra_hip_encode_spans_ext
+#pragma weak lyra_hip_decode_spans_ext
 
 namespace chromemedia {
 namespace codec {
@@ -31,8 +34,8 @@ bool CheckScope(int num_channels, int sample_rate_hz, bool enable_preprocessing,
     LOG(ERROR) << "Number of channels " << num_channels << " is not supported by codec. It needs to be 1.";
     return false;
   }
-  if (sample_rate_hz != kBatchInternalSampleRateHz) {
-    LOG(ERROR) << "Sample rate " << sample_rate_hz << " Hz needs the resampler, which this build does not provide.";
+  if (sample_rate_hz != 8000 && sample_rate_hz != 16000 && sample_rate_hz != 32000 && sample_rate_hz != 48000) {
+    LOG(ERROR) << "Sample rate " << sample_rate_hz << " Hz is not supported by codec. It needs to be 8000, 16000, 32000 or 48000.";
     return false;
   }
   if (enable_preprocessing || enable_dtx) {
@@ -113,23 +116,34 @@ bool EncodeWavs(const std::vector<std::vector<int16_t>>& wav_data, int num_chann
     return false;
   }
   const int packet_size = BatchBitrateToPacketSize(bitrate);
+  const size_t hop_samples = (size_t)sample_rate_hz / 50;   // a 20 ms hop at the files' rate
+  const bool resample = sample_rate_hz != kBatchInternalSampleRateHz;
   size_t max_hops = 0;
-  for (const auto& w : wav_data) max_hops = std::max(max_hops, w.size() / kBatchHopSamples);
+  for (const auto& w : wav_data) max_hops = std::max(max_hops, w.size() / hop_samples);
   std::vector<int32_t> ids;
-  std::vector<int16_t> pcm;
+  std::vector<int16_t> pcm, pcm16;
   std::vector<uint8_t> packets;
   for (size_t hop = 0; hop < max_hops; ++hop) {  // streams with a full hop left (encoder_main_lib.cc:71-73)
     ids.clear();
     pcm.clear();
     for (int i = 0; i < n; ++i)
-      if ((hop + 1) * kBatchHopSamples <= wav_data[i].size()) {
+      if ((hop + 1) * hop_samples <= wav_data[i].size()) {
         ids.push_back(i);
-        pcm.insert(pcm.end(), wav_data[i].begin() + hop * kBatchHopSamples,
-                   wav_data[i].begin() + (hop + 1) * kBatchHopSamples);
+        pcm.insert(pcm.end(), wav_data[i].begin() + hop * hop_samples, wav_data[i].begin() + (hop + 1) * hop_samples);
       }
     packets.resize(ids.size() * packet_size);
-    if (lyra_hip_encode(ctx.c, ids.data(), (int)ids.size(), pcm.data(), num_bits, packets.data()) != 0) {
-      LOG(ERROR) << "Unable to encode features starting at samples at byte " << hop * kBatchHopSamples << ": "
+    const int16_t* hop16 = pcm.data();
+    if (resample) {   // the stream's own encoder-side resampler (lyra_encoder.cc:119-122)
+      pcm16.resize(ids.size() * kBatchHopSamples);
+      if (lyra_hip_resample(ctx.c, LYRA_HIP_SIDE_ENCODER, ids.data(), (int)ids.size(), pcm.data(), (int)hop_samples, sample_rate_hz,
+                            kBatchInternalSampleRateHz, pcm16.data()) != 0) {
+        LOG(ERROR) << "Unable to resample the hop at sample " << hop * hop_samples << ": " << lyra_hip_last_error(ctx.c);
+        return false;
+      }
+      hop16 = pcm16.data();
+    }
+    if (lyra_hip_encode(ctx.c, ids.data(), (int)ids.size(), hop16, num_bits, packets.data()) != 0) {
+      LOG(ERROR) << "Unable to encode features starting at samples at byte " << hop * hop_samples << ": "
                  << lyra_hip_last_error(ctx.c);
       return false;
     }
@@ -205,6 +219,13 @@ bool EncodeFilesImpl(const std::vector<ghc::filesystem::path>& wav_paths,
 bool DecodeFeaturesBatch(const std::vector<std::vector<uint8_t>>& packet_streams, int packet_size,
                          const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
                          int device) {
+  return DecodeFeaturesBatch(packet_streams, packet_size, kBatchInternalSampleRateHz, model_path, decoded_audio, device);
+}
+
+bool DecodeFeaturesBatch(const std::vector<std::vector<uint8_t>>& packet_streams, int packet_size, int sample_rate_hz,
+                         const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
+                         int device) {
+  if (!CheckScope(1, sample_rate_hz, false, false)) return false;
   int num_bits = -1;
   for (int br : {3200, 6000, 9200})
     if (BatchBitrateToPacketSize(br) == packet_size) num_bits = BatchBitrateToNumQuantizedBits(br);
@@ -222,9 +243,11 @@ bool DecodeFeaturesBatch(const std::vector<std::vector<uint8_t>>& packet_streams
     LOG(ERROR) << "Could not create lyra decoder: " << lyra_hip_last_error(nullptr);
     return false;
   }
+  const size_t hop_samples = (size_t)sample_rate_hz / 50;
+  const bool resample = sample_rate_hz != kBatchInternalSampleRateHz;
   std::vector<int32_t> ids;
   std::vector<uint8_t> packets;
-  std::vector<int16_t> pcm;
+  std::vector<int16_t> pcm, pcm_ext;
   for (size_t f = 0; f < max_packets; ++f) {
     ids.clear();
     packets.clear();
@@ -239,9 +262,18 @@ bool DecodeFeaturesBatch(const std::vector<std::vector<uint8_t>>& packet_streams
       LOG(ERROR) << "Could not decode samples: " << lyra_hip_last_error(ctx.c);
       return false;
     }
+    if (resample) {   // the stream's own decoder-side resampler (lyra_decoder.cc:107-113)
+      pcm_ext.resize(ids.size() * hop_samples);
+      if (lyra_hip_resample(ctx.c, LYRA_HIP_SIDE_DECODER, ids.data(), (int)ids.size(), pcm.data(), kBatchHopSamples,
+                            kBatchInternalSampleRateHz, sample_rate_hz, pcm_ext.data()) != 0) {
+        LOG(ERROR) << "Could not resample the decoded samples: " << lyra_hip_last_error(ctx.c);
+        return false;
+      }
+    }
+    const std::vector<int16_t>& hop = resample ? pcm_ext : pcm;
     for (size_t k = 0; k < ids.size(); ++k) {
       auto& dst = (*decoded_audio)[ids[k]];
-      dst.insert(dst.end(), pcm.begin() + k * kBatchHopSamples, pcm.begin() + (k + 1) * kBatchHopSamples);
+      dst.insert(dst.end(), hop.begin() + k * hop_samples, hop.begin() + (k + 1) * hop_samples);
     }
   }
   return true;
@@ -270,10 +302,16 @@ SpanJob MakeSpanJob(const std::vector<std::vector<T>>& streams, size_t row_size,
   for (int l = 0; l < n_lanes; ++l) job.lanes.push_back((int32_t)streams.size() + l);
   return job;
 }
-bool HaveSpanCalls() {
-  if (lyra_hip_encode_spans && lyra_hip_decode_spans && lyra_hip_span_warmup_frames) return true;
-  LOG(ERROR) << "This build of the lyra_hip library has no time-parallel span calls.";
-  return false;
+bool HaveSpanCalls(int sample_rate_hz) {
+  if (!(lyra_hip_encode_spans && lyra_hip_decode_spans && lyra_hip_span_warmup_frames)) {
+    LOG(ERROR) << "This build of the lyra_hip library has no time-parallel span calls.";
+    return false;
+  }
+  if (sample_rate_hz != kBatchInternalSampleRateHz && !(lyra_hip_encode_spans_ext && lyra_hip_decode_spans_ext)) {
+    LOG(ERROR) << "This build of the lyra_hip library has no time-parallel span calls at " << sample_rate_hz << " Hz.";
+    return false;
+  }
+  return true;
 }
 
 }  // namespace
@@ -282,14 +320,14 @@ bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, i
                             int bitrate, bool enable_preprocessing, bool enable_dtx,
                             const ghc::filesystem::path& model_path, std::vector<std::vector<uint8_t>>* encoded_features,
                             int num_lanes, int device) {
-  if (!CheckScope(num_channels, sample_rate_hz, enable_preprocessing, enable_dtx) || !HaveSpanCalls()) return false;
+  if (!CheckScope(num_channels, sample_rate_hz, enable_preprocessing, enable_dtx) || !HaveSpanCalls(sample_rate_hz)) return false;
   const int num_bits = BatchBitrateToNumQuantizedBits(bitrate);
   if (num_bits < 0) { LOG(ERROR) << "Bitrate " << bitrate << " bps is not supported by codec."; return false; }
   const int n = (int)wav_data.size();
   encoded_features->assign(n, {});
   if (n == 0) return true;
   std::vector<int16_t> pcm;
-  const SpanJob job = MakeSpanJob(wav_data, kBatchHopSamples, LYRA_HIP_SIDE_ENCODER, num_lanes, &pcm);
+  const SpanJob job = MakeSpanJob(wav_data, (size_t)sample_rate_hz / 50, LYRA_HIP_SIDE_ENCODER, num_lanes, &pcm);
   Ctx ctx;
   if (lyra_hip_create(model_path.string().c_str(), device, n + (int)job.lanes.size(), LYRA_HIP_REQUANT_DEFAULT, &ctx.c) != 0) {
     LOG(ERROR) << "Could not create lyra encoder: " << lyra_hip_last_error(nullptr);
@@ -297,8 +335,12 @@ bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, i
   }
   const size_t packet_size = (size_t)BatchBitrateToPacketSize(bitrate);
   std::vector<uint8_t> packets((size_t)job.frames * packet_size);
-  if (lyra_hip_encode_spans(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), pcm.data(), num_bits,
-                            packets.data()) != 0) {
+  // (16 kHz stays on the plain call: it also runs against a library that has no `_ext` calls yet)
+  if ((sample_rate_hz == kBatchInternalSampleRateHz
+           ? lyra_hip_encode_spans(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), pcm.data(), num_bits,
+                                   packets.data())
+           : lyra_hip_encode_spans_ext(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), pcm.data(),
+                                       sample_rate_hz, num_bits, packets.data())) != 0) {
     LOG(ERROR) << "Unable to encode features: " << lyra_hip_last_error(ctx.c);
     return false;
   }
@@ -311,11 +353,19 @@ bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, i
 bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams, int packet_size,
                                 const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
                                 int num_lanes, int device) {
+  return DecodeFeaturesTimeParallel(packet_streams, packet_size, kBatchInternalSampleRateHz, model_path, decoded_audio, num_lanes,
+                                    device);
+}
+
+bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams, int packet_size, int sample_rate_hz,
+                                const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
+                                int num_lanes, int device) {
+  if (!CheckScope(1, sample_rate_hz, false, false)) return false;
   int num_bits = -1;
   for (int br : {3200, 6000, 9200})
     if (BatchBitrateToPacketSize(br) == packet_size) num_bits = BatchBitrateToNumQuantizedBits(br);
   if (num_bits < 0) { LOG(ERROR) << "The packet size (" << packet_size << " bytes) is not supported."; return false; }
-  if (!HaveSpanCalls()) return false;
+  if (!HaveSpanCalls(sample_rate_hz)) return false;
   const int n = (int)packet_streams.size();
   decoded_audio->assign(n, {});
   if (n == 0) return true;
@@ -328,15 +378,19 @@ bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_
     LOG(ERROR) << "Could not create lyra decoder: " << lyra_hip_last_error(nullptr);
     return false;
   }
-  std::vector<int16_t> pcm((size_t)job.frames * kBatchHopSamples);
-  if (lyra_hip_decode_spans(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), packets.data(), num_bits,
-                            pcm.data()) != 0) {
+  const size_t hop_samples = (size_t)sample_rate_hz / 50;
+  std::vector<int16_t> pcm((size_t)job.frames * hop_samples);
+  if ((sample_rate_hz == kBatchInternalSampleRateHz
+           ? lyra_hip_decode_spans(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), packets.data(), num_bits,
+                                   pcm.data())
+           : lyra_hip_decode_spans_ext(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), packets.data(),
+                                       num_bits, sample_rate_hz, pcm.data())) != 0) {
     LOG(ERROR) << "Could not decode samples: " << lyra_hip_last_error(ctx.c);
     return false;
   }
   for (int i = 0; i < n; ++i)
-    (*decoded_audio)[i].assign(pcm.begin() + job.spans[i].first_frame * kBatchHopSamples,
-                               pcm.begin() + (job.spans[i].first_frame + job.spans[i].n_frames) * kBatchHopSamples);
+    (*decoded_audio)[i].assign(pcm.begin() + job.spans[i].first_frame * hop_samples,
+                               pcm.begin() + (job.spans[i].first_frame + job.spans[i].n_frames) * hop_samples);
   return true;
 }
 
@@ -355,8 +409,8 @@ bool DecodeFilesImpl(const std::vector<ghc::filesystem::path>& encoded_paths,
   }
   std::vector<std::vector<int16_t>> audio;
   const int packet_size = BatchBitrateToPacketSize(bitrate);
-  if (!(num_lanes < 0 ? DecodeFeaturesBatch(streams, packet_size, model_path, &audio, device)
-                      : DecodeFeaturesTimeParallel(streams, packet_size, model_path, &audio, num_lanes, device)))
+  if (!(num_lanes < 0 ? DecodeFeaturesBatch(streams, packet_size, sample_rate_hz, model_path, &audio, device)
+                      : DecodeFeaturesTimeParallel(streams, packet_size, sample_rate_hz, model_path, &audio, num_lanes, device)))
     return false;
   for (size_t i = 0; i < output_paths.size(); ++i)
     if (!WriteWav16(output_paths[i], audio[i], 1, sample_rate_hz)) return false;

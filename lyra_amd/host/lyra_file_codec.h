@@ -5,7 +5,10 @@
 // per call).  The ...TimeParallel forms below give the same bytes for long files at batch throughput.  The `.lyra` format is the reference's: the packets of a stream concatenated, nothing else
 // (encoder_main_lib.cc:120-130; a trailing partial hop is dropped, :71-73).
 //
-// Same scope as lyra_batch_codec.h: 16 kHz mono 16-bit WAV only, no preprocessing / DTX / packet-loss simulation.
+// Scope: mono 16-bit WAV at 8, 16, 32 or 48 kHz like the reference's EncodeFile / DecodeFile (the files of one batch share
+// their rate); at a rate other than 16 kHz every stream runs through its own resampler on the device, lyra_hip_resample per
+// hop or, in the time-parallel forms, one pass inside lyra_hip_encode_spans_ext / lyra_hip_decode_spans_ext.  A hop is
+// sample_rate_hz / 50 samples.  No preprocessing / DTX / packet-loss simulation: those are refused.
 #ifndef LYRA_AMD_HOST_LYRA_FILE_CODEC_H_
 #define LYRA_AMD_HOST_LYRA_FILE_CODEC_H_
 #include <cstdint>
@@ -26,8 +29,12 @@ bool EncodeFiles(const std::vector<ghc::filesystem::path>& wav_paths,
                  const std::vector<ghc::filesystem::path>& output_paths, int bitrate, bool enable_preprocessing,
                  bool enable_dtx, const ghc::filesystem::path& model_path, int device = 0);
 
-// DecodeFeatures for a batch, no packet loss: packet_streams[i] (multiple of packet_size bytes) -> decoded_audio[i].
+// DecodeFeatures for a batch, no packet loss: packet_streams[i] (multiple of packet_size bytes) -> decoded_audio[i],
+// at 16 kHz or, second form, at sample_rate_hz.
 bool DecodeFeaturesBatch(const std::vector<std::vector<uint8_t>>& packet_streams, int packet_size,
+                         const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
+                         int device = 0);
+bool DecodeFeaturesBatch(const std::vector<std::vector<uint8_t>>& packet_streams, int packet_size, int sample_rate_hz,
                          const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
                          int device = 0);
 
@@ -37,7 +44,7 @@ bool DecodeFiles(const std::vector<ghc::filesystem::path>& encoded_paths,
                  const ghc::filesystem::path& model_path, int device = 0);
 
 // ---- Time-parallel forms: long recordings at batch throughput --------------------------------------------------------
-// The same results, byte for byte, as the four functions above, through lyra_hip_encode_spans / lyra_hip_decode_spans
+// The same results, byte for byte, as the functions above, through lyra_hip_encode_spans[_ext] / lyra_hip_decode_spans[_ext]
 // (include/lyra_hip.h "Time-parallel spans"): every file is one span, cut into chunks that run side by side on up to
 // num_lanes scratch streams of the context, each behind a discarded warm-up.  The hop-by-hop functions above advance one hop
 // per blocking call -- one file, or the long tail of a batch of unequal files, is B = 1; these take a number of steps of about
@@ -52,6 +59,9 @@ bool EncodeFilesTimeParallel(const std::vector<ghc::filesystem::path>& wav_paths
                              bool enable_dtx, const ghc::filesystem::path& model_path, int num_lanes = kDefaultSpanLanes,
                              int device = 0);
 bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams, int packet_size,
+                                const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
+                                int num_lanes = kDefaultSpanLanes, int device = 0);
+bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams, int packet_size, int sample_rate_hz,
                                 const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
                                 int num_lanes = kDefaultSpanLanes, int device = 0);
 bool DecodeFilesTimeParallel(const std::vector<ghc::filesystem::path>& encoded_paths,

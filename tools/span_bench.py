@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """One long recording, encode then decode, time-parallel against hop by hop (BASELINE config #1: one file).
 
-   python tools/span_bench.py [--hops 180000] [--lanes 4096] [--bits 184] [--out profiles/span_transcode.jsonl]
+   python tools/span_bench.py [--hops 180000] [--lanes 4096] [--bits 184] [--rate 16000] [--out profiles/span_transcode.jsonl]
 
-Two records, appended to --out:
+--rate 8000 / 32000 / 48000: the recording is at that rate and both legs run the `_ext` span calls and the file functions at it
+(encode from the rate, decode to it); the baseline is the unchanged hop-by-hop calls at the same rate, lyra_hip_resample +
+lyra_hip_encode / lyra_hip_decode + lyra_hip_resample per hop.  A third record, kernel_share, then gives the part of
+span_resample_kernel in the device time of one encode + decode span call: this script runs its device leg once more as a child
+under `rocprofv3 --kernel-trace --stats` (a run of its own, so the timed legs are not traced).
+
+Records, appended to --out:
   span_transcode   lyra_hip_encode_spans_dev + lyra_hip_decode_spans_dev on device buffers, one stream of --hops hops with
                    --lanes lanes: wall time per direction (after a warm call), useful frames/s (the recording's hops, warm-up
                    hops not counted), the plan's step count and work inflation (L + W) / L, and `verified`: a prefix of
@@ -27,14 +33,15 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 
 
-def recording(hops):
-    """speech of the golden recordings, looped, with a slowly varying gain and a little noise so that no two hops are equal"""
+def recording(hops, rate=16000):
+    """speech of the golden recordings, looped, with a slowly varying gain and a little noise so that no two hops are equal
+    (at another rate the same samples, read as a signal at that rate)"""
     w = np.load(os.path.join(ROOT, "tests", "golden", "sample_wavs.npz"))
     src = np.concatenate([w["sample1_16kHz"], w["sample2_16kHz"]]).astype(np.float32)
-    n = hops * 320
+    n = hops * (rate // 50)
     rng = np.random.default_rng(7)
     x = src[np.arange(n) % src.size] * (0.6 + 0.4 * np.sin(np.arange(n) * 1e-5)) + rng.integers(-60, 61, n)
-    return np.clip(x, -32768, 32767).astype(np.int16).reshape(hops, 320)
+    return np.clip(x, -32768, 32767).astype(np.int16).reshape(hops, rate // 50)
 
 
 def device_leg(args, pcm):
@@ -52,16 +59,18 @@ def device_leg(args, pcm):
     L = int(lane_chunks["n_frames"].max()) if lane_chunks.size else hops
     d_pcm = torch.from_numpy(pcm).to(dev)
     d_pk = torch.zeros((hops, codec.packet_size(args.bits)), dtype=torch.uint8, device=dev)
-    d_out = torch.zeros((hops, 320), dtype=torch.int16, device=dev)
+    d_out = torch.zeros((hops, args.rate // 50), dtype=torch.int16, device=dev)
+    ext = args.rate != 16000
+    kw = dict(sample_rate_hz=args.rate, d_pcm16=torch.zeros((hops, 320), dtype=torch.int16, device=dev)) if ext else {}
     times = {"encode": [], "decode": []}
     for rep in range(args.reps + 1):   # rep 0 warms (allocations, code)
         ctx.reset()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        ctx.encode_spans_dev(spans, d_pcm, args.bits, d_pk, lanes)
+        ctx.encode_spans_dev(spans, d_pcm, args.bits, d_pk, lanes, **kw)
         ctx.synchronize()
         t1 = time.perf_counter()
-        ctx.decode_spans_dev(spans, d_pk, args.bits, d_out, lanes)
+        ctx.decode_spans_dev(spans, d_pk, args.bits, d_out, lanes, **kw)
         ctx.synchronize()
         t2 = time.perf_counter()
         if rep:
@@ -73,11 +82,14 @@ def device_leg(args, pcm):
     n = min(hops, args.verify_hops)
     ok = True
     for h in range(n):
-        p = twin.encode(pcm[h:h + 1], args.bits, [0])
+        x16 = twin.resample(pcm[h:h + 1], args.rate, 16000, [0], side="encoder") if ext else pcm[h:h + 1]
+        p = twin.encode(x16, args.bits, [0])
         o = twin.decode(p, args.bits, [0])
+        if ext:
+            o = twin.resample(o, 16000, args.rate, [0], side="decoder")
         ok = ok and np.array_equal(p[0], pk[h]) and np.array_equal(o[0], out[h])
     enc, dec = float(np.median(times["encode"])), float(np.median(times["decode"]))
-    return dict(kind="span_transcode", hops=hops, lanes=int(args.lanes), bits=args.bits, chunks=int(len(chunks)), steps=int(steps),
+    return dict(kind="span_transcode", rate=args.rate, hops=hops, lanes=int(args.lanes), bits=args.bits, chunks=int(len(chunks)), steps=int(steps),
                 warmup=W, chunk_hops=L, inflation=round((L + W) / L, 4) if lane_chunks.size else 1.0,
                 encode_s=round(enc, 5), decode_s=round(dec, 5), encode_frames_per_s=round(hops / enc),
                 decode_frames_per_s=round(hops / dec), reps=args.reps, verified=bool(ok), verified_hops=n)
@@ -88,18 +100,18 @@ def file_leg(args, pcm):
     demo = os.path.join(ROOT, "lyra_amd", "file_demo")
     bitrate = {64: 3200, 120: 6000, 184: 9200}[args.bits]
     hops = min(pcm.shape[0], args.file_hops) if args.file_hops else pcm.shape[0]
-    rec = dict(kind="file_transcode", hops=hops, bits=args.bits, lanes=int(args.lanes))
+    rec = dict(kind="file_transcode", rate=args.rate, hops=hops, bits=args.bits, lanes=int(args.lanes))
     with tempfile.TemporaryDirectory() as tmp:
         wav = os.path.join(tmp, "recording.wav")
         with wave.open(wav, "wb") as w:
-            w.setnchannels(1); w.setsampwidth(2); w.setframerate(16000)
+            w.setnchannels(1); w.setsampwidth(2); w.setframerate(args.rate)
             w.writeframes(pcm[:hops].tobytes())
         outs = {}
         for name, flag in (("time_parallel", ["--time-parallel=%d" % args.lanes]), ("hop_by_hop", [])):
             out_dir = os.path.join(tmp, name)
             os.mkdir(out_dir)
             t0 = time.perf_counter()
-            r = subprocess.run([demo, *flag, lyra_amd.default_model_dir(), str(bitrate), out_dir, wav],
+            r = subprocess.run([demo, *flag, "--decode-rate=%d" % args.rate, lyra_amd.default_model_dir(), str(bitrate), out_dir, wav],
                                capture_output=True, text=True, timeout=args.file_timeout)
             rec[name + "_s"] = round(time.perf_counter() - t0, 3)
             if r.returncode != 0:
@@ -116,6 +128,33 @@ def file_leg(args, pcm):
     return rec
 
 
+def kernel_share_leg(args):
+    """this script's device leg (one warm and one timed call per direction) as a child under rocprofv3 --kernel-trace --stats:
+    the share of span_resample_kernel in the summed kernel time of the process"""
+    import csv
+    import glob
+    rec = dict(kind="kernel_share", rate=args.rate, hops=args.hops, lanes=int(args.lanes), bits=args.bits)
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "span", "--",
+               sys.executable, os.path.abspath(__file__), "--device-leg-only", "--reps", "1", "--verify-hops", "0",
+               "--hops", str(args.hops), "--lanes", str(args.lanes), "--bits", str(args.bits), "--rate", str(args.rate)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.file_timeout)
+        stats = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
+        if r.returncode != 0 or not stats:
+            rec["error"] = (r.stderr or r.stdout)[-300:]
+            return rec
+        total = mine = calls = 0
+        for row in csv.DictReader(open(stats[0])):
+            ns = int(float(row["TotalDurationNs"]))
+            total += ns
+            if "span_resample_kernel" in row["Name"]:
+                mine += ns
+                calls += int(row["Calls"])
+        rec.update(kernel_time_ms=round(total / 1e6, 3), span_resample_ms=round(mine / 1e6, 3), span_resample_calls=calls,
+                   span_resample_share=round(mine / total, 5) if total else None)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--hops", type=int, default=180000)
@@ -126,14 +165,21 @@ def main():
     ap.add_argument("--file-hops", type=int, default=0, help="hops of the file leg (0: all)")
     ap.add_argument("--file-timeout", type=int, default=900)
     ap.add_argument("--skip-file-leg", action="store_true")
+    ap.add_argument("--rate", type=int, default=16000, choices=[8000, 16000, 32000, 48000])
+    ap.add_argument("--device-leg-only", action="store_true", help="the device leg alone, nothing recorded (the traced child)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "span_transcode.jsonl"))
     args = ap.parse_args()
-    pcm = recording(args.hops)
+    pcm = recording(args.hops, args.rate)
     recs = [device_leg(args, pcm)]
     print(json.dumps(recs[0]), flush=True)
+    if args.device_leg_only:
+        return
     if not args.skip_file_leg:
         recs.append(file_leg(args, pcm))
-        print(json.dumps(recs[1]), flush=True)
+        print(json.dumps(recs[-1]), flush=True)
+    if args.rate != 16000:
+        recs.append(kernel_share_leg(args))
+        print(json.dumps(recs[-1]), flush=True)
     with open(args.out, "a") as f:
         for r in recs:
             f.write(json.dumps(r) + "\n")
