@@ -647,8 +647,34 @@ long lyra_hip_import_errors(lyra_hip_ctx* ctx, int clear);
  *   Each `_ext` call is ONE call of its side as above and the resampler pass runs on the side's own stream inside it:
  *   UNLIKE lyra_hip_decode_ext_dev, whose external-rate output completes on the noise stream, everything a
  *   lyra_hip_decode_spans_ext_dev call writes completes on lyra_hip_stream_decode().
- * Out of scope: DTX, packet loss / comfort noise (the NoiseEstimator is a true recurrence, not history), per-span sample
- * rates, per-span bitrates.  LYRA_HIP_SUBBATCHES > 1 is accepted (the call is not split). */
+ *   DTX: lyra_hip_encode_spans_dtx[_dev] is LyraEncoder::Encode with enable_dtx over the spans.  The NoiseEstimator is a true
+ *   recurrence, not history -- but it reads the 16 kHz input audio alone, never encoder state (lyra_encoder.cc:113-156), so its
+ *   decisions are computed for all frames in front of the steps: [the resampler pass at 8 / 32 / 48 kHz,] the estimator's
+ *   log-mel of every frame in one launch, then one wavefront per span walking the recurrence frame by frame.  Under DTX the
+ *   encoder does not advance on noise hops (lyra_hip_encode_dtx): what it sees is the subsequence of non-noise hops, again a
+ *   stream whose state is convolution history, so the planner, lanes, warm-up and hand-over apply unchanged to that compacted
+ *   frame list (warm-up counted in non-noise hops).
+ *   Per span frame, packet_bytes (0 = empty packet, else num_bits / 8 rounded up) and the packet row are BIT FOR BIT what
+ *   lyra_hip_resample(ENCODER) + lyra_hip_encode_dtx per hop give; in the host form the rows of noise frames are left zero, in
+ *   the `_dev` form they are not written.  Afterwards the span streams' encoder stages, encoder-side estimator slot and
+ *   resampler slot are what those calls leave (lyra_hip_export_streams returns the same bytes); a span continues a live stream
+ *   and may be continued hop by hop.  Lanes lend encoder stage state only and come back reset; their estimator and resampler
+ *   slots are not touched.  Frames outside every span are untouched in every buffer.  A span with no non-noise frame runs no
+ *   chunk and leaves the encoder stage regions untouched.  d_pcm16 as in the `_ext` forms (may be NULL at 16000).
+ *   sample_rate_hz must equal the context's lyra_hip_set_encoder_sample_rate (the rule of lyra_hip_encode_ext_dev with dtx);
+ *   d_packet_bytes is required.  That, ids, lanes, frame ranges (the planner's rules on the spans as given), pointers,
+ *   alignment and the bit count are checked before the first kernel is enqueued: LYRA_HIP_EINVAL leaves the estimator
+ *   untouched.  All scratch is sized for the worst case (every frame non-noise) up front.
+ *   The call is ONE encode-side call on lyra_hip_stream().  UNLIKE the other `_dev` span calls it BLOCKS THE HOST ONCE, until
+ *   the scan has finished, because the plan depends on the decisions; everything behind that point is enqueued without
+ *   synchronising.  lyra_hip_set_serial is supported.
+ *   lyra_hip_noise_spans[_dev] is the estimator alone, NoiseEstimator::ReceiveSamples over every frame of every span of the
+ *   16 kHz buffer (16-byte aligned): is_noise[frame] is what lyra_hip_noise_receive returns for that hop and the stream's
+ *   estimator slot afterwards what the hop-by-hop calls leave.  Side ENCODER uses the constants and filterbank of
+ *   lyra_hip_set_encoder_sample_rate and is an encode-side call, side DECODER those of 16 kHz and is a decode-side call on
+ *   lyra_hip_stream_decode().  No lanes; the `_dev` form does not synchronise.
+ * Out of scope: packet loss / comfort noise on spans (the decoder-side estimator feeds back through the decoded audio),
+ * per-span sample rates, per-span bitrates.  LYRA_HIP_SUBBATCHES > 1 is accepted (the call is not split). */
 typedef struct lyra_hip_span { int32_t stream_id; int64_t first_frame; int64_t n_frames; } lyra_hip_span;
 /* warm-up hops of side LYRA_HIP_SIDE_ENCODER / LYRA_HIP_SIDE_DECODER (25 / 25); LYRA_HIP_EINVAL for any other side */
 int lyra_hip_span_warmup_frames(int side);
@@ -670,6 +696,16 @@ int lyra_hip_encode_spans_ext(lyra_hip_ctx* ctx, const lyra_hip_span* spans, int
                               const int16_t* pcm_ext, int sample_rate_hz, int num_bits, uint8_t* packets);
 int lyra_hip_decode_spans_ext(lyra_hip_ctx* ctx, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                               const uint8_t* packets, int num_bits, int sample_rate_hz, int16_t* pcm_ext);
+int lyra_hip_encode_spans_dtx_dev(lyra_hip_ctx* ctx, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                                  const int16_t* d_pcm_ext /* [frames][rate / 50] */, int sample_rate_hz,
+                                  int16_t* d_pcm16 /* [frames][320] workspace; may be NULL at 16000 */, int num_bits,
+                                  uint8_t* d_packets /* [frames][bytes] */, int32_t* d_packet_bytes /* [frames], required */);
+int lyra_hip_encode_spans_dtx(lyra_hip_ctx* ctx, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                              const int16_t* pcm_ext, int sample_rate_hz, int num_bits, uint8_t* packets, int32_t* packet_bytes);
+int lyra_hip_noise_spans_dev(lyra_hip_ctx* ctx, int side, const lyra_hip_span* spans, int n_spans,
+                             const int16_t* d_pcm16 /* [frames][320] */, int32_t* d_is_noise /* [frames] */);
+int lyra_hip_noise_spans(lyra_hip_ctx* ctx, int side, const lyra_hip_span* spans, int n_spans, const int16_t* pcm16,
+                         int32_t* is_noise);
 /* The planner of the four calls, a pure function (no context, no device).  Chunk r is row r of the call's batch: it runs on
  * stream_id for n_warmup + n_frames steps; step i reads buffer frame first_frame - n_warmup + i and from step n_warmup on
  * writes its output there.  Chunk 0 of a span runs on the span's own stream with no warm-up; the others on lanes, behind

@@ -209,6 +209,11 @@ def _load(path=None):
         L.lyra_hip_decode_spans_ext.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, vp]
         L.lyra_hip_encode_spans_ext_dev.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, ci, vp]
         L.lyra_hip_decode_spans_ext_dev.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, vp, vp]
+    if hasattr(L, "lyra_hip_encode_spans_dtx"):
+        L.lyra_hip_encode_spans_dtx_dev.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp]
+        L.lyra_hip_encode_spans_dtx.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, vp, vp]
+        L.lyra_hip_noise_spans_dev.argtypes = [vp, ci, vp, ci, vp, vp]
+        L.lyra_hip_noise_spans.argtypes = [vp, ci, vp, ci, vp, vp]
     L.lyra_hip_set_cng_seed.argtypes = [vp, C.c_uint64]
     L.lyra_hip_set_encoder_sample_rate.argtypes = [vp, C.c_int]
     L.lyra_hip_stream.restype = vp
@@ -839,6 +844,56 @@ class LyraHip:
                        self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"), num_bits, sample_rate_hz,
                        self._dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm") if d_pcm16 is not None else None,
                        self._dev_ptr(d_pcm, "int16", (F, sample_rate_hz // 50), "pcm"))
+
+    # -- DTX on spans (lyra_hip_encode_spans_dtx / lyra_hip_noise_spans) -------------------------------------------------------
+    def encode_spans_dtx(self, spans, pcm, num_bits, lane_ids=(), sample_rate_hz=16000):
+        """encode_spans with enable_dtx: bit for bit resample(side="encoder") + encode_dtx per hop.  pcm int16
+        [frames][sample_rate_hz / 50]; sample_rate_hz must be the rate given to set_encoder_sample_rate.  Returns (packets uint8
+        [frames][bytes], packet_bytes int32 [frames]); rows of noise frames and rows outside every span are 0."""
+        sp = _spans(spans)
+        lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
+        pcm = _np(pcm, np.int16, (-1, self._span_hop(sample_rate_hz)))
+        out = np.zeros((pcm.shape[0], packet_size(num_bits)), np.uint8)
+        nbytes = np.zeros(pcm.shape[0], np.int32)
+        self._check_span_frames(sp, pcm.shape[0])
+        self._chk(self.L.lyra_hip_encode_spans_dtx(self.h, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
+                                                   pcm.ctypes.data, sample_rate_hz, num_bits, out.ctypes.data,
+                                                   nbytes.ctypes.data))
+        return out, nbytes
+
+    def encode_spans_dtx_dev(self, spans, d_pcm, num_bits, d_packets, d_packet_bytes, lane_ids=(), sample_rate_hz=16000,
+                             d_pcm16=None):
+        """encode_spans_dtx on device buffers: d_pcm int16 [frames][sample_rate_hz / 50], d_packets uint8 [frames][bytes] (rows
+        of noise frames are not written), d_packet_bytes int32 [frames], d_pcm16 int16 [frames][320] the 16 kHz workspace (not
+        needed at 16000).  Blocks the host once, until the noise decisions are known; the steps behind are only enqueued."""
+        sp = _spans(spans)
+        lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
+        F = d_pcm.shape[0]
+        self._check_span_frames(sp, F)
+        self._dev_call(self.L.lyra_hip_encode_spans_dtx_dev, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
+                       self._dev_ptr(d_pcm, "int16", (F, self._span_hop(sample_rate_hz)), "pcm"), sample_rate_hz,
+                       self._dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm") if d_pcm16 is not None else None, num_bits,
+                       self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"),
+                       self._dev_ptr(d_packet_bytes, "int32", (F,), "packet_bytes") if d_packet_bytes is not None else None)
+
+    def noise_spans(self, spans, pcm, side="encoder"):
+        """NoiseEstimator::ReceiveSamples over every frame of every span of pcm int16 [frames][320] -> is_noise int32 [frames]
+        (what noise_receive returns per hop; rows outside every span are 0)."""
+        sp = _spans(spans)
+        pcm = _np(pcm, np.int16, (-1, HOP))
+        out = np.zeros(pcm.shape[0], np.int32)
+        self._check_span_frames(sp, pcm.shape[0])
+        self._chk(self.L.lyra_hip_noise_spans(self.h, self._SIDES[side], sp.ctypes.data, sp.size, pcm.ctypes.data,
+                                              out.ctypes.data))
+        return out
+
+    def noise_spans_dev(self, spans, d_pcm, d_is_noise, side="encoder"):
+        """noise_spans on device buffers; enqueues and does not synchronise."""
+        sp = _spans(spans)
+        F = d_pcm.shape[0]
+        self._check_span_frames(sp, F)
+        self._dev_call(self.L.lyra_hip_noise_spans_dev, self._SIDES[side], sp.ctypes.data, sp.size,
+                       self._dev_ptr(d_pcm, "int16", (F, HOP), "pcm"), self._dev_ptr(d_is_noise, "int32", (F,), "is_noise"))
 
     def noise_receive_dev(self, d_ids, d_pcm, d_is_noise, side="decoder"):
         """NoiseEstimator::ReceiveSamples on device buffers: pcm int16 [B][320] -> is_noise int32 [B]."""

@@ -138,6 +138,10 @@ struct MelP { const double* hann; const double* tw_re; const double* tw_im; cons
               int start, end; };
 // NoiseEstimator::Create's constants (noise_estimator.cc:96-124): round(1 s / 20 ms), 0.5^(20 ms / 0.7 s), 0.5^(20 ms / 1 s)
 struct NoiseP { int hops_per_update; float max_smoothing, bound_decay; };
+// std::exp(float) of the estimator (noise_update_wave, span_noise_scan_kernel): float(exp(double)), see misc_kernels.hip
+__device__ __forceinline__ float expf_via_double(float x) {
+  return (float)exp((double)x);
+}
 // noise_tail: continue with the NoiseEstimator update of the same hop (state must then be a NoiseEstimator region)
 __global__ void logmel_kernel(const MelP* P, const int16_t* pcm, const int32_t* ids, int B, uint8_t* state, int stride,
                               int prev_off, float* mel, int noise_tail, NoiseP NP, int32_t* is_noise_out,
@@ -241,10 +245,11 @@ struct SpanRow { int32_t id, n_steps, n_warm, target, phase_add, handover; long 
 // step's rows between the frame-major buffer and the dense [B][row_bytes] rows of the stage kernels.  gather: frames -> dense,
 // and step_ids[r] = the row's id while it runs, else -1; scatter: dense -> frames for the rows past their warm-up.
 // unit16: rows are moved in 16-byte units (row_bytes a multiple of 16, both buffers 16-byte aligned), else byte by byte.
+// map (optional; lyra_hip_encode_spans_dtx_dev): the rows count in a compacted frame list, index c is buffer frame map[c].
 __global__ void span_gather_kernel(const SpanRow* rows, int B, int step, const uint8_t* frames, int row_bytes, int unit16,
-                                   uint8_t* dense, int32_t* step_ids);
+                                   uint8_t* dense, int32_t* step_ids, const long long* map);
 __global__ void span_scatter_kernel(const SpanRow* rows, int B, int step, const uint8_t* dense, int row_bytes, int unit16,
-                                    uint8_t* frames);
+                                    uint8_t* frames, const long long* map);
 // regions r0 .. r0 + 2 (R_E0 or R_D0) of rows[b].id: the reset state; ring phase words: target's + phase_add (target >= 0)
 __global__ void span_lane_init_kernel(const ResetP* P, const SpanRow* rows, int n, int r0, StateMap sm);
 // rows with handover != 0: regions r0 .. r0 + 2 of the lane -> the same regions of target
@@ -259,5 +264,22 @@ static_assert(sizeof(SpanRsRow) == sizeof(SpanRow), "one upload holds both kinds
 // read by all).  grid = the workgroups of all rows, 256 threads, LDS resample_lds_bytes(n_in).
 __global__ void span_resample_kernel(ResampleP P, const SpanRsRow* rows, int n_rows, uint8_t* state, const int16_t* in, int n_in,
                                      int16_t* out, int n_out);
+// ---- DTX on spans (spans_dtx_kernels.hip; lyra_hip_encode_spans_dtx_dev / lyra_hip_noise_spans_dev) --------------------------
+// One span with frames: buffer frames frame0 .. frame0 + n_frames - 1 belong to stream `id`; wg0 = the span's first workgroup of
+// span_logmel_kernel (two frames each; rows in rising wg0); region = the frames of the rows in front of it: where the span's mel
+// rows and its part of the map start.
+struct SpanDtxRow { long long frame0, n_frames; int32_t id, wg0; long long region; };
+static_assert(sizeof(SpanDtxRow) == sizeof(SpanRow), "one upload holds both kinds of row");
+constexpr int SPAN_MEL_ROW = 164;   // floats per mel row: 160 bins, Average() of them, padding to 16 bytes
+// log-mel of every frame of every row's span -> mel[region + f][SPAN_MEL_ROW]; state = a NoiseEstimator region, of which only
+// N_PREV is read (frame 0) and written (the span's last frame), both by the span's first workgroup.  grid = the workgroups
+// of all rows, 256 threads, LDS logmel_lds_bytes().
+__global__ void span_logmel_kernel(const MelP* P, const SpanDtxRow* rows, int n_rows, uint8_t* state, const int16_t* pcm,
+                                   float* mel);
+// NoiseEstimator::ReceiveSamples' decision + recurrence over the frames of one span per wavefront (grid n_rows, 64 threads):
+// flag_out[frame] = v_noise / v_active, map[region + c] = buffer frame of the span's c-th non-noise frame (map optional),
+// counts[row] = the span's non-noise frames.
+__global__ void span_noise_scan_kernel(NoiseP P, const SpanDtxRow* rows, int n_rows, uint8_t* state, const float* mel,
+                                       int32_t* flag_out, int v_noise, int v_active, long long* map, int32_t* counts);
 
 }  // namespace lyra

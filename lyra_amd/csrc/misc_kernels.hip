@@ -398,107 +398,13 @@ __device__ __forceinline__ void logmel_body(const MelP* __restrict__ Pp, const i
   int16_t* prev1 = reinterpret_cast<int16_t*>(state + (size_t)ids[two ? b1 : b0] * stride + prev_off);
   const int16_t* cur0 = pcm + (size_t)b0 * 320;
   const int16_t* cur1 = pcm + (size_t)(two ? b1 : b0) * 320;
-  // window = [previous hop | this hop] x periodic Hann, zero-padded to 1024.  The first radix-4 pass of a decimation-in-
-  // time transform combines x[n], x[n+256], x[n+512], x[n+768]: thread n reads its own three window samples of both
-  // frames (x[n+768] = 0; x[n+512] = 0 for n >= 128) straight from memory, does that butterfly in registers and writes
-  // the four results where the second pass expects them (4 * digit-reverse(n) + q) -- no staging pass, no scatter of
-  // single samples.  The samples of this hop it holds are exactly the stream's next history: thread n >= 64 holds
-  // sample n-64 of the hop, thread n < 128 sample n+192.
-  const int n = tid;
-  const bool has1 = n >= 64, has2 = n < 128;
-  const int16_t a0 = prev0[n], a1 = prev1[n];
-  const int16_t b0s = has1 ? cur0[n - 64] : prev0[n + 256], b1s = has1 ? cur1[n - 64] : prev1[n + 256];
-  const int16_t c0s = has2 ? cur0[n + 192] : (int16_t)0, c1s = has2 ? cur1[n + 192] : (int16_t)0;
-  const double h0 = P.hann[n], h1 = P.hann[n + 256], h2 = has2 ? P.hann[n + 512] : 0.0;
-  // twiddles of the second pass (L = 4), requested before the first butterfly; mel weights and band edges for the epilogue
-  double w1r, w1i, w2r, w2i, w3r, w3i;
-  {
-    const int t1 = (tid & 3) * 64;
-    w1r = P.tw4_re[t1]; w1i = P.tw4_im[t1]; w2r = P.tw4_re[2 * t1]; w2i = P.tw4_im[2 * t1];
-    w3r = P.tw4_re[3 * t1]; w3i = P.tw4_im[3 * t1];
-  }
-  const double wsel0 = PA.w[tid], wsel1 = PA.w[tid + 256], wsel2 = tid == 0 ? PA.w[512] : 0.0;
-  double vsel0 = 0.0, vsel1 = 0.0, vsel2 = 0.0;
-  if constexpr (kRates) { vsel0 = PB.w[tid]; vsel1 = PB.w[tid + 256]; vsel2 = tid == 0 ? PB.w[512] : 0.0; }
-  // band sums: 320 (frame, band) items on 256 threads -- thread t < 160 takes (frame 0, band t), thread t >= 160 takes
-  // (frame 1, band t - 96) i.e. the 96 widest bands, and threads t < 64 then also take (frame 1, band t), the narrow ones:
-  // the longest chain is ONE wide band (<= 18 bins)
-  const int my_band = tid < 160 ? tid : tid - 96;
-  const int* bandp = (kRates && tid >= 160) ? PB.band : PA.band;
-  const int be0 = bandp[my_band], be1 = bandp[my_band + 1], be2 = bandp[my_band + 2];
-  int ce0 = be0, ce1 = be1, ce2 = be2;   // edges of the second item (frame 1, band tid) of threads < 64
-  if constexpr (kRates) { if (tid < 64) { ce0 = PB.band[tid]; ce1 = PB.band[tid + 1]; ce2 = PB.band[tid + 2]; } }
-  {
-    const double ar = (double)a0 * h0, ai = two ? (double)a1 * h0 : 0.0;
-    const double br = (double)b0s * h1, bi = two ? (double)b1s * h1 : 0.0;
-    const double cr = (double)c0s * h2, ci = two ? (double)c1s * h2 : 0.0;
-    const double s0r = ar + cr, s0i = ai + ci, s1r = ar - cr, s1i = ai - ci;   // d = 0: b + d = b - d = b
-    unsigned r = __brev((unsigned)n) >> 24;                                     // reverse the four base-4 digits of n
-    r = ((r & 0xAAu) >> 1) | ((r & 0x55u) << 1);
-    f64x2* o = z + 4 * r;
-    o[0] = (f64x2){s0r + br, s0i + bi};
-    o[1] = (f64x2){s1r + bi, s1i - br};     // (a - c) - i b
-    o[2] = (f64x2){s0r - br, s0i - bi};
-    o[3] = (f64x2){s1r - bi, s1i + br};     // (a - c) + i b
-  }
+#include "logmel_window.inc"
   __syncthreads();
   // every read of the old history is done: the hop becomes the history
   if (has1) { prev0[n - 64] = b0s; if (two) prev1[n - 64] = b1s; }
   if (has2) { prev0[n + 192] = c0s; if (two) prev1[n + 192] = c1s; }
   LYRA_TSTAMP(111);
-  // four more radix-4 passes; pass s combines four L-point transforms (L = 4^s) into one 4L-point one:
-  //   y_q = sum_r (-i)^(r q) W_4L^(r k) F_r[k].  The twiddles of pass s+1 (L2-resident table) are requested before
-  // the butterflies of pass s, so their latency hides behind the LDS round trip and the barrier.
-#pragma unroll
-  for (int s = 1; s < 5; ++s) {
-    const int L = 1 << (2 * s);
-    const int k = tid & (L - 1), g = tid >> (2 * s);
-    f64x2* p = z + g * 4 * L + k;
-    double n1r = 1.0, n1i = 0.0, n2r = 1.0, n2i = 0.0, n3r = 1.0, n3i = 0.0;
-    if (s < 4) {
-      const int Ln = 4 * L, kn = tid & (Ln - 1);
-      const int t1 = kn * (256 >> (2 * (s + 1)));     // W_4L^k = W_1024^(k * 1024 / 4L)
-      n1r = P.tw4_re[t1]; n1i = P.tw4_im[t1]; n2r = P.tw4_re[2 * t1]; n2i = P.tw4_im[2 * t1];
-      n3r = P.tw4_re[3 * t1]; n3i = P.tw4_im[3 * t1];
-    }
-    const f64x2 xa = p[0], x1 = p[L], x2 = p[2 * L], x3 = p[3 * L];
-    const double br = __builtin_fma(x1.x, w1r, -(x1.y * w1i)), bi = __builtin_fma(x1.x, w1i, x1.y * w1r);
-    const double cr = __builtin_fma(x2.x, w2r, -(x2.y * w2i)), ci = __builtin_fma(x2.x, w2i, x2.y * w2r);
-    const double dr = __builtin_fma(x3.x, w3r, -(x3.y * w3i)), di = __builtin_fma(x3.x, w3i, x3.y * w3r);
-    const double s0r = xa.x + cr, s0i = xa.y + ci, s1r = xa.x - cr, s1i = xa.y - ci;
-    const double s2r = br + dr, s2i = bi + di, s3r = br - dr, s3i = bi - di;
-    p[0] = (f64x2){s0r + s2r, s0i + s2i};
-    p[L] = (f64x2){s1r + s3i, s1i - s3r};         // (a - c) - i (b - d)
-    p[2 * L] = (f64x2){s0r - s2r, s0i - s2i};
-    p[3 * L] = (f64x2){s1r - s3i, s1i + s3r};     // (a - c) + i (b - d)
-    w1r = n1r; w1i = n1i; w2r = n2r; w2i = n2i; w3r = n3r; w3i = n3i;
-    __syncthreads();
-  }
-  LYRA_TSTAMP(112);
-  // Z = FFT(a + i b):  A[k] = (Z[k] + conj(Z[N-k])) / 2,  B[k] = (Z[k] - conj(Z[N-k])) / (2 i).  In place: the item
-  // for bin k <= 512 reads Z[k] and Z[N - k] and writes index k only; index k < 512 is read by no other item and
-  // indices > 512 are never written, so no staging buffer (and no barrier before the writes) is needed.
-  for (int k = tid; k <= 512; k += 256) {
-    const int nk = (1024 - k) & 1023;
-    const f64x2 zz = z[k], yy = z[nk];
-    const double Ar = 0.5 * (zz.x + yy.x), Ai = 0.5 * (zz.y - yy.y);
-    const double Br = 0.5 * (zz.y + yy.y), Bi = 0.5 * (yy.x - zz.x);
-    z[k] = (f64x2){__builtin_sqrt(Ar * Ar + Ai * Ai), __builtin_sqrt(Br * Br + Bi * Bi)};
-  }
-  __syncthreads();
-  LYRA_TSTAMP(113);
-  // the mel weights go to the now dead upper half of the buffer: the band loops below would otherwise wait for one L2
-  // round trip per bin
-  wl[tid] = wsel0;
-  wl[tid + 256] = wsel1;
-  if (tid == 0) wl[512] = wsel2;
-  double* wl1 = kRates ? dsm + 2048 : wl;   // frame 1's weights
-  if constexpr (kRates) {
-    wl1[tid] = vsel0;
-    wl1[tid + 256] = vsel1;
-    if (tid == 0) wl1[512] = vsel2;
-  }
-  __syncthreads();
+#include "logmel_fft.inc"
   LYRA_TSTAMP(114);
   // the noise tail's view of the stream's slot is requested here, one batch, and arrives under the band sums
   const int tw = tid >> 6;
@@ -511,19 +417,7 @@ __device__ __forceinline__ void logmel_body(const MelP* __restrict__ Pp, const i
   int e0 = be0, e1 = be1, e2 = be2;
   const double* wt = (kRates && tid >= 160) ? wl1 : wl;
   auto band_item = [&](int f, int band) {
-    const double* mag = dsm + f;          // |X_f[i]| = mag[2 * i]
-    double acc = 0.0;
-    double v = mag[2 * e0], wv = wt[e0];
-    for (int i = e0; i < e2; ++i) {
-      const double vn = mag[2 * i + 2], wn = wt[i + 1];
-      const double w = v * wv;
-      acc += i < e1 ? v - w : w;
-      v = vn; wv = wn;
-    }
-    float x = (float)acc;
-    x = x > 500.f ? x : 500.f;
-    // log evaluated in double and rounded once: identical on host and device (oracle/lyra_oracle.c log_f)
-    const float lm = (float)log((double)x) / 10.f;
+#include "logmel_band.inc"
     if (mel) mel[(size_t)(b0 + f) * 160 + band] = lm;
     if (noise_tail) mel_lds[f * 160 + band] = lm;
   };
@@ -583,12 +477,9 @@ __global__ __launch_bounds__(256) void logmel_rates_kernel(const MelP* __restric
 // as the reference; the two Average() sums are sequential (std::accumulate from 0.f) and run on one lane out of
 // LDS.  std::exp(float) is evaluated as float(exp(double)): a <= 1 ULP double result rounds to the correctly rounded
 // float, which is what the host libm returns.  masked_ids (optional): ids[i], or -1 where the hop is noise -- the
-// stream list the DTX-enabled encoder runs on (lyra_encoder.cc:131-141).
+// stream list the DTX-enabled encoder runs on (lyra_encoder.cc:131-141).  (expf_via_double: kernels.h, shared with
+// span_noise_scan_kernel.)
 // =============================================================================================
-__device__ __forceinline__ float expf_via_double(float x) {
-  return (float)exp((double)x);
-}
-
 // One wavefront = one stream (slot w of the workgroup, NW slots); every thread of the workgroup calls this (two
 // workgroup barriers inside).  `mel`: the hop's 160 log-mel bins (LDS or global); `on`: the slot holds a real stream.
 __device__ __forceinline__ NoisePre noise_prefetch(int id, const uint8_t* state, bool mine) {

@@ -10,6 +10,10 @@
 // frames of the spans in front of the steps (encode: external rate -> the caller's [frames][320] workspace, which the steps
 // then read) or behind them (decode: the steps write the workspace).  The resampler needs no lanes: its state is the 34 input
 // samples in front of a frame, and those are in the buffer.
+// lyra_hip_encode_spans_dtx[_dev] puts the DTX encoder's NoiseEstimator in front of the steps (spans_dtx_kernels.hip: the log-mel
+// of all frames in one launch, then one wavefront per span for the recurrence), waits ONCE on the host for the spans' counts of
+// non-noise hops, and runs the unchanged steps on the compacted frame list: under DTX the encoder advances on non-noise hops
+// only, so what it sees is again a stream whose state is convolution history.  lyra_hip_noise_spans[_dev] is the estimator alone.
 #include "spans_plan.h"
 
 static_assert(sizeof(lyra_hip_span) == sizeof(sp::Span) && sizeof(lyra_hip_span_chunk) == sizeof(sp::Chunk) &&
@@ -32,6 +36,13 @@ struct SpanSide {
   uint8_t* d_out = nullptr;         // [cap][640]  packets (encode) / PCM (decode) in front of the scatter
   float* d_feat = nullptr;          // [cap][64]   encode: features between extractor and quantizer
   int32_t* d_step_ids = nullptr;    // [cap]       the step's id list (-1: the row has ended)
+  // DTX (encode_spans_dtx, noise_spans): grow-only like the above
+  long long dtx_cap = 0;            // frames
+  float* d_mel = nullptr;           // [dtx_cap][SPAN_MEL_ROW]  mel rows of the call's frames, span after span
+  long long* d_map = nullptr;       // [dtx_cap]   buffer frame of every non-noise frame, a region per span
+  int counts_cap = 0;
+  int32_t* h_counts = nullptr;      // pinned [counts_cap]: non-noise frames per span with frames, written by the scan
+  int32_t* d_counts = nullptr;      // the device's view of h_counts
 };
 struct SpanCalls { SpanSide side[2]; };
 
@@ -40,10 +51,13 @@ SpanCalls* span_calls_of(lyra_hip_ctx* c) { return static_cast<SpanCalls*>(c->sp
 void span_side_free(SpanSide& S) {
   if (S.h_rows) (void)hipHostFree(S.h_rows);
   S.h_rows = nullptr;
-  dfree(S.d_rows, S.d_in, S.d_out, S.d_feat, S.d_step_ids);
+  dfree(S.d_rows, S.d_in, S.d_out, S.d_feat, S.d_step_ids, S.d_mel, S.d_map);
+  if (S.h_counts) (void)hipHostFree(S.h_counts);
+  S.h_counts = S.d_counts = nullptr;
   if (S.ev_up) (void)hipEventDestroy(S.ev_up);
   S.ev_up = nullptr;
-  S.rows_cap = S.cap = 0;
+  S.rows_cap = S.cap = S.counts_cap = 0;
+  S.dtx_cap = 0;
 }
 
 void spans_free(lyra_hip_ctx* c) {
@@ -169,6 +183,56 @@ int launch_span_resample(lyra_hip_ctx* c, bool enc, hipStream_t st_, const SpanR
   return 0;
 }
 
+// Lane preparation, the T steps, hand-over and lane reset of one call on st_.  h_batch / d_batch: the plan's rows (host copy
+// and device), d_reset: one row per lane.  enc: d_src PCM [frames][320], d_dst packets [frames][nbytes]; else the reverse.
+// d_map (encode_spans_dtx): the plan counts frames in the compacted list, index c is buffer frame d_map[c].
+int span_run_steps(lyra_hip_ctx* c, bool enc, SpanSide& S, hipStream_t st_, const SpanPlan& P, const SpanRow* h_batch,
+                   const SpanRow* d_batch, const SpanRow* d_reset, int n_lanes, const void* d_src, int num_bits, void* d_dst,
+                   const long long* d_map) {
+  const int rows = (int)P.chunks.size(), nbytes = (num_bits + 7) / 8, r0 = enc ? st::R_E0 : st::R_D0;
+  int rc = 0;
+  const int n_lane_rows = rows - P.n_own;
+  if (n_lane_rows) {
+    hipLaunchKernelGGL(span_lane_init_kernel, dim3(n_lane_rows), dim3(256), 0, st_, c->model.d_reset, d_batch + P.n_own,
+                       n_lane_rows, r0, c->sm);
+    HIPCHK(c, hipGetLastError());
+  }
+  const int W = sp::warmup(enc ? sp::SIDE_ENC : sp::SIDE_DEC);
+  const int in_bytes = enc ? 640 : nbytes, out_bytes = enc ? nbytes : 640;
+  for (int i = 0; i < P.n_steps && !rc; ++i) {
+    int own = 0;
+    const int B = span_batch_at(P, h_batch, i, &own);
+    hipLaunchKernelGGL(span_gather_kernel, dim3(span_grid(B, enc ? 40 : in_bytes)), dim3(256), 0, st_, d_batch, B, i,
+                       (const uint8_t*)d_src, in_bytes, enc ? 1 : 0, S.d_in, S.d_step_ids, d_map);
+    HIPCHK(c, hipGetLastError());
+    if (enc) {
+      rc = launch_extract(c, 0, 0, S.d_step_ids, B, (const int16_t*)S.d_in, S.d_feat);
+      // warm-up steps of the lanes skip the quantizer: before step W only the spans' own rows produce
+      const int Bq = i < W ? own : B;
+      if (!rc && Bq) rc = launch_rvq_encode(c, 0, Bq, S.d_feat, num_bits / 4, nullptr, S.d_out, S.d_step_ids);
+      if (rc || !Bq) continue;
+      hipLaunchKernelGGL(span_scatter_kernel, dim3(span_grid(Bq, out_bytes)), dim3(256), 0, st_, d_batch, Bq, i, S.d_out,
+                         out_bytes, 0, (uint8_t*)d_dst, d_map);
+    } else {
+      if ((rc = launch_generate(c, 0, 0, S.d_step_ids, B, nullptr, (int16_t*)S.d_out, S.d_in, num_bits / 4))) continue;
+      const int Bs = i < W ? own : B;
+      if (!Bs) continue;
+      hipLaunchKernelGGL(span_scatter_kernel, dim3(span_grid(Bs, 40)), dim3(256), 0, st_, d_batch, Bs, i, S.d_out, out_bytes,
+                         1, (uint8_t*)d_dst, d_map);
+    }
+    HIPCHK(c, hipGetLastError());
+  }
+  if (!rc && n_lane_rows) {
+    hipLaunchKernelGGL(span_handover_kernel, dim3(n_lane_rows), dim3(256), 0, st_, d_batch + P.n_own, n_lane_rows, r0, c->sm);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (!rc && n_lanes) {   // every lane the caller lent, used or not, comes back reset
+    hipLaunchKernelGGL(span_lane_init_kernel, dim3(n_lanes), dim3(256), 0, st_, c->model.d_reset, d_reset, n_lanes, r0, c->sm);
+    HIPCHK(c, hipGetLastError());
+  }
+  return rc;
+}
+
 // The enqueue of one call.  enc: d_src PCM [frames][320], d_dst packets [frames][nbytes]; else the reverse.  X.on(): the PCM
 // of d_src / d_dst is [frames][X.n_ext()] and the steps work on X.d_pcm16.
 int spans_enqueue(lyra_hip_ctx* c, bool enc, const SpanPlan& P, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids,
@@ -176,7 +240,7 @@ int spans_enqueue(lyra_hip_ctx* c, bool enc, const SpanPlan& P, const lyra_hip_s
   if (!c->span_calls) c->span_calls = new SpanCalls();
   SpanSide& S = span_calls_of(c)->side[enc ? 0 : 1];
   hipStream_t st_ = enc ? c->se[0] : c->sd[0];
-  const int rows = (int)P.chunks.size(), nbytes = (num_bits + 7) / 8, r0 = enc ? st::R_E0 : st::R_D0;
+  const int rows = (int)P.chunks.size();
   int n_rs = 0;
   const long long rs_wgs = X.on() ? span_rs_rows(spans, n_spans, nullptr, &n_rs) : 0;
   if (rs_wgs < 0) return fail(c, LYRA_HIP_EINVAL, "spans: too many frames for one resampler pass");
@@ -202,46 +266,7 @@ int spans_enqueue(lyra_hip_ctx* c, bool enc, const SpanPlan& P, const lyra_hip_s
     d_ext_out = d_dst;
     d_dst = X.d_pcm16;
   }
-  const int n_lane_rows = rows - P.n_own;
-  if (n_lane_rows) {
-    hipLaunchKernelGGL(span_lane_init_kernel, dim3(n_lane_rows), dim3(256), 0, st_, c->model.d_reset, S.d_rows + P.n_own,
-                       n_lane_rows, r0, c->sm);
-    HIPCHK(c, hipGetLastError());
-  }
-  const int W = sp::warmup(enc ? sp::SIDE_ENC : sp::SIDE_DEC);
-  const int in_bytes = enc ? 640 : nbytes, out_bytes = enc ? nbytes : 640;
-  for (int i = 0; i < P.n_steps && !rc; ++i) {
-    int own = 0;
-    const int B = span_batch_at(P, S.h_rows, i, &own);
-    hipLaunchKernelGGL(span_gather_kernel, dim3(span_grid(B, enc ? 40 : in_bytes)), dim3(256), 0, st_, S.d_rows, B, i,
-                       (const uint8_t*)d_src, in_bytes, enc ? 1 : 0, S.d_in, S.d_step_ids);
-    HIPCHK(c, hipGetLastError());
-    if (enc) {
-      rc = launch_extract(c, 0, 0, S.d_step_ids, B, (const int16_t*)S.d_in, S.d_feat);
-      // warm-up steps of the lanes skip the quantizer: before step W only the spans' own rows produce
-      const int Bq = i < W ? own : B;
-      if (!rc && Bq) rc = launch_rvq_encode(c, 0, Bq, S.d_feat, num_bits / 4, nullptr, S.d_out, S.d_step_ids);
-      if (rc || !Bq) continue;
-      hipLaunchKernelGGL(span_scatter_kernel, dim3(span_grid(Bq, out_bytes)), dim3(256), 0, st_, S.d_rows, Bq, i, S.d_out,
-                         out_bytes, 0, (uint8_t*)d_dst);
-    } else {
-      if ((rc = launch_generate(c, 0, 0, S.d_step_ids, B, nullptr, (int16_t*)S.d_out, S.d_in, num_bits / 4))) continue;
-      const int Bs = i < W ? own : B;
-      if (!Bs) continue;
-      hipLaunchKernelGGL(span_scatter_kernel, dim3(span_grid(Bs, 40)), dim3(256), 0, st_, S.d_rows, Bs, i, S.d_out, out_bytes,
-                         1, (uint8_t*)d_dst);
-    }
-    HIPCHK(c, hipGetLastError());
-  }
-  if (!rc && n_lane_rows) {
-    hipLaunchKernelGGL(span_handover_kernel, dim3(n_lane_rows), dim3(256), 0, st_, S.d_rows + P.n_own, n_lane_rows, r0, c->sm);
-    HIPCHK(c, hipGetLastError());
-  }
-  if (!rc && n_lanes) {   // every lane the caller lent, used or not, comes back reset
-    hipLaunchKernelGGL(span_lane_init_kernel, dim3(n_lanes), dim3(256), 0, st_, c->model.d_reset, S.d_rows + rows, n_lanes, r0,
-                       c->sm);
-    HIPCHK(c, hipGetLastError());
-  }
+  rc = span_run_steps(c, enc, S, st_, P, S.h_rows, S.d_rows, S.d_rows + rows, n_lanes, d_src, num_bits, d_dst, nullptr);
   if (!rc && d_ext_out && n_rs)
     rc = launch_span_resample(c, false, st_, d_rs_rows, n_rs, rs_wgs, 16000, X.rate, X.d_pcm16, (int16_t*)d_ext_out);
   if (enc) {
@@ -315,6 +340,262 @@ int spans_call_host(lyra_hip_ctx* c, bool enc, const lyra_hip_span* spans, int n
   return rc;
 }
 
+// ---- DTX on spans ---------------------------------------------------------------------------------------------------------
+// rows of span_logmel_kernel / span_noise_scan_kernel: the spans with frames, two frames per log-mel workgroup; region = the
+// frames of the rows in front.  Returns the log-mel workgroups, -1: too many; *frames: all rows' frames.
+long long span_dtx_rows(const lyra_hip_span* spans, int n_spans, SpanDtxRow* rows, int* n_rows, long long* frames) {
+  long long wg = 0, region = 0;
+  int n = 0;
+  for (int s = 0; s < n_spans; ++s) {
+    if (!spans[s].n_frames) continue;
+    if (rows) rows[n] = SpanDtxRow{spans[s].first_frame, spans[s].n_frames, spans[s].stream_id, (int32_t)wg, region};
+    ++n;
+    wg += (spans[s].n_frames + 1) / 2;
+    region += spans[s].n_frames;
+    if (wg > INT32_MAX) return -1;
+  }
+  *n_rows = n;
+  *frames = region;
+  return wg;
+}
+
+// mel rows and map for `frames` frames, counts for n_rows spans -- the worst case of a call, before anything is enqueued
+int span_dtx_ensure(lyra_hip_ctx* c, SpanSide& S, hipStream_t st_, long long frames, int n_rows) {
+  if (frames > S.dtx_cap) {
+    HIPCHK(c, hipStreamSynchronize(st_));
+    dfree(S.d_mel, S.d_map);
+    S.dtx_cap = 0;
+    if (dalloc(&S.d_mel, (size_t)frames * SPAN_MEL_ROW) != hipSuccess || dalloc(&S.d_map, (size_t)frames) != hipSuccess) {
+      dfree(S.d_mel, S.d_map);
+      (void)hipGetLastError();
+      return fail(c, LYRA_HIP_ENOMEM, "spans: %lld mel rows of scratch failed", frames);
+    }
+    S.dtx_cap = frames;
+  }
+  if (n_rows > S.counts_cap) {
+    HIPCHK(c, hipStreamSynchronize(st_));
+    if (S.h_counts) (void)hipHostFree(S.h_counts);
+    S.h_counts = S.d_counts = nullptr;
+    S.counts_cap = 0;
+    HIPCHK(c, hipHostMalloc((void**)&S.h_counts, (size_t)n_rows * sizeof(int32_t), hipHostMallocDefault));
+    HIPCHK(c, hipHostGetDevicePointer((void**)&S.d_counts, S.h_counts, 0));
+    S.counts_cap = n_rows;
+  }
+  return 0;
+}
+
+// NoiseEstimator::ReceiveSamples over every frame of the rows' spans on st_: the log-mel pass, then the scan.  side picks the
+// region, the filterbank and the constants as launch_noise does.  flag_out[frame] = v_noise / v_active.
+int launch_span_noise(lyra_hip_ctx* c, int side, hipStream_t st_, SpanSide& S, const SpanDtxRow* d_rows, int n_rows, long long wgs,
+                      const int16_t* d_pcm16, int32_t* d_flag_out, int v_noise, int v_active, long long* d_map) {
+  uint8_t* region = c->sm.base[side == 0 ? st::R_NOISE_E : st::R_NOISE_D];
+  const int rate = side == 0 ? c->enc_noise_rate : 16000;
+  const MelP* melp = c->model.d_mel_rate[rate == 8000 ? 0 : rate == 32000 ? 2 : rate == 48000 ? 3 : 1];
+  hipLaunchKernelGGL(span_logmel_kernel, dim3((unsigned)wgs), dim3(256), logmel_lds_bytes(), st_, melp, d_rows, n_rows, region,
+                     d_pcm16, S.d_mel);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(span_noise_scan_kernel, dim3(n_rows), dim3(64), 0, st_, noise_params(rate), d_rows, n_rows, region,
+                     (const float*)S.d_mel, d_flag_out, v_noise, v_active, d_map, S.d_counts);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int spans_dtx_call_dev(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                       const int16_t* d_pcm_ext, int rate, int16_t* d_pcm16, int num_bits, uint8_t* d_packets,
+                       int32_t* d_packet_bytes) {
+  const char* what = "encode_spans_dtx";
+  if (!c) return LYRA_HIP_EINVAL;
+  int rc = check_bits(c, num_bits);
+  if (rc) return rc;
+  if (!span_rate_ok(rate)) return fail(c, LYRA_HIP_EINVAL, "%s: sample rate %d Hz (8000 / 16000 / 32000 / 48000)", what, rate);
+  if (c->enc_noise_rate != rate)   // as lyra_hip_encode_ext_dev: the DTX estimator is created at the encoder's external rate
+    return fail(c, LYRA_HIP_EINVAL, "%s: DTX at %d Hz but the encoder-side noise estimator is set up for %d Hz "
+                "(call lyra_hip_set_encoder_sample_rate(%d) first)", what, rate, c->enc_noise_rate, rate);
+  if (n_lanes < 0 || (n_lanes && !lane_ids)) return fail(c, LYRA_HIP_EINVAL, "%s: bad lane list", what);
+  SpanPlan dry;   // ids, lanes and frame ranges: the planner's rules, on the spans as given
+  if ((rc = span_plan_checked(c, sp::SIDE_ENC, spans, n_spans, lane_ids, n_lanes, &dry, what))) return rc;
+  if (!d_packet_bytes || (dry.end_frame && (!d_pcm_ext || !d_packets))) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
+  if (reinterpret_cast<uintptr_t>(d_pcm_ext) & 15) return fail(c, LYRA_HIP_EINVAL, "%s: the PCM buffer must be 16-byte aligned", what);
+  SpanExt X;
+  X.rate = rate;
+  X.d_pcm16 = X.on() ? d_pcm16 : nullptr;
+  if (X.on() && ((dry.end_frame && !X.d_pcm16) || (reinterpret_cast<uintptr_t>(X.d_pcm16) & 15)))
+    return fail(c, LYRA_HIP_EINVAL, "%s: at %d Hz the 16 kHz buffer must be given, 16-byte aligned", what, rate);
+  int n_rs = 0, n_dx = 0;
+  long long frames = 0;
+  const long long rs_wgs = X.on() ? span_rs_rows(spans, n_spans, nullptr, &n_rs) : 0;
+  const long long lm_wgs = span_dtx_rows(spans, n_spans, nullptr, &n_dx, &frames);
+  if (rs_wgs < 0 || lm_wgs < 0) return fail(c, LYRA_HIP_EINVAL, "%s: too many frames for one pass", what);
+  DEVSCOPE(c);
+  if (!c->span_calls) c->span_calls = new SpanCalls();
+  SpanSide& S = span_calls_of(c)->side[0];
+  hipStream_t st_ = c->se[0];
+  // all scratch for the worst case -- every frame active: at most one chunk per span and per lane -- before the first launch
+  const int rows_max = n_spans + n_lanes;
+  if ((rc = span_side_ensure(c, S, st_, rows_max, n_lanes + n_rs + n_dx))) return rc;
+  if ((rc = ensure_scratch(c, rows_max))) return rc;
+  if ((rc = span_dtx_ensure(c, S, st_, std::max<long long>(frames, 1), std::max(n_dx, 1)))) return rc;
+  // upload 1, behind the batch rows' place: the lanes' reset rows, the resampler's rows, the estimator's rows
+  SpanRow* h_fix = S.h_rows + rows_max;
+  for (int l = 0; l < n_lanes; ++l) h_fix[l] = SpanRow{lane_ids[l], 0, 0, -1, 0, 0, 0};
+  if (n_rs) span_rs_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(h_fix + n_lanes), &n_rs);
+  span_dtx_rows(spans, n_spans, reinterpret_cast<SpanDtxRow*>(h_fix + n_lanes + n_rs), &n_dx, &frames);
+  const SpanRow* d_fix = S.d_rows + rows_max;
+  const SpanRsRow* d_rs_rows = reinterpret_cast<const SpanRsRow*>(d_fix + n_lanes);
+  const SpanDtxRow* d_dx_rows = reinterpret_cast<const SpanDtxRow*>(d_fix + n_lanes + n_rs);
+  if ((rc = enc_side_begin(c, 0))) return rc;
+  if (n_lanes + n_rs + n_dx) {
+    HIPCHK(c, hipMemcpyAsync(S.d_rows + rows_max, h_fix, (size_t)(n_lanes + n_rs + n_dx) * sizeof(SpanRow), hipMemcpyHostToDevice,
+                             st_));
+    HIPCHK(c, hipEventRecord(S.ev_up, st_));
+    S.up_pending = true;
+  }
+  const int16_t* d_src16 = d_pcm_ext;
+  if (X.on()) {
+    if (n_rs && (rc = launch_span_resample(c, true, st_, d_rs_rows, n_rs, rs_wgs, rate, 16000, d_pcm_ext, X.d_pcm16))) return rc;
+    d_src16 = X.d_pcm16;
+  }
+  SpanPlan P;
+  std::vector<lyra_hip_span> compact((size_t)n_spans);
+  if (n_dx) {
+    if ((rc = launch_span_noise(c, 0, st_, S, d_dx_rows, n_dx, lm_wgs, d_src16, d_packet_bytes, 0, (num_bits + 7) / 8, S.d_map)))
+      return rc;
+    // the one host wait of the call: the plan depends on the decisions
+    HIPCHK(c, hipStreamSynchronize(st_));
+    S.up_pending = false;
+  }
+  {   // what the encoder sees of span s: its non-noise hops, at the start of its region of the map
+    long long region = 0;
+    int r = 0;
+    for (int s = 0; s < n_spans; ++s) {
+      compact[s] = lyra_hip_span{spans[s].stream_id, region, spans[s].n_frames ? (int64_t)S.h_counts[r++] : 0};
+      if (compact[s].n_frames < 0 || compact[s].n_frames > spans[s].n_frames)
+        return fail(c, LYRA_HIP_EHIP, "%s: the scan's count of span %d is out of range", what, s);
+      region += spans[s].n_frames;
+    }
+  }
+  if ((rc = span_plan_checked(c, sp::SIDE_ENC, compact.data(), n_spans, lane_ids, n_lanes, &P, what))) return rc;
+  const int rows = (int)P.chunks.size();
+  if (rows) {   // upload 2: the batch rows (the pinned rows in front of upload 1's, so neither waits for the other)
+    span_fill_rows(P, compact.data(), lane_ids, 0, S.h_rows);
+    HIPCHK(c, hipMemcpyAsync(S.d_rows, S.h_rows, (size_t)rows * sizeof(SpanRow), hipMemcpyHostToDevice, st_));
+    HIPCHK(c, hipEventRecord(S.ev_up, st_));
+    S.up_pending = true;
+  }
+  rc = span_run_steps(c, true, S, st_, P, S.h_rows, S.d_rows, d_fix, n_lanes, d_src16, num_bits, d_packets, S.d_map);
+  if (!rc) rc = enc_side_done(c, 0);
+  return rc;
+}
+
+// host-buffer form: frames 0 .. end - 1 of the buffers are staged; packet rows of noise frames read back as zeros
+int spans_dtx_call_host(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                        const int16_t* pcm_ext, int rate, int num_bits, uint8_t* packets, int32_t* packet_bytes) {
+  if (!c) return LYRA_HIP_EINVAL;
+  int rc = check_bits(c, num_bits);
+  if (rc) return rc;
+  if (!span_rate_ok(rate)) return fail(c, LYRA_HIP_EINVAL, "encode_spans_dtx: sample rate %d Hz (8000 / 16000 / 32000 / 48000)", rate);
+  int64_t end = 0;
+  for (int s = 0; spans && s < n_spans; ++s)
+    if (spans[s].first_frame >= 0 && spans[s].n_frames >= 0) end = std::max<int64_t>(end, spans[s].first_frame + spans[s].n_frames);
+  if (!packet_bytes || (end && (!pcm_ext || !packets))) return fail(c, LYRA_HIP_EINVAL, "encode_spans_dtx: null pointer");
+  DEVSCOPE(c);
+  const size_t nbytes = (size_t)(num_bits + 7) / 8, pcm_b = (size_t)rate / 50 * 2;
+  int16_t *d_in = nullptr, *d_p16 = nullptr;
+  uint8_t* d_out = nullptr;
+  int32_t* d_pb = nullptr;
+  const size_t e1 = (size_t)std::max<int64_t>(end, 1);
+  if (dalloc(&d_in, e1 * pcm_b / 2) != hipSuccess || dalloc(&d_out, e1 * nbytes) != hipSuccess || dalloc(&d_pb, e1) != hipSuccess ||
+      (rate != 16000 && dalloc(&d_p16, e1 * 320) != hipSuccess)) {
+    dfree(d_in, d_out, d_pb, d_p16);
+    return fail(c, LYRA_HIP_ENOMEM, "encode_spans_dtx: staging %lld frames failed", (long long)end);
+  }
+  hipStream_t st_ = c->se[0];
+  rc = 0;
+  if (end && (hipMemcpy(d_in, pcm_ext, (size_t)end * pcm_b, hipMemcpyHostToDevice) != hipSuccess ||
+              hipMemset(d_out, 0, (size_t)end * nbytes) != hipSuccess))
+    rc = fail(c, LYRA_HIP_EHIP, "encode_spans_dtx: upload failed");
+  if (!rc) rc = spans_dtx_call_dev(c, spans, n_spans, lane_ids, n_lanes, d_in, rate, d_p16, num_bits, d_out, d_pb);
+  if (!rc && hipStreamSynchronize(st_) != hipSuccess) rc = fail(c, LYRA_HIP_EHIP, "encode_spans_dtx: synchronise failed");
+  for (int s = 0; !rc && s < n_spans; ++s) {
+    const int64_t f = spans[s].first_frame, n = spans[s].n_frames;
+    if (n && (hipMemcpy(packets + f * nbytes, d_out + f * nbytes, n * nbytes, hipMemcpyDeviceToHost) != hipSuccess ||
+              hipMemcpy(packet_bytes + f, d_pb + f, n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess))
+      rc = fail(c, LYRA_HIP_EHIP, "encode_spans_dtx: download failed");
+  }
+  if (rc) (void)hipStreamSynchronize(st_);
+  dfree(d_in, d_out, d_pb, d_p16);
+  return rc;
+}
+
+int noise_spans_call_dev(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int n_spans, const int16_t* d_pcm16,
+                         int32_t* d_is_noise) {
+  const char* what = "noise_spans";
+  if (!c) return LYRA_HIP_EINVAL;
+  if (side != 0 && side != 1) return fail(c, LYRA_HIP_EINVAL, "%s: bad side", what);
+  SpanPlan dry;
+  int rc = span_plan_checked(c, side, spans, n_spans, nullptr, 0, &dry, what);
+  if (rc) return rc;
+  if (dry.end_frame && (!d_pcm16 || !d_is_noise)) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
+  if (reinterpret_cast<uintptr_t>(d_pcm16) & 15) return fail(c, LYRA_HIP_EINVAL, "%s: the PCM buffer must be 16-byte aligned", what);
+  int n_dx = 0;
+  long long frames = 0;
+  const long long lm_wgs = span_dtx_rows(spans, n_spans, nullptr, &n_dx, &frames);
+  if (lm_wgs < 0) return fail(c, LYRA_HIP_EINVAL, "%s: too many frames for one pass", what);
+  if (!n_dx) return 0;
+  DEVSCOPE(c);
+  if (!c->span_calls) c->span_calls = new SpanCalls();
+  SpanSide& S = span_calls_of(c)->side[side];
+  hipStream_t st_ = side == 0 ? c->se[0] : c->sd[0];
+  if ((rc = span_side_ensure(c, S, st_, 1, n_dx))) return rc;
+  if ((rc = span_dtx_ensure(c, S, st_, frames, n_dx))) return rc;
+  span_dtx_rows(spans, n_spans, reinterpret_cast<SpanDtxRow*>(S.h_rows), &n_dx, &frames);
+  if ((rc = side == 0 ? enc_side_begin(c, 0) : dec_side_begin(c, 0))) return rc;
+  if (side == 1 && (rc = wait_noise_stream(c))) return rc;   // the decoder-side slots may have been touched on the noise stream
+  HIPCHK(c, hipMemcpyAsync(S.d_rows, S.h_rows, (size_t)n_dx * sizeof(SpanRow), hipMemcpyHostToDevice, st_));
+  HIPCHK(c, hipEventRecord(S.ev_up, st_));
+  S.up_pending = true;
+  rc = launch_span_noise(c, side, st_, S, reinterpret_cast<const SpanDtxRow*>(S.d_rows), n_dx, lm_wgs, d_pcm16, d_is_noise, 1, 0,
+                         nullptr);
+  if (side == 0) {
+    if (!rc) rc = enc_side_done(c, 0);
+  } else {
+    if (!rc) rc = dec_side_done(c, 0, 1);
+    c->n_dec_calls++;
+  }
+  return rc;
+}
+
+int noise_spans_call_host(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int n_spans, const int16_t* pcm16,
+                          int32_t* is_noise) {
+  if (!c) return LYRA_HIP_EINVAL;
+  if (side != 0 && side != 1) return fail(c, LYRA_HIP_EINVAL, "noise_spans: bad side");
+  int64_t end = 0;
+  for (int s = 0; spans && s < n_spans; ++s)
+    if (spans[s].first_frame >= 0 && spans[s].n_frames >= 0) end = std::max<int64_t>(end, spans[s].first_frame + spans[s].n_frames);
+  if (end && (!pcm16 || !is_noise)) return fail(c, LYRA_HIP_EINVAL, "noise_spans: null pointer");
+  DEVSCOPE(c);
+  int16_t* d_in = nullptr;
+  int32_t* d_flag = nullptr;
+  const size_t e1 = (size_t)std::max<int64_t>(end, 1);
+  if (dalloc(&d_in, e1 * 320) != hipSuccess || dalloc(&d_flag, e1) != hipSuccess) {
+    dfree(d_in, d_flag);
+    return fail(c, LYRA_HIP_ENOMEM, "noise_spans: staging %lld frames failed", (long long)end);
+  }
+  hipStream_t st_ = side == 0 ? c->se[0] : c->sd[0];
+  int rc = 0;
+  if (end && hipMemcpy(d_in, pcm16, (size_t)end * 640, hipMemcpyHostToDevice) != hipSuccess)
+    rc = fail(c, LYRA_HIP_EHIP, "noise_spans: upload failed");
+  if (!rc) rc = noise_spans_call_dev(c, side, spans, n_spans, d_in, d_flag);
+  if (!rc && hipStreamSynchronize(st_) != hipSuccess) rc = fail(c, LYRA_HIP_EHIP, "noise_spans: synchronise failed");
+  for (int s = 0; !rc && s < n_spans; ++s)
+    if (spans[s].n_frames && hipMemcpy(is_noise + spans[s].first_frame, d_flag + spans[s].first_frame,
+                                       spans[s].n_frames * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+      rc = fail(c, LYRA_HIP_EHIP, "noise_spans: download failed");
+  if (rc) (void)hipStreamSynchronize(st_);
+  dfree(d_in, d_flag);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -380,6 +661,28 @@ int lyra_hip_encode_spans_ext(lyra_hip_ctx* c, const lyra_hip_span* spans, int n
 int lyra_hip_decode_spans_ext(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                               const uint8_t* packets, int num_bits, int sample_rate_hz, int16_t* pcm_ext) {
   return spans_call_host(c, false, spans, n_spans, lane_ids, n_lanes, packets, num_bits, pcm_ext, sample_rate_hz);
+}
+
+int lyra_hip_encode_spans_dtx_dev(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                                  const int16_t* d_pcm_ext, int sample_rate_hz, int16_t* d_pcm16, int num_bits,
+                                  uint8_t* d_packets, int32_t* d_packet_bytes) {
+  return spans_dtx_call_dev(c, spans, n_spans, lane_ids, n_lanes, d_pcm_ext, sample_rate_hz, d_pcm16, num_bits, d_packets,
+                            d_packet_bytes);
+}
+
+int lyra_hip_encode_spans_dtx(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                              const int16_t* pcm_ext, int sample_rate_hz, int num_bits, uint8_t* packets, int32_t* packet_bytes) {
+  return spans_dtx_call_host(c, spans, n_spans, lane_ids, n_lanes, pcm_ext, sample_rate_hz, num_bits, packets, packet_bytes);
+}
+
+int lyra_hip_noise_spans_dev(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int n_spans, const int16_t* d_pcm16,
+                             int32_t* d_is_noise) {
+  return noise_spans_call_dev(c, side, spans, n_spans, d_pcm16, d_is_noise);
+}
+
+int lyra_hip_noise_spans(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int n_spans, const int16_t* pcm16,
+                         int32_t* is_noise) {
+  return noise_spans_call_host(c, side, spans, n_spans, pcm16, is_noise);
 }
 
 }  // extern "C"

@@ -23,7 +23,8 @@ __device__ __forceinline__ bool span_unit(int B, int units, int* r, int* u) {
 
 __global__ __launch_bounds__(256) void span_gather_kernel(const SpanRow* __restrict__ rows, int B, int step,
                                                            const uint8_t* __restrict__ frames, int row_bytes, int unit16,
-                                                           uint8_t* __restrict__ dense, int32_t* __restrict__ step_ids) {
+                                                           uint8_t* __restrict__ dense, int32_t* __restrict__ step_ids,
+                                                           const long long* __restrict__ map) {
   const int units = unit16 ? row_bytes >> 4 : row_bytes;
   int r, u;
   if (!span_unit(B, units, &r, &u)) return;
@@ -31,7 +32,8 @@ __global__ __launch_bounds__(256) void span_gather_kernel(const SpanRow* __restr
   const bool runs = step < row.n_steps;
   if (u == 0) step_ids[r] = runs ? row.id : -1;
   if (!runs) return;
-  const uint8_t* src = frames + (size_t)(row.frame0 + step) * row_bytes;
+  const long long at = row.frame0 + step;   // (map: a compacted index, lyra_hip_encode_spans_dtx_dev)
+  const uint8_t* src = frames + (size_t)(map ? map[at] : at) * row_bytes;
   uint8_t* dst = dense + (size_t)r * row_bytes;
   if (unit16) st16(dst + u * 16, ld16(src + u * 16));
   else dst[u] = src[u];
@@ -39,14 +41,16 @@ __global__ __launch_bounds__(256) void span_gather_kernel(const SpanRow* __restr
 
 __global__ __launch_bounds__(256) void span_scatter_kernel(const SpanRow* __restrict__ rows, int B, int step,
                                                             const uint8_t* __restrict__ dense, int row_bytes, int unit16,
-                                                            uint8_t* __restrict__ frames) {
+                                                            uint8_t* __restrict__ frames,
+                                                            const long long* __restrict__ map) {
   const int units = unit16 ? row_bytes >> 4 : row_bytes;
   int r, u;
   if (!span_unit(B, units, &r, &u)) return;
   const SpanRow row = rows[r];
   if (step >= row.n_steps || step < row.n_warm) return;   // ended, or still warming up: nothing is stored
   const uint8_t* src = dense + (size_t)r * row_bytes;
-  uint8_t* dst = frames + (size_t)(row.frame0 + step) * row_bytes;
+  const long long at = row.frame0 + step;
+  uint8_t* dst = frames + (size_t)(map ? map[at] : at) * row_bytes;
   if (unit16) st16(dst + u * 16, ld16(src + u * 16));
   else dst[u] = src[u];
 }

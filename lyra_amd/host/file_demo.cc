@@ -1,9 +1,11 @@
 // file_demo.cc -- batched encoder_main / decoder_main (cli_example/encoder_main.cc, decoder_main.cc):
-//   file_demo [--time-parallel[=<lanes>]] [--decode-rate=<hz>] <model_dir> <bitrate> <out_dir> <a.wav> [<b.wav> ...]
+//   file_demo [--time-parallel[=<lanes>]] [--decode-rate=<hz>] [--dtx] <model_dir> <bitrate> <out_dir> <a.wav> [<b.wav> ...]
 // writes <out_dir>/<stem>.lyra and <out_dir>/<stem>_decoded.wav for every input, all files transcoded together.
 // The encoder's sample rate is the WAVs' (8, 16, 32 or 48 kHz, one per batch); --decode-rate: that of the decoded WAVs (16000).
 // --time-parallel: through EncodeFilesTimeParallel / DecodeFilesTimeParallel (long files cut into chunks that run side by
 // side; the same bytes).
+// --dtx: encoder_main's --enable_dtx; noise hops append nothing to the .lyra file.  Such a file carries no framing (the
+// reference's format), so it is not decoded: only <stem>.lyra is written.
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -27,19 +29,22 @@ int main(int argc, char** argv) {
   if (argc == 4 && std::string(argv[1]) == "--selftest-wav") return SelftestWav(argv[2], argv[3]);
   int lanes = -1;   // < 0: hop by hop
   int decode_rate = 16000;
+  bool dtx = false;
   for (; argc > 1 && std::string(argv[1]).rfind("--", 0) == 0; --argc, ++argv) {
     const std::string flag = argv[1];
     if (flag.rfind("--time-parallel", 0) == 0) {
       lanes = flag.size() > 16 && flag[15] == '=' ? std::atoi(flag.c_str() + 16) : kDefaultSpanLanes;
     } else if (flag.rfind("--decode-rate=", 0) == 0) {
       decode_rate = std::atoi(flag.c_str() + 14);
+    } else if (flag == "--dtx") {
+      dtx = true;
     } else {
       argc = 0;   // unknown flag: usage
       break;
     }
   }
   if (argc < 5) {
-    std::fprintf(stderr, "usage: file_demo [--time-parallel[=lanes]] [--decode-rate=hz] model_dir bitrate out_dir a.wav [b.wav ...]\n");
+    std::fprintf(stderr, "usage: file_demo [--time-parallel[=lanes]] [--decode-rate=hz] [--dtx] model_dir bitrate out_dir a.wav [b.wav ...]\n");
     return 2;
   }
   const fs::path model_dir = argv[1], out_dir = argv[3];
@@ -52,13 +57,13 @@ int main(int argc, char** argv) {
     decoded.push_back(out_dir / (w.stem().string() + "_decoded.wav"));
   }
   if (EncodeFiles(wavs, lyras, 1234, false, false, model_dir)) return 3;      // unsupported bitrate
-  if (EncodeFiles(wavs, lyras, bitrate, false, true, model_dir)) return 3;    // DTX is outside this build
+  if (EncodeFiles(wavs, lyras, bitrate, true, false, model_dir)) return 3;    // preprocessing is outside this build
   if (lanes >= 0) {
-    if (!EncodeFilesTimeParallel(wavs, lyras, bitrate, false, false, model_dir, lanes)) return 4;
-    if (!DecodeFilesTimeParallel(lyras, decoded, decode_rate, bitrate, model_dir, lanes)) return 5;
+    if (!EncodeFilesTimeParallel(wavs, lyras, bitrate, false, dtx, model_dir, lanes)) return 4;
+    if (!dtx && !DecodeFilesTimeParallel(lyras, decoded, decode_rate, bitrate, model_dir, lanes)) return 5;
     return 0;
   }
-  if (!EncodeFiles(wavs, lyras, bitrate, false, false, model_dir)) return 4;
-  if (!DecodeFiles(lyras, decoded, decode_rate, bitrate, model_dir)) return 5;
+  if (!EncodeFiles(wavs, lyras, bitrate, false, dtx, model_dir)) return 4;
+  if (!dtx && !DecodeFiles(lyras, decoded, decode_rate, bitrate, model_dir)) return 5;
   return 0;
 }

@@ -19,6 +19,7 @@
 #pragma weak lyra_hip_span_warmup_frames
 #pragma weak lyra_hip_encode_spans_ext
 #pragma weak lyra_hip_decode_spans_ext
+#pragma weak lyra_hip_encode_spans_dtx
 
 namespace chromemedia {
 namespace codec {
@@ -38,10 +39,11 @@ bool CheckScope(int num_channels, int sample_rate_hz, bool enable_preprocessing,
     LOG(ERROR) << "Sample rate " << sample_rate_hz << " Hz is not supported by codec. It needs to be 8000, 16000, 32000 or 48000.";
     return false;
   }
-  if (enable_preprocessing || enable_dtx) {
-    LOG(ERROR) << "Preprocessing / DTX are not part of this build.";
+  if (enable_preprocessing) {
+    LOG(ERROR) << "Preprocessing is not part of this build.";
     return false;
   }
+  (void)enable_dtx;   // LyraEncoder's DTX: lyra_hip_encode_dtx per hop / lyra_hip_encode_spans_dtx
   return true;
 }
 
@@ -103,16 +105,23 @@ bool WriteWav16(const ghc::filesystem::path& path, const std::vector<int16_t>& s
 
 bool EncodeWavs(const std::vector<std::vector<int16_t>>& wav_data, int num_channels, int sample_rate_hz, int bitrate,
                 bool enable_preprocessing, bool enable_dtx, const ghc::filesystem::path& model_path,
-                std::vector<std::vector<uint8_t>>* encoded_features, int device) {
+                std::vector<std::vector<uint8_t>>* encoded_features, int device,
+                std::vector<std::vector<int32_t>>* packet_sizes) {
   if (!CheckScope(num_channels, sample_rate_hz, enable_preprocessing, enable_dtx)) return false;
   const int num_bits = BatchBitrateToNumQuantizedBits(bitrate);
   if (num_bits < 0) { LOG(ERROR) << "Bitrate " << bitrate << " bps is not supported by codec."; return false; }
   const int n = (int)wav_data.size();
   encoded_features->assign(n, {});
+  if (packet_sizes) packet_sizes->assign(n, {});
   if (n == 0) return true;
   Ctx ctx;
   if (lyra_hip_create(model_path.string().c_str(), device, n, LYRA_HIP_REQUANT_DEFAULT, &ctx.c) != 0) {
     LOG(ERROR) << "Could not create lyra encoder: " << lyra_hip_last_error(nullptr);
+    return false;
+  }
+  // a DTX LyraEncoder hands its NoiseEstimator the files' rate (lyra_encoder.cc:82-85)
+  if (enable_dtx && lyra_hip_set_encoder_sample_rate(ctx.c, sample_rate_hz) != 0) {
+    LOG(ERROR) << "Could not set up the noise estimator: " << lyra_hip_last_error(ctx.c);
     return false;
   }
   const int packet_size = BatchBitrateToPacketSize(bitrate);
@@ -123,6 +132,7 @@ bool EncodeWavs(const std::vector<std::vector<int16_t>>& wav_data, int num_chann
   std::vector<int32_t> ids;
   std::vector<int16_t> pcm, pcm16;
   std::vector<uint8_t> packets;
+  std::vector<int32_t> sizes;
   for (size_t hop = 0; hop < max_hops; ++hop) {  // streams with a full hop left (encoder_main_lib.cc:71-73)
     ids.clear();
     pcm.clear();
@@ -142,14 +152,17 @@ bool EncodeWavs(const std::vector<std::vector<int16_t>>& wav_data, int num_chann
       }
       hop16 = pcm16.data();
     }
-    if (lyra_hip_encode(ctx.c, ids.data(), (int)ids.size(), hop16, num_bits, packets.data()) != 0) {
+    sizes.assign(ids.size(), packet_size);
+    if ((enable_dtx ? lyra_hip_encode_dtx(ctx.c, ids.data(), (int)ids.size(), hop16, num_bits, packets.data(), sizes.data())
+                    : lyra_hip_encode(ctx.c, ids.data(), (int)ids.size(), hop16, num_bits, packets.data())) != 0) {
       LOG(ERROR) << "Unable to encode features starting at samples at byte " << hop * hop_samples << ": "
                  << lyra_hip_last_error(ctx.c);
       return false;
     }
-    for (size_t k = 0; k < ids.size(); ++k) {
+    for (size_t k = 0; k < ids.size(); ++k) {   // the empty packet of a noise hop appends nothing (encoder_main_lib.cc:77-88)
       auto& dst = (*encoded_features)[ids[k]];
-      dst.insert(dst.end(), packets.begin() + k * packet_size, packets.begin() + (k + 1) * packet_size);
+      dst.insert(dst.end(), packets.begin() + k * packet_size, packets.begin() + k * packet_size + sizes[k]);
+      if (packet_sizes) (*packet_sizes)[ids[k]].push_back(sizes[k]);
     }
   }
   return true;
@@ -313,18 +326,25 @@ bool HaveSpanCalls(int sample_rate_hz) {
   }
   return true;
 }
+bool HaveSpanDtxCall() {
+  if (lyra_hip_encode_spans_dtx) return true;
+  LOG(ERROR) << "This build of the lyra_hip library has no time-parallel span call with DTX.";
+  return false;
+}
 
 }  // namespace
 
 bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, int num_channels, int sample_rate_hz,
                             int bitrate, bool enable_preprocessing, bool enable_dtx,
                             const ghc::filesystem::path& model_path, std::vector<std::vector<uint8_t>>* encoded_features,
-                            int num_lanes, int device) {
+                            int num_lanes, int device, std::vector<std::vector<int32_t>>* packet_sizes) {
   if (!CheckScope(num_channels, sample_rate_hz, enable_preprocessing, enable_dtx) || !HaveSpanCalls(sample_rate_hz)) return false;
+  if (enable_dtx && !HaveSpanDtxCall()) return false;
   const int num_bits = BatchBitrateToNumQuantizedBits(bitrate);
   if (num_bits < 0) { LOG(ERROR) << "Bitrate " << bitrate << " bps is not supported by codec."; return false; }
   const int n = (int)wav_data.size();
   encoded_features->assign(n, {});
+  if (packet_sizes) packet_sizes->assign(n, {});
   if (n == 0) return true;
   std::vector<int16_t> pcm;
   const SpanJob job = MakeSpanJob(wav_data, (size_t)sample_rate_hz / 50, LYRA_HIP_SIDE_ENCODER, num_lanes, &pcm);
@@ -335,6 +355,23 @@ bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, i
   }
   const size_t packet_size = (size_t)BatchBitrateToPacketSize(bitrate);
   std::vector<uint8_t> packets((size_t)job.frames * packet_size);
+  if (enable_dtx) {   // the non-empty packets of every file, in order (encoder_main_lib.cc:77-88)
+    std::vector<int32_t> sizes((size_t)job.frames, 0);
+    if (lyra_hip_set_encoder_sample_rate(ctx.c, sample_rate_hz) != 0 ||
+        lyra_hip_encode_spans_dtx(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), pcm.data(), sample_rate_hz,
+                                  num_bits, packets.data(), sizes.data()) != 0) {
+      LOG(ERROR) << "Unable to encode features: " << lyra_hip_last_error(ctx.c);
+      return false;
+    }
+    for (int i = 0; i < n; ++i) {
+      auto& dst = (*encoded_features)[i];
+      for (int64_t f = job.spans[i].first_frame; f < job.spans[i].first_frame + job.spans[i].n_frames; ++f) {
+        dst.insert(dst.end(), packets.begin() + f * packet_size, packets.begin() + f * packet_size + sizes[f]);
+        if (packet_sizes) (*packet_sizes)[i].push_back(sizes[f]);
+      }
+    }
+    return true;
+  }
   // (16 kHz stays on the plain call: it also runs against a library that has no `_ext` calls yet)
   if ((sample_rate_hz == kBatchInternalSampleRateHz
            ? lyra_hip_encode_spans(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), pcm.data(), num_bits,
@@ -347,6 +384,8 @@ bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, i
   for (int i = 0; i < n; ++i)
     (*encoded_features)[i].assign(packets.begin() + job.spans[i].first_frame * packet_size,
                                   packets.begin() + (job.spans[i].first_frame + job.spans[i].n_frames) * packet_size);
+  if (packet_sizes)
+    for (int i = 0; i < n; ++i) (*packet_sizes)[i].assign((size_t)job.spans[i].n_frames, (int32_t)packet_size);
   return true;
 }
 

@@ -8,7 +8,11 @@
 // Scope: mono 16-bit WAV at 8, 16, 32 or 48 kHz like the reference's EncodeFile / DecodeFile (the files of one batch share
 // their rate); at a rate other than 16 kHz every stream runs through its own resampler on the device, lyra_hip_resample per
 // hop or, in the time-parallel forms, one pass inside lyra_hip_encode_spans_ext / lyra_hip_decode_spans_ext.  A hop is
-// sample_rate_hz / 50 samples.  No preprocessing / DTX / packet-loss simulation: those are refused.
+// sample_rate_hz / 50 samples.  enable_dtx is encoder_main's --enable_dtx (lyra_hip_set_encoder_sample_rate(rate), then
+// lyra_hip_resample + lyra_hip_encode_dtx per hop or, time-parallel, lyra_hip_encode_spans_dtx): a noise hop's empty packet
+// appends nothing, so the output is the concatenation of the non-empty packets (encoder_main_lib.cc:77-88) and, like the
+// reference's, cannot be cut into hops again without the sizes -- packet_sizes returns them.  Such files are not decoded here.
+// No preprocessing / packet-loss simulation: those are refused.
 #ifndef LYRA_AMD_HOST_LYRA_FILE_CODEC_H_
 #define LYRA_AMD_HOST_LYRA_FILE_CODEC_H_
 #include <cstdint>
@@ -19,10 +23,12 @@
 namespace chromemedia {
 namespace codec {
 
-// EncodeWav for a batch: wav_data[i] -> encoded_features[i] (packets of stream i, oldest first).
+// EncodeWav for a batch: wav_data[i] -> encoded_features[i] (packets of stream i, oldest first).  packet_sizes (optional):
+// (*packet_sizes)[i][h] = bytes hop h of stream i added (0: the empty packet of a DTX noise hop).
 bool EncodeWavs(const std::vector<std::vector<int16_t>>& wav_data, int num_channels, int sample_rate_hz, int bitrate,
                 bool enable_preprocessing, bool enable_dtx, const ghc::filesystem::path& model_path,
-                std::vector<std::vector<uint8_t>>* encoded_features, int device = 0);
+                std::vector<std::vector<uint8_t>>* encoded_features, int device = 0,
+                std::vector<std::vector<int32_t>>* packet_sizes = nullptr);
 
 // EncodeFile for a batch: wav_paths[i] -> output_paths[i].
 bool EncodeFiles(const std::vector<ghc::filesystem::path>& wav_paths,
@@ -53,7 +59,8 @@ constexpr int kDefaultSpanLanes = 4096;
 bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, int num_channels, int sample_rate_hz,
                             int bitrate, bool enable_preprocessing, bool enable_dtx,
                             const ghc::filesystem::path& model_path, std::vector<std::vector<uint8_t>>* encoded_features,
-                            int num_lanes = kDefaultSpanLanes, int device = 0);
+                            int num_lanes = kDefaultSpanLanes, int device = 0,
+                            std::vector<std::vector<int32_t>>* packet_sizes = nullptr);
 bool EncodeFilesTimeParallel(const std::vector<ghc::filesystem::path>& wav_paths,
                              const std::vector<ghc::filesystem::path>& output_paths, int bitrate, bool enable_preprocessing,
                              bool enable_dtx, const ghc::filesystem::path& model_path, int num_lanes = kDefaultSpanLanes,

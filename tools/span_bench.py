@@ -9,6 +9,13 @@ lyra_hip_encode / lyra_hip_decode + lyra_hip_resample per hop.  A third record, 
 span_resample_kernel in the device time of one encode + decode span call: this script runs its device leg once more as a child
 under `rocprofv3 --kernel-trace --stats` (a run of its own, so the timed legs are not traced).
 
+--dtx (with or without --rate): encode only, LyraEncoder's DTX on a half-silent recording (two seconds of speech, two of digital
+silence, in turns).  dtx_transcode times lyra_hip_encode_spans_dtx_dev on device buffers (`verified`: a prefix of packets and
+packet sizes against lyra_hip_resample + lyra_hip_encode_dtx per hop on a twin context); dtx_file_transcode times file_demo --dtx
+with --time-parallel (EncodeWavsTimeParallel(enable_dtx)) against hop by hop (EncodeWavs(enable_dtx)) as whole processes, `verified`:
+the same .lyra; kernel_share gives the part of span_noise_scan_kernel -- the serial floor of the call -- and of span_logmel_kernel
+in the summed kernel time of the device leg.
+
 Records, appended to --out:
   span_transcode   lyra_hip_encode_spans_dev + lyra_hip_decode_spans_dev on device buffers, one stream of --hops hops with
                    --lanes lanes: wall time per direction (after a warm call), useful frames/s (the recording's hops, warm-up
@@ -42,6 +49,92 @@ def recording(hops, rate=16000):
     rng = np.random.default_rng(7)
     x = src[np.arange(n) % src.size] * (0.6 + 0.4 * np.sin(np.arange(n) * 1e-5)) + rng.integers(-60, 61, n)
     return np.clip(x, -32768, 32767).astype(np.int16).reshape(hops, rate // 50)
+
+
+def half_silent(pcm, rate):
+    """two seconds of the recording, two of digital silence, in turns"""
+    out = pcm.copy()
+    for at in range(100, out.shape[0], 200):
+        out[at:at + 100] = 0
+    return out
+
+
+def dtx_device_leg(args, pcm):
+    import torch
+    import lyra_amd
+    from lyra_amd import codec
+    dev = torch.device("cuda", 0)
+    hops, ext = pcm.shape[0], args.rate != 16000
+    ctx = lyra_amd.LyraHip(device=0, max_streams=args.lanes + 1, requant="xnnpack")
+    ctx.set_encoder_sample_rate(args.rate)
+    lanes = np.arange(1, args.lanes + 1, dtype=np.int32)
+    spans = [(0, 0, hops)]
+    d_pcm = torch.from_numpy(pcm).to(dev)
+    d_pk = torch.zeros((hops, codec.packet_size(args.bits)), dtype=torch.uint8, device=dev)
+    d_nb = torch.zeros(hops, dtype=torch.int32, device=dev)
+    d_p16 = torch.zeros((hops, 320), dtype=torch.int16, device=dev) if ext else None
+    times, front = [], []
+    for rep in range(args.reps + 1):   # rep 0 warms (allocations, code)
+        ctx.reset()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ctx.encode_spans_dtx_dev(spans, d_pcm, args.bits, d_pk, d_nb, lanes, sample_rate_hz=args.rate, d_pcm16=d_p16)
+        ctx.synchronize()
+        if rep:
+            times.append(time.perf_counter() - t0)
+    nb = d_nb.cpu().numpy()
+    for rep in range(0 if args.device_leg_only else args.reps):   # the estimator alone (log-mel pass + scan) on the call's 16 kHz audio
+        ctx.reset()
+        src16 = d_p16 if ext else d_pcm
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ctx.noise_spans_dev(spans, src16, d_nb, side="encoder")
+        ctx.synchronize()
+        front.append(time.perf_counter() - t0)
+    pk = d_pk.cpu().numpy()
+    twin = lyra_amd.LyraHip(device=0, max_streams=1, requant="xnnpack")
+    twin.set_encoder_sample_rate(args.rate)
+    n, ok = min(hops, args.verify_hops), True
+    for h in range(n):
+        x16 = twin.resample(pcm[h:h + 1], args.rate, 16000, [0], side="encoder") if ext else pcm[h:h + 1]
+        p, size = twin.encode_dtx(x16, args.bits, [0])
+        ok = ok and size[0] == nb[h] and (size[0] == 0 or np.array_equal(p[0], pk[h]))
+    t, f = float(np.median(times)), float(np.median(front)) if front else 0.0
+    return dict(kind="dtx_transcode", rate=args.rate, hops=hops, lanes=int(args.lanes), bits=args.bits, active_hops=int((nb > 0).sum()),
+                encode_s=round(t, 5), encode_frames_per_s=round(hops / t), estimator_s=round(f, 5), estimator_share=round(f / t, 4),
+                reps=args.reps, verified=bool(ok), verified_hops=n)
+
+
+def dtx_file_leg(args, pcm):
+    import lyra_amd
+    demo = os.path.join(ROOT, "lyra_amd", "file_demo")
+    bitrate = {64: 3200, 120: 6000, 184: 9200}[args.bits]
+    hops = min(pcm.shape[0], args.file_hops) if args.file_hops else pcm.shape[0]
+    rec = dict(kind="dtx_file_transcode", rate=args.rate, hops=hops, bits=args.bits, lanes=int(args.lanes))
+    with tempfile.TemporaryDirectory() as tmp:
+        wav = os.path.join(tmp, "recording.wav")
+        with wave.open(wav, "wb") as w:
+            w.setnchannels(1); w.setsampwidth(2); w.setframerate(args.rate)
+            w.writeframes(pcm[:hops].tobytes())
+        outs = {}
+        for name, flag in (("time_parallel", ["--time-parallel=%d" % args.lanes]), ("hop_by_hop", [])):
+            out_dir = os.path.join(tmp, name)
+            os.mkdir(out_dir)
+            t0 = time.perf_counter()
+            r = subprocess.run([demo, *flag, "--dtx", lyra_amd.default_model_dir(), str(bitrate), out_dir, wav],
+                               capture_output=True, text=True, timeout=args.file_timeout)
+            rec[name + "_s"] = round(time.perf_counter() - t0, 3)
+            if r.returncode != 0:
+                rec[name + "_error"] = r.stderr[-300:]
+            outs[name] = os.path.join(out_dir, "recording.lyra")
+            print(json.dumps({name + "_s": rec[name + "_s"]}), flush=True)
+        a, b = outs["time_parallel"], outs["hop_by_hop"]
+        rec["verified"] = bool(os.path.isfile(a) and os.path.isfile(b) and open(a, "rb").read() == open(b, "rb").read())
+        if os.path.isfile(a):
+            rec["lyra_bytes"] = os.path.getsize(a)
+    if rec.get("time_parallel_s") and rec.get("hop_by_hop_s"):
+        rec["hop_by_hop_over_time_parallel"] = round(rec["hop_by_hop_s"] / rec["time_parallel_s"], 2)
+    return rec
 
 
 def device_leg(args, pcm):
@@ -133,25 +226,31 @@ def kernel_share_leg(args):
     the share of span_resample_kernel in the summed kernel time of the process"""
     import csv
     import glob
-    rec = dict(kind="kernel_share", rate=args.rate, hops=args.hops, lanes=int(args.lanes), bits=args.bits)
+    rec = dict(kind="kernel_share", rate=args.rate, hops=args.hops, lanes=int(args.lanes), bits=args.bits, dtx=bool(args.dtx))
+    names = ["span_noise_scan_kernel", "span_logmel_kernel", "span_resample_kernel"] if args.dtx else ["span_resample_kernel"]
     with tempfile.TemporaryDirectory() as tmp:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "span", "--",
                sys.executable, os.path.abspath(__file__), "--device-leg-only", "--reps", "1", "--verify-hops", "0",
                "--hops", str(args.hops), "--lanes", str(args.lanes), "--bits", str(args.bits), "--rate", str(args.rate)]
+        cmd += ["--dtx"] if args.dtx else []
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.file_timeout)
         stats = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
         if r.returncode != 0 or not stats:
             rec["error"] = (r.stderr or r.stdout)[-300:]
             return rec
-        total = mine = calls = 0
+        total, mine, calls = 0, dict.fromkeys(names, 0), dict.fromkeys(names, 0)
         for row in csv.DictReader(open(stats[0])):
             ns = int(float(row["TotalDurationNs"]))
             total += ns
-            if "span_resample_kernel" in row["Name"]:
-                mine += ns
-                calls += int(row["Calls"])
-        rec.update(kernel_time_ms=round(total / 1e6, 3), span_resample_ms=round(mine / 1e6, 3), span_resample_calls=calls,
-                   span_resample_share=round(mine / total, 5) if total else None)
+            for k in names:
+                if k in row["Name"]:
+                    mine[k] += ns
+                    calls[k] += int(row["Calls"])
+        rec["kernel_time_ms"] = round(total / 1e6, 3)
+        for k in names:
+            short = k[:-len("_kernel")]
+            rec.update({short + "_ms": round(mine[k] / 1e6, 3), short + "_calls": calls[k],
+                        short + "_share": round(mine[k] / total, 5) if total else None})
     return rec
 
 
@@ -166,18 +265,21 @@ def main():
     ap.add_argument("--file-timeout", type=int, default=900)
     ap.add_argument("--skip-file-leg", action="store_true")
     ap.add_argument("--rate", type=int, default=16000, choices=[8000, 16000, 32000, 48000])
+    ap.add_argument("--dtx", action="store_true", help="LyraEncoder's DTX on a half-silent recording, encode only")
     ap.add_argument("--device-leg-only", action="store_true", help="the device leg alone, nothing recorded (the traced child)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "span_transcode.jsonl"))
     args = ap.parse_args()
     pcm = recording(args.hops, args.rate)
-    recs = [device_leg(args, pcm)]
+    if args.dtx:
+        pcm = half_silent(pcm, args.rate)
+    recs = [dtx_device_leg(args, pcm) if args.dtx else device_leg(args, pcm)]
     print(json.dumps(recs[0]), flush=True)
     if args.device_leg_only:
         return
     if not args.skip_file_leg:
-        recs.append(file_leg(args, pcm))
+        recs.append(dtx_file_leg(args, pcm) if args.dtx else file_leg(args, pcm))
         print(json.dumps(recs[-1]), flush=True)
-    if args.rate != 16000:
+    if args.rate != 16000 or args.dtx:
         recs.append(kernel_share_leg(args))
         print(json.dumps(recs[-1]), flush=True)
     with open(args.out, "a") as f:
