@@ -970,6 +970,64 @@ int lo_stream_trace_count(const lo_stream* s) { return s->trace_n; }
 int lo_stream_trace_offset(const lo_stream* s, int i) { return i < s->trace_n ? s->trace_off[i] : s->trace_len; }
 size_t lo_stream_sizeof(void) { return sizeof(lo_stream); }
 
+/* ---- state access (tests/state_bridge.py): one named tensor of lo_stream out or in, raw, in this file's own layout ----
+ * Histories are shift buffers [rows][channels], oldest row first, channels in the graph's order; a depthwise history of
+ * dilation d uses the first 2 d rows of its array (the rest is never touched) and only those are exposed.  int8 tensors of
+ * the graphs are kept here as the floats DEQUANTIZE gives (push_state_q).  All float, except mel_prev (double). */
+#include <stddef.h>
+typedef struct { const char* name; size_t off; int count, is_double; } lo_state_entry;
+#define LO_ST(nm, member, n) {nm, offsetof(lo_stream, member), n, 0}
+static const lo_state_entry lo_state_tab[] = {
+  LO_ST("e_first", e_first, 48),
+  LO_ST("e_r0[0]", e_r0[0], 2 * 64), LO_ST("e_r0[1]", e_r0[1], 6 * 64), LO_ST("e_r0[2]", e_r0[2], 18 * 64),
+  LO_ST("e_d0", e_d0, 5 * 64),
+  LO_ST("e_r1[0]", e_r1[0], 2 * 128), LO_ST("e_r1[1]", e_r1[1], 6 * 128), LO_ST("e_r1[2]", e_r1[2], 18 * 128),
+  LO_ST("e_d1", e_d1, 2 * 128),
+  LO_ST("e_r2[0]", e_r2[0], 2 * 256), LO_ST("e_r2[1]", e_r2[1], 6 * 256), LO_ST("e_r2[2]", e_r2[2], 18 * 256),
+  LO_ST("e_d2", e_d2, 2 * 256),
+  LO_ST("e_bott", e_bott, 2 * 512),
+  LO_ST("d_head", d_head, 2 * 64),
+  LO_ST("d_up0[0]", d_up0[0], 2 * 64), LO_ST("d_up0[1]", d_up0[1], 2 * 64), LO_ST("d_up0[2]", d_up0[2], 2 * 64),
+  LO_ST("d_up0[3]", d_up0[3], 2 * 64),
+  LO_ST("d_r0[0]", d_r0[0], 2 * 256), LO_ST("d_r0[1]", d_r0[1], 6 * 256), LO_ST("d_r0[2]", d_r0[2], 18 * 256),
+  LO_ST("d_up1[0]", d_up1[0], 2 * 64), LO_ST("d_up1[1]", d_up1[1], 2 * 64),
+  LO_ST("d_r1[0]", d_r1[0], 2 * 128), LO_ST("d_r1[1]", d_r1[1], 6 * 128), LO_ST("d_r1[2]", d_r1[2], 18 * 128),
+  LO_ST("d_up2", d_up2, 5 * 64),
+  LO_ST("d_r2[0]", d_r2[0], 2 * 64), LO_ST("d_r2[1]", d_r2[1], 6 * 64), LO_ST("d_r2[2]", d_r2[2], 18 * 64),
+  LO_ST("d_up3", d_up3, 48),
+  {"mel_prev", offsetof(lo_stream, mel_prev), 320, 1},
+};
+#undef LO_ST
+#define LO_STATE_N ((int)(sizeof lo_state_tab / sizeof lo_state_tab[0]))
+int lo_stream_state_count(void) { return LO_STATE_N; }
+const char* lo_stream_state_name(int i) { return i >= 0 && i < LO_STATE_N ? lo_state_tab[i].name : NULL; }
+/* elements of tensor i; negative: they are doubles, else floats */
+long lo_stream_state_len(int i) {
+  if (i < 0 || i >= LO_STATE_N) return 0;
+  return lo_state_tab[i].is_double ? -(long)lo_state_tab[i].count : (long)lo_state_tab[i].count;
+}
+static const lo_state_entry* lo_state_find(const char* name, long nbytes) {
+  for (int i = 0; i < LO_STATE_N; ++i)
+    if (strcmp(lo_state_tab[i].name, name) == 0) {
+      const long want = (long)lo_state_tab[i].count * (lo_state_tab[i].is_double ? 8 : 4);
+      return want == nbytes ? &lo_state_tab[i] : NULL;
+    }
+  return NULL;
+}
+/* 0, or -1 for an unknown name or a size that is not the tensor's */
+int lo_stream_get_state(const lo_stream* s, const char* name, void* out, long nbytes) {
+  const lo_state_entry* e = lo_state_find(name, nbytes);
+  if (!e) return -1;
+  memcpy(out, (const char*)s + e->off, (size_t)nbytes);
+  return 0;
+}
+int lo_stream_set_state(lo_stream* s, const char* name, const void* in, long nbytes) {
+  const lo_state_entry* e = lo_state_find(name, nbytes);
+  if (!e) return -1;
+  memcpy((char*)s + e->off, in, (size_t)nbytes);
+  return 0;
+}
+
 /* x' = concat(state[S][C], x[T][C]) -> buf[(S+T)][C]; state <- last S rows of buf */
 static void push_state(float* state, int S, const float* x, int T, int C, float* buf) {
   memcpy(buf, state, sizeof(float) * (size_t)S * C);

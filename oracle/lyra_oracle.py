@@ -95,6 +95,12 @@ def _bind(L):
         L.lo_run_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.lo_set_canonical_last.argtypes = [C.c_int]
+        L.lo_stream_state_name.restype = C.c_char_p
+        L.lo_stream_state_name.argtypes = [C.c_int]
+        L.lo_stream_state_len.restype = C.c_long
+        L.lo_stream_state_len.argtypes = [C.c_int]
+        L.lo_stream_get_state.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_long]
+        L.lo_stream_set_state.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_long]
     return L
 
 
@@ -185,6 +191,34 @@ class Stream:
         n = self.L.lo_stream_trace_count(self.h)
         offs = [self.L.lo_stream_trace_offset(self.h, i) for i in range(n + 1)]
         return [self.trace[offs[i]:offs[i + 1]].copy() for i in range(n)]
+
+    def _state_tensors(self):
+        """[(name, dtype, elements)] of lo_stream_get_state / lo_stream_set_state, in the order of lo_stream"""
+        out = []
+        for i in range(self.L.lo_stream_state_count()):
+            n = self.L.lo_stream_state_len(i)
+            out.append((self.L.lo_stream_state_name(i).decode(), np.float64 if n < 0 else np.float32, abs(n)))
+        return out
+
+    def state(self):
+        """Every state tensor of the stream, raw and flat in the oracle's own layout (lyra_oracle.c "state access"): histories
+        are shift buffers [rows][channels], oldest row first; int8 tensors of the graphs as dequantised floats; float32
+        except mel_prev (float64).  Names: e_first, e_r0[0..2], e_d0, ..., d_up3, mel_prev."""
+        out = {}
+        for name, dt, n in self._state_tensors():
+            a = np.empty(n, dt)
+            assert self.L.lo_stream_get_state(self.h, name.encode(), _p(a), a.nbytes) == 0, name
+            out[name] = a
+        return out
+
+    def set_state(self, state):
+        """Replace the tensors named in `state` (a dict as state() returns; any subset)."""
+        known = {name: (dt, n) for name, dt, n in self._state_tensors()}
+        for name, a in state.items():
+            dt, n = known[name]
+            a = np.ascontiguousarray(a, dt).reshape(-1)
+            assert a.size == n, (name, a.size, n)
+            assert self.L.lo_stream_set_state(self.h, name.encode(), _p(a), a.nbytes) == 0, name
 
     def encode(self, pcm):
         pcm = np.ascontiguousarray(pcm, np.int16)
