@@ -760,42 +760,6 @@ class LyraHip:
         return n
 
     # -- time-parallel spans (lyra_hip_encode_spans / lyra_hip_decode_spans) ----------------------------------------------
-    def encode_spans(self, spans, pcm, num_bits, lane_ids=(), sample_rate_hz=16000):
-        """Long spans of a few streams, time-parallel and bit for bit the hop-by-hop result.  spans: (stream_id,
-        first_frame, n_frames) triples into the frame-major pcm int16 [frames][320]; lane_ids: streams lent as scratch
-        (their encoder state is reset afterwards).  Returns packets uint8 [frames][bytes]; rows outside every span are 0.
-        sample_rate_hz other than 16000 (lyra_hip_encode_spans_ext): pcm is [frames][sample_rate_hz / 50] and the result that
-        of resample(side="encoder") + encode per hop."""
-        sp = _spans(spans)
-        lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
-        pcm = _np(pcm, np.int16, (-1, self._span_hop(sample_rate_hz)))
-        out = np.zeros((pcm.shape[0], packet_size(num_bits)), np.uint8)
-        self._check_span_frames(sp, pcm.shape[0])
-        if sample_rate_hz == 16000:
-            self._chk(self.L.lyra_hip_encode_spans(self.h, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
-                                                   pcm.ctypes.data, num_bits, out.ctypes.data))
-        else:
-            self._chk(self.L.lyra_hip_encode_spans_ext(self.h, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
-                                                       pcm.ctypes.data, sample_rate_hz, num_bits, out.ctypes.data))
-        return out
-
-    def decode_spans(self, spans, packets, num_bits, lane_ids=(), sample_rate_hz=16000):
-        """The decoder twin of encode_spans: packets uint8 [frames][bytes] -> pcm int16 [frames][320] (rows outside every
-        span are 0); the lanes' decoder state is reset afterwards.  sample_rate_hz other than 16000
-        (lyra_hip_decode_spans_ext): pcm int16 [frames][sample_rate_hz / 50], that of decode + resample(side="decoder")."""
-        sp = _spans(spans)
-        lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
-        packets = _np(packets, np.uint8, (-1, packet_size(num_bits)))
-        out = np.zeros((packets.shape[0], self._span_hop(sample_rate_hz)), np.int16)
-        self._check_span_frames(sp, packets.shape[0])
-        if sample_rate_hz == 16000:
-            self._chk(self.L.lyra_hip_decode_spans(self.h, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
-                                                   packets.ctypes.data, num_bits, out.ctypes.data))
-        else:
-            self._chk(self.L.lyra_hip_decode_spans_ext(self.h, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
-                                                       packets.ctypes.data, num_bits, sample_rate_hz, out.ctypes.data))
-        return out
-
     @staticmethod
     def _span_hop(sample_rate_hz):
         if sample_rate_hz not in (8000, 16000, 32000, 48000):
@@ -803,46 +767,77 @@ class LyraHip:
         return sample_rate_hz // 50
 
     @staticmethod
-    def _check_span_frames(sp, frames):
+    def _span_args(spans, lane_ids, frames):
+        """spans and lanes of a call on buffers of `frames` frames -> the C arguments (spans, n_spans, lane_ids, n_lanes) and
+        the arrays they point into, which the caller holds until the call has returned"""
+        sp = _spans(spans)
+        lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
         if sp.size and (np.any(sp["first_frame"] < 0) or np.any(sp["n_frames"] < 0) or
                         int(np.max(sp["first_frame"] + sp["n_frames"])) > frames):
             raise LyraHipError(f"spans: a span lies outside the {frames} frames of the buffer")
+        return (sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size), (sp, lanes)
+
+    def _opt_dev_ptr(self, t, dtype_name, shape, what):
+        """_dev_ptr of a buffer the call can do without: None -> a null pointer"""
+        return None if t is None else self._dev_ptr(t, dtype_name, shape, what)
+
+    def encode_spans(self, spans, pcm, num_bits, lane_ids=(), sample_rate_hz=16000):
+        """Long spans of a few streams, time-parallel and bit for bit the hop-by-hop result.  spans: (stream_id,
+        first_frame, n_frames) triples into the frame-major pcm int16 [frames][320]; lane_ids: streams lent as scratch
+        (their encoder state is reset afterwards).  Returns packets uint8 [frames][bytes]; rows outside every span are 0.
+        sample_rate_hz other than 16000 (lyra_hip_encode_spans_ext): pcm is [frames][sample_rate_hz / 50] and the result that
+        of resample(side="encoder") + encode per hop."""
+        pcm = _np(pcm, np.int16, (-1, self._span_hop(sample_rate_hz)))
+        out = np.zeros((pcm.shape[0], packet_size(num_bits)), np.uint8)
+        a, _held = self._span_args(spans, lane_ids, pcm.shape[0])
+        if sample_rate_hz == 16000:
+            self._chk(self.L.lyra_hip_encode_spans(self.h, *a, pcm.ctypes.data, num_bits, out.ctypes.data))
+        else:
+            self._chk(self.L.lyra_hip_encode_spans_ext(self.h, *a, pcm.ctypes.data, sample_rate_hz, num_bits, out.ctypes.data))
+        return out
+
+    def decode_spans(self, spans, packets, num_bits, lane_ids=(), sample_rate_hz=16000):
+        """The decoder twin of encode_spans: packets uint8 [frames][bytes] -> pcm int16 [frames][320] (rows outside every
+        span are 0); the lanes' decoder state is reset afterwards.  sample_rate_hz other than 16000
+        (lyra_hip_decode_spans_ext): pcm int16 [frames][sample_rate_hz / 50], that of decode + resample(side="decoder")."""
+        packets = _np(packets, np.uint8, (-1, packet_size(num_bits)))
+        out = np.zeros((packets.shape[0], self._span_hop(sample_rate_hz)), np.int16)
+        a, _held = self._span_args(spans, lane_ids, packets.shape[0])
+        if sample_rate_hz == 16000:
+            self._chk(self.L.lyra_hip_decode_spans(self.h, *a, packets.ctypes.data, num_bits, out.ctypes.data))
+        else:
+            self._chk(self.L.lyra_hip_decode_spans_ext(self.h, *a, packets.ctypes.data, num_bits, sample_rate_hz, out.ctypes.data))
+        return out
 
     def encode_spans_dev(self, spans, d_pcm, num_bits, d_packets, lane_ids=(), sample_rate_hz=16000, d_pcm16=None):
         """encode_spans on device buffers (spans and lane_ids stay host lists): d_pcm int16 [frames][320], d_packets uint8
         [frames][bytes].  Enqueues and does not synchronise.  sample_rate_hz other than 16000
         (lyra_hip_encode_spans_ext_dev): d_pcm is [frames][sample_rate_hz / 50] and d_pcm16 int16 [frames][320] the caller's
         workspace, which holds the resampled audio of the spans' frames afterwards."""
-        sp = _spans(spans)
-        lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
         F = d_pcm.shape[0]
-        self._check_span_frames(sp, F)
+        a, _held = self._span_args(spans, lane_ids, F)
+        p_packets = (d_packets, "uint8", (F, packet_size(num_bits)), "packets")
         if sample_rate_hz == 16000 and d_pcm16 is None:
-            self._dev_call(self.L.lyra_hip_encode_spans_dev, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
-                           self._dev_ptr(d_pcm, "int16", (F, HOP), "pcm"), num_bits,
-                           self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"))
+            self._dev_call(self.L.lyra_hip_encode_spans_dev, *a, self._dev_ptr(d_pcm, "int16", (F, HOP), "pcm"), num_bits,
+                           self._dev_ptr(*p_packets))
             return
-        self._dev_call(self.L.lyra_hip_encode_spans_ext_dev, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
-                       self._dev_ptr(d_pcm, "int16", (F, sample_rate_hz // 50), "pcm"), sample_rate_hz,
-                       self._dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm") if d_pcm16 is not None else None, num_bits,
-                       self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"))
+        self._dev_call(self.L.lyra_hip_encode_spans_ext_dev, *a, self._dev_ptr(d_pcm, "int16", (F, sample_rate_hz // 50), "pcm"),
+                       sample_rate_hz, self._opt_dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"), num_bits,
+                       self._dev_ptr(*p_packets))
 
     def decode_spans_dev(self, spans, d_packets, num_bits, d_pcm, lane_ids=(), sample_rate_hz=16000, d_pcm16=None):
         """decode_spans on device buffers.  Enqueues and does not synchronise.  sample_rate_hz other than 16000
         (lyra_hip_decode_spans_ext_dev): d_pcm is [frames][sample_rate_hz / 50] and d_pcm16 int16 [frames][320] receives the
         16 kHz output; all of it completes on the decode stream."""
-        sp = _spans(spans)
-        lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
         F = d_pcm.shape[0]
-        self._check_span_frames(sp, F)
+        a, _held = self._span_args(spans, lane_ids, F)
+        p_packets = (d_packets, "uint8", (F, packet_size(num_bits)), "packets")
         if sample_rate_hz == 16000 and d_pcm16 is None:
-            self._dev_call(self.L.lyra_hip_decode_spans_dev, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
-                           self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"), num_bits,
+            self._dev_call(self.L.lyra_hip_decode_spans_dev, *a, self._dev_ptr(*p_packets), num_bits,
                            self._dev_ptr(d_pcm, "int16", (F, HOP), "pcm"))
             return
-        self._dev_call(self.L.lyra_hip_decode_spans_ext_dev, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
-                       self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"), num_bits, sample_rate_hz,
-                       self._dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm") if d_pcm16 is not None else None,
+        self._dev_call(self.L.lyra_hip_decode_spans_ext_dev, *a, self._dev_ptr(*p_packets), num_bits, sample_rate_hz,
+                       self._opt_dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"),
                        self._dev_ptr(d_pcm, "int16", (F, sample_rate_hz // 50), "pcm"))
 
     # -- DTX on spans (lyra_hip_encode_spans_dtx / lyra_hip_noise_spans) -------------------------------------------------------
@@ -850,14 +845,11 @@ class LyraHip:
         """encode_spans with enable_dtx: bit for bit resample(side="encoder") + encode_dtx per hop.  pcm int16
         [frames][sample_rate_hz / 50]; sample_rate_hz must be the rate given to set_encoder_sample_rate.  Returns (packets uint8
         [frames][bytes], packet_bytes int32 [frames]); rows of noise frames and rows outside every span are 0."""
-        sp = _spans(spans)
-        lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
         pcm = _np(pcm, np.int16, (-1, self._span_hop(sample_rate_hz)))
         out = np.zeros((pcm.shape[0], packet_size(num_bits)), np.uint8)
         nbytes = np.zeros(pcm.shape[0], np.int32)
-        self._check_span_frames(sp, pcm.shape[0])
-        self._chk(self.L.lyra_hip_encode_spans_dtx(self.h, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
-                                                   pcm.ctypes.data, sample_rate_hz, num_bits, out.ctypes.data,
+        a, _held = self._span_args(spans, lane_ids, pcm.shape[0])
+        self._chk(self.L.lyra_hip_encode_spans_dtx(self.h, *a, pcm.ctypes.data, sample_rate_hz, num_bits, out.ctypes.data,
                                                    nbytes.ctypes.data))
         return out, nbytes
 
@@ -866,33 +858,28 @@ class LyraHip:
         """encode_spans_dtx on device buffers: d_pcm int16 [frames][sample_rate_hz / 50], d_packets uint8 [frames][bytes] (rows
         of noise frames are not written), d_packet_bytes int32 [frames], d_pcm16 int16 [frames][320] the 16 kHz workspace (not
         needed at 16000).  Blocks the host once, until the noise decisions are known; the steps behind are only enqueued."""
-        sp = _spans(spans)
-        lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
         F = d_pcm.shape[0]
-        self._check_span_frames(sp, F)
-        self._dev_call(self.L.lyra_hip_encode_spans_dtx_dev, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size,
+        a, _held = self._span_args(spans, lane_ids, F)
+        self._dev_call(self.L.lyra_hip_encode_spans_dtx_dev, *a,
                        self._dev_ptr(d_pcm, "int16", (F, self._span_hop(sample_rate_hz)), "pcm"), sample_rate_hz,
-                       self._dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm") if d_pcm16 is not None else None, num_bits,
+                       self._opt_dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"), num_bits,
                        self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"),
-                       self._dev_ptr(d_packet_bytes, "int32", (F,), "packet_bytes") if d_packet_bytes is not None else None)
+                       self._opt_dev_ptr(d_packet_bytes, "int32", (F,), "packet_bytes"))
 
     def noise_spans(self, spans, pcm, side="encoder"):
         """NoiseEstimator::ReceiveSamples over every frame of every span of pcm int16 [frames][320] -> is_noise int32 [frames]
         (what noise_receive returns per hop; rows outside every span are 0)."""
-        sp = _spans(spans)
         pcm = _np(pcm, np.int16, (-1, HOP))
         out = np.zeros(pcm.shape[0], np.int32)
-        self._check_span_frames(sp, pcm.shape[0])
-        self._chk(self.L.lyra_hip_noise_spans(self.h, self._SIDES[side], sp.ctypes.data, sp.size, pcm.ctypes.data,
-                                              out.ctypes.data))
+        a, _held = self._span_args(spans, (), pcm.shape[0])
+        self._chk(self.L.lyra_hip_noise_spans(self.h, self._SIDES[side], *a[:2], pcm.ctypes.data, out.ctypes.data))
         return out
 
     def noise_spans_dev(self, spans, d_pcm, d_is_noise, side="encoder"):
         """noise_spans on device buffers; enqueues and does not synchronise."""
-        sp = _spans(spans)
         F = d_pcm.shape[0]
-        self._check_span_frames(sp, F)
-        self._dev_call(self.L.lyra_hip_noise_spans_dev, self._SIDES[side], sp.ctypes.data, sp.size,
+        a, _held = self._span_args(spans, (), F)
+        self._dev_call(self.L.lyra_hip_noise_spans_dev, self._SIDES[side], *a[:2],
                        self._dev_ptr(d_pcm, "int16", (F, HOP), "pcm"), self._dev_ptr(d_is_noise, "int32", (F,), "is_noise"))
 
     def noise_receive_dev(self, d_ids, d_pcm, d_is_noise, side="decoder"):

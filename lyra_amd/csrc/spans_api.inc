@@ -14,6 +14,8 @@
 // of all frames in one launch, then one wavefront per span for the recurrence), waits ONCE on the host for the spans' counts of
 // non-noise hops, and runs the unchanged steps on the compacted frame list: under DTX the encoder advances on non-noise hops
 // only, so what it sees is again a stream whose state is convolution history.  lyra_hip_noise_spans[_dev] is the estimator alone.
+#include <type_traits>
+
 #include "spans_plan.h"
 
 static_assert(sizeof(lyra_hip_span) == sizeof(sp::Span) && sizeof(lyra_hip_span_chunk) == sizeof(sp::Chunk) &&
@@ -104,6 +106,14 @@ struct SpanPlan {
   int64_t end_frame = 0;   // one past the last buffer frame any span names
 };
 
+// one past the last buffer frame a span names -- a span without frames names its first (spans the planner refuses name none)
+int64_t span_end_frame(const lyra_hip_span* spans, int n_spans) {
+  int64_t end = 0;
+  for (int s = 0; spans && s < n_spans; ++s)
+    if (spans[s].first_frame >= 0 && spans[s].n_frames >= 0) end = std::max<int64_t>(end, spans[s].first_frame + spans[s].n_frames);
+  return end;
+}
+
 int span_plan_checked(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                       SpanPlan* P, const char* what) {
   if (n_spans <= 0 || !spans) return fail(c, LYRA_HIP_EINVAL, "%s: no spans", what);
@@ -114,7 +124,7 @@ int span_plan_checked(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int
                 "%s: span and lane ids must be distinct streams of the context (0..%d), frame ranges non-negative and disjoint",
                 what, c->max_streams - 1);
   for (const sp::Chunk& ch : P->chunks) P->n_own += ch.n_warmup == 0;
-  for (int s = 0; s < n_spans; ++s) P->end_frame = std::max<int64_t>(P->end_frame, spans[s].first_frame + spans[s].n_frames);
+  P->end_frame = span_end_frame(spans, n_spans);
   return 0;
 }
 
@@ -148,19 +158,32 @@ struct SpanExt {
   bool on() const { return rate != 16000; }
 };
 
-// rows of span_resample_kernel: the spans with frames, four frames per workgroup.  Returns the workgroups, -1: too many.
-long long span_rs_rows(const lyra_hip_span* spans, int n_spans, SpanRsRow* rows, int* n_rows) {
-  long long wg = 0;
-  int n = 0;
+// Rows of the kernels that pass once over every frame of a call, one row per span with frames.  Row = SpanRsRow:
+// span_resample_kernel, four frames per workgroup; SpanDtxRow: span_logmel_kernel / span_noise_scan_kernel, two frames per
+// log-mel workgroup, region = the frames of the rows in front.  rows == nullptr only counts.  wgs < 0: too many for one launch.
+struct SpanPass {
+  int n = 0;                      // rows
+  long long wgs = 0, frames = 0;  // workgroups and frames of all rows
+};
+template <class Row>
+SpanPass span_pass_rows(const lyra_hip_span* spans, int n_spans, Row* rows) {
+  constexpr bool dtx = std::is_same<Row, SpanDtxRow>::value;
+  SpanPass p;
   for (int s = 0; s < n_spans; ++s) {
     if (!spans[s].n_frames) continue;
-    if (rows) rows[n] = SpanRsRow{spans[s].first_frame, spans[s].n_frames, spans[s].stream_id, (int32_t)wg, {0, 0}};
-    ++n;
-    wg += (spans[s].n_frames + 3) / 4;
-    if (wg > INT32_MAX) return -1;
+    if (rows) {
+      rows[p.n] = Row{spans[s].first_frame, spans[s].n_frames, spans[s].stream_id, (int32_t)p.wgs};
+      if constexpr (dtx) rows[p.n].region = p.frames;
+    }
+    ++p.n;
+    p.wgs += dtx ? (spans[s].n_frames + 1) / 2 : (spans[s].n_frames + 3) / 4;
+    p.frames += spans[s].n_frames;
+    if (p.wgs > INT32_MAX) {
+      p.wgs = -1;
+      break;
+    }
   }
-  *n_rows = n;
-  return wg;
+  return p;
 }
 
 // one launch over every frame of every span: in [frames][n_in] -> out [frames][n_in * to / from] on st_ (slots: see
@@ -233,132 +256,171 @@ int span_run_steps(lyra_hip_ctx* c, bool enc, SpanSide& S, hipStream_t st_, cons
   return rc;
 }
 
-// The enqueue of one call.  enc: d_src PCM [frames][320], d_dst packets [frames][nbytes]; else the reverse.  X.on(): the PCM
-// of d_src / d_dst is [frames][X.n_ext()] and the steps work on X.d_pcm16.
-int spans_enqueue(lyra_hip_ctx* c, bool enc, const SpanPlan& P, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids,
-                  int n_lanes, const void* d_src, int num_bits, void* d_dst, const SpanExt& X) {
+// ---- what the calls share ------------------------------------------------------------------------------------------------
+bool span_rate_ok(int rate) { return rate == 8000 || rate == 16000 || rate == 32000 || rate == 48000; }
+hipStream_t span_stream(lyra_hip_ctx* c, int side) { return side == sp::SIDE_ENC ? c->se[0] : c->sd[0]; }
+
+// the side's state of the span calls (created on first use) and its stream
+SpanSide& span_side_open(lyra_hip_ctx* c, int side, hipStream_t* st_) {
   if (!c->span_calls) c->span_calls = new SpanCalls();
-  SpanSide& S = span_calls_of(c)->side[enc ? 0 : 1];
-  hipStream_t st_ = enc ? c->se[0] : c->sd[0];
-  const int rows = (int)P.chunks.size();
-  int n_rs = 0;
-  const long long rs_wgs = X.on() ? span_rs_rows(spans, n_spans, nullptr, &n_rs) : 0;
-  if (rs_wgs < 0) return fail(c, LYRA_HIP_EINVAL, "spans: too many frames for one resampler pass");
-  int rc = span_side_ensure(c, S, st_, std::max(rows, 1), n_lanes + n_rs);
+  *st_ = span_stream(c, side);
+  return span_calls_of(c)->side[side];
+}
+
+int span_side_begin(lyra_hip_ctx* c, int side) { return side == sp::SIDE_ENC ? enc_side_begin(c, 0) : dec_side_begin(c, 0); }
+
+// the end of the call's bracket, rc: what the enqueue gave; a decoder-side call counts as one whether or not it failed
+int span_side_close(lyra_hip_ctx* c, int side, int rc) {
+  if (side == sp::SIDE_ENC) return rc ? rc : enc_side_done(c, 0);
+  if (!rc) rc = dec_side_done(c, 0, 1);
+  c->n_dec_calls++;
+  return rc;
+}
+
+// pinned rows [first, first + n) -> the device's rows on st_; ev_up: the end of the side's last upload
+int span_upload_rows(lyra_hip_ctx* c, SpanSide& S, hipStream_t st_, int first, int n) {
+  if (!n) return 0;
+  HIPCHK(c, hipMemcpyAsync(S.d_rows + first, S.h_rows + first, (size_t)n * sizeof(SpanRow), hipMemcpyHostToDevice, st_));
+  HIPCHK(c, hipEventRecord(S.ev_up, st_));
+  S.up_pending = true;
+  return 0;
+}
+
+// In front of the encoder's steps at another rate: ONE resampler pass, *d_pcm [frames][X.n_ext()] -> the 16 kHz workspace, which
+// the steps then read: *d_pcm becomes the workspace.
+int span_encode_front(lyra_hip_ctx* c, hipStream_t st_, const SpanExt& X, const SpanRsRow* d_rs_rows, const SpanPass& rs,
+                      const int16_t** d_pcm) {
+  if (!X.on()) return 0;
+  const int rc = rs.n ? launch_span_resample(c, true, st_, d_rs_rows, rs.n, rs.wgs, X.rate, 16000, *d_pcm, X.d_pcm16) : 0;
+  if (!rc) *d_pcm = X.d_pcm16;
+  return rc;
+}
+
+// What every form checks first: the context, the side, the bit count (num_bits == nullptr: the call has none), the rate.
+int span_check_head(lyra_hip_ctx* c, const char* what, int side, const int* num_bits, int rate) {
+  if (!c) return LYRA_HIP_EINVAL;
+  if (sp::warmup(side) < 0) return fail(c, LYRA_HIP_EINVAL, "%s: bad side", what);
+  const int rc = num_bits ? check_bits(c, *num_bits) : 0;
   if (rc) return rc;
+  if (!span_rate_ok(rate)) return fail(c, LYRA_HIP_EINVAL, "%s: sample rate %d Hz (8000 / 16000 / 32000 / 48000)", what, rate);
+  return 0;
+}
+
+// The argument check of the `_dev` forms, before anything of the context is touched: span_check_head, the lane list, the
+// planner's rules on the spans as given (*P: that plan), d_pcm and d_other non-null once a span names a frame, d_pcm 16-byte
+// aligned, and at another rate the 16 kHz workspace.
+int span_check(lyra_hip_ctx* c, const char* what, int side, const int* num_bits, const lyra_hip_span* spans, int n_spans,
+               const int32_t* lane_ids, int n_lanes, const void* d_pcm, const void* d_other, const SpanExt& X, SpanPlan* P) {
+  int rc = span_check_head(c, what, side, num_bits, X.rate);
+  if (rc) return rc;
+  if (n_lanes < 0 || (n_lanes && !lane_ids)) return fail(c, LYRA_HIP_EINVAL, "%s: bad lane list", what);
+  if ((rc = span_plan_checked(c, side, spans, n_spans, lane_ids, n_lanes, P, what))) return rc;
+  if (P->end_frame && (!d_pcm || !d_other)) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
+  if (reinterpret_cast<uintptr_t>(d_pcm) & 15) return fail(c, LYRA_HIP_EINVAL, "%s: the PCM buffer must be 16-byte aligned", what);
+  if (X.on() && ((P->end_frame && !X.d_pcm16) || (reinterpret_cast<uintptr_t>(X.d_pcm16) & 15)))
+    return fail(c, LYRA_HIP_EINVAL, "%s: at %d Hz the 16 kHz buffer must be given, 16-byte aligned", what, X.rate);
+  return 0;
+}
+
+// One buffer of a blocking host-buffer form, `bytes` per frame: frames 0 .. end - 1 are staged on the device.
+enum SpanDir { SPAN_IN, SPAN_OUT, SPAN_WORK };   // uploaded | the spans' own frames read back | neither: the call's workspace
+struct SpanBuf {
+  SpanDir dir;
+  void* host;
+  size_t bytes;         // 0: the call does without the buffer, d stays null
+  bool zero = false;    // the device copy starts as zeros: rows of a span that the call does not write read back as zeros
+  uint8_t* d = nullptr;
+};
+
+// The blocking host-buffer forms: allocate, upload, run the `_dev` form (dev(), on B[k].d), synchronise, read back the spans'
+// own frames, free.  Whatever fails, the side's stream has drained before the staging buffers go.
+template <size_t N, class Dev>
+int span_staged(lyra_hip_ctx* c, const char* what, int side, const lyra_hip_span* spans, int n_spans, SpanBuf (&B)[N], Dev dev) {
+  const size_t end = (size_t)span_end_frame(spans, n_spans);
+  for (const SpanBuf& b : B)
+    if (end && b.dir != SPAN_WORK && !b.host) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
+  DEVSCOPE(c);
+  hipStream_t st_ = span_stream(c, side);
+  int rc = 0;
+  for (SpanBuf& b : B) {
+    const size_t bytes = end * b.bytes;
+    if (rc || !b.bytes) continue;
+    if (hipMalloc((void**)&b.d, std::max<size_t>(bytes, 1)) != hipSuccess)
+      rc = fail(c, LYRA_HIP_ENOMEM, "%s: staging %zu frames failed", what, end);
+    else if (bytes && (b.dir == SPAN_IN ? hipMemcpy(b.d, b.host, bytes, hipMemcpyHostToDevice)
+                       : b.zero         ? hipMemset(b.d, 0, bytes)
+                                        : hipSuccess) != hipSuccess)
+      rc = fail(c, LYRA_HIP_EHIP, "%s: upload failed", what);
+  }
+  if (!rc) rc = dev();
+  if (!rc && hipStreamSynchronize(st_) != hipSuccess) rc = fail(c, LYRA_HIP_EHIP, "%s: synchronise failed", what);
+  for (int s = 0; !rc && s < n_spans; ++s)
+    for (const SpanBuf& b : B) {
+      const size_t at = (size_t)spans[s].first_frame * b.bytes, n = (size_t)spans[s].n_frames * b.bytes;
+      if (!rc && b.dir == SPAN_OUT && n && hipMemcpy((uint8_t*)b.host + at, b.d + at, n, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(c, LYRA_HIP_EHIP, "%s: download failed", what);
+    }
+  if (rc) (void)hipStreamSynchronize(st_);
+  for (SpanBuf& b : B) dfree(b.d);
+  return rc;
+}
+
+// ---- the plain and `_ext` calls ----------------------------------------------------------------------------------------------
+// side SIDE_ENC: d_src PCM [frames][320], d_dst packets [frames][nbytes]; SIDE_DEC the reverse.  X.on(): the PCM of d_src /
+// d_dst is [frames][X.n_ext()] and the steps work on X.d_pcm16.
+int spans_call_dev(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                   const void* d_src, int num_bits, void* d_dst, const SpanExt& X = SpanExt()) {
+  const bool enc = side == sp::SIDE_ENC;
+  const char* what = enc ? "encode_spans" : "decode_spans";
+  SpanPlan P;
+  int rc = span_check(c, what, side, &num_bits, spans, n_spans, lane_ids, n_lanes, enc ? d_src : d_dst, enc ? d_dst : d_src, X, &P);
+  if (rc) return rc;
+  const SpanPass rs = X.on() ? span_pass_rows<SpanRsRow>(spans, n_spans, nullptr) : SpanPass();
+  if (rs.wgs < 0) return fail(c, LYRA_HIP_EINVAL, "%s: too many frames for one pass", what);
+  DEVSCOPE(c);
+  hipStream_t st_;
+  SpanSide& S = span_side_open(c, side, &st_);
+  const int rows = (int)P.chunks.size();
+  if ((rc = span_side_ensure(c, S, st_, std::max(rows, 1), n_lanes + rs.n))) return rc;
   if (rows && (rc = ensure_scratch(c, rows))) return rc;   // the stage kernels' own boundary buffers
   span_fill_rows(P, spans, lane_ids, n_lanes, S.h_rows);
   const int rs0 = rows + n_lanes;   // the resampler's rows lie behind the lanes' reset rows
-  if (n_rs) span_rs_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(S.h_rows + rs0), &n_rs);
-  if ((rc = enc ? enc_side_begin(c, 0) : dec_side_begin(c, 0))) return rc;
-  if (rs0 + n_rs) {
-    HIPCHK(c, hipMemcpyAsync(S.d_rows, S.h_rows, (size_t)(rs0 + n_rs) * sizeof(SpanRow), hipMemcpyHostToDevice, st_));
-    HIPCHK(c, hipEventRecord(S.ev_up, st_));
-    S.up_pending = true;
-  }
+  if (rs.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(S.h_rows + rs0));
+  if ((rc = span_side_begin(c, side))) return rc;
+  if ((rc = span_upload_rows(c, S, st_, 0, rs0 + rs.n))) return rc;
   const SpanRsRow* d_rs_rows = reinterpret_cast<const SpanRsRow*>(S.d_rows + rs0);
   void* d_ext_out = nullptr;
-  if (X.on() && enc) {   // the steps read the 16 kHz workspace ...
-    if (n_rs && (rc = launch_span_resample(c, true, st_, d_rs_rows, n_rs, rs_wgs, X.rate, 16000, (const int16_t*)d_src, X.d_pcm16)))
-      return rc;
-    d_src = X.d_pcm16;
+  if (enc) {   // the steps read the 16 kHz workspace ...
+    const int16_t* d_pcm = static_cast<const int16_t*>(d_src);
+    if ((rc = span_encode_front(c, st_, X, d_rs_rows, rs, &d_pcm))) return rc;
+    d_src = d_pcm;
   } else if (X.on()) {   // ... or write it
     d_ext_out = d_dst;
     d_dst = X.d_pcm16;
   }
   rc = span_run_steps(c, enc, S, st_, P, S.h_rows, S.d_rows, S.d_rows + rows, n_lanes, d_src, num_bits, d_dst, nullptr);
-  if (!rc && d_ext_out && n_rs)
-    rc = launch_span_resample(c, false, st_, d_rs_rows, n_rs, rs_wgs, 16000, X.rate, X.d_pcm16, (int16_t*)d_ext_out);
-  if (enc) {
-    if (!rc) rc = enc_side_done(c, 0);
-  } else {
-    if (!rc) rc = dec_side_done(c, 0, 1);
-    c->n_dec_calls++;
-  }
-  return rc;
+  if (!rc && d_ext_out && rs.n)
+    rc = launch_span_resample(c, false, st_, d_rs_rows, rs.n, rs.wgs, 16000, X.rate, X.d_pcm16, (int16_t*)d_ext_out);
+  return span_side_close(c, side, rc);
 }
 
-bool span_rate_ok(int rate) { return rate == 8000 || rate == 16000 || rate == 32000 || rate == 48000; }
-
-int spans_call_dev(lyra_hip_ctx* c, bool enc, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
-                   const void* d_src, int num_bits, void* d_dst, SpanPlan* P, const SpanExt& X = SpanExt()) {
-  const char* what = enc ? "encode_spans" : "decode_spans";
-  if (!c) return LYRA_HIP_EINVAL;
-  int rc = check_bits(c, num_bits);
-  if (rc) return rc;
-  if (!span_rate_ok(X.rate)) return fail(c, LYRA_HIP_EINVAL, "%s: sample rate %d Hz (8000 / 16000 / 32000 / 48000)", what, X.rate);
-  if (n_lanes < 0 || (n_lanes && !lane_ids)) return fail(c, LYRA_HIP_EINVAL, "%s: bad lane list", what);
-  if ((rc = span_plan_checked(c, enc ? sp::SIDE_ENC : sp::SIDE_DEC, spans, n_spans, lane_ids, n_lanes, P, what))) return rc;
-  if (P->end_frame && (!d_src || !d_dst)) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
-  const void* pcm = enc ? d_src : d_dst;
-  if (reinterpret_cast<uintptr_t>(pcm) & 15) return fail(c, LYRA_HIP_EINVAL, "%s: the PCM buffer must be 16-byte aligned", what);
-  if (X.on() && ((P->end_frame && !X.d_pcm16) || (reinterpret_cast<uintptr_t>(X.d_pcm16) & 15)))
-    return fail(c, LYRA_HIP_EINVAL, "%s: at %d Hz the 16 kHz buffer must be given, 16-byte aligned", what, X.rate);
-  DEVSCOPE(c);
-  return spans_enqueue(c, enc, *P, spans, n_spans, lane_ids, n_lanes, d_src, num_bits, d_dst, X);
-}
-
-// host-buffer form: frames 0 .. end_frame - 1 of both buffers are staged (copy, run, synchronise); PCM rows of rate / 50 samples,
-// and at a rate other than 16000 the 16 kHz workspace lives next to the staging buffers
-int spans_call_host(lyra_hip_ctx* c, bool enc, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+// host-buffer form: PCM rows of rate / 50 samples, and at a rate other than 16000 the 16 kHz workspace lives next to the
+// staging buffers
+int spans_call_host(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                     const void* src, int num_bits, void* dst, int rate = 16000) {
-  if (!c) return LYRA_HIP_EINVAL;
-  int rc = check_bits(c, num_bits);
+  const bool enc = side == sp::SIDE_ENC;
+  const char* what = enc ? "encode_spans" : "decode_spans";
+  const int rc = span_check_head(c, what, side, &num_bits, rate);
   if (rc) return rc;
-  if (!span_rate_ok(rate))
-    return fail(c, LYRA_HIP_EINVAL, "%s: sample rate %d Hz (8000 / 16000 / 32000 / 48000)", enc ? "encode_spans" : "decode_spans", rate);
-  int64_t end = 0;
-  for (int s = 0; spans && s < n_spans; ++s)
-    if (spans[s].first_frame >= 0 && spans[s].n_frames >= 0) end = std::max<int64_t>(end, spans[s].first_frame + spans[s].n_frames);
-  if (end && (!src || !dst)) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", enc ? "encode_spans" : "decode_spans");
-  DEVSCOPE(c);
   const size_t nbytes = (size_t)(num_bits + 7) / 8, pcm_b = (size_t)rate / 50 * 2;
-  const size_t in_b = (size_t)end * (enc ? pcm_b : nbytes), out_b = (size_t)end * (enc ? nbytes : pcm_b);
-  uint8_t *d_in = nullptr, *d_out = nullptr;
-  SpanExt X;
-  X.rate = rate;
-  if (end) {
-    if (dalloc(&d_in, in_b) != hipSuccess || dalloc(&d_out, out_b) != hipSuccess ||
-        (X.on() && dalloc(&X.d_pcm16, (size_t)end * 320) != hipSuccess)) {
-      dfree(d_in, d_out, X.d_pcm16);
-      return fail(c, LYRA_HIP_ENOMEM, "spans: staging %zu + %zu bytes failed", in_b, out_b);
-    }
-  }
-  hipStream_t st_ = enc ? c->se[0] : c->sd[0];
-  SpanPlan P;
-  rc = 0;
-  if (end && hipMemcpy(d_in, src, in_b, hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, LYRA_HIP_EHIP, "spans: upload failed");
-  if (!rc) rc = spans_call_dev(c, enc, spans, n_spans, lane_ids, n_lanes, d_in, num_bits, d_out, &P, X);
-  if (!rc && hipStreamSynchronize(st_) != hipSuccess) rc = fail(c, LYRA_HIP_EHIP, "spans: synchronise failed");
-  const size_t ob = enc ? nbytes : pcm_b;   // only the spans' own frames of the caller's output are written
-  for (int s = 0; !rc && s < n_spans; ++s)
-    if (spans[s].n_frames && hipMemcpy((uint8_t*)dst + spans[s].first_frame * ob, d_out + spans[s].first_frame * ob,
-                                       spans[s].n_frames * ob, hipMemcpyDeviceToHost) != hipSuccess)
-      rc = fail(c, LYRA_HIP_EHIP, "spans: download failed");
-  if (rc) (void)hipStreamSynchronize(st_);
-  dfree(d_in, d_out, X.d_pcm16);
-  return rc;
+  SpanBuf B[] = {{SPAN_IN, (void*)src, enc ? pcm_b : nbytes}, {SPAN_OUT, dst, enc ? nbytes : pcm_b},
+                 {SPAN_WORK, nullptr, rate != 16000 ? (size_t)640 : 0}};
+  return span_staged(c, what, side, spans, n_spans, B, [&] {
+    return spans_call_dev(c, side, spans, n_spans, lane_ids, n_lanes, B[0].d, num_bits, B[1].d, SpanExt{rate, (int16_t*)B[2].d});
+  });
 }
 
 // ---- DTX on spans ---------------------------------------------------------------------------------------------------------
-// rows of span_logmel_kernel / span_noise_scan_kernel: the spans with frames, two frames per log-mel workgroup; region = the
-// frames of the rows in front.  Returns the log-mel workgroups, -1: too many; *frames: all rows' frames.
-long long span_dtx_rows(const lyra_hip_span* spans, int n_spans, SpanDtxRow* rows, int* n_rows, long long* frames) {
-  long long wg = 0, region = 0;
-  int n = 0;
-  for (int s = 0; s < n_spans; ++s) {
-    if (!spans[s].n_frames) continue;
-    if (rows) rows[n] = SpanDtxRow{spans[s].first_frame, spans[s].n_frames, spans[s].stream_id, (int32_t)wg, region};
-    ++n;
-    wg += (spans[s].n_frames + 1) / 2;
-    region += spans[s].n_frames;
-    if (wg > INT32_MAX) return -1;
-  }
-  *n_rows = n;
-  *frames = region;
-  return wg;
-}
-
 // mel rows and map for `frames` frames, counts for n_rows spans -- the worst case of a call, before anything is enqueued
 int span_dtx_ensure(lyra_hip_ctx* c, SpanSide& S, hipStream_t st_, long long frames, int n_rows) {
   if (frames > S.dtx_cap) {
@@ -400,201 +462,6 @@ int launch_span_noise(lyra_hip_ctx* c, int side, hipStream_t st_, SpanSide& S, c
   return 0;
 }
 
-int spans_dtx_call_dev(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
-                       const int16_t* d_pcm_ext, int rate, int16_t* d_pcm16, int num_bits, uint8_t* d_packets,
-                       int32_t* d_packet_bytes) {
-  const char* what = "encode_spans_dtx";
-  if (!c) return LYRA_HIP_EINVAL;
-  int rc = check_bits(c, num_bits);
-  if (rc) return rc;
-  if (!span_rate_ok(rate)) return fail(c, LYRA_HIP_EINVAL, "%s: sample rate %d Hz (8000 / 16000 / 32000 / 48000)", what, rate);
-  if (c->enc_noise_rate != rate)   // as lyra_hip_encode_ext_dev: the DTX estimator is created at the encoder's external rate
-    return fail(c, LYRA_HIP_EINVAL, "%s: DTX at %d Hz but the encoder-side noise estimator is set up for %d Hz "
-                "(call lyra_hip_set_encoder_sample_rate(%d) first)", what, rate, c->enc_noise_rate, rate);
-  if (n_lanes < 0 || (n_lanes && !lane_ids)) return fail(c, LYRA_HIP_EINVAL, "%s: bad lane list", what);
-  SpanPlan dry;   // ids, lanes and frame ranges: the planner's rules, on the spans as given
-  if ((rc = span_plan_checked(c, sp::SIDE_ENC, spans, n_spans, lane_ids, n_lanes, &dry, what))) return rc;
-  if (!d_packet_bytes || (dry.end_frame && (!d_pcm_ext || !d_packets))) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
-  if (reinterpret_cast<uintptr_t>(d_pcm_ext) & 15) return fail(c, LYRA_HIP_EINVAL, "%s: the PCM buffer must be 16-byte aligned", what);
-  SpanExt X;
-  X.rate = rate;
-  X.d_pcm16 = X.on() ? d_pcm16 : nullptr;
-  if (X.on() && ((dry.end_frame && !X.d_pcm16) || (reinterpret_cast<uintptr_t>(X.d_pcm16) & 15)))
-    return fail(c, LYRA_HIP_EINVAL, "%s: at %d Hz the 16 kHz buffer must be given, 16-byte aligned", what, rate);
-  int n_rs = 0, n_dx = 0;
-  long long frames = 0;
-  const long long rs_wgs = X.on() ? span_rs_rows(spans, n_spans, nullptr, &n_rs) : 0;
-  const long long lm_wgs = span_dtx_rows(spans, n_spans, nullptr, &n_dx, &frames);
-  if (rs_wgs < 0 || lm_wgs < 0) return fail(c, LYRA_HIP_EINVAL, "%s: too many frames for one pass", what);
-  DEVSCOPE(c);
-  if (!c->span_calls) c->span_calls = new SpanCalls();
-  SpanSide& S = span_calls_of(c)->side[0];
-  hipStream_t st_ = c->se[0];
-  // all scratch for the worst case -- every frame active: at most one chunk per span and per lane -- before the first launch
-  const int rows_max = n_spans + n_lanes;
-  if ((rc = span_side_ensure(c, S, st_, rows_max, n_lanes + n_rs + n_dx))) return rc;
-  if ((rc = ensure_scratch(c, rows_max))) return rc;
-  if ((rc = span_dtx_ensure(c, S, st_, std::max<long long>(frames, 1), std::max(n_dx, 1)))) return rc;
-  // upload 1, behind the batch rows' place: the lanes' reset rows, the resampler's rows, the estimator's rows
-  SpanRow* h_fix = S.h_rows + rows_max;
-  for (int l = 0; l < n_lanes; ++l) h_fix[l] = SpanRow{lane_ids[l], 0, 0, -1, 0, 0, 0};
-  if (n_rs) span_rs_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(h_fix + n_lanes), &n_rs);
-  span_dtx_rows(spans, n_spans, reinterpret_cast<SpanDtxRow*>(h_fix + n_lanes + n_rs), &n_dx, &frames);
-  const SpanRow* d_fix = S.d_rows + rows_max;
-  const SpanRsRow* d_rs_rows = reinterpret_cast<const SpanRsRow*>(d_fix + n_lanes);
-  const SpanDtxRow* d_dx_rows = reinterpret_cast<const SpanDtxRow*>(d_fix + n_lanes + n_rs);
-  if ((rc = enc_side_begin(c, 0))) return rc;
-  if (n_lanes + n_rs + n_dx) {
-    HIPCHK(c, hipMemcpyAsync(S.d_rows + rows_max, h_fix, (size_t)(n_lanes + n_rs + n_dx) * sizeof(SpanRow), hipMemcpyHostToDevice,
-                             st_));
-    HIPCHK(c, hipEventRecord(S.ev_up, st_));
-    S.up_pending = true;
-  }
-  const int16_t* d_src16 = d_pcm_ext;
-  if (X.on()) {
-    if (n_rs && (rc = launch_span_resample(c, true, st_, d_rs_rows, n_rs, rs_wgs, rate, 16000, d_pcm_ext, X.d_pcm16))) return rc;
-    d_src16 = X.d_pcm16;
-  }
-  SpanPlan P;
-  std::vector<lyra_hip_span> compact((size_t)n_spans);
-  if (n_dx) {
-    if ((rc = launch_span_noise(c, 0, st_, S, d_dx_rows, n_dx, lm_wgs, d_src16, d_packet_bytes, 0, (num_bits + 7) / 8, S.d_map)))
-      return rc;
-    // the one host wait of the call: the plan depends on the decisions
-    HIPCHK(c, hipStreamSynchronize(st_));
-    S.up_pending = false;
-  }
-  {   // what the encoder sees of span s: its non-noise hops, at the start of its region of the map
-    long long region = 0;
-    int r = 0;
-    for (int s = 0; s < n_spans; ++s) {
-      compact[s] = lyra_hip_span{spans[s].stream_id, region, spans[s].n_frames ? (int64_t)S.h_counts[r++] : 0};
-      if (compact[s].n_frames < 0 || compact[s].n_frames > spans[s].n_frames)
-        return fail(c, LYRA_HIP_EHIP, "%s: the scan's count of span %d is out of range", what, s);
-      region += spans[s].n_frames;
-    }
-  }
-  if ((rc = span_plan_checked(c, sp::SIDE_ENC, compact.data(), n_spans, lane_ids, n_lanes, &P, what))) return rc;
-  const int rows = (int)P.chunks.size();
-  if (rows) {   // upload 2: the batch rows (the pinned rows in front of upload 1's, so neither waits for the other)
-    span_fill_rows(P, compact.data(), lane_ids, 0, S.h_rows);
-    HIPCHK(c, hipMemcpyAsync(S.d_rows, S.h_rows, (size_t)rows * sizeof(SpanRow), hipMemcpyHostToDevice, st_));
-    HIPCHK(c, hipEventRecord(S.ev_up, st_));
-    S.up_pending = true;
-  }
-  rc = span_run_steps(c, true, S, st_, P, S.h_rows, S.d_rows, d_fix, n_lanes, d_src16, num_bits, d_packets, S.d_map);
-  if (!rc) rc = enc_side_done(c, 0);
-  return rc;
-}
-
-// host-buffer form: frames 0 .. end - 1 of the buffers are staged; packet rows of noise frames read back as zeros
-int spans_dtx_call_host(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
-                        const int16_t* pcm_ext, int rate, int num_bits, uint8_t* packets, int32_t* packet_bytes) {
-  if (!c) return LYRA_HIP_EINVAL;
-  int rc = check_bits(c, num_bits);
-  if (rc) return rc;
-  if (!span_rate_ok(rate)) return fail(c, LYRA_HIP_EINVAL, "encode_spans_dtx: sample rate %d Hz (8000 / 16000 / 32000 / 48000)", rate);
-  int64_t end = 0;
-  for (int s = 0; spans && s < n_spans; ++s)
-    if (spans[s].first_frame >= 0 && spans[s].n_frames >= 0) end = std::max<int64_t>(end, spans[s].first_frame + spans[s].n_frames);
-  if (!packet_bytes || (end && (!pcm_ext || !packets))) return fail(c, LYRA_HIP_EINVAL, "encode_spans_dtx: null pointer");
-  DEVSCOPE(c);
-  const size_t nbytes = (size_t)(num_bits + 7) / 8, pcm_b = (size_t)rate / 50 * 2;
-  int16_t *d_in = nullptr, *d_p16 = nullptr;
-  uint8_t* d_out = nullptr;
-  int32_t* d_pb = nullptr;
-  const size_t e1 = (size_t)std::max<int64_t>(end, 1);
-  if (dalloc(&d_in, e1 * pcm_b / 2) != hipSuccess || dalloc(&d_out, e1 * nbytes) != hipSuccess || dalloc(&d_pb, e1) != hipSuccess ||
-      (rate != 16000 && dalloc(&d_p16, e1 * 320) != hipSuccess)) {
-    dfree(d_in, d_out, d_pb, d_p16);
-    return fail(c, LYRA_HIP_ENOMEM, "encode_spans_dtx: staging %lld frames failed", (long long)end);
-  }
-  hipStream_t st_ = c->se[0];
-  rc = 0;
-  if (end && (hipMemcpy(d_in, pcm_ext, (size_t)end * pcm_b, hipMemcpyHostToDevice) != hipSuccess ||
-              hipMemset(d_out, 0, (size_t)end * nbytes) != hipSuccess))
-    rc = fail(c, LYRA_HIP_EHIP, "encode_spans_dtx: upload failed");
-  if (!rc) rc = spans_dtx_call_dev(c, spans, n_spans, lane_ids, n_lanes, d_in, rate, d_p16, num_bits, d_out, d_pb);
-  if (!rc && hipStreamSynchronize(st_) != hipSuccess) rc = fail(c, LYRA_HIP_EHIP, "encode_spans_dtx: synchronise failed");
-  for (int s = 0; !rc && s < n_spans; ++s) {
-    const int64_t f = spans[s].first_frame, n = spans[s].n_frames;
-    if (n && (hipMemcpy(packets + f * nbytes, d_out + f * nbytes, n * nbytes, hipMemcpyDeviceToHost) != hipSuccess ||
-              hipMemcpy(packet_bytes + f, d_pb + f, n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess))
-      rc = fail(c, LYRA_HIP_EHIP, "encode_spans_dtx: download failed");
-  }
-  if (rc) (void)hipStreamSynchronize(st_);
-  dfree(d_in, d_out, d_pb, d_p16);
-  return rc;
-}
-
-int noise_spans_call_dev(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int n_spans, const int16_t* d_pcm16,
-                         int32_t* d_is_noise) {
-  const char* what = "noise_spans";
-  if (!c) return LYRA_HIP_EINVAL;
-  if (side != 0 && side != 1) return fail(c, LYRA_HIP_EINVAL, "%s: bad side", what);
-  SpanPlan dry;
-  int rc = span_plan_checked(c, side, spans, n_spans, nullptr, 0, &dry, what);
-  if (rc) return rc;
-  if (dry.end_frame && (!d_pcm16 || !d_is_noise)) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
-  if (reinterpret_cast<uintptr_t>(d_pcm16) & 15) return fail(c, LYRA_HIP_EINVAL, "%s: the PCM buffer must be 16-byte aligned", what);
-  int n_dx = 0;
-  long long frames = 0;
-  const long long lm_wgs = span_dtx_rows(spans, n_spans, nullptr, &n_dx, &frames);
-  if (lm_wgs < 0) return fail(c, LYRA_HIP_EINVAL, "%s: too many frames for one pass", what);
-  if (!n_dx) return 0;
-  DEVSCOPE(c);
-  if (!c->span_calls) c->span_calls = new SpanCalls();
-  SpanSide& S = span_calls_of(c)->side[side];
-  hipStream_t st_ = side == 0 ? c->se[0] : c->sd[0];
-  if ((rc = span_side_ensure(c, S, st_, 1, n_dx))) return rc;
-  if ((rc = span_dtx_ensure(c, S, st_, frames, n_dx))) return rc;
-  span_dtx_rows(spans, n_spans, reinterpret_cast<SpanDtxRow*>(S.h_rows), &n_dx, &frames);
-  if ((rc = side == 0 ? enc_side_begin(c, 0) : dec_side_begin(c, 0))) return rc;
-  if (side == 1 && (rc = wait_noise_stream(c))) return rc;   // the decoder-side slots may have been touched on the noise stream
-  HIPCHK(c, hipMemcpyAsync(S.d_rows, S.h_rows, (size_t)n_dx * sizeof(SpanRow), hipMemcpyHostToDevice, st_));
-  HIPCHK(c, hipEventRecord(S.ev_up, st_));
-  S.up_pending = true;
-  rc = launch_span_noise(c, side, st_, S, reinterpret_cast<const SpanDtxRow*>(S.d_rows), n_dx, lm_wgs, d_pcm16, d_is_noise, 1, 0,
-                         nullptr);
-  if (side == 0) {
-    if (!rc) rc = enc_side_done(c, 0);
-  } else {
-    if (!rc) rc = dec_side_done(c, 0, 1);
-    c->n_dec_calls++;
-  }
-  return rc;
-}
-
-int noise_spans_call_host(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int n_spans, const int16_t* pcm16,
-                          int32_t* is_noise) {
-  if (!c) return LYRA_HIP_EINVAL;
-  if (side != 0 && side != 1) return fail(c, LYRA_HIP_EINVAL, "noise_spans: bad side");
-  int64_t end = 0;
-  for (int s = 0; spans && s < n_spans; ++s)
-    if (spans[s].first_frame >= 0 && spans[s].n_frames >= 0) end = std::max<int64_t>(end, spans[s].first_frame + spans[s].n_frames);
-  if (end && (!pcm16 || !is_noise)) return fail(c, LYRA_HIP_EINVAL, "noise_spans: null pointer");
-  DEVSCOPE(c);
-  int16_t* d_in = nullptr;
-  int32_t* d_flag = nullptr;
-  const size_t e1 = (size_t)std::max<int64_t>(end, 1);
-  if (dalloc(&d_in, e1 * 320) != hipSuccess || dalloc(&d_flag, e1) != hipSuccess) {
-    dfree(d_in, d_flag);
-    return fail(c, LYRA_HIP_ENOMEM, "noise_spans: staging %lld frames failed", (long long)end);
-  }
-  hipStream_t st_ = side == 0 ? c->se[0] : c->sd[0];
-  int rc = 0;
-  if (end && hipMemcpy(d_in, pcm16, (size_t)end * 640, hipMemcpyHostToDevice) != hipSuccess)
-    rc = fail(c, LYRA_HIP_EHIP, "noise_spans: upload failed");
-  if (!rc) rc = noise_spans_call_dev(c, side, spans, n_spans, d_in, d_flag);
-  if (!rc && hipStreamSynchronize(st_) != hipSuccess) rc = fail(c, LYRA_HIP_EHIP, "noise_spans: synchronise failed");
-  for (int s = 0; !rc && s < n_spans; ++s)
-    if (spans[s].n_frames && hipMemcpy(is_noise + spans[s].first_frame, d_flag + spans[s].first_frame,
-                                       spans[s].n_frames * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
-      rc = fail(c, LYRA_HIP_EHIP, "noise_spans: download failed");
-  if (rc) (void)hipStreamSynchronize(st_);
-  dfree(d_in, d_flag);
-  return rc;
-}
 
 }  // namespace
 
@@ -613,76 +480,158 @@ int lyra_hip_spans_plan(int side, const lyra_hip_span* spans, int n_spans, const
 
 int lyra_hip_encode_spans_dev(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                               const int16_t* d_pcm, int num_bits, uint8_t* d_packets) {
-  SpanPlan P;
-  return spans_call_dev(c, true, spans, n_spans, lane_ids, n_lanes, d_pcm, num_bits, d_packets, &P);
+  return spans_call_dev(c, sp::SIDE_ENC, spans, n_spans, lane_ids, n_lanes, d_pcm, num_bits, d_packets);
 }
 
 int lyra_hip_decode_spans_dev(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                               const uint8_t* d_packets, int num_bits, int16_t* d_pcm) {
-  SpanPlan P;
-  return spans_call_dev(c, false, spans, n_spans, lane_ids, n_lanes, d_packets, num_bits, d_pcm, &P);
+  return spans_call_dev(c, sp::SIDE_DEC, spans, n_spans, lane_ids, n_lanes, d_packets, num_bits, d_pcm);
 }
 
 int lyra_hip_encode_spans(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                           const int16_t* pcm, int num_bits, uint8_t* packets) {
-  return spans_call_host(c, true, spans, n_spans, lane_ids, n_lanes, pcm, num_bits, packets);
+  return spans_call_host(c, sp::SIDE_ENC, spans, n_spans, lane_ids, n_lanes, pcm, num_bits, packets);
 }
 
 int lyra_hip_decode_spans(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                           const uint8_t* packets, int num_bits, int16_t* pcm) {
-  return spans_call_host(c, false, spans, n_spans, lane_ids, n_lanes, packets, num_bits, pcm);
+  return spans_call_host(c, sp::SIDE_DEC, spans, n_spans, lane_ids, n_lanes, packets, num_bits, pcm);
 }
 
 int lyra_hip_encode_spans_ext_dev(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                                   const int16_t* d_pcm_ext, int sample_rate_hz, int16_t* d_pcm16, int num_bits,
                                   uint8_t* d_packets) {
-  SpanPlan P;
-  SpanExt X;
-  X.rate = sample_rate_hz;
-  X.d_pcm16 = d_pcm16;
-  return spans_call_dev(c, true, spans, n_spans, lane_ids, n_lanes, d_pcm_ext, num_bits, d_packets, &P, X);
+  return spans_call_dev(c, sp::SIDE_ENC, spans, n_spans, lane_ids, n_lanes, d_pcm_ext, num_bits, d_packets,
+                        SpanExt{sample_rate_hz, d_pcm16});
 }
 
 int lyra_hip_decode_spans_ext_dev(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                                   const uint8_t* d_packets, int num_bits, int sample_rate_hz, int16_t* d_pcm16,
                                   int16_t* d_pcm_ext) {
-  SpanPlan P;
-  SpanExt X;
-  X.rate = sample_rate_hz;
-  X.d_pcm16 = d_pcm16;
-  return spans_call_dev(c, false, spans, n_spans, lane_ids, n_lanes, d_packets, num_bits, d_pcm_ext, &P, X);
+  return spans_call_dev(c, sp::SIDE_DEC, spans, n_spans, lane_ids, n_lanes, d_packets, num_bits, d_pcm_ext,
+                        SpanExt{sample_rate_hz, d_pcm16});
 }
 
 int lyra_hip_encode_spans_ext(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                               const int16_t* pcm_ext, int sample_rate_hz, int num_bits, uint8_t* packets) {
-  return spans_call_host(c, true, spans, n_spans, lane_ids, n_lanes, pcm_ext, num_bits, packets, sample_rate_hz);
+  return spans_call_host(c, sp::SIDE_ENC, spans, n_spans, lane_ids, n_lanes, pcm_ext, num_bits, packets, sample_rate_hz);
 }
 
 int lyra_hip_decode_spans_ext(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                               const uint8_t* packets, int num_bits, int sample_rate_hz, int16_t* pcm_ext) {
-  return spans_call_host(c, false, spans, n_spans, lane_ids, n_lanes, packets, num_bits, pcm_ext, sample_rate_hz);
+  return spans_call_host(c, sp::SIDE_DEC, spans, n_spans, lane_ids, n_lanes, packets, num_bits, pcm_ext, sample_rate_hz);
 }
 
 int lyra_hip_encode_spans_dtx_dev(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                                   const int16_t* d_pcm_ext, int sample_rate_hz, int16_t* d_pcm16, int num_bits,
                                   uint8_t* d_packets, int32_t* d_packet_bytes) {
-  return spans_dtx_call_dev(c, spans, n_spans, lane_ids, n_lanes, d_pcm_ext, sample_rate_hz, d_pcm16, num_bits, d_packets,
-                            d_packet_bytes);
+  const char* what = "encode_spans_dtx";
+  const int rate = sample_rate_hz;
+  const SpanExt X{rate, rate != 16000 ? d_pcm16 : nullptr};
+  SpanPlan dry;   // ids, lanes and frame ranges: the planner's rules, on the spans as given
+  int rc = span_check(c, what, sp::SIDE_ENC, &num_bits, spans, n_spans, lane_ids, n_lanes, d_pcm_ext, d_packets, X, &dry);
+  if (rc) return rc;
+  if (!d_packet_bytes) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
+  if (c->enc_noise_rate != rate)   // as lyra_hip_encode_ext_dev: the DTX estimator is created at the encoder's external rate
+    return fail(c, LYRA_HIP_EINVAL, "%s: DTX at %d Hz but the encoder-side noise estimator is set up for %d Hz "
+                "(call lyra_hip_set_encoder_sample_rate(%d) first)", what, rate, c->enc_noise_rate, rate);
+  const SpanPass rs = X.on() ? span_pass_rows<SpanRsRow>(spans, n_spans, nullptr) : SpanPass();
+  const SpanPass dx = span_pass_rows<SpanDtxRow>(spans, n_spans, nullptr);
+  if (rs.wgs < 0 || dx.wgs < 0) return fail(c, LYRA_HIP_EINVAL, "%s: too many frames for one pass", what);
+  DEVSCOPE(c);
+  hipStream_t st_;
+  SpanSide& S = span_side_open(c, sp::SIDE_ENC, &st_);
+  // all scratch for the worst case -- every frame active: at most one chunk per span and per lane -- before the first launch
+  const int rows_max = n_spans + n_lanes;
+  if ((rc = span_side_ensure(c, S, st_, rows_max, n_lanes + rs.n + dx.n))) return rc;
+  if ((rc = ensure_scratch(c, rows_max))) return rc;
+  if ((rc = span_dtx_ensure(c, S, st_, std::max<long long>(dx.frames, 1), std::max(dx.n, 1)))) return rc;
+  // upload 1, behind the batch rows' place: the lanes' reset rows, the resampler's rows, the estimator's rows
+  SpanRow* h_fix = S.h_rows + rows_max;
+  for (int l = 0; l < n_lanes; ++l) h_fix[l] = SpanRow{lane_ids[l], 0, 0, -1, 0, 0, 0};
+  if (rs.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(h_fix + n_lanes));
+  span_pass_rows(spans, n_spans, reinterpret_cast<SpanDtxRow*>(h_fix + n_lanes + rs.n));
+  const SpanRow* d_fix = S.d_rows + rows_max;
+  const SpanRsRow* d_rs_rows = reinterpret_cast<const SpanRsRow*>(d_fix + n_lanes);
+  const SpanDtxRow* d_dx_rows = reinterpret_cast<const SpanDtxRow*>(d_fix + n_lanes + rs.n);
+  if ((rc = span_side_begin(c, sp::SIDE_ENC))) return rc;
+  if ((rc = span_upload_rows(c, S, st_, rows_max, n_lanes + rs.n + dx.n))) return rc;
+  const int16_t* d_src16 = d_pcm_ext;
+  if ((rc = span_encode_front(c, st_, X, d_rs_rows, rs, &d_src16))) return rc;
+  SpanPlan P;
+  std::vector<lyra_hip_span> compact((size_t)n_spans);
+  if (dx.n) {
+    if ((rc = launch_span_noise(c, 0, st_, S, d_dx_rows, dx.n, dx.wgs, d_src16, d_packet_bytes, 0, (num_bits + 7) / 8, S.d_map)))
+      return rc;
+    // the one host wait of the call: the plan depends on the decisions
+    HIPCHK(c, hipStreamSynchronize(st_));
+    S.up_pending = false;
+  }
+  {   // what the encoder sees of span s: its non-noise hops, at the start of its region of the map
+    long long region = 0;
+    int r = 0;
+    for (int s = 0; s < n_spans; ++s) {
+      compact[s] = lyra_hip_span{spans[s].stream_id, region, spans[s].n_frames ? (int64_t)S.h_counts[r++] : 0};
+      if (compact[s].n_frames < 0 || compact[s].n_frames > spans[s].n_frames)
+        return fail(c, LYRA_HIP_EHIP, "%s: the scan's count of span %d is out of range", what, s);
+      region += spans[s].n_frames;
+    }
+  }
+  if ((rc = span_plan_checked(c, sp::SIDE_ENC, compact.data(), n_spans, lane_ids, n_lanes, &P, what))) return rc;
+  // upload 2: the batch rows (the pinned rows in front of upload 1's, so neither waits for the other)
+  span_fill_rows(P, compact.data(), lane_ids, 0, S.h_rows);
+  if ((rc = span_upload_rows(c, S, st_, 0, (int)P.chunks.size()))) return rc;
+  rc = span_run_steps(c, true, S, st_, P, S.h_rows, S.d_rows, d_fix, n_lanes, d_src16, num_bits, d_packets, S.d_map);
+  return span_side_close(c, sp::SIDE_ENC, rc);
 }
 
+// host-buffer form: packet rows of noise frames read back as zeros
 int lyra_hip_encode_spans_dtx(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                               const int16_t* pcm_ext, int sample_rate_hz, int num_bits, uint8_t* packets, int32_t* packet_bytes) {
-  return spans_dtx_call_host(c, spans, n_spans, lane_ids, n_lanes, pcm_ext, sample_rate_hz, num_bits, packets, packet_bytes);
+  const char* what = "encode_spans_dtx";
+  const int rc = span_check_head(c, what, sp::SIDE_ENC, &num_bits, sample_rate_hz);
+  if (rc) return rc;
+  if (!packet_bytes) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
+  SpanBuf B[] = {{SPAN_IN, (void*)pcm_ext, (size_t)sample_rate_hz / 50 * 2}, {SPAN_OUT, packets, (size_t)(num_bits + 7) / 8, true},
+                 {SPAN_OUT, packet_bytes, sizeof(int32_t)}, {SPAN_WORK, nullptr, sample_rate_hz != 16000 ? (size_t)640 : 0}};
+  return span_staged(c, what, sp::SIDE_ENC, spans, n_spans, B, [&] {
+    return lyra_hip_encode_spans_dtx_dev(c, spans, n_spans, lane_ids, n_lanes, (const int16_t*)B[0].d, sample_rate_hz,
+                                         (int16_t*)B[3].d, num_bits, B[1].d, (int32_t*)B[2].d);
+  });
 }
 
 int lyra_hip_noise_spans_dev(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int n_spans, const int16_t* d_pcm16,
                              int32_t* d_is_noise) {
-  return noise_spans_call_dev(c, side, spans, n_spans, d_pcm16, d_is_noise);
+  const char* what = "noise_spans";
+  SpanPlan dry;
+  int rc = span_check(c, what, side, nullptr, spans, n_spans, nullptr, 0, d_pcm16, d_is_noise, SpanExt(), &dry);
+  if (rc) return rc;
+  const SpanPass dx = span_pass_rows<SpanDtxRow>(spans, n_spans, nullptr);
+  if (dx.wgs < 0) return fail(c, LYRA_HIP_EINVAL, "%s: too many frames for one pass", what);
+  if (!dx.n) return 0;
+  DEVSCOPE(c);
+  hipStream_t st_;
+  SpanSide& S = span_side_open(c, side, &st_);
+  if ((rc = span_side_ensure(c, S, st_, 1, dx.n))) return rc;
+  if ((rc = span_dtx_ensure(c, S, st_, dx.frames, dx.n))) return rc;
+  span_pass_rows(spans, n_spans, reinterpret_cast<SpanDtxRow*>(S.h_rows));
+  if ((rc = span_side_begin(c, side))) return rc;
+  if (side == sp::SIDE_DEC && (rc = wait_noise_stream(c))) return rc;   // the decoder-side slots may have been touched on the noise stream
+  if ((rc = span_upload_rows(c, S, st_, 0, dx.n))) return rc;
+  rc = launch_span_noise(c, side, st_, S, reinterpret_cast<const SpanDtxRow*>(S.d_rows), dx.n, dx.wgs, d_pcm16, d_is_noise, 1, 0,
+                         nullptr);
+  return span_side_close(c, side, rc);
 }
 
 int lyra_hip_noise_spans(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int n_spans, const int16_t* pcm16,
                          int32_t* is_noise) {
-  return noise_spans_call_host(c, side, spans, n_spans, pcm16, is_noise);
+  const char* what = "noise_spans";
+  const int rc = span_check_head(c, what, side, nullptr, 16000);
+  if (rc) return rc;
+  SpanBuf B[] = {{SPAN_IN, (void*)pcm16, 640}, {SPAN_OUT, is_noise, sizeof(int32_t)}};
+  return span_staged(c, what, side, spans, n_spans, B, [&] {
+    return lyra_hip_noise_spans_dev(c, side, spans, n_spans, (const int16_t*)B[0].d, (int32_t*)B[1].d);
+  });
 }
 
 }  // extern "C"

@@ -28,6 +28,12 @@ namespace {
 struct Ctx {  // RAII around one GPU context
   lyra_hip_ctx* c = nullptr;
   ~Ctx() { if (c) lyra_hip_destroy(c); }
+  // what: "encoder" / "decoder", for the log line
+  bool Create(const ghc::filesystem::path& model_path, int device, int max_streams, const char* what) {
+    if (lyra_hip_create(model_path.string().c_str(), device, max_streams, LYRA_HIP_REQUANT_DEFAULT, &c) == 0) return true;
+    LOG(ERROR) << "Could not create lyra " << what << ": " << lyra_hip_last_error(nullptr);
+    return false;
+  }
 };
 
 bool CheckScope(int num_channels, int sample_rate_hz, bool enable_preprocessing, bool enable_dtx) {
@@ -44,6 +50,20 @@ bool CheckScope(int num_channels, int sample_rate_hz, bool enable_preprocessing,
     return false;
   }
   (void)enable_dtx;   // LyraEncoder's DTX: lyra_hip_encode_dtx per hop / lyra_hip_encode_spans_dtx
+  return true;
+}
+
+// num_bits of the bitrate whose packets are packet_size bytes, -1 (logged): none
+int NumBitsOfPacketSize(int packet_size) {
+  for (int br : {3200, 6000, 9200})
+    if (BatchBitrateToPacketSize(br) == packet_size) return BatchBitrateToNumQuantizedBits(br);
+  LOG(ERROR) << "The packet size (" << packet_size << " bytes) is not supported.";
+  return -1;
+}
+
+bool WholePackets(const std::vector<std::vector<uint8_t>>& packet_streams, int packet_size) {
+  for (const auto& p : packet_streams)
+    if (p.size() % packet_size != 0) { LOG(ERROR) << "Encoded stream is not a whole number of packets."; return false; }
   return true;
 }
 
@@ -115,10 +135,7 @@ bool EncodeWavs(const std::vector<std::vector<int16_t>>& wav_data, int num_chann
   if (packet_sizes) packet_sizes->assign(n, {});
   if (n == 0) return true;
   Ctx ctx;
-  if (lyra_hip_create(model_path.string().c_str(), device, n, LYRA_HIP_REQUANT_DEFAULT, &ctx.c) != 0) {
-    LOG(ERROR) << "Could not create lyra encoder: " << lyra_hip_last_error(nullptr);
-    return false;
-  }
+  if (!ctx.Create(model_path, device, n, "encoder")) return false;
   // a DTX LyraEncoder hands its NoiseEstimator the files' rate (lyra_encoder.cc:82-85)
   if (enable_dtx && lyra_hip_set_encoder_sample_rate(ctx.c, sample_rate_hz) != 0) {
     LOG(ERROR) << "Could not set up the noise estimator: " << lyra_hip_last_error(ctx.c);
@@ -239,23 +256,16 @@ bool DecodeFeaturesBatch(const std::vector<std::vector<uint8_t>>& packet_streams
                          const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
                          int device) {
   if (!CheckScope(1, sample_rate_hz, false, false)) return false;
-  int num_bits = -1;
-  for (int br : {3200, 6000, 9200})
-    if (BatchBitrateToPacketSize(br) == packet_size) num_bits = BatchBitrateToNumQuantizedBits(br);
-  if (num_bits < 0) { LOG(ERROR) << "The packet size (" << packet_size << " bytes) is not supported."; return false; }
+  const int num_bits = NumBitsOfPacketSize(packet_size);
+  if (num_bits < 0) return false;
   const int n = (int)packet_streams.size();
   decoded_audio->assign(n, {});
   if (n == 0) return true;
+  if (!WholePackets(packet_streams, packet_size)) return false;
   size_t max_packets = 0;
-  for (const auto& p : packet_streams) {
-    if (p.size() % packet_size != 0) { LOG(ERROR) << "Encoded stream is not a whole number of packets."; return false; }
-    max_packets = std::max(max_packets, p.size() / packet_size);
-  }
+  for (const auto& p : packet_streams) max_packets = std::max(max_packets, p.size() / packet_size);
   Ctx ctx;
-  if (lyra_hip_create(model_path.string().c_str(), device, n, LYRA_HIP_REQUANT_DEFAULT, &ctx.c) != 0) {
-    LOG(ERROR) << "Could not create lyra decoder: " << lyra_hip_last_error(nullptr);
-    return false;
-  }
+  if (!ctx.Create(model_path, device, n, "decoder")) return false;
   const size_t hop_samples = (size_t)sample_rate_hz / 50;
   const bool resample = sample_rate_hz != kBatchInternalSampleRateHz;
   std::vector<int32_t> ids;
@@ -326,6 +336,17 @@ bool HaveSpanCalls(int sample_rate_hz) {
   }
   return true;
 }
+// The span call of a side at a rate.  16 kHz stays on the plain call: it also runs against a library that has no `_ext` calls yet.
+int EncodeSpansAt(int rate, lyra_hip_ctx* c, const SpanJob& j, const int16_t* pcm, int num_bits, uint8_t* packets) {
+  const int n = (int)j.spans.size(), n_lanes = (int)j.lanes.size();
+  if (rate == kBatchInternalSampleRateHz) return lyra_hip_encode_spans(c, j.spans.data(), n, j.lanes.data(), n_lanes, pcm, num_bits, packets);
+  return lyra_hip_encode_spans_ext(c, j.spans.data(), n, j.lanes.data(), n_lanes, pcm, rate, num_bits, packets);
+}
+int DecodeSpansAt(int rate, lyra_hip_ctx* c, const SpanJob& j, const uint8_t* packets, int num_bits, int16_t* pcm) {
+  const int n = (int)j.spans.size(), n_lanes = (int)j.lanes.size();
+  if (rate == kBatchInternalSampleRateHz) return lyra_hip_decode_spans(c, j.spans.data(), n, j.lanes.data(), n_lanes, packets, num_bits, pcm);
+  return lyra_hip_decode_spans_ext(c, j.spans.data(), n, j.lanes.data(), n_lanes, packets, num_bits, rate, pcm);
+}
 bool HaveSpanDtxCall() {
   if (lyra_hip_encode_spans_dtx) return true;
   LOG(ERROR) << "This build of the lyra_hip library has no time-parallel span call with DTX.";
@@ -349,43 +370,26 @@ bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, i
   std::vector<int16_t> pcm;
   const SpanJob job = MakeSpanJob(wav_data, (size_t)sample_rate_hz / 50, LYRA_HIP_SIDE_ENCODER, num_lanes, &pcm);
   Ctx ctx;
-  if (lyra_hip_create(model_path.string().c_str(), device, n + (int)job.lanes.size(), LYRA_HIP_REQUANT_DEFAULT, &ctx.c) != 0) {
-    LOG(ERROR) << "Could not create lyra encoder: " << lyra_hip_last_error(nullptr);
-    return false;
-  }
+  if (!ctx.Create(model_path, device, n + (int)job.lanes.size(), "encoder")) return false;
   const size_t packet_size = (size_t)BatchBitrateToPacketSize(bitrate);
   std::vector<uint8_t> packets((size_t)job.frames * packet_size);
-  if (enable_dtx) {   // the non-empty packets of every file, in order (encoder_main_lib.cc:77-88)
-    std::vector<int32_t> sizes((size_t)job.frames, 0);
-    if (lyra_hip_set_encoder_sample_rate(ctx.c, sample_rate_hz) != 0 ||
-        lyra_hip_encode_spans_dtx(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), pcm.data(), sample_rate_hz,
-                                  num_bits, packets.data(), sizes.data()) != 0) {
-      LOG(ERROR) << "Unable to encode features: " << lyra_hip_last_error(ctx.c);
-      return false;
-    }
-    for (int i = 0; i < n; ++i) {
-      auto& dst = (*encoded_features)[i];
-      for (int64_t f = job.spans[i].first_frame; f < job.spans[i].first_frame + job.spans[i].n_frames; ++f) {
-        dst.insert(dst.end(), packets.begin() + f * packet_size, packets.begin() + f * packet_size + sizes[f]);
-        if (packet_sizes) (*packet_sizes)[i].push_back(sizes[f]);
-      }
-    }
-    return true;
-  }
-  // (16 kHz stays on the plain call: it also runs against a library that has no `_ext` calls yet)
-  if ((sample_rate_hz == kBatchInternalSampleRateHz
-           ? lyra_hip_encode_spans(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), pcm.data(), num_bits,
-                                   packets.data())
-           : lyra_hip_encode_spans_ext(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), pcm.data(),
-                                       sample_rate_hz, num_bits, packets.data())) != 0) {
+  // bytes of every frame's packet: without DTX the packet size, with it what the call reports (0: an empty packet)
+  std::vector<int32_t> sizes((size_t)job.frames, enable_dtx ? 0 : (int32_t)packet_size);
+  const bool ok = enable_dtx ? lyra_hip_set_encoder_sample_rate(ctx.c, sample_rate_hz) == 0 &&
+                                   lyra_hip_encode_spans_dtx(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(),
+                                                             pcm.data(), sample_rate_hz, num_bits, packets.data(), sizes.data()) == 0
+                             : EncodeSpansAt(sample_rate_hz, ctx.c, job, pcm.data(), num_bits, packets.data()) == 0;
+  if (!ok) {
     LOG(ERROR) << "Unable to encode features: " << lyra_hip_last_error(ctx.c);
     return false;
   }
-  for (int i = 0; i < n; ++i)
-    (*encoded_features)[i].assign(packets.begin() + job.spans[i].first_frame * packet_size,
-                                  packets.begin() + (job.spans[i].first_frame + job.spans[i].n_frames) * packet_size);
-  if (packet_sizes)
-    for (int i = 0; i < n; ++i) (*packet_sizes)[i].assign((size_t)job.spans[i].n_frames, (int32_t)packet_size);
+  for (int i = 0; i < n; ++i) {   // the non-empty packets of every file, in order (encoder_main_lib.cc:77-88)
+    auto& dst = (*encoded_features)[i];
+    for (int64_t f = job.spans[i].first_frame; f < job.spans[i].first_frame + job.spans[i].n_frames; ++f) {
+      dst.insert(dst.end(), packets.begin() + f * packet_size, packets.begin() + f * packet_size + sizes[f]);
+      if (packet_sizes) (*packet_sizes)[i].push_back(sizes[f]);
+    }
+  }
   return true;
 }
 
@@ -400,30 +404,19 @@ bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_
                                 const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
                                 int num_lanes, int device) {
   if (!CheckScope(1, sample_rate_hz, false, false)) return false;
-  int num_bits = -1;
-  for (int br : {3200, 6000, 9200})
-    if (BatchBitrateToPacketSize(br) == packet_size) num_bits = BatchBitrateToNumQuantizedBits(br);
-  if (num_bits < 0) { LOG(ERROR) << "The packet size (" << packet_size << " bytes) is not supported."; return false; }
-  if (!HaveSpanCalls(sample_rate_hz)) return false;
+  const int num_bits = NumBitsOfPacketSize(packet_size);
+  if (num_bits < 0 || !HaveSpanCalls(sample_rate_hz)) return false;
   const int n = (int)packet_streams.size();
   decoded_audio->assign(n, {});
   if (n == 0) return true;
-  for (const auto& p : packet_streams)
-    if (p.size() % packet_size != 0) { LOG(ERROR) << "Encoded stream is not a whole number of packets."; return false; }
+  if (!WholePackets(packet_streams, packet_size)) return false;
   std::vector<uint8_t> packets;
   const SpanJob job = MakeSpanJob(packet_streams, (size_t)packet_size, LYRA_HIP_SIDE_DECODER, num_lanes, &packets);
   Ctx ctx;
-  if (lyra_hip_create(model_path.string().c_str(), device, n + (int)job.lanes.size(), LYRA_HIP_REQUANT_DEFAULT, &ctx.c) != 0) {
-    LOG(ERROR) << "Could not create lyra decoder: " << lyra_hip_last_error(nullptr);
-    return false;
-  }
+  if (!ctx.Create(model_path, device, n + (int)job.lanes.size(), "decoder")) return false;
   const size_t hop_samples = (size_t)sample_rate_hz / 50;
   std::vector<int16_t> pcm((size_t)job.frames * hop_samples);
-  if ((sample_rate_hz == kBatchInternalSampleRateHz
-           ? lyra_hip_decode_spans(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), packets.data(), num_bits,
-                                   pcm.data())
-           : lyra_hip_decode_spans_ext(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), packets.data(),
-                                       num_bits, sample_rate_hz, pcm.data())) != 0) {
+  if (DecodeSpansAt(sample_rate_hz, ctx.c, job, packets.data(), num_bits, pcm.data()) != 0) {
     LOG(ERROR) << "Could not decode samples: " << lyra_hip_last_error(ctx.c);
     return false;
   }
