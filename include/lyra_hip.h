@@ -673,8 +673,31 @@ long lyra_hip_import_errors(lyra_hip_ctx* ctx, int clear);
  *   estimator slot afterwards what the hop-by-hop calls leave.  Side ENCODER uses the constants and filterbank of
  *   lyra_hip_set_encoder_sample_rate and is an encode-side call, side DECODER those of 16 kHz and is a decode-side call on
  *   lyra_hip_stream_decode().  No lanes; the `_dev` form does not synchronise.
- * Out of scope: packet loss / comfort noise on spans (the decoder-side estimator feeds back through the decoded audio),
- * per-span sample rates, per-span bitrates.  LYRA_HIP_SUBBATCHES > 1 is accepted (the call is not split). */
+ *   Packet loss: lyra_hip_decode_spans_lossy[_dev] is lyra_hip_decode_lossy_dev(sample_rate_hz) -- SetEncodedPacket when a packet
+ *   arrived + DecodeSamples(one hop), with concealment, comfort noise and cross-fades -- over the spans.  packet_bytes is a HOST
+ *   array like spans and lane_ids, [frames], 0 = no packet (lost, or DTX's empty packet), else num_bits / 8 rounded up: a
+ *   receiver knows which packets arrived.  The loss state machine depends on that pattern and on the stream's control word
+ *   alone, so every tick's legs are planned on the host (lyra_hip_spans_lossy_plan): the generative model advances on its ticks
+ *   only, from the packet or from zero features -- convolution history again, so planner, lanes, warm-up and hand-over apply to
+ *   the compacted list of those ticks; the decoder-side NoiseEstimator is a recurrence over the generative hops of the received
+ *   ticks (one log-mel launch, one wavefront per span); a comfort-noise tick reads the estimate as it stood after the received
+ *   frames in front of it, which the scan leaves as snapshots, and its phases are counter-based, so only the overlap-add is
+ *   ordered; mix and resampler are passes over all frames.
+ *   Per span frame d_pcm16 [frames][320] (required), d_pcm_ext [frames][rate / 50] (rate != 16000), d_is_noise (unchanged across
+ *   ticks without a packet) and d_is_comfort_noise (both optional) are BIT FOR BIT what lyra_hip_decode_lossy_dev gives hop by
+ *   hop on that stream.  Afterwards the span streams' three decoder stage regions, decoder-side estimator slot (log-mel history
+ *   included), comfort-noise slot (hop counter, accumulator, control word) and output resampler slot are what those calls
+ *   leave: lyra_hip_export_streams returns the same bytes.  A span continues a live stream, mid-burst included, and
+ *   lyra_hip_decode_lossy*_dev calls may follow it.  Lanes lend decoder stage state only and come back reset; their other
+ *   slots are untouched.  Frames outside every span are untouched in every buffer; a span with no generative tick runs no chunk.
+ *   A packet_bytes value that is neither 0 nor the size of num_bits, bad ids, lanes, ranges, pointers, alignment or rate and
+ *   anything the planner refuses: LYRA_HIP_EINVAL with nothing enqueued and no state changed.
+ *   The call is ONE decode-side call and everything it writes completes on lyra_hip_stream_decode() (UNLIKE the hop-by-hop
+ *   call, whose outputs complete on the noise stream).  It BLOCKS THE HOST ONCE, at its start, to read the span streams' 4-byte
+ *   control words; everything after that is enqueued without synchronising.  lyra_hip_set_serial is supported.  The state is the
+ *   hop-synchronous call's: the "do not mix" rules of lyra_hip_decode_lossy_dev hold, lyra_hip_decode_samples_dev keeps its own.
+ * Out of scope: per-frame bitrates, per-span sample rates, request sizes other than one hop on spans.
+ * LYRA_HIP_SUBBATCHES > 1 is accepted (the calls are not split). */
 typedef struct lyra_hip_span { int32_t stream_id; int64_t first_frame; int64_t n_frames; } lyra_hip_span;
 /* warm-up hops of side LYRA_HIP_SIDE_ENCODER / LYRA_HIP_SIDE_DECODER (25 / 25); LYRA_HIP_EINVAL for any other side */
 int lyra_hip_span_warmup_frames(int side);
@@ -706,6 +729,15 @@ int lyra_hip_noise_spans_dev(lyra_hip_ctx* ctx, int side, const lyra_hip_span* s
                              const int16_t* d_pcm16 /* [frames][320] */, int32_t* d_is_noise /* [frames] */);
 int lyra_hip_noise_spans(lyra_hip_ctx* ctx, int side, const lyra_hip_span* spans, int n_spans, const int16_t* pcm16,
                          int32_t* is_noise);
+int lyra_hip_decode_spans_lossy_dev(lyra_hip_ctx* ctx, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                                    const uint8_t* d_packets /* [frames][bytes of num_bits] */,
+                                    const int32_t* packet_bytes /* HOST [frames]: 0 = no packet, else the size of num_bits */,
+                                    int num_bits, int sample_rate_hz, int16_t* d_pcm16 /* [frames][320], required */,
+                                    int16_t* d_pcm_ext /* [frames][rate / 50]; may be NULL at 16000 */,
+                                    int32_t* d_is_noise /* [frames] or NULL */, int32_t* d_is_comfort_noise /* [frames] or NULL */);
+int lyra_hip_decode_spans_lossy(lyra_hip_ctx* ctx, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                                const uint8_t* packets, const int32_t* packet_bytes, int num_bits, int sample_rate_hz,
+                                int16_t* pcm16, int16_t* pcm_ext, int32_t* is_noise, int32_t* is_comfort_noise);
 /* The planner of the four calls, a pure function (no context, no device).  Chunk r is row r of the call's batch: it runs on
  * stream_id for n_warmup + n_frames steps; step i reads buffer frame first_frame - n_warmup + i and from step n_warmup on
  * writes its output there.  Chunk 0 of a span runs on the span's own stream with no warm-up; the others on lanes, behind
@@ -723,6 +755,28 @@ typedef struct lyra_hip_span_chunk {
 } lyra_hip_span_chunk;
 int lyra_hip_spans_plan(int side, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes, int max_streams,
                         lyra_hip_span_chunk* chunks, int cap, int* n_steps);
+/* The planner of lyra_hip_decode_spans_lossy, a pure function too (lyra_amd/csrc/spans_lossy_plan.h).  ctl_in[s]: the control
+ * word of span s's stream on entry (0 for a fresh stream; lyra_amd/csrc/lossy_plan.h).  Per span, counts[s]; the lists of all
+ * spans lie span after span, dense, in arrays of (sum of n_frames) entries each, any of which may be NULL:
+ *   gen_frames / gen_received  buffer frames of the ticks that run the generative model, 1 = from the packet, 0 = concealed
+ *   rx_frames                  buffer frames of the received ticks (the estimator's input, in order)
+ *   cng_frames / cng_versions  buffer frames of the comfort-noise ticks and the number of received frames of the span in front of
+ *                              each: the version of the estimate it reads (0 = the estimate on entry)
+ *   versions                   those versions, rising, each once: what the scan snapshots
+ *   info                       lossy_info per frame of the span
+ * chunks / n_steps: lyra_hip_spans_plan(DECODER) on the compacted spans (stream_id, start in gen_frames, n_gen): first_frame
+ * counts in gen_frames.  Returns the number of chunks; LYRA_HIP_EINVAL for what lyra_hip_spans_plan refuses, a packet_bytes
+ * value that is neither 0 nor packet_size, cap too small. */
+typedef struct lyra_hip_span_lossy_counts {
+  int64_t n_gen, n_received, n_cng, n_versions;
+  uint32_t ctl_out; /* the control word after the span */
+  int32_t reserved;
+} lyra_hip_span_lossy_counts;
+int lyra_hip_spans_lossy_plan(const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes, int max_streams,
+                              const int32_t* packet_bytes, int packet_size, const uint32_t* ctl_in,
+                              lyra_hip_span_lossy_counts* counts, int64_t* gen_frames, uint8_t* gen_received, int64_t* rx_frames,
+                              int64_t* cng_frames, int32_t* cng_versions, int32_t* versions, int32_t* info,
+                              lyra_hip_span_chunk* chunks, int cap, int* n_steps);
 
 /* The context's FOUR HIP streams (hipStream_t as void*), for event timing / ordering by the caller: encode side, decode
  * side, the quantizer stream of lyra_hip_encode_dev / lyra_hip_encode_dtx_dev, and the noise stream.

@@ -119,6 +119,47 @@ def spans_plan(side, spans, lane_ids, max_streams, lib=None):
     return chunks[:n], steps.value
 
 
+SPAN_LOSSY_COUNTS_DTYPE = np.dtype([("n_gen", "<i8"), ("n_received", "<i8"), ("n_cng", "<i8"), ("n_versions", "<i8"),
+                                    ("ctl_out", "<u4"), ("reserved", "<i4")], align=True)
+
+
+def spans_lossy_plan(spans, packet_bytes, packet_size_bytes, ctl_in, lane_ids, max_streams, lib=None):
+    """The planner of decode_spans_lossy (lyra_hip_spans_lossy_plan; no GPU).  packet_bytes int32 [frames] (0 = no packet),
+    ctl_in: the span streams' control words on entry.  Returns a dict: counts (SPAN_LOSSY_COUNTS_DTYPE per span), the dense lists
+    gen_frames, gen_received, rx_frames, cng_frames, cng_versions, versions, info (span after span), chunks (SPAN_CHUNK_DTYPE,
+    first_frame counting in gen_frames) and n_steps.  LyraHipError for what the call refuses."""
+    L = lib or _load()
+    sp = _spans(spans)
+    lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
+    pb = np.ascontiguousarray(np.asarray(packet_bytes, np.int32).reshape(-1))
+    ctl = np.ascontiguousarray(np.asarray(ctl_in, np.uint32).reshape(-1))
+    if ctl.size != sp.size:
+        raise LyraHipError("spans_lossy_plan: one control word per span")
+    if sp.size and (np.any(sp["first_frame"] < 0) or np.any(sp["n_frames"] < 0) or
+                    int(np.max(sp["first_frame"] + sp["n_frames"])) > pb.size):
+        raise LyraHipError(f"spans_lossy_plan: a span lies outside the {pb.size} frames of packet_bytes")
+    T = int(sp["n_frames"].sum()) if sp.size else 0
+    counts = np.zeros(max(sp.size, 1), SPAN_LOSSY_COUNTS_DTYPE)
+    out = {k: np.zeros(max(T, 1), d) for k, d in (("gen_frames", np.int64), ("gen_received", np.uint8), ("rx_frames", np.int64),
+                                                    ("cng_frames", np.int64), ("cng_versions", np.int32), ("versions", np.int32),
+                                                    ("info", np.int32))}
+    chunks = np.zeros(sp.size + lanes.size + 1, SPAN_CHUNK_DTYPE)
+    steps = C.c_int(0)
+    n = L.lyra_hip_spans_lossy_plan(sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size, int(max_streams), pb.ctypes.data,
+                                    int(packet_size_bytes), ctl.ctypes.data, counts.ctypes.data,
+                                    *(out[k].ctypes.data for k in ("gen_frames", "gen_received", "rx_frames", "cng_frames",
+                                                                   "cng_versions", "versions", "info")),
+                                    chunks.ctypes.data, chunks.size, C.addressof(steps))
+    if n < 0:
+        raise LyraHipError("lyra_hip_spans_lossy_plan: invalid spans, lanes or packet sizes")
+    counts = counts[:sp.size]
+    size = {"gen_frames": "n_gen", "gen_received": "n_gen", "rx_frames": "n_received", "cng_frames": "n_cng",
+            "cng_versions": "n_cng", "versions": "n_versions"}
+    res = {k: v[:int(counts[size[k]].sum())] for k, v in out.items() if k in size}
+    res.update(info=out["info"][:T], counts=counts, chunks=chunks[:n], n_steps=steps.value)
+    return res
+
+
 def _load(path=None):
     """The C-ABI library (default: library_path()); a second path loads a build variant beside it (lyra_amd/variants/)."""
     path = os.path.abspath(path or library_path())
@@ -214,6 +255,10 @@ def _load(path=None):
         L.lyra_hip_encode_spans_dtx.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, vp, vp]
         L.lyra_hip_noise_spans_dev.argtypes = [vp, ci, vp, ci, vp, vp]
         L.lyra_hip_noise_spans.argtypes = [vp, ci, vp, ci, vp, vp]
+    if hasattr(L, "lyra_hip_decode_spans_lossy"):
+        for suf in ("", "_dev"):
+            getattr(L, f"lyra_hip_decode_spans_lossy{suf}").argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp]
+        L.lyra_hip_spans_lossy_plan.argtypes = [vp, ci, vp, ci, ci, vp, ci, vp] + [vp] * 8 + [vp, ci, vp]
     L.lyra_hip_set_cng_seed.argtypes = [vp, C.c_uint64]
     L.lyra_hip_set_encoder_sample_rate.argtypes = [vp, C.c_int]
     L.lyra_hip_stream.restype = vp
@@ -881,6 +926,47 @@ class LyraHip:
         a, _held = self._span_args(spans, (), F)
         self._dev_call(self.L.lyra_hip_noise_spans_dev, self._SIDES[side], *a[:2],
                        self._dev_ptr(d_pcm, "int16", (F, HOP), "pcm"), self._dev_ptr(d_is_noise, "int32", (F,), "is_noise"))
+
+    # -- packet loss on spans (lyra_hip_decode_spans_lossy) -------------------------------------------------------------------
+    @staticmethod
+    def _span_packet_bytes(packet_bytes, frames):
+        pb = np.ascontiguousarray(np.asarray(packet_bytes, np.int32).reshape(-1))
+        if pb.size != frames:
+            raise LyraHipError(f"spans: packet_bytes has {pb.size} entries for {frames} frames")
+        return pb
+
+    def decode_spans_lossy(self, spans, packets, packet_bytes, num_bits, lane_ids=(), sample_rate_hz=16000):
+        """decode_lossy_dev per hop over long spans, time-parallel and bit for bit: packets uint8 [frames][bytes], packet_bytes
+        int32 [frames] (0 = no packet: lost, or DTX's empty packet).  Returns (pcm16 int16 [frames][320], pcm_ext int16
+        [frames][sample_rate_hz / 50] or None at 16000, is_noise int32 [frames], is_comfort_noise int32 [frames]); rows outside
+        every span are 0.  The lanes' decoder stage state is reset afterwards."""
+        packets = _np(packets, np.uint8, (-1, packet_size(num_bits)))
+        F = packets.shape[0]
+        pb = self._span_packet_bytes(packet_bytes, F)
+        pcm16 = np.zeros((F, HOP), np.int16)
+        ext = np.zeros((F, self._span_hop(sample_rate_hz)), np.int16) if sample_rate_hz != 16000 else None
+        is_noise, is_cn = np.zeros(F, np.int32), np.zeros(F, np.int32)
+        a, _held = self._span_args(spans, lane_ids, F)
+        self._chk(self.L.lyra_hip_decode_spans_lossy(self.h, *a, packets.ctypes.data, pb.ctypes.data, num_bits, sample_rate_hz,
+                                                     pcm16.ctypes.data, ext.ctypes.data if ext is not None else None,
+                                                     is_noise.ctypes.data, is_cn.ctypes.data))
+        return pcm16, ext, is_noise, is_cn
+
+    def decode_spans_lossy_dev(self, spans, d_packets, packet_bytes, num_bits, d_pcm16, lane_ids=(), sample_rate_hz=16000,
+                               d_pcm_ext=None, d_is_noise=None, d_is_comfort_noise=None):
+        """decode_spans_lossy on device buffers; packet_bytes stays a host array like spans and lane_ids.  d_pcm16 int16
+        [frames][320] is required, d_pcm_ext int16 [frames][sample_rate_hz / 50] at a rate other than 16000, d_is_noise /
+        d_is_comfort_noise int32 [frames] are optional.  Blocks the host once, at its start, for the span streams' control words;
+        everything else is enqueued on the decode stream."""
+        F = d_packets.shape[0]
+        pb = self._span_packet_bytes(packet_bytes, F)
+        a, _held = self._span_args(spans, lane_ids, F)
+        self._dev_call(self.L.lyra_hip_decode_spans_lossy_dev, *a,
+                       self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"), pb.ctypes.data, num_bits,
+                       sample_rate_hz, self._dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"),
+                       self._opt_dev_ptr(d_pcm_ext, "int16", (F, self._span_hop(sample_rate_hz)), "external-rate pcm"),
+                       self._opt_dev_ptr(d_is_noise, "int32", (F,), "is_noise"),
+                       self._opt_dev_ptr(d_is_comfort_noise, "int32", (F,), "is_comfort_noise"))
 
     def noise_receive_dev(self, d_ids, d_pcm, d_is_noise, side="decoder"):
         """NoiseEstimator::ReceiveSamples on device buffers: pcm int16 [B][320] -> is_noise int32 [B]."""

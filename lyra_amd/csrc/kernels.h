@@ -181,6 +181,13 @@ constexpr int TWIN_FADE_LO = -640, TWIN_FADE_N = 1921;   // fade_progress range 
 __global__ void twin_scatter_kernel(const int16_t* src, const int32_t* ids, int B, int16_t* dst);
 __global__ void twin_assemble_kernel(const TwinSlice* slices, int B, const int16_t* gan, const int16_t* cng,
                                      const float* fade_w, int16_t* out, int out_stride, int16_t* noise_dense);
+// the counter-based phase generator of the comfort noise (cng_frame.inc)
+__device__ __forceinline__ unsigned long long splitmix64_dev(unsigned long long x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
 __global__ void cng_kernel(const MelP* P, unsigned long long seed, const int32_t* ids, int B, uint8_t* state,
                            const uint8_t* noise_state, const float* features, int16_t* pcm);
 __global__ void noise_read_kernel(const int32_t* ids, int B, const uint8_t* state, int field_off, float* out);
@@ -281,5 +288,35 @@ __global__ void span_logmel_kernel(const MelP* P, const SpanDtxRow* rows, int n_
 // counts[row] = the span's non-noise frames.
 __global__ void span_noise_scan_kernel(NoiseP P, const SpanDtxRow* rows, int n_rows, uint8_t* state, const float* mel,
                                        int32_t* flag_out, int v_noise, int v_active, long long* map, int32_t* counts);
+
+// ---- packet loss on spans (spans_lossy_kernels.hip, spans_lossy_plan.h; lyra_hip_decode_spans_lossy_dev) -------------------
+// One span with frames.  Its parts of the call's dense lists: received ticks rx0 .. rx0 + n_rx - 1 (SpanLossyRx, and the mel rows),
+// run_cng ticks cng0 .. (SpanLossyCng), frames info0 .. (SpanLossyFrame); rx_wg0 / cng_wg0: the span's first workgroup of
+// span_logmel_map_kernel (two received frames each) / span_cng_kernel (one tick each), rows in rising order of both;
+// snap_v0: the snapshot row of the estimate on entry, or -1; ctl_out: the control word after the span.
+struct SpanLossyRow {
+  long long frame0, n_frames, info0;
+  int32_t id, rx0, n_rx, rx_wg0, cng0, n_cng, cng_wg0, snap_v0;
+  uint32_t ctl_out;
+  int32_t pad;
+};
+static_assert(sizeof(SpanLossyRow) == 2 * sizeof(SpanRow), "two row slots of the upload");
+struct SpanLossyRx { long long frame; int32_t snap, pad; };     // a received tick: its buffer frame; the snapshot row that takes the estimate after it, or -1
+struct SpanLossyCng { long long frame; int32_t snap, info; };   // a run_cng tick: its buffer frame, the snapshot row it reads, lossy_info
+struct SpanLossyFrame { int32_t info, back; };                  // a frame: lossy_info; frames back to the last received one (0: none in the span)
+__global__ void span_lossy_ctl_read_kernel(int32_t* io, int n, int max_streams, const uint8_t* cng_state);
+__global__ void span_lossy_feat_kernel(const SpanRow* rows, int B, int step, const uint8_t* gen_received, float* feats);
+// grid = the workgroups of all rows, 256 threads, LDS logmel_lds_bytes(); state: the decoder-side NoiseEstimator region
+__global__ void span_logmel_map_kernel(const MelP* P, const SpanLossyRow* rows, int n_rows, uint8_t* state, const SpanLossyRx* rx,
+                                       const int16_t* pcm, float* mel);
+// grid n_rows, 64 threads
+__global__ void span_lossy_scan_kernel(NoiseP P, const SpanLossyRow* rows, int n_rows, uint8_t* state, const float* mel,
+                                       const SpanLossyRx* rx, int32_t* is_noise_out, float* snaps, int32_t* entry_noise);
+// final == 0: grid = the run_cng ticks of all rows; final != 0: grid n_rows, behind the first launch.  256 threads, LDS cng_lds_bytes()
+__global__ void span_cng_kernel(const MelP* P, unsigned long long seed, const SpanLossyRow* rows, int n_rows, int final,
+                                uint8_t* state, const SpanLossyCng* ticks, const float* snaps, const float* fade_w, int16_t* pcm16);
+// grid = ceil(total / 256): one thread per frame of the rows
+__global__ void span_lossy_finish_kernel(const SpanLossyRow* rows, int n_rows, long long total, const SpanLossyFrame* frames,
+                                         uint8_t* cng_state, const int32_t* entry_noise, int32_t* is_noise, int32_t* is_cn);
 
 }  // namespace lyra

@@ -60,10 +60,7 @@ __global__ __launch_bounds__(256) void lossy_mix_kernel(const int32_t* __restric
     if (!noise) v = g[i];
     else if (!gen) v = c[i];
     else {
-      const float w = fade_w[fade + i * dir - TWIN_FADE_LO];
-      const float x = (float)g[i] * w;
-      const float y = (float)c[i] * (1.f - w);
-      v = (int16_t)(int)(x + y);
+#include "lossy_mix.inc"
     }
     o[i] = v;
   }

@@ -786,13 +786,6 @@ __global__ __launch_bounds__(256) void twin_assemble_kernel(const TwinSlice* __r
 // operation by operation in fp64 (same radix-2 butterflies and host-built twiddles as the log-mel kernel).
 // features == nullptr: the stream's decoder-side noise estimate is used (lyra_decoder.cc:328-340).
 // =============================================================================================
-__device__ __forceinline__ unsigned long long splitmix64_dev(unsigned long long x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 __global__ __launch_bounds__(256) void cng_kernel(const MelP* __restrict__ Pp, unsigned long long seed,
                                                    const int32_t* __restrict__ ids, int B,
                                                    uint8_t* __restrict__ state, const uint8_t* __restrict__ noise_state,
@@ -811,56 +804,15 @@ __global__ __launch_bounds__(256) void cng_kernel(const MelP* __restrict__ Pp, u
   double* ola = reinterpret_cast<double*>(slot + st::C_OLA);
   const float* feat = features ? features + (size_t)b * 160
                                : reinterpret_cast<const float*>(noise_state + (size_t)id * st::NOISE_BYTES + st::N_EST);
-  if (tid < 160) mel[tid] = (double)(float)exp((double)(feat[tid] * 10.f));   // std::exp(float * kNorm), float
-  for (int i = tid; i < 1024; i += 256) { re[i] = 0.0; im[i] = 0.0; }
-  __syncthreads();
-  const double PI = 3.14159265358979323846;
-  const double gain = __builtin_sqrt(1024.0 * 320.0 / (384.0 * 240.0));
   // (the slot key is zero unless the stream was imported from another id or context: state_layout.h C_KEY)
   const unsigned long long sd = seed ^ (unsigned long long)(unsigned)id ^ *reinterpret_cast<const unsigned long long*>(slot + st::C_KEY);
-  for (int i = P.start + tid; i <= P.end; i += 256) {
-    // band[v + 1] = first bin whose lower band is >= v: find this bin's lower band ch (-1 .. 159)
-    int lo = 0, hi = 161;   // band index domain v + 1
-    while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (P.band[mid] <= i) lo = mid; else hi = mid; }
-    const int ch = lo - 1;
-    const double w = P.w[i];
-    double v = 0.0;
-    if (ch >= 0 && P.wsum[ch] > 0.0) v += w * mel[ch] / P.wsum[ch];
-    if (ch + 1 < 160 && P.wsum[ch + 1] > 0.0) v += (1.0 - w) * mel[ch + 1] / P.wsum[ch + 1];
-    const unsigned long long r = splitmix64_dev(sd ^ splitmix64_dev(hop * 1024ull + (unsigned long long)i));
-    const double ang = (double)(r >> 11) * (1.0 / 9007199254740992.0) * 2.0 * PI;
-    const double a = v * gain;
-    const double xr = a * cos(ang), xi = a * sin(ang);
-    // inverse DFT through the forward butterflies: conj in, conj out; inputs go to bit-reversed positions
-    const int r0 = __brev((unsigned)i) >> 22;
-    re[r0] = xr; im[r0] = (i == 0 || i == 512) ? 0.0 : -xi;
-    if (i > 0 && i < 512) { const int r1 = __brev((unsigned)(1024 - i)) >> 22; re[r1] = xr; im[r1] = xi; }
-  }
-  __syncthreads();
-#pragma unroll 1
-  for (int p = 1; p <= 10; ++p) {
-    const int len = 1 << p, half = len >> 1;
-    for (int bf = tid; bf < 512; bf += 256) {
-      int grp = bf >> (p - 1), k = bf & (half - 1);
-      int i0 = grp * len + k, i1 = i0 + half;
-      double wr = P.tw_re[half - 1 + k], wi = P.tw_im[half - 1 + k];
-      double ur = re[i0], ui = im[i0];
-      double xr = re[i1], xi = im[i1];
-      double vr = xr * wr - xi * wi;
-      double vi = xr * wi + xi * wr;
-      re[i0] = ur + vr; im[i0] = ui + vi;
-      re[i1] = ur - vr; im[i1] = ui - vi;
-    }
-    __syncthreads();
-  }
+#include "cng_frame.inc"
   // window, overlap-add, emit the first 320 samples, shift the accumulator by one hop
   double acc[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int n = tid + 256 * q;
-    const double x = re[n] / 1024.0;
-    const double v = 0.5 - 0.5 * cos(2.0 * PI * n / 1024.0);
-    acc[q] = ola[n] + x * v;
+    acc[q] = ola[n] + cng_windowed(n);
   }
   __syncthreads();
 #pragma unroll

@@ -45,6 +45,15 @@ struct SpanSide {
   int counts_cap = 0;
   int32_t* h_counts = nullptr;      // pinned [counts_cap]: non-noise frames per span with frames, written by the scan
   int32_t* d_counts = nullptr;      // the device's view of h_counts
+  // packet loss (decode_spans_lossy, spans_lossy_api.inc): grow-only like the above
+  size_t lists_cap = 0;             // bytes
+  uint8_t* h_lists = nullptr;       // pinned: the plan's lists of the call in flight (uploaded with the rows: ev_up covers both)
+  uint8_t* d_lists = nullptr;
+  int ctl_cap = 0;
+  int32_t* h_ctl = nullptr;         // pinned [ctl_cap]: span stream ids in, their control words out.  This call's alone, and it
+  int32_t* d_ctl = nullptr;         // waits for its read kernel before it goes on: no kernel in flight ever names the buffer
+  size_t snap_cap = 0;              // floats
+  float* d_snap = nullptr;          // estimate snapshots [versions][160], then one int32 per span: is_noise() on entry
 };
 struct SpanCalls { SpanSide side[2]; };
 
@@ -56,6 +65,13 @@ void span_side_free(SpanSide& S) {
   dfree(S.d_rows, S.d_in, S.d_out, S.d_feat, S.d_step_ids, S.d_mel, S.d_map);
   if (S.h_counts) (void)hipHostFree(S.h_counts);
   S.h_counts = S.d_counts = nullptr;
+  if (S.h_lists) (void)hipHostFree(S.h_lists);
+  S.h_lists = nullptr;
+  if (S.h_ctl) (void)hipHostFree(S.h_ctl);
+  S.h_ctl = S.d_ctl = nullptr;
+  S.ctl_cap = 0;
+  dfree(S.d_lists, S.d_snap);
+  S.lists_cap = S.snap_cap = 0;
   if (S.ev_up) (void)hipEventDestroy(S.ev_up);
   S.ev_up = nullptr;
   S.rows_cap = S.cap = S.counts_cap = 0;
@@ -208,10 +224,11 @@ int launch_span_resample(lyra_hip_ctx* c, bool enc, hipStream_t st_, const SpanR
 
 // Lane preparation, the T steps, hand-over and lane reset of one call on st_.  h_batch / d_batch: the plan's rows (host copy
 // and device), d_reset: one row per lane.  enc: d_src PCM [frames][320], d_dst packets [frames][nbytes]; else the reverse.
-// d_map (encode_spans_dtx): the plan counts frames in the compacted list, index c is buffer frame d_map[c].
+// d_map (encode_spans_dtx, decode_spans_lossy): the plan counts frames in the compacted list, index c is buffer frame d_map[c].
+// d_gen_received (decode_spans_lossy): entry c of that list came with a packet; the others decode from zero features.
 int span_run_steps(lyra_hip_ctx* c, bool enc, SpanSide& S, hipStream_t st_, const SpanPlan& P, const SpanRow* h_batch,
                    const SpanRow* d_batch, const SpanRow* d_reset, int n_lanes, const void* d_src, int num_bits, void* d_dst,
-                   const long long* d_map) {
+                   const long long* d_map, const uint8_t* d_gen_received = nullptr) {
   const int rows = (int)P.chunks.size(), nbytes = (num_bits + 7) / 8, r0 = enc ? st::R_E0 : st::R_D0;
   int rc = 0;
   const int n_lane_rows = rows - P.n_own;
@@ -237,7 +254,13 @@ int span_run_steps(lyra_hip_ctx* c, bool enc, SpanSide& S, hipStream_t st_, cons
       hipLaunchKernelGGL(span_scatter_kernel, dim3(span_grid(Bq, out_bytes)), dim3(256), 0, st_, d_batch, Bq, i, S.d_out,
                          out_bytes, 0, (uint8_t*)d_dst, d_map);
     } else {
-      if ((rc = launch_generate(c, 0, 0, S.d_step_ids, B, nullptr, (int16_t*)S.d_out, S.d_in, num_bits / 4))) continue;
+      if (d_gen_received) {   // as a lossy tick: the RVQ decode of every row, zero features where the tick conceals
+        if ((rc = launch_rvq_decode(c, 0, B, nullptr, S.d_in, num_bits / 4, S.d_feat))) continue;
+        hipLaunchKernelGGL(span_lossy_feat_kernel, dim3(span_grid(B, 64)), dim3(256), 0, st_, d_batch, B, i, d_gen_received,
+                           S.d_feat);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = launch_generate(c, 0, 0, S.d_step_ids, B, S.d_feat, (int16_t*)S.d_out))) continue;
+      } else if ((rc = launch_generate(c, 0, 0, S.d_step_ids, B, nullptr, (int16_t*)S.d_out, S.d_in, num_bits / 4))) continue;
       const int Bs = i < W ? own : B;
       if (!Bs) continue;
       hipLaunchKernelGGL(span_scatter_kernel, dim3(span_grid(Bs, 40)), dim3(256), 0, st_, d_batch, Bs, i, S.d_out, out_bytes,

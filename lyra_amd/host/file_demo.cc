@@ -6,6 +6,8 @@
 // side; the same bytes).
 // --dtx: encoder_main's --enable_dtx; noise hops append nothing to the .lyra file.  Such a file carries no framing (the
 // reference's format), so it is not decoded: only <stem>.lyra is written.
+// --dtx --time-parallel: the encode's packets and sizes are also decoded in memory, time-parallel (lyra_hip_decode_spans_lossy)
+// and hop by hop (BatchLyraDecoder); the two must give the same samples, else exit code 8.  One line on stdout says so.
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -61,6 +63,28 @@ int main(int argc, char** argv) {
   if (lanes >= 0) {
     if (!EncodeFilesTimeParallel(wavs, lyras, bitrate, false, dtx, model_dir, lanes)) return 4;
     if (!dtx && !DecodeFilesTimeParallel(lyras, decoded, decode_rate, bitrate, model_dir, lanes)) return 5;
+    if (dtx) {
+      std::vector<std::vector<int16_t>> pcm(wavs.size()), tp, seq;
+      int rate = 0;
+      for (size_t i = 0; i < wavs.size(); ++i) {
+        int ch = 0, r = 0;
+        if (!ReadWav16(wavs[i], &pcm[i], &ch, &r) || ch != 1 || (i && r != rate)) return 4;
+        rate = r;
+      }
+      std::vector<std::vector<uint8_t>> packets;
+      std::vector<std::vector<int32_t>> sizes;
+      if (!EncodeWavsTimeParallel(pcm, 1, rate, bitrate, false, true, model_dir, &packets, lanes, 0, &sizes)) return 4;
+      const int packet_size = bitrate == 3200 ? 8 : bitrate == 6000 ? 15 : 23;
+      if (!DecodeFeaturesTimeParallel(packets, sizes, packet_size, decode_rate, model_dir, &tp, lanes)) return 5;
+      if (!DecodeFeaturesBatch(packets, sizes, packet_size, decode_rate, model_dir, &seq)) return 5;
+      size_t hops = 0, empty = 0;
+      for (const auto& v : sizes)
+        for (int32_t b : v) { ++hops; empty += b == 0; }
+      const bool same = tp == seq;
+      std::printf("dtx round trip: %zu hops, %zu empty packets, time-parallel and hop-by-hop decode %s\n", hops, empty,
+                  same ? "equal" : "DIFFER");
+      if (!same) return 8;
+    }
     return 0;
   }
   if (!EncodeFiles(wavs, lyras, bitrate, false, dtx, model_dir)) return 4;

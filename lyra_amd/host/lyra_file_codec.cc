@@ -20,6 +20,7 @@
 #pragma weak lyra_hip_encode_spans_ext
 #pragma weak lyra_hip_decode_spans_ext
 #pragma weak lyra_hip_encode_spans_dtx
+#pragma weak lyra_hip_decode_spans_lossy
 
 namespace chromemedia {
 namespace codec {
@@ -420,6 +421,107 @@ bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_
     LOG(ERROR) << "Could not decode samples: " << lyra_hip_last_error(ctx.c);
     return false;
   }
+  for (int i = 0; i < n; ++i)
+    (*decoded_audio)[i].assign(pcm.begin() + job.spans[i].first_frame * hop_samples,
+                               pcm.begin() + (job.spans[i].first_frame + job.spans[i].n_frames) * hop_samples);
+  return true;
+}
+
+namespace {
+// packet_sizes[i][h] is 0 or packet_size and the non-empty packets of stream i are exactly packet_streams[i]
+bool SizesMatch(const std::vector<std::vector<uint8_t>>& packet_streams, const std::vector<std::vector<int32_t>>& packet_sizes,
+                int packet_size) {
+  if (packet_sizes.size() != packet_streams.size()) { LOG(ERROR) << "One list of packet sizes per stream is required."; return false; }
+  for (size_t i = 0; i < packet_streams.size(); ++i) {
+    size_t bytes = 0;
+    for (int32_t b : packet_sizes[i]) {
+      if (b != 0 && b != packet_size) { LOG(ERROR) << "A packet size is neither 0 nor " << packet_size << "."; return false; }
+      bytes += (size_t)b;
+    }
+    if (bytes != packet_streams[i].size()) { LOG(ERROR) << "The packet sizes do not add up to the encoded stream."; return false; }
+  }
+  return true;
+}
+}  // namespace
+
+bool DecodeFeaturesBatch(const std::vector<std::vector<uint8_t>>& packet_streams,
+                         const std::vector<std::vector<int32_t>>& packet_sizes, int packet_size, int sample_rate_hz,
+                         const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio, int device) {
+  if (!CheckScope(1, sample_rate_hz, false, false) || NumBitsOfPacketSize(packet_size) < 0) return false;
+  if (!SizesMatch(packet_streams, packet_sizes, packet_size)) return false;
+  const int n = (int)packet_streams.size();
+  decoded_audio->assign(n, {});
+  if (n == 0) return true;
+  auto decoder = BatchLyraDecoder::Create(sample_rate_hz, 1, model_path, n, device);
+  if (!decoder) return false;
+  size_t hops = 0;
+  for (const auto& v : packet_sizes) hops = std::max(hops, v.size());
+  const size_t hop_samples = (size_t)sample_rate_hz / 50;
+  std::vector<size_t> at((size_t)n, 0);   // bytes of stream i consumed
+  std::vector<int32_t> ids;
+  std::vector<uint8_t> packets;
+  std::vector<int16_t> pcm((size_t)n * hop_samples);
+  for (size_t h = 0; h < hops; ++h) {
+    ids.clear();
+    packets.clear();
+    for (int i = 0; i < n; ++i)
+      if (h < packet_sizes[i].size() && packet_sizes[i][h]) {
+        ids.push_back(i);
+        packets.insert(packets.end(), packet_streams[i].begin() + at[i], packet_streams[i].begin() + at[i] + packet_size);
+        at[i] += (size_t)packet_size;
+      }
+    if (!ids.empty() && !decoder->SetEncodedPackets(absl::MakeConstSpan(ids), absl::MakeConstSpan(packets))) return false;
+    if (!decoder->DecodeSamples((int)hop_samples, absl::Span<int16_t>(pcm.data(), pcm.size()))) return false;
+    for (int i = 0; i < n; ++i)   // a stream that has ended goes on concealing; its hops are dropped
+      if (h < packet_sizes[i].size())
+        (*decoded_audio)[i].insert((*decoded_audio)[i].end(), pcm.begin() + i * hop_samples, pcm.begin() + (i + 1) * hop_samples);
+  }
+  return true;
+}
+
+bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams,
+                                const std::vector<std::vector<int32_t>>& packet_sizes, int packet_size, int sample_rate_hz,
+                                const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
+                                int num_lanes, int device) {
+  if (!CheckScope(1, sample_rate_hz, false, false)) return false;
+  const int num_bits = NumBitsOfPacketSize(packet_size);
+  if (num_bits < 0 || !HaveSpanCalls(sample_rate_hz)) return false;
+  if (!lyra_hip_decode_spans_lossy) {
+    LOG(ERROR) << "This build of the lyra_hip library has no time-parallel span call for missing packets.";
+    return false;
+  }
+  if (!SizesMatch(packet_streams, packet_sizes, packet_size)) return false;
+  const int n = (int)packet_streams.size();
+  decoded_audio->assign(n, {});
+  if (n == 0) return true;
+  // frame-major: one packet row per hop (zeros where there is none) and its size
+  SpanJob job;
+  std::vector<uint8_t> packets;
+  std::vector<int32_t> sizes;
+  for (int i = 0; i < n; ++i) {
+    job.spans.push_back({(int32_t)i, job.frames, (int64_t)packet_sizes[i].size()});
+    size_t at = 0;
+    for (int32_t b : packet_sizes[i]) {
+      packets.insert(packets.end(), (size_t)packet_size, 0);
+      if (b) std::copy(packet_streams[i].begin() + at, packet_streams[i].begin() + at + b, packets.end() - packet_size);
+      at += (size_t)b;
+      sizes.push_back(b);
+    }
+    job.frames += (int64_t)packet_sizes[i].size();
+  }
+  const int64_t worth = job.frames / (2 * lyra_hip_span_warmup_frames(LYRA_HIP_SIDE_DECODER));
+  for (int l = 0; l < (int)std::max<int64_t>(0, std::min<int64_t>(num_lanes, worth)); ++l) job.lanes.push_back(n + l);
+  Ctx ctx;
+  if (!ctx.Create(model_path, device, n + (int)job.lanes.size(), "decoder")) return false;
+  const size_t hop_samples = (size_t)sample_rate_hz / 50;
+  const bool ext = sample_rate_hz != kBatchInternalSampleRateHz;
+  std::vector<int16_t> pcm16((size_t)job.frames * kBatchHopSamples), pcm_ext(ext ? (size_t)job.frames * hop_samples : 0);
+  if (lyra_hip_decode_spans_lossy(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), packets.data(), sizes.data(),
+                                  num_bits, sample_rate_hz, pcm16.data(), ext ? pcm_ext.data() : nullptr, nullptr, nullptr) != 0) {
+    LOG(ERROR) << "Could not decode samples: " << lyra_hip_last_error(ctx.c);
+    return false;
+  }
+  const std::vector<int16_t>& pcm = ext ? pcm_ext : pcm16;
   for (int i = 0; i < n; ++i)
     (*decoded_audio)[i].assign(pcm.begin() + job.spans[i].first_frame * hop_samples,
                                pcm.begin() + (job.spans[i].first_frame + job.spans[i].n_frames) * hop_samples);

@@ -11,7 +11,9 @@
 // sample_rate_hz / 50 samples.  enable_dtx is encoder_main's --enable_dtx (lyra_hip_set_encoder_sample_rate(rate), then
 // lyra_hip_resample + lyra_hip_encode_dtx per hop or, time-parallel, lyra_hip_encode_spans_dtx): a noise hop's empty packet
 // appends nothing, so the output is the concatenation of the non-empty packets (encoder_main_lib.cc:77-88) and, like the
-// reference's, cannot be cut into hops again without the sizes -- packet_sizes returns them.  Such files are not decoded here.
+// reference's, cannot be cut into hops again without the sizes -- packet_sizes returns them.  The file functions do not decode
+// such a file; the DecodeFeatures forms that take packet_sizes do decode such a stream, and one captured from a lossy link
+// (a loss trace has the same shape: 0 = no packet this hop): concealment, comfort noise and cross-fades as LyraDecoder's.
 // No preprocessing / packet-loss simulation: those are refused.
 #ifndef LYRA_AMD_HOST_LYRA_FILE_CODEC_H_
 #define LYRA_AMD_HOST_LYRA_FILE_CODEC_H_
@@ -44,6 +46,14 @@ bool DecodeFeaturesBatch(const std::vector<std::vector<uint8_t>>& packet_streams
                          const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
                          int device = 0);
 
+// ... with hops that carry no packet (DTX's empty packets, packets lost on the way): packet_sizes[i][h] = 0 or packet_size as
+// EncodeWavs returns them, packet_streams[i] the non-empty packets concatenated.  Hop by hop through BatchLyraDecoder:
+// SetEncodedPackets for the streams with a packet, DecodeSamples(one hop) for all.
+bool DecodeFeaturesBatch(const std::vector<std::vector<uint8_t>>& packet_streams,
+                         const std::vector<std::vector<int32_t>>& packet_sizes, int packet_size, int sample_rate_hz,
+                         const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
+                         int device = 0);
+
 // DecodeFile for a batch: encoded_paths[i] (.lyra) -> output_paths[i] (16-bit mono WAV at sample_rate_hz).
 bool DecodeFiles(const std::vector<ghc::filesystem::path>& encoded_paths,
                  const std::vector<ghc::filesystem::path>& output_paths, int sample_rate_hz, int bitrate,
@@ -69,6 +79,12 @@ bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_
                                 const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
                                 int num_lanes = kDefaultSpanLanes, int device = 0);
 bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams, int packet_size, int sample_rate_hz,
+                                const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
+                                int num_lanes = kDefaultSpanLanes, int device = 0);
+// ... with hops that carry no packet, through lyra_hip_decode_spans_lossy: the samples of the DecodeFeaturesBatch form that
+// takes packet_sizes (what EncodeWavsTimeParallel(enable_dtx) returns; a loss trace has the same shape).
+bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams,
+                                const std::vector<std::vector<int32_t>>& packet_sizes, int packet_size, int sample_rate_hz,
                                 const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
                                 int num_lanes = kDefaultSpanLanes, int device = 0);
 bool DecodeFilesTimeParallel(const std::vector<ghc::filesystem::path>& encoded_paths,

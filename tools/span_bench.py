@@ -16,6 +16,14 @@ with --time-parallel (EncodeWavsTimeParallel(enable_dtx)) against hop by hop (En
 the same .lyra; kernel_share gives the part of span_noise_scan_kernel -- the serial floor of the call -- and of span_logmel_kernel
 in the summed kernel time of the device leg.
 
+--lossy (with or without --rate): decode only, a recording captured from a lossy link and one encoded with DTX.  Two
+lossy_transcode records, trace "gilbert" (two-state loss chain: 5 % of the good hops start a burst, a burst ends after a hop with
+probability 0.25 -- bursts of 4 hops on average, every length from isolated losses to full comfort noise) and trace "dtx" (the
+sizes of lyra_hip_encode_spans_dtx_dev on the half-silent recording): lyra_hip_decode_spans_lossy_dev on device buffers against the
+only other way to do the job, lyra_hip_decode_lossy_dev hop by hop on a twin context (B = 1, every call enqueued without a wait, one
+synchronise at the end); `verified`: all four outputs of all hops equal.  kernel_share gives the part of span_lossy_scan_kernel --
+the serial floor -- of span_logmel_map_kernel and of span_cng_kernel in the summed kernel time of the device leg.
+
 Records, appended to --out:
   span_transcode   lyra_hip_encode_spans_dev + lyra_hip_decode_spans_dev on device buffers, one stream of --hops hops with
                    --lanes lanes: wall time per direction (after a warm call), useful frames/s (the recording's hops, warm-up
@@ -137,6 +145,80 @@ def dtx_file_leg(args, pcm):
     return rec
 
 
+def gilbert(hops, p_loss=0.05, p_recover=0.25, seed=5):
+    """received[h] of a two-state loss chain"""
+    rng = np.random.default_rng(seed)
+    u = rng.random(hops)
+    rx, lost = np.ones(hops, bool), False
+    for h in range(hops):
+        lost = (u[h] >= p_recover) if lost else (u[h] < p_loss)
+        rx[h] = not lost
+    return rx
+
+
+def lossy_device_leg(args, pcm, trace):
+    import torch
+    import lyra_amd
+    from lyra_amd import codec
+    dev = torch.device("cuda", 0)
+    hops, ext, nbytes = pcm.shape[0], args.rate != 16000, codec.packet_size(args.bits)
+    ctx = lyra_amd.LyraHip(device=0, max_streams=args.lanes + 1, requant="xnnpack")
+    ctx.set_encoder_sample_rate(args.rate)
+    lanes = np.arange(1, args.lanes + 1, dtype=np.int32)
+    spans = [(0, 0, hops)]
+    d_pk = torch.zeros((hops, nbytes), dtype=torch.uint8, device=dev)
+    d_w16 = torch.zeros((hops, 320), dtype=torch.int16, device=dev) if ext else None
+    if trace == "dtx":
+        d_nb = torch.zeros(hops, dtype=torch.int32, device=dev)
+        ctx.encode_spans_dtx_dev(spans, torch.from_numpy(half_silent(pcm, args.rate)).to(dev), args.bits, d_pk, d_nb, lanes,
+                                 sample_rate_hz=args.rate, d_pcm16=d_w16)
+        ctx.synchronize()
+        pb = d_nb.cpu().numpy()
+    else:
+        ctx.encode_spans_dev(spans, torch.from_numpy(pcm).to(dev), args.bits, d_pk, lanes, sample_rate_hz=args.rate, d_pcm16=d_w16)
+        ctx.synchronize()
+        pb = np.where(gilbert(hops), nbytes, 0).astype(np.int32)
+
+    def outputs():
+        return (torch.zeros((hops, 320), dtype=torch.int16, device=dev),
+                torch.zeros((hops, args.rate // 50), dtype=torch.int16, device=dev) if ext else None,
+                torch.zeros(hops, dtype=torch.int32, device=dev), torch.zeros(hops, dtype=torch.int32, device=dev))
+    got, times = outputs(), []
+    for rep in range(args.reps + 1):   # rep 0 warms (allocations, code)
+        ctx.reset()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ctx.decode_spans_lossy_dev(spans, d_pk, pb, args.bits, got[0], lanes, sample_rate_hz=args.rate, d_pcm_ext=got[1],
+                                   d_is_noise=got[2], d_is_comfort_noise=got[3])
+        ctx.synchronize()
+        if rep:
+            times.append(time.perf_counter() - t0)
+    plan = codec.spans_lossy_plan(spans, pb, nbytes, [0], lanes, args.lanes + 1)
+    t = float(np.median(times))
+    rec = dict(kind="lossy_transcode", trace=trace, rate=args.rate, hops=hops, lanes=int(args.lanes), bits=args.bits,
+               received_hops=int((pb > 0).sum()), gen_hops=int(plan["counts"]["n_gen"][0]), cng_hops=int(plan["counts"]["n_cng"][0]),
+               snapshots=int(plan["counts"]["n_versions"][0]), steps=int(plan["n_steps"]), decode_s=round(t, 5),
+               decode_frames_per_s=round(hops / t), reps=args.reps)
+    if args.device_leg_only:
+        return rec
+    twin = lyra_amd.LyraHip(device=0, max_streams=1, requant="xnnpack")
+    want, d_pb, d_ids = outputs(), torch.from_numpy(pb).to(dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    base = []
+    for rep in range(2):   # rep 0 warms
+        twin.reset()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for h in range(hops):
+            twin.decode_lossy_dev(d_ids, d_pk[h:h + 1], d_pb[h:h + 1], args.bits, args.rate, want[0][h:h + 1],
+                                  want[1][h:h + 1] if ext else None, want[2][h:h + 1], want[3][h:h + 1])
+        twin.synchronize()
+        base.append(time.perf_counter() - t0)
+    same = all(torch.equal(a, b) for a, b in zip(got, want) if a is not None)
+    rec.update(hop_by_hop_s=round(base[-1], 5), hop_by_hop_over_time_parallel=round(base[-1] / t, 2), verified=bool(same),
+               verified_hops=hops)
+    return rec
+
+
 def device_leg(args, pcm):
     import torch
     import lyra_amd
@@ -228,11 +310,15 @@ def kernel_share_leg(args):
     import glob
     rec = dict(kind="kernel_share", rate=args.rate, hops=args.hops, lanes=int(args.lanes), bits=args.bits, dtx=bool(args.dtx))
     names = ["span_noise_scan_kernel", "span_logmel_kernel", "span_resample_kernel"] if args.dtx else ["span_resample_kernel"]
+    if args.lossy:
+        rec["lossy"] = True
+        names = ["span_lossy_scan_kernel", "span_logmel_map_kernel", "span_cng_kernel", "span_resample_kernel"]
     with tempfile.TemporaryDirectory() as tmp:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "span", "--",
                sys.executable, os.path.abspath(__file__), "--device-leg-only", "--reps", "1", "--verify-hops", "0",
                "--hops", str(args.hops), "--lanes", str(args.lanes), "--bits", str(args.bits), "--rate", str(args.rate)]
         cmd += ["--dtx"] if args.dtx else []
+        cmd += ["--lossy"] if args.lossy else []
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.file_timeout)
         stats = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
         if r.returncode != 0 or not stats:
@@ -266,10 +352,23 @@ def main():
     ap.add_argument("--skip-file-leg", action="store_true")
     ap.add_argument("--rate", type=int, default=16000, choices=[8000, 16000, 32000, 48000])
     ap.add_argument("--dtx", action="store_true", help="LyraEncoder's DTX on a half-silent recording, encode only")
+    ap.add_argument("--lossy", action="store_true", help="decode only: a Gilbert loss trace and a DTX trace, time-parallel against hop by hop")
     ap.add_argument("--device-leg-only", action="store_true", help="the device leg alone, nothing recorded (the traced child)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "span_transcode.jsonl"))
     args = ap.parse_args()
     pcm = recording(args.hops, args.rate)
+    if args.lossy:
+        recs = []
+        for trace in ("gilbert", "dtx"):
+            recs.append(lossy_device_leg(args, pcm, trace))
+            print(json.dumps(recs[-1]), flush=True)
+        if not args.device_leg_only:
+            recs.append(kernel_share_leg(args))
+            print(json.dumps(recs[-1]), flush=True)
+            with open(args.out, "a") as f:
+                for r in recs:
+                    f.write(json.dumps(r) + "\n")
+        return
     if args.dtx:
         pcm = half_silent(pcm, args.rate)
     recs = [dtx_device_leg(args, pcm) if args.dtx else device_leg(args, pcm)]
