@@ -23,7 +23,8 @@ def synth(B, T, seed):
 
 
 def test_config5_32768_streams_one_gpu(oracle_default):
-    """bench.py --config 5 at N = 1: one context of 32,768 streams (2.65 GB of state; every (size_t)id * stride),
+    """bench.py --config 5 at N = 1: one context of 32,768 streams (2.65 GB of state; the stage kernels' 32-bit byte
+    offsets id * slot bytes up to 486 MB, below 2^29 -- the rest of the id range is tests/test_gpu_id_range.py's),
     120 bits, 20 hops through encode_dev / decode_dev with steps overlapping: packets and PCM of the 64 base streams
     equal to the oracle, and every replica equal to its base stream, at every hop."""
     import torch
