@@ -160,8 +160,60 @@ def spans_lossy_plan(spans, packet_bytes, packet_size_bytes, ctl_in, lane_ids, m
     return res
 
 
+def _signatures():
+    """name -> (restype, argtypes) of every function of include/lyra_hip.h this module binds; tests/test_abi_cpu.py holds
+    each entry to its prototype."""
+    vp, ci, cp, cl, cu, sz = C.c_void_p, C.c_int, C.c_char_p, C.c_long, C.c_uint, C.c_size_t
+    hop = [vp, vp, ci]             # ctx, stream ids, B
+    spans = [vp, vp, ci, vp, ci]   # ctx, spans, n_spans, lane ids, n_lanes
+    ints = {   # return int
+        "create": [cp, ci, ci, ci, C.POINTER(vp)], "create_from_image": [cp, sz, ci, ci, ci, C.POINTER(vp)],
+        "reset_streams": hop, "noise_estimate": [vp, ci, vp, ci, vp],
+        "set_cng_seed": [vp, C.c_uint64], "set_encoder_sample_rate": [vp, ci],
+        "encode_begin": hop + [vp, ci, ci, ci], "encode_end": [vp, vp, vp],
+        "decode_begin": hop + [vp, ci], "decode_end": [vp, vp],
+        "twin_fetch_begin": [vp, ci, ci, ci], "twin_fetch_end": [vp, vp],
+        "encode_ext_dev": hop + [vp, ci, ci, ci, vp, vp], "decode_ext_dev": hop + [vp, ci, ci, ci, vp, vp, vp],
+        "decode_lossy_dev": hop + [vp, vp, ci, ci, vp, vp, vp, vp],
+        "encode_mixed_dev": hop + [vp, ci, vp, ci, vp, vp], "decode_lossy_mixed_dev": hop + [vp, vp, ci, vp, vp, vp, vp],
+        "encode_rates_dev": hop + [vp, vp, vp, ci, vp, vp], "decode_lossy_rates_dev": hop + [vp] * 7,
+        "decode_samples_dev": hop + [vp, vp, ci, ci, vp, vp, vp],
+        "span_warmup_frames": [ci], "spans_plan": [ci, vp, ci, vp, ci, ci, vp, ci, vp],
+        "spans_lossy_plan": [vp, ci, vp, ci, ci, vp, ci, vp] + [vp] * 8 + [vp, ci, vp],
+        "encode_spans_ext": spans + [vp, ci, ci, vp], "decode_spans_ext": spans + [vp, ci, ci, vp],
+        "encode_spans_ext_dev": spans + [vp, ci, vp, ci, vp], "decode_spans_ext_dev": spans + [vp, ci, ci, vp, vp],
+        "encode_spans_dtx": spans + [vp, ci, ci, vp, vp], "encode_spans_dtx_dev": spans + [vp, ci, vp, ci, vp, vp],
+        "run_steps_dev": [vp, C.POINTER(StepsDesc)], "synchronize": [vp], "wait_for_stream": [vp, vp], "stream_wait": [vp, vp],
+        "set_serial": [vp, ci], "set_stream_priorities": [vp, ci, ci, ci], "max_streams": [vp],
+        "profile_enable": [vp, cu], "profile_sample": [vp, ci], "profile_kernel_count": [], "profile_read": [vp, vp, vp],
+    }
+    twins = {   # return int; NAME on host buffers and NAME_dev on device buffers share the signature
+        "extract": hop + [vp, vp], "generate": hop + [vp, vp], "logmel": hop + [vp, vp], "comfort_noise": hop + [vp, vp],
+        "rvq_encode": [vp, ci, vp, ci, vp], "rvq_decode": [vp, ci, vp, vp],
+        "encode": hop + [vp, ci, vp], "decode": hop + [vp, ci, vp], "encode_dtx": hop + [vp, ci, vp, vp],
+        "noise_receive": [vp, ci, vp, ci, vp, vp], "resample": [vp, ci, vp, ci, vp, ci, ci, ci, vp],
+        "export_streams": hop + [vp], "import_streams": hop + [vp, cu],
+        "encode_spans": spans + [vp, ci, vp], "decode_spans": spans + [vp, ci, vp],
+        "noise_spans": [vp, ci, vp, ci, vp, vp], "decode_spans_lossy": spans + [vp, vp, ci, ci, vp, vp, vp, vp],
+    }
+    table = {
+        "destroy": (None, [vp]), "last_error": (cp, [vp]), "profile_kernel_name": (cp, [ci]),
+        "stream_blob_bytes": (sz, []), "state_bytes_per_stream": (sz, []), "debug_read": (cl, [vp, ci, vp, cl]),
+    }
+    table.update({name: (vp, [vp]) for name in ("stream", "stream_decode", "stream_quantizer")})
+    table.update({name + "_errors": (cl, [vp, ci])
+                  for name in ("decode_lossy", "encode_mixed", "rates", "decode_samples", "import")})
+    table.update({name: (ci, args) for name, args in ints.items()})
+    table.update({name + suf: (ci, args) for name, args in twins.items() for suf in ("", "_dev")})
+    return {"lyra_hip_" + name: sig for name, sig in table.items()}
+
+
+_SIGNATURES = _signatures()
+
+
 def _load(path=None):
-    """The C-ABI library (default: library_path()); a second path loads a build variant beside it (lyra_amd/variants/)."""
+    """The C-ABI library (default: library_path()); a second path loads a build variant beside it (lyra_amd/variants/).
+    A library that lacks a function of _SIGNATURES is refused."""
     path = os.path.abspath(path or library_path())
     if path in _libs:
         return _libs[path]
@@ -181,112 +233,25 @@ def _load(path=None):
         except Exception:
             pass
     L = C.CDLL(path)
-    vp, ci, cp = C.c_void_p, C.c_int, C.c_char_p
-    L.lyra_hip_create.argtypes = [cp, ci, ci, ci, C.POINTER(vp)]
-    L.lyra_hip_create_from_image.argtypes = [cp, C.c_size_t, ci, ci, ci, C.POINTER(vp)]
-    L.lyra_hip_destroy.argtypes = [vp]
-    L.lyra_hip_last_error.restype = cp
-    L.lyra_hip_last_error.argtypes = [vp]
-    L.lyra_hip_reset_streams.argtypes = [vp, vp, ci]
-    for name in ("extract", "generate", "logmel"):
-        for suf in ("", "_dev"):
-            getattr(L, f"lyra_hip_{name}{suf}").argtypes = [vp, vp, ci, vp, vp]
-    for suf in ("", "_dev"):
-        getattr(L, f"lyra_hip_rvq_encode{suf}").argtypes = [vp, ci, vp, ci, vp]
-        getattr(L, f"lyra_hip_rvq_decode{suf}").argtypes = [vp, ci, vp, vp]
-        getattr(L, f"lyra_hip_encode{suf}").argtypes = [vp, vp, ci, vp, ci, vp]
-        getattr(L, f"lyra_hip_decode{suf}").argtypes = [vp, vp, ci, vp, ci, vp]
-    for suf in ("", "_dev"):
-        getattr(L, f"lyra_hip_noise_receive{suf}").argtypes = [vp, ci, vp, ci, vp, vp]
-        getattr(L, f"lyra_hip_encode_dtx{suf}").argtypes = [vp, vp, ci, vp, ci, vp, vp]
-    L.lyra_hip_noise_estimate.argtypes = [vp, ci, vp, ci, vp]
-    for suf in ("", "_dev"):
-        getattr(L, f"lyra_hip_resample{suf}").argtypes = [vp, ci, vp, ci, vp, ci, ci, ci, vp]
-        getattr(L, f"lyra_hip_comfort_noise{suf}").argtypes = [vp, vp, ci, vp, vp]
-    if hasattr(L, "lyra_hip_encode_begin"):   # (build variants older than round 6 do not carry the pipelined calls)
-        L.lyra_hip_encode_begin.argtypes = [vp, vp, ci, vp, ci, ci, ci]
-        L.lyra_hip_encode_end.argtypes = [vp, vp, vp]
-        L.lyra_hip_decode_begin.argtypes = [vp, vp, ci, vp, ci]
-        L.lyra_hip_decode_end.argtypes = [vp, vp]
-        L.lyra_hip_twin_fetch_begin.argtypes = [vp, ci, ci, ci]
-        L.lyra_hip_twin_fetch_end.argtypes = [vp, vp]
-    if hasattr(L, "lyra_hip_encode_ext_dev"):   # (one hop at an external rate, one call per side: round 6)
-        L.lyra_hip_encode_ext_dev.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp]
-        L.lyra_hip_decode_ext_dev.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp]
-    if hasattr(L, "lyra_hip_decode_lossy_dev"):
-        L.lyra_hip_decode_lossy_dev.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp]
-        L.lyra_hip_decode_lossy_errors.argtypes = [vp, ci]
-        L.lyra_hip_decode_lossy_errors.restype = C.c_long
-    if hasattr(L, "lyra_hip_encode_mixed_dev"):
-        L.lyra_hip_encode_mixed_dev.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, vp]
-        L.lyra_hip_encode_mixed_errors.argtypes = [vp, ci]
-        L.lyra_hip_encode_mixed_errors.restype = C.c_long
-        L.lyra_hip_decode_lossy_mixed_dev.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp, vp, vp]
-    if hasattr(L, "lyra_hip_encode_rates_dev"):
-        L.lyra_hip_encode_rates_dev.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, vp]
-        L.lyra_hip_decode_lossy_rates_dev.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
-        L.lyra_hip_rates_errors.argtypes = [vp, ci]
-        L.lyra_hip_rates_errors.restype = C.c_long
-    if hasattr(L, "lyra_hip_decode_samples_dev"):
-        L.lyra_hip_decode_samples_dev.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp]
-        L.lyra_hip_decode_samples_errors.argtypes = [vp, ci]
-        L.lyra_hip_decode_samples_errors.restype = C.c_long
-    if hasattr(L, "lyra_hip_export_streams"):
-        L.lyra_hip_stream_blob_bytes.restype = C.c_size_t
-        L.lyra_hip_stream_blob_bytes.argtypes = []
-        for suf in ("", "_dev"):
-            getattr(L, f"lyra_hip_export_streams{suf}").argtypes = [vp, vp, ci, vp]
-            getattr(L, f"lyra_hip_import_streams{suf}").argtypes = [vp, vp, ci, vp, C.c_uint]
-        L.lyra_hip_import_errors.argtypes = [vp, ci]
-        L.lyra_hip_import_errors.restype = C.c_long
-    if hasattr(L, "lyra_hip_encode_spans"):
-        L.lyra_hip_span_warmup_frames.argtypes = [ci]
-        L.lyra_hip_spans_plan.argtypes = [ci, vp, ci, vp, ci, ci, vp, ci, vp]
-        for suf in ("", "_dev"):
-            getattr(L, f"lyra_hip_encode_spans{suf}").argtypes = [vp, vp, ci, vp, ci, vp, ci, vp]
-            getattr(L, f"lyra_hip_decode_spans{suf}").argtypes = [vp, vp, ci, vp, ci, vp, ci, vp]
-    if hasattr(L, "lyra_hip_encode_spans_ext"):
-        L.lyra_hip_encode_spans_ext.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, vp]
-        L.lyra_hip_decode_spans_ext.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, vp]
-        L.lyra_hip_encode_spans_ext_dev.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, ci, vp]
-        L.lyra_hip_decode_spans_ext_dev.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, vp, vp]
-    if hasattr(L, "lyra_hip_encode_spans_dtx"):
-        L.lyra_hip_encode_spans_dtx_dev.argtypes = [vp, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp]
-        L.lyra_hip_encode_spans_dtx.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, vp, vp]
-        L.lyra_hip_noise_spans_dev.argtypes = [vp, ci, vp, ci, vp, vp]
-        L.lyra_hip_noise_spans.argtypes = [vp, ci, vp, ci, vp, vp]
-    if hasattr(L, "lyra_hip_decode_spans_lossy"):
-        for suf in ("", "_dev"):
-            getattr(L, f"lyra_hip_decode_spans_lossy{suf}").argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp]
-        L.lyra_hip_spans_lossy_plan.argtypes = [vp, ci, vp, ci, ci, vp, ci, vp] + [vp] * 8 + [vp, ci, vp]
-    L.lyra_hip_set_cng_seed.argtypes = [vp, C.c_uint64]
-    L.lyra_hip_set_encoder_sample_rate.argtypes = [vp, C.c_int]
-    L.lyra_hip_stream.restype = vp
-    L.lyra_hip_stream.argtypes = [vp]
-    L.lyra_hip_stream_decode.restype = vp
-    L.lyra_hip_stream_decode.argtypes = [vp]
-    L.lyra_hip_stream_quantizer.restype = vp
-    L.lyra_hip_stream_quantizer.argtypes = [vp]
-    L.lyra_hip_run_steps_dev.argtypes = [vp, C.POINTER(StepsDesc)]
-    L.lyra_hip_synchronize.argtypes = [vp]
-    L.lyra_hip_wait_for_stream.argtypes = [vp, vp]
-    L.lyra_hip_stream_wait.argtypes = [vp, vp]
-    L.lyra_hip_set_serial.argtypes = [vp, ci]
-    L.lyra_hip_set_stream_priorities.argtypes = [vp, ci, ci, ci]
-    L.lyra_hip_state_bytes_per_stream.restype = C.c_size_t
-    L.lyra_hip_max_streams.argtypes = [vp]
-    L.lyra_hip_profile_enable.argtypes = [vp, C.c_uint]
-    L.lyra_hip_profile_sample.argtypes = [vp, ci]
-    L.lyra_hip_profile_kernel_name.restype = cp
-    L.lyra_hip_profile_kernel_name.argtypes = [ci]
-    L.lyra_hip_profile_read.argtypes = [vp, vp, vp]
-    L.lyra_hip_debug_read.restype = C.c_long
-    L.lyra_hip_debug_read.argtypes = [vp, ci, vp, C.c_long]
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(L, name, None)
+        if fn is None:
+            raise LyraHipError(f"{path} does not export {name}")
+        fn.restype, fn.argtypes = restype, argtypes
     _libs[path] = L
     return L
 
 
 STATE_ENCODER, STATE_DECODER, STATE_BOTH = 1, 2, 3   # LYRA_HIP_STATE_*: the `sides` of import_streams
+
+
+_TORCH = {}   # dtype name of a `_dev` buffer -> (torch.Tensor, torch's dtype), resolved once: torch stays an optional import
+
+
+def _torch_names(dtype_name):
+    import torch
+    _TORCH[dtype_name] = (torch.Tensor, getattr(torch, dtype_name))
+    return _TORCH[dtype_name]
 
 
 def _np(a, dtype, shape):
@@ -322,6 +287,8 @@ class LyraHip:
         self.max_streams = max_streams
         self.requant = requant
         self.sub_batches = sub_batches
+        self._pending_encodes = []   # (B, num_bits) of the hops begun by encode_begin, oldest first
+        self._pending_decodes = []   # B of the calls begun by decode_begin, oldest first
 
     def _create(self, h, mode, model_dir, device, max_streams, weights_image):
         if weights_image is not None:   # bytes of a lyra_v1.lyrapack (lyra_hip_create_from_image)
@@ -385,12 +352,15 @@ class LyraHip:
             return np.arange(B, dtype=np.int32)
         return _np(stream_ids, np.int32, (B,))
 
+    def _rows(self, a, dtype, width, stream_ids):
+        """a -> (contiguous [B][width] array, B, int32 [B] stream ids, 0 .. B - 1 by default), held by the caller for the call"""
+        a = _np(a, dtype, (-1, width))
+        return a, a.shape[0], self._ids(stream_ids, a.shape[0])
+
     # -- numpy (host pointer) API --------------------------------------------------------------------
     def extract(self, pcm, stream_ids=None):
         """pcm int16 [B][320] -> features float32 [B][64] (SoundStreamEncoder::Extract)."""
-        pcm = _np(pcm, np.int16, (-1, HOP))
-        B = pcm.shape[0]
-        ids = self._ids(stream_ids, B)
+        pcm, B, ids = self._rows(pcm, np.int16, HOP, stream_ids)
         out = np.empty((B, NUM_FEATURES), np.float32)
         self._chk(self.L.lyra_hip_extract(self.h, ids.ctypes.data, B, pcm.ctypes.data, out.ctypes.data))
         return out
@@ -411,26 +381,20 @@ class LyraHip:
 
     def generate(self, features, stream_ids=None):
         """features [B][64] -> pcm int16 [B][320] (AddFeatures + GenerateSamples(320))."""
-        features = _np(features, np.float32, (-1, NUM_FEATURES))
-        B = features.shape[0]
-        ids = self._ids(stream_ids, B)
+        features, B, ids = self._rows(features, np.float32, NUM_FEATURES, stream_ids)
         out = np.empty((B, HOP), np.int16)
         self._chk(self.L.lyra_hip_generate(self.h, ids.ctypes.data, B, features.ctypes.data, out.ctypes.data))
         return out
 
     def logmel(self, pcm, stream_ids=None):
-        pcm = _np(pcm, np.int16, (-1, HOP))
-        B = pcm.shape[0]
-        ids = self._ids(stream_ids, B)
+        pcm, B, ids = self._rows(pcm, np.int16, HOP, stream_ids)
         out = np.empty((B, NUM_MEL), np.float32)
         self._chk(self.L.lyra_hip_logmel(self.h, ids.ctypes.data, B, pcm.ctypes.data, out.ctypes.data))
         return out
 
     def encode(self, pcm, num_bits, stream_ids=None):
         """pcm int16 [B][320] -> packets uint8 [B][num_bits/8] (LyraEncoder::Encode, 16 kHz, no DTX)."""
-        pcm = _np(pcm, np.int16, (-1, HOP))
-        B = pcm.shape[0]
-        ids = self._ids(stream_ids, B)
+        pcm, B, ids = self._rows(pcm, np.int16, HOP, stream_ids)
         out = np.empty((B, packet_size(num_bits)), np.uint8)
         self._chk(self.L.lyra_hip_encode(self.h, ids.ctypes.data, B, pcm.ctypes.data, num_bits, out.ctypes.data))
         return out
@@ -438,13 +402,11 @@ class LyraHip:
     def encode_begin(self, pcm, num_bits, stream_ids=None, sample_rate_hz=16000, dtx=False):
         """Pipelined form of encode() (include/lyra_hip.h "Pipelined host-buffer calls"): starts a hop and returns; up to
         two hops may be in flight; pcm int16 [B][sample_rate_hz / 50] at 8 / 16 / 32 / 48 kHz.  `pcm` may be reused at once."""
-        pcm = _np(pcm, np.int16, (-1, sample_rate_hz // 50))
-        B = pcm.shape[0]
-        ids = self._ids(stream_ids, B)
+        pcm, B, ids = self._rows(pcm, np.int16, sample_rate_hz // 50, stream_ids)
         if dtx:
             self._chk(self.L.lyra_hip_set_encoder_sample_rate(self.h, sample_rate_hz))
         self._chk(self.L.lyra_hip_encode_begin(self.h, ids.ctypes.data, B, pcm.ctypes.data, sample_rate_hz, num_bits, int(dtx)))
-        self._pending_encodes = getattr(self, "_pending_encodes", []) + [(B, num_bits)]
+        self._pending_encodes.append((B, num_bits))
 
     def encode_end(self):
         """-> (packets uint8 [B][num_bits/8], packet_bytes int32 [B]) of the OLDEST hop begun."""
@@ -456,11 +418,9 @@ class LyraHip:
 
     def decode_begin(self, packets, num_bits, stream_ids=None):
         """Pipelined form of decode(): starts a call and returns (up to two in flight); decode_end() -> pcm of the oldest."""
-        packets = _np(packets, np.uint8, (-1, packet_size(num_bits)))
-        B = packets.shape[0]
-        ids = self._ids(stream_ids, B)
+        packets, B, ids = self._rows(packets, np.uint8, packet_size(num_bits), stream_ids)
         self._chk(self.L.lyra_hip_decode_begin(self.h, ids.ctypes.data, B, packets.ctypes.data, num_bits))
-        self._pending_decodes = getattr(self, "_pending_decodes", []) + [B]
+        self._pending_decodes.append(B)
 
     def decode_end(self):
         out = np.empty((self._pending_decodes.pop(0), HOP), np.int16)
@@ -469,20 +429,16 @@ class LyraHip:
 
     def decode(self, packets, num_bits, stream_ids=None):
         """packets uint8 [B][num_bits/8] -> pcm int16 [B][320] (SetEncodedPacket + DecodeSamples(320))."""
-        packets = _np(packets, np.uint8, (-1, packet_size(num_bits)))
-        B = packets.shape[0]
-        ids = self._ids(stream_ids, B)
+        packets, B, ids = self._rows(packets, np.uint8, packet_size(num_bits), stream_ids)
         out = np.empty((B, HOP), np.int16)
         self._chk(self.L.lyra_hip_decode(self.h, ids.ctypes.data, B, packets.ctypes.data, num_bits, out.ctypes.data))
         return out
 
-    _SIDES = {"encoder": 0, "decoder": 1}
+    _SIDES = SIDES
 
     def noise_receive(self, pcm, stream_ids=None, side="decoder"):
         """NoiseEstimator::ReceiveSamples, one full hop per stream -> is_noise int32 [B]."""
-        pcm = _np(pcm, np.int16, (-1, HOP))
-        B = pcm.shape[0]
-        ids = self._ids(stream_ids, B)
+        pcm, B, ids = self._rows(pcm, np.int16, HOP, stream_ids)
         out = np.empty(B, np.int32)
         self._chk(self.L.lyra_hip_noise_receive(self.h, self._SIDES[side], ids.ctypes.data, B, pcm.ctypes.data,
                                                 out.ctypes.data))
@@ -497,9 +453,7 @@ class LyraHip:
 
     def encode_dtx(self, pcm, num_bits, stream_ids=None):
         """LyraEncoder::Encode with enable_dtx -> (packets uint8 [B][nbytes], packet_bytes int32 [B]; 0 = empty packet)."""
-        pcm = _np(pcm, np.int16, (-1, HOP))
-        B = pcm.shape[0]
-        ids = self._ids(stream_ids, B)
+        pcm, B, ids = self._rows(pcm, np.int16, HOP, stream_ids)
         out = np.zeros((B, packet_size(num_bits)), np.uint8)
         nbytes = np.empty(B, np.int32)
         self._chk(self.L.lyra_hip_encode_dtx(self.h, ids.ctypes.data, B, pcm.ctypes.data, num_bits, out.ctypes.data,
@@ -586,9 +540,8 @@ class LyraHip:
         self._chk(self.L.lyra_hip_set_serial(self.h, 1 if on else 0))
 
     def _dev_ptr(self, t, dtype_name, shape, what):
-        import torch
-        want = getattr(torch, dtype_name)
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device:
+        tensor, want = _TORCH.get(dtype_name) or _torch_names(dtype_name)
+        if not isinstance(t, tensor) or not t.is_cuda or t.device.index != self.device:
             raise LyraHipError(f"{what}: expected a CUDA tensor on device {self.device}")
         if t.dtype != want:
             raise LyraHipError(f"{what}: dtype {t.dtype}, expected {want}")
@@ -597,6 +550,33 @@ class LyraHip:
         if tuple(t.shape) != tuple(shape):
             raise LyraHipError(f"{what}: shape {tuple(t.shape)}, expected {tuple(shape)}")
         return t.data_ptr()
+
+    def _opt_dev_ptr(self, t, dtype_name, shape, what):
+        """_dev_ptr of a buffer the call can do without: None -> a null pointer"""
+        return None if t is None else self._dev_ptr(t, dtype_name, shape, what)
+
+    # the buffers most `_dev` calls share, B rows each
+    def _p_ids(self, t, B):
+        return self._dev_ptr(t, "int32", (B,), "stream ids")
+
+    def _p_pcm(self, t, B):
+        return self._dev_ptr(t, "int16", (B, HOP), "pcm")
+
+    def _p_packets(self, t, B, nbytes):
+        return self._dev_ptr(t, "uint8", (B, nbytes), "packets")
+
+    def _p_packet_bytes(self, t, B):
+        return self._dev_ptr(t, "int32", (B,), "packet bytes")
+
+    def _p_noise_flags(self, d_is_noise, d_is_comfort_noise, B):
+        return (self._opt_dev_ptr(d_is_noise, "int32", (B,), "is_noise"),
+                self._opt_dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise"))
+
+    def _error_count(self, fn, clear):
+        """A device error counter (long; negative = the read itself failed), optionally cleared by the read"""
+        n = fn(self.h, 1 if clear else 0)
+        self._chk(n if n < 0 else 0)
+        return n
 
     def _torch_stream(self):
         import torch
@@ -613,18 +593,15 @@ class LyraHip:
 
     def encode_dev(self, d_ids, d_pcm, num_bits, d_packets):
         B = d_pcm.shape[0]
-        self._dev_call(self.L.lyra_hip_encode_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
-                       self._dev_ptr(d_pcm, "int16", (B, HOP), "pcm"), num_bits,
-                       self._dev_ptr(d_packets, "uint8", (B, packet_size(num_bits)), "packets"))
+        self._dev_call(self.L.lyra_hip_encode_dev, self._p_ids(d_ids, B), B, self._p_pcm(d_pcm, B), num_bits,
+                       self._p_packets(d_packets, B, packet_size(num_bits)))
 
     def encode_dtx_dev(self, d_ids, d_pcm, num_bits, d_packets, d_packet_bytes):
         """LyraEncoder::Encode with enable_dtx on device buffers: packets uint8 [B][nbytes] (rows of noise hops are
         left untouched) and packet_bytes int32 [B] (0 = empty packet)."""
         B = d_pcm.shape[0]
-        self._dev_call(self.L.lyra_hip_encode_dtx_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
-                       self._dev_ptr(d_pcm, "int16", (B, HOP), "pcm"), num_bits,
-                       self._dev_ptr(d_packets, "uint8", (B, packet_size(num_bits)), "packets"),
-                       self._dev_ptr(d_packet_bytes, "int32", (B,), "packet bytes"))
+        self._dev_call(self.L.lyra_hip_encode_dtx_dev, self._p_ids(d_ids, B), B, self._p_pcm(d_pcm, B), num_bits,
+                       self._p_packets(d_packets, B, packet_size(num_bits)), self._p_packet_bytes(d_packet_bytes, B))
 
     def encode_ext_dev(self, d_ids, d_pcm_ext, sample_rate_hz, num_bits, d_packets, d_packet_bytes=None, dtx=False):
         """LyraEncoder::Encode at an external sample rate as ONE encode-side call (lyra_hip_encode_ext_dev): resampler, with
@@ -632,10 +609,10 @@ class LyraHip:
         [B][320 * rate / 16000]."""
         B = d_pcm_ext.shape[0]
         n_ext = HOP * sample_rate_hz // 16000
-        self._dev_call(self.L.lyra_hip_encode_ext_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
+        self._dev_call(self.L.lyra_hip_encode_ext_dev, self._p_ids(d_ids, B), B,
                        self._dev_ptr(d_pcm_ext, "int16", (B, n_ext), "pcm"), sample_rate_hz, num_bits, 1 if dtx else 0,
-                       self._dev_ptr(d_packets, "uint8", (B, packet_size(num_bits)), "packets"),
-                       self._dev_ptr(d_packet_bytes, "int32", (B,), "packet bytes") if d_packet_bytes is not None else None)
+                       self._p_packets(d_packets, B, packet_size(num_bits)),
+                       self._opt_dev_ptr(d_packet_bytes, "int32", (B,), "packet bytes"))
 
     def decode_ext_dev(self, d_ids, d_packets, num_bits, sample_rate_hz, d_pcm16, d_pcm_ext=None, d_is_noise=None):
         """LyraDecoder::DecodeSamples for a received hop at an external rate as ONE decode-side call
@@ -643,11 +620,11 @@ class LyraHip:
         16000: the resampler -> d_pcm_ext [B][320 * rate / 16000].  Estimator and resampler complete on the noise stream."""
         B = d_packets.shape[0]
         n_ext = HOP * sample_rate_hz // 16000
-        self._dev_call(self.L.lyra_hip_decode_ext_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
-                       self._dev_ptr(d_packets, "uint8", (B, packet_size(num_bits)), "packets"), num_bits, sample_rate_hz,
-                       1 if d_is_noise is not None else 0, self._dev_ptr(d_pcm16, "int16", (B, HOP), "pcm"),
-                       self._dev_ptr(d_pcm_ext, "int16", (B, n_ext), "external-rate pcm") if d_pcm_ext is not None else None,
-                       self._dev_ptr(d_is_noise, "int32", (B,), "is_noise") if d_is_noise is not None else None)
+        self._dev_call(self.L.lyra_hip_decode_ext_dev, self._p_ids(d_ids, B), B,
+                       self._p_packets(d_packets, B, packet_size(num_bits)), num_bits, sample_rate_hz,
+                       1 if d_is_noise is not None else 0, self._p_pcm(d_pcm16, B),
+                       self._opt_dev_ptr(d_pcm_ext, "int16", (B, n_ext), "external-rate pcm"),
+                       self._opt_dev_ptr(d_is_noise, "int32", (B,), "is_noise"))
 
     def decode_lossy_dev(self, d_ids, d_packets, d_packet_bytes, num_bits, sample_rate_hz, d_pcm16, d_pcm_ext=None,
                          d_is_noise=None, d_is_comfort_noise=None):
@@ -657,20 +634,15 @@ class LyraHip:
         [B] optional.  The outputs complete on the noise stream."""
         B = d_packets.shape[0]
         n_ext = HOP * sample_rate_hz // 16000
-        self._dev_call(self.L.lyra_hip_decode_lossy_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
-                       self._dev_ptr(d_packets, "uint8", (B, packet_size(num_bits)), "packets"),
-                       self._dev_ptr(d_packet_bytes, "int32", (B,), "packet bytes"), num_bits, sample_rate_hz,
-                       self._dev_ptr(d_pcm16, "int16", (B, HOP), "pcm"),
-                       self._dev_ptr(d_pcm_ext, "int16", (B, n_ext), "external-rate pcm") if d_pcm_ext is not None else None,
-                       self._dev_ptr(d_is_noise, "int32", (B,), "is_noise") if d_is_noise is not None else None,
-                       self._dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise")
-                       if d_is_comfort_noise is not None else None)
+        self._dev_call(self.L.lyra_hip_decode_lossy_dev, self._p_ids(d_ids, B), B,
+                       self._p_packets(d_packets, B, packet_size(num_bits)), self._p_packet_bytes(d_packet_bytes, B),
+                       num_bits, sample_rate_hz, self._p_pcm(d_pcm16, B),
+                       self._opt_dev_ptr(d_pcm_ext, "int16", (B, n_ext), "external-rate pcm"),
+                       *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B))
 
     def decode_lossy_errors(self, clear=False):
         """packet_bytes values seen by decode_lossy_dev / run_steps that were neither 0 nor the packet size (synchronises)."""
-        n = self.L.lyra_hip_decode_lossy_errors(self.h, 1 if clear else 0)
-        self._chk(n if n < 0 else 0)
-        return n
+        return self._error_count(self.L.lyra_hip_decode_lossy_errors, clear)
 
     def encode_mixed_dev(self, d_ids, d_pcm_ext, sample_rate_hz, d_num_bits, d_packets, d_packet_bytes, dtx=False):
         """encode_ext_dev with a bit count per stream (lyra_hip_encode_mixed_dev): d_num_bits int32 [B] (multiples of 4 in
@@ -678,17 +650,14 @@ class LyraHip:
         d_packet_bytes int32 [B] (0: DTX noise hop or invalid bit count, see encode_mixed_errors)."""
         B = d_pcm_ext.shape[0]
         n_ext = HOP * sample_rate_hz // 16000
-        self._dev_call(self.L.lyra_hip_encode_mixed_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
+        self._dev_call(self.L.lyra_hip_encode_mixed_dev, self._p_ids(d_ids, B), B,
                        self._dev_ptr(d_pcm_ext, "int16", (B, n_ext), "pcm"), sample_rate_hz,
                        self._dev_ptr(d_num_bits, "int32", (B,), "num_bits"), 1 if dtx else 0,
-                       self._dev_ptr(d_packets, "uint8", (B, MAX_PACKET_BYTES), "packets"),
-                       self._dev_ptr(d_packet_bytes, "int32", (B,), "packet bytes"))
+                       self._p_packets(d_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_packet_bytes, B))
 
     def encode_mixed_errors(self, clear=False):
         """Invalid bit counts seen by encode_mixed_dev / run_steps with a bits ring (synchronises)."""
-        n = self.L.lyra_hip_encode_mixed_errors(self.h, 1 if clear else 0)
-        self._chk(n if n < 0 else 0)
-        return n
+        return self._error_count(self.L.lyra_hip_encode_mixed_errors, clear)
 
     def decode_lossy_mixed_dev(self, d_ids, d_packets, d_packet_bytes, sample_rate_hz, d_pcm16, d_pcm_ext=None,
                                d_is_noise=None, d_is_comfort_noise=None):
@@ -697,14 +666,11 @@ class LyraHip:
         anything else = no packet, counted in decode_lossy_errors."""
         B = d_packets.shape[0]
         n_ext = HOP * sample_rate_hz // 16000
-        self._dev_call(self.L.lyra_hip_decode_lossy_mixed_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
-                       self._dev_ptr(d_packets, "uint8", (B, MAX_PACKET_BYTES), "packets"),
-                       self._dev_ptr(d_packet_bytes, "int32", (B,), "packet bytes"), sample_rate_hz,
-                       self._dev_ptr(d_pcm16, "int16", (B, HOP), "pcm"),
-                       self._dev_ptr(d_pcm_ext, "int16", (B, n_ext), "external-rate pcm") if d_pcm_ext is not None else None,
-                       self._dev_ptr(d_is_noise, "int32", (B,), "is_noise") if d_is_noise is not None else None,
-                       self._dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise")
-                       if d_is_comfort_noise is not None else None)
+        self._dev_call(self.L.lyra_hip_decode_lossy_mixed_dev, self._p_ids(d_ids, B), B,
+                       self._p_packets(d_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_packet_bytes, B),
+                       sample_rate_hz, self._p_pcm(d_pcm16, B),
+                       self._opt_dev_ptr(d_pcm_ext, "int16", (B, n_ext), "external-rate pcm"),
+                       *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B))
 
     def encode_rates_dev(self, d_ids, d_pcm_ext, d_sample_rates, d_num_bits, d_packets, d_packet_bytes, dtx=False):
         """encode_mixed_dev with a sample rate per stream (lyra_hip_encode_rates_dev): d_pcm_ext int16 [B][MAX_EXT_HOP], row
@@ -712,12 +678,11 @@ class LyraHip:
         packet_bytes 0, no state advances, counted in rates_errors); the rest as encode_mixed_dev.  Does not read
         set_encoder_sample_rate's setting."""
         B = d_pcm_ext.shape[0]
-        self._dev_call(self.L.lyra_hip_encode_rates_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
+        self._dev_call(self.L.lyra_hip_encode_rates_dev, self._p_ids(d_ids, B), B,
                        self._dev_ptr(d_pcm_ext, "int16", (B, MAX_EXT_HOP), "pcm"),
                        self._dev_ptr(d_sample_rates, "int32", (B,), "sample rates"),
                        self._dev_ptr(d_num_bits, "int32", (B,), "num_bits"), 1 if dtx else 0,
-                       self._dev_ptr(d_packets, "uint8", (B, MAX_PACKET_BYTES), "packets"),
-                       self._dev_ptr(d_packet_bytes, "int32", (B,), "packet bytes"))
+                       self._p_packets(d_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_packet_bytes, B))
 
     def decode_lossy_rates_dev(self, d_ids, d_packets, d_packet_bytes, d_sample_rates, d_pcm16, d_pcm_ext,
                                d_is_noise=None, d_is_comfort_noise=None):
@@ -725,22 +690,16 @@ class LyraHip:
         [B][MAX_EXT_HOP], row b receives d_sample_rates[b] / 50 samples (320 copies of d_pcm16 at 16000; nothing, counted
         in rates_errors, at a value that is no codec rate)."""
         B = d_packets.shape[0]
-        self._dev_call(self.L.lyra_hip_decode_lossy_rates_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
-                       self._dev_ptr(d_packets, "uint8", (B, MAX_PACKET_BYTES), "packets"),
-                       self._dev_ptr(d_packet_bytes, "int32", (B,), "packet bytes"),
-                       self._dev_ptr(d_sample_rates, "int32", (B,), "sample rates"),
-                       self._dev_ptr(d_pcm16, "int16", (B, HOP), "pcm"),
+        self._dev_call(self.L.lyra_hip_decode_lossy_rates_dev, self._p_ids(d_ids, B), B,
+                       self._p_packets(d_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_packet_bytes, B),
+                       self._dev_ptr(d_sample_rates, "int32", (B,), "sample rates"), self._p_pcm(d_pcm16, B),
                        self._dev_ptr(d_pcm_ext, "int16", (B, MAX_EXT_HOP), "external-rate pcm"),
-                       self._dev_ptr(d_is_noise, "int32", (B,), "is_noise") if d_is_noise is not None else None,
-                       self._dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise")
-                       if d_is_comfort_noise is not None else None)
+                       *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B))
 
     def rates_errors(self, clear=False):
         """Sample rates seen by encode_rates_dev / decode_lossy_rates_dev / run_steps with d_rates that are no codec rate
         (synchronises)."""
-        n = self.L.lyra_hip_rates_errors(self.h, 1 if clear else 0)
-        self._chk(n if n < 0 else 0)
-        return n
+        return self._error_count(self.L.lyra_hip_rates_errors, clear)
 
     def decode_samples_dev(self, d_ids, d_packets, d_packet_bytes, num_samples, sample_rate_hz, d_pcm_ext=None,
                            d_is_noise=None, d_is_comfort_noise=None):
@@ -749,22 +708,15 @@ class LyraHip:
         packet, 8 / 15 / 23 = a packet, anything else counted in decode_samples_errors); 0 <= num_samples <= rate / 50 with
         num_samples * 16000 divisible by the rate; d_pcm_ext int16 [B][num_samples] (may be None when num_samples == 0);
         d_is_noise / d_is_comfort_noise int32 [B] optional.  The outputs complete on the noise stream."""
-        if not hasattr(self.L, "lyra_hip_decode_samples_dev"):
-            raise RuntimeError("this build of liblyra_hip.so has no lyra_hip_decode_samples_dev")
         B = d_packets.shape[0]
-        self._dev_call(self.L.lyra_hip_decode_samples_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
-                       self._dev_ptr(d_packets, "uint8", (B, MAX_PACKET_BYTES), "packets"),
-                       self._dev_ptr(d_packet_bytes, "int32", (B,), "packet bytes"), num_samples, sample_rate_hz,
-                       self._dev_ptr(d_pcm_ext, "int16", (B, num_samples), "pcm") if d_pcm_ext is not None else None,
-                       self._dev_ptr(d_is_noise, "int32", (B,), "is_noise") if d_is_noise is not None else None,
-                       self._dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise")
-                       if d_is_comfort_noise is not None else None)
+        self._dev_call(self.L.lyra_hip_decode_samples_dev, self._p_ids(d_ids, B), B,
+                       self._p_packets(d_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_packet_bytes, B),
+                       num_samples, sample_rate_hz, self._opt_dev_ptr(d_pcm_ext, "int16", (B, num_samples), "pcm"),
+                       *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B))
 
     def decode_samples_errors(self, clear=False):
         """Invalid packet sizes plus packets that found the feature FIFO full, seen by decode_samples_dev (synchronises)."""
-        n = self.L.lyra_hip_decode_samples_errors(self.h, 1 if clear else 0)
-        self._chk(n if n < 0 else 0)
-        return n
+        return self._error_count(self.L.lyra_hip_decode_samples_errors, clear)
 
     # -- stream state as blobs (lyra_hip_export_streams / lyra_hip_import_streams) -------------------------------------
     def stream_blob_bytes(self):
@@ -788,21 +740,19 @@ class LyraHip:
     def export_streams_dev(self, d_ids, d_blobs):
         """export_streams on device buffers: d_ids int32 [B] (-1 skips the row), d_blobs uint8 [B][stream_blob_bytes()]."""
         B = d_ids.shape[0]
-        self._dev_call(self.L.lyra_hip_export_streams_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
+        self._dev_call(self.L.lyra_hip_export_streams_dev, self._p_ids(d_ids, B), B,
                        self._dev_ptr(d_blobs, "uint8", (B, self.stream_blob_bytes()), "blobs"))
 
     def import_streams_dev(self, d_ids, d_blobs, sides=STATE_BOTH):
         """import_streams on device buffers.  A blob that fails validation is skipped on the device, its target stream
         left untouched and counted in import_errors(); the other rows are imported."""
         B = d_ids.shape[0]
-        self._dev_call(self.L.lyra_hip_import_streams_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
+        self._dev_call(self.L.lyra_hip_import_streams_dev, self._p_ids(d_ids, B), B,
                        self._dev_ptr(d_blobs, "uint8", (B, self.stream_blob_bytes()), "blobs"), sides)
 
     def import_errors(self, clear=False):
         """Blob rows import_streams_dev refused (synchronises)."""
-        n = self.L.lyra_hip_import_errors(self.h, 1 if clear else 0)
-        self._chk(n if n < 0 else 0)
-        return n
+        return self._error_count(self.L.lyra_hip_import_errors, clear)
 
     # -- time-parallel spans (lyra_hip_encode_spans / lyra_hip_decode_spans) ----------------------------------------------
     @staticmethod
@@ -821,10 +771,6 @@ class LyraHip:
                         int(np.max(sp["first_frame"] + sp["n_frames"])) > frames):
             raise LyraHipError(f"spans: a span lies outside the {frames} frames of the buffer")
         return (sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size), (sp, lanes)
-
-    def _opt_dev_ptr(self, t, dtype_name, shape, what):
-        """_dev_ptr of a buffer the call can do without: None -> a null pointer"""
-        return None if t is None else self._dev_ptr(t, dtype_name, shape, what)
 
     def encode_spans(self, spans, pcm, num_bits, lane_ids=(), sample_rate_hz=16000):
         """Long spans of a few streams, time-parallel and bit for bit the hop-by-hop result.  spans: (stream_id,
@@ -861,14 +807,13 @@ class LyraHip:
         workspace, which holds the resampled audio of the spans' frames afterwards."""
         F = d_pcm.shape[0]
         a, _held = self._span_args(spans, lane_ids, F)
-        p_packets = (d_packets, "uint8", (F, packet_size(num_bits)), "packets")
         if sample_rate_hz == 16000 and d_pcm16 is None:
-            self._dev_call(self.L.lyra_hip_encode_spans_dev, *a, self._dev_ptr(d_pcm, "int16", (F, HOP), "pcm"), num_bits,
-                           self._dev_ptr(*p_packets))
+            self._dev_call(self.L.lyra_hip_encode_spans_dev, *a, self._p_pcm(d_pcm, F), num_bits,
+                           self._p_packets(d_packets, F, packet_size(num_bits)))
             return
         self._dev_call(self.L.lyra_hip_encode_spans_ext_dev, *a, self._dev_ptr(d_pcm, "int16", (F, sample_rate_hz // 50), "pcm"),
                        sample_rate_hz, self._opt_dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"), num_bits,
-                       self._dev_ptr(*p_packets))
+                       self._p_packets(d_packets, F, packet_size(num_bits)))
 
     def decode_spans_dev(self, spans, d_packets, num_bits, d_pcm, lane_ids=(), sample_rate_hz=16000, d_pcm16=None):
         """decode_spans on device buffers.  Enqueues and does not synchronise.  sample_rate_hz other than 16000
@@ -876,13 +821,12 @@ class LyraHip:
         16 kHz output; all of it completes on the decode stream."""
         F = d_pcm.shape[0]
         a, _held = self._span_args(spans, lane_ids, F)
-        p_packets = (d_packets, "uint8", (F, packet_size(num_bits)), "packets")
         if sample_rate_hz == 16000 and d_pcm16 is None:
-            self._dev_call(self.L.lyra_hip_decode_spans_dev, *a, self._dev_ptr(*p_packets), num_bits,
-                           self._dev_ptr(d_pcm, "int16", (F, HOP), "pcm"))
+            self._dev_call(self.L.lyra_hip_decode_spans_dev, *a, self._p_packets(d_packets, F, packet_size(num_bits)), num_bits,
+                           self._p_pcm(d_pcm, F))
             return
-        self._dev_call(self.L.lyra_hip_decode_spans_ext_dev, *a, self._dev_ptr(*p_packets), num_bits, sample_rate_hz,
-                       self._opt_dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"),
+        self._dev_call(self.L.lyra_hip_decode_spans_ext_dev, *a, self._p_packets(d_packets, F, packet_size(num_bits)),
+                       num_bits, sample_rate_hz, self._opt_dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"),
                        self._dev_ptr(d_pcm, "int16", (F, sample_rate_hz // 50), "pcm"))
 
     # -- DTX on spans (lyra_hip_encode_spans_dtx / lyra_hip_noise_spans) -------------------------------------------------------
@@ -908,7 +852,7 @@ class LyraHip:
         self._dev_call(self.L.lyra_hip_encode_spans_dtx_dev, *a,
                        self._dev_ptr(d_pcm, "int16", (F, self._span_hop(sample_rate_hz)), "pcm"), sample_rate_hz,
                        self._opt_dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"), num_bits,
-                       self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"),
+                       self._p_packets(d_packets, F, packet_size(num_bits)),
                        self._opt_dev_ptr(d_packet_bytes, "int32", (F,), "packet_bytes"))
 
     def noise_spans(self, spans, pcm, side="encoder"):
@@ -925,7 +869,7 @@ class LyraHip:
         F = d_pcm.shape[0]
         a, _held = self._span_args(spans, (), F)
         self._dev_call(self.L.lyra_hip_noise_spans_dev, self._SIDES[side], *a[:2],
-                       self._dev_ptr(d_pcm, "int16", (F, HOP), "pcm"), self._dev_ptr(d_is_noise, "int32", (F,), "is_noise"))
+                       self._p_pcm(d_pcm, F), self._dev_ptr(d_is_noise, "int32", (F,), "is_noise"))
 
     # -- packet loss on spans (lyra_hip_decode_spans_lossy) -------------------------------------------------------------------
     @staticmethod
@@ -962,31 +906,29 @@ class LyraHip:
         pb = self._span_packet_bytes(packet_bytes, F)
         a, _held = self._span_args(spans, lane_ids, F)
         self._dev_call(self.L.lyra_hip_decode_spans_lossy_dev, *a,
-                       self._dev_ptr(d_packets, "uint8", (F, packet_size(num_bits)), "packets"), pb.ctypes.data, num_bits,
+                       self._p_packets(d_packets, F, packet_size(num_bits)), pb.ctypes.data, num_bits,
                        sample_rate_hz, self._dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"),
                        self._opt_dev_ptr(d_pcm_ext, "int16", (F, self._span_hop(sample_rate_hz)), "external-rate pcm"),
-                       self._opt_dev_ptr(d_is_noise, "int32", (F,), "is_noise"),
-                       self._opt_dev_ptr(d_is_comfort_noise, "int32", (F,), "is_comfort_noise"))
+                       *self._p_noise_flags(d_is_noise, d_is_comfort_noise, F))
 
     def noise_receive_dev(self, d_ids, d_pcm, d_is_noise, side="decoder"):
         """NoiseEstimator::ReceiveSamples on device buffers: pcm int16 [B][320] -> is_noise int32 [B]."""
         B = d_pcm.shape[0]
-        self._dev_call(self.L.lyra_hip_noise_receive_dev, self._SIDES[side], self._dev_ptr(d_ids, "int32", (B,), "stream ids"),
-                       B, self._dev_ptr(d_pcm, "int16", (B, HOP), "pcm"), self._dev_ptr(d_is_noise, "int32", (B,), "is_noise"))
+        self._dev_call(self.L.lyra_hip_noise_receive_dev, self._SIDES[side], self._p_ids(d_ids, B), B,
+                       self._p_pcm(d_pcm, B), self._dev_ptr(d_is_noise, "int32", (B,), "is_noise"))
 
     def resample_dev(self, d_ids, d_in, in_rate, out_rate, d_out, side="encoder"):
         """Resampler::Resample per stream on device buffers: int16 [B][n_in] -> int16 [B][n_in * out_rate / in_rate]."""
         B, n_in = d_in.shape
-        self._dev_call(self.L.lyra_hip_resample_dev, self._SIDES[side], self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
+        self._dev_call(self.L.lyra_hip_resample_dev, self._SIDES[side], self._p_ids(d_ids, B), B,
                        self._dev_ptr(d_in, "int16", (B, n_in), "input audio"), n_in, in_rate, out_rate,
                        self._dev_ptr(d_out, "int16", (B, n_in * out_rate // in_rate), "output audio"))
 
     def comfort_noise_dev(self, d_ids, d_features, d_pcm):
         """ComfortNoiseGenerator on device buffers; d_features float32 [B][160] or None (= decoder-side noise estimate)."""
         B = d_pcm.shape[0]
-        self._dev_call(self.L.lyra_hip_comfort_noise_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
-                       self._dev_ptr(d_features, "float32", (B, NUM_MEL), "features") if d_features is not None else None,
-                       self._dev_ptr(d_pcm, "int16", (B, HOP), "pcm"))
+        self._dev_call(self.L.lyra_hip_comfort_noise_dev, self._p_ids(d_ids, B), B,
+                       self._opt_dev_ptr(d_features, "float32", (B, NUM_MEL), "features"), self._p_pcm(d_pcm, B))
 
     def run_steps_dev(self, d_ids, num_bits, n_steps, first_step=0, d_pcm_ring=None, d_packets=None, d_pcm_out=None,
                       d_features=None, d_packet_bytes=None, d_is_noise=None, external_rate=16000, d_ext_out=None,
@@ -1011,7 +953,7 @@ class LyraHip:
             n_ext, external_rate = MAX_EXT_HOP, 0
         R = StepsDescRates()
         S = R.steps
-        S.d_stream_ids = self._dev_ptr(d_ids, "int32", (B,), "stream ids")
+        S.d_stream_ids = self._p_ids(d_ids, B)
         S.B, S.num_bits, S.first_step, S.n_steps = B, num_bits, first_step, n_steps
         S.flags = (STEP_ENCODE if encode else 0) | (STEP_DECODE if decode else 0) | (STEP_DTX if dtx else 0) | \
             (STEP_DECODER_NOISE if decoder_noise else 0) | (STEP_PACKET_LOSS if packet_loss else 0) | \
@@ -1032,11 +974,11 @@ class LyraHip:
             S.d_pcm_ring = self._dev_ptr(d_pcm_ring, "int16", (S.ring, B, n_ext), "pcm ring")
         for i in range(2):
             if d_packets is not None:
-                S.d_packets[i] = self._dev_ptr(d_packets[i], "uint8", (B, nbytes), "packets")
+                S.d_packets[i] = self._p_packets(d_packets[i], B, nbytes)
             if d_pcm_out is not None:
                 S.d_pcm_out[i] = self._dev_ptr(d_pcm_out[i], "int16", (B, HOP), "pcm out")
             if d_packet_bytes is not None:
-                S.d_packet_bytes[i] = self._dev_ptr(d_packet_bytes[i], "int32", (B,), "packet bytes")
+                S.d_packet_bytes[i] = self._p_packet_bytes(d_packet_bytes[i], B)
             if d_ext_out is not None:
                 S.d_ext_out[i] = self._dev_ptr(d_ext_out[i], "int16", (B, n_ext), "external-rate out")
         if d_features is not None:     # [B][64], or [n][B][64]: step i generates from frame (first_step + i) % n
@@ -1052,26 +994,22 @@ class LyraHip:
 
     def decode_dev(self, d_ids, d_packets, num_bits, d_pcm):
         B = d_pcm.shape[0]
-        self._dev_call(self.L.lyra_hip_decode_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
-                       self._dev_ptr(d_packets, "uint8", (B, packet_size(num_bits)), "packets"), num_bits,
-                       self._dev_ptr(d_pcm, "int16", (B, HOP), "pcm"))
+        self._dev_call(self.L.lyra_hip_decode_dev, self._p_ids(d_ids, B), B,
+                       self._p_packets(d_packets, B, packet_size(num_bits)), num_bits, self._p_pcm(d_pcm, B))
 
     def extract_dev(self, d_ids, d_pcm, d_feat):
         B = d_pcm.shape[0]
-        self._dev_call(self.L.lyra_hip_extract_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
-                       self._dev_ptr(d_pcm, "int16", (B, HOP), "pcm"),
+        self._dev_call(self.L.lyra_hip_extract_dev, self._p_ids(d_ids, B), B, self._p_pcm(d_pcm, B),
                        self._dev_ptr(d_feat, "float32", (B, NUM_FEATURES), "features"))
 
     def generate_dev(self, d_ids, d_feat, d_pcm):
         B = d_feat.shape[0]
-        self._dev_call(self.L.lyra_hip_generate_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
-                       self._dev_ptr(d_feat, "float32", (B, NUM_FEATURES), "features"),
-                       self._dev_ptr(d_pcm, "int16", (B, HOP), "pcm"))
+        self._dev_call(self.L.lyra_hip_generate_dev, self._p_ids(d_ids, B), B,
+                       self._dev_ptr(d_feat, "float32", (B, NUM_FEATURES), "features"), self._p_pcm(d_pcm, B))
 
     def logmel_dev(self, d_ids, d_pcm, d_mel):
         B = d_pcm.shape[0]
-        self._dev_call(self.L.lyra_hip_logmel_dev, self._dev_ptr(d_ids, "int32", (B,), "stream ids"), B,
-                       self._dev_ptr(d_pcm, "int16", (B, HOP), "pcm"),
+        self._dev_call(self.L.lyra_hip_logmel_dev, self._p_ids(d_ids, B), B, self._p_pcm(d_pcm, B),
                        self._dev_ptr(d_mel, "float32", (B, NUM_MEL), "mel"))
 
     def rvq_encode_dev(self, d_feat, num_bits, d_idx):

@@ -9,6 +9,8 @@
 // and all decoded samples, stream-major per DecodeSamples call.
 // LYRA_DEMO_PIPELINED=1: the same session through the two-deep pipelined halves of the calls -- EncodeAsync(t + 1) is issued
 // before WaitEncoded(t), DecodeSamplesAsync(request k + 1) before WaitDecoded(k) -- which must write the same three files.
+// LYRA_DEMO_PIPELINED=2: the two mixed -- even ticks through the blocking forms, odd ticks through the halves (a tick's decode
+// requests two deep, all delivered before the tick ends, so the forms change only with nothing in flight); the same files.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,6 +26,9 @@ using namespace chromemedia::codec;
 
 int main(int argc, char** argv) {
   if (argc != 11) { std::fprintf(stderr, "usage: see decoder_demo.cc\n"); return 2; }
+  const char* e = std::getenv("LYRA_DEMO_PIPELINED");
+  const int mode = e ? std::atoi(e) : 0;
+  if (mode < 0 || mode > 2) { std::fprintf(stderr, "LYRA_DEMO_PIPELINED must be 0, 1 or 2\n"); return 2; }
   const std::string model_dir = argv[1];
   const int rate = std::atoi(argv[4]), bitrate = std::atoi(argv[5]), dtx = std::atoi(argv[6]), n = std::atoi(argv[7]);
   std::ifstream script(argv[2]);
@@ -38,19 +43,19 @@ int main(int argc, char** argv) {
   const size_t frame = static_cast<size_t>(n) * (rate / 50);
   std::string line;
   size_t off = 0;
-  if (const char* e = std::getenv("LYRA_DEMO_PIPELINED"); e && std::atoi(e) != 0) {
+  std::vector<int> waiting;   // sizes of the decode requests begun and not yet delivered (at most two)
+  auto deliver_oldest = [&]() {
+    std::vector<int16_t> out(static_cast<size_t>(n) * waiting.front());
+    if (!dec->WaitDecoded(absl::Span<int16_t>(out.data(), out.size()))) return false;
+    pcm_out.write(reinterpret_cast<const char*>(out.data()), out.size() * 2);
+    waiting.erase(waiting.begin());
+    return true;
+  };
+  if (mode == 1) {
     std::vector<std::string> lines;
     while (std::getline(script, line))
       if (!line.empty()) lines.push_back(line);
     if (lines.size() * frame > pcm.size()) return 3;
-    std::vector<int> waiting;   // sizes of the decode requests begun and not yet delivered (at most two)
-    auto deliver_oldest = [&]() {
-      std::vector<int16_t> out(static_cast<size_t>(n) * waiting.front());
-      if (!dec->WaitDecoded(absl::Span<int16_t>(out.data(), out.size()))) return false;
-      pcm_out.write(reinterpret_cast<const char*>(out.data()), out.size() * 2);
-      waiting.erase(waiting.begin());
-      return true;
-    };
     if (!lines.empty() && !enc->EncodeAsync(absl::MakeConstSpan(pcm.data(), frame))) return 4;
     for (size_t t = 0; t < lines.size(); ++t) {
       if (t + 1 < lines.size() && !enc->EncodeAsync(absl::MakeConstSpan(pcm.data() + (t + 1) * frame, frame))) return 4;
@@ -84,13 +89,15 @@ int main(int argc, char** argv) {
       if (!deliver_oldest()) return 6;
     return 0;
   }
-  while (std::getline(script, line)) {
+  for (int tick = 0; std::getline(script, line);) {
     if (line.empty()) continue;
+    const bool halves = mode == 2 && (tick++ & 1) != 0;
     std::istringstream ls(line);
     std::string mask;
     ls >> mask;
     if (static_cast<int>(mask.size()) != n || off + frame > pcm.size()) return 3;
-    auto packets = enc->Encode(absl::MakeConstSpan(pcm.data() + off, frame));
+    const auto audio = absl::MakeConstSpan(pcm.data() + off, frame);
+    auto packets = !halves ? enc->Encode(audio) : enc->EncodeAsync(audio) ? enc->WaitEncoded() : std::nullopt;
     off += frame;
     if (!packets) return 4;
     pk_out.write(reinterpret_cast<const char*>(packets->data()), packets->size());
@@ -108,10 +115,18 @@ int main(int argc, char** argv) {
     if (!ids.empty() && !dec->SetEncodedPackets(absl::MakeConstSpan(ids), absl::MakeConstSpan(delivered))) return 5;
     int k;
     while (ls >> k) {
+      if (halves) {
+        if (waiting.size() == 2 && !deliver_oldest()) return 6;
+        if (!dec->DecodeSamplesAsync(k)) return 6;
+        waiting.push_back(k);
+        continue;
+      }
       auto out = dec->DecodeSamples(k);
       if (!out || out->size() != static_cast<size_t>(n) * k) return 6;
       pcm_out.write(reinterpret_cast<const char*>(out->data()), out->size() * 2);
     }
+    while (!waiting.empty())
+      if (!deliver_oldest()) return 6;
   }
   return 0;
 }

@@ -9,38 +9,11 @@
 
 #include "../../include/lyra_hip.h"
 #include "glog/logging.h"
+#include "host_common.h"
 
 namespace chromemedia {
 namespace codec {
-namespace {
-
-// lyra_config.h:56,131-143 (AreParamsSupported)
-bool ParamsSupported(int sample_rate_hz, int num_channels, int num_streams) {
-  if (sample_rate_hz != 8000 && sample_rate_hz != 16000 && sample_rate_hz != 32000 && sample_rate_hz != 48000) {
-    LOG(ERROR) << "Sample rate " << sample_rate_hz << " Hz is not supported by codec.";
-    return false;
-  }
-  if (num_channels != 1) {
-    LOG(ERROR) << "Number of channels " << num_channels << " is not supported by codec. It needs to be 1.";
-    return false;
-  }
-  if (num_streams < 1) {
-    LOG(ERROR) << "num_streams must be positive.";
-    return false;
-  }
-  return true;
-}
-
-lyra_hip_ctx* NewContext(const ghc::filesystem::path& model_path, int device, int num_streams) {
-  lyra_hip_ctx* ctx = nullptr;
-  if (lyra_hip_create(model_path.string().c_str(), device, num_streams, LYRA_HIP_REQUANT_DEFAULT, &ctx) != 0) {
-    LOG(ERROR) << "lyra_hip_create failed: " << lyra_hip_last_error(nullptr);
-    return nullptr;
-  }
-  return ctx;
-}
-
-}  // namespace
+using namespace host;
 
 int BatchBitrateToNumQuantizedBits(int bitrate) {
   switch (bitrate) {  // GetBitrate(bits) = ceil(bits / 8) * 8 * 50  (lyra_config.h:79-91)
@@ -52,21 +25,6 @@ int BatchBitrateToNumQuantizedBits(int bitrate) {
 }
 
 int BatchBitrateToPacketSize(int bitrate) { return (bitrate + kBatchFrameRate * 8 - 1) / (kBatchFrameRate * 8); }
-
-static int PacketSizeToBits(int packet_size) {  // PacketSizeToNumQuantizedBits, lyra_config.h:99-106
-  switch (packet_size) {
-    case 8: return 64;
-    case 15: return 120;
-    case 23: return 184;
-    default: return -1;
-  }
-}
-
-static std::vector<int32_t> Iota(int n) {
-  std::vector<int32_t> v(n);
-  for (int i = 0; i < n; ++i) v[i] = i;
-  return v;
-}
 
 // ---- encoder ---------------------------------------------------------------------------------------------------
 BatchLyraEncoder::BatchLyraEncoder(lyra_hip_ctx* ctx, int sample_rate_hz, int bitrate, bool enable_dtx, int num_streams)
@@ -92,6 +50,15 @@ std::unique_ptr<BatchLyraEncoder> BatchLyraEncoder::Create(int sample_rate_hz, i
 
 BatchLyraEncoder::~BatchLyraEncoder() { lyra_hip_destroy(ctx_); }
 
+bool BatchLyraEncoder::RightSize(absl::Span<const int16_t> audio) const {
+  const int hop_external = sample_rate_hz_ / kBatchFrameRate;
+  const size_t expected = static_cast<size_t>(num_streams_) * hop_external;
+  if (audio.size() == expected) return true;
+  LOG(ERROR) << "The number of audio samples has to be exactly " << expected << " (" << num_streams_
+             << " streams x " << hop_external << "), but is " << audio.size() << ".";
+  return false;
+}
+
 // The blocking form: upload, kernels and download on the extractor's own stream, one synchronise (lyra_hip_encode).  It
 // shares no stream with anything, which matters when a BatchLyraDecoder runs beside it on another host thread: the
 // pipelined halves below use a second and a third stream of the context (quantizer, upload), and a process's streams
@@ -101,13 +68,8 @@ std::optional<std::vector<uint8_t>> BatchLyraEncoder::Encode(const absl::Span<co
     LOG(ERROR) << "Encode() while " << in_flight_.size() << " EncodeAsync() hops are in flight: call WaitEncoded() first.";
     return std::nullopt;
   }
+  if (!RightSize(audio)) return std::nullopt;
   const int hop_external = sample_rate_hz_ / kBatchFrameRate;
-  const size_t expected = static_cast<size_t>(num_streams_) * hop_external;
-  if (audio.size() != expected) {
-    LOG(ERROR) << "The number of audio samples has to be exactly " << expected << " (" << num_streams_
-               << " streams x " << hop_external << "), but is " << audio.size() << ".";
-    return std::nullopt;
-  }
   const int16_t* pcm = audio.data();
   if (sample_rate_hz_ != kBatchInternalSampleRateHz) {   // lyra_encoder.cc:119-122
     resampled_.resize(static_cast<size_t>(num_streams_) * kBatchHopSamples);
@@ -136,13 +98,7 @@ std::optional<std::vector<uint8_t>> BatchLyraEncoder::Encode(const absl::Span<co
 }
 
 bool BatchLyraEncoder::EncodeAsync(const absl::Span<const int16_t> audio) {
-  const int hop_external = sample_rate_hz_ / kBatchFrameRate;
-  const size_t expected = static_cast<size_t>(num_streams_) * hop_external;
-  if (audio.size() != expected) {
-    LOG(ERROR) << "The number of audio samples has to be exactly " << expected << " (" << num_streams_
-               << " streams x " << hop_external << "), but is " << audio.size() << ".";
-    return false;
-  }
+  if (!RightSize(audio)) return false;
   if (in_flight_.size() >= 2) {
     LOG(ERROR) << "Two hops are already in flight: call WaitEncoded() first.";
     return false;
@@ -233,23 +189,9 @@ bool BatchLyraDecoder::SetEncodedPackets(absl::Span<const uint8_t> encoded) {
 }
 
 bool BatchLyraDecoder::SetEncodedPackets(absl::Span<const int32_t> streams, absl::Span<const uint8_t> encoded) {
-  if (failed_) {
-    LOG(ERROR) << "This decoder failed in the middle of a request; its streams are out of step with the device. Create a new one.";
-    return false;
-  }
-  if (streams.empty()) return encoded.empty();
-  const int packet_size = static_cast<int>(encoded.size() / streams.size());
+  const int packet_size = CheckEncodedPackets(failed_, streams, encoded, num_streams_);
+  if (packet_size <= 0) return packet_size == 0;
   const int bits = PacketSizeToBits(packet_size);
-  if (encoded.size() % streams.size() != 0 || bits < 0) {
-    LOG(ERROR) << "The packet size (" << encoded.size() << " bytes for " << streams.size()
-               << " streams) is not supported.";
-    return false;
-  }
-  for (int32_t id : streams)
-    if (id < 0 || id >= num_streams_) {
-      LOG(ERROR) << "Stream " << id << " does not exist.";
-      return false;
-    }
   for (size_t i = 0; i < streams.size(); ++i) {
     Stream& st = streams_[streams[i]];
     // Finish playing out any concealment or comfort noise packets before moving on to the packet we are receiving
@@ -267,7 +209,7 @@ bool BatchLyraDecoder::SetEncodedPackets(absl::Span<const int32_t> streams, absl
 
 std::optional<std::vector<int16_t>> BatchLyraDecoder::DecodeSamples(int num_samples) {
   if (num_samples < 0) {
-    LOG(ERROR) << "Number of samples has to be non-negative.";
+    LOG(ERROR) << kNegativeSamples;
     return std::nullopt;
   }
   std::vector<int16_t> out(static_cast<size_t>(num_streams_) * num_samples);
@@ -275,120 +217,115 @@ std::optional<std::vector<int16_t>> BatchLyraDecoder::DecodeSamples(int num_samp
   return out;
 }
 
+// BufferedResampler::FilterAndBuffer (buffered_resampler.cc:63-147) as arithmetic: what a request of num_samples takes
+// from the leftovers, asks of the device at 16 kHz and gets back at the external rate.  All streams are asked for the same
+// number of samples every time, so their leftover buffers have the same length, and the COUNT of leftovers after every
+// request begun is known before its samples exist: leftover_count_.  At 16 kHz there is no resampler and no buffer.
+BatchLyraDecoder::Pending BatchLyraDecoder::Plan(int num_samples) const {
+  Pending rq{num_samples, 0, num_samples, num_samples};
+  if (sample_rate_hz_ == kBatchInternalSampleRateHz) return rq;
+  rq.used = std::min(leftover_count_, num_samples);
+  rq.internal = 0;
+  if (num_samples > leftover_count_) {
+    const float ratio = static_cast<float>(sample_rate_hz_) / static_cast<float>(kBatchInternalSampleRateHz);
+    rq.internal = static_cast<int>(std::ceil(static_cast<float>(num_samples - leftover_count_) / ratio));
+  }
+  rq.produced = static_cast<int>(static_cast<long>(rq.internal) * sample_rate_hz_ / kBatchInternalSampleRateHz);
+  return rq;
+}
+
+// The state machine and the device calls of a planned request, up to the fetch.
+bool BatchLyraDecoder::Enqueue(const Pending& rq) {
+  if (EnqueueInternal(rq.internal)) return true;
+  (void)lyra_hip_twin_fetch(ctx_, num_streams_, 0, sample_rate_hz_, nullptr);   // abandon the half-assembled request
+  // EnqueueInternal does a stream's bookkeeping (packet consumed, fade / concealment progress) in the pass that gathers
+  // the device calls' arguments: after a failed round the host state of the streams handled so far has advanced while
+  // the device never ran that round.  The reference's LyraDecoder has no such window (one stream, one call); here the
+  // decoder refuses every further call instead of decoding from a state that no longer matches the device.
+  failed_ = true;
+  return false;
+}
+
+// Where a request's samples are fetched to: `out` when there is nothing to splice (the device result IS the answer),
+// else external_, from where Splice() takes them.
+int16_t* BatchLyraDecoder::FetchTarget(const Pending& rq, absl::Span<int16_t> out) {
+  if (rq.used == 0 && rq.produced == rq.num_samples) return out.data();
+  external_.resize(static_cast<size_t>(num_streams_) * rq.produced);
+  return external_.data();
+}
+
+// Per stream: the leftovers first, then the fetched samples; what the request did not ask for becomes the new leftover.
+void BatchLyraDecoder::Splice(const Pending& rq, const int16_t* fetched, absl::Span<int16_t> out) {
+  if (rq.used == 0 && rq.produced == rq.num_samples) return;   // fetched straight into `out`
+  const int to_copy = rq.num_samples - rq.used;
+  for (int s = 0; s < num_streams_; ++s) {
+    int16_t* o = out.data() + static_cast<size_t>(s) * rq.num_samples;
+    std::copy(leftover_[s].begin(), leftover_[s].begin() + rq.used, o);
+    leftover_[s].erase(leftover_[s].begin(), leftover_[s].begin() + rq.used);
+    if (rq.produced > 0) {
+      const int16_t* e = fetched + static_cast<size_t>(s) * rq.produced;
+      std::copy(e, e + to_copy, o + rq.used);
+      leftover_[s].insert(leftover_[s].end(), e + to_copy, e + rq.produced);
+    }
+  }
+}
+
+// The blocking form keeps lyra_hip_twin_fetch and does not go through the begin / end pair: that is a C-ABI path of its
+// own, with its own buffers and stream use (csrc/pipe_api.inc; compare the note above BatchLyraEncoder::Encode).  It is
+// refused while requests are in flight, so whenever it runs every request begun has been spliced and leftover_count_ ==
+// leftover_[s].size() for every stream: Plan() reads the count for both forms.
 bool BatchLyraDecoder::DecodeSamples(int num_samples, absl::Span<int16_t> out) {
   if (num_samples < 0) {
-    LOG(ERROR) << "Number of samples has to be non-negative.";
+    LOG(ERROR) << kNegativeSamples;
     return false;
   }
   if (failed_) {
-    LOG(ERROR) << "This decoder failed in the middle of a request; its streams are out of step with the device. Create a new one.";
+    LOG(ERROR) << kFailed;
     return false;
   }
   if (out.size() != static_cast<size_t>(num_streams_) * num_samples) {
     LOG(ERROR) << "Output span has " << out.size() << " samples, expected " << static_cast<size_t>(num_streams_) * num_samples;
     return false;
   }
-  // BufferedResampler::FilterAndBuffer (buffered_resampler.cc:63-147); all streams are asked for the same number of
-  // samples every time, so their leftover buffers have the same length.  At 16 kHz there is no resampler and no buffer.
   if (!pending_.empty()) {
     LOG(ERROR) << "DecodeSamples() while " << pending_.size() << " DecodeSamplesAsync() requests are in flight: call WaitDecoded() first.";
     return false;
   }
-  const bool resampling = sample_rate_hz_ != kBatchInternalSampleRateHz;
-  const int leftover = resampling ? static_cast<int>(leftover_[0].size()) : 0;
-  const int used = std::min(leftover, num_samples);
-  int internal = num_samples;
-  if (resampling) {
-    internal = 0;
-    if (num_samples > leftover) {
-      const float ratio = static_cast<float>(sample_rate_hz_) / static_cast<float>(kBatchInternalSampleRateHz);
-      internal = static_cast<int>(std::ceil(static_cast<float>(num_samples - leftover) / ratio));
-    }
-  }
-  if (!EnqueueInternal(internal)) {
-    (void)lyra_hip_twin_fetch(ctx_, num_streams_, 0, sample_rate_hz_, nullptr);   // abandon the half-assembled request
-    // EnqueueInternal does a stream's bookkeeping (packet consumed, fade / concealment progress) in the pass that gathers
-    // the device calls' arguments: after a failed round the host state of the streams handled so far has advanced while
-    // the device never ran that round.  The reference's LyraDecoder has no such window (one stream, one call); here the
-    // decoder refuses every further call instead of decoding from a state that no longer matches the device.
-    failed_ = true;
-    return false;
-  }
-  const int produced = resampling ? static_cast<int>(static_cast<long>(internal) * sample_rate_hz_ / kBatchInternalSampleRateHz)
-                                  : internal;
-  // nothing to splice: the device result IS the answer
-  const bool direct = used == 0 && produced == num_samples;
-  int16_t* dst = out.data();
-  if (!direct) {
-    external_.resize(static_cast<size_t>(num_streams_) * produced);
-    dst = external_.data();
-  }
-  if (lyra_hip_twin_fetch(ctx_, num_streams_, internal, sample_rate_hz_, dst) != 0) {
+  const Pending rq = Plan(num_samples);
+  if (!Enqueue(rq)) return false;
+  int16_t* dst = FetchTarget(rq, out);
+  if (lyra_hip_twin_fetch(ctx_, num_streams_, rq.internal, sample_rate_hz_, dst) != 0) {
     LOG(ERROR) << "Could not decode samples: " << lyra_hip_last_error(ctx_);
     failed_ = true;   // the request's samples are lost and the streams have moved on
     return false;
   }
-  if (resampling) leftover_count_ = leftover - used + (produced - (num_samples - used));
-  if (direct) return true;
-  const int to_copy = num_samples - used;
-  for (int s = 0; s < num_streams_; ++s) {
-    int16_t* o = out.data() + static_cast<size_t>(s) * num_samples;
-    std::copy(leftover_[s].begin(), leftover_[s].begin() + used, o);
-    leftover_[s].erase(leftover_[s].begin(), leftover_[s].begin() + used);
-    if (produced > 0) {
-      const int16_t* e = &external_[static_cast<size_t>(s) * produced];
-      std::copy(e, e + to_copy, o + used);
-      leftover_[s].insert(leftover_[s].end(), e + to_copy, e + produced);
-    }
-  }
+  leftover_count_ += rq.produced - rq.num_samples;
+  Splice(rq, dst, out);
   return true;
 }
 
 bool BatchLyraDecoder::DecodeSamplesAsync(int num_samples) {
   if (num_samples < 0) {
-    LOG(ERROR) << "Number of samples has to be non-negative.";
+    LOG(ERROR) << kNegativeSamples;
     return false;
   }
   if (failed_) {
-    LOG(ERROR) << "This decoder failed in the middle of a request; its streams are out of step with the device. Create a new one.";
+    LOG(ERROR) << kFailed;
     return false;
   }
   if (pending_.size() >= 2) {
     LOG(ERROR) << "Two requests are already in flight: call WaitDecoded() first.";
     return false;
   }
-  // BufferedResampler::FilterAndBuffer (buffered_resampler.cc:63-147); all streams are asked for the same number of
-  // samples every time, so their leftover buffers have the same length -- which is all that is needed here: the COUNT of
-  // leftovers after every request begun is known before its samples exist.  At 16 kHz there is no resampler and no buffer.
-  const bool resampling = sample_rate_hz_ != kBatchInternalSampleRateHz;
-  const int leftover = resampling ? leftover_count_ : 0;
-  const int used = std::min(leftover, num_samples);
-  int internal = num_samples;
-  if (resampling) {
-    internal = 0;
-    if (num_samples > leftover) {
-      const float ratio = static_cast<float>(sample_rate_hz_) / static_cast<float>(kBatchInternalSampleRateHz);
-      internal = static_cast<int>(std::ceil(static_cast<float>(num_samples - leftover) / ratio));
-    }
-  }
-  if (!EnqueueInternal(internal)) {
-    (void)lyra_hip_twin_fetch(ctx_, num_streams_, 0, sample_rate_hz_, nullptr);   // abandon the half-assembled request
-    // EnqueueInternal does a stream's bookkeeping (packet consumed, fade / concealment progress) in the pass that gathers
-    // the device calls' arguments: after a failed round the host state of the streams handled so far has advanced while
-    // the device never ran that round.  The reference's LyraDecoder has no such window (one stream, one call); here the
-    // decoder refuses every further call instead of decoding from a state that no longer matches the device.
-    failed_ = true;
-    return false;
-  }
-  const int produced = resampling ? static_cast<int>(static_cast<long>(internal) * sample_rate_hz_ / kBatchInternalSampleRateHz)
-                                  : internal;
-  if (lyra_hip_twin_fetch_begin(ctx_, num_streams_, internal, sample_rate_hz_) != 0) {
+  const Pending rq = Plan(num_samples);
+  if (!Enqueue(rq)) return false;
+  if (lyra_hip_twin_fetch_begin(ctx_, num_streams_, rq.internal, sample_rate_hz_) != 0) {
     LOG(ERROR) << "Could not decode samples: " << lyra_hip_last_error(ctx_);
     failed_ = true;   // the request's samples are lost and the streams have moved on
     return false;
   }
-  pending_.push_back(Pending{num_samples, used, produced});
-  if (resampling) leftover_count_ = leftover - used + (produced - (num_samples - used));
+  pending_.push_back(rq);
+  leftover_count_ += rq.produced - rq.num_samples;
   return true;
 }
 
@@ -403,30 +340,13 @@ bool BatchLyraDecoder::WaitDecoded(absl::Span<int16_t> out) {
     return false;   // (the request stays in flight)
   }
   pending_.erase(pending_.begin());
-  // nothing to splice: the device result IS the answer
-  const bool direct = rq.used == 0 && rq.produced == rq.num_samples;
-  int16_t* dst = out.data();
-  if (!direct) {
-    external_.resize(static_cast<size_t>(num_streams_) * rq.produced);
-    dst = external_.data();
-  }
+  int16_t* dst = FetchTarget(rq, out);
   if (lyra_hip_twin_fetch_end(ctx_, dst) != 0) {
     LOG(ERROR) << "Could not decode samples: " << lyra_hip_last_error(ctx_);
     failed_ = true;
     return false;
   }
-  if (direct) return true;
-  const int to_copy = rq.num_samples - rq.used;
-  for (int s = 0; s < num_streams_; ++s) {
-    int16_t* o = out.data() + static_cast<size_t>(s) * rq.num_samples;
-    std::copy(leftover_[s].begin(), leftover_[s].begin() + rq.used, o);
-    leftover_[s].erase(leftover_[s].begin(), leftover_[s].begin() + rq.used);
-    if (rq.produced > 0) {
-      const int16_t* e = &external_[static_cast<size_t>(s) * rq.produced];
-      std::copy(e, e + to_copy, o + rq.used);
-      leftover_[s].insert(leftover_[s].end(), e + to_copy, e + rq.produced);
-    }
-  }
+  Splice(rq, dst, out);
   return true;
 }
 

@@ -81,6 +81,8 @@ class BatchLyraEncoder {
 
  private:
   BatchLyraEncoder(lyra_hip_ctx* ctx, int sample_rate_hz, int bitrate, bool enable_dtx, int num_streams);
+  bool RightSize(absl::Span<const int16_t> audio) const;   // one frame of every stream, or LOG(ERROR)
+  bool StreamIdle(const char* method, int stream) const;   // (lyra_stream_state.cc)
   lyra_hip_ctx* ctx_;
   int sample_rate_hz_;
   int bitrate_;
@@ -171,7 +173,12 @@ class BatchLyraDecoder {
   std::vector<int32_t> need_packet_[3], need_estimated_, need_cng_, need_noise_;
   std::vector<uint8_t> packets_[3];
   std::vector<lyra_hip_twin_slice> slices_;
-  struct Pending { int num_samples, used, produced; };   // a request begun: samples asked for, taken from the leftovers, fetched
+  // a request: samples asked for, taken from the leftovers, asked of the device at 16 kHz, fetched at the external rate
+  struct Pending { int num_samples, used, internal, produced; };
+  Pending Plan(int num_samples) const;
+  bool Enqueue(const Pending& rq);                                   // EnqueueInternal, or the decoder is failed_
+  int16_t* FetchTarget(const Pending& rq, absl::Span<int16_t> out);
+  void Splice(const Pending& rq, const int16_t* fetched, absl::Span<int16_t> out);
   std::vector<Pending> pending_;                 // oldest first
   int leftover_count_ = 0;                       // leftover samples per stream once every request begun has been delivered
   std::vector<std::vector<int16_t>> leftover_;   // BufferedResampler::leftover_samples_ per stream (same length for all)

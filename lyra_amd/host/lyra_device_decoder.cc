@@ -5,38 +5,23 @@
 
 #include "../../include/lyra_hip.h"
 #include "glog/logging.h"
+#include "host_common.h"
 
 namespace chromemedia {
 namespace codec {
-namespace {
-constexpr char kFailed[] = "This decoder failed in the middle of a request; its streams are out of step with the device. Create a new one.";
-}
+using namespace host;
 
 DeviceLyraDecoder::DeviceLyraDecoder(lyra_hip_ctx* ctx, int sample_rate_hz, int num_streams)
-    : ctx_(ctx), sample_rate_hz_(sample_rate_hz), num_streams_(num_streams), all_ids_(num_streams),
+    : ctx_(ctx), sample_rate_hz_(sample_rate_hz), num_streams_(num_streams), all_ids_(Iota(num_streams)),
       state_(num_streams, lyra::DsState{0, 0, 0, 0, 0, 0, 0}),
-      staged_(static_cast<size_t>(num_streams) * LYRA_HIP_MAX_PACKET_BYTES), staged_bytes_(num_streams, 0) {
-  for (int i = 0; i < num_streams; ++i) all_ids_[i] = i;
-}
+      staged_(static_cast<size_t>(num_streams) * LYRA_HIP_MAX_PACKET_BYTES), staged_bytes_(num_streams, 0) {}
 
 std::unique_ptr<DeviceLyraDecoder> DeviceLyraDecoder::Create(int sample_rate_hz, int num_channels,
                                                               const ghc::filesystem::path& model_path,
                                                               int num_streams, int device) {
-  if (sample_rate_hz != 8000 && sample_rate_hz != 16000 && sample_rate_hz != 32000 && sample_rate_hz != 48000) {
-    LOG(ERROR) << "Sample rate " << sample_rate_hz << " Hz is not supported by codec.";
-    return nullptr;
-  }
-  if (num_channels != 1) {
-    LOG(ERROR) << "Number of channels " << num_channels << " is not supported by codec. It needs to be 1.";
-    return nullptr;
-  }
-  if (num_streams < 1) {
-    LOG(ERROR) << "num_streams must be positive.";
-    return nullptr;
-  }
-  lyra_hip_ctx* ctx = nullptr;
-  if (lyra_hip_create(model_path.string().c_str(), device, num_streams, LYRA_HIP_REQUANT_DEFAULT, &ctx) != 0) {
-    LOG(ERROR) << "lyra_hip_create failed: " << lyra_hip_last_error(nullptr);
+  if (!ParamsSupported(sample_rate_hz, num_channels, num_streams)) return nullptr;
+  lyra_hip_ctx* ctx = NewContext(model_path, device, num_streams);
+  if (ctx == nullptr) {
     LOG(ERROR) << "New model could not be instantiated.";
     return nullptr;
   }
@@ -55,23 +40,10 @@ bool DeviceLyraDecoder::SetEncodedPackets(absl::Span<const uint8_t> encoded) {
 }
 
 bool DeviceLyraDecoder::SetEncodedPackets(absl::Span<const int32_t> streams, absl::Span<const uint8_t> encoded) {
-  if (failed_) {
-    LOG(ERROR) << kFailed;
-    return false;
-  }
-  if (streams.empty()) return encoded.empty();
-  const int packet_size = static_cast<int>(encoded.size() / streams.size());
-  if (encoded.size() % streams.size() != 0 || !lyra::mixed_received(packet_size)) {
-    LOG(ERROR) << "The packet size (" << encoded.size() << " bytes for " << streams.size()
-               << " streams) is not supported.";
-    return false;
-  }
+  const int packet_size = CheckEncodedPackets(failed_, streams, encoded, num_streams_);   // (lyra::mixed_received's sizes)
+  if (packet_size <= 0) return packet_size == 0;
   bool second = false;
   for (int32_t id : streams) {
-    if (id < 0 || id >= num_streams_) {
-      LOG(ERROR) << "Stream " << id << " does not exist.";
-      return false;
-    }
     const int staged = staged_bytes_[id] != 0 ? 1 : 0;
     if (state_[id].wait + staged >= lyra::DS_FIFO_DEPTH) {
       LOG(ERROR) << "Stream " << id << " already holds " << lyra::DS_FIFO_DEPTH << " packets whose hop has not started: the "
@@ -86,12 +58,7 @@ bool DeviceLyraDecoder::SetEncodedPackets(absl::Span<const int32_t> streams, abs
                  << pending_.size() << " DecodeSamplesAsync() requests in flight: call WaitDecoded() first.";
       return false;
     }
-    if (!Begin(0)) return false;
-    if (lyra_hip_decode_samples_end(ctx_, nullptr) != 0) {
-      failed_ = true;
-      LOG(ERROR) << "Could not queue packets: " << lyra_hip_last_error(ctx_);
-      return false;
-    }
+    if (!FlushStaged()) return false;
   }
   for (size_t i = 0; i < streams.size(); ++i) {
     std::memcpy(staged_.data() + static_cast<size_t>(streams[i]) * LYRA_HIP_MAX_PACKET_BYTES,
@@ -116,9 +83,19 @@ bool DeviceLyraDecoder::Begin(int num_samples) {
   return true;
 }
 
+bool DeviceLyraDecoder::FlushStaged() {
+  if (!Begin(0)) return false;
+  if (lyra_hip_decode_samples_end(ctx_, nullptr) != 0) {
+    failed_ = true;
+    LOG(ERROR) << "Could not queue packets: " << lyra_hip_last_error(ctx_);
+    return false;
+  }
+  return true;
+}
+
 std::optional<std::vector<int16_t>> DeviceLyraDecoder::DecodeSamples(int num_samples) {
   if (num_samples < 0) {
-    LOG(ERROR) << "Number of samples has to be non-negative.";
+    LOG(ERROR) << kNegativeSamples;
     return std::nullopt;
   }
   std::vector<int16_t> out(static_cast<size_t>(num_streams_) * num_samples);
@@ -136,7 +113,7 @@ bool DeviceLyraDecoder::DecodeSamples(int num_samples, absl::Span<int16_t> out) 
 
 bool DeviceLyraDecoder::DecodeSamplesAsync(int num_samples) {
   if (num_samples < 0) {
-    LOG(ERROR) << "Number of samples has to be non-negative.";
+    LOG(ERROR) << kNegativeSamples;
     return false;
   }
   if (failed_) {

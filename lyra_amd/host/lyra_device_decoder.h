@@ -55,6 +55,8 @@ class DeviceLyraDecoder {
  private:
   DeviceLyraDecoder(lyra_hip_ctx* ctx, int sample_rate_hz, int num_streams);
   bool Begin(int num_samples);   // the staged packets + a request of num_samples to the device, host mirror advanced
+  bool FlushStaged();            // the staged packets alone: a device call of 0 samples, ended at once
+  bool StreamIdle(const char* method, int stream) const;   // (lyra_stream_state.cc)
 
   lyra_hip_ctx* ctx_;
   int sample_rate_hz_;

@@ -18,6 +18,12 @@ constexpr uint32_t kClassMagic = 0x4243594Cu;   // "LYCB"
 constexpr uint32_t kKindEncoder = 1, kKindDeviceDecoder = 2;
 constexpr size_t kClassHeaderBytes = 16;
 
+bool StreamExists(int stream, int num_streams) {
+  if (stream >= 0 && stream < num_streams) return true;
+  LOG(ERROR) << "Stream " << stream << " does not exist.";
+  return false;
+}
+
 std::optional<std::vector<uint8_t>> Export(lyra_hip_ctx* ctx, int stream, uint32_t kind, int sample_rate_hz) {
   std::vector<uint8_t> blob(kClassHeaderBytes + lyra_hip_stream_blob_bytes());
   const uint32_t header[4] = {kClassMagic, kind, static_cast<uint32_t>(sample_rate_hz), 0};
@@ -60,61 +66,42 @@ bool Import(lyra_hip_ctx* ctx, int stream, absl::Span<const uint8_t> blob, uint3
 
 }  // namespace
 
+// What ExportStream / ImportStream (`method`) check first: the stream exists and no hop is in flight.
+bool BatchLyraEncoder::StreamIdle(const char* method, int stream) const {
+  if (!StreamExists(stream, num_streams_)) return false;
+  if (in_flight_.empty()) return true;
+  LOG(ERROR) << method << "() while " << in_flight_.size() << " EncodeAsync() hops are in flight: call WaitEncoded() first.";
+  return false;
+}
+
 std::optional<std::vector<uint8_t>> BatchLyraEncoder::ExportStream(int stream) {
-  if (stream < 0 || stream >= num_streams_) {
-    LOG(ERROR) << "Stream " << stream << " does not exist.";
-    return std::nullopt;
-  }
-  if (!in_flight_.empty()) {
-    LOG(ERROR) << "ExportStream() while " << in_flight_.size() << " EncodeAsync() hops are in flight: call WaitEncoded() first.";
-    return std::nullopt;
-  }
+  if (!StreamIdle("ExportStream", stream)) return std::nullopt;
   return Export(ctx_, stream, kKindEncoder, sample_rate_hz_);
 }
 
 bool BatchLyraEncoder::ImportStream(int stream, absl::Span<const uint8_t> blob) {
-  if (stream < 0 || stream >= num_streams_) {
-    LOG(ERROR) << "Stream " << stream << " does not exist.";
-    return false;
-  }
-  if (!in_flight_.empty()) {
-    LOG(ERROR) << "ImportStream() while " << in_flight_.size() << " EncodeAsync() hops are in flight: call WaitEncoded() first.";
-    return false;
-  }
+  if (!StreamIdle("ImportStream", stream)) return false;
   return Import(ctx_, stream, blob, kKindEncoder, sample_rate_hz_, LYRA_HIP_STATE_ENCODER);
 }
 
+// The same for the decoder: the stream exists, the decoder has not failed and no request is in flight.
+bool DeviceLyraDecoder::StreamIdle(const char* method, int stream) const {
+  if (!StreamExists(stream, num_streams_)) return false;
+  if (!failed_ && pending_.empty()) return true;
+  LOG(ERROR) << method << "() on a failed decoder or while " << pending_.size()
+             << " DecodeSamplesAsync() requests are in flight: call WaitDecoded() first.";
+  return false;
+}
+
 std::optional<std::vector<uint8_t>> DeviceLyraDecoder::ExportStream(int stream) {
-  if (stream < 0 || stream >= num_streams_) {
-    LOG(ERROR) << "Stream " << stream << " does not exist.";
-    return std::nullopt;
-  }
-  if (failed_ || !pending_.empty()) {
-    LOG(ERROR) << "ExportStream() on a failed decoder or while " << pending_.size()
-               << " DecodeSamplesAsync() requests are in flight: call WaitDecoded() first.";
-    return std::nullopt;
-  }
-  if (staged_bytes_[stream] != 0) {   // the packet belongs to the stream: to the device first (the second-packet path)
-    if (!Begin(0)) return std::nullopt;
-    if (lyra_hip_decode_samples_end(ctx_, nullptr) != 0) {
-      failed_ = true;
-      LOG(ERROR) << "Could not queue packets: " << lyra_hip_last_error(ctx_);
-      return std::nullopt;
-    }
-  }
+  if (!StreamIdle("ExportStream", stream)) return std::nullopt;
+  // the packet belongs to the stream: to the device first (the second-packet path)
+  if (staged_bytes_[stream] != 0 && !FlushStaged()) return std::nullopt;
   return Export(ctx_, stream, kKindDeviceDecoder, sample_rate_hz_);
 }
 
 bool DeviceLyraDecoder::ImportStream(int stream, absl::Span<const uint8_t> blob) {
-  if (stream < 0 || stream >= num_streams_) {
-    LOG(ERROR) << "Stream " << stream << " does not exist.";
-    return false;
-  }
-  if (failed_ || !pending_.empty()) {
-    LOG(ERROR) << "ImportStream() on a failed decoder or while " << pending_.size()
-               << " DecodeSamplesAsync() requests are in flight: call WaitDecoded() first.";
-    return false;
-  }
+  if (!StreamIdle("ImportStream", stream)) return false;
   if (!Import(ctx_, stream, blob, kKindDeviceDecoder, sample_rate_hz_, LYRA_HIP_STATE_DECODER)) return false;
   // the device's seven integers as the blob holds them (validated by the import) -> the host mirror
   std::memcpy(&state_[stream], blob.data() + kClassHeaderBytes + lyra::sb::region_off(lyra::st::R_CNG) + lyra::DS_STATE,

@@ -30,6 +30,70 @@ def test_exports_match_header(lib):
         assert hasattr(lib, n), f"{n} declared in include/lyra_hip.h but not exported"
 
 
+def _header_prototypes():
+    """name -> (return type, [parameter types]) of every lyra_hip_* prototype of include/lyra_hip.h, names and `const` dropped"""
+    hdr = open(os.path.join(ROOT, "include", "lyra_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", "", hdr)
+    hdr = re.sub(r"^[ \t]*#[^\n]*", "", hdr, flags=re.M)
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(lyra_hip_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr):
+        def ctype(decl, named):
+            if "*" in decl:
+                return decl[:decl.rindex("*") + 1].replace("const", "").replace(" ", "")
+            words = [w for w in decl.split() if w != "const"]
+            return " ".join(words[:-1] if named else words)
+        assert name not in protos, name
+        params = [p.strip() for p in params.split(",")]
+        protos[name] = (ctype(" ".join(ret.split()), False), [] if params == ["void"] else [ctype(p, True) for p in params])
+    return protos
+
+
+def test_signature_table_matches_header():
+    """Every entry of lyra_amd.codec's signature table against its prototype: declared, same arity, pointers where the header
+    has pointers and nowhere else, scalars and return types of the header's width and signedness.  A hand-kept argtypes
+    list that drifts from the header corrupts memory silently."""
+    from lyra_amd import codec
+    protos = _header_prototypes()
+    assert len(protos) == 98
+
+    def is_pointer(t):
+        return t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
+    scalars = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "long": ctypes.c_long, "size_t": ctypes.c_size_t}
+    compared = 0
+    for name, (restype, argtypes) in codec._SIGNATURES.items():
+        assert name in protos, f"{name} is not declared in include/lyra_hip.h"
+        ret, params = protos[name]
+        assert len(argtypes) == len(params), (name, len(argtypes), params)
+        for i, (have, want) in enumerate(zip(argtypes, params)):
+            if want.endswith("*"):
+                assert is_pointer(have), (name, i, want, have)
+            elif want == "uint64_t":
+                assert not is_pointer(have) and ctypes.sizeof(have) == 8 and have(-1).value > 0, (name, i, have)
+            else:
+                assert have is scalars[want], (name, i, want, have)
+        if ret == "char*":
+            assert restype is ctypes.c_char_p, name
+        elif ret == "void*":
+            assert restype is ctypes.c_void_p, name
+        elif ret != "void":
+            assert restype is scalars[ret], (name, ret, restype)
+        compared += 1
+    assert compared == len(codec._SIGNATURES) == 88
+
+
+def test_load_refuses_a_library_without_a_listed_symbol(tmp_path, monkeypatch):
+    """A library that lacks a function of the signature table is refused at load, with the function's name."""
+    import lyra_amd
+    from lyra_amd import codec
+    src, so = tmp_path / "one.c", tmp_path / "libone.so"
+    src.write_text("int lyra_hip_create(void) { return 0; }\n")
+    subprocess.check_call(["gcc", "-shared", "-fPIC", "-o", str(so), str(src)])
+    monkeypatch.setattr(codec, "_libs", {})
+    with pytest.raises(lyra_amd.LyraHipError, match=r"libone\.so does not export lyra_hip_\w+"):
+        codec._load(str(so))
+
+
 def test_no_cpu_fallback(lib):
     import torch
     if torch.cuda.is_available():

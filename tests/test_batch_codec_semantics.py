@@ -48,8 +48,9 @@ def _run_session(tmp_path, oracle, rate, bitrate, dtx, pcm, script, demo=None, p
     pk, ln, pout = tmp_path / "pk.bin", tmp_path / "len.i32", tmp_path / "out.s16"
     pcm.tofile(pin)
     sc.write_text("\n".join(f"{mask} " + " ".join(map(str, sizes)) for mask, sizes in script) + "\n")
-    # pipelined: the session through EncodeAsync / WaitEncoded and DecodeSamplesAsync / WaitDecoded, two deep (decoder_demo.cc)
-    env = dict(os.environ, LYRA_DEMO_PIPELINED="1" if pipelined else "0")
+    # pipelined: the session through EncodeAsync / WaitEncoded and DecodeSamplesAsync / WaitDecoded, two deep; "mixed": blocking
+    # and pipelined forms alternating tick by tick, switching only with nothing in flight (decoder_demo.cc)
+    env = dict(os.environ, LYRA_DEMO_PIPELINED={False: "0", True: "1", "mixed": "2"}[pipelined])
     r = subprocess.run([demo, lyra_amd.default_model_dir(), str(sc), str(pin), str(rate), str(bitrate), str(int(dtx)),
                         str(n), str(pk), str(ln), str(pout)], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
@@ -131,9 +132,10 @@ def _build_fake_demo(tmp_path):
 _FAKE_DEMO_FLAGS = ["-O2"]
 
 
-@pytest.mark.parametrize("pipelined", [False, True])
-@pytest.mark.parametrize("rate,bitrate,dtx", [(16000, 6000, False), (48000, 3200, True), (8000, 9200, False),
-                                              (32000, 6000, True)])
+@pytest.mark.parametrize("rate,bitrate,dtx,pipelined",
+                         [(r, b, d, p) for p in (False, True) for r, b, d in ((16000, 6000, False), (48000, 3200, True),
+                                                                              (8000, 9200, False), (32000, 6000, True))] +
+                         [(48000, 3200, True, "mixed"), (8000, 9200, False, "mixed")])
 def test_batch_codec_host_logic_against_fake_abi(tmp_path, rate, bitrate, dtx, pipelined):
     """CPU: the C++ twins' host logic alone -- the C ABI underneath replaced by integer formulas with per-stream call
     counters (tests/host_stub), the reference model assembled from the same formulas (fake_kit.py).  Everything the
