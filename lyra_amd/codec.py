@@ -128,32 +128,46 @@ def spans_lossy_plan(spans, packet_bytes, packet_size_bytes, ctl_in, lane_ids, m
     ctl_in: the span streams' control words on entry.  Returns a dict: counts (SPAN_LOSSY_COUNTS_DTYPE per span), the dense lists
     gen_frames, gen_received, rx_frames, cng_frames, cng_versions, versions, info (span after span), chunks (SPAN_CHUNK_DTYPE,
     first_frame counting in gen_frames) and n_steps.  LyraHipError for what the call refuses."""
+    return _spans_lossy_plan(spans, packet_bytes, int(packet_size_bytes), ctl_in, lane_ids, max_streams, lib)
+
+
+def spans_lossy_plan_mixed(spans, packet_bytes, ctl_in, lane_ids, max_streams, lib=None):
+    """The planner of decode_spans_lossy_mixed (lyra_hip_spans_lossy_plan_mixed; no GPU): spans_lossy_plan with a size per frame,
+    0 / 8 / 15 / 23.  The same dict, except that gen_bytes takes the place of gen_received: 0 for a concealed tick, else the size
+    of the packet the tick is fed from."""
+    return _spans_lossy_plan(spans, packet_bytes, None, ctl_in, lane_ids, max_streams, lib)
+
+
+def _spans_lossy_plan(spans, packet_bytes, packet_size_bytes, ctl_in, lane_ids, max_streams, lib):
+    """packet_size_bytes None: the mixed form"""
+    mixed = packet_size_bytes is None
+    rx_key, what = ("gen_bytes", "spans_lossy_plan_mixed") if mixed else ("gen_received", "spans_lossy_plan")
     L = lib or _load()
     sp = _spans(spans)
     lanes = np.ascontiguousarray(np.asarray(lane_ids, np.int32).reshape(-1))
     pb = np.ascontiguousarray(np.asarray(packet_bytes, np.int32).reshape(-1))
     ctl = np.ascontiguousarray(np.asarray(ctl_in, np.uint32).reshape(-1))
     if ctl.size != sp.size:
-        raise LyraHipError("spans_lossy_plan: one control word per span")
+        raise LyraHipError(f"{what}: one control word per span")
     if sp.size and (np.any(sp["first_frame"] < 0) or np.any(sp["n_frames"] < 0) or
                     int(np.max(sp["first_frame"] + sp["n_frames"])) > pb.size):
-        raise LyraHipError(f"spans_lossy_plan: a span lies outside the {pb.size} frames of packet_bytes")
+        raise LyraHipError(f"{what}: a span lies outside the {pb.size} frames of packet_bytes")
     T = int(sp["n_frames"].sum()) if sp.size else 0
     counts = np.zeros(max(sp.size, 1), SPAN_LOSSY_COUNTS_DTYPE)
-    out = {k: np.zeros(max(T, 1), d) for k, d in (("gen_frames", np.int64), ("gen_received", np.uint8), ("rx_frames", np.int64),
+    out = {k: np.zeros(max(T, 1), d) for k, d in (("gen_frames", np.int64), (rx_key, np.uint8), ("rx_frames", np.int64),
                                                     ("cng_frames", np.int64), ("cng_versions", np.int32), ("versions", np.int32),
                                                     ("info", np.int32))}
     chunks = np.zeros(sp.size + lanes.size + 1, SPAN_CHUNK_DTYPE)
     steps = C.c_int(0)
-    n = L.lyra_hip_spans_lossy_plan(sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size, int(max_streams), pb.ctypes.data,
-                                    int(packet_size_bytes), ctl.ctypes.data, counts.ctypes.data,
-                                    *(out[k].ctypes.data for k in ("gen_frames", "gen_received", "rx_frames", "cng_frames",
-                                                                   "cng_versions", "versions", "info")),
-                                    chunks.ctypes.data, chunks.size, C.addressof(steps))
+    fn = L.lyra_hip_spans_lossy_plan_mixed if mixed else L.lyra_hip_spans_lossy_plan
+    n = fn(sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size, int(max_streams), pb.ctypes.data,
+           *(() if mixed else (packet_size_bytes,)), ctl.ctypes.data, counts.ctypes.data,
+           *(out[k].ctypes.data for k in ("gen_frames", rx_key, "rx_frames", "cng_frames", "cng_versions", "versions", "info")),
+           chunks.ctypes.data, chunks.size, C.addressof(steps))
     if n < 0:
-        raise LyraHipError("lyra_hip_spans_lossy_plan: invalid spans, lanes or packet sizes")
+        raise LyraHipError(f"lyra_hip_{what}: invalid spans, lanes or packet sizes")
     counts = counts[:sp.size]
-    size = {"gen_frames": "n_gen", "gen_received": "n_gen", "rx_frames": "n_received", "cng_frames": "n_cng",
+    size = {"gen_frames": "n_gen", rx_key: "n_gen", "rx_frames": "n_received", "cng_frames": "n_cng",
             "cng_versions": "n_cng", "versions": "n_versions"}
     res = {k: v[:int(counts[size[k]].sum())] for k, v in out.items() if k in size}
     res.update(info=out["info"][:T], counts=counts, chunks=chunks[:n], n_steps=steps.value)
@@ -211,9 +225,25 @@ def _signatures():
 _SIGNATURES = _signatures()
 
 
+def _signatures_spans_mixed():
+    """The same for include/lyra_hip_spans_mixed.h (tests/test_spans_mixed_cpu.py holds each entry to its prototype)."""
+    vp, ci = C.c_void_p, C.c_int
+    spans = [vp, vp, ci, vp, ci]   # ctx, spans, n_spans, lane ids, n_lanes
+    table = {
+        "encode_spans_mixed_dev": spans + [vp, ci, vp, vp, ci, vp, vp], "encode_spans_mixed": spans + [vp, ci, vp, ci, vp, vp],
+        "decode_spans_lossy_mixed_dev": spans + [vp, vp, ci, vp, vp, vp, vp],
+        "decode_spans_lossy_mixed": spans + [vp, vp, ci, vp, vp, vp, vp],
+        "spans_lossy_plan_mixed": [vp, ci, vp, ci, ci, vp, vp] + [vp] * 8 + [vp, ci, vp],
+    }
+    return {"lyra_hip_" + name: (ci, args) for name, args in table.items()}
+
+
+_SIGNATURES_SPANS_MIXED = _signatures_spans_mixed()
+
+
 def _load(path=None):
     """The C-ABI library (default: library_path()); a second path loads a build variant beside it (lyra_amd/variants/).
-    A library that lacks a function of _SIGNATURES is refused."""
+    A library that lacks a function of _SIGNATURES or _SIGNATURES_SPANS_MIXED is refused."""
     path = os.path.abspath(path or library_path())
     if path in _libs:
         return _libs[path]
@@ -233,7 +263,7 @@ def _load(path=None):
         except Exception:
             pass
     L = C.CDLL(path)
-    for name, (restype, argtypes) in _SIGNATURES.items():
+    for name, (restype, argtypes) in (*_SIGNATURES.items(), *_SIGNATURES_SPANS_MIXED.items()):
         fn = getattr(L, name, None)
         if fn is None:
             raise LyraHipError(f"{path} does not export {name}")
@@ -873,10 +903,10 @@ class LyraHip:
 
     # -- packet loss on spans (lyra_hip_decode_spans_lossy) -------------------------------------------------------------------
     @staticmethod
-    def _span_packet_bytes(packet_bytes, frames):
+    def _span_packet_bytes(packet_bytes, frames, name="packet_bytes"):
         pb = np.ascontiguousarray(np.asarray(packet_bytes, np.int32).reshape(-1))
         if pb.size != frames:
-            raise LyraHipError(f"spans: packet_bytes has {pb.size} entries for {frames} frames")
+            raise LyraHipError(f"spans: {name} has {pb.size} entries for {frames} frames")
         return pb
 
     def decode_spans_lossy(self, spans, packets, packet_bytes, num_bits, lane_ids=(), sample_rate_hz=16000):
@@ -910,6 +940,66 @@ class LyraHip:
                        sample_rate_hz, self._dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"),
                        self._opt_dev_ptr(d_pcm_ext, "int16", (F, self._span_hop(sample_rate_hz)), "external-rate pcm"),
                        *self._p_noise_flags(d_is_noise, d_is_comfort_noise, F))
+
+    # -- per-frame bitrates on spans (include/lyra_hip_spans_mixed.h) -----------------------------------------------------------
+    def encode_spans_mixed(self, spans, pcm, num_bits, lane_ids=(), sample_rate_hz=16000, dtx=False):
+        """encode_spans with a bit count per frame: bit for bit encode_mixed_dev per hop with that hop's count.  pcm int16
+        [frames][sample_rate_hz / 50], num_bits int32 [frames] (a multiple of 4 in 4..184 on every span frame); dtx as
+        encode_spans_dtx.  Returns (packets uint8 [frames][23], packet_bytes int32 [frames]); bytes past a row's packet_bytes,
+        rows of noise frames and rows outside every span are 0."""
+        pcm = _np(pcm, np.int16, (-1, self._span_hop(sample_rate_hz)))
+        F = pcm.shape[0]
+        bits = self._span_packet_bytes(num_bits, F, "num_bits")
+        out = np.zeros((F, MAX_PACKET_BYTES), np.uint8)
+        nbytes = np.zeros(F, np.int32)
+        a, _held = self._span_args(spans, lane_ids, F)
+        self._chk(self.L.lyra_hip_encode_spans_mixed(self.h, *a, pcm.ctypes.data, sample_rate_hz, bits.ctypes.data, int(bool(dtx)),
+                                                     out.ctypes.data, nbytes.ctypes.data))
+        return out, nbytes
+
+    def encode_spans_mixed_dev(self, spans, d_pcm, num_bits, d_packets, d_packet_bytes, lane_ids=(), sample_rate_hz=16000,
+                               d_pcm16=None, dtx=False):
+        """encode_spans_mixed on device buffers; num_bits stays a host array like spans and lane_ids.  d_pcm int16
+        [frames][sample_rate_hz / 50], d_packets uint8 [frames][23] (bytes past a row's size are not written), d_packet_bytes int32
+        [frames], d_pcm16 int16 [frames][320] the 16 kHz workspace (not needed at 16000).  Enqueues and does not synchronise,
+        except with dtx, which blocks the host once as encode_spans_dtx_dev does."""
+        F = d_pcm.shape[0]
+        bits = self._span_packet_bytes(num_bits, F, "num_bits")
+        a, _held = self._span_args(spans, lane_ids, F)
+        self._dev_call(self.L.lyra_hip_encode_spans_mixed_dev, *a,
+                       self._dev_ptr(d_pcm, "int16", (F, self._span_hop(sample_rate_hz)), "pcm"), sample_rate_hz,
+                       self._opt_dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"), bits.ctypes.data, int(bool(dtx)),
+                       self._p_packets(d_packets, F, MAX_PACKET_BYTES),
+                       self._opt_dev_ptr(d_packet_bytes, "int32", (F,), "packet_bytes"))
+
+    def decode_spans_lossy_mixed(self, spans, packets, packet_bytes, lane_ids=(), sample_rate_hz=16000):
+        """decode_spans_lossy with the size chosen per frame: packets uint8 [frames][23], packet_bytes int32 [frames] in
+        {0, 8, 15, 23}; bit for bit decode_lossy_mixed_dev per hop.  Returns what decode_spans_lossy returns."""
+        packets = _np(packets, np.uint8, (-1, MAX_PACKET_BYTES))
+        F = packets.shape[0]
+        pb = self._span_packet_bytes(packet_bytes, F)
+        pcm16 = np.zeros((F, HOP), np.int16)
+        ext = np.zeros((F, self._span_hop(sample_rate_hz)), np.int16) if sample_rate_hz != 16000 else None
+        is_noise, is_cn = np.zeros(F, np.int32), np.zeros(F, np.int32)
+        a, _held = self._span_args(spans, lane_ids, F)
+        self._chk(self.L.lyra_hip_decode_spans_lossy_mixed(self.h, *a, packets.ctypes.data, pb.ctypes.data, sample_rate_hz,
+                                                           pcm16.ctypes.data, ext.ctypes.data if ext is not None else None,
+                                                           is_noise.ctypes.data, is_cn.ctypes.data))
+        return pcm16, ext, is_noise, is_cn
+
+    def decode_spans_lossy_mixed_dev(self, spans, d_packets, packet_bytes, d_pcm16, lane_ids=(), sample_rate_hz=16000,
+                                     d_pcm_ext=None, d_is_noise=None, d_is_comfort_noise=None):
+        """decode_spans_lossy_mixed on device buffers, the arguments of decode_spans_lossy_dev without num_bits: d_packets uint8
+        [frames][23], packet_bytes a host array.  Blocks the host once, at its start."""
+        F = d_packets.shape[0]
+        pb = self._span_packet_bytes(packet_bytes, F)
+        a, _held = self._span_args(spans, lane_ids, F)
+        self._dev_call(self.L.lyra_hip_decode_spans_lossy_mixed_dev, *a, self._p_packets(d_packets, F, MAX_PACKET_BYTES),
+                       pb.ctypes.data, sample_rate_hz, self._dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"),
+                       self._opt_dev_ptr(d_pcm_ext, "int16", (F, self._span_hop(sample_rate_hz)), "external-rate pcm"),
+                       *self._p_noise_flags(d_is_noise, d_is_comfort_noise, F))
+
+    spans_lossy_plan_mixed = staticmethod(spans_lossy_plan_mixed)
 
     def noise_receive_dev(self, d_ids, d_pcm, d_is_noise, side="decoder"):
         """NoiseEstimator::ReceiveSamples on device buffers: pcm int16 [B][320] -> is_noise int32 [B]."""

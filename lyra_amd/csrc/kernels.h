@@ -319,4 +319,19 @@ __global__ void span_cng_kernel(const MelP* P, unsigned long long seed, const Sp
 __global__ void span_lossy_finish_kernel(const SpanLossyRow* rows, int n_rows, long long total, const SpanLossyFrame* frames,
                                          uint8_t* cng_state, const int32_t* entry_noise, int32_t* is_noise, int32_t* is_cn);
 
+// ---- per-frame bitrates on spans (spans_mixed_kernels.hip; lyra_hip_encode_spans_mixed_dev / lyra_hip_decode_spans_lossy_mixed_dev)
+// span_gather_kernel's movement plus one int32 per dense row, step_size[r], for the mixed quantizer kernels.  grid as the
+// uniform gather's: 40 units per row (encode) or MAX_PACKET_BYTES (decode), 256 threads.
+//   frame_bits != null (encode): frames = PCM [frames][640] in 16-byte units; step_size[r] = frame_bits[buffer frame], and 4 for
+//     a row that has ended (rvq_encode_mixed_kernel counts an invalid bit count of every row < B, masked or not);
+//   else (decode): frames = packets [frames][MAX_PACKET_BYTES]; step_size[r] = tick_bytes[row.frame0 + step] (the compacted
+//     index itself), that many bytes of the row move, and 0 for a row that has ended.
+__global__ void span_gather_mixed_kernel(const SpanRow* rows, int B, int step, const uint8_t* frames, const int32_t* frame_bits,
+                                         const uint8_t* tick_bytes, uint8_t* dense, int32_t* step_ids, int32_t* step_size,
+                                         const long long* map);
+// dense [B][MAX_PACKET_BYTES] -> frames [frames][MAX_PACKET_BYTES] for the rows past their warm-up: the first
+// (step_bits[r] + 7) / 8 bytes of the row, and packet_bytes[frame] = that size.  grid: MAX_PACKET_BYTES units per row.
+__global__ void span_scatter_mixed_kernel(const SpanRow* rows, int B, int step, const uint8_t* dense, const int32_t* step_bits,
+                                          uint8_t* frames, int32_t* packet_bytes, const long long* map);
+
 }  // namespace lyra

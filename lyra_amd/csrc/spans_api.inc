@@ -14,6 +14,8 @@
 // of all frames in one launch, then one wavefront per span for the recurrence), waits ONCE on the host for the spans' counts of
 // non-noise hops, and runs the unchanged steps on the compacted frame list: under DTX the encoder advances on non-noise hops
 // only, so what it sees is again a stream whose state is convolution history.  lyra_hip_noise_spans[_dev] is the estimator alone.
+// Per-frame bitrates (spans_mixed_api.inc) ride the same steps: span_run_steps with a SpanMixed, encode_spans_planned_dev with
+// frame_bits.
 #include <type_traits>
 
 #include "spans_plan.h"
@@ -38,6 +40,7 @@ struct SpanSide {
   uint8_t* d_out = nullptr;         // [cap][640]  packets (encode) / PCM (decode) in front of the scatter
   float* d_feat = nullptr;          // [cap][64]   encode: features between extractor and quantizer
   int32_t* d_step_ids = nullptr;    // [cap]       the step's id list (-1: the row has ended)
+  int32_t* d_step_size = nullptr;   // [cap]       per-frame bitrates: the step's bit counts (encode) / packet sizes (decode)
   // DTX (encode_spans_dtx, noise_spans): grow-only like the above
   long long dtx_cap = 0;            // frames
   float* d_mel = nullptr;           // [dtx_cap][SPAN_MEL_ROW]  mel rows of the call's frames, span after span
@@ -62,7 +65,7 @@ SpanCalls* span_calls_of(lyra_hip_ctx* c) { return static_cast<SpanCalls*>(c->sp
 void span_side_free(SpanSide& S) {
   if (S.h_rows) (void)hipHostFree(S.h_rows);
   S.h_rows = nullptr;
-  dfree(S.d_rows, S.d_in, S.d_out, S.d_feat, S.d_step_ids, S.d_mel, S.d_map);
+  dfree(S.d_rows, S.d_in, S.d_out, S.d_feat, S.d_step_ids, S.d_step_size, S.d_mel, S.d_map);
   if (S.h_counts) (void)hipHostFree(S.h_counts);
   S.h_counts = S.d_counts = nullptr;
   if (S.h_lists) (void)hipHostFree(S.h_lists);
@@ -105,12 +108,13 @@ int span_side_ensure(lyra_hip_ctx* c, SpanSide& S, hipStream_t st_, int rows, in
   }
   if (rows > S.cap) {
     HIPCHK(c, hipStreamSynchronize(st_));
-    dfree(S.d_in, S.d_out, S.d_feat, S.d_step_ids);
+    dfree(S.d_in, S.d_out, S.d_feat, S.d_step_ids, S.d_step_size);
     S.cap = 0;
     HIPCHK(c, dalloc(&S.d_in, (size_t)rows * 640));
     HIPCHK(c, dalloc(&S.d_out, (size_t)rows * 640));
     HIPCHK(c, dalloc(&S.d_feat, (size_t)rows * 64));
     HIPCHK(c, dalloc(&S.d_step_ids, (size_t)rows));
+    HIPCHK(c, dalloc(&S.d_step_size, (size_t)rows));
     S.cap = rows;
   }
   return 0;
@@ -226,10 +230,17 @@ int launch_span_resample(lyra_hip_ctx* c, bool enc, hipStream_t st_, const SpanR
 // and device), d_reset: one row per lane.  enc: d_src PCM [frames][320], d_dst packets [frames][nbytes]; else the reverse.
 // d_map (encode_spans_dtx, decode_spans_lossy): the plan counts frames in the compacted list, index c is buffer frame d_map[c].
 // d_gen_received (decode_spans_lossy): entry c of that list came with a packet; the others decode from zero features.
+// M (spans_mixed_api.inc): per-frame bitrates.  num_bits is not read, packet rows are MAX_PACKET_BYTES long, the gather leaves
+// every row's bit count (encode: M->d_frame_bits by buffer frame) or packet size (decode: d_gen_received holds the sizes) in
+// S.d_step_size and the mixed quantizer kernels take it from there: launch for launch the uniform step.
+struct SpanMixed {
+  const int32_t* d_frame_bits = nullptr;   // encode: [frames], the device copy of the caller's num_bits
+  int32_t* d_packet_bytes = nullptr;       // encode: [frames], the caller's
+};
 int span_run_steps(lyra_hip_ctx* c, bool enc, SpanSide& S, hipStream_t st_, const SpanPlan& P, const SpanRow* h_batch,
                    const SpanRow* d_batch, const SpanRow* d_reset, int n_lanes, const void* d_src, int num_bits, void* d_dst,
-                   const long long* d_map, const uint8_t* d_gen_received = nullptr) {
-  const int rows = (int)P.chunks.size(), nbytes = (num_bits + 7) / 8, r0 = enc ? st::R_E0 : st::R_D0;
+                   const long long* d_map, const uint8_t* d_gen_received = nullptr, const SpanMixed* M = nullptr) {
+  const int rows = (int)P.chunks.size(), nbytes = M ? (int)MAX_PACKET_BYTES : (num_bits + 7) / 8, r0 = enc ? st::R_E0 : st::R_D0;
   int rc = 0;
   const int n_lane_rows = rows - P.n_own;
   if (n_lane_rows) {
@@ -242,20 +253,38 @@ int span_run_steps(lyra_hip_ctx* c, bool enc, SpanSide& S, hipStream_t st_, cons
   for (int i = 0; i < P.n_steps && !rc; ++i) {
     int own = 0;
     const int B = span_batch_at(P, h_batch, i, &own);
-    hipLaunchKernelGGL(span_gather_kernel, dim3(span_grid(B, enc ? 40 : in_bytes)), dim3(256), 0, st_, d_batch, B, i,
-                       (const uint8_t*)d_src, in_bytes, enc ? 1 : 0, S.d_in, S.d_step_ids, d_map);
+    if (M)
+      hipLaunchKernelGGL(span_gather_mixed_kernel, dim3(span_grid(B, enc ? 40 : in_bytes)), dim3(256), 0, st_, d_batch, B, i,
+                         (const uint8_t*)d_src, enc ? M->d_frame_bits : nullptr, enc ? nullptr : d_gen_received, S.d_in,
+                         S.d_step_ids, S.d_step_size, d_map);
+    else
+      hipLaunchKernelGGL(span_gather_kernel, dim3(span_grid(B, enc ? 40 : in_bytes)), dim3(256), 0, st_, d_batch, B, i,
+                         (const uint8_t*)d_src, in_bytes, enc ? 1 : 0, S.d_in, S.d_step_ids, d_map);
     HIPCHK(c, hipGetLastError());
     if (enc) {
       rc = launch_extract(c, 0, 0, S.d_step_ids, B, (const int16_t*)S.d_in, S.d_feat);
       // warm-up steps of the lanes skip the quantizer: before step W only the spans' own rows produce
       const int Bq = i < W ? own : B;
-      if (!rc && Bq) rc = launch_rvq_encode(c, 0, Bq, S.d_feat, num_bits / 4, nullptr, S.d_out, S.d_step_ids);
+      if (!rc && Bq && !M) rc = launch_rvq_encode(c, 0, Bq, S.d_feat, num_bits / 4, nullptr, S.d_out, S.d_step_ids);
       if (rc || !Bq) continue;
-      hipLaunchKernelGGL(span_scatter_kernel, dim3(span_grid(Bq, out_bytes)), dim3(256), 0, st_, d_batch, Bq, i, S.d_out,
-                         out_bytes, 0, (uint8_t*)d_dst, d_map);
+      if (M) {   // (rows that have ended carry a valid count: the kernel's error word judges every row < Bq)
+        { ProfScope ps(c, K_RVQ_ENC, st_);
+          hipLaunchKernelGGL(rvq_encode_mixed_kernel, dim3(cdiv(Bq, 16)), dim3(64), 0, st_, c->model.cb, c->model.cbn, S.d_feat, Bq,
+                             S.d_step_size, S.d_out, S.d_step_ids, (int32_t*)nullptr, c->d_rvq_stats, c->d_mixed_err); }
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(span_scatter_mixed_kernel, dim3(span_grid(Bq, out_bytes)), dim3(256), 0, st_, d_batch, Bq, i, S.d_out,
+                           S.d_step_size, (uint8_t*)d_dst, M->d_packet_bytes, d_map);
+      } else
+        hipLaunchKernelGGL(span_scatter_kernel, dim3(span_grid(Bq, out_bytes)), dim3(256), 0, st_, d_batch, Bq, i, S.d_out,
+                           out_bytes, 0, (uint8_t*)d_dst, d_map);
     } else {
       if (d_gen_received) {   // as a lossy tick: the RVQ decode of every row, zero features where the tick conceals
-        if ((rc = launch_rvq_decode(c, 0, B, nullptr, S.d_in, num_bits / 4, S.d_feat))) continue;
+        if (M) {
+          { ProfScope ps(c, K_RVQ_DEC, st_);
+            hipLaunchKernelGGL(rvq_decode_mixed_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st_, c->model.cb, S.d_in, S.d_step_size, 0, B,
+                               S.d_feat); }
+          HIPCHK(c, hipGetLastError());
+        } else if ((rc = launch_rvq_decode(c, 0, B, nullptr, S.d_in, num_bits / 4, S.d_feat))) continue;
         hipLaunchKernelGGL(span_lossy_feat_kernel, dim3(span_grid(B, 64)), dim3(256), 0, st_, d_batch, B, i, d_gen_received,
                            S.d_feat);
         HIPCHK(c, hipGetLastError());
@@ -485,6 +514,104 @@ int launch_span_noise(lyra_hip_ctx* c, int side, hipStream_t st_, SpanSide& S, c
   return 0;
 }
 
+// The encode calls that report packet_bytes: DTX (lyra_hip_encode_spans_dtx_dev) and per-frame bitrates
+// (lyra_hip_encode_spans_mixed_dev, spans_mixed_api.inc), alone or together.
+//   dtx         the estimator in front of the steps, the one host wait, the steps on the compacted map; else the steps run on
+//               the spans as given and the host does not wait;
+//   frame_bits  null: every frame at num_bits.  Else a HOST array [frames], a bit count per frame (num_bits is not read):
+//               judged for every span frame before anything is enqueued, uploaded by buffer frame with the rows, and
+//               d_packet_bytes is written by the scatter.
+int span_lossy_ensure(lyra_hip_ctx* c, SpanSide& S, hipStream_t st_, size_t list_bytes, size_t snap_floats, int n_ctl);   // spans_lossy_api.inc
+int encode_spans_planned_dev(lyra_hip_ctx* c, const char* what, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids,
+                             int n_lanes, const int16_t* d_pcm_ext, int sample_rate_hz, int16_t* d_pcm16, int num_bits,
+                             const int32_t* frame_bits, bool dtx, uint8_t* d_packets, int32_t* d_packet_bytes) {
+  const int rate = sample_rate_hz;
+  const SpanExt X{rate, rate != 16000 ? d_pcm16 : nullptr};
+  SpanPlan dry;   // ids, lanes and frame ranges: the planner's rules, on the spans as given
+  int rc = span_check(c, what, sp::SIDE_ENC, frame_bits ? nullptr : &num_bits, spans, n_spans, lane_ids, n_lanes, d_pcm_ext,
+                      d_packets, X, &dry);
+  if (rc) return rc;
+  if (!d_packet_bytes) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
+  for (int s = 0; frame_bits && s < n_spans; ++s)
+    for (int64_t f = spans[s].first_frame; f < spans[s].first_frame + spans[s].n_frames; ++f)
+      if (frame_bits[f] < 4 || frame_bits[f] > 184 || (frame_bits[f] & 3))
+        return fail(c, LYRA_HIP_EINVAL, "%s: num_bits[%lld] = %d is not a multiple of 4 in 4..184", what, (long long)f,
+                    frame_bits[f]);
+  if (dtx && c->enc_noise_rate != rate)   // as lyra_hip_encode_ext_dev: the DTX estimator is created at the encoder's external rate
+    return fail(c, LYRA_HIP_EINVAL, "%s: DTX at %d Hz but the encoder-side noise estimator is set up for %d Hz "
+                "(call lyra_hip_set_encoder_sample_rate(%d) first)", what, rate, c->enc_noise_rate, rate);
+  const SpanPass rs = X.on() ? span_pass_rows<SpanRsRow>(spans, n_spans, nullptr) : SpanPass();
+  const SpanPass dx = dtx ? span_pass_rows<SpanDtxRow>(spans, n_spans, nullptr) : SpanPass();
+  if (rs.wgs < 0 || dx.wgs < 0) return fail(c, LYRA_HIP_EINVAL, "%s: too many frames for one pass", what);
+  DEVSCOPE(c);
+  hipStream_t st_;
+  SpanSide& S = span_side_open(c, sp::SIDE_ENC, &st_);
+  // all scratch for the worst case -- every frame active: at most one chunk per span and per lane -- before the first launch
+  const int rows_max = n_spans + n_lanes;
+  if ((rc = span_side_ensure(c, S, st_, rows_max, n_lanes + rs.n + dx.n))) return rc;
+  if ((rc = ensure_scratch(c, rows_max))) return rc;
+  if (dtx && (rc = span_dtx_ensure(c, S, st_, std::max<long long>(dx.frames, 1), std::max(dx.n, 1)))) return rc;
+  const size_t bits_bytes = frame_bits ? (size_t)dry.end_frame * sizeof(int32_t) : 0;
+  if (bits_bytes) {
+    if ((rc = span_lossy_ensure(c, S, st_, bits_bytes, 0, 0))) return rc;
+    if (!c->d_mixed_err) {   // the mixed quantizer's error word (mixed_api.inc), once per context
+      HIPCHK(c, dalloc(&c->d_mixed_err, 1));
+      HIPCHK(c, hipMemset(c->d_mixed_err, 0, 4));
+    }
+    for (int s = 0; s < n_spans; ++s)   // frames outside the spans are not read: their entries are never looked at either
+      if (spans[s].n_frames)
+        std::memcpy(S.h_lists + (size_t)spans[s].first_frame * sizeof(int32_t), frame_bits + spans[s].first_frame,
+                    (size_t)spans[s].n_frames * sizeof(int32_t));
+  }
+  // upload 1, behind the batch rows' place: the lanes' reset rows, the resampler's rows, the estimator's rows
+  SpanRow* h_fix = S.h_rows + rows_max;
+  for (int l = 0; l < n_lanes; ++l) h_fix[l] = SpanRow{lane_ids[l], 0, 0, -1, 0, 0, 0};
+  if (rs.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(h_fix + n_lanes));
+  if (dx.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanDtxRow*>(h_fix + n_lanes + rs.n));
+  const SpanRow* d_fix = S.d_rows + rows_max;
+  const SpanRsRow* d_rs_rows = reinterpret_cast<const SpanRsRow*>(d_fix + n_lanes);
+  const SpanDtxRow* d_dx_rows = reinterpret_cast<const SpanDtxRow*>(d_fix + n_lanes + rs.n);
+  if ((rc = span_side_begin(c, sp::SIDE_ENC))) return rc;
+  if ((rc = span_upload_rows(c, S, st_, rows_max, n_lanes + rs.n + dx.n))) return rc;
+  if (bits_bytes) {
+    HIPCHK(c, hipMemcpyAsync(S.d_lists, S.h_lists, bits_bytes, hipMemcpyHostToDevice, st_));
+    HIPCHK(c, hipEventRecord(S.ev_up, st_));
+    S.up_pending = true;
+  }
+  const int16_t* d_src16 = d_pcm_ext;
+  if ((rc = span_encode_front(c, st_, X, d_rs_rows, rs, &d_src16))) return rc;
+  SpanPlan P;
+  std::vector<lyra_hip_span> compact((size_t)n_spans);
+  if (dx.n) {
+    // (per-frame bitrates: the scatter stores the size of every frame that has a packet)
+    if ((rc = launch_span_noise(c, 0, st_, S, d_dx_rows, dx.n, dx.wgs, d_src16, d_packet_bytes, 0,
+                                frame_bits ? (int)MAX_PACKET_BYTES : (num_bits + 7) / 8, S.d_map)))
+      return rc;
+    // the one host wait of the call: the plan depends on the decisions
+    HIPCHK(c, hipStreamSynchronize(st_));
+    S.up_pending = false;
+  }
+  if (!dtx) {
+    std::copy(spans, spans + n_spans, compact.begin());
+  } else {   // what the encoder sees of span s: its non-noise hops, at the start of its region of the map
+    long long region = 0;
+    int r = 0;
+    for (int s = 0; s < n_spans; ++s) {
+      compact[s] = lyra_hip_span{spans[s].stream_id, region, spans[s].n_frames ? (int64_t)S.h_counts[r++] : 0};
+      if (compact[s].n_frames < 0 || compact[s].n_frames > spans[s].n_frames)
+        return fail(c, LYRA_HIP_EHIP, "%s: the scan's count of span %d is out of range", what, s);
+      region += spans[s].n_frames;
+    }
+  }
+  if ((rc = span_plan_checked(c, sp::SIDE_ENC, compact.data(), n_spans, lane_ids, n_lanes, &P, what))) return rc;
+  // upload 2: the batch rows (the pinned rows in front of upload 1's, so neither waits for the other)
+  span_fill_rows(P, compact.data(), lane_ids, 0, S.h_rows);
+  if ((rc = span_upload_rows(c, S, st_, 0, (int)P.chunks.size()))) return rc;
+  const SpanMixed M{reinterpret_cast<const int32_t*>(S.d_lists), d_packet_bytes};
+  rc = span_run_steps(c, true, S, st_, P, S.h_rows, S.d_rows, d_fix, n_lanes, d_src16, num_bits, d_packets, dtx ? S.d_map : nullptr,
+                      nullptr, frame_bits ? &M : nullptr);
+  return span_side_close(c, sp::SIDE_ENC, rc);
+}
 
 }  // namespace
 
@@ -548,64 +675,8 @@ int lyra_hip_decode_spans_ext(lyra_hip_ctx* c, const lyra_hip_span* spans, int n
 int lyra_hip_encode_spans_dtx_dev(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
                                   const int16_t* d_pcm_ext, int sample_rate_hz, int16_t* d_pcm16, int num_bits,
                                   uint8_t* d_packets, int32_t* d_packet_bytes) {
-  const char* what = "encode_spans_dtx";
-  const int rate = sample_rate_hz;
-  const SpanExt X{rate, rate != 16000 ? d_pcm16 : nullptr};
-  SpanPlan dry;   // ids, lanes and frame ranges: the planner's rules, on the spans as given
-  int rc = span_check(c, what, sp::SIDE_ENC, &num_bits, spans, n_spans, lane_ids, n_lanes, d_pcm_ext, d_packets, X, &dry);
-  if (rc) return rc;
-  if (!d_packet_bytes) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
-  if (c->enc_noise_rate != rate)   // as lyra_hip_encode_ext_dev: the DTX estimator is created at the encoder's external rate
-    return fail(c, LYRA_HIP_EINVAL, "%s: DTX at %d Hz but the encoder-side noise estimator is set up for %d Hz "
-                "(call lyra_hip_set_encoder_sample_rate(%d) first)", what, rate, c->enc_noise_rate, rate);
-  const SpanPass rs = X.on() ? span_pass_rows<SpanRsRow>(spans, n_spans, nullptr) : SpanPass();
-  const SpanPass dx = span_pass_rows<SpanDtxRow>(spans, n_spans, nullptr);
-  if (rs.wgs < 0 || dx.wgs < 0) return fail(c, LYRA_HIP_EINVAL, "%s: too many frames for one pass", what);
-  DEVSCOPE(c);
-  hipStream_t st_;
-  SpanSide& S = span_side_open(c, sp::SIDE_ENC, &st_);
-  // all scratch for the worst case -- every frame active: at most one chunk per span and per lane -- before the first launch
-  const int rows_max = n_spans + n_lanes;
-  if ((rc = span_side_ensure(c, S, st_, rows_max, n_lanes + rs.n + dx.n))) return rc;
-  if ((rc = ensure_scratch(c, rows_max))) return rc;
-  if ((rc = span_dtx_ensure(c, S, st_, std::max<long long>(dx.frames, 1), std::max(dx.n, 1)))) return rc;
-  // upload 1, behind the batch rows' place: the lanes' reset rows, the resampler's rows, the estimator's rows
-  SpanRow* h_fix = S.h_rows + rows_max;
-  for (int l = 0; l < n_lanes; ++l) h_fix[l] = SpanRow{lane_ids[l], 0, 0, -1, 0, 0, 0};
-  if (rs.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(h_fix + n_lanes));
-  span_pass_rows(spans, n_spans, reinterpret_cast<SpanDtxRow*>(h_fix + n_lanes + rs.n));
-  const SpanRow* d_fix = S.d_rows + rows_max;
-  const SpanRsRow* d_rs_rows = reinterpret_cast<const SpanRsRow*>(d_fix + n_lanes);
-  const SpanDtxRow* d_dx_rows = reinterpret_cast<const SpanDtxRow*>(d_fix + n_lanes + rs.n);
-  if ((rc = span_side_begin(c, sp::SIDE_ENC))) return rc;
-  if ((rc = span_upload_rows(c, S, st_, rows_max, n_lanes + rs.n + dx.n))) return rc;
-  const int16_t* d_src16 = d_pcm_ext;
-  if ((rc = span_encode_front(c, st_, X, d_rs_rows, rs, &d_src16))) return rc;
-  SpanPlan P;
-  std::vector<lyra_hip_span> compact((size_t)n_spans);
-  if (dx.n) {
-    if ((rc = launch_span_noise(c, 0, st_, S, d_dx_rows, dx.n, dx.wgs, d_src16, d_packet_bytes, 0, (num_bits + 7) / 8, S.d_map)))
-      return rc;
-    // the one host wait of the call: the plan depends on the decisions
-    HIPCHK(c, hipStreamSynchronize(st_));
-    S.up_pending = false;
-  }
-  {   // what the encoder sees of span s: its non-noise hops, at the start of its region of the map
-    long long region = 0;
-    int r = 0;
-    for (int s = 0; s < n_spans; ++s) {
-      compact[s] = lyra_hip_span{spans[s].stream_id, region, spans[s].n_frames ? (int64_t)S.h_counts[r++] : 0};
-      if (compact[s].n_frames < 0 || compact[s].n_frames > spans[s].n_frames)
-        return fail(c, LYRA_HIP_EHIP, "%s: the scan's count of span %d is out of range", what, s);
-      region += spans[s].n_frames;
-    }
-  }
-  if ((rc = span_plan_checked(c, sp::SIDE_ENC, compact.data(), n_spans, lane_ids, n_lanes, &P, what))) return rc;
-  // upload 2: the batch rows (the pinned rows in front of upload 1's, so neither waits for the other)
-  span_fill_rows(P, compact.data(), lane_ids, 0, S.h_rows);
-  if ((rc = span_upload_rows(c, S, st_, 0, (int)P.chunks.size()))) return rc;
-  rc = span_run_steps(c, true, S, st_, P, S.h_rows, S.d_rows, d_fix, n_lanes, d_src16, num_bits, d_packets, S.d_map);
-  return span_side_close(c, sp::SIDE_ENC, rc);
+  return encode_spans_planned_dev(c, "encode_spans_dtx", spans, n_spans, lane_ids, n_lanes, d_pcm_ext, sample_rate_hz, d_pcm16,
+                                  num_bits, nullptr, true, d_packets, d_packet_bytes);
 }
 
 // host-buffer form: packet rows of noise frames read back as zeros

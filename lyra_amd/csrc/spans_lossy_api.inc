@@ -51,20 +51,17 @@ int span_lossy_ensure(lyra_hip_ctx* c, SpanSide& S, hipStream_t st_, size_t list
   return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int lyra_hip_spans_lossy_plan(const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes, int max_streams,
-                              const int32_t* packet_bytes, int packet_size, const uint32_t* ctl_in,
-                              lyra_hip_span_lossy_counts* counts, int64_t* gen_frames, uint8_t* gen_received, int64_t* rx_frames,
-                              int64_t* cng_frames, int32_t* cng_versions, int32_t* versions, int32_t* info,
-                              lyra_hip_span_chunk* chunks, int cap, int* n_steps) {
+// lyra_hip_spans_lossy_plan, and with packet_size == slp::SIZE_PER_FRAME lyra_hip_spans_lossy_plan_mixed (spans_mixed_api.inc)
+int spans_lossy_plan_sized(const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes, int max_streams,
+                           const int32_t* packet_bytes, int packet_size, const uint32_t* ctl_in, lyra_hip_span_lossy_counts* counts,
+                           int64_t* gen_frames, uint8_t* gen_received, int64_t* rx_frames, int64_t* cng_frames,
+                           int32_t* cng_versions, int32_t* versions, int32_t* info, lyra_hip_span_chunk* chunks, int cap,
+                           int* n_steps) {
   const sp::Span* in = reinterpret_cast<const sp::Span*>(spans);
   std::vector<sp::Chunk> dry;
   if (sp::plan(sp::SIDE_DEC, in, n_spans, lane_ids, n_lanes, max_streams, &dry, nullptr) < 0) return LYRA_HIP_EINVAL;
   std::vector<slp::SpanLists> lists;
-  if (slp::plan(in, n_spans, packet_bytes, packet_size, ctl_in, &lists) < 0 || (n_spans && !counts)) return LYRA_HIP_EINVAL;
+  if (slp::plan_sized(in, n_spans, packet_bytes, packet_size, ctl_in, &lists) < 0 || (n_spans && !counts)) return LYRA_HIP_EINVAL;
   size_t g = 0, r = 0, k = 0, v = 0, f = 0;
   for (int s = 0; s < n_spans; ++s) {
     const slp::SpanLists& L = lists[(size_t)s];
@@ -85,25 +82,29 @@ int lyra_hip_spans_lossy_plan(const lyra_hip_span* spans, int n_spans, const int
   return n;
 }
 
-int lyra_hip_decode_spans_lossy_dev(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
-                                    const uint8_t* d_packets, const int32_t* packet_bytes, int num_bits, int sample_rate_hz,
-                                    int16_t* d_pcm16, int16_t* d_pcm_ext, int32_t* d_is_noise, int32_t* d_is_comfort_noise) {
-  const char* what = "decode_spans_lossy";
+// lyra_hip_decode_spans_lossy_dev, and with `mixed` lyra_hip_decode_spans_lossy_mixed_dev (spans_mixed_api.inc): num_bits is not
+// read, a packet has any size of the codec (8 / 15 / 23, chosen per frame), packet rows are MAX_PACKET_BYTES apart, and the list
+// uploaded as gen_received holds every tick's size, from which the steps' gather hands it to rvq_decode_mixed_kernel row by row.
+int decode_spans_lossy_sized_dev(lyra_hip_ctx* c, const char* what, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids,
+                                 int n_lanes, const uint8_t* d_packets, const int32_t* packet_bytes, int num_bits, bool mixed,
+                                 int sample_rate_hz, int16_t* d_pcm16, int16_t* d_pcm_ext, int32_t* d_is_noise,
+                                 int32_t* d_is_comfort_noise) {
   const int rate = sample_rate_hz;
   const bool ext = rate != 16000;
   const SpanExt X{rate, ext ? d_pcm16 : nullptr};
   SpanPlan dry;   // ids, lanes and frame ranges: the planner's rules, on the spans as given
-  int rc = span_check(c, what, sp::SIDE_DEC, &num_bits, spans, n_spans, lane_ids, n_lanes, ext ? d_pcm_ext : d_pcm16, d_packets, X,
-                      &dry);
+  int rc = span_check(c, what, sp::SIDE_DEC, mixed ? nullptr : &num_bits, spans, n_spans, lane_ids, n_lanes,
+                      ext ? d_pcm_ext : d_pcm16, d_packets, X, &dry);
   if (rc) return rc;
-  const int nbytes = (num_bits + 7) / 8;
+  const int nbytes = mixed ? slp::SIZE_PER_FRAME : (num_bits + 7) / 8;
   if (dry.end_frame && !packet_bytes) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
   long long total = 0;
   int n_l = 0;   // spans with frames
   for (int s = 0; s < n_spans; ++s) {
     for (int64_t f = spans[s].first_frame; f < spans[s].first_frame + spans[s].n_frames; ++f)
-      if (packet_bytes[f] != 0 && packet_bytes[f] != nbytes)
-        return fail(c, LYRA_HIP_EINVAL, "%s: packet_bytes[%lld] = %d is neither 0 nor %d", what, (long long)f, packet_bytes[f], nbytes);
+      if (packet_bytes[f] != 0 && (mixed ? !mixed_received(packet_bytes[f]) : packet_bytes[f] != nbytes))
+        return fail(c, LYRA_HIP_EINVAL, "%s: packet_bytes[%lld] = %d is neither 0 nor %s%d", what, (long long)f, packet_bytes[f],
+                    mixed ? "8, 15 or " : "", mixed ? (int)MAX_PACKET_BYTES : nbytes);
     total += spans[s].n_frames;
     n_l += spans[s].n_frames > 0;
   }
@@ -152,7 +153,7 @@ int lyra_hip_decode_spans_lossy_dev(lyra_hip_ctx* c, const lyra_hip_span* spans,
     }
     // ---- the plan ----
     std::vector<slp::SpanLists> lists;
-    if (slp::plan(reinterpret_cast<const sp::Span*>(spans), n_spans, packet_bytes, nbytes, ctl.data(), &lists) < 0)
+    if (slp::plan_sized(reinterpret_cast<const sp::Span*>(spans), n_spans, packet_bytes, nbytes, ctl.data(), &lists) < 0)
       return fail(c, LYRA_HIP_EINVAL, "%s: the plan refused the packet sizes", what);
     const std::vector<sp::Span> compact = slp::compact_gen_spans(reinterpret_cast<const sp::Span*>(spans), lists);
     if ((rc = span_plan_checked(c, sp::SIDE_DEC, reinterpret_cast<const lyra_hip_span*>(compact.data()), n_spans, lane_ids,
@@ -254,9 +255,33 @@ int lyra_hip_decode_spans_lossy_dev(lyra_hip_ctx* c, const lyra_hip_span* spans,
   };
   rc = prepare();
   // ---- 1: the steps; the generative hops of the run_gen ticks -> d_pcm16 ----
-  if (!rc) rc = span_run_steps(c, false, S, st_, P, S.h_rows, S.d_rows, d_fix, n_lanes, d_packets, num_bits, d_pcm16, d_gen, d_grx);
+  const SpanMixed M;
+  if (!rc)
+    rc = span_run_steps(c, false, S, st_, P, S.h_rows, S.d_rows, d_fix, n_lanes, d_packets, num_bits, d_pcm16, d_gen, d_grx,
+                        mixed ? &M : nullptr);
   if (!rc && n_l) rc = passes();
   return span_side_close(c, sp::SIDE_DEC, rc);
+}
+
+}  // namespace
+
+extern "C" {
+
+int lyra_hip_spans_lossy_plan(const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes, int max_streams,
+                              const int32_t* packet_bytes, int packet_size, const uint32_t* ctl_in,
+                              lyra_hip_span_lossy_counts* counts, int64_t* gen_frames, uint8_t* gen_received, int64_t* rx_frames,
+                              int64_t* cng_frames, int32_t* cng_versions, int32_t* versions, int32_t* info,
+                              lyra_hip_span_chunk* chunks, int cap, int* n_steps) {
+  if (packet_size <= 0) return LYRA_HIP_EINVAL;
+  return spans_lossy_plan_sized(spans, n_spans, lane_ids, n_lanes, max_streams, packet_bytes, packet_size, ctl_in, counts,
+                                gen_frames, gen_received, rx_frames, cng_frames, cng_versions, versions, info, chunks, cap, n_steps);
+}
+
+int lyra_hip_decode_spans_lossy_dev(lyra_hip_ctx* c, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
+                                    const uint8_t* d_packets, const int32_t* packet_bytes, int num_bits, int sample_rate_hz,
+                                    int16_t* d_pcm16, int16_t* d_pcm_ext, int32_t* d_is_noise, int32_t* d_is_comfort_noise) {
+  return decode_spans_lossy_sized_dev(c, "decode_spans_lossy", spans, n_spans, lane_ids, n_lanes, d_packets, packet_bytes, num_bits,
+                                      false, sample_rate_hz, d_pcm16, d_pcm_ext, d_is_noise, d_is_comfort_noise);
 }
 
 // host-buffer form: is_noise / is_comfort_noise may be null, pcm_ext at 16000 too

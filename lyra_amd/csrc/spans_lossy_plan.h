@@ -24,7 +24,7 @@ namespace slp {
 
 struct SpanLists {
   std::vector<int64_t> gen_frame;      // buffer frames of the run_gen ticks, in order ...
-  std::vector<uint8_t> gen_received;   // ... 1: from the packet, 0: concealed (zero features)
+  std::vector<uint8_t> gen_received;   // ... 1: from the packet, 0: concealed (zero features); plan_mixed: the packet's size
   std::vector<int64_t> rx_frame;       // buffer frames of the received ticks
   std::vector<int64_t> cng_frame;      // buffer frames of the run_cng ticks ...
   std::vector<int32_t> cng_version;    // ... and the received frames of the span in front of each
@@ -35,9 +35,14 @@ struct SpanLists {
 
 // packet_bytes[frame]: 0 = no packet, nbytes = a packet; ctl_in[s]: the control word of span s's stream on entry.
 // Returns 0, or sp::PLAN_EINVAL for a size that is neither, negative spans or missing arrays; *out is then unspecified.
-inline int plan(const sp::Span* spans, int n_spans, const int32_t* packet_bytes, int nbytes, const uint32_t* ctl_in,
-                std::vector<SpanLists>* out) {
-  if (n_spans < 0 || nbytes <= 0 || (n_spans && (!spans || !ctl_in)) || !out) return sp::PLAN_EINVAL;
+// nbytes == SIZE_PER_FRAME (plan_mixed): a packet is any size of the codec (mixed_received: 8 / 15 / 23), chosen per frame as
+// SetEncodedPacket does, and gen_received holds that size.  The state machine sees only whether a packet came, so every other
+// list is the uniform plan's for the same receive pattern.
+constexpr int SIZE_PER_FRAME = -1;
+inline int plan_sized(const sp::Span* spans, int n_spans, const int32_t* packet_bytes, int nbytes, const uint32_t* ctl_in,
+                      std::vector<SpanLists>* out) {
+  const bool mixed = nbytes == SIZE_PER_FRAME;
+  if (n_spans < 0 || (!mixed && nbytes <= 0) || (n_spans && (!spans || !ctl_in)) || !out) return sp::PLAN_EINVAL;
   out->assign((size_t)n_spans, SpanLists());
   for (int s = 0; s < n_spans; ++s) {
     const int64_t first = spans[s].first_frame, n = spans[s].n_frames;
@@ -48,7 +53,7 @@ inline int plan(const sp::Span* spans, int n_spans, const int32_t* packet_bytes,
     L.info.reserve((size_t)n);
     for (int64_t f = first; f < first + n; ++f) {
       const int32_t pb = packet_bytes[f];
-      if (pb != 0 && pb != nbytes) return sp::PLAN_EINVAL;
+      if (pb != 0 && (mixed ? !mixed_received(pb) : pb != nbytes)) return sp::PLAN_EINVAL;
       const LossyTick t = lossy_tick(ctl, pb != 0);
       ctl = t.ctl;
       if (t.run_cng) {   // in front of the tick's own update: launch_cng precedes launch_noise_masked
@@ -58,7 +63,7 @@ inline int plan(const sp::Span* spans, int n_spans, const int32_t* packet_bytes,
       }
       if (t.run_gen) {
         L.gen_frame.push_back(f);
-        L.gen_received.push_back(t.feed_est ? 1 : 0);
+        L.gen_received.push_back(!t.feed_est ? 0 : mixed ? (uint8_t)pb : 1);
       }
       if (t.feed_est) {
         L.rx_frame.push_back(f);
@@ -69,6 +74,15 @@ inline int plan(const sp::Span* spans, int n_spans, const int32_t* packet_bytes,
     L.ctl_out = ctl;
   }
   return 0;
+}
+
+inline int plan(const sp::Span* spans, int n_spans, const int32_t* packet_bytes, int nbytes, const uint32_t* ctl_in,
+                std::vector<SpanLists>* out) {
+  return nbytes <= 0 ? sp::PLAN_EINVAL : plan_sized(spans, n_spans, packet_bytes, nbytes, ctl_in, out);
+}
+inline int plan_mixed(const sp::Span* spans, int n_spans, const int32_t* packet_bytes, const uint32_t* ctl_in,
+                      std::vector<SpanLists>* out) {
+  return plan_sized(spans, n_spans, packet_bytes, SIZE_PER_FRAME, ctl_in, out);
 }
 
 // What the generative model sees: span s = the run_gen ticks of span s, laid out span after span in one dense list.

@@ -8,6 +8,7 @@
 #include <string>
 
 #include "../../include/lyra_hip.h"
+#include "../../include/lyra_hip_spans_mixed.h"
 #include "glog/logging.h"
 #include "lyra_batch_codec.h"
 
@@ -21,6 +22,8 @@
 #pragma weak lyra_hip_decode_spans_ext
 #pragma weak lyra_hip_encode_spans_dtx
 #pragma weak lyra_hip_decode_spans_lossy
+#pragma weak lyra_hip_encode_spans_mixed
+#pragma weak lyra_hip_decode_spans_lossy_mixed
 
 namespace chromemedia {
 namespace codec {
@@ -354,17 +357,21 @@ bool HaveSpanDtxCall() {
   return false;
 }
 
-}  // namespace
-
-bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, int num_channels, int sample_rate_hz,
-                            int bitrate, bool enable_preprocessing, bool enable_dtx,
-                            const ghc::filesystem::path& model_path, std::vector<std::vector<uint8_t>>* encoded_features,
-                            int num_lanes, int device, std::vector<std::vector<int32_t>>* packet_sizes) {
+// bitrates == nullptr: every hop at `bitrate`; else (*bitrates)[i][h] for hop h of file i, through lyra_hip_encode_spans_mixed
+bool EncodeSpans(const std::vector<std::vector<int16_t>>& wav_data, int num_channels, int sample_rate_hz, int bitrate,
+                 const std::vector<std::vector<int>>* bitrates, bool enable_preprocessing, bool enable_dtx,
+                 const ghc::filesystem::path& model_path, std::vector<std::vector<uint8_t>>* encoded_features, int num_lanes,
+                 int device, std::vector<std::vector<int32_t>>* packet_sizes) {
   if (!CheckScope(num_channels, sample_rate_hz, enable_preprocessing, enable_dtx) || !HaveSpanCalls(sample_rate_hz)) return false;
   if (enable_dtx && !HaveSpanDtxCall()) return false;
-  const int num_bits = BatchBitrateToNumQuantizedBits(bitrate);
+  if (bitrates && !lyra_hip_encode_spans_mixed) {
+    LOG(ERROR) << "This build of the lyra_hip library has no time-parallel span call with per-hop bitrates.";
+    return false;
+  }
+  const int num_bits = bitrates ? 0 : BatchBitrateToNumQuantizedBits(bitrate);
   if (num_bits < 0) { LOG(ERROR) << "Bitrate " << bitrate << " bps is not supported by codec."; return false; }
   const int n = (int)wav_data.size();
+  if (bitrates && (int)bitrates->size() != n) { LOG(ERROR) << "One bitrate schedule per file is required."; return false; }
   encoded_features->assign(n, {});
   if (packet_sizes) packet_sizes->assign(n, {});
   if (n == 0) return true;
@@ -372,14 +379,25 @@ bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, i
   const SpanJob job = MakeSpanJob(wav_data, (size_t)sample_rate_hz / 50, LYRA_HIP_SIDE_ENCODER, num_lanes, &pcm);
   Ctx ctx;
   if (!ctx.Create(model_path, device, n + (int)job.lanes.size(), "encoder")) return false;
-  const size_t packet_size = (size_t)BatchBitrateToPacketSize(bitrate);
+  const size_t packet_size = bitrates ? (size_t)LYRA_HIP_MAX_PACKET_BYTES : (size_t)BatchBitrateToPacketSize(bitrate);
   std::vector<uint8_t> packets((size_t)job.frames * packet_size);
-  // bytes of every frame's packet: without DTX the packet size, with it what the call reports (0: an empty packet)
-  std::vector<int32_t> sizes((size_t)job.frames, enable_dtx ? 0 : (int32_t)packet_size);
-  const bool ok = enable_dtx ? lyra_hip_set_encoder_sample_rate(ctx.c, sample_rate_hz) == 0 &&
-                                   lyra_hip_encode_spans_dtx(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(),
-                                                             pcm.data(), sample_rate_hz, num_bits, packets.data(), sizes.data()) == 0
-                             : EncodeSpansAt(sample_rate_hz, ctx.c, job, pcm.data(), num_bits, packets.data()) == 0;
+  // bytes of every frame's packet: without DTX the packet size, with it or with per-hop bitrates what the call reports
+  std::vector<int32_t> sizes((size_t)job.frames, enable_dtx || bitrates ? 0 : (int32_t)packet_size);
+  std::vector<int32_t> bits;   // per frame
+  for (int i = 0; bitrates && i < n; ++i) {
+    if ((int64_t)(*bitrates)[i].size() < job.spans[i].n_frames) { LOG(ERROR) << "A bitrate schedule is shorter than its file."; return false; }
+    for (int64_t h = 0; h < job.spans[i].n_frames; ++h) {
+      bits.push_back(BatchBitrateToNumQuantizedBits((*bitrates)[i][h]));
+      if (bits.back() < 0) { LOG(ERROR) << "Bitrate " << (*bitrates)[i][h] << " bps is not supported by codec."; return false; }
+    }
+  }
+  const int n_lanes = (int)job.lanes.size();
+  const bool ok = (!enable_dtx || lyra_hip_set_encoder_sample_rate(ctx.c, sample_rate_hz) == 0) &&
+                  (bitrates     ? lyra_hip_encode_spans_mixed(ctx.c, job.spans.data(), n, job.lanes.data(), n_lanes, pcm.data(),
+                                                              sample_rate_hz, bits.data(), enable_dtx, packets.data(), sizes.data())
+                   : enable_dtx ? lyra_hip_encode_spans_dtx(ctx.c, job.spans.data(), n, job.lanes.data(), n_lanes, pcm.data(),
+                                                            sample_rate_hz, num_bits, packets.data(), sizes.data())
+                                : EncodeSpansAt(sample_rate_hz, ctx.c, job, pcm.data(), num_bits, packets.data())) == 0;
   if (!ok) {
     LOG(ERROR) << "Unable to encode features: " << lyra_hip_last_error(ctx.c);
     return false;
@@ -392,6 +410,24 @@ bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, i
     }
   }
   return true;
+}
+}  // namespace
+
+bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, int num_channels, int sample_rate_hz,
+                            int bitrate, bool enable_preprocessing, bool enable_dtx,
+                            const ghc::filesystem::path& model_path, std::vector<std::vector<uint8_t>>* encoded_features,
+                            int num_lanes, int device, std::vector<std::vector<int32_t>>* packet_sizes) {
+  return EncodeSpans(wav_data, num_channels, sample_rate_hz, bitrate, nullptr, enable_preprocessing, enable_dtx, model_path,
+                     encoded_features, num_lanes, device, packet_sizes);
+}
+
+bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, int num_channels, int sample_rate_hz,
+                            const std::vector<std::vector<int>>& bitrates, bool enable_preprocessing, bool enable_dtx,
+                            const ghc::filesystem::path& model_path, std::vector<std::vector<uint8_t>>* encoded_features,
+                            std::vector<std::vector<int32_t>>* packet_sizes, int num_lanes, int device) {
+  if (!packet_sizes) { LOG(ERROR) << "With per-hop bitrates the packet sizes are part of the result."; return false; }
+  return EncodeSpans(wav_data, num_channels, sample_rate_hz, 0, &bitrates, enable_preprocessing, enable_dtx, model_path,
+                     encoded_features, num_lanes, device, packet_sizes);
 }
 
 bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams, int packet_size,
@@ -428,14 +464,18 @@ bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_
 }
 
 namespace {
-// packet_sizes[i][h] is 0 or packet_size and the non-empty packets of stream i are exactly packet_streams[i]
+// packet_sizes[i][h] is 0 or packet_size (packet_size 0: or any size of the codec) and the non-empty packets of stream i are
+// exactly packet_streams[i]
 bool SizesMatch(const std::vector<std::vector<uint8_t>>& packet_streams, const std::vector<std::vector<int32_t>>& packet_sizes,
                 int packet_size) {
   if (packet_sizes.size() != packet_streams.size()) { LOG(ERROR) << "One list of packet sizes per stream is required."; return false; }
   for (size_t i = 0; i < packet_streams.size(); ++i) {
     size_t bytes = 0;
     for (int32_t b : packet_sizes[i]) {
-      if (b != 0 && b != packet_size) { LOG(ERROR) << "A packet size is neither 0 nor " << packet_size << "."; return false; }
+      if (b != 0 && (packet_size ? b != packet_size : b != 8 && b != 15 && b != LYRA_HIP_MAX_PACKET_BYTES)) {
+        LOG(ERROR) << "A packet size (" << b << ") is neither 0 nor " << (packet_size ? std::to_string(packet_size) : "8, 15 or 23") << ".";
+        return false;
+      }
       bytes += (size_t)b;
     }
     if (bytes != packet_streams[i].size()) { LOG(ERROR) << "The packet sizes do not add up to the encoded stream."; return false; }
@@ -479,17 +519,21 @@ bool DecodeFeaturesBatch(const std::vector<std::vector<uint8_t>>& packet_streams
   return true;
 }
 
-bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams,
-                                const std::vector<std::vector<int32_t>>& packet_sizes, int packet_size, int sample_rate_hz,
-                                const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
-                                int num_lanes, int device) {
+namespace {
+// packet_size 0: every hop's size is its own (8 / 15 / 23), through lyra_hip_decode_spans_lossy_mixed
+bool DecodeSpansLossy(const std::vector<std::vector<uint8_t>>& packet_streams,
+                      const std::vector<std::vector<int32_t>>& packet_sizes, int packet_size, int sample_rate_hz,
+                      const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio, int num_lanes,
+                      int device) {
   if (!CheckScope(1, sample_rate_hz, false, false)) return false;
-  const int num_bits = NumBitsOfPacketSize(packet_size);
+  const int num_bits = packet_size ? NumBitsOfPacketSize(packet_size) : 0;
   if (num_bits < 0 || !HaveSpanCalls(sample_rate_hz)) return false;
-  if (!lyra_hip_decode_spans_lossy) {
-    LOG(ERROR) << "This build of the lyra_hip library has no time-parallel span call for missing packets.";
+  if (packet_size ? !lyra_hip_decode_spans_lossy : !lyra_hip_decode_spans_lossy_mixed) {
+    LOG(ERROR) << "This build of the lyra_hip library has no time-parallel span call for missing packets"
+               << (packet_size ? "." : " of per-hop sizes.");
     return false;
   }
+  const int row_size = packet_size ? packet_size : LYRA_HIP_MAX_PACKET_BYTES;
   if (!SizesMatch(packet_streams, packet_sizes, packet_size)) return false;
   const int n = (int)packet_streams.size();
   decoded_audio->assign(n, {});
@@ -502,8 +546,8 @@ bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_
     job.spans.push_back({(int32_t)i, job.frames, (int64_t)packet_sizes[i].size()});
     size_t at = 0;
     for (int32_t b : packet_sizes[i]) {
-      packets.insert(packets.end(), (size_t)packet_size, 0);
-      if (b) std::copy(packet_streams[i].begin() + at, packet_streams[i].begin() + at + b, packets.end() - packet_size);
+      packets.insert(packets.end(), (size_t)row_size, 0);
+      if (b) std::copy(packet_streams[i].begin() + at, packet_streams[i].begin() + at + b, packets.end() - row_size);
       at += (size_t)b;
       sizes.push_back(b);
     }
@@ -516,8 +560,12 @@ bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_
   const size_t hop_samples = (size_t)sample_rate_hz / 50;
   const bool ext = sample_rate_hz != kBatchInternalSampleRateHz;
   std::vector<int16_t> pcm16((size_t)job.frames * kBatchHopSamples), pcm_ext(ext ? (size_t)job.frames * hop_samples : 0);
-  if (lyra_hip_decode_spans_lossy(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), packets.data(), sizes.data(),
-                                  num_bits, sample_rate_hz, pcm16.data(), ext ? pcm_ext.data() : nullptr, nullptr, nullptr) != 0) {
+  const int n_lanes = (int)job.lanes.size();
+  int16_t* const ext_out = ext ? pcm_ext.data() : nullptr;
+  if ((packet_size ? lyra_hip_decode_spans_lossy(ctx.c, job.spans.data(), n, job.lanes.data(), n_lanes, packets.data(), sizes.data(),
+                                                 num_bits, sample_rate_hz, pcm16.data(), ext_out, nullptr, nullptr)
+                   : lyra_hip_decode_spans_lossy_mixed(ctx.c, job.spans.data(), n, job.lanes.data(), n_lanes, packets.data(),
+                                                       sizes.data(), sample_rate_hz, pcm16.data(), ext_out, nullptr, nullptr)) != 0) {
     LOG(ERROR) << "Could not decode samples: " << lyra_hip_last_error(ctx.c);
     return false;
   }
@@ -526,6 +574,22 @@ bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_
     (*decoded_audio)[i].assign(pcm.begin() + job.spans[i].first_frame * hop_samples,
                                pcm.begin() + (job.spans[i].first_frame + job.spans[i].n_frames) * hop_samples);
   return true;
+}
+}  // namespace
+
+bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams,
+                                const std::vector<std::vector<int32_t>>& packet_sizes, int packet_size, int sample_rate_hz,
+                                const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
+                                int num_lanes, int device) {
+  if (NumBitsOfPacketSize(packet_size) < 0) return false;
+  return DecodeSpansLossy(packet_streams, packet_sizes, packet_size, sample_rate_hz, model_path, decoded_audio, num_lanes, device);
+}
+
+bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams,
+                                const std::vector<std::vector<int32_t>>& packet_sizes, int sample_rate_hz,
+                                const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
+                                int num_lanes, int device) {
+  return DecodeSpansLossy(packet_streams, packet_sizes, 0, sample_rate_hz, model_path, decoded_audio, num_lanes, device);
 }
 
 namespace {

@@ -71,6 +71,13 @@ bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, i
                             const ghc::filesystem::path& model_path, std::vector<std::vector<uint8_t>>* encoded_features,
                             int num_lanes = kDefaultSpanLanes, int device = 0,
                             std::vector<std::vector<int32_t>>* packet_sizes = nullptr);
+// ... with a bitrate per hop, LyraEncoder::set_bitrate between hops, through lyra_hip_encode_spans_mixed
+// (include/lyra_hip_spans_mixed.h): bitrates[i][h] = 3200 / 6000 / 9200 for hop h of file i.  packet_sizes is part of the result:
+// encoded_features[i] is the non-empty packets concatenated and cannot be cut into hops without them.
+bool EncodeWavsTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, int num_channels, int sample_rate_hz,
+                            const std::vector<std::vector<int>>& bitrates, bool enable_preprocessing, bool enable_dtx,
+                            const ghc::filesystem::path& model_path, std::vector<std::vector<uint8_t>>* encoded_features,
+                            std::vector<std::vector<int32_t>>* packet_sizes, int num_lanes = kDefaultSpanLanes, int device = 0);
 bool EncodeFilesTimeParallel(const std::vector<ghc::filesystem::path>& wav_paths,
                              const std::vector<ghc::filesystem::path>& output_paths, int bitrate, bool enable_preprocessing,
                              bool enable_dtx, const ghc::filesystem::path& model_path, int num_lanes = kDefaultSpanLanes,
@@ -85,6 +92,12 @@ bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_
 // takes packet_sizes (what EncodeWavsTimeParallel(enable_dtx) returns; a loss trace has the same shape).
 bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams,
                                 const std::vector<std::vector<int32_t>>& packet_sizes, int packet_size, int sample_rate_hz,
+                                const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
+                                int num_lanes = kDefaultSpanLanes, int device = 0);
+// ... with every hop's size its own, as SetEncodedPacket reads it, through lyra_hip_decode_spans_lossy_mixed: packet_sizes[i][h]
+// = 0 / 8 / 15 / 23, packet_streams[i] the non-empty packets concatenated (what the EncodeWavsTimeParallel form above returns).
+bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams,
+                                const std::vector<std::vector<int32_t>>& packet_sizes, int sample_rate_hz,
                                 const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
                                 int num_lanes = kDefaultSpanLanes, int device = 0);
 bool DecodeFilesTimeParallel(const std::vector<ghc::filesystem::path>& encoded_paths,

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """One long recording, encode then decode, time-parallel against hop by hop (BASELINE config #1: one file).
 
-   python tools/span_bench.py [--hops 180000] [--lanes 4096] [--bits 184] [--rate 16000] [--out profiles/span_transcode.jsonl]
+   python tools/span_bench.py [--hops 180000] [--lanes 4096] [--bits 184] [--rate 16000] [--dtx | --lossy | --mixed]
+                              [--out profiles/span_transcode.jsonl]
 
 --rate 8000 / 32000 / 48000: the recording is at that rate and both legs run the `_ext` span calls and the file functions at it
 (encode from the rate, decode to it); the baseline is the unchanged hop-by-hop calls at the same rate, lyra_hip_resample +
@@ -23,6 +24,13 @@ sizes of lyra_hip_encode_spans_dtx_dev on the half-silent recording): lyra_hip_d
 only other way to do the job, lyra_hip_decode_lossy_dev hop by hop on a twin context (B = 1, every call enqueued without a wait, one
 synchronise at the end); `verified`: all four outputs of all hops equal.  kernel_share gives the part of span_lossy_scan_kernel --
 the serial floor -- of span_logmel_map_kernel and of span_cng_kernel in the summed kernel time of the device leg.
+
+--mixed (with or without --rate): per-frame bitrates (include/lyra_hip_spans_mixed.h).  The bitrate cycles 3200 -> 6000 -> 9200
+every 50 hops.  One mixed_transcode record: lyra_hip_encode_spans_mixed_dev against the uniform span call at 184 bits on the same
+audio, and lyra_hip_decode_spans_lossy_mixed_dev on the "gilbert" trace against lyra_hip_decode_spans_lossy_dev at 184 bits on the
+same trace (`*_over_uniform`: mixed time / uniform time); both also against the only other way to do the job, the hop-by-hop mixed
+calls lyra_hip_encode_mixed_dev / lyra_hip_decode_lossy_mixed_dev on a twin context (B = 1, every call enqueued without a wait,
+one synchronise at the end); `verified`: packets up to their size and sizes, and all four decoder outputs, of all hops equal.
 
 Records, appended to --out:
   span_transcode   lyra_hip_encode_spans_dev + lyra_hip_decode_spans_dev on device buffers, one stream of --hops hops with
@@ -219,6 +227,87 @@ def lossy_device_leg(args, pcm, trace):
     return rec
 
 
+def mixed_device_leg(args, pcm):
+    import torch
+    import lyra_amd
+    from lyra_amd import codec
+    dev = torch.device("cuda", 0)
+    hops, ext, row = pcm.shape[0], args.rate != 16000, codec.MAX_PACKET_BYTES
+    ctx = lyra_amd.LyraHip(device=0, max_streams=args.lanes + 1, requant="xnnpack")
+    lanes = np.arange(1, args.lanes + 1, dtype=np.int32)
+    spans = [(0, 0, hops)]
+    bits = np.array([64, 120, 184], np.int32)[(np.arange(hops) // 50) % 3]
+    rx = gilbert(hops)
+    pb = np.where(rx, (bits + 7) // 8, 0).astype(np.int32)
+    d_pcm = torch.from_numpy(pcm).to(dev)
+    d_w16 = torch.zeros((hops, 320), dtype=torch.int16, device=dev) if ext else None
+    d_pk, d_pk184 = (torch.zeros((hops, row), dtype=torch.uint8, device=dev) for _ in range(2))
+    d_nb = torch.zeros(hops, dtype=torch.int32, device=dev)
+
+    def outputs():
+        return (torch.zeros((hops, 320), dtype=torch.int16, device=dev),
+                torch.zeros((hops, args.rate // 50), dtype=torch.int16, device=dev) if ext else None,
+                torch.zeros(hops, dtype=torch.int32, device=dev), torch.zeros(hops, dtype=torch.int32, device=dev))
+    got, uni = outputs(), outputs()
+    legs = {   # the 8- and 15-byte packets are prefixes of the 184-bit one: the decode legs read d_pk184
+        "encode": lambda: ctx.encode_spans_mixed_dev(spans, d_pcm, bits, d_pk, d_nb, lanes, sample_rate_hz=args.rate, d_pcm16=d_w16),
+        "encode_uniform": lambda: ctx.encode_spans_dev(spans, d_pcm, 184, d_pk184, lanes, sample_rate_hz=args.rate, d_pcm16=d_w16),
+        "decode": lambda: ctx.decode_spans_lossy_mixed_dev(spans, d_pk184, pb, got[0], lanes, sample_rate_hz=args.rate,
+                                                           d_pcm_ext=got[1], d_is_noise=got[2], d_is_comfort_noise=got[3]),
+        "decode_uniform": lambda: ctx.decode_spans_lossy_dev(spans, d_pk184, np.where(rx, row, 0).astype(np.int32), 184, uni[0], lanes,
+                                                             sample_rate_hz=args.rate, d_pcm_ext=uni[1], d_is_noise=uni[2],
+                                                             d_is_comfort_noise=uni[3]),
+    }
+    times = {k: [] for k in legs}
+    for rep in range(args.reps + 1):   # rep 0 warms (allocations, code)
+        for name, call in legs.items():
+            ctx.reset()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            call()
+            ctx.synchronize()
+            if rep:
+                times[name].append(time.perf_counter() - t0)
+    t = {k: float(np.median(v)) for k, v in times.items()}
+    plan = codec.spans_lossy_plan_mixed(spans, pb, [0], lanes, args.lanes + 1)
+    rec = dict(kind="mixed_transcode", rate=args.rate, hops=hops, lanes=int(args.lanes), switch_every=50,
+               received_hops=int(rx.sum()), steps_decode=int(plan["n_steps"]), reps=args.reps,
+               encode_s=round(t["encode"], 5), encode_uniform_s=round(t["encode_uniform"], 5),
+               encode_over_uniform=round(t["encode"] / t["encode_uniform"], 3), encode_frames_per_s=round(hops / t["encode"]),
+               decode_s=round(t["decode"], 5), decode_uniform_s=round(t["decode_uniform"], 5),
+               decode_over_uniform=round(t["decode"] / t["decode_uniform"], 3), decode_frames_per_s=round(hops / t["decode"]),
+               mixed_errors=int(ctx.encode_mixed_errors()))
+    if args.device_leg_only:
+        return rec
+    # hop by hop on a twin: a short warm run, then the whole recording
+    twin = lyra_amd.LyraHip(device=0, max_streams=1, requant="xnnpack")
+    d_ids, d_bits, d_pb = torch.zeros(1, dtype=torch.int32, device=dev), torch.from_numpy(bits).to(dev), torch.from_numpy(pb).to(dev)
+    t_pk, t_nb, want = torch.zeros_like(d_pk), torch.zeros_like(d_nb), outputs()
+    base = {}
+    for n in (min(hops, 500), hops):
+        twin.reset()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for h in range(n):
+            twin.encode_mixed_dev(d_ids, d_pcm[h:h + 1], args.rate, d_bits[h:h + 1], t_pk[h:h + 1], t_nb[h:h + 1])
+        twin.synchronize()
+        t1 = time.perf_counter()
+        for h in range(n):
+            twin.decode_lossy_mixed_dev(d_ids, d_pk184[h:h + 1], d_pb[h:h + 1], args.rate, want[0][h:h + 1],
+                                        want[1][h:h + 1] if ext else None, want[2][h:h + 1], want[3][h:h + 1])
+        twin.synchronize()
+        base = dict(encode=t1 - t0, decode=time.perf_counter() - t1)
+    live = torch.arange(row, device=dev)[None, :] < d_nb[:, None]
+    same_enc = torch.equal(d_nb, t_nb) and torch.equal(d_nb.cpu(), torch.from_numpy((bits + 7) // 8)) and \
+        torch.equal(torch.where(live, d_pk, 0), torch.where(live, t_pk, 0))
+    same_dec = all(torch.equal(a, b) for a, b in zip(got, want) if a is not None)
+    rec.update(encode_hop_by_hop_s=round(base["encode"], 5), decode_hop_by_hop_s=round(base["decode"], 5),
+               encode_hop_by_hop_over_time_parallel=round(base["encode"] / t["encode"], 2),
+               decode_hop_by_hop_over_time_parallel=round(base["decode"] / t["decode"], 2),
+               verified=bool(same_enc and same_dec), verified_hops=hops)
+    return rec
+
+
 def device_leg(args, pcm):
     import torch
     import lyra_amd
@@ -353,10 +442,19 @@ def main():
     ap.add_argument("--rate", type=int, default=16000, choices=[8000, 16000, 32000, 48000])
     ap.add_argument("--dtx", action="store_true", help="LyraEncoder's DTX on a half-silent recording, encode only")
     ap.add_argument("--lossy", action="store_true", help="decode only: a Gilbert loss trace and a DTX trace, time-parallel against hop by hop")
+    ap.add_argument("--mixed", action="store_true", help="per-frame bitrates, switching every 50 hops: against the uniform span calls "
+                    "and the hop-by-hop mixed calls")
     ap.add_argument("--device-leg-only", action="store_true", help="the device leg alone, nothing recorded (the traced child)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "span_transcode.jsonl"))
     args = ap.parse_args()
     pcm = recording(args.hops, args.rate)
+    if args.mixed:
+        rec = mixed_device_leg(args, pcm)
+        print(json.dumps(rec), flush=True)
+        if not args.device_leg_only:
+            with open(args.out, "a") as f:
+                f.write(json.dumps(rec) + "\n")
+        return
     if args.lossy:
         recs = []
         for trace in ("gilbert", "dtx"):
