@@ -697,7 +697,8 @@ long lyra_hip_import_errors(lyra_hip_ctx* ctx, int clear);
  *   control words; everything after that is enqueued without synchronising.  lyra_hip_set_serial is supported.  The state is the
  *   hop-synchronous call's: the "do not mix" rules of lyra_hip_decode_lossy_dev hold, lyra_hip_decode_samples_dev keeps its own.
  *   Per-frame bitrates (set_bitrate between hops; a packet size per frame): lyra_hip_spans_mixed.h, which includes this header.
- * Out of scope: per-span sample rates, request sizes other than one hop on spans.
+ *   Per-span sample rates (recordings at 8, 16, 32 and 48 kHz in one call): lyra_hip_spans_rates.h, which includes that one.
+ * Out of scope: request sizes other than one hop on spans.
  * LYRA_HIP_SUBBATCHES > 1 is accepted (the calls are not split). */
 typedef struct lyra_hip_span { int32_t stream_id; int64_t first_frame; int64_t n_frames; } lyra_hip_span;
 /* warm-up hops of side LYRA_HIP_SIDE_ENCODER / LYRA_HIP_SIDE_DECODER (25 / 25); LYRA_HIP_EINVAL for any other side */

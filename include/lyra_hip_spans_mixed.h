@@ -32,7 +32,8 @@ extern "C" {
  *   The `_dev` forms allocate nothing beyond the side's grow-only scratch, and every refusal comes before the first kernel:
  *   LYRA_HIP_EINVAL with nothing enqueued and no state changed.  lyra_hip_encode_mixed_errors() reads 0 after any of them.
  *   The host-buffer forms stage frames 0 .. the last span's end, run, synchronise and write the spans' frames of the outputs.
- * Out of scope: per-span sample rates, request sizes other than one hop on spans. */
+ * Per-span sample rates: lyra_hip_spans_rates.h, which includes this header.
+ * Out of scope: request sizes other than one hop on spans. */
 
 /* LyraEncoder::Encode with set_bitrate between hops, over spans.  num_bits is a HOST array [frames]: a multiple of 4 in 4..184 for
  * EVERY frame of every span (frames outside spans are not read), else LYRA_HIP_EINVAL with nothing enqueued.  Bytes past

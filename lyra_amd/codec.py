@@ -241,9 +241,23 @@ def _signatures_spans_mixed():
 _SIGNATURES_SPANS_MIXED = _signatures_spans_mixed()
 
 
+def _signatures_spans_rates():
+    """The same for include/lyra_hip_spans_rates.h (tests/test_spans_rates_cpu.py holds each entry to its prototype)."""
+    vp, ci = C.c_void_p, C.c_int
+    spans = [vp, vp, ci, vp, ci]   # ctx, spans, n_spans, lane ids, n_lanes
+    table = {
+        "encode_spans_rates_dev": spans + [vp, vp, vp, vp, ci, vp, vp], "decode_spans_lossy_rates_dev": spans + [vp] * 7,
+        "decode_spans_rates_dev": spans + [vp, ci, vp, vp, vp],
+    }
+    return {"lyra_hip_" + name: (ci, args) for name, args in table.items()}
+
+
+_SIGNATURES_SPANS_RATES = _signatures_spans_rates()
+
+
 def _load(path=None):
     """The C-ABI library (default: library_path()); a second path loads a build variant beside it (lyra_amd/variants/).
-    A library that lacks a function of _SIGNATURES or _SIGNATURES_SPANS_MIXED is refused."""
+    A library that lacks a function of _SIGNATURES, _SIGNATURES_SPANS_MIXED or _SIGNATURES_SPANS_RATES is refused."""
     path = os.path.abspath(path or library_path())
     if path in _libs:
         return _libs[path]
@@ -263,7 +277,7 @@ def _load(path=None):
         except Exception:
             pass
     L = C.CDLL(path)
-    for name, (restype, argtypes) in (*_SIGNATURES.items(), *_SIGNATURES_SPANS_MIXED.items()):
+    for name, (restype, argtypes) in (*_SIGNATURES.items(), *_SIGNATURES_SPANS_MIXED.items(), *_SIGNATURES_SPANS_RATES.items()):
         fn = getattr(L, name, None)
         if fn is None:
             raise LyraHipError(f"{path} does not export {name}")
@@ -1000,6 +1014,58 @@ class LyraHip:
                        *self._p_noise_flags(d_is_noise, d_is_comfort_noise, F))
 
     spans_lossy_plan_mixed = staticmethod(spans_lossy_plan_mixed)
+
+    # -- per-span sample rates on spans (include/lyra_hip_spans_rates.h) ---------------------------------------------------------
+    @staticmethod
+    def _span_rates(sample_rates, n_spans):
+        rates = np.ascontiguousarray(np.asarray(sample_rates, np.int32).reshape(-1))
+        if rates.size != n_spans:
+            raise LyraHipError(f"spans: sample_rates has {rates.size} entries for {n_spans} spans")
+        return rates
+
+    def encode_spans_rates_dev(self, spans, d_pcm_ext, sample_rates, d_pcm16, num_bits, d_packets, d_packet_bytes, lane_ids=(),
+                               dtx=False):
+        """encode_spans_mixed_dev with a sample rate per span: bit for bit encode_rates_dev per hop.  sample_rates int32 [n_spans]
+        from 8000 / 16000 / 32000 / 48000 and num_bits int32 [frames] stay host arrays like spans and lane_ids.  d_pcm_ext int16
+        [frames][MAX_EXT_HOP], a frame of span s holds sample_rates[s] / 50 samples at the front of its row; d_pcm16 int16 [frames][320] (required: it receives the 16 kHz audio of every span frame),
+        d_packets uint8 [frames][23], d_packet_bytes int32 [frames].  Enqueues and does not synchronise, except with dtx, which
+        blocks the host once as encode_spans_dtx_dev does."""
+        F = d_pcm_ext.shape[0]
+        bits = self._span_packet_bytes(num_bits, F, "num_bits")
+        a, _held = self._span_args(spans, lane_ids, F)
+        rates = self._span_rates(sample_rates, a[1])
+        self._dev_call(self.L.lyra_hip_encode_spans_rates_dev, *a,
+                       self._dev_ptr(d_pcm_ext, "int16", (F, MAX_EXT_HOP), "external-rate pcm"), rates.ctypes.data,
+                       self._opt_dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"), bits.ctypes.data, int(bool(dtx)),
+                       self._p_packets(d_packets, F, MAX_PACKET_BYTES),
+                       self._opt_dev_ptr(d_packet_bytes, "int32", (F,), "packet_bytes"))
+
+    def decode_spans_lossy_rates_dev(self, spans, d_packets, packet_bytes, sample_rates, d_pcm16, d_pcm_ext, lane_ids=(),
+                                     d_is_noise=None, d_is_comfort_noise=None):
+        """decode_spans_lossy_mixed_dev with a sample rate per span: bit for bit decode_lossy_rates_dev per hop.  packet_bytes int32
+        [frames] in {0, 8, 15, 23} and sample_rates stay host arrays; d_packets uint8 [frames][23], d_pcm16 int16 [frames][320] and d_pcm_ext
+        int16 [frames][MAX_EXT_HOP] both required, d_is_noise / d_is_comfort_noise int32 [frames] optional.  Blocks the host
+        once, at its start."""
+        F = d_packets.shape[0]
+        pb = self._span_packet_bytes(packet_bytes, F)
+        a, _held = self._span_args(spans, lane_ids, F)
+        rates = self._span_rates(sample_rates, a[1])
+        self._dev_call(self.L.lyra_hip_decode_spans_lossy_rates_dev, *a, self._p_packets(d_packets, F, MAX_PACKET_BYTES),
+                       pb.ctypes.data, rates.ctypes.data, self._opt_dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"),
+                       self._opt_dev_ptr(d_pcm_ext, "int16", (F, MAX_EXT_HOP), "external-rate pcm"),
+                       *self._p_noise_flags(d_is_noise, d_is_comfort_noise, F))
+
+    def decode_spans_rates_dev(self, spans, d_packets, num_bits, sample_rates, d_pcm16, d_pcm_ext, lane_ids=()):
+        """decode_spans_dev with a sample rate per span (no loss, one num_bits): bit for bit decode_dev + resample_dev(side="decoder")
+        per hop.  d_packets uint8 [frames][bytes], d_pcm16 int16 [frames][320] and d_pcm_ext int16 [frames][MAX_EXT_HOP] both
+        required; a frame of span s gets sample_rates[s] / 50 samples at the front of its d_pcm_ext row.  Enqueues and does not
+        synchronise."""
+        F = d_packets.shape[0]
+        a, _held = self._span_args(spans, lane_ids, F)
+        rates = self._span_rates(sample_rates, a[1])
+        self._dev_call(self.L.lyra_hip_decode_spans_rates_dev, *a, self._p_packets(d_packets, F, packet_size(num_bits)), num_bits,
+                       rates.ctypes.data, self._opt_dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"),
+                       self._opt_dev_ptr(d_pcm_ext, "int16", (F, MAX_EXT_HOP), "external-rate pcm"))
 
     def noise_receive_dev(self, d_ids, d_pcm, d_is_noise, side="decoder"):
         """NoiseEstimator::ReceiveSamples on device buffers: pcm int16 [B][320] -> is_noise int32 [B]."""

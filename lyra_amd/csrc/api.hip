@@ -2073,3 +2073,4 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
 #include "spans_api.inc"
 #include "spans_lossy_api.inc"
 #include "spans_mixed_api.inc"
+#include "spans_rates_api.inc"

@@ -334,4 +334,19 @@ __global__ void span_gather_mixed_kernel(const SpanRow* rows, int B, int step, c
 __global__ void span_scatter_mixed_kernel(const SpanRow* rows, int B, int step, const uint8_t* dense, const int32_t* step_bits,
                                           uint8_t* frames, int32_t* packet_bytes, const long long* map);
 
+// ---- per-span sample rates on spans (spans_rates_kernels.hip; include/lyra_hip_spans_rates.h) ---------------------------------
+// The passes over every frame of a call with the rate looked up per row: SpanRsRow::pad[0] holds the span's rate (8000 / 16000 /
+// 32000 / 48000), and the estimator's kernels read it from rate_rows[i] for their row i (one row per span with frames in both).
+// span_resample_kernel with tab = the [2][3] designs of resample_rates_kernel; dir 0: in = external rate, rows in_stride apart
+// with rate / 50 samples each, out = 16 kHz; dir 1 the reverse.  A 16 kHz row is copied and touches no slot.  grid and block as
+// span_resample_kernel, LDS resample_rates_lds_bytes().
+__global__ void span_resample_rates_kernel(const ResampleP* tab, int dir, const SpanRsRow* rows, int n_rows, uint8_t* state,
+                                           const int16_t* in, int in_stride, int16_t* out, int out_stride);
+// span_logmel_kernel / span_noise_scan_kernel with P4 = the four rates' MelP, np_tab = the four rates' NoiseP
+__global__ void span_logmel_rates_kernel(const MelP* P4, const SpanDtxRow* rows, const SpanRsRow* rate_rows, int n_rows,
+                                         uint8_t* state, const int16_t* pcm, float* mel);
+__global__ void span_noise_scan_rates_kernel(const NoiseP* np_tab, const SpanDtxRow* rows, const SpanRsRow* rate_rows, int n_rows,
+                                             uint8_t* state, const float* mel, int32_t* flag_out, int v_noise, int v_active,
+                                             long long* map, int32_t* counts);
+
 }  // namespace lyra

@@ -16,6 +16,8 @@
 // only, so what it sees is again a stream whose state is convolution history.  lyra_hip_noise_spans[_dev] is the estimator alone.
 // Per-frame bitrates (spans_mixed_api.inc) ride the same steps: span_run_steps with a SpanMixed, encode_spans_planned_dev with
 // frame_bits.
+// Per-span sample rates (spans_rates_api.inc) ride the same bodies: a SpanExt that holds the caller's array of rates, and the
+// passes over every frame are the per-row kernels of spans_rates_kernels.hip.
 #include <type_traits>
 
 #include "spans_plan.h"
@@ -170,23 +172,28 @@ int span_batch_at(const SpanPlan& P, const SpanRow* rows, int step, int* own_run
 
 inline int span_grid(int B, int units) { return (int)(((long long)B * units + 255) / 256); }
 
-// The external-rate side of an `_ext` call: rate 16000 = none, the call is the plain one.
+// The external-rate side of an `_ext` call: ONE rate (16000 = none, the call is the plain one), or a rate per span
+// (spans_rates_api.inc): `rates` is the caller's HOST array [n_spans], `rate` is not read, rows of the external-rate buffer are
+// MAX_EXT_HOP samples apart whatever the span's rate, the 16 kHz buffer is always needed (a 16 kHz span is copied through), and
+// the passes over every frame are the kernels of spans_rates_kernels.hip.
 struct SpanExt {
   int rate = 16000;
   int16_t* d_pcm16 = nullptr;   // [frames][320], the caller's: resampled input (encode) / the steps' output (decode)
-  int n_ext() const { return rate / 50; }
-  bool on() const { return rate != 16000; }
+  const int32_t* rates = nullptr;
+  int n_ext() const { return rates ? (int)LYRA_HIP_MAX_EXT_HOP : rate / 50; }   // samples between rows of the external-rate buffer
+  bool on() const { return rates || rate != 16000; }
 };
 
 // Rows of the kernels that pass once over every frame of a call, one row per span with frames.  Row = SpanRsRow:
 // span_resample_kernel, four frames per workgroup; SpanDtxRow: span_logmel_kernel / span_noise_scan_kernel, two frames per
 // log-mel workgroup, region = the frames of the rows in front.  rows == nullptr only counts.  wgs < 0: too many for one launch.
+// rates (SpanRsRow, a rate per span): the row carries its span's rate, for the estimator's rows of the same index too.
 struct SpanPass {
   int n = 0;                      // rows
   long long wgs = 0, frames = 0;  // workgroups and frames of all rows
 };
 template <class Row>
-SpanPass span_pass_rows(const lyra_hip_span* spans, int n_spans, Row* rows) {
+SpanPass span_pass_rows(const lyra_hip_span* spans, int n_spans, Row* rows, const int32_t* rates = nullptr) {
   constexpr bool dtx = std::is_same<Row, SpanDtxRow>::value;
   SpanPass p;
   for (int s = 0; s < n_spans; ++s) {
@@ -194,6 +201,7 @@ SpanPass span_pass_rows(const lyra_hip_span* spans, int n_spans, Row* rows) {
     if (rows) {
       rows[p.n] = Row{spans[s].first_frame, spans[s].n_frames, spans[s].stream_id, (int32_t)p.wgs};
       if constexpr (dtx) rows[p.n].region = p.frames;
+      else rows[p.n].pad[0] = rates ? rates[s] : 0;
     }
     ++p.n;
     p.wgs += dtx ? (spans[s].n_frames + 1) / 2 : (spans[s].n_frames + 3) / 4;
@@ -206,18 +214,28 @@ SpanPass span_pass_rows(const lyra_hip_span* spans, int n_spans, Row* rows) {
   return p;
 }
 
-// one launch over every frame of every span: in [frames][n_in] -> out [frames][n_in * to / from] on st_ (slots: see
-// launch_resample -- behind run_steps' launches ahead on the quantizer stream / on the noise stream)
-int launch_span_resample(lyra_hip_ctx* c, bool enc, hipStream_t st_, const SpanRsRow* d_rows, int n_rows, long long wgs, int from,
-                         int to, const int16_t* d_in, int16_t* d_out) {
+// one launch over every frame of every span on st_: enc: d_in [frames][X.n_ext()] at the external rate -> d_out [frames][320];
+// else d_in [frames][320] -> d_out [frames][X.n_ext()] (slots: see launch_resample -- behind run_steps' launches ahead on the
+// quantizer stream / on the noise stream).  X.rates: the rows carry their rates and c->d_rs_tab is there (rates_ensure).
+int launch_span_resample(lyra_hip_ctx* c, bool enc, hipStream_t st_, const SpanRsRow* d_rows, int n_rows, long long wgs,
+                         const SpanExt& X, const int16_t* d_in, int16_t* d_out) {
+  const int from = enc ? X.rate : 16000, to = enc ? 16000 : X.rate;
   ResampleP P;
-  if (!resample_design(from, to, &P)) return fail(c, LYRA_HIP_EINVAL, "spans: unsupported resampling %d -> %d Hz", from, to);
+  if (!X.rates && !resample_design(from, to, &P))
+    return fail(c, LYRA_HIP_EINVAL, "spans: unsupported resampling %d -> %d Hz", from, to);
   int rc = 0;
   if (enc) {
     if ((rc = wait_ahead(c))) return rc;
   } else if (c->rs_sn_pending) {
     if ((rc = wait_noise_stream(c))) return rc;
     c->rs_sn_pending = false;
+  }
+  if (X.rates) {
+    hipLaunchKernelGGL(span_resample_rates_kernel, dim3((unsigned)wgs), dim3(256), resample_rates_lds_bytes(), st_,
+                       (const ResampleP*)c->d_rs_tab, enc ? 0 : 1, d_rows, n_rows, c->sm.base[enc ? st::R_RS_E : st::R_RS_D], d_in,
+                       enc ? X.n_ext() : 320, d_out, enc ? 320 : X.n_ext());
+    HIPCHK(c, hipGetLastError());
+    return 0;
   }
   const int n_in = from / 50, n_out = to / 50;
   hipLaunchKernelGGL(span_resample_kernel, dim3((unsigned)wgs), dim3(256), resample_lds_bytes(n_in), st_, P, d_rows, n_rows,
@@ -343,7 +361,7 @@ int span_upload_rows(lyra_hip_ctx* c, SpanSide& S, hipStream_t st_, int first, i
 int span_encode_front(lyra_hip_ctx* c, hipStream_t st_, const SpanExt& X, const SpanRsRow* d_rs_rows, const SpanPass& rs,
                       const int16_t** d_pcm) {
   if (!X.on()) return 0;
-  const int rc = rs.n ? launch_span_resample(c, true, st_, d_rs_rows, rs.n, rs.wgs, X.rate, 16000, *d_pcm, X.d_pcm16) : 0;
+  const int rc = rs.n ? launch_span_resample(c, true, st_, d_rs_rows, rs.n, rs.wgs, X, *d_pcm, X.d_pcm16) : 0;
   if (!rc) *d_pcm = X.d_pcm16;
   return rc;
 }
@@ -359,18 +377,23 @@ int span_check_head(lyra_hip_ctx* c, const char* what, int side, const int* num_
 }
 
 // The argument check of the `_dev` forms, before anything of the context is touched: span_check_head, the lane list, the
-// planner's rules on the spans as given (*P: that plan), d_pcm and d_other non-null once a span names a frame, d_pcm 16-byte
-// aligned, and at another rate the 16 kHz workspace.
+// planner's rules on the spans as given (*P: that plan), with a rate per span every span's rate, d_pcm and d_other non-null once
+// a span names a frame, d_pcm 16-byte aligned, and at another rate (always, with a rate per span) the 16 kHz workspace.
 int span_check(lyra_hip_ctx* c, const char* what, int side, const int* num_bits, const lyra_hip_span* spans, int n_spans,
                const int32_t* lane_ids, int n_lanes, const void* d_pcm, const void* d_other, const SpanExt& X, SpanPlan* P) {
   int rc = span_check_head(c, what, side, num_bits, X.rate);
   if (rc) return rc;
   if (n_lanes < 0 || (n_lanes && !lane_ids)) return fail(c, LYRA_HIP_EINVAL, "%s: bad lane list", what);
   if ((rc = span_plan_checked(c, side, spans, n_spans, lane_ids, n_lanes, P, what))) return rc;
+  for (int s = 0; X.rates && s < n_spans; ++s)
+    if (!span_rate_ok(X.rates[s]))
+      return fail(c, LYRA_HIP_EINVAL, "%s: sample_rates[%d] = %d Hz (8000 / 16000 / 32000 / 48000)", what, s, X.rates[s]);
   if (P->end_frame && (!d_pcm || !d_other)) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
   if (reinterpret_cast<uintptr_t>(d_pcm) & 15) return fail(c, LYRA_HIP_EINVAL, "%s: the PCM buffer must be 16-byte aligned", what);
-  if (X.on() && ((P->end_frame && !X.d_pcm16) || (reinterpret_cast<uintptr_t>(X.d_pcm16) & 15)))
+  if (X.on() && ((P->end_frame && !X.d_pcm16) || (reinterpret_cast<uintptr_t>(X.d_pcm16) & 15))) {
+    if (X.rates) return fail(c, LYRA_HIP_EINVAL, "%s: with a rate per span the 16 kHz buffer must be given, 16-byte aligned", what);
     return fail(c, LYRA_HIP_EINVAL, "%s: at %d Hz the 16 kHz buffer must be given, 16-byte aligned", what, X.rate);
+  }
   return 0;
 }
 
@@ -419,17 +442,18 @@ int span_staged(lyra_hip_ctx* c, const char* what, int side, const lyra_hip_span
 
 // ---- the plain and `_ext` calls ----------------------------------------------------------------------------------------------
 // side SIDE_ENC: d_src PCM [frames][320], d_dst packets [frames][nbytes]; SIDE_DEC the reverse.  X.on(): the PCM of d_src /
-// d_dst is [frames][X.n_ext()] and the steps work on X.d_pcm16.
+// d_dst is [frames][X.n_ext()] and the steps work on X.d_pcm16.  what: the call's name in error texts (null: that of the side).
 int spans_call_dev(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids, int n_lanes,
-                   const void* d_src, int num_bits, void* d_dst, const SpanExt& X = SpanExt()) {
+                   const void* d_src, int num_bits, void* d_dst, const SpanExt& X = SpanExt(), const char* what = nullptr) {
   const bool enc = side == sp::SIDE_ENC;
-  const char* what = enc ? "encode_spans" : "decode_spans";
+  if (!what) what = enc ? "encode_spans" : "decode_spans";
   SpanPlan P;
   int rc = span_check(c, what, side, &num_bits, spans, n_spans, lane_ids, n_lanes, enc ? d_src : d_dst, enc ? d_dst : d_src, X, &P);
   if (rc) return rc;
   const SpanPass rs = X.on() ? span_pass_rows<SpanRsRow>(spans, n_spans, nullptr) : SpanPass();
   if (rs.wgs < 0) return fail(c, LYRA_HIP_EINVAL, "%s: too many frames for one pass", what);
   DEVSCOPE(c);
+  if (X.rates && (rc = rates_ensure(c))) return rc;
   hipStream_t st_;
   SpanSide& S = span_side_open(c, side, &st_);
   const int rows = (int)P.chunks.size();
@@ -437,7 +461,7 @@ int spans_call_dev(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int n_
   if (rows && (rc = ensure_scratch(c, rows))) return rc;   // the stage kernels' own boundary buffers
   span_fill_rows(P, spans, lane_ids, n_lanes, S.h_rows);
   const int rs0 = rows + n_lanes;   // the resampler's rows lie behind the lanes' reset rows
-  if (rs.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(S.h_rows + rs0));
+  if (rs.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(S.h_rows + rs0), X.rates);
   if ((rc = span_side_begin(c, side))) return rc;
   if ((rc = span_upload_rows(c, S, st_, 0, rs0 + rs.n))) return rc;
   const SpanRsRow* d_rs_rows = reinterpret_cast<const SpanRsRow*>(S.d_rows + rs0);
@@ -452,7 +476,7 @@ int spans_call_dev(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int n_
   }
   rc = span_run_steps(c, enc, S, st_, P, S.h_rows, S.d_rows, S.d_rows + rows, n_lanes, d_src, num_bits, d_dst, nullptr);
   if (!rc && d_ext_out && rs.n)
-    rc = launch_span_resample(c, false, st_, d_rs_rows, rs.n, rs.wgs, 16000, X.rate, X.d_pcm16, (int16_t*)d_ext_out);
+    rc = launch_span_resample(c, false, st_, d_rs_rows, rs.n, rs.wgs, X, X.d_pcm16, (int16_t*)d_ext_out);
   return span_side_close(c, side, rc);
 }
 
@@ -500,9 +524,20 @@ int span_dtx_ensure(lyra_hip_ctx* c, SpanSide& S, hipStream_t st_, long long fra
 
 // NoiseEstimator::ReceiveSamples over every frame of the rows' spans on st_: the log-mel pass, then the scan.  side picks the
 // region, the filterbank and the constants as launch_noise does.  flag_out[frame] = v_noise / v_active.
+// d_rate_rows (a rate per span, encoder side): row i's filterbank and constants are those of d_rate_rows[i]'s rate.
 int launch_span_noise(lyra_hip_ctx* c, int side, hipStream_t st_, SpanSide& S, const SpanDtxRow* d_rows, int n_rows, long long wgs,
-                      const int16_t* d_pcm16, int32_t* d_flag_out, int v_noise, int v_active, long long* d_map) {
+                      const int16_t* d_pcm16, int32_t* d_flag_out, int v_noise, int v_active, long long* d_map,
+                      const SpanRsRow* d_rate_rows = nullptr) {
   uint8_t* region = c->sm.base[side == 0 ? st::R_NOISE_E : st::R_NOISE_D];
+  if (d_rate_rows) {
+    hipLaunchKernelGGL(span_logmel_rates_kernel, dim3((unsigned)wgs), dim3(256), logmel_lds_bytes(), st_, c->model.d_mel_rate[0],
+                       d_rows, d_rate_rows, n_rows, region, d_pcm16, S.d_mel);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(span_noise_scan_rates_kernel, dim3(n_rows), dim3(64), 0, st_, (const NoiseP*)c->d_noise_tab, d_rows,
+                       d_rate_rows, n_rows, region, (const float*)S.d_mel, d_flag_out, v_noise, v_active, d_map, S.d_counts);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
   const int rate = side == 0 ? c->enc_noise_rate : 16000;
   const MelP* melp = c->model.d_mel_rate[rate == 8000 ? 0 : rate == 32000 ? 2 : rate == 48000 ? 3 : 1];
   hipLaunchKernelGGL(span_logmel_kernel, dim3((unsigned)wgs), dim3(256), logmel_lds_bytes(), st_, melp, d_rows, n_rows, region,
@@ -521,12 +556,16 @@ int launch_span_noise(lyra_hip_ctx* c, int side, hipStream_t st_, SpanSide& S, c
 //   frame_bits  null: every frame at num_bits.  Else a HOST array [frames], a bit count per frame (num_bits is not read):
 //               judged for every span frame before anything is enqueued, uploaded by buffer frame with the rows, and
 //               d_packet_bytes is written by the scatter.
+//   span_rates  null: every span at sample_rate_hz.  Else a HOST array [n_spans], a rate per span (spans_rates_api.inc;
+//               sample_rate_hz is not read): d_pcm_ext rows are MAX_EXT_HOP apart, d_pcm16 is required, and with dtx each span's
+//               estimator is that of its own rate, whatever lyra_hip_set_encoder_sample_rate says.
 int span_lossy_ensure(lyra_hip_ctx* c, SpanSide& S, hipStream_t st_, size_t list_bytes, size_t snap_floats, int n_ctl);   // spans_lossy_api.inc
 int encode_spans_planned_dev(lyra_hip_ctx* c, const char* what, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids,
                              int n_lanes, const int16_t* d_pcm_ext, int sample_rate_hz, int16_t* d_pcm16, int num_bits,
-                             const int32_t* frame_bits, bool dtx, uint8_t* d_packets, int32_t* d_packet_bytes) {
-  const int rate = sample_rate_hz;
-  const SpanExt X{rate, rate != 16000 ? d_pcm16 : nullptr};
+                             const int32_t* frame_bits, bool dtx, uint8_t* d_packets, int32_t* d_packet_bytes,
+                             const int32_t* span_rates = nullptr) {
+  const int rate = span_rates ? 16000 : sample_rate_hz;
+  const SpanExt X{rate, span_rates || rate != 16000 ? d_pcm16 : nullptr, span_rates};
   SpanPlan dry;   // ids, lanes and frame ranges: the planner's rules, on the spans as given
   int rc = span_check(c, what, sp::SIDE_ENC, frame_bits ? nullptr : &num_bits, spans, n_spans, lane_ids, n_lanes, d_pcm_ext,
                       d_packets, X, &dry);
@@ -537,13 +576,14 @@ int encode_spans_planned_dev(lyra_hip_ctx* c, const char* what, const lyra_hip_s
       if (frame_bits[f] < 4 || frame_bits[f] > 184 || (frame_bits[f] & 3))
         return fail(c, LYRA_HIP_EINVAL, "%s: num_bits[%lld] = %d is not a multiple of 4 in 4..184", what, (long long)f,
                     frame_bits[f]);
-  if (dtx && c->enc_noise_rate != rate)   // as lyra_hip_encode_ext_dev: the DTX estimator is created at the encoder's external rate
+  if (dtx && !span_rates && c->enc_noise_rate != rate)   // as lyra_hip_encode_ext_dev: the DTX estimator is created at the encoder's external rate
     return fail(c, LYRA_HIP_EINVAL, "%s: DTX at %d Hz but the encoder-side noise estimator is set up for %d Hz "
                 "(call lyra_hip_set_encoder_sample_rate(%d) first)", what, rate, c->enc_noise_rate, rate);
   const SpanPass rs = X.on() ? span_pass_rows<SpanRsRow>(spans, n_spans, nullptr) : SpanPass();
   const SpanPass dx = dtx ? span_pass_rows<SpanDtxRow>(spans, n_spans, nullptr) : SpanPass();
   if (rs.wgs < 0 || dx.wgs < 0) return fail(c, LYRA_HIP_EINVAL, "%s: too many frames for one pass", what);
   DEVSCOPE(c);
+  if (span_rates && (rc = rates_ensure(c))) return rc;
   hipStream_t st_;
   SpanSide& S = span_side_open(c, sp::SIDE_ENC, &st_);
   // all scratch for the worst case -- every frame active: at most one chunk per span and per lane -- before the first launch
@@ -566,7 +606,7 @@ int encode_spans_planned_dev(lyra_hip_ctx* c, const char* what, const lyra_hip_s
   // upload 1, behind the batch rows' place: the lanes' reset rows, the resampler's rows, the estimator's rows
   SpanRow* h_fix = S.h_rows + rows_max;
   for (int l = 0; l < n_lanes; ++l) h_fix[l] = SpanRow{lane_ids[l], 0, 0, -1, 0, 0, 0};
-  if (rs.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(h_fix + n_lanes));
+  if (rs.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(h_fix + n_lanes), span_rates);
   if (dx.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanDtxRow*>(h_fix + n_lanes + rs.n));
   const SpanRow* d_fix = S.d_rows + rows_max;
   const SpanRsRow* d_rs_rows = reinterpret_cast<const SpanRsRow*>(d_fix + n_lanes);
@@ -585,7 +625,7 @@ int encode_spans_planned_dev(lyra_hip_ctx* c, const char* what, const lyra_hip_s
   if (dx.n) {
     // (per-frame bitrates: the scatter stores the size of every frame that has a packet)
     if ((rc = launch_span_noise(c, 0, st_, S, d_dx_rows, dx.n, dx.wgs, d_src16, d_packet_bytes, 0,
-                                frame_bits ? (int)MAX_PACKET_BYTES : (num_bits + 7) / 8, S.d_map)))
+                                frame_bits ? (int)MAX_PACKET_BYTES : (num_bits + 7) / 8, S.d_map, span_rates ? d_rs_rows : nullptr)))
       return rc;
     // the one host wait of the call: the plan depends on the decisions
     HIPCHK(c, hipStreamSynchronize(st_));

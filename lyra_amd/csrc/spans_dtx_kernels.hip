@@ -26,26 +26,11 @@ __device__ __forceinline__ void st16(void* p, i32x4 v) { *reinterpret_cast<i32x4
 //   later frames:      previous hop = the row in front of the frame.
 // Output per frame: the 160 log-mel bins and, beside them, Average() of the bins as noise_update_wave forms it (sequential
 // float sum from 0.f, then / 160.f): it does not depend on the estimator's state, so it is taken off the serial scan.
-__global__ __launch_bounds__(256) void span_logmel_kernel(const MelP* __restrict__ Pp, const SpanDtxRow* __restrict__ rows,
+__global__ __launch_bounds__(256) void span_logmel_kernel(const MelP* __restrict__ P1, const SpanDtxRow* __restrict__ rows,
                                                            int n_rows, uint8_t* __restrict__ state,
                                                            const int16_t* __restrict__ pcm, float* __restrict__ mel) {
-  int lo = 0, hi = n_rows - 1;   // the last row whose first workgroup is not behind this one
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (rows[mid].wg0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const SpanDtxRow row = rows[lo];
-  const long long f0 = ((long long)blockIdx.x - row.wg0) * 2;
-  if (f0 >= row.n_frames) return;   // (workgroup-uniform, before any barrier)
-  const bool two = f0 + 1 < row.n_frames, first = f0 == 0;
-  int16_t* slot_prev = reinterpret_cast<int16_t*>(state + (size_t)row.id * st::NOISE_BYTES + st::N_PREV);
-  const int16_t* cur0 = pcm + (size_t)(row.frame0 + f0) * 320;
-  const int16_t* cur1 = two ? cur0 + 320 : cur0;
-  const int16_t* prev0 = first ? slot_prev : cur0 - 320;
-  const int16_t* prev1 = two ? cur0 : prev0;
-  const int16_t* last = pcm + (size_t)(row.frame0 + row.n_frames - 1) * 320;
-  float* out = mel + (size_t)(row.region + f0) * SPAN_MEL_ROW;
-#include "span_logmel.inc"
+  auto mel_of_row = [&](int) { return P1; };   // one filterbank per call
+#include "span_logmel_rows.inc"
 }
 static_assert(st::N_PREV % 16 == 0 && st::NOISE_BYTES % 16 == 0 && SPAN_MEL_ROW % 4 == 0, "16-byte moves");
 
@@ -57,26 +42,8 @@ __global__ __launch_bounds__(64) void span_noise_scan_kernel(NoiseP P, const Spa
                                                               uint8_t* __restrict__ state, const float* __restrict__ mel,
                                                               int32_t* __restrict__ flag_out, int v_noise, int v_active,
                                                               long long* __restrict__ map, int32_t* __restrict__ counts) {
-  const int lane = threadIdx.x;
   if ((int)blockIdx.x >= n_rows) return;
-  const SpanDtxRow row = rows[blockIdx.x];
-  uint8_t* base = state + (size_t)row.id * st::NOISE_BYTES;
-  const float* m = mel + (size_t)row.region * SPAN_MEL_ROW;
-  const long long n = row.n_frames;
-  struct Extra {};
-  auto load_extra = [](long long, bool) { return Extra(); };
-  auto on_entry = [](const float (&)[3], int) {};
-  auto on_frame = [&](long long j, bool is_noise, long long active, const float (&)[3], Extra) {
-    if (lane == 0) {
-      const long long frame = row.frame0 + j;
-      flag_out[frame] = is_noise ? v_noise : v_active;
-      if (map && !is_noise) map[row.region + active] = frame;
-    }
-  };
-  auto on_exit = [&](long long active) {
-    if (lane == 0) counts[blockIdx.x] = (int32_t)active;
-  };
-#include "span_noise_scan.inc"
+#include "span_noise_scan_rows.inc"
 }
 
 }  // namespace lyra

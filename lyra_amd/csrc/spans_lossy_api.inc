@@ -85,13 +85,15 @@ int spans_lossy_plan_sized(const lyra_hip_span* spans, int n_spans, const int32_
 // lyra_hip_decode_spans_lossy_dev, and with `mixed` lyra_hip_decode_spans_lossy_mixed_dev (spans_mixed_api.inc): num_bits is not
 // read, a packet has any size of the codec (8 / 15 / 23, chosen per frame), packet rows are MAX_PACKET_BYTES apart, and the list
 // uploaded as gen_received holds every tick's size, from which the steps' gather hands it to rvq_decode_mixed_kernel row by row.
+// span_rates (spans_rates_api.inc): a HOST array [n_spans], a rate per span; sample_rate_hz is not read, d_pcm_ext rows are
+// MAX_EXT_HOP apart and required, and the output resampler is the per-row one.
 int decode_spans_lossy_sized_dev(lyra_hip_ctx* c, const char* what, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids,
                                  int n_lanes, const uint8_t* d_packets, const int32_t* packet_bytes, int num_bits, bool mixed,
                                  int sample_rate_hz, int16_t* d_pcm16, int16_t* d_pcm_ext, int32_t* d_is_noise,
-                                 int32_t* d_is_comfort_noise) {
-  const int rate = sample_rate_hz;
-  const bool ext = rate != 16000;
-  const SpanExt X{rate, ext ? d_pcm16 : nullptr};
+                                 int32_t* d_is_comfort_noise, const int32_t* span_rates = nullptr) {
+  const int rate = span_rates ? 16000 : sample_rate_hz;
+  const bool ext = span_rates || rate != 16000;
+  const SpanExt X{rate, ext ? d_pcm16 : nullptr, span_rates};
   SpanPlan dry;   // ids, lanes and frame ranges: the planner's rules, on the spans as given
   int rc = span_check(c, what, sp::SIDE_DEC, mixed ? nullptr : &num_bits, spans, n_spans, lane_ids, n_lanes,
                       ext ? d_pcm_ext : d_pcm16, d_packets, X, &dry);
@@ -111,6 +113,7 @@ int decode_spans_lossy_sized_dev(lyra_hip_ctx* c, const char* what, const lyra_h
   const SpanPass rs = ext ? span_pass_rows<SpanRsRow>(spans, n_spans, nullptr) : SpanPass();
   if (rs.wgs < 0 || total > INT32_MAX / 2) return fail(c, LYRA_HIP_EINVAL, "%s: too many frames for one pass", what);
   DEVSCOPE(c);
+  if (span_rates && (rc = rates_ensure(c))) return rc;
   hipStream_t st_;
   SpanSide& S = span_side_open(c, sp::SIDE_DEC, &st_);
   // the scratch whose size does not depend on the plan, before anything is enqueued: at most one chunk per span and per lane
@@ -173,7 +176,7 @@ int decode_spans_lossy_sized_dev(lyra_hip_ctx* c, const char* what, const lyra_h
     span_fill_rows(P, reinterpret_cast<const lyra_hip_span*>(compact.data()), lane_ids, 0, S.h_rows);
     SpanRow* h_fix = S.h_rows + rows_max;
     for (int l = 0; l < n_lanes; ++l) h_fix[l] = SpanRow{lane_ids[l], 0, 0, -1, 0, 0, 0};
-    if (rs.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(h_fix + n_lanes));
+    if (rs.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(h_fix + n_lanes), span_rates);
     SpanLossyRow* h_lrows = reinterpret_cast<SpanLossyRow*>(h_fix + n_lanes + rs.n);
     long long* h_gen = reinterpret_cast<long long*>(S.h_lists + o_gen);
     SpanLossyRx* h_rx = reinterpret_cast<SpanLossyRx*>(S.h_lists + o_rx);
@@ -250,7 +253,7 @@ int decode_spans_lossy_sized_dev(lyra_hip_ctx* c, const char* what, const lyra_h
                        d_frame, cng_region, (const int32_t*)d_entry, d_is_noise, d_is_comfort_noise);
     HIPCHK(c, hipGetLastError());
     // ---- 6: the output resampler ----
-    if (ext && rs.n) return launch_span_resample(c, false, st_, d_rs_rows, rs.n, rs.wgs, 16000, rate, d_pcm16, d_pcm_ext);
+    if (ext && rs.n) return launch_span_resample(c, false, st_, d_rs_rows, rs.n, rs.wgs, X, d_pcm16, d_pcm_ext);
     return 0;
   };
   rc = prepare();

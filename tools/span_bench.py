@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One long recording, encode then decode, time-parallel against hop by hop (BASELINE config #1: one file).
 
-   python tools/span_bench.py [--hops 180000] [--lanes 4096] [--bits 184] [--rate 16000] [--dtx | --lossy | --mixed]
+   python tools/span_bench.py [--hops 180000] [--lanes 4096] [--bits 184] [--rate 16000] [--dtx | --lossy | --mixed | --rates]
                               [--out profiles/span_transcode.jsonl]
 
 --rate 8000 / 32000 / 48000: the recording is at that rate and both legs run the `_ext` span calls and the file functions at it
@@ -31,6 +31,17 @@ audio, and lyra_hip_decode_spans_lossy_mixed_dev on the "gilbert" trace against 
 same trace (`*_over_uniform`: mixed time / uniform time); both also against the only other way to do the job, the hop-by-hop mixed
 calls lyra_hip_encode_mixed_dev / lyra_hip_decode_lossy_mixed_dev on a twin context (B = 1, every call enqueued without a wait,
 one synchronise at the end); `verified`: packets up to their size and sizes, and all four decoder outputs, of all hops equal.
+
+--rates: per-span sample rates (include/lyra_hip_spans_rates.h).  Four recordings of --hops hops each, at 8, 16, 32 and 48 kHz,
+with --lanes lanes.  One rates_transcode record with, for the encode, lossy-decode ("gilbert" trace) and plain-decode families,
+  (a) `*_s`               one rates call for all four recordings, the lanes shared;
+  (b) `*_split_s`         the same work as four uniform span calls, one per rate, the lanes given to each in turn
+                          (lyra_hip_encode_spans_mixed_dev, lyra_hip_decode_spans_lossy_mixed_dev, lyra_hip_decode_spans_ext_dev);
+  (c) `*_hop_by_hop_s`    the hop-by-hop rates calls on a twin context (B = 4, every call enqueued without a wait, one synchronise
+                          at the end; plain decode: lyra_hip_decode_dev and lyra_hip_resample_dev per rate);
+`verified`: every output of (a) equals that of (b) byte for byte; steps / steps_split: the step counts of (a) and (b) from
+lyra_hip_spans_plan (lossy: from lyra_hip_spans_lossy_plan_mixed).  kernel_share gives the part of span_resample_rates_kernel in
+the summed kernel time of one call of each family.
 
 Records, appended to --out:
   span_transcode   lyra_hip_encode_spans_dev + lyra_hip_decode_spans_dev on device buffers, one stream of --hops hops with
@@ -308,6 +319,158 @@ def mixed_device_leg(args, pcm):
     return rec
 
 
+RATES = (8000, 16000, 32000, 48000)
+
+
+def rates_device_leg(args):
+    import torch
+    import lyra_amd
+    from lyra_amd import codec
+    dev = torch.device("cuda", 0)
+    hops, row, EXT, nbytes = args.hops, codec.MAX_PACKET_BYTES, codec.MAX_EXT_HOP, codec.packet_size(args.bits)
+    F, n_streams = 4 * hops, 4 + args.lanes
+    ctx = lyra_amd.LyraHip(device=0, max_streams=n_streams, requant="xnnpack")
+    lanes = np.arange(4, n_streams, dtype=np.int32)
+    spans = [(k, k * hops, hops) for k in range(4)]
+    pcm = [recording(hops, r) for r in RATES]
+    ext = np.zeros((F, EXT), np.int16)
+    for k, x in enumerate(pcm):
+        ext[k * hops:(k + 1) * hops, :x.shape[1]] = x
+    bits = np.full(F, args.bits, np.int32)
+    rx = gilbert(F)
+    pb = np.where(rx, nbytes, 0).astype(np.int32)
+    z = lambda *shape, dtype=torch.int16: torch.zeros(shape, dtype=dtype, device=dev)
+    d_ext, d_p16, d_pk, d_nb = torch.from_numpy(ext).to(dev), z(F, 320), z(F, row, dtype=torch.uint8), z(F, dtype=torch.int32)
+    lossy = (z(F, 320), z(F, EXT), z(F, dtype=torch.int32), z(F, dtype=torch.int32))
+    plain = (z(F, 320), z(F, EXT))
+    d_pkn = z(F, nbytes, dtype=torch.uint8)   # the plain decode's rows are nbytes apart
+    one = {
+        "encode": lambda: ctx.encode_spans_rates_dev(spans, d_ext, RATES, d_p16, bits, d_pk, d_nb, lanes),
+        "lossy_decode": lambda: ctx.decode_spans_lossy_rates_dev(spans, d_pk, pb, RATES, lossy[0], lossy[1], lanes, d_is_noise=lossy[2],
+                                                                 d_is_comfort_noise=lossy[3]),
+        "plain_decode": lambda: ctx.decode_spans_rates_dev(spans, d_pkn, args.bits, RATES, plain[0], plain[1], lanes),
+    }
+
+    def timed(calls, reps):
+        times = {k: [] for k in calls}
+        for rep in range(reps + 1):   # rep 0 warms (allocations, code)
+            for name, call in calls.items():
+                ctx.reset()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                call()
+                ctx.synchronize()
+                if rep:
+                    times[name].append(time.perf_counter() - t0)
+                if name == "encode":
+                    d_pkn.copy_(d_pk[:, :nbytes])
+        return {k: float(np.median(v)) for k, v in times.items()}
+    t = timed(one, args.reps)
+    if args.device_leg_only:
+        return dict(kind="rates_transcode", hops=hops, lanes=int(args.lanes))
+    # (b) four uniform span calls on the same context, recording k as stream k, the lanes given to each in turn
+    span1 = lambda k: [(k, 0, hops)]
+    u_ext = [torch.from_numpy(x).to(dev) for x in pcm]
+    u_p16 = [z(hops, 320) for _ in RATES]
+    u_pk, u_nb = [z(hops, row, dtype=torch.uint8) for _ in RATES], [z(hops, dtype=torch.int32) for _ in RATES]
+    u_lossy = [(z(hops, 320), z(hops, r // 50), z(hops, dtype=torch.int32), z(hops, dtype=torch.int32)) for r in RATES]
+    u_plain = [(z(hops, 320), z(hops, r // 50)) for r in RATES]
+    u_pkn = [z(hops, nbytes, dtype=torch.uint8) for _ in RATES]
+    cut = lambda a, k: a[k * hops:(k + 1) * hops]
+
+    def split_encode():
+        for k, r in enumerate(RATES):
+            ctx.encode_spans_mixed_dev(span1(k), u_ext[k], cut(bits, k), u_pk[k], u_nb[k], lanes, sample_rate_hz=r,
+                                       d_pcm16=u_p16[k] if r != 16000 else None)
+
+    def split_lossy():
+        for k, r in enumerate(RATES):
+            o = u_lossy[k]
+            ctx.decode_spans_lossy_mixed_dev(span1(k), u_pk[k], cut(pb, k), o[0], lanes, sample_rate_hz=r,
+                                             d_pcm_ext=o[1] if r != 16000 else None, d_is_noise=o[2], d_is_comfort_noise=o[3])
+
+    def split_plain():
+        for k, r in enumerate(RATES):
+            o = u_plain[k]
+            ctx.decode_spans_dev(span1(k), u_pkn[k], args.bits, o[1] if r != 16000 else o[0], lanes, sample_rate_hz=r,
+                                 d_pcm16=o[0] if r != 16000 else None)
+    ts = {}
+    for name, call in (("encode", split_encode), ("lossy_decode", split_lossy), ("plain_decode", split_plain)):
+        times = []
+        for rep in range(args.reps + 1):
+            ctx.reset()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            call()
+            ctx.synchronize()
+            if rep:
+                times.append(time.perf_counter() - t0)
+        ts[name] = float(np.median(times))
+        if name == "encode":
+            for k in range(4):
+                u_pkn[k].copy_(u_pk[k][:, :nbytes])
+    same = True
+    for k, r in enumerate(RATES):
+        hop = r // 50
+        same = same and torch.equal(cut(d_nb, k), u_nb[k]) and torch.equal(cut(d_pk, k)[:, :nbytes], u_pk[k][:, :nbytes])
+        same = same and (r == 16000 or torch.equal(cut(d_p16, k), u_p16[k]))
+        same = same and torch.equal(cut(lossy[0], k), u_lossy[k][0]) and torch.equal(cut(lossy[2], k), u_lossy[k][2]) and \
+            torch.equal(cut(lossy[3], k), u_lossy[k][3]) and torch.equal(cut(plain[0], k), u_plain[k][0])
+        same = same and torch.equal(cut(lossy[1], k)[:, :hop], u_lossy[k][1] if r != 16000 else u_lossy[k][0])
+        same = same and torch.equal(cut(plain[1], k)[:, :hop], u_plain[k][1] if r != 16000 else u_plain[k][0])
+    # (c) hop by hop on a twin, B = 4
+    twin = lyra_amd.LyraHip(device=0, max_streams=4, requant="xnnpack")
+    d_ids, d_rates = torch.arange(4, dtype=torch.int32, device=dev), torch.tensor(RATES, dtype=torch.int32, device=dev)
+    h_ext = d_ext.view(4, hops, EXT).transpose(0, 1).contiguous()           # [hops][4][960]
+    h_bits = torch.full((4,), args.bits, dtype=torch.int32, device=dev)
+    h_pk, h_nb = z(hops, 4, row, dtype=torch.uint8), z(hops, 4, dtype=torch.int32)
+    h_pb = torch.from_numpy(pb).to(dev).view(4, hops).transpose(0, 1).contiguous()
+    h_out = (z(hops, 4, 320), z(hops, 4, EXT), z(hops, 4, dtype=torch.int32), z(hops, 4, dtype=torch.int32))
+    h_pkn, h_16 = z(hops, 4, nbytes, dtype=torch.uint8), z(hops, 4, 320)
+    h_rs = {r: z(hops, 1, r // 50) for r in RATES if r != 16000}
+    one_id = {r: torch.tensor([k], dtype=torch.int32, device=dev) for k, r in enumerate(RATES)}
+
+    def hbh_encode(n):
+        for h in range(n):
+            twin.encode_rates_dev(d_ids, h_ext[h], d_rates, h_bits, h_pk[h], h_nb[h])
+
+    def hbh_lossy(n):
+        for h in range(n):
+            twin.decode_lossy_rates_dev(d_ids, h_pk[h], h_pb[h], d_rates, h_out[0][h], h_out[1][h], h_out[2][h], h_out[3][h])
+
+    def hbh_plain(n):
+        for h in range(n):
+            twin.decode_dev(d_ids, h_pkn[h], args.bits, h_16[h])
+            for k, r in enumerate(RATES):
+                if r != 16000:
+                    twin.resample_dev(one_id[r], h_16[h, k:k + 1], 16000, r, h_rs[r][h], side="decoder")
+    tc = {}
+    for name, call in (("encode", hbh_encode), ("lossy_decode", hbh_lossy), ("plain_decode", hbh_plain)):
+        for n in (min(hops, 300), hops):   # a short warm run, then the whole recordings
+            twin.reset()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            call(n)
+            twin.synchronize()
+            tc[name] = time.perf_counter() - t0
+        if name == "encode":
+            h_pkn.copy_(h_pk[:, :, :nbytes])
+    same_hbh = torch.equal(h_pk.transpose(0, 1).reshape(F, row)[:, :nbytes], d_pk[:, :nbytes]) and \
+        torch.equal(h_out[0].transpose(0, 1).reshape(F, 320), lossy[0]) and torch.equal(h_16.transpose(0, 1).reshape(F, 320), plain[0])
+    _, steps = codec.spans_plan("encoder", spans, lanes, n_streams)
+    _, steps1 = codec.spans_plan("encoder", span1(0), lanes, n_streams)
+    lossy_steps = codec.spans_lossy_plan_mixed(spans, pb, [0] * 4, lanes, n_streams)["n_steps"]
+    lossy_split = sum(codec.spans_lossy_plan_mixed(span1(k), cut(pb, k), [0], lanes, n_streams)["n_steps"] for k in range(4))
+    rec = dict(kind="rates_transcode", hops=hops, recordings=4, lanes=int(args.lanes), bits=args.bits, reps=args.reps,
+               warmup=codec.span_warmup_frames("encoder"), steps=int(steps), steps_split=int(4 * steps1),
+               lossy_steps=int(lossy_steps), lossy_steps_split=int(lossy_split), received_hops=int(rx.sum()),
+               verified=bool(same), verified_hop_by_hop=bool(same_hbh))
+    for name in one:
+        rec.update({name + "_s": round(t[name], 5), name + "_split_s": round(ts[name], 5), name + "_hop_by_hop_s": round(tc[name], 5),
+                    name + "_split_over_one": round(ts[name] / t[name], 3), name + "_hop_by_hop_over_one": round(tc[name] / t[name], 2)})
+    return rec
+
+
 def device_leg(args, pcm):
     import torch
     import lyra_amd
@@ -399,6 +562,9 @@ def kernel_share_leg(args):
     import glob
     rec = dict(kind="kernel_share", rate=args.rate, hops=args.hops, lanes=int(args.lanes), bits=args.bits, dtx=bool(args.dtx))
     names = ["span_noise_scan_kernel", "span_logmel_kernel", "span_resample_kernel"] if args.dtx else ["span_resample_kernel"]
+    if args.rates:
+        rec = dict(kind="kernel_share", rates=True, hops=args.hops, lanes=int(args.lanes), bits=args.bits)
+        names = ["span_resample_rates_kernel"]
     if args.lossy:
         rec["lossy"] = True
         names = ["span_lossy_scan_kernel", "span_logmel_map_kernel", "span_cng_kernel", "span_resample_kernel"]
@@ -408,6 +574,7 @@ def kernel_share_leg(args):
                "--hops", str(args.hops), "--lanes", str(args.lanes), "--bits", str(args.bits), "--rate", str(args.rate)]
         cmd += ["--dtx"] if args.dtx else []
         cmd += ["--lossy"] if args.lossy else []
+        cmd += ["--rates"] if args.rates else []
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.file_timeout)
         stats = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
         if r.returncode != 0 or not stats:
@@ -444,9 +611,21 @@ def main():
     ap.add_argument("--lossy", action="store_true", help="decode only: a Gilbert loss trace and a DTX trace, time-parallel against hop by hop")
     ap.add_argument("--mixed", action="store_true", help="per-frame bitrates, switching every 50 hops: against the uniform span calls "
                     "and the hop-by-hop mixed calls")
+    ap.add_argument("--rates", action="store_true", help="per-span sample rates: four recordings at 8 / 16 / 32 / 48 kHz in one call "
+                    "against four uniform span calls and the hop-by-hop rates calls")
     ap.add_argument("--device-leg-only", action="store_true", help="the device leg alone, nothing recorded (the traced child)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "span_transcode.jsonl"))
     args = ap.parse_args()
+    if args.rates:
+        recs = [rates_device_leg(args)]
+        print(json.dumps(recs[0]), flush=True)
+        if not args.device_leg_only:
+            recs.append(kernel_share_leg(args))
+            print(json.dumps(recs[-1]), flush=True)
+            with open(args.out, "a") as f:
+                for r in recs:
+                    f.write(json.dumps(r) + "\n")
+        return
     pcm = recording(args.hops, args.rate)
     if args.mixed:
         rec = mixed_device_leg(args, pcm)
