@@ -255,9 +255,23 @@ def _signatures_spans_rates():
 _SIGNATURES_SPANS_RATES = _signatures_spans_rates()
 
 
+def _signatures_encode_streams():
+    """The same for include/lyra_hip_encode_streams.h (tests/test_encode_streams_cpu.py holds each entry to its prototype)."""
+    vp, ci, cl = C.c_void_p, C.c_int, C.c_long
+    table = {
+        "encode_streams_dev": [vp, vp, ci, vp, cl] + [vp] * 6, "encode_streams_begin": [vp, vp, ci] + [vp] * 4,
+        "encode_streams_end": [vp, vp, vp],
+    }
+    return {"lyra_hip_" + name: (ci, args) for name, args in table.items()}
+
+
+_SIGNATURES_ENCODE_STREAMS = _signatures_encode_streams()
+
+
 def _load(path=None):
     """The C-ABI library (default: library_path()); a second path loads a build variant beside it (lyra_amd/variants/).
-    A library that lacks a function of _SIGNATURES, _SIGNATURES_SPANS_MIXED or _SIGNATURES_SPANS_RATES is refused."""
+    A library that lacks a function of _SIGNATURES, _SIGNATURES_SPANS_MIXED, _SIGNATURES_SPANS_RATES or
+    _SIGNATURES_ENCODE_STREAMS is refused."""
     path = os.path.abspath(path or library_path())
     if path in _libs:
         return _libs[path]
@@ -277,7 +291,8 @@ def _load(path=None):
         except Exception:
             pass
     L = C.CDLL(path)
-    for name, (restype, argtypes) in (*_SIGNATURES.items(), *_SIGNATURES_SPANS_MIXED.items(), *_SIGNATURES_SPANS_RATES.items()):
+    for name, (restype, argtypes) in (*_SIGNATURES.items(), *_SIGNATURES_SPANS_MIXED.items(), *_SIGNATURES_SPANS_RATES.items(),
+                                       *_SIGNATURES_ENCODE_STREAMS.items()):
         fn = getattr(L, name, None)
         if fn is None:
             raise LyraHipError(f"{path} does not export {name}")
@@ -333,6 +348,7 @@ class LyraHip:
         self.sub_batches = sub_batches
         self._pending_encodes = []   # (B, num_bits) of the hops begun by encode_begin, oldest first
         self._pending_decodes = []   # B of the calls begun by decode_begin, oldest first
+        self._pending_stream_encodes = []   # B of the hops begun by encode_streams_begin, oldest first
 
     def _create(self, h, mode, model_dir, device, max_streams, weights_image):
         if weights_image is not None:   # bytes of a lyra_v1.lyrapack (lyra_hip_create_from_image)
@@ -458,6 +474,42 @@ class LyraHip:
         out = np.empty((B, packet_size(num_bits)), np.uint8)
         lens = np.empty(B, np.int32)
         self._chk(self.L.lyra_hip_encode_end(self.h, out.ctypes.data, lens.ctypes.data))
+        return out, lens
+
+    def encode_streams_begin(self, pcm, sample_rates, num_bits, dtx=None, stream_ids=None):
+        """Pipelined encode of streams that differ in sample rate, bitrate and DTX (lyra_hip_encode_streams_begin): pcm int16,
+        PACKED -- row b holds sample_rates[b] / 50 samples, rows back to back (a numpy array, or a CPU torch tensor, e.g. a
+        pinned one); sample_rates / num_bits int32 [B]; dtx [B] 0 / non-zero or None (no stream uses DTX).  Up to two hops in
+        flight; `pcm` may be reused at once."""
+        rates = _np(sample_rates, np.int32, (-1,))
+        B = rates.shape[0]
+        bits = _np(num_bits, np.int32, (B,))
+        flags = None if dtx is None else _np(np.asarray(dtx) != 0, np.int32, (B,))
+        ids = self._ids(stream_ids, B)
+        # (the library reads sum(rates / 50) samples once it has accepted every rate; a list it refuses is not sized here)
+        n = int(rates.sum()) // 50 if np.isin(rates, (8000, 16000, 32000, 48000)).all() else None
+        if hasattr(pcm, "data_ptr"):   # a CPU torch tensor is read in place
+            if pcm.is_cuda or str(pcm.dtype) != "torch.int16" or not pcm.is_contiguous() or n not in (None, pcm.numel()):
+                raise LyraHipError(f"pcm: expected a contiguous CPU int16 tensor of {n} samples")
+            p_pcm = pcm.data_ptr()
+        else:
+            pcm = _np(pcm, np.int16, (-1,))
+            if n not in (None, pcm.size):
+                raise LyraHipError(f"pcm: {pcm.size} samples, expected {n} (the sum of sample_rates / 50)")
+            p_pcm = pcm.ctypes.data
+        self._chk(self.L.lyra_hip_encode_streams_begin(self.h, ids.ctypes.data, B, p_pcm, rates.ctypes.data, bits.ctypes.data,
+                                                       None if flags is None else flags.ctypes.data))
+        self._pending_stream_encodes.append(B)
+
+    def encode_streams_end(self):
+        """-> (packets uint8 [B][MAX_PACKET_BYTES], zero behind each packet's bytes, packet_bytes int32 [B]) of the OLDEST
+        hop begun by encode_streams_begin."""
+        if not self._pending_stream_encodes:
+            self._chk(self.L.lyra_hip_encode_streams_end(self.h, None, None))
+        B = self._pending_stream_encodes.pop(0)
+        out = np.empty((B, MAX_PACKET_BYTES), np.uint8)
+        lens = np.empty(B, np.int32)
+        self._chk(self.L.lyra_hip_encode_streams_end(self.h, out.ctypes.data, lens.ctypes.data))
         return out, lens
 
     def decode_begin(self, packets, num_bits, stream_ids=None):
@@ -726,6 +778,26 @@ class LyraHip:
                        self._dev_ptr(d_pcm_ext, "int16", (B, MAX_EXT_HOP), "pcm"),
                        self._dev_ptr(d_sample_rates, "int32", (B,), "sample rates"),
                        self._dev_ptr(d_num_bits, "int32", (B,), "num_bits"), 1 if dtx else 0,
+                       self._p_packets(d_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_packet_bytes, B))
+
+    def encode_streams_dev(self, d_ids, d_pcm_ext, d_sample_rates, d_num_bits, d_packets, d_packet_bytes, d_dtx=None,
+                           d_pcm_offsets=None, n_pcm_samples=None):
+        """encode_rates_dev with DTX per stream and, optionally, packed audio rows (lyra_hip_encode_streams_dev): d_dtx int32
+        [B] (0: the stream's encoder has no noise estimator) or None (no stream uses DTX); d_pcm_ext int16, any shape: row b
+        holds d_sample_rates[b] / 50 samples at d_pcm_offsets[b] (int32 [B], multiples of 8 samples inside the buffer; None:
+        b * MAX_EXT_HOP); n_pcm_samples: how much of d_pcm_ext the rows may lie in (None: all of it).  A row with a bad offset
+        is treated as one with an invalid rate (rates_errors)."""
+        B = d_sample_rates.shape[0]
+        if n_pcm_samples is None:
+            n_pcm_samples = d_pcm_ext.numel()
+        elif n_pcm_samples > d_pcm_ext.numel():
+            raise LyraHipError(f"pcm: n_pcm_samples {n_pcm_samples} exceeds the tensor's {d_pcm_ext.numel()} samples")
+        self._dev_call(self.L.lyra_hip_encode_streams_dev, self._p_ids(d_ids, B), B,
+                       self._dev_ptr(d_pcm_ext, "int16", tuple(d_pcm_ext.shape), "pcm"), int(n_pcm_samples),
+                       self._opt_dev_ptr(d_pcm_offsets, "int32", (B,), "pcm offsets"),
+                       self._dev_ptr(d_sample_rates, "int32", (B,), "sample rates"),
+                       self._dev_ptr(d_num_bits, "int32", (B,), "num_bits"),
+                       self._opt_dev_ptr(d_dtx, "int32", (B,), "dtx flags"),
                        self._p_packets(d_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_packet_bytes, B))
 
     def decode_lossy_rates_dev(self, d_ids, d_packets, d_packet_bytes, d_sample_rates, d_pcm16, d_pcm_ext,

@@ -144,6 +144,8 @@ struct lyra_hip_ctx {
   unsigned* d_ds_err = nullptr;      // invalid packet sizes + packets that found the ring full
   long n_ds_calls = 0;
   void* ds_host = nullptr;           // DsHost: the two requests in flight of lyra_hip_decode_samples_begin / _end
+  void* es_host = nullptr;           // EsHost (encode_streams_api.inc): the two slots of lyra_hip_encode_streams_begin / _end
+  long es_begun = 0, es_ended = 0;   // ... and how many of its calls were begun / ended
   // lyra_hip_export_streams / lyra_hip_import_streams (stream_state_api.inc)
   unsigned* d_import_err = nullptr;  // blob rows lyra_hip_import_streams_dev refused
   uint8_t* d_blobs = nullptr;        // staging of the host forms, blob_cap rows
@@ -229,6 +231,7 @@ void lossy_free(lyra_hip_ctx* c);
 void ds_free(lyra_hip_ctx* c);
 void pipe_free(lyra_hip_ctx* c);
 void rates_free(lyra_hip_ctx* c);
+void es_free(lyra_hip_ctx* c);
 void blob_free(lyra_hip_ctx* c);
 void spans_free(lyra_hip_ctx* c);
 // One owner per device buffer.  Buffers that are sized by one count (the frames of a call, the streams of the context) are
@@ -810,11 +813,11 @@ int lossy_tick_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_
 // per-stream sample rates (rates_api.inc)
 int rates_ensure(lyra_hip_ctx* c);
 int launch_noise_rates(lyra_hip_ctx* c, hipStream_t st_, const int32_t* d_ids, const int32_t* d_rates, int B,
-                       const int16_t* d_pcm, int32_t* d_is_noise, int32_t* d_masked_ids);
+                       const int16_t* d_pcm, int32_t* d_is_noise, int32_t* d_masked_ids, const int32_t* d_dtx = nullptr);
 int launch_resample_rates(lyra_hip_ctx* c, int dir, const int32_t* d_ids, const int32_t* d_rates, int B, const int16_t* d_in,
                           int in_stride, int16_t* d_out, int out_stride, int32_t* d_ids_out, hipStream_t st_);
 int encode_rates_resample(lyra_hip_ctx* c, const int32_t* d_ids, const int32_t* d_rates, int B, const int16_t* d_pcm_ext,
-                          const int16_t** in, const int32_t** ids);
+                          const int16_t** in, const int32_t** ids, const int32_t* d_offsets = nullptr, long n_pcm = -1);
 int resample_rates_in_ahead(lyra_hip_ctx* c, const int32_t* d_ids, const int32_t* d_rates, int B, const int16_t* d_in, long step);
 int rates_uniform_bits(lyra_hip_ctx* c, int num_bits, const int32_t** bits);
 
@@ -823,9 +826,10 @@ int rates_uniform_bits(lyra_hip_ctx* c, int num_bits, const int32_t** bits);
 //   d_bits  null: every frame at num_bits (rvq_encode_kernel, packet rows num_bits / 8 rounded up apart); else each frame at
 //           d_bits[b] (mixed_api.inc: rvq_encode_mixed_kernel, packet rows LYRA_HIP_MAX_PACKET_BYTES apart);
 //   d_rates (rates_api.inc, with d_bits): the estimator runs with each row's own rate, and d_ids may hold -1 for rows that
-//           are absent from this hop (no state advances, packet_bytes 0).
+//           are absent from this hop (no state advances, packet_bytes 0);
+//   d_dtx   (encode_streams_api.inc, with dtx and d_rates): the estimator runs only on the rows whose flag is set.
 int encode16(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int16_t* d_pcm, bool dtx, int num_bits, const int32_t* d_bits,
-             const int32_t* d_rates, uint8_t* d_packets, int32_t* d_packet_bytes) {
+             const int32_t* d_rates, uint8_t* d_packets, int32_t* d_packet_bytes, const int32_t* d_dtx = nullptr) {
   DEVSCOPE(c);
   int rc = ensure_scratch(c, B);
   if (rc) return rc;
@@ -845,7 +849,7 @@ int encode16(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int16_t* d_pcm,
       // `live` travels with the features: both were last read by the quantizer(s) of the call before the previous one
       const EventList busy = encq_buffer_free(c, 0, 1);
       for (int i = 0; i < busy.n; ++i) HIPCHK(c, hipStreamWaitEvent(c->se[0], busy.e[i], 0));
-      rc = d_rates ? launch_noise_rates(c, c->se[0], d_ids, d_rates, B, d_pcm, c->d_flag_enc, live)
+      rc = d_rates ? launch_noise_rates(c, c->se[0], d_ids, d_rates, B, d_pcm, c->d_flag_enc, live, d_dtx)
                    : launch_noise(c, 0, c->se[0], d_ids, B, d_pcm, c->d_flag_enc, live);
       if (!rc) rc = launch_extract(c, 0, 0, live, B, d_pcm, feat);
     } else {
@@ -1088,6 +1092,7 @@ void lyra_hip_destroy(lyra_hip_ctx* c) {
   lossy_free(c);
   ds_free(c);
   pipe_free(c);
+  es_free(c);
   spans_free(c);
   if (c->h_zc) (void)hipHostFree(c->h_zc);
   c->h_zc = nullptr;
@@ -2068,6 +2073,7 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
 #include "lossy_api.inc"
 #include "mixed_api.inc"
 #include "rates_api.inc"
+#include "encode_streams_api.inc"
 #include "decode_samples_api.inc"
 #include "stream_state_api.inc"
 #include "spans_api.inc"

@@ -156,6 +156,11 @@ __global__ void logmel_rates_kernel(const MelP* P4, const int16_t* pcm, const in
                                     uint8_t* state, int stride, int prev_off, const NoiseP* np_tab, int32_t* is_noise_out,
                                     int32_t* masked_ids);
 size_t logmel_rates_lds_bytes();
+// the same with DTX per row (lyra_hip_encode_streams_dev): a row with dtx[i] == 0 does not touch its estimator slot, keeps its
+// id in masked_ids and is 0 in is_noise_out.  LDS logmel_rates_lds_bytes().
+__global__ void logmel_streams_kernel(const MelP* P4, const int16_t* pcm, const int32_t* ids, const int32_t* rates,
+                                      const int32_t* dtx, int B, uint8_t* state, int stride, int prev_off, const NoiseP* np_tab,
+                                      int32_t* is_noise_out, int32_t* masked_ids);
 __global__ void noise_update_kernel(NoiseP P, const int32_t* ids, int B, uint8_t* state, const float* mel,
                                     int32_t* is_noise_out, int32_t* masked_ids);
 // Resampler (lyra/resampler.cc): out/in = up/down, coef[phase][tap] oldest tap first (oracle lo_resampler_design)
@@ -172,6 +177,12 @@ __global__ void resample_rates_kernel(const ResampleP* tab, int dir, const int32
                                       uint8_t* state, const int16_t* in, int in_stride, int16_t* out, int out_stride,
                                       int32_t* ids_out, unsigned* err);
 size_t resample_rates_lds_bytes();
+// resample_rates_kernel, dir 0, with packed rows: row b at in + offsets[b] samples (offsets null: b * in_stride) inside a
+// buffer of n_in_total samples; a row with a bad offset or outside the buffer is treated as one with an invalid rate.
+// LDS resample_rates_lds_bytes().
+__global__ void resample_streams_kernel(const ResampleP* tab, const int32_t* rates, const int32_t* ids, int B, uint8_t* state,
+                                        const int16_t* in, const int32_t* offsets, int in_stride, long n_in_total, int16_t* out,
+                                        int out_stride, int32_t* ids_out, unsigned* err);
 // ---- device half of BatchLyraDecoder (host/lyra_batch_codec.cc): hop buffers stay on the device, the host keeps ints --
 // One slice of LyraDecoder::DecodeSamplesInternal's loop for one stream (lyra_decoder.cc:228-315): which samples of the
 // conditioned generative-model hop and of the comfort-noise hop go where, and how they are cross-faded

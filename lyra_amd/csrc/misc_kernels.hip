@@ -353,10 +353,13 @@ __device__ __forceinline__ int digit_reverse4_1024(int n) {   // reverse the fiv
 // kRates (logmel_rates_kernel): `Pp` is the array of the four rates' MelP (model.h d_mel_rate), `rates` holds one rate per
 // row and `np_tab` the four NoiseP; the two streams of a workgroup may differ in rate, so the mel weights (a second table
 // in LDS behind the FFT buffer), the band edges and the estimator's constants are selected per stream.
+// kRowDtx (logmel_streams_kernel, with kRates): `dtx` holds one flag per row; a row with dtx[b] == 0 takes the path of an
+// id -1 row (its estimator slot, the log-mel history included, is neither read nor written), except that masked_ids[b] is
+// its id and is_noise_out[b] is 0.
 __device__ __forceinline__ int mel_rate_index(int rate) { return rate == 8000 ? 0 : rate == 32000 ? 2 : rate == 48000 ? 3 : 1; }
 size_t logmel_rates_lds_bytes() { return (size_t)(1024 * 2 + 514) * 8; }
 
-template <bool kMasked, bool kRates = false>
+template <bool kMasked, bool kRates = false, bool kRowDtx = false>
 __device__ __forceinline__ void logmel_body(const MelP* __restrict__ Pp, const int16_t* __restrict__ pcm,
                                             const int32_t* __restrict__ ids, int B,
                                             uint8_t* __restrict__ state, int stride, int prev_off,
@@ -364,7 +367,8 @@ __device__ __forceinline__ void logmel_body(const MelP* __restrict__ Pp, const i
                                             int32_t* __restrict__ is_noise_out,
                                             int32_t* __restrict__ masked_ids,
                                             const int32_t* __restrict__ rates = nullptr,
-                                            const NoiseP* __restrict__ np_tab = nullptr) {
+                                            const NoiseP* __restrict__ np_tab = nullptr,
+                                            const int32_t* __restrict__ dtx = nullptr) {
   typedef double f64x2 __attribute__((ext_vector_type(2)));
   const MelP& P = Pp[kRates ? 1 : 0];   // (window and twiddles are the same tables at every rate)
   extern __shared__ __attribute__((aligned(16))) double dsm[];
@@ -382,7 +386,16 @@ __device__ __forceinline__ void logmel_body(const MelP* __restrict__ Pp, const i
     if constexpr (kRates) {   // the list the extractor and the quantizer run on names masked rows too
       if (masked_ids && tid < 2 && b0_ + tid < B && ids[b0_ + tid] < 0) masked_ids[b0_ + tid] = -1;
     }
-    const bool ok0 = ids[b0_] >= 0, ok1 = two_ && ids[b0_ + 1] >= 0;
+    bool ok0 = ids[b0_] >= 0, ok1 = two_ && ids[b0_ + 1] >= 0;
+    if constexpr (kRowDtx) {   // a row whose encoder has no estimator: its id passes through, it is never noise, and from
+      // here on it is an absent row -- decided before the first barrier, like the id -1 rows
+      if (tid < 2 && b0_ + tid < B && ids[b0_ + tid] >= 0 && dtx[b0_ + tid] == 0) {
+        if (masked_ids) masked_ids[b0_ + tid] = ids[b0_ + tid];
+        if (is_noise_out) is_noise_out[b0_ + tid] = 0;
+      }
+      ok0 = ok0 && dtx[b0_] != 0;
+      ok1 = ok1 && dtx[b0_ + 1] != 0;
+    }
     if (!ok0 && !ok1) return;   // (workgroup-uniform, before any barrier)
     if (!ok0) b0_ += 1;
     two_ = ok0 && ok1;
@@ -468,6 +481,21 @@ __global__ __launch_bounds__(256) void logmel_rates_kernel(const MelP* __restric
   LYRA_STRESS(7);
   logmel_body<true, true>(P4, pcm, ids, B, state, stride, prev_off, nullptr, 1, NoiseP{}, is_noise_out, masked_ids, rates,
                           np_tab);
+}
+
+// Encoders with and without DTX in one batch (lyra_hip_encode_streams_dev): logmel_rates_kernel with one flag per row.  The
+// reference creates no estimator for an encoder without DTX (lyra_encoder.cc:80): such a row's slot is not touched.
+__global__ __launch_bounds__(256) void logmel_streams_kernel(const MelP* __restrict__ P4, const int16_t* __restrict__ pcm,
+                                                              const int32_t* __restrict__ ids,
+                                                              const int32_t* __restrict__ rates,
+                                                              const int32_t* __restrict__ dtx, int B,
+                                                              uint8_t* __restrict__ state, int stride, int prev_off,
+                                                              const NoiseP* __restrict__ np_tab,
+                                                              int32_t* __restrict__ is_noise_out,
+                                                              int32_t* __restrict__ masked_ids) {
+  LYRA_STRESS(7);
+  logmel_body<true, true, true>(P4, pcm, ids, B, state, stride, prev_off, nullptr, 1, NoiseP{}, is_noise_out, masked_ids, rates,
+                                np_tab, dtx);
 }
 
 // =============================================================================================
@@ -724,6 +752,60 @@ __global__ __launch_bounds__(256) void resample_rates_kernel(const ResampleP* __
   if (lane < H) rsb[lane] = hist[lane];
   // the FIR reads what other lanes of this wavefront have just written to its LDS row: no workgroup barrier is possible
   // behind the early returns above and none is needed, but the order is pinned rather than assumed
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#include "resample_fir.inc"
+#include "resample_slot.inc"
+}
+
+// Packed rows (lyra_hip_encode_streams_dev): resample_rates_kernel, dir 0, with row b at in + offsets[b] (offsets == nullptr:
+// b * in_stride) inside a buffer of n_in_total samples.  A row whose offset is negative, no multiple of 8 samples (16 bytes)
+// or whose [offset, offset + rates[b] / 50) leaves the buffer is treated as a row with an invalid rate: nothing of it is
+// read, it writes nothing, is counted in *err and named -1 in ids_out.
+__global__ __launch_bounds__(256) void resample_streams_kernel(const ResampleP* __restrict__ tab,
+                                                                const int32_t* __restrict__ rates,
+                                                                const int32_t* __restrict__ ids, int B,
+                                                                uint8_t* __restrict__ state, const int16_t* __restrict__ in,
+                                                                const int32_t* __restrict__ offsets, int in_stride,
+                                                                long n_in_total, int16_t* __restrict__ out, int out_stride,
+                                                                int32_t* __restrict__ ids_out, unsigned* __restrict__ err) {
+  LYRA_STRESS(8);
+  extern __shared__ __attribute__((aligned(16))) float rsb_all[];   // [4][RS_TAPS - 1 + 960, padded to 4]
+  constexpr int H = st::RS_TAPS - 1;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const int b = blockIdx.x * 4 + w;
+  if (b >= B) return;
+  const int rate = __builtin_amdgcn_readfirstlane(rates[b]);
+  const int di = rate == 8000 ? 0 : rate == 32000 ? 1 : rate == 48000 ? 2 : -1;
+  const int id = ids[b];
+  const long off = offsets ? (long)__builtin_amdgcn_readfirstlane(offsets[b]) : (long)b * in_stride;
+  const int n_in = rate / 50;
+  const bool ok = (di >= 0 || rate == 16000) && off >= 0 && (off & 7) == 0 && off + n_in <= n_in_total;
+  int16_t* dst = out + (size_t)b * out_stride;
+  if (!ok) {   // (wave-uniform)
+    if (lane == 0) {
+      atomicAdd(err, 1u);
+      if (ids_out) ids_out[b] = -1;
+    }
+    return;
+  }
+  const int16_t* src = in + off;
+  if (ids_out && lane == 0) ids_out[b] = id;
+  if (di < 0) {   // 16 kHz: no resampler (lyra_encoder.cc:59)
+    for (int i = lane; i < 320; i += 64) dst[i] = src[i];
+    return;
+  }
+  const ResampleP& P = tab[di];
+  const int n_out = 320;
+  float* rsb = rsb_all + w * ((H + 960 + 3) & ~3);
+  const bool vec = (reinterpret_cast<uintptr_t>(in) & 15) == 0;   // (every offset and every n_in is a multiple of 8)
+#include "resample_load.inc"
+  uint8_t* slot = state + (size_t)id * st::RS_BYTES;
+  float* hist = reinterpret_cast<float*>(slot + st::RS_HIST);
+  const int in_pos = *reinterpret_cast<const int*>(slot + st::RS_IN_POS);
+  if (lane < H) rsb[lane] = hist[lane];
+  // (as in resample_rates_kernel: a wavefront reads only the LDS row it wrote)
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");

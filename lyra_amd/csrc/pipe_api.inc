@@ -133,6 +133,8 @@ int lyra_hip_encode_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const int1
   if ((rc = pipe_ensure(c))) return rc;
   PipeState* P = pipe_of(c);
   if (P->begun - P->ended >= 2) return fail(c, LYRA_HIP_EINVAL, "encode_begin: two calls are already in flight (lyra_hip_encode_end)");
+  if (c->es_begun != c->es_ended)   // (the two encode pipelines share the encode-side streams' order: one at a time)
+    return fail(c, LYRA_HIP_EINVAL, "encode_begin: a lyra_hip_encode_streams_begin call is in flight (lyra_hip_encode_streams_end)");
   PipeSlot& S = P->slot[P->begun & 1];
   if ((rc = pipe_slot_ensure(c, &S))) return rc;
   const int n_ext = sample_rate_hz / 50, nbytes = (num_bits + 7) / 8;

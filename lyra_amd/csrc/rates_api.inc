@@ -32,13 +32,20 @@ int rates_ensure(lyra_hip_ctx* c) {
   HIPCHK(c, hipMemcpy(c->d_noise_tab, np, sizeof np, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemset(c->d_rates_err, 0, 4));
   HIPCHK(c, set_lds(logmel_rates_kernel, logmel_rates_lds_bytes()));
+  HIPCHK(c, set_lds(logmel_streams_kernel, logmel_rates_lds_bytes()));
   return 0;
 }
 
-// launch_noise(side 0) with the rate per row; rows of id -1 are skipped
+// launch_noise(side 0) with the rate per row; rows of id -1 are skipped.  d_dtx (lyra_hip_encode_streams_dev): one flag per
+// row, rows without DTX pass through.
 int launch_noise_rates(lyra_hip_ctx* c, hipStream_t st_, const int32_t* d_ids, const int32_t* d_rates, int B,
-                       const int16_t* d_pcm, int32_t* d_is_noise, int32_t* d_masked_ids) {
+                       const int16_t* d_pcm, int32_t* d_is_noise, int32_t* d_masked_ids, const int32_t* d_dtx) {
   { ProfScope ps(c, K_NOISE, st_);
+    if (d_dtx)
+      hipLaunchKernelGGL(logmel_streams_kernel, dim3(cdiv(B, 2)), dim3(256), logmel_rates_lds_bytes(), st_, c->model.d_mel_rate[0],
+                         d_pcm, d_ids, d_rates, d_dtx, B, c->sm.base[st::R_NOISE_E], (int)st::NOISE_BYTES, (int)st::N_PREV,
+                         (const NoiseP*)c->d_noise_tab, d_is_noise, d_masked_ids);
+    else
     hipLaunchKernelGGL(logmel_rates_kernel, dim3(cdiv(B, 2)), dim3(256), logmel_rates_lds_bytes(), st_, c->model.d_mel_rate[0],
                        d_pcm, d_ids, d_rates, B, c->sm.base[st::R_NOISE_E], (int)st::NOISE_BYTES, (int)st::N_PREV,
                        (const NoiseP*)c->d_noise_tab, d_is_noise, d_masked_ids); }
@@ -57,9 +64,11 @@ int launch_resample_rates(lyra_hip_ctx* c, int dir, const int32_t* d_ids, const 
   return 0;
 }
 
-// encode_ext_resample with the rate per row: *in = the 16 kHz hops, *ids = the id list of the rows with a codec rate
+// encode_ext_resample with the rate per row: *in = the 16 kHz hops, *ids = the id list of the rows with a codec rate.
+// n_pcm >= 0 (lyra_hip_encode_streams_dev): d_pcm_ext holds n_pcm samples with row b at d_offsets[b] (null: b * 960), and a
+// row that leaves the buffer is named -1 too (resample_streams_kernel).
 int encode_rates_resample(lyra_hip_ctx* c, const int32_t* d_ids, const int32_t* d_rates, int B, const int16_t* d_pcm_ext,
-                          const int16_t** in, const int32_t** ids) {
+                          const int16_t** in, const int32_t** ids, const int32_t* d_offsets, long n_pcm) {
   DEVSCOPE(c);
   int rc = ensure_scratch(c, B);
   if (rc) return rc;
@@ -71,8 +80,16 @@ int encode_rates_resample(lyra_hip_ctx* c, const int32_t* d_ids, const int32_t* 
   int32_t* vids = c->d_rate_ids_call[c->n_encq_calls & 1];
   const EventList busy = encq_buffer_free(c, 0, 1);
   for (int i = 0; i < busy.n; ++i) HIPCHK(c, hipStreamWaitEvent(c->se[0], busy.e[i], 0));
-  if ((rc = launch_resample_rates(c, 0, d_ids, d_rates, B, d_pcm_ext, LYRA_HIP_MAX_EXT_HOP, c->d_rs16[0], 320, vids, c->se[0])))
+  if (n_pcm >= 0) {
+    { ProfScope ps(c, K_RESAMPLE, c->se[0]);
+      hipLaunchKernelGGL(resample_streams_kernel, dim3(cdiv(B, 4)), dim3(256), resample_rates_lds_bytes(), c->se[0],
+                         (const ResampleP*)c->d_rs_tab, d_rates, d_ids, B, c->sm.base[st::R_RS_E], d_pcm_ext, d_offsets,
+                         (int)LYRA_HIP_MAX_EXT_HOP, n_pcm, c->d_rs16[0], 320, vids, c->d_rates_err); }
+    HIPCHK(c, hipGetLastError());
+  } else if ((rc = launch_resample_rates(c, 0, d_ids, d_rates, B, d_pcm_ext, LYRA_HIP_MAX_EXT_HOP, c->d_rs16[0], 320, vids,
+                                         c->se[0]))) {
     return rc;
+  }
   if ((rc = se0_to_chunks(c))) return rc;
   *in = c->d_rs16[0];
   *ids = vids;
