@@ -268,10 +268,23 @@ def _signatures_encode_streams():
 _SIGNATURES_ENCODE_STREAMS = _signatures_encode_streams()
 
 
+def _signatures_decode_streams():
+    """The same for include/lyra_hip_decode_streams.h (tests/test_decode_streams_cpu.py holds each entry to its prototype)."""
+    vp, ci, cl = C.c_void_p, C.c_int, C.c_long
+    table = {
+        "decode_streams_dev": [vp, vp, ci, vp, vp, vp, vp, cl] + [vp] * 4, "decode_streams_begin": [vp, vp, ci] + [vp] * 3,
+        "decode_streams_end": [vp] * 4,
+    }
+    return {"lyra_hip_" + name: (ci, args) for name, args in table.items()}
+
+
+_SIGNATURES_DECODE_STREAMS = _signatures_decode_streams()
+
+
 def _load(path=None):
     """The C-ABI library (default: library_path()); a second path loads a build variant beside it (lyra_amd/variants/).
-    A library that lacks a function of _SIGNATURES, _SIGNATURES_SPANS_MIXED, _SIGNATURES_SPANS_RATES or
-    _SIGNATURES_ENCODE_STREAMS is refused."""
+    A library that lacks a function of _SIGNATURES, _SIGNATURES_SPANS_MIXED, _SIGNATURES_SPANS_RATES,
+    _SIGNATURES_ENCODE_STREAMS or _SIGNATURES_DECODE_STREAMS is refused."""
     path = os.path.abspath(path or library_path())
     if path in _libs:
         return _libs[path]
@@ -292,7 +305,7 @@ def _load(path=None):
             pass
     L = C.CDLL(path)
     for name, (restype, argtypes) in (*_SIGNATURES.items(), *_SIGNATURES_SPANS_MIXED.items(), *_SIGNATURES_SPANS_RATES.items(),
-                                       *_SIGNATURES_ENCODE_STREAMS.items()):
+                                       *_SIGNATURES_ENCODE_STREAMS.items(), *_SIGNATURES_DECODE_STREAMS.items()):
         fn = getattr(L, name, None)
         if fn is None:
             raise LyraHipError(f"{path} does not export {name}")
@@ -349,6 +362,7 @@ class LyraHip:
         self._pending_encodes = []   # (B, num_bits) of the hops begun by encode_begin, oldest first
         self._pending_decodes = []   # B of the calls begun by decode_begin, oldest first
         self._pending_stream_encodes = []   # B of the hops begun by encode_streams_begin, oldest first
+        self._pending_stream_decodes = []   # (B, packed samples) of the hops begun by decode_streams_begin, oldest first
 
     def _create(self, h, mode, model_dir, device, max_streams, weights_image):
         if weights_image is not None:   # bytes of a lyra_v1.lyrapack (lyra_hip_create_from_image)
@@ -511,6 +525,41 @@ class LyraHip:
         lens = np.empty(B, np.int32)
         self._chk(self.L.lyra_hip_encode_streams_end(self.h, out.ctypes.data, lens.ctypes.data))
         return out, lens
+
+    def decode_streams_begin(self, packets, packet_bytes, sample_rates, stream_ids=None):
+        """Pipelined hop of decoders that differ in sample rate and packet size (lyra_hip_decode_streams_begin): packets uint8
+        [B][MAX_PACKET_BYTES], packet_bytes int32 [B] (0 = no packet on this hop, else 8 / 15 / 23), sample_rates int32 [B];
+        numpy arrays or CPU torch tensors (e.g. pinned ones).  Up to two hops in flight; the arrays may be reused at once."""
+        def host(a, dtype, shape):   # a CPU torch tensor is read in place
+            if hasattr(a, "data_ptr"):
+                if a.is_cuda or not a.is_contiguous() or str(a.dtype) != "torch." + np.dtype(dtype).name:
+                    raise LyraHipError(f"expected a contiguous CPU {np.dtype(dtype).name} tensor")
+                if shape[0] >= 0 and tuple(a.shape) != tuple(shape):
+                    raise LyraHipError(f"shape {tuple(a.shape)}, expected {tuple(shape)}")
+                return a, a.data_ptr(), a.shape[0]
+            a = _np(a, dtype, shape)
+            return a, a.ctypes.data, a.shape[0]
+        rates, p_rates, B = host(sample_rates, np.int32, (-1,))
+        packets, p_packets, _ = host(packets, np.uint8, (B, MAX_PACKET_BYTES))
+        sizes, p_sizes, _ = host(packet_bytes, np.int32, (B,))
+        ids = self._ids(stream_ids, B)
+        total = int(np.asarray(rates).astype(np.int64).sum()) // 50   # (what end() sizes its array by: before the call)
+        self._chk(self.L.lyra_hip_decode_streams_begin(self.h, ids.ctypes.data, B, p_packets, p_sizes, p_rates))
+        self._pending_stream_decodes.append((B, total))
+
+    def decode_streams_end(self):
+        """-> (pcm int16, PACKED: row b holds sample_rates[b] / 50 samples, rows back to back in batch order; is_noise int32
+        [B]; is_comfort_noise int32 [B]) of the OLDEST hop begun by decode_streams_begin."""
+        if not self._pending_stream_decodes:
+            self._chk(self.L.lyra_hip_decode_streams_end(self.h, None, None, None))
+        B, total = self._pending_stream_decodes[0]
+        pcm = np.empty(total, np.int16)
+        noise = np.empty(B, np.int32)
+        cn = np.empty(B, np.int32)
+        rc = self.L.lyra_hip_decode_streams_end(self.h, pcm.ctypes.data, noise.ctypes.data, cn.ctypes.data)
+        self._pending_stream_decodes.pop(0)   # (the library gives the slot back whatever the wait returns)
+        self._chk(rc)
+        return pcm, noise, cn
 
     def decode_begin(self, packets, num_bits, stream_ids=None):
         """Pipelined form of decode(): starts a call and returns (up to two in flight); decode_end() -> pcm of the oldest."""
@@ -810,6 +859,26 @@ class LyraHip:
                        self._p_packets(d_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_packet_bytes, B),
                        self._dev_ptr(d_sample_rates, "int32", (B,), "sample rates"), self._p_pcm(d_pcm16, B),
                        self._dev_ptr(d_pcm_ext, "int16", (B, MAX_EXT_HOP), "external-rate pcm"),
+                       *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B))
+
+    def decode_streams_dev(self, d_ids, d_packets, d_packet_bytes, d_sample_rates, d_pcm, d_pcm_offsets=None, d_pcm16=None,
+                           d_is_noise=None, d_is_comfort_noise=None, n_pcm_samples=None):
+        """decode_lossy_rates_dev with, optionally, packed output rows and without the 16 kHz hop
+        (lyra_hip_decode_streams_dev): d_pcm int16, any shape: row b's d_sample_rates[b] / 50 samples go to d_pcm_offsets[b]
+        (int32 [B], multiples of 8 samples inside the buffer; None: b * MAX_EXT_HOP); n_pcm_samples: how much of d_pcm the
+        rows may lie in (None: all of it); d_pcm16 int16 [B][HOP] or None (library scratch).  A row with a bad offset is
+        treated as one with an invalid rate: nothing of d_pcm is written for it (rates_errors)."""
+        B = d_sample_rates.shape[0]
+        if n_pcm_samples is None:
+            n_pcm_samples = d_pcm.numel()
+        elif n_pcm_samples > d_pcm.numel():
+            raise LyraHipError(f"pcm: n_pcm_samples {n_pcm_samples} exceeds the tensor's {d_pcm.numel()} samples")
+        self._dev_call(self.L.lyra_hip_decode_streams_dev, self._p_ids(d_ids, B), B,
+                       self._p_packets(d_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_packet_bytes, B),
+                       self._dev_ptr(d_sample_rates, "int32", (B,), "sample rates"),
+                       self._dev_ptr(d_pcm, "int16", tuple(d_pcm.shape), "pcm"), int(n_pcm_samples),
+                       self._opt_dev_ptr(d_pcm_offsets, "int32", (B,), "pcm offsets"),
+                       self._opt_dev_ptr(d_pcm16, "int16", (B, HOP), "16 kHz pcm"),
                        *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B))
 
     def rates_errors(self, clear=False):

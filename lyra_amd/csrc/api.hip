@@ -146,6 +146,11 @@ struct lyra_hip_ctx {
   void* ds_host = nullptr;           // DsHost: the two requests in flight of lyra_hip_decode_samples_begin / _end
   void* es_host = nullptr;           // EsHost (encode_streams_api.inc): the two slots of lyra_hip_encode_streams_begin / _end
   long es_begun = 0, es_ended = 0;   // ... and how many of its calls were begun / ended
+  // lyra_hip_decode_streams_dev / _begin / _end (decode_streams_api.inc)
+  int16_t* d_dstr16[2] = {};         // [dstr16_cap][320] the 16 kHz hop of a call without d_pcm16, by lossy-call parity as d_lossy_gan
+  int dstr16_cap = 0;
+  void* dstr_host = nullptr;         // DstrHost: the two slots of lyra_hip_decode_streams_begin / _end
+  long dstr_begun = 0, dstr_ended = 0;   // ... and how many of its calls were begun / ended
   // lyra_hip_export_streams / lyra_hip_import_streams (stream_state_api.inc)
   unsigned* d_import_err = nullptr;  // blob rows lyra_hip_import_streams_dev refused
   uint8_t* d_blobs = nullptr;        // staging of the host forms, blob_cap rows
@@ -232,6 +237,7 @@ void ds_free(lyra_hip_ctx* c);
 void pipe_free(lyra_hip_ctx* c);
 void rates_free(lyra_hip_ctx* c);
 void es_free(lyra_hip_ctx* c);
+void dstr_free(lyra_hip_ctx* c);
 void blob_free(lyra_hip_ctx* c);
 void spans_free(lyra_hip_ctx* c);
 // One owner per device buffer.  Buffers that are sized by one count (the frames of a call, the streams of the context) are
@@ -809,7 +815,8 @@ int launch_noise(lyra_hip_ctx* c, int side, hipStream_t st_, const int32_t* d_id
 enum { LOSSY_UNIFORM, LOSSY_MIXED_BYTES, LOSSY_MIXED_BITS };
 int lossy_tick_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_packets, const int32_t* d_pkt_bytes,
                       const uint8_t* d_rx, int num_bits, int ext, int16_t* d_pcm16, int16_t* d_pcm_ext, int32_t* d_is_noise,
-                      int32_t* d_is_cn, int mixed = LOSSY_UNIFORM, const int32_t* d_rates = nullptr);   // lossy_api.inc
+                      int32_t* d_is_cn, int mixed = LOSSY_UNIFORM, const int32_t* d_rates = nullptr,
+                      const int32_t* d_offsets = nullptr, long n_pcm = -1);   // lossy_api.inc
 // per-stream sample rates (rates_api.inc)
 int rates_ensure(lyra_hip_ctx* c);
 int launch_noise_rates(lyra_hip_ctx* c, hipStream_t st_, const int32_t* d_ids, const int32_t* d_rates, int B,
@@ -1093,6 +1100,7 @@ void lyra_hip_destroy(lyra_hip_ctx* c) {
   ds_free(c);
   pipe_free(c);
   es_free(c);
+  dstr_free(c);
   spans_free(c);
   if (c->h_zc) (void)hipHostFree(c->h_zc);
   c->h_zc = nullptr;
@@ -2075,6 +2083,7 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
 #include "rates_api.inc"
 #include "encode_streams_api.inc"
 #include "decode_samples_api.inc"
+#include "decode_streams_api.inc"
 #include "stream_state_api.inc"
 #include "spans_api.inc"
 #include "spans_lossy_api.inc"

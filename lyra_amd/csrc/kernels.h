@@ -183,6 +183,13 @@ size_t resample_rates_lds_bytes();
 __global__ void resample_streams_kernel(const ResampleP* tab, const int32_t* rates, const int32_t* ids, int B, uint8_t* state,
                                         const int16_t* in, const int32_t* offsets, int in_stride, long n_in_total, int16_t* out,
                                         int out_stride, int32_t* ids_out, unsigned* err);
+// resample_rates_kernel, dir 1, with packed rows (lyra_hip_decode_streams_dev): row b's rates[b] / 50 samples go to
+// out + offsets[b] (offsets null: b * out_stride) inside a buffer of n_out_total samples; a row with a bad offset or outside
+// the buffer is treated as one with an invalid rate (nothing written, slot untouched, counted in *err).
+// LDS resample_rates_lds_bytes().
+__global__ void resample_streams_out_kernel(const ResampleP* tab, const int32_t* rates, const int32_t* ids, int B, uint8_t* state,
+                                            const int16_t* in, int in_stride, int16_t* out, const int32_t* offsets,
+                                            int out_stride, long n_out_total, unsigned* err);
 // ---- device half of BatchLyraDecoder (host/lyra_batch_codec.cc): hop buffers stay on the device, the host keeps ints --
 // One slice of LyraDecoder::DecodeSamplesInternal's loop for one stream (lyra_decoder.cc:228-315): which samples of the
 // conditioned generative-model hop and of the comfort-noise hop go where, and how they are cross-faded

@@ -63,7 +63,7 @@ int serial_noise_half_done(lyra_hip_ctx* c) {
 // One tick of B streams.  d_pkt_bytes / d_rx may be null (every packet whole / every row received).
 int lossy_tick_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_packets, const int32_t* d_pkt_bytes,
                       const uint8_t* d_rx, int num_bits, int ext, int16_t* d_pcm16, int16_t* d_pcm_ext, int32_t* d_is_noise,
-                      int32_t* d_is_cn, int mixed, const int32_t* d_rates) {
+                      int32_t* d_is_cn, int mixed, const int32_t* d_rates, const int32_t* d_offsets, long n_pcm) {
   DEVSCOPE(c);
   int rc = ensure_scratch(c, B);
   if (rc) return rc;
@@ -102,7 +102,15 @@ int lossy_tick_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_
                      (const uint8_t*)c->sm.base[st::R_NOISE_D], d_is_noise, d_is_cn);
   HIPCHK(c, hipGetLastError());
   if ((rc = launch_noise_masked(c, est_ids, B, gan, d_is_noise))) return rc;
-  if (d_rates) {   // per-stream rates (rates_api.inc): d_pcm_ext rows LYRA_HIP_MAX_EXT_HOP apart
+  if (d_rates && n_pcm >= 0) {   // per-stream rates, packed rows (decode_streams_api.inc): d_pcm_ext holds n_pcm samples with
+    // row b at d_offsets[b] (null: b * LYRA_HIP_MAX_EXT_HOP); a row that leaves the buffer writes nothing
+    { ProfScope ps(c, K_RESAMPLE, c->sn);
+      hipLaunchKernelGGL(resample_streams_out_kernel, dim3(cdiv(B, 4)), dim3(256), resample_rates_lds_bytes(), c->sn,
+                         (const ResampleP*)c->d_rs_tab, d_rates, d_ids, B, c->sm.base[st::R_RS_D], (const int16_t*)d_pcm16, 320,
+                         d_pcm_ext, d_offsets, (int)LYRA_HIP_MAX_EXT_HOP, n_pcm, c->d_rates_err); }
+    HIPCHK(c, hipGetLastError());
+    c->rs_sn_pending = true;
+  } else if (d_rates) {   // per-stream rates (rates_api.inc): d_pcm_ext rows LYRA_HIP_MAX_EXT_HOP apart
     if ((rc = launch_resample_rates(c, 1, d_ids, d_rates, B, d_pcm16, 320, d_pcm_ext, LYRA_HIP_MAX_EXT_HOP, nullptr, c->sn)))
       return rc;
     c->rs_sn_pending = true;

@@ -813,6 +813,57 @@ __global__ __launch_bounds__(256) void resample_streams_kernel(const ResampleP* 
 #include "resample_slot.inc"
 }
 
+// The decode-direction twin (lyra_hip_decode_streams_dev): resample_rates_kernel, dir 1, with row b's rates[b] / 50 samples
+// at out + offsets[b] (offsets == nullptr: b * out_stride) inside a buffer of n_out_total samples.  A row whose offset is
+// negative, no multiple of 8 samples or whose [offset, offset + rates[b] / 50) leaves the buffer is treated as a row with
+// an invalid rate: the test comes before anything of the row is read; the row writes nothing, its slot is neither read
+// nor written, and it is counted in *err.
+__global__ __launch_bounds__(256) void resample_streams_out_kernel(const ResampleP* __restrict__ tab,
+                                                                    const int32_t* __restrict__ rates,
+                                                                    const int32_t* __restrict__ ids, int B,
+                                                                    uint8_t* __restrict__ state, const int16_t* __restrict__ in,
+                                                                    int in_stride, int16_t* __restrict__ out,
+                                                                    const int32_t* __restrict__ offsets, int out_stride,
+                                                                    long n_out_total, unsigned* __restrict__ err) {
+  LYRA_STRESS(8);
+  extern __shared__ __attribute__((aligned(16))) float rsb_all[];   // [4][RS_TAPS - 1 + 960, padded to 4]
+  constexpr int H = st::RS_TAPS - 1;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const int b = blockIdx.x * 4 + w;
+  if (b >= B) return;
+  const int rate = __builtin_amdgcn_readfirstlane(rates[b]);
+  const int di = rate == 8000 ? 0 : rate == 32000 ? 1 : rate == 48000 ? 2 : -1;
+  const long off = offsets ? (long)__builtin_amdgcn_readfirstlane(offsets[b]) : (long)b * out_stride;
+  const int n_out = rate / 50;
+  const bool ok = (di >= 0 || rate == 16000) && off >= 0 && (off & 7) == 0 && off + n_out <= n_out_total;
+  if (!ok) {   // (wave-uniform)
+    if (lane == 0) atomicAdd(err, 1u);
+    return;
+  }
+  const int16_t* src = in + (size_t)b * in_stride;
+  int16_t* dst = out + off;
+  if (di < 0) {   // 16 kHz: no resampler (lyra_decoder.cc:129), the hop itself
+    for (int i = lane; i < 320; i += 64) dst[i] = src[i];
+    return;
+  }
+  const int id = ids[b];
+  const ResampleP& P = tab[3 + di];
+  const int n_in = 320;
+  float* rsb = rsb_all + w * ((H + 960 + 3) & ~3);
+  const bool vec = (in_stride & 7) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;   // (as resample_rates_kernel, dir 1)
+#include "resample_load.inc"
+  uint8_t* slot = state + (size_t)id * st::RS_BYTES;
+  float* hist = reinterpret_cast<float*>(slot + st::RS_HIST);
+  const int in_pos = *reinterpret_cast<const int*>(slot + st::RS_IN_POS);
+  if (lane < H) rsb[lane] = hist[lane];
+  // (as in resample_rates_kernel: a wavefront reads only the LDS row it wrote)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#include "resample_fir.inc"
+#include "resample_slot.inc"
+}
+
 // =============================================================================================
 // Device half of the batched LyraDecoder twin (host/lyra_batch_codec.cc).  The host runs the reference's per-stream
 // state machine on integers only; the conditioned hops of the generative model and of the comfort-noise generator live
