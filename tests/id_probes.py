@@ -52,7 +52,7 @@ def _call_order(probes, cap, rng):
     for t in range(n_tiles):
         while len(tiles[t]) < sizes[t]:
             tiles[t].append(rest.pop())
-    assert not rest
+    assert not rest, f"{len(rest)} probe ids fit in no tile"
     return [tiles[t][i] for t in range(n_tiles) for i in rng.permutation(len(tiles[t]))]
 
 
@@ -61,7 +61,7 @@ def probe_plan(stage_region_bytes, cap, seed=289262):
     the arena; the count is no multiple of TILE, so the last tile is ragged); `witnesses` ids next to the probes that no codec
     call may ever be given."""
     stage_region_bytes = [int(b) for b in stage_region_bytes]
-    assert len(stage_region_bytes) == N_STAGE_REGIONS and cap > 2 * OLD_EDGE
+    assert len(stage_region_bytes) == N_STAGE_REGIONS and cap > 2 * OLD_EDGE, (len(stage_region_bytes), "stage regions; cap", cap)
     rng = np.random.default_rng(seed)
     cross = crossings(stage_region_bytes, cap)
     ids = {0, 1, OLD_EDGE - 1, OLD_EDGE, cap - 2, cap - 1}

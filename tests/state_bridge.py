@@ -87,7 +87,7 @@ class Tensor:
         if q is not None:
             v = pack[q[0]]
             self.scale, self.zero = np.float32(v[q[1]]), int(v[q[1] + 1])
-            assert float(v[q[1] + 1]) == self.zero and -128 <= self.zero <= 127
+            assert float(v[q[1] + 1]) == self.zero and -128 <= self.zero <= 127, f"{self.name}: zero point {v[q[1] + 1]} is no int8 code"
 
     @property
     def side(self):
@@ -97,7 +97,7 @@ class Tensor:
 def read_pack(path=PACK):
     """name -> float32 array of every `.q` entry of the weight container (pack_format.h: 16-byte header, 96-byte entries)"""
     raw = open(path, "rb").read()
-    assert raw[:8] == b"LYRAPK01"
+    assert raw[:8] == b"LYRAPK01", f"{path}: begins with {raw[:8]!r}, not with the weight pack's magic"
     out = {}
     for i in range(struct.unpack_from("<I", raw, 8)[0]):
         off = 16 + 96 * i
@@ -113,6 +113,20 @@ def compile_tool(directory):
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I", CSRC,
                            os.path.join(ROOT, "tests", "stream_state", "blob_tool.cc"), "-o", exe])
     return exe
+
+
+def _verdicts(tool, tmp_path, blobs, mode=MODES["xnnpack"]):
+    """blob_tool's validate() verdict per blob"""
+    path = str(tmp_path / "blobs.bin")
+    np.ascontiguousarray(blobs, np.uint8).tofile(path)
+    return [int(x) for x in subprocess.check_output([tool, "validate", path, str(mode)]).split()]
+
+
+def _reset_blob(tool, tmp_path, mode=MODES["xnnpack"]):
+    """the blob of a freshly reset stream, as blob_tool writes it"""
+    path = str(tmp_path / "reset.bin")
+    subprocess.check_call([tool, "reset", path, str(mode)])
+    return np.fromfile(path, np.uint8)
 
 
 def at16(k):
@@ -226,7 +240,7 @@ class Bridge:
         `header_from` (a blob of the target, e.g. a reset export); the six stage regions and M_PREV are built from `state`,
         the phase words from the frame counts, padding zero."""
         blob = np.array(header_from, np.uint8).copy()
-        assert blob.shape == (self.bytes,)
+        assert blob.shape == (self.bytes,), f"a blob of shape {blob.shape}, not of {self.bytes} bytes"
         h = self.L["h"]["mode"]
         assert int(np.frombuffer(blob[h:h + 4].tobytes(), "<u4")[0]) == MODES[mode], "header_from is of another mode"
         blob[self.scope()] = 0
@@ -238,7 +252,7 @@ class Bridge:
             x = np.asarray(state[t.name]).reshape(t.R, t.C)
             stored = x.astype(np.float32) if t.dtype == "f32" else self.codes_of(t, x)
             if t.dtype == "f32":
-                assert np.array_equal(_bits(stored), _bits(x))
+                assert np.array_equal(_bits(stored), _bits(x)), f"{t.name}: float32 state changes when stored as float32"
             a, b = self.span(t)
             blob[a:b] = np.ascontiguousarray(self._rows_to_blob(t, stored, ph.get(t.region, 0))).view(np.uint8).ravel()
         return blob
@@ -246,7 +260,7 @@ class Bridge:
     def from_blob(self, blob):
         """a blob -> oracle state (dict as Stream.state(): flat arrays, float32, mel_prev float64)"""
         blob = np.ascontiguousarray(blob, np.uint8)
-        assert blob.shape == (self.bytes,)
+        assert blob.shape == (self.bytes,), f"a blob of shape {blob.shape}, not of {self.bytes} bytes"
         ph = self.phases(blob)
         np_t = {"f32": "<f4", "i8": np.int8, "i16": "<i2"}
         out = {}

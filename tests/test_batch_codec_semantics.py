@@ -4,12 +4,15 @@ straddles hops, packet-loss concealment, comfort noise, cross-fades.  The C++ tw
 (lyra_amd/decoder_demo); the expectation is oracle/lyra_codec_model.py, the per-stream restatement of the reference's
 classes over the CPU oracle.  Packets bit-exact; PCM bit-exact wherever only the generative model speaks, within 1 LSB
 where comfort noise is mixed in (device fp64 sin/cos/exp vs host libm, see test_resampler_cng.py), within 2 LSB at the
-other rates where such a sample lies in the output resampler's window (test_gpu_lossy_decode.py: Tally, CnReach)."""
+other rates where such a sample lies in the output resampler's window (tests/receiver_models.py: Tally, CnReach)."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
+
+from receiver_models import CnReach, Tally
+from sessions import _run_session
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
@@ -38,35 +41,11 @@ def test_reference_model_decoder_state_machine(oracle_default):
     assert not dec.is_comfort_noise()
 
 
-def _run_session(tmp_path, oracle, rate, bitrate, dtx, pcm, script, demo=None, pipelined=False):
-    import lyra_amd
-    if demo is None:
-        demo = os.path.join(ROOT, "lyra_amd", "decoder_demo")
-        assert os.path.exists(demo), "lyra_amd/decoder_demo not built (__graft_entry__.build())"
-    T, n, hop = pcm.shape
-    pin, sc = tmp_path / "in.s16", tmp_path / "script.txt"
-    pk, ln, pout = tmp_path / "pk.bin", tmp_path / "len.i32", tmp_path / "out.s16"
-    pcm.tofile(pin)
-    sc.write_text("\n".join(f"{mask} " + " ".join(map(str, sizes)) for mask, sizes in script) + "\n")
-    # pipelined: the session through EncodeAsync / WaitEncoded and DecodeSamplesAsync / WaitDecoded, two deep; "mixed": blocking
-    # and pipelined forms alternating tick by tick, switching only with nothing in flight (decoder_demo.cc)
-    env = dict(os.environ, LYRA_DEMO_PIPELINED={False: "0", True: "1", "mixed": "2"}[pipelined])
-    r = subprocess.run([demo, lyra_amd.default_model_dir(), str(sc), str(pin), str(rate), str(bitrate), str(int(dtx)),
-                        str(n), str(pk), str(ln), str(pout)], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
-    ps = {3200: 8, 6000: 15, 9200: 23}[bitrate]
-    packets = np.fromfile(pk, np.uint8).reshape(T, n, ps)
-    lengths = np.fromfile(ln, np.int32).reshape(T, n)
-    out = np.fromfile(pout, np.int16)
-    return packets, lengths, out
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("rate,bitrate,dtx", [(16000, 6000, False), (48000, 3200, False), (8000, 9200, False),
                                               (16000, 9200, True), (32000, 6000, True)])
 def test_batch_codec_session_vs_reference_model(tmp_path, golden_dir, oracle_default, rate, bitrate, dtx):
     from oracle import lyra_codec_model as M
-    from test_gpu_lossy_decode import CnReach, Tally
     from oracle import lyra_oracle
     bits = {3200: 64, 6000: 120, 9200: 184}[bitrate]
     speech = np.load(os.path.join(golden_dir, "sample_wavs.npz"))["sample1_16kHz"]

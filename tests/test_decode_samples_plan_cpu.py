@@ -18,6 +18,8 @@ import sys
 import numpy as np
 import pytest
 
+from signals import _gilbert_ticks
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 DEPTH = 4   # DS_FIFO_DEPTH; the driver prints the header's value and the test compares
 
@@ -58,14 +60,8 @@ int main(int argc, char** argv) {
 '''
 
 
-def _gilbert(rng, ticks, p_loss=None, p_recover=None):
-    p_loss = rng.uniform(0.02, 0.5) if p_loss is None else p_loss
-    p_recover = rng.uniform(0.1, 0.9) if p_recover is None else p_recover
-    lost, s = rng.random() < 0.3, []
-    for _ in range(ticks):
-        lost = (rng.random() >= p_recover) if lost else (rng.random() < p_loss)
-        s.append(not lost)
-    return s
+def _gilbert(rng, ticks):
+    return _gilbert_ticks(rng, ticks, recover_from=0.1).tolist()
 
 
 def _scripts(rng, rate):

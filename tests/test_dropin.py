@@ -21,6 +21,9 @@ import pytest
 
 from oracle import lyra_dropin as D
 
+from sessions import _session, lsd_per_hop
+from signals import _read_wav, _write_wav
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 pytestmark = pytest.mark.skipif(not D.available(), reason="oracle/_ref/liblyra_ref_hip.so not built (needs /root/reference)")
 
@@ -87,7 +90,6 @@ def test_gpu_reference_classes_on_hip_plugins_vs_oracle_backed_build(oracle_defa
     """lyra_integration_test.cc:49-149 with the HIP factories: the reference's LyraEncoder / LyraDecoder, created by their
     public Create(), over the first 150 hops of sample1_16kHz.wav."""
     from oracle import lyra_ref as R
-    from test_whole_file_known_answers import lsd_per_hop
     assert R.available()
     hops = _hops(golden_dir)[:150]
     enc = D.LyraEncoder(oracle_default, 16000, bitrate, False, model_dir)
@@ -137,10 +139,9 @@ def test_gpu_reference_decoder_concealment_on_hip_plugins(oracle_default, golden
 def test_gpu_reference_classes_on_hip_plugins_other_rates_and_dtx(oracle_default, golden_dir, model_dir, rate, bitrate, dtx):
     """The sample rates and the DTX mode of lyra_integration_test.cc:49-149 / lyra_encoder.cc:119-141: the reference's own
     resampling, noise decision and empty-packet logic around the HIP plugins (four scripted streams with loss, a silent
-    stretch and odd request sizes -- tests/test_reference_glue.py _session), against the oracle-backed build of the same
+    stretch and odd request sizes -- tests/sessions.py _session), against the oracle-backed build of the same
     sources, packet for packet and sample for sample."""
     from oracle import lyra_ref as R
-    from test_reference_glue import _session
     pcm, script = _session(golden_dir, rate, bitrate)
     n = pcm.shape[1]
     D.load(oracle_default).dropin_set_max_streams(64)
@@ -187,7 +188,6 @@ def test_gpu_reference_file_codec_on_hip_plugins(oracle_default, golden_dir, mod
     """EncodeFile / DecodeFile (cli_example/encoder_main_lib.cc:99-140, decoder_main_lib.cc:142-222 -- what encoder_main /
     decoder_main call; BASELINE config #1) on the HIP plugins vs the oracle-backed build: .lyra bytes and decoded wav."""
     from oracle import lyra_ref as R
-    from test_reference_glue import _read_wav, _write_wav
     pcm = np.load(os.path.join(golden_dir, "sample_wavs.npz"))["sample1_16kHz"]
     _write_wav(tmp_path / "in.wav", pcm)
     ref_dir = R.make_model_dir(tmp_path / "ref_model")

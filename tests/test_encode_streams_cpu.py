@@ -14,21 +14,15 @@ import pytest
 
 from lyra_amd import codec
 
+from abi_loading import _protos, load_library
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 NEW = {"lyra_hip_encode_streams_dev": 11, "lyra_hip_encode_streams_begin": 7, "lyra_hip_encode_streams_end": 3}
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.isfile(codec.library_path()):
-        codec.build_library()
-    return codec._load()
-
-
-def _protos(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(lyra_hip_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", hdr, flags=re.S)}
+    return load_library()
 
 
 def test_header_fourth_table_and_library_agree_on_the_three_symbols(lib):

@@ -7,6 +7,9 @@ import subprocess
 import numpy as np
 import pytest
 
+import signals
+from signals import _write_wav
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
@@ -96,20 +99,8 @@ def test_cpp_batch_codec_twins(oracle_default, golden_dir, tmp_path, bitrate):
     assert np.array_equal(out, ref["pcm"])
 
 
-def _write_wav(path, pcm, rate=16000):
-    import wave
-    with wave.open(str(path), "wb") as w:
-        w.setnchannels(1)
-        w.setsampwidth(2)
-        w.setframerate(rate)
-        w.writeframes(np.asarray(pcm, np.int16).tobytes())
-
-
 def _read_wav(path):
-    import wave
-    with wave.open(str(path), "rb") as w:
-        assert w.getnchannels() == 1 and w.getsampwidth() == 2 and w.getframerate() == 16000
-        return np.frombuffer(w.readframes(w.getnframes()), np.int16)
+    return signals._read_wav(path, 16000)
 
 
 @pytest.mark.gpu

@@ -6,111 +6,19 @@ is_noise, is_comfort_noise and the decoder-side noise estimate after every call;
 already exist where the regimes coincide (lyra_hip_decode_lossy_mixed_dev for n = one hop, lyra_hip_decode_dev when every
 packet arrives)."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(__file__))
-from test_gpu_lossy_decode import SEED, CnReach, Tally, _ctx, _patterns, _speech   # noqa: E402
+from gpu_plumbing import make_ctx
+from receiver_models import DEPTH, Device, Model, _model_packets as _packets
+from signals import _patterns, _speech
 
 pytestmark = pytest.mark.gpu
-BYTES = {64: 8, 120: 15, 184: 23}
-ROW = 23
-DEPTH = 4     # LYRA_HIP_DECODE_SAMPLES_FIFO
 
 
-def _packets(oracle, golden_dir, bits_per_stream, T, offset=0):
-    """-> [T][n][23] uint8 rows and [n] sizes: every stream encoded at its own bitrate by the reference model's encoder"""
-    from oracle import lyra_codec_model as M
-    n = len(bits_per_stream)
-    pcm = _speech(golden_dir, n, T, offset)
-    rows = np.zeros((T, n, ROW), np.uint8)
-    for s, bits in enumerate(bits_per_stream):
-        enc = M.RefLyraEncoder(oracle, 16000, bits, False)
-        for t in range(T):
-            p = enc.Encode(pcm[t, s])
-            rows[t, s, :p.size] = p
-    return rows, np.array([BYTES[b] for b in bits_per_stream], np.int32)
-
-
-class Device:
-    """decode_samples_dev call by call on alternating device buffers (the calls of a run are NOT synchronised one by one
-    unless the caller reads the result)."""
-
-    def __init__(self, ctx, ids, rate):
-        import torch
-        self.torch, self.ctx, self.rate = torch, ctx, rate
-        self.dev = torch.device("cuda", 0)
-        self.set_ids(ids)
-        self.k = 0
-
-    def set_ids(self, ids):
-        torch = self.torch
-        self.ids = np.asarray(ids, np.int32)
-        B = self.ids.size
-        self.d_ids = torch.from_numpy(self.ids.copy()).to(self.dev)
-        self.pk = [torch.zeros((B, ROW), dtype=torch.uint8, device=self.dev) for _ in range(2)]
-        self.nb = [torch.zeros(B, dtype=torch.int32, device=self.dev) for _ in range(2)]
-        self.isn = [torch.zeros(B, dtype=torch.int32, device=self.dev) for _ in range(2)]
-        self.icn = [torch.zeros(B, dtype=torch.int32, device=self.dev) for _ in range(2)]
-
-    def call(self, rows, nbytes, n, read=True):
-        torch, k = self.torch, self.k & 1
-        self.k += 1
-        B = self.ids.size
-        self.pk[k].copy_(torch.from_numpy(np.ascontiguousarray(rows, np.uint8)))
-        self.nb[k].copy_(torch.from_numpy(np.ascontiguousarray(nbytes, np.int32)))
-        out = torch.zeros((B, n), dtype=torch.int16, device=self.dev) if n else None
-        self.ctx.decode_samples_dev(self.d_ids, self.pk[k], self.nb[k], n, self.rate, out, self.isn[k], self.icn[k])
-        if not read:
-            return out
-        self.ctx.synchronize()
-        pcm = out.cpu().numpy() if n else np.zeros((B, 0), np.int16)
-        return pcm, self.isn[k].cpu().numpy().copy(), self.icn[k].cpu().numpy().copy()
-
-
-class Model:
-    """One RefLyraDecoder per stream id, with the bounded feature FIFO of the device call: a packet that finds DEPTH vectors
-    waiting is not delivered."""
-
-    def __init__(self, oracle, rate, ids):
-        from oracle import lyra_codec_model as M
-        self.M, self.oracle, self.rate = M, oracle, rate
-        self.decs, self.reach = {}, {}
-        for i in ids:
-            self.reset(int(i))
-        self.tally = Tally()
-        self.saw_cn = self.saw_mix = self.saw_back = self.saw_two = self.dropped = 0
-
-    def reset(self, i):
-        self.decs[i] = self.M.RefLyraDecoder(self.oracle, self.rate, cng_seed=SEED ^ i)
-        self.reach[i] = CnReach(self.rate)
-
-    def call(self, where, ids, rows, nbytes, n, got):
-        pcm, isn, icn = got
-        for r, i in enumerate(int(x) for x in ids):
-            dec = self.decs[i]
-            if nbytes[r] in (8, 15, 23):
-                if len(dec.model.q) - (1 if dec.model.next > 0 else 0) >= DEPTH:
-                    self.dropped += 1
-                else:
-                    dec.SetEncodedPacket(rows[r, :nbytes[r]])
-            was_cn = dec.is_comfort_noise()
-            want = dec.DecodeSamples(n)
-            assert dec.leftover.size == 0
-            self.tally.check(pcm[r], want, self.reach[i](dec, n), f"{where}, row {r} (id {i}), n {n}")
-            assert icn[r] == int(dec.is_comfort_noise()), (where, r)
-            assert isn[r] == int(dec.is_noise), f"{where}, row {r}: is_noise"
-            self.saw_cn += int(dec.is_comfort_noise())
-            self.saw_mix += int(any(g and c for g, c, _, _ in dec.last_segments))
-            self.saw_back += int(was_cn and not dec.is_comfort_noise())
-            self.saw_two += int(len(dec.last_segments) == 2)
-
-    def check_estimates(self, ctx, where, ids):
-        est = ctx.noise_estimate(np.asarray(ids, np.int32), side="decoder")
-        for r, i in enumerate(int(x) for x in ids):
-            assert np.allclose(est[r], self.decs[i].noise.noise_estimate(), rtol=1e-5, atol=1e-6), f"{where}, row {r}: estimate"
+def _ctx(max_streams=256):
+    return make_ctx(max_streams)
 
 
 def _ten_ms_calls(mask, phase):

@@ -3,10 +3,10 @@ lyra_hip_decode_streams_dev, its two-deep host form lyra_hip_decode_streams_begi
 MixedBatchLyraDecoder (through mixed_decoder_demo).  Expectation of the device calls: lyra_hip_decode_lossy_rates_dev on a
 twin context `u` with the same comfort-noise seed, fed the same packets -- the 16 kHz hop, each row's rate / 50 samples, both
 flags and every byte of the exported stream state.  Expectation of the class: oracle/lyra_codec_model.RefLyraDecoder per
-stream, under the criteria of tests/test_gpu_lossy_decode.py (Tally, CnReach).
+stream, under the criteria of tests/receiver_models.py (Tally, CnReach).
 
 Shapes.  The resampler and the mix serve 4 rows per workgroup, the estimator 2: B = 37 (10 workgroups, the last with one row)
-and B = 5.  Packets are random bytes with sizes from a bursty loss pattern (test_gpu_mixed_rate._packets); rows 0..11 -- three
+and B = 5.  Packets are random bytes with sizes from a bursty loss pattern (signals._random_packets); rows 0..11 -- three
 rows of every rate -- lose hops 2..13 and receive 23-byte packets on hops 14..23, the pattern of
 test_gpu_mixed_rate._decode_case, which takes every rate group into comfort noise and back: asserted on `u`'s flags."""
 import ctypes
@@ -17,12 +17,13 @@ import sys
 import numpy as np
 import pytest
 
+from gpu_plumbing import _dev, _ids, _t, make_ctx as _ctx
+from receiver_models import CnReach, Tally
+from row_cases import ROW, _decode_rates, _rates, _same_state
+from signals import RATES, _gilbert, _random_packets as _packets, _speech
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.abspath(os.path.join(HERE, ".."))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-
-from test_gpu_mixed_rate import RATES, ROW, _ctx, _decode_rates, _dev, _gilbert, _ids, _packets, _rates, _t  # noqa: E402
 
 FILL = 0x3333
 EINVAL = -1
@@ -82,13 +83,6 @@ def _cn_and_back(cn, rates):
     for r in np.unique(rates):
         g = cn[:, rates == r]
         assert (g == 1).any() and ((g[:-1] == 1) & (g[1:] == 0)).any(), (int(r), "the twin never left comfort noise")
-
-
-def _same_state(a, u, ids, where):
-    sa, su = a.export_streams(ids), u.export_streams(ids)
-    bad = np.flatnonzero((sa != su).any(axis=1))
-    assert bad.size == 0, (where, "exported state differs for rows", bad[:8],
-                           "first byte", int(np.flatnonzero(sa[bad[0]] != su[bad[0]])[0]) if bad.size else None)
 
 
 # ---- 1. the padded layout equals the rates call ---------------------------------------------------------------------------
@@ -439,7 +433,6 @@ def session_reference(golden_dir, oracle_default):
     and what RefLyraDecoder(rate, seed ^ stream) per stream plays: computed once.  -> (packets [T][n][23], lengths [T][n]
     as received, per stream the played samples [T][rate / 50], the comfort-noise reach of each, is_comfort_noise [T][n])."""
     from oracle import lyra_codec_model as M
-    from test_gpu_lossy_decode import CnReach, _speech
     n, T = N_STREAMS, T_SESSION
     pcm = _speech(golden_dir, n, T, offset=17)
     rng = np.random.default_rng(78)
@@ -500,7 +493,6 @@ def _run_demo(tmp_path, mode, packets, lengths):
 
 @pytest.mark.gpu
 def test_mixed_batch_decoder_equals_the_reference_model(tmp_path, session_reference):
-    from test_gpu_lossy_decode import Tally
     packets, lengths, want, cn_reach, is_cn = session_reference
     runs = [_run_demo(tmp_path, mode, packets, lengths) for mode in ("0", "1")]
     assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1]), "the two demo modes differ"

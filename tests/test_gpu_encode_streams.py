@@ -17,14 +17,15 @@ import subprocess
 import numpy as np
 import pytest
 
+from gpu_plumbing import _dev, _ids, _t, make_ctx
+from row_cases import ROW, SENTINEL, _check_sentinel_rows as _check_rows, _same_state
+from signals import RATES, _pcm_rows, _speech
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.abspath(os.path.join(HERE, ".."))
 
-RATES = (8000, 16000, 32000, 48000)
 BITS = (64, 120, 184)
-ROW = 960
 T_HOPS = 40
-SENTINEL = 0xA5
 EINVAL = -1
 BAD_RATE = 44100
 # Flagged hops that the oracle's NoiseEstimators call noise / not noise, per rate (8, 16, 32, 48 kHz), for B = 37, T = 40 and
@@ -35,48 +36,11 @@ BAD_RATE = 44100
 _COND_CPU = {"noise": (100, 81, 46, 71), "not_noise": (153, 187, 157, 197)}
 
 
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def _t(a, dtype=None):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a if dtype is None else np.asarray(a, dtype))).to(_dev())
-
-
 def _ctx(max_streams=64, **kw):
-    import lyra_amd
-    return lyra_amd.LyraHip(device=0, max_streams=max_streams, **kw)
+    return make_ctx(max_streams, **kw)
 
 
-def _ids(B, max_streams, seed):
-    return np.random.default_rng(seed).permutation(max_streams)[:B].astype(np.int32)
-
-
-def _speech(golden_dir, n, T, offset=0):
-    sp = np.load(os.path.join(golden_dir, "sample_wavs.npz"))["sample1_16kHz"].astype(np.int16)
-    out = np.empty((T, n, 320), np.int16)
-    for s in range(n):
-        start = (offset + 2357 * s) % (sp.size - T * 320)
-        out[:, s] = sp[start:start + T * 320].reshape(T, 320)
-    return out
-
-
-def _pcm_rows(golden_dir, B, T, rates, silent_every, seed, fill):
-    """[T][B][960] int16: row b holds rates[b] / 50 samples of speech at its rate (repeated / decimated 16 kHz samples:
-    any int16 input is a valid hop), `fill` behind them; every silent_every-th stream is silent from hop 5 on."""
-    pcm = _speech(golden_dir, B, T, offset=seed)
-    if silent_every:
-        pcm[5:, ::silent_every] = 0
-    out = np.full((T, B, ROW), fill, np.int16)
-    for b, r in enumerate(rates):
-        if r in RATES:
-            out[:, b, :r // 50] = np.repeat(pcm[:, b], r // 16000, axis=1) if r >= 16000 else pcm[:, b, ::2]
-    return out
-
-
-def _layout(B):
+def _row_layout(B):
     """-> (rates [B] with BAD_RATE for the absent rows, bits [B], fixed [B]: 1 / 0 = flag pinned on / off, -1 = redrawn)."""
     rates = np.array([RATES[(b // 3) % 4] for b in range(B)], np.int32)
     bits = np.array([BITS[(b + b // 16) % 3] for b in range(B)], np.int32)
@@ -129,27 +93,12 @@ def _uniform(u, ids, pcm_t, rates, bits, flags):
     return pk, pb
 
 
-def _check_rows(got_pk, got_pb, want_pk, want_pb, where):
-    assert np.array_equal(got_pb, want_pb), (where, got_pb, want_pb)
-    for b in range(got_pb.size):
-        n = int(got_pb[b])
-        assert np.array_equal(got_pk[b, :n], want_pk[b, :n]), (where, b)
-        assert (got_pk[b, n:] == SENTINEL).all(), (where, b, "bytes past packet_bytes were written")
-
-
-def _same_state(a, u, ids, where):
-    sa, su = a.export_streams(ids), u.export_streams(ids)
-    bad = np.flatnonzero((sa != su).any(axis=1))
-    assert bad.size == 0, (where, "exported state differs for rows", bad[:8],
-                           "first byte", int(np.flatnonzero(sa[bad[0]] != su[bad[0]])[0]) if bad.size else None)
-
-
 # ---- 1. per-row DTX equals the uniform calls -----------------------------------------------------------------------------
 
 def _per_row_case(golden_dir, B, sub_batches, serial):
     ms = 64
     ids = _ids(B, ms, B + 11)
-    rates, bits, fixed = _layout(B)
+    rates, bits, fixed = _row_layout(B)
     flags = _flags(B, T_HOPS, fixed, B)
     pcm_a = _pcm_rows(golden_dir, B, T_HOPS, rates, 3, B, 0x1111)
     pcm_u = _pcm_rows(golden_dir, B, T_HOPS, rates, 3, B, 0x2222)   # (a read past the row would differ)
@@ -352,7 +301,7 @@ def test_begin_end_equals_the_dev_call(golden_dir):
     import lyra_amd
     import torch
     B, T, ms = 37, 16, 64
-    rates, bits, fixed = _layout(B)
+    rates, bits, fixed = _row_layout(B)
     rates[[5, 6]] = (32000, 32000)   # (begin() refuses an invalid rate: every row is present here)
     flags = _flags(B, T, fixed, 2)
     # the id list changes between requests in flight; a stream's rate belongs to the stream, so ids move inside rate groups

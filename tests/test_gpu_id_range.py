@@ -34,22 +34,18 @@ one of them can still agree with its base stream and with the oracle's state.  M
 id 262,144 of R_E0 onto id 0 -- a probe of the same call with another signal -- and id 144,632 of R_D1 onto id 0 as well.
 
 Creation of a context is refused with LYRA_HIP_ENOMEM only when the card lacks the memory; only then do the tests skip."""
-import os
 import re
-import sys
 import time
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(__file__))
-import id_probes                                                                       # noqa: E402
-import state_bridge                                                                    # noqa: E402
-from test_gpu_lossy_decode import LossyModel, _full_batch_mask, _lossy_check, _speech   # noqa: E402
-from test_gpu_round3 import synth                                                      # noqa: E402
-from test_gpu_spans import _audio, _sequential                                          # noqa: E402
-from test_gpu_state_vs_oracle import (BITS, MODES, NBYTES, OracleSide, _compare_states, _device_hop, _inputs,  # noqa: E402
-                                      _same_rows)
+import id_probes
+from oracle_states import MODES, OracleSide, _compare_states, _device_hop, _inputs, _same_rows
+from receiver_models import LossyModel, _full_batch_mask, _lossy_check
+from signals import _audio_spans as _audio, _speech, synth
+from span_cases import _sequential
+import state_bridge
 
 pytestmark = pytest.mark.gpu
 ENOMEM = -5                  # LYRA_HIP_ENOMEM

@@ -10,47 +10,24 @@ import sys
 import numpy as np
 import pytest
 
+from gpu_plumbing import _dev, _ids, _same, _t, make_ctx as _ctx
+from receiver_models import LossyModel
+from row_cases import SENTINEL, _check_sentinel_rows as _check_rows, _draw_bits
+from signals import _gilbert, _patterns, _speech
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.abspath(os.path.join(HERE, ".."))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
 
 SIZES = (8, 15, 23)                       # the codec's packet sizes: 64 / 120 / 184 bits
-ENC_BITS = (64, 120, 184, 4, 100, 180)    # bit counts drawn per row: the three bitrates and other multiples of 4
-SENTINEL = 0xA5
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def _ctx(max_streams):
-    import lyra_amd
-    return lyra_amd.LyraHip(device=0, max_streams=max_streams)
-
-
-def _t(a, dtype=None):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a if dtype is None else np.asarray(a, dtype))).to(_dev())
-
-
-def _ids(B, max_streams, seed):
-    return np.random.default_rng(seed).permutation(max_streams)[:B].astype(np.int32)
 
 
 def _pcm(golden_dir, B, T, rate, silent_every=0, seed=0):
-    """[T][B][rate / 50] int16: speech (test_gpu_lossy_decode._speech), every silent_every-th stream silent from hop 5 on
+    """[T][B][rate / 50] int16: speech (signals._speech), every silent_every-th stream silent from hop 5 on
     (DTX), at other rates each sample repeated (any int16 input is a valid hop for the encoder's resampler)."""
-    from test_gpu_lossy_decode import _speech
     pcm = _speech(golden_dir, B, T, offset=seed)
     if silent_every:
         pcm[5:, ::silent_every] = 0
     return np.repeat(pcm, rate // 16000, axis=2) if rate > 16000 else pcm
-
-
-def _draw_bits(rng, B):
-    return rng.choice(ENC_BITS, size=B, p=[0.25, 0.25, 0.25, 0.08, 0.09, 0.08]).astype(np.int32)
 
 
 def _encode_uniform(ctx, d_ids, d_pcm, rate, bits, dtx):
@@ -74,14 +51,6 @@ def _encode_uniform(ctx, d_ids, d_pcm, rate, bits, dtx):
         pk[sel, :n] = d_pk.cpu().numpy()
         pb[sel] = d_pb.cpu().numpy() if dtx else n
     return pk, pb
-
-
-def _check_rows(got_pk, got_pb, want_pk, want_pb, where):
-    assert np.array_equal(got_pb, want_pb), (where, np.flatnonzero(got_pb != want_pb)[:8])
-    for b in range(got_pb.size):
-        n = int(got_pb[b])
-        assert np.array_equal(got_pk[b, :n], want_pk[b, :n]), (where, b)
-        assert (got_pk[b, n:] == SENTINEL).all(), (where, b, "bytes past packet_bytes were written")
 
 
 # ---- encoder -------------------------------------------------------------------------------------------------------------
@@ -158,18 +127,6 @@ def test_encode_mixed_vs_reference_model(golden_dir, oracle_default):
 
 # ---- decoder -------------------------------------------------------------------------------------------------------------
 
-def _gilbert(rng, T, B, p_loss=0.1, p_stay=0.75):
-    """[T][B] 0/1 received; bursty loss, and rows 0..15 lose ticks 4..15 (comfort noise, then the fade back)."""
-    m = np.ones((T, B), np.uint8)
-    lost = rng.random(B) < p_loss
-    for t in range(T):
-        lost = np.where(lost, rng.random(B) < p_stay, rng.random(B) < p_loss * (1 - p_stay) / (1 - p_loss))
-        m[t] = ~lost
-    m[4:16, :min(16, B)] = 0
-    m[20:27, 16:min(24, B)] = 0
-    return m
-
-
 def _mixed_run(ctx, ids, packets, sizes, rate, fill):
     """decode_lossy_mixed_dev per tick: packets [T][B][23] (bytes past sizes[t][b] set to `fill`) -> outputs per tick."""
     import torch
@@ -220,11 +177,6 @@ def _uniform_run(ctx, ids, packets, sizes, group, rate):
             icn[sel] = d[3].cpu().numpy()
         out.append((o16, oext, isn, icn))
     return out
-
-
-def _same(got, want, where):
-    for k, name in enumerate(("pcm16", "pcm_ext", "is_noise", "is_comfort_noise")):
-        assert np.array_equal(got[k], want[k]), (where, name, np.flatnonzero((got[k] != want[k]).reshape(len(got[k]), -1).any(1))[:8])
 
 
 @pytest.mark.gpu
@@ -282,7 +234,6 @@ def test_decode_mixed_vs_reference_model(golden_dir, oracle_default, rate):
     RefLyraDecoder with SetEncodedPacket(packet[:size]) on received ticks: generative samples exact, comfort-noise samples
     within 1 LSB, flags exact (LossyModel)."""
     from oracle import lyra_codec_model as M
-    from test_gpu_lossy_decode import LossyModel, _patterns
     B, T = 6, 36
     ids = [21, 4, 9, 50, 0, 33]
     pcm = _pcm(golden_dir, B, T, 16000, seed=rate)

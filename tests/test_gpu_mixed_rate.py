@@ -10,34 +10,13 @@ import sys
 import numpy as np
 import pytest
 
+from gpu_plumbing import _dev, _ids, _t, make_ctx as _ctx
+from receiver_models import LossyModel
+from row_cases import ROW, SENTINEL, _check_sentinel_rows as _check_rows, _decode_rates, _draw_bits, _rates
+from signals import RATES, _gilbert, _pcm_rows, _random_packets as _packets
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.abspath(os.path.join(HERE, ".."))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-
-from test_gpu_mixed_bitrate import SENTINEL, _check_rows, _ctx, _dev, _draw_bits, _gilbert, _ids, _t  # noqa: E402
-
-RATES = (8000, 16000, 32000, 48000)
-ROW = 960
-
-
-def _rates(B):
-    """Fixed per stream; with every third stream silent (DTX input) every rate has silent and speaking streams from B = 12."""
-    return np.array([RATES[(b // 3) % 4] for b in range(B)], np.int32)
-
-
-def _pcm_rows(golden_dir, B, T, rates, silent_every, seed, fill):
-    """[T][B][960] int16: row b holds rates[b] / 50 samples of speech at its rate (repeated / decimated 16 kHz samples:
-    any int16 input is a valid hop), `fill` behind them."""
-    from test_gpu_lossy_decode import _speech
-    pcm = _speech(golden_dir, B, T, offset=seed)
-    if silent_every:
-        pcm[5:, ::silent_every] = 0
-    out = np.full((T, B, ROW), fill, np.int16)
-    for b, r in enumerate(rates):
-        if r in RATES:
-            out[:, b, :r // 50] = np.repeat(pcm[:, b], r // 16000, axis=1) if r >= 16000 else pcm[:, b, ::2]
-    return out
 
 
 def _encode_uniform(u, ids, pcm_t, rates, bits, dtx):
@@ -131,20 +110,6 @@ def _decode_uniform(u, ids, pk_t, sz_t, rates):
     return out16, ext, noise, cn
 
 
-def _decode_rates(a, ids, pk_t, sz_t, rates, dn=None):
-    """-> (pcm16, ext rows, is_noise, is_comfort_noise); dn: a persistent is_noise buffer (default: a fresh one of -3)."""
-    import torch
-    B = ids.size
-    d16 = torch.zeros((B, 320), dtype=torch.int16, device=_dev())
-    dx = torch.full((B, ROW), 0x3333, dtype=torch.int16, device=_dev())
-    if dn is None:
-        dn = torch.full((B,), -3, dtype=torch.int32, device=_dev())
-    dc = torch.full((B,), -3, dtype=torch.int32, device=_dev())
-    a.decode_lossy_rates_dev(_t(ids), _t(pk_t), _t(sz_t), _t(rates), d16, dx, dn, dc)
-    a.synchronize()
-    return d16.cpu().numpy(), dx.cpu().numpy(), dn.cpu().numpy(), dc.cpu().numpy()
-
-
 def _check_decode(got, want, rates, where):
     g16, gx, gn, gc = got
     w16, wx, wn, wc = want
@@ -158,13 +123,6 @@ def _check_decode(got, want, rates, where):
             assert np.array_equal(gx[b, :320], g16[b]), (where, b)
     # is_noise is left alone on ticks without a packet: both calls start from -3 there
     assert np.array_equal(gn, wn), where
-
-
-def _packets(rng, T, B):
-    """[T][B][23] random packets, sizes 0 / 8 / 15 / 23 from a bursty loss pattern; streams 0..15 lose ticks 4..15."""
-    rx = _gilbert(rng, T, B)
-    sizes = rng.choice((8, 15, 23), size=(T, B)).astype(np.int32) * rx
-    return rng.integers(0, 256, size=(T, B, 23)).astype(np.uint8), sizes
 
 
 def _decode_case(B, serial):
@@ -260,7 +218,6 @@ def test_against_the_reference_model(golden_dir, oracle_default):
     against RefLyraEncoder created at each stream's rate; the decoder under test_gpu_lossy_decode.LossyModel's criteria."""
     import torch
     from oracle import lyra_codec_model as M
-    from test_gpu_lossy_decode import LossyModel
     B, T = 16, 60
     ids = _ids(B, 64, 13)
     rates = np.repeat(np.array(RATES, np.int32), 4)

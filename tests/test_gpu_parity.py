@@ -14,6 +14,9 @@ import os
 import numpy as np
 import pytest
 
+import signals
+from sessions import _mixed_as_suffixed
+
 pytestmark = pytest.mark.gpu
 
 
@@ -42,8 +45,7 @@ def _g(golden_dir, name):
 
 
 def synth(B, T, seed=0x4C797261):
-    rng = np.random.Generator(np.random.PCG64(seed))
-    return rng.integers(-32768, 32768, size=(T, B, 320)).astype(np.int16)
+    return signals.synth(B, T, seed)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -77,7 +79,6 @@ def test_speech_golden_builtin_modes(ctx_builtin, golden_dir, mode, suf):
 
 def test_speech_golden_builtin_mixed(ctx_builtin, golden_dir):
     """Mode "builtin_mixed" (round 6) against the flatbuffers executed in that mode (tools/make_golden.py --mixed)."""
-    from test_oracle_golden import _mixed_as_suffixed
     _speech_golden(ctx_builtin["builtin_mixed"], _mixed_as_suffixed(golden_dir), "mixed")
 
 

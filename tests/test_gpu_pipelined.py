@@ -8,14 +8,14 @@ import os
 import numpy as np
 import pytest
 
+from sessions import _run_session, _session
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
 @pytest.mark.parametrize("rate,bitrate,dtx", [(16000, 9200, False), (48000, 6000, True), (8000, 3200, False), (32000, 9200, True)])
 def test_pipelined_twins_equal_the_blocking_twins(tmp_path, golden_dir, rate, bitrate, dtx):
-    from test_batch_codec_semantics import _run_session
-    from test_reference_glue import _session
     pcm, script = _session(golden_dir, rate, bitrate)
     (tmp_path / "a").mkdir(); (tmp_path / "b").mkdir()
     pa, la, oa = _run_session(tmp_path / "a", None, rate, bitrate, dtx, pcm, script)

@@ -14,12 +14,9 @@ import os
 import numpy as np
 import pytest
 
+from signals import synth
+
 pytestmark = pytest.mark.gpu
-
-
-def synth(B, T, seed):
-    rng = np.random.Generator(np.random.PCG64(seed))
-    return rng.integers(-32768, 32768, size=(T, B, 320)).astype(np.int16)
 
 
 def test_config5_32768_streams_one_gpu(oracle_default):

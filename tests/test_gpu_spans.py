@@ -10,60 +10,22 @@ import wave
 import numpy as np
 import pytest
 
+from gpu_plumbing import make_ctx
+from signals import _audio_spans as _audio
+import span_cases
+from span_cases import _check_state, _sequential
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 MAX_STREAMS = 96
 
 
 def _ctx(mode="xnnpack", max_streams=MAX_STREAMS):
-    import lyra_amd
-    return lyra_amd.LyraHip(device=0, max_streams=max_streams, requant=mode)
-
-
-def _audio(golden_dir, hops, seed):
-    """speech of the two golden recordings, looped from a seed-dependent offset, with a little noise on top: [hops][320]"""
-    rng = np.random.default_rng(seed)
-    w = np.load(os.path.join(golden_dir, "sample_wavs.npz"))
-    src = np.concatenate([w["sample1_16kHz"], w["sample2_16kHz"]]).astype(np.int32)
-    off = int(rng.integers(0, src.size))
-    idx = (off + np.arange(hops * 320)) % src.size
-    x = src[idx] + rng.integers(-200, 201, hops * 320)
-    return np.clip(x, -32768, 32767).astype(np.int16).reshape(hops, 320)
-
-
-def _sequential(ctx, rows_by_id, num_bits, encode):
-    """hop by hop on `ctx`, one blocking call per hop over the streams that still have rows: {id: [n][.]} -> {id: [n][.]}"""
-    out = {i: [] for i in rows_by_id}
-    for h in range(max((len(v) for v in rows_by_id.values()), default=0)):
-        ids = [i for i, v in rows_by_id.items() if h < len(v)]
-        batch = np.stack([rows_by_id[i][h] for i in ids])
-        res = ctx.encode(batch, num_bits, ids) if encode else ctx.decode(batch, num_bits, ids)
-        for k, i in enumerate(ids):
-            out[i].append(res[k])
-    width = (num_bits + 7) // 8 if encode else 320
-    return {i: (np.stack(v) if v else np.zeros((0, width), np.uint8 if encode else np.int16)) for i, v in out.items()}
+    return make_ctx(max_streams, mode)
 
 
 def _layout(rows_by_id, gap=3):
-    """frame-major buffer with `gap` foreign rows between the spans (they must come back untouched): spans, buffer"""
-    spans, parts, at = [], [], 0
-    for i, v in rows_by_id.items():
-        filler = np.full((gap,) + v.shape[1:], 85, v.dtype)
-        parts += [filler, v]
-        spans.append((i, at + gap, len(v)))
-        at += gap + len(v)
-    return spans, np.concatenate(parts)
-
-
-def _check_state(where, ctx, twin, span_ids, lanes):
-    """span streams: the blob of the stream that ran hop by hop on the twin.  Lanes: the blob of the same id on the twin,
-    where that stream has never been used (a blob's header names its source id, so a freshly reset stream of the SAME id
-    is the one to compare with)."""
-    assert np.array_equal(ctx.export_streams(span_ids), twin.export_streams(span_ids)), f"{where}: span streams' blobs"
-    if len(lanes):
-        got, fresh = ctx.export_streams(lanes), twin.export_streams(lanes)
-        bad = [int(lanes[k]) for k in range(len(lanes)) if not np.array_equal(got[k], fresh[k])]
-        assert not bad, f"{where}: lanes {bad} are not in the reset state"
+    return span_cases._layout(rows_by_id, gap, tail=0)
 
 
 def _round_trip(where, ctx, twin, pcm_by_id, num_bits, lanes, lanes_dirty=False):

@@ -17,99 +17,22 @@ import wave
 import numpy as np
 import pytest
 
+from gpu_plumbing import FILL, _filled, make_ctx
+import span_cases
+from signals import _audio_dtx as _audio
+from span_cases import _check_rows, _check_state, _layout
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 MAX_STREAMS = 96
-FILL = 85   # every byte of the rows outside the spans, in every buffer
-SHORT = (("S", (3, 6)), ("Z", (4, 7)), ("N", (2, 4)), ("Z", (3, 6)))      # segment kinds and lengths in hops [lo, hi)
-LONG = (("S", (10, 18)), ("Z", (5, 11)), ("N", (3, 6)), ("Z", (4, 9)))
 
 
 def _ctx(mode="xnnpack", rate=16000):
-    import lyra_amd
-    c = lyra_amd.LyraHip(device=0, max_streams=MAX_STREAMS, requant=mode)
-    c.set_encoder_sample_rate(rate)
-    return c
-
-
-def _audio(golden_dir, hops, rate, seed):
-    """[hops][rate / 50]: the golden recordings read as a signal at `rate` from a seed-dependent offset, in segments of speech
-    (S), digital silence (Z) and +-12 noise (N)"""
-    rng = np.random.default_rng(seed)
-    w = np.load(os.path.join(golden_dir, "sample_wavs.npz"))
-    src = np.concatenate([w["sample1_16kHz"], w["sample2_16kHz"]]).astype(np.int32)
-    hop = rate // 50
-    x = (src[(int(rng.integers(0, src.size)) + np.arange(hops * hop)) % src.size] * 3).reshape(hops, hop)
-    pattern = SHORT if hops < 100 else LONG
-    at = k = 0
-    while at < hops:
-        kind, (lo, hi) = pattern[k % len(pattern)]
-        n = int(rng.integers(lo, hi))
-        if kind == "Z":
-            x[at:at + n] = 0
-        elif kind == "N":
-            x[at:at + n] = rng.integers(-12, 13, x[at:at + n].shape)
-        at += n; k += 1
-    return np.clip(x, -32768, 32767).astype(np.int16)
+    return make_ctx(MAX_STREAMS, mode, rate)
 
 
 def _twin_encode(twin, ext_by_id, rate, num_bits):
-    """hop by hop with DTX: {id: [n][rate / 50]} -> packets {id: [n][bytes]}, sizes {id: [n]}, 16 kHz hops {id: [n][320]}"""
-    pk, nb, p16 = ({i: [] for i in ext_by_id} for _ in range(3))
-    for h in range(max((len(v) for v in ext_by_id.values()), default=0)):
-        ids = [i for i, v in ext_by_id.items() if h < len(v)]
-        x = np.stack([ext_by_id[i][h] for i in ids])
-        x16 = twin.resample(x, rate, 16000, ids, side="encoder") if rate != 16000 else x
-        res, size = twin.encode_dtx(x16, num_bits, ids)
-        for k, i in enumerate(ids):
-            pk[i].append(res[k]); nb[i].append(size[k]); p16[i].append(x16[k])
-    w = (num_bits + 7) // 8
-    return ({i: np.stack(v) if v else np.zeros((0, w), np.uint8) for i, v in pk.items()},
-            {i: np.array(v, np.int32) for i, v in nb.items()},
-            {i: np.stack(v) if v else np.zeros((0, 320), np.int16) for i, v in p16.items()})
-
-
-def _layout(rows_by_id, gaps):
-    """frame-major buffer, gaps[k] filler rows in front of span k (0: the span touches the one before), two behind the last"""
-    first = next(iter(rows_by_id.values()))
-    def filler(g):
-        return np.full((g, first.shape[1] * first.dtype.itemsize), FILL, np.uint8).view(first.dtype)
-    spans, parts, at = [], [], 0
-    for (i, v), gap in zip(rows_by_id.items(), gaps):
-        parts += [filler(gap), v]
-        spans.append((i, at + gap, len(v)))
-        at += gap + len(v)
-    return spans, np.ascontiguousarray(np.concatenate(parts + [filler(2)]))
-
-
-def _filled(dev, frames, width, dtype):
-    import torch
-    return torch.from_numpy(np.full((frames, width * np.dtype(dtype).itemsize), FILL, np.uint8).view(dtype)).to(dev)
-
-
-def _check_rows(where, got, spans, want_by_id, written=None):
-    """rows of the spans equal the twin's (written[id]: only those rows; the others still hold the filler, like every row
-    outside the spans)"""
-    covered = np.zeros(len(got), bool)
-    for (i, first, n) in spans:
-        covered[first:first + n] = True
-        if not n:
-            continue
-        rows, want = got[first:first + n].reshape(n, -1), want_by_id[i].reshape(n, -1)
-        on = np.ones(n, bool) if written is None else written[i]
-        diff = np.flatnonzero((rows[on] != want[on]).any(axis=1))
-        assert len(diff) == 0, f"{where}: stream {i} differs at written hops {list(diff[:8])} of {n}"
-        assert (rows[~on].view(np.uint8) == FILL).all(), f"{where}: stream {i}: rows of noise hops were written"
-    assert (got[~covered].view(np.uint8) == FILL).all(), f"{where}: rows outside every span were written"
-
-
-def _check_state(where, ctx, twin, span_ids, lanes):
-    assert np.array_equal(ctx.export_streams(span_ids), twin.export_streams(span_ids)), f"{where}: span streams' blobs"
-    if not len(lanes):
-        return
-    got, fresh = ctx.export_streams(lanes), twin.export_streams(lanes)   # the twin never used the lanes' ids
-    bad = [int(lanes[k]) for k in range(len(lanes)) if not np.array_equal(got[k], fresh[k])]
-    assert not bad, f"{where}: lanes {bad} are not in the reset state"
+    return span_cases._twin_encode_ext(twin, ext_by_id, rate, num_bits, dtx=True)
 
 
 def _assert_input(where, sizes_by_id, W, rate, long_id, lanes):

@@ -10,91 +10,18 @@ import wave
 import numpy as np
 import pytest
 
+from gpu_plumbing import FILL, _filled, make_ctx
+from signals import _audio_ext as _audio
+from span_cases import (_check_rows, _check_state, _in_pos_offsets, _layout, _twin_decode_ext as _twin_decode,
+                        _twin_encode_ext as _twin_encode)
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 MAX_STREAMS = 96
-FILL = 85   # every byte of the rows outside the spans, in every buffer
 
 
 def _ctx(mode="xnnpack"):
-    import lyra_amd
-    return lyra_amd.LyraHip(device=0, max_streams=MAX_STREAMS, requant=mode)
-
-
-def _audio(golden_dir, hops, rate, seed):
-    """[hops][rate / 50]: the golden recordings' samples read as a signal at `rate`, looped from a seed-dependent offset, with
-    noise and a few full-scale bursts on top (the resampler's clip is part of what is compared)"""
-    rng = np.random.default_rng(seed)
-    w = np.load(os.path.join(golden_dir, "sample_wavs.npz"))
-    src = np.concatenate([w["sample1_16kHz"], w["sample2_16kHz"]]).astype(np.int32)
-    n = hops * (rate // 50)
-    x = src[(int(rng.integers(0, src.size)) + np.arange(n)) % src.size] * 3 + rng.integers(-300, 301, n)
-    for at in rng.integers(0, max(n - 40, 1), 3 if n > 40 else 0):
-        x[at:at + 40] = rng.choice([-40000, 40000], 40)
-    return np.clip(x, -32768, 32767).astype(np.int16).reshape(hops, rate // 50)
-
-
-def _twin_encode(twin, ext_by_id, rate, num_bits):
-    """hop by hop: {id: [n][rate / 50]} -> packets {id: [n][bytes]}, 16 kHz hops {id: [n][320]}"""
-    pk, p16 = {i: [] for i in ext_by_id}, {i: [] for i in ext_by_id}
-    for h in range(max((len(v) for v in ext_by_id.values()), default=0)):
-        ids = [i for i, v in ext_by_id.items() if h < len(v)]
-        x16 = twin.resample(np.stack([ext_by_id[i][h] for i in ids]), rate, 16000, ids, side="encoder")
-        res = twin.encode(x16, num_bits, ids)
-        for k, i in enumerate(ids):
-            pk[i].append(res[k]); p16[i].append(x16[k])
-    nb = (num_bits + 7) // 8
-    return ({i: np.stack(v) if v else np.zeros((0, nb), np.uint8) for i, v in pk.items()},
-            {i: np.stack(v) if v else np.zeros((0, 320), np.int16) for i, v in p16.items()})
-
-
-def _twin_decode(twin, pk_by_id, rate, num_bits):
-    """hop by hop: packets -> external-rate PCM {id: [n][rate / 50]}, 16 kHz PCM {id: [n][320]}"""
-    ext, p16 = {i: [] for i in pk_by_id}, {i: [] for i in pk_by_id}
-    for h in range(max((len(v) for v in pk_by_id.values()), default=0)):
-        ids = [i for i, v in pk_by_id.items() if h < len(v)]
-        x16 = twin.decode(np.stack([pk_by_id[i][h] for i in ids]), num_bits, ids)
-        res = twin.resample(x16, 16000, rate, ids, side="decoder")
-        for k, i in enumerate(ids):
-            ext[i].append(res[k]); p16[i].append(x16[k])
-    return ({i: np.stack(v) if v else np.zeros((0, rate // 50), np.int16) for i, v in ext.items()},
-            {i: np.stack(v) if v else np.zeros((0, 320), np.int16) for i, v in p16.items()})
-
-
-def _layout(rows_by_id, gaps):
-    """frame-major buffer, gaps[k] filler rows in front of span k (0: the span touches the one before) and two behind the
-    last: spans, buffer"""
-    first = next(iter(rows_by_id.values()))
-    def filler(g):
-        return np.full((g, first.shape[1] * first.dtype.itemsize), FILL, np.uint8).view(first.dtype)
-    spans, parts, at = [], [], 0
-    for (i, v), gap in zip(rows_by_id.items(), gaps):
-        parts += [filler(gap), v]
-        spans.append((i, at + gap, len(v)))
-        at += gap + len(v)
-    return spans, np.ascontiguousarray(np.concatenate(parts + [filler(2)]))
-
-
-def _filled(dev, frames, width, dtype):
-    import torch
-    return torch.from_numpy(np.full((frames, width * np.dtype(dtype).itemsize), FILL, np.uint8).view(dtype)).to(dev)
-
-
-def _check_rows(where, got, spans, want_by_id):
-    """rows of the spans equal the twin's; every other row still holds the filler"""
-    covered = np.zeros(len(got), bool)
-    for (i, first, n) in spans:
-        covered[first:first + n] = True
-        diff = np.flatnonzero((got[first:first + n] != want_by_id[i]).any(axis=1)) if n else []
-        assert len(diff) == 0, f"{where}: stream {i} differs at hops {list(diff[:8])} of {n}"
-    assert (got[~covered].view(np.uint8) == FILL).all(), f"{where}: rows outside every span were written"
-
-
-def _check_state(where, ctx, twin, span_ids, lanes):
-    assert np.array_equal(ctx.export_streams(span_ids), twin.export_streams(span_ids)), f"{where}: span streams' blobs"
-    got, fresh = ctx.export_streams(lanes), twin.export_streams(lanes)   # the twin never used the lanes' ids
-    bad = [int(lanes[k]) for k in range(len(lanes)) if not np.array_equal(got[k], fresh[k])]
-    assert not bad, f"{where}: lanes {bad} are not in the reset state"
+    return make_ctx(MAX_STREAMS, mode)
 
 
 @pytest.mark.parametrize("rate,num_bits,mode", [(8000, 64, "xnnpack"), (32000, 120, "xnnpack"), (48000, 184, "xnnpack"),
@@ -134,20 +61,6 @@ def test_spans_at_other_rates_equal_hop_by_hop_calls(golden_dir, rate, num_bits,
     _check_rows(where + " 16 kHz pcm", d_p16.cpu().numpy(), spans, want_d16)
     assert np.array_equal(d_pk.cpu().numpy(), buf), f"{where}: the packet buffer was written"
     _check_state(where + " after decode", ctx, twin, list(lengths), lanes)
-
-
-def _in_pos_offsets(ctx, scratch_id):
-    """Byte offsets of RS_IN_POS of the encoder's and the decoder's resampler slot in a blob, found on the device: resampling
-    zeros into a fresh stream's slot leaves its history as it was and moves the phase word alone."""
-    offs = []
-    for side, n_in, to in (("encoder", 3, (48000, 16000)), ("decoder", 2, (16000, 8000))):
-        before = ctx.export_streams([scratch_id])[0]
-        ctx.resample(np.zeros((1, n_in), np.int16), to[0], to[1], [scratch_id], side=side)
-        after = ctx.export_streams([scratch_id])[0]
-        at = np.flatnonzero(before != after)
-        assert at.size == 1 and after[at[0]] == n_in and before[at[0]] == 0, (side, at)
-        offs.append(int(at[0]))
-    return offs
 
 
 def test_span_continues_a_live_stream_is_continued_and_keeps_a_decimation_phase(golden_dir):

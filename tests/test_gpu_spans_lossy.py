@@ -15,167 +15,19 @@ import wave
 import numpy as np
 import pytest
 
+from gpu_plumbing import FILL, _filled, make_ctx
+from signals import _bursts, _long_trace, _speech_hops as _speech, _stretches
+from span_cases import (CNG, GEN, _check_rows, _check_state, _dirty_lane, _layout, _packets,
+                        _twin_decode_lossy as _twin_decode)
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 MAX_STREAMS = 96
-FILL = 85   # every byte of the rows outside the spans, in every buffer
 SEED = 0x5EEDC0DE
-GEN, CNG, RX, CN = 1, 2, 4, 8   # lossy_info (lyra_amd/csrc/lossy_plan.h)
-LONG = (("S", (10, 18)), ("Z", (5, 11)), ("N", (3, 6)), ("Z", (4, 9)))
 
 
 def _ctx(mode="xnnpack", rate=16000):
-    import lyra_amd
-    c = lyra_amd.LyraHip(device=0, max_streams=MAX_STREAMS, requant=mode)
-    c.set_encoder_sample_rate(rate)
-    c.set_cng_seed(SEED)
-    return c
-
-
-def _speech(golden_dir, hops, seed, half_silent=False):
-    """[hops][320] at 16 kHz from the golden recordings; half_silent: segments of speech, digital silence and +-12 noise"""
-    rng = np.random.default_rng(seed)
-    w = np.load(os.path.join(golden_dir, "sample_wavs.npz"))
-    src = np.concatenate([w["sample1_16kHz"], w["sample2_16kHz"]]).astype(np.int32)
-    x = (src[(int(rng.integers(0, src.size)) + np.arange(hops * 320)) % src.size] * 3).reshape(hops, 320)
-    at = k = 0
-    while half_silent and at < hops:
-        kind, (lo, hi) = LONG[k % len(LONG)]
-        n = int(rng.integers(lo, hi))
-        if kind == "Z":
-            x[at:at + n] = 0
-        elif kind == "N":
-            x[at:at + n] = rng.integers(-12, 13, x[at:at + n].shape)
-        at += n; k += 1
-    return np.clip(x, -32768, 32767).astype(np.int16)
-
-
-def _packets(enc, golden_dir, n, num_bits, seed):
-    """n packets of golden speech (the encoder side of `enc`, stream 0, time-parallel on lanes 1..40)"""
-    if n == 0:
-        return np.zeros((0, (num_bits + 7) // 8), np.uint8)
-    enc.reset([0])
-    return enc.encode_spans([(0, 0, n)], _speech(golden_dir, n, seed), num_bits, np.arange(1, 41, dtype=np.int32))
-
-
-def _bursts(n, *at_len):
-    rx = np.ones(n, bool)
-    for at, length in at_len:
-        rx[at:at + length] = False
-    return rx
-
-
-def _long_trace(plan_of):
-    """350 frames: isolated losses, bursts of 3, 4, 5 (both sides of the 4-hop concealment limit), 8, 12 and 20 (run_gen == 0
-    ticks, full comfort noise), then -- placed on the call's plan (plan_of(trace) -> (plan, the span's first buffer frame); the
-    span is the call's first), which bursts of at most 6 do not move -- a burst of 5 that starts inside a lane chunk's warm-up
-    and one that straddles a chunk boundary"""
-    import lyra_amd.codec as codec
-    n = 350
-    rx = _bursts(n, (30, 1), (34, 1), (45, 3), (60, 4), (75, 5), (95, 8), (140, 12), (200, 20), (260, 1), (300, 9))
-    plan, first = plan_of(rx)
-    W = codec.span_warmup_frames("decoder")
-    lane_chunks = [c for c in plan["chunks"] if c["span"] == 0 and c["n_warmup"] > 0]
-    assert len(lane_chunks) >= 2, "the long span is not cut into lane chunks"
-    gen = plan["gen_frames"] - first   # compacted index -> frame of the span
-    def clear(f):   # ten received frames on either side: the new burst merges with no other
-        return f - 10 >= 0 and f + 15 <= n and rx[f - 10:f + 15].all()
-    warm = [int(gen[g]) for c in lane_chunks for g in range(int(c["first_frame"]) - W + 2, int(c["first_frame"]) - 8)
-            if clear(int(gen[g]))]
-    assert warm, "no room for a burst inside a warm-up"
-    rx[warm[0]:warm[0] + 5] = False
-    edge = [int(gen[int(c["first_frame"])]) - 2 for c in lane_chunks if clear(int(gen[int(c["first_frame"])]) - 2)]
-    assert edge, "no room for a burst across a chunk boundary"
-    rx[edge[-1]:edge[-1] + 5] = False
-    return rx
-
-
-def _twin_decode(twin, pk_by_id, rx_by_id, rate, num_bits, watch=None):
-    """hop by hop: {id: pcm16 [n][320]}, {id: pcm_ext [n][rate / 50]}, {id: is_noise [n]}, {id: is_cn [n]} and, for stream
-    `watch`, the decoder-side noise estimate after every tick [n][160]"""
-    import torch
-    dev = torch.device("cuda", 0)
-    nbytes, hop = (num_bits + 7) // 8, rate // 50
-    out = [{i: [] for i in pk_by_id} for _ in range(4)]
-    est = []
-    for h in range(max((len(v) for v in pk_by_id.values()), default=0)):
-        ids = [i for i, v in pk_by_id.items() if h < len(v)]
-        B = len(ids)
-        d_ids = torch.tensor(ids, dtype=torch.int32, device=dev)
-        d_pk = torch.from_numpy(np.stack([pk_by_id[i][h] for i in ids])).to(dev)
-        d_pb = torch.tensor([nbytes if rx_by_id[i][h] else 0 for i in ids], dtype=torch.int32, device=dev)
-        d_16 = torch.zeros((B, 320), dtype=torch.int16, device=dev)
-        d_ext = torch.zeros((B, hop), dtype=torch.int16, device=dev) if rate != 16000 else None
-        d_n, d_cn = (torch.full((B,), -7, dtype=torch.int32, device=dev) for _ in range(2))
-        twin.decode_lossy_dev(d_ids, d_pk, d_pb, num_bits, rate, d_16, d_ext, d_n, d_cn)
-        twin.synchronize()
-        res = (d_16.cpu().numpy(), d_ext.cpu().numpy() if d_ext is not None else d_16.cpu().numpy(), d_n.cpu().numpy(),
-               d_cn.cpu().numpy())
-        for k, i in enumerate(ids):
-            for o, r in zip(out, res):
-                o[i].append(r[k])
-        if watch in ids:
-            est.append(twin.noise_estimate([watch])[0].copy())
-    shape = ((0, 320), (0, hop), (0,), (0,))
-    dt = (np.int16, np.int16, np.int32, np.int32)
-    stacked = [{i: np.stack(v) if v else np.zeros(s, d) for i, v in o.items()} for o, s, d in zip(out, shape, dt)]
-    return (*stacked, np.array(est, np.float32))
-
-
-def _layout(rows_by_id, gaps):
-    """frame-major buffer, gaps[k] filler rows in front of span k (0: the span touches the one before), two behind the last"""
-    first = next(iter(rows_by_id.values()))
-    def filler(g):
-        return np.full((g, first.shape[1] * first.dtype.itemsize), FILL, np.uint8).view(first.dtype)
-    spans, parts, at = [], [], 0
-    for (i, v), gap in zip(rows_by_id.items(), gaps):
-        parts += [filler(gap), v]
-        spans.append((i, at + gap, len(v)))
-        at += gap + len(v)
-    return spans, np.ascontiguousarray(np.concatenate(parts + [filler(2)]))
-
-
-def _filled(dev, frames, width, dtype):
-    import torch
-    return torch.from_numpy(np.full((frames, width * np.dtype(dtype).itemsize), FILL, np.uint8).view(dtype)).to(dev)
-
-
-def _check_rows(where, got, spans, want_by_id):
-    covered = np.zeros(len(got), bool)
-    for (i, first, n) in spans:
-        covered[first:first + n] = True
-        if not n:
-            continue
-        rows, want = got[first:first + n].reshape(n, -1), want_by_id[i].reshape(n, -1)
-        diff = np.flatnonzero((rows != want).any(axis=1))
-        assert len(diff) == 0, f"{where}: stream {i} differs at hops {list(diff[:8])} ({len(diff)} of {n})"
-    assert (got[~covered].view(np.uint8) == FILL).all(), f"{where}: rows outside every span were written"
-
-
-def _check_state(where, ctx, twin, span_ids, lanes):
-    got, want = ctx.export_streams(span_ids), twin.export_streams(span_ids)
-    bad = [int(span_ids[k]) for k in range(len(span_ids)) if not np.array_equal(got[k], want[k])]
-    assert not bad, f"{where}: the blobs of span streams {bad} differ from the twin's"
-    if len(lanes):   # the twin never ran a decoder stage on the lanes' ids; what else their slots held, it holds too
-        got, want = ctx.export_streams(lanes), twin.export_streams(lanes)
-        bad = [int(lanes[k]) for k in range(len(lanes)) if not np.array_equal(got[k], want[k])]
-        assert not bad, f"{where}: lanes {bad}: decoder stages not reset, or another slot touched"
-
-
-def _dirty_lane(contexts, lane, golden_dir):
-    """estimator, comfort-noise and resampler slots of a lane that are not the reset state; its decoder stages stay reset"""
-    x = _speech(golden_dir, 3, 900)
-    for c in contexts:
-        for h in x:
-            c.noise_receive(h[None], [lane], side="decoder")
-        c.comfort_noise(stream_ids=[lane])
-        c.resample(x[:1], 16000, 48000, [lane], side="decoder")
-
-
-def _stretches(mask):
-    """[(first, one past last)] of the runs of True"""
-    edges = np.flatnonzero(np.diff(np.concatenate([[0], mask.astype(np.int8), [0]])))
-    return list(zip(edges[::2], edges[1::2]))
+    return make_ctx(MAX_STREAMS, mode, rate, SEED)
 
 
 def _assert_trace(where, plan, k_long, rx_long, est_after, want_16, want_cn, need_plan_bursts):

@@ -8,106 +8,26 @@ The bit schedules and size schedules are drawn per frame and then adjusted on th
 exercise holds by construction; it is asserted before anything is compared (_assert_encode_schedule, _assert_size_changes)."""
 import os
 import subprocess
-import sys
 import wave
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(__file__))
-from test_gpu_spans_dtx import _audio                                                                     # noqa: E402
-from test_gpu_spans_lossy import (CNG, FILL, RX, SEED, _bursts, _check_rows, _check_state, _dirty_lane, _filled, _layout,  # noqa: E402
-                                  _long_trace, _packets, _speech, _stretches)
+from gpu_plumbing import FILL, _filled, make_ctx
+from signals import _audio_dtx as _audio, _bursts, _plain, _speech_hops as _speech, _stretches
+from span_cases import (BITS, ROW, _by_frame, _check_packets, _check_rows, _check_state, _decode_schedule, _dirty_lane,
+                        _draw_sizes, _encode_plan, _layout, _other, _packets, _rows_of, _twin_decode_mixed as _twin_decode,
+                        _twin_encode_rows as _twin_encode)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 MAX_STREAMS = 96
-ROW = 23                                       # LYRA_HIP_MAX_PACKET_BYTES
-BITS = np.array([4, 8, 12, 64, 100, 120, 180, 184], np.int32)   # 100 bits: 25 stages, the last byte carries a zero low nibble
-SIZES = np.array([8, 15, 23], np.int32)
+SEED = 0x5EEDC0DE
 EINVAL = -1
 
 
 def _ctx(mode="xnnpack", rate=16000):
-    import lyra_amd
-    c = lyra_amd.LyraHip(device=0, max_streams=MAX_STREAMS, requant=mode)
-    c.set_encoder_sample_rate(rate)
-    c.set_cng_seed(SEED)
-    return c
-
-
-def _plain(golden_dir, hops, rate, seed):
-    """[hops][rate / 50]: the golden recordings read as a signal at `rate` from a seed-dependent offset"""
-    rng = np.random.default_rng(seed)
-    w = np.load(os.path.join(golden_dir, "sample_wavs.npz"))
-    src = np.concatenate([w["sample1_16kHz"], w["sample2_16kHz"]]).astype(np.int32)
-    hop = rate // 50
-    x = (src[(int(rng.integers(0, src.size)) + np.arange(hops * hop)) % src.size] * 3).reshape(hops, hop)
-    return np.clip(x, -32768, 32767).astype(np.int16)
-
-
-def _other(value, choices):
-    """the choice behind `value`, cyclically: a different one"""
-    return choices[(int(np.flatnonzero(choices == value)[0]) + 1) % len(choices)]
-
-
-# ---- the twins ----------------------------------------------------------------------------------------------------------------
-def _twin_encode(twin, ext_by_id, bits_by_id, rate, dtx=False):
-    """hop by hop: {id: [n][rate / 50]}, {id: [n] bit counts} -> rows {id: [n][23], FILL behind each packet}, sizes {id: [n]}"""
-    import torch
-    dev = torch.device("cuda", 0)
-    pk, nb = ({i: [] for i in ext_by_id} for _ in range(2))
-    for h in range(max((len(v) for v in ext_by_id.values()), default=0)):
-        ids = [i for i, v in ext_by_id.items() if h < len(v)]
-        B = len(ids)
-        d_ids = torch.tensor(ids, dtype=torch.int32, device=dev)
-        d_x = torch.from_numpy(np.stack([ext_by_id[i][h] for i in ids])).to(dev)
-        d_bits = torch.tensor([int(bits_by_id[i][h]) for i in ids], dtype=torch.int32, device=dev)
-        d_pk, d_nb = _filled(dev, B, ROW, np.uint8), _filled(dev, B, 1, np.int32).view(-1)
-        twin.encode_mixed_dev(d_ids, d_x, rate, d_bits, d_pk, d_nb, dtx=dtx)
-        twin.synchronize()
-        rows, sizes = d_pk.cpu().numpy(), d_nb.cpu().numpy()
-        for k, i in enumerate(ids):
-            pk[i].append(rows[k]); nb[i].append(sizes[k])
-    assert twin.encode_mixed_errors() == 0
-    return ({i: np.stack(v) if v else np.zeros((0, ROW), np.uint8) for i, v in pk.items()},
-            {i: np.array(v, np.int32) for i, v in nb.items()})
-
-
-def _twin_decode(twin, pk_by_id, pb_by_id, rate):
-    """hop by hop: {id: pcm16 [n][320]}, {id: pcm_ext [n][rate / 50]}, {id: is_noise [n]}, {id: is_cn [n]}"""
-    import torch
-    dev = torch.device("cuda", 0)
-    hop = rate // 50
-    out = [{i: [] for i in pk_by_id} for _ in range(4)]
-    for h in range(max((len(v) for v in pk_by_id.values()), default=0)):
-        ids = [i for i, v in pk_by_id.items() if h < len(v)]
-        B = len(ids)
-        d_ids = torch.tensor(ids, dtype=torch.int32, device=dev)
-        d_pk = torch.from_numpy(np.stack([pk_by_id[i][h] for i in ids])).to(dev)
-        d_pb = torch.tensor([int(pb_by_id[i][h]) for i in ids], dtype=torch.int32, device=dev)
-        d_16 = torch.zeros((B, 320), dtype=torch.int16, device=dev)
-        d_ext = torch.zeros((B, hop), dtype=torch.int16, device=dev) if rate != 16000 else None
-        d_n, d_cn = (torch.full((B,), -7, dtype=torch.int32, device=dev) for _ in range(2))
-        twin.decode_lossy_mixed_dev(d_ids, d_pk, d_pb, rate, d_16, d_ext, d_n, d_cn)
-        twin.synchronize()
-        res = (d_16.cpu().numpy(), d_ext.cpu().numpy() if d_ext is not None else d_16.cpu().numpy(), d_n.cpu().numpy(),
-               d_cn.cpu().numpy())
-        for k, i in enumerate(ids):
-            for o, r in zip(out, res):
-                o[i].append(r[k])
-    assert twin.decode_lossy_errors() == 0
-    shape = ((0, 320), (0, hop), (0,), (0,))
-    dt = (np.int16, np.int16, np.int32, np.int32)
-    return [{i: np.stack(v) if v else np.zeros(s, d) for i, v in o.items()} for o, s, d in zip(out, shape, dt)]
-
-
-def _by_frame(spans, by_id, F, dtype=np.int32):
-    """{id: [n]} -> [F], FILL bytes outside the spans"""
-    out = np.full(F * np.dtype(dtype).itemsize, FILL, np.uint8).view(dtype).copy()
-    for (i, first, n) in spans:
-        out[first:first + n] = by_id[i]
-    return out
+    return make_ctx(MAX_STREAMS, mode, rate, SEED)
 
 
 # ---- encode -------------------------------------------------------------------------------------------------------------------
@@ -125,20 +45,6 @@ def _producing_rows(chunks, n_steps, W, frame_of):
         out.append([(r, frame_of(int(chunks[r]["first_frame"]) - int(chunks[r]["n_warmup"]) + i)) for r in range(Bq)
                     if i < steps_of[r] and i >= chunks[r]["n_warmup"]])
     return out
-
-
-def _encode_plan(spans, active_by_id, lanes):
-    """the encoder's plan on the frames that reach it (active_by_id: {id: [n] bool}, all True without DTX) and the map of its
-    frame index to buffer frames"""
-    import lyra_amd.codec as codec
-    compact, frame_map, region = [], {}, 0
-    for (i, first, n) in spans:
-        at = np.flatnonzero(active_by_id[i])
-        compact.append((i, region, len(at)))
-        frame_map.update({region + c: first + int(f) for c, f in enumerate(at)})
-        region += n
-    chunks, n_steps = codec.spans_plan("encoder", compact, lanes, MAX_STREAMS)
-    return chunks, n_steps, frame_map, compact
 
 
 def _encode_schedule(rng, F, chunks, n_steps, W, frame_map):
@@ -172,16 +78,6 @@ def _assert_encode_schedule(where, bits, chunks, n_steps, W, frame_map):
     assert any({4, 184} <= t for t in tiles), (where, "no tile holds a 4-bit and a 184-bit row")
     assert all(step for step in rows), (where, "a step produces nothing")
     assert all(len({int(bits[f]) for _, f in step}) >= 2 for step in rows), (where, "a step's rows share one bit count")
-
-
-def _check_packets(where, got_pk, got_nb, spans, want_pk, want_nb):
-    F = len(got_pk)
-    _check_rows(where + " packet_bytes", got_nb.reshape(F, 1), spans, want_nb)
-    _check_rows(where + " packet rows", got_pk, spans, want_pk)   # (the twin's rows: FILL behind every packet, FILL in noise rows)
-    nb = _by_frame(spans, want_nb, F)
-    for (i, first, n) in spans:
-        for f in range(first, first + n):
-            assert (got_pk[f, nb[f]:] == FILL).all(), f"{where}: stream {i}: bytes behind the packet of frame {f} were written"
 
 
 ENCODE_CASES = [(16000, False, "xnnpack"), (48000, True, "xnnpack"), (8000, False, "builtin_mixed")]
@@ -250,70 +146,6 @@ def _assert_prefixes(enc, golden_dir):
     for bits, nb in ((64, 8), (120, 15)):
         assert np.array_equal(_packets(enc, golden_dir, 30, bits, 31), full[:, :nb]), f"{bits}-bit packets are no prefix"
     _prefix_checked.append(True)
-
-
-def _rows_of(pk184, pb):
-    """what the receiver holds: the first pb bytes of each packet, FILL behind them and in the rows of lost packets"""
-    rows = np.full((len(pb), ROW), FILL, np.uint8)
-    for h, n in enumerate(pb):
-        rows[h, :n] = pk184[h, :n]
-    return rows
-
-
-def _draw_sizes(rng, rx):
-    return np.where(rx, rng.choice(SIZES, len(rx)), 0).astype(np.int32)
-
-
-def _size_changes(plan, g0, n_gen):
-    """compacted indices g0 <= g < g0 + n_gen of the span's ticks fed from a packet whose size differs from the last such
-    tick's in front of them"""
-    gb, last, out = plan["gen_bytes"], 0, set()
-    for g in range(g0, g0 + n_gen):
-        if gb[g]:
-            if last and gb[g] != last:
-                out.add(g)
-            last = int(gb[g])
-    return out
-
-
-def _assert_size_changes(where, plan, k_long, first, W):
-    """on the long span: a size change on a lane chunk's first tick, one inside a warm-up, and one on the first received tick
-    behind a comfort-noise stretch"""
-    counts = plan["counts"]
-    g0, n_gen = int(counts["n_gen"][:k_long].sum()), int(counts["n_gen"][k_long])
-    changes = _size_changes(plan, g0, n_gen)
-    lane_chunks = [c for c in plan["chunks"] if c["span"] == k_long and c["n_warmup"] > 0]
-    assert any(int(c["first_frame"]) in changes for c in lane_chunks), (where, "no size change on a chunk's first tick")
-    assert any(g in changes for c in lane_chunks for g in range(int(c["first_frame"]) - W, int(c["first_frame"]))), \
-        (where, "no size change inside a warm-up")
-    info = plan["info"][:350]   # (the long span is the call's first)
-    frame_of = plan["gen_frames"] - first
-    behind_cng = {h for h in range(1, 350) if info[h] & RX and info[h - 1] & CNG and not info[h - 1] & RX}
-    assert any(int(frame_of[g]) in behind_cng for g in changes), (where, "no size change behind a comfort-noise stretch")
-
-
-def _decode_schedule(where, rng, spans, rx, lanes, F, W):
-    """rx[7]: the long loss trace, placed on the call's plan; then a size per received frame {id: [n]}, drawn from SIZES and
-    adjusted on the plan: a switch on the first packet behind a comfort-noise stretch and on a lane chunk's first tick"""
-    import lyra_amd.codec as codec
-    first = spans[0][1]
-    def plan_of(rx7):   # (the plan depends on the receive pattern alone)
-        pb = _by_frame(spans, {i: np.where(rx7 if i == 7 else rx[i], ROW, 0) for (i, _, _) in spans}, F)
-        return codec.spans_lossy_plan(spans, pb, ROW, [0] * len(spans), lanes, MAX_STREAMS), first
-    rx[7] = _long_trace(plan_of)
-    pb = {i: _draw_sizes(rng, rx[i]) for (i, _, _) in spans}
-    plan, _ = plan_of(rx[7])
-    frame_of = plan["gen_frames"] - first
-    info = plan["info"][:350]
-    def switch_at(h):
-        before = pb[7][:h][pb[7][:h] > 0]
-        pb[7][h] = _other(before[-1], SIZES)
-    chunk_first = [int(frame_of[int(c["first_frame"])]) for c in plan["chunks"] if c["span"] == 0 and c["n_warmup"] > 0]
-    switch_at(next(h for h in range(1, 350) if rx[7][h] and info[h - 1] & CNG and not rx[7][h - 1]))
-    switch_at(next(h for h in chunk_first if rx[7][h]))
-    mixed_plan = codec.spans_lossy_plan_mixed(spans, _by_frame(spans, pb, F), [0] * len(spans), lanes, MAX_STREAMS)
-    _assert_size_changes(where, mixed_plan, 0, first, W)
-    return pb
 
 
 DECODE_CASES = [(16000, "xnnpack"), (48000, "xnnpack"), (32000, "builtin_mixed")]

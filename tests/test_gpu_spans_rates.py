@@ -8,25 +8,21 @@ filler outside the spans, the span streams' exported blobs and the lanes' agains
 External-rate rows are 960 samples apart.  What lies behind a row's rate / 50 samples is FILL in the span call's buffer and zero
 in the twin's, so a call that read it would differ.  In the shared layout spans of different rates touch in the buffer: frame 0
 of the second has to take its resampler history from its stream's slot, not from the 34 samples in front of it."""
-import os
-import sys
+import functools
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(__file__))
-from test_gpu_spans_dtx import _audio                                                                     # noqa: E402
-from test_gpu_spans_ext import _in_pos_offsets                                                            # noqa: E402
-from test_gpu_spans_lossy import (FILL, SEED, _bursts, _check_rows, _check_state, _dirty_lane, _filled, _layout,  # noqa: E402
-                                  _packets, _stretches)
-from test_gpu_spans_mixed import (BITS, ROW, _by_frame, _check_packets, _decode_schedule, _draw_sizes,   # noqa: E402
-                                  _encode_plan, _plain, _rows_of)
+from gpu_plumbing import FILL, _dev, _filled, make_ctx
+from signals import _audio_dtx as _audio, _bursts, _pattern, _plain, _stretches
+import span_cases
+from span_cases import (BITS, EXT, FILL16, ROW, _by_frame, _check_packets, _check_rows, _check_state, _decode_schedule,
+                        _dirty_lane, _draw_sizes, _encode_plan, _in_pos_offsets, _layout, _packets, _padded, _rows_of)
 
 pytestmark = pytest.mark.gpu
 MAX_STREAMS = 96
-EXT = 960                                      # LYRA_HIP_MAX_EXT_HOP
+SEED = 0x5EEDC0DE
 EINVAL = -1
-FILL16 = 21845                                 # two FILL bytes
 # (stream id, frames, rate) in buffer order and the filler rows in front of each: lengths 0, 1, 3 and 5 leave a resampler
 # workgroup (four frames) partly empty or cross its boundary, 60 / 61 / 140 run on lanes; 7|11, 20|5 and 9|13 touch in the
 # buffer at different rates; all four rates; a 16 kHz span on lanes and a short one
@@ -40,18 +36,7 @@ SHORT = {0: "", 1: "Z", 3: "ZSZ", 5: "ZSZZZ"}  # short spans by hand: a noise fr
 
 
 def _ctx(mode="xnnpack"):
-    import lyra_amd
-    c = lyra_amd.LyraHip(device=0, max_streams=MAX_STREAMS, requant=mode)
-    c.set_cng_seed(SEED)
-    return c
-
-
-def _pattern(golden_dir, kinds, rate, seed):
-    x = _plain(golden_dir, len(kinds), rate, seed)
-    for h, kind in enumerate(kinds):
-        if kind == "Z":
-            x[h] = 0
-    return x
+    return make_ctx(MAX_STREAMS, mode, cng_seed=SEED)
 
 
 def _span_audio(golden_dir, n, rate, seed):
@@ -59,97 +44,14 @@ def _span_audio(golden_dir, n, rate, seed):
     return _pattern(golden_dir, SHORT[n], rate, seed) if n in SHORT else _audio(golden_dir, n, rate, seed)
 
 
-def _padded(x, fill):
-    """[n][hop] -> [n][960], `fill` behind the samples"""
-    out = np.full((len(x), EXT), fill, np.int16)
-    out[:, :x.shape[1]] = x
-    return out
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-# ---- the twins ----------------------------------------------------------------------------------------------------------------
+# ---- the twins and the check of the external-rate rows, at this layout's rates ------------------------------------------------
 def _twin_encode(twin, aux, ext_by_id, bits_by_id, dtx=False):
-    """hop by hop through encode_rates_dev: {id: [n][rate / 50]}, {id: [n] bit counts} -> rows {id: [n][23], FILL behind each
-    packet}, sizes {id: [n]} and, from resample(side="encoder") on `aux` (a context that runs nothing else; None: not wanted),
-    the 16 kHz hops {id: [n][320]}"""
-    import torch
-    dev = _dev()
-    pk, nb, p16 = ({i: [] for i in ext_by_id} for _ in range(3))
-    for h in range(max((len(v) for v in ext_by_id.values()), default=0)):
-        ids = [i for i, v in ext_by_id.items() if h < len(v)]
-        B = len(ids)
-        d_ids = torch.tensor(ids, dtype=torch.int32, device=dev)
-        d_x = torch.from_numpy(np.concatenate([_padded(ext_by_id[i][h][None], 0) for i in ids])).to(dev)
-        d_rates = torch.tensor([RATE_OF[i] for i in ids], dtype=torch.int32, device=dev)
-        d_bits = torch.tensor([int(bits_by_id[i][h]) for i in ids], dtype=torch.int32, device=dev)
-        d_pk, d_nb = _filled(dev, B, ROW, np.uint8), _filled(dev, B, 1, np.int32).view(-1)
-        twin.encode_rates_dev(d_ids, d_x, d_rates, d_bits, d_pk, d_nb, dtx=dtx)
-        twin.synchronize()
-        rows, sizes = d_pk.cpu().numpy(), d_nb.cpu().numpy()
-        for k, i in enumerate(ids):
-            pk[i].append(rows[k]); nb[i].append(sizes[k])
-            x = ext_by_id[i][h]
-            if aux is not None:
-                p16[i].append(x if RATE_OF[i] == 16000 else aux.resample(x[None], RATE_OF[i], 16000, [i], side="encoder")[0])
-    assert twin.encode_mixed_errors() == 0 and twin.rates_errors() == 0
-    return ({i: np.stack(v) if v else np.zeros((0, ROW), np.uint8) for i, v in pk.items()},
-            {i: np.array(v, np.int32) for i, v in nb.items()},
-            {i: np.stack(v) if v else np.zeros((0, 320), np.int16) for i, v in p16.items()})
+    return span_cases._twin_encode_rows(twin, ext_by_id, bits_by_id, RATE_OF, dtx, aux)
 
 
-def _twin_decode(twin, pk_by_id, pb_by_id):
-    """hop by hop through decode_lossy_rates_dev: {id: pcm16 [n][320]}, {id: pcm_ext [n][rate / 50]}, {id: is_noise [n]},
-    {id: is_cn [n]}"""
-    import torch
-    dev = _dev()
-    out = [{i: [] for i in pk_by_id} for _ in range(4)]
-    for h in range(max((len(v) for v in pk_by_id.values()), default=0)):
-        ids = [i for i, v in pk_by_id.items() if h < len(v)]
-        B = len(ids)
-        d_ids = torch.tensor(ids, dtype=torch.int32, device=dev)
-        d_pk = torch.from_numpy(np.stack([pk_by_id[i][h] for i in ids])).to(dev)
-        d_pb = torch.tensor([int(pb_by_id[i][h]) for i in ids], dtype=torch.int32, device=dev)
-        d_rates = torch.tensor([RATE_OF[i] for i in ids], dtype=torch.int32, device=dev)
-        d_16, d_ext = torch.zeros((B, 320), dtype=torch.int16, device=dev), torch.zeros((B, EXT), dtype=torch.int16, device=dev)
-        d_n, d_cn = (torch.full((B,), -7, dtype=torch.int32, device=dev) for _ in range(2))
-        twin.decode_lossy_rates_dev(d_ids, d_pk, d_pb, d_rates, d_16, d_ext, d_n, d_cn)
-        twin.synchronize()
-        res = (d_16.cpu().numpy(), d_ext.cpu().numpy(), d_n.cpu().numpy(), d_cn.cpu().numpy())
-        for k, i in enumerate(ids):
-            for o, r in zip(out, res):
-                o[i].append(r[k][:RATE_OF[i] // 50] if r is res[1] else r[k])
-    assert twin.decode_lossy_errors() == 0 and twin.rates_errors() == 0
-    shapes = {i: ((0, 320), (0, RATE_OF[i] // 50), (0,), (0,)) for i in pk_by_id}
-    dt = (np.int16, np.int16, np.int32, np.int32)
-    return [{i: np.stack(v) if v else np.zeros(shapes[i][k], dt[k]) for i, v in o.items()} for k, o in enumerate(out)]
-
-
-def _twin_decode_plain(twin, pk_by_id, num_bits):
-    """hop by hop through decode + resample(side="decoder"): {id: pcm16 [n][320]}, {id: pcm_ext [n][rate / 50]}"""
-    p16, ext = ({i: [] for i in pk_by_id} for _ in range(2))
-    for h in range(max((len(v) for v in pk_by_id.values()), default=0)):
-        ids = [i for i, v in pk_by_id.items() if h < len(v)]
-        x16 = twin.decode(np.stack([pk_by_id[i][h] for i in ids]), num_bits, ids)
-        for k, i in enumerate(ids):
-            p16[i].append(x16[k])
-            ext[i].append(x16[k] if RATE_OF[i] == 16000 else twin.resample(x16[k][None], 16000, RATE_OF[i], [i], side="decoder")[0])
-    return ({i: np.stack(v) if v else np.zeros((0, 320), np.int16) for i, v in p16.items()},
-            {i: np.stack(v) if v else np.zeros((0, RATE_OF[i] // 50), np.int16) for i, v in ext.items()})
-
-
-def _check_ext(where, got, spans, want_by_id):
-    """[F][960]: the rows of span s equal the twin's up to rate / 50 samples; everything else still holds the filler"""
-    untouched = np.ones(got.shape, bool)
-    for (i, first, n) in spans:
-        hop = RATE_OF[i] // 50
-        untouched[first:first + n, :hop] = False
-        diff = np.flatnonzero((got[first:first + n, :hop] != want_by_id[i]).any(axis=1)) if n else []
-        assert len(diff) == 0, f"{where}: stream {i} ({RATE_OF[i]} Hz) differs at hops {list(diff[:8])} ({len(diff)} of {n})"
-    assert (got[untouched] == FILL16).all(), f"{where}: samples behind a row's rate / 50, or rows outside every span, were written"
+_twin_decode = functools.partial(span_cases._twin_decode_rates, rate_of=RATE_OF)          # (twin, pk_by_id, pb_by_id)
+_twin_decode_plain = functools.partial(span_cases._twin_decode_plain, rate_of=RATE_OF)    # (twin, pk_by_id, num_bits)
+_check_ext = functools.partial(span_cases._check_ext, rate_of=RATE_OF)                    # (where, got, spans, want_by_id)
 
 
 def _rates_of(spans):

@@ -2,20 +2,18 @@
 the `_dev` form and read back the spans' own frames) at its corners: gaps between spans, a span of no frames, rows behind the
 last span, calls with nothing to do, and a large call behind a small one on the same context.  The C functions are called
 through ctx.L with the output arrays prefilled, so that a row the call must not write still holds the filler afterwards.  Every
-row of a span is compared BIT FOR BIT with the hop-by-hop calls on a twin context (the twin helpers of test_gpu_spans_ext.py
-and test_gpu_spans_dtx.py), computed once per rate and shared."""
-import os
-import sys
-
+row of a span is compared BIT FOR BIT with the hop-by-hop calls on a twin context (the twin helpers of
+tests/span_cases.py), computed once per rate and shared."""
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(__file__))
-import test_gpu_spans_dtx as dtx   # noqa: E402
-import test_gpu_spans_ext as ext   # noqa: E402
+import gpu_plumbing
+from gpu_plumbing import FILL, make_ctx
+from signals import _audio_dtx, _audio_ext
+from span_cases import _check_rows, _twin_decode_ext, _twin_encode_ext
 
 pytestmark = pytest.mark.gpu
-FILL = ext.FILL
+MAX_STREAMS = 96
 BITS = 120
 A, B, C = 5, 9, 2            # the spans' streams
 LANES = np.array([40, 41], np.int32)
@@ -37,7 +35,11 @@ def _buffer(rows_by_id, spans, frames):
 
 
 def _filled(frames, width, dtype):
-    return np.full((frames, width * np.dtype(dtype).itemsize), FILL, np.uint8).view(dtype)
+    return gpu_plumbing._filled(None, frames, width, dtype)
+
+
+def _ctx(rate):
+    return make_ctx(MAX_STREAMS, rate=rate)
 
 
 def _want(golden_dir, rate):
@@ -49,27 +51,27 @@ def _want(golden_dir, rate):
     W = codec.span_warmup_frames("encoder")
     assert W == codec.span_warmup_frames("decoder")
     spans, frames = _job(W)
-    twin = dtx._ctx(rate=rate)
+    twin = _ctx(rate=rate)
     ids = np.concatenate([[A, B, C], LANES]).astype(np.int32)
     w = dict(spans=spans, frames=frames, blobs={})
-    w["pcm"] = {i: ext._audio(golden_dir, n, rate, 300 + i) for (i, _, n) in spans}
+    w["pcm"] = {i: _audio_ext(golden_dir, n, rate, 300 + i) for (i, _, n) in spans}
     if rate == 16000:
         w["pk"] = {i: np.stack([twin.encode(h[None], BITS, [i])[0] for h in v]) if len(v) else np.zeros((0, BITS // 8), np.uint8)
                    for i, v in w["pcm"].items()}
     else:
-        w["pk"], _ = ext._twin_encode(twin, w["pcm"], rate, BITS)
+        w["pk"], _ = _twin_encode_ext(twin, w["pcm"], rate, BITS)
     w["blobs"]["encode"] = twin.export_streams(ids)
     if rate == 16000:
         w["out"] = {i: np.stack([twin.decode(p[None], BITS, [i])[0] for p in v]) if len(v) else np.zeros((0, 320), np.int16)
                     for i, v in w["pk"].items()}
     else:
-        w["out"], _ = ext._twin_decode(twin, w["pk"], rate, BITS)
+        w["out"], _ = _twin_decode_ext(twin, w["pk"], rate, BITS)
     w["blobs"]["decode"] = twin.export_streams(ids)
-    w["dtx_pcm"] = {i: dtx._audio(golden_dir, n, rate, 400 + i) for (i, _, n) in spans}
-    w["dtx_pk"], w["dtx_nb"], _ = dtx._twin_encode(twin, w["dtx_pcm"], rate, BITS)
+    w["dtx_pcm"] = {i: _audio_dtx(golden_dir, n, rate, 400 + i) for (i, _, n) in spans}
+    w["dtx_pk"], w["dtx_nb"], _ = _twin_encode_ext(twin, w["dtx_pcm"], rate, BITS, dtx=True)
     assert 5 <= (w["dtx_nb"][C] > 0).sum() <= len(w["dtx_nb"][C]) - 5, "the DTX input needs both kinds of hop"
     w["blobs"]["dtx"] = twin.export_streams(ids)
-    w["noise_pcm"] = {i: dtx._audio(golden_dir, n, 16000, 500 + i) for (i, _, n) in spans}
+    w["noise_pcm"] = {i: _audio_dtx(golden_dir, n, 16000, 500 + i) for (i, _, n) in spans}
     for side in ("encoder", "decoder"):
         w["noise_" + side] = {i: np.array([twin.noise_receive(h[None], [i], side=side)[0] for h in v], np.int32).reshape(-1, 1)
                               for i, v in w["noise_pcm"].items()}
@@ -81,17 +83,7 @@ def _want(golden_dir, rate):
 
 def _rows(where, got, spans, want_by_id, zero=None):
     """rows of the spans equal the twin's (zero[id]: those rows are zeros instead); every other row still holds the filler"""
-    covered = np.zeros(len(got), bool)
-    for (i, at, n) in spans:
-        covered[at:at + n] = True
-        if not n:
-            continue
-        rows, want = got[at:at + n].reshape(n, -1), want_by_id[i].reshape(n, -1)
-        z = np.zeros(n, bool) if zero is None else zero[i]
-        diff = np.flatnonzero((rows[~z] != want[~z]).any(axis=1))
-        assert len(diff) == 0, f"{where}: stream {i} differs at hops {list(diff[:8])} of {n}"
-        assert not rows[z].any(), f"{where}: stream {i}: rows of noise hops are not zeros"
-    assert (got[~covered].view(np.uint8) == FILL).all(), f"{where}: rows outside every span were written"
+    _check_rows(where, got, spans, want_by_id, None if zero is None else {i: ~z for i, z in zero.items()}, skipped=0)
 
 
 def _span_args(spans, lanes):
@@ -162,7 +154,7 @@ def _run(where, ctx, w, rate):
 def test_gaps_and_sentinels(golden_dir, rate):
     """Three streams, two lanes, a span of no frames, gaps in front of, between and behind the spans: rows outside the spans keep
     the filler, rows inside equal the hop-by-hop calls."""
-    ctx = dtx._ctx(rate=rate)
+    ctx = _ctx(rate=rate)
     _run(f"{rate} Hz", ctx, _want(golden_dir, rate), rate)
     ctx.close()
 
@@ -171,15 +163,15 @@ def test_gaps_and_sentinels(golden_dir, rate):
 def test_grow_after_small(golden_dir, rate):
     """One span of 3 frames and no lanes through every form, then the call of test_gaps_and_sentinels on the same context: the
     scratch of the span calls grows and the result is that of a fresh context."""
-    ctx = dtx._ctx(rate=rate)
+    ctx = _ctx(rate=rate)
     hop, nb, small = rate // 50, BITS // 8, [(SMALL, 0, 3)]
-    pcm = ext._audio(golden_dir, 3, rate, 7)
+    pcm = _audio_ext(golden_dir, 3, rate, 7)
     pk = np.zeros((3, nb), np.uint8)
     assert _encode(ctx, small, [], rate, pcm, pk) == 0, ctx.last_error()
     assert _decode(ctx, small, [], rate, pk, np.zeros((3, hop), np.int16)) == 0, ctx.last_error()
     assert _encode_dtx(ctx, small, [], rate, pcm, pk, np.zeros(3, np.int32)) == 0, ctx.last_error()
     for side in ("encoder", "decoder"):
-        assert _noise(ctx, small, side, ext._audio(golden_dir, 3, 16000, 8), np.zeros(3, np.int32)) == 0, ctx.last_error()
+        assert _noise(ctx, small, side, _audio_ext(golden_dir, 3, 16000, 8), np.zeros(3, np.int32)) == 0, ctx.last_error()
     _run(f"{rate} Hz behind a small call", ctx, _want(golden_dir, rate), rate)
     ctx.close()
 
@@ -190,10 +182,10 @@ def test_nothing_to_do(golden_dir):
     import torch
     import lyra_amd.codec as codec
     rate = 48000
-    ctx = dtx._ctx(rate=rate)
+    ctx = _ctx(rate=rate)
     dev = torch.device("cuda", 0)
     ids = np.concatenate([[A, B, C], LANES]).astype(np.int32)
-    x = ext._audio(golden_dir, 4, rate, 11)
+    x = _audio_ext(golden_dir, 4, rate, 11)
     for h in x:   # streams A and C are not in the reset state, on either side
         p = ctx.encode_dtx(ctx.resample(np.stack([h, h]), rate, 16000, [A, C], side="encoder"), BITS, [A, C])[0]
         ctx.resample(ctx.decode(p, BITS, [A, C]), 16000, rate, [A, C], side="decoder")
@@ -223,8 +215,8 @@ def test_nothing_to_do(golden_dir):
             assert b is None or (b.view(np.uint8) == FILL).all()
 
         def device(width, dtype):
-            return None if null else dtx._filled(dev, F, width, dtype)
-        d_nbytes = dtx._filled(dev, F, 1, np.int32)
+            return None if null else gpu_plumbing._filled(dev, F, width, dtype)
+        d_nbytes = gpu_plumbing._filled(dev, F, 1, np.int32)
         d_bufs = [device(320, np.int16), device(960, np.int16), device(nb, np.uint8), device(1, np.int32)]
         d16, d48, dpk, dflags = (None if t is None else t.data_ptr() for t in d_bufs)
         assert L.lyra_hip_encode_spans_dev(h, *a, d16, BITS, dpk) == 0, ctx.last_error()

@@ -5,15 +5,14 @@ against the reference model (RefLyraDecoder with cng_seed = seed of the FIRST co
 test_gpu_lossy_decode.py's Tally / CnReach bounds.  Refusal uses only blobs that tests/test_stream_state_cpu.py shows
 validate() rejects."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(__file__))
-from test_gpu_lossy_decode import CnReach, _speech                                    # noqa: E402
-from test_gpu_decode_samples import Device, Model, _packets                           # noqa: E402
-from test_gpu_mixed_bitrate import _gilbert                                           # noqa: E402
+import gpu_plumbing
+from gpu_plumbing import make_ctx
+from receiver_models import Device, Model, _model_packets as _packets
+from signals import _gilbert, _speech
 
 pytestmark = pytest.mark.gpu
 RATE, BITS, ENC_BYTES = 48000, 120, 15
@@ -22,24 +21,10 @@ R_E1, R_NOISE_D, R_RS_D, R_CNG = 1, 8, 10, 11
 
 
 def _ctx(max_streams, seed=None, mode="xnnpack"):
-    import lyra_amd
-    c = lyra_amd.LyraHip(device=0, max_streams=max_streams, requant=mode)
-    if seed is not None:
-        c.set_cng_seed(seed)
-    c.set_encoder_sample_rate(RATE)
-    return c
+    return make_ctx(max_streams, mode, RATE, seed)
 
 
-class SeededModel(Model):
-    """test_gpu_decode_samples.Model with the comfort-noise seed of a context that is not the default one"""
-
-    def __init__(self, oracle, rate, ids, seed):
-        self.seed = seed
-        super().__init__(oracle, rate, ids)
-
-    def reset(self, i):
-        self.decs[i] = self.M.RefLyraDecoder(self.oracle, self.rate, cng_seed=self.seed ^ i)
-        self.reach[i] = CnReach(self.rate)
+SeededModel = Model   # (oracle, rate, ids, seed): with the comfort-noise seed of a context that is not the default one
 
 
 def _enc_input(golden_dir, n, T):
@@ -82,8 +67,7 @@ class Rig:
 
 
 def _same(where, a, b):
-    for k, (x, y) in enumerate(zip(a, b)):
-        assert np.array_equal(x, y), f"{where}: output {k} differs in rows {np.flatnonzero((np.asarray(x) != np.asarray(y)).reshape(len(x), -1).any(axis=1)).tolist()}"
+    gpu_plumbing._same(a, b, where, names=None)
 
 
 def _loss_script(T1, T2, n, size):

@@ -3,15 +3,12 @@ product's own (slot sizes from tests/stream_state/blob_tool.cc compiled over str
 them), the set holds both sides of every 2^31 crossing, the witnesses are no probes, the last slot under the cap ends inside
 2^32 in every region, and the cap is the number lyra_hip_create's refusal prints."""
 import ctypes
-import os
 import re
-import sys
 
 import pytest
 
-sys.path.insert(0, os.path.dirname(__file__))
-import id_probes                                                                       # noqa: E402
-import state_bridge                                                                    # noqa: E402
+import id_probes
+import state_bridge
 
 # stage slots of a made-up layout: two that never reach 2^31 under the cap, one that hits it exactly, one that is no multiple
 # of 256, the widest; side slots narrower than the widest

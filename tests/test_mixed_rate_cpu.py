@@ -9,14 +9,14 @@ import subprocess
 import numpy as np
 import pytest
 
+from abi_loading import load_library
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import lyra_amd
-    lyra_amd.build_library()
-    return ctypes.CDLL(lyra_amd.library_path())
+    return load_library(raw=True)
 
 
 def test_rates_calls_are_exported(lib):

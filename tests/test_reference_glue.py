@@ -14,6 +14,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from receiver_models import CnReach, Tally
+from sessions import _run_session, _session
+from signals import _read_wav, _write_wav
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
@@ -133,27 +137,6 @@ SESSIONS = [(16000, 6000, False), (48000, 3200, False), (8000, 9200, False), (16
 BITS = {3200: 64, 6000: 120, 9200: 184}
 
 
-def _session(golden_dir, rate, bitrate, T=40, n=4):
-    from oracle import lyra_oracle
-    speech = np.load(os.path.join(golden_dir, "sample_wavs.npz"))["sample1_16kHz"]
-    hop = rate // 50
-    up = lyra_oracle.Resampler(16000, rate) if rate != 16000 else None
-    base = speech[:16000 * 2]
-    ext = np.concatenate([up.Resample(base[i:i + 320]) for i in range(0, base.size, 320)]) if up is not None else base
-    rng = np.random.default_rng(rate + bitrate)
-    s0 = ext[:T * hop]
-    s1 = s0.copy(); s1[10 * hop:25 * hop] = 0
-    s2 = np.clip(rng.normal(0, 500, T * hop), -32768, 32767).astype(np.int16)
-    s3 = np.concatenate([np.zeros(5 * hop, np.int16), ext[:(T - 5) * hop]])
-    pcm = np.stack([s.reshape(T, hop) for s in (s0, s1, s2, s3)], axis=1).astype(np.int16)     # [T][n][hop]
-    script = []
-    for t in range(T):
-        mask = "".join(["0" if 12 <= t < 21 else "1", "1", "0" if t % 7 == 3 else "1", "1"])
-        sizes = [hop] if t % 3 == 0 else ([hop // 4 + 3, hop - hop // 4 - 3] if t % 3 == 1 else [1, hop // 2, hop - hop // 2 - 1])
-        script.append((mask, sizes))
-    return pcm, script
-
-
 @pytest.mark.parametrize("rate,bitrate,dtx", SESSIONS)
 def test_codec_model_vs_reference_classes(ref, oracle_default, golden_dir, rate, bitrate, dtx):
     """oracle/lyra_codec_model.py (Python restatement) vs the reference's LyraEncoder / LyraDecoder over the same
@@ -164,7 +147,6 @@ def test_codec_model_vs_reference_classes(ref, oracle_default, golden_dir, rate,
     NoiseEstimator::Create its EXTERNAL sample rate (lyra_encoder.cc:82-85), which changes the estimator's time
     constants at 8 / 32 / 48 kHz; round 2's restatement, oracle and kernels all assumed 16 kHz."""
     from oracle import lyra_codec_model as M
-    from test_gpu_lossy_decode import CnReach, Tally
     bits = BITS[bitrate]
     pcm, script = _session(golden_dir, rate, bitrate)
     n = pcm.shape[1]
@@ -200,19 +182,6 @@ def test_reference_decoder_accepts_any_request_size(ref, oracle_default):
     assert d.DecodeSamples(0).size == 0
     assert d.DecodeSamples(5000).size == 5000           # pure concealment, many hops in one request
     assert not d.SetEncodedPacket(np.zeros(9, np.uint8))  # unsupported packet size
-
-
-def _write_wav(path, pcm, rate=16000):
-    import wave
-    with wave.open(str(path), "wb") as w:
-        w.setnchannels(1); w.setsampwidth(2); w.setframerate(rate)
-        w.writeframes(np.asarray(pcm, np.int16).tobytes())
-
-
-def _read_wav(path):
-    import wave
-    with wave.open(str(path), "rb") as w:
-        return np.frombuffer(w.readframes(w.getnframes()), np.int16), w.getframerate()
 
 
 def test_reference_file_codec_vs_model(ref, oracle_default, golden_dir, tmp_path):
@@ -320,8 +289,6 @@ def test_gpu_batch_twins_vs_reference_classes(ref, oracle_default, golden_dir, t
     within 1 LSB where device comfort noise (fp64 sin / cos / exp) goes in, 2 LSB at other rates where such a sample lies
     in the resampler's window.  The reference model beside each class says which samples those are."""
     from oracle import lyra_codec_model as M
-    from test_batch_codec_semantics import _run_session
-    from test_gpu_lossy_decode import CnReach, Tally
     bits = BITS[bitrate]
     pcm, script = _session(golden_dir, rate, bitrate)
     n = pcm.shape[1]
@@ -391,7 +358,6 @@ def test_gpu_batch_decoder_large_requests_vs_reference_class(ref, oracle_default
     """DecodeSamples with requests far beyond one hop (the reference's BufferedResampler / LyraDecoder accept any
     num_samples): several hops per request -- so most of what is played is concealment and comfort noise -- including
     requests of more than 960 internal samples, which the device resampler serves in chunks (lyra_hip_twin_fetch)."""
-    from test_batch_codec_semantics import _run_session
     bitrate, bits = 6000, 120
     pcm, _ = _session(golden_dir, rate, bitrate, T=14)
     n, hop = pcm.shape[1], rate // 50
@@ -425,7 +391,6 @@ def test_gpu_batch_twins_many_streams_random_loss_vs_reference_classes(ref, orac
     """192 streams, 24 ticks, every stream losing its packets independently (18 %, in bursts), odd request sizes: the
     rounds of BatchLyraDecoder's loop now hold large mixed groups (received / concealing / comfort noise / fading, hops
     starting and ending in different rounds) -- against 192 pairs of the reference's LyraEncoder / LyraDecoder."""
-    from test_batch_codec_semantics import _run_session
     rate, bitrate, bits = 16000, 9200, 184
     n, T, hop = 192, 24, 320
     speech = np.load(os.path.join(golden_dir, "sample_wavs.npz"))["sample1_16kHz"]

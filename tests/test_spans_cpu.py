@@ -15,6 +15,8 @@ import pytest
 
 from lyra_amd import codec
 
+from abi_loading import load_library
+
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 MEASURED = {"encoder": 23, "decoder": 25}   # last differing hop after a restart, CPU oracle, 140 hops of noise (the issue)
 N_HOPS = 84
@@ -23,9 +25,7 @@ RESTARTS = (26, 33, 41, 52)                 # >= W: the restarted stream begins 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.isfile(codec.library_path()):
-        codec.build_library()
-    return codec._load()
+    return load_library()
 
 
 def test_warmup_frames_cover_the_measured_restarts(lib):

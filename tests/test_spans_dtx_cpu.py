@@ -13,6 +13,8 @@ import pytest
 
 from lyra_amd import codec
 
+from abi_loading import load_library
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 NEW = {"lyra_hip_encode_spans_dtx_dev": 11, "lyra_hip_encode_spans_dtx": 10, "lyra_hip_noise_spans_dev": 6,
@@ -22,9 +24,7 @@ N_HOPS, BITS = 150, 64
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.isfile(codec.library_path()):
-        codec.build_library()
-    return codec._load()
+    return load_library()
 
 
 def test_header_ctypes_and_library_agree_on_the_new_symbols(lib):

@@ -18,6 +18,9 @@ import pytest
 
 from lyra_amd import codec
 
+from abi_loading import load_library
+from signals import _gilbert_ticks as _gilbert
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NEW = {"lyra_hip_decode_spans_lossy_dev": 13, "lyra_hip_decode_spans_lossy": 13, "lyra_hip_spans_lossy_plan": 19}
 MAX_STREAMS = 96
@@ -41,9 +44,7 @@ int main() {
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.isfile(codec.library_path()):
-        codec.build_library()
-    return codec._load()
+    return load_library()
 
 
 @pytest.fixture(scope="module")
@@ -126,15 +127,6 @@ def _check(tick, spans, rx_all, ctl_in, lanes, nbytes=15):
     chunks, steps = codec.spans_plan("decoder", compact, lanes, MAX_STREAMS)
     assert np.array_equal(got["chunks"], chunks) and got["n_steps"] == steps
     return got
-
-
-def _gilbert(rng, n):
-    p_loss, p_recover = rng.uniform(0.02, 0.5), rng.uniform(0.05, 0.9)
-    lost, out = rng.random() < 0.3, []
-    for _ in range(n):
-        lost = (rng.random() >= p_recover) if lost else (rng.random() < p_loss)
-        out.append(not lost)
-    return np.array(out, bool)
 
 
 def test_planner_equals_the_loop_over_lossy_tick_from_every_control_word(lib, tick):

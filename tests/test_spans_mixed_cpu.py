@@ -17,6 +17,9 @@ import pytest
 
 from lyra_amd import codec
 
+from abi_loading import _protos, load_library
+from signals import _gilbert_ticks as _gilbert
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NEW = {"lyra_hip_encode_spans_mixed_dev": 12, "lyra_hip_encode_spans_mixed": 11, "lyra_hip_decode_spans_lossy_mixed_dev": 12,
        "lyra_hip_decode_spans_lossy_mixed": 12, "lyra_hip_spans_lossy_plan_mixed": 18}
@@ -28,15 +31,7 @@ LISTS = ("gen_frames", "rx_frames", "cng_frames", "cng_versions", "versions", "i
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.isfile(codec.library_path()):
-        codec.build_library()
-    return codec._load()
-
-
-def _protos(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(lyra_hip_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", hdr, flags=re.S)}
+    return load_library()
 
 
 def test_header_second_table_and_library_agree_on_the_five_symbols(lib):
@@ -68,15 +63,6 @@ def test_header_second_table_and_library_agree_on_the_five_symbols(lib):
     assert len(all_protos) == 98, len(all_protos)   # (the parse of tests/test_abi_cpu.py)
     assert len(codec._SIGNATURES) == 88
     assert not set(NEW) & set(codec._SIGNATURES)
-
-
-def _gilbert(rng, n):
-    p_loss, p_recover = rng.uniform(0.02, 0.5), rng.uniform(0.05, 0.9)
-    lost, out = rng.random() < 0.3, []
-    for _ in range(n):
-        lost = (rng.random() >= p_recover) if lost else (rng.random() < p_loss)
-        out.append(not lost)
-    return np.array(out, bool)
 
 
 def _same_as_uniform(spans, pb, ctl_in, lanes):

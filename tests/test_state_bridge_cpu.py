@@ -2,16 +2,14 @@
 the tensor table covers the stage regions exactly, a fresh oracle stream becomes the product's reset blob, and
 oracle state -> blob -> oracle state is the identity at ring phases before, at and after every wrap-around (a dilation-9
 ring wraps after 9 hops, the phase word after 18)."""
-import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(__file__))
-import state_bridge                                                                    # noqa: E402
-from test_stream_state_cpu import _reset_blob, _verdicts                               # noqa: E402
+from oracle_states import directed_oracle_run
+import state_bridge
+from state_bridge import _reset_blob, _verdicts
 
 MODES = ["xnnpack", "exact", "gemmlowp_double", "builtin_mixed"]
 
@@ -173,7 +171,6 @@ def test_directed_run_meets_its_conditions_on_the_oracle(bridge, oracles, mode):
     """the oracle's half of tests/test_gpu_state_vs_oracle.py::test_directed_states_one_hop_at_a_time, which asserts on the
     reference alone: finite state and outputs, every int8 tap at both rails on hop 1, PCM at both rails -- and that the
     directed states are states the blob can hold (every int8 float is a code)"""
-    from test_gpu_state_vs_oracle import directed_oracle_run
     states0, pe, pd, _, _, per_hop, counts = directed_oracle_run(bridge, oracles[mode])
     assert len(counts) == 8 and all(lo > 0 and hi > 0 for lo, hi, _ in counts.values()), counts
     assert set(int(v) for v in pe) | set(int(v) for v in pd) >= {0, 17}     # both ends of the phase range are drawn

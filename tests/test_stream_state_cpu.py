@@ -11,18 +11,17 @@ import subprocess
 import numpy as np
 import pytest
 
+from abi_loading import load_library
+from state_bridge import _reset_blob, _verdicts, compile_tool
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-CSRC = os.path.join(ROOT, "lyra_amd", "csrc")
 MODE = 2   # LYRA_HIP_REQUANT_XNNPACK
 R_E1, R_E2, R_D0, R_D1, R_NOISE_E, R_NOISE_D, R_RS_E, R_RS_D, R_CNG = 1, 2, 3, 4, 7, 8, 9, 10, 11
 
 
 @pytest.fixture(scope="module")
 def tool(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("blob_tool") / "blob_tool")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I", CSRC,
-                           os.path.join(ROOT, "tests", "stream_state", "blob_tool.cc"), "-o", exe])
-    return exe
+    return compile_tool(tmp_path_factory.mktemp("blob_tool"))
 
 
 @pytest.fixture(scope="module")
@@ -32,21 +31,7 @@ def L(tool):
 
 @pytest.fixture(scope="module")
 def lib():
-    import lyra_amd
-    lyra_amd.build_library()
-    return ctypes.CDLL(lyra_amd.library_path())
-
-
-def _verdicts(tool, tmp_path, blobs, mode=MODE):
-    path = str(tmp_path / "blobs.bin")
-    np.ascontiguousarray(blobs, np.uint8).tofile(path)
-    return [int(x) for x in subprocess.check_output([tool, "validate", path, str(mode)]).split()]
-
-
-def _reset_blob(tool, tmp_path, mode=MODE):
-    path = str(tmp_path / "reset.bin")
-    subprocess.check_call([tool, "reset", path, str(mode)])
-    return np.fromfile(path, np.uint8)
+    return load_library(raw=True)
 
 
 def _region_off(L, r):

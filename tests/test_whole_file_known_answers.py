@@ -16,7 +16,8 @@ import numpy as np
 import pytest
 
 from oracle import lyra_oracle
-from oracle.logmel_np import LogMelExtractor
+
+from sessions import lsd_per_hop
 
 SHA = {  # mode -> bits -> sha256[:16] of the first 150 packets of sample1_16kHz.wav
     "exact": {64: "a460adeb4ac4f1c8", 120: "8ddf7e64edc74415", 184: "afe043bd95a159ca"},
@@ -39,16 +40,6 @@ def hops_of(golden_dir, name):
 
 def sha16(packets):
     return hashlib.sha256(np.ascontiguousarray(packets).tobytes()).hexdigest()[:16]
-
-
-def lsd_per_hop(pcm_in, pcm_out):
-    """lyra_integration_test.cc:101-142: 64-bin log-mel of both signals, 10 * sqrt(mean((a-b)^2))... per hop."""
-    e1, e2 = LogMelExtractor(num_mel=64), LogMelExtractor(num_mel=64)
-    out = []
-    for a, b in zip(pcm_in, pcm_out):
-        x, y = e1.extract(a), e2.extract(b)
-        out.append(10 * np.sqrt(((x - y) ** 2).sum() / 64))
-    return np.array(out)
 
 
 # ------------------------------------------------------------------------------------------------------------------
