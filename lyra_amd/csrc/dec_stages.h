@@ -364,9 +364,33 @@ constexpr int NTD1 = S1_THREADS;
 // Block 4 = bias + x[3] . W[5..9] is the carried tail.  A wave computes NTW of the 20 N tiles starting at tile0.
 // HB: LDS scratch of this wave (NTW x 4 x 64 floats): block 0 -- complete after pass 1 -- waits there for the epilogue
 // instead of in 4 NTW registers across pass 2 (at the 128-VGPR cap they spilled).
-template <int NTW>
+// The weights stream through a ring of PFB_T + 1 stages (lyra_dev.h gemm_f32_core PFB; the activations keep depth 1):
+// pass 1's first PFB_T chunks arrive in `pre` -- dec_s1_tconv_wpre, called in front of the barrier before the tconv, for
+// NP >= NTW tiles -- and pass 2's are requested before the rotate / park code between the passes.
+namespace {
+constexpr int PFB_T = PFB_DEC_S1 < 1 ? 1 : (PFB_DEC_S1 > 8 ? 8 : PFB_DEC_S1);   // a pass has 8 K chunks
+}
+template <int NP>
+struct TconvPre { f32x4 b[PFB_T][NP]; float bias[NP]; };
+// ntw (wave-uniform): how many of the NP tiles this wave computes
+template <int NP>
+__device__ __forceinline__ TconvPre<NP> dec_s1_tconv_wpre(const DecS1P& P, int tile0, int ntw) {
+  const int lane = threadIdx.x & 63;
+  const f32x4 LYRA_GLOBAL* wb = wave_uniform(P.up.w + tile0 * 16 * 64);
+  TconvPre<NP> pre;
+#pragma unroll
+  for (int j = 0; j < NP; ++j)
+    if (j < ntw) {
+#pragma unroll
+      for (int p = 0; p < PFB_T; ++p) pre.b[p][j] = wb[(j * 16 + p) * 64 + lane];
+      pre.bias[j] = as_global(P.up.b)[((tile0 + j) * 16 + (lane & 15)) & 63];
+    }
+  return pre;
+}
+template <int NTW, int NP>
 __device__ __forceinline__ void dec_s1_tconv(const float* XB, const float* SB, const DecS1P& P, const TileCtx& cx,
-                                             int b0, float* __restrict__ out1, int tile0, float* HB) {
+                                             int b0, float* __restrict__ out1, int tile0, float* HB, const TconvPre<NP>& pre) {
+  static_assert(NP >= NTW, "the prefetched ring covers this wave's tiles");
   const int lane = threadIdx.x & 63;
   const int m = lane & 15, q = lane >> 4;
   f32x4 acc[2][NTW];
@@ -376,13 +400,23 @@ __device__ __forceinline__ void dec_s1_tconv(const float* XB, const float* SB, c
   };
   const f32x4* wfrag = P.up.w + tile0 * 16 * 64;   // per N tile 16 K chunks: 0-7 taps 0..4, 8-15 taps 5..9
   {
-    f32x4 bias4[NTW];
+    f32x4 bias4[NTW], wb[PFB_T][NTW];
 #pragma unroll
     for (int j = 0; j < NTW; ++j) {
-      const float v = as_global(P.up.b)[((tile0 + j) * 16 + (lane & 15)) & 63];
+      const float v = pre.bias[j];
       bias4[j] = (f32x4){v, v, v, v};
+#pragma unroll
+      for (int p = 0; p < PFB_T; ++p) wb[p][j] = pre.b[p][j];
     }
-    gemm_f32_init<2, NTW, 8, 16>(XB, aoff, wfrag, bias4, acc);
+    gemm_f32_core<2, NTW, 8, 16, 2, 1, false, PFB_T>(XB, aoff, wfrag, acc, bias4, wb);
+  }
+  f32x4 wb2[PFB_T][NTW];   // pass 2's first chunks: in flight across the rotate / park code
+  {
+    const f32x4 LYRA_GLOBAL* w2 = wave_uniform(wfrag + 8 * 64);
+#pragma unroll
+    for (int p = 0; p < PFB_T; ++p)
+#pragma unroll
+      for (int j = 0; j < NTW; ++j) wb2[p][j] = w2[(j * 16 + p) * 64 + lane];
   }
   LYRA_TSTAMP(54);
   LYRA_WSTAMP(114);
@@ -399,7 +433,7 @@ __device__ __forceinline__ void dec_s1_tconv(const float* XB, const float* SB, c
       acc[1][j][e] = lo ? bb : biasb;              // blocks 3 | 4 (block 4 starts from the bare bias)
     }
   }
-  gemm_f32<2, NTW, 8, 16, false>(XB, aoff, wfrag + 8 * 64, acc);
+  gemm_f32_cont_pre<2, NTW, 8, 16, 1, PFB_T>(XB, aoff, wfrag + 8 * 64, wb2, acc);
   LYRA_TSTAMP(55);
   LYRA_WSTAMP(115);
   int lane_e = threadIdx.x & 63;
@@ -489,6 +523,17 @@ __device__ __forceinline__ void dec_s1_body(const DecS1P& P, const float* __rest
   resblocks128<SD1, NTD1>(XB, DB, PB, cx, P.dw, P.pw, P.cv, st::D_R1_0, st::D_R1_1, st::D_R1_2, H0);
   LYRA_TSTAMP(52);
   LYRA_WSTAMP(112);
+  // The warm-up loads returned long ago (loads return in order and later ones have been waited for): their tokens are
+  // consumed HERE, not at the end of the kernel: three registers less across the tconv, the kernel's register peak (that
+  // alone took the 12 B per lane of scratch to 8; the tconv's prefetched operands arriving as values took the rest).
+  l2_warm_sink(warm, state, B);
+  l2_warm_sink(warm_code, state, B);
+  // transposed conv k10/s5: 20 N tiles over the waves (5 each with 4 waves; 3,3,3,3,2,2,2,2 with 8); its first weight
+  // chunks and the bias are requested in front of the barrier that precedes it
+  constexpr int HEAD_TILES = NTD1 == 256 ? 5 : 3;
+  const bool head = NTD1 == 256 || wave < 4;
+  const int tile0 = NTD1 == 256 ? wave * 5 : (head ? wave * 3 : 12 + (wave - 4) * 2);
+  const auto up_pre = dec_s1_tconv_wpre<HEAD_TILES>(P, tile0, head ? HEAD_TILES : 2);
   for (int idx = tid; idx < 4 * SD1 * 32; idx += NTD1) {
     int p4 = idx & 31, rs = idx >> 5;
     f32x4* x = reinterpret_cast<f32x4*>(&XB[rs * CS1 + p4 * 4]);
@@ -497,20 +542,15 @@ __device__ __forceinline__ void dec_s1_body(const DecS1P& P, const float* __rest
   __syncthreads();
   LYRA_TSTAMP(53);
   LYRA_WSTAMP(113);
-  // transposed conv k10/s5: 20 N tiles over the waves (5 each with 4 waves; 3,3,3,3,2,2,2,2 with 8)
   // (DB and PB, 2 x 17 KB, are free once the residual blocks are done: the waves' head scratch, 20 KB in all, fits)
-  constexpr int HEAD_TILES = NTD1 == 256 ? 5 : 3;
   static_assert((NTD1 / 64) * HEAD_TILES * 256 <= 2 * 4 * SD1 * CS1, "head scratch fits into DB + PB");
   float* HB = DB + wave * (HEAD_TILES * 4 * 64);
-  if (NTD1 == 256) dec_s1_tconv<5>(XB, SB, P, cx, b0, out1, wave * 5, HB);
-  else if (wave < 4) dec_s1_tconv<3>(XB, SB, P, cx, b0, out1, wave * 3, HB);
-  else dec_s1_tconv<2>(XB, SB, P, cx, b0, out1, 12 + (wave - 4) * 2, HB);
+  if (head) dec_s1_tconv<HEAD_TILES>(XB, SB, P, cx, b0, out1, tile0, HB, up_pre);
+  else dec_s1_tconv<2>(XB, SB, P, cx, b0, out1, tile0, HB, up_pre);
   if (tid < SD1 && cx.valid(tid)) {   // this region's ring phase
     int ph = sphase[tid] + 1;
     *cx.at<int>(cx.soff(tid) + (uint32_t)(st::PHASE)) = ph >= st::PHASE_MOD ? 0 : ph;
   }
-  l2_warm_sink(warm, state, B);
-  l2_warm_sink(warm_code, state, B);
 }
 
 // =============================================================================================
@@ -570,7 +610,18 @@ __device__ __forceinline__ void dec_s2_body(const DecS2P& P, const float* __rest
     const f32x4 a4 = lrelu4(xr[i][0]);
     *reinterpret_cast<f32x4*>(&XB[(3 * SD2 + (wm * 5 + i) * 16 + m) * CS0 + wn * 16 + q * 4]) = a4;
   }
+  // the tconv's whole initial weight ring, requested in front of the barrier (xr is dead: its registers carry the ring)
+  constexpr int PFU = gemm_pf<2, 1>(), PFBU = PFB_DEC_S2 > PFU ? PFB_DEC_S2 : PFU;
+  WPre<1, PFBU> up_pre;
+  if (wave < 3 * SD2 / 4) {
+    const f32x4 LYRA_GLOBAL* ub = wave_uniform(P.up.w);
+#pragma unroll
+    for (int p = 0; p < PFBU; ++p) up_pre.b[p][0] = ub[p * 64 + lane];
+    const float bias = as_global(P.up.b)[0];
+    up_pre.init[0] = (f32x4){bias, bias, bias, bias};   // (one output channel: the splat is every phase's bias)
+  }
   __syncthreads();
+  LYRA_TSTAMP(63);
   // tconv k64/s16, polyphase: blocks b = 0..22 (+1 of padding), rows (b, s); K = 4 x 64 (newest input first: chunk
   // group g reads input block b - g = LDS row b + 3 - g); N = 16 phases; every chain starts from the bias.
   // 24*S rows = 6 M tiles per 4 streams: waves 0..(3 * S / 4 - 1) take two each.
@@ -580,9 +631,8 @@ __device__ __forceinline__ void dec_s2_body(const DecS2P& P, const float* __rest
       int R = (2 * wave + i) * 16 + m, b = R / SD2, s = R & (SD2 - 1);
       return ((b + 3 - (c >> 2)) * SD2 + s) * CS0 + (c & 3) * 16 + q * 4;
     };
-    const float bias = as_global(P.up.b)[0];
-    const f32x4 bias4[1] = {(f32x4){bias, bias, bias, bias}};
-    gemm_f32_init<2, 1, 16, 16, gemm_pf<2, 1>(), true>(XB, aoff, P.up.w, bias4, acc);   // (one output channel: the splat is every phase's bias)
+    gemm_f32_pre<2, 1, 16, 16, PFU, true, PFBU>(XB, aoff, P.up.w, up_pre, acc);
+    LYRA_TSTAMP(64);
     // row (b, s) = this lane's C column; its four values are phases 4q .. 4q + 3 = four CONSECUTIVE output samples
 #pragma unroll
     for (int i = 0; i < 2; ++i) {

@@ -8,7 +8,7 @@
 // fmaf chain == XNNPACK's micro-kernel order);
 // everything between two GEMMs (LeakyReLU, depthwise dilated conv, residual add, history update) is fused
 // around them in LDS/registers.  The stages are launched as kernels of their own (enc_kernels.hip: stage 0 with
-// 4 streams / 256 threads / 29 KB LDS, four tiles per CU; stage 1 with 8 streams / 512 threads / 35 KB, two per CU) or
+// 4 streams / 256 threads / 29 KB LDS, four tiles per CU; stage 1 with 8 streams / 512 threads / 60 KB, two per CU) or
 // back to back on one 8-stream / 512-thread tile by the per-side kernel (enc_side_kernel.hip).
 // Per stream and step the only HBM traffic is PCM in, history read/write and one small inter-stage activation.
 #ifndef LYRA_AMD_CSRC_ENC_STAGES_H_
@@ -129,6 +129,9 @@ __device__ __forceinline__ void enc_s0_body(const EncS0P& P, const int16_t* __re
     const f32x4 a4 = lrelu4(xr[i][0]);
     *reinterpret_cast<f32x4*>(&XB[(5 * S0 + (wm * 5 + i) * 16 + m) * CS0 + wn * 16 + q * 4]) = a4;
   }
+  // phase E's whole initial weight ring, requested in front of the barrier (xr is dead: its registers carry the ring)
+  constexpr int MTWE = (4 * S0) / 16, NTWE = 8 / NW0, PFE = gemm_pf<MTWE, NTWE>(), PFBE = PFB_ENC_S0 > PFE ? PFB_ENC_S0 : PFE;
+  const auto down_pre = gemm_f32_wprefetch<NTWE, 40, 40, PFBE, true>(P.down.w + (wave * NTWE) * 40 * 64, P.down.b, wave * NTWE * 16);
   __syncthreads();
   for (int idx = tid; idx < 5 * S0 * 16; idx += NT0) {
     int p4 = idx & 15, s = (idx >> 4) & (S0 - 1), j = (idx >> 4) / S0;
@@ -140,15 +143,14 @@ __device__ __forceinline__ void enc_s0_body(const EncS0P& P, const int16_t* __re
 
   // ---- E. conv k10/s5: [4*S rows] x K=640 x N=128 -----------------------------------------------
   {
-    constexpr int MTW = (4 * S0) / 16, NTW = 8 / NW0;
+    constexpr int MTW = MTWE, NTW = NTWE;
     f32x4 acc[MTW][NTW];
     auto aoff = [&](int i, int c) {
       int tap = c >> 2, c16 = c & 3;
       int R = i * 16 + m;
       return ((5 * (R / S0) + tap) * S0 + (R & (S0 - 1))) * CS0 + c16 * 16 + q * 4;
     };
-    gemm_f32_bias<MTW, NTW, 40, 40, gemm_pf<MTW, NTW>(), true>(XB, aoff, P.down.w + (wave * NTW) * 40 * 64, P.down.b,
-                                                               wave * NTW * 16, acc);
+    gemm_f32_pre<MTW, NTW, 40, 40, PFE, true, PFBE>(XB, aoff, P.down.w + (wave * NTW) * 40 * 64, down_pre, acc);
     LYRA_TSTAMP(5);
 #pragma unroll
     for (int j = 0; j < NTW; ++j) {   // row (tau, s) = this lane's C column, 4 consecutive physical channels: one 16-byte store
@@ -228,6 +230,13 @@ __device__ __forceinline__ void enc_s1_body(const EncS1P& P, const float* __rest
   resblocks128<S1, NT1>(XB + 2 * S1 * CS1, DB, PB, cx, P.dw, P.pw, P.cv, st::E_R1_0, st::E_R1_1, st::E_R1_2, H0);
 
   LYRA_TSTAMP(72);
+  // The warm-up loads returned long ago (loads return in order and later ones have been waited for): their tokens are
+  // consumed here, not at the end of the kernel, so that they do not ride through the closing conv's weight ring.
+  l2_warm_sink(warm, state, B);
+  l2_warm_sink(warm_code, state, B);
+  // the closing conv's whole initial weight ring, requested in front of the barrier that precedes it
+  constexpr int MTWD = (2 * S1) / 16, NTWD = 16 / NW1, PFD = gemm_pf<MTWD, NTWD>(), PFBD = PFB_ENC_S1 > PFD ? PFB_ENC_S1 : PFD;
+  const auto down_pre = gemm_f32_wprefetch<NTWD, 16, 16, PFBD>(P.down.w + (wave * NTWD) * 16 * 64, P.down.b, wave * NTWD * 16);
   for (int idx = tid; idx < 4 * S1 * 32; idx += NT1) {
     int p4 = idx & 31, rs = idx >> 5;
     f32x4* x = reinterpret_cast<f32x4*>(&XB[(2 * S1 + rs) * CS1 + p4 * 4]);
@@ -242,23 +251,28 @@ __device__ __forceinline__ void enc_s1_body(const EncS1P& P, const float* __rest
   }
 
   {  // conv k4/s2, 2 groups: per group [2*S rows] x K=256 x N=128; a wave's N tiles lie in one group
-    constexpr int MTW = (2 * S1) / 16, NTW = 16 / NW1;
+    constexpr int MTW = MTWD, NTW = NTWD;
     f32x4 acc[MTW][NTW];
     const int nt0 = wave * NTW, g = nt0 >> 3;
+    LYRA_TSTAMP(74);
     auto aoff = [&](int i, int c) {
       int tap = c >> 2, c16 = c & 3;
       int R = i * 16 + m;
       return ((2 * (R / S1) + tap) * S1 + (R & (S1 - 1))) * CS1 + g * 64 + c16 * 16 + q * 4;
     };
-    gemm_f32_bias<MTW, NTW, 16, 16, gemm_pf<MTW, NTW>()>(XB, aoff, P.down.w + nt0 * 16 * 64, P.down.b, nt0 * 16, acc);
+    gemm_f32_pre<MTW, NTW, 16, 16, PFD, false, PFBD>(XB, aoff, P.down.w + nt0 * 16 * 64, down_pre, acc);
+    LYRA_TSTAMP(75);
+    int lane_e = threadIdx.x & 63;   // the epilogue's address arithmetic starts HERE, not in registers held across the GEMM
+    asm volatile("" : "+v"(lane_e));
+    const int q_e = lane_e >> 4;
 #pragma unroll
     for (int j = 0; j < NTW; ++j) {
-      const int pc = at16((nt0 + j) * 16 + (lane & 15));
+      const int pc = at16((nt0 + j) * 16 + (lane_e & 15));
 #pragma unroll
       for (int i = 0; i < MTW; ++i)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          int R = i * 16 + q * 4 + e, tau = R / S1, s = R & (S1 - 1);
+          int R = i * 16 + q_e * 4 + e, tau = R / S1, s = R & (S1 - 1);
           if (valid(s)) *goff<float>(out1 + (size_t)b0 * 512, (uint32_t)(((s * 2 + tau) * 256 + pc) * 4)) = acc[i][j][e];
         }
     }
@@ -269,8 +283,6 @@ __device__ __forceinline__ void enc_s1_body(const EncS1P& P, const float* __rest
     int ph = sphase[tid] + 1;
     *(int LYRA_GLOBAL*)gat(soff(tid) + (uint32_t)st::PHASE) = ph >= st::PHASE_MOD ? 0 : ph;
   }
-  l2_warm_sink(warm, state, B);
-  l2_warm_sink(warm_code, state, B);
 }
 
 }  // namespace lyra

@@ -12,6 +12,24 @@ constexpr int S0_STREAMS = 4;     // streams per workgroup of the 64-channel sta
 constexpr int S1_THREADS = 512;   // threads per tile of the 128-channel stages: 8 waves, 4 per SIMD with two tiles per CU
                                   // (256 = the 4-wave layout)
 
+// ---- weight-ring depth (gemm_f32_core PFB) of the conv that closes each fp32 stage kernel -------
+// These convs stream their weights from L2 at 0.25 B per MAC while the kernel's tiles finish one after the other; the
+// depths come from the sweep in profiles/closing_convs_depth.txt (-D overrides: that sweep's builds).
+#ifndef LYRA_PFB_ENC_S0
+#define LYRA_PFB_ENC_S0 3
+#endif
+#ifndef LYRA_PFB_ENC_S1
+#define LYRA_PFB_ENC_S1 3
+#endif
+#ifndef LYRA_PFB_DEC_S1
+#define LYRA_PFB_DEC_S1 2
+#endif
+#ifndef LYRA_PFB_DEC_S2
+#define LYRA_PFB_DEC_S2 4
+#endif
+constexpr int PFB_ENC_S0 = LYRA_PFB_ENC_S0, PFB_ENC_S1 = LYRA_PFB_ENC_S1, PFB_DEC_S1 = LYRA_PFB_DEC_S1,
+              PFB_DEC_S2 = LYRA_PFB_DEC_S2;
+
 // ---- encoder ---------------------------------------------------------------------------------
 struct EncS0P { ConvF first; DwF dw[3]; ConvF pw[3]; ConvF cv[3]; ConvF down; WarmRange warm; };
 struct EncS1P { DwF dw[3]; ConvF pw[3]; ConvF cv[3]; ConvF down; WarmRange warm; };

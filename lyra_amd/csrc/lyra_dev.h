@@ -321,10 +321,15 @@ __device__ __forceinline__ WPre<NTW, PF> gemm_f32_wprefetch(const f32x4* bfrag_g
   return pre;
 }
 
-template <int MTW, int NTW, int KC, int KS, int INIT, int PF, bool SWAP = false, class AOff>
+// PFB: the depth of the WEIGHT stream alone (a ring of PFB + 1 stages of NTW fragments); the activation fragments keep PF.
+// A further stage of both costs (NTW + MTW) * 4 registers, a further weight stage NTW * 4 -- and it is the weights that come
+// from L2: the convs that close the fp32 stage kernels (M = 16 or 32 rows against K = 256 .. 640) stream 0.25 B of weights
+// per MAC, and PF chunks of their few MFMAs do not cover a loaded L2 round trip.  PFB = PF is the single-depth pipeline.
+template <int MTW, int NTW, int KC, int KS, int INIT, int PF, bool SWAP = false, int PFB = PF, class AOff>
 __device__ __forceinline__ void gemm_f32_core(const float* lds, AOff a_off, const f32x4* bfrag_generic,
                                               f32x4 (&acc)[MTW][NTW], const f32x4 (&init)[NTW],
                                               const f32x4 (*pre_b)[NTW] = nullptr) {
+  static_assert(PFB >= PF && PF >= 1, "the weight ring is at least as deep as the activation ring");
   const int lane = threadIdx.x & 63;
   const f32x4 LYRA_GLOBAL* bbase = wave_uniform(bfrag_generic);
   if (INIT == 2) {   // the splat lives in the LAST M tile's accumulator: the first MFMA of tile i reads it from there and
@@ -332,25 +337,33 @@ __device__ __forceinline__ void gemm_f32_core(const float* lds, AOff a_off, cons
 #pragma unroll
     for (int j = 0; j < NTW; ++j) acc[MTW - 1][j] = init[j];
   }
-  f32x4 bq[PF + 1][NTW], aq[PF + 1][MTW];
+  f32x4 bq[PFB + 1][NTW], aq[PF + 1][MTW];
 #pragma unroll
-  for (int p = 0; p < PF; ++p)
+  for (int p = 0; p < PFB; ++p)
     if (p < KC) {
 #pragma unroll
       for (int j = 0; j < NTW; ++j) bq[p][j] = pre_b ? pre_b[p][j] : bbase[(j * KS + p) * 64 + lane];
+      if (p < PF) {
 #pragma unroll
-      for (int i = 0; i < MTW; ++i) aq[p][i] = *reinterpret_cast<const f32x4*>(lds + a_off(i, p));
+        for (int i = 0; i < MTW; ++i) aq[p][i] = *reinterpret_cast<const f32x4*>(lds + a_off(i, p));
+      }
     }
 #pragma unroll
   for (int c = 0; c < KC; ++c) {
+    if (c + PFB < KC) {
+      const int sl = (c + PFB) % (PFB + 1);
+#pragma unroll
+      for (int j = 0; j < NTW; ++j) bq[sl][j] = bbase[(j * KS + (c + PFB)) * 64 + lane];
+    }
     if (c + PF < KC) {
       const int sl = (c + PF) % (PF + 1);
 #pragma unroll
-      for (int j = 0; j < NTW; ++j) bq[sl][j] = bbase[(j * KS + (c + PF)) * 64 + lane];
-#pragma unroll
       for (int i = 0; i < MTW; ++i) aq[sl][i] = *reinterpret_cast<const f32x4*>(lds + a_off(i, c + PF));
     }
-    const int cur = c % (PF + 1);
+    // A deeper weight ring only exists if the requests stay where they are written: left alone, the instruction scheduler
+    // sinks them towards their uses (fewer live registers, the depth gone).  Nothing crosses a chunk's request point.
+    if constexpr (PFB > PF) __builtin_amdgcn_sched_barrier(0);
+    const int cb = c % (PFB + 1), ca = c % (PF + 1);
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
@@ -359,8 +372,8 @@ __device__ __forceinline__ void gemm_f32_core(const float* lds, AOff a_off, cons
         for (int j = 0; j < NTW; ++j) {
           const bool first = c == 0 && kk == 0;
           const f32x4 cin = (first && INIT == 0) ? (f32x4){0.f, 0.f, 0.f, 0.f} : (first && INIT == 2) ? acc[MTW - 1][j] : acc[i][j];
-          acc[i][j] = SWAP ? __builtin_amdgcn_mfma_f32_16x16x4f32(bq[cur][j][kk], aq[cur][i][kk], cin, 0, 0, 0)
-                           : __builtin_amdgcn_mfma_f32_16x16x4f32(aq[cur][i][kk], bq[cur][j][kk], cin, 0, 0, 0);
+          acc[i][j] = SWAP ? __builtin_amdgcn_mfma_f32_16x16x4f32(bq[cb][j][kk], aq[ca][i][kk], cin, 0, 0, 0)
+                           : __builtin_amdgcn_mfma_f32_16x16x4f32(aq[ca][i][kk], bq[cb][j][kk], cin, 0, 0, 0);
         }
   }
 }
@@ -371,6 +384,13 @@ __device__ __forceinline__ void gemm_f32(const float* lds, AOff a_off, const f32
                                          f32x4 (&acc)[MTW][NTW]) {
   f32x4 none[NTW];
   gemm_f32_core<MTW, NTW, KC, KS, ZERO ? 0 : 1, PF>(lds, a_off, bfrag_generic, acc, none);
+}
+// a chain continued from an earlier GEMM (acc carries values in), its first PFB weight chunks requested earlier
+template <int MTW, int NTW, int KC, int KS, int PF, int PFB, class AOff>
+__device__ __forceinline__ void gemm_f32_cont_pre(const float* lds, AOff a_off, const f32x4* bfrag_generic,
+                                                  const f32x4 (&pre_b)[PFB][NTW], f32x4 (&acc)[MTW][NTW]) {
+  f32x4 none[NTW];
+  gemm_f32_core<MTW, NTW, KC, KS, 1, PF, false, PFB>(lds, a_off, bfrag_generic, acc, none, pre_b);
 }
 
 // The chains start from the bias (logical channel order; n0 = first output channel of the wave's first N tile):
@@ -394,12 +414,13 @@ __device__ __forceinline__ void gemm_f32_bias(const float* lds, AOff a_off, cons
   gemm_f32_core<MTW, NTW, KC, KS, 2, PF, SWAP>(lds, a_off, bfrag_generic, acc, init);
 }
 
-// ... with the first weight chunks and the bias splats requested earlier (gemm_f32_wprefetch with the same NTW, KC, KS, PF)
+// ... with the first weight chunks and the bias splats requested earlier (gemm_f32_wprefetch
+// with the same NTW, KC, KS and the weight depth PFB)
 template <int MTW, int NTW, int KC, int KS = KC,
-          int PF = (4 * MTW * NTW >= 16 ? 1 : (4 * MTW * NTW >= 8 ? 2 : 3)), bool SWAP = false, class AOff>
+          int PF = (4 * MTW * NTW >= 16 ? 1 : (4 * MTW * NTW >= 8 ? 2 : 3)), bool SWAP = false, int PFB = PF, class AOff>
 __device__ __forceinline__ void gemm_f32_pre(const float* lds, AOff a_off, const f32x4* bfrag_generic,
-                                             const WPre<NTW, PF>& pre, f32x4 (&acc)[MTW][NTW]) {
-  gemm_f32_core<MTW, NTW, KC, KS, 2, PF, SWAP>(lds, a_off, bfrag_generic, acc, pre.init, pre.b);
+                                             const WPre<NTW, PFB>& pre, f32x4 (&acc)[MTW][NTW]) {
+  gemm_f32_core<MTW, NTW, KC, KS, 2, PF, SWAP, PFB>(lds, a_off, bfrag_generic, acc, pre.init, pre.b);
 }
 template <int MTW, int NTW>
 constexpr int gemm_pf() { return 4 * MTW * NTW >= 16 ? 1 : (4 * MTW * NTW >= 8 ? 2 : 3); }
