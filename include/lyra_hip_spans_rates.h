@@ -35,8 +35,9 @@ extern "C" {
  *   kernels as its uniform twin.  LYRA_HIP_SUBBATCHES > 1 and lyra_hip_set_serial are supported.
  *   Any rate other than the four, a null sample_rates, a null or misaligned d_pcm16 / d_pcm_ext, and whatever the uniform twin
  *   refuses: LYRA_HIP_EINVAL before the first kernel, with no state changed and lyra_hip_rates_errors() unchanged.
- *   Device-buffer (`_dev`) forms only: a caller with host buffers stages them as the host-buffer forms of the uniform calls do.
- * Out of scope: host-buffer forms, a packed (unpadded) external-rate layout, request sizes other than one hop on spans. */
+ *   Device-buffer (`_dev`) forms on the padded layout only.  Host-buffer forms and a packed (unpadded) external-rate layout, which
+ *   takes a sixth of this one's memory at 8 kHz: lyra_hip_spans_packed.h, which includes this header.
+ * Out of scope: request sizes other than one hop on spans. */
 
 /* lyra_hip_encode_spans_mixed_dev with a rate per span.  num_bits HOST [frames] (a multiple of 4 in 4..184 on every span frame),
  * dtx, d_packets rows LYRA_HIP_MAX_PACKET_BYTES apart and the required d_packet_bytes: as there. */

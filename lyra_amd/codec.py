@@ -119,6 +119,22 @@ def spans_plan(side, spans, lane_ids, max_streams, lib=None):
     return chunks[:n], steps.value
 
 
+def spans_packed_layout(spans, sample_rates, lib=None):
+    """The back-to-back layout of the packed span calls (lyra_hip_spans_packed_layout; no GPU): (ext_offsets int64 [n_spans],
+    total samples).  Span s takes n_frames * sample_rates[s] / 50 samples from ext_offsets[s]; a span of no frames takes nothing.
+    LyraHipError for a rate that is none of 8000 / 16000 / 32000 / 48000 or a negative frame count."""
+    L = lib or _load()
+    sp = _spans(spans)
+    rates = np.ascontiguousarray(np.asarray(sample_rates, np.int32).reshape(-1))
+    if rates.size != sp.size:
+        raise LyraHipError(f"spans: sample_rates has {rates.size} entries for {sp.size} spans")
+    offsets = np.zeros(sp.size, np.int64)
+    total = L.lyra_hip_spans_packed_layout(sp.ctypes.data, sp.size, rates.ctypes.data, offsets.ctypes.data)
+    if total < 0:
+        raise LyraHipError("lyra_hip_spans_packed_layout: invalid spans or sample rates")
+    return offsets, int(total)
+
+
 SPAN_LOSSY_COUNTS_DTYPE = np.dtype([("n_gen", "<i8"), ("n_received", "<i8"), ("n_cng", "<i8"), ("n_versions", "<i8"),
                                     ("ctl_out", "<u4"), ("reserved", "<i4")], align=True)
 
@@ -255,6 +271,26 @@ def _signatures_spans_rates():
 _SIGNATURES_SPANS_RATES = _signatures_spans_rates()
 
 
+def _signatures_spans_packed():
+    """The same for include/lyra_hip_spans_packed.h (tests/test_spans_packed_cpu.py holds each entry to its prototype)."""
+    vp, ci, ll = C.c_void_p, C.c_int, C.c_longlong
+    spans = [vp, vp, ci, vp, ci]   # ctx, spans, n_spans, lane ids, n_lanes
+    table = {
+        "encode_spans_packed_dev": spans + [vp, ll, vp, vp, vp, vp, ci, vp, vp],
+        "decode_spans_lossy_packed_dev": spans + [vp, vp, vp, vp, vp, ll, vp, vp, vp],
+        "decode_spans_packed_dev": spans + [vp, ci, vp, vp, vp, ll, vp],
+        "encode_spans_packed": spans + [vp, ll, vp, vp, vp, ci, vp, vp],
+        "decode_spans_lossy_packed": spans + [vp, vp, vp, vp, vp, ll, vp, vp, vp],
+        "decode_spans_packed": spans + [vp, ci, vp, vp, vp, ll, vp],
+    }
+    table = {"lyra_hip_" + name: (ci, args) for name, args in table.items()}
+    table["lyra_hip_spans_packed_layout"] = (ll, [vp, ci, vp, vp])
+    return table
+
+
+_SIGNATURES_SPANS_PACKED = _signatures_spans_packed()
+
+
 def _signatures_encode_streams():
     """The same for include/lyra_hip_encode_streams.h (tests/test_encode_streams_cpu.py holds each entry to its prototype)."""
     vp, ci, cl = C.c_void_p, C.c_int, C.c_long
@@ -283,7 +319,7 @@ _SIGNATURES_DECODE_STREAMS = _signatures_decode_streams()
 
 def _load(path=None):
     """The C-ABI library (default: library_path()); a second path loads a build variant beside it (lyra_amd/variants/).
-    A library that lacks a function of _SIGNATURES, _SIGNATURES_SPANS_MIXED, _SIGNATURES_SPANS_RATES,
+    A library that lacks a function of _SIGNATURES, _SIGNATURES_SPANS_MIXED, _SIGNATURES_SPANS_RATES, _SIGNATURES_SPANS_PACKED,
     _SIGNATURES_ENCODE_STREAMS or _SIGNATURES_DECODE_STREAMS is refused."""
     path = os.path.abspath(path or library_path())
     if path in _libs:
@@ -305,6 +341,7 @@ def _load(path=None):
             pass
     L = C.CDLL(path)
     for name, (restype, argtypes) in (*_SIGNATURES.items(), *_SIGNATURES_SPANS_MIXED.items(), *_SIGNATURES_SPANS_RATES.items(),
+                                       *_SIGNATURES_SPANS_PACKED.items(),
                                        *_SIGNATURES_ENCODE_STREAMS.items(), *_SIGNATURES_DECODE_STREAMS.items()):
         fn = getattr(L, name, None)
         if fn is None:
@@ -1207,6 +1244,115 @@ class LyraHip:
         self._dev_call(self.L.lyra_hip_decode_spans_rates_dev, *a, self._p_packets(d_packets, F, packet_size(num_bits)), num_bits,
                        rates.ctypes.data, self._opt_dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"),
                        self._opt_dev_ptr(d_pcm_ext, "int16", (F, MAX_EXT_HOP), "external-rate pcm"))
+
+    # -- per-span sample rates on a packed external-rate buffer (include/lyra_hip_spans_packed.h) --------------------------------
+    spans_packed_layout = staticmethod(spans_packed_layout)
+
+    @staticmethod
+    def _span_offsets(ext_offsets, n_spans):
+        """ext_offsets (None: the back-to-back layout) -> (C argument, the array it points into)"""
+        if ext_offsets is None:
+            return None, None
+        off = np.ascontiguousarray(np.asarray(ext_offsets, np.int64).reshape(-1))
+        if off.size != n_spans:
+            raise LyraHipError(f"spans: ext_offsets has {off.size} entries for {n_spans} spans")
+        return off.ctypes.data, off
+
+    def encode_spans_packed_dev(self, spans, d_pcm_ext, sample_rates, d_pcm16, num_bits, d_packets, d_packet_bytes, lane_ids=(),
+                                dtx=False, ext_offsets=None):
+        """encode_spans_rates_dev on the packed layout: d_pcm_ext int16 [n_ext_samples] is flat, span s's frames lie back to back
+        from ext_offsets[s] (int64 [n_spans], multiples of 8; None: the layout of spans_packed_layout), sample_rates[s] / 50
+        samples each.  Every frame-major buffer -- d_pcm16 int16 [frames][320] (required), num_bits, d_packets uint8 [frames][23],
+        d_packet_bytes int32 [frames] -- is indexed by first_frame as ever.  Bit for bit encode_spans_rates_dev."""
+        F = d_pcm16.shape[0]
+        bits = self._span_packet_bytes(num_bits, F, "num_bits")
+        a, _held = self._span_args(spans, lane_ids, F)
+        rates = self._span_rates(sample_rates, a[1])
+        p_off, _off = self._span_offsets(ext_offsets, a[1])
+        n_ext = int(d_pcm_ext.numel())
+        self._dev_call(self.L.lyra_hip_encode_spans_packed_dev, *a,
+                       self._dev_ptr(d_pcm_ext, "int16", (n_ext,), "external-rate pcm"), n_ext, p_off, rates.ctypes.data,
+                       self._dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"), bits.ctypes.data, int(bool(dtx)),
+                       self._p_packets(d_packets, F, MAX_PACKET_BYTES),
+                       self._opt_dev_ptr(d_packet_bytes, "int32", (F,), "packet_bytes"))
+
+    def decode_spans_lossy_packed_dev(self, spans, d_packets, packet_bytes, sample_rates, d_pcm16, d_pcm_ext, lane_ids=(),
+                                      d_is_noise=None, d_is_comfort_noise=None, ext_offsets=None):
+        """decode_spans_lossy_rates_dev on the packed layout (see encode_spans_packed_dev): span s gets exactly n_frames *
+        sample_rates[s] / 50 samples from ext_offsets[s] of the flat d_pcm_ext, nothing else of it is written.  Blocks the host
+        once, at its start."""
+        F = d_packets.shape[0]
+        pb = self._span_packet_bytes(packet_bytes, F)
+        a, _held = self._span_args(spans, lane_ids, F)
+        rates = self._span_rates(sample_rates, a[1])
+        p_off, _off = self._span_offsets(ext_offsets, a[1])
+        n_ext = int(d_pcm_ext.numel())
+        self._dev_call(self.L.lyra_hip_decode_spans_lossy_packed_dev, *a, self._p_packets(d_packets, F, MAX_PACKET_BYTES),
+                       pb.ctypes.data, rates.ctypes.data, self._dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"),
+                       self._dev_ptr(d_pcm_ext, "int16", (n_ext,), "external-rate pcm"), n_ext, p_off,
+                       *self._p_noise_flags(d_is_noise, d_is_comfort_noise, F))
+
+    def decode_spans_packed_dev(self, spans, d_packets, num_bits, sample_rates, d_pcm16, d_pcm_ext, lane_ids=(), ext_offsets=None):
+        """decode_spans_rates_dev (no loss, one num_bits) on the packed layout.  Enqueues and does not synchronise."""
+        F = d_packets.shape[0]
+        a, _held = self._span_args(spans, lane_ids, F)
+        rates = self._span_rates(sample_rates, a[1])
+        p_off, _off = self._span_offsets(ext_offsets, a[1])
+        n_ext = int(d_pcm_ext.numel())
+        self._dev_call(self.L.lyra_hip_decode_spans_packed_dev, *a, self._p_packets(d_packets, F, packet_size(num_bits)), num_bits,
+                       rates.ctypes.data, self._dev_ptr(d_pcm16, "int16", (F, HOP), "16 kHz pcm"),
+                       self._dev_ptr(d_pcm_ext, "int16", (n_ext,), "external-rate pcm"), n_ext, p_off)
+
+    def encode_spans_packed(self, spans, pcm_ext, sample_rates, num_bits, lane_ids=(), dtx=False, ext_offsets=None):
+        """encode_spans_packed_dev from host arrays: pcm_ext int16 [n_ext_samples] flat, num_bits int32 [frames].  Uploads exactly
+        the spans' samples.  Returns (packets uint8 [frames][23], packet_bytes int32 [frames]); bytes past a row's size, rows of
+        noise frames and rows outside every span are 0."""
+        pcm_ext = _np(pcm_ext, np.int16, (-1,))
+        bits = np.ascontiguousarray(np.asarray(num_bits, np.int32).reshape(-1))
+        F = bits.size
+        out = np.zeros((F, MAX_PACKET_BYTES), np.uint8)
+        nbytes = np.zeros(F, np.int32)
+        a, _held = self._span_args(spans, lane_ids, F)
+        rates = self._span_rates(sample_rates, a[1])
+        p_off, _off = self._span_offsets(ext_offsets, a[1])
+        self._chk(self.L.lyra_hip_encode_spans_packed(self.h, *a, pcm_ext.ctypes.data, pcm_ext.size, p_off, rates.ctypes.data,
+                                                      bits.ctypes.data, int(bool(dtx)), out.ctypes.data, nbytes.ctypes.data))
+        return out, nbytes
+
+    def decode_spans_lossy_packed(self, spans, packets, packet_bytes, sample_rates, n_ext_samples=None, lane_ids=(),
+                                  ext_offsets=None):
+        """decode_spans_lossy_packed_dev from host arrays: packets uint8 [frames][23], packet_bytes int32 [frames] in {0, 8, 15,
+        23}.  n_ext_samples: the length of the flat output (None: that of the back-to-back layout).  Returns (pcm16 int16
+        [frames][320], pcm_ext int16 [n_ext_samples], is_noise, is_comfort_noise int32 [frames]); everything outside the spans is 0."""
+        packets = _np(packets, np.uint8, (-1, MAX_PACKET_BYTES))
+        F = packets.shape[0]
+        pb = self._span_packet_bytes(packet_bytes, F)
+        a, _held = self._span_args(spans, lane_ids, F)
+        rates = self._span_rates(sample_rates, a[1])
+        p_off, _off = self._span_offsets(ext_offsets, a[1])
+        if n_ext_samples is None:
+            n_ext_samples = spans_packed_layout(_held[0], rates, self.L)[1]
+        pcm16, ext = np.zeros((F, HOP), np.int16), np.zeros(int(n_ext_samples), np.int16)
+        is_noise, is_cn = np.zeros(F, np.int32), np.zeros(F, np.int32)
+        self._chk(self.L.lyra_hip_decode_spans_lossy_packed(self.h, *a, packets.ctypes.data, pb.ctypes.data, rates.ctypes.data,
+                                                            pcm16.ctypes.data, ext.ctypes.data, ext.size, p_off,
+                                                            is_noise.ctypes.data, is_cn.ctypes.data))
+        return pcm16, ext, is_noise, is_cn
+
+    def decode_spans_packed(self, spans, packets, num_bits, sample_rates, n_ext_samples=None, lane_ids=(), ext_offsets=None):
+        """decode_spans_packed_dev from host arrays: packets uint8 [frames][bytes of num_bits].  Returns (pcm16 int16
+        [frames][320], pcm_ext int16 [n_ext_samples])."""
+        packets = _np(packets, np.uint8, (-1, packet_size(num_bits)))
+        F = packets.shape[0]
+        a, _held = self._span_args(spans, lane_ids, F)
+        rates = self._span_rates(sample_rates, a[1])
+        p_off, _off = self._span_offsets(ext_offsets, a[1])
+        if n_ext_samples is None:
+            n_ext_samples = spans_packed_layout(_held[0], rates, self.L)[1]
+        pcm16, ext = np.zeros((F, HOP), np.int16), np.zeros(int(n_ext_samples), np.int16)
+        self._chk(self.L.lyra_hip_decode_spans_packed(self.h, *a, packets.ctypes.data, num_bits, rates.ctypes.data,
+                                                      pcm16.ctypes.data, ext.ctypes.data, ext.size, p_off))
+        return pcm16, ext
 
     def noise_receive_dev(self, d_ids, d_pcm, d_is_noise, side="decoder"):
         """NoiseEstimator::ReceiveSamples on device buffers: pcm int16 [B][320] -> is_noise int32 [B]."""

@@ -188,7 +188,7 @@ struct lyra_hip_ctx {
   // optional per-kernel timing with HIP events on the launching stream (bench.py roofline leg)
   unsigned profiling = 0;  // bit i set: bracket launches of kernel i
   int prof_every = 1;      // ... every prof_every-th launch of it (lyra_hip_profile_sample)
-  long prof_seen[16] = {};
+  long prof_seen[16] = {};   // (K_COUNT <= 16)
   struct Span { int kid; hipEvent_t a, b; };
   std::vector<Span> spans;
   std::vector<hipEvent_t> event_pool;
@@ -365,11 +365,12 @@ int code_warm_bytes(const char* kernel) {
 }
 
 enum { K_ENC_S0, K_ENC_S1, K_ENC_S2, K_RVQ_ENC, K_RVQ_DEC, K_DEC_S0, K_DEC_S1, K_DEC_S2, K_LOGMEL, K_NOISE, K_RESAMPLE,
-       K_CNG, K_ENC_SIDE, K_DEC_SIDE, K_COUNT };
+       K_CNG, K_ENC_SIDE, K_DEC_SIDE, K_SPAN_RS_RATES, K_SPAN_RS_PACKED, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"enc_s0_kernel", "enc_s1_kernel", "enc_s2_kernel", "rvq_encode_kernel",
                                            "rvq_decode_kernel", "dec_s0_kernel", "dec_s1_kernel", "dec_s2_kernel",
                                            "logmel_kernel", "logmel_noise_kernel", "resample_kernel", "cng_kernel",
-                                           "enc_side_kernel", "dec_side_kernel"};
+                                           "enc_side_kernel", "dec_side_kernel", "span_resample_rates_kernel",
+                                           "span_resample_packed_kernel"};
 
 hipEvent_t take_event(lyra_hip_ctx* c) {
   if (!c->event_pool.empty()) { hipEvent_t e = c->event_pool.back(); c->event_pool.pop_back(); return e; }
@@ -2089,3 +2090,4 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
 #include "spans_lossy_api.inc"
 #include "spans_mixed_api.inc"
 #include "spans_rates_api.inc"
+#include "spans_packed_api.inc"

@@ -385,4 +385,11 @@ __global__ void span_noise_scan_rates_kernel(const NoiseP* np_tab, const SpanDtx
                                              uint8_t* state, const float* mel, int32_t* flag_out, int v_noise, int v_active,
                                              long long* map, int32_t* counts);
 
+// ---- per-span sample rates on a packed external-rate buffer (spans_packed_kernels.hip; include/lyra_hip_spans_packed.h) --------
+// span_resample_rates_kernel with the external-rate side one flat array: SpanRsRow::pad[1] holds the span's base in units of 8
+// samples, frame f of the span lies at pad[1] * 8 + f * (rate / 50); the 16 kHz side stays [frames][320] by buffer frame.
+// dir 0: in = external rate, out = 16 kHz; dir 1 the reverse.  grid, block and LDS as span_resample_rates_kernel.
+__global__ void span_resample_packed_kernel(const ResampleP* tab, int dir, const SpanRsRow* rows, int n_rows, uint8_t* state,
+                                            const int16_t* in, int16_t* out);
+
 }  // namespace lyra

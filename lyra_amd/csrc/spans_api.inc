@@ -180,6 +180,8 @@ struct SpanExt {
   int rate = 16000;
   int16_t* d_pcm16 = nullptr;   // [frames][320], the caller's: resampled input (encode) / the steps' output (decode)
   const int32_t* rates = nullptr;
+  const long long* base = nullptr;   // with rates (spans_packed_api.inc): the external-rate buffer is flat, HOST [n_spans] = each
+                                     // span's first sample, checked by the caller (spans_packed_plan.h); n_ext() is not used
   int n_ext() const { return rates ? (int)LYRA_HIP_MAX_EXT_HOP : rate / 50; }   // samples between rows of the external-rate buffer
   bool on() const { return rates || rate != 16000; }
 };
@@ -193,7 +195,8 @@ struct SpanPass {
   long long wgs = 0, frames = 0;  // workgroups and frames of all rows
 };
 template <class Row>
-SpanPass span_pass_rows(const lyra_hip_span* spans, int n_spans, Row* rows, const int32_t* rates = nullptr) {
+SpanPass span_pass_rows(const lyra_hip_span* spans, int n_spans, Row* rows, const int32_t* rates = nullptr,
+                        const long long* base = nullptr) {
   constexpr bool dtx = std::is_same<Row, SpanDtxRow>::value;
   SpanPass p;
   for (int s = 0; s < n_spans; ++s) {
@@ -201,7 +204,10 @@ SpanPass span_pass_rows(const lyra_hip_span* spans, int n_spans, Row* rows, cons
     if (rows) {
       rows[p.n] = Row{spans[s].first_frame, spans[s].n_frames, spans[s].stream_id, (int32_t)p.wgs};
       if constexpr (dtx) rows[p.n].region = p.frames;
-      else rows[p.n].pad[0] = rates ? rates[s] : 0;
+      else {
+        rows[p.n].pad[0] = rates ? rates[s] : 0;
+        rows[p.n].pad[1] = base ? (int32_t)(base[s] / 8) : 0;   // (packed: span_resample_packed_kernel)
+      }
     }
     ++p.n;
     p.wgs += dtx ? (spans[s].n_frames + 1) / 2 : (spans[s].n_frames + 3) / 4;
@@ -230,7 +236,16 @@ int launch_span_resample(lyra_hip_ctx* c, bool enc, hipStream_t st_, const SpanR
     if ((rc = wait_noise_stream(c))) return rc;
     c->rs_sn_pending = false;
   }
+  if (X.base) {   // the flat external-rate buffer: the rows carry their bases too
+    ProfScope ps(c, K_SPAN_RS_PACKED, st_);
+    hipLaunchKernelGGL(span_resample_packed_kernel, dim3((unsigned)wgs), dim3(256), resample_rates_lds_bytes(), st_,
+                       (const ResampleP*)c->d_rs_tab, enc ? 0 : 1, d_rows, n_rows, c->sm.base[enc ? st::R_RS_E : st::R_RS_D], d_in,
+                       d_out);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
   if (X.rates) {
+    ProfScope ps(c, K_SPAN_RS_RATES, st_);
     hipLaunchKernelGGL(span_resample_rates_kernel, dim3((unsigned)wgs), dim3(256), resample_rates_lds_bytes(), st_,
                        (const ResampleP*)c->d_rs_tab, enc ? 0 : 1, d_rows, n_rows, c->sm.base[enc ? st::R_RS_E : st::R_RS_D], d_in,
                        enc ? X.n_ext() : 320, d_out, enc ? 320 : X.n_ext());
@@ -461,7 +476,7 @@ int spans_call_dev(lyra_hip_ctx* c, int side, const lyra_hip_span* spans, int n_
   if (rows && (rc = ensure_scratch(c, rows))) return rc;   // the stage kernels' own boundary buffers
   span_fill_rows(P, spans, lane_ids, n_lanes, S.h_rows);
   const int rs0 = rows + n_lanes;   // the resampler's rows lie behind the lanes' reset rows
-  if (rs.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(S.h_rows + rs0), X.rates);
+  if (rs.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(S.h_rows + rs0), X.rates, X.base);
   if ((rc = span_side_begin(c, side))) return rc;
   if ((rc = span_upload_rows(c, S, st_, 0, rs0 + rs.n))) return rc;
   const SpanRsRow* d_rs_rows = reinterpret_cast<const SpanRsRow*>(S.d_rows + rs0);
@@ -559,13 +574,14 @@ int launch_span_noise(lyra_hip_ctx* c, int side, hipStream_t st_, SpanSide& S, c
 //   span_rates  null: every span at sample_rate_hz.  Else a HOST array [n_spans], a rate per span (spans_rates_api.inc;
 //               sample_rate_hz is not read): d_pcm_ext rows are MAX_EXT_HOP apart, d_pcm16 is required, and with dtx each span's
 //               estimator is that of its own rate, whatever lyra_hip_set_encoder_sample_rate says.
+//   ext_base    with span_rates (spans_packed_api.inc): d_pcm_ext is flat, HOST [n_spans] = each span's first sample.
 int span_lossy_ensure(lyra_hip_ctx* c, SpanSide& S, hipStream_t st_, size_t list_bytes, size_t snap_floats, int n_ctl);   // spans_lossy_api.inc
 int encode_spans_planned_dev(lyra_hip_ctx* c, const char* what, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids,
                              int n_lanes, const int16_t* d_pcm_ext, int sample_rate_hz, int16_t* d_pcm16, int num_bits,
                              const int32_t* frame_bits, bool dtx, uint8_t* d_packets, int32_t* d_packet_bytes,
-                             const int32_t* span_rates = nullptr) {
+                             const int32_t* span_rates = nullptr, const long long* ext_base = nullptr) {
   const int rate = span_rates ? 16000 : sample_rate_hz;
-  const SpanExt X{rate, span_rates || rate != 16000 ? d_pcm16 : nullptr, span_rates};
+  const SpanExt X{rate, span_rates || rate != 16000 ? d_pcm16 : nullptr, span_rates, span_rates ? ext_base : nullptr};
   SpanPlan dry;   // ids, lanes and frame ranges: the planner's rules, on the spans as given
   int rc = span_check(c, what, sp::SIDE_ENC, frame_bits ? nullptr : &num_bits, spans, n_spans, lane_ids, n_lanes, d_pcm_ext,
                       d_packets, X, &dry);
@@ -606,7 +622,7 @@ int encode_spans_planned_dev(lyra_hip_ctx* c, const char* what, const lyra_hip_s
   // upload 1, behind the batch rows' place: the lanes' reset rows, the resampler's rows, the estimator's rows
   SpanRow* h_fix = S.h_rows + rows_max;
   for (int l = 0; l < n_lanes; ++l) h_fix[l] = SpanRow{lane_ids[l], 0, 0, -1, 0, 0, 0};
-  if (rs.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(h_fix + n_lanes), span_rates);
+  if (rs.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(h_fix + n_lanes), span_rates, X.base);
   if (dx.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanDtxRow*>(h_fix + n_lanes + rs.n));
   const SpanRow* d_fix = S.d_rows + rows_max;
   const SpanRsRow* d_rs_rows = reinterpret_cast<const SpanRsRow*>(d_fix + n_lanes);

@@ -86,14 +86,16 @@ int spans_lossy_plan_sized(const lyra_hip_span* spans, int n_spans, const int32_
 // read, a packet has any size of the codec (8 / 15 / 23, chosen per frame), packet rows are MAX_PACKET_BYTES apart, and the list
 // uploaded as gen_received holds every tick's size, from which the steps' gather hands it to rvq_decode_mixed_kernel row by row.
 // span_rates (spans_rates_api.inc): a HOST array [n_spans], a rate per span; sample_rate_hz is not read, d_pcm_ext rows are
-// MAX_EXT_HOP apart and required, and the output resampler is the per-row one.
+// MAX_EXT_HOP apart and required, and the output resampler is the per-row one.  ext_base (spans_packed_api.inc): with
+// span_rates, d_pcm_ext is flat and HOST [n_spans] holds each span's first sample.
 int decode_spans_lossy_sized_dev(lyra_hip_ctx* c, const char* what, const lyra_hip_span* spans, int n_spans, const int32_t* lane_ids,
                                  int n_lanes, const uint8_t* d_packets, const int32_t* packet_bytes, int num_bits, bool mixed,
                                  int sample_rate_hz, int16_t* d_pcm16, int16_t* d_pcm_ext, int32_t* d_is_noise,
-                                 int32_t* d_is_comfort_noise, const int32_t* span_rates = nullptr) {
+                                 int32_t* d_is_comfort_noise, const int32_t* span_rates = nullptr,
+                                 const long long* ext_base = nullptr) {
   const int rate = span_rates ? 16000 : sample_rate_hz;
   const bool ext = span_rates || rate != 16000;
-  const SpanExt X{rate, ext ? d_pcm16 : nullptr, span_rates};
+  const SpanExt X{rate, ext ? d_pcm16 : nullptr, span_rates, span_rates ? ext_base : nullptr};
   SpanPlan dry;   // ids, lanes and frame ranges: the planner's rules, on the spans as given
   int rc = span_check(c, what, sp::SIDE_DEC, mixed ? nullptr : &num_bits, spans, n_spans, lane_ids, n_lanes,
                       ext ? d_pcm_ext : d_pcm16, d_packets, X, &dry);
@@ -176,7 +178,7 @@ int decode_spans_lossy_sized_dev(lyra_hip_ctx* c, const char* what, const lyra_h
     span_fill_rows(P, reinterpret_cast<const lyra_hip_span*>(compact.data()), lane_ids, 0, S.h_rows);
     SpanRow* h_fix = S.h_rows + rows_max;
     for (int l = 0; l < n_lanes; ++l) h_fix[l] = SpanRow{lane_ids[l], 0, 0, -1, 0, 0, 0};
-    if (rs.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(h_fix + n_lanes), span_rates);
+    if (rs.n) span_pass_rows(spans, n_spans, reinterpret_cast<SpanRsRow*>(h_fix + n_lanes), span_rates, X.base);
     SpanLossyRow* h_lrows = reinterpret_cast<SpanLossyRow*>(h_fix + n_lanes + rs.n);
     long long* h_gen = reinterpret_cast<long long*>(S.h_lists + o_gen);
     SpanLossyRx* h_rx = reinterpret_cast<SpanLossyRx*>(S.h_lists + o_rx);

@@ -9,6 +9,7 @@
 
 #include "../../include/lyra_hip.h"
 #include "../../include/lyra_hip_spans_mixed.h"
+#include "../../include/lyra_hip_spans_packed.h"
 #include "glog/logging.h"
 #include "lyra_batch_codec.h"
 
@@ -24,6 +25,9 @@
 #pragma weak lyra_hip_decode_spans_lossy
 #pragma weak lyra_hip_encode_spans_mixed
 #pragma weak lyra_hip_decode_spans_lossy_mixed
+#pragma weak lyra_hip_encode_spans_packed
+#pragma weak lyra_hip_decode_spans_lossy_packed
+#pragma weak lyra_hip_decode_spans_packed
 
 namespace chromemedia {
 namespace codec {
@@ -308,26 +312,31 @@ bool DecodeFeaturesBatch(const std::vector<std::vector<uint8_t>>& packet_streams
 
 namespace {
 
-// Frame-major concatenation of the streams' whole rows (row_size units each) + one span per stream; the lanes are the ids
-// behind the files'.  Lanes are capped so that a lane chunk is at least as long as its warm-up (work inflation <= 2).
+// Concatenation of the streams' whole rows (row_sizes[i] units each for stream i) + one span per stream; the lanes are the
+// ids behind the files'.  Lanes are capped so that a lane chunk is at least as long as its warm-up (work inflation <= 2).
 struct SpanJob {
   std::vector<lyra_hip_span> spans;
   std::vector<int32_t> lanes;
   int64_t frames = 0;
 };
 template <class T>
-SpanJob MakeSpanJob(const std::vector<std::vector<T>>& streams, size_t row_size, int side, int num_lanes, std::vector<T>* rows) {
+SpanJob MakeSpanJob(const std::vector<std::vector<T>>& streams, const std::vector<size_t>& row_sizes, int side, int num_lanes,
+                    std::vector<T>* rows) {
   SpanJob job;
   for (size_t i = 0; i < streams.size(); ++i) {
-    const int64_t n = (int64_t)(streams[i].size() / row_size);
+    const int64_t n = (int64_t)(streams[i].size() / row_sizes[i]);
     job.spans.push_back({(int32_t)i, job.frames, n});
-    rows->insert(rows->end(), streams[i].begin(), streams[i].begin() + n * row_size);
+    rows->insert(rows->end(), streams[i].begin(), streams[i].begin() + n * row_sizes[i]);
     job.frames += n;
   }
   const int64_t worth = job.frames / (2 * lyra_hip_span_warmup_frames(side));
   const int n_lanes = (int)std::max<int64_t>(0, std::min<int64_t>(num_lanes, worth));
   for (int l = 0; l < n_lanes; ++l) job.lanes.push_back((int32_t)streams.size() + l);
   return job;
+}
+template <class T>
+SpanJob MakeSpanJob(const std::vector<std::vector<T>>& streams, size_t row_size, int side, int num_lanes, std::vector<T>* rows) {
+  return MakeSpanJob(streams, std::vector<size_t>(streams.size(), row_size), side, num_lanes, rows);
 }
 bool HaveSpanCalls(int sample_rate_hz) {
   if (!(lyra_hip_encode_spans && lyra_hip_decode_spans && lyra_hip_span_warmup_frames)) {
@@ -590,6 +599,188 @@ bool DecodeFeaturesTimeParallel(const std::vector<std::vector<uint8_t>>& packet_
                                 const ghc::filesystem::path& model_path, std::vector<std::vector<int16_t>>* decoded_audio,
                                 int num_lanes, int device) {
   return DecodeSpansLossy(packet_streams, packet_sizes, 0, sample_rate_hz, model_path, decoded_audio, num_lanes, device);
+}
+
+// ---- files of any rate side by side (include/lyra_hip_spans_packed.h) -----------------------------------------------------------
+namespace {
+bool HavePackedSpanCalls() {
+  if (lyra_hip_encode_spans_packed && lyra_hip_decode_spans_lossy_packed && lyra_hip_decode_spans_packed &&
+      lyra_hip_span_warmup_frames)
+    return true;
+  LOG(ERROR) << "This build of the lyra_hip library has no packed per-rate span calls.";
+  return false;
+}
+bool CheckRates(const std::vector<int>& sample_rates_hz, size_t n) {
+  if (sample_rates_hz.size() != n) { LOG(ERROR) << "One sample rate per file is required."; return false; }
+  for (int r : sample_rates_hz)
+    if (!CheckScope(1, r, false, false)) return false;
+  return true;
+}
+
+bool EncodeSpansAnyRate(const std::vector<std::vector<int16_t>>& wav_data, const std::vector<int>& sample_rates_hz, int bitrate,
+                        const std::vector<std::vector<int>>* bitrates, bool enable_dtx, const ghc::filesystem::path& model_path,
+                        std::vector<std::vector<uint8_t>>* encoded_features, std::vector<std::vector<int32_t>>* packet_sizes,
+                        int num_lanes, int device) {
+  if (!HavePackedSpanCalls() || !CheckRates(sample_rates_hz, wav_data.size())) return false;
+  const int uniform_bits = bitrates ? 0 : BatchBitrateToNumQuantizedBits(bitrate);
+  if (uniform_bits < 0) { LOG(ERROR) << "Bitrate " << bitrate << " bps is not supported by codec."; return false; }
+  const int n = (int)wav_data.size();
+  if (bitrates && (int)bitrates->size() != n) { LOG(ERROR) << "One bitrate schedule per file is required."; return false; }
+  encoded_features->assign(n, {});
+  if (packet_sizes) packet_sizes->assign(n, {});
+  if (n == 0) return true;
+  std::vector<size_t> hops((size_t)n);
+  for (int i = 0; i < n; ++i) hops[i] = (size_t)sample_rates_hz[i] / 50;
+  std::vector<int16_t> pcm;   // the files' whole hops back to back: the packed layout with ext_offsets == NULL
+  const SpanJob job = MakeSpanJob(wav_data, hops, LYRA_HIP_SIDE_ENCODER, num_lanes, &pcm);
+  std::vector<int32_t> bits, rates(sample_rates_hz.begin(), sample_rates_hz.end());
+  for (int i = 0; i < n; ++i) {
+    if (bitrates && (int64_t)(*bitrates)[i].size() < job.spans[i].n_frames) { LOG(ERROR) << "A bitrate schedule is shorter than its file."; return false; }
+    for (int64_t h = 0; h < job.spans[i].n_frames; ++h) {
+      bits.push_back(bitrates ? BatchBitrateToNumQuantizedBits((*bitrates)[i][h]) : uniform_bits);
+      if (bits.back() < 0) { LOG(ERROR) << "Bitrate " << (*bitrates)[i][h] << " bps is not supported by codec."; return false; }
+    }
+  }
+  bits.push_back(4);   // (never empty)
+  Ctx ctx;
+  if (!ctx.Create(model_path, device, n + (int)job.lanes.size(), "encoder")) return false;
+  const size_t row = (size_t)LYRA_HIP_MAX_PACKET_BYTES;
+  std::vector<uint8_t> packets((size_t)job.frames * row + 1);
+  std::vector<int32_t> sizes((size_t)job.frames + 1, 0);
+  if (lyra_hip_encode_spans_packed(ctx.c, job.spans.data(), n, job.lanes.data(), (int)job.lanes.size(), pcm.data(),
+                                   (long long)pcm.size(), nullptr, rates.data(), bits.data(), enable_dtx, packets.data(),
+                                   sizes.data()) != 0) {
+    LOG(ERROR) << "Unable to encode features: " << lyra_hip_last_error(ctx.c);
+    return false;
+  }
+  for (int i = 0; i < n; ++i) {   // the non-empty packets of every file, in order (encoder_main_lib.cc:77-88)
+    auto& dst = (*encoded_features)[i];
+    for (int64_t f = job.spans[i].first_frame; f < job.spans[i].first_frame + job.spans[i].n_frames; ++f) {
+      dst.insert(dst.end(), packets.begin() + f * row, packets.begin() + f * row + sizes[f]);
+      if (packet_sizes) (*packet_sizes)[i].push_back(sizes[f]);
+    }
+  }
+  return true;
+}
+}  // namespace
+
+bool EncodeWavsAnyRateTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, const std::vector<int>& sample_rates_hz,
+                                   int bitrate, bool enable_dtx, const ghc::filesystem::path& model_path,
+                                   std::vector<std::vector<uint8_t>>* encoded_features,
+                                   std::vector<std::vector<int32_t>>* packet_sizes, int num_lanes, int device) {
+  return EncodeSpansAnyRate(wav_data, sample_rates_hz, bitrate, nullptr, enable_dtx, model_path, encoded_features, packet_sizes,
+                            num_lanes, device);
+}
+
+bool EncodeWavsAnyRateTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, const std::vector<int>& sample_rates_hz,
+                                   const std::vector<std::vector<int>>& bitrates, bool enable_dtx,
+                                   const ghc::filesystem::path& model_path, std::vector<std::vector<uint8_t>>* encoded_features,
+                                   std::vector<std::vector<int32_t>>* packet_sizes, int num_lanes, int device) {
+  if (!packet_sizes) { LOG(ERROR) << "With per-hop bitrates the packet sizes are part of the result."; return false; }
+  return EncodeSpansAnyRate(wav_data, sample_rates_hz, 0, &bitrates, enable_dtx, model_path, encoded_features, packet_sizes,
+                            num_lanes, device);
+}
+
+bool DecodeFeaturesAnyRateTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams,
+                                       const std::vector<std::vector<int32_t>>& packet_sizes,
+                                       const std::vector<int>& sample_rates_hz, const ghc::filesystem::path& model_path,
+                                       std::vector<std::vector<int16_t>>* decoded_audio, int num_lanes, int device) {
+  if (!HavePackedSpanCalls() || !CheckRates(sample_rates_hz, packet_streams.size())) return false;
+  if (!SizesMatch(packet_streams, packet_sizes, 0)) return false;
+  const int n = (int)packet_streams.size();
+  decoded_audio->assign(n, {});
+  if (n == 0) return true;
+  // every hop with a packet of one size: the call without loss handling, on packet rows of that size
+  int one_size = -1;
+  for (const auto& v : packet_sizes)
+    for (int32_t b : v) one_size = one_size < 0 || one_size == b ? b : 0;
+  const bool plain = one_size > 0;
+  const size_t row = plain ? (size_t)one_size : (size_t)LYRA_HIP_MAX_PACKET_BYTES;
+  SpanJob job;
+  std::vector<uint8_t> packets;
+  std::vector<int32_t> sizes, rates(sample_rates_hz.begin(), sample_rates_hz.end());
+  long long samples = 0;
+  std::vector<long long> at_sample((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    job.spans.push_back({(int32_t)i, job.frames, (int64_t)packet_sizes[i].size()});
+    size_t at = 0;
+    for (int32_t b : packet_sizes[i]) {
+      packets.insert(packets.end(), row, 0);
+      if (b) std::copy(packet_streams[i].begin() + at, packet_streams[i].begin() + at + b, packets.end() - row);
+      at += (size_t)b;
+      sizes.push_back(b);
+    }
+    job.frames += (int64_t)packet_sizes[i].size();
+    at_sample[i] = samples;   // the back-to-back layout (lyra_hip_spans_packed_layout)
+    samples += (long long)packet_sizes[i].size() * (sample_rates_hz[i] / 50);
+  }
+  const int64_t worth = job.frames / (2 * lyra_hip_span_warmup_frames(LYRA_HIP_SIDE_DECODER));
+  for (int l = 0; l < (int)std::max<int64_t>(0, std::min<int64_t>(num_lanes, worth)); ++l) job.lanes.push_back(n + l);
+  Ctx ctx;
+  if (!ctx.Create(model_path, device, n + (int)job.lanes.size(), "decoder")) return false;
+  packets.push_back(0);   // (never empty)
+  sizes.push_back(0);
+  std::vector<int16_t> pcm((size_t)samples + 1);
+  const int n_lanes = (int)job.lanes.size();
+  if ((plain ? lyra_hip_decode_spans_packed(ctx.c, job.spans.data(), n, job.lanes.data(), n_lanes, packets.data(),
+                                            NumBitsOfPacketSize(one_size), rates.data(), nullptr, pcm.data(), samples, nullptr)
+             : lyra_hip_decode_spans_lossy_packed(ctx.c, job.spans.data(), n, job.lanes.data(), n_lanes, packets.data(), sizes.data(),
+                                                  rates.data(), nullptr, pcm.data(), samples, nullptr, nullptr, nullptr)) != 0) {
+    LOG(ERROR) << "Could not decode samples: " << lyra_hip_last_error(ctx.c);
+    return false;
+  }
+  for (int i = 0; i < n; ++i)
+    (*decoded_audio)[i].assign(pcm.begin() + at_sample[i],
+                               pcm.begin() + at_sample[i] + (long long)packet_sizes[i].size() * (sample_rates_hz[i] / 50));
+  return true;
+}
+
+bool EncodeFilesAnyRateTimeParallel(const std::vector<ghc::filesystem::path>& wav_paths,
+                                    const std::vector<ghc::filesystem::path>& output_paths, int bitrate, bool enable_dtx,
+                                    const ghc::filesystem::path& model_path, int num_lanes, int device) {
+  if (wav_paths.size() != output_paths.size()) { LOG(ERROR) << "One output path per input file is required."; return false; }
+  std::vector<std::vector<int16_t>> wavs(wav_paths.size());
+  std::vector<int> rates(wav_paths.size());
+  for (size_t i = 0; i < wav_paths.size(); ++i) {
+    int ch = 0;
+    if (!ReadWav16(wav_paths[i], &wavs[i], &ch, &rates[i]) || !CheckScope(ch, rates[i], false, enable_dtx)) return false;
+  }
+  std::vector<std::vector<uint8_t>> encoded;
+  if (!EncodeWavsAnyRateTimeParallel(wavs, rates, bitrate, enable_dtx, model_path, &encoded, nullptr, std::max(num_lanes, 0), device)) {
+    LOG(ERROR) << "Unable to encode features for the batch starting with " << (wav_paths.empty() ? "" : wav_paths[0].string());
+    return false;
+  }
+  for (size_t i = 0; i < output_paths.size(); ++i) {
+    std::ofstream out(output_paths[i].string(), std::ios_base::binary | std::ios_base::trunc);
+    if (!out.is_open()) { LOG(ERROR) << "Could not open output file " << output_paths[i].string(); return false; }
+    out.write(reinterpret_cast<const char*>(encoded[i].data()), encoded[i].size());
+  }
+  return true;
+}
+
+bool DecodeFilesAnyRateTimeParallel(const std::vector<ghc::filesystem::path>& encoded_paths,
+                                    const std::vector<ghc::filesystem::path>& output_paths,
+                                    const std::vector<int>& sample_rates_hz, int bitrate, const ghc::filesystem::path& model_path,
+                                    int num_lanes, int device) {
+  if (encoded_paths.size() != output_paths.size()) { LOG(ERROR) << "One output path per input file is required."; return false; }
+  if (!CheckRates(sample_rates_hz, encoded_paths.size())) return false;
+  if (BatchBitrateToNumQuantizedBits(bitrate) < 0) { LOG(ERROR) << "Bitrate " << bitrate << " bps is not supported by codec."; return false; }
+  const int packet_size = BatchBitrateToPacketSize(bitrate);
+  std::vector<std::vector<uint8_t>> streams(encoded_paths.size());
+  std::vector<std::vector<int32_t>> sizes(encoded_paths.size());
+  for (size_t i = 0; i < encoded_paths.size(); ++i) {
+    std::ifstream in(encoded_paths[i].string(), std::ios::binary);
+    if (!in.is_open()) { LOG(ERROR) << "Could not open " << encoded_paths[i].string(); return false; }
+    streams[i].assign((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    sizes[i].assign(streams[i].size() / (size_t)packet_size, packet_size);
+  }
+  if (!WholePackets(streams, packet_size)) return false;
+  std::vector<std::vector<int16_t>> audio;
+  if (!DecodeFeaturesAnyRateTimeParallel(streams, sizes, sample_rates_hz, model_path, &audio, std::max(num_lanes, 0), device))
+    return false;
+  for (size_t i = 0; i < output_paths.size(); ++i)
+    if (!WriteWav16(output_paths[i], audio[i], 1, sample_rates_hz[i])) return false;
+  return true;
 }
 
 namespace {

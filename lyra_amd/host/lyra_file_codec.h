@@ -104,6 +104,41 @@ bool DecodeFilesTimeParallel(const std::vector<ghc::filesystem::path>& encoded_p
                              const std::vector<ghc::filesystem::path>& output_paths, int sample_rate_hz, int bitrate,
                              const ghc::filesystem::path& model_path, int num_lanes = kDefaultSpanLanes, int device = 0);
 
+// ---- Time-parallel forms for files of ANY rate side by side ---------------------------------------------------------------------
+// An archive of recordings at 8, 16, 32 and 48 kHz in ONE call per direction, through lyra_hip_encode_spans_packed /
+// lyra_hip_decode_spans[_lossy]_packed (include/lyra_hip_spans_packed.h): every file is one span at its own rate, the files' samples
+// lie back to back in one flat buffer and exactly those samples cross the bus.  sample_rates_hz holds one rate per file / stream.
+// Per file the bytes are those of the functions above at that file's rate.  With enable_dtx each file's estimator runs at its own
+// rate.  Lanes are capped as above, on the total number of hops.
+bool EncodeWavsAnyRateTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, const std::vector<int>& sample_rates_hz,
+                                   int bitrate, bool enable_dtx, const ghc::filesystem::path& model_path,
+                                   std::vector<std::vector<uint8_t>>* encoded_features,
+                                   std::vector<std::vector<int32_t>>* packet_sizes, int num_lanes = kDefaultSpanLanes,
+                                   int device = 0);
+// ... with a bitrate per hop: bitrates[i][h] = 3200 / 6000 / 9200 for hop h of file i
+bool EncodeWavsAnyRateTimeParallel(const std::vector<std::vector<int16_t>>& wav_data, const std::vector<int>& sample_rates_hz,
+                                   const std::vector<std::vector<int>>& bitrates, bool enable_dtx,
+                                   const ghc::filesystem::path& model_path, std::vector<std::vector<uint8_t>>* encoded_features,
+                                   std::vector<std::vector<int32_t>>* packet_sizes, int num_lanes = kDefaultSpanLanes,
+                                   int device = 0);
+// packet_sizes[i][h] = 0 / 8 / 15 / 23, packet_streams[i] the non-empty packets concatenated (what the functions above return);
+// decoded_audio[i] holds packet_sizes[i].size() hops at sample_rates_hz[i].  Streams whose hops all carry a packet of one size
+// take the call without loss handling, which never blocks the host.
+bool DecodeFeaturesAnyRateTimeParallel(const std::vector<std::vector<uint8_t>>& packet_streams,
+                                       const std::vector<std::vector<int32_t>>& packet_sizes,
+                                       const std::vector<int>& sample_rates_hz, const ghc::filesystem::path& model_path,
+                                       std::vector<std::vector<int16_t>>* decoded_audio, int num_lanes = kDefaultSpanLanes,
+                                       int device = 0);
+// Whole files: the encode reads each WAV's own rate (mono, one of the four); the decode takes a rate per output file and cuts
+// every .lyra file into packets of the bitrate's size.
+bool EncodeFilesAnyRateTimeParallel(const std::vector<ghc::filesystem::path>& wav_paths,
+                                    const std::vector<ghc::filesystem::path>& output_paths, int bitrate, bool enable_dtx,
+                                    const ghc::filesystem::path& model_path, int num_lanes = kDefaultSpanLanes, int device = 0);
+bool DecodeFilesAnyRateTimeParallel(const std::vector<ghc::filesystem::path>& encoded_paths,
+                                    const std::vector<ghc::filesystem::path>& output_paths,
+                                    const std::vector<int>& sample_rates_hz, int bitrate, const ghc::filesystem::path& model_path,
+                                    int num_lanes = kDefaultSpanLanes, int device = 0);
+
 // Minimal RIFF/WAVE PCM16 I/O (the reference uses audio_dsp's wav_util: Read16BitWavFileToVector /
 // Write16BitWavFileFromVector).  False on anything but uncompressed 16-bit PCM.
 bool ReadWav16(const ghc::filesystem::path& path, std::vector<int16_t>* samples, int* num_channels,

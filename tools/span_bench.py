@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One long recording, encode then decode, time-parallel against hop by hop (BASELINE config #1: one file).
 
-   python tools/span_bench.py [--hops 180000] [--lanes 4096] [--bits 184] [--rate 16000] [--dtx | --lossy | --mixed | --rates]
+   python tools/span_bench.py [--hops 180000] [--lanes 4096] [--bits 184] [--rate 16000] [--dtx | --lossy | --mixed | --rates [--packed]]
                               [--out profiles/span_transcode.jsonl]
 
 --rate 8000 / 32000 / 48000: the recording is at that rate and both legs run the `_ext` span calls and the file functions at it
@@ -42,6 +42,16 @@ with --lanes lanes.  One rates_transcode record with, for the encode, lossy-deco
 `verified`: every output of (a) equals that of (b) byte for byte; steps / steps_split: the step counts of (a) and (b) from
 lyra_hip_spans_plan (lossy: from lyra_hip_spans_lossy_plan_mixed).  kernel_share gives the part of span_resample_rates_kernel in
 the summed kernel time of one call of each family.
+
+--rates --packed: the packed external-rate layout and the host-buffer forms (include/lyra_hip_spans_packed.h).  The four
+recordings of --rates, from HOST arrays, two ways, five timed runs each behind a warm one, per direction (encode, lossy decode on
+the "gilbert" trace, plain decode):
+  (a) `padded`   what a caller of the `_rates_dev` forms has to do: pad every row to 960 samples on the host, upload, call,
+                 synchronise, download, and for the decodes cut the rows back to rate / 50 samples;
+  (b) `packed`   one call of lyra_hip_encode_spans_packed / lyra_hip_decode_spans_lossy_packed / lyra_hip_decode_spans_packed.
+One rates_packed_transcode record: per direction and way the median with min and max in seconds and the bytes moved each way;
+`verified`: both ways give the same packets, sizes and samples; and `resample_pass_ms`: from lyra_hip_profile_*, the time of
+span_resample_rates_kernel and of span_resample_packed_kernel per direction on the same recordings (median, min, max of five).
 
 Records, appended to --out:
   span_transcode   lyra_hip_encode_spans_dev + lyra_hip_decode_spans_dev on device buffers, one stream of --hops hops with
@@ -471,6 +481,124 @@ def rates_device_leg(args):
     return rec
 
 
+def rates_packed_leg(args):
+    import ctypes as C
+    import torch
+    import lyra_amd
+    from lyra_amd import codec
+    dev = torch.device("cuda", 0)
+    hops, row, EXT, nbytes = args.hops, codec.MAX_PACKET_BYTES, codec.MAX_EXT_HOP, codec.packet_size(args.bits)
+    F, n_streams, runs = 4 * hops, 4 + args.lanes, 5
+    ctx = lyra_amd.LyraHip(device=0, max_streams=n_streams, requant="xnnpack")
+    lanes = np.arange(4, n_streams, dtype=np.int32)
+    spans = [(k, k * hops, hops) for k in range(4)]
+    sp, rates = codec._spans(spans), np.asarray(RATES, np.int32)
+    pcm = [recording(hops, r) for r in RATES]
+    flat = np.concatenate([x.reshape(-1) for x in pcm])
+    offsets, total = codec.spans_packed_layout(spans, RATES)
+    assert total == flat.size
+    bits = np.full(F, args.bits, np.int32)
+    pb = np.where(gilbert(F), nbytes, 0).astype(np.int32)
+    head = (ctx.h, sp.ctypes.data, sp.size, lanes.ctypes.data, lanes.size)
+    z = lambda *shape, dtype=torch.int16: torch.zeros(shape, dtype=dtype, device=dev)
+    moved = {}
+
+    def unpad(rows):   # [F][960] -> the flat layout
+        return np.concatenate([rows[k * hops:(k + 1) * hops, :r // 50].reshape(-1) for k, r in enumerate(RATES)])
+
+    def padded_encode():
+        ext = np.zeros((F, EXT), np.int16)
+        for k, x in enumerate(pcm):
+            ext[k * hops:(k + 1) * hops, :x.shape[1]] = x
+        d_pk, d_nb = z(F, row, dtype=torch.uint8), z(F, dtype=torch.int32)
+        ctx.encode_spans_rates_dev(spans, torch.from_numpy(ext).to(dev), RATES, z(F, 320), bits, d_pk, d_nb, lanes)
+        ctx.synchronize()
+        moved["encode", "padded"] = (ext.nbytes, F * row + F * 4)
+        return d_pk.cpu().numpy(), d_nb.cpu().numpy()
+
+    def packed_encode():
+        moved["encode", "packed"] = (flat.nbytes, F * row + F * 4)
+        return ctx.encode_spans_packed(spans, flat, RATES, bits, lanes)
+
+    def padded_decode(lossy, rows_np):
+        d_ext = z(F, EXT)
+        if lossy:
+            ctx.decode_spans_lossy_rates_dev(spans, torch.from_numpy(rows_np).to(dev), pb, RATES, z(F, 320), d_ext, lanes)
+        else:
+            ctx.decode_spans_rates_dev(spans, torch.from_numpy(rows_np).to(dev), args.bits, RATES, z(F, 320), d_ext, lanes)
+        ctx.synchronize()
+        moved["lossy_decode" if lossy else "plain_decode", "padded"] = (rows_np.nbytes, F * EXT * 2)
+        return unpad(d_ext.cpu().numpy())
+
+    def packed_decode(lossy, rows_np):   # through the C ABI: without the optional 16 kHz output
+        out = np.zeros(total, np.int16)
+        if lossy:
+            rc = ctx.L.lyra_hip_decode_spans_lossy_packed(*head, rows_np.ctypes.data, pb.ctypes.data, rates.ctypes.data, None,
+                                                          out.ctypes.data, total, None, None, None)
+        else:
+            rc = ctx.L.lyra_hip_decode_spans_packed(*head, rows_np.ctypes.data, args.bits, rates.ctypes.data, None, out.ctypes.data,
+                                                    total, None)
+        assert rc == 0, ctx.last_error()
+        moved["lossy_decode" if lossy else "plain_decode", "packed"] = (rows_np.nbytes, out.nbytes)
+        return out
+
+    def timed(call):
+        times, result = [], None
+        for run in range(runs + 1):   # run 0 warms (allocations, code)
+            ctx.reset()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            result = call()
+            if run:
+                times.append(time.perf_counter() - t0)
+        return times, result
+
+    rec = dict(kind="rates_packed_transcode", hops=hops, recordings=4, lanes=int(args.lanes), bits=args.bits, runs=runs,
+               samples_packed=int(total), samples_padded=int(F * EXT))
+    stat = lambda v: dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v)))
+    t_pad, (pk, nb) = timed(padded_encode)
+    t_pkd, (pk2, nb2) = timed(packed_encode)
+    ok = bool(np.array_equal(nb, nb2) and np.array_equal(pk, pk2))
+    rec["encode"] = dict(padded_s=stat(t_pad), packed_s=stat(t_pkd))
+    rows23, rows_n = np.ascontiguousarray(pk), np.ascontiguousarray(pk[:, :nbytes])
+    for name, lossy, rows_np in (("lossy_decode", True, rows23), ("plain_decode", False, rows_n)):
+        t_pad, a = timed(lambda: padded_decode(lossy, rows_np))
+        t_pkd, b = timed(lambda: packed_decode(lossy, rows_np))
+        ok = ok and bool(np.array_equal(a, b))
+        rec[name] = dict(padded_s=stat(t_pad), packed_s=stat(t_pkd))
+    for (name, way), (up, down) in moved.items():
+        rec[name][way + "_bytes_up"], rec[name][way + "_bytes_down"] = int(up), int(down)
+    rec["verified"] = ok
+    # the resampler pass alone, on device buffers: the padded kernel and the packed one, per direction
+    kernels = ("span_resample_rates_kernel", "span_resample_packed_kernel")
+    ext = np.zeros((F, EXT), np.int16)
+    for k, x in enumerate(pcm):
+        ext[k * hops:(k + 1) * hops, :x.shape[1]] = x
+    d_pad, d_flat, d_p16 = torch.from_numpy(ext).to(dev), torch.from_numpy(flat).to(dev), z(F, 320)
+    d_pk, d_nb, d_pkn = z(F, row, dtype=torch.uint8), z(F, dtype=torch.int32), torch.from_numpy(rows_n).to(dev)
+    passes = {
+        ("encode", kernels[0]): lambda: ctx.encode_spans_rates_dev(spans, d_pad, RATES, d_p16, bits, d_pk, d_nb, lanes),
+        ("encode", kernels[1]): lambda: ctx.encode_spans_packed_dev(spans, d_flat, RATES, d_p16, bits, d_pk, d_nb, lanes),
+        ("plain_decode", kernels[0]): lambda: ctx.decode_spans_rates_dev(spans, d_pkn, args.bits, RATES, d_p16, d_pad, lanes),
+        ("plain_decode", kernels[1]): lambda: ctx.decode_spans_packed_dev(spans, d_pkn, args.bits, RATES, d_p16, d_flat, lanes),
+    }
+    ctx.profile_enable(True, only=list(kernels))
+    rec["resample_pass_ms"] = {}
+    for (name, kernel), call in passes.items():
+        ms = []
+        for run in range(runs + 1):
+            ctx.reset()
+            call()
+            ctx.synchronize()
+            got = ctx.profile_read()[kernel]
+            assert got[1] == 1, (kernel, got)
+            if run:
+                ms.append(got[0])
+        rec["resample_pass_ms"].setdefault(name, {})[kernel] = stat(ms)
+    ctx.profile_enable(False)
+    return rec
+
+
 def device_leg(args, pcm):
     import torch
     import lyra_amd
@@ -613,9 +741,19 @@ def main():
                     "and the hop-by-hop mixed calls")
     ap.add_argument("--rates", action="store_true", help="per-span sample rates: four recordings at 8 / 16 / 32 / 48 kHz in one call "
                     "against four uniform span calls and the hop-by-hop rates calls")
+    ap.add_argument("--packed", action="store_true", help="with --rates: the packed layout and the host-buffer forms against padding "
+                    "on the host around the `_rates_dev` forms, and the two resampler kernels' times")
     ap.add_argument("--device-leg-only", action="store_true", help="the device leg alone, nothing recorded (the traced child)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "span_transcode.jsonl"))
     args = ap.parse_args()
+    if args.packed:
+        if not args.rates:
+            ap.error("--packed goes with --rates")
+        rec = rates_packed_leg(args)
+        print(json.dumps(rec), flush=True)
+        with open(args.out, "a") as f:
+            f.write(json.dumps(rec) + "\n")
+        return
     if args.rates:
         recs = [rates_device_leg(args)]
         print(json.dumps(recs[0]), flush=True)
