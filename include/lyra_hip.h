@@ -475,8 +475,8 @@ long lyra_hip_rates_errors(lyra_hip_ctx* ctx, int clear);
  *   Request size: the same for every row of a call, free to change from call to call; 0 <= num_samples <=
  *   sample_rate_hz / 50 and num_samples * 16000 divisible by sample_rate_hz (any n at 8 and 16 kHz, even n at 32 kHz,
  *   multiples of 3 at 48 kHz; 10 ms qualifies at every rate), else LYRA_HIP_EINVAL and nothing is enqueued.  Under that rule
- *   BufferedResampler's leftover (buffered_resampler.cc:92-147) stays empty for ever.  Other sizes, and requests above one
- *   hop, are BatchLyraDecoder's (lyra_amd/host/lyra_batch_codec.cc).
+ *   BufferedResampler's leftover (buffered_resampler.cc:92-147) stays empty for ever.  Other sizes, and requests of up
+ *   to four hops, are lyra_hip_decode_samples_any_dev's (lyra_hip_decode_samples_any.h).
  *   The feature FIFO holds LYRA_HIP_DECODE_SAMPLES_FIFO waiting vectors per stream (the reference's is unbounded): a packet
  *   that finds it full is NOT delivered -- the stream goes on as if the packet had never come -- and is counted in
  *   lyra_hip_decode_samples_errors.  A receiver that pulls audio at the rate packets arrive never holds more than 2.

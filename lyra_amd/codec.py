@@ -317,10 +317,24 @@ def _signatures_decode_streams():
 _SIGNATURES_DECODE_STREAMS = _signatures_decode_streams()
 
 
+def _signatures_decode_samples_any():
+    """The same for include/lyra_hip_decode_samples_any.h (tests/test_decode_samples_any_cpu.py holds each entry to its
+    prototype)."""
+    vp, ci = C.c_void_p, C.c_int
+    table = {
+        "decode_samples_any_dev": [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp],
+        "decode_samples_any_begin": [vp, vp, ci, vp, vp, ci, ci], "decode_samples_any_end": [vp, vp],
+    }
+    return {"lyra_hip_" + name: (ci, args) for name, args in table.items()}
+
+
+_SIGNATURES_DECODE_SAMPLES_ANY = _signatures_decode_samples_any()
+
+
 def _load(path=None):
     """The C-ABI library (default: library_path()); a second path loads a build variant beside it (lyra_amd/variants/).
     A library that lacks a function of _SIGNATURES, _SIGNATURES_SPANS_MIXED, _SIGNATURES_SPANS_RATES, _SIGNATURES_SPANS_PACKED,
-    _SIGNATURES_ENCODE_STREAMS or _SIGNATURES_DECODE_STREAMS is refused."""
+    _SIGNATURES_ENCODE_STREAMS, _SIGNATURES_DECODE_STREAMS or _SIGNATURES_DECODE_SAMPLES_ANY is refused."""
     path = os.path.abspath(path or library_path())
     if path in _libs:
         return _libs[path]
@@ -342,7 +356,8 @@ def _load(path=None):
     L = C.CDLL(path)
     for name, (restype, argtypes) in (*_SIGNATURES.items(), *_SIGNATURES_SPANS_MIXED.items(), *_SIGNATURES_SPANS_RATES.items(),
                                        *_SIGNATURES_SPANS_PACKED.items(),
-                                       *_SIGNATURES_ENCODE_STREAMS.items(), *_SIGNATURES_DECODE_STREAMS.items()):
+                                       *_SIGNATURES_ENCODE_STREAMS.items(), *_SIGNATURES_DECODE_STREAMS.items(),
+                                       *_SIGNATURES_DECODE_SAMPLES_ANY.items()):
         fn = getattr(L, name, None)
         if fn is None:
             raise LyraHipError(f"{path} does not export {name}")
@@ -399,6 +414,7 @@ class LyraHip:
         self._pending_encodes = []   # (B, num_bits) of the hops begun by encode_begin, oldest first
         self._pending_decodes = []   # B of the calls begun by decode_begin, oldest first
         self._pending_stream_encodes = []   # B of the hops begun by encode_streams_begin, oldest first
+        self._pending_any_decodes = []      # (B, num_samples) of the requests begun by decode_samples_any_begin, oldest first
         self._pending_stream_decodes = []   # (B, packed samples) of the hops begun by decode_streams_begin, oldest first
 
     def _create(self, h, mode, model_dir, device, max_streams, weights_image):
@@ -935,6 +951,37 @@ class LyraHip:
                        self._p_packets(d_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_packet_bytes, B),
                        num_samples, sample_rate_hz, self._opt_dev_ptr(d_pcm_ext, "int16", (B, num_samples), "pcm"),
                        *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B))
+
+    def decode_samples_any_dev(self, d_ids, d_packets, d_packet_bytes, num_samples, sample_rate_hz, d_pcm_ext=None,
+                               d_is_noise=None, d_is_comfort_noise=None):
+        """decode_samples_dev for ANY request size of 0 .. 4 hops (lyra_hip_decode_samples_any_dev): BufferedResampler's
+        leftover is part of the stream, and a request above one hop runs the reference loop in up to four rounds inside the
+        call.  Arguments as decode_samples_dev; 0 <= num_samples <= 4 * rate / 50."""
+        B = d_packets.shape[0]
+        self._dev_call(self.L.lyra_hip_decode_samples_any_dev, self._p_ids(d_ids, B), B,
+                       self._p_packets(d_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_packet_bytes, B),
+                       num_samples, sample_rate_hz, self._opt_dev_ptr(d_pcm_ext, "int16", (B, num_samples), "pcm"),
+                       *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B))
+
+    def decode_samples_any_begin(self, packets, packet_bytes, num_samples, sample_rate_hz, stream_ids=None):
+        """Pipelined host-buffer form (lyra_hip_decode_samples_any_begin): packets uint8 [B][MAX_PACKET_BYTES], packet_bytes
+        int32 [B].  Up to two requests in flight; the arrays may be reused at once."""
+        packets, B, ids = self._rows(packets, np.uint8, MAX_PACKET_BYTES, stream_ids)
+        sizes = _np(packet_bytes, np.int32, (B,))
+        self._chk(self.L.lyra_hip_decode_samples_any_begin(self.h, ids.ctypes.data, B, packets.ctypes.data, sizes.ctypes.data,
+                                                           num_samples, sample_rate_hz))
+        self._pending_any_decodes.append((B, num_samples))
+
+    def decode_samples_any_end(self):
+        """-> pcm int16 [B][num_samples] of the OLDEST request begun by decode_samples_any_begin."""
+        if not self._pending_any_decodes:
+            self._chk(self.L.lyra_hip_decode_samples_any_end(self.h, None))
+        B, n = self._pending_any_decodes[0]
+        out = np.empty((B, n), np.int16)
+        rc = self.L.lyra_hip_decode_samples_any_end(self.h, out.ctypes.data)
+        self._pending_any_decodes.pop(0)   # (the library gives the slot back whatever the wait returns)
+        self._chk(rc)
+        return out
 
     def decode_samples_errors(self, clear=False):
         """Invalid packet sizes plus packets that found the feature FIFO full, seen by decode_samples_dev (synchronises)."""

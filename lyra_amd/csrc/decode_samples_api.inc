@@ -186,6 +186,9 @@ int lyra_hip_decode_samples_begin(lyra_hip_ctx* c, const int32_t* ids, int B, co
   if (c->dstr_begun != c->dstr_ended)   // (as lyra_hip_decode_begin: one decode pipeline at a time)
     return fail(c, LYRA_HIP_EINVAL, "decode_samples_begin: a lyra_hip_decode_streams_begin call is in flight "
                 "(lyra_hip_decode_streams_end)");
+  if (c->dsa_begun != c->dsa_ended)
+    return fail(c, LYRA_HIP_EINVAL, "decode_samples_begin: a lyra_hip_decode_samples_any_begin request is in flight "
+                "(lyra_hip_decode_samples_any_end)");
   DsHostSlot& S = H->slot[H->begun & 1];
   const size_t n = (size_t)c->max_streams;
   if (!S.h_in) HIPCHK(c, hipHostMalloc((void**)&S.h_in, n * 32, hipHostMallocDefault));

@@ -252,6 +252,16 @@ __global__ void ds_est_gather_kernel(const int32_t* ids, int B, const int32_t* i
 __global__ void ds_slice_kernel(const int32_t* ids, int B, const int32_t* info, const int16_t* gan_new, const int16_t* cng_new,
                                 int16_t* gan_held, int16_t* cng_held, const float* fade_w, int16_t* out, int out_stride,
                                 const uint8_t* noise_state, int32_t* is_noise, int32_t* is_cn);
+// lyra_hip_decode_samples_any_dev (decode_samples_any_kernels.hip): ds_plan_kernel for one round of a call of up to four hops,
+// with the internal length per row: call [B][4] = {old leftover count, used, n_int, new count}, written in round 0
+__global__ void ds_plan_any_kernel(const int32_t* ids, int B, const int32_t* pkt_bytes, int round, int n_ext, int rate,
+                                   uint8_t* rs_state, int32_t* call, uint8_t* cng_state, int32_t* gen_ids, int32_t* cng1_ids,
+                                   int32_t* cng2_ids, int32_t* est_ids, int32_t* info, float* feats, float* ring, unsigned* err);
+// the end of such a call at 8 / 32 / 48 kHz: resampler over call[b][2] samples per row, old leftover + new samples -> out
+// [B][n_ext], surplus -> the slot's leftover
+size_t ds_splice_lds_bytes();
+__global__ void ds_splice_kernel(ResampleP P, const int32_t* ids, int B, const int32_t* call, uint8_t* state, const int16_t* in,
+                                 int in_stride, int16_t* out, int n_ext);
 size_t logmel_lds_bytes();
 size_t cng_lds_bytes();
 struct ResetP { int8_t e_r2_1, e_r2_2, e_d2, e_bott, d_r0_0, d_r0_1, d_r0_2; };

@@ -95,6 +95,8 @@ constexpr int NOISE_BYTES = align256(N_BOUND + 160 * 4);
 constexpr int RS_RADIUS = 17;                      // kernel radius in input samples (resampler.cc:33-38)
 constexpr int RS_TAPS = 2 * RS_RADIUS + 1;
 constexpr int RS_IN_POS = 0;                       // int32: input samples consumed so far (decimation phase)
+// R_RS_D bytes 4..11: BufferedResampler's leftover of lyra_hip_decode_samples_any_dev (decode_samples_any_plan.h: int32 count,
+// int16[2] samples; all zero = empty); 12..15 unused
 constexpr int RS_HIST = 16;                        // f32[34]: the last RS_TAPS - 1 input samples
 constexpr int RS_BYTES = align256(RS_HIST + (RS_TAPS - 1) * 4);
 

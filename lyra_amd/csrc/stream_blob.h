@@ -20,6 +20,7 @@
 //   R_NOISE_E / R_NOISE_D  N_INIT, N_IS_NOISE                       0 or 1
 //                          N_HOPS                                   0 .. NOISE_HOPS_MAX - 1   (hops_per_update at 48 kHz)
 //   R_RS_E / R_RS_D        RS_IN_POS                                0 .. 5              first tap of the decimator
+//   R_RS_D                 DSA_LEFT_COUNT (decode_samples_any_plan.h) 0 .. DSA_LEFT_MAX   trip count and offset of the splice
 //   R_CNG  LOSSY_CTL       concealment / 320  (bits 0-7)            0 .. 4
 //                          fade / 320         (bits 8-15)           0 .. 2              index into the cross-fade table
 //                          direction          (bit 16), bits 17-31  0 / 1, zero
@@ -40,6 +41,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "decode_samples_any_plan.h"
 #include "decode_samples_plan.h"
 #include "state_layout.h"
 
@@ -110,7 +112,7 @@ constexpr uint32_t FINGERPRINT = fingerprint();
 // ---- validate ------------------------------------------------------------------------------------------------------------
 // 0: the blob may be imported; else the first failing check (V_*).  `blob` must be 4-byte aligned.
 enum Verdict { V_OK = 0, V_MAGIC, V_VERSION, V_BYTES, V_FINGERPRINT, V_MODE, V_MODEL, V_SRC_ID, V_HEADER_ZERO, V_PHASE,
-               V_NOISE, V_RS_IN_POS, V_LOSSY_CTL, V_DS_STATE, V_CNG_HEADER };
+               V_NOISE, V_RS_IN_POS, V_LOSSY_CTL, V_DS_STATE, V_CNG_HEADER, V_DSA_LEFT };
 
 LYRA_LOSSY_HD inline uint32_t ld32(const uint8_t* p) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -160,6 +162,8 @@ LYRA_LOSSY_HD inline int validate(const uint8_t* blob, uint32_t requant_mode) {
   uint32_t zc = ld32(g + 12);
   for (int o = DS_STATE + (int)sizeof(DsState); o < st::C_OLA; o += 4) zc |= ld32(g + o);   // includes the key word
   LYRA_SB_CHECK(zc == 0, V_CNG_HEADER);
+  // BufferedResampler's leftover count of lyra_hip_decode_samples_any_dev (zero in every blob written before that call existed)
+  LYRA_SB_CHECK(ld32(blob + region_off(st::R_RS_D) + DSA_LEFT_COUNT) <= (uint32_t)DSA_LEFT_MAX, V_DSA_LEFT);
 #undef LYRA_SB_CHECK
   return rc;
 }

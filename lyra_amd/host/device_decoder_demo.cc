@@ -4,6 +4,7 @@
 //                       <packets_out.bin> <lengths_out.i32> <pcm_out.s16>
 // LYRA_DEMO_PIPELINED=1: DecodeSamplesAsync(request k + 1) is issued before WaitDecoded(k).  A request the decoder refuses
 // (outside its size rule) ends the program with exit code 6, as a failed DecodeSamples ends decoder_demo.
+// LYRA_DEMO_ANY_SIZE=1: AnySizeDeviceLyraDecoder (lyra_device_decoder_any.h) instead: requests of any size up to four hops.
 //
 //   device_decoder_demo --bench <model_dir> <sample_rate> <num_streams> <hops> <loss_percent> <reps>
 // times one session -- 10 ms requests, a packet every second request, two-state (Gilbert) loss with mean burst 2, host
@@ -23,6 +24,7 @@
 
 #include "lyra_batch_codec.h"
 #include "lyra_device_decoder.h"
+#include "lyra_device_decoder_any.h"
 
 using namespace chromemedia::codec;
 
@@ -117,11 +119,140 @@ int Bench(int argc, char** argv) {
   return 0;
 }
 
-}  // namespace
+// The same session under an audio back end's callback of `cb` frames (any size up to four hops): every hop the received
+// packets, then the callbacks whose samples the packets handed over so far cover.  A hop without a callback is followed by a
+// second packet for its streams, which cannot overtake requests in flight: the pipelined form drains first.
+template <class Dec>
+bool CallbackSession(Dec* dec, int n, int ps, int hop, int cb, int hops, const std::vector<uint8_t>& packets,
+                     const std::vector<uint8_t>& received, bool pipelined, std::vector<int16_t>* out) {
+  std::vector<int32_t> ids;
+  std::vector<uint8_t> delivered;
+  int waiting = 0;
+  long played = 0;
+  bool idle_hop = false;
+  absl::Span<int16_t> span(out->data(), (size_t)n * cb);
+  for (int t = 0; t < hops; ++t) {
+    ids.clear();
+    delivered.clear();
+    for (int s = 0; s < n; ++s)
+      if (received[(size_t)t * n + s]) {
+        ids.push_back(s);
+        const uint8_t* p = packets.data() + ((size_t)t * n + s) * ps;
+        delivered.insert(delivered.end(), p, p + ps);
+      }
+    if (idle_hop)
+      for (; waiting > 0; --waiting)
+        if (!dec->WaitDecoded(span)) return false;
+    if (!ids.empty() && !dec->SetEncodedPackets(absl::MakeConstSpan(ids), absl::MakeConstSpan(delivered))) return false;
+    idle_hop = true;
+    while (played + cb <= (long)(t + 1) * hop) {
+      played += cb;
+      idle_hop = false;
+      if (!pipelined) {
+        if (!dec->DecodeSamples(cb, span)) return false;
+        continue;
+      }
+      if (waiting == 2) { if (!dec->WaitDecoded(span)) return false; --waiting; }
+      if (!dec->DecodeSamplesAsync(cb)) return false;
+      ++waiting;
+    }
+  }
+  for (; waiting > 0; --waiting)
+    if (!dec->WaitDecoded(span)) return false;
+  return true;
+}
 
-int main(int argc, char** argv) {
-  if (argc > 1 && std::strcmp(argv[1], "--bench") == 0) return Bench(argc, argv);
-  if (argc != 11) { std::fprintf(stderr, "usage: see device_decoder_demo.cc\n"); return 2; }
+//   device_decoder_demo --bench-any <model_dir> <sample_rate> <num_streams> <hops> <loss_percent> <reps> <callback_frames>
+// Bench's session and loss model under callbacks of <callback_frames>, through BatchLyraDecoder and AnySizeDeviceLyraDecoder.
+int BenchAny(int argc, char** argv) {
+  if (argc != 9) { std::fprintf(stderr, "usage: see device_decoder_demo.cc\n"); return 2; }
+  const std::string model_dir = argv[2];
+  const int rate = std::atoi(argv[3]), n = std::atoi(argv[4]), hops = std::atoi(argv[5]), reps = std::atoi(argv[7]);
+  const int cb = std::atoi(argv[8]);
+  const double loss = std::atof(argv[6]) / 100.0;
+  const int hop = rate / 50, ps = 15;
+  if (cb <= 0 || cb > 4 * hop) return 2;
+  std::mt19937 rng(5);
+  std::vector<uint8_t> packets((size_t)hops * n * ps), received((size_t)hops * n, 1);
+  {
+    auto enc = BatchLyraEncoder::Create(rate, 1, 6000, false, model_dir, n);
+    if (!enc) return 1;
+    std::vector<int16_t> pcm((size_t)n * hop);
+    for (int t = 0; t < hops; ++t) {
+      for (auto& v : pcm) v = (int16_t)((int)(rng() % 4001) - 2000);
+      auto p = enc->Encode(absl::MakeConstSpan(pcm));
+      if (!p || (int)p->size() != n * ps) return 4;
+      std::memcpy(packets.data() + (size_t)t * n * ps, p->data(), p->size());
+    }
+  }
+  if (loss > 0) {
+    std::uniform_real_distribution<double> u(0, 1);
+    const double p_lost = loss / (2.0 * (1.0 - loss)), p_back = 0.5;
+    for (int s = 0; s < n; ++s) {
+      bool rx = true;
+      for (int t = 0; t < hops; ++t) {
+        received[(size_t)t * n + s] = rx;
+        rx = rx ? u(rng) >= p_lost : u(rng) < p_back;
+      }
+    }
+  }
+  // The receiver's jitter buffer: callbacks that do not line up with the hops let every loss episode leave part of a
+  // concealed hop in front of the next packet, so the decoder's queue grows (the reference's does, without bound); a packet
+  // that would be the fourth to wait is dropped as late.  Decided here, on the shared plan functions, so that both decoders
+  // get the same script -- each object runs its blocking and its pipelined session of every pass, 2 * (reps + 1) in a row.
+  long late = 0;
+  const int sessions = 2 * (reps + 1);
+  std::vector<uint8_t> script((size_t)sessions * hops * n);
+  for (int s = 0; s < n; ++s) {
+    lyra::DsState st = {0, 0, 0, 0, 0, 0, 0};
+    int left = 0;
+    for (int rep = 0; rep < sessions; ++rep) {
+      long played = 0;
+      for (int t = 0; t < hops; ++t) {
+        bool rx = received[(size_t)t * n + s] != 0;
+        if (rx && st.wait >= lyra::DS_FIFO_DEPTH - 1) { rx = false; ++late; }
+        script[((size_t)rep * hops + t) * n + s] = rx;
+        bool first = true;
+        for (; played + cb <= (long)(t + 1) * hop; played += cb, first = false) {
+          const lyra::DsaStep step = lyra::ds_any_step(left, cb, rate);
+          left = step.left;
+          for (int r = 0, R = lyra::ds_any_rounds(cb, rate); r < R; ++r)
+            st = lyra::ds_plan(st, rx && first && r == 0, lyra::ds_any_round_total(step.n_int, r)).s;
+        }
+        if (first) st = lyra::ds_plan(st, rx, 0).s;   // (no callback in this hop: the packet waits)
+      }
+    }
+  }
+  auto batch = BatchLyraDecoder::Create(rate, 1, model_dir, n);
+  auto device = AnySizeDeviceLyraDecoder::Create(rate, 1, model_dir, n);
+  if (!batch || !device) return 1;
+  std::vector<int16_t> out((size_t)n * cb);
+  const char* names[4] = {"batch_blocking", "batch_pipelined", "any_size_blocking", "any_size_pipelined"};
+  std::vector<double> fps[4];
+  for (int rep = 0; rep <= reps; ++rep)   // pass 0 warms every form up and is not counted
+    for (int f = 0; f < 4; ++f) {
+      const auto t0 = std::chrono::steady_clock::now();
+      const size_t sess = (size_t)rep * 2 + (f & 1);
+      received.assign(script.begin() + sess * hops * n, script.begin() + (sess + 1) * hops * n);
+      const bool ok = f < 2 ? CallbackSession(batch.get(), n, ps, hop, cb, hops, packets, received, f == 1, &out)
+                            : CallbackSession(device.get(), n, ps, hop, cb, hops, packets, received, f == 3, &out);
+      const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      if (!ok) return 6;
+      if (rep) fps[f].push_back((double)n * hops / dt);
+    }
+  std::printf("{\"bench\": \"decode_samples_any_host\", \"streams\": %d, \"rate\": %d, \"callback\": %d, \"loss\": %.2f, \"hops\": %d, "
+              "\"reps\": %d, \"late_packets_dropped\": %ld", n, rate, cb, loss, hops, reps, late);
+  for (int f = 0; f < 4; ++f) {
+    std::sort(fps[f].begin(), fps[f].end());
+    std::printf(", \"%s\": {\"frames_per_s_median\": %.0f, \"min\": %.0f, \"max\": %.0f}", names[f], fps[f][fps[f].size() / 2],
+                fps[f].front(), fps[f].back());
+  }
+  std::printf("}\n");
+  return 0;
+}
+
+template <class Dec>
+int Script(char** argv) {
   const std::string model_dir = argv[1];
   const int rate = std::atoi(argv[4]), bitrate = std::atoi(argv[5]), dtx = std::atoi(argv[6]), n = std::atoi(argv[7]);
   std::ifstream script(argv[2]);
@@ -130,7 +261,7 @@ int main(int argc, char** argv) {
   std::vector<int16_t> pcm(raw.size() / 2);
   std::memcpy(pcm.data(), raw.data(), pcm.size() * 2);
   auto enc = BatchLyraEncoder::Create(rate, 1, bitrate, dtx != 0, model_dir, n);
-  auto dec = DeviceLyraDecoder::Create(rate, 1, model_dir, n);
+  auto dec = Dec::Create(rate, 1, model_dir, n);
   if (!enc || !dec) { std::fprintf(stderr, "creation failed\n"); return 1; }
   std::ofstream pk_out(argv[8], std::ios::binary), len_out(argv[9], std::ios::binary), pcm_out(argv[10], std::ios::binary);
   const char* e = std::getenv("LYRA_DEMO_PIPELINED");
@@ -183,4 +314,14 @@ int main(int argc, char** argv) {
   while (!waiting.empty())
     if (!deliver_oldest()) return 6;
   return 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc > 1 && std::strcmp(argv[1], "--bench") == 0) return Bench(argc, argv);
+  if (argc > 1 && std::strcmp(argv[1], "--bench-any") == 0) return BenchAny(argc, argv);
+  if (argc != 11) { std::fprintf(stderr, "usage: see device_decoder_demo.cc\n"); return 2; }
+  const char* any = std::getenv("LYRA_DEMO_ANY_SIZE");
+  return any && std::atoi(any) != 0 ? Script<AnySizeDeviceLyraDecoder>(argv) : Script<DeviceLyraDecoder>(argv);
 }

@@ -4,7 +4,7 @@
 // BatchLyraDecoder's method names and signatures (lyra_batch_codec.h), so one can stand in for the other; the differences:
 //   - a request is 0 .. sample_rate_hz / 50 samples and a whole number of 16 kHz samples (any n at 8 and 16 kHz, even n at
 //     32 kHz, multiples of 3 at 48 kHz; 10 ms qualifies at every rate).  Other sizes are refused (false / nullopt +
-//     LOG(ERROR)): they are BatchLyraDecoder's;
+//     LOG(ERROR)): they are AnySizeDeviceLyraDecoder's (lyra_device_decoder_any.h, up to four hops) or BatchLyraDecoder's;
 //   - every stream holds at most LYRA_HIP_DECODE_SAMPLES_FIFO packets whose hop has not started; SetEncodedPackets refuses
 //     the whole call when one of its streams is full (the reference's queue is unbounded);
 //   - per request the host does integer bookkeeping only (decode_samples_plan.h, the function the device runs): one
