@@ -331,10 +331,25 @@ def _signatures_decode_samples_any():
 _SIGNATURES_DECODE_SAMPLES_ANY = _signatures_decode_samples_any()
 
 
+def _signatures_decode_samples_streams():
+    """The same for include/lyra_hip_decode_samples_streams.h (tests/test_decode_samples_streams_plan_cpu.py holds each entry to
+    its prototype)."""
+    vp, ci, cl = C.c_void_p, C.c_int, C.c_long
+    table = {
+        "decode_samples_streams_dev": [vp, vp, ci, vp, vp, vp, vp, ci, vp, cl, vp, vp, vp],
+        "decode_samples_streams_begin": [vp, vp, ci] + [vp] * 4, "decode_samples_streams_end": [vp] * 4,
+    }
+    return {"lyra_hip_" + name: (ci, args) for name, args in table.items()}
+
+
+_SIGNATURES_DECODE_SAMPLES_STREAMS = _signatures_decode_samples_streams()
+
+
 def _load(path=None):
     """The C-ABI library (default: library_path()); a second path loads a build variant beside it (lyra_amd/variants/).
     A library that lacks a function of _SIGNATURES, _SIGNATURES_SPANS_MIXED, _SIGNATURES_SPANS_RATES, _SIGNATURES_SPANS_PACKED,
-    _SIGNATURES_ENCODE_STREAMS, _SIGNATURES_DECODE_STREAMS or _SIGNATURES_DECODE_SAMPLES_ANY is refused."""
+    _SIGNATURES_ENCODE_STREAMS, _SIGNATURES_DECODE_STREAMS, _SIGNATURES_DECODE_SAMPLES_ANY or
+    _SIGNATURES_DECODE_SAMPLES_STREAMS is refused."""
     path = os.path.abspath(path or library_path())
     if path in _libs:
         return _libs[path]
@@ -357,7 +372,7 @@ def _load(path=None):
     for name, (restype, argtypes) in (*_SIGNATURES.items(), *_SIGNATURES_SPANS_MIXED.items(), *_SIGNATURES_SPANS_RATES.items(),
                                        *_SIGNATURES_SPANS_PACKED.items(),
                                        *_SIGNATURES_ENCODE_STREAMS.items(), *_SIGNATURES_DECODE_STREAMS.items(),
-                                       *_SIGNATURES_DECODE_SAMPLES_ANY.items()):
+                                       *_SIGNATURES_DECODE_SAMPLES_ANY.items(), *_SIGNATURES_DECODE_SAMPLES_STREAMS.items()):
         fn = getattr(L, name, None)
         if fn is None:
             raise LyraHipError(f"{path} does not export {name}")
@@ -416,6 +431,7 @@ class LyraHip:
         self._pending_stream_encodes = []   # B of the hops begun by encode_streams_begin, oldest first
         self._pending_any_decodes = []      # (B, num_samples) of the requests begun by decode_samples_any_begin, oldest first
         self._pending_stream_decodes = []   # (B, packed samples) of the hops begun by decode_streams_begin, oldest first
+        self._pending_sample_stream_decodes = []   # the same for decode_samples_streams_begin
 
     def _create(self, h, mode, model_dir, device, max_streams, weights_image):
         if weights_image is not None:   # bytes of a lyra_v1.lyrapack (lyra_hip_create_from_image)
@@ -982,6 +998,54 @@ class LyraHip:
         self._pending_any_decodes.pop(0)   # (the library gives the slot back whatever the wait returns)
         self._chk(rc)
         return out
+
+    def decode_samples_streams_dev(self, d_ids, d_packets, d_packet_bytes, d_sample_rates, d_num_samples, max_hops, d_pcm,
+                                   d_pcm_offsets=None, d_is_noise=None, d_is_comfort_noise=None, n_pcm_samples=None):
+        """decode_samples_any_dev with a sample rate, a request size and an output offset PER ROW
+        (lyra_hip_decode_samples_streams_dev): d_sample_rates / d_num_samples int32 [B]; max_hops 1..4: the rounds the call
+        enqueues (a row needs ceil(n * 16000 / rate) <= 320 * max_hops); d_pcm int16, any shape: row b's d_num_samples[b]
+        samples go to d_pcm_offsets[b] (int32 [B], any alignment; None: b * 4 * MAX_EXT_HOP); n_pcm_samples: how much of d_pcm
+        the rows may lie in (None: all of it).  A row with a bad rate, size or offset, or one that needs more rounds, runs as a
+        row without a packet and with a request of 0 samples and is counted in rates_errors."""
+        B = d_sample_rates.shape[0]
+        if n_pcm_samples is None:
+            n_pcm_samples = d_pcm.numel()
+        elif n_pcm_samples > d_pcm.numel():
+            raise LyraHipError(f"pcm: n_pcm_samples {n_pcm_samples} exceeds the tensor's {d_pcm.numel()} samples")
+        self._dev_call(self.L.lyra_hip_decode_samples_streams_dev, self._p_ids(d_ids, B), B,
+                       self._p_packets(d_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_packet_bytes, B),
+                       self._dev_ptr(d_sample_rates, "int32", (B,), "sample rates"),
+                       self._dev_ptr(d_num_samples, "int32", (B,), "request sizes"), int(max_hops),
+                       self._dev_ptr(d_pcm, "int16", tuple(d_pcm.shape), "pcm"), int(n_pcm_samples),
+                       self._opt_dev_ptr(d_pcm_offsets, "int32", (B,), "pcm offsets"),
+                       *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B))
+
+    def decode_samples_streams_begin(self, packets, packet_bytes, sample_rates, num_samples, stream_ids=None):
+        """Pipelined host-buffer form (lyra_hip_decode_samples_streams_begin): packets uint8 [B][MAX_PACKET_BYTES],
+        packet_bytes, sample_rates and num_samples int32 [B].  Up to two requests in flight; the arrays may be reused at once."""
+        packets, B, ids = self._rows(packets, np.uint8, MAX_PACKET_BYTES, stream_ids)
+        sizes = _np(packet_bytes, np.int32, (B,))
+        rates = _np(sample_rates, np.int32, (B,))
+        ns = _np(num_samples, np.int32, (B,))
+        total = int(np.maximum(ns, 0).astype(np.int64).sum())   # (what end() sizes its array by: before the call)
+        self._chk(self.L.lyra_hip_decode_samples_streams_begin(self.h, ids.ctypes.data, B, packets.ctypes.data, sizes.ctypes.data,
+                                                               rates.ctypes.data, ns.ctypes.data))
+        self._pending_sample_stream_decodes.append((B, total))
+
+    def decode_samples_streams_end(self):
+        """-> (pcm int16, PACKED: row b holds num_samples[b] samples, rows back to back in batch order; is_noise int32 [B];
+        is_comfort_noise int32 [B]) of the OLDEST request begun by decode_samples_streams_begin."""
+        if not self._pending_sample_stream_decodes:
+            self._chk(self.L.lyra_hip_decode_samples_streams_end(self.h, None, None, None))
+        B, total = self._pending_sample_stream_decodes[0]
+        pcm = np.empty(total, np.int16)
+        noise = np.empty(B, np.int32)
+        cn = np.empty(B, np.int32)
+        rc = self.L.lyra_hip_decode_samples_streams_end(self.h, pcm.ctypes.data if total else None, noise.ctypes.data,
+                                                        cn.ctypes.data)
+        self._pending_sample_stream_decodes.pop(0)   # (the library gives the slot back whatever the wait returns)
+        self._chk(rc)
+        return pcm, noise, cn
 
     def decode_samples_errors(self, clear=False):
         """Invalid packet sizes plus packets that found the feature FIFO full, seen by decode_samples_dev (synchronises)."""

@@ -146,6 +146,8 @@ struct lyra_hip_ctx {
   void* ds_host = nullptr;           // DsHost: the two requests in flight of lyra_hip_decode_samples_begin / _end
   void* dsa = nullptr;               // Dsa (decode_samples_any_api.inc): call buffers and host slots of lyra_hip_decode_samples_any_*
   long dsa_begun = 0, dsa_ended = 0; // ... and how many lyra_hip_decode_samples_any_begin requests were begun / ended
+  void* dss = nullptr;               // Dss (decode_samples_streams_api.inc): call words and host slots of lyra_hip_decode_samples_streams_*
+  long dss_begun = 0, dss_ended = 0; // ... and how many lyra_hip_decode_samples_streams_begin requests were begun / ended
   void* es_host = nullptr;           // EsHost (encode_streams_api.inc): the two slots of lyra_hip_encode_streams_begin / _end
   long es_begun = 0, es_ended = 0;   // ... and how many of its calls were begun / ended
   // lyra_hip_decode_streams_dev / _begin / _end (decode_streams_api.inc)
@@ -237,6 +239,7 @@ void twin_free(lyra_hip_ctx* c);
 void lossy_free(lyra_hip_ctx* c);
 void ds_free(lyra_hip_ctx* c);
 void dsa_free(lyra_hip_ctx* c);
+void dss_free(lyra_hip_ctx* c);
 void pipe_free(lyra_hip_ctx* c);
 void rates_free(lyra_hip_ctx* c);
 void es_free(lyra_hip_ctx* c);
@@ -1103,6 +1106,7 @@ void lyra_hip_destroy(lyra_hip_ctx* c) {
   lossy_free(c);
   ds_free(c);
   dsa_free(c);
+  dss_free(c);
   pipe_free(c);
   es_free(c);
   dstr_free(c);
@@ -2090,6 +2094,7 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
 #include "decode_samples_api.inc"
 #include "decode_streams_api.inc"
 #include "decode_samples_any_api.inc"
+#include "decode_samples_streams_api.inc"
 #include "stream_state_api.inc"
 #include "spans_api.inc"
 #include "spans_lossy_api.inc"

@@ -176,7 +176,10 @@ int lyra_hip_decode_samples_any_begin(lyra_hip_ctx* c, const int32_t* ids, int B
     const DsHost* H = static_cast<const DsHost*>(c->ds_host);
     if ((P && P->d_begun != P->d_ended) || (H && H->begun != H->ended) || c->dstr_begun != c->dstr_ended)
       return fail(c, LYRA_HIP_EINVAL, "decode_samples_any_begin: a lyra_hip_decode_begin, lyra_hip_decode_streams_begin or "
-                  "lyra_hip_decode_samples_begin request is in flight (call its _end first)"); }
+                  "lyra_hip_decode_samples_begin request is in flight (call its _end first)");
+    if (c->dss_begun != c->dss_ended)
+      return fail(c, LYRA_HIP_EINVAL, "decode_samples_any_begin: a lyra_hip_decode_samples_streams_begin request is in flight "
+                  "(lyra_hip_decode_samples_streams_end)"); }
   DsaHostSlot& S = dsa_of(c)->slot[c->dsa_begun & 1];
   const size_t n = (size_t)c->max_streams;
   if (!S.h_in) HIPCHK(c, hipHostMalloc((void**)&S.h_in, n * 32, hipHostMallocDefault));

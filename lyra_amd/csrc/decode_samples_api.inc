@@ -189,6 +189,9 @@ int lyra_hip_decode_samples_begin(lyra_hip_ctx* c, const int32_t* ids, int B, co
   if (c->dsa_begun != c->dsa_ended)
     return fail(c, LYRA_HIP_EINVAL, "decode_samples_begin: a lyra_hip_decode_samples_any_begin request is in flight "
                 "(lyra_hip_decode_samples_any_end)");
+  if (c->dss_begun != c->dss_ended)
+    return fail(c, LYRA_HIP_EINVAL, "decode_samples_begin: a lyra_hip_decode_samples_streams_begin request is in flight "
+                "(lyra_hip_decode_samples_streams_end)");
   DsHostSlot& S = H->slot[H->begun & 1];
   const size_t n = (size_t)c->max_streams;
   if (!S.h_in) HIPCHK(c, hipHostMalloc((void**)&S.h_in, n * 32, hipHostMallocDefault));

@@ -1,0 +1,250 @@
+// decode_samples_streams_api.inc -- part of api.hip: lyra_hip_decode_samples_streams_dev
+// (include/lyra_hip_decode_samples_streams.h), lyra_hip_decode_samples_any_dev with a sample rate, a request size and an output
+// offset per row (decode_samples_streams_plan.h).  The call is dsa_launch (decode_samples_any_api.inc) with
+//   - max_hops rounds, given by the caller: the rows' sizes are on the device, a launch count is not;
+//   - ds_plan_streams_kernel in place of ds_plan_any_kernel: round 0 validates each row and plans an invalid one as a row
+//     without a packet and with a request of 0 samples;
+//   - ds_slice_kernel ALWAYS into the internal-rate scratch [cap][1280] (unchanged: its stride is a launch constant, and the
+//     flags it writes are those of the uniform call), and ds_splice_streams_kernel behind the last round for every rate: the
+//     resampler of the row's own design from the context's table, or the copy of a 16 kHz row to its offset.
+// Every other kernel, the per-round and per-parity buffering (Dsa's buffers are shared: the three DecodeSamples calls take
+// turns by n_ds_calls) and the "count on the decode stream, samples on the noise stream" rule are the any-size call's.
+#include "decode_samples_streams_plan.h"
+#include "../../include/lyra_hip_decode_samples_streams.h"
+
+static_assert(lyra::DSS_ROW_STRIDE == LYRA_HIP_DECODE_SAMPLES_MAX_HOPS * LYRA_HIP_MAX_EXT_HOP, "documented default row stride");
+
+namespace {
+
+struct DssSlot {
+  uint8_t* h_in = nullptr;     // pinned: [ids | packet_bytes | rates | sizes | offsets] int32, B each, then packets [B][23]
+  uint8_t* h_out = nullptr;    // pinned: [is_noise | is_comfort_noise] int32, B each, then the packed samples
+  uint8_t* d_in = nullptr;     // the same on the device
+  uint8_t* d_out = nullptr;
+  hipEvent_t ev_done = nullptr;
+  int cap = 0;                 // rows the four buffers hold
+  int B = 0;
+  long total = 0;              // samples of the packed request
+};
+struct Dss {
+  int cap = 0;
+  int32_t* d_call = nullptr;   // [2 call parities][cap][DSS_CALL_WORDS]
+  DssSlot slot[2];
+};
+
+constexpr size_t kDssInRow = 5 * 4 + LYRA_HIP_MAX_PACKET_BYTES;   // bytes per stream going up
+constexpr size_t kDssOutRow = 2 * 4 + (size_t)DSS_ROW_STRIDE * 2; // ... and at most coming down
+
+Dss* dss_of(lyra_hip_ctx* c) {
+  if (!c->dss) c->dss = new Dss();
+  return static_cast<Dss*>(c->dss);
+}
+void dss_slot_free(DssSlot* S) {
+  if (S->h_in) (void)hipHostFree(S->h_in);
+  if (S->h_out) (void)hipHostFree(S->h_out);
+  S->h_in = S->h_out = nullptr;
+  dfree(S->d_in, S->d_out);
+  S->cap = 0;
+}
+void dss_free(lyra_hip_ctx* c) {
+  Dss* A = static_cast<Dss*>(c->dss);
+  if (!A) return;
+  for (DssSlot& S : A->slot) {
+    dss_slot_free(&S);
+    if (S.ev_done) (void)hipEventDestroy(S.ev_done);
+  }
+  dfree(A->d_call);
+  delete A;
+  c->dss = nullptr;
+}
+
+int dss_ensure(lyra_hip_ctx* c, int B) {
+  Dss* A = dss_of(c);
+  if (B <= A->cap) return 0;
+  int rc = sync_all(c);   // (the words of the calls in flight)
+  if (rc) return rc;
+  dfree(A->d_call);
+  A->cap = 0;
+  HIPCHK(c, dalloc(&A->d_call, (size_t)2 * DSS_CALL_WORDS * (size_t)B));
+  A->cap = B;
+  return 0;
+}
+
+// Rows of the slot's staging.  The slot's previous user, two requests back, has ended (its kernels have read d_in, its
+// download has left d_out and h_out), so growing it disturbs nothing in flight.
+int dss_slot_ensure(lyra_hip_ctx* c, DssSlot* S, int B) {
+  if (!S->ev_done) HIPCHK(c, hipEventCreateWithFlags(&S->ev_done, hipEventDisableTiming));
+  if (B <= S->cap) return 0;
+  dss_slot_free(S);
+  const size_t n = (size_t)B;
+  HIPCHK(c, hipHostMalloc((void**)&S->h_in, n * kDssInRow, hipHostMallocDefault));
+  HIPCHK(c, hipHostMalloc((void**)&S->h_out, n * kDssOutRow, hipHostMallocDefault));
+  HIPCHK(c, dalloc(&S->d_in, n * kDssInRow));
+  HIPCHK(c, dalloc(&S->d_out, n * kDssOutRow));
+  S->cap = B;   // (only now: after a failed allocation the next call frees what exists and starts over)
+  return 0;
+}
+
+// everything the call allocates or builds on first use
+int dss_ensure_all(lyra_hip_ctx* c, int B) {
+  int rc = ensure_scratch(c, B);
+  if (!rc) rc = rates_ensure(c);   // the per-row designs and the invalid-row counter
+  if (!rc) rc = ds_ensure(c, B);   // the streams' rings and held hops, the error word, the rows the DecodeSamples calls share
+  if (!rc) rc = dsa_ensure(c, B);  // the per-round buffers and the internal-rate scratch of the any-size call
+  if (!rc) rc = dss_ensure(c, B);
+  return rc;
+}
+
+int dss_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_packets, const int32_t* d_pkt_bytes,
+               const int32_t* d_rates, const int32_t* d_sizes, int max_hops, int16_t* d_pcm, long n_pcm,
+               const int32_t* d_offsets, int32_t* d_is_noise, int32_t* d_is_cn) {
+  DEVSCOPE(c);
+  int rc = dss_ensure_all(c, B);
+  if (rc) return rc;
+  Dsa* A = dsa_of(c);
+  Dss* S = dss_of(c);
+  const int R = max_hops;
+  const size_t cap = (size_t)A->cap, set = (size_t)(c->n_ds_calls & 1);
+  auto ids_of = [&](int r, int list) { return A->d_ids + ((set * DSA_MAX_HOPS + r) * 4 + list) * cap; };
+  auto info_of = [&](int r) { return A->d_info + (set * DSA_MAX_HOPS + r) * 4 * cap; };
+  auto gan_of = [&](int r) { return A->d_gan_new + (set * DSA_MAX_HOPS + r) * 320 * cap; };
+  int32_t* call = S->d_call + set * DSS_CALL_WORDS * (size_t)S->cap;
+  // ---- decode stream: one unsplit decode-side call ---------------------------------------------------------------------
+  if ((rc = dec_side_begin(c, 0, 1))) return rc;
+  { ProfScope ps(c, K_RVQ_DEC, c->sd[0]);
+    hipLaunchKernelGGL(rvq_decode_mixed_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sd[0], c->model.cb, d_packets, d_pkt_bytes, 0, B,
+                       c->d_ds_feat); }
+  HIPCHK(c, hipGetLastError());
+  for (int r = 0; r < R; ++r) {
+    hipLaunchKernelGGL(ds_plan_streams_kernel, dim3(cdiv(B, 256)), dim3(256), 0, c->sd[0], d_ids, B,
+                       r == 0 ? d_pkt_bytes : nullptr, r, d_rates, d_sizes, d_offsets, max_hops, n_pcm, c->sm.base[st::R_RS_D],
+                       call, c->sm.base[st::R_CNG], ids_of(r, 0), ids_of(r, 1), ids_of(r, 2), ids_of(r, 3), info_of(r),
+                       c->d_ds_feat, c->d_ds_ring, c->d_ds_err, c->d_rates_err);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = launch_generate(c, 0, 0, ids_of(r, 0), B, c->d_ds_feat, gan_of(r)))) return rc;
+  }
+  if ((rc = dec_side_done(c, 0, 1))) return rc;
+  c->n_dec_calls++;
+  // ---- noise stream: the rounds' comfort noise, estimator, comfort noise, slices; then the splice, as ONE noise call ------
+  if ((rc = noise_dev_begin(c))) return rc;
+  for (int r = 0; r < R; ++r) {
+    const int32_t* info = info_of(r);
+    const int16_t* gan_new = gan_of(r);
+    if ((rc = launch_cng(c, c->sn, ids_of(r, 1), B, nullptr, c->d_ds_cng_new))) return rc;
+    hipLaunchKernelGGL(ds_est_gather_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sn, d_ids, B, info, gan_new,
+                       (const int16_t*)c->d_ds_gan, c->d_ds_est);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = launch_noise_masked(c, ids_of(r, 3), B, c->d_ds_est, d_is_noise))) return rc;
+    if ((rc = launch_cng(c, c->sn, ids_of(r, 2), B, nullptr, c->d_ds_cng_new))) return rc;
+    hipLaunchKernelGGL(ds_slice_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sn, d_ids, B, info, gan_new,
+                       (const int16_t*)c->d_ds_cng_new, c->d_ds_gan, c->d_ds_cng, (const float*)c->d_fade, A->d_pcm16 + 320 * r,
+                       DSA_MAX_INTERNAL, (const uint8_t*)c->sm.base[st::R_NOISE_D], d_is_noise, d_is_cn);
+    HIPCHK(c, hipGetLastError());
+  }
+  { ProfScope ps(c, K_RESAMPLE, c->sn);
+    hipLaunchKernelGGL(ds_splice_streams_kernel, dim3(cdiv(B, 4)), dim3(256), ds_splice_streams_lds_bytes(), c->sn,
+                       (const ResampleP*)c->d_rs_tab, d_ids, B, (const int32_t*)call, c->sm.base[st::R_RS_D],
+                       (const int16_t*)A->d_pcm16, DSA_MAX_INTERNAL, d_pcm, d_offsets); }
+  HIPCHK(c, hipGetLastError());
+  c->rs_sn_pending = true;
+  if ((rc = noise_dev_done(c))) return rc;
+  c->n_ds_calls++;
+  return serial_noise_half_done(c);
+}
+
+}  // namespace
+
+extern "C" {
+
+int lyra_hip_decode_samples_streams_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_packets,
+                                        const int32_t* d_packet_bytes, const int32_t* d_sample_rates,
+                                        const int32_t* d_num_samples, int max_hops, int16_t* d_pcm, long n_pcm_samples,
+                                        const int32_t* d_pcm_offsets, int32_t* d_is_noise, int32_t* d_is_comfort_noise) {
+  int rc = check_batch(c, B);
+  if (rc) return rc;
+  if (!d_ids || !d_packets || !d_packet_bytes || !d_sample_rates || !d_num_samples || !d_pcm)
+    return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams: null pointer");
+  if (max_hops < 1 || max_hops > DSA_MAX_HOPS)
+    return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams: max_hops %d outside 1..%d", max_hops, DSA_MAX_HOPS);
+  if (n_pcm_samples < 0) return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams: n_pcm_samples %ld", n_pcm_samples);
+  return dss_launch(c, d_ids, B, d_packets, d_packet_bytes, d_sample_rates, d_num_samples, max_hops, d_pcm, n_pcm_samples,
+                    d_pcm_offsets, d_is_noise, d_is_comfort_noise);
+}
+
+int lyra_hip_decode_samples_streams_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const uint8_t* packets,
+                                          const int32_t* packet_bytes, const int32_t* sample_rates, const int32_t* num_samples) {
+  int rc = check_batch(c, B);
+  if (rc) return rc;
+  if (!packets || !packet_bytes || !sample_rates || !num_samples)
+    return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_begin: null pointer");
+  if ((rc = check_ids_host(c, ids, B))) return rc;
+  for (int b = 0; b < B; ++b) {
+    const int v = dss_size_verdict(sample_rates[b], num_samples[b]);
+    if (v == DSS_BAD_RATE) return check_rate(c, sample_rates[b]);
+    if (v != DSS_OK)
+      return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_begin: %d samples at %d Hz at position %d: a request must be 0..%d "
+                  "samples (%d hops)", num_samples[b], sample_rates[b], b, DSA_MAX_HOPS * (sample_rates[b] / 50), DSA_MAX_HOPS);
+    const int pb = packet_bytes[b];   // PacketSizeToNumQuantizedBits (lyra_config.h:99-106), 0: no packet
+    if (pb != 0 && pb != 8 && pb != 15 && pb != LYRA_HIP_MAX_PACKET_BYTES)
+      return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_begin: packet of %d bytes at position %d (0, 8, 15 or 23)", pb, b);
+  }
+  if (c->dss_begun - c->dss_ended >= 2)
+    return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_begin: two requests are already in flight "
+                "(lyra_hip_decode_samples_streams_end)");
+  { const PipeState* P = pipe_of(c);   // (one decode pipeline at a time: they share the decode-side streams' order)
+    const DsHost* H = static_cast<const DsHost*>(c->ds_host);
+    if ((P && P->d_begun != P->d_ended) || (H && H->begun != H->ended) || c->dstr_begun != c->dstr_ended ||
+        c->dsa_begun != c->dsa_ended)
+      return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_begin: a lyra_hip_decode_begin, lyra_hip_decode_streams_begin, "
+                  "lyra_hip_decode_samples_begin or lyra_hip_decode_samples_any_begin request is in flight (call its _end first)"); }
+  DEVSCOPE(c);
+  // everything the call allocates or builds on first use, BEFORE anything is enqueued: a failure here leaves the streams idle
+  DssSlot& S = dss_of(c)->slot[c->dss_begun & 1];
+  if ((rc = dss_slot_ensure(c, &S, B))) return rc;
+  if ((rc = dss_ensure_all(c, B))) return rc;
+  const size_t n = (size_t)B;
+  int32_t* h = reinterpret_cast<int32_t*>(S.h_in);
+  std::vector<long> offs(n);
+  const long total = dss_packed_offsets(num_samples, B, offs.data());
+  for (int b = 0; b < B; ++b) {
+    h[b] = ids[b];
+    h[n + b] = packet_bytes[b];
+    h[2 * n + b] = sample_rates[b];
+    h[3 * n + b] = num_samples[b];
+    h[4 * n + b] = (int32_t)offs[b];   // (at most max_streams * 3840 < 2^31: lyra_hip_create's bound on max_streams)
+  }
+  std::memcpy(S.h_in + n * 20, packets, n * LYRA_HIP_MAX_PACKET_BYTES);
+  // one upload from pinned staging on the decode-side stream, in front of the call's first kernel
+  HIPCHK(c, hipMemcpyAsync(S.d_in, S.h_in, n * kDssInRow, hipMemcpyHostToDevice, c->sd[0]));
+  const int32_t* m = reinterpret_cast<const int32_t*>(S.d_in);
+  int32_t* flags = reinterpret_cast<int32_t*>(S.d_out);
+  int16_t* pcm = reinterpret_cast<int16_t*>(S.d_out + n * 8);
+  if ((rc = dss_launch(c, m, B, S.d_in + n * 20, m + n, m + 2 * n, m + 3 * n, dss_batch_rounds(sample_rates, num_samples, B), pcm,
+                       total, m + 4 * n, flags, flags + n)))
+    return rc;
+  // flags and samples are written by the noise-stream half: their download rides on that stream, behind the splice
+  HIPCHK(c, hipMemcpyAsync(S.h_out, S.d_out, n * 8 + (size_t)total * 2, hipMemcpyDeviceToHost, c->sn));
+  HIPCHK(c, hipEventRecord(S.ev_done, c->sn));
+  S.B = B;
+  S.total = total;
+  c->dss_begun++;
+  return 0;
+}
+
+int lyra_hip_decode_samples_streams_end(lyra_hip_ctx* c, int16_t* pcm, int32_t* is_noise, int32_t* is_comfort_noise) {
+  if (!c) return LYRA_HIP_EINVAL;
+  if (!c->dss || c->dss_ended == c->dss_begun)
+    return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_end: no request in flight");
+  DssSlot& S = dss_of(c)->slot[c->dss_ended & 1];
+  if (S.total > 0 && !pcm) return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_end: null pointer");
+  DEVSCOPE(c);
+  c->dss_ended++;                  // whatever happens below, the slot is given back
+  HIPCHK(c, hipEventSynchronize(S.ev_done));
+  const size_t n = (size_t)S.B;
+  if (is_noise) std::memcpy(is_noise, S.h_out, n * 4);
+  if (is_comfort_noise) std::memcpy(is_comfort_noise, S.h_out + n * 4, n * 4);
+  if (S.total > 0) std::memcpy(pcm, S.h_out + n * 8, (size_t)S.total * 2);
+  return 0;
+}
+
+}  // extern "C"

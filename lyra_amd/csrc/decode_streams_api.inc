@@ -110,6 +110,9 @@ int lyra_hip_decode_streams_begin(lyra_hip_ctx* c, const int32_t* ids, int B, co
     if (c->dsa_begun != c->dsa_ended)
       return fail(c, LYRA_HIP_EINVAL, "decode_streams_begin: a lyra_hip_decode_samples_any_begin request is in flight "
                   "(lyra_hip_decode_samples_any_end)");
+    if (c->dss_begun != c->dss_ended)
+      return fail(c, LYRA_HIP_EINVAL, "decode_streams_begin: a lyra_hip_decode_samples_streams_begin request is in flight "
+                  "(lyra_hip_decode_samples_streams_end)");
     const DsHost* H = static_cast<const DsHost*>(c->ds_host);
     if (H && H->begun != H->ended)
       return fail(c, LYRA_HIP_EINVAL, "decode_streams_begin: a lyra_hip_decode_samples_begin request is in flight "

@@ -262,6 +262,18 @@ __global__ void ds_plan_any_kernel(const int32_t* ids, int B, const int32_t* pkt
 size_t ds_splice_lds_bytes();
 __global__ void ds_splice_kernel(ResampleP P, const int32_t* ids, int B, const int32_t* call, uint8_t* state, const int16_t* in,
                                  int in_stride, int16_t* out, int n_ext);
+// lyra_hip_decode_samples_streams_dev (decode_samples_streams_kernels.hip): the two kernels above with the request size, the
+// rate and the output offset per row.  call [B][DSS_CALL_WORDS] (decode_samples_streams_plan.h), written in round 0, which
+// also validates the row and counts an invalid one in *rates_err; offsets null: row b at b * DSS_ROW_STRIDE
+__global__ void ds_plan_streams_kernel(const int32_t* ids, int B, const int32_t* pkt_bytes, int round, const int32_t* rates,
+                                       const int32_t* num_samples, const int32_t* offsets, int max_hops, long n_pcm_samples,
+                                       uint8_t* rs_state, int32_t* call, uint8_t* cng_state, int32_t* gen_ids, int32_t* cng1_ids,
+                                       int32_t* cng2_ids, int32_t* est_ids, int32_t* info, float* feats, float* ring,
+                                       unsigned* err, unsigned* rates_err);
+// tab: the context's [2][3] designs (rates_api.inc); a 16 kHz row is copied from `in`, an invalid row touches nothing
+size_t ds_splice_streams_lds_bytes();
+__global__ void ds_splice_streams_kernel(const ResampleP* tab, const int32_t* ids, int B, const int32_t* call, uint8_t* state,
+                                         const int16_t* in, int in_stride, int16_t* out, const int32_t* offsets);
 size_t logmel_lds_bytes();
 size_t cng_lds_bytes();
 struct ResetP { int8_t e_r2_1, e_r2_2, e_d2, e_bott, d_r0_0, d_r0_1, d_r0_2; };

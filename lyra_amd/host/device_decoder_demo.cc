@@ -5,6 +5,14 @@
 // LYRA_DEMO_PIPELINED=1: DecodeSamplesAsync(request k + 1) is issued before WaitDecoded(k).  A request the decoder refuses
 // (outside its size rule) ends the program with exit code 6, as a failed DecodeSamples ends decoder_demo.
 // LYRA_DEMO_ANY_SIZE=1: AnySizeDeviceLyraDecoder (lyra_device_decoder_any.h) instead: requests of any size up to four hops.
+// LYRA_DEMO_MIXED_ANY_SIZE=1: another program altogether,
+//   device_decoder_demo <model_dir> <pcm_in.s16> <num_streams> <hops>
+// <pcm_in.s16> holds [hops][num_streams][320] samples at 16 kHz.  Stream s decodes at 8 / 16 / 32 / 48 kHz (s % 4) under its
+// back end's callback of 160 / 256 / 441 / 1024 frames.  ONE MixedAnySizeDeviceLyraDecoder (lyra_mixed_device_decoder.h) serves
+// all of them, one request per round of callbacks; one AnySizeDeviceLyraDecoder per (rate, size) class gets the same packets
+// and the same requests (each with all <num_streams> slots, of which it uses its class's: a stream keeps its number, which
+// seeds its comfort noise).  Every sample, is_comfort_noise() and leftover_samples() are compared: exit code 8 on a difference,
+// else "mixed any-size: <n> samples equal".
 //
 //   device_decoder_demo --bench <model_dir> <sample_rate> <num_streams> <hops> <loss_percent> <reps>
 // times one session -- 10 ms requests, a packet every second request, two-state (Gilbert) loss with mean burst 2, host
@@ -17,6 +25,8 @@
 #include <cstring>
 #include <fstream>
 #include <iterator>
+#include <memory>
+#include <optional>
 #include <random>
 #include <sstream>
 #include <string>
@@ -25,6 +35,7 @@
 #include "lyra_batch_codec.h"
 #include "lyra_device_decoder.h"
 #include "lyra_device_decoder_any.h"
+#include "lyra_mixed_device_decoder.h"
 
 using namespace chromemedia::codec;
 
@@ -316,9 +327,90 @@ int Script(char** argv) {
   return 0;
 }
 
+int MixedAnySize(int argc, char** argv) {
+  if (argc != 5) { std::fprintf(stderr, "usage: see device_decoder_demo.cc\n"); return 2; }
+  const std::string model_dir = argv[1];
+  const int n = std::atoi(argv[3]), hops = std::atoi(argv[4]);
+  static const int kRate[4] = {8000, 16000, 32000, 48000}, kCallback[4] = {160, 256, 441, 1024};
+  if (n < 4 || n % 4 != 0 || hops < 1) return 2;
+  std::ifstream in(argv[2], std::ios::binary);
+  std::vector<char> raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+  std::vector<int16_t> pcm(raw.size() / 2);
+  std::memcpy(pcm.data(), raw.data(), pcm.size() * 2);
+  if (pcm.size() < (size_t)hops * n * 320) return 3;
+  std::vector<int> rates(n);
+  for (int s = 0; s < n; ++s) rates[s] = kRate[s % 4];
+  auto enc = BatchLyraEncoder::Create(16000, 1, 6000, false, model_dir, n);
+  auto mixed = MixedAnySizeDeviceLyraDecoder::Create(absl::MakeConstSpan(rates), model_dir);
+  std::unique_ptr<AnySizeDeviceLyraDecoder> uniform[4];
+  for (int c = 0; c < 4; ++c) uniform[c] = AnySizeDeviceLyraDecoder::Create(kRate[c], 1, model_dir, n);
+  if (!enc || !mixed || !uniform[0] || !uniform[1] || !uniform[2] || !uniform[3]) { std::fprintf(stderr, "creation failed\n"); return 1; }
+  long played[4] = {0, 0, 0, 0}, compared = 0, requests = 0;
+  for (int t = 0; t < hops; ++t) {
+    auto packets = enc->Encode(absl::MakeConstSpan(pcm.data() + (size_t)t * n * 320, (size_t)n * 320));
+    if (!packets) return 4;
+    const int ps = enc->packet_size();
+    // stream 1 loses hops 4 .. 15 (into comfort noise and back), the others a hop now and then
+    std::vector<int32_t> ids, class_ids[4];
+    std::vector<uint8_t> delivered, class_delivered[4];
+    for (int s = 0; s < n; ++s) {
+      const bool lost = s == 1 ? (t >= 4 && t < 16) : (t * 7 + s * 3) % 10 == 0;
+      if (lost) continue;
+      ids.push_back(s);
+      class_ids[s % 4].push_back(s);
+      delivered.insert(delivered.end(), packets->begin() + s * ps, packets->begin() + (s + 1) * ps);
+      class_delivered[s % 4].insert(class_delivered[s % 4].end(), packets->begin() + s * ps, packets->begin() + (s + 1) * ps);
+    }
+    if (!ids.empty() && !mixed->SetEncodedPackets(absl::MakeConstSpan(ids), absl::MakeConstSpan(delivered))) return 5;
+    for (int c = 0; c < 4; ++c)
+      if (!class_ids[c].empty() &&
+          !uniform[c]->SetEncodedPackets(absl::MakeConstSpan(class_ids[c]), absl::MakeConstSpan(class_delivered[c])))
+        return 5;
+    for (;;) {   // rounds of callbacks: every class whose next callback fits into the playout time of the packets so far
+      bool due[4];
+      std::vector<int32_t> streams;
+      std::vector<int> sizes;
+      for (int c = 0; c < 4; ++c) due[c] = played[c] + kCallback[c] <= (long)(t + 1) * (kRate[c] / 50);
+      for (int s = 0; s < n; ++s)
+        if (due[s % 4]) { streams.push_back(s); sizes.push_back(kCallback[s % 4]); }
+      if (streams.empty()) break;
+      auto got = mixed->DecodeSamples(absl::MakeConstSpan(streams), absl::MakeConstSpan(sizes));
+      if (!got) return 6;
+      ++requests;
+      std::optional<std::vector<int16_t>> want[4];
+      for (int c = 0; c < 4; ++c)
+        if (due[c]) {
+          want[c] = uniform[c]->DecodeSamples(kCallback[c]);
+          if (!want[c]) return 6;
+          played[c] += kCallback[c];
+        }
+      size_t at = 0;
+      for (int32_t s : streams) {
+        const int c = s % 4, cb = kCallback[c];
+        if (std::memcmp(got->data() + at, want[c]->data() + (size_t)s * cb, (size_t)cb * 2) != 0) {
+          std::fprintf(stderr, "hop %d, stream %d (%d Hz, %d frames): samples differ\n", t, s, kRate[c], cb);
+          return 8;
+        }
+        at += cb;
+        compared += cb;
+      }
+      for (int s = 0; s < n; ++s)
+        if (mixed->is_comfort_noise(s) != uniform[s % 4]->is_comfort_noise(s) ||
+            mixed->leftover_samples(s) != uniform[s % 4]->leftover_samples(s)) {
+          std::fprintf(stderr, "hop %d, stream %d: is_comfort_noise or leftover_samples differ\n", t, s);
+          return 8;
+        }
+    }
+  }
+  std::printf("mixed any-size: %ld samples equal in %ld requests, %d streams, %d hops\n", compared, requests, n, hops);
+  return compared > 0 ? 0 : 8;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+  { const char* mixed = std::getenv("LYRA_DEMO_MIXED_ANY_SIZE");
+    if (mixed && std::atoi(mixed) != 0) return MixedAnySize(argc, argv); }
   if (argc > 1 && std::strcmp(argv[1], "--bench") == 0) return Bench(argc, argv);
   if (argc > 1 && std::strcmp(argv[1], "--bench-any") == 0) return BenchAny(argc, argv);
   if (argc != 11) { std::fprintf(stderr, "usage: see device_decoder_demo.cc\n"); return 2; }
