@@ -444,7 +444,9 @@ int lyra_hip_decode_lossy_mixed_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_i
  * lyra_hip_set_serial supported.  Null pointers (every argument but d_is_noise / d_is_comfort_noise is required) or B out of
  * range: LYRA_HIP_EINVAL, nothing enqueued.  In lyra_hip_run_steps_dev: LYRA_HIP_STEP_MIXED_RATE.
  * With DTX per stream as well, packed audio rows and a two-deep host-buffer form: lyra_hip_encode_streams.h; the decode
- * side with packed rows, an optional 16 kHz hop and the same host-buffer form: lyra_hip_decode_streams.h. */
+ * side with packed rows, an optional 16 kHz hop and the same host-buffer form: lyra_hip_decode_streams.h.  What a media
+ * server does between the two -- every participant hears the sum of the others, decode, mix-minus and encode in one call:
+ * lyra_hip_bridge.h. */
 #define LYRA_HIP_MAX_EXT_HOP 960   /* row stride, in samples, of external-rate audio in the calls below: the 48 kHz hop */
 int lyra_hip_encode_rates_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_ids, int B,
                               const int16_t* d_pcm_ext /* [B][960] */, const int32_t* d_sample_rates /* [B] */,

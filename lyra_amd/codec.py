@@ -345,11 +345,63 @@ def _signatures_decode_samples_streams():
 _SIGNATURES_DECODE_SAMPLES_STREAMS = _signatures_decode_samples_streams()
 
 
+class BridgeTick(C.Structure):
+    """lyra_hip_bridge_tick (include/lyra_hip_bridge.h)"""
+    _fields_ = [("d_stream_ids", C.c_void_p), ("B", C.c_int), ("d_packets", C.c_void_p), ("d_packet_bytes", C.c_void_p),
+                ("d_order", C.c_void_p), ("d_room_start", C.c_void_p), ("n_rooms", C.c_int), ("n_members", C.c_int),
+                ("d_muted", C.c_void_p), ("flags", C.c_uint), ("d_num_bits", C.c_void_p), ("d_dtx", C.c_void_p),
+                ("d_out_packets", C.c_void_p), ("d_out_packet_bytes", C.c_void_p), ("d_pcm16", C.c_void_p),
+                ("d_mix", C.c_void_p), ("d_is_noise", C.c_void_p), ("d_is_comfort_noise", C.c_void_p)]
+
+
+BRIDGE_SKIP_COMFORT_NOISE = 1   # LYRA_HIP_BRIDGE_SKIP_COMFORT_NOISE
+BRIDGE_MAX_ROOM = 32767         # LYRA_HIP_BRIDGE_MAX_ROOM
+
+
+def _signatures_bridge():
+    """The same for include/lyra_hip_bridge.h (tests/test_bridge_cpu.py holds each entry to its prototype)."""
+    vp, ci, cu, cl = C.c_void_p, C.c_int, C.c_uint, C.c_long
+    table = {
+        "bridge_plan": (ci, [vp, ci, vp, vp, vp, vp]), "bridge_mix_dev": (ci, [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp]),
+        "bridge_tick_dev": (ci, [vp, vp]), "bridge_begin": (ci, [vp, vp, ci, vp, vp, vp, vp, cu, vp, vp]),
+        "bridge_end": (ci, [vp] * 5), "bridge_errors": (cl, [vp, ci]),
+    }
+    return {"lyra_hip_" + name: sig for name, sig in table.items()}
+
+
+_SIGNATURES_BRIDGE = _signatures_bridge()
+
+
+def _load_bridge(L, path):
+    """_SIGNATURES_BRIDGE applied to a loaded library; one that lacks a function of it is refused."""
+    for name, (restype, argtypes) in _SIGNATURES_BRIDGE.items():
+        fn = getattr(L, name, None)
+        if fn is None:
+            raise LyraHipError(f"{path} does not export {name}")
+        fn.restype, fn.argtypes = restype, argtypes
+    return L
+
+
+def bridge_plan(rooms, lib=None):
+    """The membership index of the conference bridge (lyra_hip_bridge_plan; no GPU): rooms int32 [B], a room label >= 0 per
+    row or < 0 for a row in no room -> (order int32 [n_members], room_start int32 [n_rooms + 1]).  Rooms in ascending label
+    order, rows ascending inside a room.  LyraHipError for a room of more than BRIDGE_MAX_ROOM members."""
+    L = lib or _load()
+    rooms = np.ascontiguousarray(np.asarray(rooms, np.int32).reshape(-1))
+    order = np.zeros(max(rooms.size, 1), np.int32)
+    start = np.zeros(rooms.size + 1, np.int32)
+    n_rooms, n_members = C.c_int(0), C.c_int(0)
+    if L.lyra_hip_bridge_plan(rooms.ctypes.data, rooms.size, order.ctypes.data, start.ctypes.data, C.addressof(n_rooms),
+                              C.addressof(n_members)) != 0:
+        raise LyraHipError(f"lyra_hip_bridge_plan: a room of more than {BRIDGE_MAX_ROOM} members")
+    return order[:n_members.value].copy(), start[:n_rooms.value + 1].copy()
+
+
 def _load(path=None):
     """The C-ABI library (default: library_path()); a second path loads a build variant beside it (lyra_amd/variants/).
     A library that lacks a function of _SIGNATURES, _SIGNATURES_SPANS_MIXED, _SIGNATURES_SPANS_RATES, _SIGNATURES_SPANS_PACKED,
     _SIGNATURES_ENCODE_STREAMS, _SIGNATURES_DECODE_STREAMS, _SIGNATURES_DECODE_SAMPLES_ANY or
-    _SIGNATURES_DECODE_SAMPLES_STREAMS is refused."""
+    _SIGNATURES_DECODE_SAMPLES_STREAMS is refused, and so is one that lacks a function of _SIGNATURES_BRIDGE (_load_bridge)."""
     path = os.path.abspath(path or library_path())
     if path in _libs:
         return _libs[path]
@@ -377,7 +429,7 @@ def _load(path=None):
         if fn is None:
             raise LyraHipError(f"{path} does not export {name}")
         fn.restype, fn.argtypes = restype, argtypes
-    _libs[path] = L
+    _libs[path] = _load_bridge(L, path)
     return L
 
 
@@ -432,6 +484,7 @@ class LyraHip:
         self._pending_any_decodes = []      # (B, num_samples) of the requests begun by decode_samples_any_begin, oldest first
         self._pending_stream_decodes = []   # (B, packed samples) of the hops begun by decode_streams_begin, oldest first
         self._pending_sample_stream_decodes = []   # the same for decode_samples_streams_begin
+        self._pending_bridge_ticks = []     # B of the ticks begun by bridge_begin, oldest first
 
     def _create(self, h, mode, model_dir, device, max_streams, weights_image):
         if weights_image is not None:   # bytes of a lyra_v1.lyrapack (lyra_hip_create_from_image)
@@ -949,6 +1002,76 @@ class LyraHip:
                        self._opt_dev_ptr(d_pcm_offsets, "int32", (B,), "pcm offsets"),
                        self._opt_dev_ptr(d_pcm16, "int16", (B, HOP), "16 kHz pcm"),
                        *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B))
+
+    # -- the conference bridge (include/lyra_hip_bridge.h) ---------------------------------------------
+    def bridge_mix_dev(self, d_pcm16, d_order, d_room_start, d_mix, d_muted=None, d_is_comfort_noise=None):
+        """The mix-minus alone (lyra_hip_bridge_mix_dev): d_pcm16 / d_mix int16 [B][320]; d_order int32 [n_members] row
+        numbers with a room's rows contiguous, d_room_start int32 [n_rooms + 1] (bridge_plan); d_muted / d_is_comfort_noise
+        int32 [B] or None: rows that are no source.  Row b of d_mix receives the clamped sum of the other sources of its room,
+        zeros if no room names it.  Bad d_order entries are skipped and counted in bridge_errors.  Completes on the
+        encode-side stream."""
+        B = d_pcm16.shape[0]
+        n_members, n_rooms = d_order.shape[0], d_room_start.shape[0] - 1
+        self._dev_call(self.L.lyra_hip_bridge_mix_dev, self._p_pcm(d_pcm16, B), B,
+                       self._dev_ptr(d_order, "int32", (n_members,), "order") if n_members else None,
+                       self._dev_ptr(d_room_start, "int32", (n_rooms + 1,), "room_start"), n_rooms, n_members,
+                       self._opt_dev_ptr(d_muted, "int32", (B,), "muted"),
+                       self._opt_dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise"), self._p_pcm(d_mix, B))
+
+    def bridge_tick_dev(self, d_ids, d_packets, d_packet_bytes, d_order, d_room_start, d_num_bits, d_out_packets,
+                        d_out_packet_bytes, d_muted=None, d_dtx=None, flags=0, d_pcm16=None, d_mix=None, d_is_noise=None,
+                        d_is_comfort_noise=None):
+        """One tick of the bridge (lyra_hip_bridge_tick_dev): decode_lossy_mixed_dev(16000) on d_packets uint8 [B][23] /
+        d_packet_bytes int32 [B], the mix of bridge_mix_dev (flags: BRIDGE_SKIP_COMFORT_NOISE), encode_streams_dev at 16 kHz
+        on the mix with d_num_bits int32 [B] / d_dtx int32 [B] or None into d_out_packets uint8 [B][23] /
+        d_out_packet_bytes int32 [B].  d_pcm16 / d_mix int16 [B][320], d_is_noise / d_is_comfort_noise int32 [B]: optional
+        outputs.  Bit for bit the three calls in a row, outputs and stream state."""
+        B = d_packets.shape[0]
+        n_members, n_rooms = d_order.shape[0], d_room_start.shape[0] - 1
+        t = BridgeTick(self._p_ids(d_ids, B), B, self._p_packets(d_packets, B, MAX_PACKET_BYTES),
+                       self._p_packet_bytes(d_packet_bytes, B),
+                       self._dev_ptr(d_order, "int32", (n_members,), "order") if n_members else None,
+                       self._dev_ptr(d_room_start, "int32", (n_rooms + 1,), "room_start"), n_rooms, n_members,
+                       self._opt_dev_ptr(d_muted, "int32", (B,), "muted"), int(flags),
+                       self._dev_ptr(d_num_bits, "int32", (B,), "num_bits"),
+                       self._opt_dev_ptr(d_dtx, "int32", (B,), "dtx flags"),
+                       self._p_packets(d_out_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_out_packet_bytes, B),
+                       self._opt_dev_ptr(d_pcm16, "int16", (B, HOP), "16 kHz pcm"),
+                       self._opt_dev_ptr(d_mix, "int16", (B, HOP), "mix"),
+                       *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B))
+        self._dev_call(self.L.lyra_hip_bridge_tick_dev, C.addressof(t))
+
+    def bridge_begin(self, packets, packet_bytes, rooms, num_bits, muted=None, dtx=None, flags=0, stream_ids=None):
+        """Pipelined tick of the bridge from host arrays (lyra_hip_bridge_begin): packets uint8 [B][23], packet_bytes int32 [B]
+        (0 / 8 / 15 / 23), rooms int32 [B] (a label >= 0, or < 0: in no room), num_bits int32 [B], muted / dtx [B] or None.
+        Up to two ticks in flight; the arrays may be reused at once."""
+        packets = _np(packets, np.uint8, (-1, MAX_PACKET_BYTES))
+        B = packets.shape[0]
+        sizes, labels, bits = (_np(a, np.int32, (B,)) for a in (packet_bytes, rooms, num_bits))
+        m = None if muted is None else _np(np.asarray(muted) != 0, np.int32, (B,))
+        d = None if dtx is None else _np(np.asarray(dtx) != 0, np.int32, (B,))
+        ids = self._ids(stream_ids, B)
+        self._chk(self.L.lyra_hip_bridge_begin(self.h, ids.ctypes.data, B, packets.ctypes.data, sizes.ctypes.data,
+                                               labels.ctypes.data, None if m is None else m.ctypes.data, int(flags),
+                                               bits.ctypes.data, None if d is None else d.ctypes.data))
+        self._pending_bridge_ticks.append(B)
+
+    def bridge_end(self):
+        """-> (out_packets uint8 [B][23], zero behind each packet's bytes; out_packet_bytes, is_noise, is_comfort_noise int32
+        [B]) of the OLDEST tick begun by bridge_begin."""
+        if not self._pending_bridge_ticks:
+            self._chk(self.L.lyra_hip_bridge_end(self.h, None, None, None, None))
+        B = self._pending_bridge_ticks[0]
+        out = np.empty((B, MAX_PACKET_BYTES), np.uint8)
+        lens, noise, cn = (np.empty(B, np.int32) for _ in range(3))
+        rc = self.L.lyra_hip_bridge_end(self.h, out.ctypes.data, lens.ctypes.data, noise.ctypes.data, cn.ctypes.data)
+        self._pending_bridge_ticks.pop(0)   # (the library gives the slot back whatever the wait returns)
+        self._chk(rc)
+        return out, lens, noise, cn
+
+    def bridge_errors(self, clear=False):
+        """d_order entries outside [0, B) that the bridge's mix skipped (synchronises)."""
+        return self._error_count(self.L.lyra_hip_bridge_errors, clear)
 
     def rates_errors(self, clear=False):
         """Sample rates seen by encode_rates_dev / decode_lossy_rates_dev / run_steps with d_rates that are no codec rate

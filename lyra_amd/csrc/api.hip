@@ -155,6 +155,16 @@ struct lyra_hip_ctx {
   int dstr16_cap = 0;
   void* dstr_host = nullptr;         // DstrHost: the two slots of lyra_hip_decode_streams_begin / _end
   long dstr_begun = 0, dstr_ended = 0;   // ... and how many of its calls were begun / ended
+  // the conference bridge (bridge_api.inc)
+  unsigned* d_bridge_err = nullptr;  // d_order entries outside [0, B) that bridge_mix_kernel skipped
+  int16_t* d_brg_mix[2] = {};        // [brg_cap][320] the mix of a tick without d_mix, by lossy-call parity as d_dstr16
+  int32_t* d_brg_flags[2] = {};      // [brg_cap] is_comfort_noise of a tick that skips comfort noise but was given no array
+  int brg_cap = 0;
+  int32_t* d_brg_const = nullptr;    // [2][max_streams] the encode leg's constants: 16000 in every row | 320 * b
+  hipEvent_t ev_brg_mix = nullptr;   // the tick's edge: recorded on sn behind lossy_mix_kernel, waited for by se[0]
+  hipEvent_t lossy_mix_hook = nullptr;   // set by the bridge around lossy_tick_launch only: recorded on sn behind lossy_mix_kernel
+  void* brg_host = nullptr;          // BrgHost: the two slots of lyra_hip_bridge_begin / _end
+  long brg_begun = 0, brg_ended = 0; // ... and how many of its ticks were begun / ended
   // lyra_hip_export_streams / lyra_hip_import_streams (stream_state_api.inc)
   unsigned* d_import_err = nullptr;  // blob rows lyra_hip_import_streams_dev refused
   uint8_t* d_blobs = nullptr;        // staging of the host forms, blob_cap rows
@@ -244,6 +254,7 @@ void pipe_free(lyra_hip_ctx* c);
 void rates_free(lyra_hip_ctx* c);
 void es_free(lyra_hip_ctx* c);
 void dstr_free(lyra_hip_ctx* c);
+void brg_free(lyra_hip_ctx* c);
 void blob_free(lyra_hip_ctx* c);
 void spans_free(lyra_hip_ctx* c);
 // One owner per device buffer.  Buffers that are sized by one count (the frames of a call, the streams of the context) are
@@ -1110,6 +1121,7 @@ void lyra_hip_destroy(lyra_hip_ctx* c) {
   pipe_free(c);
   es_free(c);
   dstr_free(c);
+  brg_free(c);
   spans_free(c);
   if (c->h_zc) (void)hipHostFree(c->h_zc);
   c->h_zc = nullptr;
@@ -2095,6 +2107,7 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
 #include "decode_streams_api.inc"
 #include "decode_samples_any_api.inc"
 #include "decode_samples_streams_api.inc"
+#include "bridge_api.inc"
 #include "stream_state_api.inc"
 #include "spans_api.inc"
 #include "spans_lossy_api.inc"

@@ -183,6 +183,8 @@ int lyra_hip_decode_samples_begin(lyra_hip_ctx* c, const int32_t* ids, int B, co
   DsHost* H = static_cast<DsHost*>(c->ds_host);
   if (H->begun - H->ended >= 2)
     return fail(c, LYRA_HIP_EINVAL, "decode_samples_begin: two requests are already in flight (lyra_hip_decode_samples_end)");
+  if (c->brg_begun != c->brg_ended)   // (the bridge runs on both sides' streams)
+    return fail(c, LYRA_HIP_EINVAL, "decode_samples_begin: a lyra_hip_bridge_begin tick is in flight (lyra_hip_bridge_end)");
   if (c->dstr_begun != c->dstr_ended)   // (as lyra_hip_decode_begin: one decode pipeline at a time)
     return fail(c, LYRA_HIP_EINVAL, "decode_samples_begin: a lyra_hip_decode_streams_begin call is in flight "
                 "(lyra_hip_decode_streams_end)");

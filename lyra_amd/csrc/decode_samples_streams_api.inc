@@ -191,6 +191,8 @@ int lyra_hip_decode_samples_streams_begin(lyra_hip_ctx* c, const int32_t* ids, i
   if (c->dss_begun - c->dss_ended >= 2)
     return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_begin: two requests are already in flight "
                 "(lyra_hip_decode_samples_streams_end)");
+  if (c->brg_begun != c->brg_ended)   // (the bridge runs on both sides' streams)
+    return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_begin: a lyra_hip_bridge_begin tick is in flight (lyra_hip_bridge_end)");
   { const PipeState* P = pipe_of(c);   // (one decode pipeline at a time: they share the decode-side streams' order)
     const DsHost* H = static_cast<const DsHost*>(c->ds_host);
     if ((P && P->d_begun != P->d_ended) || (H && H->begun != H->ended) || c->dstr_begun != c->dstr_ended ||

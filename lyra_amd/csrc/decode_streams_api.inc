@@ -104,6 +104,8 @@ int lyra_hip_decode_streams_begin(lyra_hip_ctx* c, const int32_t* ids, int B, co
   }
   if (c->dstr_begun - c->dstr_ended >= 2)
     return fail(c, LYRA_HIP_EINVAL, "decode_streams_begin: two calls are already in flight (lyra_hip_decode_streams_end)");
+  if (c->brg_begun != c->brg_ended)   // (the bridge runs on both sides' streams)
+    return fail(c, LYRA_HIP_EINVAL, "decode_streams_begin: a lyra_hip_bridge_begin tick is in flight (lyra_hip_bridge_end)");
   { const PipeState* P = pipe_of(c);
     if (P && P->d_begun != P->d_ended)
       return fail(c, LYRA_HIP_EINVAL, "decode_streams_begin: a lyra_hip_decode_begin call is in flight (lyra_hip_decode_end)");

@@ -240,6 +240,10 @@ __global__ void lossy_plan_mixed_kernel(const int32_t* ids, int B, const int32_t
 __global__ void lossy_mix_kernel(const int32_t* ids, int B, const int32_t* info, const int16_t* gan, const int16_t* cng,
                                  const float* fade_w, int16_t* out, const uint8_t* noise_state, int32_t* is_noise,
                                  int32_t* is_cn);
+// ---- conference bridge (bridge_kernels.hip; include/lyra_hip_bridge.h) --------------------------------------------------
+// mix-minus over an inverted membership index: one wavefront per room, bad index entries skipped and counted in *err
+__global__ void bridge_mix_kernel(const int16_t* pcm, int B, const int32_t* order, const int32_t* room_start, int n_rooms,
+                                  int n_members, const int32_t* muted, const int32_t* is_cn, int16_t* mix, unsigned* err);
 // ---- any request size up to one hop (decode_samples_kernels.hip, decode_samples_plan.h; lyra_hip_decode_samples_dev) ------
 // plan: transition, id lists (-1: the row skips the leg), info [B][4], feature ring push / pop, features of starting hops
 __global__ void ds_plan_kernel(const int32_t* ids, int B, const int32_t* pkt_bytes, int n_internal, uint8_t* cng_state,

@@ -101,6 +101,8 @@ int lossy_tick_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_
                      (const int16_t*)gan, (const int16_t*)c->d_lossy_cng, (const float*)c->d_fade, d_pcm16,
                      (const uint8_t*)c->sm.base[st::R_NOISE_D], d_is_noise, d_is_cn);
   HIPCHK(c, hipGetLastError());
+  // (bridge_api.inc: the hop and the mix's flags are complete here; the estimator behind reads `gan` only)
+  if (c->lossy_mix_hook) HIPCHK(c, hipEventRecord(c->lossy_mix_hook, c->sn));
   if ((rc = launch_noise_masked(c, est_ids, B, gan, d_is_noise))) return rc;
   if (d_rates && n_pcm >= 0) {   // per-stream rates, packed rows (decode_streams_api.inc): d_pcm_ext holds n_pcm samples with
     // row b at d_offsets[b] (null: b * LYRA_HIP_MAX_EXT_HOP); a row that leaves the buffer writes nothing

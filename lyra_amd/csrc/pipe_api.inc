@@ -133,6 +133,8 @@ int lyra_hip_encode_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const int1
   if ((rc = pipe_ensure(c))) return rc;
   PipeState* P = pipe_of(c);
   if (P->begun - P->ended >= 2) return fail(c, LYRA_HIP_EINVAL, "encode_begin: two calls are already in flight (lyra_hip_encode_end)");
+  if (c->brg_begun != c->brg_ended)   // (the bridge runs on both sides' streams)
+    return fail(c, LYRA_HIP_EINVAL, "encode_begin: a lyra_hip_bridge_begin tick is in flight (lyra_hip_bridge_end)");
   if (c->es_begun != c->es_ended)   // (the two encode pipelines share the encode-side streams' order: one at a time)
     return fail(c, LYRA_HIP_EINVAL, "encode_begin: a lyra_hip_encode_streams_begin call is in flight (lyra_hip_encode_streams_end)");
   PipeSlot& S = P->slot[P->begun & 1];
@@ -224,6 +226,8 @@ int lyra_hip_decode_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const uint
   if ((rc = pipe_ensure(c))) return rc;
   PipeState* P = pipe_of(c);
   if (P->d_begun - P->d_ended >= 2) return fail(c, LYRA_HIP_EINVAL, "decode_begin: two calls are already in flight (lyra_hip_decode_end)");
+  if (c->brg_begun != c->brg_ended)   // (the bridge runs on both sides' streams)
+    return fail(c, LYRA_HIP_EINVAL, "decode_begin: a lyra_hip_bridge_begin tick is in flight (lyra_hip_bridge_end)");
   if (c->dstr_begun != c->dstr_ended)   // (the decode pipelines share the decode-side streams' order: one at a time)
     return fail(c, LYRA_HIP_EINVAL, "decode_begin: a lyra_hip_decode_streams_begin call is in flight (lyra_hip_decode_streams_end)");
   if (c->dsa_begun != c->dsa_ended)

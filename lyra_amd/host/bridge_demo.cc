@@ -1,0 +1,99 @@
+// bridge_demo.cc -- drives LyraConferenceBridge (lyra_conference_bridge.h) through a scripted call:
+//   bridge_demo <model_dir> <streams.txt> <script.i32> <packets_in.bin> <lengths_in.i32> <packets_out.bin> <lengths_out.i32>
+//               <mode> <skip_comfort_noise>
+// streams.txt: one line "bitrate enable_dtx" per stream.  script: [ticks][num_streams][3] int32 -- room (< 0: none), muted,
+// bitrate of every stream as of that tick, applied before the tick is begun.  packets_in: [ticks][num_streams][23] bytes;
+// lengths_in: [ticks][num_streams] int32, 0 = no packet from that stream on that tick.  Writes every tick's outgoing packets
+// [num_streams][23] and lengths [num_streams] int32.
+// mode 0: Tick() per tick.  mode 1: the same call through TickAsync / WaitTick, two ticks deep (tick t + 1 is begun before tick
+// t is waited for); it must write the same two files.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iterator>
+#include <memory>
+#include <vector>
+
+#include "lyra_conference_bridge.h"
+
+using namespace chromemedia::codec;
+
+namespace {
+
+constexpr int kRow = kBridgePacketRowBytes;
+
+template <class T>
+bool ReadFile(const char* path, std::vector<T>* out) {
+  std::ifstream in(path, std::ios::binary);
+  if (!in) return false;
+  std::vector<char> raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+  if (raw.size() % sizeof(T) != 0) return false;
+  out->resize(raw.size() / sizeof(T));
+  if (!raw.empty()) std::memcpy(out->data(), raw.data(), raw.size());
+  return true;
+}
+
+int Fail(const char* what) {
+  std::fprintf(stderr, "bridge_demo: %s\n", what);
+  return 1;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc != 10) {
+    std::fprintf(stderr, "usage: bridge_demo <model_dir> <streams.txt> <script.i32> <packets_in.bin> <lengths_in.i32> "
+                         "<packets_out.bin> <lengths_out.i32> <mode 0|1> <skip_comfort_noise 0|1>\n");
+    return 2;
+  }
+  std::vector<BridgeStream> streams;
+  {
+    std::ifstream f(argv[2]);
+    int bitrate, dtx;
+    while (f >> bitrate >> dtx) streams.push_back({bitrate, dtx != 0});
+  }
+  const size_t n = streams.size();
+  std::vector<int32_t> script, lengths;
+  std::vector<uint8_t> packets;
+  if (n == 0 || !ReadFile(argv[3], &script) || !ReadFile(argv[4], &packets) || !ReadFile(argv[5], &lengths))
+    return Fail("unreadable input");
+  const size_t ticks = lengths.size() / n;
+  if (lengths.size() != ticks * n || script.size() != ticks * n * 3 || packets.size() != ticks * n * kRow)
+    return Fail("the input files disagree about ticks and streams");
+  const bool pipelined = std::atoi(argv[8]) != 0;
+  auto bridge = LyraConferenceBridge::Create(absl::MakeConstSpan(streams), argv[1], 0, std::atoi(argv[9]) != 0);
+  if (!bridge) return Fail("Create failed");
+  std::ofstream out_pk(argv[6], std::ios::binary), out_len(argv[7], std::ios::binary);
+  std::vector<uint8_t> rows(n * kRow);
+  std::vector<int32_t> lens(n);
+  auto deliver = [&]() {
+    if (!bridge->WaitTick(absl::Span<uint8_t>(rows.data(), rows.size()), absl::Span<int32_t>(lens.data(), lens.size()))) return false;
+    out_pk.write(reinterpret_cast<const char*>(rows.data()), static_cast<std::streamsize>(rows.size()));
+    out_len.write(reinterpret_cast<const char*>(lens.data()), static_cast<std::streamsize>(lens.size() * sizeof(int32_t)));
+    return true;
+  };
+  for (size_t t = 0; t < ticks; ++t) {
+    for (size_t s = 0; s < n; ++s) {
+      const int32_t* row = &script[(t * n + s) * 3];
+      if (!bridge->SetRoom(static_cast<int>(s), row[0]) || !bridge->SetMuted(static_cast<int>(s), row[1] != 0) ||
+          !bridge->set_bitrate(static_cast<int>(s), row[2]))
+        return Fail("the script names a setting the bridge refuses");
+    }
+    if (!bridge->SetEncodedPackets(absl::MakeConstSpan(&packets[t * n * kRow], n * kRow), absl::MakeConstSpan(&lengths[t * n], n)))
+      return Fail("SetEncodedPackets failed");
+    if (!pipelined) {
+      auto got = bridge->Tick();
+      if (!got) return Fail("Tick failed");
+      out_pk.write(reinterpret_cast<const char*>(got->first.data()), static_cast<std::streamsize>(got->first.size()));
+      out_len.write(reinterpret_cast<const char*>(got->second.data()), static_cast<std::streamsize>(got->second.size() * sizeof(int32_t)));
+      continue;
+    }
+    if (!bridge->TickAsync()) return Fail("TickAsync failed");
+    if (t >= 1 && !deliver()) return Fail("WaitTick failed");
+  }
+  if (pipelined)
+    while (bridge->ticks_in_flight() > 0)
+      if (!deliver()) return Fail("WaitTick failed");
+  return 0;
+}

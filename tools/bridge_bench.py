@@ -1,0 +1,262 @@
+"""Throughput of the conference bridge (include/lyra_hip_bridge.h): JSON lines appended to --out.  4096 participants, a packet per
+participant and tick (speech encoded at 6 kb/s) under Gilbert loss at 10 %, outgoing 6 kb/s with DTX on every other stream.
+  (a) "tick_dev":   one lyra_hip_bridge_tick_dev per tick, as a C caller issues it (without the binding's stream brackets:
+                    torch_order = False) -- with rooms of 4, rooms of 16 and ONE room of all participants (one wavefront sums
+                    4096 rows: the kernel's worst case);
+  (b) "python_mix": what a Python caller could do before: decode_lossy_mixed_dev, torch index_add_ / gather / clamp on the caller's
+                    stream (bracketed by lyra_hip_stream_wait / lyra_hip_wait_for_stream, which the binding does around every
+                    `_dev` call), encode_streams_dev;
+  (c) "begin_end":  lyra_hip_bridge_begin / _end two deep from host arrays, against "host_three_calls": the blocking host path --
+                    decode_streams_begin / _end, a numpy mix, encode_streams_begin / _end;
+  (d) "run_steps":  the ceiling: the same batch through lyra_hip_run_steps_dev with independent encode (DTX) and lossy decode legs
+                    and no mix.
+Forms of one comparison ALTERNATE window by window on contexts of their own; every shape is warmed up first; `reps` windows per
+form, median and min..max in ticks x streams per second.  (a) and (c) are verified against (b) on a prefix of ticks: outgoing
+packets and sizes bit for bit ((d) computes something else and is not).  "mix_kernel_us": the mix alone, device events around
+back-to-back lyra_hip_bridge_mix_dev calls (memset + kernel), per layout.
+    python tools/bridge_bench.py [--streams 4096] [--hops 200] [--reps 5] [--out profiles/bridge.jsonl]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def stats(B, hops, ts):
+    f = sorted(B * hops / t for t in ts)
+    return {"ticks_x_streams_per_s_median": round(f[len(f) // 2]), "min": round(f[0]), "max": round(f[-1])}
+
+
+def timed(windows, reps):
+    """windows: name -> (callable, context); alternated, rep 0 warms every shape up and is not counted"""
+    import torch
+    times = {k: [] for k in windows}
+    for rep in range(reps + 1):
+        for name, (run, ctx) in windows.items():
+            ctx.synchronize()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run()
+            ctx.synchronize()
+            torch.cuda.synchronize()
+            if rep:
+                times[name].append(time.perf_counter() - t0)
+    return times
+
+
+def np_mix(x, room_of, first_rows):
+    """the mix-minus where every room's rows lie together (first_rows: each room's first row; everybody a source), vectorised"""
+    x = x.astype(np.int32)
+    s = np.add.reduceat(x, first_rows, axis=0)
+    return np.clip(s[room_of] - x, -32768, 32767).astype(np.int16)
+
+
+def main():
+    import torch
+    import lyra_amd
+    from lyra_amd import codec
+    from lossy_steps_bench import gilbert, speech_ring
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", type=int, default=4096)
+    ap.add_argument("--hops", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--verify", type=int, default=12, help="ticks of the prefix on which the forms are compared")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bridge.jsonl"))
+    a = ap.parse_args()
+    B, dev, ring = a.streams, torch.device("cuda", 0), 50
+    rng = np.random.default_rng(3)
+    t_ = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
+    d_ids = torch.arange(B, dtype=torch.int32, device=dev)
+    ids = np.arange(B, dtype=np.int32)
+    # ---- the incoming packets: `ring` hops of speech per participant, encoded once at 120 bits -----------------------------
+    speech = speech_ring(ring, B, rng)
+    prep = lyra_amd.LyraHip(device=0, max_streams=B)
+    pk = np.zeros((ring, B, 23), np.uint8)
+    d15 = torch.zeros((B, 15), dtype=torch.uint8, device=dev)
+    for t in range(ring):
+        prep.encode_dev(d_ids, t_(speech[t]), 120, d15)
+        prep.synchronize()
+        pk[t, :, :15] = d15.cpu().numpy()
+    prep.close()
+    rx = gilbert(rng, a.hops, B, 0.10)
+    nb = (rx.astype(np.int32) * 15)
+    bits = np.full(B, 120, np.int32)
+    dtx = (np.arange(B) % 2).astype(np.int32)
+    d_pk, d_nb, d_bits, d_dtx = t_(pk), t_(nb), t_(bits), t_(dtx)
+    layouts = {"rooms_of_4": ids // 4, "rooms_of_16": ids // 16, "one_room": np.zeros(B, np.int32)}
+    lines, ref_b = [], []   # ref_b: form (b)'s packets and sizes on the prefix, rooms of 4
+
+    def new_bufs():
+        return ([torch.zeros((B, 23), dtype=torch.uint8, device=dev) for _ in range(2)],
+                [torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2)],
+                [torch.zeros((B, 320), dtype=torch.int16, device=dev) for _ in range(2)],
+                [torch.zeros((B, 320), dtype=torch.int16, device=dev) for _ in range(2)])
+
+    # ---- (a) against (b), per layout ---------------------------------------------------------------------------------------
+    for name, room_of in layouts.items():
+        order, start = codec.bridge_plan(room_of)
+        n_rooms = start.size - 1
+        d_order, d_start, d_room = t_(order), t_(start), t_(room_of.astype(np.int64))
+        ca, cb = lyra_amd.LyraHip(device=0, max_streams=B), lyra_amd.LyraHip(device=0, max_streams=B)
+        try:
+            # (a) has no torch work between its calls: it runs as a C caller would, without the binding's brackets around every
+            # `_dev` call (which order each call behind the WHOLE call before it); its inputs are complete before the first tick
+            ca.torch_order = False
+            out_a, len_a, _, _ = new_bufs()
+            out_b, len_b, x_b, mix_b = new_bufs()
+            rates16 = torch.full((B,), 16000, dtype=torch.int32, device=dev)
+            offs = torch.arange(B, dtype=torch.int32, device=dev) * 320
+            sums = torch.zeros((n_rooms, 320), dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
+
+            def tick_a(t):
+                ca.bridge_tick_dev(d_ids, d_pk[t % ring], d_nb[t], d_order, d_start, d_bits, out_a[t & 1], len_a[t & 1],
+                                   None, d_dtx)
+
+            def tick_b(t):
+                k = t & 1
+                cb.decode_lossy_mixed_dev(d_ids, d_pk[t % ring], d_nb[t], 16000, x_b[k])
+                x = x_b[k].to(torch.int32)
+                sums.zero_()
+                sums.index_add_(0, d_room, x)
+                mix_b[k].copy_((sums[d_room] - x).clamp_(-32768, 32767))
+                cb.encode_streams_dev(d_ids, mix_b[k], rates16, d_bits, out_b[k], len_b[k], d_dtx, offs, 320 * B)
+
+            verified = 0
+            for t in range(min(a.verify, a.hops)):
+                tick_a(t)
+                tick_b(t)
+                ca.synchronize()
+                cb.synchronize()
+                torch.cuda.synchronize()
+                la, lb = len_a[t & 1].cpu().numpy(), len_b[t & 1].cpu().numpy()
+                pa, pb = out_a[t & 1].cpu().numpy(), out_b[t & 1].cpu().numpy()
+                same = np.array_equal(la, lb) and all(np.array_equal(pa[b, :la[b]], pb[b, :la[b]]) for b in range(B))
+                if not same:
+                    raise SystemExit(f"{name}: tick_dev and python_mix differ at tick {t}")
+                verified += 1
+                if name == "rooms_of_4":
+                    ref_b.append((pb.copy(), lb.copy()))
+            ca.reset()
+            cb.reset()
+            times = timed({"tick_dev": (lambda: [tick_a(t) for t in range(a.hops)], ca),
+                           "python_mix": (lambda: [tick_b(t) for t in range(a.hops)], cb)}, a.reps)
+            line = {"bench": "bridge", "case": "dev", "layout": name, "streams": B, "rooms": int(n_rooms), "loss": 0.10,
+                    "hops": a.hops, "reps": a.reps, "verified_ticks": verified}
+            for k, ts in times.items():
+                line[k] = stats(B, a.hops, ts)
+            line["tick_dev_over_python_mix"] = round(line["tick_dev"]["ticks_x_streams_per_s_median"] /
+                                                     line["python_mix"]["ticks_x_streams_per_s_median"], 3)
+            # the mix alone: events on the encode-side stream around back-to-back calls (no binding brackets)
+            ca.synchronize()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            per, n, how = [], 100, "device events around 100 calls back to back (memset + kernel)"
+            try:
+                st = torch.cuda.ExternalStream(ca.stream_handle(), device=dev)
+            except Exception:   # no way to put an event on the library's stream: the host clock around the same calls
+                st, how = None, "host clock around 100 calls back to back and a synchronise (memset + kernel + launches)"
+            for rep in range(a.reps + 1):
+                t0 = time.perf_counter()
+                if st is not None:
+                    e0.record(st)
+                for _ in range(n):
+                    ca.bridge_mix_dev(x_b[0], d_order, d_start, mix_b[1])
+                if st is not None:
+                    e1.record(st)
+                ca.synchronize()
+                if rep:
+                    per.append((e0.elapsed_time(e1) * 1000.0 if st is not None else (time.perf_counter() - t0) * 1e6) / n)
+            per.sort()
+            line["mix_kernel_us"] = {"median": round(per[len(per) // 2], 2), "min": round(per[0], 2), "max": round(per[-1], 2), "what": how}
+            line["errors"] = {"bridge": int(ca.bridge_errors()), "lossy": int(ca.decode_lossy_errors()),
+                              "mixed": int(ca.encode_mixed_errors())}
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+        finally:
+            ca.close()
+            cb.close()
+
+    # ---- (c) the host forms, rooms of 4 ------------------------------------------------------------------------------------
+    room_of = layouts["rooms_of_4"]
+    cc, ch = lyra_amd.LyraHip(device=0, max_streams=B), lyra_amd.LyraHip(device=0, max_streams=B)
+    try:
+        rates16 = np.full(B, 16000, np.int32)
+        first_rows = np.flatnonzero(np.diff(room_of, prepend=-1))
+
+        def host_three(t):
+            ch.decode_streams_begin(pk[t % ring], nb[t], rates16)
+            x, _, _ = ch.decode_streams_end()
+            ch.encode_streams_begin(np_mix(x.reshape(B, 320), room_of, first_rows), rates16, bits, dtx)
+            return ch.encode_streams_end()
+
+        def begin_end(hops, keep=None):
+            for t in range(hops):
+                cc.bridge_begin(pk[t % ring], nb[t], room_of, bits, None, dtx)
+                if t >= 1:
+                    got = cc.bridge_end()
+                    if keep is not None:
+                        keep.append(got)
+            got = cc.bridge_end()
+            if keep is not None:
+                keep.append(got)
+
+        n_ver = min(a.verify, a.hops)
+        got = []
+        begin_end(n_ver, got)
+        for t in range(n_ver):
+            want, (pb, lb) = host_three(t), ref_b[t]
+            for form, (p, n) in (("begin_end", got[t][:2]), ("host_three_calls", want)):
+                if not (np.array_equal(n, lb) and all(np.array_equal(p[b, :lb[b]], pb[b, :lb[b]]) for b in range(B))):
+                    raise SystemExit(f"{form} and python_mix differ at tick {t}")
+        cc.reset()
+        ch.reset()
+        times = timed({"begin_end": (lambda: begin_end(a.hops), cc),
+                       "host_three_calls": (lambda: [host_three(t) for t in range(a.hops)], ch)}, a.reps)
+        line = {"bench": "bridge", "case": "host", "layout": "rooms_of_4", "streams": B, "loss": 0.10, "hops": a.hops,
+                "reps": a.reps, "verified_ticks": n_ver}
+        for k, ts in times.items():
+            line[k] = stats(B, a.hops, ts)
+        line["begin_end_over_host_three_calls"] = round(line["begin_end"]["ticks_x_streams_per_s_median"] /
+                                                        line["host_three_calls"]["ticks_x_streams_per_s_median"], 3)
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    finally:
+        cc.close()
+        ch.close()
+
+    # ---- (d) the ceiling: run_steps, independent legs, no mix --------------------------------------------------------------
+    cd = lyra_amd.LyraHip(device=0, max_streams=B)
+    try:
+        d_ring = t_(speech)
+        d_rx = t_(rx)
+        pkts = [torch.zeros((B, 15), dtype=torch.uint8, device=dev) for _ in range(2)]
+        lens = [torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2)]
+        outs = [torch.zeros((B, 320), dtype=torch.int16, device=dev) for _ in range(2)]
+
+        def steps():
+            cd.run_steps_dev(d_ids, 120, a.hops, 0, d_ring, pkts, outs, d_packet_bytes=lens, dtx=True, packet_loss=True,
+                             d_received_ring=d_rx)
+
+        times = timed({"run_steps": (steps, cd)}, a.reps)
+        line = {"bench": "bridge", "case": "ceiling", "streams": B, "loss": 0.10, "hops": a.hops, "reps": a.reps,
+                "run_steps": stats(B, a.hops, times["run_steps"]),
+                "what": "encode (DTX) + lossy decode legs of lyra_hip_run_steps_dev, no mix, not verified against the bridge"}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    finally:
+        cd.close()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "a") as f:
+        for line in lines:
+            f.write(json.dumps(line) + "\n")
+
+
+if __name__ == "__main__":
+    main()
