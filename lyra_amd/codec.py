@@ -397,11 +397,44 @@ def bridge_plan(rooms, lib=None):
     return order[:n_members.value].copy(), start[:n_rooms.value + 1].copy()
 
 
+class SpeakersTick(C.Structure):
+    """lyra_hip_speakers_tick (include/lyra_hip_speakers.h): the fields of BridgeTick, then the selection's"""
+    _fields_ = BridgeTick._fields_ + [("max_speakers", C.c_int), ("d_levels", C.c_void_p), ("d_is_speaker", C.c_void_p)]
+
+
+SPEAKERS_SKIP_COMFORT_NOISE = 1   # LYRA_HIP_SPEAKERS_SKIP_COMFORT_NOISE
+SPEAKERS_MAX = 8                  # LYRA_HIP_SPEAKERS_MAX
+
+
+def _signatures_speakers():
+    """The same for include/lyra_hip_speakers.h (tests/test_speakers_cpu.py holds each entry to its prototype)."""
+    vp, ci, cu = C.c_void_p, C.c_int, C.c_uint
+    table = {
+        "speakers_mix_dev": [vp, vp, ci, vp, vp, ci, ci, vp, vp, ci, vp, vp, vp], "speakers_tick_dev": [vp, vp],
+        "speakers_begin": [vp, vp, ci, vp, vp, vp, vp, cu, vp, vp, ci], "speakers_end": [vp] * 7,
+    }
+    return {"lyra_hip_" + name: (ci, args) for name, args in table.items()}
+
+
+_SIGNATURES_SPEAKERS = _signatures_speakers()
+
+
+def _load_speakers(L, path):
+    """_SIGNATURES_SPEAKERS applied to a loaded library; one that lacks a function of it is refused."""
+    for name, (restype, argtypes) in _SIGNATURES_SPEAKERS.items():
+        fn = getattr(L, name, None)
+        if fn is None:
+            raise LyraHipError(f"{path} does not export {name}")
+        fn.restype, fn.argtypes = restype, argtypes
+    return L
+
+
 def _load(path=None):
     """The C-ABI library (default: library_path()); a second path loads a build variant beside it (lyra_amd/variants/).
     A library that lacks a function of _SIGNATURES, _SIGNATURES_SPANS_MIXED, _SIGNATURES_SPANS_RATES, _SIGNATURES_SPANS_PACKED,
     _SIGNATURES_ENCODE_STREAMS, _SIGNATURES_DECODE_STREAMS, _SIGNATURES_DECODE_SAMPLES_ANY or
-    _SIGNATURES_DECODE_SAMPLES_STREAMS is refused, and so is one that lacks a function of _SIGNATURES_BRIDGE (_load_bridge)."""
+    _SIGNATURES_DECODE_SAMPLES_STREAMS is refused, and so is one that lacks a function of _SIGNATURES_BRIDGE (_load_bridge) or _SIGNATURES_SPEAKERS
+    (_load_speakers)."""
     path = os.path.abspath(path or library_path())
     if path in _libs:
         return _libs[path]
@@ -429,7 +462,7 @@ def _load(path=None):
         if fn is None:
             raise LyraHipError(f"{path} does not export {name}")
         fn.restype, fn.argtypes = restype, argtypes
-    _libs[path] = _load_bridge(L, path)
+    _libs[path] = _load_speakers(_load_bridge(L, path), path)
     return L
 
 
@@ -485,6 +518,7 @@ class LyraHip:
         self._pending_stream_decodes = []   # (B, packed samples) of the hops begun by decode_streams_begin, oldest first
         self._pending_sample_stream_decodes = []   # the same for decode_samples_streams_begin
         self._pending_bridge_ticks = []     # B of the ticks begun by bridge_begin, oldest first
+        self._pending_speakers_ticks = []   # ... and by speakers_begin (the library holds both kinds in one queue of two)
 
     def _create(self, h, mode, model_dir, device, max_streams, weights_image):
         if weights_image is not None:   # bytes of a lyra_v1.lyrapack (lyra_hip_create_from_image)
@@ -1065,13 +1099,90 @@ class LyraHip:
         out = np.empty((B, MAX_PACKET_BYTES), np.uint8)
         lens, noise, cn = (np.empty(B, np.int32) for _ in range(3))
         rc = self.L.lyra_hip_bridge_end(self.h, out.ctypes.data, lens.ctypes.data, noise.ctypes.data, cn.ctypes.data)
-        self._pending_bridge_ticks.pop(0)   # (the library gives the slot back whatever the wait returns)
+        self._chk_other_kind(rc)            # (refused: the oldest tick is speakers_begin's; nothing was consumed)
+        self._pending_bridge_ticks.pop(0)   # (otherwise the library gives the slot back whatever the wait returns)
         self._chk(rc)
         return out, lens, noise, cn
+
+    def _chk_other_kind(self, rc):
+        """bridge_end / speakers_end on a tick that the other begin() started: the library refuses and keeps the tick"""
+        if rc != 0 and "the oldest tick was begun by" in self.last_error():
+            self._chk(rc)
 
     def bridge_errors(self, clear=False):
         """d_order entries outside [0, B) that the bridge's mix skipped (synchronises)."""
         return self._error_count(self.L.lyra_hip_bridge_errors, clear)
+
+    # -- the bridge with loudest-N selection (include/lyra_hip_speakers.h) -----------------------------
+    def speakers_mix_dev(self, d_pcm16, d_order, d_room_start, d_mix, max_speakers, d_muted=None, d_is_comfort_noise=None,
+                         d_levels=None, d_is_speaker=None):
+        """The selection mix alone (lyra_hip_speakers_mix_dev): the buffers of bridge_mix_dev; max_speakers in
+        1 .. SPEAKERS_MAX; d_levels int64 [B] and d_is_speaker int32 [B]: optional outputs, written for every row.  Row b of
+        d_mix receives the clamped sum of the max_speakers loudest sources of its room, itself left out.  Bad d_order entries
+        are skipped and counted in bridge_errors.  Completes on the encode-side stream."""
+        B = d_pcm16.shape[0]
+        n_members, n_rooms = d_order.shape[0], d_room_start.shape[0] - 1
+        self._dev_call(self.L.lyra_hip_speakers_mix_dev, self._p_pcm(d_pcm16, B), B,
+                       self._dev_ptr(d_order, "int32", (n_members,), "order") if n_members else None,
+                       self._dev_ptr(d_room_start, "int32", (n_rooms + 1,), "room_start"), n_rooms, n_members,
+                       self._opt_dev_ptr(d_muted, "int32", (B,), "muted"),
+                       self._opt_dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise"), int(max_speakers),
+                       self._p_pcm(d_mix, B), self._opt_dev_ptr(d_levels, "int64", (B,), "levels"),
+                       self._opt_dev_ptr(d_is_speaker, "int32", (B,), "is_speaker"))
+
+    def speakers_tick_dev(self, d_ids, d_packets, d_packet_bytes, d_order, d_room_start, d_num_bits, d_out_packets,
+                          d_out_packet_bytes, max_speakers, d_muted=None, d_dtx=None, flags=0, d_pcm16=None, d_mix=None,
+                          d_is_noise=None, d_is_comfort_noise=None, d_levels=None, d_is_speaker=None):
+        """One tick of the bridge with selection (lyra_hip_speakers_tick_dev): bridge_tick_dev with the mix of
+        speakers_mix_dev (flags: SPEAKERS_SKIP_COMFORT_NOISE) and its two further optional outputs, d_levels int64 [B] and
+        d_is_speaker int32 [B].  Bit for bit the three calls in a row, outputs and stream state."""
+        B = d_packets.shape[0]
+        n_members, n_rooms = d_order.shape[0], d_room_start.shape[0] - 1
+        t = SpeakersTick(self._p_ids(d_ids, B), B, self._p_packets(d_packets, B, MAX_PACKET_BYTES),
+                         self._p_packet_bytes(d_packet_bytes, B),
+                         self._dev_ptr(d_order, "int32", (n_members,), "order") if n_members else None,
+                         self._dev_ptr(d_room_start, "int32", (n_rooms + 1,), "room_start"), n_rooms, n_members,
+                         self._opt_dev_ptr(d_muted, "int32", (B,), "muted"), int(flags),
+                         self._dev_ptr(d_num_bits, "int32", (B,), "num_bits"),
+                         self._opt_dev_ptr(d_dtx, "int32", (B,), "dtx flags"),
+                         self._p_packets(d_out_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_out_packet_bytes, B),
+                         self._opt_dev_ptr(d_pcm16, "int16", (B, HOP), "16 kHz pcm"),
+                         self._opt_dev_ptr(d_mix, "int16", (B, HOP), "mix"),
+                         *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B), int(max_speakers),
+                         self._opt_dev_ptr(d_levels, "int64", (B,), "levels"),
+                         self._opt_dev_ptr(d_is_speaker, "int32", (B,), "is_speaker"))
+        self._dev_call(self.L.lyra_hip_speakers_tick_dev, C.addressof(t))
+
+    def speakers_begin(self, packets, packet_bytes, rooms, num_bits, max_speakers, muted=None, dtx=None, flags=0,
+                       stream_ids=None):
+        """Pipelined tick of the bridge with selection from host arrays (lyra_hip_speakers_begin): the arrays of bridge_begin
+        and max_speakers in 1 .. SPEAKERS_MAX.  Up to two ticks in flight, bridge_begin's included."""
+        packets = _np(packets, np.uint8, (-1, MAX_PACKET_BYTES))
+        B = packets.shape[0]
+        sizes, labels, bits = (_np(a, np.int32, (B,)) for a in (packet_bytes, rooms, num_bits))
+        m = None if muted is None else _np(np.asarray(muted) != 0, np.int32, (B,))
+        d = None if dtx is None else _np(np.asarray(dtx) != 0, np.int32, (B,))
+        ids = self._ids(stream_ids, B)
+        self._chk(self.L.lyra_hip_speakers_begin(self.h, ids.ctypes.data, B, packets.ctypes.data, sizes.ctypes.data,
+                                                 labels.ctypes.data, None if m is None else m.ctypes.data, int(flags),
+                                                 bits.ctypes.data, None if d is None else d.ctypes.data, int(max_speakers)))
+        self._pending_speakers_ticks.append(B)
+
+    def speakers_end(self):
+        """-> (out_packets uint8 [B][23], out_packet_bytes, is_noise, is_comfort_noise int32 [B], levels int64 [B], is_speaker
+        int32 [B]) of the OLDEST tick in flight, which must be one begun by speakers_begin."""
+        if not self._pending_speakers_ticks:
+            self._chk(self.L.lyra_hip_speakers_end(self.h, None, None, None, None, None, None))
+        B = self._pending_speakers_ticks[0]
+        out = np.empty((B, MAX_PACKET_BYTES), np.uint8)
+        lens, noise, cn, spk = (np.empty(B, np.int32) for _ in range(4))
+        levels = np.empty(B, np.int64)
+        rc = self.L.lyra_hip_speakers_end(self.h, out.ctypes.data, lens.ctypes.data, noise.ctypes.data, cn.ctypes.data,
+                                          levels.ctypes.data, spk.ctypes.data)
+        self._chk_other_kind(rc)              # (refused: the oldest tick is bridge_begin's; nothing was consumed)
+        self._pending_speakers_ticks.pop(0)   # (otherwise the library gives the slot back whatever the wait returns)
+        self._chk(rc)
+        return out, lens, noise, cn, levels, spk
 
     def rates_errors(self, clear=False):
         """Sample rates seen by encode_rates_dev / decode_lossy_rates_dev / run_steps with d_rates that are no codec rate

@@ -165,6 +165,13 @@ struct lyra_hip_ctx {
   hipEvent_t lossy_mix_hook = nullptr;   // set by the bridge around lossy_tick_launch only: recorded on sn behind lossy_mix_kernel
   void* brg_host = nullptr;          // BrgHost: the two slots of lyra_hip_bridge_begin / _end
   long brg_begun = 0, brg_ended = 0; // ... and how many of its ticks were begun / ended
+  // loudest-N selection (speakers_api.inc): the scratch of its three kernels, [2] by lossy-call parity as d_brg_mix
+  int32_t* d_spk_list[2] = {};       // [spk_cap][8] the speaker rows of every room, -1 padded
+  int32_t* d_spk_pos_room[2] = {};   // [spk_cap] the room of every position of the index (-1: none)
+  unsigned long long* d_spk_keys[2] = {};   // [spk_cap] the candidate keys of rooms above 64 members
+  int64_t* d_spk_levels[2] = {};     // [spk_cap] the levels of a call that was given no array
+  int32_t* d_spk_flags[2] = {};      // [spk_cap] ... and its speaker flags
+  int spk_cap = 0;
   // lyra_hip_export_streams / lyra_hip_import_streams (stream_state_api.inc)
   unsigned* d_import_err = nullptr;  // blob rows lyra_hip_import_streams_dev refused
   uint8_t* d_blobs = nullptr;        // staging of the host forms, blob_cap rows
@@ -255,6 +262,7 @@ void rates_free(lyra_hip_ctx* c);
 void es_free(lyra_hip_ctx* c);
 void dstr_free(lyra_hip_ctx* c);
 void brg_free(lyra_hip_ctx* c);
+void spk_free(lyra_hip_ctx* c);
 void blob_free(lyra_hip_ctx* c);
 void spans_free(lyra_hip_ctx* c);
 // One owner per device buffer.  Buffers that are sized by one count (the frames of a call, the streams of the context) are
@@ -1122,6 +1130,7 @@ void lyra_hip_destroy(lyra_hip_ctx* c) {
   es_free(c);
   dstr_free(c);
   brg_free(c);
+  spk_free(c);
   spans_free(c);
   if (c->h_zc) (void)hipHostFree(c->h_zc);
   c->h_zc = nullptr;
@@ -2108,6 +2117,7 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
 #include "decode_samples_any_api.inc"
 #include "decode_samples_streams_api.inc"
 #include "bridge_api.inc"
+#include "speakers_api.inc"
 #include "stream_state_api.inc"
 #include "spans_api.inc"
 #include "spans_lossy_api.inc"

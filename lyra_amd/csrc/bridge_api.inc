@@ -21,6 +21,7 @@ struct BrgSlot {
   uint8_t* d_out = nullptr;
   hipEvent_t ev_done = nullptr;
   int B = 0;
+  int max_speakers = 0;        // 0: a full-mix tick (lyra_hip_bridge_begin); else a tick of lyra_hip_speakers_begin
 };
 struct BrgHost { BrgSlot slot[2]; };
 
@@ -28,6 +29,15 @@ struct BrgHost { BrgSlot slot[2]; };
 constexpr size_t kBrgInArrays = 7;
 size_t brg_in_bytes(size_t n) { return (kBrgInArrays * n + 1) * 4 + n * LYRA_HIP_MAX_PACKET_BYTES; }
 size_t brg_out_bytes(size_t n) { return 3 * n * 4 + n * LYRA_HIP_MAX_PACKET_BYTES; }
+// a tick of lyra_hip_speakers_begin (speakers_api.inc) comes down through the same slots as
+// [out_packet_bytes | is_noise | is_comfort_noise | is_speaker] int32, levels int64, out packets: the slots have room for it
+constexpr size_t kSpkOutWords = 6;
+size_t spk_out_bytes(size_t n) { return kSpkOutWords * n * 4 + n * LYRA_HIP_MAX_PACKET_BYTES; }
+// speakers_api.inc: the scratch of the selection mix, and its three kernels on se[0]
+int spk_ensure(lyra_hip_ctx* c, int B);
+int spk_mix_launch(lyra_hip_ctx* c, const int16_t* d_pcm16, int B, const int32_t* d_order, const int32_t* d_room_start,
+                   int n_rooms, int n_members, const int32_t* d_muted, const int32_t* d_is_cn, int max_speakers, int16_t* d_mix,
+                   int64_t* d_levels, int32_t* d_is_speaker, int set);
 
 void brg_free(lyra_hip_ctx* c) {
   dfree(c->d_brg_mix[0], c->d_brg_mix[1], c->d_brg_flags[0], c->d_brg_flags[1], c->d_brg_const, c->d_bridge_err);
@@ -49,9 +59,9 @@ void brg_free(lyra_hip_ctx* c) {
 int brg_slot_ensure(lyra_hip_ctx* c, BrgSlot* S) {
   const size_t n = (size_t)c->max_streams;
   if (!S->h_in) HIPCHK(c, hipHostMalloc((void**)&S->h_in, brg_in_bytes(n), hipHostMallocDefault));
-  if (!S->h_out) HIPCHK(c, hipHostMalloc((void**)&S->h_out, brg_out_bytes(n), hipHostMallocDefault));
+  if (!S->h_out) HIPCHK(c, hipHostMalloc((void**)&S->h_out, spk_out_bytes(n), hipHostMallocDefault));
   if (!S->d_in) HIPCHK(c, dalloc(&S->d_in, brg_in_bytes(n)));
-  if (!S->d_out) HIPCHK(c, dalloc(&S->d_out, brg_out_bytes(n)));
+  if (!S->d_out) HIPCHK(c, dalloc(&S->d_out, spk_out_bytes(n)));
   if (!S->ev_done) HIPCHK(c, hipEventCreateWithFlags(&S->ev_done, hipEventDisableTiming));
   return 0;
 }
@@ -127,6 +137,140 @@ bool brg_other_in_flight(lyra_hip_ctx* c) {
          c->dss_begun != c->dss_ended || c->twin_out_n != 0;
 }
 
+// One tick, for both kinds of mix.  max_speakers 0: the full mix of lyra_hip_bridge_tick_dev; 1 .. 8: the selection mix of
+// lyra_hip_speakers_tick_dev (speakers_api.inc) with its two further outputs.  `what` names the call in messages.
+int brg_tick_impl(lyra_hip_ctx* c, const char* what, const lyra_hip_bridge_tick* T, int max_speakers, int64_t* d_levels,
+                  int32_t* d_is_speaker) {
+  const int B = T->B;
+  int rc = check_batch(c, B);
+  if (rc) return rc;
+  if (!T->d_stream_ids || !T->d_packets || !T->d_packet_bytes || !T->d_num_bits || !T->d_out_packets || !T->d_out_packet_bytes)
+    return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
+  if ((rc = brg_check_index(c, what, B, T->d_order, T->d_room_start, T->n_rooms, T->n_members))) return rc;
+  if (T->flags & ~LYRA_HIP_BRIDGE_SKIP_COMFORT_NOISE) return fail(c, LYRA_HIP_EINVAL, "%s: unknown flags 0x%x", what, T->flags);
+  if (brg_misaligned(T->d_pcm16) || brg_misaligned(T->d_mix) || (T->d_mix && T->d_pcm16 == T->d_mix))
+    return fail(c, LYRA_HIP_EINVAL, "%s: d_pcm16 and d_mix must be 16-byte aligned and distinct", what);
+  DEVSCOPE(c);
+  // everything the tick allocates or builds on first use, BEFORE anything is enqueued
+  if ((rc = ensure_scratch(c, B))) return rc;
+  if ((rc = rates_ensure(c))) return rc;
+  if ((rc = lossy_ensure(c, B))) return rc;
+  if (!T->d_pcm16 && (rc = dstr16_ensure(c, B))) return rc;
+  if ((rc = brg_ensure(c, B))) return rc;
+  if (max_speakers && (rc = spk_ensure(c, B))) return rc;
+  const int set = (int)(c->n_lossy_calls & 1);
+  const bool skip_cn = (T->flags & LYRA_HIP_BRIDGE_SKIP_COMFORT_NOISE) != 0;
+  int16_t* pcm16 = T->d_pcm16 ? T->d_pcm16 : c->d_dstr16[set];
+  int16_t* mix = T->d_mix ? T->d_mix : c->d_brg_mix[set];
+  int32_t* is_cn = T->d_is_comfort_noise ? T->d_is_comfort_noise : skip_cn ? c->d_brg_flags[set] : nullptr;
+  // ---- decode leg: lyra_hip_decode_lossy_mixed_dev at 16 kHz, with the event behind its mix ----
+  c->lossy_mix_hook = c->ev_brg_mix;
+  rc = lossy_tick_launch(c, T->d_stream_ids, B, T->d_packets, T->d_packet_bytes, nullptr, 0, 16000, pcm16, nullptr, T->d_is_noise,
+                         is_cn, LOSSY_MIXED_BYTES);
+  c->lossy_mix_hook = nullptr;
+  if (rc) return rc;
+  // ---- the edge and the mix: se[0] behind this tick's hop and flags ----
+  if ((rc = enc_cross_begin(c, 0, 1))) return rc;
+  HIPCHK(c, hipStreamWaitEvent(c->se[0], c->ev_brg_mix, 0));
+  rc = max_speakers ? spk_mix_launch(c, pcm16, B, T->d_order, T->d_room_start, T->n_rooms, T->n_members, T->d_muted,
+                                     skip_cn ? is_cn : nullptr, max_speakers, mix, d_levels, d_is_speaker, set)
+                    : brg_mix_launch(c, pcm16, B, T->d_order, T->d_room_start, T->n_rooms, T->n_members, T->d_muted,
+                                     skip_cn ? is_cn : nullptr, mix);
+  if (rc) return rc;
+  // ---- encode leg ----
+  const int32_t* rates16 = c->d_brg_const;
+  return lyra_hip_encode_streams_dev(c, T->d_stream_ids, B, mix, 320L * B, rates16 + c->max_streams, rates16, T->d_num_bits,
+                                     T->d_dtx, T->d_out_packets, T->d_out_packet_bytes);
+}
+
+// begin() of both kinds of tick (max_speakers as in brg_tick_impl): one validation, one staging, one upload, one download
+int brg_begin_impl(lyra_hip_ctx* c, const char* what, const int32_t* ids, int B, const uint8_t* packets,
+                   const int32_t* packet_bytes, const int32_t* rooms, const int32_t* muted, unsigned flags,
+                   const int32_t* num_bits, const int32_t* dtx, int max_speakers) {
+  int rc = check_batch(c, B);
+  if (rc) return rc;
+  if (!packets || !packet_bytes || !rooms || !num_bits) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
+  if (flags & ~LYRA_HIP_BRIDGE_SKIP_COMFORT_NOISE) return fail(c, LYRA_HIP_EINVAL, "%s: unknown flags 0x%x", what, flags);
+  if ((rc = check_ids_host(c, ids, B))) return rc;
+  for (int b = 0; b < B; ++b) {
+    if ((rc = check_bits(c, num_bits[b]))) return rc;
+    const int pb = packet_bytes[b];   // PacketSizeToNumQuantizedBits (lyra_config.h:99-106), 0: no packet on this tick
+    if (pb != 0 && pb != 8 && pb != 15 && pb != LYRA_HIP_MAX_PACKET_BYTES)
+      return fail(c, LYRA_HIP_EINVAL, "%s: packet of %d bytes at position %d (0, 8, 15 or 23)", what, pb, b);
+  }
+  if (c->brg_begun - c->brg_ended >= 2)
+    return fail(c, LYRA_HIP_EINVAL, "%s: two ticks are already in flight (call _end first)", what);
+  if (brg_other_in_flight(c))
+    return fail(c, LYRA_HIP_EINVAL, "%s: another pipelined request is in flight (call its _end first)", what);
+  DEVSCOPE(c);
+  if (!c->brg_host) c->brg_host = new BrgHost();
+  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->brg_begun & 1];
+  if ((rc = brg_slot_ensure(c, &S))) return rc;
+  // (the slot's previous user, two ticks back, has ended: its kernels on every stream have read d_in, its download has left
+  // d_out and h_out)
+  const size_t n = (size_t)B;
+  int32_t* h = reinterpret_cast<int32_t*>(S.h_in);
+  int n_rooms = 0, n_members = 0;
+  if (bridge::plan(rooms, B, h + 2 * n, h + 6 * n, &n_rooms, &n_members))
+    return fail(c, LYRA_HIP_EINVAL, "%s: a room of more than %d members", what, LYRA_HIP_BRIDGE_MAX_ROOM);
+  // everything the tick allocates or builds on first use, BEFORE anything is enqueued: a failure here leaves the streams idle
+  if ((rc = ensure_scratch(c, B))) return rc;
+  if ((rc = rates_ensure(c))) return rc;
+  if ((rc = lossy_ensure(c, B))) return rc;
+  if ((rc = dstr16_ensure(c, B))) return rc;
+  if ((rc = brg_ensure(c, B))) return rc;
+  if (max_speakers && (rc = spk_ensure(c, B))) return rc;
+  for (int b = 0; b < B; ++b) {
+    h[b] = ids[b];
+    h[n + b] = packet_bytes[b];
+    h[3 * n + b] = muted ? (muted[b] != 0) : 0;
+    h[4 * n + b] = num_bits[b];
+    h[5 * n + b] = dtx ? (dtx[b] != 0) : 0;
+  }
+  std::memcpy(S.h_in + (kBrgInArrays * n + 1) * 4, packets, n * LYRA_HIP_MAX_PACKET_BYTES);
+  // one upload from pinned staging on the decode-side stream, in front of the tick's first kernel.  The encode leg reads ids,
+  // bits and DTX flags on se[0] / sq[0]: both are behind the tick's edge, which is behind the decode-side half and so the copy.
+  HIPCHK(c, hipMemcpyAsync(S.d_in, S.h_in, brg_in_bytes(n), hipMemcpyHostToDevice, c->sd[0]));
+  const int32_t* m = reinterpret_cast<const int32_t*>(S.d_in);
+  int32_t* o = reinterpret_cast<int32_t*>(S.d_out);
+  const size_t out_words = max_speakers ? kSpkOutWords : 3;
+  uint8_t* out_pk = S.d_out + out_words * n * 4;
+  // empty packets, and the bytes behind a shorter one, read back as zeros; the extractor's stream is ahead of the quantizer's
+  HIPCHK(c, hipMemsetAsync(out_pk, 0, n * LYRA_HIP_MAX_PACKET_BYTES, c->se[0]));
+  lyra_hip_bridge_tick T = {};
+  T.d_stream_ids = m;
+  T.B = B;
+  T.d_packets = S.d_in + (kBrgInArrays * n + 1) * 4;
+  T.d_packet_bytes = m + n;
+  T.d_order = m + 2 * n;
+  T.d_room_start = m + 6 * n;
+  T.n_rooms = n_rooms;
+  T.n_members = n_members;
+  T.d_muted = muted ? m + 3 * n : nullptr;
+  T.flags = flags;
+  T.d_num_bits = m + 4 * n;
+  T.d_dtx = dtx ? m + 5 * n : nullptr;
+  T.d_out_packets = out_pk;
+  T.d_out_packet_bytes = o;
+  T.d_is_noise = o + n;
+  T.d_is_comfort_noise = o + 2 * n;
+  // (a selection tick: is_speaker behind the three int32 arrays, then the levels, 8-byte aligned at 16 * n bytes)
+  if ((rc = brg_tick_impl(c, what, &T, max_speakers, max_speakers ? reinterpret_cast<int64_t*>(o + 4 * n) : nullptr,
+                          max_speakers ? o + 3 * n : nullptr)))
+    return rc;
+  // packets and sizes are written by the quantizer on sq[0], the flags by the noise-stream half: the one download rides on
+  // sq[0] behind the end of that half (the quantizer itself is already enqueued and does not wait for it).  The levels and
+  // speaker flags of a selection tick are written on se[0] by the mix's kernels: the quantizer on sq[0] waits for the
+  // extractor's event on se[0] (encq_handoff, api.hip), which is enqueued behind them, so sq[0] is behind them as well.
+  HIPCHK(c, hipStreamWaitEvent(c->sq[0], c->ev_noise[(c->n_noise_calls - 1) & 1], 0));
+  HIPCHK(c, hipMemcpyAsync(S.h_out, S.d_out, out_words * n * 4 + n * LYRA_HIP_MAX_PACKET_BYTES, hipMemcpyDeviceToHost, c->sq[0]));
+  HIPCHK(c, hipEventRecord(S.ev_done, c->sq[0]));
+  S.B = B;
+  S.max_speakers = max_speakers;
+  c->brg_begun++;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -155,132 +299,24 @@ int lyra_hip_bridge_mix_dev(lyra_hip_ctx* c, const int16_t* d_pcm16, int B, cons
 int lyra_hip_bridge_tick_dev(lyra_hip_ctx* c, const lyra_hip_bridge_tick* T) {
   if (!c) return LYRA_HIP_EINVAL;
   if (!T) return fail(c, LYRA_HIP_EINVAL, "bridge_tick: null pointer");
-  const int B = T->B;
-  int rc = check_batch(c, B);
-  if (rc) return rc;
-  if (!T->d_stream_ids || !T->d_packets || !T->d_packet_bytes || !T->d_num_bits || !T->d_out_packets || !T->d_out_packet_bytes)
-    return fail(c, LYRA_HIP_EINVAL, "bridge_tick: null pointer");
-  if ((rc = brg_check_index(c, "bridge_tick", B, T->d_order, T->d_room_start, T->n_rooms, T->n_members))) return rc;
-  if (T->flags & ~LYRA_HIP_BRIDGE_SKIP_COMFORT_NOISE) return fail(c, LYRA_HIP_EINVAL, "bridge_tick: unknown flags 0x%x", T->flags);
-  if (brg_misaligned(T->d_pcm16) || brg_misaligned(T->d_mix) || (T->d_mix && T->d_pcm16 == T->d_mix))
-    return fail(c, LYRA_HIP_EINVAL, "bridge_tick: d_pcm16 and d_mix must be 16-byte aligned and distinct");
-  DEVSCOPE(c);
-  // everything the tick allocates or builds on first use, BEFORE anything is enqueued
-  if ((rc = ensure_scratch(c, B))) return rc;
-  if ((rc = rates_ensure(c))) return rc;
-  if ((rc = lossy_ensure(c, B))) return rc;
-  if (!T->d_pcm16 && (rc = dstr16_ensure(c, B))) return rc;
-  if ((rc = brg_ensure(c, B))) return rc;
-  const int set = (int)(c->n_lossy_calls & 1);
-  const bool skip_cn = (T->flags & LYRA_HIP_BRIDGE_SKIP_COMFORT_NOISE) != 0;
-  int16_t* pcm16 = T->d_pcm16 ? T->d_pcm16 : c->d_dstr16[set];
-  int16_t* mix = T->d_mix ? T->d_mix : c->d_brg_mix[set];
-  int32_t* is_cn = T->d_is_comfort_noise ? T->d_is_comfort_noise : skip_cn ? c->d_brg_flags[set] : nullptr;
-  // ---- decode leg: lyra_hip_decode_lossy_mixed_dev at 16 kHz, with the event behind its mix ----
-  c->lossy_mix_hook = c->ev_brg_mix;
-  rc = lossy_tick_launch(c, T->d_stream_ids, B, T->d_packets, T->d_packet_bytes, nullptr, 0, 16000, pcm16, nullptr, T->d_is_noise,
-                         is_cn, LOSSY_MIXED_BYTES);
-  c->lossy_mix_hook = nullptr;
-  if (rc) return rc;
-  // ---- the edge and the mix: se[0] behind this tick's hop and flags ----
-  if ((rc = enc_cross_begin(c, 0, 1))) return rc;
-  HIPCHK(c, hipStreamWaitEvent(c->se[0], c->ev_brg_mix, 0));
-  if ((rc = brg_mix_launch(c, pcm16, B, T->d_order, T->d_room_start, T->n_rooms, T->n_members, T->d_muted,
-                           skip_cn ? is_cn : nullptr, mix)))
-    return rc;
-  // ---- encode leg ----
-  const int32_t* rates16 = c->d_brg_const;
-  return lyra_hip_encode_streams_dev(c, T->d_stream_ids, B, mix, 320L * B, rates16 + c->max_streams, rates16, T->d_num_bits,
-                                     T->d_dtx, T->d_out_packets, T->d_out_packet_bytes);
+  return brg_tick_impl(c, "bridge_tick", T, 0, nullptr, nullptr);
 }
 
 int lyra_hip_bridge_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const uint8_t* packets, const int32_t* packet_bytes,
                           const int32_t* rooms, const int32_t* muted, unsigned flags, const int32_t* num_bits,
                           const int32_t* dtx) {
   if (!c) return LYRA_HIP_EINVAL;
-  int rc = check_batch(c, B);
-  if (rc) return rc;
-  if (!packets || !packet_bytes || !rooms || !num_bits) return fail(c, LYRA_HIP_EINVAL, "bridge_begin: null pointer");
-  if (flags & ~LYRA_HIP_BRIDGE_SKIP_COMFORT_NOISE) return fail(c, LYRA_HIP_EINVAL, "bridge_begin: unknown flags 0x%x", flags);
-  if ((rc = check_ids_host(c, ids, B))) return rc;
-  for (int b = 0; b < B; ++b) {
-    if ((rc = check_bits(c, num_bits[b]))) return rc;
-    const int pb = packet_bytes[b];   // PacketSizeToNumQuantizedBits (lyra_config.h:99-106), 0: no packet on this tick
-    if (pb != 0 && pb != 8 && pb != 15 && pb != LYRA_HIP_MAX_PACKET_BYTES)
-      return fail(c, LYRA_HIP_EINVAL, "bridge_begin: packet of %d bytes at position %d (0, 8, 15 or 23)", pb, b);
-  }
-  if (c->brg_begun - c->brg_ended >= 2)
-    return fail(c, LYRA_HIP_EINVAL, "bridge_begin: two ticks are already in flight (lyra_hip_bridge_end)");
-  if (brg_other_in_flight(c))
-    return fail(c, LYRA_HIP_EINVAL, "bridge_begin: another pipelined request is in flight (call its _end first)");
-  DEVSCOPE(c);
-  if (!c->brg_host) c->brg_host = new BrgHost();
-  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->brg_begun & 1];
-  if ((rc = brg_slot_ensure(c, &S))) return rc;
-  // (the slot's previous user, two ticks back, has ended: its kernels on every stream have read d_in, its download has left
-  // d_out and h_out)
-  const size_t n = (size_t)B;
-  int32_t* h = reinterpret_cast<int32_t*>(S.h_in);
-  int n_rooms = 0, n_members = 0;
-  if (bridge::plan(rooms, B, h + 2 * n, h + 6 * n, &n_rooms, &n_members))
-    return fail(c, LYRA_HIP_EINVAL, "bridge_begin: a room of more than %d members", LYRA_HIP_BRIDGE_MAX_ROOM);
-  // everything the tick allocates or builds on first use, BEFORE anything is enqueued: a failure here leaves the streams idle
-  if ((rc = ensure_scratch(c, B))) return rc;
-  if ((rc = rates_ensure(c))) return rc;
-  if ((rc = lossy_ensure(c, B))) return rc;
-  if ((rc = dstr16_ensure(c, B))) return rc;
-  if ((rc = brg_ensure(c, B))) return rc;
-  for (int b = 0; b < B; ++b) {
-    h[b] = ids[b];
-    h[n + b] = packet_bytes[b];
-    h[3 * n + b] = muted ? (muted[b] != 0) : 0;
-    h[4 * n + b] = num_bits[b];
-    h[5 * n + b] = dtx ? (dtx[b] != 0) : 0;
-  }
-  std::memcpy(S.h_in + (kBrgInArrays * n + 1) * 4, packets, n * LYRA_HIP_MAX_PACKET_BYTES);
-  // one upload from pinned staging on the decode-side stream, in front of the tick's first kernel.  The encode leg reads ids,
-  // bits and DTX flags on se[0] / sq[0]: both are behind the tick's edge, which is behind the decode-side half and so the copy.
-  HIPCHK(c, hipMemcpyAsync(S.d_in, S.h_in, brg_in_bytes(n), hipMemcpyHostToDevice, c->sd[0]));
-  const int32_t* m = reinterpret_cast<const int32_t*>(S.d_in);
-  int32_t* o = reinterpret_cast<int32_t*>(S.d_out);
-  uint8_t* out_pk = S.d_out + 3 * n * 4;
-  // empty packets, and the bytes behind a shorter one, read back as zeros; the extractor's stream is ahead of the quantizer's
-  HIPCHK(c, hipMemsetAsync(out_pk, 0, n * LYRA_HIP_MAX_PACKET_BYTES, c->se[0]));
-  lyra_hip_bridge_tick T = {};
-  T.d_stream_ids = m;
-  T.B = B;
-  T.d_packets = S.d_in + (kBrgInArrays * n + 1) * 4;
-  T.d_packet_bytes = m + n;
-  T.d_order = m + 2 * n;
-  T.d_room_start = m + 6 * n;
-  T.n_rooms = n_rooms;
-  T.n_members = n_members;
-  T.d_muted = muted ? m + 3 * n : nullptr;
-  T.flags = flags;
-  T.d_num_bits = m + 4 * n;
-  T.d_dtx = dtx ? m + 5 * n : nullptr;
-  T.d_out_packets = out_pk;
-  T.d_out_packet_bytes = o;
-  T.d_is_noise = o + n;
-  T.d_is_comfort_noise = o + 2 * n;
-  if ((rc = lyra_hip_bridge_tick_dev(c, &T))) return rc;
-  // packets and sizes are written by the quantizer on sq[0], the flags by the noise-stream half: the one download rides on
-  // sq[0] behind the end of that half (the quantizer itself is already enqueued and does not wait for it)
-  HIPCHK(c, hipStreamWaitEvent(c->sq[0], c->ev_noise[(c->n_noise_calls - 1) & 1], 0));
-  HIPCHK(c, hipMemcpyAsync(S.h_out, S.d_out, brg_out_bytes(n), hipMemcpyDeviceToHost, c->sq[0]));
-  HIPCHK(c, hipEventRecord(S.ev_done, c->sq[0]));
-  S.B = B;
-  c->brg_begun++;
-  return 0;
+  return brg_begin_impl(c, "bridge_begin", ids, B, packets, packet_bytes, rooms, muted, flags, num_bits, dtx, 0);
 }
 
 int lyra_hip_bridge_end(lyra_hip_ctx* c, uint8_t* out_packets, int32_t* out_packet_bytes, int32_t* is_noise,
                         int32_t* is_comfort_noise) {
   if (!c) return LYRA_HIP_EINVAL;
   if (!c->brg_host || c->brg_ended == c->brg_begun) return fail(c, LYRA_HIP_EINVAL, "bridge_end: no tick in flight");
+  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->brg_ended & 1];
+  if (S.max_speakers) return fail(c, LYRA_HIP_EINVAL, "bridge_end: the oldest tick was begun by lyra_hip_speakers_begin");
   if (!out_packets || !out_packet_bytes) return fail(c, LYRA_HIP_EINVAL, "bridge_end: null pointer");
   DEVSCOPE(c);
-  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->brg_ended & 1];
   c->brg_ended++;                  // whatever happens below, the slot is given back
   HIPCHK(c, hipEventSynchronize(S.ev_done));
   const size_t n = (size_t)S.B;

@@ -244,6 +244,19 @@ __global__ void lossy_mix_kernel(const int32_t* ids, int B, const int32_t* info,
 // mix-minus over an inverted membership index: one wavefront per room, bad index entries skipped and counted in *err
 __global__ void bridge_mix_kernel(const int16_t* pcm, int B, const int32_t* order, const int32_t* room_start, int n_rooms,
                                   int n_members, const int32_t* muted, const int32_t* is_cn, int16_t* mix, unsigned* err);
+// ---- loudest-N speaker selection (speakers_kernels.hip; include/lyra_hip_speakers.h) --------------------------------------
+// level[b] = sum of squares of row b (int64), for every row; zeroes row b of mix, is_speaker[b], and pos_room[b] to -1
+__global__ void speakers_level_kernel(const int16_t* pcm, int B, long long* levels, int16_t* mix, int32_t* is_speaker,
+                                      int32_t* pos_room, int n_members);
+// one wavefront per room over levels and the index only: the room's max_speakers loudest candidates into spk[room][8] (-1
+// padded) and is_speaker, the room number of every position into pos_room; bad index entries counted in *err (here only)
+__global__ void speakers_select_kernel(const long long* levels, int B, const int32_t* order, const int32_t* room_start,
+                                       int n_rooms, int n_members, const int32_t* muted, const int32_t* is_cn,
+                                       int max_speakers, unsigned long long* keys, int32_t* spk, int32_t* pos_room,
+                                       int32_t* is_speaker, unsigned* err);
+// one wavefront per 8 consecutive positions of the index: the sum of the room's speaker rows minus the listener's own
+__global__ void speakers_mix_kernel(const int16_t* pcm, int B, const int32_t* order, int n_members, const int32_t* pos_room,
+                                    int n_rooms, const int32_t* spk, int16_t* mix);
 // ---- any request size up to one hop (decode_samples_kernels.hip, decode_samples_plan.h; lyra_hip_decode_samples_dev) ------
 // plan: transition, id lists (-1: the row skips the leg), info [B][4], feature ring push / pop, features of starting hops
 __global__ void ds_plan_kernel(const int32_t* ids, int B, const int32_t* pkt_bytes, int n_internal, uint8_t* cng_state,

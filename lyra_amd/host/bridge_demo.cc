@@ -1,21 +1,25 @@
 // bridge_demo.cc -- drives LyraConferenceBridge (lyra_conference_bridge.h) through a scripted call:
 //   bridge_demo <model_dir> <streams.txt> <script.i32> <packets_in.bin> <lengths_in.i32> <packets_out.bin> <lengths_out.i32>
-//               <mode> <skip_comfort_noise>
+//               <mode> <skip_comfort_noise> [--max-speakers=N --speakers-out=<speakers_out.i32>]
 // streams.txt: one line "bitrate enable_dtx" per stream.  script: [ticks][num_streams][3] int32 -- room (< 0: none), muted,
 // bitrate of every stream as of that tick, applied before the tick is begun.  packets_in: [ticks][num_streams][23] bytes;
 // lengths_in: [ticks][num_streams] int32, 0 = no packet from that stream on that tick.  Writes every tick's outgoing packets
 // [num_streams][23] and lengths [num_streams] int32.
 // mode 0: Tick() per tick.  mode 1: the same call through TickAsync / WaitTick, two ticks deep (tick t + 1 is begun before tick
 // t is waited for); it must write the same two files.
+// --max-speakers=N: the same call through LyraSpeakerBridge (lyra_speaker_bridge.h), every room mixed from its N loudest
+// sources; every delivered tick's speaker flags [num_streams] int32 go to the file of --speakers-out.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iterator>
 #include <memory>
+#include <utility>
 #include <vector>
 
 #include "lyra_conference_bridge.h"
+#include "lyra_speaker_bridge.h"
 
 using namespace chromemedia::codec;
 
@@ -41,10 +45,23 @@ int Fail(const char* what) {
 
 }  // namespace
 
-int main(int argc, char** argv) {
-  if (argc != 10) {
+int main(int argc_all, char** argv_all) {
+  // options first: what is left is the nine positional arguments
+  int max_speakers = 0;
+  const char* speakers_path = nullptr;
+  std::vector<char*> positional;
+  for (int i = 0; i < argc_all; ++i) {
+    if (std::strncmp(argv_all[i], "--max-speakers=", 15) == 0) max_speakers = std::atoi(argv_all[i] + 15);
+    else if (std::strncmp(argv_all[i], "--speakers-out=", 15) == 0) speakers_path = argv_all[i] + 15;
+    else positional.push_back(argv_all[i]);
+  }
+  const int argc = static_cast<int>(positional.size());
+  char** argv = positional.data();
+  const bool select = max_speakers != 0 || speakers_path != nullptr;
+  if (argc != 10 || (select && (max_speakers == 0 || speakers_path == nullptr))) {
     std::fprintf(stderr, "usage: bridge_demo <model_dir> <streams.txt> <script.i32> <packets_in.bin> <lengths_in.i32> "
-                         "<packets_out.bin> <lengths_out.i32> <mode 0|1> <skip_comfort_noise 0|1>\n");
+                         "<packets_out.bin> <lengths_out.i32> <mode 0|1> <skip_comfort_noise 0|1> "
+                         "[--max-speakers=N --speakers-out=<speakers_out.i32>]\n");
     return 2;
   }
   std::vector<BridgeStream> streams;
@@ -62,15 +79,31 @@ int main(int argc, char** argv) {
   if (lengths.size() != ticks * n || script.size() != ticks * n * 3 || packets.size() != ticks * n * kRow)
     return Fail("the input files disagree about ticks and streams");
   const bool pipelined = std::atoi(argv[8]) != 0;
-  auto bridge = LyraConferenceBridge::Create(absl::MakeConstSpan(streams), argv[1], 0, std::atoi(argv[9]) != 0);
+  std::unique_ptr<LyraConferenceBridge> bridge;
+  LyraSpeakerBridge* speakers = nullptr;
+  if (select) {
+    auto b = LyraSpeakerBridge::Create(absl::MakeConstSpan(streams), argv[1], 0, std::atoi(argv[9]) != 0, max_speakers);
+    speakers = b.get();
+    bridge = std::move(b);
+  } else {
+    bridge = LyraConferenceBridge::Create(absl::MakeConstSpan(streams), argv[1], 0, std::atoi(argv[9]) != 0);
+  }
   if (!bridge) return Fail("Create failed");
-  std::ofstream out_pk(argv[6], std::ios::binary), out_len(argv[7], std::ios::binary);
+  std::ofstream out_pk(argv[6], std::ios::binary), out_len(argv[7], std::ios::binary), out_spk;
+  if (speakers) out_spk.open(speakers_path, std::ios::binary);
+  auto write_speakers = [&]() {   // as of the tick just delivered
+    if (!speakers) return;
+    std::vector<int32_t> flags(n);
+    for (size_t s = 0; s < n; ++s) flags[s] = speakers->is_speaker(static_cast<int>(s)) ? 1 : 0;
+    out_spk.write(reinterpret_cast<const char*>(flags.data()), static_cast<std::streamsize>(flags.size() * sizeof(int32_t)));
+  };
   std::vector<uint8_t> rows(n * kRow);
   std::vector<int32_t> lens(n);
   auto deliver = [&]() {
     if (!bridge->WaitTick(absl::Span<uint8_t>(rows.data(), rows.size()), absl::Span<int32_t>(lens.data(), lens.size()))) return false;
     out_pk.write(reinterpret_cast<const char*>(rows.data()), static_cast<std::streamsize>(rows.size()));
     out_len.write(reinterpret_cast<const char*>(lens.data()), static_cast<std::streamsize>(lens.size() * sizeof(int32_t)));
+    write_speakers();
     return true;
   };
   for (size_t t = 0; t < ticks; ++t) {
@@ -87,6 +120,7 @@ int main(int argc, char** argv) {
       if (!got) return Fail("Tick failed");
       out_pk.write(reinterpret_cast<const char*>(got->first.data()), static_cast<std::streamsize>(got->first.size()));
       out_len.write(reinterpret_cast<const char*>(got->second.data()), static_cast<std::streamsize>(got->second.size() * sizeof(int32_t)));
+      write_speakers();
       continue;
     }
     if (!bridge->TickAsync()) return Fail("TickAsync failed");

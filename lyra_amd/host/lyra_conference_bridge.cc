@@ -37,9 +37,8 @@ LyraConferenceBridge::LyraConferenceBridge(lyra_hip_ctx* ctx, absl::Span<const B
   }
 }
 
-std::unique_ptr<LyraConferenceBridge> LyraConferenceBridge::Create(absl::Span<const BridgeStream> streams,
-                                                                  const ghc::filesystem::path& model_path, int device,
-                                                                  bool skip_comfort_noise) {
+lyra_hip_ctx* LyraConferenceBridge::NewBridgeContext(absl::Span<const BridgeStream> streams,
+                                                     const ghc::filesystem::path& model_path, int device) {
   const int n = static_cast<int>(streams.size());
   if (n == 0) {
     LOG(ERROR) << "num_streams must be positive.";
@@ -51,11 +50,27 @@ std::unique_ptr<LyraConferenceBridge> LyraConferenceBridge::Create(absl::Span<co
       return nullptr;
     }
   lyra_hip_ctx* ctx = NewContext(model_path, device, n);
-  if (ctx == nullptr) {
-    LOG(ERROR) << "Could not create the bridge's context.";
-    return nullptr;
-  }
+  if (ctx == nullptr) LOG(ERROR) << "Could not create the bridge's context.";
+  return ctx;
+}
+
+std::unique_ptr<LyraConferenceBridge> LyraConferenceBridge::Create(absl::Span<const BridgeStream> streams,
+                                                                  const ghc::filesystem::path& model_path, int device,
+                                                                  bool skip_comfort_noise) {
+  lyra_hip_ctx* ctx = NewBridgeContext(streams, model_path, device);
+  if (ctx == nullptr) return nullptr;
   return std::unique_ptr<LyraConferenceBridge>(new LyraConferenceBridge(ctx, streams, skip_comfort_noise));
+}
+
+int LyraConferenceBridge::BeginTick(lyra_hip_ctx* ctx, const int32_t* ids, int n, const uint8_t* packets,
+                                    const int32_t* packet_bytes, const int32_t* rooms, const int32_t* muted, unsigned flags,
+                                    const int32_t* bits, const int32_t* dtx) {
+  return lyra_hip_bridge_begin(ctx, ids, n, packets, packet_bytes, rooms, muted, flags, bits, dtx);
+}
+
+int LyraConferenceBridge::EndTick(lyra_hip_ctx* ctx, uint8_t* rows, int32_t* lengths, int32_t* is_noise,
+                                  int32_t* is_comfort_noise) {
+  return lyra_hip_bridge_end(ctx, rows, lengths, is_noise, is_comfort_noise);
 }
 
 LyraConferenceBridge::~LyraConferenceBridge() { lyra_hip_destroy(ctx_); }
@@ -126,6 +141,7 @@ bool LyraConferenceBridge::ResetStream(int stream) {
   }
   staged_bytes_[stream] = 0;
   noise_[stream] = cn_[stream] = 0;
+  ForgetStream(stream);
   return true;
 }
 
@@ -192,8 +208,8 @@ bool LyraConferenceBridge::TickAsync() {
     return false;
   }
   // (begin() copies every array at call time: rooms, mutes and bitrates set after it reach the next tick only)
-  if (lyra_hip_bridge_begin(ctx_, ids_.data(), num_streams(), staged_.data(), staged_bytes_.data(), rooms_.data(), muted_.data(),
-                            flags_, bits_.data(), dtx_.data()) != 0) {
+  if (BeginTick(ctx_, ids_.data(), num_streams(), staged_.data(), staged_bytes_.data(), rooms_.data(), muted_.data(), flags_,
+                bits_.data(), dtx_.data()) != 0) {
     LOG(ERROR) << "Unable to run the tick: " << lyra_hip_last_error(ctx_);
     failed_ = true;
     return false;
@@ -219,7 +235,7 @@ bool LyraConferenceBridge::WaitTick(absl::Span<uint8_t> rows, absl::Span<int32_t
     return false;
   }
   --in_flight_;
-  if (lyra_hip_bridge_end(ctx_, rows.data(), lengths.data(), noise_.data(), cn_.data()) != 0) {
+  if (EndTick(ctx_, rows.data(), lengths.data(), noise_.data(), cn_.data()) != 0) {
     LOG(ERROR) << "Unable to run the tick: " << lyra_hip_last_error(ctx_);
     failed_ = true;   // the tick's packets are lost and the streams have moved on
     return false;

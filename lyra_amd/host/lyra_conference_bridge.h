@@ -37,7 +37,7 @@ class LyraConferenceBridge {
   static std::unique_ptr<LyraConferenceBridge> Create(absl::Span<const BridgeStream> streams,
                                                       const ghc::filesystem::path& model_path, int device = 0,
                                                       bool skip_comfort_noise = false);
-  ~LyraConferenceBridge();
+  virtual ~LyraConferenceBridge();
   // Membership, mute and the outgoing bitrate (LyraEncoder::set_bitrate) of one stream, from the NEXT tick begun; ticks in
   // flight keep what they were begun with.  room < 0: in no room (hears silence, is heard by nobody).  false for a stream
   // that does not exist, an unsupported bitrate, or a room that would exceed 32767 members.
@@ -70,9 +70,21 @@ class LyraConferenceBridge {
   int num_streams() const { return static_cast<int>(ids_.size()); }
   int ticks_in_flight() const { return in_flight_; }
 
- private:
+ protected:
+  // For a bridge with another mix (lyra_speaker_bridge.h): the host logic above is this class's, and the device calls of a
+  // tick go through the three hooks below.  NewBridgeContext is what Create checks and creates: nullptr + LOG(ERROR) if
+  // `streams` is empty or a bitrate is unsupported.
   LyraConferenceBridge(lyra_hip_ctx* ctx, absl::Span<const BridgeStream> streams, bool skip_comfort_noise);
+  static lyra_hip_ctx* NewBridgeContext(absl::Span<const BridgeStream> streams, const ghc::filesystem::path& model_path,
+                                        int device);
+  // begin() and end() of the C ABI's two-deep host form: 0 on success; the arrays hold num_streams entries.
+  virtual int BeginTick(lyra_hip_ctx* ctx, const int32_t* ids, int n, const uint8_t* packets, const int32_t* packet_bytes,
+                        const int32_t* rooms, const int32_t* muted, unsigned flags, const int32_t* bits, const int32_t* dtx);
+  virtual int EndTick(lyra_hip_ctx* ctx, uint8_t* rows, int32_t* lengths, int32_t* is_noise, int32_t* is_comfort_noise);
+  virtual void ForgetStream(int stream) { (void)stream; }   // ResetStream: what a subclass holds per stream reads false again
   bool Exists(int stream) const { return stream >= 0 && stream < num_streams(); }
+
+ private:
   lyra_hip_ctx* ctx_;
   unsigned flags_;
   std::vector<int32_t> ids_;            // stream slots 0 .. num_streams - 1 of the context

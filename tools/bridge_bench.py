@@ -14,7 +14,15 @@ Forms of one comparison ALTERNATE window by window on contexts of their own; eve
 form, median and min..max in ticks x streams per second.  (a) and (c) are verified against (b) on a prefix of ticks: outgoing
 packets and sizes bit for bit ((d) computes something else and is not).  "mix_kernel_us": the mix alone, device events around
 back-to-back lyra_hip_bridge_mix_dev calls (memset + kernel), per layout.
-    python tools/bridge_bench.py [--streams 4096] [--hops 200] [--reps 5] [--out profiles/bridge.jsonl]"""
+--max-speakers N runs the loudest-N leg INSTEAD (include/lyra_hip_speakers.h), per layout, three forms alternating in one run:
+  "speakers_tick_dev": one lyra_hip_speakers_tick_dev per tick (torch_order = False, as (a));
+  "tick_dev":          (a), the full mix, on the same packets;
+  "python_select":     the same selection in torch between the two existing calls: levels, topk per room over the keys
+                       (level << 15 | 32767 - position, so that ties fall as the kernel's), index_add_, gather, clamp.
+speakers_tick_dev is verified against python_select on the prefix, packets and sizes bit for bit.  "select_kernels_us": the
+three kernels alone around back-to-back lyra_hip_speakers_mix_dev calls; "empty_share": the share of empty outgoing packets
+(what DTX did not have to send) over one further pass of --hops ticks, of all streams and of the streams with DTX on.
+    python tools/bridge_bench.py [--streams 4096] [--hops 200] [--reps 5] [--max-speakers N] [--out profiles/bridge.jsonl]"""
 import argparse
 import json
 import os
@@ -67,6 +75,7 @@ def main():
     ap.add_argument("--hops", type=int, default=200)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--verify", type=int, default=12, help="ticks of the prefix on which the forms are compared")
+    ap.add_argument("--max-speakers", type=int, default=0, help="run the loudest-N leg with this N instead of the legs above")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bridge.jsonl"))
     a = ap.parse_args()
     B, dev, ring = a.streams, torch.device("cuda", 0), 50
@@ -97,6 +106,130 @@ def main():
                 [torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2)],
                 [torch.zeros((B, 320), dtype=torch.int16, device=dev) for _ in range(2)],
                 [torch.zeros((B, 320), dtype=torch.int16, device=dev) for _ in range(2)])
+
+    def append(lines):
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "a") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+    # ---- the loudest-N leg, per layout (rooms of one size M, a room's rows together) ----------------------------------------
+    if a.max_speakers:
+        N = a.max_speakers
+        for name, room_of in layouts.items():
+            order, start = codec.bridge_plan(room_of)
+            n_rooms = start.size - 1
+            M = B // n_rooms
+            k_sel = min(N, M)
+            d_order, d_start, d_room = t_(order), t_(start), t_(room_of.astype(np.int64))
+            cs, ca, ct = (lyra_amd.LyraHip(device=0, max_streams=B) for _ in range(3))
+            try:
+                cs.torch_order = ca.torch_order = False
+                out_s, len_s, _, _ = new_bufs()
+                out_a, len_a, _, _ = new_bufs()
+                out_t, len_t, x_t, mix_t = new_bufs()
+                rates16 = torch.full((B,), 16000, dtype=torch.int32, device=dev)
+                offs = torch.arange(B, dtype=torch.int32, device=dev) * 320
+                sums = torch.zeros((n_rooms, 320), dtype=torch.int32, device=dev)
+                pos_key = (32767 - torch.arange(M, dtype=torch.int64, device=dev))[None, :]
+                room_base = (torch.arange(n_rooms, dtype=torch.int64, device=dev) * M)[:, None]
+                room_sel = torch.arange(n_rooms, dtype=torch.int64, device=dev)[:, None].expand(n_rooms, k_sel).reshape(-1)
+                torch.cuda.synchronize()
+
+                def tick_s(t):
+                    cs.speakers_tick_dev(d_ids, d_pk[t % ring], d_nb[t], d_order, d_start, d_bits, out_s[t & 1], len_s[t & 1], N,
+                                         None, d_dtx)
+
+                def tick_a(t):
+                    ca.bridge_tick_dev(d_ids, d_pk[t % ring], d_nb[t], d_order, d_start, d_bits, out_a[t & 1], len_a[t & 1],
+                                       None, d_dtx)
+
+                def tick_t(t):
+                    k = t & 1
+                    ct.decode_lossy_mixed_dev(d_ids, d_pk[t % ring], d_nb[t], 16000, x_t[k])
+                    x = x_t[k].to(torch.int32)
+                    x64 = x.to(torch.int64)
+                    levels = (x64 * x64).sum(dim=1)
+                    keys = (levels.view(n_rooms, M) << 15) | pos_key            # unique per room: louder first, then earlier
+                    vals, idx = torch.topk(keys, k_sel, dim=1)
+                    valid = ((vals >> 15) > 0).reshape(-1)                      # a zero-level row is no candidate
+                    rows = (idx + room_base).reshape(-1)
+                    sums.zero_()
+                    sums.index_add_(0, room_sel, x[rows] * valid[:, None].to(torch.int32))
+                    is_spk = torch.zeros(B, dtype=torch.int32, device=dev)
+                    is_spk[rows] = valid.to(torch.int32)
+                    mix_t[k].copy_((sums[d_room] - x * is_spk[:, None]).clamp_(-32768, 32767))
+                    ct.encode_streams_dev(d_ids, mix_t[k], rates16, d_bits, out_t[k], len_t[k], d_dtx, offs, 320 * B)
+
+                verified = 0
+                for t in range(min(a.verify, a.hops)):
+                    tick_s(t)
+                    tick_t(t)
+                    cs.synchronize()
+                    ct.synchronize()
+                    torch.cuda.synchronize()
+                    ls, lt = len_s[t & 1].cpu().numpy(), len_t[t & 1].cpu().numpy()
+                    ps, pt = out_s[t & 1].cpu().numpy(), out_t[t & 1].cpu().numpy()
+                    if not (np.array_equal(ls, lt) and all(np.array_equal(ps[b, :ls[b]], pt[b, :ls[b]]) for b in range(B))):
+                        raise SystemExit(f"{name}: speakers_tick_dev and python_select differ at tick {t}")
+                    verified += 1
+                cs.reset()
+                ct.reset()
+                times = timed({"speakers_tick_dev": (lambda: [tick_s(t) for t in range(a.hops)], cs),
+                               "tick_dev": (lambda: [tick_a(t) for t in range(a.hops)], ca),
+                               "python_select": (lambda: [tick_t(t) for t in range(a.hops)], ct)}, a.reps)
+                line = {"bench": "bridge", "case": "speakers", "layout": name, "streams": B, "rooms": int(n_rooms),
+                        "max_speakers": N, "loss": 0.10, "hops": a.hops, "reps": a.reps, "verified_ticks": verified}
+                for k, ts in times.items():
+                    line[k] = stats(B, a.hops, ts)
+                med = lambda k: line[k]["ticks_x_streams_per_s_median"]   # noqa: E731
+                line["speakers_over_tick_dev"] = round(med("speakers_tick_dev") / med("tick_dev"), 3)
+                line["speakers_over_python_select"] = round(med("speakers_tick_dev") / med("python_select"), 3)
+                # the three kernels alone, as "mix_kernel_us" below
+                cs.synchronize()
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                per, n, how = [], 100, "device events around 100 calls back to back (three kernels)"
+                try:
+                    st = torch.cuda.ExternalStream(cs.stream_handle(), device=dev)
+                except Exception:
+                    st, how = None, "host clock around 100 calls back to back and a synchronise (three kernels + launches)"
+                for rep in range(a.reps + 1):
+                    t0 = time.perf_counter()
+                    if st is not None:
+                        e0.record(st)
+                    for _ in range(n):
+                        cs.speakers_mix_dev(x_t[0], d_order, d_start, mix_t[1], N)
+                    if st is not None:
+                        e1.record(st)
+                    cs.synchronize()
+                    if rep:
+                        per.append((e0.elapsed_time(e1) * 1000.0 if st is not None else (time.perf_counter() - t0) * 1e6) / n)
+                per.sort()
+                line["select_kernels_us"] = {"median": round(per[len(per) // 2], 2), "min": round(per[0], 2),
+                                             "max": round(per[-1], 2), "what": how}
+                # what DTX did not send: one further pass per mix, the empty outgoing packets counted tick by tick
+                share = {}
+                for form, ctx, tick, lens in (("speakers_tick_dev", cs, tick_s, len_s), ("tick_dev", ca, tick_a, len_a)):
+                    ctx.reset()
+                    empty = np.zeros(B, np.int64)
+                    for t in range(a.hops):
+                        tick(t)
+                        ctx.synchronize()
+                        empty += lens[t & 1].cpu().numpy() == 0
+                    share[form] = {"all_streams": round(float(empty.sum()) / (B * a.hops), 4),
+                                   "dtx_streams": round(float(empty[dtx != 0].sum()) / (int((dtx != 0).sum()) * a.hops), 4)}
+                line["empty_share"] = share
+                line["errors"] = {"bridge": int(cs.bridge_errors()), "lossy": int(cs.decode_lossy_errors()),
+                                  "mixed": int(cs.encode_mixed_errors())}
+                print(json.dumps(line), flush=True)
+                lines.append(line)
+            finally:
+                cs.close()
+                ca.close()
+                ct.close()
+        append(lines)
+        return
 
     # ---- (a) against (b), per layout ---------------------------------------------------------------------------------------
     for name, room_of in layouts.items():
@@ -252,10 +385,7 @@ def main():
         lines.append(line)
     finally:
         cd.close()
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "a") as f:
-        for line in lines:
-            f.write(json.dumps(line) + "\n")
+    append(lines)
 
 
 if __name__ == "__main__":
