@@ -429,12 +429,53 @@ def _load_speakers(L, path):
     return L
 
 
+class SharedTick(C.Structure):
+    """lyra_hip_shared_tick (include/lyra_hip_shared_bridge.h)"""
+    _fields_ = [("d_stream_ids", C.c_void_p), ("B", C.c_int), ("d_packets", C.c_void_p), ("d_packet_bytes", C.c_void_p),
+                ("d_order", C.c_void_p), ("d_room_start", C.c_void_p), ("n_rooms", C.c_int), ("n_members", C.c_int),
+                ("d_muted", C.c_void_p), ("flags", C.c_uint), ("d_out_packets", C.c_void_p), ("d_out_packet_bytes", C.c_void_p),
+                ("d_pcm16", C.c_void_p), ("d_is_noise", C.c_void_p), ("d_is_comfort_noise", C.c_void_p),
+                ("max_speakers", C.c_int), ("d_levels", C.c_void_p), ("d_is_speaker", C.c_void_p),
+                ("d_room_keys", C.c_void_p), ("d_slots", C.c_void_p), ("n_table_rooms", C.c_int),
+                ("d_enc_stream_ids", C.c_void_p), ("d_enc_num_bits", C.c_void_p), ("d_enc_dtx", C.c_void_p),
+                ("d_enc_mix", C.c_void_p), ("d_enc_packets", C.c_void_p), ("d_enc_packet_bytes", C.c_void_p),
+                ("d_slot_of", C.c_void_p)]
+
+
+SHARED_SLOTS = 8                  # LYRA_HIP_SHARED_SLOTS
+
+
+def _signatures_shared():
+    """The same for include/lyra_hip_shared_bridge.h (tests/test_shared_bridge_cpu.py holds each entry to its prototype)."""
+    vp, ci, cu = C.c_void_p, C.c_int, C.c_uint
+    table = {
+        "shared_mix_dev": [vp, vp, vp, ci, vp, vp, ci, ci, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp],
+        "shared_tick_dev": [vp, vp],
+        "shared_begin": [vp, vp, ci, vp, vp, vp, vp, cu, ci, vp, ci, vp, vp, vp], "shared_end": [vp] * 8,
+        "shared_reset_rooms": [vp, vp, ci],
+    }
+    return {"lyra_hip_" + name: (ci, args) for name, args in table.items()}
+
+
+_SIGNATURES_SHARED = _signatures_shared()
+
+
+def _load_shared(L, path):
+    """_SIGNATURES_SHARED applied to a loaded library; one that lacks a function of it is refused."""
+    for name, (restype, argtypes) in _SIGNATURES_SHARED.items():
+        fn = getattr(L, name, None)
+        if fn is None:
+            raise LyraHipError(f"{path} does not export {name}")
+        fn.restype, fn.argtypes = restype, argtypes
+    return L
+
+
 def _load(path=None):
     """The C-ABI library (default: library_path()); a second path loads a build variant beside it (lyra_amd/variants/).
     A library that lacks a function of _SIGNATURES, _SIGNATURES_SPANS_MIXED, _SIGNATURES_SPANS_RATES, _SIGNATURES_SPANS_PACKED,
     _SIGNATURES_ENCODE_STREAMS, _SIGNATURES_DECODE_STREAMS, _SIGNATURES_DECODE_SAMPLES_ANY or
     _SIGNATURES_DECODE_SAMPLES_STREAMS is refused, and so is one that lacks a function of _SIGNATURES_BRIDGE (_load_bridge) or _SIGNATURES_SPEAKERS
-    (_load_speakers)."""
+    (_load_speakers) or _SIGNATURES_SHARED (_load_shared)."""
     path = os.path.abspath(path or library_path())
     if path in _libs:
         return _libs[path]
@@ -462,7 +503,7 @@ def _load(path=None):
         if fn is None:
             raise LyraHipError(f"{path} does not export {name}")
         fn.restype, fn.argtypes = restype, argtypes
-    _libs[path] = _load_speakers(_load_bridge(L, path), path)
+    _libs[path] = _load_shared(_load_speakers(_load_bridge(L, path), path), path)
     return L
 
 
@@ -519,6 +560,7 @@ class LyraHip:
         self._pending_sample_stream_decodes = []   # the same for decode_samples_streams_begin
         self._pending_bridge_ticks = []     # B of the ticks begun by bridge_begin, oldest first
         self._pending_speakers_ticks = []   # ... and by speakers_begin (the library holds both kinds in one queue of two)
+        self._pending_shared_ticks = []     # ... and by shared_begin (the same queue)
 
     def _create(self, h, mode, model_dir, device, max_streams, weights_image):
         if weights_image is not None:   # bytes of a lyra_v1.lyrapack (lyra_hip_create_from_image)
@@ -1183,6 +1225,111 @@ class LyraHip:
         self._pending_speakers_ticks.pop(0)   # (otherwise the library gives the slot back whatever the wait returns)
         self._chk(rc)
         return out, lens, noise, cn, levels, spk
+
+    # -- the bridge with shared encoders (include/lyra_hip_shared_bridge.h) ------------------------------
+    def shared_mix_dev(self, d_pcm16, d_ids, d_order, d_room_start, d_slots, d_enc_mix, max_speakers, d_room_keys=None,
+                       d_muted=None, d_is_comfort_noise=None, d_levels=None, d_is_speaker=None, d_slot_of=None):
+        """Levels, selection, slot update and the encoder mixes alone (lyra_hip_shared_mix_dev): d_pcm16 int16 [B][320], d_ids
+        int32 [B] the participants' stream ids, the index of bridge_mix_dev, d_slots int32 [n_table_rooms][SHARED_SLOTS] (in and
+        out; -1: a free slot), d_room_keys int32 [n_rooms] or None (room r uses table row r), d_enc_mix int16
+        [n_rooms * (1 + max_speakers)][320]; d_levels int64 [B], d_is_speaker and d_slot_of int32 [B]: optional outputs.
+        Completes on the encode-side stream."""
+        B = d_pcm16.shape[0]
+        n_members, n_rooms = d_order.shape[0], d_room_start.shape[0] - 1
+        E = n_rooms * (1 + int(max_speakers))
+        n_table = d_slots.shape[0]
+        self._dev_call(self.L.lyra_hip_shared_mix_dev, self._p_pcm(d_pcm16, B), self._p_ids(d_ids, B), B,
+                       self._dev_ptr(d_order, "int32", (n_members,), "order") if n_members else None,
+                       self._dev_ptr(d_room_start, "int32", (n_rooms + 1,), "room_start"), n_rooms, n_members,
+                       self._opt_dev_ptr(d_muted, "int32", (B,), "muted"),
+                       self._opt_dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise"), int(max_speakers),
+                       self._opt_dev_ptr(d_room_keys, "int32", (n_rooms,), "room keys"),
+                       self._dev_ptr(d_slots, "int32", (n_table, SHARED_SLOTS), "slot table"), n_table,
+                       self._dev_ptr(d_enc_mix, "int16", (E, HOP), "encoder mixes"),
+                       self._opt_dev_ptr(d_levels, "int64", (B,), "levels"),
+                       self._opt_dev_ptr(d_is_speaker, "int32", (B,), "is_speaker"),
+                       self._opt_dev_ptr(d_slot_of, "int32", (B,), "slot_of"))
+
+    def shared_tick_dev(self, d_ids, d_packets, d_packet_bytes, d_order, d_room_start, d_out_packets, d_out_packet_bytes,
+                        max_speakers, d_slots, d_enc_ids, d_enc_num_bits, d_room_keys=None, d_enc_dtx=None, d_muted=None,
+                        flags=0, d_pcm16=None, d_is_noise=None, d_is_comfort_noise=None, d_levels=None, d_is_speaker=None,
+                        d_enc_mix=None, d_enc_packets=None, d_enc_packet_bytes=None, d_slot_of=None):
+        """One tick of the bridge with shared encoders (lyra_hip_shared_tick_dev): the decode leg and the selection of
+        speakers_tick_dev, then ONE encode_streams_dev call on E = n_rooms * (1 + max_speakers) encoder rows (d_enc_ids,
+        d_enc_num_bits, d_enc_dtx int32 [E]: bitrate and DTX belong to a room and a slot, not to a listener) and the fan-out of
+        the E packets into d_out_packets uint8 [B][23] / d_out_packet_bytes int32 [B].  d_slots / d_room_keys as in
+        shared_mix_dev.  Optional outputs: d_pcm16, d_is_noise, d_is_comfort_noise, d_levels, d_is_speaker, d_slot_of [B];
+        d_enc_mix int16 [E][320], d_enc_packets uint8 [E][23], d_enc_packet_bytes int32 [E]."""
+        B = d_packets.shape[0]
+        n_members, n_rooms = d_order.shape[0], d_room_start.shape[0] - 1
+        E = n_rooms * (1 + int(max_speakers))
+        n_table = d_slots.shape[0]
+        t = SharedTick(self._p_ids(d_ids, B), B, self._p_packets(d_packets, B, MAX_PACKET_BYTES),
+                       self._p_packet_bytes(d_packet_bytes, B),
+                       self._dev_ptr(d_order, "int32", (n_members,), "order") if n_members else None,
+                       self._dev_ptr(d_room_start, "int32", (n_rooms + 1,), "room_start"), n_rooms, n_members,
+                       self._opt_dev_ptr(d_muted, "int32", (B,), "muted"), int(flags),
+                       self._p_packets(d_out_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_out_packet_bytes, B),
+                       self._opt_dev_ptr(d_pcm16, "int16", (B, HOP), "16 kHz pcm"),
+                       *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B), int(max_speakers),
+                       self._opt_dev_ptr(d_levels, "int64", (B,), "levels"),
+                       self._opt_dev_ptr(d_is_speaker, "int32", (B,), "is_speaker"),
+                       self._opt_dev_ptr(d_room_keys, "int32", (n_rooms,), "room keys"),
+                       self._dev_ptr(d_slots, "int32", (n_table, SHARED_SLOTS), "slot table"), n_table,
+                       self._dev_ptr(d_enc_ids, "int32", (E,), "encoder stream ids") if E else None,
+                       self._dev_ptr(d_enc_num_bits, "int32", (E,), "encoder num_bits") if E else None,
+                       self._opt_dev_ptr(d_enc_dtx, "int32", (E,), "encoder dtx flags"),
+                       self._opt_dev_ptr(d_enc_mix, "int16", (E, HOP), "encoder mixes"),
+                       self._opt_dev_ptr(d_enc_packets, "uint8", (E, MAX_PACKET_BYTES), "encoder packets"),
+                       self._opt_dev_ptr(d_enc_packet_bytes, "int32", (E,), "encoder packet sizes"),
+                       self._opt_dev_ptr(d_slot_of, "int32", (B,), "slot_of"))
+        self._dev_call(self.L.lyra_hip_shared_tick_dev, C.addressof(t))
+
+    def shared_begin(self, packets, packet_bytes, rooms, max_speakers, room_labels, enc_ids, enc_bits, enc_dtx=None,
+                     muted=None, flags=0, stream_ids=None):
+        """Pipelined tick of the bridge with shared encoders from host arrays (lyra_hip_shared_begin): packets, packet_bytes,
+        rooms, muted as bridge_begin; room_labels int32 [n_rooms], strictly ascending and exactly the labels >= 0 present in
+        rooms; enc_ids / enc_bits / enc_dtx int32 [n_rooms][1 + max_speakers]: the encoder stream, bit count and DTX switch of
+        every room's common row and slots.  The slot table is the context's, one row per label.  Up to two ticks in flight,
+        bridge_begin's and speakers_begin's included."""
+        packets = _np(packets, np.uint8, (-1, MAX_PACKET_BYTES))
+        B = packets.shape[0]
+        sizes, labels = (_np(a, np.int32, (B,)) for a in (packet_bytes, rooms))
+        keys = _np(room_labels, np.int32, (-1,))
+        eids, ebits = (_np(a, np.int32, (-1,)) for a in (enc_ids, enc_bits))
+        m = None if muted is None else _np(np.asarray(muted) != 0, np.int32, (B,))
+        d = None if enc_dtx is None else _np(np.asarray(enc_dtx) != 0, np.int32, (-1,))
+        if 1 <= int(max_speakers) <= SPEAKERS_MAX:    # (anything else the library refuses before it reads an array)
+            E = keys.size * (1 + int(max_speakers))
+            if eids.size != E or ebits.size != E or (d is not None and d.size != E):
+                raise LyraHipError(f"shared_begin: enc_ids, enc_bits and enc_dtx take {keys.size} x (1 + {int(max_speakers)}) entries")
+        ids = self._ids(stream_ids, B)
+        self._chk(self.L.lyra_hip_shared_begin(self.h, ids.ctypes.data, B, packets.ctypes.data, sizes.ctypes.data,
+                                               labels.ctypes.data, None if m is None else m.ctypes.data, int(flags),
+                                               int(max_speakers), keys.ctypes.data, keys.size, eids.ctypes.data,
+                                               ebits.ctypes.data, None if d is None else d.ctypes.data))
+        self._pending_shared_ticks.append(B)
+
+    def shared_end(self):
+        """-> (out_packets uint8 [B][23], out_packet_bytes, is_noise, is_comfort_noise int32 [B], levels int64 [B], is_speaker,
+        slot_of int32 [B]) of the OLDEST tick in flight, which must be one begun by shared_begin."""
+        if not self._pending_shared_ticks:
+            self._chk(self.L.lyra_hip_shared_end(self.h, None, None, None, None, None, None, None))
+        B = self._pending_shared_ticks[0]
+        out = np.empty((B, MAX_PACKET_BYTES), np.uint8)
+        lens, noise, cn, spk, slot = (np.empty(B, np.int32) for _ in range(5))
+        levels = np.empty(B, np.int64)
+        rc = self.L.lyra_hip_shared_end(self.h, out.ctypes.data, lens.ctypes.data, noise.ctypes.data, cn.ctypes.data,
+                                        levels.ctypes.data, spk.ctypes.data, slot.ctypes.data)
+        self._chk_other_kind(rc)            # (refused: the oldest tick is of another kind; nothing was consumed)
+        self._pending_shared_ticks.pop(0)   # (otherwise the library gives the slot back whatever the wait returns)
+        self._chk(rc)
+        return out, lens, noise, cn, levels, spk, slot
+
+    def shared_reset_rooms(self, room_labels):
+        """Drain the context and free the slot-table rows of these room labels (lyra_hip_shared_reset_rooms)."""
+        keys = _np(room_labels, np.int32, (-1,))
+        self._chk(self.L.lyra_hip_shared_reset_rooms(self.h, keys.ctypes.data, keys.size))
 
     def rates_errors(self, clear=False):
         """Sample rates seen by encode_rates_dev / decode_lossy_rates_dev / run_steps with d_rates that are no codec rate

@@ -172,6 +172,15 @@ struct lyra_hip_ctx {
   int64_t* d_spk_levels[2] = {};     // [spk_cap] the levels of a call that was given no array
   int32_t* d_spk_flags[2] = {};      // [spk_cap] ... and its speaker flags
   int spk_cap = 0;
+  // shared encoders (shared_bridge_api.inc): scratch by lossy-call parity, rows = max(B, E) of the largest tick so far
+  int32_t* d_shr_slot_row[2] = {};   // [shr_cap][8] the speaker row of every slot of every room (-1: free)
+  int32_t* d_shr_row_room[2] = {};   // [shr_cap] the room of every participant row (-1: none)
+  int32_t* d_shr_slot_of[2] = {};    // [shr_cap] slot_of of a tick that was given no array
+  int16_t* d_shr_mix[2] = {};        // [shr_cap][320] ... its encoder mixes
+  uint8_t* d_shr_pk[2] = {};         // [shr_cap][23] ... its encoder packets
+  int32_t* d_shr_len[2] = {};        // [shr_cap] ... and their sizes
+  int shr_cap = 0;
+  int32_t* d_shr_table = nullptr;    // [max_streams][8] the slot table of lyra_hip_shared_begin: one row per room label
   // lyra_hip_export_streams / lyra_hip_import_streams (stream_state_api.inc)
   unsigned* d_import_err = nullptr;  // blob rows lyra_hip_import_streams_dev refused
   uint8_t* d_blobs = nullptr;        // staging of the host forms, blob_cap rows
@@ -263,6 +272,7 @@ void es_free(lyra_hip_ctx* c);
 void dstr_free(lyra_hip_ctx* c);
 void brg_free(lyra_hip_ctx* c);
 void spk_free(lyra_hip_ctx* c);
+void shr_free(lyra_hip_ctx* c);
 void blob_free(lyra_hip_ctx* c);
 void spans_free(lyra_hip_ctx* c);
 // One owner per device buffer.  Buffers that are sized by one count (the frames of a call, the streams of the context) are
@@ -1131,6 +1141,7 @@ void lyra_hip_destroy(lyra_hip_ctx* c) {
   dstr_free(c);
   brg_free(c);
   spk_free(c);
+  shr_free(c);
   spans_free(c);
   if (c->h_zc) (void)hipHostFree(c->h_zc);
   c->h_zc = nullptr;
@@ -2118,6 +2129,7 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
 #include "decode_samples_streams_api.inc"
 #include "bridge_api.inc"
 #include "speakers_api.inc"
+#include "shared_bridge_api.inc"
 #include "stream_state_api.inc"
 #include "spans_api.inc"
 #include "spans_lossy_api.inc"

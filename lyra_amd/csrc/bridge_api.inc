@@ -21,7 +21,8 @@ struct BrgSlot {
   uint8_t* d_out = nullptr;
   hipEvent_t ev_done = nullptr;
   int B = 0;
-  int max_speakers = 0;        // 0: a full-mix tick (lyra_hip_bridge_begin); else a tick of lyra_hip_speakers_begin
+  int max_speakers = 0;        // 0: a full-mix tick (lyra_hip_bridge_begin); else a tick of lyra_hip_speakers_begin ...
+  bool shared = false;         // ... or, with this set, of lyra_hip_shared_begin (shared_bridge_api.inc)
 };
 struct BrgHost { BrgSlot slot[2]; };
 
@@ -38,6 +39,27 @@ int spk_ensure(lyra_hip_ctx* c, int B);
 int spk_mix_launch(lyra_hip_ctx* c, const int16_t* d_pcm16, int B, const int32_t* d_order, const int32_t* d_room_start,
                    int n_rooms, int n_members, const int32_t* d_muted, const int32_t* d_is_cn, int max_speakers, int16_t* d_mix,
                    int64_t* d_levels, int32_t* d_is_speaker, int set);
+// shared_bridge_api.inc: what a shared-encoder tick has in place of the per-listener bit counts, DTX flags and mix; its
+// scratch; its mix on se[0] (levels, selection, slot update, the E encoder mixes); and its staging, which is the largest:
+// going up [ids | packet_bytes | order | muted | room_start | room_keys | enc_ids | enc_bits | enc_dtx], coming down
+// [out_packet_bytes | is_noise | is_comfort_noise | is_speaker] int32, levels int64, slot_of int32, out packets
+struct ShrTick {
+  const int32_t* d_room_keys;
+  int32_t* d_slots;
+  int n_table_rooms;
+  const int32_t *d_enc_stream_ids, *d_enc_num_bits, *d_enc_dtx;
+  int16_t* d_enc_mix;
+  uint8_t* d_enc_packets;
+  int32_t *d_enc_packet_bytes, *d_slot_of;
+};
+constexpr size_t kShrInArrays = 9, kShrOutWords = 7;
+size_t shr_in_bytes(size_t n) { return (kShrInArrays * n + 1) * 4 + n * LYRA_HIP_MAX_PACKET_BYTES; }
+size_t shr_out_bytes(size_t n) { return kShrOutWords * n * 4 + n * LYRA_HIP_MAX_PACKET_BYTES; }
+int shr_ensure(lyra_hip_ctx* c, int rows);
+int shr_mix_launch(lyra_hip_ctx* c, const int16_t* d_pcm16, const int32_t* d_stream_ids, int B, const int32_t* d_order,
+                   const int32_t* d_room_start, int n_rooms, int n_members, const int32_t* d_muted, const int32_t* d_is_cn,
+                   int max_speakers, const ShrTick& sh, int16_t* d_enc_mix, int64_t* d_levels, int32_t* d_is_speaker,
+                   int32_t* d_slot_of, int set);
 
 void brg_free(lyra_hip_ctx* c) {
   dfree(c->d_brg_mix[0], c->d_brg_mix[1], c->d_brg_flags[0], c->d_brg_flags[1], c->d_brg_const, c->d_bridge_err);
@@ -58,10 +80,10 @@ void brg_free(lyra_hip_ctx* c) {
 
 int brg_slot_ensure(lyra_hip_ctx* c, BrgSlot* S) {
   const size_t n = (size_t)c->max_streams;
-  if (!S->h_in) HIPCHK(c, hipHostMalloc((void**)&S->h_in, brg_in_bytes(n), hipHostMallocDefault));
-  if (!S->h_out) HIPCHK(c, hipHostMalloc((void**)&S->h_out, spk_out_bytes(n), hipHostMallocDefault));
-  if (!S->d_in) HIPCHK(c, dalloc(&S->d_in, brg_in_bytes(n)));
-  if (!S->d_out) HIPCHK(c, dalloc(&S->d_out, spk_out_bytes(n)));
+  if (!S->h_in) HIPCHK(c, hipHostMalloc((void**)&S->h_in, shr_in_bytes(n), hipHostMallocDefault));
+  if (!S->h_out) HIPCHK(c, hipHostMalloc((void**)&S->h_out, shr_out_bytes(n), hipHostMallocDefault));
+  if (!S->d_in) HIPCHK(c, dalloc(&S->d_in, shr_in_bytes(n)));
+  if (!S->d_out) HIPCHK(c, dalloc(&S->d_out, shr_out_bytes(n)));
   if (!S->ev_done) HIPCHK(c, hipEventCreateWithFlags(&S->ev_done, hipEventDisableTiming));
   return 0;
 }
@@ -108,6 +130,9 @@ int brg_ensure(lyra_hip_ctx* c, int B) {
 
 bool brg_misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
+int shr_encode_fanout(lyra_hip_ctx* c, const lyra_hip_bridge_tick* T, int max_speakers, int E, const ShrTick& sh,
+                      const int16_t* enc_mix, const int32_t* slot_of, int set);
+
 int brg_check_index(lyra_hip_ctx* c, const char* what, int B, const int32_t* d_order, const int32_t* d_room_start, int n_rooms,
                     int n_members) {
   if (n_rooms < 0 || n_rooms > B || n_members < 0 || n_members > B)
@@ -137,31 +162,46 @@ bool brg_other_in_flight(lyra_hip_ctx* c) {
          c->dss_begun != c->dss_ended || c->twin_out_n != 0;
 }
 
-// One tick, for both kinds of mix.  max_speakers 0: the full mix of lyra_hip_bridge_tick_dev; 1 .. 8: the selection mix of
-// lyra_hip_speakers_tick_dev (speakers_api.inc) with its two further outputs.  `what` names the call in messages.
+// One tick, for every kind of mix.  max_speakers 0: the full mix of lyra_hip_bridge_tick_dev; 1 .. 8: the selection mix of
+// lyra_hip_speakers_tick_dev (speakers_api.inc) with its two further outputs; with `sh`, the shared-encoder tick of
+// lyra_hip_shared_tick_dev (shared_bridge_api.inc): the selection, then E = n_rooms * (1 + max_speakers) encoder rows in place of
+// B and the fan-out behind the quantizer (T->d_num_bits, d_dtx and d_mix are not read).  `what` names the call in messages.
 int brg_tick_impl(lyra_hip_ctx* c, const char* what, const lyra_hip_bridge_tick* T, int max_speakers, int64_t* d_levels,
-                  int32_t* d_is_speaker) {
+                  int32_t* d_is_speaker, const ShrTick* sh = nullptr) {
   const int B = T->B;
   int rc = check_batch(c, B);
   if (rc) return rc;
-  if (!T->d_stream_ids || !T->d_packets || !T->d_packet_bytes || !T->d_num_bits || !T->d_out_packets || !T->d_out_packet_bytes)
+  if (!T->d_stream_ids || !T->d_packets || !T->d_packet_bytes || (!sh && !T->d_num_bits) || !T->d_out_packets ||
+      !T->d_out_packet_bytes)
     return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
   if ((rc = brg_check_index(c, what, B, T->d_order, T->d_room_start, T->n_rooms, T->n_members))) return rc;
+  const int E = sh ? T->n_rooms * (1 + max_speakers) : 0;   // (n_rooms <= B: at most 9 * max_streams)
+  if (sh) {
+    if (!sh->d_slots || (E > 0 && (!sh->d_enc_stream_ids || !sh->d_enc_num_bits)))
+      return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
+    if (sh->n_table_rooms < 1) return fail(c, LYRA_HIP_EINVAL, "%s: n_table_rooms %d", what, sh->n_table_rooms);
+    if (E > c->max_streams)
+      return fail(c, LYRA_HIP_EINVAL, "%s: %d rooms x (1 + %d) encoder rows exceed max_streams (%d): use the loudest-N tick", what,
+                  T->n_rooms, max_speakers, c->max_streams);
+    if (brg_misaligned(sh->d_enc_mix) || (sh->d_enc_mix && T->d_pcm16 == sh->d_enc_mix))
+      return fail(c, LYRA_HIP_EINVAL, "%s: d_pcm16 and d_enc_mix must be 16-byte aligned and distinct", what);
+  }
   if (T->flags & ~LYRA_HIP_BRIDGE_SKIP_COMFORT_NOISE) return fail(c, LYRA_HIP_EINVAL, "%s: unknown flags 0x%x", what, T->flags);
   if (brg_misaligned(T->d_pcm16) || brg_misaligned(T->d_mix) || (T->d_mix && T->d_pcm16 == T->d_mix))
     return fail(c, LYRA_HIP_EINVAL, "%s: d_pcm16 and d_mix must be 16-byte aligned and distinct", what);
   DEVSCOPE(c);
   // everything the tick allocates or builds on first use, BEFORE anything is enqueued
-  if ((rc = ensure_scratch(c, B))) return rc;
+  if ((rc = ensure_scratch(c, std::max(B, E)))) return rc;   // (E: the encode leg of a shared-encoder tick, else 0)
   if ((rc = rates_ensure(c))) return rc;
   if ((rc = lossy_ensure(c, B))) return rc;
   if (!T->d_pcm16 && (rc = dstr16_ensure(c, B))) return rc;
   if ((rc = brg_ensure(c, B))) return rc;
   if (max_speakers && (rc = spk_ensure(c, B))) return rc;
+  if (sh && (rc = shr_ensure(c, std::max(B, E)))) return rc;
   const int set = (int)(c->n_lossy_calls & 1);
   const bool skip_cn = (T->flags & LYRA_HIP_BRIDGE_SKIP_COMFORT_NOISE) != 0;
   int16_t* pcm16 = T->d_pcm16 ? T->d_pcm16 : c->d_dstr16[set];
-  int16_t* mix = T->d_mix ? T->d_mix : c->d_brg_mix[set];
+  int16_t* mix = sh ? (sh->d_enc_mix ? sh->d_enc_mix : c->d_shr_mix[set]) : T->d_mix ? T->d_mix : c->d_brg_mix[set];
   int32_t* is_cn = T->d_is_comfort_noise ? T->d_is_comfort_noise : skip_cn ? c->d_brg_flags[set] : nullptr;
   // ---- decode leg: lyra_hip_decode_lossy_mixed_dev at 16 kHz, with the event behind its mix ----
   c->lossy_mix_hook = c->ev_brg_mix;
@@ -172,13 +212,17 @@ int brg_tick_impl(lyra_hip_ctx* c, const char* what, const lyra_hip_bridge_tick*
   // ---- the edge and the mix: se[0] behind this tick's hop and flags ----
   if ((rc = enc_cross_begin(c, 0, 1))) return rc;
   HIPCHK(c, hipStreamWaitEvent(c->se[0], c->ev_brg_mix, 0));
-  rc = max_speakers ? spk_mix_launch(c, pcm16, B, T->d_order, T->d_room_start, T->n_rooms, T->n_members, T->d_muted,
+  int32_t* slot_of = sh ? (sh->d_slot_of ? sh->d_slot_of : c->d_shr_slot_of[set]) : nullptr;
+  rc = sh ? shr_mix_launch(c, pcm16, T->d_stream_ids, B, T->d_order, T->d_room_start, T->n_rooms, T->n_members, T->d_muted,
+                           skip_cn ? is_cn : nullptr, max_speakers, *sh, mix, d_levels, d_is_speaker, slot_of, set)
+       : max_speakers ? spk_mix_launch(c, pcm16, B, T->d_order, T->d_room_start, T->n_rooms, T->n_members, T->d_muted,
                                      skip_cn ? is_cn : nullptr, max_speakers, mix, d_levels, d_is_speaker, set)
                     : brg_mix_launch(c, pcm16, B, T->d_order, T->d_room_start, T->n_rooms, T->n_members, T->d_muted,
                                      skip_cn ? is_cn : nullptr, mix);
   if (rc) return rc;
   // ---- encode leg ----
   const int32_t* rates16 = c->d_brg_const;
+  if (sh) return shr_encode_fanout(c, T, max_speakers, E, *sh, mix, slot_of, set);
   return lyra_hip_encode_streams_dev(c, T->d_stream_ids, B, mix, 320L * B, rates16 + c->max_streams, rates16, T->d_num_bits,
                                      T->d_dtx, T->d_out_packets, T->d_out_packet_bytes);
 }
@@ -267,6 +311,7 @@ int brg_begin_impl(lyra_hip_ctx* c, const char* what, const int32_t* ids, int B,
   HIPCHK(c, hipEventRecord(S.ev_done, c->sq[0]));
   S.B = B;
   S.max_speakers = max_speakers;
+  S.shared = false;
   c->brg_begun++;
   return 0;
 }
@@ -314,7 +359,8 @@ int lyra_hip_bridge_end(lyra_hip_ctx* c, uint8_t* out_packets, int32_t* out_pack
   if (!c) return LYRA_HIP_EINVAL;
   if (!c->brg_host || c->brg_ended == c->brg_begun) return fail(c, LYRA_HIP_EINVAL, "bridge_end: no tick in flight");
   BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->brg_ended & 1];
-  if (S.max_speakers) return fail(c, LYRA_HIP_EINVAL, "bridge_end: the oldest tick was begun by lyra_hip_speakers_begin");
+  if (S.max_speakers)
+    return fail(c, LYRA_HIP_EINVAL, "bridge_end: the oldest tick was begun by lyra_hip_%s_begin", S.shared ? "shared" : "speakers");
   if (!out_packets || !out_packet_bytes) return fail(c, LYRA_HIP_EINVAL, "bridge_end: null pointer");
   DEVSCOPE(c);
   c->brg_ended++;                  // whatever happens below, the slot is given back

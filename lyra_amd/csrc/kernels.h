@@ -245,9 +245,10 @@ __global__ void lossy_mix_kernel(const int32_t* ids, int B, const int32_t* info,
 __global__ void bridge_mix_kernel(const int16_t* pcm, int B, const int32_t* order, const int32_t* room_start, int n_rooms,
                                   int n_members, const int32_t* muted, const int32_t* is_cn, int16_t* mix, unsigned* err);
 // ---- loudest-N speaker selection (speakers_kernels.hip; include/lyra_hip_speakers.h) --------------------------------------
-// level[b] = sum of squares of row b (int64), for every row; zeroes row b of mix, is_speaker[b], and pos_room[b] to -1
+// level[b] = sum of squares of row b (int64), for every row; zeroes row b of mix (where given), is_speaker[b], and pos_room[b]
+// to -1; slot_of / row_room (shared encoders only, else nullptr): [b] to -1
 __global__ void speakers_level_kernel(const int16_t* pcm, int B, long long* levels, int16_t* mix, int32_t* is_speaker,
-                                      int32_t* pos_room, int n_members);
+                                      int32_t* pos_room, int n_members, int32_t* slot_of, int32_t* row_room);
 // one wavefront per room over levels and the index only: the room's max_speakers loudest candidates into spk[room][8] (-1
 // padded) and is_speaker, the room number of every position into pos_room; bad index entries counted in *err (here only)
 __global__ void speakers_select_kernel(const long long* levels, int B, const int32_t* order, const int32_t* room_start,
@@ -257,6 +258,20 @@ __global__ void speakers_select_kernel(const long long* levels, int B, const int
 // one wavefront per 8 consecutive positions of the index: the sum of the room's speaker rows minus the listener's own
 __global__ void speakers_mix_kernel(const int16_t* pcm, int B, const int32_t* order, int n_members, const int32_t* pos_room,
                                     int n_rooms, const int32_t* spk, int16_t* mix);
+// ---- shared encoders (shared_bridge_kernels.hip; include/lyra_hip_shared_bridge.h) ----------------------------------------
+// one wavefront per room behind speakers_select_kernel: the room's row of the slot table updated, the speaker row of every
+// slot into slot_row[room][8], slot_of of the speakers, the room of every member row into row_room; a bad key counted in *err
+__global__ void shared_slots_kernel(const int32_t* spk, const int32_t* stream_ids, int B, const int32_t* order,
+                                    const int32_t* room_start, int n_rooms, int n_members, int max_speakers,
+                                    const int32_t* room_keys, int n_table_rooms, int32_t* slots, int32_t* slot_row,
+                                    int32_t* slot_of, int32_t* row_room, unsigned* err);
+// one wavefront per encoder row e = room * (1 + N) + c: the sum of the room's speaker rows, minus the row in slot c - 1
+__global__ void shared_mix_kernel(const int16_t* pcm, int B, int n_rooms, int max_speakers, const int32_t* spk,
+                                  const int32_t* slot_row, const int32_t* room_keys, int n_table_rooms, int16_t* enc_mix);
+// one thread per byte of the outgoing packets: row b receives the packet and size of its room's encoder row
+__global__ void shared_fanout_kernel(int B, int n_rooms, int max_speakers, const int32_t* row_room, const int32_t* slot_of,
+                                     const uint8_t* enc_packets, const int32_t* enc_packet_bytes, uint8_t* out_packets,
+                                     int32_t* out_packet_bytes);
 // ---- any request size up to one hop (decode_samples_kernels.hip, decode_samples_plan.h; lyra_hip_decode_samples_dev) ------
 // plan: transition, id lists (-1: the row skips the leg), info [B][4], feature ring push / pop, features of starting hops
 __global__ void ds_plan_kernel(const int32_t* ids, int B, const int32_t* pkt_bytes, int n_internal, uint8_t* cng_state,

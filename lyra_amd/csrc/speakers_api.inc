@@ -43,7 +43,7 @@ int spk_mix_launch(lyra_hip_ctx* c, const int16_t* d_pcm16, int B, const int32_t
   int32_t* flags = d_is_speaker ? d_is_speaker : c->d_spk_flags[set];
   int32_t* pos_room = c->d_spk_pos_room[set];
   hipLaunchKernelGGL(speakers_level_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->se[0], d_pcm16, B, levels, d_mix, flags, pos_room,
-                     n_members);
+                     n_members, (int32_t*)nullptr, (int32_t*)nullptr);
   HIPCHK(c, hipGetLastError());
   if (n_rooms > 0 && n_members > 0) {
     hipLaunchKernelGGL(speakers_select_kernel, dim3(cdiv(n_rooms, 4)), dim3(256), 0, c->se[0], levels, B, d_order, d_room_start,
@@ -132,6 +132,7 @@ int lyra_hip_speakers_end(lyra_hip_ctx* c, uint8_t* out_packets, int32_t* out_pa
   if (!c->brg_host || c->brg_ended == c->brg_begun) return fail(c, LYRA_HIP_EINVAL, "speakers_end: no tick in flight");
   BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->brg_ended & 1];
   if (!S.max_speakers) return fail(c, LYRA_HIP_EINVAL, "speakers_end: the oldest tick was begun by the full-mix begin()");
+  if (S.shared) return fail(c, LYRA_HIP_EINVAL, "speakers_end: the oldest tick was begun by lyra_hip_shared_begin");
   if (!out_packets || !out_packet_bytes) return fail(c, LYRA_HIP_EINVAL, "speakers_end: null pointer");
   DEVSCOPE(c);
   c->brg_ended++;                  // whatever happens below, the slot is given back

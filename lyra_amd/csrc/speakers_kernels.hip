@@ -16,37 +16,12 @@ namespace lyra {
 
 namespace {
 
-constexpr int SPK_MAX = 8;      // LYRA_HIP_SPEAKERS_MAX: speakers per room, and the width of a speaker list
+#include "speakers_rows.inc"   // SPK_MAX, SPK_LANES, SpkAcc, spk_add, spk_clamp, spk_minus: shared with shared_bridge_kernels.hip
+
 constexpr int SPK_CHUNK = 8;    // positions per wavefront of the mix
-constexpr int SPK_LANES = 40;   // 40 lanes x 16 bytes = one 640-byte row
 constexpr int SPK_POS = 32767;  // LYRA_HIP_BRIDGE_MAX_ROOM: positions inside a room take 15 bits of a key
 
 typedef unsigned long long u64;
-
-struct SpkAcc { int v[8]; };
-
-__device__ __forceinline__ void spk_add(SpkAcc& s, const uint4& x) {
-  const unsigned w[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    s.v[2 * i] += (int)(short)(w[i] & 0xffffu);
-    s.v[2 * i + 1] += (int)w[i] >> 16;
-  }
-}
-
-__device__ __forceinline__ int spk_clamp(int v) { return v < -32768 ? -32768 : v > 32767 ? 32767 : v; }
-
-// clamp(S - (own ? x : 0)), eight samples
-__device__ __forceinline__ uint4 spk_minus(const SpkAcc& s, const uint4& x, bool own) {
-  const unsigned w[4] = {x.x, x.y, x.z, x.w};
-  unsigned o[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int lo = own ? (int)(short)(w[i] & 0xffffu) : 0, hi = own ? (int)w[i] >> 16 : 0;
-    o[i] = ((unsigned)spk_clamp(s.v[2 * i] - lo) & 0xffffu) | ((unsigned)spk_clamp(s.v[2 * i + 1] - hi) << 16);
-  }
-  return make_uint4(o[0], o[1], o[2], o[3]);
-}
 
 __device__ __forceinline__ u64 wave_max(u64 v) {
 #pragma unroll
@@ -62,10 +37,13 @@ __device__ __forceinline__ u64 wave_max(u64 v) {
 // One wavefront per row, four rows per workgroup; lanes 0..39 own 16 bytes (8 samples) of the row.  A square is at most 2^30
 // and a row's sum at most 320 * 2^30 < 2^39: 64-bit accumulation, a shuffle reduction, one 8-byte store.  The row's mix is
 // zeroed (rows that no room names hear zeros; the mix kernel overwrites the others), is_speaker[row] too, and pos_room[row]
-// is set to "no room" for row < n_members (n_members <= B, checked on the host), in place of three memsets.
+// is set to "no room" for row < n_members (n_members <= B, checked on the host), in place of three memsets.  The shared-encoder
+// tick (shared_bridge_kernels.hip) has no per-listener mix: it passes mix = nullptr, which skips those stores, and two further
+// words per row to set to -1, slot_of[row] and row_room[row]; the loudest-N calls pass nullptr for both.
 __global__ __launch_bounds__(256) void speakers_level_kernel(const int16_t* __restrict__ pcm, int B, long long* __restrict__ levels,
                                                               int16_t* __restrict__ mix, int32_t* __restrict__ is_speaker,
-                                                              int32_t* __restrict__ pos_room, int n_members) {
+                                                              int32_t* __restrict__ pos_room, int n_members,
+                                                              int32_t* __restrict__ slot_of, int32_t* __restrict__ row_room) {
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= B) return;
   u64 acc = 0;
@@ -77,7 +55,7 @@ __global__ __launch_bounds__(256) void speakers_level_kernel(const int16_t* __re
       const int a = (int)(short)(w[i] & 0xffffu), b = (int)w[i] >> 16;
       acc += (u64)(unsigned)(a * a) + (u64)(unsigned)(b * b);   // (32768^2 = 2^30 fits an int)
     }
-    reinterpret_cast<uint4*>(mix + (size_t)row * 320)[lane] = make_uint4(0u, 0u, 0u, 0u);
+    if (mix) reinterpret_cast<uint4*>(mix + (size_t)row * 320)[lane] = make_uint4(0u, 0u, 0u, 0u);
   }
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
@@ -85,6 +63,8 @@ __global__ __launch_bounds__(256) void speakers_level_kernel(const int16_t* __re
     levels[row] = (long long)acc;
     is_speaker[row] = 0;
     if (row < n_members) pos_room[row] = -1;
+    if (slot_of) slot_of[row] = -1;
+    if (row_room) row_room[row] = -1;
   }
 }
 

@@ -1,6 +1,7 @@
 // bridge_demo.cc -- drives LyraConferenceBridge (lyra_conference_bridge.h) through a scripted call:
 //   bridge_demo <model_dir> <streams.txt> <script.i32> <packets_in.bin> <lengths_in.i32> <packets_out.bin> <lengths_out.i32>
-//               <mode> <skip_comfort_noise> [--max-speakers=N --speakers-out=<speakers_out.i32>]
+//               <mode> <skip_comfort_noise> [--max-speakers=N --speakers-out=<speakers_out.i32>
+//               [--shared-encoders [--slots-out=<slots_out.i32>]]]
 // streams.txt: one line "bitrate enable_dtx" per stream.  script: [ticks][num_streams][3] int32 -- room (< 0: none), muted,
 // bitrate of every stream as of that tick, applied before the tick is begun.  packets_in: [ticks][num_streams][23] bytes;
 // lengths_in: [ticks][num_streams] int32, 0 = no packet from that stream on that tick.  Writes every tick's outgoing packets
@@ -9,6 +10,11 @@
 // t is waited for); it must write the same two files.
 // --max-speakers=N: the same call through LyraSpeakerBridge (lyra_speaker_bridge.h), every room mixed from its N loudest
 // sources; every delivered tick's speaker flags [num_streams] int32 go to the file of --speakers-out.
+// --shared-encoders (with --max-speakers): the same call through LyraSharedBridge (lyra_shared_bridge.h), 1 + N encoders per
+// room.  Bitrate and DTX belong to a room there: before every tick each room takes the script's bitrate, and the streams.txt
+// DTX switch, of its FIRST member (the lowest stream number); the other members' entries are not used.  The bridge gets as many
+// rooms as the script's largest label + 1.  --slots-out: every delivered tick's speaker slots [num_streams] int32 (-1: none).
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,6 +25,7 @@
 #include <vector>
 
 #include "lyra_conference_bridge.h"
+#include "lyra_shared_bridge.h"
 #include "lyra_speaker_bridge.h"
 
 using namespace chromemedia::codec;
@@ -49,19 +56,24 @@ int main(int argc_all, char** argv_all) {
   // options first: what is left is the nine positional arguments
   int max_speakers = 0;
   const char* speakers_path = nullptr;
+  const char* slots_path = nullptr;
+  bool shared_encoders = false;
   std::vector<char*> positional;
   for (int i = 0; i < argc_all; ++i) {
     if (std::strncmp(argv_all[i], "--max-speakers=", 15) == 0) max_speakers = std::atoi(argv_all[i] + 15);
     else if (std::strncmp(argv_all[i], "--speakers-out=", 15) == 0) speakers_path = argv_all[i] + 15;
+    else if (std::strncmp(argv_all[i], "--slots-out=", 12) == 0) slots_path = argv_all[i] + 12;
+    else if (std::strcmp(argv_all[i], "--shared-encoders") == 0) shared_encoders = true;
     else positional.push_back(argv_all[i]);
   }
   const int argc = static_cast<int>(positional.size());
   char** argv = positional.data();
   const bool select = max_speakers != 0 || speakers_path != nullptr;
-  if (argc != 10 || (select && (max_speakers == 0 || speakers_path == nullptr))) {
+  if (argc != 10 || (select && (max_speakers == 0 || speakers_path == nullptr)) || (shared_encoders && !select) ||
+      (slots_path && !shared_encoders)) {
     std::fprintf(stderr, "usage: bridge_demo <model_dir> <streams.txt> <script.i32> <packets_in.bin> <lengths_in.i32> "
                          "<packets_out.bin> <lengths_out.i32> <mode 0|1> <skip_comfort_noise 0|1> "
-                         "[--max-speakers=N --speakers-out=<speakers_out.i32>]\n");
+                         "[--max-speakers=N --speakers-out=<speakers_out.i32> [--shared-encoders [--slots-out=<slots_out.i32>]]]\n");
     return 2;
   }
   std::vector<BridgeStream> streams;
@@ -81,7 +93,14 @@ int main(int argc_all, char** argv_all) {
   const bool pipelined = std::atoi(argv[8]) != 0;
   std::unique_ptr<LyraConferenceBridge> bridge;
   LyraSpeakerBridge* speakers = nullptr;
-  if (select) {
+  LyraSharedBridge* shared = nullptr;
+  if (shared_encoders) {
+    int max_rooms = 1;
+    for (size_t i = 0; i < ticks * n; ++i) max_rooms = std::max(max_rooms, script[i * 3] + 1);
+    auto b = LyraSharedBridge::Create(absl::MakeConstSpan(streams), argv[1], 0, std::atoi(argv[9]) != 0, max_speakers, max_rooms);
+    shared = b.get();
+    bridge = std::move(b);
+  } else if (select) {
     auto b = LyraSpeakerBridge::Create(absl::MakeConstSpan(streams), argv[1], 0, std::atoi(argv[9]) != 0, max_speakers);
     speakers = b.get();
     bridge = std::move(b);
@@ -90,12 +109,18 @@ int main(int argc_all, char** argv_all) {
   }
   if (!bridge) return Fail("Create failed");
   std::ofstream out_pk(argv[6], std::ios::binary), out_len(argv[7], std::ios::binary), out_spk;
-  if (speakers) out_spk.open(speakers_path, std::ios::binary);
+  std::ofstream out_slots;
+  if (speakers || shared) out_spk.open(speakers_path, std::ios::binary);
+  if (slots_path) out_slots.open(slots_path, std::ios::binary);
   auto write_speakers = [&]() {   // as of the tick just delivered
-    if (!speakers) return;
-    std::vector<int32_t> flags(n);
-    for (size_t s = 0; s < n; ++s) flags[s] = speakers->is_speaker(static_cast<int>(s)) ? 1 : 0;
+    if (!speakers && !shared) return;
+    std::vector<int32_t> flags(n), slots(n, -1);
+    for (size_t s = 0; s < n; ++s) {
+      flags[s] = (speakers ? speakers->is_speaker(static_cast<int>(s)) : shared->is_speaker(static_cast<int>(s))) ? 1 : 0;
+      if (shared) slots[s] = shared->slot(static_cast<int>(s));
+    }
     out_spk.write(reinterpret_cast<const char*>(flags.data()), static_cast<std::streamsize>(flags.size() * sizeof(int32_t)));
+    if (slots_path) out_slots.write(reinterpret_cast<const char*>(slots.data()), static_cast<std::streamsize>(slots.size() * sizeof(int32_t)));
   };
   std::vector<uint8_t> rows(n * kRow);
   std::vector<int32_t> lens(n);
@@ -107,6 +132,11 @@ int main(int argc_all, char** argv_all) {
     return true;
   };
   for (size_t t = 0; t < ticks; ++t) {
+    for (size_t s = n; shared && s-- > 0;) {   // descending: the room's FIRST member is the last to set it
+      const int32_t* row = &script[(t * n + s) * 3];
+      if (row[0] >= 0 && (!shared->SetRoomBitrate(row[0], row[2]) || !shared->SetRoomDtx(row[0], streams[s].enable_dtx)))
+        return Fail("the script names a room setting the bridge refuses");
+    }
     for (size_t s = 0; s < n; ++s) {
       const int32_t* row = &script[(t * n + s) * 3];
       if (!bridge->SetRoom(static_cast<int>(s), row[0]) || !bridge->SetMuted(static_cast<int>(s), row[1] != 0) ||

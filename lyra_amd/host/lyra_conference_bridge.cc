@@ -38,7 +38,8 @@ LyraConferenceBridge::LyraConferenceBridge(lyra_hip_ctx* ctx, absl::Span<const B
 }
 
 lyra_hip_ctx* LyraConferenceBridge::NewBridgeContext(absl::Span<const BridgeStream> streams,
-                                                     const ghc::filesystem::path& model_path, int device) {
+                                                     const ghc::filesystem::path& model_path, int device,
+                                                     int extra_streams) {
   const int n = static_cast<int>(streams.size());
   if (n == 0) {
     LOG(ERROR) << "num_streams must be positive.";
@@ -49,7 +50,7 @@ lyra_hip_ctx* LyraConferenceBridge::NewBridgeContext(absl::Span<const BridgeStre
       LOG(ERROR) << "Bitrate " << s.bitrate << " bps is not supported by codec.";
       return nullptr;
     }
-  lyra_hip_ctx* ctx = NewContext(model_path, device, n);
+  lyra_hip_ctx* ctx = NewContext(model_path, device, n + extra_streams);
   if (ctx == nullptr) LOG(ERROR) << "Could not create the bridge's context.";
   return ctx;
 }

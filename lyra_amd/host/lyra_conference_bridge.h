@@ -73,10 +73,11 @@ class LyraConferenceBridge {
  protected:
   // For a bridge with another mix (lyra_speaker_bridge.h): the host logic above is this class's, and the device calls of a
   // tick go through the three hooks below.  NewBridgeContext is what Create checks and creates: nullptr + LOG(ERROR) if
-  // `streams` is empty or a bitrate is unsupported.
+  // `streams` is empty or a bitrate is unsupported.  extra_streams: stream slots behind the participants', for a subclass that
+  // runs encoders of its own (lyra_shared_bridge.h).
   LyraConferenceBridge(lyra_hip_ctx* ctx, absl::Span<const BridgeStream> streams, bool skip_comfort_noise);
   static lyra_hip_ctx* NewBridgeContext(absl::Span<const BridgeStream> streams, const ghc::filesystem::path& model_path,
-                                        int device);
+                                        int device, int extra_streams = 0);
   // begin() and end() of the C ABI's two-deep host form: 0 on success; the arrays hold num_streams entries.
   virtual int BeginTick(lyra_hip_ctx* ctx, const int32_t* ids, int n, const uint8_t* packets, const int32_t* packet_bytes,
                         const int32_t* rooms, const int32_t* muted, unsigned flags, const int32_t* bits, const int32_t* dtx);

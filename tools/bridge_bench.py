@@ -22,7 +22,18 @@ back-to-back lyra_hip_bridge_mix_dev calls (memset + kernel), per layout.
 speakers_tick_dev is verified against python_select on the prefix, packets and sizes bit for bit.  "select_kernels_us": the
 three kernels alone around back-to-back lyra_hip_speakers_mix_dev calls; "empty_share": the share of empty outgoing packets
 (what DTX did not have to send) over one further pass of --hops ticks, of all streams and of the streams with DTX on.
-    python tools/bridge_bench.py [--streams 4096] [--hops 200] [--reps 5] [--max-speakers N] [--out profiles/bridge.jsonl]"""
+--max-speakers N --shared runs the shared-encoder leg INSTEAD (include/lyra_hip_shared_bridge.h), per layout, two forms
+alternating in one run on the same packets:
+  "shared_tick_dev":   one lyra_hip_shared_tick_dev per tick: E = rooms x (1 + N) encoder rows (120 bits, DTX on every other
+                       row, encoder ids 0 .. E - 1), the slot table on the device, the fan-out;
+  "speakers_tick_dev": the loudest-N tick, one encoder chain per participant.
+On the prefix shared_tick_dev is held to the loudest-N tick's levels and speaker flags (the same selection), to "a speaker
+holds one slot, nobody else does", and to a numpy fan-out of its own encoder packets, bit for bit.  "shared_kernels_us": levels,
+selection, slot update and the E mixes around back-to-back lyra_hip_shared_mix_dev calls; "distinct_packets_per_tick": how many
+different non-empty packets a tick sends, against the streams it sends them to.  --layout L runs one layout only: give this
+leg a process per layout -- with all three in one process the later layouts measured about 40 % slower in both forms (DESIGN.md
+4.4, "Shared encoders"; cause not found).
+    python tools/bridge_bench.py [--streams 4096] [--hops 200] [--reps 5] [--max-speakers N [--shared] [--layout L]] [--out profiles/bridge.jsonl]"""
 import argparse
 import json
 import os
@@ -76,6 +87,9 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--verify", type=int, default=12, help="ticks of the prefix on which the forms are compared")
     ap.add_argument("--max-speakers", type=int, default=0, help="run the loudest-N leg with this N instead of the legs above")
+    ap.add_argument("--shared", action="store_true", help="with --max-speakers: the shared-encoder tick against the loudest-N tick")
+    ap.add_argument("--layout", default=None, choices=["rooms_of_4", "rooms_of_16", "one_room"],
+                    help="with --max-speakers: this layout only (a process of its own per layout)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bridge.jsonl"))
     a = ap.parse_args()
     B, dev, ring = a.streams, torch.device("cuda", 0), 50
@@ -99,6 +113,8 @@ def main():
     dtx = (np.arange(B) % 2).astype(np.int32)
     d_pk, d_nb, d_bits, d_dtx = t_(pk), t_(nb), t_(bits), t_(dtx)
     layouts = {"rooms_of_4": ids // 4, "rooms_of_16": ids // 16, "one_room": np.zeros(B, np.int32)}
+    if a.layout and a.max_speakers:
+        layouts = {a.layout: layouts[a.layout]}
     lines, ref_b = [], []   # ref_b: form (b)'s packets and sizes on the prefix, rooms of 4
 
     def new_bufs():
@@ -112,6 +128,114 @@ def main():
         with open(a.out, "a") as f:
             for line in lines:
                 f.write(json.dumps(line) + "\n")
+
+    # ---- the shared-encoder leg, per layout: E encoder rows against B -------------------------------------------------------
+    if a.shared:
+        if not a.max_speakers:
+            raise SystemExit("--shared needs --max-speakers N")
+        N = a.max_speakers
+        for name, room_of in layouts.items():
+            order, start = codec.bridge_plan(room_of)
+            n_rooms = start.size - 1
+            E = n_rooms * (1 + N)
+            d_order, d_start = t_(order), t_(start)
+            csh, cs = (lyra_amd.LyraHip(device=0, max_streams=max(B, E)) for _ in range(2))
+            try:
+                csh.torch_order = cs.torch_order = False
+                out_h, len_h, x_h, _ = new_bufs()
+                out_s, len_s, _, _ = new_bufs()
+                table = torch.full((n_rooms, codec.SHARED_SLOTS), -1, dtype=torch.int32, device=dev)
+                e_ids = torch.arange(E, dtype=torch.int32, device=dev)
+                e_bits = torch.full((E,), 120, dtype=torch.int32, device=dev)
+                e_dtx = (torch.arange(E, dtype=torch.int32, device=dev) % 2).contiguous()
+                e_mix = torch.zeros((E, 320), dtype=torch.int16, device=dev)
+                e_pk = torch.zeros((E, 23), dtype=torch.uint8, device=dev)
+                e_len = torch.zeros(E, dtype=torch.int32, device=dev)
+                lv_h, lv_s = (torch.zeros(B, dtype=torch.int64, device=dev) for _ in range(2))
+                sp_h, sp_s, slot_h = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(3))
+                torch.cuda.synchronize()
+
+                def tick_h(t, check=False):
+                    extra = (lv_h, sp_h, None, e_pk, e_len, slot_h) if check else (None,) * 6
+                    csh.shared_tick_dev(d_ids, d_pk[t % ring], d_nb[t], d_order, d_start, out_h[t & 1], len_h[t & 1], N, table,
+                                        e_ids, e_bits, None, e_dtx, None, 0, x_h[0] if check else None, None, None, *extra)
+
+                def tick_s(t, check=False):
+                    cs.speakers_tick_dev(d_ids, d_pk[t % ring], d_nb[t], d_order, d_start, d_bits, out_s[t & 1], len_s[t & 1], N,
+                                         None, d_dtx, 0, None, None, None, None, *((lv_s, sp_s) if check else (None, None)))
+
+                verified = 0
+                for t in range(min(a.verify, a.hops)):
+                    tick_h(t, True)
+                    tick_s(t, True)
+                    csh.synchronize()
+                    cs.synchronize()
+                    torch.cuda.synchronize()
+                    slot, spk = slot_h.cpu().numpy(), sp_h.cpu().numpy()
+                    if not (torch.equal(lv_h, lv_s) and torch.equal(sp_h, sp_s) and np.array_equal(slot >= 0, spk == 1)):
+                        raise SystemExit(f"{name}: shared_tick_dev and speakers_tick_dev select differently at tick {t}")
+                    rows = room_of * (1 + N) + np.where(slot >= 0, 1 + slot, 0)
+                    if not (np.array_equal(out_h[t & 1].cpu().numpy(), e_pk.cpu().numpy()[rows]) and
+                            np.array_equal(len_h[t & 1].cpu().numpy(), e_len.cpu().numpy()[rows])):
+                        raise SystemExit(f"{name}: the fan-out of shared_tick_dev differs from its encoder packets at tick {t}")
+                    verified += 1
+                csh.reset()
+                cs.reset()
+                table.fill_(-1)
+                times = timed({"shared_tick_dev": (lambda: [tick_h(t) for t in range(a.hops)], csh),
+                               "speakers_tick_dev": (lambda: [tick_s(t) for t in range(a.hops)], cs)}, a.reps)
+                line = {"bench": "bridge", "case": "shared", "layout": name, "streams": B, "rooms": int(n_rooms),
+                        "max_speakers": N, "encoder_rows": int(E), "loss": 0.10, "hops": a.hops, "reps": a.reps,
+                        "verified_ticks": verified}
+                for k, ts in times.items():
+                    line[k] = stats(B, a.hops, ts)
+                med = lambda k: line[k]["ticks_x_streams_per_s_median"]   # noqa: E731
+                line["shared_over_speakers"] = round(med("shared_tick_dev") / med("speakers_tick_dev"), 3)
+                sh, sp = line["shared_tick_dev"], line["speakers_tick_dev"]
+                line["verdict"] = ("SLOWER" if sh["max"] < sp["min"] else "faster" if sh["min"] > sp["max"] else "inside the spreads")
+                # levels, selection, slot update and the E mixes alone
+                csh.synchronize()
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                per, n, how = [], 100, "device events around 100 calls back to back (four kernels)"
+                try:
+                    st = torch.cuda.ExternalStream(csh.stream_handle(), device=dev)
+                except Exception:
+                    st, how = None, "host clock around 100 calls back to back and a synchronise (four kernels + launches)"
+                for r in range(a.reps + 1):
+                    t0 = time.perf_counter()
+                    if st is not None:
+                        e0.record(st)
+                    for _ in range(n):
+                        csh.shared_mix_dev(x_h[0], d_ids, d_order, d_start, table, e_mix, N)
+                    if st is not None:
+                        e1.record(st)
+                    csh.synchronize()
+                    if r:
+                        per.append((e0.elapsed_time(e1) * 1000.0 if st is not None else (time.perf_counter() - t0) * 1e6) / n)
+                per.sort()
+                line["shared_kernels_us"] = {"median": round(per[len(per) // 2], 2), "min": round(per[0], 2),
+                                             "max": round(per[-1], 2), "what": how}
+                # how many different packets a tick sends: one further pass of a few ticks
+                csh.reset()
+                table.fill_(-1)
+                distinct, sent = [], []
+                for t in range(min(20, a.hops)):
+                    tick_h(t)
+                    csh.synchronize()
+                    p, ln = out_h[t & 1].cpu().numpy(), len_h[t & 1].cpu().numpy()
+                    distinct.append(int(np.unique(p[ln > 0], axis=0).shape[0]))
+                    sent.append(int((ln > 0).sum()))
+                line["distinct_packets_per_tick"] = {"median": int(np.median(distinct)), "sent_to_streams_median": int(np.median(sent))}
+                line["errors"] = {"bridge": int(csh.bridge_errors()), "lossy": int(csh.decode_lossy_errors()),
+                                  "mixed": int(csh.encode_mixed_errors())}
+                print(json.dumps(line), flush=True)
+                lines.append(line)
+            finally:
+                csh.close()
+                cs.close()
+        append(lines)
+        return
 
     # ---- the loudest-N leg, per layout (rooms of one size M, a room's rows together) ----------------------------------------
     if a.max_speakers:
