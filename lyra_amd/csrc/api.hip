@@ -25,6 +25,7 @@
 #include "../../include/lyra_hip.h"
 #include "model.h"
 #include "tflite_pack.h"
+#include "pipelines.h"
 
 using namespace lyra;
 
@@ -143,18 +144,16 @@ struct lyra_hip_ctx {
   float* d_ds_feat = nullptr;        // [ds_cap][64] features of the rows' packets / of the hops that start (decode stream only)
   unsigned* d_ds_err = nullptr;      // invalid packet sizes + packets that found the ring full
   long n_ds_calls = 0;
-  void* ds_host = nullptr;           // DsHost: the two requests in flight of lyra_hip_decode_samples_begin / _end
+  void* ds_host = nullptr;           // DsHostSlot[2]: the two requests in flight of lyra_hip_decode_samples_begin / _end
   void* dsa = nullptr;               // Dsa (decode_samples_any_api.inc): call buffers and host slots of lyra_hip_decode_samples_any_*
-  long dsa_begun = 0, dsa_ended = 0; // ... and how many lyra_hip_decode_samples_any_begin requests were begun / ended
   void* dss = nullptr;               // Dss (decode_samples_streams_api.inc): call words and host slots of lyra_hip_decode_samples_streams_*
-  long dss_begun = 0, dss_ended = 0; // ... and how many lyra_hip_decode_samples_streams_begin requests were begun / ended
   void* es_host = nullptr;           // EsHost (encode_streams_api.inc): the two slots of lyra_hip_encode_streams_begin / _end
-  long es_begun = 0, es_ended = 0;   // ... and how many of its calls were begun / ended
+  // every pipelined host-buffer form (pipelines.h): requests begun / ended so far, by pipeline
+  long pl_begun[PL_COUNT] = {}, pl_ended[PL_COUNT] = {};
   // lyra_hip_decode_streams_dev / _begin / _end (decode_streams_api.inc)
   int16_t* d_dstr16[2] = {};         // [dstr16_cap][320] the 16 kHz hop of a call without d_pcm16, by lossy-call parity as d_lossy_gan
   int dstr16_cap = 0;
   void* dstr_host = nullptr;         // DstrHost: the two slots of lyra_hip_decode_streams_begin / _end
-  long dstr_begun = 0, dstr_ended = 0;   // ... and how many of its calls were begun / ended
   // the conference bridge (bridge_api.inc)
   unsigned* d_bridge_err = nullptr;  // d_order entries outside [0, B) that bridge_mix_kernel skipped
   int16_t* d_brg_mix[2] = {};        // [brg_cap][320] the mix of a tick without d_mix, by lossy-call parity as d_dstr16
@@ -164,7 +163,6 @@ struct lyra_hip_ctx {
   hipEvent_t ev_brg_mix = nullptr;   // the tick's edge: recorded on sn behind lossy_mix_kernel, waited for by se[0]
   hipEvent_t lossy_mix_hook = nullptr;   // set by the bridge around lossy_tick_launch only: recorded on sn behind lossy_mix_kernel
   void* brg_host = nullptr;          // BrgHost: the two slots of lyra_hip_bridge_begin / _end
-  long brg_begun = 0, brg_ended = 0; // ... and how many of its ticks were begun / ended
   // loudest-N selection (speakers_api.inc): the scratch of its three kernels, [2] by lossy-call parity as d_brg_mix
   int32_t* d_spk_list[2] = {};       // [spk_cap][8] the speaker rows of every room, -1 padded
   int32_t* d_spk_pos_room[2] = {};   // [spk_cap] the room of every position of the index (-1: none)
@@ -248,6 +246,27 @@ int fail(lyra_hip_ctx* c, int code, const char* fmt, ...) {
 
 template <class T>
 hipError_t dalloc(T** p, size_t n) { return hipMalloc((void**)p, n * sizeof(T)); }
+
+// Who is in flight (pipelines.h).  pl_admit is every begin()'s guard, in front of anything it enqueues: the pipeline's own
+// depth, then its row of the exclusion table.
+long pl_in_flight(const lyra_hip_ctx* c, int p) { return c->pl_begun[p] - c->pl_ended[p]; }
+int pl_blocker(const lyra_hip_ctx* c, Pipeline p) {   // a pipeline in flight that p's row excludes, or -1
+  for (int o = 0; o < PL_COUNT; ++o)
+    if (PL_EXCLUDES[p][o] && pl_in_flight(c, o)) return o;
+  return -1;
+}
+int pl_admit(lyra_hip_ctx* c, Pipeline p, const char* who) {
+  if (pl_in_flight(c, p) >= PL_DEPTH)
+    return fail(c, LYRA_HIP_EINVAL, "%s: two requests are already in flight (lyra_hip_%s_end)", who, PL_NAME[p]);
+  const int o = pl_blocker(c, p);
+  if (o >= 0) return fail(c, LYRA_HIP_EINVAL, "%s: a lyra_hip_%s_begin call is in flight (lyra_hip_%s_end)", who, PL_NAME[o], PL_NAME[o]);
+  return 0;
+}
+bool pl_any_in_flight(const lyra_hip_ctx* c) {   // ... or a decoder-twin request is being assembled
+  for (int p = 0; p < PL_COUNT; ++p)
+    if (pl_in_flight(c, p)) return true;
+  return c->twin_out_n != 0;
+}
 
 int pipe_sync(lyra_hip_ctx* c);   // the copy streams of the pipelined host-buffer calls (pipe_api.inc)
 int sync_all(lyra_hip_ctx* c) {

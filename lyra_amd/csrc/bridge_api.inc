@@ -153,13 +153,14 @@ int brg_mix_launch(lyra_hip_ctx* c, const int16_t* d_pcm16, int B, const int32_t
   return 0;
 }
 
-// a pipelined host-buffer request of any other kind is in flight (the forms share the streams' order: one kind at a time)
-bool brg_other_in_flight(lyra_hip_ctx* c) {
-  const PipeState* P = pipe_of(c);
-  const DsHost* H = static_cast<const DsHost*>(c->ds_host);
-  return (P && (P->begun != P->ended || P->d_begun != P->d_ended || P->f_begun != P->f_ended)) || (H && H->begun != H->ended) ||
-         c->es_begun != c->es_ended || c->dstr_begun != c->dstr_ended || c->dsa_begun != c->dsa_ended ||
-         c->dss_begun != c->dss_ended || c->twin_out_n != 0;
+// begin() of every kind of tick: two ticks deep, no pipelined request of any other kind in flight (the tick runs on both sides'
+// streams), no decoder-twin request being assembled.  (pl_admit with the wording the three kinds of tick have always had.)
+int brg_admit(lyra_hip_ctx* c, const char* what) {
+  if (pl_in_flight(c, PL_BRIDGE) >= PL_DEPTH)
+    return fail(c, LYRA_HIP_EINVAL, "%s: two ticks are already in flight (call _end first)", what);
+  if (pl_blocker(c, PL_BRIDGE) >= 0 || c->twin_out_n != 0)
+    return fail(c, LYRA_HIP_EINVAL, "%s: another pipelined request is in flight (call its _end first)", what);
+  return 0;
 }
 
 // One tick, for every kind of mix.  max_speakers 0: the full mix of lyra_hip_bridge_tick_dev; 1 .. 8: the selection mix of
@@ -242,13 +243,10 @@ int brg_begin_impl(lyra_hip_ctx* c, const char* what, const int32_t* ids, int B,
     if (pb != 0 && pb != 8 && pb != 15 && pb != LYRA_HIP_MAX_PACKET_BYTES)
       return fail(c, LYRA_HIP_EINVAL, "%s: packet of %d bytes at position %d (0, 8, 15 or 23)", what, pb, b);
   }
-  if (c->brg_begun - c->brg_ended >= 2)
-    return fail(c, LYRA_HIP_EINVAL, "%s: two ticks are already in flight (call _end first)", what);
-  if (brg_other_in_flight(c))
-    return fail(c, LYRA_HIP_EINVAL, "%s: another pipelined request is in flight (call its _end first)", what);
+  if ((rc = brg_admit(c, what))) return rc;
   DEVSCOPE(c);
   if (!c->brg_host) c->brg_host = new BrgHost();
-  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->brg_begun & 1];
+  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->pl_begun[PL_BRIDGE] & 1];
   if ((rc = brg_slot_ensure(c, &S))) return rc;
   // (the slot's previous user, two ticks back, has ended: its kernels on every stream have read d_in, its download has left
   // d_out and h_out)
@@ -312,7 +310,7 @@ int brg_begin_impl(lyra_hip_ctx* c, const char* what, const int32_t* ids, int B,
   S.B = B;
   S.max_speakers = max_speakers;
   S.shared = false;
-  c->brg_begun++;
+  c->pl_begun[PL_BRIDGE]++;
   return 0;
 }
 
@@ -357,13 +355,13 @@ int lyra_hip_bridge_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const uint
 int lyra_hip_bridge_end(lyra_hip_ctx* c, uint8_t* out_packets, int32_t* out_packet_bytes, int32_t* is_noise,
                         int32_t* is_comfort_noise) {
   if (!c) return LYRA_HIP_EINVAL;
-  if (!c->brg_host || c->brg_ended == c->brg_begun) return fail(c, LYRA_HIP_EINVAL, "bridge_end: no tick in flight");
-  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->brg_ended & 1];
+  if (!c->brg_host || c->pl_ended[PL_BRIDGE] == c->pl_begun[PL_BRIDGE]) return fail(c, LYRA_HIP_EINVAL, "bridge_end: no tick in flight");
+  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->pl_ended[PL_BRIDGE] & 1];
   if (S.max_speakers)
     return fail(c, LYRA_HIP_EINVAL, "bridge_end: the oldest tick was begun by lyra_hip_%s_begin", S.shared ? "shared" : "speakers");
   if (!out_packets || !out_packet_bytes) return fail(c, LYRA_HIP_EINVAL, "bridge_end: null pointer");
   DEVSCOPE(c);
-  c->brg_ended++;                  // whatever happens below, the slot is given back
+  c->pl_ended[PL_BRIDGE]++;                  // whatever happens below, the slot is given back
   HIPCHK(c, hipEventSynchronize(S.ev_done));
   const size_t n = (size_t)S.B;
   std::memcpy(out_packet_bytes, S.h_out, n * 4);

@@ -13,6 +13,9 @@
 //                  ds_slice_kernel -> the output resampler on n * 16000 / rate samples per row,
 // the noise-stream half being ONE noise call.  For n = one hop the kernels that touch a sample are the lossy call's, in
 // its order.
+// This file also holds what the three DecodeSamples calls share on the host: ds_run, the one launcher (a DsCall says in what
+// lyra_hip_decode_samples_dev, _any_dev and _streams_dev differ), and ds_host_begin / ds_host_end, the staging of the two
+// uniform host forms.  The kernels' shared bodies are in decode_samples_rows.h.
 #include "decode_samples_plan.h"
 
 static_assert(lyra::DS_FIFO_DEPTH == LYRA_HIP_DECODE_SAMPLES_FIFO, "documented depth of the feature FIFO");
@@ -32,26 +35,28 @@ void ds_free_call_buffers(lyra_hip_ctx* c) {
   c->ds_cap = 0;
 }
 
-// lyra_hip_decode_samples_begin / _end: two requests in flight, each with pinned staging for its arguments and a device
-// row buffer for its result.
+// One request in flight of the two uniform host forms, lyra_hip_decode_samples_begin / _end and lyra_hip_decode_samples_any_begin
+// / _end (two slots each): pinned staging for its arguments and a device row buffer for its result.
 struct DsHostSlot {
   uint8_t* h_in = nullptr;     // pinned: ids [max_streams] | packet bytes [max_streams] | packets [max_streams][24]
   int32_t* d_ids = nullptr; int32_t* d_nb = nullptr; uint8_t* d_pk = nullptr;
-  int16_t* d_out = nullptr;    // [max_streams][960]
+  int16_t* d_out = nullptr;    // [max_streams][row]: 960 samples, DSA_MAX_HOPS * 960 for the any-size form
   hipEvent_t ev_ready = nullptr;
   int B = 0, n = 0;
 };
-struct DsHost { DsHostSlot slot[2]; long begun = 0, ended = 0; };
+void ds_host_slots_free(DsHostSlot* slots) {
+  for (int i = 0; i < 2; ++i) {
+    DsHostSlot& S = slots[i];
+    if (S.h_in) (void)hipHostFree(S.h_in);
+    dfree(S.d_ids, S.d_nb, S.d_pk, S.d_out);
+    if (S.ev_ready) (void)hipEventDestroy(S.ev_ready);
+  }
+}
 
 void ds_free(lyra_hip_ctx* c) {
-  if (DsHost* H = static_cast<DsHost*>(c->ds_host)) {
-    for (DsHostSlot& S : H->slot) {
-      if (S.h_in) (void)hipHostFree(S.h_in);
-      void* ds[] = {S.d_ids, S.d_nb, S.d_pk, S.d_out};
-      for (void* p : ds) if (p) (void)hipFree(p);
-      if (S.ev_ready) (void)hipEventDestroy(S.ev_ready);
-    }
-    delete H;
+  if (DsHostSlot* slots = static_cast<DsHostSlot*>(c->ds_host)) {
+    ds_host_slots_free(slots);
+    delete[] slots;
     c->ds_host = nullptr;
   }
   ds_free_call_buffers(c);
@@ -88,6 +93,72 @@ int ds_ensure(lyra_hip_ctx* c, int B) {
   return 0;
 }
 
+// One DecodeSamples call, whichever of the three: everything in which lyra_hip_decode_samples_dev, _any_dev and _streams_dev
+// differ, apart from the launch of a round's plan kernel and of the kernel that ends the call (ds_run's two arguments).
+struct DsCall {
+  const int32_t* d_ids; int B; const uint8_t* d_packets; const int32_t* d_pkt_bytes;
+  int rounds;                  // plan rounds, of one hop at most each
+  bool hops;                   // false: SetEncodedPacket alone (a uniform request of 0 samples): one plan and one slice, no hop starts
+  // what a round's decode-stream half hands its noise-stream half, of this call's parity: the one-hop call's single-round
+  // buffers in the context, or Dsa's (decode_samples_any_api.inc)
+  int32_t* ids;                // [rounds][4 lists][cap]
+  int32_t* info;               // [rounds][cap][4]
+  int16_t* gan_new;            // [rounds][cap][320]
+  size_t cap;
+  int16_t* out16; int out_stride;   // ds_slice_kernel's rows: round r writes at out16 + 320 r
+  bool tail;                   // the call ends in the resampler or a splice kernel, on the noise stream
+  int32_t* d_is_noise; int32_t* d_is_cn;
+  int32_t* ids_of(int r, int list) const { return ids + ((size_t)r * 4 + list) * cap; }
+  int32_t* info_of(int r) const { return info + (size_t)r * 4 * cap; }
+  int16_t* gan_of(int r) const { return gan_new + (size_t)r * 320 * cap; }
+};
+
+// The call: one unsplit decode-side call and ONE noise call.  plan(r) launches round r's plan kernel on sd[0]; tail() launches
+// what ends the call on sn and returns a code.  The caller has allocated everything.
+template <class Plan, class Tail>
+int ds_run(lyra_hip_ctx* c, const DsCall& K, Plan plan, Tail tail) {
+  const int B = K.B;
+  // ---- decode stream: one unsplit decode-side call (on split contexts it stands for every chunk, dec_side_done) ----
+  int rc = dec_side_begin(c, 0, 1);
+  if (rc) return rc;
+  { ProfScope ps(c, K_RVQ_DEC, c->sd[0]);
+    hipLaunchKernelGGL(rvq_decode_mixed_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sd[0], c->model.cb, K.d_packets, K.d_pkt_bytes, 0,
+                       B, c->d_ds_feat); }
+  HIPCHK(c, hipGetLastError());
+  for (int r = 0; r < K.rounds; ++r) {
+    plan(r);
+    HIPCHK(c, hipGetLastError());
+    if (K.hops && (rc = launch_generate(c, 0, 0, K.ids_of(r, 0), B, c->d_ds_feat, K.gan_of(r)))) return rc;
+  }
+  if ((rc = dec_side_done(c, 0, 1))) return rc;
+  c->n_dec_calls++;
+  // ---- noise stream: per round comfort noise, estimator, comfort noise, slices; then the tail, as ONE noise call ----
+  if ((rc = noise_dev_begin(c))) return rc;
+  for (int r = 0; r < K.rounds; ++r) {
+    const int32_t* info = K.info_of(r);
+    const int16_t* gan_new = K.gan_of(r);
+    if (K.hops) {
+      if ((rc = launch_cng(c, c->sn, K.ids_of(r, 1), B, nullptr, c->d_ds_cng_new))) return rc;
+      hipLaunchKernelGGL(ds_est_gather_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sn, K.d_ids, B, info, gan_new,
+                         (const int16_t*)c->d_ds_gan, c->d_ds_est);
+      HIPCHK(c, hipGetLastError());
+      if ((rc = launch_noise_masked(c, K.ids_of(r, 3), B, c->d_ds_est, K.d_is_noise))) return rc;   // the rows whose received hop completes
+      if ((rc = launch_cng(c, c->sn, K.ids_of(r, 2), B, nullptr, c->d_ds_cng_new))) return rc;
+    }
+    hipLaunchKernelGGL(ds_slice_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sn, K.d_ids, B, info, gan_new,
+                       (const int16_t*)c->d_ds_cng_new, c->d_ds_gan, c->d_ds_cng, (const float*)c->d_fade, K.out16 + 320 * r,
+                       K.out_stride, (const uint8_t*)c->sm.base[st::R_NOISE_D], K.d_is_noise, K.d_is_cn);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (K.tail) {
+    if ((rc = tail())) return rc;
+    c->rs_sn_pending = true;
+  }
+  if ((rc = noise_dev_done(c))) return rc;
+  c->n_ds_calls++;
+  return serial_noise_half_done(c);
+}
+
 int ds_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_packets, const int32_t* d_pkt_bytes, int n_ext,
               int n_int, int ext, int16_t* d_pcm_ext, int32_t* d_is_noise, int32_t* d_is_cn) {
   DEVSCOPE(c);
@@ -95,50 +166,98 @@ int ds_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_pac
   if (rc) return rc;
   if ((rc = ds_ensure(c, B))) return rc;
   const int set = (int)(c->n_ds_calls & 1);
-  const size_t cap = (size_t)c->ds_cap;
-  int32_t* gen_ids = c->d_ds_ids[set];
-  int32_t* cng1_ids = gen_ids + cap;
-  int32_t* cng2_ids = gen_ids + 2 * cap;
-  int32_t* est_ids = gen_ids + 3 * cap;
-  int32_t* info = c->d_ds_info[set];
-  int16_t* gan_new = c->d_ds_gan_new[set];
-  // ---- decode stream: one unsplit decode-side call (on split contexts it stands for every chunk, dec_side_done) ----
-  if ((rc = dec_side_begin(c, 0, 1))) return rc;
-  { ProfScope ps(c, K_RVQ_DEC, c->sd[0]);
-    hipLaunchKernelGGL(rvq_decode_mixed_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sd[0], c->model.cb, d_packets, d_pkt_bytes, 0, B,
-                       c->d_ds_feat); }
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(ds_plan_kernel, dim3(cdiv(B, 256)), dim3(256), 0, c->sd[0], d_ids, B, d_pkt_bytes, n_int,
-                     c->sm.base[st::R_CNG], gen_ids, cng1_ids, cng2_ids, est_ids, info, c->d_ds_feat, c->d_ds_ring, c->d_ds_err);
-  HIPCHK(c, hipGetLastError());
-  // (n == 0 is SetEncodedPacket alone: no pass, so no hop starts)
-  if (n_int > 0 && (rc = launch_generate(c, 0, 0, gen_ids, B, c->d_ds_feat, gan_new))) return rc;
-  if ((rc = dec_side_done(c, 0, 1))) return rc;
-  c->n_dec_calls++;
-  // ---- noise stream: comfort noise, estimator, comfort noise, slices, resampler as ONE noise call ---------------------
-  if ((rc = noise_dev_begin(c))) return rc;
-  if (n_int > 0) {
-    if ((rc = launch_cng(c, c->sn, cng1_ids, B, nullptr, c->d_ds_cng_new))) return rc;
-    hipLaunchKernelGGL(ds_est_gather_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sn, d_ids, B, (const int32_t*)info,
-                       (const int16_t*)gan_new, (const int16_t*)c->d_ds_gan, c->d_ds_est);
-    HIPCHK(c, hipGetLastError());
-    if ((rc = launch_noise_masked(c, est_ids, B, c->d_ds_est, d_is_noise))) return rc;   // the rows whose received hop completes
-    if ((rc = launch_cng(c, c->sn, cng2_ids, B, nullptr, c->d_ds_cng_new))) return rc;
-  }
-  int16_t* out16 = ext == 16000 ? d_pcm_ext : c->d_ds_pcm16;
-  hipLaunchKernelGGL(ds_slice_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sn, d_ids, B, (const int32_t*)info,
-                     (const int16_t*)gan_new, (const int16_t*)c->d_ds_cng_new, c->d_ds_gan, c->d_ds_cng,
-                     (const float*)c->d_fade, out16, ext == 16000 ? n_ext : 320, (const uint8_t*)c->sm.base[st::R_NOISE_D],
-                     d_is_noise, d_is_cn);
-  HIPCHK(c, hipGetLastError());
-  if (ext != 16000 && n_int > 0) {
-    if ((rc = launch_resample(c, 1, d_ids, B, c->d_ds_pcm16, n_int, 16000, ext, d_pcm_ext, nullptr, 320, n_ext, c->sn))) return rc;
-    c->rs_sn_pending = true;
-  }
-  if ((rc = noise_dev_done(c))) return rc;
-  c->n_ds_calls++;
-  return serial_noise_half_done(c);
+  const bool direct = ext == 16000;   // (n == 0 is SetEncodedPacket alone: no pass, so no hop starts)
+  const DsCall K = {d_ids, B, d_packets, d_pkt_bytes, 1, n_int > 0, c->d_ds_ids[set], c->d_ds_info[set], c->d_ds_gan_new[set],
+                    (size_t)c->ds_cap, direct ? d_pcm_ext : c->d_ds_pcm16, direct ? n_ext : 320, !direct && n_int > 0, d_is_noise,
+                    d_is_cn};
+  return ds_run(
+      c, K,
+      [&](int) {
+        hipLaunchKernelGGL(ds_plan_kernel, dim3(cdiv(B, 256)), dim3(256), 0, c->sd[0], d_ids, B, d_pkt_bytes, n_int,
+                           c->sm.base[st::R_CNG], K.ids_of(0, 0), K.ids_of(0, 1), K.ids_of(0, 2), K.ids_of(0, 3), K.info,
+                           c->d_ds_feat, c->d_ds_ring, c->d_ds_err);
+      },
+      [&] { return launch_resample(c, 1, d_ids, B, c->d_ds_pcm16, n_int, 16000, ext, d_pcm_ext, nullptr, 320, n_ext, c->sn); });
 }
+
+int ds_check_size(lyra_hip_ctx* c, int num_samples, int sample_rate_hz) {
+  int rc = check_rate(c, sample_rate_hz);
+  if (rc) return rc;
+  if (ds_internal_samples(num_samples, sample_rate_hz) < 0)
+    return fail(c, LYRA_HIP_EINVAL, "decode_samples: %d samples at %d Hz: a request must be 0..%d samples and a whole number of "
+                "16 kHz samples (other sizes: BatchLyraDecoder)", num_samples, sample_rate_hz, sample_rate_hz / 50);
+  return 0;
+}
+
+// The two uniform calls with HOST buffers, in two halves (the form of lyra_hip_decode_begin / _end): begin() copies ids, sizes
+// and packets into pinned staging, uploads them on the decode-side stream and enqueues the `_dev` call into the slot's row
+// buffer; end() downloads the OLDEST begun request straight into the caller's memory -- on the (idle) quantizer stream
+// while a younger request's kernels run, on the noise stream itself when there is none -- and synchronises that stream only.
+struct DsHostForm {
+  Pipeline pl;
+  const char* who;
+  size_t row;                                          // samples per stream of a slot's row buffer
+  DsHostSlot* (*slots)(lyra_hip_ctx*);                 // the form's two slots, created on first use
+  int (*check_size)(lyra_hip_ctx*, int num_samples, int sample_rate_hz);
+  int (*dev)(lyra_hip_ctx*, const int32_t*, int, const uint8_t*, const int32_t*, int, int, int16_t*, int32_t*, int32_t*);
+};
+
+int ds_host_begin(lyra_hip_ctx* c, const DsHostForm& F, const int32_t* ids, int B, const uint8_t* packets,
+                  const int32_t* packet_bytes, int num_samples, int sample_rate_hz) {
+  int rc = check_batch(c, B);
+  if (rc) return rc;
+  if ((rc = F.check_size(c, num_samples, sample_rate_hz))) return rc;
+  if (!packets || !packet_bytes) return fail(c, LYRA_HIP_EINVAL, "%s_begin: null pointer", F.who);
+  if ((rc = check_ids_host(c, ids, B))) return rc;
+  DEVSCOPE(c);
+  if ((rc = pl_admit(c, F.pl, F.who))) return rc;
+  DsHostSlot& S = F.slots(c)[c->pl_begun[F.pl] & 1];
+  const size_t n = (size_t)c->max_streams;
+  if (!S.h_in) HIPCHK(c, hipHostMalloc((void**)&S.h_in, n * 32, hipHostMallocDefault));
+  if (!S.d_ids) HIPCHK(c, dalloc(&S.d_ids, n));
+  if (!S.d_nb) HIPCHK(c, dalloc(&S.d_nb, n));
+  if (!S.d_pk) HIPCHK(c, dalloc(&S.d_pk, n * 24));
+  if (!S.d_out) HIPCHK(c, dalloc(&S.d_out, n * F.row));
+  if (!S.ev_ready) HIPCHK(c, hipEventCreateWithFlags(&S.ev_ready, hipEventDisableTiming));
+  // (the slot's previous user, two requests back, has ended: its kernels on both streams have read these buffers)
+  std::memcpy(S.h_in, ids, (size_t)B * 4);
+  std::memcpy(S.h_in + n * 4, packet_bytes, (size_t)B * 4);
+  std::memcpy(S.h_in + n * 8, packets, (size_t)B * LYRA_HIP_MAX_PACKET_BYTES);
+  HIPCHK(c, hipMemcpyAsync(S.d_ids, S.h_in, (size_t)B * 4, hipMemcpyHostToDevice, c->sd[0]));
+  HIPCHK(c, hipMemcpyAsync(S.d_nb, S.h_in + n * 4, (size_t)B * 4, hipMemcpyHostToDevice, c->sd[0]));
+  HIPCHK(c, hipMemcpyAsync(S.d_pk, S.h_in + n * 8, (size_t)B * LYRA_HIP_MAX_PACKET_BYTES, hipMemcpyHostToDevice, c->sd[0]));
+  if ((rc = F.dev(c, S.d_ids, B, S.d_pk, S.d_nb, num_samples, sample_rate_hz, S.d_out, nullptr, nullptr))) return rc;
+  HIPCHK(c, hipEventRecord(S.ev_ready, c->sn));
+  S.B = B;
+  S.n = num_samples;
+  c->pl_begun[F.pl]++;
+  return 0;
+}
+
+int ds_host_end(lyra_hip_ctx* c, const DsHostForm& F, int16_t* pcm) {
+  if (!c) return LYRA_HIP_EINVAL;
+  if (!pl_in_flight(c, F.pl)) return fail(c, LYRA_HIP_EINVAL, "%s_end: no request in flight", F.who);
+  DsHostSlot& S = F.slots(c)[c->pl_ended[F.pl] & 1];
+  if (S.n > 0 && !pcm) return fail(c, LYRA_HIP_EINVAL, "%s_end: null pointer", F.who);
+  DEVSCOPE(c);
+  c->pl_ended[F.pl]++;             // whatever happens below, the slot is given back
+  if (S.n == 0) {
+    HIPCHK(c, hipEventSynchronize(S.ev_ready));
+    return 0;
+  }
+  const bool overlap = pl_in_flight(c, F.pl) != 0;
+  hipStream_t down = overlap ? c->sq[0] : c->sn;
+  if (overlap) HIPCHK(c, hipStreamWaitEvent(down, S.ev_ready, 0));
+  HIPCHK(c, hipMemcpyAsync(pcm, S.d_out, (size_t)S.B * (size_t)S.n * 2, hipMemcpyDeviceToHost, down));
+  HIPCHK(c, hipStreamSynchronize(down));
+  return 0;
+}
+
+DsHostSlot* ds_host_slots(lyra_hip_ctx* c) {
+  if (!c->ds_host) c->ds_host = new DsHostSlot[2]();
+  return static_cast<DsHostSlot*>(c->ds_host);
+}
+const DsHostForm kDsHostForm = {PL_DECODE_SAMPLES, "decode_samples", 960, ds_host_slots, ds_check_size, lyra_hip_decode_samples_dev};
 
 }  // namespace
 
@@ -149,93 +268,22 @@ int lyra_hip_decode_samples_dev(lyra_hip_ctx* c, const int32_t* d_ids, int B, co
                                 int32_t* d_is_noise, int32_t* d_is_comfort_noise) {
   int rc = check_batch(c, B);
   if (rc) return rc;
-  if ((rc = check_rate(c, sample_rate_hz))) return rc;
-  const int n_int = ds_internal_samples(num_samples, sample_rate_hz);
-  if (n_int < 0)
-    return fail(c, LYRA_HIP_EINVAL, "decode_samples: %d samples at %d Hz: a request must be 0..%d samples and a whole number of "
-                "16 kHz samples (other sizes: BatchLyraDecoder)", num_samples, sample_rate_hz, sample_rate_hz / 50);
+  if ((rc = ds_check_size(c, num_samples, sample_rate_hz))) return rc;
   if (!d_ids || !d_packets || !d_packet_bytes || (num_samples > 0 && !d_pcm_ext))
     return fail(c, LYRA_HIP_EINVAL, "decode_samples: null pointer");
-  return ds_launch(c, d_ids, B, d_packets, d_packet_bytes, num_samples, n_int, sample_rate_hz, d_pcm_ext, d_is_noise,
-                   d_is_comfort_noise);
+  return ds_launch(c, d_ids, B, d_packets, d_packet_bytes, num_samples, ds_internal_samples(num_samples, sample_rate_hz),
+                   sample_rate_hz, d_pcm_ext, d_is_noise, d_is_comfort_noise);
 }
 
 long lyra_hip_decode_samples_errors(lyra_hip_ctx* c, int clear) {
   return read_error_counter(c, &lyra_hip_ctx::d_ds_err, clear);
 }
 
-// The same with HOST buffers, in two halves (the form of lyra_hip_decode_begin / _end): begin() copies ids, sizes and packets
-// into pinned staging, uploads them on the decode-side stream and enqueues lyra_hip_decode_samples_dev into the slot's row
-// buffer; end() downloads the OLDEST begun request straight into the caller's memory -- on the (idle) quantizer stream
-// while a younger request's kernels run, on the noise stream itself when there is none -- and synchronises that stream only.
 int lyra_hip_decode_samples_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const uint8_t* packets,
                                   const int32_t* packet_bytes, int num_samples, int sample_rate_hz) {
-  int rc = check_batch(c, B);
-  if (rc) return rc;
-  if ((rc = check_rate(c, sample_rate_hz))) return rc;
-  if (ds_internal_samples(num_samples, sample_rate_hz) < 0)
-    return fail(c, LYRA_HIP_EINVAL, "decode_samples: %d samples at %d Hz: a request must be 0..%d samples and a whole number of "
-                "16 kHz samples (other sizes: BatchLyraDecoder)", num_samples, sample_rate_hz, sample_rate_hz / 50);
-  if (!packets || !packet_bytes) return fail(c, LYRA_HIP_EINVAL, "decode_samples_begin: null pointer");
-  if ((rc = check_ids_host(c, ids, B))) return rc;
-  DEVSCOPE(c);
-  if (!c->ds_host) c->ds_host = new DsHost();
-  DsHost* H = static_cast<DsHost*>(c->ds_host);
-  if (H->begun - H->ended >= 2)
-    return fail(c, LYRA_HIP_EINVAL, "decode_samples_begin: two requests are already in flight (lyra_hip_decode_samples_end)");
-  if (c->brg_begun != c->brg_ended)   // (the bridge runs on both sides' streams)
-    return fail(c, LYRA_HIP_EINVAL, "decode_samples_begin: a lyra_hip_bridge_begin tick is in flight (lyra_hip_bridge_end)");
-  if (c->dstr_begun != c->dstr_ended)   // (as lyra_hip_decode_begin: one decode pipeline at a time)
-    return fail(c, LYRA_HIP_EINVAL, "decode_samples_begin: a lyra_hip_decode_streams_begin call is in flight "
-                "(lyra_hip_decode_streams_end)");
-  if (c->dsa_begun != c->dsa_ended)
-    return fail(c, LYRA_HIP_EINVAL, "decode_samples_begin: a lyra_hip_decode_samples_any_begin request is in flight "
-                "(lyra_hip_decode_samples_any_end)");
-  if (c->dss_begun != c->dss_ended)
-    return fail(c, LYRA_HIP_EINVAL, "decode_samples_begin: a lyra_hip_decode_samples_streams_begin request is in flight "
-                "(lyra_hip_decode_samples_streams_end)");
-  DsHostSlot& S = H->slot[H->begun & 1];
-  const size_t n = (size_t)c->max_streams;
-  if (!S.h_in) HIPCHK(c, hipHostMalloc((void**)&S.h_in, n * 32, hipHostMallocDefault));
-  if (!S.d_ids) HIPCHK(c, dalloc(&S.d_ids, n));
-  if (!S.d_nb) HIPCHK(c, dalloc(&S.d_nb, n));
-  if (!S.d_pk) HIPCHK(c, dalloc(&S.d_pk, n * 24));
-  if (!S.d_out) HIPCHK(c, dalloc(&S.d_out, n * 960));
-  if (!S.ev_ready) HIPCHK(c, hipEventCreateWithFlags(&S.ev_ready, hipEventDisableTiming));
-  // (the slot's previous user, two requests back, has ended: its kernels on both streams have read these buffers)
-  std::memcpy(S.h_in, ids, (size_t)B * 4);
-  std::memcpy(S.h_in + n * 4, packet_bytes, (size_t)B * 4);
-  std::memcpy(S.h_in + n * 8, packets, (size_t)B * LYRA_HIP_MAX_PACKET_BYTES);
-  HIPCHK(c, hipMemcpyAsync(S.d_ids, S.h_in, (size_t)B * 4, hipMemcpyHostToDevice, c->sd[0]));
-  HIPCHK(c, hipMemcpyAsync(S.d_nb, S.h_in + n * 4, (size_t)B * 4, hipMemcpyHostToDevice, c->sd[0]));
-  HIPCHK(c, hipMemcpyAsync(S.d_pk, S.h_in + n * 8, (size_t)B * LYRA_HIP_MAX_PACKET_BYTES, hipMemcpyHostToDevice, c->sd[0]));
-  if ((rc = lyra_hip_decode_samples_dev(c, S.d_ids, B, S.d_pk, S.d_nb, num_samples, sample_rate_hz, S.d_out, nullptr, nullptr)))
-    return rc;
-  HIPCHK(c, hipEventRecord(S.ev_ready, c->sn));
-  S.B = B;
-  S.n = num_samples;
-  H->begun++;
-  return 0;
+  return ds_host_begin(c, kDsHostForm, ids, B, packets, packet_bytes, num_samples, sample_rate_hz);
 }
 
-int lyra_hip_decode_samples_end(lyra_hip_ctx* c, int16_t* pcm) {
-  if (!c) return LYRA_HIP_EINVAL;
-  DsHost* H = static_cast<DsHost*>(c->ds_host);
-  if (!H || H->ended == H->begun) return fail(c, LYRA_HIP_EINVAL, "decode_samples_end: no request in flight");
-  DsHostSlot& S = H->slot[H->ended & 1];
-  if (S.n > 0 && !pcm) return fail(c, LYRA_HIP_EINVAL, "null pointer");
-  DEVSCOPE(c);
-  H->ended++;
-  if (S.n == 0) {
-    HIPCHK(c, hipEventSynchronize(S.ev_ready));
-    return 0;
-  }
-  const bool overlap = H->ended != H->begun;
-  hipStream_t down = overlap ? c->sq[0] : c->sn;
-  if (overlap) HIPCHK(c, hipStreamWaitEvent(down, S.ev_ready, 0));
-  HIPCHK(c, hipMemcpyAsync(pcm, S.d_out, (size_t)S.B * (size_t)S.n * 2, hipMemcpyDeviceToHost, down));
-  HIPCHK(c, hipStreamSynchronize(down));
-  return 0;
-}
+int lyra_hip_decode_samples_end(lyra_hip_ctx* c, int16_t* pcm) { return ds_host_end(c, kDsHostForm, pcm); }
 
 }  // extern "C"

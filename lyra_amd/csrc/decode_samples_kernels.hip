@@ -5,16 +5,14 @@
 // pass, the estimator's input gathered from whole received hops, the estimator, comfort noise for the rows that start
 // their hop in the second pass (they read the UPDATED estimate), the slices, the output resampler.
 #include "kernels.h"
-#include "decode_samples_plan.h"
+#include "decode_samples_rows.h"
 
 namespace lyra {
 
-// One thread per row applies the transition and hands out the call's id lists (-1 = the row skips that leg) and the
-// four info words; then 16 lanes per row move feature vectors as float4: the packet's features into the stream's ring
-// when their hop does not start in this call, and the features of the hop that starts -- the ring's oldest, or
-// ZeroFeatureEstimator's 64 x 0.0f -- into the row the decoder chain reads.  A packet whose hop starts in this same call
-// never goes through the ring.  Counted in *err, one atomic per wavefront at most: sizes that are neither 0 nor a
-// packet size of the codec, packets that found the ring full, rows whose plan left its proven bounds.
+// One thread per row applies the transition and hands out the call's id lists and the four info words (ds_plan_row,
+// decode_samples_rows.h); then 16 lanes per row move feature vectors through the stream's ring (ds_plan_move).  Counted in
+// *err, one atomic per wavefront at most: sizes that are neither 0 nor a packet size of the codec, packets that found the
+// ring full, rows whose plan left its proven bounds.
 __global__ __launch_bounds__(256) void ds_plan_kernel(const int32_t* __restrict__ ids, int B,
                                                        const int32_t* __restrict__ pkt_bytes, int n_internal,
                                                        uint8_t* __restrict__ cng_state, int32_t* __restrict__ gen_ids,
@@ -22,48 +20,18 @@ __global__ __launch_bounds__(256) void ds_plan_kernel(const int32_t* __restrict_
                                                        int32_t* __restrict__ est_ids, int32_t* __restrict__ info,
                                                        float* __restrict__ feats, float* __restrict__ ring,
                                                        unsigned* __restrict__ err) {
-  __shared__ int sh_id[256], sh_push[256], sh_src[256];
+  __shared__ DsPlanLds sh;
   const int tid = threadIdx.x, b0 = blockIdx.x * 256, b = b0 + tid;
   int nerr = 0;
-  sh_push[tid] = -1;
-  sh_src[tid] = DS_SRC_NONE;
+  ds_plan_lds_clear(sh, tid);
   if (b < B) {
-    const int id = ids[b];
     const int pb = pkt_bytes[b];
     const bool rx = mixed_received(pb);
     if (pb != 0 && !rx) nerr++;
-    DsState* sp = reinterpret_cast<DsState*>(cng_state + (size_t)id * st::CNG_BYTES + DS_STATE);
-    const DsPlan p = ds_plan(*sp, rx, n_internal);
-    *sp = p.s;
-    nerr += p.dropped + p.bad;
-    gen_ids[b] = p.gen_start >= 0 ? id : -1;
-    cng1_ids[b] = p.cng_start == 0 ? id : -1;
-    cng2_ids[b] = p.cng_start == 1 ? id : -1;
-    est_ids[b] = p.est_seg >= 0 ? id : -1;
-    int32_t w[4];
-    ds_info(p, w);
-    *reinterpret_cast<int4*>(info + (size_t)b * 4) = make_int4(w[0], w[1], w[2], w[3]);
-    const bool direct = p.push_slot >= 0 && p.gen_src == p.push_slot;   // this call's packet starts its hop at once
-    sh_id[tid] = id;
-    sh_push[tid] = direct ? -1 : p.push_slot;
-    sh_src[tid] = direct ? DS_SRC_NONE : p.gen_src;
+    ds_plan_row(sh, tid, b, ids[b], rx, n_internal, true, nerr, cng_state, gen_ids, cng1_ids, cng2_ids, est_ids, info);
   }
-  const unsigned long long bad = __ballot(nerr != 0);
-  if (bad) {   // (wave-uniform)
-    int n = nerr;
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
-    if ((tid & 63) == 0) atomicAdd(err, (unsigned)n);
-  }
-  __syncthreads();
-  const int rows = min(256, B - b0), q = tid & 15;
-  for (int r = tid >> 4; r < rows; r += 16) {
-    const int push = sh_push[r], src = sh_src[r];
-    float4* row = reinterpret_cast<float4*>(feats + (size_t)(b0 + r) * 64);
-    float4* slots = reinterpret_cast<float4*>(ring + (size_t)sh_id[r] * DS_FIFO_DEPTH * 64);
-    if (push >= 0) slots[push * 16 + q] = row[q];          // (push != src: the ring was not empty)
-    if (src == DS_SRC_ZERO) row[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    else if (src >= 0) row[q] = slots[src * 16 + q];
-  }
+  ds_wave_count(nerr, err, tid);
+  ds_plan_move(sh, tid, b0, B, feats, ring);
 }
 
 // est_in[b][0..320) = the whole received hop that completes in this call: the hop the stream holds (the part an earlier

@@ -1,6 +1,6 @@
 // decode_samples_streams_api.inc -- part of api.hip: lyra_hip_decode_samples_streams_dev
 // (include/lyra_hip_decode_samples_streams.h), lyra_hip_decode_samples_any_dev with a sample rate, a request size and an output
-// offset per row (decode_samples_streams_plan.h).  The call is dsa_launch (decode_samples_any_api.inc) with
+// offset per row (decode_samples_streams_plan.h).  The call is the any-size call's (ds_run, decode_samples_api.inc) with
 //   - max_hops rounds, given by the caller: the rows' sizes are on the device, a launch count is not;
 //   - ds_plan_streams_kernel in place of ds_plan_any_kernel: round 0 validates each row and plans an invalid one as a row
 //     without a packet and with a request of 0 samples;
@@ -103,53 +103,27 @@ int dss_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_pa
   if (rc) return rc;
   Dsa* A = dsa_of(c);
   Dss* S = dss_of(c);
-  const int R = max_hops;
-  const size_t cap = (size_t)A->cap, set = (size_t)(c->n_ds_calls & 1);
-  auto ids_of = [&](int r, int list) { return A->d_ids + ((set * DSA_MAX_HOPS + r) * 4 + list) * cap; };
-  auto info_of = [&](int r) { return A->d_info + (set * DSA_MAX_HOPS + r) * 4 * cap; };
-  auto gan_of = [&](int r) { return A->d_gan_new + (set * DSA_MAX_HOPS + r) * 320 * cap; };
+  const size_t set = (size_t)(c->n_ds_calls & 1);
+  DsCall K = {d_ids, B, d_packets, d_pkt_bytes, max_hops, true, nullptr, nullptr, nullptr, 0, A->d_pcm16, DSA_MAX_INTERNAL, true,
+              d_is_noise, d_is_cn};
+  dsa_round_bufs(A, set, &K);
   int32_t* call = S->d_call + set * DSS_CALL_WORDS * (size_t)S->cap;
-  // ---- decode stream: one unsplit decode-side call ---------------------------------------------------------------------
-  if ((rc = dec_side_begin(c, 0, 1))) return rc;
-  { ProfScope ps(c, K_RVQ_DEC, c->sd[0]);
-    hipLaunchKernelGGL(rvq_decode_mixed_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sd[0], c->model.cb, d_packets, d_pkt_bytes, 0, B,
-                       c->d_ds_feat); }
-  HIPCHK(c, hipGetLastError());
-  for (int r = 0; r < R; ++r) {
-    hipLaunchKernelGGL(ds_plan_streams_kernel, dim3(cdiv(B, 256)), dim3(256), 0, c->sd[0], d_ids, B,
-                       r == 0 ? d_pkt_bytes : nullptr, r, d_rates, d_sizes, d_offsets, max_hops, n_pcm, c->sm.base[st::R_RS_D],
-                       call, c->sm.base[st::R_CNG], ids_of(r, 0), ids_of(r, 1), ids_of(r, 2), ids_of(r, 3), info_of(r),
-                       c->d_ds_feat, c->d_ds_ring, c->d_ds_err, c->d_rates_err);
-    HIPCHK(c, hipGetLastError());
-    if ((rc = launch_generate(c, 0, 0, ids_of(r, 0), B, c->d_ds_feat, gan_of(r)))) return rc;
-  }
-  if ((rc = dec_side_done(c, 0, 1))) return rc;
-  c->n_dec_calls++;
-  // ---- noise stream: the rounds' comfort noise, estimator, comfort noise, slices; then the splice, as ONE noise call ------
-  if ((rc = noise_dev_begin(c))) return rc;
-  for (int r = 0; r < R; ++r) {
-    const int32_t* info = info_of(r);
-    const int16_t* gan_new = gan_of(r);
-    if ((rc = launch_cng(c, c->sn, ids_of(r, 1), B, nullptr, c->d_ds_cng_new))) return rc;
-    hipLaunchKernelGGL(ds_est_gather_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sn, d_ids, B, info, gan_new,
-                       (const int16_t*)c->d_ds_gan, c->d_ds_est);
-    HIPCHK(c, hipGetLastError());
-    if ((rc = launch_noise_masked(c, ids_of(r, 3), B, c->d_ds_est, d_is_noise))) return rc;
-    if ((rc = launch_cng(c, c->sn, ids_of(r, 2), B, nullptr, c->d_ds_cng_new))) return rc;
-    hipLaunchKernelGGL(ds_slice_kernel, dim3(cdiv(B, 4)), dim3(256), 0, c->sn, d_ids, B, info, gan_new,
-                       (const int16_t*)c->d_ds_cng_new, c->d_ds_gan, c->d_ds_cng, (const float*)c->d_fade, A->d_pcm16 + 320 * r,
-                       DSA_MAX_INTERNAL, (const uint8_t*)c->sm.base[st::R_NOISE_D], d_is_noise, d_is_cn);
-    HIPCHK(c, hipGetLastError());
-  }
-  { ProfScope ps(c, K_RESAMPLE, c->sn);
-    hipLaunchKernelGGL(ds_splice_streams_kernel, dim3(cdiv(B, 4)), dim3(256), ds_splice_streams_lds_bytes(), c->sn,
-                       (const ResampleP*)c->d_rs_tab, d_ids, B, (const int32_t*)call, c->sm.base[st::R_RS_D],
-                       (const int16_t*)A->d_pcm16, DSA_MAX_INTERNAL, d_pcm, d_offsets); }
-  HIPCHK(c, hipGetLastError());
-  c->rs_sn_pending = true;
-  if ((rc = noise_dev_done(c))) return rc;
-  c->n_ds_calls++;
-  return serial_noise_half_done(c);
+  return ds_run(
+      c, K,
+      [&](int r) {
+        hipLaunchKernelGGL(ds_plan_streams_kernel, dim3(cdiv(B, 256)), dim3(256), 0, c->sd[0], d_ids, B,
+                           r == 0 ? d_pkt_bytes : nullptr, r, d_rates, d_sizes, d_offsets, max_hops, n_pcm, c->sm.base[st::R_RS_D],
+                           call, c->sm.base[st::R_CNG], K.ids_of(r, 0), K.ids_of(r, 1), K.ids_of(r, 2), K.ids_of(r, 3), K.info_of(r),
+                           c->d_ds_feat, c->d_ds_ring, c->d_ds_err, c->d_rates_err);
+      },
+      [&] {
+        { ProfScope ps(c, K_RESAMPLE, c->sn);
+          hipLaunchKernelGGL(ds_splice_streams_kernel, dim3(cdiv(B, 4)), dim3(256), ds_splice_lds_bytes(), c->sn,
+                             (const ResampleP*)c->d_rs_tab, d_ids, B, (const int32_t*)call, c->sm.base[st::R_RS_D],
+                             (const int16_t*)A->d_pcm16, DSA_MAX_INTERNAL, d_pcm, d_offsets); }
+        HIPCHK(c, hipGetLastError());
+        return 0;
+      });
 }
 
 }  // namespace
@@ -188,20 +162,10 @@ int lyra_hip_decode_samples_streams_begin(lyra_hip_ctx* c, const int32_t* ids, i
     if (pb != 0 && pb != 8 && pb != 15 && pb != LYRA_HIP_MAX_PACKET_BYTES)
       return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_begin: packet of %d bytes at position %d (0, 8, 15 or 23)", pb, b);
   }
-  if (c->dss_begun - c->dss_ended >= 2)
-    return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_begin: two requests are already in flight "
-                "(lyra_hip_decode_samples_streams_end)");
-  if (c->brg_begun != c->brg_ended)   // (the bridge runs on both sides' streams)
-    return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_begin: a lyra_hip_bridge_begin tick is in flight (lyra_hip_bridge_end)");
-  { const PipeState* P = pipe_of(c);   // (one decode pipeline at a time: they share the decode-side streams' order)
-    const DsHost* H = static_cast<const DsHost*>(c->ds_host);
-    if ((P && P->d_begun != P->d_ended) || (H && H->begun != H->ended) || c->dstr_begun != c->dstr_ended ||
-        c->dsa_begun != c->dsa_ended)
-      return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_begin: a lyra_hip_decode_begin, lyra_hip_decode_streams_begin, "
-                  "lyra_hip_decode_samples_begin or lyra_hip_decode_samples_any_begin request is in flight (call its _end first)"); }
+  if ((rc = pl_admit(c, PL_DECODE_SAMPLES_STREAMS, "decode_samples_streams_begin"))) return rc;
   DEVSCOPE(c);
   // everything the call allocates or builds on first use, BEFORE anything is enqueued: a failure here leaves the streams idle
-  DssSlot& S = dss_of(c)->slot[c->dss_begun & 1];
+  DssSlot& S = dss_of(c)->slot[c->pl_begun[PL_DECODE_SAMPLES_STREAMS] & 1];
   if ((rc = dss_slot_ensure(c, &S, B))) return rc;
   if ((rc = dss_ensure_all(c, B))) return rc;
   const size_t n = (size_t)B;
@@ -229,18 +193,18 @@ int lyra_hip_decode_samples_streams_begin(lyra_hip_ctx* c, const int32_t* ids, i
   HIPCHK(c, hipEventRecord(S.ev_done, c->sn));
   S.B = B;
   S.total = total;
-  c->dss_begun++;
+  c->pl_begun[PL_DECODE_SAMPLES_STREAMS]++;
   return 0;
 }
 
 int lyra_hip_decode_samples_streams_end(lyra_hip_ctx* c, int16_t* pcm, int32_t* is_noise, int32_t* is_comfort_noise) {
   if (!c) return LYRA_HIP_EINVAL;
-  if (!c->dss || c->dss_ended == c->dss_begun)
+  if (!c->dss || c->pl_ended[PL_DECODE_SAMPLES_STREAMS] == c->pl_begun[PL_DECODE_SAMPLES_STREAMS])
     return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_end: no request in flight");
-  DssSlot& S = dss_of(c)->slot[c->dss_ended & 1];
+  DssSlot& S = dss_of(c)->slot[c->pl_ended[PL_DECODE_SAMPLES_STREAMS] & 1];
   if (S.total > 0 && !pcm) return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_end: null pointer");
   DEVSCOPE(c);
-  c->dss_ended++;                  // whatever happens below, the slot is given back
+  c->pl_ended[PL_DECODE_SAMPLES_STREAMS]++;                  // whatever happens below, the slot is given back
   HIPCHK(c, hipEventSynchronize(S.ev_done));
   const size_t n = (size_t)S.B;
   if (is_noise) std::memcpy(is_noise, S.h_out, n * 4);

@@ -102,27 +102,11 @@ int lyra_hip_decode_streams_begin(lyra_hip_ctx* c, const int32_t* ids, int B, co
     if (pb != 0 && pb != 8 && pb != 15 && pb != LYRA_HIP_MAX_PACKET_BYTES)
       return fail(c, LYRA_HIP_EINVAL, "decode_streams_begin: packet of %d bytes at position %d (0, 8, 15 or 23)", pb, b);
   }
-  if (c->dstr_begun - c->dstr_ended >= 2)
-    return fail(c, LYRA_HIP_EINVAL, "decode_streams_begin: two calls are already in flight (lyra_hip_decode_streams_end)");
-  if (c->brg_begun != c->brg_ended)   // (the bridge runs on both sides' streams)
-    return fail(c, LYRA_HIP_EINVAL, "decode_streams_begin: a lyra_hip_bridge_begin tick is in flight (lyra_hip_bridge_end)");
-  { const PipeState* P = pipe_of(c);
-    if (P && P->d_begun != P->d_ended)
-      return fail(c, LYRA_HIP_EINVAL, "decode_streams_begin: a lyra_hip_decode_begin call is in flight (lyra_hip_decode_end)");
-    if (c->dsa_begun != c->dsa_ended)
-      return fail(c, LYRA_HIP_EINVAL, "decode_streams_begin: a lyra_hip_decode_samples_any_begin request is in flight "
-                  "(lyra_hip_decode_samples_any_end)");
-    if (c->dss_begun != c->dss_ended)
-      return fail(c, LYRA_HIP_EINVAL, "decode_streams_begin: a lyra_hip_decode_samples_streams_begin request is in flight "
-                  "(lyra_hip_decode_samples_streams_end)");
-    const DsHost* H = static_cast<const DsHost*>(c->ds_host);
-    if (H && H->begun != H->ended)
-      return fail(c, LYRA_HIP_EINVAL, "decode_streams_begin: a lyra_hip_decode_samples_begin request is in flight "
-                  "(lyra_hip_decode_samples_end)"); }
+  if ((rc = pl_admit(c, PL_DECODE_STREAMS, "decode_streams_begin"))) return rc;
   DEVSCOPE(c);
   if ((rc = ensure_scratch(c, B))) return rc;
   if (!c->dstr_host) c->dstr_host = new DstrHost();
-  DstrSlot& S = static_cast<DstrHost*>(c->dstr_host)->slot[c->dstr_begun & 1];
+  DstrSlot& S = static_cast<DstrHost*>(c->dstr_host)->slot[c->pl_begun[PL_DECODE_STREAMS] & 1];
   if ((rc = dstr_slot_ensure(c, &S))) return rc;
   // everything the tick allocates or builds on first use, BEFORE anything is enqueued: a failure here leaves the streams idle
   if ((rc = rates_ensure(c))) return rc;
@@ -155,17 +139,17 @@ int lyra_hip_decode_streams_begin(lyra_hip_ctx* c, const int32_t* ids, int B, co
   HIPCHK(c, hipEventRecord(S.ev_done, c->sn));
   S.B = B;
   S.total = total;
-  c->dstr_begun++;
+  c->pl_begun[PL_DECODE_STREAMS]++;
   return 0;
 }
 
 int lyra_hip_decode_streams_end(lyra_hip_ctx* c, int16_t* pcm, int32_t* is_noise, int32_t* is_comfort_noise) {
   if (!c) return LYRA_HIP_EINVAL;
-  if (!c->dstr_host || c->dstr_ended == c->dstr_begun) return fail(c, LYRA_HIP_EINVAL, "decode_streams_end: no call in flight");
+  if (!c->dstr_host || c->pl_ended[PL_DECODE_STREAMS] == c->pl_begun[PL_DECODE_STREAMS]) return fail(c, LYRA_HIP_EINVAL, "decode_streams_end: no call in flight");
   if (!pcm) return fail(c, LYRA_HIP_EINVAL, "decode_streams_end: null pointer");
   DEVSCOPE(c);
-  DstrSlot& S = static_cast<DstrHost*>(c->dstr_host)->slot[c->dstr_ended & 1];
-  c->dstr_ended++;                 // whatever happens below, the slot is given back
+  DstrSlot& S = static_cast<DstrHost*>(c->dstr_host)->slot[c->pl_ended[PL_DECODE_STREAMS] & 1];
+  c->pl_ended[PL_DECODE_STREAMS]++;                 // whatever happens below, the slot is given back
   HIPCHK(c, hipEventSynchronize(S.ev_done));
   const size_t n = (size_t)S.B;
   if (is_noise) std::memcpy(is_noise, S.h_out, n * 4);

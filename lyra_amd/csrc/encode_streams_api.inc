@@ -77,18 +77,12 @@ int lyra_hip_encode_streams_begin(lyra_hip_ctx* c, const int32_t* ids, int B, co
     if ((rc = check_rate(c, sample_rates[b]))) return rc;
     if ((rc = check_bits(c, num_bits[b]))) return rc;
   }
-  if (c->es_begun - c->es_ended >= 2)
-    return fail(c, LYRA_HIP_EINVAL, "encode_streams_begin: two calls are already in flight (lyra_hip_encode_streams_end)");
-  if (c->brg_begun != c->brg_ended)   // (the bridge runs on both sides' streams)
-    return fail(c, LYRA_HIP_EINVAL, "encode_streams_begin: a lyra_hip_bridge_begin tick is in flight (lyra_hip_bridge_end)");
-  { const PipeState* P = pipe_of(c);
-    if (P && P->begun != P->ended)
-      return fail(c, LYRA_HIP_EINVAL, "encode_streams_begin: a lyra_hip_encode_begin call is in flight (lyra_hip_encode_end)"); }
+  if ((rc = pl_admit(c, PL_ENCODE_STREAMS, "encode_streams_begin"))) return rc;
   DEVSCOPE(c);
   if ((rc = ensure_scratch(c, B))) return rc;
   if ((rc = rates_ensure(c))) return rc;
   if (!c->es_host) c->es_host = new EsHost();
-  EsSlot& S = static_cast<EsHost*>(c->es_host)->slot[c->es_begun & 1];
+  EsSlot& S = static_cast<EsHost*>(c->es_host)->slot[c->pl_begun[PL_ENCODE_STREAMS] & 1];
   if ((rc = es_slot_ensure(c, &S))) return rc;
   // (the slot's previous user, two calls back, has ended: its kernels have read d_meta / d_in, its download has left h_out)
   const size_t n = (size_t)B;
@@ -106,7 +100,7 @@ int lyra_hip_encode_streams_begin(lyra_hip_ctx* c, const int32_t* ids, int B, co
   // under its kernels; with none, on the extractor's own stream.  Either way the host waits for them HERE: `pcm` is the
   // caller's again on return, and every kernel below is enqueued after its inputs have arrived.  (The noise stream also ends
   // the decode-side calls: on a context that decodes as well this wait covers decoder kernels that are on it -- see the header.)
-  hipStream_t up = c->es_begun != c->es_ended ? c->sn : c->se[0];
+  hipStream_t up = c->pl_begun[PL_ENCODE_STREAMS] != c->pl_ended[PL_ENCODE_STREAMS] ? c->sn : c->se[0];
   HIPCHK(c, hipMemcpyAsync(S.d_meta, h, n * 5 * 4, hipMemcpyHostToDevice, up));
   HIPCHK(c, hipMemcpyAsync(S.d_in, pcm, (size_t)total * 2, hipMemcpyHostToDevice, up));
   HIPCHK(c, hipStreamSynchronize(up));
@@ -121,17 +115,17 @@ int lyra_hip_encode_streams_begin(lyra_hip_ctx* c, const int32_t* ids, int B, co
   HIPCHK(c, hipMemcpyAsync(S.h_out + (size_t)c->max_streams * 24, S.d_len, (size_t)B * 4, hipMemcpyDeviceToHost, c->sq[0]));
   HIPCHK(c, hipEventRecord(S.ev_done, c->sq[0]));
   S.B = B;
-  c->es_begun++;
+  c->pl_begun[PL_ENCODE_STREAMS]++;
   return 0;
 }
 
 int lyra_hip_encode_streams_end(lyra_hip_ctx* c, uint8_t* packets, int32_t* packet_bytes) {
   if (!c) return LYRA_HIP_EINVAL;
-  if (!c->es_host || c->es_ended == c->es_begun) return fail(c, LYRA_HIP_EINVAL, "encode_streams_end: no call in flight");
+  if (!c->es_host || c->pl_ended[PL_ENCODE_STREAMS] == c->pl_begun[PL_ENCODE_STREAMS]) return fail(c, LYRA_HIP_EINVAL, "encode_streams_end: no call in flight");
   if (!packets || !packet_bytes) return fail(c, LYRA_HIP_EINVAL, "encode_streams_end: null pointer");
   DEVSCOPE(c);
-  EsSlot& S = static_cast<EsHost*>(c->es_host)->slot[c->es_ended & 1];
-  c->es_ended++;                   // whatever happens below, the slot is given back
+  EsSlot& S = static_cast<EsHost*>(c->es_host)->slot[c->pl_ended[PL_ENCODE_STREAMS] & 1];
+  c->pl_ended[PL_ENCODE_STREAMS]++;                   // whatever happens below, the slot is given back
   HIPCHK(c, hipEventSynchronize(S.ev_done));
   std::memcpy(packets, S.h_out, (size_t)S.B * LYRA_HIP_MAX_PACKET_BYTES);
   std::memcpy(packet_bytes, S.h_out + (size_t)c->max_streams * 24, (size_t)S.B * 4);

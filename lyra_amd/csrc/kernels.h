@@ -290,7 +290,7 @@ __global__ void ds_plan_any_kernel(const int32_t* ids, int B, const int32_t* pkt
                                    uint8_t* rs_state, int32_t* call, uint8_t* cng_state, int32_t* gen_ids, int32_t* cng1_ids,
                                    int32_t* cng2_ids, int32_t* est_ids, int32_t* info, float* feats, float* ring, unsigned* err);
 // the end of such a call at 8 / 32 / 48 kHz: resampler over call[b][2] samples per row, old leftover + new samples -> out
-// [B][n_ext], surplus -> the slot's leftover
+// [B][n_ext], surplus -> the slot's leftover.  (The plan kernels' and the splice kernels' shared bodies: decode_samples_rows.h.)
 size_t ds_splice_lds_bytes();
 __global__ void ds_splice_kernel(ResampleP P, const int32_t* ids, int B, const int32_t* call, uint8_t* state, const int16_t* in,
                                  int in_stride, int16_t* out, int n_ext);
@@ -302,8 +302,8 @@ __global__ void ds_plan_streams_kernel(const int32_t* ids, int B, const int32_t*
                                        uint8_t* rs_state, int32_t* call, uint8_t* cng_state, int32_t* gen_ids, int32_t* cng1_ids,
                                        int32_t* cng2_ids, int32_t* est_ids, int32_t* info, float* feats, float* ring,
                                        unsigned* err, unsigned* rates_err);
-// tab: the context's [2][3] designs (rates_api.inc); a 16 kHz row is copied from `in`, an invalid row touches nothing
-size_t ds_splice_streams_lds_bytes();
+// tab: the context's [2][3] designs (rates_api.inc); a 16 kHz row is copied from `in`, an invalid row touches nothing; LDS of
+// ds_splice_lds_bytes()
 __global__ void ds_splice_streams_kernel(const ResampleP* tab, const int32_t* ids, int B, const int32_t* call, uint8_t* state,
                                          const int16_t* in, int in_stride, int16_t* out, const int32_t* offsets);
 size_t logmel_lds_bytes();

@@ -37,11 +37,8 @@ struct PipeFetch {             // decoder twin: a request begun -- where its row
 };
 struct PipeState {
   PipeSlot slot[2];
-  long begun = 0, ended = 0;
   PipeFetch fetch[2];
-  long f_begun = 0, f_ended = 0;
   PipeDec dec[2];
-  long d_begun = 0, d_ended = 0;
   // Copy streams: the uploads of the encode pipeline and the downloads of the decoder twin overlap the kernels.  They are
   // BORROWED from the context -- the noise-estimator stream, idle in both twins (the decoder twin runs its estimator on the
   // decode-side stream) -- rather than created:
@@ -132,12 +129,8 @@ int lyra_hip_encode_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const int1
   if ((rc = ensure_scratch(c, B))) return rc;
   if ((rc = pipe_ensure(c))) return rc;
   PipeState* P = pipe_of(c);
-  if (P->begun - P->ended >= 2) return fail(c, LYRA_HIP_EINVAL, "encode_begin: two calls are already in flight (lyra_hip_encode_end)");
-  if (c->brg_begun != c->brg_ended)   // (the bridge runs on both sides' streams)
-    return fail(c, LYRA_HIP_EINVAL, "encode_begin: a lyra_hip_bridge_begin tick is in flight (lyra_hip_bridge_end)");
-  if (c->es_begun != c->es_ended)   // (the two encode pipelines share the encode-side streams' order: one at a time)
-    return fail(c, LYRA_HIP_EINVAL, "encode_begin: a lyra_hip_encode_streams_begin call is in flight (lyra_hip_encode_streams_end)");
-  PipeSlot& S = P->slot[P->begun & 1];
+  if ((rc = pl_admit(c, PL_ENCODE, "encode_begin"))) return rc;
+  PipeSlot& S = P->slot[c->pl_begun[PL_ENCODE] & 1];
   if ((rc = pipe_slot_ensure(c, &S))) return rc;
   const int n_ext = sample_rate_hz / 50, nbytes = (num_bits + 7) / 8;
   const size_t pcm_b = (size_t)B * n_ext * 2;
@@ -149,7 +142,7 @@ int lyra_hip_encode_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const int1
   // With no other call in flight there is nothing to overlap the upload with: it goes on the extractor's own stream and
   // the copy stream -- one more hardware queue of the few a process has (GPU_MAX_HW_QUEUES, 4 by default) -- stays unused,
   // so that a purely blocking caller (Encode = begin + end) runs exactly as lyra_hip_encode does.
-  const bool overlap = P->begun != P->ended;
+  const bool overlap = c->pl_begun[PL_ENCODE] != c->pl_ended[PL_ENCODE];
   hipStream_t up = overlap ? P->s_up : c->se[0];
   std::memcpy(S.h_in, ids, (size_t)B * 4);
   HIPCHK(c, hipMemcpyAsync(S.d_ids, S.h_in, (size_t)B * 4, hipMemcpyHostToDevice, up));
@@ -189,18 +182,18 @@ int lyra_hip_encode_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const int1
   if (dtx) HIPCHK(c, hipMemcpyAsync(S.h_out + (size_t)c->max_streams * 24, S.d_len, (size_t)B * 4, hipMemcpyDeviceToHost, c->sq[0]));
   HIPCHK(c, hipEventRecord(S.ev_done, c->sq[0]));
   S.B = B; S.nbytes = nbytes; S.dtx = dtx;
-  P->begun++;
+  c->pl_begun[PL_ENCODE]++;
   return 0;
 }
 
 int lyra_hip_encode_end(lyra_hip_ctx* c, uint8_t* packets, int32_t* packet_bytes) {
   if (!c) return LYRA_HIP_EINVAL;
   PipeState* P = pipe_of(c);
-  if (!P || P->ended == P->begun) return fail(c, LYRA_HIP_EINVAL, "encode_end: no call in flight");
+  if (!P || c->pl_ended[PL_ENCODE] == c->pl_begun[PL_ENCODE]) return fail(c, LYRA_HIP_EINVAL, "encode_end: no call in flight");
   if (!packets) return fail(c, LYRA_HIP_EINVAL, "null pointer");
   DEVSCOPE(c);
-  PipeSlot& S = P->slot[P->ended & 1];
-  P->ended++;                      // whatever happens below, the slot is given back
+  PipeSlot& S = P->slot[c->pl_ended[PL_ENCODE] & 1];
+  c->pl_ended[PL_ENCODE]++;                      // whatever happens below, the slot is given back
   HIPCHK(c, hipEventSynchronize(S.ev_done));
   std::memcpy(packets, S.h_out, (size_t)S.B * S.nbytes);
   if (packet_bytes) {
@@ -225,17 +218,8 @@ int lyra_hip_decode_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const uint
   if ((rc = ensure_scratch(c, B))) return rc;
   if ((rc = pipe_ensure(c))) return rc;
   PipeState* P = pipe_of(c);
-  if (P->d_begun - P->d_ended >= 2) return fail(c, LYRA_HIP_EINVAL, "decode_begin: two calls are already in flight (lyra_hip_decode_end)");
-  if (c->brg_begun != c->brg_ended)   // (the bridge runs on both sides' streams)
-    return fail(c, LYRA_HIP_EINVAL, "decode_begin: a lyra_hip_bridge_begin tick is in flight (lyra_hip_bridge_end)");
-  if (c->dstr_begun != c->dstr_ended)   // (the decode pipelines share the decode-side streams' order: one at a time)
-    return fail(c, LYRA_HIP_EINVAL, "decode_begin: a lyra_hip_decode_streams_begin call is in flight (lyra_hip_decode_streams_end)");
-  if (c->dsa_begun != c->dsa_ended)
-    return fail(c, LYRA_HIP_EINVAL, "decode_begin: a lyra_hip_decode_samples_any_begin request is in flight (lyra_hip_decode_samples_any_end)");
-  if (c->dss_begun != c->dss_ended)
-    return fail(c, LYRA_HIP_EINVAL, "decode_begin: a lyra_hip_decode_samples_streams_begin request is in flight "
-                "(lyra_hip_decode_samples_streams_end)");
-  PipeDec& S = P->dec[P->d_begun & 1];
+  if ((rc = pl_admit(c, PL_DECODE, "decode_begin"))) return rc;
+  PipeDec& S = P->dec[c->pl_begun[PL_DECODE] & 1];
   const size_t n = (size_t)c->max_streams;
   if (!S.h_in) {
     HIPCHK(c, hipHostMalloc((void**)&S.h_in, n * 4 + n * 24, hipHostMallocDefault));
@@ -266,19 +250,19 @@ int lyra_hip_decode_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const uint
   }
   HIPCHK(c, hipEventRecord(S.ev_ready, c->sd[0]));
   S.B = B;
-  P->d_begun++;
+  c->pl_begun[PL_DECODE]++;
   return 0;
 }
 
 int lyra_hip_decode_end(lyra_hip_ctx* c, int16_t* pcm) {
   if (!c) return LYRA_HIP_EINVAL;
   PipeState* P = pipe_of(c);
-  if (!P || P->d_ended == P->d_begun) return fail(c, LYRA_HIP_EINVAL, "decode_end: no call in flight");
+  if (!P || c->pl_ended[PL_DECODE] == c->pl_begun[PL_DECODE]) return fail(c, LYRA_HIP_EINVAL, "decode_end: no call in flight");
   if (!pcm) return fail(c, LYRA_HIP_EINVAL, "null pointer");
   DEVSCOPE(c);
-  PipeDec& S = P->dec[P->d_ended & 1];
-  P->d_ended++;
-  const bool overlap = P->d_ended != P->d_begun;
+  PipeDec& S = P->dec[c->pl_ended[PL_DECODE] & 1];
+  c->pl_ended[PL_DECODE]++;
+  const bool overlap = c->pl_ended[PL_DECODE] != c->pl_begun[PL_DECODE];
   hipStream_t down = overlap ? P->s_down : c->sd[0];
   if (overlap) HIPCHK(c, hipStreamWaitEvent(P->s_down, S.ev_ready, 0));
   HIPCHK(c, hipMemcpyAsync(pcm, S.d_pcm, (size_t)S.B * 640, hipMemcpyDeviceToHost, down));
@@ -306,12 +290,13 @@ int lyra_hip_twin_fetch_begin(lyra_hip_ctx* c, int num_streams, int num_internal
     c->twin_out_n = 0;
     return code;
   };
-  if (P->f_begun - P->f_ended >= 2) return abandon(fail(c, LYRA_HIP_EINVAL, "twin_fetch_begin: two requests are already in flight"));
+  // (its own depth only, not pl_admit: a refusal here abandons the request being assembled, and no other pipeline refuses it)
+  if (pl_in_flight(c, PL_TWIN_FETCH) >= PL_DEPTH) return abandon(fail(c, LYRA_HIP_EINVAL, "twin_fetch_begin: two requests are already in flight"));
   if (n < 0 || (n > 0 && c->twin_out_n != n)) {
     const int assembled = c->twin_out_n;
     return abandon(fail(c, LYRA_HIP_EINVAL, "twin_fetch: %d samples requested, %d assembled", n, assembled));
   }
-  PipeFetch& F = P->fetch[P->f_begun & 1];
+  PipeFetch& F = P->fetch[c->pl_begun[PL_TWIN_FETCH] & 1];
   F.bytes = 0;
   F.src = nullptr;
   if (n > 0) {
@@ -352,20 +337,20 @@ int lyra_hip_twin_fetch_begin(lyra_hip_ctx* c, int num_streams, int num_internal
   std::swap(c->d_twin_ext, P->alt_ext); std::swap(c->twin_ext_cap, P->alt_ext_cap);
   c->twin_args_used = 0;
   c->twin_out_n = 0;
-  P->f_begun++;
+  c->pl_begun[PL_TWIN_FETCH]++;
   return 0;
 }
 
 int lyra_hip_twin_fetch_end(lyra_hip_ctx* c, int16_t* out) {
   if (!c) return LYRA_HIP_EINVAL;
   PipeState* P = pipe_of(c);
-  if (!P || P->f_ended == P->f_begun) return fail(c, LYRA_HIP_EINVAL, "twin_fetch_end: no request in flight");
+  if (!P || c->pl_ended[PL_TWIN_FETCH] == c->pl_begun[PL_TWIN_FETCH]) return fail(c, LYRA_HIP_EINVAL, "twin_fetch_end: no request in flight");
   DEVSCOPE(c);
-  PipeFetch& F = P->fetch[P->f_ended & 1];
-  P->f_ended++;
+  PipeFetch& F = P->fetch[c->pl_ended[PL_TWIN_FETCH] & 1];
+  c->pl_ended[PL_TWIN_FETCH]++;
   // Nothing begun after this request: no kernels to overlap the download with -- it rides on the decode-side stream itself,
   // as in lyra_hip_twin_fetch, and the copy stream (one more of the process's few hardware queues) stays unused.
-  const bool overlap = P->f_ended != P->f_begun || c->twin_args_used != 0;
+  const bool overlap = c->pl_ended[PL_TWIN_FETCH] != c->pl_begun[PL_TWIN_FETCH] || c->twin_args_used != 0;
   hipStream_t down = overlap ? P->s_down : c->sd[0];
   if (overlap) HIPCHK(c, hipStreamWaitEvent(P->s_down, F.ev_ready, 0));
   if (F.bytes) {

@@ -185,13 +185,10 @@ int lyra_hip_shared_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const uint
     if (pb != 0 && pb != 8 && pb != 15 && pb != LYRA_HIP_MAX_PACKET_BYTES)
       return fail(c, LYRA_HIP_EINVAL, "%s: packet of %d bytes at position %d (0, 8, 15 or 23)", what, pb, b);
   }
-  if (c->brg_begun - c->brg_ended >= 2)
-    return fail(c, LYRA_HIP_EINVAL, "%s: two ticks are already in flight (call _end first)", what);
-  if (brg_other_in_flight(c))
-    return fail(c, LYRA_HIP_EINVAL, "%s: another pipelined request is in flight (call its _end first)", what);
+  if ((rc = brg_admit(c, what))) return rc;
   DEVSCOPE(c);
   if (!c->brg_host) c->brg_host = new BrgHost();
-  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->brg_begun & 1];
+  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->pl_begun[PL_BRIDGE] & 1];
   if ((rc = brg_slot_ensure(c, &S))) return rc;
   // (the slot's previous user, two ticks back, has ended)  going up, int32: ids | packet_bytes | order | muted [B] each,
   // room_start [B + 1], room keys [B], enc_ids | enc_bits | enc_dtx [E] each, then the packets
@@ -268,20 +265,20 @@ int lyra_hip_shared_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const uint
   S.B = B;
   S.max_speakers = max_speakers;
   S.shared = true;
-  c->brg_begun++;
+  c->pl_begun[PL_BRIDGE]++;
   return 0;
 }
 
 int lyra_hip_shared_end(lyra_hip_ctx* c, uint8_t* out_packets, int32_t* out_packet_bytes, int32_t* is_noise,
                         int32_t* is_comfort_noise, int64_t* levels, int32_t* is_speaker, int32_t* slot_of) {
   if (!c) return LYRA_HIP_EINVAL;
-  if (!c->brg_host || c->brg_ended == c->brg_begun) return fail(c, LYRA_HIP_EINVAL, "shared_end: no tick in flight");
-  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->brg_ended & 1];
+  if (!c->brg_host || c->pl_ended[PL_BRIDGE] == c->pl_begun[PL_BRIDGE]) return fail(c, LYRA_HIP_EINVAL, "shared_end: no tick in flight");
+  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->pl_ended[PL_BRIDGE] & 1];
   if (!S.shared)
     return fail(c, LYRA_HIP_EINVAL, "shared_end: the oldest tick was begun by %s", S.max_speakers ? "lyra_hip_speakers_begin" : "the full-mix begin()");
   if (!out_packets || !out_packet_bytes) return fail(c, LYRA_HIP_EINVAL, "shared_end: null pointer");
   DEVSCOPE(c);
-  c->brg_ended++;                  // whatever happens below, the slot is given back
+  c->pl_ended[PL_BRIDGE]++;                  // whatever happens below, the slot is given back
   HIPCHK(c, hipEventSynchronize(S.ev_done));
   const size_t n = (size_t)S.B;
   std::memcpy(out_packet_bytes, S.h_out, n * 4);

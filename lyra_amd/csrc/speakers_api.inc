@@ -129,13 +129,13 @@ int lyra_hip_speakers_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const ui
 int lyra_hip_speakers_end(lyra_hip_ctx* c, uint8_t* out_packets, int32_t* out_packet_bytes, int32_t* is_noise,
                           int32_t* is_comfort_noise, int64_t* levels, int32_t* is_speaker) {
   if (!c) return LYRA_HIP_EINVAL;
-  if (!c->brg_host || c->brg_ended == c->brg_begun) return fail(c, LYRA_HIP_EINVAL, "speakers_end: no tick in flight");
-  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->brg_ended & 1];
+  if (!c->brg_host || c->pl_ended[PL_BRIDGE] == c->pl_begun[PL_BRIDGE]) return fail(c, LYRA_HIP_EINVAL, "speakers_end: no tick in flight");
+  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->pl_ended[PL_BRIDGE] & 1];
   if (!S.max_speakers) return fail(c, LYRA_HIP_EINVAL, "speakers_end: the oldest tick was begun by the full-mix begin()");
   if (S.shared) return fail(c, LYRA_HIP_EINVAL, "speakers_end: the oldest tick was begun by lyra_hip_shared_begin");
   if (!out_packets || !out_packet_bytes) return fail(c, LYRA_HIP_EINVAL, "speakers_end: null pointer");
   DEVSCOPE(c);
-  c->brg_ended++;                  // whatever happens below, the slot is given back
+  c->pl_ended[PL_BRIDGE]++;                  // whatever happens below, the slot is given back
   HIPCHK(c, hipEventSynchronize(S.ev_done));
   const size_t n = (size_t)S.B;
   std::memcpy(out_packet_bytes, S.h_out, n * 4);

@@ -18,11 +18,7 @@ void blob_free(lyra_hip_ctx* c) {
 int blob_call_begin(lyra_hip_ctx* c, int B, const char* what) {
   int rc = check_batch(c, B);
   if (rc) return rc;
-  const PipeState* P = pipe_of(c);
-  const DsHost* H = static_cast<const DsHost*>(c->ds_host);
-  if ((P && (P->begun != P->ended || P->d_begun != P->d_ended || P->f_begun != P->f_ended)) || (H && H->begun != H->ended) ||
-      c->es_begun != c->es_ended || c->dstr_begun != c->dstr_ended || c->dsa_begun != c->dsa_ended ||
-      c->dss_begun != c->dss_ended || c->brg_begun != c->brg_ended || c->twin_out_n != 0)
+  if (pl_any_in_flight(c))
     return fail(c, LYRA_HIP_EINVAL, "%s: a pipelined request is outstanding (call its _end first)", what);
   for (int r = 0; r < st::R_COUNT; ++r)
     if (c->sm.bytes[r] != sb::region_bytes(r)) return fail(c, LYRA_HIP_EINVAL, "%s: region %d is not laid out as the blob's", what, r);

@@ -72,9 +72,8 @@ int twin_stage(lyra_hip_ctx* c, const void* src, size_t bytes, void** d_out) {
   // With pipelined requests (lyra_hip_twin_fetch_begin / _end) the previous request's arguments may not have been uploaded
   // yet when this one is staged: requests alternate between the two halves of the arena, and a request may only start
   // while at most one other is still in flight -- the half's previous user has ended by then.
-  const PipeState* P = pipe_of(c);
-  const size_t half = c->twin_args_cap / 2, base = P ? (size_t)(P->f_begun & 1) * half : 0;
-  if (c->twin_args_used == 0 && P && P->f_begun - P->f_ended >= 2)
+  const size_t half = c->twin_args_cap / 2, base = (size_t)(c->pl_begun[PL_TWIN_FETCH] & 1) * half;
+  if (c->twin_args_used == 0 && pl_in_flight(c, PL_TWIN_FETCH) >= PL_DEPTH)
     return fail(c, LYRA_HIP_EINVAL, "twin: two requests are already in flight (lyra_hip_twin_fetch_end)");
   if (c->twin_args_used + need > half) {   // half full: everything staged so far has to be consumed first
     HIPCHK(c, hipStreamSynchronize(c->sd[0]));

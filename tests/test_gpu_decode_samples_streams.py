@@ -300,6 +300,58 @@ def test_host_form_and_refusals(golden_dir, oracle_default):
         ctx.close(); ref.close()
 
 
+def test_decode_pipelines_refuse_each_other_as_before():
+    """Which decode pipeline's begin() is refused while which other one is in flight, for every ordered pair of the five decode
+    pipelines and for a bridge tick against each of them in both directions.  The relation is written out here: every pair
+    of different pipelines refuses, except decode <-> decode_samples (allowed, not known to be intended); a second begin() of
+    the pipeline that is in flight is accepted (each is two deep).  Two streams, no packets, requests of 0 samples where the
+    call has a size; lyra_hip_decode_begin, decode_streams_begin and the bridge tick run one real hop."""
+    from lyra_amd.codec import LyraHipError
+    ids = np.array([40, 41], np.int32)
+    none, pk = np.zeros(2, np.int32), np.zeros((2, 23), np.uint8)
+    r48 = np.full(2, 48000, np.int32)
+    ctx = make_ctx(64)
+    try:
+        L = ctx.L
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.lyra_hip_decode_samples_begin.restype, L.lyra_hip_decode_samples_begin.argtypes = ci, [vp, vp, ci, vp, vp, ci, ci]
+        L.lyra_hip_decode_samples_end.restype, L.lyra_hip_decode_samples_end.argtypes = ci, [vp, vp]
+
+        def one_hop_begin():
+            if L.lyra_hip_decode_samples_begin(ctx.h, ids.ctypes.data, 2, pk.ctypes.data, none.ctypes.data, 0, 48000) != 0:
+                raise LyraHipError(ctx.last_error())
+
+        def one_hop_end():
+            assert L.lyra_hip_decode_samples_end(ctx.h, None) == 0
+
+        pipes = {
+            "decode": (lambda: ctx.decode_begin(pk[:, :8].copy(), 64, ids), ctx.decode_end),
+            "decode_streams": (lambda: ctx.decode_streams_begin(pk, none, r48, ids), ctx.decode_streams_end),
+            "decode_samples": (one_hop_begin, one_hop_end),
+            "decode_samples_any": (lambda: ctx.decode_samples_any_begin(pk, none, 0, 48000, ids), ctx.decode_samples_any_end),
+            "decode_samples_streams": (lambda: ctx.decode_samples_streams_begin(pk, none, r48, none, ids),
+                                       ctx.decode_samples_streams_end),
+            "bridge": (lambda: ctx.bridge_begin(pk, none, [0, 0], [64, 64], stream_ids=ids), ctx.bridge_end),
+        }
+        decoders = [p for p in pipes if p != "bridge"]
+        refuses = {(x, y): x != y and {x, y} != {"decode", "decode_samples"} for x in pipes for y in pipes}
+        pairs = [(x, y) for x in decoders for y in decoders] + [("bridge", y) for y in decoders] + \
+                [(x, "bridge") for x in decoders]
+        assert len(pairs) == 35 and sum(refuses[p] for p in pairs) == 28
+        for x, y in pairs:
+            pipes[x][0]()
+            if refuses[x, y]:
+                with pytest.raises(LyraHipError):
+                    pipes[y][0]()
+            else:
+                pipes[y][0]()                  # accepted: it raises otherwise
+                pipes[y][1]()
+            pipes[x][1]()
+            ctx.export_streams(ids)            # (refused while anything is in flight: both were ended, a refused begin left nothing)
+    finally:
+        ctx.close()
+
+
 def test_a_leftover_travels(golden_dir, oracle_default):
     """A 48 kHz stream that holds 2 samples is exported from a context driven by the new call and imported into one driven by
     decode_samples_any_dev; both go on, bit for bit."""
