@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void ds_splice_kernel(ResampleP P, const int32
   const int b = blockIdx.x * 4 + w;
   if (b >= B) return;
   const int4 cw = *reinterpret_cast<const int4*>(call + (size_t)b * 4);
-  ds_splice_row(P, ds_splice_lds_row(rsb_all, w), lane, cw, state + (size_t)ids[b] * st::RS_BYTES, in + (size_t)b * in_stride,
+  ds_splice_row(P, ds_splice_lds_row(rsb_all, w), lane, cw, state, ids[b], in + (size_t)b * in_stride,
                 out + (size_t)b * n_ext, n_ext);
 }
 

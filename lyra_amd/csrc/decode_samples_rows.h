@@ -5,6 +5,7 @@
 #pragma once
 #include "kernels.h"
 #include "decode_samples_any_plan.h"
+#include "resample_pass.h"
 
 namespace lyra {
 
@@ -66,7 +67,7 @@ __device__ __forceinline__ void ds_plan_move(const DsPlanLds& sh, int tid, int b
   }
 }
 
-// Where resample_fir.inc's `dst[i] = v` goes in ds_splice_row: the first n_new resampled samples to the caller's row behind
+// rs_fir's destination (`dst[i] = v`, resample_pass.h) in ds_splice_row: the first n_new resampled samples to the caller's row behind
 // the old leftover, the surplus (at most DSA_LEFT_MAX) to the slot's leftover; anything beyond is dropped.
 struct SpliceDst {
   int16_t* row; int16_t* left; int n_new;
@@ -81,18 +82,17 @@ struct SpliceDst {
 };
 
 // One wavefront, one row at 8 / 32 / 48 kHz: the row's n_int internal samples (cw.z, 0..1280, at src) run through the stream's
-// resampler (slot) with the text of resample_kernel (resample_fir.inc, resample_slot.inc: same taps, same separately rounded
+// resampler (slot `id` of the region `state`) as resample_kernel's do (rs_stream_pass, resample_pass.h: same taps, same separately rounded
 // products, same history and phase write-back); row = the old leftover's first `used` samples (cw.y), then the new ones; the
 // surplus becomes the stream's leftover.  Counts come from the call words cw alone (the slot's count may already be the next
 // call's).  A row with n_int == 0 touches no resampler state: it serves from the leftover and moves what remains to the front.
 // Rows are of any length and alignment, so samples move one int16 at a time.  rsb is the wavefront's own LDS row: no workgroup
 // barrier, the order of its writes and reads is pinned by wavefront fences.
-__device__ __forceinline__ void ds_splice_row(const ResampleP& P, float* rsb, int lane, int4 cw, uint8_t* slot,
+__device__ __forceinline__ void ds_splice_row(const ResampleP& P, float* rsb, int lane, int4 cw, uint8_t* state, int id,
                                               const int16_t* __restrict__ src, int16_t* __restrict__ row, int n_ext) {
-  constexpr int H = st::RS_TAPS - 1;
   const int used = __builtin_amdgcn_readfirstlane(cw.y);
   const int n_in = min(__builtin_amdgcn_readfirstlane(cw.z), DSA_MAX_INTERNAL);
-  int16_t* left = reinterpret_cast<int16_t*>(slot + DSA_LEFT_SAMPLES);
+  int16_t* left = reinterpret_cast<int16_t*>(state + (size_t)id * st::RS_BYTES + DSA_LEFT_SAMPLES);
   int16_t keep = 0;
   if (lane < DSA_LEFT_MAX) keep = left[lane];
   if (lane < used) row[lane] = keep;
@@ -101,18 +101,8 @@ __device__ __forceinline__ void ds_splice_row(const ResampleP& P, float* rsb, in
     if (used > 0 && lane < DSA_LEFT_MAX) left[lane] = lane + used < DSA_LEFT_MAX ? next : (int16_t)0;
     return;
   }
-  const bool vec = false;
-#include "resample_load.inc"
-  float* hist = reinterpret_cast<float*>(slot + st::RS_HIST);
-  const int in_pos = *reinterpret_cast<const int*>(slot + st::RS_IN_POS);
-  if (lane < H) rsb[lane] = hist[lane];
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   const int n_out = n_in / P.down;   // (down-sampling: n_in is even and the phase 0, decode_samples_any_plan.h)
-  const SpliceDst dst{row + used, left, n_ext - used};
-#include "resample_fir.inc"
-#include "resample_slot.inc"
+  rs_stream_pass<false, SpliceDst>(&P, rsb, lane, state, id, src, n_in, false, SpliceDst{row + used, left, n_ext - used}, n_out);
   if (lane < DSA_LEFT_MAX && lane >= cw.w) left[lane] = 0;   // (the FIR wrote the cw.w samples that stay)
 }
 

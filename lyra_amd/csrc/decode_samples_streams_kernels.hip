@@ -88,12 +88,12 @@ __global__ __launch_bounds__(256) void ds_splice_streams_kernel(const ResampleP*
   const long off = offsets ? (long)__builtin_amdgcn_readfirstlane(offsets[b]) : dss_default_offset(b);
   int16_t* row = out + off;
   const int16_t* src = in + (size_t)b * in_stride;
-  const int di = rate == 8000 ? 0 : rate == 32000 ? 1 : rate == 48000 ? 2 : -1;
+  const int di = rs_design_index(rate);
   if (di < 0) {   // 16 kHz: the samples themselves
     for (int i = lane; i < n_ext; i += 64) row[i] = src[i];
     return;
   }
-  ds_splice_row(tab[3 + di], ds_splice_lds_row(rsb_all, w), lane, cw, state + (size_t)ids[b] * st::RS_BYTES, src, row, n_ext);
+  ds_splice_row(tab[3 + di], ds_splice_lds_row(rsb_all, w), lane, cw, state, ids[b], src, row, n_ext);
 }
 
 }  // namespace lyra

@@ -217,7 +217,7 @@ constexpr int TWIN_FADE_LO = -640, TWIN_FADE_N = 1921;   // fade_progress range 
 __global__ void twin_scatter_kernel(const int16_t* src, const int32_t* ids, int B, int16_t* dst);
 __global__ void twin_assemble_kernel(const TwinSlice* slices, int B, const int16_t* gan, const int16_t* cng,
                                      const float* fade_w, int16_t* out, int out_stride, int16_t* noise_dense);
-// the counter-based phase generator of the comfort noise (cng_frame.inc)
+// the counter-based phase generator of the comfort noise (cng_frame.h)
 __device__ __forceinline__ unsigned long long splitmix64_dev(unsigned long long x) {
   x += 0x9E3779B97F4A7C15ull;
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -356,6 +356,17 @@ __global__ void span_handover_kernel(const SpanRow* rows, int n, int r0, StateMa
 // call's SpanRows, hence their size.
 struct SpanRsRow { long long frame0, n_frames; int32_t id, wg0, pad[2]; };
 static_assert(sizeof(SpanRsRow) == sizeof(SpanRow), "one upload holds both kinds of row");
+// The row of workgroup wg where the grid is the workgroups of all rows (SpanRsRow, SpanDtxRow, SpanLossyRow): the last row whose
+// first workgroup (member wg0) is not behind wg; rows in rising wg0, rows[0].*wg0 == 0, n_rows >= 1.  Scalar work: blockIdx alone.
+template <typename Row>
+__device__ __forceinline__ int span_row_of_workgroup(const Row* rows, int n_rows, int32_t Row::*wg0, int wg) {
+  int lo = 0, hi = n_rows - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (rows[mid].*wg0 <= wg) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
 // in [frames][n_in] -> out [frames][n_out] for the frames of the rows' spans, with the design P (n_out = n_in * up / down);
 // state = the resampler region of the side (R_RS_E / R_RS_D): read and written by each span's frame 0 only (the phase word is
 // read by all).  grid = the workgroups of all rows, 256 threads, LDS resample_lds_bytes(n_in).

@@ -4,6 +4,7 @@
 // masked list, mix, NoiseEstimator on the received rows, output resampler (noise stream).
 #include "kernels.h"
 #include "lossy_plan.h"
+#include "cng_frame.h"
 
 namespace lyra {
 
@@ -56,13 +57,7 @@ __global__ __launch_bounds__(256) void lossy_mix_kernel(const int32_t* __restric
 #pragma unroll
   for (int j = 0; j < 5; ++j) {
     const int i = lane + 64 * j;
-    int16_t v;
-    if (!noise) v = g[i];
-    else if (!gen) v = c[i];
-    else {
-#include "lossy_mix.inc"
-    }
-    o[i] = v;
+    o[i] = !noise ? g[i] : !gen ? c[i] : lossy_fade_sample(fade_w, fade, dir, i, g, c);
   }
   if (lane == 0) {
     if (is_cn) is_cn[b] = (f & LOSSY_CN) ? 1 : 0;

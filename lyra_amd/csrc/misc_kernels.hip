@@ -1,6 +1,9 @@
 // misc_kernels.hip -- residual vector quantizer, packet (un)packing, log-mel front end, state reset.
 #include "kernels.h"
 #include "lossy_plan.h"
+#include "logmel_stages.h"
+#include "resample_pass.h"
+#include "cng_frame.h"
 
 #ifdef LYRA_TIMING
 extern "C" int lyra_hip_debug_timing_misc(long long* out) {
@@ -356,7 +359,6 @@ __device__ __forceinline__ int digit_reverse4_1024(int n) {   // reverse the fiv
 // kRowDtx (logmel_streams_kernel, with kRates): `dtx` holds one flag per row; a row with dtx[b] == 0 takes the path of an
 // id -1 row (its estimator slot, the log-mel history included, is neither read nor written), except that masked_ids[b] is
 // its id and is_noise_out[b] is 0.
-__device__ __forceinline__ int mel_rate_index(int rate) { return rate == 8000 ? 0 : rate == 32000 ? 2 : rate == 48000 ? 3 : 1; }
 size_t logmel_rates_lds_bytes() { return (size_t)(1024 * 2 + 514) * 8; }
 
 template <bool kMasked, bool kRates = false, bool kRowDtx = false>
@@ -369,16 +371,13 @@ __device__ __forceinline__ void logmel_body(const MelP* __restrict__ Pp, const i
                                             const int32_t* __restrict__ rates = nullptr,
                                             const NoiseP* __restrict__ np_tab = nullptr,
                                             const int32_t* __restrict__ dtx = nullptr) {
-  typedef double f64x2 __attribute__((ext_vector_type(2)));
   const MelP& P = Pp[kRates ? 1 : 0];   // (window and twiddles are the same tables at every rate)
   extern __shared__ __attribute__((aligned(16))) double dsm[];
-  f64x2* z = reinterpret_cast<f64x2*>(dsm);   // Z[1024], (re, im) = (frame A, frame B) interleaved; later (|X_A[k]|, |X_B[k]|)
-  // LDS reuse once the two spectra are separated (z[k], k > 512, is then dead): the mel weights of bins 0..512, the hop's
-  // mel vectors [2][160] floats and noise_update_wave's [2][2][160] + [2][2] floats -- 16 KB per workgroup in all
-  double* wl = dsm + 1026;
-  float* mel_lds = reinterpret_cast<float*>(dsm + 1540);
-  float* tail_sh = reinterpret_cast<float*>(dsm + 1540 + 160);
-  float* tail_avg = reinterpret_cast<float*>(dsm + 1540 + 160 + 320);
+  // LDS (logmel_stages.h): the FFT buffer, then in its dead upper half the mel weights, the hop's mel vectors [2][160] floats
+  // and noise_update_wave's [2][2][160] + [2][2] floats -- 16 KB per workgroup in all
+  float* mel_lds = reinterpret_cast<float*>(dsm + LOGMEL_MEL);
+  float* tail_sh = reinterpret_cast<float*>(dsm + LOGMEL_MEL + 160);
+  float* tail_avg = reinterpret_cast<float*>(dsm + LOGMEL_MEL + 160 + 320);
   const int tid = threadIdx.x;
   int b0_ = blockIdx.x * 2;
   bool two_ = b0_ + 1 < B;
@@ -411,33 +410,28 @@ __device__ __forceinline__ void logmel_body(const MelP* __restrict__ Pp, const i
   int16_t* prev1 = reinterpret_cast<int16_t*>(state + (size_t)ids[two ? b1 : b0] * stride + prev_off);
   const int16_t* cur0 = pcm + (size_t)b0 * 320;
   const int16_t* cur1 = pcm + (size_t)(two ? b1 : b0) * 320;
-#include "logmel_window.inc"
+  const LogmelWin win = logmel_window<kRates>(P, PA, PB, two, prev0, prev1, cur0, cur1, reinterpret_cast<f64x2*>(dsm), tid);
   __syncthreads();
   // every read of the old history is done: the hop becomes the history
-  if (has1) { prev0[n - 64] = b0s; if (two) prev1[n - 64] = b1s; }
-  if (has2) { prev0[n + 192] = c0s; if (two) prev1[n + 192] = c1s; }
+  if (tid >= 64) { prev0[tid - 64] = win.b0s; if (two) prev1[tid - 64] = win.b1s; }
+  if (tid < 128) { prev0[tid + 192] = win.c0s; if (two) prev1[tid + 192] = win.c1s; }
   LYRA_TSTAMP(111);
-#include "logmel_fft.inc"
+  logmel_fft<kRates>(P, win, dsm, tid);
   LYRA_TSTAMP(114);
   // the noise tail's view of the stream's slot is requested here, one batch, and arrives under the band sums
   const int tw = tid >> 6;
   const int tail_id = ids[(tw == 1 && two) ? b1 : b0];
   NoisePre npre = {};
   if (noise_tail) npre = noise_prefetch(tail_id, state, tw < 2);
-  // bins whose lower band is b-1 contribute (v - v*w) to band b, bins whose lower band is b contribute v*w; ascending
-  // bin order (== the reference's scatter loop order per band); the next bin's operands are read one trip ahead
-  // (what band_item sums over is rebound per item under kRates: each frame has its own edges and weights)
-  int e0 = be0, e1 = be1, e2 = be2;
-  const double* wt = (kRates && tid >= 160) ? wl1 : wl;
-  auto band_item = [&](int f, int band) {
-#include "logmel_band.inc"
+  // (what a band item sums over is chosen per item under kRates: each frame has its own edges and weights)
+  auto band_item = [&](int f, int band, int e0, int e1, int e2) {
+    const float lm = logmel_band(dsm, f, e0, e1, e2, logmel_wl<kRates>(dsm, f));
     if (mel) mel[(size_t)(b0 + f) * 160 + band] = lm;
     if (noise_tail) mel_lds[f * 160 + band] = lm;
   };
-  if (tid < 160) band_item(0, tid);
-  else if (two) band_item(1, tid - 96);
-  if constexpr (kRates) { e0 = ce0; e1 = ce1; e2 = ce2; wt = wl1; }
-  if (tid < 64 && two) band_item(1, tid);
+  if (tid < 160) band_item(0, tid, win.be0, win.be1, win.be2);
+  else if (two) band_item(1, tid - 96, win.be0, win.be1, win.be2);
+  if (tid < 64 && two) band_item(1, tid, win.ce0, win.ce1, win.ce2);
   LYRA_TSTAMP(115);
   if (noise_tail) {   // (uniform)
     __syncthreads();
@@ -683,25 +677,13 @@ __global__ __launch_bounds__(256) void resample_kernel(ResampleP P, const int32_
                                                         int out_stride) {
   LYRA_STRESS(8);
   extern __shared__ __attribute__((aligned(16))) float rsb_all[];   // [4][RS_TAPS - 1 + n_in, padded to 4]
-  constexpr int H = st::RS_TAPS - 1;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const int b = blockIdx.x * 4 + w;
   const bool on = b < B;
   const int bb = on ? b : B - 1;
-  float* rsb = rsb_all + w * ((H + n_in + 3) & ~3);
-  const int16_t* src = in + (size_t)bb * in_stride;
-  // the new samples do not wait for the stream id; 16-byte items when the rows allow it
-  const bool vec = ((in_stride | n_in) & 7) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
-#include "resample_load.inc"
-  uint8_t* slot = state + (size_t)ids[bb] * st::RS_BYTES;
-  float* hist = reinterpret_cast<float*>(slot + st::RS_HIST);
-  const int in_pos = *reinterpret_cast<const int*>(slot + st::RS_IN_POS);
-  if (lane < H) rsb[lane] = hist[lane];
-  __syncthreads();
-  if (!on) return;
-  int16_t* dst = out + (size_t)b * out_stride;
-#include "resample_fir.inc"
-#include "resample_slot.inc"
+  const bool vec = ((in_stride | n_in) & 7) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;   // 16-byte items where the rows allow
+  rs_stream_pass<true>(&P, rsb_all + w * ((RS_H + n_in + 3) & ~3), lane, state, ids[bb],
+                       in + (size_t)bb * in_stride, n_in, vec, out + (size_t)b * out_stride, n_out, on);
 }
 
 // Per-stream sample rates (lyra_hip_encode_rates_dev / lyra_hip_decode_lossy_rates_dev): row b is resampled between
@@ -721,12 +703,11 @@ __global__ __launch_bounds__(256) void resample_rates_kernel(const ResampleP* __
                                                               int32_t* __restrict__ ids_out, unsigned* __restrict__ err) {
   LYRA_STRESS(8);
   extern __shared__ __attribute__((aligned(16))) float rsb_all[];   // [4][RS_TAPS - 1 + 960, padded to 4]
-  constexpr int H = st::RS_TAPS - 1;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const int b = blockIdx.x * 4 + w;
   if (b >= B) return;
   const int rate = __builtin_amdgcn_readfirstlane(rates[b]);
-  const int di = rate == 8000 ? 0 : rate == 32000 ? 1 : rate == 48000 ? 2 : -1;
+  const int di = rs_design_index(rate);
   const int id = ids[b];
   const int16_t* src = in + (size_t)b * in_stride;
   int16_t* dst = out + (size_t)b * out_stride;
@@ -740,23 +721,11 @@ __global__ __launch_bounds__(256) void resample_rates_kernel(const ResampleP* __
     return;
   }
   if (ids_out && lane == 0) ids_out[b] = id;
-  const ResampleP& P = tab[dir * 3 + di];
   const int n_ext = rate / 50;
   const int n_in = dir == 0 ? n_ext : 320, n_out = dir == 0 ? 320 : n_ext;
-  float* rsb = rsb_all + w * ((H + 960 + 3) & ~3);
   const bool vec = (in_stride & 7) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;   // (every n_in is a multiple of 8)
-#include "resample_load.inc"
-  uint8_t* slot = state + (size_t)id * st::RS_BYTES;
-  float* hist = reinterpret_cast<float*>(slot + st::RS_HIST);
-  const int in_pos = *reinterpret_cast<const int*>(slot + st::RS_IN_POS);
-  if (lane < H) rsb[lane] = hist[lane];
-  // the FIR reads what other lanes of this wavefront have just written to its LDS row: no workgroup barrier is possible
-  // behind the early returns above and none is needed, but the order is pinned rather than assumed
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#include "resample_fir.inc"
-#include "resample_slot.inc"
+  rs_stream_pass(tab + dir * 3 + di, rsb_all + w * ((RS_H + 960 + 3) & ~3), lane, state, id, src, n_in, vec,
+                 dst, n_out);
 }
 
 // Packed rows (lyra_hip_encode_streams_dev): resample_rates_kernel, dir 0, with row b at in + offsets[b] (offsets == nullptr:
@@ -772,13 +741,13 @@ __global__ __launch_bounds__(256) void resample_streams_kernel(const ResampleP* 
                                                                 int32_t* __restrict__ ids_out, unsigned* __restrict__ err) {
   LYRA_STRESS(8);
   extern __shared__ __attribute__((aligned(16))) float rsb_all[];   // [4][RS_TAPS - 1 + 960, padded to 4]
-  constexpr int H = st::RS_TAPS - 1;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const int b = blockIdx.x * 4 + w;
   if (b >= B) return;
   const int rate = __builtin_amdgcn_readfirstlane(rates[b]);
-  const int di = rate == 8000 ? 0 : rate == 32000 ? 1 : rate == 48000 ? 2 : -1;
-  const int id = ids[b];
+  const int di = rs_design_index(rate);
+  // (wave-uniform like the rate; said so, the slot's address costs no vector registers: 63, and 65 cost a wave -- DESIGN.md 4.4)
+  const int id = __builtin_amdgcn_readfirstlane(ids[b]);
   const long off = offsets ? (long)__builtin_amdgcn_readfirstlane(offsets[b]) : (long)b * in_stride;
   const int n_in = rate / 50;
   const bool ok = (di >= 0 || rate == 16000) && off >= 0 && (off & 7) == 0 && off + n_in <= n_in_total;
@@ -796,21 +765,8 @@ __global__ __launch_bounds__(256) void resample_streams_kernel(const ResampleP* 
     for (int i = lane; i < 320; i += 64) dst[i] = src[i];
     return;
   }
-  const ResampleP& P = tab[di];
-  const int n_out = 320;
-  float* rsb = rsb_all + w * ((H + 960 + 3) & ~3);
   const bool vec = (reinterpret_cast<uintptr_t>(in) & 15) == 0;   // (every offset and every n_in is a multiple of 8)
-#include "resample_load.inc"
-  uint8_t* slot = state + (size_t)id * st::RS_BYTES;
-  float* hist = reinterpret_cast<float*>(slot + st::RS_HIST);
-  const int in_pos = *reinterpret_cast<const int*>(slot + st::RS_IN_POS);
-  if (lane < H) rsb[lane] = hist[lane];
-  // (as in resample_rates_kernel: a wavefront reads only the LDS row it wrote)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#include "resample_fir.inc"
-#include "resample_slot.inc"
+  rs_stream_pass(tab + di, rsb_all + w * ((RS_H + 960 + 3) & ~3), lane, state, id, src, n_in, vec, dst, 320);
 }
 
 // The decode-direction twin (lyra_hip_decode_streams_dev): resample_rates_kernel, dir 1, with row b's rates[b] / 50 samples
@@ -827,12 +783,11 @@ __global__ __launch_bounds__(256) void resample_streams_out_kernel(const Resampl
                                                                     long n_out_total, unsigned* __restrict__ err) {
   LYRA_STRESS(8);
   extern __shared__ __attribute__((aligned(16))) float rsb_all[];   // [4][RS_TAPS - 1 + 960, padded to 4]
-  constexpr int H = st::RS_TAPS - 1;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const int b = blockIdx.x * 4 + w;
   if (b >= B) return;
   const int rate = __builtin_amdgcn_readfirstlane(rates[b]);
-  const int di = rate == 8000 ? 0 : rate == 32000 ? 1 : rate == 48000 ? 2 : -1;
+  const int di = rs_design_index(rate);
   const long off = offsets ? (long)__builtin_amdgcn_readfirstlane(offsets[b]) : (long)b * out_stride;
   const int n_out = rate / 50;
   const bool ok = (di >= 0 || rate == 16000) && off >= 0 && (off & 7) == 0 && off + n_out <= n_out_total;
@@ -846,22 +801,9 @@ __global__ __launch_bounds__(256) void resample_streams_out_kernel(const Resampl
     for (int i = lane; i < 320; i += 64) dst[i] = src[i];
     return;
   }
-  const int id = ids[b];
-  const ResampleP& P = tab[3 + di];
-  const int n_in = 320;
-  float* rsb = rsb_all + w * ((H + 960 + 3) & ~3);
   const bool vec = (in_stride & 7) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;   // (as resample_rates_kernel, dir 1)
-#include "resample_load.inc"
-  uint8_t* slot = state + (size_t)id * st::RS_BYTES;
-  float* hist = reinterpret_cast<float*>(slot + st::RS_HIST);
-  const int in_pos = *reinterpret_cast<const int*>(slot + st::RS_IN_POS);
-  if (lane < H) rsb[lane] = hist[lane];
-  // (as in resample_rates_kernel: a wavefront reads only the LDS row it wrote)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#include "resample_fir.inc"
-#include "resample_slot.inc"
+  rs_stream_pass(tab + 3 + di, rsb_all + w * ((RS_H + 960 + 3) & ~3), lane, state, ids[b], src, 320, vec,
+                 dst, n_out);
 }
 
 // =============================================================================================
@@ -939,13 +881,13 @@ __global__ __launch_bounds__(256) void cng_kernel(const MelP* __restrict__ Pp, u
                                : reinterpret_cast<const float*>(noise_state + (size_t)id * st::NOISE_BYTES + st::N_EST);
   // (the slot key is zero unless the stream was imported from another id or context: state_layout.h C_KEY)
   const unsigned long long sd = seed ^ (unsigned long long)(unsigned)id ^ *reinterpret_cast<const unsigned long long*>(slot + st::C_KEY);
-#include "cng_frame.inc"
+  cng_frame(P, tid, feat, sd, hop, re, im, mel);
   // window, overlap-add, emit the first 320 samples, shift the accumulator by one hop
   double acc[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int n = tid + 256 * q;
-    acc[q] = ola[n] + cng_windowed(n);
+    acc[q] = ola[n] + cng_windowed(re, n);
   }
   __syncthreads();
 #pragma unroll

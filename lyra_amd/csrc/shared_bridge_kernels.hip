@@ -12,12 +12,11 @@
 // not trusted: room_start is clamped, every order[] entry, key, row number and slot that went through memory is checked against
 // its range where it is read, before it addresses anything.
 #include "kernels.h"
+#include "speakers_rows.h"   // SPK_MAX, SPK_LANES, SpkAcc, spk_add, spk_minus
 
 namespace lyra {
 
 namespace {
-
-#include "speakers_rows.inc"   // SPK_MAX, SPK_LANES, SpkAcc, spk_add, spk_minus
 
 constexpr int PKT = 23;   // LYRA_HIP_MAX_PACKET_BYTES
 

@@ -1,12 +1,26 @@
-// span_noise_scan.inc -- text of span_noise_scan_kernel (spans_dtx_kernels.hip) and span_lossy_scan_kernel (spans_lossy_kernels.hip):
-// NoiseEstimator::ReceiveSamples' decision + recurrence over a list of frames, one wavefront, state in registers.
-// In scope: P (NoiseP), lane, base (the stream's estimator slot), m (the list's mel rows, SPAN_MEL_ROW floats each), n (frames of
-// the list), the type Extra and the hooks
-//   load_extra(j, in)                      what on_frame needs of list entry j beside its mel row, requested with the row
-//   on_entry(est, last_is_noise)           the slot's estimate and is_noise() before the first frame
-//   on_frame(j, is_noise, active, est, x)  frame j decided and applied: active = non-noise frames in front of it, est = the
-//                                          estimate after it, x = its Extra
-//   on_exit(active)                        the slot is written
+// span_noise_scan.h -- NoiseEstimator::ReceiveSamples' decision + recurrence over a list of frames, one wavefront, state in
+// registers: the body of span_noise_scan_kernel, span_noise_scan_rates_kernel and span_lossy_scan_kernel.  Same float operations
+// in the same order as noise_update_wave (misc_kernels.hip), restated here because the state lives elsewhere.
+#pragma once
+#include "kernels.h"
+
+namespace lyra {
+
+// One wavefront of 64 lanes (a workgroup of its own: static LDS of 160 floats), lane l owns bins l, l + 64, l + 128 (< 160).
+// P: the estimator's constants; base: the stream's estimator slot, read once on entry and written once on exit; m: the list's
+// mel rows (SPAN_MEL_ROW floats each: 160 bins, then their Average()); n: frames of the list.  The frames are walked in order
+// -- ComputeIsNoise, then DecayBounds or the update.  Mel rows do not depend on the state: the rows of the next four frames
+// are requested while the current four are worked on.  Average(smoothed) does depend on it and stays a sequential 160-term
+// chain: the 160 values go through LDS and lane 0 sums them.
+// Hooks, a struct passed by reference, says what the caller does with the decisions:
+//   typename Hooks::Extra                    what on_frame needs of a list entry beside its mel row
+//   load_extra(j, in)                        that of entry j (in == false: past the list, any value), requested with the row
+//   on_entry(est, last_is_noise)             the slot's estimate and is_noise() before the first frame
+//   on_frame(j, is_noise, active, est, x)    frame j applied: active = non-noise frames in front of it, est = the estimate after it
+//   on_exit(active)                          the slot is written
+template <typename Hooks>
+__device__ __forceinline__ void span_noise_scan(const NoiseP& P, int lane, uint8_t* base, const float* m, long long n, Hooks& hooks) {
+  typedef typename Hooks::Extra Extra;
   typedef float f32x4_t __attribute__((ext_vector_type(4)));
   __shared__ __attribute__((aligned(16))) float sh[160];
   int* hdr = reinterpret_cast<int*>(base);
@@ -29,7 +43,7 @@
   int initialised = hdr[st::N_INIT / 4];
   int hops = hdr[st::N_HOPS / 4];
   int last_is_noise = hdr[st::N_IS_NOISE / 4];
-  on_entry(est, last_is_noise);
+  hooks.on_entry(est, last_is_noise);
   long long active = 0;
   constexpr int PF = 4;
   float nb[PF][3], na[PF];
@@ -42,7 +56,7 @@
 #pragma unroll
       for (int i = 0; i < 3; ++i) nb[k][i] = in && lane + 64 * i < 160 ? r[lane + 64 * i] : 0.f;
       na[k] = in ? r[160] : 0.f;
-      nx[k] = load_extra(in ? fb + k : 0, in);
+      nx[k] = hooks.load_extra(in ? fb + k : 0, in);
     }
   };
   request(0);
@@ -123,7 +137,7 @@
         hops = (hops + 1) % P.hops_per_update;
       }
       last_is_noise = is_noise ? 1 : 0;
-      on_frame(fb + k, is_noise, active, est, cx[k]);
+      hooks.on_frame(fb + k, is_noise, active, est, cx[k]);
       active += is_noise ? 0 : 1;
     }
   }
@@ -137,4 +151,40 @@
     hdr[st::N_HOPS / 4] = hops;
     hdr[st::N_IS_NOISE / 4] = last_is_noise;
   }
-  on_exit(active);
+  hooks.on_exit(active);
+}
+
+// The hooks of a DTX scan over the span `row`: flag_out[frame] = v_noise / v_active, map[region + c] = buffer frame of the
+// span's c-th non-noise frame (map optional), *count = the span's non-noise frames.
+struct SpanDtxScanHooks {
+  struct Extra {};
+  int lane;
+  const SpanDtxRow& row;
+  int32_t* flag_out;
+  int v_noise, v_active;
+  long long* map;
+  int32_t* count;
+  __device__ __forceinline__ Extra load_extra(long long, bool) const { return Extra(); }
+  __device__ __forceinline__ void on_entry(const float (&)[3], int) const {}
+  __device__ __forceinline__ void on_frame(long long j, bool is_noise, long long active, const float (&)[3], Extra) const {
+    if (lane == 0) {
+      const long long frame = row.frame0 + j;
+      flag_out[frame] = is_noise ? v_noise : v_active;
+      if (map && !is_noise) map[row.region + active] = frame;
+    }
+  }
+  __device__ __forceinline__ void on_exit(long long active) const {
+    if (lane == 0) *count = (int32_t)active;
+  }
+};
+
+// the DTX scan of the wavefront's span rows[blockIdx.x] (blockIdx.x < the number of rows) with the constants P
+__device__ __forceinline__ void span_dtx_scan(const NoiseP& P, const SpanDtxRow* rows, uint8_t* state, const float* mel,
+                                              int32_t* flag_out, int v_noise, int v_active, long long* map, int32_t* counts) {
+  const int lane = threadIdx.x;
+  const SpanDtxRow row = rows[blockIdx.x];
+  SpanDtxScanHooks hooks{lane, row, flag_out, v_noise, v_active, map, counts + blockIdx.x};
+  span_noise_scan(P, lane, state + (size_t)row.id * st::NOISE_BYTES, mel + (size_t)row.region * SPAN_MEL_ROW, row.n_frames, hooks);
+}
+
+}  // namespace lyra

@@ -4,19 +4,15 @@
 // can be computed before any encoder stage runs.  Two kernels:
 //   span_logmel_kernel      the estimator's log-mel front end.  Its state is one hop of history (N_PREV), and inside a span that
 //                           hop is the row in front of the frame: every frame of every span in ONE launch (the argument of
-//                           span_resample_kernel).  The arithmetic is logmel_body's -- logmel_window.inc, logmel_fft.inc and
-//                           logmel_band.inc are the text of both.
+//                           span_resample_kernel).  The arithmetic is logmel_body's: both call the stages of logmel_stages.h.
 //   span_noise_scan_kernel  the recurrence.  It is serial in time but small (160 bins, five floats per bin, two integers): one
 //                           wavefront per span walks its frames with the state in registers.  Same float operations in the same
 //                           order as noise_update_wave (misc_kernels.hip), restated here because the state lives elsewhere.
 #include "kernels.h"
+#include "logmel_stages.h"
+#include "span_noise_scan.h"
 
 namespace lyra {
-
-namespace {
-__device__ __forceinline__ i32x4 ld16(const void* p) { return *reinterpret_cast<const i32x4*>(p); }
-__device__ __forceinline__ void st16(void* p, i32x4 v) { *reinterpret_cast<i32x4*>(p) = v; }
-}  // namespace
 
 // One workgroup per pair of consecutive frames (f0, f0 + 1) of ONE span (rows[] names the first workgroup of each span with
 // frames; the lookup is on blockIdx alone); a span of an odd number of frames ends in a workgroup of one frame.
@@ -29,10 +25,9 @@ __device__ __forceinline__ void st16(void* p, i32x4 v) { *reinterpret_cast<i32x4
 __global__ __launch_bounds__(256) void span_logmel_kernel(const MelP* __restrict__ P1, const SpanDtxRow* __restrict__ rows,
                                                            int n_rows, uint8_t* __restrict__ state,
                                                            const int16_t* __restrict__ pcm, float* __restrict__ mel) {
-  auto mel_of_row = [&](int) { return P1; };   // one filterbank per call
-#include "span_logmel_rows.inc"
+  // one filterbank per call
+  span_logmel_row(*P1, rows[span_row_of_workgroup(rows, n_rows, &SpanDtxRow::wg0, (int)blockIdx.x)], (int)blockIdx.x, state, pcm, mel);
 }
-static_assert(st::N_PREV % 16 == 0 && st::NOISE_BYTES % 16 == 0 && SPAN_MEL_ROW % 4 == 0, "16-byte moves");
 
 // One wavefront per span, lane l owns bins l, l + 64, l + 128 (< 160) as in noise_update_wave.  The slot is read once, the frames
 // are walked in order -- ComputeIsNoise, then DecayBounds or the update -- and the slot is written once.  Mel rows do not depend
@@ -43,7 +38,7 @@ __global__ __launch_bounds__(64) void span_noise_scan_kernel(NoiseP P, const Spa
                                                               int32_t* __restrict__ flag_out, int v_noise, int v_active,
                                                               long long* __restrict__ map, int32_t* __restrict__ counts) {
   if ((int)blockIdx.x >= n_rows) return;
-#include "span_noise_scan_rows.inc"
+  span_dtx_scan(P, rows, state, mel, flag_out, v_noise, v_active, map, counts);
 }
 
 }  // namespace lyra

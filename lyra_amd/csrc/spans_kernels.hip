@@ -7,6 +7,7 @@
 // the dense buffer.  Every access is guarded by the row count of the step and the row's own step range.
 // The one kernel here that computes is span_resample_kernel at the end: the spans' resampler at 8 / 32 / 48 kHz, one launch per call.
 #include "kernels.h"
+#include "resample_pass.h"
 
 namespace lyra {
 
@@ -101,52 +102,22 @@ __global__ __launch_bounds__(256) void span_handover_kernel(const SpanRow* __res
 // of every span in ONE launch, in front of the steps (encode: external rate -> 16 kHz) or behind them (decode).  The FIR's
 // whole state is its last 34 input samples and the decimation phase, and inside a span those samples lie in the input buffer
 // right in front of the frame, so no frame waits for another.  One wavefront per frame, four frames of ONE span per workgroup
-// (rows[] names the first workgroup of each span with frames; the lookup is on blockIdx alone, so it is scalar work).
-//   frame 0 of a span: history from the span stream's slot -- never from the buffer, the rows in front may be another span's
-//                      -- and the only wavefront that writes the slot: RS_HIST = the span's last 34 input samples, RS_IN_POS
-//                      advanced by n_frames * n_in mod 6, what n_frames calls of resample_kernel leave.
-//   later frames:      history = the 34 samples in front of the frame.  Of the slot they read the phase word alone, which the
-//                      frame-0 wavefront may be replacing meanwhile: old and new value differ by a multiple of n_in, n_in is a
-//                      multiple of `down` and `down` divides 6, so `first` below is the same from either.  A relaxed atomic
-//                      load says that this is meant; an up-sampling pass has no phase and does not read it.
-// Same taps, same acc = acc + coef * x chain, same clip as resample_kernel: resample_fir.inc is the text of both.
+// (rows[] names the first workgroup of each span with frames: span_row_of_workgroup).  Frame 0 of a span takes its history from
+// the span stream's slot -- never from the buffer, the rows in front may be another span's -- and alone writes the slot; later
+// frames take the 34 samples in front of the frame (rs_span_pass, resample_pass.h: the FIR is resample_kernel's).
 __global__ __launch_bounds__(256) void span_resample_kernel(ResampleP P, const SpanRsRow* __restrict__ rows, int n_rows,
                                                              uint8_t* __restrict__ state, const int16_t* __restrict__ in,
                                                              int n_in, int16_t* __restrict__ out, int n_out) {
   extern __shared__ __attribute__((aligned(16))) float rsb_all[];   // [4][RS_TAPS - 1 + n_in, padded to 4]
-  constexpr int H = st::RS_TAPS - 1;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  int lo = 0, hi = n_rows - 1;   // the last row whose first workgroup is not behind this one
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (rows[mid].wg0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const SpanRsRow row = rows[lo];
+  const SpanRsRow row = rows[span_row_of_workgroup(rows, n_rows, &SpanRsRow::wg0, (int)blockIdx.x)];
   const long long f = ((long long)blockIdx.x - row.wg0) * 4 + w;   // frame of the span
   if (f >= row.n_frames) return;   // (wave-uniform)
-  float* rsb = rsb_all + w * ((H + n_in + 3) & ~3);
+  // rows of 160 / 320 / 640 / 960 samples in a 16-byte aligned buffer; n_in > RS_H: `last` lies inside the span's last frame
   const int16_t* src = in + (size_t)(row.frame0 + f) * n_in;
-  int16_t* dst = out + (size_t)(row.frame0 + f) * n_out;
-  const bool vec = true;   // rows of 160 / 320 / 640 / 960 samples in a 16-byte aligned buffer
-#include "resample_load.inc"
-  uint8_t* slot = state + (size_t)row.id * st::RS_BYTES;
-  float* hist = reinterpret_cast<float*>(slot + st::RS_HIST);
-  const int in_pos = f == 0 || P.down > 1
-                         ? __hip_atomic_load(reinterpret_cast<const int*>(slot + st::RS_IN_POS), __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT)
-                         : 0;
-  if (lane < H) rsb[lane] = f == 0 ? hist[lane] : (float)src[lane - H];
-  // the FIR reads what other lanes of this wavefront have just written to its LDS row (as in resample_rates_kernel)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#include "resample_fir.inc"
-  if (f != 0) return;
-  const int16_t* last = in + (size_t)(row.frame0 + row.n_frames) * n_in - H;   // (n_in > H: inside the span's last frame)
-  if (lane < H) hist[lane] = (float)last[lane];
-  if (lane == 0)
-    __hip_atomic_store(reinterpret_cast<int*>(slot + st::RS_IN_POS), (in_pos + (int)(row.n_frames % 6) * (n_in % 6)) % 6,
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  rs_span_pass(&P, rsb_all + w * ((RS_H + n_in + 3) & ~3), lane, state + (size_t)row.id * st::RS_BYTES, f, row.n_frames, src,
+               src - RS_H, in + (size_t)(row.frame0 + row.n_frames) * n_in - RS_H, n_in, out + (size_t)(row.frame0 + f) * n_out,
+               n_out);
 }
 
 }  // namespace lyra

@@ -3,35 +3,23 @@
 // tick does; what is left for the device, in stream order:
 //   span_lossy_feat_kernel    a step's concealed rows get ZeroFeatureEstimator's 64 x 0.0f in place of the RVQ decode;
 //   span_logmel_map_kernel    the estimator's log-mel of every RECEIVED frame in one launch: span_logmel_kernel with the previous
-//                             hop taken from the previous received frame of the span (span_logmel.inc is the text of both);
-//   span_lossy_scan_kernel    the recurrence over the received list, one wavefront per span (span_noise_scan.inc is the text of
-//                             this kernel and span_noise_scan_kernel); it also writes the estimate to a snapshot row after the
+//                             hop taken from the previous received frame of the span (both call span_logmel, logmel_stages.h);
+//   span_lossy_scan_kernel    the recurrence over the received list, one wavefront per span (span_noise_scan, span_noise_scan.h,
+//                             as span_noise_scan_kernel, with hooks of its own); it also writes the estimate to a snapshot row after the
 //                             frames the plan marks, and is_noise of the received frames;
 //   span_cng_kernel           comfort noise + mix of every run_cng tick.  The phases are counter-based, so every frame's inverse
 //                             STFT is independent; only the overlap-add is ordered, and a hop overlaps the three frames in front
-//                             of it: workgroup k synthesises frames k - 3 .. k (cng_frame.inc, the text of cng_kernel too) and
+//                             of it: workgroup k synthesises frames k - 3 .. k (cng_frame, cng_frame.h, as cng_kernel) and
 //                             adds them oldest first, exactly the additions the sequential accumulator has seen.  No scratch.
 //                             A second launch, one workgroup per span, leaves the accumulator and the hop counter;
 //   span_lossy_finish_kernel  is_comfort_noise, is_noise of the frames without a packet, the final control word.
 #include "kernels.h"
 #include "lossy_plan.h"
+#include "cng_frame.h"
+#include "logmel_stages.h"
+#include "span_noise_scan.h"
 
 namespace lyra {
-
-namespace {
-__device__ __forceinline__ i32x4 ld16(const void* p) { return *reinterpret_cast<const i32x4*>(p); }
-__device__ __forceinline__ void st16(void* p, i32x4 v) { *reinterpret_cast<i32x4*>(p) = v; }
-
-// the last row whose first workgroup (member wg0) is not behind workgroup wg; rows in rising wg0, rows[0].*wg0 == 0
-__device__ __forceinline__ int row_of_workgroup(const SpanLossyRow* rows, int n_rows, int32_t SpanLossyRow::*wg0, int wg) {
-  int lo = 0, hi = n_rows - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (rows[mid].*wg0 <= wg) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-}  // namespace
 
 // io[r]: a stream id in, that stream's control word out (one thread per span; the one thing the host waits for)
 __global__ __launch_bounds__(256) void span_lossy_ctl_read_kernel(int32_t* __restrict__ io, int n, int max_streams,
@@ -65,7 +53,7 @@ __global__ __launch_bounds__(256) void span_logmel_map_kernel(const MelP* __rest
                                                                int n_rows, uint8_t* __restrict__ state,
                                                                const SpanLossyRx* __restrict__ rx,
                                                                const int16_t* __restrict__ pcm, float* __restrict__ mel) {
-  const SpanLossyRow row = rows[row_of_workgroup(rows, n_rows, &SpanLossyRow::rx_wg0, (int)blockIdx.x)];
+  const SpanLossyRow row = rows[span_row_of_workgroup(rows, n_rows, &SpanLossyRow::rx_wg0, (int)blockIdx.x)];
   const int j0 = ((int)blockIdx.x - row.rx_wg0) * 2;
   if (j0 >= row.n_rx) return;   // (workgroup-uniform, before any barrier)
   const bool two = j0 + 1 < row.n_rx, first = j0 == 0;
@@ -76,8 +64,7 @@ __global__ __launch_bounds__(256) void span_logmel_map_kernel(const MelP* __rest
   const int16_t* prev0 = first ? slot_prev : pcm + (size_t)list[j0 - 1].frame * 320;
   const int16_t* prev1 = two ? cur0 : prev0;
   const int16_t* last = pcm + (size_t)list[row.n_rx - 1].frame * 320;
-  float* out = mel + (size_t)(row.rx0 + j0) * SPAN_MEL_ROW;
-#include "span_logmel.inc"
+  span_logmel(*Pp, two, first, cur0, cur1, prev0, prev1, slot_prev, last, mel + (size_t)(row.rx0 + j0) * SPAN_MEL_ROW);
 }
 
 // One wavefront per span over its received list.  snaps[row][160]: the estimate (N_EST) after the entries whose snap names a
@@ -87,31 +74,34 @@ __global__ __launch_bounds__(64) void span_lossy_scan_kernel(NoiseP P, const Spa
                                                               uint8_t* __restrict__ state, const float* __restrict__ mel,
                                                               const SpanLossyRx* __restrict__ rx, int32_t* __restrict__ is_noise_out,
                                                               float* __restrict__ snaps, int32_t* __restrict__ entry_noise) {
-  const int lane = threadIdx.x;
   if ((int)blockIdx.x >= n_rows) return;
   const SpanLossyRow row = rows[blockIdx.x];
-  uint8_t* base = state + (size_t)row.id * st::NOISE_BYTES;
-  const float* m = mel + (size_t)row.rx0 * SPAN_MEL_ROW;
-  const long long n = row.n_rx;
-  const SpanLossyRx* list = rx + row.rx0;
-  struct Extra { long long frame; int snap; };
-  auto load_extra = [&](long long j, bool in) { return in ? Extra{list[j].frame, list[j].snap} : Extra{0, -1}; };
-  auto snapshot = [&](int at, const float (&est)[3]) {
-    if (at < 0) return;   // (wave-uniform)
+  struct Hooks {
+    struct Extra { long long frame; int snap; };
+    int lane;
+    const SpanLossyRx* list;
+    int snap_v0;
+    int32_t* is_noise_out;
+    float* snaps;
+    int32_t* entry_noise;
+    __device__ __forceinline__ Extra load_extra(long long j, bool in) const { return in ? Extra{list[j].frame, list[j].snap} : Extra{0, -1}; }
+    __device__ __forceinline__ void snapshot(int at, const float (&est)[3]) const {
+      if (at < 0) return;   // (wave-uniform)
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
-      if (lane + 64 * i < 160) snaps[(size_t)at * 160 + lane + 64 * i] = est[i];
-  };
-  auto on_entry = [&](const float (&est)[3], int last_is_noise) {
-    snapshot(row.snap_v0, est);
-    if (lane == 0) entry_noise[blockIdx.x] = last_is_noise;
-  };
-  auto on_frame = [&](long long, bool is_noise, long long, const float (&est)[3], Extra x) {
-    if (lane == 0 && is_noise_out) is_noise_out[x.frame] = is_noise ? 1 : 0;
-    snapshot(x.snap, est);
-  };
-  auto on_exit = [](long long) {};
-#include "span_noise_scan.inc"
+      for (int i = 0; i < 3; ++i)
+        if (lane + 64 * i < 160) snaps[(size_t)at * 160 + lane + 64 * i] = est[i];
+    }
+    __device__ __forceinline__ void on_entry(const float (&est)[3], int last_is_noise) const {
+      snapshot(snap_v0, est);
+      if (lane == 0) *entry_noise = last_is_noise;
+    }
+    __device__ __forceinline__ void on_frame(long long, bool is_noise, long long, const float (&est)[3], Extra x) const {
+      if (lane == 0 && is_noise_out) is_noise_out[x.frame] = is_noise ? 1 : 0;
+      snapshot(x.snap, est);
+    }
+    __device__ __forceinline__ void on_exit(long long) const {}
+  } hooks{(int)threadIdx.x, rx + row.rx0, row.snap_v0, is_noise_out, snaps, entry_noise + blockIdx.x};
+  span_noise_scan(P, hooks.lane, state + (size_t)row.id * st::NOISE_BYTES, mel + (size_t)row.rx0 * SPAN_MEL_ROW, row.n_rx, hooks);
 }
 
 // Comfort noise and mix.  final == 0: grid = the run_cng ticks of all rows; workgroup k of a span produces tick k: its hop is
@@ -119,7 +109,7 @@ __global__ __launch_bounds__(64) void span_lossy_scan_kernel(NoiseP P, const Spa
 // accumulator held there -- the slot's C_OLA on entry while that still reaches (position < 1024), else the 0.0 that the shift
 // brought in (so that -0.0 cannot survive) -- and of frames k - 3 .. k.  Frame j has hop counter C_HOP + j and reads the
 // estimate snapshot of its tick.  The clipped hop is the tick's output or is cross-faded with the generative hop already in
-// pcm16[frame] (lossy_mix.inc, the text of lossy_mix_kernel too), in place.  Nothing of the slot is written.
+// pcm16[frame] (lossy_fade_sample, as lossy_mix_kernel), in place.  Nothing of the slot is written.
 // final != 0: grid = rows; the workgroup of a span with n_cng > 0 forms positions 320 n_cng .. + 1023 the same way -- what the
 // sequential accumulator holds after the span -- and writes C_OLA and C_HOP + n_cng.
 __global__ __launch_bounds__(256) void span_cng_kernel(const MelP* __restrict__ Pp, unsigned long long seed,
@@ -141,7 +131,7 @@ __global__ __launch_bounds__(256) void span_cng_kernel(const MelP* __restrict__ 
     tk = rows[rw].n_cng;
     if (tk == 0) return;   // (workgroup-uniform, like every return here)
   } else {
-    rw = row_of_workgroup(rows, n_rows, &SpanLossyRow::cng_wg0, (int)blockIdx.x);
+    rw = span_row_of_workgroup(rows, n_rows, &SpanLossyRow::cng_wg0, (int)blockIdx.x);
     tk = (int)blockIdx.x - rows[rw].cng_wg0;
     if (tk >= rows[rw].n_cng) return;
   }
@@ -163,11 +153,11 @@ __global__ __launch_bounds__(256) void span_cng_kernel(const MelP* __restrict__ 
   for (int j = tk > 3 ? tk - 3 : 0; j <= j_last; ++j) {
     const float* feat = snaps + (size_t)list[j].snap * 160;
     const unsigned long long hop = hop0 + (unsigned long long)j;
-#include "cng_frame.inc"
+    cng_frame(P, tid, feat, sd, hop, re, im, mel);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int at = 320 * (tk - j) + tid + 256 * q;   // the accumulator position inside frame j
-      if (at < 1024) acc[q] = acc[q] + cng_windowed(at);
+      if (at < 1024) acc[q] = acc[q] + cng_windowed(re, at);
     }
     __syncthreads();   // re[] is rebuilt by the next frame
   }
@@ -190,12 +180,7 @@ __global__ __launch_bounds__(256) void span_cng_kernel(const MelP* __restrict__ 
     double y = acc[q];
     y = y < -32768.0 ? -32768.0 : (y > 32767.0 ? 32767.0 : y);   // ClipToInt16<double>
     hop_out[i] = (int16_t)y;   // (read back by this thread alone)
-    int16_t v;
-    if (!gen) v = c[i];
-    else {
-#include "lossy_mix.inc"
-    }
-    o[i] = v;
+    o[i] = !gen ? c[i] : lossy_fade_sample(fade_w, fade, dir, i, g, c);
   }
 }
 

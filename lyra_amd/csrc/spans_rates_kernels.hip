@@ -6,19 +6,18 @@
 // scalar work and the coefficients stay scalar operands.  The row's rate rides in SpanRsRow::pad[0]; the estimator's kernels read it
 // from the resampler's row of the same index (both lists hold one row per span with frames, in the order of the call's spans).
 //   span_resample_rates_kernel    span_resample_kernel; rows of the external-rate buffer are padded to a stride
-//   span_logmel_rates_kernel      span_logmel_kernel (span_logmel_rows.inc is the text of both)
-//   span_noise_scan_rates_kernel  span_noise_scan_kernel (span_noise_scan_rows.inc is the text of both)
+//   span_logmel_rates_kernel      span_logmel_kernel (both call span_logmel_row, logmel_stages.h)
+//   span_noise_scan_rates_kernel  span_noise_scan_kernel (both call span_dtx_scan, span_noise_scan.h)
 #include "kernels.h"
+#include "logmel_stages.h"
+#include "resample_pass.h"
+#include "span_noise_scan.h"
 
 namespace lyra {
 
 namespace {
 __device__ __forceinline__ i32x4 ld16(const void* p) { return *reinterpret_cast<const i32x4*>(p); }
 __device__ __forceinline__ void st16(void* p, i32x4 v) { *reinterpret_cast<i32x4*>(p) = v; }
-// the row of tab [2][3] = [dir][8000, 32000, 48000] (rates_ensure); -1: 16 kHz, the pass is a copy
-__device__ __forceinline__ int rs_design_index(int rate) { return rate == 8000 ? 0 : rate == 32000 ? 1 : rate == 48000 ? 2 : -1; }
-// the row of the four rates' MelP / NoiseP (8 / 16 / 32 / 48 kHz)
-__device__ __forceinline__ int rate_index4(int rate) { return rate == 8000 ? 0 : rate == 32000 ? 2 : rate == 48000 ? 3 : 1; }
 }  // namespace
 
 // dir 0: in = the external-rate buffer (rows in_stride samples apart, rate / 50 valid samples at the front of each), out = the
@@ -31,7 +30,7 @@ __device__ __forceinline__ int rate_index4(int rate) { return rate == 8000 ? 0 :
 //   frame 0 of a span  history from the span stream's slot -- never from the buffer, the row in front may be another span's,
 //                      at another rate -- and the only wavefront that writes the slot.
 //   the phase          later frames read the slot's phase word, which the frame-0 wavefront may be replacing meanwhile.  Old
-//                      and new value differ by a multiple of n_in, and `first` (resample_fir.inc) depends on in_pos % down
+//                      and new value differ by a multiple of n_in, and `first` (rs_fir, resample_pass.h) depends on in_pos % down
 //                      alone.  Per design: 8000 -> 16000 and 16000 -> 32000 / 48000 interpolate (down = 1, the word is not
 //                      read); 32000 -> 16000: n_in = 640, down = 2; 48000 -> 16000: n_in = 960, down = 3; 16000 -> 8000:
 //                      n_in = 320, down = 2.  In each n_in is a multiple of down, and down divides 6, the modulus the word
@@ -42,14 +41,8 @@ __global__ __launch_bounds__(256) void span_resample_rates_kernel(const Resample
                                                                    uint8_t* __restrict__ state, const int16_t* __restrict__ in,
                                                                    int in_stride, int16_t* __restrict__ out, int out_stride) {
   extern __shared__ __attribute__((aligned(16))) float rsb_all[];   // [4][RS_TAPS - 1 + 960, padded to 4]
-  constexpr int H = st::RS_TAPS - 1;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  int lo = 0, hi = n_rows - 1;   // the last row whose first workgroup is not behind this one
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (rows[mid].wg0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const SpanRsRow row = rows[lo];
+  const SpanRsRow row = rows[span_row_of_workgroup(rows, n_rows, &SpanRsRow::wg0, (int)blockIdx.x)];
   const long long f = ((long long)blockIdx.x - row.wg0) * 4 + w;   // frame of the span
   if (f >= row.n_frames) return;   // (wave-uniform)
   const int rate = row.pad[0];
@@ -60,33 +53,14 @@ __global__ __launch_bounds__(256) void span_resample_rates_kernel(const Resample
     if (lane < 40) st16(dst + lane * 8, ld16(src + lane * 8));
     return;
   }
-  const ResampleP& P = tab[dir * 3 + di];
   const int n_ext = rate / 50;
   const int n_in = dir == 0 ? n_ext : 320, n_out = dir == 0 ? 320 : n_ext;
-  float* rsb = rsb_all + w * ((H + 960 + 3) & ~3);
-  const bool vec = true;   // rows of 160 / 320 / 640 / 960 samples, strides of 320 / 960, in a 16-byte aligned buffer
-#include "resample_load.inc"
-  uint8_t* slot = state + (size_t)row.id * st::RS_BYTES;
-  float* hist = reinterpret_cast<float*>(slot + st::RS_HIST);
-  const int in_pos = f == 0 || P.down > 1
-                         ? __hip_atomic_load(reinterpret_cast<const int*>(slot + st::RS_IN_POS), __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT)
-                         : 0;
-  // (f > 0: src - in_stride is row f - 1 of this span)
-  if (lane < H) rsb[lane] = f == 0 ? hist[lane] : (float)src[lane - in_stride + n_in - H];
-  // the FIR reads what other lanes of this wavefront have just written to its LDS row (as in resample_rates_kernel)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#include "resample_fir.inc"
-  if (f != 0) return;
-  const int16_t* last = in + (size_t)(row.frame0 + row.n_frames - 1) * in_stride + n_in - H;   // (n_in > H)
-  if (lane < H) hist[lane] = (float)last[lane];
-  if (lane == 0)
-    __hip_atomic_store(reinterpret_cast<int*>(slot + st::RS_IN_POS), (in_pos + (int)(row.n_frames % 6) * (n_in % 6)) % 6,
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // rows of 160 / 320 / 640 / 960 samples, strides of 320 / 960, in a 16-byte aligned buffer; f > 0: src - in_stride is row
+  // f - 1 of this span; n_in > RS_H
+  rs_span_pass(tab + dir * 3 + di, rsb_all + w * ((RS_H + 960 + 3) & ~3), lane, state + (size_t)row.id * st::RS_BYTES, f,
+               row.n_frames, src, src - in_stride + n_in - RS_H,
+               in + (size_t)(row.frame0 + row.n_frames - 1) * in_stride + n_in - RS_H, n_in, dst, n_out);
 }
-static_assert(st::RS_TAPS - 1 < 160, "the history lies inside one frame at every rate");
 
 // span_logmel_kernel with the filterbank of the row's rate: P4 = the four rates' MelP (model.h d_mel_rate[0], the table
 // logmel_rates_kernel indexes).  Both frames of a workgroup are one span's, so one filterbank serves the workgroup.
@@ -94,8 +68,8 @@ __global__ __launch_bounds__(256) void span_logmel_rates_kernel(const MelP* __re
                                                                  const SpanRsRow* __restrict__ rate_rows, int n_rows,
                                                                  uint8_t* __restrict__ state, const int16_t* __restrict__ pcm,
                                                                  float* __restrict__ mel) {
-  auto mel_of_row = [&](int i) { return P4 + rate_index4(rate_rows[i].pad[0]); };
-#include "span_logmel_rows.inc"
+  const int r = span_row_of_workgroup(rows, n_rows, &SpanDtxRow::wg0, (int)blockIdx.x);
+  span_logmel_row(P4[mel_rate_index(rate_rows[r].pad[0])], rows[r], (int)blockIdx.x, state, pcm, mel);
 }
 
 // span_noise_scan_kernel with the constants of the row's rate: np_tab = the four rates' NoiseP (rates_ensure's d_noise_tab).
@@ -106,8 +80,7 @@ __global__ __launch_bounds__(64) void span_noise_scan_rates_kernel(const NoiseP*
                                                                     int32_t* __restrict__ flag_out, int v_noise, int v_active,
                                                                     long long* __restrict__ map, int32_t* __restrict__ counts) {
   if ((int)blockIdx.x >= n_rows) return;
-  const NoiseP P = np_tab[rate_index4(rate_rows[blockIdx.x].pad[0])];
-#include "span_noise_scan_rows.inc"
+  span_dtx_scan(np_tab[mel_rate_index(rate_rows[blockIdx.x].pad[0])], rows, state, mel, flag_out, v_noise, v_active, map, counts);
 }
 
 }  // namespace lyra

@@ -11,12 +11,11 @@
 // The index is the caller's and is not trusted (as bridge_kernels.hip): room_start is clamped, every order[] entry is checked
 // against [0, B), and every row number that went through memory (the speaker lists, pos_room) is checked again where it is read.
 #include "kernels.h"
+#include "speakers_rows.h"   // SPK_MAX, SPK_LANES, SpkAcc, spk_add, spk_clamp, spk_minus: shared with shared_bridge_kernels.hip
 
 namespace lyra {
 
 namespace {
-
-#include "speakers_rows.inc"   // SPK_MAX, SPK_LANES, SpkAcc, spk_add, spk_clamp, spk_minus: shared with shared_bridge_kernels.hip
 
 constexpr int SPK_CHUNK = 8;    // positions per wavefront of the mix
 constexpr int SPK_POS = 32767;  // LYRA_HIP_BRIDGE_MAX_ROOM: positions inside a room take 15 bits of a key

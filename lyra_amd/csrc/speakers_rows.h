@@ -1,6 +1,11 @@
-// speakers_rows.inc -- the row arithmetic that speakers_kernels.hip and shared_bridge_kernels.hip share; included inside
-// namespace lyra { namespace {.  A 640-byte row of 320 int16 samples is 40 lanes x 16 bytes; a lane sums its eight samples of
-// up to SPK_MAX rows in int32 and takes at most one row out again before the clamp.
+// speakers_rows.h -- the row arithmetic that speakers_kernels.hip and shared_bridge_kernels.hip share.  A 640-byte row of 320
+// int16 samples is 40 lanes x 16 bytes; a lane sums its eight samples of up to SPK_MAX rows in int32 and takes at most one row
+// out again before the clamp.
+#pragma once
+#include "kernels.h"
+
+namespace lyra {
+
 constexpr int SPK_MAX = 8;      // LYRA_HIP_SPEAKERS_MAX: speakers per room, and the width of a speaker list
 constexpr int SPK_LANES = 40;   // 40 lanes x 16 bytes = one 640-byte row
 
@@ -28,3 +33,5 @@ __device__ __forceinline__ uint4 spk_minus(const SpkAcc& s, const uint4& x, bool
   }
   return make_uint4(o[0], o[1], o[2], o[3]);
 }
+
+}  // namespace lyra

@@ -23,6 +23,30 @@ BUDGET = {
     "dec_s1_kernel": (128, 0),
     "dec_s2_kernel": (120, 0),
     "rvq_encode_kernel": (114, 0),   # 106 + 8 accumulation registers
+    # the side kernels whose bodies are the device functions of resample_pass.h, logmel_stages.h, span_noise_scan.h and
+    # cng_frame.h: the VGPRs each had while those bodies were text included into it
+    "resample_kernel": (99, 0),
+    "resample_rates_kernel": (105, 0),
+    "resample_streams_kernel": (64, 0),
+    "resample_streams_out_kernel": (101, 0),
+    "span_resample_kernel": (97, 0),
+    "span_resample_rates_kernel": (99, 0),
+    "span_resample_packed_kernel": (99, 0),
+    "ds_splice_kernel": (61, 0),
+    "ds_splice_streams_kernel": (69, 0),
+    "logmel_kernel": (62, 0),
+    "logmel_masked_kernel": (62, 0),
+    "logmel_rates_kernel": (68, 0),
+    "logmel_streams_kernel": (68, 0),
+    "span_logmel_kernel": (57, 0),
+    "span_logmel_map_kernel": (57, 0),
+    "span_logmel_rates_kernel": (57, 0),
+    "span_noise_scan_kernel": (101, 0),
+    "span_noise_scan_rates_kernel": (101, 0),
+    "span_lossy_scan_kernel": (105, 0),
+    "cng_kernel": (68, 0),
+    "span_cng_kernel": (96, 0),
+    "lossy_mix_kernel": (21, 0),
 }
 
 
