@@ -4,7 +4,11 @@ the argument checks.  Helpers: tests/bridge_models.py.
 
 Shapes.  lossy_mix and the resampler serve 4 rows per workgroup, the estimators 2, the mix kernel one room per wavefront and 4
 per workgroup with member chunks of 8: B = 37 and B = 5 for the tick (the shapes of test_gpu_decode_streams.py), B = 330 with
-rooms of 1, 2, 3, 8, 9, 16, 17 and 257 (313 rows; the rest in no room) for the kernel."""
+rooms of 1, 2, 3, 8, 9, 16, 17 and 257 (313 rows; the rest in no room) for the kernel.
+
+Stream kind: the contexts here (32 to 512 streams) run on the CU-masked streams the library picks up to 1,024 streams, which
+are blocking streams with respect to the NULL stream; the cases with streams="plain" run on hipStreamNonBlocking streams, the
+kind of a 4,096-stream context (tests/gpu_plumbing.py make_ctx)."""
 import os
 import subprocess
 
@@ -12,7 +16,7 @@ import numpy as np
 import pytest
 
 from bridge_models import SKIP_CN, BridgeModel, bridge_kernel_case, np_bridge_mix, np_bridge_plan
-from gpu_plumbing import _dev, _ids, _t, make_ctx as _ctx
+from gpu_plumbing import _dev, _ids, _t, make_ctx as _ctx, stream_cases
 from receiver_models import _full_batch_mask, _model_packets
 from row_cases import _draw_bits, _same_state
 
@@ -173,9 +177,10 @@ def _compose_case(B, mode="xnnpack", serial=False, flags=0, T=40, **kw):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("B,mode", [(37, "xnnpack"), (5, "xnnpack"), (37, "builtin_mixed")])
-def test_tick_equals_its_composition(B, mode):
-    _compose_case(B, mode)
+@pytest.mark.parametrize("B,mode,streams", stream_cases([(37, "xnnpack"), (5, "xnnpack"), (37, "builtin_mixed")],
+                                                        plain=(37, "xnnpack")))
+def test_tick_equals_its_composition(B, mode, streams):
+    _compose_case(B, mode, streams=streams)
 
 
 @pytest.mark.gpu
@@ -286,12 +291,12 @@ def _host_script(B, T, seed):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("depth", [1, 2])
-def test_begin_end_equal_the_dev_call(depth):
+@pytest.mark.parametrize("depth,streams", stream_cases([1, 2], plain=2))
+def test_begin_end_equal_the_dev_call(depth, streams):
     B, ms, T = 37, 64, 24
     ids = _ids(B, ms, 11)
     script = _host_script(B, T, 21)
-    a, u = _ctx(ms), _ctx(ms)
+    a, u = _ctx(ms, streams=streams), _ctx(ms, streams=streams)
     try:
         bufs = _Bufs(B)
         want = [_tick(u, bufs, ids, s["pk"], s["sz"], s["rooms"], s["muted"], s["bits"], s["dtx"], SKIP_CN) for s in script]

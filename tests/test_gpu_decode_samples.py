@@ -4,21 +4,25 @@ on the C oracle, stream by stream and call by call, compared with test_gpu_lossy
 only the generative model speaks, within 1 LSB where comfort noise reaches (that file's bounds; none of its own) --
 is_noise, is_comfort_noise and the decoder-side noise estimate after every call; and bit for bit against the calls that
 already exist where the regimes coincide (lyra_hip_decode_lossy_mixed_dev for n = one hop, lyra_hip_decode_dev when every
-packet arrives)."""
+packet arrives).
+
+Stream kind: the contexts here (256 streams) run on the CU-masked streams the library picks up to 1,024 streams, which are
+blocking streams with respect to the NULL stream; the case with streams="plain" runs on hipStreamNonBlocking streams, the kind
+of a 4,096-stream context (tests/gpu_plumbing.py make_ctx)."""
 import os
 
 import numpy as np
 import pytest
 
-from gpu_plumbing import make_ctx
+from gpu_plumbing import make_ctx, stream_cases
 from receiver_models import DEPTH, Device, Model, _model_packets as _packets
 from signals import _patterns, _speech
 
 pytestmark = pytest.mark.gpu
 
 
-def _ctx(max_streams=256):
-    return make_ctx(max_streams)
+def _ctx(max_streams=256, streams=None):
+    return make_ctx(max_streams, streams=streams)
 
 
 def _ten_ms_calls(mask, phase):
@@ -58,8 +62,8 @@ def test_ten_ms_receiver_vs_reference_model(golden_dir, oracle_default, rate):
     assert model.saw_cn and model.saw_mix and model.saw_back
 
 
-@pytest.mark.parametrize("rate", [16000, 48000])
-def test_one_hop_requests_equal_lossy_mixed_bit_for_bit(golden_dir, oracle_default, rate):
+@pytest.mark.parametrize("rate,streams", stream_cases([16000, 48000], plain=48000))
+def test_one_hop_requests_equal_lossy_mixed_bit_for_bit(golden_dir, oracle_default, rate, streams):
     """n = one hop, at most one packet per call: the same kernels in the same order as lyra_hip_decode_lossy_mixed_dev on
     a second context with the same seed -- samples (comfort noise included), is_noise, is_comfort_noise, estimates."""
     import torch
@@ -68,7 +72,7 @@ def test_one_hop_requests_equal_lossy_mixed_bit_for_bit(golden_dir, oracle_defau
     ids = [5, 17, 2, 40, 9, 33, 21, 0, 63, 12, 48, 7]
     rows, size = _packets(oracle_default, golden_dir, bits, T, offset=777)
     mask = np.repeat(_patterns(T), 3, axis=1)
-    a, b = _ctx(), _ctx()
+    a, b = _ctx(streams=streams), _ctx(streams=streams)
     try:
         devc = Device(a, ids, rate)
         dev = torch.device("cuda", 0)

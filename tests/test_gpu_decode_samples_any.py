@@ -3,13 +3,17 @@ BufferedResampler's leftover included.  Expectations: oracle/lyra_codec_model.py
 stream and call by call, with receiver_models' Tally / CnReach -- exact where only the generative model speaks, within 1 LSB
 where comfort noise reaches (that module's bounds; none of its own) --, both flags and the decoder-side estimate; and bit for
 bit against lyra_hip_decode_samples_dev where the old size rule holds, against the same samples asked for in pieces, and
-against the same streams in other batch shapes or moved to another context."""
+against the same streams in other batch shapes or moved to another context.
+
+Stream kind: the contexts here (64 to 512 streams) run on the CU-masked streams the library picks up to 1,024 streams, which
+are blocking streams with respect to the NULL stream; the case with streams="plain" runs on hipStreamNonBlocking streams, the
+kind of a 4,096-stream context (tests/gpu_plumbing.py make_ctx)."""
 import ctypes
 
 import numpy as np
 import pytest
 
-from gpu_plumbing import make_ctx
+from gpu_plumbing import make_ctx, stream_cases
 from receiver_models import ROW, Device, _model_packets as _packets
 from receiver_models_any import DeviceAny, ModelAny
 
@@ -137,13 +141,13 @@ def test_old_rule_sizes_are_the_old_call(golden_dir, oracle_default):
         a.close(); b.close()
 
 
-@pytest.mark.parametrize("rate", [16000, 48000])
-def test_whole_equals_pieces(golden_dir, oracle_default, rate):
+@pytest.mark.parametrize("rate,streams", stream_cases([16000, 48000], plain=48000))
+def test_whole_equals_pieces(golden_dir, oracle_default, rate, streams):
     """4 packets queued by n = 0 calls, then one request of 4 hops against four requests of one hop on a second context; then
     the same without packets (concealment, the fade to comfort noise) and with one late packet: PCM and state byte for byte."""
     ids, hop = [9, 2], rate // 50
     rows, size = _packets(oracle_default, golden_dir, [184, 64], 9, offset=40)
-    a, b = make_ctx(64), make_ctx(64)
+    a, b = make_ctx(64, streams=streams), make_ctx(64, streams=streams)
     try:
         da, db = DeviceAny(a, ids, rate), DeviceAny(b, ids, rate)
         none = np.zeros(2, np.int32)

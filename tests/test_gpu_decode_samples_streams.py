@@ -1,7 +1,11 @@
 """lyra_hip_decode_samples_streams_dev: DecodeSamples(n) on the device with a sample rate and a request size per stream in one
 call.  Expectations: the reference model (RefLyraDecoder through receiver_models' Tally / CnReach, that module's bounds and none
 of its own) and, bit for bit, lyra_hip_decode_samples_any_dev called once per (rate, size) class on a twin context: samples,
-flags and the exported stream state."""
+flags and the exported stream state.
+
+Stream kind: the contexts here (64 to 512 streams) run on the CU-masked streams the library picks up to 1,024 streams, which
+are blocking streams with respect to the NULL stream; the test named "on_plain_streams" runs on hipStreamNonBlocking streams,
+the kind of a 4,096-stream context (tests/gpu_plumbing.py make_ctx)."""
 import ctypes
 import os
 import subprocess
@@ -92,7 +96,16 @@ def test_against_the_reference_model(session, oracle_default):
 def test_bit_for_bit_against_the_uniform_call(session):
     """The session on a second context as one decode_samples_any_dev call per (rate, size) class; half-way rows 1 and 5 are
     served by the uniform call on the FIRST context too, for five calls, and come back."""
-    a, b = make_ctx(128), make_ctx(128)
+    _uniform_call_case(session, None)
+
+
+def test_bit_for_bit_against_the_uniform_call_on_plain_streams(session):
+    """The same on hipStreamNonBlocking streams, the kind a 4,096-stream context runs on (gpu_plumbing.make_ctx)."""
+    _uniform_call_case(session, "plain")
+
+
+def _uniform_call_case(session, streams):
+    a, b = make_ctx(128, streams=streams), make_ctx(128, streams=streams)
     sw = np.array([1, 5])
     keep = np.setdiff1d(np.arange(8), sw)
     half = len(session) // 2

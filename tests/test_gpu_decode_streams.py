@@ -8,7 +8,11 @@ stream, under the criteria of tests/receiver_models.py (Tally, CnReach).
 Shapes.  The resampler and the mix serve 4 rows per workgroup, the estimator 2: B = 37 (10 workgroups, the last with one row)
 and B = 5.  Packets are random bytes with sizes from a bursty loss pattern (signals._random_packets); rows 0..11 -- three
 rows of every rate -- lose hops 2..13 and receive 23-byte packets on hops 14..23, the pattern of
-test_gpu_mixed_rate._decode_case, which takes every rate group into comfort noise and back: asserted on `u`'s flags."""
+test_gpu_mixed_rate._decode_case, which takes every rate group into comfort noise and back: asserted on `u`'s flags.
+
+Stream kind: the contexts here (64 streams) run on the CU-masked streams the library picks up to 1,024 streams, which are
+blocking streams with respect to the NULL stream; the case with streams="plain" runs on hipStreamNonBlocking streams, the kind
+of a 4,096-stream context (tests/gpu_plumbing.py make_ctx)."""
 import ctypes
 import os
 import subprocess
@@ -17,7 +21,7 @@ import sys
 import numpy as np
 import pytest
 
-from gpu_plumbing import _dev, _ids, _t, make_ctx as _ctx
+from gpu_plumbing import _dev, _ids, _t, make_ctx as _ctx, stream_cases
 from receiver_models import CnReach, Tally
 from row_cases import ROW, _decode_rates, _rates, _same_state
 from signals import RATES, _gilbert, _random_packets as _packets, _speech
@@ -87,13 +91,13 @@ def _cn_and_back(cn, rates):
 
 # ---- 1. the padded layout equals the rates call ---------------------------------------------------------------------------
 
-def _padded_case(B, serial):
+def _padded_case(B, serial, streams=None):
     T, ms = 40, 64
     ids = _ids(B, ms, B + 9)
     rates = _rates(B)
     pk, sz = _case_packets(T, B, B)
     pad = np.arange(B, dtype=np.int32) * ROW
-    a, u = _ctx(ms), _ctx(ms)
+    a, u = _ctx(ms, streams=streams), _ctx(ms, streams=streams)
     try:
         if serial:
             a.set_serial(True)
@@ -112,9 +116,9 @@ def _padded_case(B, serial):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("B,serial", [(37, False), (37, True), (5, False)])
-def test_padded_layout_equals_the_rates_call(B, serial):
-    _padded_case(B, serial)
+@pytest.mark.parametrize("B,serial,streams", stream_cases([(37, False), (37, True), (5, False)], plain=(37, False)))
+def test_padded_layout_equals_the_rates_call(B, serial, streams):
+    _padded_case(B, serial, streams)
 
 
 _CHILD = """

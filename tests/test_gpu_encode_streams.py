@@ -10,14 +10,18 @@ with 5 rows) and B = 5.  Rows 0..7 of the B = 37 layout pin the pairs (on, off),
 estimator workgroups 0..3 on every hop; every other flag is redrawn every hop.  T = 40 hops with every third stream silent
 from hop 5 on, as the DTX case of tests/test_gpu_mixed_rate.py: on the CPU, oracle NoiseEstimators at the rows' rates fed
 exactly the flagged hops of this audio and these flags decide "noise" and "not noise" at every rate (counts in
-_COND_CPU below), so the flagged rows give empty and non-empty packets at every rate."""
+_COND_CPU below), so the flagged rows give empty and non-empty packets at every rate.
+
+Stream kind: the contexts here (64 streams) run on the CU-masked streams the library picks up to 1,024 streams, which are
+blocking streams with respect to the NULL stream; the case with streams="plain" runs on hipStreamNonBlocking streams, the kind
+of a 4,096-stream context (tests/gpu_plumbing.py make_ctx)."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from gpu_plumbing import _dev, _ids, _t, make_ctx
+from gpu_plumbing import _dev, _ids, _t, make_ctx, stream_cases
 from row_cases import ROW, SENTINEL, _check_sentinel_rows as _check_rows, _same_state
 from signals import RATES, _pcm_rows, _speech
 
@@ -95,7 +99,7 @@ def _uniform(u, ids, pcm_t, rates, bits, flags):
 
 # ---- 1. per-row DTX equals the uniform calls -----------------------------------------------------------------------------
 
-def _per_row_case(golden_dir, B, sub_batches, serial):
+def _per_row_case(golden_dir, B, sub_batches, serial, streams=None):
     ms = 64
     ids = _ids(B, ms, B + 11)
     rates, bits, fixed = _row_layout(B)
@@ -103,7 +107,7 @@ def _per_row_case(golden_dir, B, sub_batches, serial):
     pcm_a = _pcm_rows(golden_dir, B, T_HOPS, rates, 3, B, 0x1111)
     pcm_u = _pcm_rows(golden_dir, B, T_HOPS, rates, 3, B, 0x2222)   # (a read past the row would differ)
     absent = int((~np.isin(rates, RATES)).sum())
-    a, u = _ctx(ms, sub_batches=sub_batches), _ctx(ms)
+    a, u = _ctx(ms, sub_batches=sub_batches, streams=streams), _ctx(ms, streams=streams)
     try:
         if serial:
             a.set_serial(True)
@@ -131,9 +135,10 @@ def _per_row_case(golden_dir, B, sub_batches, serial):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("B,sub_batches,serial", [(37, None, False), (37, 2, False), (37, None, True), (5, None, False)])
-def test_per_row_dtx_equals_the_uniform_calls(golden_dir, B, sub_batches, serial):
-    _per_row_case(golden_dir, B, sub_batches, serial)
+@pytest.mark.parametrize("B,sub_batches,serial,streams", stream_cases([(37, None, False), (37, 2, False), (37, None, True),
+                                                                       (5, None, False)], plain=(37, None, False)))
+def test_per_row_dtx_equals_the_uniform_calls(golden_dir, B, sub_batches, serial, streams):
+    _per_row_case(golden_dir, B, sub_batches, serial, streams)
 
 
 # ---- 2. fixed flags -------------------------------------------------------------------------------------------------------

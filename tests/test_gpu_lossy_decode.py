@@ -4,7 +4,11 @@ reference model oracle/lyra_codec_model.py (RefLyraDecoder, DecodeSamples(rate /
 ticks with a packet) sample for sample -- exact where only the generative model speaks, within 1 LSB where comfort noise
 goes in (Tally, LossyModel; also used by the BatchLyraDecoder tests), is_noise and the decoder-side estimate included --
 up to full batches; BatchLyraDecoder through lyra_amd/decoder_demo (bit for bit), the existing device path when every
-packet arrives (bit for bit), and run_steps against the single calls (bit for bit)."""
+packet arrives (bit for bit), and run_steps against the single calls (bit for bit).
+
+Stream kind: the contexts here (64 to 512 streams) run on the CU-masked streams the library picks up to 1,024 streams, which
+are blocking streams with respect to the NULL stream; the case with streams="plain" runs on hipStreamNonBlocking streams, the
+kind of a 4,096-stream context (tests/gpu_plumbing.py make_ctx)."""
 import os
 import subprocess
 import sys
@@ -12,15 +16,15 @@ import sys
 import numpy as np
 import pytest
 
-from gpu_plumbing import make_ctx
+from gpu_plumbing import make_ctx, stream_cases
 from receiver_models import BYTES, CnReach, LossyModel, _full_batch_mask, _lossy_check, _lossy_run, cn_flags
 from signals import _patterns, _speech
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
-def _ctx(max_streams=256):
-    return make_ctx(max_streams)
+def _ctx(max_streams=256, streams=None):
+    return make_ctx(max_streams, streams=streams)
 
 
 @pytest.mark.parametrize("rate", [8000, 32000, 48000])
@@ -72,7 +76,7 @@ def test_lossy_sessions_vs_reference_model(golden_dir, oracle_default, rate, bit
     assert model.saw_cn and model.saw_mix and model.saw_back
 
 
-def _lossy_full_batch(golden_dir, oracle, rate, bits, B, T, mask, max_streams, seed):
+def _lossy_full_batch(golden_dir, oracle, rate, bits, B, T, mask, max_streams, seed, streams=None):
     from oracle import lyra_codec_model as M
     rng = np.random.default_rng(seed)
     ids = rng.choice(max_streams - 1, B - 1, replace=False).tolist() + [max_streams - 1]
@@ -81,7 +85,7 @@ def _lossy_full_batch(golden_dir, oracle, rate, bits, B, T, mask, max_streams, s
     encs = [M.RefLyraEncoder(oracle, 16000, bits, False) for _ in range(B)]
     packets = np.stack([np.stack([encs[s].Encode(pcm[t, s]) for s in range(B)]) for t in range(T)])
     model = LossyModel(oracle, rate, ids)
-    ctx = _ctx(max_streams)
+    ctx = _ctx(max_streams, streams)
     try:
         _lossy_check(ctx, model, ids, packets, mask, bits)
         assert ctx.decode_lossy_errors() == 0
@@ -93,8 +97,9 @@ def _lossy_full_batch(golden_dir, oracle, rate, bits, B, T, mask, max_streams, s
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("rate,bits,B", [(16000, 120, 263), (8000, 64, 37), (32000, 184, 37), (48000, 120, 37)])
-def test_lossy_full_batch_vs_reference_model(golden_dir, oracle_default, rate, bits, B):
+@pytest.mark.parametrize("rate,bits,B,streams", stream_cases([(16000, 120, 263), (8000, 64, 37), (32000, 184, 37), (48000, 120, 37)],
+                                                             plain=(48000, 120, 37)))
+def test_lossy_full_batch_vs_reference_model(golden_dir, oracle_default, rate, bits, B, streams):
     """Past one workgroup of every kernel of the tick, with scattered ids up to max_streams - 1 and distinct speech per
     stream: lossy_plan_kernel's blocks of 256 rows and their feature zeroing, logmel_masked_kernel's pairs in all four
     received / lost combinations at every tick, lossy_mix_kernel's and resample_kernel's tiles of 4 rows (one all lost),
@@ -105,7 +110,7 @@ def test_lossy_full_batch_vs_reference_model(golden_dir, oracle_default, rate, b
         pairs = {(int(mask[t, 2 * k]), int(mask[t, 2 * k + 1])) for k in range(B // 2)}
         assert pairs == {(0, 0), (0, 1), (1, 0), (1, 1)}, t
     assert any((mask[t, 4 * j:4 * j + 4] == 0).all() for t in range(T) for j in range(B // 4))
-    model = _lossy_full_batch(golden_dir, oracle_default, rate, bits, B, T, mask, 512, rate + B)
+    model = _lossy_full_batch(golden_dir, oracle_default, rate, bits, B, T, mask, 512, rate + B, streams)
     assert model.saw_back >= 2 and model.saw_mix and model.saw_cn
 
 

@@ -5,7 +5,11 @@ the `_dev` call with its refusals, bridge_demo --shared-encoders, and the argume
 
 Shapes.  The slot kernel serves one room per wavefront and the mix kernel one encoder row, four per workgroup, the fan-out 256
 bytes per workgroup: the kernel cases of the loudest-N test (B = 330, rooms of 1 .. 257, and rooms of 63 / 64 / 65 / 129) give
-8 and 4 rooms, E = 16 .. 72 encoder rows; B = 37 and B = 5 for the tick."""
+8 and 4 rooms, E = 16 .. 72 encoder rows; B = 37 and B = 5 for the tick.
+
+Stream kind: the contexts here (64 to 512 streams) run on the CU-masked streams the library picks up to 1,024 streams, which
+are blocking streams with respect to the NULL stream; the cases with streams="plain" run on hipStreamNonBlocking streams, the
+kind of a 4,096-stream context (tests/gpu_plumbing.py make_ctx)."""
 import os
 import subprocess
 
@@ -13,7 +17,7 @@ import numpy as np
 import pytest
 
 from bridge_models import np_bridge_plan
-from gpu_plumbing import _dev, _ids, _t, make_ctx as _ctx
+from gpu_plumbing import _dev, _ids, _t, make_ctx as _ctx, stream_cases
 from receiver_models import _full_batch_mask
 from row_cases import _draw_bits, _same_state
 from shared_bridge_models import EVENTS, SLOTS, np_fanout, np_shared_mix, run_slot_script, slot_script
@@ -307,9 +311,10 @@ def _compose_case(B, mode="xnnpack", serial=False, flags=0, T=40, N=2, **kw):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("B,mode", [(37, "xnnpack"), (5, "xnnpack"), (37, "builtin_mixed")])
-def test_tick_equals_its_composition(B, mode):
-    _compose_case(B, mode)
+@pytest.mark.parametrize("B,mode,streams", stream_cases([(37, "xnnpack"), (5, "xnnpack"), (37, "builtin_mixed")],
+                                                        plain=(37, "xnnpack")))
+def test_tick_equals_its_composition(B, mode, streams):
+    _compose_case(B, mode, streams=streams)
 
 
 @pytest.mark.gpu
@@ -446,12 +451,12 @@ def _same_tick(got, w, t):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("depth", [1, 2])
-def test_begin_end_equal_the_dev_call(depth):
+@pytest.mark.parametrize("depth,streams", stream_cases([1, 2], plain=2))
+def test_begin_end_equal_the_dev_call(depth, streams):
     B, ms, T, N = 37, 64, 16, 3
     ids = _ids(B, ms, 11)
     script = _host_ticks(B, T, 21, N)
-    a, u = _ctx(ms), _ctx(ms)
+    a, u = _ctx(ms, streams=streams), _ctx(ms, streams=streams)
     try:
         want = _want_ticks(u, ids, script, N, SKIP_CN, ms)
         got = []

@@ -2,7 +2,11 @@
 chunks that run side by side behind a discarded warm-up.  Every comparison is BIT FOR BIT against the hop-by-hop calls
 lyra_hip_encode / lyra_hip_decode on a twin context fed the same streams: packets, PCM, the span streams' exported state,
 and the lanes' state against a freshly reset stream's.  One case holds the packets against the CPU oracle directly, one the
-whole-file functions against EncodeFiles / DecodeFiles."""
+whole-file functions against EncodeFiles / DecodeFiles.
+
+Stream kind: the contexts here (96 streams) run on the CU-masked streams the library picks up to 1,024 streams, which are
+blocking streams with respect to the NULL stream; the case with streams="plain" runs on hipStreamNonBlocking streams, the kind
+of a 4,096-stream context (tests/gpu_plumbing.py make_ctx)."""
 import os
 import subprocess
 import wave
@@ -10,7 +14,7 @@ import wave
 import numpy as np
 import pytest
 
-from gpu_plumbing import make_ctx
+from gpu_plumbing import make_ctx, stream_cases
 from signals import _audio_spans as _audio
 import span_cases
 from span_cases import _check_state, _sequential
@@ -20,8 +24,8 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 MAX_STREAMS = 96
 
 
-def _ctx(mode="xnnpack", max_streams=MAX_STREAMS):
-    return make_ctx(max_streams, mode)
+def _ctx(mode="xnnpack", max_streams=MAX_STREAMS, streams=None):
+    return make_ctx(max_streams, mode, streams=streams)
 
 
 def _layout(rows_by_id, gap=3):
@@ -71,10 +75,10 @@ def test_spans_equal_hop_by_hop_calls(golden_dir, mode, num_bits):
     _round_trip(f"{mode}/{num_bits}", ctx, twin, pcm, num_bits, lanes)
 
 
-@pytest.mark.parametrize("n_lanes", [0, 1, 37])
-def test_lane_counts(golden_dir, n_lanes):
+@pytest.mark.parametrize("n_lanes,streams", stream_cases([0, 1, 37], plain=37))
+def test_lane_counts(golden_dir, n_lanes, streams):
     """n_lanes = 0 runs the spans sequentially on their own ids; 1 and many cut them.  The lanes come in DIRTY."""
-    ctx, twin = _ctx(), _ctx()
+    ctx, twin = _ctx(streams=streams), _ctx(streams=streams)
     pcm = {4: _audio(golden_dir, 700, 1), 9: _audio(golden_dir, 410, 2)}
     lanes = np.arange(40, 40 + n_lanes, dtype=np.int32)
     if n_lanes:   # whatever a lane held is lost: run some hops on them first, on both sides

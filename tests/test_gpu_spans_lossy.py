@@ -7,7 +7,11 @@ whole blob: decoder stages, estimator, comfort-noise and resampler slots) and th
 The loss traces are built here, and what they have to exercise is asserted before anything is compared (_assert_trace): on
 the plan -- a burst that starts inside a lane chunk's warm-up, one that straddles a chunk boundary -- and on the TWIN's
 output -- two comfort-noise stretches of the 350-frame span read different estimates, the comfort-noise hops are not silent,
-a received tick cross-fades back from comfort noise."""
+a received tick cross-fades back from comfort noise.
+
+Stream kind: the contexts here (96 streams) run on the CU-masked streams the library picks up to 1,024 streams, which are
+blocking streams with respect to the NULL stream; the case with streams="plain" runs on hipStreamNonBlocking streams, the kind
+of a 4,096-stream context (tests/gpu_plumbing.py make_ctx)."""
 import os
 import subprocess
 import wave
@@ -15,7 +19,7 @@ import wave
 import numpy as np
 import pytest
 
-from gpu_plumbing import FILL, _filled, make_ctx
+from gpu_plumbing import FILL, _filled, make_ctx, stream_cases
 from signals import _bursts, _long_trace, _speech_hops as _speech, _stretches
 from span_cases import (CNG, GEN, _check_rows, _check_state, _dirty_lane, _layout, _packets,
                         _twin_decode_lossy as _twin_decode)
@@ -26,8 +30,8 @@ MAX_STREAMS = 96
 SEED = 0x5EEDC0DE
 
 
-def _ctx(mode="xnnpack", rate=16000):
-    return make_ctx(MAX_STREAMS, mode, rate, SEED)
+def _ctx(mode="xnnpack", rate=16000, streams=None):
+    return make_ctx(MAX_STREAMS, mode, rate, SEED, streams=streams)
 
 
 def _assert_trace(where, plan, k_long, rx_long, est_after, want_16, want_cn, need_plan_bursts):
@@ -121,11 +125,11 @@ def test_one_call_of_mixed_span_lengths_equals_hop_by_hop_lossy(golden_dir, rate
     _check_state(where, ctx, twin, list(lengths), lanes)
 
 
-@pytest.mark.parametrize("n_lanes", [40, 0])
-def test_span_continues_a_live_lossy_stream_mid_burst_and_is_continued(golden_dir, n_lanes):
+@pytest.mark.parametrize("n_lanes,streams", stream_cases([40, 0], plain=40))
+def test_span_continues_a_live_lossy_stream_mid_burst_and_is_continued(golden_dir, n_lanes, streams):
     """5 lost ticks hop by hop, a span of 200 that begins inside that burst and ends inside another, 10 more ticks hop by hop
     (two lost, then packets): all three pieces equal the twin that went hop by hop throughout.  n_lanes = 0: sequential."""
-    ctx, twin, enc = _ctx(), _ctx(), _ctx()
+    ctx, twin, enc = _ctx(streams=streams), _ctx(streams=streams), _ctx()
     sid, k, n, tail, bits, rate = 13, 5, 200, 10, 120, 32000
     lanes = np.arange(30, 30 + n_lanes, dtype=np.int32)
     pk = _packets(enc, golden_dir, k + n + tail, bits, 55)

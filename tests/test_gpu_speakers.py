@@ -4,7 +4,11 @@ host form against the `_dev` call, bridge_demo --max-speakers, and the argument 
 
 Shapes.  The level kernel serves 4 rows per workgroup, the select kernel one room per wavefront (keys in registers up to 64
 members, in memory above), the mix kernel 8 positions per wavefront and 32 per workgroup: B = 330 with rooms of 1, 2, 3, 8, 9,
-16, 17 and 257, and again with rooms of 63, 64, 65 and 129, for the kernels; B = 37 and B = 5 for the tick."""
+16, 17 and 257, and again with rooms of 63, 64, 65 and 129, for the kernels; B = 37 and B = 5 for the tick.
+
+Stream kind: the contexts here (up to 512 streams) run on the CU-masked streams the library picks up to 1,024 streams, which
+are blocking streams with respect to the NULL stream; the cases with streams="plain" run on hipStreamNonBlocking streams, the
+kind of a 4,096-stream context (tests/gpu_plumbing.py make_ctx)."""
 import os
 import subprocess
 
@@ -12,7 +16,7 @@ import numpy as np
 import pytest
 
 from bridge_models import np_bridge_mix, np_bridge_plan
-from gpu_plumbing import _dev, _ids, _t, make_ctx as _ctx
+from gpu_plumbing import _dev, _ids, _t, make_ctx as _ctx, stream_cases
 from receiver_models import _full_batch_mask
 from row_cases import _draw_bits, _same_state
 from speaker_models import SKIP_CN, np_levels, np_speakers_mix, speakers_kernel_case, threshold_case
@@ -222,9 +226,10 @@ def _compose_case(B, mode="xnnpack", serial=False, flags=0, T=40, N=2, **kw):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("B,mode", [(37, "xnnpack"), (5, "xnnpack"), (37, "builtin_mixed")])
-def test_tick_equals_its_composition(B, mode):
-    _compose_case(B, mode)
+@pytest.mark.parametrize("B,mode,streams", stream_cases([(37, "xnnpack"), (5, "xnnpack"), (37, "builtin_mixed")],
+                                                        plain=(37, "xnnpack")))
+def test_tick_equals_its_composition(B, mode, streams):
+    _compose_case(B, mode, streams=streams)
 
 
 @pytest.mark.gpu
@@ -295,12 +300,12 @@ def _begin(c, s, N, ids, flags=0):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("depth", [1, 2])
-def test_begin_end_equal_the_dev_call(depth):
+@pytest.mark.parametrize("depth,streams", stream_cases([1, 2], plain=2))
+def test_begin_end_equal_the_dev_call(depth, streams):
     B, ms, T, N = 37, 64, 16, 3
     ids = _ids(B, ms, 11)
     script = _host_script(B, T, 21)
-    a, u = _ctx(ms), _ctx(ms)
+    a, u = _ctx(ms, streams=streams), _ctx(ms, streams=streams)
     try:
         bufs = _Bufs(B)
         want = [_tick(u, bufs, ids, s["pk"], s["sz"], s["rooms"], s["muted"], s["bits"], s["dtx"], SKIP_CN, N) for s in script]

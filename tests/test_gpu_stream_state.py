@@ -3,14 +3,18 @@ context with another max_streams and another comfort-noise seed, and continued t
 had it stayed -- every comparison between two device runs is bit for bit, no row left out.  The moved decoder is also held
 against the reference model (RefLyraDecoder with cng_seed = seed of the FIRST context ^ id in the first context) with
 test_gpu_lossy_decode.py's Tally / CnReach bounds.  Refusal uses only blobs that tests/test_stream_state_cpu.py shows
-validate() rejects."""
+validate() rejects.
+
+Stream kind: the contexts of up to 1,024 streams here run on the CU-masked streams the library picks for them, which are
+blocking streams with respect to the NULL stream (the 4,096-stream case: hipStreamNonBlocking streams); the case with
+streams="plain" runs its small contexts on hipStreamNonBlocking streams too (tests/gpu_plumbing.py make_ctx)."""
 import os
 
 import numpy as np
 import pytest
 
 import gpu_plumbing
-from gpu_plumbing import make_ctx
+from gpu_plumbing import make_ctx, stream_cases
 from receiver_models import Device, Model, _model_packets as _packets
 from signals import _gilbert, _speech
 
@@ -20,8 +24,8 @@ SEED_A, SEED_B = 0x1234ABCD5EED, 0x0BADC0DE77
 R_E1, R_NOISE_D, R_RS_D, R_CNG = 1, 8, 10, 11
 
 
-def _ctx(max_streams, seed=None, mode="xnnpack"):
-    return make_ctx(max_streams, mode, RATE, seed)
+def _ctx(max_streams, seed=None, mode="xnnpack", streams=None):
+    return make_ctx(max_streams, mode, RATE, seed, streams=streams)
 
 
 SeededModel = Model   # (oracle, rate, ids, seed): with the comfort-noise seed of a context that is not the default one
@@ -93,8 +97,8 @@ def _loss_script(T1, T2, n, size):
     return calls, hop_of
 
 
-@pytest.mark.parametrize("mode", ["xnnpack", "builtin_mixed"])
-def test_continuation_in_another_context_under_other_ids(golden_dir, oracle_default, oracle_mixed, mode):
+@pytest.mark.parametrize("mode,streams", stream_cases(["xnnpack", "builtin_mixed"], plain="xnnpack"))
+def test_continuation_in_another_context_under_other_ids(golden_dir, oracle_default, oracle_mixed, mode, streams):
     import torch
     oracle = oracle_default if mode == "xnnpack" else oracle_mixed
     T1, T2, n = 30, 104, 8
@@ -104,7 +108,7 @@ def test_continuation_in_another_context_under_other_ids(golden_dir, oracle_defa
     calls, hop_of = _loss_script(T1, T2, n, size)
     pcm = _enc_input(golden_dir, n, T1 + T2)
     model = SeededModel(oracle, RATE, ids_a, SEED_A)
-    a, b = _ctx(64, SEED_A, mode), _ctx(96, SEED_B, mode)
+    a, b = _ctx(64, SEED_A, mode, streams), _ctx(96, SEED_B, mode, streams)
     try:
         ra, rb = Rig(a, ids_a), Rig(b, ids_b)
 
