@@ -470,12 +470,77 @@ def _load_shared(L, path):
     return L
 
 
+class BridgeSpansCall(C.Structure):
+    """lyra_hip_spans_bridge_call (include/lyra_hip_bridge_spans.h)"""
+    _fields_ = [("spans", C.c_void_p), ("P", C.c_int), ("lane_ids", C.c_void_p), ("n_lanes", C.c_int), ("rooms", C.c_void_p),
+                ("d_packets", C.c_void_p), ("packet_bytes", C.c_void_p), ("d_muted", C.c_void_p), ("flags", C.c_uint),
+                ("num_bits", C.c_void_p), ("dtx", C.c_void_p), ("d_out_packets", C.c_void_p),
+                ("d_out_packet_bytes", C.c_void_p), ("d_pcm16", C.c_void_p), ("d_mix", C.c_void_p),
+                ("d_is_noise", C.c_void_p), ("d_is_comfort_noise", C.c_void_p), ("max_speakers", C.c_int),
+                ("d_levels", C.c_void_p), ("d_is_speaker", C.c_void_p)]
+
+
+def _signatures_bridge_spans():
+    """The same for include/lyra_hip_bridge_spans.h (tests/test_bridge_spans_cpu.py holds each entry to its prototype)."""
+    vp, ci, cu = C.c_void_p, C.c_int, C.c_uint
+    table = {
+        "spans_bridge_plan": [vp, ci, vp, vp, vp, vp, vp, vp],
+        "spans_bridge_mix_dev": [vp, vp, ci, vp, vp, vp, vp, ci, vp, vp, vp],
+        "spans_bridge_dev": [vp, vp],
+        "spans_bridge": [vp, vp, ci, vp, ci, vp, vp, vp, vp, cu, vp, vp, ci] + [vp] * 8,
+    }
+    return {"lyra_hip_" + name: (ci, args) for name, args in table.items()}
+
+
+_SIGNATURES_BRIDGE_SPANS = _signatures_bridge_spans()
+
+
+def _load_bridge_spans(L, path):
+    """_SIGNATURES_BRIDGE_SPANS applied to a loaded library; one that lacks a function of it is refused."""
+    for name, (restype, argtypes) in _SIGNATURES_BRIDGE_SPANS.items():
+        fn = getattr(L, name, None)
+        if fn is None:
+            raise LyraHipError(f"{path} does not export {name}")
+        fn.restype, fn.argtypes = restype, argtypes
+    return L
+
+
+def _bridge_spans_args(spans, rooms):
+    """participants of a recording and their room labels -> (SPAN_DTYPE array [P], int32 [P]); LyraHipError where the shapes
+    do not fit, before the library is called"""
+    sp = _spans(spans)
+    labels = np.ascontiguousarray(np.asarray(rooms, np.int32).reshape(-1))
+    if sp.size < 1:
+        raise LyraHipError("bridge_spans: no participants")
+    if labels.size != sp.size:
+        raise LyraHipError(f"bridge_spans: rooms has {labels.size} entries for {sp.size} participants")
+    if np.any(sp["n_frames"] != sp["n_frames"][0]):
+        raise LyraHipError("bridge_spans: every participant's span needs the same n_frames")
+    return sp, labels
+
+
+def bridge_spans_plan(spans, rooms, lib=None):
+    """The data model of a recording through the bridge, checked (lyra_hip_spans_bridge_plan; no GPU): spans are (stream_id,
+    first_frame, n_frames) per participant with one n_frames = T for all, rooms int32 [P] labels (< 0: in no room) ->
+    (order int32 [n_members] participant numbers, room_start int32 [n_rooms + 1], T).  LyraHipError for unequal n_frames,
+    overlapping or negative ranges, an id named twice, or a room of more than BRIDGE_MAX_ROOM members."""
+    L = lib or _load()
+    sp, labels = _bridge_spans_args(spans, rooms)
+    order = np.zeros(sp.size, np.int32)
+    start = np.zeros(sp.size + 1, np.int32)
+    n_rooms, n_members, n_ticks = C.c_int(0), C.c_int(0), C.c_int64(0)
+    if L.lyra_hip_spans_bridge_plan(sp.ctypes.data, sp.size, labels.ctypes.data, order.ctypes.data, start.ctypes.data,
+                                    C.addressof(n_rooms), C.addressof(n_members), C.addressof(n_ticks)) != 0:
+        raise LyraHipError("lyra_hip_spans_bridge_plan: invalid spans or rooms")
+    return order[:n_members.value].copy(), start[:n_rooms.value + 1].copy(), n_ticks.value
+
+
 def _load(path=None):
     """The C-ABI library (default: library_path()); a second path loads a build variant beside it (lyra_amd/variants/).
     A library that lacks a function of _SIGNATURES, _SIGNATURES_SPANS_MIXED, _SIGNATURES_SPANS_RATES, _SIGNATURES_SPANS_PACKED,
     _SIGNATURES_ENCODE_STREAMS, _SIGNATURES_DECODE_STREAMS, _SIGNATURES_DECODE_SAMPLES_ANY or
     _SIGNATURES_DECODE_SAMPLES_STREAMS is refused, and so is one that lacks a function of _SIGNATURES_BRIDGE (_load_bridge) or _SIGNATURES_SPEAKERS
-    (_load_speakers) or _SIGNATURES_SHARED (_load_shared)."""
+    (_load_speakers) or _SIGNATURES_SHARED (_load_shared) or _SIGNATURES_BRIDGE_SPANS (_load_bridge_spans)."""
     path = os.path.abspath(path or library_path())
     if path in _libs:
         return _libs[path]
@@ -503,7 +568,7 @@ def _load(path=None):
         if fn is None:
             raise LyraHipError(f"{path} does not export {name}")
         fn.restype, fn.argtypes = restype, argtypes
-    _libs[path] = _load_shared(_load_speakers(_load_bridge(L, path), path), path)
+    _libs[path] = _load_bridge_spans(_load_shared(_load_speakers(_load_bridge(L, path), path), path), path)
     return L
 
 
@@ -1845,6 +1910,82 @@ class LyraHip:
         self._chk(self.L.lyra_hip_decode_spans_packed(self.h, *a, packets.ctypes.data, num_bits, rates.ctypes.data,
                                                       pcm16.ctypes.data, ext.ctypes.data, ext.size, p_off))
         return pcm16, ext
+
+    # -- a recording through the bridge, time-parallel (include/lyra_hip_bridge_spans.h) ------------------------------------------
+    bridge_spans_plan = staticmethod(bridge_spans_plan)
+
+    def _bridge_spans_frames(self, spans, rooms, lane_ids, frames):
+        """the host arguments of the three calls below on buffers of `frames` frames, and the arrays they point into"""
+        sp, labels = _bridge_spans_args(spans, rooms)
+        a, held = self._span_args(sp, lane_ids, frames)
+        return a, labels, (held, labels)
+
+    def bridge_spans_mix_dev(self, spans, rooms, d_pcm16, d_mix, max_speakers=0, d_muted=None, d_is_comfort_noise=None,
+                             d_levels=None, d_is_speaker=None):
+        """The bridge's mix as one pass over all ticks (lyra_hip_spans_bridge_mix_dev): participant p's tick t is frame
+        spans[p].first_frame + t of d_pcm16 / d_mix int16 [frames][320]; rooms int32 [P] host labels.  max_speakers 0: the full
+        mix of bridge_mix_dev per tick; 1 .. SPEAKERS_MAX: the selection of speakers_mix_dev with d_levels int64 [frames] /
+        d_is_speaker int32 [frames] (optional).  d_muted / d_is_comfort_noise int32 [frames] or None.  Frames outside the spans
+        are untouched.  Completes on the encode-side stream."""
+        F = d_pcm16.shape[0]
+        a, labels, _held = self._bridge_spans_frames(spans, rooms, (), F)
+        self._dev_call(self.L.lyra_hip_spans_bridge_mix_dev, a[0], a[1], labels.ctypes.data, self._p_pcm(d_pcm16, F),
+                       self._opt_dev_ptr(d_muted, "int32", (F,), "muted"),
+                       self._opt_dev_ptr(d_is_comfort_noise, "int32", (F,), "is_comfort_noise"), int(max_speakers),
+                       self._p_pcm(d_mix, F), self._opt_dev_ptr(d_levels, "int64", (F,), "levels"),
+                       self._opt_dev_ptr(d_is_speaker, "int32", (F,), "is_speaker"))
+
+    def bridge_spans_dev(self, spans, rooms, d_packets, packet_bytes, num_bits, d_out_packets, d_out_packet_bytes, d_pcm16,
+                         d_mix, lane_ids=(), d_muted=None, dtx=None, flags=0, max_speakers=0, d_is_noise=None,
+                         d_is_comfort_noise=None, d_levels=None, d_is_speaker=None):
+        """A meeting recording through the bridge in one call (lyra_hip_spans_bridge_dev): bit for bit bridge_tick_dev
+        (max_speakers 0) or speakers_tick_dev over the T ticks of the spans.  spans, rooms [P], lane_ids, packet_bytes int32
+        [frames] (0 / 8 / 15 / 23), num_bits int32 [frames] and dtx [P] or None stay host arrays; d_packets / d_out_packets uint8
+        [frames][23], d_out_packet_bytes int32 [frames], d_pcm16 / d_mix int16 [frames][320] (required workspace and output),
+        d_muted int32 [frames] or None; d_is_noise / d_is_comfort_noise / d_is_speaker int32 [frames], d_levels int64 [frames]:
+        optional outputs.  Blocks the host once at its start, and once more where dtx names a participant; with DTX the
+        context's encoder rate must be 16000."""
+        F = d_packets.shape[0]
+        a, labels, _held = self._bridge_spans_frames(spans, rooms, lane_ids, F)
+        pb = self._span_packet_bytes(packet_bytes, F)
+        bits = self._span_packet_bytes(num_bits, F, "num_bits")
+        d = None if dtx is None else _np(np.asarray(dtx) != 0, np.int32, (a[1],))
+        call = BridgeSpansCall(a[0], a[1], a[2], a[3], labels.ctypes.data, self._p_packets(d_packets, F, MAX_PACKET_BYTES),
+                               pb.ctypes.data, self._opt_dev_ptr(d_muted, "int32", (F,), "muted"), int(flags), bits.ctypes.data,
+                               None if d is None else d.ctypes.data, self._p_packets(d_out_packets, F, MAX_PACKET_BYTES),
+                               self._p_packet_bytes(d_out_packet_bytes, F), self._p_pcm(d_pcm16, F), self._p_pcm(d_mix, F),
+                               *self._p_noise_flags(d_is_noise, d_is_comfort_noise, F), int(max_speakers),
+                               self._opt_dev_ptr(d_levels, "int64", (F,), "levels"),
+                               self._opt_dev_ptr(d_is_speaker, "int32", (F,), "is_speaker"))
+        self._dev_call(self.L.lyra_hip_spans_bridge_dev, C.addressof(call))
+
+    def bridge_spans(self, spans, rooms, packets, packet_bytes, num_bits, lane_ids=(), muted=None, dtx=None, flags=0,
+                     max_speakers=0):
+        """bridge_spans_dev from host arrays (lyra_hip_spans_bridge): packets uint8 [frames][23], packet_bytes / num_bits int32
+        [frames], muted [frames] or None, dtx [P] or None.  Returns a dict of frame-indexed arrays: out_packets uint8
+        [frames][23] (zero behind each packet's bytes), out_packet_bytes, is_noise, is_comfort_noise int32 [frames], pcm16 and
+        mix int16 [frames][320], and with max_speakers >= 1 levels int64 [frames] and is_speaker int32 [frames]; rows outside
+        every span are 0."""
+        packets = _np(packets, np.uint8, (-1, MAX_PACKET_BYTES))
+        F = packets.shape[0]
+        a, labels, _held = self._bridge_spans_frames(spans, rooms, lane_ids, F)
+        pb = self._span_packet_bytes(packet_bytes, F)
+        bits = self._span_packet_bytes(num_bits, F, "num_bits")
+        m = None if muted is None else self._span_packet_bytes(np.asarray(muted) != 0, F, "muted")
+        d = None if dtx is None else _np(np.asarray(dtx) != 0, np.int32, (a[1],))
+        out = {"out_packets": np.zeros((F, MAX_PACKET_BYTES), np.uint8), "out_packet_bytes": np.zeros(F, np.int32),
+               "pcm16": np.zeros((F, HOP), np.int16), "mix": np.zeros((F, HOP), np.int16),
+               "is_noise": np.zeros(F, np.int32), "is_comfort_noise": np.zeros(F, np.int32)}
+        if max_speakers:
+            out["levels"], out["is_speaker"] = np.zeros(F, np.int64), np.zeros(F, np.int32)
+        sel = [out[k].ctypes.data if k in out else None for k in ("levels", "is_speaker")]
+        self._chk(self.L.lyra_hip_spans_bridge(self.h, *a, labels.ctypes.data, packets.ctypes.data, pb.ctypes.data,
+                                               None if m is None else m.ctypes.data, int(flags), bits.ctypes.data,
+                                               None if d is None else d.ctypes.data, int(max_speakers),
+                                               out["out_packets"].ctypes.data, out["out_packet_bytes"].ctypes.data,
+                                               out["pcm16"].ctypes.data, out["mix"].ctypes.data, out["is_noise"].ctypes.data,
+                                               out["is_comfort_noise"].ctypes.data, *sel))
+        return out
 
     def noise_receive_dev(self, d_ids, d_pcm, d_is_noise, side="decoder"):
         """NoiseEstimator::ReceiveSamples on device buffers: pcm int16 [B][320] -> is_noise int32 [B]."""

@@ -7,7 +7,10 @@
 // lengths_in: [ticks][num_streams] int32, 0 = no packet from that stream on that tick.  Writes every tick's outgoing packets
 // [num_streams][23] and lengths [num_streams] int32.
 // mode 0: Tick() per tick.  mode 1: the same call through TickAsync / WaitTick, two ticks deep (tick t + 1 is begun before tick
-// t is waited for); it must write the same two files.
+// t is waited for); it must write the same two files.  mode 2: the whole recording time-parallel through
+// BridgeRecordingTimeParallel (lyra_bridge_recording.h), one device call per stretch of constant membership, on
+// --lanes=L lent stream slots (default 64); it must write the same files again, with --max-speakers=N too (not with
+// --shared-encoders).
 // --max-speakers=N: the same call through LyraSpeakerBridge (lyra_speaker_bridge.h), every room mixed from its N loudest
 // sources; every delivered tick's speaker flags [num_streams] int32 go to the file of --speakers-out.
 // --shared-encoders (with --max-speakers): the same call through LyraSharedBridge (lyra_shared_bridge.h), 1 + N encoders per
@@ -24,6 +27,7 @@
 #include <utility>
 #include <vector>
 
+#include "lyra_bridge_recording.h"
 #include "lyra_conference_bridge.h"
 #include "lyra_shared_bridge.h"
 #include "lyra_speaker_bridge.h"
@@ -58,12 +62,14 @@ int main(int argc_all, char** argv_all) {
   const char* speakers_path = nullptr;
   const char* slots_path = nullptr;
   bool shared_encoders = false;
+  int lanes = 64;
   std::vector<char*> positional;
   for (int i = 0; i < argc_all; ++i) {
     if (std::strncmp(argv_all[i], "--max-speakers=", 15) == 0) max_speakers = std::atoi(argv_all[i] + 15);
     else if (std::strncmp(argv_all[i], "--speakers-out=", 15) == 0) speakers_path = argv_all[i] + 15;
     else if (std::strncmp(argv_all[i], "--slots-out=", 12) == 0) slots_path = argv_all[i] + 12;
     else if (std::strcmp(argv_all[i], "--shared-encoders") == 0) shared_encoders = true;
+    else if (std::strncmp(argv_all[i], "--lanes=", 8) == 0) lanes = std::atoi(argv_all[i] + 8);
     else positional.push_back(argv_all[i]);
   }
   const int argc = static_cast<int>(positional.size());
@@ -72,8 +78,9 @@ int main(int argc_all, char** argv_all) {
   if (argc != 10 || (select && (max_speakers == 0 || speakers_path == nullptr)) || (shared_encoders && !select) ||
       (slots_path && !shared_encoders)) {
     std::fprintf(stderr, "usage: bridge_demo <model_dir> <streams.txt> <script.i32> <packets_in.bin> <lengths_in.i32> "
-                         "<packets_out.bin> <lengths_out.i32> <mode 0|1> <skip_comfort_noise 0|1> "
-                         "[--max-speakers=N --speakers-out=<speakers_out.i32> [--shared-encoders [--slots-out=<slots_out.i32>]]]\n");
+                         "<packets_out.bin> <lengths_out.i32> <mode 0|1|2> <skip_comfort_noise 0|1> "
+                         "[--max-speakers=N --speakers-out=<speakers_out.i32> [--shared-encoders [--slots-out=<slots_out.i32>]]] "
+                         "[--lanes=L]\n");
     return 2;
   }
   std::vector<BridgeStream> streams;
@@ -90,7 +97,24 @@ int main(int argc_all, char** argv_all) {
   const size_t ticks = lengths.size() / n;
   if (lengths.size() != ticks * n || script.size() != ticks * n * 3 || packets.size() != ticks * n * kRow)
     return Fail("the input files disagree about ticks and streams");
-  const bool pipelined = std::atoi(argv[8]) != 0;
+  const int mode = std::atoi(argv[8]);
+  if (mode == 2) {   // the recording as a whole
+    if (shared_encoders) return Fail("mode 2 has no shared encoders");
+    std::vector<int32_t> flags;
+    auto got = BridgeRecordingTimeParallel(absl::MakeConstSpan(streams), argv[1], absl::MakeConstSpan(packets),
+                                           absl::MakeConstSpan(lengths), absl::MakeConstSpan(script), std::atoi(argv[9]) != 0,
+                                           max_speakers, lanes, 0, &flags);
+    if (!got) return Fail("BridgeRecordingTimeParallel failed");
+    std::ofstream out_pk(argv[6], std::ios::binary), out_len(argv[7], std::ios::binary);
+    out_pk.write(reinterpret_cast<const char*>(got->first.data()), static_cast<std::streamsize>(got->first.size()));
+    out_len.write(reinterpret_cast<const char*>(got->second.data()), static_cast<std::streamsize>(got->second.size() * sizeof(int32_t)));
+    if (speakers_path) {
+      std::ofstream out_spk(speakers_path, std::ios::binary);
+      out_spk.write(reinterpret_cast<const char*>(flags.data()), static_cast<std::streamsize>(flags.size() * sizeof(int32_t)));
+    }
+    return 0;
+  }
+  const bool pipelined = mode != 0;
   std::unique_ptr<LyraConferenceBridge> bridge;
   LyraSpeakerBridge* speakers = nullptr;
   LyraSharedBridge* shared = nullptr;

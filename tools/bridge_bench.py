@@ -33,7 +33,18 @@ selection, slot update and the E mixes around back-to-back lyra_hip_shared_mix_d
 different non-empty packets a tick sends, against the streams it sends them to.  --layout L runs one layout only: give this
 leg a process per layout -- with all three in one process the later layouts measured about 40 % slower in both forms (DESIGN.md
 4.4, "Shared encoders"; cause not found).
-    python tools/bridge_bench.py [--streams 4096] [--hops 200] [--reps 5] [--max-speakers N [--shared] [--layout L]] [--out profiles/bridge.jsonl]"""
+--recording runs the recorded-meeting leg INSTEAD (include/lyra_hip_bridge_spans.h): meetings of 8 participants in one room, 10 %
+Gilbert loss, DTX on every other row, of 9,000 ticks (3 minutes) and 180,000 ticks (1 hour), on 4,096 lanes:
+  "spans_dev": ONE lyra_hip_spans_bridge_dev call for the whole meeting, median of --reps with min..max (streams reset in front of
+               every call, outside the timed window), in seconds and as a multiple of real time;
+  "tick_dev":  the same ticks through lyra_hip_bridge_tick_dev (lyra_hip_speakers_tick_dev with --max-speakers N), 8 rows each,
+               torch_order = False.  The 3-minute meeting runs whole; of the hour the first 2,000 ticks are timed and the time
+               SCALED to 180,000 ("scaled_from_ticks" says so).
+"equal": outgoing packets and sizes of both forms bit for bit over the ticks the tick form ran.  "pass": the mix pass alone
+(lyra_hip_spans_bridge_mix_dev on the meeting's decoded hops), device events around it on the encode-side stream, and its share
+of the call.  No threshold is fixed in advance: "verdict" says faster, SLOWER or inside the spreads as the other legs do.
+    python tools/bridge_bench.py [--streams 4096] [--hops 200] [--reps 5] [--max-speakers N [--shared] [--layout L]]
+                                 [--recording [--max-speakers N] [--lanes 4096]] [--out profiles/bridge.jsonl]"""
 import argparse
 import json
 import os
@@ -76,6 +87,130 @@ def np_mix(x, room_of, first_rows):
     return np.clip(s[room_of] - x, -32768, 32767).astype(np.int16)
 
 
+def recording(a):
+    """the --recording leg (see the module's docstring)"""
+    import torch
+    import lyra_amd
+    from lossy_steps_bench import gilbert, speech_ring
+    P, ring, N, dev = 8, 50, a.max_speakers, torch.device("cuda", 0)
+    rng = np.random.default_rng(3)
+    t_ = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
+    ids = np.arange(P, dtype=np.int32)
+    lanes = np.arange(P, P + a.lanes, dtype=np.int32)
+    rooms = np.zeros(P, np.int32)
+    dtx = (np.arange(P) % 2).astype(np.int32)
+    d_ids, d_dtx = t_(ids), t_(dtx)
+    speech = speech_ring(ring, P, rng)
+    prep = lyra_amd.LyraHip(device=0, max_streams=P)
+    pk = np.zeros((ring, P, 23), np.uint8)
+    d15 = torch.zeros((P, 15), dtype=torch.uint8, device=dev)
+    for t in range(ring):
+        prep.encode_dev(d_ids, t_(speech[t]), 120, d15)
+        prep.synchronize()
+        pk[t, :, :15] = d15.cpu().numpy()
+    prep.close()
+    order, start = lyra_amd.codec.bridge_plan(rooms)
+    d_order, d_start = t_(order), t_(start)
+    lines = []
+    for T, tick_ticks in ((9000, 9000), (180000, 2000)):
+        rx = gilbert(rng, T, P, 0.10)
+        nb = rx.astype(np.int32) * 15                                   # [T][P]
+        F = P * T
+        spans = [(int(p), int(p) * T, T) for p in ids]                  # participant-major: frame p * T + t
+        pk_frames = np.ascontiguousarray(pk[np.arange(T) % ring].transpose(1, 0, 2)).reshape(F, 23)
+        nb_frames = np.ascontiguousarray(nb.T).reshape(F)
+        bits_frames = np.full(F, 120, np.int32)
+        d_pkf = t_(pk_frames)
+        cs, ct = (lyra_amd.LyraHip(device=0, max_streams=P + a.lanes) for _ in range(2))
+        try:
+            cs.torch_order = ct.torch_order = False
+            out_s = torch.zeros((F, 23), dtype=torch.uint8, device=dev)
+            len_s = torch.zeros(F, dtype=torch.int32, device=dev)
+            x_s, mix_s = (torch.zeros((F, 320), dtype=torch.int16, device=dev) for _ in range(2))
+            out_t = torch.zeros((tick_ticks, P, 23), dtype=torch.uint8, device=dev)
+            len_t = torch.zeros((tick_ticks, P), dtype=torch.int32, device=dev)
+            d_pk_ring, d_nb, d_bits = t_(pk), t_(nb[:tick_ticks]), t_(np.full(P, 120, np.int32))
+            torch.cuda.synchronize()
+
+            def one_call():
+                cs.bridge_spans_dev(spans, rooms, d_pkf, nb_frames, bits_frames, out_s, len_s, x_s, mix_s, lane_ids=lanes, dtx=dtx,
+                                    max_speakers=N)
+
+            def ticks(n):
+                for t in range(n):
+                    if N:
+                        ct.speakers_tick_dev(d_ids, d_pk_ring[t % ring], d_nb[t], d_order, d_start, d_bits, out_t[t], len_t[t], N,
+                                             None, d_dtx)
+                    else:
+                        ct.bridge_tick_dev(d_ids, d_pk_ring[t % ring], d_nb[t], d_order, d_start, d_bits, out_t[t], len_t[t],
+                                           None, d_dtx)
+
+            def clocked(ctx, run):
+                ctx.reset()
+                ctx.synchronize()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                run()
+                ctx.synchronize()
+                torch.cuda.synchronize()
+                return time.perf_counter() - t0
+
+            ticks(200)                                                   # warm-up of both forms, not counted
+            clocked(cs, one_call)
+            span_s = sorted(clocked(cs, one_call) for _ in range(a.reps))
+            out_t.zero_()
+            tick_s = clocked(ct, lambda: ticks(tick_ticks))
+            # outgoing packets and sizes, bit for bit, over the ticks the tick form ran (both buffers started as zeros)
+            got_len = len_s.view(P, T)[:, :tick_ticks].t()
+            got_pk = out_s.view(P, T, 23)[:, :tick_ticks].transpose(0, 1)
+            equal = bool(torch.equal(got_len, len_t) and torch.equal(got_pk, out_t))
+            # the pass alone: events on the encode-side stream around it
+            how = "device events around one lyra_hip_spans_bridge_mix_dev call"
+            try:
+                st = torch.cuda.ExternalStream(cs.stream_handle(), device=dev)
+            except Exception:
+                st, how = None, "host clock around one lyra_hip_spans_bridge_mix_dev call and a synchronise"
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            per = []
+            for rep in range(a.reps + 1):
+                cs.synchronize()
+                t0 = time.perf_counter()
+                if st is not None:
+                    e0.record(st)
+                cs.bridge_spans_mix_dev(spans, rooms, x_s, mix_s, N)
+                if st is not None:
+                    e1.record(st)
+                cs.synchronize()
+                if rep:
+                    per.append(e0.elapsed_time(e1) if st is not None else (time.perf_counter() - t0) * 1e3)
+            per.sort()
+            med = span_s[len(span_s) // 2]
+            tick_whole = tick_s * T / tick_ticks
+            line = {"bench": "bridge", "case": "recording", "participants": P, "ticks": T, "minutes": T / 3000.0, "lanes": int(a.lanes),
+                    "max_speakers": N, "loss": 0.10, "reps": a.reps,
+                    "spans_dev": {"seconds_median": round(med, 4), "min": round(span_s[0], 4), "max": round(span_s[-1], 4),
+                                  "times_real_time": round(T * 0.02 / med, 1)},
+                    "tick_dev": {"seconds": round(tick_whole, 3), "timed_ticks": tick_ticks,
+                                 "scaled_from_ticks": tick_ticks if tick_ticks != T else None,
+                                 "times_real_time": round(T * 0.02 / tick_whole, 1)},
+                    "tick_dev_over_spans_dev": round(tick_whole / med, 2),
+                    "verdict": "faster" if span_s[-1] < tick_whole else "SLOWER" if span_s[0] > tick_whole else "inside the spreads",
+                    "equal": equal, "equal_over_ticks": tick_ticks,
+                    "pass": {"ms_median": round(per[len(per) // 2], 3), "min": round(per[0], 3), "max": round(per[-1], 3),
+                             "share_of_call": round(per[len(per) // 2] / (med * 1e3), 4), "what": how},
+                    "errors": {"bridge": int(cs.bridge_errors()), "lossy": int(cs.decode_lossy_errors()),
+                               "mixed": int(cs.encode_mixed_errors())}}
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+        finally:
+            cs.close()
+            ct.close()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "a") as f:
+        for line in lines:
+            f.write(json.dumps(line) + "\n")
+
+
 def main():
     import torch
     import lyra_amd
@@ -90,8 +225,14 @@ def main():
     ap.add_argument("--shared", action="store_true", help="with --max-speakers: the shared-encoder tick against the loudest-N tick")
     ap.add_argument("--layout", default=None, choices=["rooms_of_4", "rooms_of_16", "one_room"],
                     help="with --max-speakers: this layout only (a process of its own per layout)")
+    ap.add_argument("--recording", action="store_true", help="the recorded-meeting leg: one time-parallel call against the ticks")
+    ap.add_argument("--lanes", type=int, default=4096, help="with --recording: stream slots lent to the call")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bridge.jsonl"))
     a = ap.parse_args()
+    if a.recording:
+        if a.shared:
+            raise SystemExit("--recording has no shared-encoder form")
+        return recording(a)
     B, dev, ring = a.streams, torch.device("cuda", 0), 50
     rng = np.random.default_rng(3)
     t_ = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
