@@ -589,6 +589,11 @@ def _np(a, dtype, shape):
     return a.reshape(shape)
 
 
+def _np01(a, shape):
+    """an optional array of switches as int32 zeros and ones (None stays None)"""
+    return None if a is None else _np(np.asarray(a) != 0, np.int32, shape)
+
+
 class LyraHip:
     """One GPU context: weights + per-stream state for `max_streams` streams."""
 
@@ -623,9 +628,7 @@ class LyraHip:
         self._pending_any_decodes = []      # (B, num_samples) of the requests begun by decode_samples_any_begin, oldest first
         self._pending_stream_decodes = []   # (B, packed samples) of the hops begun by decode_streams_begin, oldest first
         self._pending_sample_stream_decodes = []   # the same for decode_samples_streams_begin
-        self._pending_bridge_ticks = []     # B of the ticks begun by bridge_begin, oldest first
-        self._pending_speakers_ticks = []   # ... and by speakers_begin (the library holds both kinds in one queue of two)
-        self._pending_shared_ticks = []     # ... and by shared_begin (the same queue)
+        self._pending_ticks = []   # (kind, B) of the ticks begun by bridge_begin / speakers_begin / shared_begin, oldest first
 
     def _create(self, h, mode, model_dir, device, max_streams, weights_image):
         if weights_image is not None:   # bytes of a lyra_v1.lyrapack (lyra_hip_create_from_image)
@@ -1145,6 +1148,71 @@ class LyraHip:
                        *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B))
 
     # -- the conference bridge (include/lyra_hip_bridge.h) ---------------------------------------------
+    # What the calls of its three kinds of tick share -- the full mix here, the loudest-N selection and the shared encoders
+    # below -- is built once:
+    def _p_bridge_index(self, d_order, d_room_start):
+        """-> (d_order, d_room_start, n_rooms, n_members) as the mix and tick calls take the index of bridge_plan"""
+        n_members, n_rooms = d_order.shape[0], d_room_start.shape[0] - 1
+        return (self._dev_ptr(d_order, "int32", (n_members,), "order") if n_members else None,
+                self._dev_ptr(d_room_start, "int32", (n_rooms + 1,), "room_start"), n_rooms, n_members)
+
+    def _p_mix_sources(self, d_order, d_room_start, d_muted, d_is_comfort_noise, B):
+        """-> the index, then the two optional lists of rows that are no source: the middle arguments of the mix calls"""
+        return (*self._p_bridge_index(d_order, d_room_start), self._opt_dev_ptr(d_muted, "int32", (B,), "muted"),
+                self._opt_dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise"))
+
+    def _p_selection(self, max_speakers, d_levels, d_is_speaker, B):
+        """-> (max_speakers, d_levels, d_is_speaker): what a selection adds to a mix call and to a tick struct"""
+        return (int(max_speakers), self._opt_dev_ptr(d_levels, "int64", (B,), "levels"),
+                self._opt_dev_ptr(d_is_speaker, "int32", (B,), "is_speaker"))
+
+    def _p_tick_head(self, d_ids, d_packets, d_packet_bytes, d_order, d_room_start, d_muted, flags):
+        """-> B and the leading fields of the three tick structs, d_stream_ids .. flags"""
+        B = d_packets.shape[0]
+        return B, (self._p_ids(d_ids, B), B, self._p_packets(d_packets, B, MAX_PACKET_BYTES),
+                   self._p_packet_bytes(d_packet_bytes, B), *self._p_bridge_index(d_order, d_room_start),
+                   self._opt_dev_ptr(d_muted, "int32", (B,), "muted"), int(flags))
+
+    def _p_tick_outputs(self, d_out_packets, d_out_packet_bytes, d_pcm16, B):
+        """-> the fields d_out_packets, d_out_packet_bytes, d_pcm16 of the three tick structs"""
+        return (self._p_packets(d_out_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_out_packet_bytes, B),
+                self._opt_dev_ptr(d_pcm16, "int16", (B, HOP), "16 kHz pcm"))
+
+    def _p_listener_bits(self, d_num_bits, d_dtx, B):
+        """-> the fields d_num_bits, d_dtx of the ticks that encode a row per listener"""
+        return (self._dev_ptr(d_num_bits, "int32", (B,), "num_bits"), self._opt_dev_ptr(d_dtx, "int32", (B,), "dtx flags"))
+
+    def _tick_begin_args(self, packets, packet_bytes, rooms, muted, flags, stream_ids):
+        """-> B, the host arrays (to be kept alive over the call) and the leading arguments of the three begin() calls"""
+        packets = _np(packets, np.uint8, (-1, MAX_PACKET_BYTES))
+        B = packets.shape[0]
+        sizes, labels = (_np(a, np.int32, (B,)) for a in (packet_bytes, rooms))
+        m = _np01(muted, (B,))
+        ids = self._ids(stream_ids, B)
+        return B, (packets, sizes, labels, m, ids), (self.h, ids.ctypes.data, B, packets.ctypes.data, sizes.ctypes.data,
+                                                     labels.ctypes.data, None if m is None else m.ctypes.data, int(flags))
+
+    def _tick_begin(self, kind, fn, B, *args):
+        self._chk(fn(*args))
+        self._pending_ticks.append((kind, B))
+
+    def _tick_end(self, kind, fn, n_flags, with_levels):
+        """end() of the three kinds of tick -> (out_packets uint8 [B][23], n_flags int32 [B] arrays -- with_levels: levels int64
+        [B] behind the third) in the order of the library's arguments.  The arrays are sized by the oldest tick in flight,
+        whatever its kind: an end() of another kind the library refuses, keeping the tick, and its message is what the caller
+        sees."""
+        if not self._pending_ticks:
+            self._chk(fn(self.h, *[None] * (1 + n_flags + with_levels)))
+        begun, B = self._pending_ticks[0]
+        out = np.empty((B, MAX_PACKET_BYTES), np.uint8)
+        flags = [np.empty(B, np.int32) for _ in range(n_flags)]
+        arrays = flags[:3] + ([np.empty(B, np.int64)] if with_levels else []) + flags[3:]
+        rc = fn(self.h, out.ctypes.data, *(a.ctypes.data for a in arrays))
+        if begun == kind:
+            self._pending_ticks.pop(0)   # (the library gives the slot back whatever the wait returns)
+        self._chk(rc)
+        return (out, *arrays)
+
     def bridge_mix_dev(self, d_pcm16, d_order, d_room_start, d_mix, d_muted=None, d_is_comfort_noise=None):
         """The mix-minus alone (lyra_hip_bridge_mix_dev): d_pcm16 / d_mix int16 [B][320]; d_order int32 [n_members] row
         numbers with a room's rows contiguous, d_room_start int32 [n_rooms + 1] (bridge_plan); d_muted / d_is_comfort_noise
@@ -1152,12 +1220,8 @@ class LyraHip:
         zeros if no room names it.  Bad d_order entries are skipped and counted in bridge_errors.  Completes on the
         encode-side stream."""
         B = d_pcm16.shape[0]
-        n_members, n_rooms = d_order.shape[0], d_room_start.shape[0] - 1
         self._dev_call(self.L.lyra_hip_bridge_mix_dev, self._p_pcm(d_pcm16, B), B,
-                       self._dev_ptr(d_order, "int32", (n_members,), "order") if n_members else None,
-                       self._dev_ptr(d_room_start, "int32", (n_rooms + 1,), "room_start"), n_rooms, n_members,
-                       self._opt_dev_ptr(d_muted, "int32", (B,), "muted"),
-                       self._opt_dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise"), self._p_pcm(d_mix, B))
+                       *self._p_mix_sources(d_order, d_room_start, d_muted, d_is_comfort_noise, B), self._p_pcm(d_mix, B))
 
     def bridge_tick_dev(self, d_ids, d_packets, d_packet_bytes, d_order, d_room_start, d_num_bits, d_out_packets,
                         d_out_packet_bytes, d_muted=None, d_dtx=None, flags=0, d_pcm16=None, d_mix=None, d_is_noise=None,
@@ -1167,17 +1231,9 @@ class LyraHip:
         on the mix with d_num_bits int32 [B] / d_dtx int32 [B] or None into d_out_packets uint8 [B][23] /
         d_out_packet_bytes int32 [B].  d_pcm16 / d_mix int16 [B][320], d_is_noise / d_is_comfort_noise int32 [B]: optional
         outputs.  Bit for bit the three calls in a row, outputs and stream state."""
-        B = d_packets.shape[0]
-        n_members, n_rooms = d_order.shape[0], d_room_start.shape[0] - 1
-        t = BridgeTick(self._p_ids(d_ids, B), B, self._p_packets(d_packets, B, MAX_PACKET_BYTES),
-                       self._p_packet_bytes(d_packet_bytes, B),
-                       self._dev_ptr(d_order, "int32", (n_members,), "order") if n_members else None,
-                       self._dev_ptr(d_room_start, "int32", (n_rooms + 1,), "room_start"), n_rooms, n_members,
-                       self._opt_dev_ptr(d_muted, "int32", (B,), "muted"), int(flags),
-                       self._dev_ptr(d_num_bits, "int32", (B,), "num_bits"),
-                       self._opt_dev_ptr(d_dtx, "int32", (B,), "dtx flags"),
-                       self._p_packets(d_out_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_out_packet_bytes, B),
-                       self._opt_dev_ptr(d_pcm16, "int16", (B, HOP), "16 kHz pcm"),
+        B, head = self._p_tick_head(d_ids, d_packets, d_packet_bytes, d_order, d_room_start, d_muted, flags)
+        t = BridgeTick(*head, *self._p_listener_bits(d_num_bits, d_dtx, B),
+                       *self._p_tick_outputs(d_out_packets, d_out_packet_bytes, d_pcm16, B),
                        self._opt_dev_ptr(d_mix, "int16", (B, HOP), "mix"),
                        *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B))
         self._dev_call(self.L.lyra_hip_bridge_tick_dev, C.addressof(t))
@@ -1186,35 +1242,14 @@ class LyraHip:
         """Pipelined tick of the bridge from host arrays (lyra_hip_bridge_begin): packets uint8 [B][23], packet_bytes int32 [B]
         (0 / 8 / 15 / 23), rooms int32 [B] (a label >= 0, or < 0: in no room), num_bits int32 [B], muted / dtx [B] or None.
         Up to two ticks in flight; the arrays may be reused at once."""
-        packets = _np(packets, np.uint8, (-1, MAX_PACKET_BYTES))
-        B = packets.shape[0]
-        sizes, labels, bits = (_np(a, np.int32, (B,)) for a in (packet_bytes, rooms, num_bits))
-        m = None if muted is None else _np(np.asarray(muted) != 0, np.int32, (B,))
-        d = None if dtx is None else _np(np.asarray(dtx) != 0, np.int32, (B,))
-        ids = self._ids(stream_ids, B)
-        self._chk(self.L.lyra_hip_bridge_begin(self.h, ids.ctypes.data, B, packets.ctypes.data, sizes.ctypes.data,
-                                               labels.ctypes.data, None if m is None else m.ctypes.data, int(flags),
-                                               bits.ctypes.data, None if d is None else d.ctypes.data))
-        self._pending_bridge_ticks.append(B)
+        B, _alive, head = self._tick_begin_args(packets, packet_bytes, rooms, muted, flags, stream_ids)
+        bits, d = _np(num_bits, np.int32, (B,)), _np01(dtx, (B,))
+        self._tick_begin("bridge", self.L.lyra_hip_bridge_begin, B, *head, bits.ctypes.data, None if d is None else d.ctypes.data)
 
     def bridge_end(self):
         """-> (out_packets uint8 [B][23], zero behind each packet's bytes; out_packet_bytes, is_noise, is_comfort_noise int32
         [B]) of the OLDEST tick begun by bridge_begin."""
-        if not self._pending_bridge_ticks:
-            self._chk(self.L.lyra_hip_bridge_end(self.h, None, None, None, None))
-        B = self._pending_bridge_ticks[0]
-        out = np.empty((B, MAX_PACKET_BYTES), np.uint8)
-        lens, noise, cn = (np.empty(B, np.int32) for _ in range(3))
-        rc = self.L.lyra_hip_bridge_end(self.h, out.ctypes.data, lens.ctypes.data, noise.ctypes.data, cn.ctypes.data)
-        self._chk_other_kind(rc)            # (refused: the oldest tick is speakers_begin's; nothing was consumed)
-        self._pending_bridge_ticks.pop(0)   # (otherwise the library gives the slot back whatever the wait returns)
-        self._chk(rc)
-        return out, lens, noise, cn
-
-    def _chk_other_kind(self, rc):
-        """bridge_end / speakers_end on a tick that the other begin() started: the library refuses and keeps the tick"""
-        if rc != 0 and "the oldest tick was begun by" in self.last_error():
-            self._chk(rc)
+        return self._tick_end("bridge", self.L.lyra_hip_bridge_end, 3, False)
 
     def bridge_errors(self, clear=False):
         """d_order entries outside [0, B) that the bridge's mix skipped (synchronises)."""
@@ -1228,14 +1263,10 @@ class LyraHip:
         d_mix receives the clamped sum of the max_speakers loudest sources of its room, itself left out.  Bad d_order entries
         are skipped and counted in bridge_errors.  Completes on the encode-side stream."""
         B = d_pcm16.shape[0]
-        n_members, n_rooms = d_order.shape[0], d_room_start.shape[0] - 1
+        sel = self._p_selection(max_speakers, d_levels, d_is_speaker, B)
         self._dev_call(self.L.lyra_hip_speakers_mix_dev, self._p_pcm(d_pcm16, B), B,
-                       self._dev_ptr(d_order, "int32", (n_members,), "order") if n_members else None,
-                       self._dev_ptr(d_room_start, "int32", (n_rooms + 1,), "room_start"), n_rooms, n_members,
-                       self._opt_dev_ptr(d_muted, "int32", (B,), "muted"),
-                       self._opt_dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise"), int(max_speakers),
-                       self._p_pcm(d_mix, B), self._opt_dev_ptr(d_levels, "int64", (B,), "levels"),
-                       self._opt_dev_ptr(d_is_speaker, "int32", (B,), "is_speaker"))
+                       *self._p_mix_sources(d_order, d_room_start, d_muted, d_is_comfort_noise, B), sel[0],
+                       self._p_pcm(d_mix, B), *sel[1:])
 
     def speakers_tick_dev(self, d_ids, d_packets, d_packet_bytes, d_order, d_room_start, d_num_bits, d_out_packets,
                           d_out_packet_bytes, max_speakers, d_muted=None, d_dtx=None, flags=0, d_pcm16=None, d_mix=None,
@@ -1243,55 +1274,35 @@ class LyraHip:
         """One tick of the bridge with selection (lyra_hip_speakers_tick_dev): bridge_tick_dev with the mix of
         speakers_mix_dev (flags: SPEAKERS_SKIP_COMFORT_NOISE) and its two further optional outputs, d_levels int64 [B] and
         d_is_speaker int32 [B].  Bit for bit the three calls in a row, outputs and stream state."""
-        B = d_packets.shape[0]
-        n_members, n_rooms = d_order.shape[0], d_room_start.shape[0] - 1
-        t = SpeakersTick(self._p_ids(d_ids, B), B, self._p_packets(d_packets, B, MAX_PACKET_BYTES),
-                         self._p_packet_bytes(d_packet_bytes, B),
-                         self._dev_ptr(d_order, "int32", (n_members,), "order") if n_members else None,
-                         self._dev_ptr(d_room_start, "int32", (n_rooms + 1,), "room_start"), n_rooms, n_members,
-                         self._opt_dev_ptr(d_muted, "int32", (B,), "muted"), int(flags),
-                         self._dev_ptr(d_num_bits, "int32", (B,), "num_bits"),
-                         self._opt_dev_ptr(d_dtx, "int32", (B,), "dtx flags"),
-                         self._p_packets(d_out_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_out_packet_bytes, B),
-                         self._opt_dev_ptr(d_pcm16, "int16", (B, HOP), "16 kHz pcm"),
+        B, head = self._p_tick_head(d_ids, d_packets, d_packet_bytes, d_order, d_room_start, d_muted, flags)
+        t = SpeakersTick(*head, *self._p_listener_bits(d_num_bits, d_dtx, B),
+                         *self._p_tick_outputs(d_out_packets, d_out_packet_bytes, d_pcm16, B),
                          self._opt_dev_ptr(d_mix, "int16", (B, HOP), "mix"),
-                         *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B), int(max_speakers),
-                         self._opt_dev_ptr(d_levels, "int64", (B,), "levels"),
-                         self._opt_dev_ptr(d_is_speaker, "int32", (B,), "is_speaker"))
+                         *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B),
+                         *self._p_selection(max_speakers, d_levels, d_is_speaker, B))
         self._dev_call(self.L.lyra_hip_speakers_tick_dev, C.addressof(t))
 
     def speakers_begin(self, packets, packet_bytes, rooms, num_bits, max_speakers, muted=None, dtx=None, flags=0,
                        stream_ids=None):
         """Pipelined tick of the bridge with selection from host arrays (lyra_hip_speakers_begin): the arrays of bridge_begin
         and max_speakers in 1 .. SPEAKERS_MAX.  Up to two ticks in flight, bridge_begin's included."""
-        packets = _np(packets, np.uint8, (-1, MAX_PACKET_BYTES))
-        B = packets.shape[0]
-        sizes, labels, bits = (_np(a, np.int32, (B,)) for a in (packet_bytes, rooms, num_bits))
-        m = None if muted is None else _np(np.asarray(muted) != 0, np.int32, (B,))
-        d = None if dtx is None else _np(np.asarray(dtx) != 0, np.int32, (B,))
-        ids = self._ids(stream_ids, B)
-        self._chk(self.L.lyra_hip_speakers_begin(self.h, ids.ctypes.data, B, packets.ctypes.data, sizes.ctypes.data,
-                                                 labels.ctypes.data, None if m is None else m.ctypes.data, int(flags),
-                                                 bits.ctypes.data, None if d is None else d.ctypes.data, int(max_speakers)))
-        self._pending_speakers_ticks.append(B)
+        B, _alive, head = self._tick_begin_args(packets, packet_bytes, rooms, muted, flags, stream_ids)
+        bits, d = _np(num_bits, np.int32, (B,)), _np01(dtx, (B,))
+        self._tick_begin("speakers", self.L.lyra_hip_speakers_begin, B, *head, bits.ctypes.data,
+                         None if d is None else d.ctypes.data, int(max_speakers))
 
     def speakers_end(self):
         """-> (out_packets uint8 [B][23], out_packet_bytes, is_noise, is_comfort_noise int32 [B], levels int64 [B], is_speaker
         int32 [B]) of the OLDEST tick in flight, which must be one begun by speakers_begin."""
-        if not self._pending_speakers_ticks:
-            self._chk(self.L.lyra_hip_speakers_end(self.h, None, None, None, None, None, None))
-        B = self._pending_speakers_ticks[0]
-        out = np.empty((B, MAX_PACKET_BYTES), np.uint8)
-        lens, noise, cn, spk = (np.empty(B, np.int32) for _ in range(4))
-        levels = np.empty(B, np.int64)
-        rc = self.L.lyra_hip_speakers_end(self.h, out.ctypes.data, lens.ctypes.data, noise.ctypes.data, cn.ctypes.data,
-                                          levels.ctypes.data, spk.ctypes.data)
-        self._chk_other_kind(rc)              # (refused: the oldest tick is bridge_begin's; nothing was consumed)
-        self._pending_speakers_ticks.pop(0)   # (otherwise the library gives the slot back whatever the wait returns)
-        self._chk(rc)
-        return out, lens, noise, cn, levels, spk
+        return self._tick_end("speakers", self.L.lyra_hip_speakers_end, 4, True)
 
     # -- the bridge with shared encoders (include/lyra_hip_shared_bridge.h) ------------------------------
+    def _p_slot_table(self, d_room_keys, d_slots, n_rooms):
+        """-> (d_room_keys, d_slots, n_table_rooms) of shared_mix_dev and the shared tick struct"""
+        n_table = d_slots.shape[0]
+        return (self._opt_dev_ptr(d_room_keys, "int32", (n_rooms,), "room keys"),
+                self._dev_ptr(d_slots, "int32", (n_table, SHARED_SLOTS), "slot table"), n_table)
+
     def shared_mix_dev(self, d_pcm16, d_ids, d_order, d_room_start, d_slots, d_enc_mix, max_speakers, d_room_keys=None,
                        d_muted=None, d_is_comfort_noise=None, d_levels=None, d_is_speaker=None, d_slot_of=None):
         """Levels, selection, slot update and the encoder mixes alone (lyra_hip_shared_mix_dev): d_pcm16 int16 [B][320], d_ids
@@ -1300,19 +1311,13 @@ class LyraHip:
         [n_rooms * (1 + max_speakers)][320]; d_levels int64 [B], d_is_speaker and d_slot_of int32 [B]: optional outputs.
         Completes on the encode-side stream."""
         B = d_pcm16.shape[0]
-        n_members, n_rooms = d_order.shape[0], d_room_start.shape[0] - 1
+        n_rooms = d_room_start.shape[0] - 1
         E = n_rooms * (1 + int(max_speakers))
-        n_table = d_slots.shape[0]
+        sel = self._p_selection(max_speakers, d_levels, d_is_speaker, B)
         self._dev_call(self.L.lyra_hip_shared_mix_dev, self._p_pcm(d_pcm16, B), self._p_ids(d_ids, B), B,
-                       self._dev_ptr(d_order, "int32", (n_members,), "order") if n_members else None,
-                       self._dev_ptr(d_room_start, "int32", (n_rooms + 1,), "room_start"), n_rooms, n_members,
-                       self._opt_dev_ptr(d_muted, "int32", (B,), "muted"),
-                       self._opt_dev_ptr(d_is_comfort_noise, "int32", (B,), "is_comfort_noise"), int(max_speakers),
-                       self._opt_dev_ptr(d_room_keys, "int32", (n_rooms,), "room keys"),
-                       self._dev_ptr(d_slots, "int32", (n_table, SHARED_SLOTS), "slot table"), n_table,
-                       self._dev_ptr(d_enc_mix, "int16", (E, HOP), "encoder mixes"),
-                       self._opt_dev_ptr(d_levels, "int64", (B,), "levels"),
-                       self._opt_dev_ptr(d_is_speaker, "int32", (B,), "is_speaker"),
+                       *self._p_mix_sources(d_order, d_room_start, d_muted, d_is_comfort_noise, B), sel[0],
+                       *self._p_slot_table(d_room_keys, d_slots, n_rooms),
+                       self._dev_ptr(d_enc_mix, "int16", (E, HOP), "encoder mixes"), *sel[1:],
                        self._opt_dev_ptr(d_slot_of, "int32", (B,), "slot_of"))
 
     def shared_tick_dev(self, d_ids, d_packets, d_packet_bytes, d_order, d_room_start, d_out_packets, d_out_packet_bytes,
@@ -1325,22 +1330,13 @@ class LyraHip:
         the E packets into d_out_packets uint8 [B][23] / d_out_packet_bytes int32 [B].  d_slots / d_room_keys as in
         shared_mix_dev.  Optional outputs: d_pcm16, d_is_noise, d_is_comfort_noise, d_levels, d_is_speaker, d_slot_of [B];
         d_enc_mix int16 [E][320], d_enc_packets uint8 [E][23], d_enc_packet_bytes int32 [E]."""
-        B = d_packets.shape[0]
-        n_members, n_rooms = d_order.shape[0], d_room_start.shape[0] - 1
+        B, head = self._p_tick_head(d_ids, d_packets, d_packet_bytes, d_order, d_room_start, d_muted, flags)
+        n_rooms = d_room_start.shape[0] - 1
         E = n_rooms * (1 + int(max_speakers))
-        n_table = d_slots.shape[0]
-        t = SharedTick(self._p_ids(d_ids, B), B, self._p_packets(d_packets, B, MAX_PACKET_BYTES),
-                       self._p_packet_bytes(d_packet_bytes, B),
-                       self._dev_ptr(d_order, "int32", (n_members,), "order") if n_members else None,
-                       self._dev_ptr(d_room_start, "int32", (n_rooms + 1,), "room_start"), n_rooms, n_members,
-                       self._opt_dev_ptr(d_muted, "int32", (B,), "muted"), int(flags),
-                       self._p_packets(d_out_packets, B, MAX_PACKET_BYTES), self._p_packet_bytes(d_out_packet_bytes, B),
-                       self._opt_dev_ptr(d_pcm16, "int16", (B, HOP), "16 kHz pcm"),
-                       *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B), int(max_speakers),
-                       self._opt_dev_ptr(d_levels, "int64", (B,), "levels"),
-                       self._opt_dev_ptr(d_is_speaker, "int32", (B,), "is_speaker"),
-                       self._opt_dev_ptr(d_room_keys, "int32", (n_rooms,), "room keys"),
-                       self._dev_ptr(d_slots, "int32", (n_table, SHARED_SLOTS), "slot table"), n_table,
+        t = SharedTick(*head, *self._p_tick_outputs(d_out_packets, d_out_packet_bytes, d_pcm16, B),
+                       *self._p_noise_flags(d_is_noise, d_is_comfort_noise, B),
+                       *self._p_selection(max_speakers, d_levels, d_is_speaker, B),
+                       *self._p_slot_table(d_room_keys, d_slots, n_rooms),
                        self._dev_ptr(d_enc_ids, "int32", (E,), "encoder stream ids") if E else None,
                        self._dev_ptr(d_enc_num_bits, "int32", (E,), "encoder num_bits") if E else None,
                        self._opt_dev_ptr(d_enc_dtx, "int32", (E,), "encoder dtx flags"),
@@ -1357,39 +1353,20 @@ class LyraHip:
         rooms; enc_ids / enc_bits / enc_dtx int32 [n_rooms][1 + max_speakers]: the encoder stream, bit count and DTX switch of
         every room's common row and slots.  The slot table is the context's, one row per label.  Up to two ticks in flight,
         bridge_begin's and speakers_begin's included."""
-        packets = _np(packets, np.uint8, (-1, MAX_PACKET_BYTES))
-        B = packets.shape[0]
-        sizes, labels = (_np(a, np.int32, (B,)) for a in (packet_bytes, rooms))
-        keys = _np(room_labels, np.int32, (-1,))
-        eids, ebits = (_np(a, np.int32, (-1,)) for a in (enc_ids, enc_bits))
-        m = None if muted is None else _np(np.asarray(muted) != 0, np.int32, (B,))
-        d = None if enc_dtx is None else _np(np.asarray(enc_dtx) != 0, np.int32, (-1,))
+        B, _alive, head = self._tick_begin_args(packets, packet_bytes, rooms, muted, flags, stream_ids)
+        keys, eids, ebits = (_np(a, np.int32, (-1,)) for a in (room_labels, enc_ids, enc_bits))
+        d = _np01(enc_dtx, (-1,))
         if 1 <= int(max_speakers) <= SPEAKERS_MAX:    # (anything else the library refuses before it reads an array)
             E = keys.size * (1 + int(max_speakers))
             if eids.size != E or ebits.size != E or (d is not None and d.size != E):
                 raise LyraHipError(f"shared_begin: enc_ids, enc_bits and enc_dtx take {keys.size} x (1 + {int(max_speakers)}) entries")
-        ids = self._ids(stream_ids, B)
-        self._chk(self.L.lyra_hip_shared_begin(self.h, ids.ctypes.data, B, packets.ctypes.data, sizes.ctypes.data,
-                                               labels.ctypes.data, None if m is None else m.ctypes.data, int(flags),
-                                               int(max_speakers), keys.ctypes.data, keys.size, eids.ctypes.data,
-                                               ebits.ctypes.data, None if d is None else d.ctypes.data))
-        self._pending_shared_ticks.append(B)
+        self._tick_begin("shared", self.L.lyra_hip_shared_begin, B, *head, int(max_speakers), keys.ctypes.data, keys.size,
+                         eids.ctypes.data, ebits.ctypes.data, None if d is None else d.ctypes.data)
 
     def shared_end(self):
         """-> (out_packets uint8 [B][23], out_packet_bytes, is_noise, is_comfort_noise int32 [B], levels int64 [B], is_speaker,
         slot_of int32 [B]) of the OLDEST tick in flight, which must be one begun by shared_begin."""
-        if not self._pending_shared_ticks:
-            self._chk(self.L.lyra_hip_shared_end(self.h, None, None, None, None, None, None, None))
-        B = self._pending_shared_ticks[0]
-        out = np.empty((B, MAX_PACKET_BYTES), np.uint8)
-        lens, noise, cn, spk, slot = (np.empty(B, np.int32) for _ in range(5))
-        levels = np.empty(B, np.int64)
-        rc = self.L.lyra_hip_shared_end(self.h, out.ctypes.data, lens.ctypes.data, noise.ctypes.data, cn.ctypes.data,
-                                        levels.ctypes.data, spk.ctypes.data, slot.ctypes.data)
-        self._chk_other_kind(rc)            # (refused: the oldest tick is of another kind; nothing was consumed)
-        self._pending_shared_ticks.pop(0)   # (otherwise the library gives the slot back whatever the wait returns)
-        self._chk(rc)
-        return out, lens, noise, cn, levels, spk, slot
+        return self._tick_end("shared", self.L.lyra_hip_shared_end, 5, True)
 
     def shared_reset_rooms(self, room_labels):
         """Drain the context and free the slot-table rows of these room labels (lyra_hip_shared_reset_rooms)."""

@@ -2149,9 +2149,9 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
 #include "decode_streams_api.inc"
 #include "decode_samples_any_api.inc"
 #include "decode_samples_streams_api.inc"
-#include "bridge_api.inc"
 #include "speakers_api.inc"
 #include "shared_bridge_api.inc"
+#include "bridge_api.inc"
 #include "stream_state_api.inc"
 #include "spans_api.inc"
 #include "spans_lossy_api.inc"

@@ -1,4 +1,7 @@
-// bridge_api.inc -- part of api.hip: the conference bridge (include/lyra_hip_bridge.h).
+// bridge_api.inc -- part of api.hip, behind speakers_api.inc and shared_bridge_api.inc (the mixes it dispatches to): the
+// conference bridge (include/lyra_hip_bridge.h) and the entry points of its three kinds of tick -- the full mix, the loudest-N
+// selection (include/lyra_hip_speakers.h) and the shared encoders (include/lyra_hip_shared_bridge.h).  Each of the mix call,
+// the tick, begin() and end() is one body for all three; where the arrays of a tick lie in the staging is bridge_staging.h.
 //   lyra_hip_bridge_mix_dev: bridge_mix_kernel alone (bridge_kernels.hip), a stateless encode-side call on se[0].
 //   lyra_hip_bridge_tick_dev: lossy_tick_launch (the decode leg, as lyra_hip_decode_lossy_mixed_dev at 16 kHz) -> the mix on
 //     se[0] -> lyra_hip_encode_streams_dev on the mix (every rate 16000, row b at 320 * b).  The one edge the composition adds:
@@ -9,57 +12,25 @@
 //     event only.
 #include "../../include/lyra_hip_bridge.h"
 #include "bridge_plan.h"
+#include "bridge_staging.h"
 
 static_assert(bridge::MAX_ROOM == LYRA_HIP_BRIDGE_MAX_ROOM, "the planner's bound is the header's");
+static_assert(bridge_staging::PACKET_BYTES == LYRA_HIP_MAX_PACKET_BYTES, "the staging's packet rows are the library's");
 
 namespace {
 
+using BrgKind = bridge_staging::Kind;
+
 struct BrgSlot {
-  uint8_t* h_in = nullptr;     // pinned: the int32 arrays going up (kBrgInArrays, below), then packets [B][23]
-  uint8_t* h_out = nullptr;    // pinned: [out_packet_bytes | is_noise | is_comfort_noise] int32, B each, then out packets [B][23]
-  uint8_t* d_in = nullptr;     // the same on the device (room for max_streams rows each)
+  uint8_t* h_in = nullptr;     // pinned: what goes up, as bridge_staging::layout(kind, B, E) says
+  uint8_t* h_out = nullptr;    // pinned: what comes down
+  uint8_t* d_in = nullptr;     // the same on the device (room for the largest tick of any kind: bridge_staging::slot_*_bytes)
   uint8_t* d_out = nullptr;
   hipEvent_t ev_done = nullptr;
   int B = 0;
-  int max_speakers = 0;        // 0: a full-mix tick (lyra_hip_bridge_begin); else a tick of lyra_hip_speakers_begin ...
-  bool shared = false;         // ... or, with this set, of lyra_hip_shared_begin (shared_bridge_api.inc)
+  BrgKind kind = bridge_staging::FULL;   // which begin() filled the slot
 };
 struct BrgHost { BrgSlot slot[2]; };
-
-// going up, int32 [n] each (room_start: n + 1): ids | packet_bytes | order | muted | num_bits | dtx | room_start
-constexpr size_t kBrgInArrays = 7;
-size_t brg_in_bytes(size_t n) { return (kBrgInArrays * n + 1) * 4 + n * LYRA_HIP_MAX_PACKET_BYTES; }
-size_t brg_out_bytes(size_t n) { return 3 * n * 4 + n * LYRA_HIP_MAX_PACKET_BYTES; }
-// a tick of lyra_hip_speakers_begin (speakers_api.inc) comes down through the same slots as
-// [out_packet_bytes | is_noise | is_comfort_noise | is_speaker] int32, levels int64, out packets: the slots have room for it
-constexpr size_t kSpkOutWords = 6;
-size_t spk_out_bytes(size_t n) { return kSpkOutWords * n * 4 + n * LYRA_HIP_MAX_PACKET_BYTES; }
-// speakers_api.inc: the scratch of the selection mix, and its three kernels on se[0]
-int spk_ensure(lyra_hip_ctx* c, int B);
-int spk_mix_launch(lyra_hip_ctx* c, const int16_t* d_pcm16, int B, const int32_t* d_order, const int32_t* d_room_start,
-                   int n_rooms, int n_members, const int32_t* d_muted, const int32_t* d_is_cn, int max_speakers, int16_t* d_mix,
-                   int64_t* d_levels, int32_t* d_is_speaker, int set);
-// shared_bridge_api.inc: what a shared-encoder tick has in place of the per-listener bit counts, DTX flags and mix; its
-// scratch; its mix on se[0] (levels, selection, slot update, the E encoder mixes); and its staging, which is the largest:
-// going up [ids | packet_bytes | order | muted | room_start | room_keys | enc_ids | enc_bits | enc_dtx], coming down
-// [out_packet_bytes | is_noise | is_comfort_noise | is_speaker] int32, levels int64, slot_of int32, out packets
-struct ShrTick {
-  const int32_t* d_room_keys;
-  int32_t* d_slots;
-  int n_table_rooms;
-  const int32_t *d_enc_stream_ids, *d_enc_num_bits, *d_enc_dtx;
-  int16_t* d_enc_mix;
-  uint8_t* d_enc_packets;
-  int32_t *d_enc_packet_bytes, *d_slot_of;
-};
-constexpr size_t kShrInArrays = 9, kShrOutWords = 7;
-size_t shr_in_bytes(size_t n) { return (kShrInArrays * n + 1) * 4 + n * LYRA_HIP_MAX_PACKET_BYTES; }
-size_t shr_out_bytes(size_t n) { return kShrOutWords * n * 4 + n * LYRA_HIP_MAX_PACKET_BYTES; }
-int shr_ensure(lyra_hip_ctx* c, int rows);
-int shr_mix_launch(lyra_hip_ctx* c, const int16_t* d_pcm16, const int32_t* d_stream_ids, int B, const int32_t* d_order,
-                   const int32_t* d_room_start, int n_rooms, int n_members, const int32_t* d_muted, const int32_t* d_is_cn,
-                   int max_speakers, const ShrTick& sh, int16_t* d_enc_mix, int64_t* d_levels, int32_t* d_is_speaker,
-                   int32_t* d_slot_of, int set);
 
 void brg_free(lyra_hip_ctx* c) {
   dfree(c->d_brg_mix[0], c->d_brg_mix[1], c->d_brg_flags[0], c->d_brg_flags[1], c->d_brg_const, c->d_bridge_err);
@@ -79,11 +50,11 @@ void brg_free(lyra_hip_ctx* c) {
 }
 
 int brg_slot_ensure(lyra_hip_ctx* c, BrgSlot* S) {
-  const size_t n = (size_t)c->max_streams;
-  if (!S->h_in) HIPCHK(c, hipHostMalloc((void**)&S->h_in, shr_in_bytes(n), hipHostMallocDefault));
-  if (!S->h_out) HIPCHK(c, hipHostMalloc((void**)&S->h_out, shr_out_bytes(n), hipHostMallocDefault));
-  if (!S->d_in) HIPCHK(c, dalloc(&S->d_in, shr_in_bytes(n)));
-  if (!S->d_out) HIPCHK(c, dalloc(&S->d_out, shr_out_bytes(n)));
+  const size_t in = bridge_staging::slot_in_bytes((size_t)c->max_streams), out = bridge_staging::slot_out_bytes((size_t)c->max_streams);
+  if (!S->h_in) HIPCHK(c, hipHostMalloc((void**)&S->h_in, in, hipHostMallocDefault));
+  if (!S->h_out) HIPCHK(c, hipHostMalloc((void**)&S->h_out, out, hipHostMallocDefault));
+  if (!S->d_in) HIPCHK(c, dalloc(&S->d_in, in));
+  if (!S->d_out) HIPCHK(c, dalloc(&S->d_out, out));
   if (!S->ev_done) HIPCHK(c, hipEventCreateWithFlags(&S->ev_done, hipEventDisableTiming));
   return 0;
 }
@@ -130,8 +101,14 @@ int brg_ensure(lyra_hip_ctx* c, int B) {
 
 bool brg_misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
-int shr_encode_fanout(lyra_hip_ctx* c, const lyra_hip_bridge_tick* T, int max_speakers, int E, const ShrTick& sh,
-                      const int16_t* enc_mix, const int32_t* slot_of, int set);
+// the buffer checks of every mix call, the pass over spans (bridge_spans_api.inc) included; `mix_name`: d_mix or d_enc_mix
+int brg_check_buffers(lyra_hip_ctx* c, const char* what, const int16_t* d_pcm16, const int16_t* d_mix, const char* mix_name,
+                      const int64_t* d_levels) {
+  if (brg_misaligned(d_pcm16) || brg_misaligned(d_mix) || d_pcm16 == d_mix)
+    return fail(c, LYRA_HIP_EINVAL, "%s: d_pcm16 and %s must be 16-byte aligned and distinct", what, mix_name);
+  if ((reinterpret_cast<uintptr_t>(d_levels) & 7u) != 0) return fail(c, LYRA_HIP_EINVAL, "%s: d_levels must be 8-byte aligned", what);
+  return 0;
+}
 
 int brg_check_index(lyra_hip_ctx* c, const char* what, int B, const int32_t* d_order, const int32_t* d_room_start, int n_rooms,
                     int n_members) {
@@ -151,6 +128,55 @@ int brg_mix_launch(lyra_hip_ctx* c, const int16_t* d_pcm16, int B, const int32_t
     HIPCHK(c, hipGetLastError());
   }
   return 0;
+}
+
+// A mix of any kind, as the three mix calls and the tick hand it over.  max_speakers 0: the full mix; 1 .. 8: the selection
+// (speakers_api.inc) with d_levels and d_is_speaker; with `sh`, the shared encoders' (shared_bridge_api.inc), whose d_mix is
+// the encoder rows' and which reads d_stream_ids and writes d_slot_of.
+struct BrgMix {
+  const int16_t* d_pcm16;
+  const int32_t* d_stream_ids;
+  int B;
+  const int32_t *d_order, *d_room_start;
+  int n_rooms, n_members;
+  const int32_t *d_muted, *d_is_cn;
+  int max_speakers;
+  const ShrTick* sh;
+  int16_t* d_mix;
+  int64_t* d_levels;
+  int32_t *d_is_speaker, *d_slot_of;
+};
+
+// the kernels of the mix on se[0]; the scratch of its kind has been ensured
+int brg_mix_any(lyra_hip_ctx* c, const BrgMix& M, int set) {
+  if (M.sh)
+    return shr_mix_launch(c, M.d_pcm16, M.d_stream_ids, M.B, M.d_order, M.d_room_start, M.n_rooms, M.n_members, M.d_muted, M.d_is_cn,
+                          M.max_speakers, *M.sh, M.d_mix, M.d_levels, M.d_is_speaker,
+                          M.d_slot_of ? M.d_slot_of : c->d_shr_slot_of[set], set);
+  if (M.max_speakers)
+    return spk_mix_launch(c, M.d_pcm16, M.B, M.d_order, M.d_room_start, M.n_rooms, M.n_members, M.d_muted, M.d_is_cn,
+                          M.max_speakers, M.d_mix, M.d_levels, M.d_is_speaker, set);
+  return brg_mix_launch(c, M.d_pcm16, M.B, M.d_order, M.d_room_start, M.n_rooms, M.n_members, M.d_muted, M.d_is_cn, M.d_mix);
+}
+
+// The mix alone, a stateless encode-side call on se[0]: lyra_hip_bridge_mix_dev (`select` false), lyra_hip_speakers_mix_dev
+// and, with M.sh, lyra_hip_shared_mix_dev.
+int brg_mix_call(lyra_hip_ctx* c, const char* what, const BrgMix& M, bool select) {
+  int rc = check_batch(c, M.B);
+  if (rc) return rc;
+  if (!M.d_pcm16 || !M.d_mix || (M.sh && (!M.d_stream_ids || !M.sh->d_slots))) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
+  if ((rc = brg_check_index(c, what, M.B, M.d_order, M.d_room_start, M.n_rooms, M.n_members))) return rc;
+  if ((rc = brg_check_buffers(c, what, M.d_pcm16, M.d_mix, M.sh ? "d_enc_mix" : "d_mix", M.d_levels))) return rc;
+  if (select && (rc = spk_check_n(c, what, M.max_speakers))) return rc;
+  if (M.sh && M.sh->n_table_rooms < 1) return fail(c, LYRA_HIP_EINVAL, "%s: n_table_rooms %d", what, M.sh->n_table_rooms);
+  DEVSCOPE(c);
+  if ((rc = brg_ensure_mix(c))) return rc;
+  if (select && (rc = spk_ensure(c, M.B))) return rc;
+  if (M.sh && (rc = shr_ensure(c, M.B))) return rc;   // (the encoder mixes are the caller's: the scratch is sized by B alone)
+  if ((rc = enc_side_begin(c, 0))) return rc;
+  rc = brg_mix_any(c, M, (int)(c->n_lossy_calls & 1));
+  if (!rc) rc = enc_side_done(c, 0);
+  return rc;
 }
 
 // begin() of every kind of tick: two ticks deep, no pipelined request of any other kind in flight (the tick runs on both sides'
@@ -214,13 +240,9 @@ int brg_tick_impl(lyra_hip_ctx* c, const char* what, const lyra_hip_bridge_tick*
   if ((rc = enc_cross_begin(c, 0, 1))) return rc;
   HIPCHK(c, hipStreamWaitEvent(c->se[0], c->ev_brg_mix, 0));
   int32_t* slot_of = sh ? (sh->d_slot_of ? sh->d_slot_of : c->d_shr_slot_of[set]) : nullptr;
-  rc = sh ? shr_mix_launch(c, pcm16, T->d_stream_ids, B, T->d_order, T->d_room_start, T->n_rooms, T->n_members, T->d_muted,
-                           skip_cn ? is_cn : nullptr, max_speakers, *sh, mix, d_levels, d_is_speaker, slot_of, set)
-       : max_speakers ? spk_mix_launch(c, pcm16, B, T->d_order, T->d_room_start, T->n_rooms, T->n_members, T->d_muted,
-                                     skip_cn ? is_cn : nullptr, max_speakers, mix, d_levels, d_is_speaker, set)
-                    : brg_mix_launch(c, pcm16, B, T->d_order, T->d_room_start, T->n_rooms, T->n_members, T->d_muted,
-                                     skip_cn ? is_cn : nullptr, mix);
-  if (rc) return rc;
+  const BrgMix M = {pcm16, T->d_stream_ids, B, T->d_order, T->d_room_start, T->n_rooms, T->n_members, T->d_muted,
+                    skip_cn ? is_cn : nullptr, max_speakers, sh, mix, d_levels, d_is_speaker, slot_of};
+  if ((rc = brg_mix_any(c, M, set))) return rc;
   // ---- encode leg ----
   const int32_t* rates16 = c->d_brg_const;
   if (sh) return shr_encode_fanout(c, T, max_speakers, E, *sh, mix, slot_of, set);
@@ -228,17 +250,38 @@ int brg_tick_impl(lyra_hip_ctx* c, const char* what, const lyra_hip_bridge_tick*
                                      T->d_dtx, T->d_out_packets, T->d_out_packet_bytes);
 }
 
-// begin() of both kinds of tick (max_speakers as in brg_tick_impl): one validation, one staging, one upload, one download
+// what lyra_hip_shared_begin has in place of num_bits and dtx: the labels of the rooms present and their encoder rows
+struct ShrBegin {
+  const int32_t* room_labels;
+  int n_rooms;
+  const int32_t *enc_ids, *enc_bits, *enc_dtx;
+};
+
+// begin() of every kind of tick (max_speakers as in brg_tick_impl; `sb`: a shared-encoder tick): one validation, one staging,
+// one upload, one download
 int brg_begin_impl(lyra_hip_ctx* c, const char* what, const int32_t* ids, int B, const uint8_t* packets,
                    const int32_t* packet_bytes, const int32_t* rooms, const int32_t* muted, unsigned flags,
-                   const int32_t* num_bits, const int32_t* dtx, int max_speakers) {
+                   const int32_t* num_bits, const int32_t* dtx, int max_speakers, const ShrBegin* sb = nullptr) {
   int rc = check_batch(c, B);
   if (rc) return rc;
-  if (!packets || !packet_bytes || !rooms || !num_bits) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
+  if (!packets || !packet_bytes || !rooms ||
+      (sb ? sb->n_rooms > 0 && (!sb->room_labels || !sb->enc_ids || !sb->enc_bits) : !num_bits))
+    return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
   if (flags & ~LYRA_HIP_BRIDGE_SKIP_COMFORT_NOISE) return fail(c, LYRA_HIP_EINVAL, "%s: unknown flags 0x%x", what, flags);
+  int E = 0;
+  if (sb) {   // the encoder rows: their count, and their ids in front of the participants'
+    if (sb->n_rooms < 0 || sb->n_rooms > B) return fail(c, LYRA_HIP_EINVAL, "%s: n_rooms %d outside 0..B (%d)", what, sb->n_rooms, B);
+    E = sb->n_rooms * (1 + max_speakers);
+    if (E > c->max_streams)
+      return fail(c, LYRA_HIP_EINVAL, "%s: %d rooms x (1 + %d) encoder rows exceed max_streams (%d): use the loudest-N tick", what,
+                  sb->n_rooms, max_speakers, c->max_streams);
+    if (E > 0 && (rc = check_ids_host(c, sb->enc_ids, E))) return rc;
+  }
   if ((rc = check_ids_host(c, ids, B))) return rc;
+  for (int e = 0; e < E; ++e)
+    if ((rc = check_bits(c, sb->enc_bits[e]))) return rc;
   for (int b = 0; b < B; ++b) {
-    if ((rc = check_bits(c, num_bits[b]))) return rc;
+    if (!sb && (rc = check_bits(c, num_bits[b]))) return rc;
     const int pb = packet_bytes[b];   // PacketSizeToNumQuantizedBits (lyra_config.h:99-106), 0: no packet on this tick
     if (pb != 0 && pb != 8 && pb != 15 && pb != LYRA_HIP_MAX_PACKET_BYTES)
       return fail(c, LYRA_HIP_EINVAL, "%s: packet of %d bytes at position %d (0, 8, 15 or 23)", what, pb, b);
@@ -250,67 +293,154 @@ int brg_begin_impl(lyra_hip_ctx* c, const char* what, const int32_t* ids, int B,
   if ((rc = brg_slot_ensure(c, &S))) return rc;
   // (the slot's previous user, two ticks back, has ended: its kernels on every stream have read d_in, its download has left
   // d_out and h_out)
-  const size_t n = (size_t)B;
+  const BrgKind kind = sb ? bridge_staging::SHARED : max_speakers ? bridge_staging::SPEAKERS : bridge_staging::FULL;
+  const bridge_staging::Layout L = bridge_staging::layout(kind, (size_t)B, (size_t)E);
   int32_t* h = reinterpret_cast<int32_t*>(S.h_in);
   int n_rooms = 0, n_members = 0;
-  if (bridge::plan(rooms, B, h + 2 * n, h + 6 * n, &n_rooms, &n_members))
+  if (bridge::plan(rooms, B, h + L.order, h + L.room_start, &n_rooms, &n_members))
     return fail(c, LYRA_HIP_EINVAL, "%s: a room of more than %d members", what, LYRA_HIP_BRIDGE_MAX_ROOM);
+  int at = -1;
+  if (const int bad = sb ? shared_bridge::check_labels(rooms, h + L.order, h + L.room_start, n_rooms, sb->room_labels, sb->n_rooms,
+                                                       c->max_streams, &at)
+                         : 0)
+    return fail(c, LYRA_HIP_EINVAL, "%s: room_labels (%d given, %d rooms present; position %d, code %d) must be the labels "
+                "present in rooms, strictly ascending and below max_streams (%d)", what, sb->n_rooms, n_rooms, at, bad, c->max_streams);
   // everything the tick allocates or builds on first use, BEFORE anything is enqueued: a failure here leaves the streams idle
-  if ((rc = ensure_scratch(c, B))) return rc;
+  if ((rc = ensure_scratch(c, std::max(B, E)))) return rc;
   if ((rc = rates_ensure(c))) return rc;
   if ((rc = lossy_ensure(c, B))) return rc;
   if ((rc = dstr16_ensure(c, B))) return rc;
   if ((rc = brg_ensure(c, B))) return rc;
   if (max_speakers && (rc = spk_ensure(c, B))) return rc;
-  for (int b = 0; b < B; ++b) {
-    h[b] = ids[b];
-    h[n + b] = packet_bytes[b];
-    h[3 * n + b] = muted ? (muted[b] != 0) : 0;
-    h[4 * n + b] = num_bits[b];
-    h[5 * n + b] = dtx ? (dtx[b] != 0) : 0;
+  if (sb) {
+    if ((rc = shr_ensure(c, std::max(B, E)))) return rc;
+    if (!c->d_shr_table) {   // one row per label below max_streams, all free
+      HIPCHK(c, dalloc(&c->d_shr_table, (size_t)c->max_streams * LYRA_HIP_SHARED_SLOTS));
+      HIPCHK(c, hipMemset(c->d_shr_table, 0xFF, (size_t)c->max_streams * LYRA_HIP_SHARED_SLOTS * 4));
+    }
   }
-  std::memcpy(S.h_in + (kBrgInArrays * n + 1) * 4, packets, n * LYRA_HIP_MAX_PACKET_BYTES);
+  for (int b = 0; b < B; ++b) {
+    h[L.ids + b] = ids[b];
+    h[L.packet_bytes + b] = packet_bytes[b];
+    h[L.muted + b] = muted ? (muted[b] != 0) : 0;
+    if (sb) continue;
+    h[L.num_bits + b] = num_bits[b];
+    h[L.dtx + b] = dtx ? (dtx[b] != 0) : 0;
+  }
+  for (int r = 0; sb && r < n_rooms; ++r) h[L.room_keys + r] = sb->room_labels[r];
+  for (int e = 0; e < E; ++e) {
+    h[L.enc_ids + e] = sb->enc_ids[e];
+    h[L.enc_bits + e] = sb->enc_bits[e];
+    h[L.enc_dtx + e] = sb->enc_dtx ? (sb->enc_dtx[e] != 0) : 0;
+  }
+  std::memcpy(S.h_in + L.in_packets * 4, packets, (size_t)B * LYRA_HIP_MAX_PACKET_BYTES);
   // one upload from pinned staging on the decode-side stream, in front of the tick's first kernel.  The encode leg reads ids,
   // bits and DTX flags on se[0] / sq[0]: both are behind the tick's edge, which is behind the decode-side half and so the copy.
-  HIPCHK(c, hipMemcpyAsync(S.d_in, S.h_in, brg_in_bytes(n), hipMemcpyHostToDevice, c->sd[0]));
+  HIPCHK(c, hipMemcpyAsync(S.d_in, S.h_in, L.in_bytes, hipMemcpyHostToDevice, c->sd[0]));
   const int32_t* m = reinterpret_cast<const int32_t*>(S.d_in);
   int32_t* o = reinterpret_cast<int32_t*>(S.d_out);
-  const size_t out_words = max_speakers ? kSpkOutWords : 3;
-  uint8_t* out_pk = S.d_out + out_words * n * 4;
+  uint8_t* out_pk = S.d_out + L.out_packets * 4;
   // empty packets, and the bytes behind a shorter one, read back as zeros; the extractor's stream is ahead of the quantizer's
-  HIPCHK(c, hipMemsetAsync(out_pk, 0, n * LYRA_HIP_MAX_PACKET_BYTES, c->se[0]));
+  // (a shared-encoder tick's fan-out writes every byte of them)
+  if (!sb) HIPCHK(c, hipMemsetAsync(out_pk, 0, (size_t)B * LYRA_HIP_MAX_PACKET_BYTES, c->se[0]));
   lyra_hip_bridge_tick T = {};
-  T.d_stream_ids = m;
+  T.d_stream_ids = m + L.ids;
   T.B = B;
-  T.d_packets = S.d_in + (kBrgInArrays * n + 1) * 4;
-  T.d_packet_bytes = m + n;
-  T.d_order = m + 2 * n;
-  T.d_room_start = m + 6 * n;
+  T.d_packets = S.d_in + L.in_packets * 4;
+  T.d_packet_bytes = m + L.packet_bytes;
+  T.d_order = m + L.order;
+  T.d_room_start = m + L.room_start;
   T.n_rooms = n_rooms;
   T.n_members = n_members;
-  T.d_muted = muted ? m + 3 * n : nullptr;
+  T.d_muted = muted ? m + L.muted : nullptr;
   T.flags = flags;
-  T.d_num_bits = m + 4 * n;
-  T.d_dtx = dtx ? m + 5 * n : nullptr;
+  T.d_num_bits = sb ? nullptr : m + L.num_bits;
+  T.d_dtx = dtx ? m + L.dtx : nullptr;
   T.d_out_packets = out_pk;
-  T.d_out_packet_bytes = o;
-  T.d_is_noise = o + n;
-  T.d_is_comfort_noise = o + 2 * n;
-  // (a selection tick: is_speaker behind the three int32 arrays, then the levels, 8-byte aligned at 16 * n bytes)
-  if ((rc = brg_tick_impl(c, what, &T, max_speakers, max_speakers ? reinterpret_cast<int64_t*>(o + 4 * n) : nullptr,
-                          max_speakers ? o + 3 * n : nullptr)))
+  T.d_out_packet_bytes = o + L.out_packet_bytes;
+  T.d_is_noise = o + L.is_noise;
+  T.d_is_comfort_noise = o + L.is_comfort_noise;
+  ShrTick sh = {};
+  if (sb) {
+    sh.d_room_keys = m + L.room_keys;
+    sh.d_slots = c->d_shr_table;
+    sh.n_table_rooms = c->max_streams;
+    sh.d_enc_stream_ids = m + L.enc_ids;
+    sh.d_enc_num_bits = m + L.enc_bits;
+    sh.d_enc_dtx = sb->enc_dtx ? m + L.enc_dtx : nullptr;
+    sh.d_slot_of = o + L.slot_of;
+  }
+  if ((rc = brg_tick_impl(c, what, &T, max_speakers, max_speakers ? reinterpret_cast<int64_t*>(o + L.levels) : nullptr,
+                          max_speakers ? o + L.is_speaker : nullptr, sb ? &sh : nullptr)))
     return rc;
-  // packets and sizes are written by the quantizer on sq[0], the flags by the noise-stream half: the one download rides on
-  // sq[0] behind the end of that half (the quantizer itself is already enqueued and does not wait for it).  The levels and
-  // speaker flags of a selection tick are written on se[0] by the mix's kernels: the quantizer on sq[0] waits for the
-  // extractor's event on se[0] (encq_handoff, api.hip), which is enqueued behind them, so sq[0] is behind them as well.
+  // packets and sizes are written by the quantizer on sq[0] (a shared-encoder tick: by the fan-out behind it), the flags by the
+  // noise-stream half: the one download rides on sq[0] behind the end of that half (the quantizer itself is already enqueued and
+  // does not wait for it).  The levels, speaker flags and slot_of of a selection tick are written on se[0] by the mix's kernels:
+  // the quantizer on sq[0] waits for the extractor's event on se[0] (encq_handoff, api.hip), which is enqueued behind them, so
+  // sq[0] is behind them as well.  A shared-encoder tick without rooms has no quantizer and ends on se[0] instead.
   HIPCHK(c, hipStreamWaitEvent(c->sq[0], c->ev_noise[(c->n_noise_calls - 1) & 1], 0));
-  HIPCHK(c, hipMemcpyAsync(S.h_out, S.d_out, out_words * n * 4 + n * LYRA_HIP_MAX_PACKET_BYTES, hipMemcpyDeviceToHost, c->sq[0]));
+  if (sb && E == 0) HIPCHK(c, hipStreamWaitEvent(c->sq[0], c->ev_encs[2][0], 0));
+  HIPCHK(c, hipMemcpyAsync(S.h_out, S.d_out, L.out_bytes, hipMemcpyDeviceToHost, c->sq[0]));
   HIPCHK(c, hipEventRecord(S.ev_done, c->sq[0]));
   S.B = B;
-  S.max_speakers = max_speakers;
-  S.shared = false;
+  S.kind = kind;
   c->pl_begun[PL_BRIDGE]++;
+  return 0;
+}
+
+// end() of every kind of tick: `kind` is the caller's, and the optional outputs are those its kind of tick has
+int brg_end_impl(lyra_hip_ctx* c, const char* what, BrgKind kind, uint8_t* out_packets, int32_t* out_packet_bytes, int32_t* is_noise,
+                 int32_t* is_comfort_noise, int64_t* levels = nullptr, int32_t* is_speaker = nullptr, int32_t* slot_of = nullptr) {
+  if (!c->brg_host || c->pl_ended[PL_BRIDGE] == c->pl_begun[PL_BRIDGE]) return fail(c, LYRA_HIP_EINVAL, "%s: no tick in flight", what);
+  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->pl_ended[PL_BRIDGE] & 1];
+  static const char* const begun_by[] = {"the full-mix begin()", "lyra_hip_speakers_begin", "lyra_hip_shared_begin"};
+  if (S.kind != kind) return fail(c, LYRA_HIP_EINVAL, "%s: the oldest tick was begun by %s", what, begun_by[S.kind]);
+  if (!out_packets || !out_packet_bytes) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
+  DEVSCOPE(c);
+  c->pl_ended[PL_BRIDGE]++;                  // whatever happens below, the slot is given back
+  HIPCHK(c, hipEventSynchronize(S.ev_done));
+  const size_t n = (size_t)S.B;
+  const bridge_staging::Layout L = bridge_staging::layout(kind, n, 0);   // (what comes down does not depend on E)
+  const int32_t* o = reinterpret_cast<const int32_t*>(S.h_out);
+  std::memcpy(out_packet_bytes, o + L.out_packet_bytes, n * 4);
+  if (is_noise) std::memcpy(is_noise, o + L.is_noise, n * 4);
+  if (is_comfort_noise) std::memcpy(is_comfort_noise, o + L.is_comfort_noise, n * 4);
+  if (is_speaker) std::memcpy(is_speaker, o + L.is_speaker, n * 4);
+  if (levels) std::memcpy(levels, o + L.levels, n * 8);
+  if (slot_of) std::memcpy(slot_of, o + L.slot_of, n * 4);
+  std::memcpy(out_packets, o + L.out_packets, n * LYRA_HIP_MAX_PACKET_BYTES);
+  return 0;
+}
+
+// the fields the three public tick structs have in common (they are separate types, with the same names)
+template <class Tick>
+lyra_hip_bridge_tick brg_common_fields(const Tick& S) {
+  lyra_hip_bridge_tick T = {};
+  T.d_stream_ids = S.d_stream_ids;
+  T.B = S.B;
+  T.d_packets = S.d_packets;
+  T.d_packet_bytes = S.d_packet_bytes;
+  T.d_order = S.d_order;
+  T.d_room_start = S.d_room_start;
+  T.n_rooms = S.n_rooms;
+  T.n_members = S.n_members;
+  T.d_muted = S.d_muted;
+  T.flags = S.flags;
+  T.d_out_packets = S.d_out_packets;
+  T.d_out_packet_bytes = S.d_out_packet_bytes;
+  T.d_pcm16 = S.d_pcm16;
+  T.d_is_noise = S.d_is_noise;
+  T.d_is_comfort_noise = S.d_is_comfort_noise;
+  return T;
+}
+
+// the refusals of a selection tick's struct, in front of brg_tick_impl's
+template <class Tick>
+int brg_check_selection(lyra_hip_ctx* c, const char* what, const Tick* S) {
+  if (!S) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
+  const int rc = spk_check_n(c, what, S->max_speakers);
+  if (rc) return rc;
+  if ((reinterpret_cast<uintptr_t>(S->d_levels) & 7u) != 0) return fail(c, LYRA_HIP_EINVAL, "%s: d_levels must be 8-byte aligned", what);
   return 0;
 }
 
@@ -322,28 +452,67 @@ int lyra_hip_bridge_plan(const int32_t* rooms, int B, int32_t* order, int32_t* r
   return bridge::plan(rooms, B, order, room_start, n_rooms, n_members) ? LYRA_HIP_EINVAL : 0;
 }
 
+// ---- the mix alone ----
+
 int lyra_hip_bridge_mix_dev(lyra_hip_ctx* c, const int16_t* d_pcm16, int B, const int32_t* d_order, const int32_t* d_room_start,
                             int n_rooms, int n_members, const int32_t* d_muted, const int32_t* d_is_comfort_noise,
                             int16_t* d_mix) {
-  int rc = check_batch(c, B);
-  if (rc) return rc;
-  if (!d_pcm16 || !d_mix) return fail(c, LYRA_HIP_EINVAL, "bridge_mix: null pointer");
-  if ((rc = brg_check_index(c, "bridge_mix", B, d_order, d_room_start, n_rooms, n_members))) return rc;
-  if (brg_misaligned(d_pcm16) || brg_misaligned(d_mix) || d_pcm16 == d_mix)
-    return fail(c, LYRA_HIP_EINVAL, "bridge_mix: d_pcm16 and d_mix must be 16-byte aligned and distinct");
-  DEVSCOPE(c);
-  if ((rc = brg_ensure_mix(c))) return rc;
-  if ((rc = enc_side_begin(c, 0))) return rc;
-  rc = brg_mix_launch(c, d_pcm16, B, d_order, d_room_start, n_rooms, n_members, d_muted, d_is_comfort_noise, d_mix);
-  if (!rc) rc = enc_side_done(c, 0);
-  return rc;
+  const BrgMix M = {d_pcm16, nullptr, B, d_order, d_room_start, n_rooms, n_members, d_muted, d_is_comfort_noise, 0, nullptr, d_mix,
+                    nullptr, nullptr, nullptr};
+  return brg_mix_call(c, "bridge_mix", M, false);
 }
+
+int lyra_hip_speakers_mix_dev(lyra_hip_ctx* c, const int16_t* d_pcm16, int B, const int32_t* d_order, const int32_t* d_room_start,
+                              int n_rooms, int n_members, const int32_t* d_muted, const int32_t* d_is_comfort_noise,
+                              int max_speakers, int16_t* d_mix, int64_t* d_levels, int32_t* d_is_speaker) {
+  const BrgMix M = {d_pcm16, nullptr, B, d_order, d_room_start, n_rooms, n_members, d_muted, d_is_comfort_noise, max_speakers,
+                    nullptr, d_mix, d_levels, d_is_speaker, nullptr};
+  return brg_mix_call(c, "speakers_mix", M, true);
+}
+
+int lyra_hip_shared_mix_dev(lyra_hip_ctx* c, const int16_t* d_pcm16, const int32_t* d_stream_ids, int B, const int32_t* d_order,
+                            const int32_t* d_room_start, int n_rooms, int n_members, const int32_t* d_muted,
+                            const int32_t* d_is_comfort_noise, int max_speakers, const int32_t* d_room_keys, int32_t* d_slots,
+                            int n_table_rooms, int16_t* d_enc_mix, int64_t* d_levels, int32_t* d_is_speaker, int32_t* d_slot_of) {
+  ShrTick sh = {};
+  sh.d_room_keys = d_room_keys;
+  sh.d_slots = d_slots;
+  sh.n_table_rooms = n_table_rooms;
+  const BrgMix M = {d_pcm16, d_stream_ids, B, d_order, d_room_start, n_rooms, n_members, d_muted, d_is_comfort_noise, max_speakers,
+                    &sh, d_enc_mix, d_levels, d_is_speaker, d_slot_of};
+  return brg_mix_call(c, "shared_mix", M, true);
+}
+
+// ---- one tick on device buffers ----
 
 int lyra_hip_bridge_tick_dev(lyra_hip_ctx* c, const lyra_hip_bridge_tick* T) {
   if (!c) return LYRA_HIP_EINVAL;
   if (!T) return fail(c, LYRA_HIP_EINVAL, "bridge_tick: null pointer");
   return brg_tick_impl(c, "bridge_tick", T, 0, nullptr, nullptr);
 }
+
+int lyra_hip_speakers_tick_dev(lyra_hip_ctx* c, const lyra_hip_speakers_tick* S) {
+  if (!c) return LYRA_HIP_EINVAL;
+  const int rc = brg_check_selection(c, "speakers_tick", S);
+  if (rc) return rc;
+  lyra_hip_bridge_tick T = brg_common_fields(*S);
+  T.d_num_bits = S->d_num_bits;
+  T.d_dtx = S->d_dtx;
+  T.d_mix = S->d_mix;
+  return brg_tick_impl(c, "speakers_tick", &T, S->max_speakers, S->d_levels, S->d_is_speaker);
+}
+
+int lyra_hip_shared_tick_dev(lyra_hip_ctx* c, const lyra_hip_shared_tick* S) {
+  if (!c) return LYRA_HIP_EINVAL;
+  const int rc = brg_check_selection(c, "shared_tick", S);
+  if (rc) return rc;
+  const lyra_hip_bridge_tick T = brg_common_fields(*S);
+  const ShrTick sh = {S->d_room_keys, S->d_slots, S->n_table_rooms, S->d_enc_stream_ids, S->d_enc_num_bits, S->d_enc_dtx,
+                      S->d_enc_mix, S->d_enc_packets, S->d_enc_packet_bytes, S->d_slot_of};
+  return brg_tick_impl(c, "shared_tick", &T, S->max_speakers, S->d_levels, S->d_is_speaker, &sh);
+}
+
+// ---- the two-deep host-buffer form ----
 
 int lyra_hip_bridge_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const uint8_t* packets, const int32_t* packet_bytes,
                           const int32_t* rooms, const int32_t* muted, unsigned flags, const int32_t* num_bits,
@@ -352,23 +521,43 @@ int lyra_hip_bridge_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const uint
   return brg_begin_impl(c, "bridge_begin", ids, B, packets, packet_bytes, rooms, muted, flags, num_bits, dtx, 0);
 }
 
+int lyra_hip_speakers_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const uint8_t* packets, const int32_t* packet_bytes,
+                            const int32_t* rooms, const int32_t* muted, unsigned flags, const int32_t* num_bits,
+                            const int32_t* dtx, int max_speakers) {
+  if (!c) return LYRA_HIP_EINVAL;
+  int rc = spk_check_n(c, "speakers_begin", max_speakers);
+  if (rc) return rc;
+  return brg_begin_impl(c, "speakers_begin", ids, B, packets, packet_bytes, rooms, muted, flags, num_bits, dtx, max_speakers);
+}
+
+int lyra_hip_shared_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const uint8_t* packets, const int32_t* packet_bytes,
+                          const int32_t* rooms, const int32_t* muted, unsigned flags, int max_speakers, const int32_t* room_labels,
+                          int n_rooms, const int32_t* enc_ids, const int32_t* enc_bits, const int32_t* enc_dtx) {
+  if (!c) return LYRA_HIP_EINVAL;
+  int rc = spk_check_n(c, "shared_begin", max_speakers);
+  if (rc) return rc;
+  const ShrBegin sb = {room_labels, n_rooms, enc_ids, enc_bits, enc_dtx};
+  return brg_begin_impl(c, "shared_begin", ids, B, packets, packet_bytes, rooms, muted, flags, nullptr, nullptr, max_speakers, &sb);
+}
+
 int lyra_hip_bridge_end(lyra_hip_ctx* c, uint8_t* out_packets, int32_t* out_packet_bytes, int32_t* is_noise,
                         int32_t* is_comfort_noise) {
   if (!c) return LYRA_HIP_EINVAL;
-  if (!c->brg_host || c->pl_ended[PL_BRIDGE] == c->pl_begun[PL_BRIDGE]) return fail(c, LYRA_HIP_EINVAL, "bridge_end: no tick in flight");
-  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->pl_ended[PL_BRIDGE] & 1];
-  if (S.max_speakers)
-    return fail(c, LYRA_HIP_EINVAL, "bridge_end: the oldest tick was begun by lyra_hip_%s_begin", S.shared ? "shared" : "speakers");
-  if (!out_packets || !out_packet_bytes) return fail(c, LYRA_HIP_EINVAL, "bridge_end: null pointer");
-  DEVSCOPE(c);
-  c->pl_ended[PL_BRIDGE]++;                  // whatever happens below, the slot is given back
-  HIPCHK(c, hipEventSynchronize(S.ev_done));
-  const size_t n = (size_t)S.B;
-  std::memcpy(out_packet_bytes, S.h_out, n * 4);
-  if (is_noise) std::memcpy(is_noise, S.h_out + n * 4, n * 4);
-  if (is_comfort_noise) std::memcpy(is_comfort_noise, S.h_out + 2 * n * 4, n * 4);
-  std::memcpy(out_packets, S.h_out + 3 * n * 4, n * LYRA_HIP_MAX_PACKET_BYTES);
-  return 0;
+  return brg_end_impl(c, "bridge_end", bridge_staging::FULL, out_packets, out_packet_bytes, is_noise, is_comfort_noise);
+}
+
+int lyra_hip_speakers_end(lyra_hip_ctx* c, uint8_t* out_packets, int32_t* out_packet_bytes, int32_t* is_noise,
+                          int32_t* is_comfort_noise, int64_t* levels, int32_t* is_speaker) {
+  if (!c) return LYRA_HIP_EINVAL;
+  return brg_end_impl(c, "speakers_end", bridge_staging::SPEAKERS, out_packets, out_packet_bytes, is_noise, is_comfort_noise, levels,
+                      is_speaker);
+}
+
+int lyra_hip_shared_end(lyra_hip_ctx* c, uint8_t* out_packets, int32_t* out_packet_bytes, int32_t* is_noise,
+                        int32_t* is_comfort_noise, int64_t* levels, int32_t* is_speaker, int32_t* slot_of) {
+  if (!c) return LYRA_HIP_EINVAL;
+  return brg_end_impl(c, "shared_end", bridge_staging::SHARED, out_packets, out_packet_bytes, is_noise, is_comfort_noise, levels,
+                      is_speaker, slot_of);
 }
 
 long lyra_hip_bridge_errors(lyra_hip_ctx* c, int clear) {

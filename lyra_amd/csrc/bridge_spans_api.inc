@@ -87,13 +87,11 @@ int bsp_plan_checked(lyra_hip_ctx* c, const char* what, const lyra_hip_span* spa
   return 0;
 }
 
-// the buffer checks the pass shares with the ticks' mix calls
+// the buffer checks the pass shares with the ticks' mix calls (brg_check_buffers, bridge_api.inc), and its own range of N
 int bsp_check_buffers(lyra_hip_ctx* c, const char* what, const int16_t* d_pcm16, const int16_t* d_mix, const int64_t* d_levels,
                       int max_speakers) {
   if (!d_pcm16 || !d_mix) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
-  if (brg_misaligned(d_pcm16) || brg_misaligned(d_mix) || d_pcm16 == d_mix)
-    return fail(c, LYRA_HIP_EINVAL, "%s: d_pcm16 and d_mix must be 16-byte aligned and distinct", what);
-  if ((reinterpret_cast<uintptr_t>(d_levels) & 7u) != 0) return fail(c, LYRA_HIP_EINVAL, "%s: d_levels must be 8-byte aligned", what);
+  if (const int rc = brg_check_buffers(c, what, d_pcm16, d_mix, "d_mix", d_levels)) return rc;
   if (max_speakers < 0 || max_speakers > LYRA_HIP_SPEAKERS_MAX)
     return fail(c, LYRA_HIP_EINVAL, "%s: max_speakers %d outside 0..%d", what, max_speakers, LYRA_HIP_SPEAKERS_MAX);
   return 0;

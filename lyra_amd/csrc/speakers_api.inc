@@ -1,8 +1,8 @@
-// speakers_api.inc -- part of api.hip, behind bridge_api.inc: the conference bridge with loudest-N selection
-// (include/lyra_hip_speakers.h).  The tick and the two-deep host form are those of bridge_api.inc (brg_tick_impl,
-// brg_begin_impl: one body for both kinds of mix, the same slots and in-flight counters), with max_speakers >= 1; what is new
-// here is the mix itself -- three kernels on se[0] (speakers_kernels.hip) -- its scratch, and the end() that also delivers
-// levels and speaker flags.
+// speakers_api.inc -- part of api.hip, in front of bridge_api.inc: the loudest-N selection of the conference bridge
+// (include/lyra_hip_speakers.h).  What is here is the mix itself -- three kernels on se[0] (speakers_kernels.hip) -- and its
+// scratch.  The tick, the two-deep host form and the entry points are those of bridge_api.inc (brg_tick_impl, brg_begin_impl,
+// brg_end_impl, brg_mix_call: one body for every kind of mix, the same slots and in-flight counters), with max_speakers >= 1.
+#include "../../include/lyra_hip_bridge.h"
 #include "../../include/lyra_hip_speakers.h"
 
 static_assert(LYRA_HIP_SPEAKERS_SKIP_COMFORT_NOISE == LYRA_HIP_BRIDGE_SKIP_COMFORT_NOISE, "one flag word for both ticks");
@@ -64,87 +64,3 @@ int spk_check_n(lyra_hip_ctx* c, const char* what, int max_speakers) {
 }
 
 }  // namespace
-
-extern "C" {
-
-int lyra_hip_speakers_mix_dev(lyra_hip_ctx* c, const int16_t* d_pcm16, int B, const int32_t* d_order, const int32_t* d_room_start,
-                              int n_rooms, int n_members, const int32_t* d_muted, const int32_t* d_is_comfort_noise,
-                              int max_speakers, int16_t* d_mix, int64_t* d_levels, int32_t* d_is_speaker) {
-  int rc = check_batch(c, B);
-  if (rc) return rc;
-  if (!d_pcm16 || !d_mix) return fail(c, LYRA_HIP_EINVAL, "speakers_mix: null pointer");
-  if ((rc = brg_check_index(c, "speakers_mix", B, d_order, d_room_start, n_rooms, n_members))) return rc;
-  if (brg_misaligned(d_pcm16) || brg_misaligned(d_mix) || d_pcm16 == d_mix)
-    return fail(c, LYRA_HIP_EINVAL, "speakers_mix: d_pcm16 and d_mix must be 16-byte aligned and distinct");
-  if ((reinterpret_cast<uintptr_t>(d_levels) & 7u) != 0) return fail(c, LYRA_HIP_EINVAL, "speakers_mix: d_levels must be 8-byte aligned");
-  if ((rc = spk_check_n(c, "speakers_mix", max_speakers))) return rc;
-  DEVSCOPE(c);
-  if ((rc = brg_ensure_mix(c))) return rc;
-  if ((rc = spk_ensure(c, B))) return rc;
-  if ((rc = enc_side_begin(c, 0))) return rc;
-  rc = spk_mix_launch(c, d_pcm16, B, d_order, d_room_start, n_rooms, n_members, d_muted, d_is_comfort_noise, max_speakers, d_mix,
-                      d_levels, d_is_speaker, (int)(c->n_lossy_calls & 1));
-  if (!rc) rc = enc_side_done(c, 0);
-  return rc;
-}
-
-int lyra_hip_speakers_tick_dev(lyra_hip_ctx* c, const lyra_hip_speakers_tick* S) {
-  if (!c) return LYRA_HIP_EINVAL;
-  if (!S) return fail(c, LYRA_HIP_EINVAL, "speakers_tick: null pointer");
-  int rc = spk_check_n(c, "speakers_tick", S->max_speakers);
-  if (rc) return rc;
-  if ((reinterpret_cast<uintptr_t>(S->d_levels) & 7u) != 0)
-    return fail(c, LYRA_HIP_EINVAL, "speakers_tick: d_levels must be 8-byte aligned");
-  lyra_hip_bridge_tick T = {};   // the leading fields, one by one: the two structs are separate types
-  T.d_stream_ids = S->d_stream_ids;
-  T.B = S->B;
-  T.d_packets = S->d_packets;
-  T.d_packet_bytes = S->d_packet_bytes;
-  T.d_order = S->d_order;
-  T.d_room_start = S->d_room_start;
-  T.n_rooms = S->n_rooms;
-  T.n_members = S->n_members;
-  T.d_muted = S->d_muted;
-  T.flags = S->flags;
-  T.d_num_bits = S->d_num_bits;
-  T.d_dtx = S->d_dtx;
-  T.d_out_packets = S->d_out_packets;
-  T.d_out_packet_bytes = S->d_out_packet_bytes;
-  T.d_pcm16 = S->d_pcm16;
-  T.d_mix = S->d_mix;
-  T.d_is_noise = S->d_is_noise;
-  T.d_is_comfort_noise = S->d_is_comfort_noise;
-  return brg_tick_impl(c, "speakers_tick", &T, S->max_speakers, S->d_levels, S->d_is_speaker);
-}
-
-int lyra_hip_speakers_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const uint8_t* packets, const int32_t* packet_bytes,
-                            const int32_t* rooms, const int32_t* muted, unsigned flags, const int32_t* num_bits,
-                            const int32_t* dtx, int max_speakers) {
-  if (!c) return LYRA_HIP_EINVAL;
-  int rc = spk_check_n(c, "speakers_begin", max_speakers);
-  if (rc) return rc;
-  return brg_begin_impl(c, "speakers_begin", ids, B, packets, packet_bytes, rooms, muted, flags, num_bits, dtx, max_speakers);
-}
-
-int lyra_hip_speakers_end(lyra_hip_ctx* c, uint8_t* out_packets, int32_t* out_packet_bytes, int32_t* is_noise,
-                          int32_t* is_comfort_noise, int64_t* levels, int32_t* is_speaker) {
-  if (!c) return LYRA_HIP_EINVAL;
-  if (!c->brg_host || c->pl_ended[PL_BRIDGE] == c->pl_begun[PL_BRIDGE]) return fail(c, LYRA_HIP_EINVAL, "speakers_end: no tick in flight");
-  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->pl_ended[PL_BRIDGE] & 1];
-  if (!S.max_speakers) return fail(c, LYRA_HIP_EINVAL, "speakers_end: the oldest tick was begun by the full-mix begin()");
-  if (S.shared) return fail(c, LYRA_HIP_EINVAL, "speakers_end: the oldest tick was begun by lyra_hip_shared_begin");
-  if (!out_packets || !out_packet_bytes) return fail(c, LYRA_HIP_EINVAL, "speakers_end: null pointer");
-  DEVSCOPE(c);
-  c->pl_ended[PL_BRIDGE]++;                  // whatever happens below, the slot is given back
-  HIPCHK(c, hipEventSynchronize(S.ev_done));
-  const size_t n = (size_t)S.B;
-  std::memcpy(out_packet_bytes, S.h_out, n * 4);
-  if (is_noise) std::memcpy(is_noise, S.h_out + n * 4, n * 4);
-  if (is_comfort_noise) std::memcpy(is_comfort_noise, S.h_out + 2 * n * 4, n * 4);
-  if (is_speaker) std::memcpy(is_speaker, S.h_out + 3 * n * 4, n * 4);
-  if (levels) std::memcpy(levels, S.h_out + 4 * n * 4, n * 8);
-  std::memcpy(out_packets, S.h_out + kSpkOutWords * n * 4, n * LYRA_HIP_MAX_PACKET_BYTES);
-  return 0;
-}
-
-}  // extern "C"

@@ -4,7 +4,8 @@
    gfx950 code object; the older headers and tables are what they were;
 2. the planner: tests/bridge/bridge_plan_test.cc, a program of its own over lyra_amd/csrc/bridge_plan.h built with
    -fsanitize=address,undefined and run as a program, against the numpy restatement of tests/bridge_models.py -- and the
-   library's lyra_hip_bridge_plan against the same;
+   library's lyra_hip_bridge_plan against the same; and the staging layout of begin() / end():
+   tests/bridge/bridge_staging_test.cc over lyra_amd/csrc/bridge_staging.h, built and run the same way;
 3. the host logic of LyraConferenceBridge: tests/bridge/bridge_class_test.cc, linked against a fake of the new calls
    (tests/bridge/fake_bridge_abi.cc) next to the unchanged fake of tests/host_stub, built with the same flags and run as a
    program; the older classes' objects reference nothing of the new calls."""
@@ -150,6 +151,15 @@ def test_planner_program_under_sanitizers_equals_the_restatement(plan_exe, tmp_p
     for i in range(start.size - 1):
         m = order[start[i]:start[i + 1]]
         assert (np.diff(m) > 0).all() and (rooms[m] == labels[i]).all()
+
+
+def test_staging_layout_program_under_sanitizers(tmp_path):
+    """tests/bridge/bridge_staging_test.cc over lyra_amd/csrc/bridge_staging.h: where the arrays of every kind of tick lie in
+    the two staging slots of begin() / end() -- no overlap, the alignments, the bytes moved, the room in a slot."""
+    exe = str(tmp_path / "bridge_staging_test")
+    subprocess.check_call(SAN + ["-I" + os.path.join(ROOT, "lyra_amd", "csrc"), "-o", exe, os.path.join(HERE, "bridge_staging_test.cc")])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=SAN_ENV)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
 
 
 # ---- 3. the class -----------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """The conference bridge on the device (include/lyra_hip_bridge.h): the mix kernel against the formula, the tick against the
 three calls it composes, the tick against the reference model, the two-deep host form against the `_dev` call, bridge_demo, and
-the argument checks.  Helpers: tests/bridge_models.py.
+the argument checks.  Helpers: tests/bridge_models.py, tests/bridge_tick_cases.py.
 
 Shapes.  lossy_mix and the resampler serve 4 rows per workgroup, the estimators 2, the mix kernel one room per wavefront and 4
 per workgroup with member chunks of 8: B = 37 and B = 5 for the tick (the shapes of test_gpu_decode_streams.py), B = 330 with
@@ -9,21 +9,17 @@ rooms of 1, 2, 3, 8, 9, 16, 17 and 257 (313 rows; the rest in no room) for the k
 Stream kind: the contexts here (32 to 512 streams) run on the CU-masked streams the library picks up to 1,024 streams, which
 are blocking streams with respect to the NULL stream; the cases with streams="plain" run on hipStreamNonBlocking streams, the
 kind of a 4,096-stream context (tests/gpu_plumbing.py make_ctx)."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from bridge_models import SKIP_CN, BridgeModel, bridge_kernel_case, np_bridge_mix, np_bridge_plan
+from bridge_tick_cases import (SIZES, Bufs, TickKind, begin, begin_end_ticks, compose_case, demo_conference, host_script,
+                               rooms_of_six_then_random, run_demo)
 from gpu_plumbing import _dev, _ids, _t, make_ctx as _ctx, stream_cases
 from receiver_models import _full_batch_mask, _model_packets
 from row_cases import _draw_bits, _same_state
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.abspath(os.path.join(HERE, ".."))
 EINVAL = -1
-SIZES = np.array([8, 15, 23], np.int32)
 
 
 def _index(rooms):
@@ -96,19 +92,11 @@ def test_mix_kernel_equals_the_formula_and_survives_a_bad_index():
 
 # ---- 2. the tick equals its composition -----------------------------------------------------------------------------------
 
-class _Bufs:
-    def __init__(self, B):
-        import torch
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=_dev())   # noqa: E731
-        self.pcm16, self.mix = z((B, 320), torch.int16), z((B, 320), torch.int16)
-        self.isn, self.icn = z((B,), torch.int32), z((B,), torch.int32)
-        self.out, self.out_n = z((B, 23), torch.uint8), z((B,), torch.int32)
-
-    def read(self):
-        return tuple(t.cpu().numpy().copy() for t in (self.out_n, self.out, self.pcm16, self.mix, self.isn, self.icn))
-
-
 NAMES = ("out sizes", "out packets", "pcm16", "mix", "is_noise", "is_comfort_noise")
+
+
+def _Bufs(B):
+    return Bufs(B, NAMES)
 
 
 def _tick(a, bufs, ids, pk, sz, rooms, muted, bits, dtx, flags):
@@ -135,45 +123,27 @@ def _composed(u, bufs, ids, pk, sz, rooms, muted, bits, dtx, flags):
     return bufs.read()
 
 
-def _compose_case(B, mode="xnnpack", serial=False, flags=0, T=40, **kw):
-    ms = 64
-    rng = np.random.default_rng(100 + B)
-    ids = _ids(B, ms, B + 3)
-    mask = _full_batch_mask(T, B, rng)
-    rooms = [(np.arange(B) // 4).astype(np.int32), rng.integers(-1, 4, B).astype(np.int32)]   # membership changes at tick 20
-    if flags & SKIP_CN:
-        mask[:, :4] = 1
-        mask[6:20, 1] = 0           # row 1 of room 0 (rows 0..3) is lost for 14 ticks: comfort noise from the fifth on
-    muted = (rng.random(B) < 0.15).astype(np.int32)
-    muted[:4] = 0
-    dtx = (np.arange(B) % 2).astype(np.int32)
-    a, u = _ctx(ms, mode, **kw), _ctx(ms, mode, **kw)
-    try:
-        if serial:
-            a.set_serial(True)
-            u.set_serial(True)
-        ba, bu = [_Bufs(B), _Bufs(B)], [_Bufs(B), _Bufs(B)]
-        flag_mattered = 0
-        for t in range(T):
-            pk = rng.integers(0, 256, (B, 23), dtype=np.uint8)
-            sz = (rng.choice(SIZES, B) * mask[t]).astype(np.int32)
-            bits = _draw_bits(rng, B)
-            r = rooms[t >= 20]
-            got = _tick(a, ba[t & 1], ids, pk, sz, r, muted, bits, dtx, flags)
-            want = _composed(u, bu[t & 1], ids, pk, sz, r, muted, bits, dtx, flags)
-            for name, g, w in zip(NAMES, got, want):
-                assert np.array_equal(g, w), (f"tick {t}: {name} differs in rows",
-                                              np.flatnonzero((g != w).reshape(B, -1).any(axis=1))[:16])
-            if flags & SKIP_CN and t < 20:
-                plain = np_bridge_mix(want[2], *_index(r), muted, None)
-                flag_mattered += int(not np.array_equal(plain[:4], want[3][:4]))
-        assert a.decode_lossy_errors() == 0 and a.encode_mixed_errors() == 0 and a.bridge_errors() == 0
-        if flags & SKIP_CN:
-            assert flag_mattered >= 1, "SKIP_COMFORT_NOISE never changed the mix of the room with the lost member"
-        _same_state(a, u, ids, "after the last tick")
-    finally:
-        a.close()
-        u.close()
+class _FullMix(TickKind):
+    names = NAMES
+
+    def tick(self, c, a, bufs, pk, sz, rooms):
+        return _tick(a, bufs, c.ids, pk, sz, rooms, c.muted, c.bits, c.dtx, c.flags)
+
+    def composed(self, c, u, bufs, pk, sz, rooms):
+        return _composed(u, bufs, c.ids, pk, sz, rooms, c.muted, c.bits, c.dtx, c.flags)
+
+    def observe(self, c, t, rooms, got, want):
+        if c.flags & SKIP_CN and t < 20:
+            plain = np_bridge_mix(want[2], *_index(rooms), c.muted, None)
+            c.count["flag"] += int(not np.array_equal(plain[:4], want[3][:4]))
+
+    def verdict(self, c):
+        if c.flags & SKIP_CN:
+            assert c.count["flag"] >= 1, "SKIP_COMFORT_NOISE never changed the mix of the room with the lost member"
+
+
+def _compose_case(B, mode="xnnpack", **kw):
+    compose_case(_FullMix(), B, mode, **kw)
 
 
 @pytest.mark.gpu
@@ -279,15 +249,7 @@ def test_tick_against_the_reference_model(oracle_default, golden_dir):
 # ---- 4. bridge_begin / bridge_end equal the `_dev` call -------------------------------------------------------------------
 
 def _host_script(B, T, seed):
-    rng = np.random.default_rng(seed)
-    mask = _full_batch_mask(T, B, rng)
-    ticks = []
-    for t in range(T):
-        rooms = rng.integers(-1, 5, B).astype(np.int32) if t >= T // 2 else (np.arange(B) // 6).astype(np.int32)
-        ticks.append(dict(pk=rng.integers(0, 256, (B, 23), dtype=np.uint8), sz=(rng.choice(SIZES, B) * mask[t]).astype(np.int32),
-                          rooms=rooms, muted=(rng.random(B) < 0.1).astype(np.int32), bits=_draw_bits(rng, B),
-                          dtx=(np.arange(B) % 2).astype(np.int32)))
-    return ticks
+    return host_script(B, T, seed, rooms_of_six_then_random(B, T))
 
 
 @pytest.mark.gpu
@@ -300,13 +262,7 @@ def test_begin_end_equal_the_dev_call(depth, streams):
     try:
         bufs = _Bufs(B)
         want = [_tick(u, bufs, ids, s["pk"], s["sz"], s["rooms"], s["muted"], s["bits"], s["dtx"], SKIP_CN) for s in script]
-        got = []
-        for t, s in enumerate(script):
-            a.bridge_begin(s["pk"], s["sz"], s["rooms"], s["bits"], s["muted"], s["dtx"], SKIP_CN, ids)
-            if t + 1 >= depth:
-                got.append(a.bridge_end())
-        while len(got) < T:
-            got.append(a.bridge_end())
+        got = begin_end_ticks(a, script, a.bridge_end, depth, ids, SKIP_CN)
         for t in range(T):
             out, out_n, isn, icn = got[t]
             w = want[t]
@@ -328,7 +284,7 @@ def test_begin_refusals_enqueue_nothing_and_pipelines_exclude_each_other():
     L = a.L
     try:
         for c in (a, u):
-            c.bridge_begin(s[0]["pk"], s[0]["sz"], s[0]["rooms"], s[0]["bits"], s[0]["muted"], s[0]["dtx"], 0, ids)
+            begin(c, s[0], ids)
             c.bridge_end()
         before = a.export_streams(ids)
 
@@ -352,7 +308,7 @@ def test_begin_refusals_enqueue_nothing_and_pipelines_exclude_each_other():
         assert np.array_equal(a.export_streams(ids), before), "a refused begin() changed stream state"
         # a third begin() is refused; the two in flight complete as on the twin
         for t in (1, 2):
-            a.bridge_begin(s[t]["pk"], s[t]["sz"], s[t]["rooms"], s[t]["bits"], s[t]["muted"], s[t]["dtx"], 0, ids)
+            begin(a, s[t], ids)
         refused()
         # ... and so are the other pipelined forms while a tick is in flight, and export / import
         rates = np.full(B, 16000, np.int32)
@@ -383,39 +339,12 @@ def test_begin_refusals_enqueue_nothing_and_pipelines_exclude_each_other():
 
 # ---- 5. the class, through bridge_demo ------------------------------------------------------------------------------------
 
-def _run_demo(tmp_path, mode, streams, script, packets, lengths, skip_cn):
-    import lyra_amd
-    demo = os.path.join(ROOT, "lyra_amd", "bridge_demo")
-    assert os.path.exists(demo), "lyra_amd/bridge_demo not built (__graft_entry__.build())"
-    (tmp_path / "streams.txt").write_text("".join(f"{b} {d}\n" for b, d in streams))
-    script.tofile(tmp_path / "script.i32")
-    packets.tofile(tmp_path / "pk.bin")
-    lengths.tofile(tmp_path / "len.i32")
-    out, out_n = tmp_path / f"out{mode}.bin", tmp_path / f"out{mode}.i32"
-    r = subprocess.run([demo, lyra_amd.default_model_dir(), str(tmp_path / "streams.txt"), str(tmp_path / "script.i32"),
-                        str(tmp_path / "pk.bin"), str(tmp_path / "len.i32"), str(out), str(out_n), str(mode), str(int(skip_cn))],
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (mode, r.returncode, r.stderr[-3000:])
-    T, n = lengths.shape
-    return np.fromfile(out, np.uint8).reshape(T, n, 23), np.fromfile(out_n, np.int32).reshape(T, n)
-
-
 @pytest.mark.gpu
 def test_bridge_demo_both_modes_equal_begin_end_from_python(tmp_path):
     T, n = 30, 13
-    rng = np.random.default_rng(31)
-    rates = (3200, 6000, 9200)
-    streams = [(rates[s % 3], s % 2) for s in range(n)]
-    script = np.zeros((T, n, 3), np.int32)
-    script[:, :, 0] = (np.arange(n) // 4)[None, :]
-    script[T // 2:, :, 0] = rng.integers(-1, 3, n)[None, :]           # everybody moves at half time ...
-    script[:, :, 1] = rng.random((T, n)) < 0.1                         # ... mutes come and go ...
-    script[:, :, 2] = np.array(rates)[rng.integers(0, 3, (T, n))]      # ... and bitrates change from tick to tick
-    mask = _full_batch_mask(T, n, rng)
-    packets = rng.integers(0, 256, (T, n, 23), dtype=np.uint8)
-    lengths = (rng.choice(SIZES, (T, n)) * mask).astype(np.int32)
-    blocking = _run_demo(tmp_path, 0, streams, script, packets, lengths, True)
-    pipelined = _run_demo(tmp_path, 1, streams, script, packets, lengths, True)
+    streams, script, packets, lengths = demo_conference(31, T, n, 4, 3)
+    blocking = run_demo(tmp_path, 0, streams, script, packets, lengths, True)
+    pipelined = run_demo(tmp_path, 1, streams, script, packets, lengths, True)
     assert np.array_equal(blocking[1], pipelined[1]) and np.array_equal(blocking[0], pipelined[0])
     assert (blocking[1] == 0).any() and (blocking[1] > 0).any()
     a = _ctx(n)

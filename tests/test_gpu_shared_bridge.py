@@ -1,7 +1,8 @@
 """The loudest-N bridge with shared encoders on the device (include/lyra_hip_shared_bridge.h): the kernels against the model
 (two successive updates, permuted keys into a larger table, sentinels, a bad index, a bad key), the scripted conference with
 its slot events, the tick against the calls it composes, free slots carrying the room's packet, the two-deep host form against
-the `_dev` call with its refusals, bridge_demo --shared-encoders, and the argument checks.  Helpers: tests/shared_bridge_models.py.
+the `_dev` call with its refusals, bridge_demo --shared-encoders, and the argument checks.  Helpers:
+tests/shared_bridge_models.py, tests/bridge_tick_cases.py.
 
 Shapes.  The slot kernel serves one room per wavefront and the mix kernel one encoder row, four per workgroup, the fan-out 256
 bytes per workgroup: the kernel cases of the loudest-N test (B = 330, rooms of 1 .. 257, and rooms of 63 / 64 / 65 / 129) give
@@ -10,23 +11,18 @@ bytes per workgroup: the kernel cases of the loudest-N test (B = 330, rooms of 1
 Stream kind: the contexts here (64 to 512 streams) run on the CU-masked streams the library picks up to 1,024 streams, which
 are blocking streams with respect to the NULL stream; the cases with streams="plain" run on hipStreamNonBlocking streams, the
 kind of a 4,096-stream context (tests/gpu_plumbing.py make_ctx)."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from bridge_models import np_bridge_plan
+from bridge_tick_cases import (Bufs, TickKind, begin, begin_end_ticks, compose_case, demo_conference, host_script,
+                               rooms_redrawn_every_fourth_tick, run_demo)
 from gpu_plumbing import _dev, _ids, _t, make_ctx as _ctx, stream_cases
-from receiver_models import _full_batch_mask
 from row_cases import _draw_bits, _same_state
 from shared_bridge_models import EVENTS, SLOTS, np_fanout, np_shared_mix, run_slot_script, slot_script
 from speaker_models import SKIP_CN, np_levels, speakers_kernel_case, threshold_case
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.abspath(os.path.join(HERE, ".."))
 EINVAL = -1
-SIZES = np.array([8, 15, 23], np.int32)
 MIX_FILL, LEVEL_FILL, FLAG_FILL, TABLE_FILL = 0x3333, 0x5555555555555555, 0x77777777, 0x66666666
 
 
@@ -187,24 +183,13 @@ def test_the_scripted_conference_keeps_its_slots_on_the_device():
 
 # ---- 2. the tick equals its composition -----------------------------------------------------------------------------------
 
-class _TickBufs:
-    """Every output of one tick with B rows and room for E_max encoder rows"""
-
-    def __init__(self, B, e_max):
-        import torch
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=_dev())   # noqa: E731
-        self.pcm16, self.isn, self.icn = z((B, 320), torch.int16), z((B,), torch.int32), z((B,), torch.int32)
-        self.out, self.out_n = z((B, 23), torch.uint8), z((B,), torch.int32)
-        self.levels, self.spk, self.slot_of = z((B,), torch.int64), z((B,), torch.int32), z((B,), torch.int32)
-        self.enc_mix, self.enc_pk, self.enc_n = z((e_max, 320), torch.int16), z((e_max, 23), torch.uint8), z((e_max,), torch.int32)
-
-    def read(self, E):
-        return tuple(t.cpu().numpy().copy() for t in (self.out_n, self.out, self.pcm16, self.isn, self.icn, self.levels, self.spk,
-                                                      self.slot_of, self.enc_mix[:E], self.enc_pk[:E], self.enc_n[:E]))
-
-
 NAMES = ("out sizes", "out packets", "pcm16", "is_noise", "is_comfort_noise", "levels", "is_speaker", "slot_of", "enc_mix",
          "enc packets", "enc sizes")
+
+
+def _TickBufs(B, e_max):
+    """Every output of one tick with B rows and room for E_max encoder rows"""
+    return Bufs(B, NAMES, e_max)
 
 
 def _labels(rooms):
@@ -262,52 +247,44 @@ def _enc_settings(rng, rooms, N, ids, ms, bits=None, dtx=None):
     return tuple(v.reshape(n_rooms, 1 + N) for v in (e_ids, e_bits, e_dtx))
 
 
-def _compose_case(B, mode="xnnpack", serial=False, flags=0, T=40, N=2, **kw):
-    ms = 128
-    rng = np.random.default_rng(200 + B)
-    ids = _ids(B, ms, B + 5)
-    mask = _full_batch_mask(T, B, rng)
-    rooms = [(np.arange(B) // 4).astype(np.int32), rng.integers(-1, 4, B).astype(np.int32)]   # membership changes at tick 20
-    if flags & SKIP_CN:
-        mask[:, :4] = 1
-        mask[6:20, 1] = 0           # row 1 of room 0 is lost for 14 ticks: comfort noise from the fifth on
-    muted = (rng.random(B) < 0.15).astype(np.int32)
-    muted[:4] = 0
-    if flags & SKIP_CN:
-        muted[2:4] = 1
-    enc = [_enc_settings(rng, r, N, ids, ms) for r in rooms]
-    assert np.intersect1d(enc[0][0], ids).size >= 1, "some encoder ids must coincide with participants' ids"
-    e_max = max(e[0].size for e in enc)
-    every_id = np.union1d(ids, np.concatenate([e[0].reshape(-1) for e in enc])).astype(np.int32)
-    a, u = _ctx(ms, mode, **kw), _ctx(ms, mode, **kw)
-    try:
-        if serial:
-            a.set_serial(True)
-            u.set_serial(True)
-        ba, bu = [_TickBufs(B, e_max), _TickBufs(B, e_max)], [_TickBufs(B, e_max), _TickBufs(B, e_max)]
+class _SharedEncoders(TickKind):
+    names = NAMES
+    ms, seed, id_offset = 128, 200, 5
+
+    def prepare(self, c, rng):
+        if c.flags & SKIP_CN:
+            c.muted[2:4] = 1
+        c.enc = [_enc_settings(rng, r, c.N, c.ids, c.ms) for r in c.rooms]
+        assert np.intersect1d(c.enc[0][0], c.ids).size >= 1, "some encoder ids must coincide with participants' ids"
+        c.state_ids = np.union1d(c.ids, np.concatenate([e[0].reshape(-1) for e in c.enc])).astype(np.int32)
         n_table = 12                # (the labels, which are the keys here, reach 9)
-        table_u = np.full((n_table, SLOTS), -1, np.int32)
-        table_a = _t(table_u)
-        moved = shared = 0
-        for t in range(T):
-            pk = rng.integers(0, 256, (B, 23), dtype=np.uint8)
-            sz = (rng.choice(SIZES, B) * mask[t]).astype(np.int32)
-            r, e = rooms[t >= 20], enc[t >= 20]
-            before = table_u.copy()
-            got = _shared_tick(a, ba[t & 1], table_a, ids, pk, sz, r, muted, flags, N, e)
-            want = _composed_tick(u, bu[t & 1], table_u, ids, pk, sz, r, muted, flags, N, e)
-            for name, g, w in zip(NAMES, got, want):
-                assert np.array_equal(g, w), (f"tick {t}: {name} differs in rows",
-                                              np.flatnonzero((g != w).reshape(g.shape[0], -1).any(axis=1))[:16])
-            assert np.array_equal(table_a.cpu().numpy(), table_u), f"tick {t}: the slot table"
-            moved += int(t > 0 and not np.array_equal(before, table_u))
-            shared += int((np.unique(want[1][want[0] > 0], axis=0).shape[0]) < int((want[0] > 0).sum()))
-        assert a.decode_lossy_errors() == 0 and a.encode_mixed_errors() == 0 and a.bridge_errors() == 0
-        assert moved >= 2 and shared >= T // 4,"the table never changed, or no packet was ever shared"
-        _same_state(a, u, every_id, "after the last tick")
-    finally:
-        a.close()
-        u.close()
+        c.table_u = np.full((n_table, SLOTS), -1, np.int32)
+        c.table_a = _t(c.table_u)
+
+    def bufs(self, c):
+        return _TickBufs(c.B, max(e[0].size for e in c.enc))
+
+    def draw(self, c, rng):
+        """(bit counts and DTX flags belong to the encoder rows: nothing is drawn per tick)"""
+
+    def tick(self, c, a, bufs, pk, sz, rooms):
+        c.before = c.table_u.copy()
+        return _shared_tick(a, bufs, c.table_a, c.ids, pk, sz, rooms, c.muted, c.flags, c.N, c.enc[c.t >= 20])
+
+    def composed(self, c, u, bufs, pk, sz, rooms):
+        return _composed_tick(u, bufs, c.table_u, c.ids, pk, sz, rooms, c.muted, c.flags, c.N, c.enc[c.t >= 20])
+
+    def observe(self, c, t, rooms, got, want):
+        assert np.array_equal(c.table_a.cpu().numpy(), c.table_u), f"tick {t}: the slot table"
+        c.count["moved"] += int(t > 0 and not np.array_equal(c.before, c.table_u))
+        c.count["shared"] += int((np.unique(want[1][want[0] > 0], axis=0).shape[0]) < int((want[0] > 0).sum()))
+
+    def verdict(self, c):
+        assert c.count["moved"] >= 2 and c.count["shared"] >= c.T // 4, "the table never changed, or no packet was ever shared"
+
+
+def _compose_case(B, mode="xnnpack", N=2, **kw):
+    compose_case(_SharedEncoders(), B, mode, N=N, **kw)
 
 
 @pytest.mark.gpu
@@ -383,24 +360,18 @@ def test_free_slots_carry_the_rooms_packet_bit_for_bit():
 def _host_ticks(B, T, seed, N):
     """T ticks of host arrays for shared_begin: rooms of 6 at first, redrawn every fourth tick (five rooms of about 7 and rows
     in no room), nobody in any room at tick 9; the encoder settings of a room go with its label."""
-    rng = np.random.default_rng(seed)
-    mask = _full_batch_mask(T, B, rng)
-    rooms = (np.arange(B) // 6).astype(np.int32)
-    ticks = []
-    for t in range(T):
-        if t and t % 4 == 0:
-            rooms = rng.integers(-1, 5, B).astype(np.int32)
-        r = np.full(B, -1, np.int32) if t == 9 else rooms
-        labels = _labels(r)
-        cell = labels[:, None] * (1 + N) + np.arange(1 + N)[None, :]
-        ticks.append({"pk": rng.integers(0, 256, (B, 23), dtype=np.uint8), "sz": (rng.choice(SIZES, B) * mask[t]).astype(np.int32),
-                      "rooms": r, "labels": labels, "muted": (rng.random(B) < 0.1).astype(np.int32),
-                      "enc": (cell.astype(np.int32), np.array([64, 120, 184], np.int32)[cell % 3], (cell % 2).astype(np.int32))})
+    ticks = host_script(B, T, seed, rooms_redrawn_every_fourth_tick(B), per_listener=False)
+    for t, s in enumerate(ticks):
+        if t == 9:
+            s["rooms"] = np.full(B, -1, np.int32)
+        s["labels"] = _labels(s["rooms"])
+        cell = s["labels"][:, None] * (1 + N) + np.arange(1 + N)[None, :]
+        s["enc"] = (cell.astype(np.int32), np.array([64, 120, 184], np.int32)[cell % 3], (cell % 2).astype(np.int32))
     return ticks
 
 
 def _begin(c, s, N, ids, flags=0):
-    c.shared_begin(s["pk"], s["sz"], s["rooms"], N, s["labels"], *s["enc"], s["muted"], flags, ids)
+    begin(c, s, ids, flags, N)
 
 
 @pytest.mark.gpu
@@ -459,13 +430,7 @@ def test_begin_end_equal_the_dev_call(depth, streams):
     a, u = _ctx(ms, streams=streams), _ctx(ms, streams=streams)
     try:
         want = _want_ticks(u, ids, script, N, SKIP_CN, ms)
-        got = []
-        for t, s in enumerate(script):
-            _begin(a, s, N, ids, SKIP_CN)
-            if t + 1 >= depth:
-                got.append(a.shared_end())
-        while len(got) < T:
-            got.append(a.shared_end())
+        got = begin_end_ticks(a, script, a.shared_end, depth, ids, SKIP_CN, N)
         for t in range(T):
             _same_tick(got[t], want[t], t)
         assert sum(int((g[6] >= 0).sum()) for g in got) > T and not got[9][1].any() and not got[9][0].any()
@@ -676,37 +641,14 @@ def test_dev_argument_checks_refuse_and_leave_the_context_alone():
 # ---- 7. the class, through bridge_demo --shared-encoders ------------------------------------------------------------------
 
 def _demo(tmp_path, mode, streams, script, packets, lengths, N):
-    import lyra_amd
-    demo = os.path.join(ROOT, "lyra_amd", "bridge_demo")
-    assert os.path.exists(demo), "lyra_amd/bridge_demo not built (__graft_entry__.build())"
-    names = {k: str(tmp_path / f"{k}{mode}") for k in ("out.bin", "out.i32", "spk.i32", "slots.i32")}
-    (tmp_path / "streams.txt").write_text("".join(f"{b} {d}\n" for b, d in streams))
-    for name, a in (("script.i32", script), ("pk.bin", packets), ("len.i32", lengths)):
-        a.tofile(tmp_path / name)
-    r = subprocess.run([demo, lyra_amd.default_model_dir(), str(tmp_path / "streams.txt"), str(tmp_path / "script.i32"),
-                        str(tmp_path / "pk.bin"), str(tmp_path / "len.i32"), names["out.bin"], names["out.i32"], str(mode), "1",
-                        f"--max-speakers={N}", "--speakers-out=" + names["spk.i32"], "--shared-encoders",
-                        "--slots-out=" + names["slots.i32"]], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (mode, r.returncode, r.stderr[-3000:])
-    T, n = lengths.shape
-    return (np.fromfile(names["out.bin"], np.uint8).reshape(T, n, 23), np.fromfile(names["out.i32"], np.int32).reshape(T, n),
-            np.fromfile(names["spk.i32"], np.int32).reshape(T, n), np.fromfile(names["slots.i32"], np.int32).reshape(T, n))
+    return run_demo(tmp_path, mode, streams, script, packets, lengths, True, (f"--max-speakers={N}", "--shared-encoders"),
+                    (("--speakers-out", "spk.i32"), ("--slots-out", "slots.i32")))
 
 
 @pytest.mark.gpu
 def test_bridge_demo_with_shared_encoders_equals_begin_end_from_python(tmp_path):
     T, n, N = 30, 13, 2
-    rng = np.random.default_rng(41)
-    rates = (3200, 6000, 9200)
-    streams = [(rates[s % 3], s % 2) for s in range(n)]
-    script = np.zeros((T, n, 3), np.int32)
-    script[:, :, 0] = (np.arange(n) // 6)[None, :]
-    script[T // 2:, :, 0] = rng.integers(-1, 2, n)[None, :]           # everybody moves at half time ...
-    script[:, :, 1] = rng.random((T, n)) < 0.1                         # ... mutes come and go ...
-    script[:, :, 2] = np.array(rates)[rng.integers(0, 3, (T, n))]      # ... and the first member's bitrate changes the room's
-    mask = _full_batch_mask(T, n, rng)
-    packets = rng.integers(0, 256, (T, n, 23), dtype=np.uint8)
-    lengths = (rng.choice(SIZES, (T, n)) * mask).astype(np.int32)
+    streams, script, packets, lengths = demo_conference(41, T, n, 6, 2)     # (the first member's bitrate is the room's)
     blocking = _demo(tmp_path, 0, streams, script, packets, lengths, N)
     pipelined = _demo(tmp_path, 1, streams, script, packets, lengths, N)
     for b, p in zip(blocking, pipelined):

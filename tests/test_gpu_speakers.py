@@ -1,6 +1,7 @@
 """The conference bridge with loudest-N selection on the device (include/lyra_hip_speakers.h): the three kernels against the
 formula, the equivalence with the full mix where nobody is left out, the tick against the three calls it composes, the two-deep
-host form against the `_dev` call, bridge_demo --max-speakers, and the argument checks.  Helpers: tests/speaker_models.py.
+host form against the `_dev` call, bridge_demo --max-speakers, and the argument checks.  Helpers: tests/speaker_models.py,
+tests/bridge_tick_cases.py.
 
 Shapes.  The level kernel serves 4 rows per workgroup, the select kernel one room per wavefront (keys in registers up to 64
 members, in memory above), the mix kernel 8 positions per wavefront and 32 per workgroup: B = 330 with rooms of 1, 2, 3, 8, 9,
@@ -9,22 +10,18 @@ members, in memory above), the mix kernel 8 positions per wavefront and 32 per w
 Stream kind: the contexts here (up to 512 streams) run on the CU-masked streams the library picks up to 1,024 streams, which
 are blocking streams with respect to the NULL stream; the cases with streams="plain" run on hipStreamNonBlocking streams, the
 kind of a 4,096-stream context (tests/gpu_plumbing.py make_ctx)."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from bridge_models import np_bridge_mix, np_bridge_plan
+from bridge_tick_cases import (SIZES, Bufs, TickKind, begin, begin_end_ticks, compose_case, demo_conference, host_script,
+                               rooms_redrawn_every_fourth_tick, run_demo)
 from gpu_plumbing import _dev, _ids, _t, make_ctx as _ctx, stream_cases
 from receiver_models import _full_batch_mask
 from row_cases import _draw_bits, _same_state
 from speaker_models import SKIP_CN, np_levels, np_speakers_mix, speakers_kernel_case, threshold_case
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.abspath(os.path.join(HERE, ".."))
 EINVAL = -1
-SIZES = np.array([8, 15, 23], np.int32)
 MIX_FILL, LEVEL_FILL, FLAG_FILL = 0x3333, 0x5555555555555555, 0x77777777
 
 
@@ -135,21 +132,11 @@ def test_with_at_most_eight_candidates_per_room_it_is_the_full_mix(kernel_case):
 
 # ---- 3. the tick equals its composition -----------------------------------------------------------------------------------
 
-class _Bufs:
-    def __init__(self, B):
-        import torch
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=_dev())   # noqa: E731
-        self.pcm16, self.mix = z((B, 320), torch.int16), z((B, 320), torch.int16)
-        self.isn, self.icn = z((B,), torch.int32), z((B,), torch.int32)
-        self.out, self.out_n = z((B, 23), torch.uint8), z((B,), torch.int32)
-        self.levels, self.spk = z((B,), torch.int64), z((B,), torch.int32)
-
-    def read(self):
-        return tuple(t.cpu().numpy().copy() for t in (self.out_n, self.out, self.pcm16, self.mix, self.isn, self.icn,
-                                                      self.levels, self.spk))
-
-
 NAMES = ("out sizes", "out packets", "pcm16", "mix", "is_noise", "is_comfort_noise", "levels", "is_speaker")
+
+
+def _Bufs(B):
+    return Bufs(B, NAMES)
 
 
 def _tick(a, bufs, ids, pk, sz, rooms, muted, bits, dtx, flags, N):
@@ -178,51 +165,35 @@ def _composed(u, bufs, ids, pk, sz, rooms, muted, bits, dtx, flags, N):
     return bufs.read()
 
 
-def _compose_case(B, mode="xnnpack", serial=False, flags=0, T=40, N=2, **kw):
-    ms = 64
-    rng = np.random.default_rng(100 + B)
-    ids = _ids(B, ms, B + 3)
-    mask = _full_batch_mask(T, B, rng)
-    rooms = [(np.arange(B) // 4).astype(np.int32), rng.integers(-1, 4, B).astype(np.int32)]   # membership changes at tick 20
-    if flags & SKIP_CN:
-        mask[:, :4] = 1
-        mask[6:20, 1] = 0           # row 1 of room 0 (rows 0..3) is lost for 14 ticks: comfort noise from the fifth on
-    muted = (rng.random(B) < 0.15).astype(np.int32)
-    muted[:4] = 0
-    if flags & SKIP_CN:
-        muted[2:4] = 1              # ... and one of the room's two sources: a speaker (N = 2) unless the flag takes it out
-    dtx = (np.arange(B) % 2).astype(np.int32)
-    a, u = _ctx(ms, mode, **kw), _ctx(ms, mode, **kw)
-    try:
-        if serial:
-            a.set_serial(True)
-            u.set_serial(True)
-        ba, bu = [_Bufs(B), _Bufs(B)], [_Bufs(B), _Bufs(B)]
-        selection_mattered = flag_mattered = 0
-        for t in range(T):
-            pk = rng.integers(0, 256, (B, 23), dtype=np.uint8)
-            sz = (rng.choice(SIZES, B) * mask[t]).astype(np.int32)
-            bits = _draw_bits(rng, B)
-            r = rooms[t >= 20]
-            got = _tick(a, ba[t & 1], ids, pk, sz, r, muted, bits, dtx, flags, N)
-            want = _composed(u, bu[t & 1], ids, pk, sz, r, muted, bits, dtx, flags, N)
-            for name, g, w in zip(NAMES, got, want):
-                assert np.array_equal(g, w), (f"tick {t}: {name} differs in rows",
-                                              np.flatnonzero((g != w).reshape(B, -1).any(axis=1))[:16])
-            index = np_bridge_plan(r)
-            selection_mattered += int(not np.array_equal(np_bridge_mix(want[2], *index, muted,
-                                                                       want[5] if flags & SKIP_CN else None), want[3]))
-            if flags & SKIP_CN and t < 20:
-                _, _, plain = np_speakers_mix(want[2], *index, N, muted, None)
-                flag_mattered += int(plain[1] == 1 and want[7][1] == 0)     # the lost row stops being a speaker
-        assert a.decode_lossy_errors() == 0 and a.encode_mixed_errors() == 0 and a.bridge_errors() == 0
-        assert selection_mattered >= 1, "the selection never changed the mix"
-        if flags & SKIP_CN:
-            assert flag_mattered >= 1, "SKIP_COMFORT_NOISE never took the lost row off the speaker list"
-        _same_state(a, u, ids, "after the last tick")
-    finally:
-        a.close()
-        u.close()
+class _Selection(TickKind):
+    names = NAMES
+
+    def prepare(self, c, rng):
+        if c.flags & SKIP_CN:
+            c.muted[2:4] = 1        # ... and one of the room's two sources: a speaker (N = 2) unless the flag takes it out
+
+    def tick(self, c, a, bufs, pk, sz, rooms):
+        return _tick(a, bufs, c.ids, pk, sz, rooms, c.muted, c.bits, c.dtx, c.flags, c.N)
+
+    def composed(self, c, u, bufs, pk, sz, rooms):
+        return _composed(u, bufs, c.ids, pk, sz, rooms, c.muted, c.bits, c.dtx, c.flags, c.N)
+
+    def observe(self, c, t, rooms, got, want):
+        index = np_bridge_plan(rooms)
+        c.count["selection"] += int(not np.array_equal(np_bridge_mix(want[2], *index, c.muted,
+                                                                     want[5] if c.flags & SKIP_CN else None), want[3]))
+        if c.flags & SKIP_CN and t < 20:
+            _, _, plain = np_speakers_mix(want[2], *index, c.N, c.muted, None)
+            c.count["flag"] += int(plain[1] == 1 and want[7][1] == 0)     # the lost row stops being a speaker
+
+    def verdict(self, c):
+        assert c.count["selection"] >= 1, "the selection never changed the mix"
+        if c.flags & SKIP_CN:
+            assert c.count["flag"] >= 1, "SKIP_COMFORT_NOISE never took the lost row off the speaker list"
+
+
+def _compose_case(B, mode="xnnpack", N=2, **kw):
+    compose_case(_Selection(), B, mode, N=N, **kw)
 
 
 @pytest.mark.gpu
@@ -281,22 +252,11 @@ def test_tick_with_library_scratch_for_the_optional_outputs():
 # ---- 5. speakers_begin / speakers_end equal the `_dev` call ---------------------------------------------------------------
 
 def _host_script(B, T, seed):
-    """T ticks of host arrays; the membership is drawn anew every fourth tick: rooms of 6, then five rooms of about 7 with rows
-    in no room, so that N = 3 always leaves talkers out"""
-    rng = np.random.default_rng(seed)
-    mask = _full_batch_mask(T, B, rng)
-    dtx = (np.arange(B) % 2).astype(np.int32)
-    ticks, rooms = [], (np.arange(B) // 6).astype(np.int32)
-    for t in range(T):
-        if t and t % 4 == 0:
-            rooms = rng.integers(-1, 5, B).astype(np.int32)
-        ticks.append({"pk": rng.integers(0, 256, (B, 23), dtype=np.uint8), "sz": (rng.choice(SIZES, B) * mask[t]).astype(np.int32),
-                      "rooms": rooms, "muted": (rng.random(B) < 0.1).astype(np.int32), "bits": _draw_bits(rng, B), "dtx": dtx})
-    return ticks
+    return host_script(B, T, seed, rooms_redrawn_every_fourth_tick(B))
 
 
 def _begin(c, s, N, ids, flags=0):
-    c.speakers_begin(s["pk"], s["sz"], s["rooms"], s["bits"], N, s["muted"], s["dtx"], flags, ids)
+    begin(c, s, ids, flags, N)
 
 
 @pytest.mark.gpu
@@ -309,13 +269,7 @@ def test_begin_end_equal_the_dev_call(depth, streams):
     try:
         bufs = _Bufs(B)
         want = [_tick(u, bufs, ids, s["pk"], s["sz"], s["rooms"], s["muted"], s["bits"], s["dtx"], SKIP_CN, N) for s in script]
-        got = []
-        for t, s in enumerate(script):
-            _begin(a, s, N, ids, SKIP_CN)
-            if t + 1 >= depth:
-                got.append(a.speakers_end())
-        while len(got) < T:
-            got.append(a.speakers_end())
+        got = begin_end_ticks(a, script, a.speakers_end, depth, ids, SKIP_CN, N)
         for t in range(T):
             out, out_n, isn, icn, levels, spk = got[t]
             w = want[t]
@@ -351,11 +305,11 @@ def test_begin_refusals_enqueue_nothing_and_the_two_kinds_of_tick_share_one_queu
         assert np.array_equal(a.export_streams(ids), before), "a refused begin() changed stream state"
         # one queue of two for both kinds: a selection tick, then a full-mix tick; a third of either kind is refused
         _begin(a, s[1], N, ids)
-        a.bridge_begin(s[2]["pk"], s[2]["sz"], s[2]["rooms"], s[2]["bits"], s[2]["muted"], s[2]["dtx"], 0, ids)
+        begin(a, s[2], ids)
         with pytest.raises(Err):
             _begin(a, s[3], N, ids)
         with pytest.raises(Err):
-            a.bridge_begin(s[3]["pk"], s[3]["sz"], s[3]["rooms"], s[3]["bits"], s[3]["muted"], s[3]["dtx"], 0, ids)
+            begin(a, s[3], ids)
         # the other pipelined forms, export / import: refused while a tick is in flight
         rates = np.full(B, 16000, np.int32)
         with pytest.raises(Err):
@@ -374,7 +328,7 @@ def test_begin_refusals_enqueue_nothing_and_the_two_kinds_of_tick_share_one_queu
         bufs = _Bufs(B)
         w1 = _tick(u, bufs, ids, s[1]["pk"], s[1]["sz"], s[1]["rooms"], s[1]["muted"], s[1]["bits"], s[1]["dtx"], 0, N)
         assert np.array_equal(got1[1], w1[0]) and np.array_equal(got1[0], w1[1]) and np.array_equal(got1[5], w1[7])
-        u.bridge_begin(s[2]["pk"], s[2]["sz"], s[2]["rooms"], s[2]["bits"], s[2]["muted"], s[2]["dtx"], 0, ids)
+        begin(u, s[2], ids)
         w2 = u.bridge_end()
         assert np.array_equal(got2[1], w2[1]) and np.array_equal(got2[0], w2[0])
         _same_state(a, u, ids, "after the refusals")
@@ -462,37 +416,14 @@ def test_dev_argument_checks_refuse_and_leave_the_context_alone():
 # ---- 7. the class, through bridge_demo --max-speakers ---------------------------------------------------------------------
 
 def _run_demo(tmp_path, mode, streams, script, packets, lengths, skip_cn, N):
-    import lyra_amd
-    demo = os.path.join(ROOT, "lyra_amd", "bridge_demo")
-    assert os.path.exists(demo), "lyra_amd/bridge_demo not built (__graft_entry__.build())"
-    (tmp_path / "streams.txt").write_text("".join(f"{b} {d}\n" for b, d in streams))
-    script.tofile(tmp_path / "script.i32")
-    packets.tofile(tmp_path / "pk.bin")
-    lengths.tofile(tmp_path / "len.i32")
-    out, out_n, spk = tmp_path / f"out{mode}.bin", tmp_path / f"out{mode}.i32", tmp_path / f"spk{mode}.i32"
-    r = subprocess.run([demo, lyra_amd.default_model_dir(), str(tmp_path / "streams.txt"), str(tmp_path / "script.i32"),
-                        str(tmp_path / "pk.bin"), str(tmp_path / "len.i32"), str(out), str(out_n), str(mode), str(int(skip_cn)),
-                        f"--max-speakers={N}", f"--speakers-out={spk}"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (mode, r.returncode, r.stderr[-3000:])
-    T, n = lengths.shape
-    return (np.fromfile(out, np.uint8).reshape(T, n, 23), np.fromfile(out_n, np.int32).reshape(T, n),
-            np.fromfile(spk, np.int32).reshape(T, n))
+    return run_demo(tmp_path, mode, streams, script, packets, lengths, skip_cn, (f"--max-speakers={N}",),
+                    (("--speakers-out", "spk.i32"),))
 
 
 @pytest.mark.gpu
 def test_bridge_demo_with_max_speakers_equals_begin_end_from_python(tmp_path):
     T, n, N = 30, 13, 3
-    rng = np.random.default_rng(31)
-    rates = (3200, 6000, 9200)
-    streams = [(rates[s % 3], s % 2) for s in range(n)]
-    script = np.zeros((T, n, 3), np.int32)
-    script[:, :, 0] = (np.arange(n) // 6)[None, :]
-    script[T // 2:, :, 0] = rng.integers(-1, 2, n)[None, :]           # everybody moves at half time ...
-    script[:, :, 1] = rng.random((T, n)) < 0.1                         # ... mutes come and go ...
-    script[:, :, 2] = np.array(rates)[rng.integers(0, 3, (T, n))]      # ... and bitrates change from tick to tick
-    mask = _full_batch_mask(T, n, rng)
-    packets = rng.integers(0, 256, (T, n, 23), dtype=np.uint8)
-    lengths = (rng.choice(SIZES, (T, n)) * mask).astype(np.int32)
+    streams, script, packets, lengths = demo_conference(31, T, n, 6, 2)
     blocking = _run_demo(tmp_path, 0, streams, script, packets, lengths, True, N)
     pipelined = _run_demo(tmp_path, 1, streams, script, packets, lengths, True, N)
     for b, p in zip(blocking, pipelined):
