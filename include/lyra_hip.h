@@ -544,13 +544,22 @@ int lyra_hip_twin_noise(lyra_hip_ctx* ctx, const int32_t* stream_ids, int B);
 int lyra_hip_twin_fetch(lyra_hip_ctx* ctx, int num_streams, int num_internal_samples, int out_rate, int16_t* out);
 
 /* ---- Pipelined host-buffer calls (round 6) ----------------------------------------------------------------------------
- * Two-deep pipelined forms of the blocking host-buffer calls above, for a caller that feeds hop after hop: begin() stages
- * the caller's data in pinned memory, uploads it on a copy stream of its own, enqueues the kernels and the download and
- * returns; end() waits for the OLDEST begun call and copies its result out.  At most two calls may be in flight; with
- * begin(n + 1) issued before end(n) the upload of hop n + 1 and the download of hop n run under the kernels (blocking
- * calls idle the chain for both: BatchLyraEncoder + BatchLyraDecoder on two host threads 7.8-8.3 M frames/s, pipelined:
- * DESIGN.md 5).  The caller's buffers may be reused as soon as begin() / end() returns.  Results are bit-identical to the
- * blocking calls.  Do not mix blocking and pipelined calls of one kind on one context while calls are in flight.
+ * Two-deep pipelined forms of the blocking host-buffer calls above, for a caller that feeds hop after hop: begin() copies
+ * the small arrays (stream ids; the decoder's packets) into pinned slots of the context, uploads the audio STRAIGHT from the
+ * caller's memory, waits on the host for that upload, enqueues the kernels and the download and returns; end() waits for the
+ * OLDEST begun call and copies its result out.  At most two calls may be in flight; with begin(n + 1) issued before end(n)
+ * the upload of hop n + 1 and the download of hop n run under the kernels (blocking calls idle the chain for both:
+ * BatchLyraEncoder + BatchLyraDecoder on two host threads 7.8-8.3 M frames/s, pipelined: DESIGN.md 5).
+ * The caller's buffers may be reused as soon as begin() / end() returns, pageable or pinned (hipHostMalloc,
+ * hipHostRegister): begin() has read the small arrays on the host and has WAITED for the audio upload, in every branch;
+ * end() has waited for its download (tests/test_gpu_pinned_buffers.py).  Which stream carries the upload: with another call
+ * of the pipeline in flight, the context's noise stream (lyra_hip_stream_noise; it serves as the copy stream, no stream is
+ * created for it), so that the copy runs under the older call's kernels; with none in flight, the encode-side stream itself.
+ * The wait is for that stream: on a context that also runs decoder-side legs which complete on the noise stream
+ * (lyra_hip_noise_receive_dev, lyra_hip_decode_ext_dev, lyra_hip_run_steps_dev with the estimator) begin() waits for those
+ * kernels too -- keep an encoder pipeline and such decoder legs on contexts of their own if that matters.
+ * Results are bit-identical to the blocking calls.  Do not mix blocking and pipelined calls of one kind on one context while
+ * calls are in flight.
  *
  * lyra_hip_encode_begin: LyraEncoder::Encode for B streams (lyra/lyra_encoder.cc:113-156) -- pcm [B][sample_rate_hz / 50]
  *   at 8 / 16 / 32 / 48 kHz (the encoder's own resampler runs on the device, :119-122), dtx != 0 as lyra_hip_encode_dtx

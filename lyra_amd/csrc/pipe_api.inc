@@ -154,12 +154,13 @@ int lyra_hip_encode_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const int1
       HIPCHK(c, hipStreamWaitEvent(c->se[k], S.ev_up, 0));
       HIPCHK(c, hipStreamWaitEvent(c->sq[k], S.ev_up, 0));
     }
-  } else if (c->nsub > 1) {
-    // A split batch: the other chunks' extractors run on se[1..] and read what se[0] has just uploaded.  The upload is
-    // waited for HERE, on the host (nothing of this pipeline is in flight in this branch, so nothing is lost), as the
-    // overlapped branch above does for the copy stream: a kernel enqueued after the copy has completed needs no
-    // cross-stream edge behind a copy (the one place that had such an edge, lyra_hip_decode_begin's first form, misbehaved:
-    // profiles/EXPERIMENTS.md).
+  } else {
+    // The upload is waited for HERE, on the host, whatever nsub is (nothing of this pipeline is in flight in this branch, so
+    // nothing is lost), as the overlapped branch above does for the copy stream.  `pcm` is the caller's again on return: from
+    // pinned memory the copy is asynchronous, and without this wait it would read what the caller has put there since
+    // (tests/test_gpu_pinned_buffers.py).  With a split batch the other chunks' extractors run on se[1..] and read what
+    // se[0] has just uploaded: a kernel enqueued after the copy has completed needs no cross-stream edge behind a copy (the
+    // one place that had such an edge, lyra_hip_decode_begin's first form, misbehaved: profiles/EXPERIMENTS.md).
     HIPCHK(c, hipStreamSynchronize(c->se[0]));
   }
   const int16_t* d16 = S.d_in;

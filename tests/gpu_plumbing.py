@@ -151,6 +151,11 @@ class LateStream:
             self.ms_per_matmul = max((time.perf_counter() - t0) * 1e3 / 8, 1e-3)
         self.reps = max(1, int(np.ceil(self.ms / self.ms_per_matmul)))
 
+    def resize(self, ms):
+        """`ms` milliseconds of late work per hold from here on, by the timing made at construction"""
+        self.ms = float(ms)
+        self.reps = max(1, int(np.ceil(self.ms / self.ms_per_matmul)))
+
     def hold(self):
         """enqueue the late work on the stream (call under `with torch.cuda.stream(self.stream)` or not: it names the stream)"""
         import torch
@@ -189,6 +194,53 @@ class LateStream:
 
 def late_stream(ms):
     return LateStream(ms)
+
+
+SCRUB16, SCRUB32, SCRUB_F = 0x3333, 0x33333333, -7777.0   # what a host buffer holds once its call has returned
+
+
+def scrub(*buffers, ids=(), max_streams=0):
+    """Overwrite pinned host tensors in place, as a caller that reuses its buffers on return: samples SCRUB16, bytes FILL,
+    int32 arrays SCRUB32 (no rate, packet size, bit count, request size or room label a test uses), floats SCRUB_F.  `ids`:
+    arrays of stream ids become max_streams - 1 - id -- other ids, still distinct and inside the context: the kernels index
+    the per-stream state by id unchecked, so a stale read of an id must show as a wrong result and a wrong state, never as a
+    write outside the state (max_streams even: no id stays what it was)."""
+    import torch
+    pattern = {torch.int16: SCRUB16, torch.uint8: FILL, torch.int32: SCRUB32, torch.float32: SCRUB_F}
+    for t in buffers:
+        assert t.is_pinned(), "a buffer under test is not in pinned memory"
+        t.fill_(pattern[t.dtype])
+    for t in ids:
+        assert t.is_pinned() and t.dtype == torch.int32 and max_streams % 2 == 0
+        t.copy_(max_streams - 1 - t)
+
+
+class Held:
+    """Host-buffer calls on context `c` made while its four library streams wait behind the late caller's work
+    (lyra_hip_wait_for_stream: the public way to order library work behind a caller stream): an upload that such a call
+    enqueues cannot start before the late work ends, so a call that returns without having waited for it leaves the upload to
+    read whatever the caller has put into the buffer since.  call(fn, *buffers, ids=...) holds, asserts that the hold is live,
+    runs fn and scrubs the buffers on return.  `returned_early` counts the calls that came back with the late work pending
+    (calls that enqueue nothing behind it may: what matters is the result).  live = False: the call and the scrub without the
+    hold, for a call's first use, whose allocations and kernel loads no hold of a few milliseconds outlasts."""
+
+    def __init__(self, c, late):
+        self.c, self.late, self.calls, self.returned_early, self.live = c, late, 0, 0, True
+
+    def call(self, fn, *buffers, ids=()):
+        c, late = self.c, self.late
+        if not self.live:
+            got = fn()
+            scrub(*buffers, ids=ids, max_streams=c.max_streams)
+            return got
+        late.hold()
+        c._chk(c.L.lyra_hip_wait_for_stream(c.h, late.stream.cuda_stream))
+        assert not late.stream.query(), "the late work was over before the call was made: nothing held the library back"
+        got = fn()
+        self.calls += 1
+        self.returned_early += int(not late.stream.query())
+        scrub(*buffers, ids=ids, max_streams=c.max_streams)
+        return got
 
 
 def late_delay_ms(synchronised_call_s):
