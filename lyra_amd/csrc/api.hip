@@ -26,6 +26,7 @@
 #include "model.h"
 #include "tflite_pack.h"
 #include "pipelines.h"
+#include "host_staging.h"
 
 using namespace lyra;
 
@@ -33,6 +34,39 @@ namespace {
 std::string g_create_error;
 std::mutex g_create_mu;
 }  // namespace
+
+struct Dsa {                         // decode_samples_any_api.inc
+  int cap = 0;                       // rows the call buffers hold; set once all of them exist
+  int32_t* d_ids = nullptr;          // [2 call parities][4 rounds][4 lists][cap]
+  int32_t* d_info = nullptr;         // [2][4][cap][4]
+  int16_t* d_gan_new = nullptr;      // [2][4][cap][320]
+  int32_t* d_call = nullptr;         // [2][cap][4]
+  int16_t* d_pcm16 = nullptr;        // [cap][1280] internal-rate output in front of the resampler (noise stream only)
+};
+struct Dss {                         // decode_samples_streams_api.inc
+  int cap = 0;
+  int32_t* d_call = nullptr;         // [2 call parities][cap][DSS_CALL_WORDS]
+};
+
+// One request in flight of a pipelined host-buffer form (pipelines.h): its staging and what its end() has to know.  The same
+// type for every pipeline; where a pipeline's arrays lie in the four runs is host_staging.h.  Owned by the context
+// (lyra_hip_ctx::pl_slot), grown by host_slot_ensure, freed by host_slots_free.
+struct HostSlot {
+  uint8_t* h_in = nullptr;         // pinned: what goes up
+  uint8_t* h_out = nullptr;        // pinned: what comes down
+  uint8_t* d_in = nullptr;         // device: the kernels' inputs
+  uint8_t* d_out = nullptr;        // device: their outputs
+  size_t cap[4] = {};              // bytes of the four, in this order; grow-only
+  hipEvent_t ev_done = nullptr;    // behind the request's last operation (its download, where begin() enqueues one)
+  int B = 0;
+  // what the pipelines remember between begin() and end()
+  long total = 0;                  // samples of a packed request (decode_streams, decode_samples_streams)
+  int n = 0;                       // samples per row (decode_samples, decode_samples_any)
+  int nbytes = 0, dtx = 0;         // packet size and DTX switch (encode)
+  int kind = 0;                    // bridge_staging::Kind of the tick (bridge)
+  const int16_t* src = nullptr;    // the rows of a twin request ...
+  size_t src_bytes = 0;            // ... and their size (twin_fetch)
+};
 
 struct lyra_hip_ctx {
   int device = 0;
@@ -144,16 +178,15 @@ struct lyra_hip_ctx {
   float* d_ds_feat = nullptr;        // [ds_cap][64] features of the rows' packets / of the hops that start (decode stream only)
   unsigned* d_ds_err = nullptr;      // invalid packet sizes + packets that found the ring full
   long n_ds_calls = 0;
-  void* ds_host = nullptr;           // DsHostSlot[2]: the two requests in flight of lyra_hip_decode_samples_begin / _end
-  void* dsa = nullptr;               // Dsa (decode_samples_any_api.inc): call buffers and host slots of lyra_hip_decode_samples_any_*
-  void* dss = nullptr;               // Dss (decode_samples_streams_api.inc): call words and host slots of lyra_hip_decode_samples_streams_*
-  void* es_host = nullptr;           // EsHost (encode_streams_api.inc): the two slots of lyra_hip_encode_streams_begin / _end
-  // every pipelined host-buffer form (pipelines.h): requests begun / ended so far, by pipeline
+  Dsa dsa;                           // the call buffers of lyra_hip_decode_samples_any_dev (decode_samples_any_api.inc)
+  Dss dss;                           // the call words of lyra_hip_decode_samples_streams_dev (decode_samples_streams_api.inc)
+  // every pipelined host-buffer form (pipelines.h): requests begun / ended so far, by pipeline, and the staging of the
+  // requests in flight: request i of pipeline p uses pl_slot[p][i % PL_DEPTH]
   long pl_begun[PL_COUNT] = {}, pl_ended[PL_COUNT] = {};
+  HostSlot pl_slot[PL_COUNT][PL_DEPTH];
   // lyra_hip_decode_streams_dev / _begin / _end (decode_streams_api.inc)
   int16_t* d_dstr16[2] = {};         // [dstr16_cap][320] the 16 kHz hop of a call without d_pcm16, by lossy-call parity as d_lossy_gan
   int dstr16_cap = 0;
-  void* dstr_host = nullptr;         // DstrHost: the two slots of lyra_hip_decode_streams_begin / _end
   // the conference bridge (bridge_api.inc)
   unsigned* d_bridge_err = nullptr;  // d_order entries outside [0, B) that bridge_mix_kernel skipped
   int16_t* d_brg_mix[2] = {};        // [brg_cap][320] the mix of a tick without d_mix, by lossy-call parity as d_dstr16
@@ -162,7 +195,6 @@ struct lyra_hip_ctx {
   int32_t* d_brg_const = nullptr;    // [2][max_streams] the encode leg's constants: 16000 in every row | 320 * b
   hipEvent_t ev_brg_mix = nullptr;   // the tick's edge: recorded on sn behind lossy_mix_kernel, waited for by se[0]
   hipEvent_t lossy_mix_hook = nullptr;   // set by the bridge around lossy_tick_launch only: recorded on sn behind lossy_mix_kernel
-  void* brg_host = nullptr;          // BrgHost: the two slots of lyra_hip_bridge_begin / _end
   // loudest-N selection (speakers_api.inc): the scratch of its three kernels, [2] by lossy-call parity as d_brg_mix
   int32_t* d_spk_list[2] = {};       // [spk_cap][8] the speaker rows of every room, -1 padded
   int32_t* d_spk_pos_room[2] = {};   // [spk_cap] the room of every position of the index (-1: none)
@@ -202,7 +234,13 @@ struct lyra_hip_ctx {
   bool zc(int B) const { return h_zc && B <= ZC_MAX; }
   uint8_t* d_twin_args = nullptr;
   size_t twin_args_cap = 0, twin_args_used = 0;
-  void* pipe = nullptr;            // PipeState (pipe_api.inc): the two-deep pipelined host-buffer calls, created on first use
+  // lyra_hip_encode_begin, lyra_hip_decode_end and lyra_hip_twin_fetch_begin / _end (pipe_api.inc) beside their slots:
+  hipStream_t s_up = nullptr, s_down = nullptr;   // the copy streams, borrowed from the context (pipe_ensure)
+  hipEvent_t ev_pipe_up[PL_DEPTH] = {};           // the end of an overlapped upload of lyra_hip_encode_begin, by slot
+  // the decoder twin's output rows are double-buffered: the request being assembled owns d_twin_out / d_twin_ext, the
+  // request before it (whose download may not have been asked for yet) the pair parked here
+  int16_t* d_twin_alt_out = nullptr; int16_t* d_twin_alt_ext = nullptr;
+  size_t twin_alt_out_cap = 0, twin_alt_ext_cap = 0;
   void* span_calls = nullptr;      // SpanCalls (spans_api.inc): plan rows and scratch of the time-parallel span calls, created on first use
   void* bsp = nullptr;             // BspState (bridge_spans_api.inc): index staging and scratch of the bridge over spans, created on first use
   int tile_div[6] = {1, 1, 1, 1, 1, 1};   // tiles per workgroup of each stage kernel (LYRA_TILE_LOOP), see tile_div()
@@ -269,9 +307,91 @@ bool pl_any_in_flight(const lyra_hip_ctx* c) {   // ... or a decoder-twin reques
   return c->twin_out_n != 0;
 }
 
-int pipe_sync(lyra_hip_ctx* c);   // the copy streams of the pipelined host-buffer calls (pipe_api.inc)
-int sync_all(lyra_hip_ctx* c) {
-  { int rc = pipe_sync(c); if (rc) return rc; }
+
+// ---- the staging slots of the pipelined forms ----
+// request begun next / the oldest request in flight
+HostSlot& host_slot_begin(lyra_hip_ctx* c, Pipeline p) { return c->pl_slot[p][c->pl_begun[p] % PL_DEPTH]; }
+HostSlot& host_slot_end(lyra_hip_ctx* c, Pipeline p) { return c->pl_slot[p][c->pl_ended[p] % PL_DEPTH]; }
+template <class T>
+T* slot_at(uint8_t* run, size_t offset) { return reinterpret_cast<T*>(run + offset); }
+
+int host_slot_event(lyra_hip_ctx* c, HostSlot& S) {
+  if (!S.ev_done) HIPCHK(c, hipEventCreateWithFlags(&S.ev_done, hipEventDisableTiming));
+  return 0;
+}
+// The slot's event and room for a request.  Each pipeline has its sizing rule (host_staging.h `room`): most ask for the room of
+// max_streams rows, so the first call allocates and no later one does; decode_samples_streams asks for the rows of the request
+// and grows.  A run that is too small is freed and allocated anew; its capacity is recorded only after success, so a call
+// after a failed allocation allocates exactly what is still missing.  Growth needs no stream synchronise: the slot's
+// previous user, two requests back, has ended -- its kernels have read d_in, its download has left d_out and h_out.
+int host_slot_ensure(lyra_hip_ctx* c, HostSlot& S, size_t in_bytes, size_t out_bytes, size_t d_in_bytes, size_t d_out_bytes) {
+  int rc = host_slot_event(c, S);
+  if (rc) return rc;
+  uint8_t** const run[4] = {&S.h_in, &S.h_out, &S.d_in, &S.d_out};
+  const size_t want[4] = {in_bytes, out_bytes, d_in_bytes, d_out_bytes};
+  for (int i = 0; i < 4; ++i) {
+    if (want[i] <= S.cap[i]) continue;
+    if (*run[i]) (void)(i < 2 ? hipHostFree(*run[i]) : hipFree(*run[i]));
+    *run[i] = nullptr;
+    S.cap[i] = 0;
+    if (i < 2) HIPCHK(c, hipHostMalloc((void**)run[i], want[i], hipHostMallocDefault));
+    else HIPCHK(c, hipMalloc((void**)run[i], want[i]));
+    S.cap[i] = want[i];
+  }
+  return 0;
+}
+int host_slot_ensure(lyra_hip_ctx* c, HostSlot& S, const host_staging::Room& r) {
+  return host_slot_ensure(c, S, r.h_in, r.h_out, r.d_in, r.d_out);
+}
+void host_slots_free(lyra_hip_ctx* c) {   // every slot of every pipeline (lyra_hip_destroy)
+  for (auto& slots : c->pl_slot)
+    for (HostSlot& S : slots) {
+      if (S.h_in) (void)hipHostFree(S.h_in);
+      if (S.h_out) (void)hipHostFree(S.h_out);
+      if (S.d_in) (void)hipFree(S.d_in);
+      if (S.d_out) (void)hipFree(S.d_out);
+      if (S.ev_done) (void)hipEventDestroy(S.ev_done);
+      S = HostSlot();
+    }
+}
+// The tail of every begin(): the event behind the request's last operation on `st_`, and the request counts as begun.
+int host_slot_begun(lyra_hip_ctx* c, Pipeline p, HostSlot& S, int B, hipStream_t st_) {
+  HIPCHK(c, hipEventRecord(S.ev_done, st_));
+  S.B = B;
+  c->pl_begun[p]++;
+  return 0;
+}
+// The head of every end(), in two steps, because a pipeline's own refusals lie between them.  host_slot_oldest: the oldest
+// request's slot, or null with the pipeline's refusal set (`who`: the bridge's three end() calls name themselves).
+// host_slot_ended: the slot is given back -- whatever happens afterwards -- and, for the pipelines whose begin() enqueues the
+// download (`wait`), the host waits for it; the others download in end(), on a stream of their choice.
+HostSlot* host_slot_oldest(lyra_hip_ctx* c, Pipeline p, const char* who = nullptr) {
+  if (pl_in_flight(c, p)) return &host_slot_end(c, p);
+  if (who) (void)fail(c, LYRA_HIP_EINVAL, "%s: no %s in flight", who, PL_IN_FLIGHT_NOUN[p]);
+  else (void)fail(c, LYRA_HIP_EINVAL, "%s_end: no %s in flight", PL_NAME[p], PL_IN_FLIGHT_NOUN[p]);
+  return nullptr;
+}
+int host_slot_ended(lyra_hip_ctx* c, Pipeline p, HostSlot& S, bool wait) {
+  c->pl_ended[p]++;
+  if (wait) HIPCHK(c, hipEventSynchronize(S.ev_done));
+  return 0;
+}
+
+// One word on the device that kernels count refused input in (read_error_counter): allocated, cleared, and published only
+// when both succeeded, so no call ever trusts an uncleared word.
+int err_word_ensure(lyra_hip_ctx* c, unsigned** slot) {
+  if (*slot) return 0;
+  unsigned* p = nullptr;
+  HIPCHK(c, dalloc(&p, 1));
+  if (hipMemset(p, 0, 4) != hipSuccess) {
+    (void)hipFree(p);
+    return fail(c, LYRA_HIP_EHIP, "clearing an error word failed");
+  }
+  *slot = p;
+  return 0;
+}
+
+int sync_all(lyra_hip_ctx* c) {   // (the copy streams of pipe_api.inc are library streams: covered)
   for (int k = 0; k < lyra_hip_ctx::KMAX; ++k) {
     if (c->se[k]) HIPCHK(c, hipStreamSynchronize(c->se[k]));
     if (c->sd[k]) HIPCHK(c, hipStreamSynchronize(c->sd[k]));
@@ -288,7 +408,6 @@ void dsa_free(lyra_hip_ctx* c);
 void dss_free(lyra_hip_ctx* c);
 void pipe_free(lyra_hip_ctx* c);
 void rates_free(lyra_hip_ctx* c);
-void es_free(lyra_hip_ctx* c);
 void dstr_free(lyra_hip_ctx* c);
 void brg_free(lyra_hip_ctx* c);
 void spk_free(lyra_hip_ctx* c);
@@ -897,10 +1016,7 @@ int encode16(lyra_hip_ctx* c, const int32_t* d_ids, int B, const int16_t* d_pcm,
   DEVSCOPE(c);
   int rc = ensure_scratch(c, B);
   if (rc) return rc;
-  if (d_bits && !c->d_mixed_err) {
-    HIPCHK(c, dalloc(&c->d_mixed_err, 1));
-    HIPCHK(c, hipMemset(c->d_mixed_err, 0, 4));
-  }
+  if (d_bits && (rc = err_word_ensure(c, &c->d_mixed_err))) return rc;
   return run_chunks(c, CALL_ENCQ, B, false, [&](int, int, int, int) {
     float* feat = encq_features(c);
     int32_t* live = nullptr;
@@ -1158,7 +1274,7 @@ void lyra_hip_destroy(lyra_hip_ctx* c) {
   dsa_free(c);
   dss_free(c);
   pipe_free(c);
-  es_free(c);
+  host_slots_free(c);
   dstr_free(c);
   brg_free(c);
   spk_free(c);

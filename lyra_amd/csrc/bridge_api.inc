@@ -1,7 +1,8 @@
 // bridge_api.inc -- part of api.hip, behind speakers_api.inc and shared_bridge_api.inc (the mixes it dispatches to): the
 // conference bridge (include/lyra_hip_bridge.h) and the entry points of its three kinds of tick -- the full mix, the loudest-N
 // selection (include/lyra_hip_speakers.h) and the shared encoders (include/lyra_hip_shared_bridge.h).  Each of the mix call,
-// the tick, begin() and end() is one body for all three; where the arrays of a tick lie in the staging is bridge_staging.h.
+// the tick, begin() and end() is one body for all three; where the arrays of a tick lie in the staging is bridge_staging.h,
+// the staging itself the context's slots of PL_BRIDGE (HostSlot, api.hip), with room for the largest tick of any kind.
 //   lyra_hip_bridge_mix_dev: bridge_mix_kernel alone (bridge_kernels.hip), a stateless encode-side call on se[0].
 //   lyra_hip_bridge_tick_dev: lossy_tick_launch (the decode leg, as lyra_hip_decode_lossy_mixed_dev at 16 kHz) -> the mix on
 //     se[0] -> lyra_hip_encode_streams_dev on the mix (every rate 16000, row b at 320 * b).  The one edge the composition adds:
@@ -21,52 +22,15 @@ namespace {
 
 using BrgKind = bridge_staging::Kind;
 
-struct BrgSlot {
-  uint8_t* h_in = nullptr;     // pinned: what goes up, as bridge_staging::layout(kind, B, E) says
-  uint8_t* h_out = nullptr;    // pinned: what comes down
-  uint8_t* d_in = nullptr;     // the same on the device (room for the largest tick of any kind: bridge_staging::slot_*_bytes)
-  uint8_t* d_out = nullptr;
-  hipEvent_t ev_done = nullptr;
-  int B = 0;
-  BrgKind kind = bridge_staging::FULL;   // which begin() filled the slot
-};
-struct BrgHost { BrgSlot slot[2]; };
-
 void brg_free(lyra_hip_ctx* c) {
   dfree(c->d_brg_mix[0], c->d_brg_mix[1], c->d_brg_flags[0], c->d_brg_flags[1], c->d_brg_const, c->d_bridge_err);
   c->brg_cap = 0;
   if (c->ev_brg_mix) (void)hipEventDestroy(c->ev_brg_mix);
   c->ev_brg_mix = nullptr;
-  BrgHost* H = static_cast<BrgHost*>(c->brg_host);
-  if (!H) return;
-  for (BrgSlot& S : H->slot) {
-    if (S.h_in) (void)hipHostFree(S.h_in);
-    if (S.h_out) (void)hipHostFree(S.h_out);
-    dfree(S.d_in, S.d_out);
-    if (S.ev_done) (void)hipEventDestroy(S.ev_done);
-  }
-  delete H;
-  c->brg_host = nullptr;
-}
-
-int brg_slot_ensure(lyra_hip_ctx* c, BrgSlot* S) {
-  const size_t in = bridge_staging::slot_in_bytes((size_t)c->max_streams), out = bridge_staging::slot_out_bytes((size_t)c->max_streams);
-  if (!S->h_in) HIPCHK(c, hipHostMalloc((void**)&S->h_in, in, hipHostMallocDefault));
-  if (!S->h_out) HIPCHK(c, hipHostMalloc((void**)&S->h_out, out, hipHostMallocDefault));
-  if (!S->d_in) HIPCHK(c, dalloc(&S->d_in, in));
-  if (!S->d_out) HIPCHK(c, dalloc(&S->d_out, out));
-  if (!S->ev_done) HIPCHK(c, hipEventCreateWithFlags(&S->ev_done, hipEventDisableTiming));
-  return 0;
 }
 
 // The error word of bridge_mix_kernel: all lyra_hip_bridge_mix_dev needs.
-int brg_ensure_mix(lyra_hip_ctx* c) {
-  if (!c->d_bridge_err) {
-    HIPCHK(c, dalloc(&c->d_bridge_err, 1));
-    HIPCHK(c, hipMemset(c->d_bridge_err, 0, 4));
-  }
-  return 0;
-}
+int brg_ensure_mix(lyra_hip_ctx* c) { return err_word_ensure(c, &c->d_bridge_err); }
 
 // The edge's event, the constants of the encode leg (every rate 16000, row b at sample 320 * b) and the tick's scratch: the mix and the comfort-noise flags of a call that was given none.  Two sets, picked by lossy-call parity
 // as d_dstr16 is (and like it not what keeps call n + 1 off call n's set today: tick n + 1's noise-stream half waits for tick
@@ -75,10 +39,7 @@ int brg_ensure(lyra_hip_ctx* c, int B) {
   int rc = brg_ensure_mix(c);
   if (rc) return rc;
   if (!c->ev_brg_mix) HIPCHK(c, hipEventCreateWithFlags(&c->ev_brg_mix, hipEventDisableTiming));
-  if (!c->d_mixed_err) {   // (encode16 would allocate it on the way: everything up front)
-    HIPCHK(c, dalloc(&c->d_mixed_err, 1));
-    HIPCHK(c, hipMemset(c->d_mixed_err, 0, 4));
-  }
+  if ((rc = err_word_ensure(c, &c->d_mixed_err))) return rc;   // (encode16 would allocate it on the way: everything up front)
   if (!c->d_brg_const) {
     const size_t n = (size_t)c->max_streams;
     std::vector<int32_t> h(2 * n);
@@ -288,11 +249,8 @@ int brg_begin_impl(lyra_hip_ctx* c, const char* what, const int32_t* ids, int B,
   }
   if ((rc = brg_admit(c, what))) return rc;
   DEVSCOPE(c);
-  if (!c->brg_host) c->brg_host = new BrgHost();
-  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->pl_begun[PL_BRIDGE] & 1];
-  if ((rc = brg_slot_ensure(c, &S))) return rc;
-  // (the slot's previous user, two ticks back, has ended: its kernels on every stream have read d_in, its download has left
-  // d_out and h_out)
+  HostSlot& S = host_slot_begin(c, PL_BRIDGE);
+  if ((rc = host_slot_ensure(c, S, host_staging::bridge((size_t)c->max_streams)))) return rc;
   const BrgKind kind = sb ? bridge_staging::SHARED : max_speakers ? bridge_staging::SPEAKERS : bridge_staging::FULL;
   const bridge_staging::Layout L = bridge_staging::layout(kind, (size_t)B, (size_t)E);
   int32_t* h = reinterpret_cast<int32_t*>(S.h_in);
@@ -381,24 +339,21 @@ int brg_begin_impl(lyra_hip_ctx* c, const char* what, const int32_t* ids, int B,
   HIPCHK(c, hipStreamWaitEvent(c->sq[0], c->ev_noise[(c->n_noise_calls - 1) & 1], 0));
   if (sb && E == 0) HIPCHK(c, hipStreamWaitEvent(c->sq[0], c->ev_encs[2][0], 0));
   HIPCHK(c, hipMemcpyAsync(S.h_out, S.d_out, L.out_bytes, hipMemcpyDeviceToHost, c->sq[0]));
-  HIPCHK(c, hipEventRecord(S.ev_done, c->sq[0]));
-  S.B = B;
   S.kind = kind;
-  c->pl_begun[PL_BRIDGE]++;
-  return 0;
+  return host_slot_begun(c, PL_BRIDGE, S, B, c->sq[0]);
 }
 
 // end() of every kind of tick: `kind` is the caller's, and the optional outputs are those its kind of tick has
 int brg_end_impl(lyra_hip_ctx* c, const char* what, BrgKind kind, uint8_t* out_packets, int32_t* out_packet_bytes, int32_t* is_noise,
                  int32_t* is_comfort_noise, int64_t* levels = nullptr, int32_t* is_speaker = nullptr, int32_t* slot_of = nullptr) {
-  if (!c->brg_host || c->pl_ended[PL_BRIDGE] == c->pl_begun[PL_BRIDGE]) return fail(c, LYRA_HIP_EINVAL, "%s: no tick in flight", what);
-  BrgSlot& S = static_cast<BrgHost*>(c->brg_host)->slot[c->pl_ended[PL_BRIDGE] & 1];
+  HostSlot* oldest = host_slot_oldest(c, PL_BRIDGE, what);
+  if (!oldest) return LYRA_HIP_EINVAL;
+  HostSlot& S = *oldest;
   static const char* const begun_by[] = {"the full-mix begin()", "lyra_hip_speakers_begin", "lyra_hip_shared_begin"};
   if (S.kind != kind) return fail(c, LYRA_HIP_EINVAL, "%s: the oldest tick was begun by %s", what, begun_by[S.kind]);
   if (!out_packets || !out_packet_bytes) return fail(c, LYRA_HIP_EINVAL, "%s: null pointer", what);
   DEVSCOPE(c);
-  c->pl_ended[PL_BRIDGE]++;                  // whatever happens below, the slot is given back
-  HIPCHK(c, hipEventSynchronize(S.ev_done));
+  if (const int rc = host_slot_ended(c, PL_BRIDGE, S, true)) return rc;
   const size_t n = (size_t)S.B;
   const bridge_staging::Layout L = bridge_staging::layout(kind, n, 0);   // (what comes down does not depend on E)
   const int32_t* o = reinterpret_cast<const int32_t*>(S.h_out);

@@ -19,32 +19,12 @@ static_assert(lyra::DSA_MAX_HOPS == LYRA_HIP_DECODE_SAMPLES_MAX_HOPS, "documente
 
 namespace {
 
-struct Dsa {
-  int cap = 0;                       // rows the call buffers hold; set once all of them exist
-  int32_t* d_ids = nullptr;          // [2 call parities][4 rounds][4 lists][cap]
-  int32_t* d_info = nullptr;         // [2][4][cap][4]
-  int16_t* d_gan_new = nullptr;      // [2][4][cap][320]
-  int32_t* d_call = nullptr;         // [2][cap][4]
-  int16_t* d_pcm16 = nullptr;        // [cap][1280] internal-rate output in front of the resampler (noise stream only)
-  DsHostSlot slot[2];                // lyra_hip_decode_samples_any_begin / _end (ds_host_begin, decode_samples_api.inc)
-};
-
-Dsa* dsa_of(lyra_hip_ctx* c) {
-  if (!c->dsa) c->dsa = new Dsa();
-  return static_cast<Dsa*>(c->dsa);
-}
+Dsa* dsa_of(lyra_hip_ctx* c) { return &c->dsa; }   // the call buffers (lyra_hip_ctx::dsa, api.hip)
 void dsa_free_call_buffers(Dsa* A) {
   dfree(A->d_ids, A->d_info, A->d_gan_new, A->d_call, A->d_pcm16);
   A->cap = 0;
 }
-void dsa_free(lyra_hip_ctx* c) {
-  Dsa* A = static_cast<Dsa*>(c->dsa);
-  if (!A) return;
-  ds_host_slots_free(A->slot);
-  dsa_free_call_buffers(A);
-  delete A;
-  c->dsa = nullptr;
-}
+void dsa_free(lyra_hip_ctx* c) { dsa_free_call_buffers(&c->dsa); }
 
 int dsa_ensure(lyra_hip_ctx* c, int B) {
   Dsa* A = dsa_of(c);
@@ -113,9 +93,9 @@ int dsa_check_size(lyra_hip_ctx* c, int num_samples, int sample_rate_hz) {
   return 0;
 }
 
-DsHostSlot* dsa_host_slots(lyra_hip_ctx* c) { return dsa_of(c)->slot; }
-const DsHostForm kDsaHostForm = {PL_DECODE_SAMPLES_ANY, "decode_samples_any", (size_t)DSA_MAX_HOPS * 960, dsa_host_slots,
-                                 dsa_check_size, lyra_hip_decode_samples_any_dev};
+static_assert(host_staging::MAX_HOPS == lyra::DSA_MAX_HOPS, "the staging's rows are the call's");
+const DsHostForm kDsaHostForm = {PL_DECODE_SAMPLES_ANY, "decode_samples_any", (size_t)DSA_MAX_HOPS, dsa_check_size,
+                                 lyra_hip_decode_samples_any_dev};
 
 }  // namespace
 

@@ -35,30 +35,7 @@ void ds_free_call_buffers(lyra_hip_ctx* c) {
   c->ds_cap = 0;
 }
 
-// One request in flight of the two uniform host forms, lyra_hip_decode_samples_begin / _end and lyra_hip_decode_samples_any_begin
-// / _end (two slots each): pinned staging for its arguments and a device row buffer for its result.
-struct DsHostSlot {
-  uint8_t* h_in = nullptr;     // pinned: ids [max_streams] | packet bytes [max_streams] | packets [max_streams][24]
-  int32_t* d_ids = nullptr; int32_t* d_nb = nullptr; uint8_t* d_pk = nullptr;
-  int16_t* d_out = nullptr;    // [max_streams][row]: 960 samples, DSA_MAX_HOPS * 960 for the any-size form
-  hipEvent_t ev_ready = nullptr;
-  int B = 0, n = 0;
-};
-void ds_host_slots_free(DsHostSlot* slots) {
-  for (int i = 0; i < 2; ++i) {
-    DsHostSlot& S = slots[i];
-    if (S.h_in) (void)hipHostFree(S.h_in);
-    dfree(S.d_ids, S.d_nb, S.d_pk, S.d_out);
-    if (S.ev_ready) (void)hipEventDestroy(S.ev_ready);
-  }
-}
-
 void ds_free(lyra_hip_ctx* c) {
-  if (DsHostSlot* slots = static_cast<DsHostSlot*>(c->ds_host)) {
-    ds_host_slots_free(slots);
-    delete[] slots;
-    c->ds_host = nullptr;
-  }
   ds_free_call_buffers(c);
   free_bufs(ds_stream_bufs(c));
   dfree(c->d_ds_err);
@@ -76,15 +53,7 @@ int ds_ensure(lyra_hip_ctx* c, int B) {
   int rc = ds_ensure_streams(c);
   if (!rc) rc = fade_ensure(c);
   if (rc) return rc;
-  if (!c->d_ds_err) {
-    unsigned* p = nullptr;
-    HIPCHK(c, dalloc(&p, 1));
-    if (hipMemset(p, 0, 4) != hipSuccess) {
-      (void)hipFree(p);
-      return fail(c, LYRA_HIP_EHIP, "decode_samples: clearing the error word failed");
-    }
-    c->d_ds_err = p;
-  }
+  if ((rc = err_word_ensure(c, &c->d_ds_err))) return rc;
   if (B <= c->ds_cap) return 0;
   if ((rc = sync_all(c))) return rc;   // (the buffers of the calls in flight)
   ds_free_call_buffers(c);
@@ -193,11 +162,11 @@ int ds_check_size(lyra_hip_ctx* c, int num_samples, int sample_rate_hz) {
 // and packets into pinned staging, uploads them on the decode-side stream and enqueues the `_dev` call into the slot's row
 // buffer; end() downloads the OLDEST begun request straight into the caller's memory -- on the (idle) quantizer stream
 // while a younger request's kernels run, on the noise stream itself when there is none -- and synchronises that stream only.
+// A request's slot: pinned staging for its arguments and a device row buffer for its result (host_staging::decode_samples).
 struct DsHostForm {
   Pipeline pl;
   const char* who;
-  size_t row;                                          // samples per stream of a slot's row buffer
-  DsHostSlot* (*slots)(lyra_hip_ctx*);                 // the form's two slots, created on first use
+  size_t hops;                                         // hops of 960 samples per stream in a slot's row buffer
   int (*check_size)(lyra_hip_ctx*, int num_samples, int sample_rate_hz);
   int (*dev)(lyra_hip_ctx*, const int32_t*, int, const uint8_t*, const int32_t*, int, int, int16_t*, int32_t*, int32_t*);
 };
@@ -211,53 +180,42 @@ int ds_host_begin(lyra_hip_ctx* c, const DsHostForm& F, const int32_t* ids, int 
   if ((rc = check_ids_host(c, ids, B))) return rc;
   DEVSCOPE(c);
   if ((rc = pl_admit(c, F.pl, F.who))) return rc;
-  DsHostSlot& S = F.slots(c)[c->pl_begun[F.pl] & 1];
-  const size_t n = (size_t)c->max_streams;
-  if (!S.h_in) HIPCHK(c, hipHostMalloc((void**)&S.h_in, n * 32, hipHostMallocDefault));
-  if (!S.d_ids) HIPCHK(c, dalloc(&S.d_ids, n));
-  if (!S.d_nb) HIPCHK(c, dalloc(&S.d_nb, n));
-  if (!S.d_pk) HIPCHK(c, dalloc(&S.d_pk, n * 24));
-  if (!S.d_out) HIPCHK(c, dalloc(&S.d_out, n * F.row));
-  if (!S.ev_ready) HIPCHK(c, hipEventCreateWithFlags(&S.ev_ready, hipEventDisableTiming));
-  // (the slot's previous user, two requests back, has ended: its kernels on both streams have read these buffers)
-  std::memcpy(S.h_in, ids, (size_t)B * 4);
-  std::memcpy(S.h_in + n * 4, packet_bytes, (size_t)B * 4);
-  std::memcpy(S.h_in + n * 8, packets, (size_t)B * LYRA_HIP_MAX_PACKET_BYTES);
-  HIPCHK(c, hipMemcpyAsync(S.d_ids, S.h_in, (size_t)B * 4, hipMemcpyHostToDevice, c->sd[0]));
-  HIPCHK(c, hipMemcpyAsync(S.d_nb, S.h_in + n * 4, (size_t)B * 4, hipMemcpyHostToDevice, c->sd[0]));
-  HIPCHK(c, hipMemcpyAsync(S.d_pk, S.h_in + n * 8, (size_t)B * LYRA_HIP_MAX_PACKET_BYTES, hipMemcpyHostToDevice, c->sd[0]));
-  if ((rc = F.dev(c, S.d_ids, B, S.d_pk, S.d_nb, num_samples, sample_rate_hz, S.d_out, nullptr, nullptr))) return rc;
-  HIPCHK(c, hipEventRecord(S.ev_ready, c->sn));
-  S.B = B;
+  HostSlot& S = host_slot_begin(c, F.pl);
+  const host_staging::DecodeSamples L = host_staging::decode_samples((size_t)c->max_streams, F.hops);
+  if ((rc = host_slot_ensure(c, S, L.room))) return rc;
+  std::memcpy(S.h_in + L.h_ids, ids, (size_t)B * 4);
+  std::memcpy(S.h_in + L.h_packet_bytes, packet_bytes, (size_t)B * 4);
+  std::memcpy(S.h_in + L.h_packets, packets, (size_t)B * LYRA_HIP_MAX_PACKET_BYTES);
+  int32_t* d_ids = slot_at<int32_t>(S.d_in, L.d_ids);
+  int32_t* d_nb = slot_at<int32_t>(S.d_in, L.d_packet_bytes);
+  uint8_t* d_pk = S.d_in + L.d_packets;
+  HIPCHK(c, hipMemcpyAsync(d_ids, S.h_in + L.h_ids, (size_t)B * 4, hipMemcpyHostToDevice, c->sd[0]));
+  HIPCHK(c, hipMemcpyAsync(d_nb, S.h_in + L.h_packet_bytes, (size_t)B * 4, hipMemcpyHostToDevice, c->sd[0]));
+  HIPCHK(c, hipMemcpyAsync(d_pk, S.h_in + L.h_packets, (size_t)B * LYRA_HIP_MAX_PACKET_BYTES, hipMemcpyHostToDevice, c->sd[0]));
+  if ((rc = F.dev(c, d_ids, B, d_pk, d_nb, num_samples, sample_rate_hz, slot_at<int16_t>(S.d_out, L.d_pcm), nullptr, nullptr)))
+    return rc;
   S.n = num_samples;
-  c->pl_begun[F.pl]++;
-  return 0;
+  return host_slot_begun(c, F.pl, S, B, c->sn);
 }
 
 int ds_host_end(lyra_hip_ctx* c, const DsHostForm& F, int16_t* pcm) {
   if (!c) return LYRA_HIP_EINVAL;
-  if (!pl_in_flight(c, F.pl)) return fail(c, LYRA_HIP_EINVAL, "%s_end: no request in flight", F.who);
-  DsHostSlot& S = F.slots(c)[c->pl_ended[F.pl] & 1];
+  HostSlot* oldest = host_slot_oldest(c, F.pl);
+  if (!oldest) return LYRA_HIP_EINVAL;
+  HostSlot& S = *oldest;
   if (S.n > 0 && !pcm) return fail(c, LYRA_HIP_EINVAL, "%s_end: null pointer", F.who);
   DEVSCOPE(c);
-  c->pl_ended[F.pl]++;             // whatever happens below, the slot is given back
-  if (S.n == 0) {
-    HIPCHK(c, hipEventSynchronize(S.ev_ready));
-    return 0;
-  }
+  const int rc = host_slot_ended(c, F.pl, S, S.n == 0);   // (a request of 0 samples has nothing to download: wait for its kernels)
+  if (rc || S.n == 0) return rc;
   const bool overlap = pl_in_flight(c, F.pl) != 0;
   hipStream_t down = overlap ? c->sq[0] : c->sn;
-  if (overlap) HIPCHK(c, hipStreamWaitEvent(down, S.ev_ready, 0));
+  if (overlap) HIPCHK(c, hipStreamWaitEvent(down, S.ev_done, 0));
   HIPCHK(c, hipMemcpyAsync(pcm, S.d_out, (size_t)S.B * (size_t)S.n * 2, hipMemcpyDeviceToHost, down));
   HIPCHK(c, hipStreamSynchronize(down));
   return 0;
 }
 
-DsHostSlot* ds_host_slots(lyra_hip_ctx* c) {
-  if (!c->ds_host) c->ds_host = new DsHostSlot[2]();
-  return static_cast<DsHostSlot*>(c->ds_host);
-}
-const DsHostForm kDsHostForm = {PL_DECODE_SAMPLES, "decode_samples", 960, ds_host_slots, ds_check_size, lyra_hip_decode_samples_dev};
+const DsHostForm kDsHostForm = {PL_DECODE_SAMPLES, "decode_samples", 1, ds_check_size, lyra_hip_decode_samples_dev};
 
 }  // namespace
 

@@ -16,50 +16,15 @@ static_assert(lyra::DSS_ROW_STRIDE == LYRA_HIP_DECODE_SAMPLES_MAX_HOPS * LYRA_HI
 
 namespace {
 
-struct DssSlot {
-  uint8_t* h_in = nullptr;     // pinned: [ids | packet_bytes | rates | sizes | offsets] int32, B each, then packets [B][23]
-  uint8_t* h_out = nullptr;    // pinned: [is_noise | is_comfort_noise] int32, B each, then the packed samples
-  uint8_t* d_in = nullptr;     // the same on the device
-  uint8_t* d_out = nullptr;
-  hipEvent_t ev_done = nullptr;
-  int cap = 0;                 // rows the four buffers hold
-  int B = 0;
-  long total = 0;              // samples of the packed request
-};
-struct Dss {
-  int cap = 0;
-  int32_t* d_call = nullptr;   // [2 call parities][cap][DSS_CALL_WORDS]
-  DssSlot slot[2];
-};
+static_assert(host_staging::MAX_HOPS * host_staging::MAX_EXT_HOP == lyra::DSS_ROW_STRIDE, "the staging's rows are the call's");
 
-constexpr size_t kDssInRow = 5 * 4 + LYRA_HIP_MAX_PACKET_BYTES;   // bytes per stream going up
-constexpr size_t kDssOutRow = 2 * 4 + (size_t)DSS_ROW_STRIDE * 2; // ... and at most coming down
-
-Dss* dss_of(lyra_hip_ctx* c) {
-  if (!c->dss) c->dss = new Dss();
-  return static_cast<Dss*>(c->dss);
-}
-void dss_slot_free(DssSlot* S) {
-  if (S->h_in) (void)hipHostFree(S->h_in);
-  if (S->h_out) (void)hipHostFree(S->h_out);
-  S->h_in = S->h_out = nullptr;
-  dfree(S->d_in, S->d_out);
-  S->cap = 0;
-}
 void dss_free(lyra_hip_ctx* c) {
-  Dss* A = static_cast<Dss*>(c->dss);
-  if (!A) return;
-  for (DssSlot& S : A->slot) {
-    dss_slot_free(&S);
-    if (S.ev_done) (void)hipEventDestroy(S.ev_done);
-  }
-  dfree(A->d_call);
-  delete A;
-  c->dss = nullptr;
+  dfree(c->dss.d_call);
+  c->dss.cap = 0;
 }
 
 int dss_ensure(lyra_hip_ctx* c, int B) {
-  Dss* A = dss_of(c);
+  Dss* A = &c->dss;
   if (B <= A->cap) return 0;
   int rc = sync_all(c);   // (the words of the calls in flight)
   if (rc) return rc;
@@ -67,21 +32,6 @@ int dss_ensure(lyra_hip_ctx* c, int B) {
   A->cap = 0;
   HIPCHK(c, dalloc(&A->d_call, (size_t)2 * DSS_CALL_WORDS * (size_t)B));
   A->cap = B;
-  return 0;
-}
-
-// Rows of the slot's staging.  The slot's previous user, two requests back, has ended (its kernels have read d_in, its
-// download has left d_out and h_out), so growing it disturbs nothing in flight.
-int dss_slot_ensure(lyra_hip_ctx* c, DssSlot* S, int B) {
-  if (!S->ev_done) HIPCHK(c, hipEventCreateWithFlags(&S->ev_done, hipEventDisableTiming));
-  if (B <= S->cap) return 0;
-  dss_slot_free(S);
-  const size_t n = (size_t)B;
-  HIPCHK(c, hipHostMalloc((void**)&S->h_in, n * kDssInRow, hipHostMallocDefault));
-  HIPCHK(c, hipHostMalloc((void**)&S->h_out, n * kDssOutRow, hipHostMallocDefault));
-  HIPCHK(c, dalloc(&S->d_in, n * kDssInRow));
-  HIPCHK(c, dalloc(&S->d_out, n * kDssOutRow));
-  S->cap = B;   // (only now: after a failed allocation the next call frees what exists and starts over)
   return 0;
 }
 
@@ -102,7 +52,7 @@ int dss_launch(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_pa
   int rc = dss_ensure_all(c, B);
   if (rc) return rc;
   Dsa* A = dsa_of(c);
-  Dss* S = dss_of(c);
+  const Dss* S = &c->dss;
   const size_t set = (size_t)(c->n_ds_calls & 1);
   DsCall K = {d_ids, B, d_packets, d_pkt_bytes, max_hops, true, nullptr, nullptr, nullptr, 0, A->d_pcm16, DSA_MAX_INTERNAL, true,
               d_is_noise, d_is_cn};
@@ -165,51 +115,48 @@ int lyra_hip_decode_samples_streams_begin(lyra_hip_ctx* c, const int32_t* ids, i
   if ((rc = pl_admit(c, PL_DECODE_SAMPLES_STREAMS, "decode_samples_streams_begin"))) return rc;
   DEVSCOPE(c);
   // everything the call allocates or builds on first use, BEFORE anything is enqueued: a failure here leaves the streams idle
-  DssSlot& S = dss_of(c)->slot[c->pl_begun[PL_DECODE_SAMPLES_STREAMS] & 1];
-  if ((rc = dss_slot_ensure(c, &S, B))) return rc;
-  if ((rc = dss_ensure_all(c, B))) return rc;
+  // (the slot holds the rows of the largest request it has carried: it grows with B, unlike the other pipelines')
+  HostSlot& S = host_slot_begin(c, PL_DECODE_SAMPLES_STREAMS);
   const size_t n = (size_t)B;
-  int32_t* h = reinterpret_cast<int32_t*>(S.h_in);
+  const host_staging::DecodeSamplesStreams L = host_staging::decode_samples_streams(n);
+  if ((rc = host_slot_ensure(c, S, L.room))) return rc;
+  if ((rc = dss_ensure_all(c, B))) return rc;
   std::vector<long> offs(n);
   const long total = dss_packed_offsets(num_samples, B, offs.data());
-  for (int b = 0; b < B; ++b) {
-    h[b] = ids[b];
-    h[n + b] = packet_bytes[b];
-    h[2 * n + b] = sample_rates[b];
-    h[3 * n + b] = num_samples[b];
-    h[4 * n + b] = (int32_t)offs[b];   // (at most max_streams * 3840 < 2^31: lyra_hip_create's bound on max_streams)
-  }
-  std::memcpy(S.h_in + n * 20, packets, n * LYRA_HIP_MAX_PACKET_BYTES);
+  std::memcpy(S.h_in + L.ids, ids, n * 4);
+  std::memcpy(S.h_in + L.packet_bytes, packet_bytes, n * 4);
+  std::memcpy(S.h_in + L.rates, sample_rates, n * 4);
+  std::memcpy(S.h_in + L.sizes, num_samples, n * 4);
+  int32_t* h_offsets = slot_at<int32_t>(S.h_in, L.offsets);
+  for (int b = 0; b < B; ++b) h_offsets[b] = (int32_t)offs[b];   // (at most max_streams * 3840 < 2^31: lyra_hip_create's bound on max_streams)
+  std::memcpy(S.h_in + L.packets, packets, n * LYRA_HIP_MAX_PACKET_BYTES);
   // one upload from pinned staging on the decode-side stream, in front of the call's first kernel
-  HIPCHK(c, hipMemcpyAsync(S.d_in, S.h_in, n * kDssInRow, hipMemcpyHostToDevice, c->sd[0]));
-  const int32_t* m = reinterpret_cast<const int32_t*>(S.d_in);
-  int32_t* flags = reinterpret_cast<int32_t*>(S.d_out);
-  int16_t* pcm = reinterpret_cast<int16_t*>(S.d_out + n * 8);
-  if ((rc = dss_launch(c, m, B, S.d_in + n * 20, m + n, m + 2 * n, m + 3 * n, dss_batch_rounds(sample_rates, num_samples, B), pcm,
-                       total, m + 4 * n, flags, flags + n)))
+  HIPCHK(c, hipMemcpyAsync(S.d_in, S.h_in, L.in_bytes, hipMemcpyHostToDevice, c->sd[0]));
+  if ((rc = dss_launch(c, slot_at<int32_t>(S.d_in, L.ids), B, S.d_in + L.packets, slot_at<int32_t>(S.d_in, L.packet_bytes),
+                       slot_at<int32_t>(S.d_in, L.rates), slot_at<int32_t>(S.d_in, L.sizes),
+                       dss_batch_rounds(sample_rates, num_samples, B), slot_at<int16_t>(S.d_out, L.pcm), total,
+                       slot_at<int32_t>(S.d_in, L.offsets), slot_at<int32_t>(S.d_out, L.is_noise),
+                       slot_at<int32_t>(S.d_out, L.is_comfort_noise))))
     return rc;
   // flags and samples are written by the noise-stream half: their download rides on that stream, behind the splice
-  HIPCHK(c, hipMemcpyAsync(S.h_out, S.d_out, n * 8 + (size_t)total * 2, hipMemcpyDeviceToHost, c->sn));
-  HIPCHK(c, hipEventRecord(S.ev_done, c->sn));
-  S.B = B;
+  HIPCHK(c, hipMemcpyAsync(S.h_out, S.d_out, L.pcm + (size_t)total * 2, hipMemcpyDeviceToHost, c->sn));
   S.total = total;
-  c->pl_begun[PL_DECODE_SAMPLES_STREAMS]++;
-  return 0;
+  return host_slot_begun(c, PL_DECODE_SAMPLES_STREAMS, S, B, c->sn);
 }
 
 int lyra_hip_decode_samples_streams_end(lyra_hip_ctx* c, int16_t* pcm, int32_t* is_noise, int32_t* is_comfort_noise) {
   if (!c) return LYRA_HIP_EINVAL;
-  if (!c->dss || c->pl_ended[PL_DECODE_SAMPLES_STREAMS] == c->pl_begun[PL_DECODE_SAMPLES_STREAMS])
-    return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_end: no request in flight");
-  DssSlot& S = dss_of(c)->slot[c->pl_ended[PL_DECODE_SAMPLES_STREAMS] & 1];
+  HostSlot* oldest = host_slot_oldest(c, PL_DECODE_SAMPLES_STREAMS);
+  if (!oldest) return LYRA_HIP_EINVAL;
+  HostSlot& S = *oldest;
   if (S.total > 0 && !pcm) return fail(c, LYRA_HIP_EINVAL, "decode_samples_streams_end: null pointer");
   DEVSCOPE(c);
-  c->pl_ended[PL_DECODE_SAMPLES_STREAMS]++;                  // whatever happens below, the slot is given back
-  HIPCHK(c, hipEventSynchronize(S.ev_done));
+  if (const int rc = host_slot_ended(c, PL_DECODE_SAMPLES_STREAMS, S, true)) return rc;
   const size_t n = (size_t)S.B;
-  if (is_noise) std::memcpy(is_noise, S.h_out, n * 4);
-  if (is_comfort_noise) std::memcpy(is_comfort_noise, S.h_out + n * 4, n * 4);
-  if (S.total > 0) std::memcpy(pcm, S.h_out + n * 8, (size_t)S.total * 2);
+  const host_staging::DecodeSamplesStreams L = host_staging::decode_samples_streams(n);
+  if (is_noise) std::memcpy(is_noise, S.h_out + L.is_noise, n * 4);
+  if (is_comfort_noise) std::memcpy(is_comfort_noise, S.h_out + L.is_comfort_noise, n * 4);
+  if (S.total > 0) std::memcpy(pcm, S.h_out + L.pcm, (size_t)S.total * 2);
   return 0;
 }
 

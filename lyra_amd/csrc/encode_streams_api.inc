@@ -3,51 +3,10 @@
 //   lyra_hip_encode_streams_dev: lyra_hip_encode_rates_dev with the DTX switch per row (logmel_streams_kernel: a row without
 //     DTX takes the path of an absent row through the estimator, lyra_encoder.cc:80) and with audio rows at offsets of their
 //     own inside one buffer (resample_streams_kernel: a row that leaves the buffer is an absent row).
-//   lyra_hip_encode_streams_begin / _end: its two-deep host-buffer form, as lyra_hip_encode_begin / _end (pipe_api.inc) with
-//     slots of its own.  begin() waits for the audio upload on the host in every branch, so the caller's buffer is free on
+//   lyra_hip_encode_streams_begin / _end: its two-deep host-buffer form, as lyra_hip_encode_begin / _end (pipe_api.inc); where
+//     the arrays lie in the slot: host_staging::encode_streams.  begin() waits for the audio upload on the host in every branch, so the caller's buffer is free on
 //     return and no kernel needs a cross-stream edge behind a copy.
 #include "../../include/lyra_hip_encode_streams.h"
-
-namespace {
-
-struct EsSlot {
-  int32_t* h_meta = nullptr;   // pinned: [ids | rates | bits | dtx | offsets], B each (room for max_streams each)
-  uint8_t* h_out = nullptr;    // pinned: [packets [max_streams][23] (24 apart per stream in total) | packet_bytes]
-  int32_t* d_meta = nullptr;   // the same five arrays on the device
-  int16_t* d_in = nullptr;     // [max_streams * 960] packed audio
-  uint8_t* d_pk = nullptr;     // [max_streams][23]
-  int32_t* d_len = nullptr;    // [max_streams]
-  hipEvent_t ev_done = nullptr;
-  int B = 0;
-};
-struct EsHost { EsSlot slot[2]; };
-
-void es_free(lyra_hip_ctx* c) {
-  EsHost* E = static_cast<EsHost*>(c->es_host);
-  if (!E) return;
-  for (EsSlot& S : E->slot) {
-    if (S.h_meta) (void)hipHostFree(S.h_meta);
-    if (S.h_out) (void)hipHostFree(S.h_out);
-    dfree(S.d_meta, S.d_in, S.d_pk, S.d_len);
-    if (S.ev_done) (void)hipEventDestroy(S.ev_done);
-  }
-  delete E;
-  c->es_host = nullptr;
-}
-
-int es_slot_ensure(lyra_hip_ctx* c, EsSlot* S) {
-  const size_t n = (size_t)c->max_streams;
-  if (!S->h_meta) HIPCHK(c, hipHostMalloc((void**)&S->h_meta, n * 5 * 4, hipHostMallocDefault));
-  if (!S->h_out) HIPCHK(c, hipHostMalloc((void**)&S->h_out, n * 24 + n * 4, hipHostMallocDefault));
-  if (!S->d_meta) HIPCHK(c, dalloc(&S->d_meta, n * 5));
-  if (!S->d_in) HIPCHK(c, dalloc(&S->d_in, n * LYRA_HIP_MAX_EXT_HOP));
-  if (!S->d_pk) HIPCHK(c, dalloc(&S->d_pk, n * LYRA_HIP_MAX_PACKET_BYTES));
-  if (!S->d_len) HIPCHK(c, dalloc(&S->d_len, n));
-  if (!S->ev_done) HIPCHK(c, hipEventCreateWithFlags(&S->ev_done, hipEventDisableTiming));
-  return 0;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -81,19 +40,18 @@ int lyra_hip_encode_streams_begin(lyra_hip_ctx* c, const int32_t* ids, int B, co
   DEVSCOPE(c);
   if ((rc = ensure_scratch(c, B))) return rc;
   if ((rc = rates_ensure(c))) return rc;
-  if (!c->es_host) c->es_host = new EsHost();
-  EsSlot& S = static_cast<EsHost*>(c->es_host)->slot[c->pl_begun[PL_ENCODE_STREAMS] & 1];
-  if ((rc = es_slot_ensure(c, &S))) return rc;
-  // (the slot's previous user, two calls back, has ended: its kernels have read d_meta / d_in, its download has left h_out)
-  const size_t n = (size_t)B;
-  int32_t* h = S.h_meta;
+  HostSlot& S = host_slot_begin(c, PL_ENCODE_STREAMS);
+  const host_staging::EncodeStreams L = host_staging::encode_streams((size_t)B, (size_t)c->max_streams);
+  if ((rc = host_slot_ensure(c, S, L.room))) return rc;
+  std::memcpy(S.h_in + L.ids, ids, (size_t)B * 4);
+  std::memcpy(S.h_in + L.rates, sample_rates, (size_t)B * 4);
+  std::memcpy(S.h_in + L.bits, num_bits, (size_t)B * 4);
+  int32_t* h_dtx = slot_at<int32_t>(S.h_in, L.dtx);
+  int32_t* h_offsets = slot_at<int32_t>(S.h_in, L.offsets);
   long total = 0;
   for (int b = 0; b < B; ++b) {
-    h[b] = ids[b];
-    h[n + b] = sample_rates[b];
-    h[2 * n + b] = num_bits[b];
-    h[3 * n + b] = dtx ? (dtx[b] != 0) : 0;
-    h[4 * n + b] = (int32_t)total;   // (at most max_streams * 960 < 2^31: lyra_hip_create's bound on max_streams)
+    h_dtx[b] = dtx ? (dtx[b] != 0) : 0;
+    h_offsets[b] = (int32_t)total;   // (at most max_streams * 960 < 2^31: lyra_hip_create's bound on max_streams)
     total += sample_rates[b] / 50;
   }
   // With another call of this pipeline in flight the uploads go on the copy stream (the noise stream, as pipe_api.inc) and run
@@ -101,34 +59,36 @@ int lyra_hip_encode_streams_begin(lyra_hip_ctx* c, const int32_t* ids, int B, co
   // caller's again on return, and every kernel below is enqueued after its inputs have arrived.  (The noise stream also ends
   // the decode-side calls: on a context that decodes as well this wait covers decoder kernels that are on it -- see the header.)
   hipStream_t up = c->pl_begun[PL_ENCODE_STREAMS] != c->pl_ended[PL_ENCODE_STREAMS] ? c->sn : c->se[0];
-  HIPCHK(c, hipMemcpyAsync(S.d_meta, h, n * 5 * 4, hipMemcpyHostToDevice, up));
-  HIPCHK(c, hipMemcpyAsync(S.d_in, pcm, (size_t)total * 2, hipMemcpyHostToDevice, up));
+  uint8_t* d_meta = S.d_in + L.d_meta;
+  int16_t* d_pcm = slot_at<int16_t>(S.d_in, L.d_pcm);
+  uint8_t* d_pk = S.d_out + L.d_packets;
+  int32_t* d_len = slot_at<int32_t>(S.d_out, L.d_packet_bytes);
+  HIPCHK(c, hipMemcpyAsync(d_meta, S.h_in, L.meta_bytes, hipMemcpyHostToDevice, up));
+  HIPCHK(c, hipMemcpyAsync(d_pcm, pcm, (size_t)total * 2, hipMemcpyHostToDevice, up));
   HIPCHK(c, hipStreamSynchronize(up));
   // empty packets, and the bytes behind a shorter one, read back as zeros; the extractor's stream is ahead of the quantizer's
-  HIPCHK(c, hipMemsetAsync(S.d_pk, 0, (size_t)B * LYRA_HIP_MAX_PACKET_BYTES, c->se[0]));
-  const int32_t* m = S.d_meta;
-  if ((rc = lyra_hip_encode_streams_dev(c, m, B, S.d_in, total, m + 4 * n, m + n, m + 2 * n, dtx ? m + 3 * n : nullptr, S.d_pk,
-                                        S.d_len)))
+  HIPCHK(c, hipMemsetAsync(d_pk, 0, (size_t)B * LYRA_HIP_MAX_PACKET_BYTES, c->se[0]));
+  if ((rc = lyra_hip_encode_streams_dev(c, slot_at<int32_t>(d_meta, L.ids), B, d_pcm, total, slot_at<int32_t>(d_meta, L.offsets),
+                                        slot_at<int32_t>(d_meta, L.rates), slot_at<int32_t>(d_meta, L.bits),
+                                        dtx ? slot_at<int32_t>(d_meta, L.dtx) : nullptr, d_pk, d_len)))
     return rc;
   // packets and lengths are written by the quantizer on sq[0] (the call is not split): their download rides on that stream
-  HIPCHK(c, hipMemcpyAsync(S.h_out, S.d_pk, (size_t)B * LYRA_HIP_MAX_PACKET_BYTES, hipMemcpyDeviceToHost, c->sq[0]));
-  HIPCHK(c, hipMemcpyAsync(S.h_out + (size_t)c->max_streams * 24, S.d_len, (size_t)B * 4, hipMemcpyDeviceToHost, c->sq[0]));
-  HIPCHK(c, hipEventRecord(S.ev_done, c->sq[0]));
-  S.B = B;
-  c->pl_begun[PL_ENCODE_STREAMS]++;
-  return 0;
+  HIPCHK(c, hipMemcpyAsync(S.h_out + L.h_packets, d_pk, (size_t)B * LYRA_HIP_MAX_PACKET_BYTES, hipMemcpyDeviceToHost, c->sq[0]));
+  HIPCHK(c, hipMemcpyAsync(S.h_out + L.h_packet_bytes, d_len, (size_t)B * 4, hipMemcpyDeviceToHost, c->sq[0]));
+  return host_slot_begun(c, PL_ENCODE_STREAMS, S, B, c->sq[0]);
 }
 
 int lyra_hip_encode_streams_end(lyra_hip_ctx* c, uint8_t* packets, int32_t* packet_bytes) {
   if (!c) return LYRA_HIP_EINVAL;
-  if (!c->es_host || c->pl_ended[PL_ENCODE_STREAMS] == c->pl_begun[PL_ENCODE_STREAMS]) return fail(c, LYRA_HIP_EINVAL, "encode_streams_end: no call in flight");
+  HostSlot* oldest = host_slot_oldest(c, PL_ENCODE_STREAMS);
+  if (!oldest) return LYRA_HIP_EINVAL;
   if (!packets || !packet_bytes) return fail(c, LYRA_HIP_EINVAL, "encode_streams_end: null pointer");
   DEVSCOPE(c);
-  EsSlot& S = static_cast<EsHost*>(c->es_host)->slot[c->pl_ended[PL_ENCODE_STREAMS] & 1];
-  c->pl_ended[PL_ENCODE_STREAMS]++;                   // whatever happens below, the slot is given back
-  HIPCHK(c, hipEventSynchronize(S.ev_done));
-  std::memcpy(packets, S.h_out, (size_t)S.B * LYRA_HIP_MAX_PACKET_BYTES);
-  std::memcpy(packet_bytes, S.h_out + (size_t)c->max_streams * 24, (size_t)S.B * 4);
+  HostSlot& S = *oldest;
+  if (const int rc = host_slot_ended(c, PL_ENCODE_STREAMS, S, true)) return rc;
+  const host_staging::EncodeStreams L = host_staging::encode_streams((size_t)S.B, (size_t)c->max_streams);
+  std::memcpy(packets, S.h_out + L.h_packets, (size_t)S.B * LYRA_HIP_MAX_PACKET_BYTES);
+  std::memcpy(packet_bytes, S.h_out + L.h_packet_bytes, (size_t)S.B * 4);
   return 0;
 }
 

@@ -26,10 +26,7 @@ void lossy_free(lyra_hip_ctx* c) {
 int lossy_ensure(lyra_hip_ctx* c, int B) {
   int rc = fade_ensure(c);
   if (rc) return rc;
-  if (!c->d_lossy_err) {
-    HIPCHK(c, dalloc(&c->d_lossy_err, 1));
-    HIPCHK(c, hipMemset(c->d_lossy_err, 0, 4));
-  }
+  if ((rc = err_word_ensure(c, &c->d_lossy_err))) return rc;
   if (B <= c->lossy_cap) return 0;
   if ((rc = sync_all(c))) return rc;   // (the buffers of the calls in flight)
   lossy_free_call_bufs(c);

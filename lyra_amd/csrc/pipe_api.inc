@@ -13,100 +13,35 @@
 
 namespace {
 
-struct PipeSlot {
-  uint8_t* h_in = nullptr;     // pinned: the stream ids (the audio goes up from the caller's memory)
-  uint8_t* h_out = nullptr;    // pinned: [packets | packet_bytes]
-  int16_t* d_in = nullptr;     // [max_streams][960] audio at the external rate
-  int16_t* d_16k = nullptr;    // [max_streams][320] ... resampled (external rate != 16 kHz)
-  int32_t* d_ids = nullptr;
-  uint8_t* d_pk = nullptr;     // [max_streams][23]
-  int32_t* d_len = nullptr;    // [max_streams]
-  hipEvent_t ev_up = nullptr, ev_done = nullptr;
-  int B = 0, nbytes = 0, dtx = 0;
-};
-struct PipeDec {               // lyra_hip_decode_begin / _end: one slot per call in flight
-  uint8_t* h_in = nullptr;     // pinned: [ids | packets]
-  int32_t* d_ids = nullptr;
-  uint8_t* d_pk = nullptr;     // [max_streams][23]
-  int16_t* d_pcm = nullptr;    // [max_streams][320]
-  hipEvent_t ev_ready = nullptr;
-  int B = 0;
-};
-struct PipeFetch {             // decoder twin: a request begun -- where its rows are and the event behind its last kernel
-  const int16_t* src = nullptr; size_t bytes = 0; hipEvent_t ev_ready = nullptr;
-};
-struct PipeState {
-  PipeSlot slot[2];
-  PipeFetch fetch[2];
-  PipeDec dec[2];
-  // Copy streams: the uploads of the encode pipeline and the downloads of the decoder twin overlap the kernels.  They are
-  // BORROWED from the context -- the noise-estimator stream, idle in both twins (the decoder twin runs its estimator on the
-  // decode-side stream) -- rather than created:
-  // a process's streams share a handful of hardware queues (GPU_MAX_HW_QUEUES, 4 by default), and every additional stream
-  // lands on a queue that a busy stream of this or the other twin's context already uses (measured: both twins on two
-  // threads 7.5 -> 4.5 M frames/s with two created copy streams per context).
-  hipStream_t s_up = nullptr, s_down = nullptr;
-  // the decoder twin's output rows are double-buffered: the request being assembled owns c->d_twin_out / d_twin_ext, the
-  // request before it (whose download may not have been asked for yet) the pair parked here
-  int16_t* alt_out = nullptr; int16_t* alt_ext = nullptr; size_t alt_out_cap = 0, alt_ext_cap = 0;
-};
-
-PipeState* pipe_of(lyra_hip_ctx* c) { return static_cast<PipeState*>(c->pipe); }
-
+// What these three pipelines have beside their slots (HostSlot, api.hip; host_staging::encode / decode; a twin request's slot
+// holds where its rows are and the event behind its last kernel).
+// Copy streams: the uploads of the encode pipeline and the downloads of the decoder twin overlap the kernels.  They are
+// BORROWED from the context -- the noise-estimator stream, idle in both twins (the decoder twin runs its estimator on the
+// decode-side stream) -- rather than created:
+// a process's streams share a handful of hardware queues (GPU_MAX_HW_QUEUES, 4 by default), and every additional stream
+// lands on a queue that a busy stream of this or the other twin's context already uses (measured: both twins on two
+// threads 7.5 -> 4.5 M frames/s with two created copy streams per context).
+// (both on the noise stream: with the streams of two contexts on queues 0-3 in the same order -- lyra_hip_create -- an
+// encoder twin then uses queues 0 (extractor), 2 (quantizer), 3 (uploads) and a decoder twin beside it queue 1 (decoder
+// chain) and 3 (downloads): only the two copy streams share a queue)
+// The events of all three pipelines' slots are created here, in front of every admission check.
 int pipe_ensure(lyra_hip_ctx* c) {
-  if (c->pipe) return 0;
-  PipeState* P = new PipeState();
-  c->pipe = P;
-  const unsigned ef = hipEventDisableTiming;
-  // (both on the noise stream: with the streams of two contexts on queues 0-3 in the same order -- lyra_hip_create -- an
-  // encoder twin then uses queues 0 (extractor), 2 (quantizer), 3 (uploads) and a decoder twin beside it queue 1 (decoder
-  // chain) and 3 (downloads): only the two copy streams share a queue)
-  P->s_up = c->sn;
-  P->s_down = c->sn;
-  for (int i = 0; i < 2; ++i) {
-    HIPCHK(c, hipEventCreateWithFlags(&P->slot[i].ev_up, ef));
-    HIPCHK(c, hipEventCreateWithFlags(&P->slot[i].ev_done, ef));
-    HIPCHK(c, hipEventCreateWithFlags(&P->fetch[i].ev_ready, ef));
-    HIPCHK(c, hipEventCreateWithFlags(&P->dec[i].ev_ready, ef));
+  c->s_up = c->sn;
+  c->s_down = c->sn;
+  for (int i = 0; i < PL_DEPTH; ++i) {
+    if (!c->ev_pipe_up[i]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_pipe_up[i], hipEventDisableTiming));
+    for (Pipeline p : {PL_ENCODE, PL_TWIN_FETCH, PL_DECODE})
+      if (const int rc = host_slot_event(c, c->pl_slot[p][i])) return rc;
   }
   return 0;
 }
-int pipe_slot_ensure(lyra_hip_ctx* c, PipeSlot* S) {
-  if (S->h_in) return 0;
-  const size_t n = (size_t)c->max_streams;
-  HIPCHK(c, hipHostMalloc((void**)&S->h_in, n * 4, hipHostMallocDefault));
-  HIPCHK(c, hipHostMalloc((void**)&S->h_out, n * 24 + n * 4, hipHostMallocDefault));
-  HIPCHK(c, dalloc(&S->d_in, n * 960));
-  HIPCHK(c, dalloc(&S->d_16k, n * 320));
-  HIPCHK(c, dalloc(&S->d_ids, n));
-  HIPCHK(c, dalloc(&S->d_pk, n * 24));
-  HIPCHK(c, dalloc(&S->d_len, n));
-  return 0;
-}
-int pipe_sync(lyra_hip_ctx*) { return 0; }   // (the copy streams are library streams: sync_all covers them)
 void pipe_free(lyra_hip_ctx* c) {
-  PipeState* P = pipe_of(c);
-  if (!P) return;
-  for (int i = 0; i < 2; ++i) {
-    PipeSlot& S = P->slot[i];
-    if (S.h_in) (void)hipHostFree(S.h_in);
-    if (S.h_out) (void)hipHostFree(S.h_out);
-    void* ds[] = {S.d_in, S.d_16k, S.d_ids, S.d_pk, S.d_len};
-    for (void* p : ds) if (p) (void)hipFree(p);
-    if (S.ev_up) (void)hipEventDestroy(S.ev_up);
-    if (S.ev_done) (void)hipEventDestroy(S.ev_done);
-    if (P->fetch[i].ev_ready) (void)hipEventDestroy(P->fetch[i].ev_ready);
-    PipeDec& Dd = P->dec[i];
-    if (Dd.h_in) (void)hipHostFree(Dd.h_in);
-    void* dd[] = {Dd.d_ids, Dd.d_pk, Dd.d_pcm};
-    for (void* p : dd) if (p) (void)hipFree(p);
-    if (Dd.ev_ready) (void)hipEventDestroy(Dd.ev_ready);
+  for (hipEvent_t& e : c->ev_pipe_up) {
+    if (e) (void)hipEventDestroy(e);
+    e = nullptr;
   }
-  if (P->alt_out) (void)hipFree(P->alt_out);
-  if (P->alt_ext) (void)hipFree(P->alt_ext);
-
-  delete P;
-  c->pipe = nullptr;
+  dfree(c->d_twin_alt_out, c->d_twin_alt_ext);
+  c->twin_alt_out_cap = c->twin_alt_ext_cap = 0;
 }
 }  // namespace
 
@@ -128,13 +63,18 @@ int lyra_hip_encode_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const int1
   DEVSCOPE(c);
   if ((rc = ensure_scratch(c, B))) return rc;
   if ((rc = pipe_ensure(c))) return rc;
-  PipeState* P = pipe_of(c);
   if ((rc = pl_admit(c, PL_ENCODE, "encode_begin"))) return rc;
-  PipeSlot& S = P->slot[c->pl_begun[PL_ENCODE] & 1];
-  if ((rc = pipe_slot_ensure(c, &S))) return rc;
+  HostSlot& S = host_slot_begin(c, PL_ENCODE);
+  const host_staging::Encode L = host_staging::encode((size_t)c->max_streams);
+  if ((rc = host_slot_ensure(c, S, L.room))) return rc;
+  int32_t* d_ids = slot_at<int32_t>(S.d_in, L.d_ids);
+  int16_t* d_in = slot_at<int16_t>(S.d_in, L.d_pcm);
+  int16_t* d_16k = slot_at<int16_t>(S.d_in, L.d_pcm16);
+  uint8_t* d_pk = S.d_out + L.d_packets;
+  int32_t* d_len = slot_at<int32_t>(S.d_out, L.d_packet_bytes);
+  hipEvent_t ev_up = c->ev_pipe_up[c->pl_begun[PL_ENCODE] % PL_DEPTH];
   const int n_ext = sample_rate_hz / 50, nbytes = (num_bits + 7) / 8;
   const size_t pcm_b = (size_t)B * n_ext * 2;
-  // The slot's previous user (call begun - 2) has ended: its kernels have consumed d_in / d_ids, its download has left h_out.
   // The audio goes up straight from the caller's memory (the runtime copies pageable memory at the speed of pinned memory on
   // this platform, profiles/r05_batch_twins_host_time.txt; a staging copy would cost a core 0.1-0.2 ms per hop) on the copy
   // stream, which carries nothing else: waiting for it here -- so that the caller may reuse `pcm` on return -- waits for the
@@ -143,16 +83,16 @@ int lyra_hip_encode_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const int1
   // the copy stream -- one more hardware queue of the few a process has (GPU_MAX_HW_QUEUES, 4 by default) -- stays unused,
   // so that a purely blocking caller (Encode = begin + end) runs exactly as lyra_hip_encode does.
   const bool overlap = c->pl_begun[PL_ENCODE] != c->pl_ended[PL_ENCODE];
-  hipStream_t up = overlap ? P->s_up : c->se[0];
-  std::memcpy(S.h_in, ids, (size_t)B * 4);
-  HIPCHK(c, hipMemcpyAsync(S.d_ids, S.h_in, (size_t)B * 4, hipMemcpyHostToDevice, up));
-  HIPCHK(c, hipMemcpyAsync(S.d_in, pcm, pcm_b, hipMemcpyHostToDevice, up));
+  hipStream_t up = overlap ? c->s_up : c->se[0];
+  std::memcpy(S.h_in + L.h_ids, ids, (size_t)B * 4);
+  HIPCHK(c, hipMemcpyAsync(d_ids, S.h_in + L.h_ids, (size_t)B * 4, hipMemcpyHostToDevice, up));
+  HIPCHK(c, hipMemcpyAsync(d_in, pcm, pcm_b, hipMemcpyHostToDevice, up));
   if (overlap) {
-    HIPCHK(c, hipEventRecord(S.ev_up, P->s_up));
-    HIPCHK(c, hipStreamSynchronize(P->s_up));
+    HIPCHK(c, hipEventRecord(ev_up, c->s_up));
+    HIPCHK(c, hipStreamSynchronize(c->s_up));
     for (int k = 0; k < c->nsub; ++k) {
-      HIPCHK(c, hipStreamWaitEvent(c->se[k], S.ev_up, 0));
-      HIPCHK(c, hipStreamWaitEvent(c->sq[k], S.ev_up, 0));
+      HIPCHK(c, hipStreamWaitEvent(c->se[k], ev_up, 0));
+      HIPCHK(c, hipStreamWaitEvent(c->sq[k], ev_up, 0));
     }
   } else {
     // The upload is waited for HERE, on the host, whatever nsub is (nothing of this pipeline is in flight in this branch, so
@@ -163,42 +103,40 @@ int lyra_hip_encode_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const int1
     // one place that had such an edge, lyra_hip_decode_begin's first form, misbehaved: profiles/EXPERIMENTS.md).
     HIPCHK(c, hipStreamSynchronize(c->se[0]));
   }
-  const int16_t* d16 = S.d_in;
+  const int16_t* d16 = d_in;
   if (sample_rate_hz != 16000) {   // lyra_encoder.cc:119-122: the encoder's own resampler
-    if ((rc = lyra_hip_resample_dev(c, LYRA_HIP_SIDE_ENCODER, S.d_ids, B, S.d_in, n_ext, sample_rate_hz, 16000, S.d_16k))) return rc;
-    d16 = S.d_16k;
+    if ((rc = lyra_hip_resample_dev(c, LYRA_HIP_SIDE_ENCODER, d_ids, B, d_in, n_ext, sample_rate_hz, 16000, d_16k))) return rc;
+    d16 = d_16k;
   }
   if (dtx) {
-    HIPCHK(c, hipMemsetAsync(S.d_pk, 0, (size_t)B * nbytes, c->se[0]));   // empty packets read back as zeros (lyra_hip_encode_dtx)
-    rc = lyra_hip_encode_dtx_dev(c, S.d_ids, B, d16, num_bits, S.d_pk, S.d_len);
+    HIPCHK(c, hipMemsetAsync(d_pk, 0, (size_t)B * nbytes, c->se[0]));   // empty packets read back as zeros (lyra_hip_encode_dtx)
+    rc = lyra_hip_encode_dtx_dev(c, d_ids, B, d16, num_bits, d_pk, d_len);
   } else {
-    rc = lyra_hip_encode_dev(c, S.d_ids, B, d16, num_bits, S.d_pk);
+    rc = lyra_hip_encode_dev(c, d_ids, B, d16, num_bits, d_pk);
   }
   if (rc) return rc;
   // the packets (and DTX's lengths) are written by the quantizer on sq[0]: their small download rides on that stream -- a
   // stream of its own would be one more hardware queue for a 94 KB copy, and a process holds only a few (GPU_MAX_HW_QUEUES)
   for (int k = 1; k < c->nsub; ++k)   // (a split batch: the chunks' quantizers run on sq[1..]; encq_done recorded their ends)
     HIPCHK(c, hipStreamWaitEvent(c->sq[0], c->ev_encs[c->sq_slot[k]][k], 0));
-  HIPCHK(c, hipMemcpyAsync(S.h_out, S.d_pk, (size_t)B * nbytes, hipMemcpyDeviceToHost, c->sq[0]));
-  if (dtx) HIPCHK(c, hipMemcpyAsync(S.h_out + (size_t)c->max_streams * 24, S.d_len, (size_t)B * 4, hipMemcpyDeviceToHost, c->sq[0]));
-  HIPCHK(c, hipEventRecord(S.ev_done, c->sq[0]));
-  S.B = B; S.nbytes = nbytes; S.dtx = dtx;
-  c->pl_begun[PL_ENCODE]++;
-  return 0;
+  HIPCHK(c, hipMemcpyAsync(S.h_out + L.h_packets, d_pk, (size_t)B * nbytes, hipMemcpyDeviceToHost, c->sq[0]));
+  if (dtx) HIPCHK(c, hipMemcpyAsync(S.h_out + L.h_packet_bytes, d_len, (size_t)B * 4, hipMemcpyDeviceToHost, c->sq[0]));
+  S.nbytes = nbytes; S.dtx = dtx;
+  return host_slot_begun(c, PL_ENCODE, S, B, c->sq[0]);
 }
 
 int lyra_hip_encode_end(lyra_hip_ctx* c, uint8_t* packets, int32_t* packet_bytes) {
   if (!c) return LYRA_HIP_EINVAL;
-  PipeState* P = pipe_of(c);
-  if (!P || c->pl_ended[PL_ENCODE] == c->pl_begun[PL_ENCODE]) return fail(c, LYRA_HIP_EINVAL, "encode_end: no call in flight");
+  HostSlot* oldest = host_slot_oldest(c, PL_ENCODE);
+  if (!oldest) return LYRA_HIP_EINVAL;
   if (!packets) return fail(c, LYRA_HIP_EINVAL, "null pointer");
   DEVSCOPE(c);
-  PipeSlot& S = P->slot[c->pl_ended[PL_ENCODE] & 1];
-  c->pl_ended[PL_ENCODE]++;                      // whatever happens below, the slot is given back
-  HIPCHK(c, hipEventSynchronize(S.ev_done));
-  std::memcpy(packets, S.h_out, (size_t)S.B * S.nbytes);
+  HostSlot& S = *oldest;
+  if (const int rc = host_slot_ended(c, PL_ENCODE, S, true)) return rc;
+  const host_staging::Encode L = host_staging::encode((size_t)c->max_streams);
+  std::memcpy(packets, S.h_out + L.h_packets, (size_t)S.B * S.nbytes);
   if (packet_bytes) {
-    if (S.dtx) std::memcpy(packet_bytes, S.h_out + (size_t)c->max_streams * 24, (size_t)S.B * 4);
+    if (S.dtx) std::memcpy(packet_bytes, S.h_out + L.h_packet_bytes, (size_t)S.B * 4);
     else for (int i = 0; i < S.B; ++i) packet_bytes[i] = S.nbytes;
   }
   return 0;
@@ -218,20 +156,15 @@ int lyra_hip_decode_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const uint
   DEVSCOPE(c);
   if ((rc = ensure_scratch(c, B))) return rc;
   if ((rc = pipe_ensure(c))) return rc;
-  PipeState* P = pipe_of(c);
   if ((rc = pl_admit(c, PL_DECODE, "decode_begin"))) return rc;
-  PipeDec& S = P->dec[c->pl_begun[PL_DECODE] & 1];
-  const size_t n = (size_t)c->max_streams;
-  if (!S.h_in) {
-    HIPCHK(c, hipHostMalloc((void**)&S.h_in, n * 4 + n * 24, hipHostMallocDefault));
-    HIPCHK(c, dalloc(&S.d_ids, n));
-    HIPCHK(c, dalloc(&S.d_pk, n * 24));
-    HIPCHK(c, dalloc(&S.d_pcm, n * 320));
-  }
+  HostSlot& S = host_slot_begin(c, PL_DECODE);
+  const host_staging::Decode L = host_staging::decode((size_t)c->max_streams);
+  if ((rc = host_slot_ensure(c, S, L.room))) return rc;
+  int32_t* d_ids = slot_at<int32_t>(S.d_in, L.d_ids);
+  uint8_t* d_pk = S.d_in + L.d_packets;
   const int nbytes = (num_bits + 7) / 8;
-  // (the slot's previous user, two calls back, has ended: its download has left d_pcm and its kernels have read d_pk)
-  std::memcpy(S.h_in, ids, (size_t)B * 4);
-  std::memcpy(S.h_in + n * 4, packets, (size_t)B * nbytes);
+  std::memcpy(S.h_in + L.h_ids, ids, (size_t)B * 4);
+  std::memcpy(S.h_in + L.h_packets, packets, (size_t)B * nbytes);
   // Each chunk of a split batch uploads its own rows on its own stream, so every kernel follows its inputs in stream
   // order.  (Round 6: with one upload on sd[0] and an event for the other chunks' streams, the second chunk of a call
   // begun while another was in flight decoded the packets the slot held two calls earlier.)
@@ -240,33 +173,31 @@ int lyra_hip_decode_begin(lyra_hip_ctx* c, const int32_t* ids, int B, const uint
     int lo = 0, cnt = B;
     if (nk > 1) chunk_of(c, B, k, &lo, &cnt);
     if (cnt <= 0) continue;
-    HIPCHK(c, hipMemcpyAsync(S.d_ids + lo, S.h_in + (size_t)lo * 4, (size_t)cnt * 4, hipMemcpyHostToDevice, c->sd[k]));
-    HIPCHK(c, hipMemcpyAsync(S.d_pk + (size_t)lo * nbytes, S.h_in + n * 4 + (size_t)lo * nbytes, (size_t)cnt * nbytes,
+    HIPCHK(c, hipMemcpyAsync(d_ids + lo, S.h_in + L.h_ids + (size_t)lo * 4, (size_t)cnt * 4, hipMemcpyHostToDevice, c->sd[k]));
+    HIPCHK(c, hipMemcpyAsync(d_pk + (size_t)lo * nbytes, S.h_in + L.h_packets + (size_t)lo * nbytes, (size_t)cnt * nbytes,
                              hipMemcpyHostToDevice, c->sd[k]));
   }
-  if ((rc = lyra_hip_decode_dev(c, S.d_ids, B, S.d_pk, num_bits, S.d_pcm))) return rc;
+  if ((rc = lyra_hip_decode_dev(c, d_ids, B, d_pk, num_bits, slot_at<int16_t>(S.d_out, L.d_pcm)))) return rc;
   {   // the chunks of a split batch end on sd[1..]: their "done" records (dec_side_done) are this call's
     const int done_slot = (int)((c->n_dec_calls - 1) & 1);
     for (int k = 1; k < c->nsub; ++k) HIPCHK(c, hipStreamWaitEvent(c->sd[0], c->ev_dec[done_slot][k], 0));
   }
-  HIPCHK(c, hipEventRecord(S.ev_ready, c->sd[0]));
-  S.B = B;
-  c->pl_begun[PL_DECODE]++;
-  return 0;
+  return host_slot_begun(c, PL_DECODE, S, B, c->sd[0]);
 }
 
 int lyra_hip_decode_end(lyra_hip_ctx* c, int16_t* pcm) {
   if (!c) return LYRA_HIP_EINVAL;
-  PipeState* P = pipe_of(c);
-  if (!P || c->pl_ended[PL_DECODE] == c->pl_begun[PL_DECODE]) return fail(c, LYRA_HIP_EINVAL, "decode_end: no call in flight");
+  HostSlot* oldest = host_slot_oldest(c, PL_DECODE);
+  if (!oldest) return LYRA_HIP_EINVAL;
   if (!pcm) return fail(c, LYRA_HIP_EINVAL, "null pointer");
   DEVSCOPE(c);
-  PipeDec& S = P->dec[c->pl_ended[PL_DECODE] & 1];
-  c->pl_ended[PL_DECODE]++;
+  HostSlot& S = *oldest;
+  (void)host_slot_ended(c, PL_DECODE, S, false);
   const bool overlap = c->pl_ended[PL_DECODE] != c->pl_begun[PL_DECODE];
-  hipStream_t down = overlap ? P->s_down : c->sd[0];
-  if (overlap) HIPCHK(c, hipStreamWaitEvent(P->s_down, S.ev_ready, 0));
-  HIPCHK(c, hipMemcpyAsync(pcm, S.d_pcm, (size_t)S.B * 640, hipMemcpyDeviceToHost, down));
+  hipStream_t down = overlap ? c->s_down : c->sd[0];
+  if (overlap) HIPCHK(c, hipStreamWaitEvent(c->s_down, S.ev_done, 0));
+  const host_staging::Decode L = host_staging::decode((size_t)c->max_streams);
+  HIPCHK(c, hipMemcpyAsync(pcm, S.d_out + L.d_pcm, (size_t)S.B * 640, hipMemcpyDeviceToHost, down));
   HIPCHK(c, hipStreamSynchronize(down));
   return 0;
 }
@@ -283,7 +214,6 @@ int lyra_hip_twin_fetch_begin(lyra_hip_ctx* c, int num_streams, int num_internal
   if (rc) return rc;
   DEVSCOPE(c);
   if ((rc = pipe_ensure(c))) return rc;
-  PipeState* P = pipe_of(c);
   const int n = num_internal_samples;
   auto abandon = [&](int code) {
     (void)hipStreamSynchronize(c->sd[0]);
@@ -297,8 +227,8 @@ int lyra_hip_twin_fetch_begin(lyra_hip_ctx* c, int num_streams, int num_internal
     const int assembled = c->twin_out_n;
     return abandon(fail(c, LYRA_HIP_EINVAL, "twin_fetch: %d samples requested, %d assembled", n, assembled));
   }
-  PipeFetch& F = P->fetch[c->pl_begun[PL_TWIN_FETCH] & 1];
-  F.bytes = 0;
+  HostSlot& F = host_slot_begin(c, PL_TWIN_FETCH);   // (no staging: the rows stay where the twin calls assembled them)
+  F.src_bytes = 0;
   F.src = nullptr;
   if (n > 0) {
     const int16_t* src = c->d_twin_out;
@@ -328,35 +258,34 @@ int lyra_hip_twin_fetch_begin(lyra_hip_ctx* c, int num_streams, int num_internal
       row = (size_t)n_ext;
     }
     F.src = src;
-    F.bytes = (size_t)num_streams * row * 2;
+    F.src_bytes = (size_t)num_streams * row * 2;
   }
-  HIPCHK(c, hipEventRecord(F.ev_ready, c->sd[0]));
+  if ((rc = host_slot_begun(c, PL_TWIN_FETCH, F, num_streams, c->sd[0]))) return rc;
   // The staged host arguments of this request stay where they are until the stream has consumed them: the next request
   // stages into the OTHER half of the arena (twin_stage), whose previous user has ended by then.  Likewise its rows: the
   // next request assembles into the other pair of buffers.
-  std::swap(c->d_twin_out, P->alt_out); std::swap(c->twin_out_cap, P->alt_out_cap);
-  std::swap(c->d_twin_ext, P->alt_ext); std::swap(c->twin_ext_cap, P->alt_ext_cap);
+  std::swap(c->d_twin_out, c->d_twin_alt_out); std::swap(c->twin_out_cap, c->twin_alt_out_cap);
+  std::swap(c->d_twin_ext, c->d_twin_alt_ext); std::swap(c->twin_ext_cap, c->twin_alt_ext_cap);
   c->twin_args_used = 0;
   c->twin_out_n = 0;
-  c->pl_begun[PL_TWIN_FETCH]++;
   return 0;
 }
 
 int lyra_hip_twin_fetch_end(lyra_hip_ctx* c, int16_t* out) {
   if (!c) return LYRA_HIP_EINVAL;
-  PipeState* P = pipe_of(c);
-  if (!P || c->pl_ended[PL_TWIN_FETCH] == c->pl_begun[PL_TWIN_FETCH]) return fail(c, LYRA_HIP_EINVAL, "twin_fetch_end: no request in flight");
+  HostSlot* oldest = host_slot_oldest(c, PL_TWIN_FETCH);
+  if (!oldest) return LYRA_HIP_EINVAL;
   DEVSCOPE(c);
-  PipeFetch& F = P->fetch[c->pl_ended[PL_TWIN_FETCH] & 1];
-  c->pl_ended[PL_TWIN_FETCH]++;
+  HostSlot& F = *oldest;
+  (void)host_slot_ended(c, PL_TWIN_FETCH, F, false);
   // Nothing begun after this request: no kernels to overlap the download with -- it rides on the decode-side stream itself,
   // as in lyra_hip_twin_fetch, and the copy stream (one more of the process's few hardware queues) stays unused.
   const bool overlap = c->pl_ended[PL_TWIN_FETCH] != c->pl_begun[PL_TWIN_FETCH] || c->twin_args_used != 0;
-  hipStream_t down = overlap ? P->s_down : c->sd[0];
-  if (overlap) HIPCHK(c, hipStreamWaitEvent(P->s_down, F.ev_ready, 0));
-  if (F.bytes) {
+  hipStream_t down = overlap ? c->s_down : c->sd[0];
+  if (overlap) HIPCHK(c, hipStreamWaitEvent(c->s_down, F.ev_done, 0));
+  if (F.src_bytes) {
     if (!out) return fail(c, LYRA_HIP_EINVAL, "null pointer");
-    HIPCHK(c, hipMemcpyAsync(out, F.src, F.bytes, hipMemcpyDeviceToHost, down));
+    HIPCHK(c, hipMemcpyAsync(out, F.src, F.src_bytes, hipMemcpyDeviceToHost, down));
   }
   HIPCHK(c, hipStreamSynchronize(down));
   return 0;

@@ -1,7 +1,7 @@
 // pipelines.h -- the pipelined host-buffer forms of the C ABI (a `_begin` that enqueues, an `_end` that hands the oldest
 // result over) and which of them may be in flight together.  Plain C++: tests/test_pipeline_exclusion_cpu.py compiles this
 // header with the host compiler and prints the table.  The counters are lyra_hip_ctx::pl_begun / pl_ended, the checks
-// pl_admit and pl_any_in_flight (api.hip).
+// pl_admit and pl_any_in_flight, the staging of the requests in flight lyra_hip_ctx::pl_slot (api.hip; host_staging.h).
 #pragma once
 
 namespace lyra {
@@ -23,6 +23,9 @@ constexpr int PL_DEPTH = 2;    // requests of one pipeline in flight at most
 
 constexpr const char* PL_NAME[PL_COUNT] = {"encode", "decode", "twin_fetch", "encode_streams", "decode_streams",
                                            "decode_samples", "decode_samples_any", "decode_samples_streams", "bridge"};
+// what each pipeline's end() calls a request in its refusal "..._end: no <noun> in flight": the wordings the families grew
+// up with, which callers and the host classes' fakes know
+constexpr const char* PL_IN_FLIGHT_NOUN[PL_COUNT] = {"call", "call", "request", "call", "call", "request", "request", "request", "tick"};
 
 // PL_EXCLUDES[p][o]: p's begin() is refused while a request of o is in flight.  The two encode pipelines share the encode-side
 // streams' order, the decode pipelines the decode-side streams', a bridge tick runs on both sides' streams.

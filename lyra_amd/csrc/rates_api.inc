@@ -25,12 +25,11 @@ int rates_ensure(lyra_hip_ctx* c) {
       return fail(c, LYRA_HIP_EHIP, "rates: resampler design");
   NoiseP np[4];
   for (int i = 0; i < 4; ++i) np[i] = noise_params(kAll[i]);
+  if (const int rc = err_word_ensure(c, &c->d_rates_err)) return rc;
   HIPCHK(c, dalloc(&c->d_rs_tab, tab.size()));
   HIPCHK(c, dalloc(&c->d_noise_tab, 4));
-  HIPCHK(c, dalloc(&c->d_rates_err, 1));
   HIPCHK(c, hipMemcpy(c->d_rs_tab, tab.data(), tab.size() * sizeof(ResampleP), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->d_noise_tab, np, sizeof np, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemset(c->d_rates_err, 0, 4));
   HIPCHK(c, set_lds(logmel_rates_kernel, logmel_rates_lds_bytes()));
   HIPCHK(c, set_lds(logmel_streams_kernel, logmel_rates_lds_bytes()));
   return 0;

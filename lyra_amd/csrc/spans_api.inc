@@ -610,10 +610,7 @@ int encode_spans_planned_dev(lyra_hip_ctx* c, const char* what, const lyra_hip_s
   const size_t bits_bytes = frame_bits ? (size_t)dry.end_frame * sizeof(int32_t) : 0;
   if (bits_bytes) {
     if ((rc = span_lossy_ensure(c, S, st_, bits_bytes, 0, 0))) return rc;
-    if (!c->d_mixed_err) {   // the mixed quantizer's error word (mixed_api.inc), once per context
-      HIPCHK(c, dalloc(&c->d_mixed_err, 1));
-      HIPCHK(c, hipMemset(c->d_mixed_err, 0, 4));
-    }
+    if ((rc = err_word_ensure(c, &c->d_mixed_err))) return rc;   // the mixed quantizer's error word (mixed_api.inc)
     for (int s = 0; s < n_spans; ++s)   // frames outside the spans are not read: their entries are never looked at either
       if (spans[s].n_frames)
         std::memcpy(S.h_lists + (size_t)spans[s].first_frame * sizeof(int32_t), frame_bits + spans[s].first_frame,

@@ -57,15 +57,7 @@ int import_run(lyra_hip_ctx* c, const int32_t* d_ids, int B, const uint8_t* d_bl
   int rc = sync_all(c);
   if (rc) return rc;
   if ((sides & LYRA_HIP_STATE_DECODER) && (rc = ds_ensure_streams(c))) return rc;
-  if (!c->d_import_err) {
-    unsigned* p = nullptr;
-    HIPCHK(c, dalloc(&p, 1));
-    if (hipMemset(p, 0, 4) != hipSuccess) {
-      (void)hipFree(p);
-      return fail(c, LYRA_HIP_EHIP, "import_streams: clearing the error word failed");
-    }
-    c->d_import_err = p;
-  }
+  if ((rc = err_word_ensure(c, &c->d_import_err))) return rc;
   hipLaunchKernelGGL(state_import_kernel, dim3(B), dim3(256), 0, c->se[0], d_ids, B, c->max_streams, c->sm, c->d_ds_ring,
                      c->d_ds_gan, c->d_ds_cng, (unsigned)c->mode, c->cng_seed, sides, d_blobs, c->d_import_err);
   HIPCHK(c, hipGetLastError());

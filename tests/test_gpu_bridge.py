@@ -275,6 +275,32 @@ def test_begin_end_equal_the_dev_call(depth, streams):
 
 
 @pytest.mark.gpu
+def test_a_larger_tick_begun_behind_one_in_flight():
+    """A tick of 5 rows begun while a tick of 2 rows is in flight, on a context of 8 streams: the scratch of both legs grows
+    under a tick in flight.  Against the `_dev` call on the twin."""
+    ms, sizes = 8, (2, 5)
+    a, u = _ctx(ms), _ctx(ms)
+    try:
+        ids = np.arange(ms, dtype=np.int32)
+        ticks = [_host_script(B, 1, 23 + B)[0] for B in sizes]
+        for s in ticks:
+            s["rooms"][:] = 0   # everybody in one room
+        want = [_tick(u, _Bufs(B), ids[:B], s["pk"], s["sz"], s["rooms"], s["muted"], s["bits"], s["dtx"], SKIP_CN)
+                for B, s in zip(sizes, ticks)]
+        for B, s in zip(sizes, ticks):
+            begin(a, s, ids[:B], SKIP_CN)
+        for k in range(len(sizes)):
+            out, out_n, isn, icn = a.bridge_end()
+            w = want[k]
+            assert np.array_equal(out_n, w[0]) and np.array_equal(out, w[1]), f"tick {k}: packets"
+            assert np.array_equal(isn, w[4]) and np.array_equal(icn, w[5]), f"tick {k}: flags"
+        _same_state(a, u, ids, "after the last tick")
+    finally:
+        a.close()
+        u.close()
+
+
+@pytest.mark.gpu
 def test_begin_refusals_enqueue_nothing_and_pipelines_exclude_each_other():
     import lyra_amd
     B, ms = 37, 64

@@ -322,6 +322,40 @@ def test_odd_request_sizes_through_the_resampler(golden_dir, oracle_default):
         assert model.saw_two and model.saw_mix
 
 
+def test_host_form_with_a_larger_batch_begun_behind_one_in_flight(golden_dir, oracle_default):
+    """lyra_hip_decode_samples_begin / _end (the C calls: the Python mirror has none) on a fresh context: requests of 2, 5 and
+    max_streams = 8 rows, each begun while the one before is in flight -- the scratch grows under a request in flight, and at
+    8 rows the last row of every array of the slot borders the next array.  Against the blocking `_dev` call on a second
+    context."""
+    import ctypes
+    rate, ms = 48000, 8
+    rows, size = _packets(oracle_default, golden_dir, [120, 184, 64, 184, 120, 64, 184, 120], 3)
+    calls = [(2, 480), (5, 960), (8, 3)]
+    ctx, ref = _ctx(ms), _ctx(ms)
+    try:
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        begin, end = ctx.L.lyra_hip_decode_samples_begin, ctx.L.lyra_hip_decode_samples_end
+        begin.restype, begin.argtypes = ci, [vp, vp, ci, vp, vp, ci, ci]
+        end.restype, end.argtypes = ci, [vp, vp]
+        ids = np.arange(ms, dtype=np.int32)
+        want = [Device(ref, ids[:B], rate).call(rows[k][:B], size[:B], n)[0] for k, (B, n) in enumerate(calls)]
+        got = [np.full((B, n), 0x3333, np.int16) for B, n in calls]
+        assert end(ctx.h, got[0].ctypes.data) != 0                                  # nothing in flight
+        for k, (B, n) in enumerate(calls):
+            pk, nb = np.ascontiguousarray(rows[k][:B]), np.ascontiguousarray(size[:B])
+            assert begin(ctx.h, ids.ctypes.data, B, pk.ctypes.data, nb.ctypes.data, n, rate) == 0, ctx.last_error()
+            pk[...] = 0xEE                                                          # the arrays are the caller's again
+            if k:
+                assert end(ctx.h, got[k - 1].ctypes.data) == 0
+        assert end(ctx.h, got[-1].ctypes.data) == 0
+        for k, (w, g) in enumerate(zip(want, got)):
+            assert np.array_equal(w, g), f"request {k}"
+        assert np.array_equal(ctx.export_streams(ids), ref.export_streams(ids))
+        assert ctx.decode_samples_errors() == 0
+    finally:
+        ctx.close(); ref.close()
+
+
 @pytest.mark.parametrize("pipelined", [False, True])
 def test_device_decoder_class_equals_batch_decoder(tmp_path, golden_dir, pipelined):
     """DeviceLyraDecoder through lyra_amd/device_decoder_demo against BatchLyraDecoder through lyra_amd/decoder_demo on the

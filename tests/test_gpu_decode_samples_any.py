@@ -302,6 +302,31 @@ def test_host_form_and_refusals(golden_dir, oracle_default):
         ctx.close(); ref.close()
 
 
+def test_a_larger_batch_begun_behind_one_in_flight(golden_dir, oracle_default):
+    """Requests of 2, 5 and max_streams = 8 rows, each begun while the one before is in flight: the scratch grows under a
+    request in flight, and at 8 rows the last row of every array of the slot borders the next array.  Against the blocking
+    `_dev` call on a second context."""
+    rate, ms = 48000, 8
+    rows, size = _packets(oracle_default, golden_dir, [120, 184, 64, 184, 120, 64, 184, 120], 3)
+    calls = [(2, 441), (5, 1024), (8, 3840)]
+    ctx, ref = make_ctx(ms), make_ctx(ms)
+    try:
+        ids = np.arange(ms, dtype=np.int32)
+        want = [DeviceAny(ref, ids[:B], rate).call(rows[k][:B], size[:B], n)[0] for k, (B, n) in enumerate(calls)]
+        got = []
+        for k, (B, n) in enumerate(calls):
+            ctx.decode_samples_any_begin(rows[k][:B].copy(), size[:B].copy(), n, rate, ids[:B])
+            if k:
+                got.append(ctx.decode_samples_any_end())
+        got.append(ctx.decode_samples_any_end())
+        for k, (w, g) in enumerate(zip(want, got)):
+            assert np.array_equal(w, g), f"request {k}"
+        assert np.array_equal(ctx.export_streams(ids), ref.export_streams(ids))
+        assert ctx.decode_samples_errors() == 0
+    finally:
+        ctx.close(); ref.close()
+
+
 @pytest.mark.parametrize("pipelined", [False, True])
 def test_any_size_class_equals_batch_decoder(tmp_path, golden_dir, pipelined):
     """AnySizeDeviceLyraDecoder through lyra_amd/device_decoder_demo (LYRA_DEMO_ANY_SIZE=1) against BatchLyraDecoder, which keeps

@@ -313,6 +313,32 @@ def test_host_form_and_refusals(golden_dir, oracle_default):
         ctx.close(); ref.close()
 
 
+def test_a_larger_batch_begun_behind_one_in_flight(golden_dir, oracle_default):
+    """A request of 5 rows begun while a request of 2 rows is in flight, on a context of 8 streams: the second slot is
+    allocated for more rows than the first, and the scratch grows under a request in flight.  Then a request of 8 rows in the
+    first slot, which has to grow.  Against the blocking `_dev` call on a second context."""
+    rates = np.array([48000, 8000, 32000, 16000, 48000, 8000, 32000, 16000], np.int32)
+    rows, size = _packets(oracle_default, golden_dir, [120, 184, 64, 184, 120, 64, 184, 120], 3)
+    calls = [(2, [441, 161]), (5, [1024, 1, 641, 7, 3840]), (8, [2, 640, 2560, 1280, 959, 160, 128, 1024])]
+    ctx, ref = make_ctx(8), make_ctx(8)
+    try:
+        ids = np.arange(8, dtype=np.int32)
+        want = [DeviceStreams(ref, ids[:B], rates[:B]).call(rows[k][:B], size[:B], n) for k, (B, n) in enumerate(calls)]
+        got = []
+        for k, (B, n) in enumerate(calls):
+            ctx.decode_samples_streams_begin(rows[k][:B].copy(), size[:B].copy(), rates[:B].copy(), n, ids[:B])
+            if k:
+                got.append(ctx.decode_samples_streams_end())
+        got.append(ctx.decode_samples_streams_end())
+        for k, (w, g) in enumerate(zip(want, got)):
+            assert np.array_equal(np.concatenate(w[0]), g[0]), f"request {k}: packed pcm"
+            assert np.array_equal(w[1], g[1]) and np.array_equal(w[2], g[2]), f"request {k}: flags"
+        assert np.array_equal(ctx.export_streams(ids), ref.export_streams(ids))
+        assert ctx.decode_samples_errors() == 0 and ctx.rates_errors() == 0
+    finally:
+        ctx.close(); ref.close()
+
+
 def test_decode_pipelines_refuse_each_other_as_before():
     """Which decode pipeline's begin() is refused while which other one is in flight, for every ordered pair of the five decode
     pipelines and for a bridge tick against each of them in both directions.  The relation is written out here: every pair

@@ -424,6 +424,31 @@ def test_begin_end_equals_the_dev_call():
         u.close()
 
 
+@pytest.mark.gpu
+def test_a_larger_batch_begun_behind_one_in_flight():
+    """A hop of 5 rows begun while a hop of 2 rows is in flight, on a context of 8 streams: the scratch grows under a request
+    in flight.  Against the blocking `_dev` call on the twin."""
+    ms, sizes = 8, (2, 5)
+    rates = np.array([48000, 8000, 16000, 32000, 8000], np.int32)
+    pk, sz = _packets(np.random.default_rng(43), len(sizes), 5)
+    sz[:, :2] = 23
+    a, u = _ctx(ms), _ctx(ms)
+    try:
+        ids = np.arange(5, dtype=np.int32)
+        want = [_want_host(u, ids[:B], pk[k][:B], sz[k][:B], rates[:B]) for k, B in enumerate(sizes)]
+        for k, B in enumerate(sizes):
+            a.decode_streams_begin(pk[k][:B].copy(), sz[k][:B].copy(), rates[:B].copy(), stream_ids=ids[:B])
+        got = [a.decode_streams_end(), a.decode_streams_end()]
+        for k in range(len(sizes)):
+            for x, y, what in zip(got[k], want[k], ("samples", "is_noise", "is_comfort_noise")):
+                assert np.array_equal(x, y), (f"request {k}", what)
+        assert a.rates_errors() == 0 and a.decode_lossy_errors() == 0
+        _same_state(a, u, ids, "after the last request")
+    finally:
+        a.close()
+        u.close()
+
+
 # ---- 7. the class against the reference model -----------------------------------------------------------------------------
 
 N_STREAMS, T_SESSION = 8, 60

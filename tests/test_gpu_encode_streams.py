@@ -400,6 +400,34 @@ def test_begin_end_equals_the_dev_call(golden_dir):
         u.close()
 
 
+@pytest.mark.gpu
+def test_a_larger_batch_begun_behind_one_in_flight(golden_dir):
+    """Batches of 2, 5 and max_streams = 8 rows, each begun while the one before is in flight: the scratch grows under a request
+    in flight, and at 8 rows the last row of every array of the slot borders the next array.  Against the `_dev` call."""
+    ms, sizes = 8, (2, 5, 8)
+    rates = np.array([48000, 8000, 16000, 32000, 8000, 48000, 16000, 32000], np.int32)
+    bits = np.array([184, 64, 120, 184, 64, 120, 184, 64], np.int32)
+    flags = np.array([1, 0, 1, 0, 0, 1, 1, 1], np.int32)
+    pcm = _pcm_rows(golden_dir, ms, len(sizes), rates, 0, 6, 0)
+    a, u = _ctx(ms), _ctx(ms)
+    try:
+        ids = np.arange(ms, dtype=np.int32)
+        want = [_want_host(u, ids[:B], pcm[k][:B], rates[:B], bits[:B], flags[:B]) for k, B in enumerate(sizes)]
+        got = []
+        for k, B in enumerate(sizes):
+            a.encode_streams_begin(_pack(pcm[k][:B], rates[:B])[0], rates[:B], bits[:B], flags[:B], ids[:B])
+            if k:
+                got.append(a.encode_streams_end())
+        got.append(a.encode_streams_end())
+        for k in range(len(sizes)):
+            assert np.array_equal(got[k][1], want[k][1]) and np.array_equal(got[k][0], want[k][0]), f"request {k}"
+        assert a.rates_errors() == 0 and a.encode_mixed_errors() == 0
+        _same_state(a, u, ids, "after the last request")
+    finally:
+        a.close()
+        u.close()
+
+
 # ---- 7. the class against the reference model -----------------------------------------------------------------------------
 
 BITRATE_BITS = {3200: 64, 6000: 120, 9200: 184}

@@ -139,3 +139,81 @@ def test_pipelined_calls_with_stream_ids_that_change_every_hop(sub_batches):
             assert np.array_equal(got_pcm[t], want_pcm[t]), f"PCM of hop {t}"
     finally:
         a.close(); b.close()
+
+
+def test_a_larger_batch_begun_behind_one_in_flight():
+    """Batches of 2, 5 and max_streams = 8 rows, each begun while the one before is in flight: the scratch grows under a request
+    in flight, and at 8 rows the last row of every array of a slot borders the next array.  Encode (48 kHz, so the slot's
+    external-rate and 16 kHz rows are both in use) and decode, against the blocking calls on a second context."""
+    import lyra_amd
+    ms, bits, sizes = 8, 184, (2, 5, 8)
+    rng = np.random.Generator(np.random.PCG64(11))
+    p48 = [rng.integers(-20000, 20000, size=(B, 960)).astype(np.int16) for B in sizes]
+    a, b = lyra_amd.LyraHip(max_streams=ms), lyra_amd.LyraHip(max_streams=ms)
+    try:
+        ids = [np.arange(B, dtype=np.int32) for B in sizes]
+        want_pk = [a.encode(a.resample(p48[k], 48000, 16000, ids[k], side="encoder"), bits, ids[k]) for k in range(3)]
+        want_pcm = [a.decode(want_pk[k], bits, ids[k]) for k in range(3)]
+        got_pk, got_pcm = [], []
+        for k in range(3):
+            b.encode_begin(p48[k], bits, ids[k], sample_rate_hz=48000)
+            if k:
+                got_pk.append(b.encode_end())
+        got_pk.append(b.encode_end())
+        for k in range(3):
+            b.decode_begin(want_pk[k], bits, ids[k])
+            if k:
+                got_pcm.append(b.decode_end())
+        got_pcm.append(b.decode_end())
+        for k in range(3):
+            assert (got_pk[k][1] == bits // 8).all() and np.array_equal(got_pk[k][0], want_pk[k]), f"packets of request {k}"
+            assert np.array_equal(got_pcm[k], want_pcm[k]), f"PCM of request {k}"
+    finally:
+        a.close(); b.close()
+
+
+def test_twin_fetch_with_a_larger_batch_begun_behind_one_in_flight():
+    """lyra_hip_twin_fetch_begin / _end (the C calls: only the C++ classes drive them otherwise) on a fresh context: requests
+    of 2, 5 and max_streams = 8 decoded hops at 48 kHz, each assembled and begun while the one before is in flight, so the
+    twin's row buffers grow under a request in flight.  Against lyra_hip_twin_fetch on a second context."""
+    import lyra_amd
+
+    class Slice(C.Structure):
+        _fields_ = [(n, C.c_int32) for n in ("id", "gan_off", "gen_n", "cng_off", "cng_n", "fade", "fade_dir", "out_off",
+                                             "noise_row")]
+    vp, ci = C.c_void_p, C.c_int
+    rate, calls = 48000, [(2, 320), (5, 320), (8, 160)]
+    a, u = lyra_amd.LyraHip(max_streams=8), lyra_amd.LyraHip(max_streams=8)
+    try:
+        for L in (a.L, u.L):
+            L.lyra_hip_twin_decode.argtypes = [vp, vp, ci, vp, ci]
+            L.lyra_hip_twin_assemble.argtypes = [vp, vp, ci, ci]
+            L.lyra_hip_twin_fetch.argtypes = [vp, ci, ci, ci, vp]
+            L.lyra_hip_twin_fetch_begin.argtypes = [vp, ci, ci, ci]
+            L.lyra_hip_twin_fetch_end.argtypes = [vp, vp]
+
+        packets = np.random.Generator(np.random.PCG64(3)).integers(0, 256, size=(len(calls), 8, 23)).astype(np.uint8)
+
+        def assemble(ctx, k, B, n):
+            ids = np.arange(B, dtype=np.int32)
+            assert ctx.L.lyra_hip_twin_decode(ctx.h, ids.ctypes.data, B, packets[k].ctypes.data, 184) == 0, ctx.last_error()
+            sl = (Slice * B)(*[Slice(b, 0, n, 0, 0, 0, 1, 0, -1) for b in range(B)])
+            assert ctx.L.lyra_hip_twin_assemble(ctx.h, C.addressof(sl), B, n) == 0, ctx.last_error()
+
+        want = [np.zeros((B, 3 * n), np.int16) for B, n in calls]
+        got = [np.full((B, 3 * n), 0x3333, np.int16) for B, n in calls]
+        for k, (B, n) in enumerate(calls):
+            assemble(u, k, B, n)
+            assert u.L.lyra_hip_twin_fetch(u.h, B, n, rate, want[k].ctypes.data) == 0, u.last_error()
+        assert a.L.lyra_hip_twin_fetch_end(a.h, got[0].ctypes.data) != 0          # nothing in flight
+        for k, (B, n) in enumerate(calls):
+            assemble(a, k, B, n)
+            assert a.L.lyra_hip_twin_fetch_begin(a.h, B, n, rate) == 0, a.last_error()
+            if k:
+                assert a.L.lyra_hip_twin_fetch_end(a.h, got[k - 1].ctypes.data) == 0, a.last_error()
+        assert a.L.lyra_hip_twin_fetch_end(a.h, got[-1].ctypes.data) == 0, a.last_error()
+        for k in range(len(calls)):
+            assert want[k].any(), f"request {k}: the blocking twin delivered silence"
+            assert np.array_equal(got[k], want[k]), f"request {k}"
+    finally:
+        a.close(); u.close()

@@ -20,12 +20,14 @@ int main() {
     for (int o = 0; o < lyra::PL_COUNT; ++o) std::printf(" %d", (int)lyra::PL_EXCLUDES[p][o]);
     std::printf("\n");
   }
+  for (int p = 0; p < lyra::PL_COUNT; ++p) std::printf("%s %s\n", lyra::PL_NAME[p], lyra::PL_IN_FLIGHT_NOUN[p]);
   return 0;
 }
 '''
 
 NAMES = ["encode", "decode", "twin_fetch", "encode_streams", "decode_streams", "decode_samples", "decode_samples_any",
          "decode_samples_streams", "bridge"]
+PL_COUNT = len(NAMES)
 DECODE_GROUP = ["decode", "decode_streams", "decode_samples", "decode_samples_any", "decode_samples_streams"]
 # row: the pipeline whose begin() is asked; column: the pipeline in flight; 1: refused
 #            enc dec twf es  dst ds  dsa dss brg
@@ -41,7 +43,7 @@ RELATION = [[0, 0, 0, 1, 0, 0, 0, 0, 1],    # encode
 
 
 @pytest.fixture(scope="module")
-def table(tmp_path_factory):
+def table_lines(tmp_path_factory):
     if shutil.which("g++") is None:
         pytest.skip("no host C++ compiler")
     d = tmp_path_factory.mktemp("pipelines")
@@ -51,8 +53,13 @@ def table(tmp_path_factory):
                            "-o", str(exe)], timeout=300)
     lines = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60, check=True).stdout.split("\n")[:-1]
     count, depth = (int(x) for x in lines[0].split())
-    assert count == 9 and depth == 2 and len(lines) == 10
-    return {ln.split()[0]: [int(x) for x in ln.split()[1:]] for ln in lines[1:]}
+    assert count == 9 and depth == 2 and len(lines) == 1 + 2 * PL_COUNT
+    return lines
+
+
+@pytest.fixture(scope="module")
+def table(table_lines):
+    return {ln.split()[0]: [int(x) for x in ln.split()[1:]] for ln in table_lines[1:PL_COUNT + 1]}
 
 
 def test_the_table_is_the_relation_written_out_here(table):
@@ -75,6 +82,27 @@ def test_symmetric(table):
     for i, a in enumerate(NAMES):
         for j, b in enumerate(NAMES):
             assert table[a][j] == table[b][i], (a, b)
+
+
+def test_end_refusals_keep_their_wordings(table_lines):
+    """What each pipeline's end() calls a request when none is in flight: three wordings, kept as data beside the names."""
+    nouns = dict(ln.split() for ln in table_lines[PL_COUNT + 1:])
+    assert nouns == {"encode": "call", "decode": "call", "twin_fetch": "request", "encode_streams": "call", "decode_streams": "call",
+                     "decode_samples": "request", "decode_samples_any": "request", "decode_samples_streams": "request",
+                     "bridge": "tick"}
+
+
+def test_staging_layout_program_under_sanitizers(tmp_path):
+    """tests/host_staging/host_staging_test.cc over lyra_amd/csrc/host_staging.h: where the arrays of every pipeline's requests
+    lie in the four runs of a staging slot -- no overlap, 256-byte boundaries on the device, the alignments, at least the
+    room each family's own buffers had, no more than that plus padding."""
+    exe = str(tmp_path / "host_staging_test")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "lyra_amd", "csrc"), "-o", exe,
+                           os.path.join(ROOT, "tests", "host_staging", "host_staging_test.cc")], timeout=300)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1"))
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
 
 
 def test_the_one_gap_in_the_decode_group(table):
