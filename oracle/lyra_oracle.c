@@ -1466,11 +1466,9 @@ void lo_noise_update(lo_noise* n, const float* cur) {                  /* Update
   n->num_hops_received = (n->num_hops_received + 1) % n->num_hops_per_update;
 }
 
-/* ReceiveSamples for one full hop (:144-173): log-mel, decision, then decay or update.  Returns is_noise. */
-int lo_noise_receive(const lo_model* m, lo_noise* n, const int16_t* pcm, float* mel_out) {
-  float mel[MEL_BANDS];
-  logmel_core(m, &m->mel_rate[n->rate_idx], n->mel_prev, pcm, mel);
-  if (mel_out) memcpy(mel_out, mel, sizeof mel);
+/* The second half of ReceiveSamples (:161-173) on a log-mel vector handed in: decision, then decay or update.  Returns
+   is_noise.  (Its own entry point so that a test can drive the recurrence with mel bits computed elsewhere.) */
+int lo_noise_receive_mel(lo_noise* n, const float* mel) {
   n->is_noise = lo_noise_compute_is_noise(n, mel);
   if (n->is_noise) {
     for (int i = 0; i < MEL_BANDS; ++i) n->bound[i] = n->bound[i] * n->bound_decay;   /* DecayBounds */
@@ -1478,6 +1476,14 @@ int lo_noise_receive(const lo_model* m, lo_noise* n, const int16_t* pcm, float* 
     lo_noise_update(n, mel);
   }
   return n->is_noise;
+}
+
+/* ReceiveSamples for one full hop (:144-173): log-mel, then lo_noise_receive_mel.  Returns is_noise. */
+int lo_noise_receive(const lo_model* m, lo_noise* n, const int16_t* pcm, float* mel_out) {
+  float mel[MEL_BANDS];
+  logmel_core(m, &m->mel_rate[n->rate_idx], n->mel_prev, pcm, mel);
+  if (mel_out) memcpy(mel_out, mel, sizeof mel);
+  return lo_noise_receive_mel(n, mel);
 }
 void lo_noise_get(const lo_noise* n, float* estimate, float* bound) {
   if (estimate) memcpy(estimate, n->estimate, sizeof n->estimate);

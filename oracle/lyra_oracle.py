@@ -75,6 +75,7 @@ def _bind(L):
         L.lo_noise_compute_is_noise.argtypes = [C.c_void_p, C.c_void_p]
         L.lo_noise_update.argtypes = [C.c_void_p, C.c_void_p]
         L.lo_noise_receive.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.lo_noise_receive_mel.argtypes = [C.c_void_p, C.c_void_p]
         L.lo_noise_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.lo_resampler_new.restype = C.c_void_p
         L.lo_resampler_new.argtypes = [C.c_int, C.c_int]
@@ -269,6 +270,13 @@ class NoiseEstimator:
         assert pcm.size == 320
         mel = np.empty(160, np.float32)
         return bool(self.L.lo_noise_receive(self.o.h, self.h, _p(pcm), _p(mel))), mel
+
+    def ReceiveMel(self, mel):
+        """The second half of ReceiveSamples on a log-mel vector handed in (float32 [160]): decide, then decay or update
+        -> is_noise."""
+        mel = np.ascontiguousarray(mel, np.float32)
+        assert mel.size == 160
+        return bool(self.L.lo_noise_receive_mel(self.h, _p(mel)))
 
     def UpdateNoiseEstimate(self, mel):
         mel = np.ascontiguousarray(mel, np.float32)
