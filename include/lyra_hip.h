@@ -448,7 +448,8 @@ int lyra_hip_decode_lossy_mixed_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_i
  * server does between the two -- every participant hears the sum of the others, decode, mix-minus and encode in one call:
  * lyra_hip_bridge.h; the same with only the few loudest talkers of each room in the mix, and who is speaking reported:
  * lyra_hip_speakers.h; and that with every distinct mix of a room encoded once and the packet shared by everyone who hears it:
- * lyra_hip_shared_bridge.h; a RECORDED meeting through the bridge, all ticks time-parallel in one call: lyra_hip_bridge_spans.h. */
+ * lyra_hip_shared_bridge.h; a RECORDED meeting through the bridge, all ticks time-parallel in one call: lyra_hip_bridge_spans.h;
+ * and one whose participants join, leave and move rooms while it runs, still in one call: lyra_hip_spans_meeting.h. */
 #define LYRA_HIP_MAX_EXT_HOP 960   /* row stride, in samples, of external-rate audio in the calls below: the 48 kHz hop */
 int lyra_hip_encode_rates_dev(lyra_hip_ctx* ctx, const int32_t* d_stream_ids, int B,
                               const int16_t* d_pcm_ext /* [B][960] */, const int32_t* d_sample_rates /* [B] */,

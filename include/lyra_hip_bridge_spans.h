@@ -82,8 +82,8 @@
  *   spans' frames of the outputs only; the caller's arrays outside the spans are untouched.  out_packets rows read back zero
  *   behind each packet's bytes.  pcm16, mix, is_noise, is_comfort_noise, levels and is_speaker may be NULL.
  *
- * Out of scope: shared encoders over spans, membership that changes inside one call, request sizes other than one hop,
- * external sample rates (the bridge is 16 kHz by construction), pipelined begin / end forms. */
+ * Out of scope: shared encoders over spans, request sizes other than one hop, external sample rates (the bridge is 16 kHz by
+ * construction), pipelined begin / end forms.  Participants who join, leave or move rooms inside one call: lyra_hip_spans_meeting.h. */
 #ifndef LYRA_HIP_BRIDGE_SPANS_H_
 #define LYRA_HIP_BRIDGE_SPANS_H_
 

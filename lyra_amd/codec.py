@@ -535,12 +535,94 @@ def bridge_spans_plan(spans, rooms, lib=None):
     return order[:n_members.value].copy(), start[:n_rooms.value + 1].copy(), n_ticks.value
 
 
+MEETING_STAY_DTYPE = np.dtype([("participant", "<i4"), ("room", "<i4"), ("first_tick", "<i8"), ("n_ticks", "<i8")], align=True)
+MEETING_MAX_ENTRIES = 1 << 22   # LYRA_HIP_MEETING_MAX_ENTRIES
+
+
+class MeetingSpansCall(C.Structure):
+    """lyra_hip_spans_meeting_call (include/lyra_hip_spans_meeting.h)"""
+    _fields_ = [("spans", C.c_void_p), ("P", C.c_int), ("lane_ids", C.c_void_p), ("n_lanes", C.c_int), ("stays", C.c_void_p),
+                ("n_stays", C.c_int), ("d_packets", C.c_void_p), ("packet_bytes", C.c_void_p), ("d_muted", C.c_void_p),
+                ("flags", C.c_uint), ("num_bits", C.c_void_p), ("dtx", C.c_void_p), ("d_out_packets", C.c_void_p),
+                ("d_out_packet_bytes", C.c_void_p), ("d_pcm16", C.c_void_p), ("d_mix", C.c_void_p),
+                ("d_is_noise", C.c_void_p), ("d_is_comfort_noise", C.c_void_p), ("max_speakers", C.c_int),
+                ("d_levels", C.c_void_p), ("d_is_speaker", C.c_void_p)]
+
+
+def _signatures_spans_meeting():
+    """The same for include/lyra_hip_spans_meeting.h (tests/test_spans_meeting_cpu.py holds each entry to its prototype)."""
+    vp, ci, cu = C.c_void_p, C.c_int, C.c_uint
+    table = {
+        "spans_meeting_plan": [vp, ci, vp, ci] + [vp] * 7,
+        "spans_meeting_mix_dev": [vp, vp, ci, vp, ci, vp, vp, vp, ci, vp, vp, vp],
+        "spans_meeting_dev": [vp, vp],
+        "spans_meeting": [vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, cu, vp, vp, ci] + [vp] * 8,
+    }
+    return {"lyra_hip_" + name: (ci, args) for name, args in table.items()}
+
+
+_SIGNATURES_SPANS_MEETING = _signatures_spans_meeting()
+
+
+def _load_spans_meeting(L, path):
+    """_SIGNATURES_SPANS_MEETING applied to a loaded library; one that lacks a function of it is refused."""
+    for name, (restype, argtypes) in _SIGNATURES_SPANS_MEETING.items():
+        fn = getattr(L, name, None)
+        if fn is None:
+            raise LyraHipError(f"{path} does not export {name}")
+        fn.restype, fn.argtypes = restype, argtypes
+    return L
+
+
+def _stays(stays):
+    """[(participant, room, first_tick, n_ticks), ...] or a MEETING_STAY_DTYPE array -> contiguous MEETING_STAY_DTYPE array"""
+    if isinstance(stays, np.ndarray) and stays.dtype == MEETING_STAY_DTYPE:
+        return np.ascontiguousarray(stays)
+    return np.array([tuple(int(v) for v in s) for s in stays], MEETING_STAY_DTYPE).reshape(-1)
+
+
+def _meeting_args(spans, stays):
+    """participants of a meeting and its schedule -> (SPAN_DTYPE array [P], MEETING_STAY_DTYPE array); LyraHipError where the
+    shapes do not fit, before the library is called"""
+    sp, st = _spans(spans), _stays(stays)
+    if sp.size < 1:
+        raise LyraHipError("meeting: no participants")
+    if st.size and (st["participant"].min() < 0 or st["participant"].max() >= sp.size):
+        raise LyraHipError(f"meeting: a stay names a participant outside 0..{sp.size - 1}")
+    present = np.bincount(st["participant"], weights=st["n_ticks"], minlength=sp.size) if st.size else np.zeros(sp.size)
+    if np.any(present != sp["n_frames"]):
+        raise LyraHipError("meeting: the stays of a participant do not sum to its span's n_frames")
+    return sp, st
+
+
+def meeting_plan(spans, stays, lib=None):
+    """The data model of a meeting with a schedule, checked (lyra_hip_spans_meeting_plan; no GPU): spans are (stream_id,
+    first_frame, n_frames = present ticks) per participant, stays (participant, room, first_tick, n_ticks) sorted by
+    (participant, first_tick) -> dict(n_ticks, epoch_tick int64 [n_epochs + 1], epoch_entry int64 [n_epochs + 1],
+    entry_participant int32 [n_entries], entry_room int32 [n_entries]: the dense room number inside the epoch, -1 in no room).
+    LyraHipError for what the header calls LYRA_HIP_EINVAL."""
+    L = lib or _load()
+    sp, st = _meeting_args(spans, stays)
+    n_epochs, n_entries, n_ticks = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    head = (sp.ctypes.data, sp.size, st.ctypes.data if st.size else None, st.size, C.addressof(n_epochs), C.addressof(n_entries),
+            C.addressof(n_ticks))
+    if L.lyra_hip_spans_meeting_plan(*head, None, None, None, None) != 0:
+        raise LyraHipError("lyra_hip_spans_meeting_plan: invalid spans or stays")
+    tick, entry = np.zeros(n_epochs.value + 1, np.int64), np.zeros(n_epochs.value + 1, np.int64)
+    part, room = np.zeros(max(n_entries.value, 1), np.int32), np.zeros(max(n_entries.value, 1), np.int32)
+    if L.lyra_hip_spans_meeting_plan(*head, tick.ctypes.data, entry.ctypes.data, part.ctypes.data, room.ctypes.data) != 0:
+        raise LyraHipError("lyra_hip_spans_meeting_plan: invalid spans or stays")
+    return dict(n_ticks=n_ticks.value, epoch_tick=tick, epoch_entry=entry, entry_participant=part[:n_entries.value].copy(),
+                entry_room=room[:n_entries.value].copy())
+
+
 def _load(path=None):
     """The C-ABI library (default: library_path()); a second path loads a build variant beside it (lyra_amd/variants/).
     A library that lacks a function of _SIGNATURES, _SIGNATURES_SPANS_MIXED, _SIGNATURES_SPANS_RATES, _SIGNATURES_SPANS_PACKED,
     _SIGNATURES_ENCODE_STREAMS, _SIGNATURES_DECODE_STREAMS, _SIGNATURES_DECODE_SAMPLES_ANY or
     _SIGNATURES_DECODE_SAMPLES_STREAMS is refused, and so is one that lacks a function of _SIGNATURES_BRIDGE (_load_bridge) or _SIGNATURES_SPEAKERS
-    (_load_speakers) or _SIGNATURES_SHARED (_load_shared) or _SIGNATURES_BRIDGE_SPANS (_load_bridge_spans)."""
+    (_load_speakers) or _SIGNATURES_SHARED (_load_shared) or _SIGNATURES_BRIDGE_SPANS (_load_bridge_spans) or
+    _SIGNATURES_SPANS_MEETING (_load_spans_meeting)."""
     path = os.path.abspath(path or library_path())
     if path in _libs:
         return _libs[path]
@@ -568,7 +650,7 @@ def _load(path=None):
         if fn is None:
             raise LyraHipError(f"{path} does not export {name}")
         fn.restype, fn.argtypes = restype, argtypes
-    _libs[path] = _load_bridge_spans(_load_shared(_load_speakers(_load_bridge(L, path), path), path), path)
+    _libs[path] = _load_spans_meeting(_load_bridge_spans(_load_shared(_load_speakers(_load_bridge(L, path), path), path), path), path)
     return L
 
 
@@ -1962,6 +2044,75 @@ class LyraHip:
                                                out["out_packets"].ctypes.data, out["out_packet_bytes"].ctypes.data,
                                                out["pcm16"].ctypes.data, out["mix"].ctypes.data, out["is_noise"].ctypes.data,
                                                out["is_comfort_noise"].ctypes.data, *sel))
+        return out
+
+    # -- a meeting with a schedule, time-parallel (include/lyra_hip_spans_meeting.h) ----------------------------------------------
+    meeting_plan = staticmethod(meeting_plan)
+
+    def _meeting_frames(self, spans, stays, lane_ids, frames):
+        """the host arguments of the three calls below on buffers of `frames` frames, and the arrays they point into"""
+        sp, st = _meeting_args(spans, stays)
+        a, held = self._span_args(sp, lane_ids, frames)
+        return a, (st.ctypes.data if st.size else None, st.size), (held, st)
+
+    def meeting_spans_mix_dev(self, spans, stays, d_pcm16, d_mix, max_speakers=0, d_muted=None, d_is_comfort_noise=None,
+                              d_levels=None, d_is_speaker=None):
+        """The bridge's mix over a meeting with a schedule as one pass (lyra_hip_spans_meeting_mix_dev): participant p's k-th
+        present tick is frame spans[p].first_frame + k of d_pcm16 / d_mix int16 [frames][320]; stays (participant, room,
+        first_tick, n_ticks) say who is present where.  max_speakers, d_muted, d_is_comfort_noise, d_levels and d_is_speaker as
+        bridge_spans_mix_dev.  Frames outside the spans are untouched.  Completes on the encode-side stream."""
+        F = d_pcm16.shape[0]
+        a, s, _held = self._meeting_frames(spans, stays, (), F)
+        self._dev_call(self.L.lyra_hip_spans_meeting_mix_dev, a[0], a[1], s[0], s[1], self._p_pcm(d_pcm16, F),
+                       self._opt_dev_ptr(d_muted, "int32", (F,), "muted"),
+                       self._opt_dev_ptr(d_is_comfort_noise, "int32", (F,), "is_comfort_noise"), int(max_speakers),
+                       self._p_pcm(d_mix, F), self._opt_dev_ptr(d_levels, "int64", (F,), "levels"),
+                       self._opt_dev_ptr(d_is_speaker, "int32", (F,), "is_speaker"))
+
+    def meeting_spans_dev(self, spans, stays, d_packets, packet_bytes, num_bits, d_out_packets, d_out_packet_bytes, d_pcm16,
+                          d_mix, lane_ids=(), d_muted=None, dtx=None, flags=0, max_speakers=0, d_is_noise=None,
+                          d_is_comfort_noise=None, d_levels=None, d_is_speaker=None):
+        """A recorded meeting whose participants join, leave and move rooms, through the bridge in one call
+        (lyra_hip_spans_meeting_dev): bit for bit bridge_tick_dev (max_speakers 0) or speakers_tick_dev over the meeting's ticks
+        with the present participants as rows.  spans [P] (n_frames = present ticks), stays, lane_ids, packet_bytes / num_bits
+        int32 [frames] and dtx [P] or None stay host arrays; the device buffers are those of bridge_spans_dev."""
+        F = d_packets.shape[0]
+        a, s, _held = self._meeting_frames(spans, stays, lane_ids, F)
+        pb = self._span_packet_bytes(packet_bytes, F)
+        bits = self._span_packet_bytes(num_bits, F, "num_bits")
+        d = None if dtx is None else _np(np.asarray(dtx) != 0, np.int32, (a[1],))
+        call = MeetingSpansCall(a[0], a[1], a[2], a[3], s[0], s[1], self._p_packets(d_packets, F, MAX_PACKET_BYTES),
+                                pb.ctypes.data, self._opt_dev_ptr(d_muted, "int32", (F,), "muted"), int(flags), bits.ctypes.data,
+                                None if d is None else d.ctypes.data, self._p_packets(d_out_packets, F, MAX_PACKET_BYTES),
+                                self._p_packet_bytes(d_out_packet_bytes, F), self._p_pcm(d_pcm16, F), self._p_pcm(d_mix, F),
+                                *self._p_noise_flags(d_is_noise, d_is_comfort_noise, F), int(max_speakers),
+                                self._opt_dev_ptr(d_levels, "int64", (F,), "levels"),
+                                self._opt_dev_ptr(d_is_speaker, "int32", (F,), "is_speaker"))
+        self._dev_call(self.L.lyra_hip_spans_meeting_dev, C.addressof(call))
+
+    def meeting_spans(self, spans, stays, packets, packet_bytes, num_bits, lane_ids=(), muted=None, dtx=None, flags=0,
+                      max_speakers=0):
+        """meeting_spans_dev from host arrays (lyra_hip_spans_meeting); arguments and the returned dict of frame-indexed arrays
+        as bridge_spans, with stays in place of rooms; rows outside every span are 0."""
+        packets = _np(packets, np.uint8, (-1, MAX_PACKET_BYTES))
+        F = packets.shape[0]
+        a, s, _held = self._meeting_frames(spans, stays, lane_ids, F)
+        pb = self._span_packet_bytes(packet_bytes, F)
+        bits = self._span_packet_bytes(num_bits, F, "num_bits")
+        m = None if muted is None else self._span_packet_bytes(np.asarray(muted) != 0, F, "muted")
+        d = None if dtx is None else _np(np.asarray(dtx) != 0, np.int32, (a[1],))
+        out = {"out_packets": np.zeros((F, MAX_PACKET_BYTES), np.uint8), "out_packet_bytes": np.zeros(F, np.int32),
+               "pcm16": np.zeros((F, HOP), np.int16), "mix": np.zeros((F, HOP), np.int16),
+               "is_noise": np.zeros(F, np.int32), "is_comfort_noise": np.zeros(F, np.int32)}
+        if max_speakers:
+            out["levels"], out["is_speaker"] = np.zeros(F, np.int64), np.zeros(F, np.int32)
+        sel = [out[k].ctypes.data if k in out else None for k in ("levels", "is_speaker")]
+        self._chk(self.L.lyra_hip_spans_meeting(self.h, *a, s[0], s[1], packets.ctypes.data, pb.ctypes.data,
+                                                None if m is None else m.ctypes.data, int(flags), bits.ctypes.data,
+                                                None if d is None else d.ctypes.data, int(max_speakers),
+                                                out["out_packets"].ctypes.data, out["out_packet_bytes"].ctypes.data,
+                                                out["pcm16"].ctypes.data, out["mix"].ctypes.data, out["is_noise"].ctypes.data,
+                                                out["is_comfort_noise"].ctypes.data, *sel))
         return out
 
     def noise_receive_dev(self, d_ids, d_pcm, d_is_noise, side="decoder"):

@@ -243,6 +243,7 @@ struct lyra_hip_ctx {
   size_t twin_alt_out_cap = 0, twin_alt_ext_cap = 0;
   void* span_calls = nullptr;      // SpanCalls (spans_api.inc): plan rows and scratch of the time-parallel span calls, created on first use
   void* bsp = nullptr;             // BspState (bridge_spans_api.inc): index staging and scratch of the bridge over spans, created on first use
+  void* meet = nullptr;            // MeetState (meeting_api.inc): table staging and scratch of the meeting call, created on first use
   int tile_div[6] = {1, 1, 1, 1, 1, 1};   // tiles per workgroup of each stage kernel (LYRA_TILE_LOOP), see tile_div()
   bool chunk_local = false;                       // see wait_encode_side
   bool ids_stable = false;                        // inside lyra_hip_run_steps_dev, after its first step: see enc_cross_begin
@@ -415,6 +416,7 @@ void shr_free(lyra_hip_ctx* c);
 void blob_free(lyra_hip_ctx* c);
 void spans_free(lyra_hip_ctx* c);
 void bsp_free(lyra_hip_ctx* c);
+void meet_free(lyra_hip_ctx* c);
 // One owner per device buffer.  Buffers that are sized by one count (the frames of a call, the streams of the context) are
 // listed ONCE, as {slot, bytes per row, name}; free_bufs and alloc_bufs walk that list.  dfree is for the buffers with a size
 // of their own.  (A slot is the T* member seen as a void*, the hipMalloc((void**)&p) idiom of dalloc: it assumes that all
@@ -1281,6 +1283,7 @@ void lyra_hip_destroy(lyra_hip_ctx* c) {
   shr_free(c);
   spans_free(c);
   bsp_free(c);
+  meet_free(c);
   if (c->h_zc) (void)hipHostFree(c->h_zc);
   c->h_zc = nullptr;
   free_scratch(c);
@@ -2275,3 +2278,4 @@ long lyra_hip_debug_read(lyra_hip_ctx* c, int which, float* host_out, long capac
 #include "spans_rates_api.inc"
 #include "spans_packed_api.inc"
 #include "bridge_spans_api.inc"
+#include "meeting_api.inc"

@@ -11,6 +11,12 @@
 // BridgeRecordingTimeParallel (lyra_bridge_recording.h), one device call per stretch of constant membership, on
 // --lanes=L lent stream slots (default 64); it must write the same files again, with --max-speakers=N too (not with
 // --shared-encoders).
+// mode 3: the whole recording through BridgeMeetingTimeParallel: ONE device call whatever the membership does, --lanes as mode 2.
+// --present=<present.i32>: [ticks][num_streams] int32, 0 = the stream takes no part in that tick: it is no row of the tick,
+// nothing is decoded or encoded for it, and its outgoing row is zeros with length 0.  Mode 3 hands the file to
+// BridgeMeetingTimeParallel.  Modes 0 and 1 leave absent streams out of the tick's rows -- LyraConferenceBridge has every stream
+// as a row of every tick, so with --present they run the ticks through the C ABI's begin / end forms themselves (mode 1 two
+// deep) -- and must write the same files as mode 3.  Mode 2 and --shared-encoders take no --present.
 // --max-speakers=N: the same call through LyraSpeakerBridge (lyra_speaker_bridge.h), every room mixed from its N loudest
 // sources; every delivered tick's speaker flags [num_streams] int32 go to the file of --speakers-out.
 // --shared-encoders (with --max-speakers): the same call through LyraSharedBridge (lyra_shared_bridge.h), 1 + N encoders per
@@ -27,6 +33,8 @@
 #include <utility>
 #include <vector>
 
+#include "../../include/lyra_hip_bridge.h"
+#include "../../include/lyra_hip_speakers.h"
 #include "lyra_bridge_recording.h"
 #include "lyra_conference_bridge.h"
 #include "lyra_shared_bridge.h"
@@ -54,6 +62,78 @@ int Fail(const char* what) {
   return 1;
 }
 
+int BitrateBits(int bitrate) { return bitrate == 3200 ? 64 : bitrate == 6000 ? 120 : bitrate == 9200 ? 184 : -1; }
+
+// Modes 0 and 1 with --present: every tick's rows are the streams present on it, through lyra_hip_bridge_begin / _end or
+// lyra_hip_speakers_begin / _end (two ticks deep when `pipelined`); a tick with nobody present is no call.  Fills
+// out_rows [ticks][n][23], out_lens and flags [ticks][n]; what belongs to an absent stream stays zero.
+bool RunPresentTicks(const char* model_dir, const std::vector<BridgeStream>& streams, const std::vector<int32_t>& script,
+                     const std::vector<uint8_t>& packets, const std::vector<int32_t>& lengths, const std::vector<int32_t>& present,
+                     bool pipelined, bool skip_comfort_noise, int max_speakers, std::vector<uint8_t>* out_rows,
+                     std::vector<int32_t>* out_lens, std::vector<int32_t>* flags) {
+  const size_t n = streams.size(), ticks = lengths.size() / n;
+  out_rows->assign(ticks * n * kRow, 0);
+  out_lens->assign(ticks * n, 0);
+  flags->assign(ticks * n, 0);
+  lyra_hip_ctx* ctx = nullptr;
+  if (lyra_hip_create(model_dir, 0, static_cast<int>(n), LYRA_HIP_REQUANT_DEFAULT, &ctx) != 0) return false;
+  std::vector<std::vector<size_t>> in_flight;   // the rows (tick * n + stream) of the ticks begun and not yet ended, oldest first
+  bool ok = true;
+  auto end_oldest = [&]() {
+    const std::vector<size_t> rows = in_flight.front();
+    in_flight.erase(in_flight.begin());
+    const size_t B = rows.size();
+    std::vector<uint8_t> pk(B * kRow);
+    std::vector<int32_t> len(B), spk(B, 0);
+    const int rc = max_speakers ? lyra_hip_speakers_end(ctx, pk.data(), len.data(), nullptr, nullptr, nullptr, spk.data())
+                                : lyra_hip_bridge_end(ctx, pk.data(), len.data(), nullptr, nullptr);
+    if (rc != 0) return false;
+    for (size_t b = 0; b < B; ++b) {
+      std::memcpy(&(*out_rows)[rows[b] * kRow], &pk[b * kRow], kRow);
+      (*out_lens)[rows[b]] = len[b];
+      (*flags)[rows[b]] = spk[b];
+    }
+    return true;
+  };
+  for (size_t t = 0; ok && t < ticks; ++t) {
+    std::vector<size_t> rows;
+    for (size_t s = 0; s < n; ++s)
+      if (present[t * n + s] != 0) rows.push_back(t * n + s);
+    const size_t B = rows.size();
+    if (B == 0) continue;
+    std::vector<int32_t> ids(B), len(B), rooms(B), muted(B), bits(B), dtx(B);
+    std::vector<uint8_t> pk(B * kRow, 0);
+    for (size_t b = 0; ok && b < B; ++b) {
+      const size_t at = rows[b];
+      ids[b] = static_cast<int32_t>(at % n);
+      len[b] = lengths[at];
+      if (len[b] < 0 || len[b] > kRow) ok = false;
+      else std::memcpy(&pk[b * kRow], &packets[at * kRow], static_cast<size_t>(len[b]));
+      rooms[b] = script[at * 3];
+      muted[b] = script[at * 3 + 1] != 0;
+      bits[b] = BitrateBits(script[at * 3 + 2]);
+      dtx[b] = streams[at % n].enable_dtx ? 1 : 0;
+      if (bits[b] < 0) ok = false;
+    }
+    if (!ok) break;
+    const unsigned fl = skip_comfort_noise ? LYRA_HIP_SPEAKERS_SKIP_COMFORT_NOISE : 0u;
+    const int rc = max_speakers ? lyra_hip_speakers_begin(ctx, ids.data(), static_cast<int>(B), pk.data(), len.data(), rooms.data(),
+                                                          muted.data(), fl, bits.data(), dtx.data(), max_speakers)
+                                : lyra_hip_bridge_begin(ctx, ids.data(), static_cast<int>(B), pk.data(), len.data(), rooms.data(),
+                                                        muted.data(), fl, bits.data(), dtx.data());
+    if (rc != 0) {
+      ok = false;
+      break;
+    }
+    in_flight.push_back(rows);
+    if (in_flight.size() > (pipelined ? 1u : 0u)) ok = end_oldest();
+  }
+  while (ok && !in_flight.empty()) ok = end_oldest();
+  if (!ok) std::fprintf(stderr, "bridge_demo: %s\n", lyra_hip_last_error(ctx));
+  lyra_hip_destroy(ctx);
+  return ok;
+}
+
 }  // namespace
 
 int main(int argc_all, char** argv_all) {
@@ -61,6 +141,7 @@ int main(int argc_all, char** argv_all) {
   int max_speakers = 0;
   const char* speakers_path = nullptr;
   const char* slots_path = nullptr;
+  const char* present_path = nullptr;
   bool shared_encoders = false;
   int lanes = 64;
   std::vector<char*> positional;
@@ -70,6 +151,7 @@ int main(int argc_all, char** argv_all) {
     else if (std::strncmp(argv_all[i], "--slots-out=", 12) == 0) slots_path = argv_all[i] + 12;
     else if (std::strcmp(argv_all[i], "--shared-encoders") == 0) shared_encoders = true;
     else if (std::strncmp(argv_all[i], "--lanes=", 8) == 0) lanes = std::atoi(argv_all[i] + 8);
+    else if (std::strncmp(argv_all[i], "--present=", 10) == 0) present_path = argv_all[i] + 10;
     else positional.push_back(argv_all[i]);
   }
   const int argc = static_cast<int>(positional.size());
@@ -78,9 +160,9 @@ int main(int argc_all, char** argv_all) {
   if (argc != 10 || (select && (max_speakers == 0 || speakers_path == nullptr)) || (shared_encoders && !select) ||
       (slots_path && !shared_encoders)) {
     std::fprintf(stderr, "usage: bridge_demo <model_dir> <streams.txt> <script.i32> <packets_in.bin> <lengths_in.i32> "
-                         "<packets_out.bin> <lengths_out.i32> <mode 0|1|2> <skip_comfort_noise 0|1> "
+                         "<packets_out.bin> <lengths_out.i32> <mode 0|1|2|3> <skip_comfort_noise 0|1> "
                          "[--max-speakers=N --speakers-out=<speakers_out.i32> [--shared-encoders [--slots-out=<slots_out.i32>]]] "
-                         "[--lanes=L]\n");
+                         "[--lanes=L] [--present=<present.i32>]\n");
     return 2;
   }
   std::vector<BridgeStream> streams;
@@ -98,6 +180,39 @@ int main(int argc_all, char** argv_all) {
   if (lengths.size() != ticks * n || script.size() != ticks * n * 3 || packets.size() != ticks * n * kRow)
     return Fail("the input files disagree about ticks and streams");
   const int mode = std::atoi(argv[8]);
+  std::vector<int32_t> present;
+  if (present_path) {
+    if (mode == 2 || shared_encoders) return Fail("--present goes with modes 0, 1 and 3, without shared encoders");
+    if (!ReadFile(present_path, &present) || present.size() != ticks * n) return Fail("the presence file disagrees about ticks and streams");
+  }
+  auto write_all = [&](const std::vector<uint8_t>& rows_out, const std::vector<int32_t>& lens_out, const std::vector<int32_t>& flags) {
+    std::ofstream out_pk(argv[6], std::ios::binary), out_len(argv[7], std::ios::binary);
+    out_pk.write(reinterpret_cast<const char*>(rows_out.data()), static_cast<std::streamsize>(rows_out.size()));
+    out_len.write(reinterpret_cast<const char*>(lens_out.data()), static_cast<std::streamsize>(lens_out.size() * sizeof(int32_t)));
+    if (speakers_path) {
+      std::ofstream out_spk(speakers_path, std::ios::binary);
+      out_spk.write(reinterpret_cast<const char*>(flags.data()), static_cast<std::streamsize>(flags.size() * sizeof(int32_t)));
+    }
+  };
+  if (mode == 3) {   // the meeting as a whole, schedule and all
+    if (shared_encoders) return Fail("mode 3 has no shared encoders");
+    std::vector<int32_t> flags;
+    auto got = BridgeMeetingTimeParallel(absl::MakeConstSpan(streams), argv[1], absl::MakeConstSpan(packets),
+                                         absl::MakeConstSpan(lengths), absl::MakeConstSpan(script), absl::MakeConstSpan(present),
+                                         std::atoi(argv[9]) != 0, max_speakers, lanes, 0, &flags);
+    if (!got) return Fail("BridgeMeetingTimeParallel failed");
+    write_all(got->first, got->second, flags);
+    return 0;
+  }
+  if (present_path) {   // modes 0 and 1 with absent streams left out of the rows
+    std::vector<uint8_t> rows_out;
+    std::vector<int32_t> lens_out, flags;
+    if (!RunPresentTicks(argv[1], streams, script, packets, lengths, present, mode != 0, std::atoi(argv[9]) != 0, max_speakers,
+                         &rows_out, &lens_out, &flags))
+      return Fail("a tick failed");
+    write_all(rows_out, lens_out, flags);
+    return 0;
+  }
   if (mode == 2) {   // the recording as a whole
     if (shared_encoders) return Fail("mode 2 has no shared encoders");
     std::vector<int32_t> flags;

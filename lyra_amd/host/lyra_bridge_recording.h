@@ -50,6 +50,49 @@ std::optional<std::pair<std::vector<uint8_t>, std::vector<int32_t>>> BridgeRecor
     absl::Span<const int32_t> lengths, absl::Span<const int32_t> script, bool skip_comfort_noise, int max_speakers,
     int num_lanes, int device = 0, std::vector<int32_t>* is_speaker = nullptr);
 
+// The first tick of every call BridgeMeetingTimeParallel makes, in order: tick 0, and every tick in front of which the entries
+// of the schedule so far (one per present stream and stretch of constant membership and presence; the C ABI's
+// LYRA_HIP_MEETING_MAX_ENTRIES) would exceed max_entries.  present: [ticks][num_streams], or null: everyone always.  Empty for
+// ticks == 0.  Host only.
+inline std::vector<int64_t> BridgeMeetingCallStarts(const int32_t* script, const int32_t* present, int64_t ticks, int num_streams,
+                                                    int64_t max_entries) {
+  std::vector<int64_t> starts;
+  const size_t n = static_cast<size_t>(num_streams);
+  auto where = [&](int64_t t, size_t s) -> int64_t {   // -2: absent, -1: in no room, else the room
+    const size_t at = static_cast<size_t>(t) * n + s;
+    if (present != nullptr && present[at] == 0) return -2;
+    return script[at * kBridgeScriptFields] < 0 ? -1 : script[at * kBridgeScriptFields];
+  };
+  int64_t entries = 0;
+  for (int64_t t = 0; t < ticks; ++t) {
+    bool change = t == 0;
+    int64_t here = 0;
+    for (size_t s = 0; s < n; ++s) {
+      change = change || where(t, s) != where(t - 1, s);
+      here += where(t, s) != -2;
+    }
+    if (!change) continue;
+    if (t == 0 || entries + here > max_entries) {
+      starts.push_back(t);
+      entries = 0;
+    }
+    entries += here;
+  }
+  return starts;
+}
+
+// The same recording with a SCHEDULE (include/lyra_hip_spans_meeting.h): present [ticks][num_streams] says on which ticks a
+// stream takes part (empty: everyone always); on the others it is no row of the tick -- nothing is decoded or encoded for it,
+// its state does not advance, and its outgoing row is zeros with length 0.  Rooms may change from tick to tick as before.
+// Spans and stays are derived from the script's room column and `present`, every stream's packets, lengths, mutes and
+// bitrates are compacted to its present ticks, and the whole meeting is ONE device call (more only where the schedule has more
+// than LYRA_HIP_MEETING_MAX_ENTRIES entries: BridgeMeetingCallStarts).  Byte for byte what the tick bridges give when absent
+// streams are left out of a tick's rows.  nullopt as BridgeRecordingTimeParallel, and for a `present` of another size.
+std::optional<std::pair<std::vector<uint8_t>, std::vector<int32_t>>> BridgeMeetingTimeParallel(
+    absl::Span<const BridgeStream> streams, const ghc::filesystem::path& model_path, absl::Span<const uint8_t> packets,
+    absl::Span<const int32_t> lengths, absl::Span<const int32_t> script, absl::Span<const int32_t> present,
+    bool skip_comfort_noise, int max_speakers, int num_lanes, int device = 0, std::vector<int32_t>* is_speaker = nullptr);
+
 }  // namespace codec
 }  // namespace chromemedia
 #endif

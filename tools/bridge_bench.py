@@ -43,8 +43,19 @@ Gilbert loss, DTX on every other row, of 9,000 ticks (3 minutes) and 180,000 tic
 "equal": outgoing packets and sizes of both forms bit for bit over the ticks the tick form ran.  "pass": the mix pass alone
 (lyra_hip_spans_bridge_mix_dev on the meeting's decoded hops), device events around it on the encode-side stream, and its share
 of the call.  No threshold is fixed in advance: "verdict" says faster, SLOWER or inside the spreads as the other legs do.
+--recording --churn TICKS runs the meeting WITH A SCHEDULE instead (include/lyra_hip_spans_meeting.h): 3 minutes (9,000 ticks) of
+32 participants in 4 rooms on 4,096 lanes, 10 % Gilbert loss, DTX on every other row, and on average one membership event in
+TICKS ticks (a participant leaves, comes back or moves rooms).  In one process, alternating, median of --reps with min..max:
+  "meeting_dev":           ONE lyra_hip_spans_meeting_dev call;
+  "cut_spans_bridge_dev":  the same meeting as consecutive lyra_hip_spans_bridge_dev calls cut at every event, the method without
+                           a schedule -- where absent participants are rows in no room, decoded and encoded on every tick,
+                           because that is all that call can express;
+  "tick_dev_present_rows": the tick form with the present participants as rows.
+The first and the last must give the same outgoing packets and sizes bit for bit: asserted.  "pass": the schedule-driven mix pass
+alone, device events around it; "epochs" / "entries": the planner's counts.  A second line, "meeting_constant", is the
+like-for-like row: nobody comes or goes, the meeting call against one lyra_hip_spans_bridge_dev call in the same run.
     python tools/bridge_bench.py [--streams 4096] [--hops 200] [--reps 5] [--max-speakers N [--shared] [--layout L]]
-                                 [--recording [--max-speakers N] [--lanes 4096]] [--out profiles/bridge.jsonl]"""
+                                 [--recording [--max-speakers N] [--lanes 4096] [--churn TICKS]] [--out profiles/bridge.jsonl]"""
 import argparse
 import json
 import os
@@ -211,6 +222,199 @@ def recording(a):
             f.write(json.dumps(line) + "\n")
 
 
+def draw_churn(rng, P, T, n_rooms, every):
+    """a meeting of T ticks whose membership changes on average once in `every` ticks (0: never): a drawn participant leaves,
+    comes back (where it is away) or moves to another room -> (present bool [T][P], room int32 [T][P], events)"""
+    present, room = np.ones((T, P), bool), np.tile((np.arange(P) % n_rooms).astype(np.int32), (T, 1))
+    at = np.sort(rng.choice(np.arange(1, T), T // every, replace=False)) if every else []
+    for t in at:
+        p = int(rng.integers(0, P))
+        if not present[t, p]:
+            present[t:, p] = True
+        elif rng.random() < 0.5:
+            present[t:, p] = False
+        else:
+            room[t:, p] = (room[t, p] + 1 + rng.integers(0, n_rooms - 1)) % n_rooms
+    return present, room, len(at)
+
+
+def stays_of(present, room):
+    """(present, room) tables -> (stays sorted by (participant, first_tick), present ticks per participant)"""
+    T, P = present.shape
+    stays = []
+    for p in range(P):
+        key = np.where(present[:, p], room[:, p], -2)
+        cuts = np.flatnonzero(np.diff(key)) + 1
+        for lo, hi in zip(np.concatenate([[0], cuts]), np.concatenate([cuts, [T]])):
+            if key[lo] != -2:
+                stays.append((p, int(key[lo]), int(lo), int(hi - lo)))
+    return stays, present.sum(axis=0)
+
+
+def churn(a):
+    """the --recording --churn leg (see the module's docstring)"""
+    import torch
+    import lyra_amd
+    from lossy_steps_bench import gilbert, speech_ring
+    P, T, n_rooms, ring, N, dev = 32, 9000, 4, 50, a.max_speakers, torch.device("cuda", 0)
+    rng = np.random.default_rng(5)
+    t_ = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
+    ids = np.arange(P, dtype=np.int32)
+    lanes = np.arange(P, P + a.lanes, dtype=np.int32)
+    dtx = (np.arange(P) % 2).astype(np.int32)
+    speech = speech_ring(ring, P, rng)
+    prep = lyra_amd.LyraHip(device=0, max_streams=P)
+    pk = np.zeros((ring, P, 23), np.uint8)
+    d15 = torch.zeros((P, 15), dtype=torch.uint8, device=dev)
+    for t in range(ring):
+        prep.encode_dev(t_(ids), t_(speech[t]), 120, d15)
+        prep.synchronize()
+        pk[t, :, :15] = d15.cpu().numpy()
+    prep.close()
+    nb = gilbert(rng, T, P, 0.10).astype(np.int32) * 15              # [T][P] by meeting tick
+    pk_all = pk[np.arange(T) % ring]                                 # [T][P][23]
+    lines = []
+    for every in (a.churn, 0):                                       # the churny meeting, then the like-for-like row
+        present, room, n_events = draw_churn(rng, P, T, n_rooms, every)
+        stays, n_present = stays_of(present, room)
+        first = np.concatenate([[0], np.cumsum(n_present)[:-1]]).astype(np.int64)
+        spans = [(int(p), int(first[p]), int(n_present[p])) for p in range(P)]
+        F = int(n_present.sum())
+        frame_of = np.full((T, P), -1, np.int64)                     # the meeting call's frame of (tick, participant)
+        for p in range(P):
+            frame_of[present[:, p], p] = first[p] + np.arange(n_present[p])
+        here = frame_of >= 0
+        pk_f, nb_f = np.zeros((F, 23), np.uint8), np.zeros(F, np.int32)
+        pk_f[frame_of[here]], nb_f[frame_of[here]] = pk_all[here], nb[here]
+        bits_f = np.full(F, 120, np.int32)
+        plan = lyra_amd.codec.meeting_plan(spans, stays)
+        # (b) the parent's method: everybody a row of every tick (absent: in no room), one call per stretch between events
+        key = np.where(present, room, -1)
+        cuts = [0] + [t for t in range(1, T) if (key[t] != key[t - 1]).any()] + [T]
+        Fb = P * T
+        spans_b = [(int(p), int(p) * T, T) for p in range(P)]
+        pk_b = np.ascontiguousarray(pk_all.transpose(1, 0, 2)).reshape(Fb, 23)
+        nb_b, bits_b = np.ascontiguousarray(nb.T).reshape(Fb), np.full(Fb, 120, np.int32)
+        # (c) the ticks with the present rows only: per stretch of constant membership the rows, their index and their inputs
+        stretches = []
+        for lo, hi in zip(cuts[:-1], cuts[1:]):
+            rows = np.flatnonzero(present[lo])
+            if not rows.size:
+                continue
+            order, start = lyra_amd.codec.bridge_plan(room[lo, rows])
+            stretches.append(dict(lo=lo, n=hi - lo, rows=rows, ids=t_(ids[rows]), order=t_(order), start=t_(start), dtx=t_(dtx[rows]),
+                                  bits=t_(np.full(rows.size, 120, np.int32)), pk=t_(pk_all[lo:hi][:, rows]), nb=t_(nb[lo:hi][:, rows]),
+                                  out=torch.zeros((hi - lo, rows.size, 23), dtype=torch.uint8, device=dev),
+                                  len=torch.zeros((hi - lo, rows.size), dtype=torch.int32, device=dev),
+                                  frames=t_(frame_of[lo:hi][:, rows])))
+        ca, cb, cc = (lyra_amd.LyraHip(device=0, max_streams=P + a.lanes) for _ in range(3))
+        try:
+            ca.torch_order = cb.torch_order = cc.torch_order = False
+            out_a, len_a = torch.zeros((F, 23), dtype=torch.uint8, device=dev), torch.zeros(F, dtype=torch.int32, device=dev)
+            x_a, mix_a = (torch.zeros((F, 320), dtype=torch.int16, device=dev) for _ in range(2))
+            out_b, len_b = torch.zeros((Fb, 23), dtype=torch.uint8, device=dev), torch.zeros(Fb, dtype=torch.int32, device=dev)
+            x_b, mix_b = (torch.zeros((Fb, 320), dtype=torch.int16, device=dev) for _ in range(2))
+            d_pk_a, d_pk_b = t_(pk_f), t_(pk_b)
+            torch.cuda.synchronize()
+
+            def form_a():
+                ca.meeting_spans_dev(spans, stays, d_pk_a, nb_f, bits_f, out_a, len_a, x_a, mix_a, lane_ids=lanes, dtx=dtx, max_speakers=N)
+
+            def form_b(n=None):
+                for lo, hi in list(zip(cuts[:-1], cuts[1:]))[:n]:
+                    part = [(i, f0 + lo, hi - lo) for (i, f0, _) in spans_b]
+                    cb.bridge_spans_dev(part, key[lo], d_pk_b, nb_b, bits_b, out_b, len_b, x_b, mix_b, lane_ids=lanes, dtx=dtx,
+                                        max_speakers=N)
+
+            def form_c(n=None):
+                for s in stretches[:n]:
+                    for t in range(s["n"]):
+                        args = (s["ids"], s["pk"][t], s["nb"][t], s["order"], s["start"], s["bits"], s["out"][t], s["len"][t])
+                        if N:
+                            cc.speakers_tick_dev(*args, N, None, s["dtx"])
+                        else:
+                            cc.bridge_tick_dev(*args, None, s["dtx"])
+
+            def clocked(ctx, run):
+                ctx.reset()
+                ctx.synchronize()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                run()
+                ctx.synchronize()
+                torch.cuda.synchronize()
+                return time.perf_counter() - t0
+
+            clocked(ca, form_a)                                          # warm-up of the three forms, not counted
+            clocked(cb, lambda: form_b(4))
+            clocked(cc, lambda: form_c(2))
+            times = {"a": [], "b": [], "c": []}
+            for _ in range(a.reps):                                      # alternating, in one process
+                times["a"].append(clocked(ca, form_a))
+                times["b"].append(clocked(cb, form_b))
+                if every:
+                    times["c"].append(clocked(cc, form_c))
+            if every:                                                    # (a) and (c): the same outgoing packets and sizes
+                for s in stretches:
+                    f = s["frames"].reshape(-1)
+                    assert torch.equal(len_a[f], s["len"].reshape(-1)) and torch.equal(out_a[f], s["out"].reshape(-1, 23)), \
+                        f"the meeting call and the ticks differ in the stretch from tick {s['lo']}"
+            # (b) agrees with (a) where a participant is present and in the same company: not asserted, absent rows differ by design
+            how = "device events around one lyra_hip_spans_meeting_mix_dev call"
+            try:
+                st = torch.cuda.ExternalStream(ca.stream_handle(), device=dev)
+            except Exception:
+                st, how = None, "host clock around one lyra_hip_spans_meeting_mix_dev call and a synchronise"
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            per = []
+            for rep in range(a.reps + 1):
+                ca.synchronize()
+                t0 = time.perf_counter()
+                if st is not None:
+                    e0.record(st)
+                ca.meeting_spans_mix_dev(spans, stays, x_a, mix_a, N)
+                if st is not None:
+                    e1.record(st)
+                ca.synchronize()
+                if rep:
+                    per.append(e0.elapsed_time(e1) if st is not None else (time.perf_counter() - t0) * 1e3)
+            per.sort()
+
+            def summary(ts):
+                ts = sorted(ts)
+                return {"seconds_median": round(ts[len(ts) // 2], 4), "min": round(ts[0], 4), "max": round(ts[-1], 4),
+                        "times_real_time": round(T * 0.02 / ts[len(ts) // 2], 1)}
+
+            def verdict(x, y):
+                return "faster" if max(x) < min(y) else "SLOWER" if min(x) > max(y) else "inside the spreads"
+
+            line = {"bench": "bridge", "case": "meeting_churn" if every else "meeting_constant", "participants": P, "rooms": n_rooms,
+                    "ticks": T, "lanes": int(a.lanes), "max_speakers": N, "loss": 0.10, "reps": a.reps, "churn_ticks": every,
+                    "events": n_events, "epochs": int(len(plan["epoch_tick"]) - 1), "entries": int(len(plan["entry_participant"])),
+                    "present_frames": F, "meeting_dev": summary(times["a"]),
+                    "cut_spans_bridge_dev": dict(summary(times["b"]), calls=len(cuts) - 1, frames=Fb,
+                                                 note="the parent's method: absent participants are rows in no room, decoded and "
+                                                      "encoded on every tick" if every else "one call, constant membership"),
+                    "meeting_dev_vs_cut_calls": verdict(times["a"], times["b"]),
+                    "pass": {"ms_median": round(per[len(per) // 2], 3), "min": round(per[0], 3), "max": round(per[-1], 3), "what": how},
+                    "errors": {"bridge": int(ca.bridge_errors()), "lossy": int(ca.decode_lossy_errors()),
+                               "mixed": int(ca.encode_mixed_errors())}}
+            if every:
+                line["tick_dev_present_rows"] = summary(times["c"])
+                line["meeting_dev_vs_ticks"] = verdict(times["a"], times["c"])
+                line["equal"] = True
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+        finally:
+            ca.close()
+            cb.close()
+            cc.close()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "a") as f:
+        for line in lines:
+            f.write(json.dumps(line) + "\n")
+
+
 def main():
     import torch
     import lyra_amd
@@ -227,12 +431,14 @@ def main():
                     help="with --max-speakers: this layout only (a process of its own per layout)")
     ap.add_argument("--recording", action="store_true", help="the recorded-meeting leg: one time-parallel call against the ticks")
     ap.add_argument("--lanes", type=int, default=4096, help="with --recording: stream slots lent to the call")
+    ap.add_argument("--churn", type=int, default=0, help="with --recording: the meeting with a schedule, one membership event in "
+                                                         "this many ticks on average")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bridge.jsonl"))
     a = ap.parse_args()
     if a.recording:
         if a.shared:
             raise SystemExit("--recording has no shared-encoder form")
-        return recording(a)
+        return churn(a) if a.churn else recording(a)
     B, dev, ring = a.streams, torch.device("cuda", 0), 50
     rng = np.random.default_rng(3)
     t_ = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)   # noqa: E731
